@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- markers/sec through the calculate_a_and_vara genome scan + MM^T build wall-clock on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run, one rank per GPU)
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]   (N > 1: launched by torch.distributed.run, one rank per GPU)
 
 Workload (BASELINE.json north_star / configs[2], the configuration the metric is quoted on): synthetic
 10,000 individuals x 1,000,000 biallelic SNPs, single trait.  STRONG scaling: the 1,000,000 markers are split into N
@@ -12,9 +12,12 @@ the a-posteriori certification of the digit-slice kernel, followed by find_qtl's
 over the rank's shard; for N > 1 the n^3 product W = S V S is shared by rows (one all-gather) and the shards'
 (max tsq, first index) pairs are all-gathered inside the step.  value = 1,000,000 markers / max-over-ranks step time.
 The MM^T build (calculateMMt_rcpp.cpp:95; exact int32 partial SYRK per rank + one RCCL sum + finish) is timed separately
-and reported as mmt_build_s.  Secondary entries (N = 1): BASELINE configs[1] (5,000 x 500,000), the fp64-mode scan and
-the 7-digit scan of the headline shape.  The CPU baseline is the C oracle (a port of the reference's in-memory branch) on
-a bounded marker sample on rank 0's host cores.
+and reported as mmt_build_s.  A plain run does only that: set up, warm up, time the K steps, print one JSON line.
+--full then measures what the headline does not need: the stand-alone genotype pass, the secondary entries (N = 1: BASELINE
+configs[1] (5,000 x 500,000), the fp64-mode scan, the 7-digit scan of the headline shape and the other A/Bs), the CPU baseline
+-- the C oracle (a port of the reference's in-memory branch) on a bounded marker sample on rank 0's host cores -- and the
+parity gate of the timed step against it.  --dump-outputs DIR writes a, vara, the selected marker and tsqmax of the last timed
+step (dump_outputs).
 """
 import argparse
 import hashlib
@@ -107,6 +110,21 @@ class Run:
         t = self.torch.tensor([x], dtype=self.torch.float64, device=None if self.backend == "gloo" else self.dev)
         self.dist.all_reduce(t, op=self.dist.ReduceOp.MAX)
         return float(t.item())
+
+    def gather_markers(self, x):
+        """This rank's per-marker results (device vector of its shard) -> the whole marker range in marker order, on the host of
+        every rank.  Shards differ in length by at most one marker: each travels padded to the longest."""
+        if self.world == 1:
+            return x.cpu().numpy()
+        from eagleeverything_amd.sharded import shard_range
+        sizes = [m1 - m0 for m0, m1 in (shard_range(self.Ltot, r, self.world) for r in range(self.world))]
+        buf = self.torch.zeros(max(sizes), dtype=x.dtype, device=x.device)
+        buf[:x.numel()] = x
+        if self.backend == "gloo":
+            buf = buf.cpu()
+        parts = [self.torch.empty_like(buf) for _ in sizes]
+        self.dist.all_gather(parts, buf)
+        return np.concatenate([p[:s].cpu().numpy() for p, s in zip(parts, sizes)])
 
     # ---- MM^T build: partial SYRK per shard + one sum to rank 0 + finish ----------------------------
     def mmt_build(self, reps):
@@ -248,6 +266,30 @@ class Run:
         elapsed = self.max_over_ranks(time.perf_counter() - t3)
         parts = {k: float(np.mean([e[k][0].elapsed_time(e[k][1]) for e in evs])) / 1e3 for k in names}
         return sel, elapsed, parts
+
+
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, a, vara, selected_marker, tsqmax, cap=DUMP_CAP_BYTES):
+    """--dump-outputs: what the last timed step hands its caller, as out_dir/<name>.npy in float64 -- a and vara per marker, the
+    selected marker (1-based, 0 = none: find_qtl.R's pick) and its tsq -- so that two builds can be compared output for output.
+    When a and vara together exceed `cap` bytes, a fixed seeded sample of markers is written instead, with its 0-based marker
+    indices in marker_index.npy.  Returns the names written."""
+    a = np.asarray(a, dtype=np.float64).ravel()
+    vara = np.asarray(vara, dtype=np.float64).ravel()
+    out = {}
+    if a.nbytes + vara.nbytes > cap - 4096:   # (headroom for the .npy headers and the two scalars)
+        k = (cap - 4096) // 24                # a, vara and the index: 24 bytes per sampled marker
+        idx = np.sort(np.random.default_rng(0).choice(a.size, size=k, replace=False))
+        a, vara = a[idx], vara[idx]
+        out["marker_index"] = idx.astype(np.float64)
+    out.update({"a": a, "vara": vara, "selected_marker": np.array([selected_marker], dtype=np.float64),
+                "tsqmax": np.array([tsqmax], dtype=np.float64)})
+    os.makedirs(out_dir, exist_ok=True)
+    for name, x in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), x)
+    return sorted(out)
 
 
 def vara_roofline(sh, kern_s, S_used):
@@ -470,7 +512,9 @@ def main_abi(args):
         t_ops = time.time() - t1
         geno_scan = {"asciifileMt": geno["asciifileMt"]}
         leg, _ = abi_leg(args, torch, geno_scan, n, L, S_h, V_h, a_h, device, args.steps, args.warmup)
-        leg.pop("results")
+        a_r, v_r = leg.pop("results")
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, a_r, v_r, leg["selected_marker"], leg["tsqmax"])
         ph = leg["phases_per_device"][0]
         info = rcpp_api.device_info(device)
         np_ = (n + 255) // 256 * 256
@@ -529,9 +573,14 @@ def parse_args(argv=None):
     ap.add_argument("--mode", choices=["f64", "i8"], default=os.environ.get("EAGLE_SCAN_MODE", "i8"))
     ap.add_argument("--slices", type=int, default=0, help="int8 digit slices of W in i8 mode (0 = chosen from the error bound)")
     ap.add_argument("--mmt-reps", type=int, default=2)
-    ap.add_argument("--cpu-sample", type=int, default=32768, help="markers in the CPU-baseline sample (0 = skip)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary entries (C2, fp64 mode, 7 digits)")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the reference-shaped (host files -> host results) secondary leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run what it does not need: the stand-alone genotype pass, the secondary entries, "
+                         "the CPU baseline and the parity gate (off: set up, warm up, time the steps, print the line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned (a, vara, selected marker, tsqmax) as DIR/<name>.npy in float64")
+    ap.add_argument("--cpu-sample", type=int, default=32768, help="with --full: markers in the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary entries (C2, fp64 mode, 7 digits)")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the reference-shaped (host files -> host results) secondary leg")
     ap.add_argument("--simple-operands", action="store_true", help="seeded random SPD S / V instead of the model algebra")
     ap.add_argument("--save-operands", default=None, help="write S, V, a_hat (torch.save) after computing them")
     ap.add_argument("--load-operands", default=None, help="read S, V, a_hat written by --save-operands (used by the PMC passes of\n                    tools/profile_gpu.sh: rocSOLVER's eigh crashes under rocprofv3 counter collection)")
@@ -593,6 +642,9 @@ def main():
     if args.gpus < 1:
         print("bench.py: --gpus must be >= 1", file=sys.stderr)
         sys.exit(2)
+    if args.steps < 1 or args.warmup < 0:
+        print("bench.py: --steps must be >= 1 and --warmup >= 0", file=sys.stderr)
+        sys.exit(2)
     if args.form == "abi":
         sys.exit(main_abi(args))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -650,19 +702,27 @@ def main():
     value = Ltot * args.steps / elapsed
     kern_s = parts["kern"]
     cert = sh.certificate() if sh.mode == 1 else None
+    if args.dump_outputs:
+        a_all, vara_all = run.gather_markers(a_step), run.gather_markers(vara_step)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, a_all, vara_all, sel[0], sel[1])
+        del a_all, vara_all
 
     if world > 1:
         del a_step, vara_step
-    # the HBM-bound kernel of the scan on its own (a = Mt v: L*n genotype bytes, read once), outside the timed steps
-    gp = []
-    for _ in range(4):
-        g0, g1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        g0.record()
-        sh.gemv_a()
-        g1.record()
-        torch.cuda.synchronize(dev)
-        gp.append(g0.elapsed_time(g1))
-    gpass_s = float(np.median(gp[1:])) / 1e3
+    # everything below `if args.full` is measured after the headline and is not needed for it
+    gpass_s = None
+    if args.full:
+        # the HBM-bound kernel of the scan on its own (a = Mt v: L*n genotype bytes, read once), outside the timed steps
+        gp = []
+        for _ in range(4):
+            g0, g1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            g0.record()
+            sh.gemv_a()
+            g1.record()
+            torch.cuda.synchronize(dev)
+            gp.append(g0.elapsed_time(g1))
+        gpass_s = float(np.median(gp[1:])) / 1e3
 
     # ---- roofline of the dominant kernel (vara) ---------------------------------------------------
     np_, Lp, Lloc = sh.np_, sh.Lp, sh.Lloc
@@ -723,14 +783,15 @@ def main():
                       "achieved": w_flops / parts["w"] / 1e12, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
                       "frac": w_flops / parts["w"] / 1e12 / FP64_MFMA_PEAK_TFLOPS, "ms": parts["w"] * 1e3,
                       "note": "includes v = S a_hat, the symmetry check, the fold and (N > 1) the all-gather of W's rows"},
-        "genotype_pass": {"bound": "hbm", "kernel": "k_slice_vec + k_gemv_mfma (a = Mt v; algorithmic bytes = L_pad*n_pad genotype bytes)",
-                          "achieved": Lp * np_ / gpass_s / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                          "frac": Lp * np_ / gpass_s / 1e9 / HBM_PEAK_GBS, "kernel_ms": gpass_s * 1e3},
         "syrk_f4": {"bound": "mfma", "kernel": "k_syrk_f4w (v_mfma_scale_f32_32x32x64_f8f6f4, fp4 x fp4, exact; 384 x 256 tiles)", "dtype": "fp4",
                     "achieved": (np_ * (np_ + 256.0)) * Lp / syrk_s / 1e12, "peak": FP4_MFMA_PEAK_TOPS,
                     "unit": "TFLOP/s", "frac": (np_ * (np_ + 256.0)) * Lp / syrk_s / 1e12 / FP4_MFMA_PEAK_TOPS,
                     "kernel_ms": syrk_s * 1e3},
     }
+    if gpass_s is not None:
+        secondary["genotype_pass"] = {"bound": "hbm", "kernel": "k_slice_vec + k_gemv_mfma (a = Mt v; algorithmic bytes = L_pad*n_pad genotype bytes)",
+                                      "achieved": Lp * np_ / gpass_s / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                      "frac": Lp * np_ / gpass_s / 1e9 / HBM_PEAK_GBS, "kernel_ms": gpass_s * 1e3}
     if w_choice:
         secondary["w_sharing_preflight_s"] = w_choice
 
@@ -740,7 +801,7 @@ def main():
     parity = None
     cpu_in = None
     all_marker_parity = None
-    if rank == 0 and world == 1 and args.cpu_sample > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_sample > 0:
         ns = min(args.cpu_sample, Lloc)
         nm = min(8192, Lloc)
         cpu_in = {"ns": ns, "Mt_s": sh.Mt8[:ns, :n].cpu().numpy(), "Sh": run.S.cpu().numpy(), "Vh": run.V.cpu().numpy(), "ah": run.ahat.cpu().numpy(),
@@ -748,7 +809,7 @@ def main():
                   "M_s": np.ascontiguousarray(sh.Mt8[:nm, :n].cpu().numpy().T), "nm": nm}
 
     # ---- secondary entries (N = 1): fp64-mode and 7-digit scans of the headline shape, and BASELINE configs[1] --------
-    if world == 1 and not args.no_secondary and sh.mode == 1:
+    if args.full and world == 1 and not args.no_secondary and sh.mode == 1:
         sel_i8 = sel
         sh.mode = 0
         s64, el64, p64 = run.timed(1, 1)
@@ -912,7 +973,7 @@ def main():
                 os.unlink(os.path.join(tmpd, f))
             os.rmdir(tmpd)
             rcpp_api.drop_cache(local_rank)
-    if world == 1 and not args.no_secondary and sh.mode == 1 and not args.load_operands:
+    if args.full and world == 1 and not args.no_secondary and sh.mode == 1 and not args.load_operands:
         # BASELINE configs[1]: 5,000 x 500,000 on one card (its operands come from an eigen-decomposition: not under --load-operands)
         del run, sh
         torch.cuda.empty_cache()

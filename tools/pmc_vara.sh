@@ -4,7 +4,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/pmc_vara
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="$ROOT/bench.py --cpu-sample 0 --steps 2 --warmup 1 --simple-operands --mode i8 $@"
+ARGS="$ROOT/bench.py --full --cpu-sample 0 --steps 2 --warmup 1 --simple-operands --mode i8 $@"
 rocprofv3 --kernel-include-regex "k_vara_i8" --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum --output-format csv -d $OUT/tcc -o pmc -- python3 $ARGS > $OUT/tcc.log 2>&1 || tail -5 $OUT/tcc.log
 rocprofv3 --kernel-include-regex "k_vara_i8" --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -o pmc -- python3 $ARGS > $OUT/fetch.log 2>&1 || tail -5 $OUT/fetch.log
 cd $ROOT

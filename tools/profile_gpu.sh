@@ -14,11 +14,11 @@ OPS=/tmp/eagle_bench_operands.pt
 # SECONDARY=1: the stats pass and the FETCH_SIZE / SQ / GRBM passes also run bench.py's secondary entries (fp64-mode scan, spectral
 # scan, Z builds), so that k_vara_f64, k_spectral_scan and k_zbuild_i8 appear in the summary
 if [ -n "$SECONDARY" ]; then NOSEC="--no-e2e"; else NOSEC="--no-secondary"; fi
-ARGS="$ROOT/bench.py --cpu-sample 0 $NOSEC --steps 3 --warmup 1 --load-operands $OPS $@"
+ARGS="$ROOT/bench.py --full --cpu-sample 0 $NOSEC --steps 3 --warmup 1 --load-operands $OPS $@"
 KF="--kernel-include-regex k_vara_i8|k_vara_f64|k_syrk_f4|k_gemm_f64|k_gemv|k_mmt_finish|k_slice_w|k_pack_fp4|k_transpose_pack_fp4|k_cert|k_spectral|k_zbuild|k_gram_rowabs|k_gram_hi|k_last_digit|k_w8_"
 echo "== stats pass";
 # the stats pass profiles the bench command itself (model-algebra operands; the CPU sample and the secondary entries are skipped)
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o stats -- python3 $ROOT/bench.py --cpu-sample 0 $NOSEC --save-operands $OPS "$@" > $OUT/stats.log 2>&1 || { tail -5 $OUT/stats.log; exit 1; }
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o stats -- python3 $ROOT/bench.py --full --cpu-sample 0 $NOSEC --save-operands $OPS "$@" > $OUT/stats.log 2>&1 || { tail -5 $OUT/stats.log; exit 1; }
 echo "== pmc FETCH_SIZE"
 rocprofv3 $KF --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o pmc -- python3 $ARGS > $OUT/pmc_fetch.log 2>&1 || { tail -5 $OUT/pmc_fetch.log; exit 1; }
 echo "== pmc WRITE_SIZE"
