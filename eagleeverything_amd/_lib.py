@@ -41,6 +41,10 @@ SIGNATURES = {
     "eagle_last_w_info": (C.c_int, [C.c_void_p, C.c_void_p]),
     "eagle_last_scan_digits": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     "eagle_get_row_column": (C.c_int, [C.c_void_p, C.c_char_p, c_lp]),
+    "eagle_reshape_m": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, c_lp, C.c_long, c_lp, C.c_int, c_lp]),
+    "eagle_view_load_counts": (C.c_int, [C.c_void_p, c_lp]),
+    "eagle_dev_gather_cols_i8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_long, C.c_long, C.c_void_p,
+                                           C.c_long, C.c_void_p]),
     "eagle_create_M_ascii": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p,
                                        C.c_double, c_lp, C.c_int, C.c_char_p]),
     "eagle_create_Mt_ascii": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_double, c_lp, C.c_int]),

@@ -210,6 +210,12 @@ class HipBackend:
                                        device=self.device).astype(np.int64)
 
 
+    def reshape(self, geno, indxNA):
+        """AM.R:345-366 in VIEW mode: drops the individuals indxNA (1-based) from both genotype files without writing either; the
+        returned geno names the views."""
+        return reshape_geno(geno, indxNA, view=True, device=self.device)
+
+
 class SpectralBackend(HipBackend):
     """The same loop with the scan in the eigenbasis of MM^T (include/eagle_hip.h section 1d; OPT-IN, needs the R-side change
     INTEGRATION.md describes): K = MM^T/max + 0.95 I is fixed for the whole run, so Z = Mt U is made once after calcMMt and
@@ -236,17 +242,38 @@ class SpectralBackend(HipBackend):
         return int(np.flatnonzero(tsq == np.nanmax(tsq))[0]) + 1         # find_qtl.R:71-83
 
 
-def AM(trait, X, geno, availmemGb=8, ncpu=1, maxit=20, quiet=True, backend=None, message=None, algebra=None):
-    """E/R/AM.R:400-475 for a complete-data trait vector and a ready design matrix X (n x q, intercept included).
+def reshape_geno(geno, indxNA, view=False, device=0):
+    """AM.R:345-366: ReshapeM on the two files of `geno`, then geno names the results (<file>tmp) and carries the new dims.
+    view=False writes the files (what a backend without its own `reshape` gets); view=True registers views on `device`."""
+    from . import r_api
+    newdims = r_api.ReshapeM(geno["asciifileM"], geno["asciifileMt"], indxNA, geno["dim_of_ascii_M"], view=view, device=device)
+    return {"asciifileM": geno["asciifileM"] + "tmp", "asciifileMt": geno["asciifileMt"] + "tmp", "dim_of_ascii_M": newdims}
 
-    Returns dict(selected_loci = 1-based marker columns in order of selection, extBIC = list, ve, vg of the last fit).
+
+def AM(trait, X, geno, availmemGb=8, ncpu=1, maxit=20, quiet=True, backend=None, message=None, algebra=None):
+    """E/R/AM.R:320-475 for a trait vector and a ready design matrix X (n x q, intercept included).
+
+    Individuals whose trait or any column of X is NaN are dropped (AM.R:320-329: an NA covariate makes the trait NA): from trait
+    and X, and from the genotype files through backend.reshape(geno, indxNA) (AM.R:345-366; reshape_geno writing the files when
+    the backend has no `reshape`).  A trait without NaN makes no such call.
+    Returns dict(selected_loci = 1-based marker columns in order of selection, extBIC = list, ve, vg of the last fit, indxNA = the
+    dropped rows, 1-based and largest first, and dim_of_ascii_M of the genotypes the loop ran on).
     selected_loci starts as [NA] exactly like AM.R:260, so the selected_loci masking never fires."""
     backend = backend or HipBackend()
     if algebra is not None:  # "host" (LAPACK, the reference's placement) or "device" (SURVEY 8 f-4: rocSOLVER / the fp64 MFMA GEMM through the C ABI)
         host_model.set_algebra(algebra)
     say = message or (lambda *_: None)
-    trait = np.asarray(trait, dtype=np.float64).ravel()
+    trait = np.asarray(trait, dtype=np.float64).ravel().copy()
     currentX = np.asarray(X, dtype=np.float64)
+    trait[np.isnan(currentX).reshape(currentX.shape[0], -1).any(axis=1)] = np.nan   # AM.R:320-329
+    from . import r_api
+    indxNA = r_api.check_for_NA_in_trait(trait)                                     # AM.R:332
+    if indxNA.size:                                                                  # AM.R:337-366
+        keep = np.ones(trait.size, dtype=bool)
+        keep[indxNA - 1] = False
+        trait, currentX = trait[keep], currentX[keep]
+        say(" The following rows are being removed from pheno due to missing data: %s" % " ".join(str(int(i)) for i in indxNA))
+        geno = backend.reshape(geno, indxNA) if hasattr(backend, "reshape") else reshape_geno(geno, indxNA)
     nmarkers = geno["dim_of_ascii_M"][1]
     selected_loci = [np.nan]
     new_selected_locus = np.nan
@@ -285,4 +312,4 @@ def AM(trait, X, geno, availmemGb=8, ncpu=1, maxit=20, quiet=True, backend=None,
         loci = picks[:-1]
         ext = [v for i, v in enumerate(extBIC) if i != len(selected_loci) - 1]
     return {"selected_loci": loci, "all_picks": picks, "extBIC": ext, "extBIC_trace": list(extBIC), "ve": best.get("ve"),
-            "vg": best.get("vg")}
+            "vg": best.get("vg"), "indxNA": indxNA, "dim_of_ascii_M": list(geno["dim_of_ascii_M"])}

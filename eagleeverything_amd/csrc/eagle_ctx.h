@@ -34,6 +34,18 @@ struct GenoEntry {
     void* dev_f4 = nullptr;     // fp4 image of `dev` (two genotypes per byte): operand of the MM^T kernel, made by the first calculateMMt on the file
 };
 
+// A VIEW alias of eagle_reshape_m: the file ReshapeM_rcpp would write, served from the source file (or its resident image)
+// through a keep-map.  axis 0: the lines of M.ascii (individuals), axis 1: the characters of every line of Mt.ascii.
+struct ViewAlias {
+    std::string alias, src;
+    off_t src_size = 0;
+    long src_mtime_ns = 0;
+    int axis = 0;
+    std::vector<int32_t> keep;        // source line (axis 0) / character (axis 1) of every line / character of the alias, increasing
+    long lines = 0;                   // lines of the alias
+    int32_t* d_keep = nullptr;        // the keep-map in HBM (axis 1; made on first use)
+};
+
 struct eagle_ctx {
     int device = -1;
     // multi-device: the ctx eagle_open_devices returns is the LEAD (first device); it owns one sub-context per further device.
@@ -60,6 +72,8 @@ struct eagle_ctx {
     double scan_budget_used = 0.0; int scan_bound_level = 0; double scan_w_err = 0.0;   // of the last digit-slice scan (eagle_last_scan_budget)
     bool spectral_off = false;  // a scan that took a digit off under the spectral bound fell back to fp64: this context stops trying
     std::vector<GenoEntry> cache;
+    std::vector<ViewAlias> views;        // eagle_reshape_m(..., EAGLE_RESHAPE_VIEW, ...) aliases of this device
+    long view_loads[4] = {0, 0, 0, 0};   // view windows loaded, by source (EAGLE_VIEW_RESIDENT ... in eagle_hip.h; eagle_view_load_counts)
     // results of the last calls, kept in HBM
     double* d_mmt = nullptr; long mmt_n = 0; double* d_mmt_max = nullptr;
     double* d_a = nullptr; double* d_vara = nullptr; long scan_L = 0; long scan_cap = 0;
@@ -178,5 +192,13 @@ int eagle_get_resident(eagle_ctx* ctx, const char* path, long rows, long cols, d
 int eagle_get_resident_window(eagle_ctx* ctx, const char* path, long row0, long rows, long col0, long cols, double max_mem_gb, int threads,
                               const GenoEntry** out);
 size_t eagle_resident_budget();
+// The VIEW alias `path` names on this context, or nullptr.
+static inline const ViewAlias* eagle_view_find(const eagle_ctx* ctx, const char* path) {
+    for (auto& v : ctx->views) if (v.alias == path) return &v;
+    return nullptr;
+}
+// Size and mtime that key the cache entries of `path`: the file's own, or for a VIEW alias its source's as recorded at
+// registration.  EAGLE_ERR_OPEN if the file is missing, EAGLE_ERR_FORMAT if an alias's source changed since.
+int eagle_file_key(eagle_ctx* ctx, const char* path, off_t* size, long* mtime_ns);
 size_t eagle_drop_f4_images(eagle_ctx* ctx);   // frees the fp4 MM^T operand images kept with resident files; bytes given back
 #endif

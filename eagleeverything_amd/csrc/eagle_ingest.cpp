@@ -167,6 +167,29 @@ struct SidecarWriter {
 
 extern "C" int eagle_get_row_column(eagle_ctx* ctx, const char* fname, long dims_out[2]) {
     if (!ctx || !fname || !dims_out) return EAGLE_ERR_ARG;
+    if (const ViewAlias* v = eagle_view_find(ctx, fname)) {  // what the file eagle_reshape_m would have written gives
+        off_t size; long mt;
+        int rc = eagle_file_key(ctx, fname, &size, &mt);
+        if (rc) return rc;
+        dims_out[0] = v->lines;
+        dims_out[1] = 0;
+        if (v->lines == 0) return EAGLE_OK;
+        FILE* f = fopen(v->src.c_str(), "r");
+        if (!f) return failf(ctx, EAGLE_ERR_OPEN, "\n\n ERROR: Could not open  %s\n\n", v->src.c_str());
+        char* line = nullptr;
+        size_t cap = 0;
+        ssize_t len = -1;
+        for (long r = 0; r <= (v->axis == 0 ? (long)v->keep[0] : 0L); r++) len = getline(&line, &cap, f);  // the alias's first line
+        fclose(f);
+        if (len >= 0) {
+            std::string first;
+            if (v->axis == 0) first.assign(line, (size_t)len);
+            else for (int32_t c : v->keep) if (c < len) first.push_back(line[c]);
+            dims_out[1] = count_tokens(first.data(), first.data() + first.size());
+        }
+        free(line);
+        return EAGLE_OK;
+    }
     MappedFile m;
     if (!map_file(fname, m)) return failf(ctx, EAGLE_ERR_OPEN, "\n\n ERROR: Could not open  %s\n\n", fname);  // getRowColumn.cpp:35-38
     LineIndex ix;

@@ -8,6 +8,7 @@
 //   k_gemv_mfma ........... a = Mt v (+ diagonal term of vara)          (calculate_a_and_vara_rcpp.cpp:91,
 //                                                                        calculate_reduced_a_rcpp.cpp:83-84)
 //   k_tsq_* ............... tsq = a^2/vara, first arg-max ignoring NaN  (E/R/find_qtl.R:71-83)
+//   k_*_cols .............. column subsets of Mt for the VIEW aliases of eagle_reshape_m (E/src/ReshapeM_rcpp.cpp:94-110)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -1976,6 +1977,146 @@ extern "C" int eagle_dev_unpack2b(eagle_ctx* ctx, const uint8_t* raw, long rows,
         hipLaunchKernelGGL(k_unpack2b, grid, dim3(256), 0, (hipStream_t)stream, raw + r0 * stride, nr, cols, stride, shift, out + r0 * ld_out,
                            ld_out, bad_dev);
     }
+    LAUNCH_CHECK(ctx);
+    return EAGLE_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Column subsets of Mt (the VIEW aliases of eagle_reshape_m): output column j of every row comes from source column
+// map[j] - base.  One lane writes 16 contiguous output bytes of one row (the row's zero padding up to ld_out included) and
+// reads the keep-map entries of its columns through L2 (200 KB at n = 50,000: no LDS copy).
+//   k_gather_cols_i8 ..... resident int8 image of the source -> subset image.  HBM-bound: a lane whose 16 columns are one
+//                          run of the source (every lane but the ~16 around each NA) reads 4 or 5 aligned dwords and
+//                          funnel-shifts them; the others gather bytes.
+//   k_decode_ascii_cols .. text lines of the source -> subset image, validating the kept characters and (eol >= 0) the
+//                          line end at byte `eol` of every line, as k_decode_ascii does for the rewritten file.
+//   k_unpack2b_cols ...... rows of the 2-bit sidecar of the source -> subset image; code 3 is invalid.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void store16(int8_t* dst, long c16, long ld_out, const uint32_t w[4]) {
+    if (c16 + 16 <= ld_out) {
+        i32x4 v = {(int)w[0], (int)w[1], (int)w[2], (int)w[3]};
+        *(i32x4*)dst = v;
+    } else {
+        for (int k = 0; k < 4 && c16 + 4 * k < ld_out; k++) *(uint32_t*)(dst + 4 * k) = w[k];  // ld_out % 4 == 0
+    }
+}
+__global__ __launch_bounds__(256) void k_gather_cols_i8(const int8_t* __restrict__ src, long ld_src, const int32_t* __restrict__ map,
+                                                        long base, long rows, long ncols, int8_t* __restrict__ out, long ld_out, long lanes_per_row) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= rows * lanes_per_row) return;
+    const long row = t / lanes_per_row, c16 = (t - row * lanes_per_row) * 16;
+    const int8_t* s = src + row * ld_src;
+    uint32_t w[4] = {0, 0, 0, 0};
+    if (c16 + 16 <= ncols && map[c16 + 15] - map[c16] == 15) {
+        const long first = map[c16] - base;
+        const uint32_t* a = (const uint32_t*)(s + (first & ~3L));
+        const int r = (int)(first & 3);
+        uint32_t v[5];
+#pragma unroll
+        for (int k = 0; k < 4; k++) v[k] = a[k];
+        if (r) {
+            v[4] = a[4];  // holds the run's last byte: inside the row, since ld_src % 4 == 0
+#pragma unroll
+            for (int k = 0; k < 4; k++) w[k] = __builtin_amdgcn_alignbyte(v[k + 1], v[k], r);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; k++) w[k] = v[k];
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < 16; q++) {
+            const long j = c16 + q;
+            if (j < ncols) w[q >> 2] |= (uint32_t)(uint8_t)s[map[j] - base] << (8 * (q & 3));
+        }
+    }
+    store16(out + row * ld_out + c16, c16, ld_out, w);
+}
+__global__ __launch_bounds__(256) void k_decode_ascii_cols(const uint8_t* __restrict__ raw, long stride, const int32_t* __restrict__ map,
+                                                           long base, long rows, long ncols, long eol, int8_t* __restrict__ out, long ld_out,
+                                                           long lanes_per_row, int* __restrict__ bad) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= rows * lanes_per_row) return;
+    const long row = t / lanes_per_row, c16 = (t - row * lanes_per_row) * 16;
+    const uint8_t* s = raw + row * stride;
+    uint32_t w[4] = {0, 0, 0, 0};
+    int nbad = 0;
+#pragma unroll
+    for (int q = 0; q < 16; q++) {
+        const long j = c16 + q;
+        if (j < ncols) {
+            const int ch = s[map[j] - base];
+            if (ch < '0' || ch > '2') nbad++;
+            w[q >> 2] |= (uint32_t)(uint8_t)(int8_t)(ch - '0' - 1) << (8 * (q & 3));
+        }
+    }
+    const long owner = (ncols < ld_out ? ncols : ld_out - 1) / 16 * 16;  // the lane of column ncols checks the line end
+    if (eol >= 0 && c16 == owner) {
+        const int ch = s[eol];
+        if (ch != '\n' && ch != '\r') nbad++;
+    }
+    store16(out + row * ld_out + c16, c16, ld_out, w);
+    if (nbad) atomicAdd(bad, nbad);
+}
+__global__ __launch_bounds__(256) void k_unpack2b_cols(const uint8_t* __restrict__ raw, long stride, const int32_t* __restrict__ map,
+                                                       long base, long rows, long ncols, int8_t* __restrict__ out, long ld_out,
+                                                       long lanes_per_row, int* __restrict__ bad) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= rows * lanes_per_row) return;
+    const long row = t / lanes_per_row, c16 = (t - row * lanes_per_row) * 16;
+    const uint8_t* s = raw + row * stride;
+    uint32_t w[4] = {0, 0, 0, 0};
+    int nbad = 0;
+#pragma unroll
+    for (int q = 0; q < 16; q++) {
+        const long j = c16 + q;
+        if (j < ncols) {
+            const long idx = map[j] - base;
+            const int g = (s[idx >> 2] >> (2 * (idx & 3))) & 3;
+            if (g == 3) nbad++;
+            w[q >> 2] |= (uint32_t)(uint8_t)(int8_t)(g - 1) << (8 * (q & 3));
+        }
+    }
+    store16(out + row * ld_out + c16, c16, ld_out, w);
+    if (nbad) atomicAdd(bad, nbad);
+}
+static int cols_launch_shape(eagle_ctx* ctx, long rows, long ncols, long ld_out, long* lanes, dim3* grid) {
+    if (ld_out % 4 || ncols > ld_out || rows < 0) return eagle_fail(ctx, EAGLE_ERR_ARG, "column subset: bad shape");
+    *lanes = (ld_out + 15) / 16;
+    const long blocks = (rows * *lanes + 255) / 256;
+    if (blocks > 0x7fffffffL) return eagle_fail(ctx, EAGLE_ERR_ARG, "column subset: too many rows");
+    *grid = dim3((unsigned)blocks);
+    return EAGLE_OK;
+}
+// out[r][j] = src[r][map[j] - base] (j < ncols), 0 up to ld_out.  Every map[j] - base must lie in [0, ld_src).
+extern "C" int eagle_dev_gather_cols_i8(eagle_ctx* ctx, const int8_t* src, long ld_src, const int32_t* map, long base, long rows, long ncols,
+                                        int8_t* out, long ld_out, void* stream) {
+    if (rows <= 0) return EAGLE_OK;
+    if (ld_src % 4 || ((uintptr_t)src & 3)) return eagle_fail(ctx, EAGLE_ERR_ARG, "gather_cols_i8: source rows must be 4-byte aligned");
+    long lanes; dim3 grid;
+    int rc = cols_launch_shape(ctx, rows, ncols, ld_out, &lanes, &grid);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_gather_cols_i8, grid, dim3(256), 0, (hipStream_t)stream, src, ld_src, map, base, rows, ncols, out, ld_out, lanes);
+    LAUNCH_CHECK(ctx);
+    return EAGLE_OK;
+}
+extern "C" int eagle_dev_decode_ascii_cols(eagle_ctx* ctx, const uint8_t* raw, long stride, const int32_t* map, long base, long rows, long ncols,
+                                           long eol, int8_t* out, long ld_out, int* bad_dev, void* stream) {
+    if (rows <= 0) return EAGLE_OK;
+    long lanes; dim3 grid;
+    int rc = cols_launch_shape(ctx, rows, ncols, ld_out, &lanes, &grid);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_decode_ascii_cols, grid, dim3(256), 0, (hipStream_t)stream, raw, stride, map, base, rows, ncols, eol, out, ld_out, lanes,
+                       bad_dev);
+    LAUNCH_CHECK(ctx);
+    return EAGLE_OK;
+}
+extern "C" int eagle_dev_unpack2b_cols(eagle_ctx* ctx, const uint8_t* raw, long stride, const int32_t* map, long base, long rows, long ncols,
+                                       int8_t* out, long ld_out, int* bad_dev, void* stream) {
+    if (rows <= 0) return EAGLE_OK;
+    long lanes; dim3 grid;
+    int rc = cols_launch_shape(ctx, rows, ncols, ld_out, &lanes, &grid);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_unpack2b_cols, grid, dim3(256), 0, (hipStream_t)stream, raw, stride, map, base, rows, ncols, out, ld_out, lanes, bad_dev);
     LAUNCH_CHECK(ctx);
     return EAGLE_OK;
 }

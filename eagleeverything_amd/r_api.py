@@ -5,6 +5,8 @@
   calculate_a_and_vara ... E/R/calculate_a_and_vara.R:1-34
   find_qtl ............... E/R/find_qtl.R:1-84      (.find_qtl; host algebra from host_model)
   extract_geno, constructX E/R/extract_geno.R:1-19, E/R/constructX.R:1-24
+  ReshapeM ............... E/R/ReshapeM.R:1-11
+  check_for_NA_in_trait .. E/R/check_for_NA_in_trait.R:1-25
 
 `geno` is the reference's list {asciifileM, asciifileMt, dim_of_ascii_M = (n, L)} (E/R/ReadMarker.R:306-307).
 selected_loci follow R: 1-based, NA = numpy.nan.  The "-1 only if no NA anywhere" rule
@@ -25,7 +27,7 @@ def _shift_if_no_na(selected_loci):
 
 
 def calculateMMt(geno, availmemGb, ncpu, selected_loci=np.nan, dim_of_ascii_M=None, quiet=True, message=None, device=0):
-    if not os.path.exists(geno):  # calculateMMt.R:19-23
+    if not os.path.exists(geno) and not rcpp_api.is_view(geno, device):  # calculateMMt.R:19-23 (a view alias has no file)
         if message:
             message(" Error: The binary packed file %s cannot be found.\n" % geno)
             message(" calculateMMt has terminated with errors.")
@@ -60,6 +62,19 @@ def extract_geno(fnameM, colnum, availmemGb=8, dim_of_ascii_M=None, device=0):
     """E/R/extract_geno.R:1-19 (colnum is 1-based; the C++ side is 0-based)."""
     return rcpp_api.extract_geno_rcpp(f_name_ascii=fnameM, max_memory_in_Gbytes=availmemGb, selected_locus=colnum - 1,
                                       dims=dim_of_ascii_M, device=device)
+
+
+def check_for_NA_in_trait(trait):
+    """check_for_NA_in_trait.R:1-25: the 1-based positions of NA (NaN) in trait, largest first, or an empty array."""
+    idx = np.flatnonzero(np.isnan(np.asarray(trait, dtype=np.float64).ravel())) + 1
+    return idx[::-1].copy()
+
+
+def ReshapeM(fnameM, fnameMt, indxNA, dims, view=False, device=0):
+    """ReshapeM.R:1-11: indxNA is 1-based (R), the C++ side 0-based.  Returns the new dims of M (lines, length of the last line).
+    view=True: no files are written; fnameM + "tmp" and fnameMt + "tmp" become views on `device`'s context."""
+    return rcpp_api.ReshapeM_rcpp(fnameM=fnameM, fnameMt=fnameMt, indxNA=np.asarray(indxNA, dtype=np.int64) - 1, dims=dims, view=view,
+                                  device=device)
 
 
 def constructX(fnameM, currentX, loci_indx, availmemGb=8, dim_of_ascii_M=None, device=0):

@@ -48,6 +48,7 @@ def close_all():
     for h in _ctx.values():
         L.eagle_close(h)
     _ctx.clear()
+    _views.clear()
     _callbacks.clear()
 
 
@@ -380,6 +381,46 @@ def getRowColumn(fname, device=0):
     d = (C.c_long * 2)()
     _check(ctx, L.eagle_get_row_column(ctx, os.fsencode(fname), d))
     return [int(d[0]), int(d[1])]
+
+
+RESHAPE_FILES, RESHAPE_VIEW = 0, 1
+_views = {}   # device -> alias paths registered by ReshapeM_rcpp(view=True)
+
+
+def ReshapeM_rcpp(fnameM, fnameMt, indxNA, dims, view=False, device=0):
+    """-> newdims (ReshapeM_rcpp.cpp:17-120): the individuals indxNA (0-based, any order) dropped from M.ascii and Mt.ascii
+    under the names fnameM + "tmp" / fnameMt + "tmp".  view=False writes both files (host I/O only: no device is opened) and,
+    when `device`'s context is open, drops views of the same names from it so that its later calls read the new files;
+    view=True writes nothing and registers the two names as views on this device's context, which every later call of this
+    module with the same `device` reads through (include/eagle_hip.h, eagle_reshape_m)."""
+    L = _lib.load()
+    na = np.ascontiguousarray(np.atleast_1d(np.asarray(indxNA, dtype=np.int64)).ravel(), dtype=np.int64)
+    if na.size and not np.all(np.asarray(indxNA) == na):
+        raise ValueError("ReshapeM_rcpp: indxNA must be whole numbers")
+    out = (C.c_long * 2)()
+    ctx = context(device) if view else _ctx.get(device)   # FILES: an open context forgets its views of these names
+    rc = L.eagle_reshape_m(ctx, os.fsencode(fnameM), os.fsencode(fnameMt), na.ctypes.data_as(c_lp), na.size, _dims(dims),
+                           RESHAPE_VIEW if view else RESHAPE_FILES, out)
+    if rc != 0:
+        raise EagleError(rc, L.eagle_last_error(ctx).decode())
+    names = _views.setdefault(device, set())
+    for f in (str(fnameM) + "tmp", str(fnameMt) + "tmp"):
+        (names.add if view else names.discard)(f)
+    return [int(out[0]), int(out[1])]
+
+
+def view_load_counts(device=0):
+    """Windows of view aliases loaded so far on `device`'s context, by source (eagle_view_load_counts)."""
+    L = _lib.load()
+    ctx = context(device)
+    out = (C.c_long * 4)()
+    _check(ctx, L.eagle_view_load_counts(ctx, out))
+    return dict(zip(("resident", "sidecar", "text", "scanner"), (int(v) for v in out)))
+
+
+def is_view(path, device=0):
+    """True when `path` is a view alias registered on `device`'s context (no file of that name need exist)."""
+    return str(path) in _views.get(device, ())
 
 
 def createM_ASCII_rcpp(f_name, f_name_ascii, type, AA, AB, BB, max_memory_in_Gbytes, dims, quiet=True, message=None,

@@ -192,6 +192,30 @@ int eagle_extract_geno(eagle_ctx* ctx, const char* f_name_ascii, double max_memo
  *     it (EAGLE_HIP_SIDECAR=0 disables writing and reading).
  * ------------------------------------------------------------------------------------------- */
 
+/* Replaces  std::vector<long> ReshapeM_rcpp(CharacterVector fnameM, CharacterVector fnameMt, std::vector<long> indxNA,
+ *           std::vector<long> dims)              E/src/ReshapeM_rcpp.cpp:17-120 (called from E/R/ReshapeM.R:8, AM.R:345-366)
+ * Drops the individuals indxNA (0-based, any order; dims = (n, L) of M) from M.ascii and Mt.ascii.  The results are named
+ * fnameM + "tmp" and fnameMt + "tmp", as the reference names its files (:51,94); newdims_out = the reference's value, {lines of
+ * the new M, length of the last line of M}.  A duplicate index or one outside [0, dims[0]) is EAGLE_ERR_ARG (the reference's
+ * erase throws on the one and removes the wrong column on the other); a line of Mt that does not reach the largest index is
+ * EAGLE_ERR_FORMAT.
+ *   EAGLE_RESHAPE_FILES: writes both files, byte for byte what the reference writes (every kept line followed by '\n'), with
+ *     parallel host I/O and no device work.  ctx may be NULL (errors then through eagle_last_error(NULL)).
+ *   EAGLE_RESHAPE_VIEW: writes nothing.  The two names become aliases on this context (and every sub-context of an
+ *     eagle_open_devices one): every call of this library that reads a file -- eagle_read_block, the MM^T and scan entry points,
+ *     eagle_extract_geno, eagle_get_row_column (what the rewritten file would give), eagle_spectral_prepare -- reads the source
+ *     file, its 2-bit sidecar or its resident HBM image through a keep-map of individuals, and gets exactly the int8 image the
+ *     rewritten file would give, zero padding included: results are equal bit for bit.  A resident source Mt image is subset
+ *     by one HBM gather (k_gather_cols_i8).  The alias's resident images are keyed by its name plus the source's size and mtime
+ *     at registration; if a source changes after that, every call on the alias fails with EAGLE_ERR_FORMAT.  Registering the
+ *     names again (either mode) replaces the view and drops the alias's images; eagle_drop_cache keeps the views, eagle_close
+ *     frees them.  nNA == 0 gives an identity view.  A view belongs to ONE context: another process or context (a rank of
+ *     eagleeverything_amd.sharded) that opens the alias path gets EAGLE_ERR_OPEN. */
+#define EAGLE_RESHAPE_FILES 0
+#define EAGLE_RESHAPE_VIEW 1
+int eagle_reshape_m(eagle_ctx* ctx, const char* fnameM, const char* fnameMt, const long* indxNA, long nNA, const long dims[2], int mode,
+                    long newdims_out[2]);
+
 /* Replaces  std::vector<long> getRowColumn(std::string fname)      E/src/getRowColumn.cpp:20-72, RcppExports.cpp:143-151
  * dims_out = (lines, whitespace-separated tokens of the first line). */
 int eagle_get_row_column(eagle_ctx* ctx, const char* fname, long dims_out[2]);
@@ -311,6 +335,18 @@ int eagle_dev_decode_ascii(eagle_ctx* ctx, const uint8_t* raw, long rows, long c
                            int8_t* out, long ld_out, int* bad_chars_dev, void* stream);
 int eagle_dev_transpose_i8(eagle_ctx* ctx, const int8_t* in, long rows, long cols, long ld_in, int8_t* out,
                            long ld_out, void* stream);
+/* out[r*ld_out + j] = src[r*ld_src + map[j] - base] for j < ncols, 0 for ncols <= j < ld_out (r < rows): the column subset of a
+ * resident Mt image behind the VIEW aliases of eagle_reshape_m.  map: device int32, increasing; ld_src, ld_out % 4 == 0; every
+ * map[j] - base in [0, ld_src). */
+int eagle_dev_gather_cols_i8(eagle_ctx* ctx, const int8_t* src, long ld_src, const int32_t* map, long base, long rows, long ncols,
+                             int8_t* out, long ld_out, void* stream);
+/* How many windows of VIEW aliases this context (all its sub-contexts) has loaded, by source: from the source's resident HBM
+ * image (k_gather_cols_i8 / row copies), its 2-bit sidecar, its fixed-width text, or the general line scanner. */
+#define EAGLE_VIEW_RESIDENT 0
+#define EAGLE_VIEW_SIDECAR 1
+#define EAGLE_VIEW_TEXT 2
+#define EAGLE_VIEW_SCANNER 3
+int eagle_view_load_counts(eagle_ctx* ctx, long counts_out[4]);
 int eagle_dev_i8_to_f64_colmajor(eagle_ctx* ctx, const int8_t* in, long rows, long cols, long ld_in,
                                  double* out_colmajor, void* stream);
 
