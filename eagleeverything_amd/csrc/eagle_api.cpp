@@ -1,4 +1,4 @@
-// eagle_api.cpp -- host side of libeaglehip.so: context, genotype tile streamer, and the
+// eagle_api.cpp -- host side of libeaglehip.so: context, streamed marker chunks, and the
 // reference-shaped entry points of section 1 of include/eagle_hip.h.
 //
 // What is replaced (E/ = MyPackage/Eagle/ of the reference):
@@ -115,11 +115,6 @@ template <class T> static T* arena_take(eagle_ctx* ctx, size_t bytes) {
     T* p = (T*)((char*)ctx->arena + ctx->arena_off);
     ctx->arena_off += arena_round(bytes);
     return p;
-}
-static double now_s() {
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return ts.tv_sec + 1e-9 * ts.tv_nsec;
 }
 static bool timing_on() { static int v = -1; if (v < 0) v = getenv("EAGLE_HIP_TIMING") ? 1 : 0; return v == 1; }
 
@@ -307,8 +302,6 @@ extern "C" eagle_ctx* eagle_open_env(void) {
 }
 extern "C" int eagle_device_count(eagle_ctx* ctx) { return ctx ? 1 + (int)ctx->peers.size() : 0; }
 
-static inline int ndev_of(eagle_ctx* ctx) { return 1 + (int)ctx->peers.size(); }
-static inline eagle_ctx* dev_ctx(eagle_ctx* ctx, int k) { return k == 0 ? ctx : ctx->peers[k - 1]; }
 // fn(k, ctx_k) on every device: the lead's share on the calling thread (the only one that may send messages to R), one
 // worker thread per further device; all joined before return.  First hard error wins, then the soft sentinel.
 template <class F> static int run_on_devices(eagle_ctx* ctx, F fn) {
@@ -328,13 +321,6 @@ template <class F> static int run_on_devices(eagle_ctx* ctx, F fn) {
     return EAGLE_OK;
 }
 
-// this device's resident genotype copies only (safe from a per-device worker thread)
-static void drop_cache_local(eagle_ctx* ctx) {
-    (void)hipSetDevice(ctx->device);
-    for (auto& g : ctx->cache) { if (g.dev) (void)hipFree(g.dev); if (g.dev_s) (void)hipFree(g.dev_s); if (g.cshift) (void)hipFree(g.cshift); if (g.l1) (void)hipFree(g.l1); if (g.dev_f4) (void)hipFree(g.dev_f4); }
-    ctx->cache.clear();
-    if (ctx->f4_buf) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(ctx->f4_buf); ctx->f4_buf = nullptr; ctx->f4_cap = 0; }
-}
 // The resident genotype files AND the grow-only workspaces this context holds between calls (the scan arena -- a background reservation
 // in flight included --, the workspace of the int8 W products): everything a caller can get back without closing the context.
 static void drop_workspaces(eagle_ctx* c) {
@@ -466,763 +452,9 @@ static int parse_selected(eagle_ctx* ctx, const double* sel, long nsel, long bou
     return msg ? eagle_fail(ctx, EAGLE_ERR_ARG, msg) : EAGLE_OK;
 }
 
-// ------------------------------------------------------------------------------------------------
-// Tile streamer: lines [row0, row0+nrows), characters [col0, col0+ncols) of a no-space ASCII genotype file
-// -> int8 {-1,0,1} at dst[r*ld + c] in HBM (padding untouched; callers zero it).
-// Fast path: fixed-width file (every line `width` characters + '\n'), pread() straight into pinned memory by
-// `threads` workers, double-buffered against the H2D copy + decode kernel.  The decode kernel verifies the
-// end-of-line byte of every row, so a file that is not fixed-width is detected, and the general path (scan
-// for newlines on the host, copy the first `width` characters of each line) is used instead.
-// ------------------------------------------------------------------------------------------------
-struct FileInfo {
-    int fd = -1;
-    off_t size = 0;
-    long mtime_ns = 0;
-    long width = -1;   // characters per line if fixed-width, else -1
-    long nlines = -1;
-    ~FileInfo() { if (fd >= 0) close(fd); }
-};
-
-static int open_file(eagle_ctx* ctx, const char* path, FileInfo& fi) {
-    fi.fd = open(path, O_RDONLY);
-    if (fi.fd < 0) return failf(ctx, EAGLE_ERR_OPEN, "ERROR: Could not open  %s", path);  // ReadBlock.cpp:42-45
-    struct stat st;
-    if (fstat(fi.fd, &st) != 0) return failf(ctx, EAGLE_ERR_OPEN, "ERROR: Could not stat  %s", path);
-    fi.size = st.st_size;
-    fi.mtime_ns = (long)st.st_mtim.tv_sec * 1000000000L + st.st_mtim.tv_nsec;
-    // probe the first line
-    char buf[1 << 16];
-    long pos = 0, width = -1;
-    while (pos < fi.size && width < 0) {
-        ssize_t got = pread(fi.fd, buf, sizeof buf, pos);
-        if (got <= 0) break;
-        void* nl = memchr(buf, '\n', (size_t)got);
-        if (nl) width = pos + ((char*)nl - buf);
-        pos += got;
-    }
-    if (width >= 0 && fi.size % (width + 1) == 0) {
-        fi.width = width;
-        fi.nlines = fi.size / (width + 1);
-    } else if (width >= 0 && (fi.size + 1) % (width + 1) == 0) {  // last line without '\n'
-        fi.width = width;
-        fi.nlines = (fi.size + 1) / (width + 1);
-    }
-    return EAGLE_OK;
-}
-
-static void parallel_pread(int fd, uint8_t* dst, long dst_stride, long nrows, long nbytes, off_t off0, long src_stride,
-                           int threads, volatile int* io_err) {
-    auto work = [&](long r0, long r1) {
-        if (src_stride == dst_stride && nbytes == src_stride) {  // contiguous range
-            long total = (r1 - r0) * src_stride, done = 0;
-            while (done < total) {
-                ssize_t got = pread(fd, dst + r0 * dst_stride + done, (size_t)(total - done), off0 + r0 * src_stride + done);
-                if (got <= 0) {  // reading past EOF by the missing final '\n' is fine
-                    if (got == 0 && total - done <= 1) { dst[r0 * dst_stride + done] = '\n'; break; }
-                    *io_err = 1;
-                    return;
-                }
-                done += got;
-            }
-            return;
-        }
-        for (long r = r0; r < r1; r++) {
-            long done = 0;
-            while (done < nbytes) {
-                ssize_t got = pread(fd, dst + r * dst_stride + done, (size_t)(nbytes - done), off0 + r * src_stride + done);
-                if (got <= 0) {
-                    if (got == 0 && nbytes - done <= 1) { dst[r * dst_stride + done] = '\n'; break; }
-                    *io_err = 1;
-                    return;
-                }
-                done += got;
-            }
-        }
-    };
-    // a thread per >= 2 MiB of the read, 32 at most: num_cores comes from the caller (R hands detectCores()), and spawning
-    // hundreds of threads per 64 MiB staging buffer costs more than the reads
-    const long by_size = (nrows * nbytes) >> 21;
-    if (threads > 32) threads = 32;
-    if (threads > by_size) threads = (int)by_size;
-    if (threads <= 1 || nrows < 2 * threads) { work(0, nrows); return; }
-    std::vector<std::thread> pool;
-    long per = (nrows + threads - 1) / threads;
-    for (int t = 0; t < threads; t++) {
-        long r0 = t * per, r1 = std::min(nrows, r0 + per);
-        if (r0 >= r1) break;
-        pool.emplace_back(work, r0, r1);
-    }
-    for (auto& th : pool) th.join();
-}
-
-// Two pinned host buffers + two device buffers of at least `need` bytes each, owned by the ctx (grow-only).
-int eagle_stage_ensure(eagle_ctx* ctx, size_t need) {
-    if (need <= ctx->stage_cap) return EAGLE_OK;
-    (void)hipStreamSynchronize(ctx->stream);
-    for (int b = 0; b < 2; b++) {
-        if (ctx->stage_pin[b]) { (void)hipHostFree(ctx->stage_pin[b]); ctx->stage_pin[b] = nullptr; }
-        if (ctx->stage_raw[b]) { (void)hipFree(ctx->stage_raw[b]); ctx->stage_raw[b] = nullptr; }
-    }
-    ctx->stage_cap = 0;
-    for (int b = 0; b < 2; b++) {
-        HIPCHK(ctx, hipHostMalloc(&ctx->stage_pin[b], need, hipHostMallocDefault));
-        HIPCHK(ctx, hipMalloc(&ctx->stage_raw[b], need));
-    }
-    ctx->stage_cap = need;
-    return EAGLE_OK;
-}
-
-static int load_tile_fixed(eagle_ctx* ctx, FileInfo& fi, long row0, long nrows, long col0, long ncols, int8_t* dst,
-                           long ld, double max_mem_gb, int threads) {
-    const long line = fi.width + 1;
-    // take the end-of-line byte along when the window reaches the end of the line: the decode kernel then
-    // verifies it, which is what detects a file that is not fixed-width after all
-    const bool at_end = (col0 + ncols == fi.width);
-    const long src_bytes = at_end ? ncols + 1 : ncols;
-    const long stride = src_bytes;
-    // staging budget: a quarter of availmemGb per buffer, within [one row, 64 MiB]; the two pinned / device staging
-    // buffers live in the ctx (page-locking 100s of MB per call costs more than the copy it feeds)
-    double budget = max_mem_gb > 0 ? max_mem_gb * 1e9 / 4.0 : 64e6;
-    long chunk_rows = (long)std::max(1.0, std::min(budget, 67108864.0) / (double)stride);
-    chunk_rows = std::min(chunk_rows, nrows);
-    int rcs = eagle_stage_ensure(ctx, (size_t)chunk_rows * stride);
-    if (rcs) return rcs;
-    char* pin[2] = {(char*)ctx->stage_pin[0], (char*)ctx->stage_pin[1]};
-    uint8_t* raw[2] = {(uint8_t*)ctx->stage_raw[0], (uint8_t*)ctx->stage_raw[1]};
-    // the bad-character counter lives in the ctx scratch page: a hipMalloc / hipFree per tile would synchronise the device,
-    // i.e. wait for the kernels of the previous chunk when the tile is a chunk of a streamed file
-    int* const bad = (int*)((char*)ctx->d_scratch + EAGLE_SCR_LOADER_BAD);
-    hipEvent_t done[2] = {nullptr, nullptr};
-    HIPCHK(ctx, hipMemsetAsync(bad, 0, sizeof(int), ctx->stream));
-    for (int b = 0; b < 2; b++) HIPCHK(ctx, hipEventCreateWithFlags(&done[b], hipEventDisableTiming));
-    int rc = EAGLE_OK;
-    volatile int io_err = 0;
-    long k = 0;
-    for (long r = 0; r < nrows && rc == EAGLE_OK; r += chunk_rows, k++) {
-        const int b = (int)(k & 1);
-        const long nr = std::min(chunk_rows, nrows - r);
-        if (k >= 2) {
-            hipError_t e = hipEventSynchronize(done[b]);  // the copy out of pin[b] two chunks ago has finished
-            if (e != hipSuccess) { rc = eagle_fail_hip(ctx, e, "hipEventSynchronize"); break; }
-        }
-        const double tp = now_s();
-        parallel_pread(fi.fd, (uint8_t*)pin[b], stride, nr, src_bytes, (off_t)(row0 + r) * line + col0, line, threads,
-                       &io_err);
-        ctx->st_pread_s += now_s() - tp;
-        ctx->st_file_bytes += nr * src_bytes;
-        if (io_err) { rc = eagle_fail(ctx, EAGLE_ERR_FORMAT, "short read: file has fewer lines than requested"); break; }
-        hipError_t e = hipMemcpyAsync(raw[b], pin[b], (size_t)nr * stride, hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) { rc = eagle_fail_hip(ctx, e, "hipMemcpyAsync H2D"); break; }
-        e = hipEventRecord(done[b], ctx->stream);
-        if (e != hipSuccess) { rc = eagle_fail_hip(ctx, e, "hipEventRecord"); break; }
-        rc = eagle_dev_decode_ascii(ctx, raw[b], nr, ncols, stride, dst + r * ld, ld, bad, ctx->stream);
-    }
-    int nbad = 0;
-    if (rc == EAGLE_OK) {
-        hipError_t e = hipMemcpyAsync(&nbad, bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) rc = eagle_fail_hip(ctx, e, "decode sync");
-    } else {
-        (void)hipStreamSynchronize(ctx->stream);
-    }
-    for (int b = 0; b < 2; b++) if (done[b]) (void)hipEventDestroy(done[b]);
-    if (rc == EAGLE_OK && nbad)
-        rc = failf(ctx, EAGLE_ERR_FORMAT, "%d characters outside '0'..'2' (or misplaced line ends) in the requested tile", nbad);
-    return rc;
-}
-
-// Tile from the 2-bit sidecar "<path>.e2b" when there is a valid one (made from this very text file: same size and
-// mtime): a quarter of the bytes to read.  Returns 1 when there is none (the caller parses the text), else a status.
-static int load_tile_sidecar(eagle_ctx* ctx, const char* path, const FileInfo& fi, long row0, long nrows, long col0, long ncols,
-                             int8_t* dst, long ld, int threads) {
-    if (!eagle_sidecar_enabled()) return 1;
-    std::string sp = std::string(path) + ".e2b";
-    int fd = open(sp.c_str(), O_RDONLY);
-    if (fd < 0) return 1;
-    struct Closer { int fd; ~Closer() { close(fd); } } closer{fd};
-    E2bHeader h;
-    if (pread(fd, &h, sizeof h, 0) != (ssize_t)sizeof h || memcmp(h.magic, "EAGLE2B", 8) != 0 || h.version != 1) return 1;
-    if ((off_t)h.src_size != fi.size || h.src_mtime_ns != fi.mtime_ns) return 1;  // stale: the text file changed
-    if ((uint64_t)(row0 + nrows) > h.rows || (uint64_t)(col0 + ncols) > h.cols) return 1;
-    struct stat st;
-    if (fstat(fd, &st) != 0 || (uint64_t)st.st_size < sizeof h + h.rows * h.row_bytes) return 1;
-    const long b0 = col0 / 4, b1 = (col0 + ncols + 3) / 4;
-    const bool whole_rows = col0 == 0 && (uint64_t)ncols == h.cols;  // then the rows are one contiguous byte range
-    const long nb = whole_rows ? (long)h.row_bytes : b1 - b0;
-    const long stride = (nb + 15) / 16 * 16;
-    long chunk_rows = std::max(1L, std::min(nrows, (long)(67108864 / stride)));
-    int rc = eagle_stage_ensure(ctx, (size_t)chunk_rows * stride);
-    if (rc) return rc;
-    int* const bad = (int*)((char*)ctx->d_scratch + EAGLE_SCR_LOADER_BAD);  // (see load_tile_fixed)
-    HIPCHK(ctx, hipMemsetAsync(bad, 0, sizeof(int), ctx->stream));
-    hipEvent_t done[2] = {nullptr, nullptr};
-    for (int b = 0; b < 2; b++) HIPCHK(ctx, hipEventCreateWithFlags(&done[b], hipEventDisableTiming));
-    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int b = 0; b < 2; b++) if (e[b]) (void)hipEventDestroy(e[b]); } } evg{done};
-    volatile int io_err = 0;
-    long k = 0;
-    for (long r = 0; r < nrows; r += chunk_rows, k++) {
-        const int b = (int)(k & 1);
-        const long nr = std::min(chunk_rows, nrows - r);
-        if (k >= 2) HIPCHK(ctx, hipEventSynchronize(done[b]));
-        const double tp = now_s();
-        parallel_pread(fd, (uint8_t*)ctx->stage_pin[b], stride, nr, nb, (off_t)sizeof h + (off_t)(row0 + r) * (off_t)h.row_bytes + b0,
-                       (long)h.row_bytes, threads, &io_err);
-        ctx->st_pread_s += now_s() - tp;
-        ctx->st_file_bytes += nr * nb;
-        if (io_err) { (void)hipStreamSynchronize(ctx->stream); return eagle_fail(ctx, EAGLE_ERR_FORMAT, "short read from the 2-bit sidecar"); }
-        HIPCHK(ctx, hipMemcpyAsync(ctx->stage_raw[b], ctx->stage_pin[b], (size_t)nr * stride, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipEventRecord(done[b], ctx->stream));
-        rc = eagle_dev_unpack2b(ctx, (const uint8_t*)ctx->stage_raw[b], nr, ncols, stride, (int)(col0 % 4), dst + r * ld, ld, bad, ctx->stream);
-        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-    }
-    int nbad = 0;
-    HIPCHK(ctx, hipMemcpyAsync(&nbad, bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (nbad) return failf(ctx, EAGLE_ERR_FORMAT, "%d invalid genotype codes in %s", nbad, sp.c_str());
-    return EAGLE_OK;
-}
-
-// General path: arbitrary line lengths.  Lines are located on the host; the first `col0+ncols` characters of
-// each wanted line are required to exist (the reference indexes past the end of a short line: undefined).
-static int load_tile_general(eagle_ctx* ctx, FileInfo& fi, long row0, long nrows, long col0, long ncols, int8_t* dst,
-                             long ld) {
-    FILE* f = fdopen(dup(fi.fd), "r");
-    if (!f) return eagle_fail(ctx, EAGLE_ERR_OPEN, "fdopen failed");
-    rewind(f);
-    const long chunk_rows = std::max(1L, std::min(nrows, (long)(67108864 / std::max(1L, ncols))));
-    PinBuf pin;
-    DevBuf raw, bad;
-    int rc = EAGLE_OK;
-    hipError_t e;
-    if ((e = pin.alloc((size_t)chunk_rows * ncols)) != hipSuccess || (e = raw.alloc((size_t)chunk_rows * ncols)) != hipSuccess ||
-        (e = bad.alloc(sizeof(int))) != hipSuccess) {
-        fclose(f);
-        return eagle_fail_hip(ctx, e, "alloc");
-    }
-    (void)hipMemsetAsync(bad.p, 0, sizeof(int), ctx->stream);
-    char* line = nullptr;
-    size_t cap = 0;
-    long filled = 0, out_row = 0;
-    for (long rr = 0; rr < row0 + nrows && rc == EAGLE_OK; rr++) {
-        ssize_t len = getline(&line, &cap, f);
-        if (len < 0) { rc = eagle_fail(ctx, EAGLE_ERR_FORMAT, "file has fewer lines than requested"); break; }
-        if (rr < row0) continue;
-        while (len > 0 && (line[len - 1] == '\n' || line[len - 1] == '\r')) len--;
-        if (len < col0 + ncols) { rc = eagle_fail(ctx, EAGLE_ERR_FORMAT, "line shorter than the requested columns"); break; }
-        memcpy((char*)pin.p + filled * ncols, line + col0, (size_t)ncols);
-        filled++;
-        if (filled == chunk_rows || rr == row0 + nrows - 1) {
-            e = hipMemcpyAsync(raw.p, pin.p, (size_t)filled * ncols, hipMemcpyHostToDevice, ctx->stream);
-            if (e != hipSuccess) { rc = eagle_fail_hip(ctx, e, "H2D"); break; }
-            rc = eagle_dev_decode_ascii(ctx, raw.as<uint8_t>(), filled, ncols, ncols, dst + out_row * ld, ld, bad.as<int>(),
-                                        ctx->stream);
-            e = hipStreamSynchronize(ctx->stream);  // single staging buffer
-            if (e != hipSuccess) { rc = eagle_fail_hip(ctx, e, "sync"); break; }
-            out_row += filled;
-            filled = 0;
-        }
-    }
-    free(line);
-    fclose(f);
-    int nbad = 0;
-    if (rc == EAGLE_OK) {
-        e = hipMemcpy(&nbad, bad.p, sizeof(int), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = eagle_fail_hip(ctx, e, "D2H");
-        else if (nbad) rc = failf(ctx, EAGLE_ERR_FORMAT, "%d characters outside '0'..'2' in the requested tile", nbad);
-    }
-    return rc;
-}
-
-// public: load a window of a genotype text file into a caller-owned HBM int8 buffer
-static int load_view(eagle_ctx* ctx, const ViewAlias& v, long row0, long nrows, long col0, long ncols, int8_t* dst, long ld,
-                     double max_mem_gb, int threads);
-extern "C" int eagle_dev_load_ascii(eagle_ctx* ctx, const char* path, long row0, long nrows, long col0, long ncols,
-                                    int8_t* dst, long ld, double max_mem_gb, int threads) {
-    if (!ctx) return EAGLE_ERR_ARG;
-    if (row0 < 0 || nrows < 0 || col0 < 0 || ncols < 0 || ld % 4 || ncols > ld) return eagle_fail(ctx, EAGLE_ERR_ARG, "load_ascii: bad window");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (const ViewAlias* v = eagle_view_find(ctx, path)) return load_view(ctx, *v, row0, nrows, col0, ncols, dst, ld, max_mem_gb, threads);
-    FileInfo fi;
-    int rc = open_file(ctx, path, fi);
-    if (rc) return rc;
-    if (nrows == 0 || ncols == 0) return EAGLE_OK;
-    rc = load_tile_sidecar(ctx, path, fi, row0, nrows, col0, ncols, dst, ld, threads);
-    if (rc != 1) return rc;
-    if (fi.width >= 0) {
-        if (row0 + nrows > fi.nlines) return eagle_fail(ctx, EAGLE_ERR_FORMAT, "file has fewer lines than requested");
-        if (col0 + ncols > fi.width) return eagle_fail(ctx, EAGLE_ERR_FORMAT, "line shorter than the requested columns");
-        rc = load_tile_fixed(ctx, fi, row0, nrows, col0, ncols, dst, ld, max_mem_gb, threads);
-        if (rc != EAGLE_ERR_FORMAT) return rc;
-        // a misplaced line end means the file is not fixed-width after all: fall through to the line scanner
-    }
-    return load_tile_general(ctx, fi, row0, nrows, col0, ncols, dst, ld);
-}
-
-// How many bytes of genotypes may stay resident per file: EAGLE_HIP_MAX_RESIDENT_GB (tests force the streamed path
-// with it), otherwise whatever HBM has free.  Files above it are streamed through HBM in marker chunks.
-#define EAGLE_STREAM 2
-static size_t resident_budget() {
-    const char* e = getenv("EAGLE_HIP_MAX_RESIDENT_GB");
-    if (e && *e) return (size_t)(atof(e) * 1e9);
-    return (size_t)-1;
-}
-
-// Resident genotype tile of a whole file: `rows` lines x first `cols` characters, zero padded to
-// [pad128(rows)][pad128(cols)].
-// Returns EAGLE_OK (*out set), EAGLE_STREAM (too large: the caller streams marker chunks) or an error.
-// reserve_bytes: HBM the caller still needs for operands and workspaces.
-static bool file_key(const char* path, off_t* size, long* mtime_ns) {
-    struct stat st;
-    if (stat(path, &st) != 0) return false;
-    *size = st.st_size;
-    *mtime_ns = (long)st.st_mtim.tv_sec * 1000000000L + st.st_mtim.tv_nsec;
-    return true;
-}
-// A VIEW alias is keyed by its name and its source's size and mtime; a source that changed since registration fails every
-// call on the alias (never stale bits).
-static int view_check(eagle_ctx* ctx, const ViewAlias& v) {
-    off_t size; long mt;
-    if (!file_key(v.src.c_str(), &size, &mt)) return failf(ctx, EAGLE_ERR_OPEN, "ERROR: Could not open  %s (the source of %s)", v.src.c_str(), v.alias.c_str());
-    if (size != v.src_size || mt != v.src_mtime_ns)
-        return failf(ctx, EAGLE_ERR_FORMAT, "%s changed after the view %s was registered (call eagle_reshape_m again)", v.src.c_str(), v.alias.c_str());
-    return EAGLE_OK;
-}
-int eagle_file_key(eagle_ctx* ctx, const char* path, off_t* size, long* mtime_ns) {
-    if (const ViewAlias* v = eagle_view_find(ctx, path)) {
-        int rc = view_check(ctx, *v);
-        if (rc) return rc;
-        *size = v->src_size; *mtime_ns = v->src_mtime_ns;
-        return EAGLE_OK;
-    }
-    return file_key(path, size, mtime_ns) ? EAGLE_OK : failf(ctx, EAGLE_ERR_OPEN, "ERROR: Could not open  %s", path);
-}
-static void free_entry(GenoEntry& g) {
-    if (g.dev) (void)hipFree(g.dev);
-    if (g.dev_s) (void)hipFree(g.dev_s);
-    if (g.cshift) (void)hipFree(g.cshift);
-    if (g.l1) (void)hipFree(g.l1);
-    if (g.dev_f4) (void)hipFree(g.dev_f4);
-    g.dev = g.dev_s = g.cshift = nullptr; g.l1 = nullptr; g.dev_f4 = nullptr;
-}
-// Whole-file resident copy (rows lines x cols characters from the origin), current size and mtime.
-const GenoEntry* eagle_cache_find(eagle_ctx* ctx, const char* path, long rows, long cols) {
-    off_t size; long mt;
-    if (eagle_file_key(ctx, path, &size, &mt)) return nullptr;
-    for (auto& g : ctx->cache)
-        if (g.path == path && g.size == size && g.mtime_ns == mt && g.row0 == 0 && g.col0 == 0 && g.rows == rows && g.cols == cols) return &g;
-    return nullptr;
-}
-// An entry that can serve the window [row0, row0+rows) x [col0, col0+cols): the same window, or an image from the origin that
-// holds it as a prefix (all columns and the first `rows` lines, or all lines and the first `cols` characters): what the lead of
-// a multi-device context finds when the converters left the whole file resident.
-static GenoEntry* cache_find_window(eagle_ctx* ctx, const char* path, off_t size, long mt, long row0, long rows, long col0, long cols) {
-    for (auto& g : ctx->cache) {
-        if (!(g.path == path && g.size == size && g.mtime_ns == mt)) continue;
-        if (g.row0 == row0 && g.col0 == col0 && g.rows == rows && g.cols == cols) return &g;
-        if (row0 == 0 && col0 == 0 && g.row0 == 0 && g.col0 == 0 &&
-            ((g.cols == cols && g.rows >= rows && rows % 256 == 0) || (g.rows == rows && g.cols >= cols && cols % 256 == 0)))
-            return &g;
-    }
-    return nullptr;
-}
-static void cache_drop_path(eagle_ctx* ctx, const char* path) {
-    for (size_t i = 0; i < ctx->cache.size();)
-        if (ctx->cache[i].path == path) {
-            free_entry(ctx->cache[i]);
-            ctx->cache.erase(ctx->cache.begin() + i);
-        } else i++;
-}
-int eagle_cache_adopt(eagle_ctx* ctx, const char* path, long rows, long cols, long rows_pad, long ld, int8_t* dev) {
-    cache_drop_path(ctx, path);
-    GenoEntry g;
-    int rk = eagle_file_key(ctx, path, &g.size, &g.mtime_ns);
-    if (rk) { (void)hipFree(dev); return rk; }
-    g.path = path; g.rows = rows; g.cols = cols; g.rows_pad = rows_pad; g.ld = ld; g.dev = dev;
-    ctx->cache.push_back(g);
-    return EAGLE_OK;
-}
-
-// Resident int8 image of the window [row0, row0+rows) x [col0, col0+cols) of a genotype text file, zero padded to
-// [pad256(rows)][pad256(cols)] (the whole file: row0 = col0 = 0).
-// Returns EAGLE_OK (*out set), EAGLE_STREAM (too large: the caller streams marker chunks) or an error.
-// reserve_bytes: HBM the caller still needs for operands and workspaces.
-static int get_resident(eagle_ctx* ctx, const char* path, long row0, long rows, long col0, long cols, double max_mem_gb, int threads,
-                        GenoEntry** out, size_t reserve_bytes = (size_t)1 << 30) {
-    off_t fsize; long mt;
-    int rk = eagle_file_key(ctx, path, &fsize, &mt);
-    if (rk) return rk;
-    if (GenoEntry* hit = cache_find_window(ctx, path, fsize, mt, row0, rows, col0, cols)) { *out = hit; return EAGLE_OK; }
-    for (size_t i = 0; i < ctx->cache.size();)  // stale entries of the same path (the file changed) and other windows of it
-        if (ctx->cache[i].path == path) { free_entry(ctx->cache[i]); ctx->cache.erase(ctx->cache.begin() + i); } else i++;
-    GenoEntry g;
-    g.path = path; g.size = fsize; g.mtime_ns = mt; g.rows = rows; g.cols = cols; g.row0 = row0; g.col0 = col0;
-    g.rows_pad = eagle_pad(rows); g.ld = eagle_pad(cols);
-    size_t bytes = (size_t)g.rows_pad * (size_t)g.ld;
-    if (bytes > resident_budget()) return EAGLE_STREAM;
-    size_t freeb = 0, totalb = 0;
-    HIPCHK(ctx, hipMemGetInfo(&freeb, &totalb));
-    if (bytes + reserve_bytes > freeb) {
-        drop_cache_local(ctx);
-        HIPCHK(ctx, hipMemGetInfo(&freeb, &totalb));
-        if (bytes + reserve_bytes > freeb) return EAGLE_STREAM;  // does not fit beside the operands: stream it
-    }
-    HIPCHK(ctx, hipMalloc((void**)&g.dev, bytes));
-    hipError_t e = hipMemsetAsync(g.dev, 0, bytes, ctx->stream);
-    if (e != hipSuccess) { (void)hipFree(g.dev); return eagle_fail_hip(ctx, e, "memset"); }
-    int rc = eagle_dev_load_ascii(ctx, path, row0, rows, col0, cols, g.dev, g.ld, max_mem_gb, threads);
-    if (rc) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(g.dev); return rc; }
-    ctx->cache.push_back(g);
-    *out = &ctx->cache.back();
-    return EAGLE_OK;
-}
-
-int eagle_get_resident(eagle_ctx* ctx, const char* path, long rows, long cols, double max_mem_gb, int threads, const GenoEntry** out) {
-    GenoEntry* g = nullptr;
-    int rc = get_resident(ctx, path, 0, rows, 0, cols, max_mem_gb, threads, &g);
-    *out = g;
-    return rc;
-}
-int eagle_get_resident_window(eagle_ctx* ctx, const char* path, long row0, long rows, long col0, long cols, double max_mem_gb, int threads,
-                              const GenoEntry** out) {
-    GenoEntry* g = nullptr;
-    int rc = get_resident(ctx, path, row0, rows, col0, cols, max_mem_gb, threads, &g);
-    *out = g;
-    return rc;
-}
-size_t eagle_resident_budget() { return resident_budget(); }
-
-// ------------------------------------------------------------------------------------------------
-// VIEW aliases of eagle_reshape_m (E/src/ReshapeM_rcpp.cpp): the window [row0, row0+nrows) x [col0, col0+ncols) of the file
-// ReshapeM_rcpp would write, made from the source -- the same int8 image, zero padding included, that loading the rewritten
-// file gives.  An M view (axis 0) drops lines: runs of consecutive kept lines are copied from the source's resident image or
-// loaded from the source file.  An Mt view (axis 1) drops characters: the kept columns are gathered on the device from the
-// resident image (k_gather_cols_i8), the rows of the 2-bit sidecar (k_unpack2b_cols) or fixed-width text (k_decode_ascii_cols);
-// text that is not fixed-width is gathered on the host line by line.
-// ------------------------------------------------------------------------------------------------
-extern "C" int eagle_dev_decode_ascii_cols(eagle_ctx* ctx, const uint8_t* raw, long stride, const int32_t* map, long base, long rows, long ncols,
-                                           long eol, int8_t* out, long ld_out, int* bad_dev, void* stream);
-extern "C" int eagle_dev_unpack2b_cols(eagle_ctx* ctx, const uint8_t* raw, long stride, const int32_t* map, long base, long rows, long ncols,
-                                       int8_t* out, long ld_out, int* bad_dev, void* stream);
-
-// Rows of nb bytes each, pread into the staging ring (double-buffered against the H2D copy) and handed to
-// launch(raw, stride = nb, first_row, rows, bad) on ctx->stream.  The rows are the runs {source row, count} in order: source row q
-// starts at file offset off0 + q * src_stride, and one run is one pread of consecutive rows (split across workers when large).
-// The number of bad bytes the kernels counted lands in *nbad.
-struct RowRun { long src_row, count; };
-template <class Launch>
-static int stream_rows(eagle_ctx* ctx, int fd, off_t off0, long src_stride, const std::vector<RowRun>& runs, long nb, int threads, int* nbad,
-                       Launch launch) {
-    long nrows = 0;
-    for (const RowRun& q : runs) nrows += q.count;
-    const long stride = nb;
-    const long chunk_rows = std::max(1L, std::min(nrows, (long)(67108864 / std::max(1L, stride))));
-    int rc = eagle_stage_ensure(ctx, (size_t)chunk_rows * stride);
-    if (rc) return rc;
-    int* const bad = (int*)((char*)ctx->d_scratch + EAGLE_SCR_LOADER_BAD);
-    HIPCHK(ctx, hipMemsetAsync(bad, 0, sizeof(int), ctx->stream));
-    hipEvent_t done[2] = {nullptr, nullptr};
-    for (int b = 0; b < 2; b++) HIPCHK(ctx, hipEventCreateWithFlags(&done[b], hipEventDisableTiming));
-    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int b = 0; b < 2; b++) if (e[b]) (void)hipEventDestroy(e[b]); } } evg{done};
-    volatile int io_err = 0;
-    size_t ri = 0;
-    long pos = 0, k = 0;  // next row: runs[ri].src_row + pos
-    for (long r = 0; r < nrows; r += chunk_rows, k++) {
-        const int b = (int)(k & 1);
-        const long nr = std::min(chunk_rows, nrows - r);
-        if (k >= 2) HIPCHK(ctx, hipEventSynchronize(done[b]));
-        const double tp = now_s();
-        for (long filled = 0; filled < nr && !io_err;) {
-            const long m = std::min(runs[ri].count - pos, nr - filled);
-            parallel_pread(fd, (uint8_t*)ctx->stage_pin[b] + filled * stride, stride, m, nb, off0 + (off_t)(runs[ri].src_row + pos) * src_stride,
-                           src_stride, threads, &io_err);
-            filled += m;
-            pos += m;
-            if (pos == runs[ri].count) { ri++; pos = 0; }
-        }
-        ctx->st_pread_s += now_s() - tp;
-        ctx->st_file_bytes += nr * nb;
-        if (io_err) { (void)hipStreamSynchronize(ctx->stream); return eagle_fail(ctx, EAGLE_ERR_FORMAT, "short read: file has fewer lines than requested"); }
-        HIPCHK(ctx, hipMemcpyAsync(ctx->stage_raw[b], ctx->stage_pin[b], (size_t)nr * stride, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipEventRecord(done[b], ctx->stream));
-        rc = launch((const uint8_t*)ctx->stage_raw[b], stride, r, nr, bad);
-        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-    }
-    HIPCHK(ctx, hipMemcpyAsync(nbad, bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return EAGLE_OK;
-}
-
-// The 2-bit sidecar of `src` (open file descriptor in *fd, header in *h) when there is a valid one for the text file `fi` that holds
-// rows x cols, else false.  The checks of load_tile_sidecar.
-static bool view_sidecar(const std::string& src, const FileInfo& fi, long rows, long cols, int* fd, E2bHeader* h) {
-    if (!eagle_sidecar_enabled()) return false;
-    *fd = open((src + ".e2b").c_str(), O_RDONLY);
-    if (*fd < 0) return false;
-    struct stat st;
-    if (pread(*fd, h, sizeof *h, 0) == (ssize_t)sizeof *h && memcmp(h->magic, "EAGLE2B", 8) == 0 && h->version == 1 && (off_t)h->src_size == fi.size &&
-        h->src_mtime_ns == fi.mtime_ns && (uint64_t)rows <= h->rows && (uint64_t)cols <= h->cols && fstat(*fd, &st) == 0 &&
-        (uint64_t)st.st_size >= sizeof *h + h->rows * h->row_bytes)
-        return true;
-    close(*fd);
-    *fd = -1;
-    return false;
-}
-
-static const GenoEntry* resident_source(eagle_ctx* ctx, const ViewAlias& v, long rows, long cols) {
-    for (auto& g : ctx->cache)
-        if (g.path == v.src && g.size == v.src_size && g.mtime_ns == v.src_mtime_ns && g.row0 == 0 && g.col0 == 0 && g.dev && g.rows >= rows &&
-            g.cols >= cols)
-            return &g;
-    return nullptr;
-}
-
-static int load_view_cols(eagle_ctx* ctx, ViewAlias& v, long row0, long nrows, long col0, long ncols, int8_t* dst, long ld, int threads) {
-    const char* src = v.src.c_str();
-    const long c_first = v.keep[(size_t)col0], c_last = v.keep[(size_t)(col0 + ncols - 1)];
-    if (!v.d_keep) {
-        const size_t bytes = sizeof(int32_t) * std::max((size_t)1, v.keep.size());
-        HIPCHK(ctx, hipMalloc((void**)&v.d_keep, bytes));
-        HIPCHK(ctx, hipMemcpy(v.d_keep, v.keep.data(), sizeof(int32_t) * v.keep.size(), hipMemcpyHostToDevice));
-    }
-    const int32_t* map = v.d_keep + col0;
-    int rc;
-    // 1. the source is resident (the converters left it there, or an earlier call on it): one HBM gather
-    if (const GenoEntry* g = resident_source(ctx, v, row0 + nrows, c_last + 1)) {
-        rc = eagle_dev_gather_cols_i8(ctx, g->dev + row0 * g->ld, g->ld, map, 0, nrows, ncols, dst, ld, ctx->stream);
-        if (rc) return rc;
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        ctx->view_loads[EAGLE_VIEW_RESIDENT]++;
-        return EAGLE_OK;
-    }
-    FileInfo fi;
-    rc = open_file(ctx, src, fi);
-    if (rc) return rc;
-    // 2. the 2-bit sidecar of the source: whole codes bytes [c_first / 4, c_last / 4] of every row
-    const std::vector<RowRun> rows_run{{row0, nrows}};
-    int sfd = -1;
-    E2bHeader h;
-    if (view_sidecar(v.src, fi, row0 + nrows, c_last + 1, &sfd, &h)) {
-        struct Closer { int fd; ~Closer() { close(fd); } } closer{sfd};
-        const long b0 = c_first / 4, nb = c_last / 4 + 1 - b0;
-        int nbad = 0;
-        rc = stream_rows(ctx, sfd, (off_t)sizeof h + b0, (long)h.row_bytes, rows_run, nb, threads, &nbad,
-                         [&](const uint8_t* raw, long stride, long r, long nr, int* bad) {
-                             return eagle_dev_unpack2b_cols(ctx, raw, stride, map, 4 * b0, nr, ncols, dst + r * ld, ld, bad, ctx->stream);
-                         });
-        if (rc) return rc;
-        if (nbad) return failf(ctx, EAGLE_ERR_FORMAT, "%d invalid genotype codes in %s.e2b", nbad, src);
-        ctx->view_loads[EAGLE_VIEW_SIDECAR]++;
-        return EAGLE_OK;
-    }
-    // 3. fixed-width text: bytes [c_first, c_last] of every line (through the line end when the window reaches the alias's line end)
-    if (fi.width >= 0) {
-        if (row0 + nrows > fi.nlines) return eagle_fail(ctx, EAGLE_ERR_FORMAT, "file has fewer lines than requested");
-        if (c_last >= fi.width) return eagle_fail(ctx, EAGLE_ERR_FORMAT, "line shorter than the requested columns");
-        const bool at_end = col0 + ncols == (long)v.keep.size();   // (the keep-list spans the whole first line)
-        const long nb = (at_end ? fi.width + 1 : c_last + 1) - c_first;
-        int nbad = 0;
-        rc = stream_rows(ctx, fi.fd, (off_t)c_first, fi.width + 1, rows_run, nb, threads, &nbad,
-                         [&](const uint8_t* raw, long stride, long r, long nr, int* bad) {
-                             return eagle_dev_decode_ascii_cols(ctx, raw, stride, map, c_first, nr, ncols, at_end ? fi.width - c_first : -1,
-                                                                dst + r * ld, ld, bad, ctx->stream);
-                         });
-        if (rc) return rc;
-        if (nbad == 0) { ctx->view_loads[EAGLE_VIEW_TEXT]++; return EAGLE_OK; }
-        // a bad character or a misplaced line end: not fixed-width after all (or not a genotype file): the line scanner decides
-    }
-    // 4. any other text: lines located and gathered on the host, decoded on the device
-    ctx->view_loads[EAGLE_VIEW_SCANNER]++;
-    FILE* f = fdopen(dup(fi.fd), "r");
-    if (!f) return eagle_fail(ctx, EAGLE_ERR_OPEN, "fdopen failed");
-    struct FCloser { FILE* f; ~FCloser() { fclose(f); } } fcloser{f};
-    rewind(f);
-    const long chunk_rows = std::max(1L, std::min(nrows, (long)(67108864 / std::max(1L, ncols))));
-    PinBuf pin;
-    DevBuf raw, bad;
-    HIPCHK(ctx, pin.alloc((size_t)chunk_rows * ncols));
-    HIPCHK(ctx, raw.alloc((size_t)chunk_rows * ncols));
-    HIPCHK(ctx, bad.alloc(sizeof(int)));
-    HIPCHK(ctx, hipMemsetAsync(bad.p, 0, sizeof(int), ctx->stream));
-    char* line = nullptr;
-    size_t cap = 0;
-    struct Freer { char** p; ~Freer() { free(*p); } } freer{&line};
-    long filled = 0, out_row = 0;
-    for (long rr = 0; rr < row0 + nrows; rr++) {
-        ssize_t len = getline(&line, &cap, f);
-        if (len < 0) return eagle_fail(ctx, EAGLE_ERR_FORMAT, "file has fewer lines than requested");
-        if (rr < row0) continue;
-        while (len > 0 && (line[len - 1] == '\n' || line[len - 1] == '\r')) len--;
-        if (len <= c_last) return eagle_fail(ctx, EAGLE_ERR_FORMAT, "line shorter than the requested columns");
-        char* o = (char*)pin.p + filled * ncols;
-        for (long j = 0; j < ncols; j++) o[j] = line[v.keep[(size_t)(col0 + j)]];
-        filled++;
-        if (filled == chunk_rows || rr == row0 + nrows - 1) {
-            HIPCHK(ctx, hipMemcpyAsync(raw.p, pin.p, (size_t)filled * ncols, hipMemcpyHostToDevice, ctx->stream));
-            rc = eagle_dev_decode_ascii(ctx, raw.as<uint8_t>(), filled, ncols, ncols, dst + out_row * ld, ld, bad.as<int>(), ctx->stream);
-            if (rc) return rc;
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // single staging buffer
-            out_row += filled;
-            filled = 0;
-        }
-    }
-    int nbad = 0;
-    HIPCHK(ctx, hipMemcpy(&nbad, bad.p, sizeof(int), hipMemcpyDeviceToHost));
-    if (nbad) return failf(ctx, EAGLE_ERR_FORMAT, "%d characters outside '0'..'2' in the requested tile", nbad);
-    return EAGLE_OK;
-}
-
-static int load_view(eagle_ctx* ctx, const ViewAlias& cv, long row0, long nrows, long col0, long ncols, int8_t* dst, long ld,
-                     double max_mem_gb, int threads) {
-    ViewAlias& v = const_cast<ViewAlias&>(cv);  // (the device keep-map is made on first use)
-    int rc = view_check(ctx, v);
-    if (rc) return rc;
-    if (nrows == 0 || ncols == 0) return EAGLE_OK;
-    if (v.axis == 1) {
-        if (row0 + nrows > v.lines) return eagle_fail(ctx, EAGLE_ERR_FORMAT, "file has fewer lines than requested");
-        if (col0 + ncols > (long)v.keep.size()) return eagle_fail(ctx, EAGLE_ERR_FORMAT, "line shorter than the requested columns");
-        return load_view_cols(ctx, v, row0, nrows, col0, ncols, dst, ld, threads);
-    }
-    if (row0 + nrows > (long)v.keep.size()) return eagle_fail(ctx, EAGLE_ERR_FORMAT, "file has fewer lines than requested");
-    std::vector<RowRun> runs;  // runs of consecutive kept lines
-    for (long i = 0; i < nrows;) {
-        long j = i + 1;
-        while (j < nrows && v.keep[(size_t)(row0 + j)] == v.keep[(size_t)(row0 + j - 1)] + 1) j++;
-        runs.push_back({(long)v.keep[(size_t)(row0 + i)], j - i});
-        i = j;
-    }
-    const long src_rows = runs.back().src_row + runs.back().count;
-    // 1. the source is resident: one 2-D copy per run
-    if (const GenoEntry* g = resident_source(ctx, v, src_rows, col0 + ncols)) {
-        long i = 0;
-        for (const RowRun& q : runs) {
-            HIPCHK(ctx, hipMemcpy2DAsync(dst + i * ld, (size_t)ld, g->dev + q.src_row * g->ld + col0, (size_t)g->ld, (size_t)ncols, (size_t)q.count,
-                                         hipMemcpyDeviceToDevice, ctx->stream));
-            i += q.count;
-        }
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        ctx->view_loads[EAGLE_VIEW_RESIDENT]++;
-        return EAGLE_OK;
-    }
-    // 2. / 3. the source's sidecar or fixed-width text, opened once, one pread per run into the staging ring
-    FileInfo fi;
-    rc = open_file(ctx, v.src.c_str(), fi);
-    if (rc) return rc;
-    int sfd = -1;
-    E2bHeader h;
-    if (view_sidecar(v.src, fi, src_rows, col0 + ncols, &sfd, &h)) {
-        struct Closer { int fd; ~Closer() { close(fd); } } closer{sfd};
-        const long b0 = col0 / 4, nb = (col0 + ncols + 3) / 4 - b0;
-        int nbad = 0;
-        rc = stream_rows(ctx, sfd, (off_t)sizeof h + b0, (long)h.row_bytes, runs, nb, threads, &nbad,
-                         [&](const uint8_t* raw, long stride, long r, long nr, int* bad) {
-                             return eagle_dev_unpack2b(ctx, raw, nr, ncols, stride, (int)(col0 % 4), dst + r * ld, ld, bad, ctx->stream);
-                         });
-        if (rc) return rc;
-        if (nbad) return failf(ctx, EAGLE_ERR_FORMAT, "%d invalid genotype codes in %s.e2b", nbad, v.src.c_str());
-        ctx->view_loads[EAGLE_VIEW_SIDECAR]++;
-        return EAGLE_OK;
-    }
-    if (fi.width >= 0) {
-        if (src_rows > fi.nlines) return eagle_fail(ctx, EAGLE_ERR_FORMAT, "file has fewer lines than requested");
-        if (col0 + ncols > fi.width) return eagle_fail(ctx, EAGLE_ERR_FORMAT, "line shorter than the requested columns");
-        // the end-of-line byte goes along when the window reaches the line end: the decode kernel checks it (load_tile_fixed)
-        const long nb = col0 + ncols == fi.width ? ncols + 1 : ncols;
-        int nbad = 0;
-        rc = stream_rows(ctx, fi.fd, (off_t)col0, fi.width + 1, runs, nb, threads, &nbad,
-                         [&](const uint8_t* raw, long stride, long r, long nr, int* bad) {
-                             return eagle_dev_decode_ascii(ctx, raw, nr, ncols, stride, dst + r * ld, ld, bad, ctx->stream);
-                         });
-        if (rc) return rc;
-        if (nbad == 0) { ctx->view_loads[EAGLE_VIEW_TEXT]++; return EAGLE_OK; }
-    }
-    // 4. not fixed-width after all: each run through the general loader, as the rewritten file would be read
-    ctx->view_loads[EAGLE_VIEW_SCANNER]++;
-    long i = 0;
-    for (const RowRun& q : runs) {
-        rc = eagle_dev_load_ascii(ctx, v.src.c_str(), q.src_row, q.count, col0, ncols, dst + i * ld, ld, max_mem_gb, threads);
-        if (rc) return rc;
-        i += q.count;
-    }
-    return EAGLE_OK;
-}
-
-// Lines and the lengths of the first and last line of a text file: from the first line and the size when the file is fixed-width
-// (what the loaders assume and verify), else from a line index.
-static bool text_shape(const char* path, long* nlines, long* first_len, long* last_len) {
-    FileInfo fi;
-    if (open_file(nullptr, path, fi)) return false;
-    if (fi.width >= 0) { *nlines = fi.nlines; *first_len = *last_len = fi.width; return true; }
-    ReshapeMap m;
-    if (!m.open_ro(path)) return false;
-    LineIndex ix;
-    index_lines_buf(m.p, m.size, host_threads(), ix);
-    *nlines = ix.nlines();
-    *first_len = *nlines > 0 ? (long)(ix.end(0) - ix.begin(0)) : 0;
-    *last_len = *nlines > 0 ? (long)(ix.end(*nlines - 1) - ix.begin(*nlines - 1)) : 0;
-    return true;
-}
-
-static void view_drop(eagle_ctx* c, const std::string& alias) {
-    for (size_t i = 0; i < c->views.size();)
-        if (c->views[i].alias == alias) {
-            if (c->views[i].d_keep) { (void)hipSetDevice(c->device); (void)hipStreamSynchronize(c->stream); (void)hipFree(c->views[i].d_keep); }
-            c->views.erase(c->views.begin() + (long)i);
-        } else i++;
-    if (!c->cache.empty()) { (void)hipSetDevice(c->device); (void)hipStreamSynchronize(c->stream); cache_drop_path(c, alias.c_str()); }
-}
-
-extern "C" int eagle_view_load_counts(eagle_ctx* ctx, long counts_out[4]) {
-    if (!ctx || !counts_out) return EAGLE_ERR_ARG;
-    for (int p = 0; p < 4; p++) {
-        counts_out[p] = 0;
-        for (int k = 0; k < ndev_of(ctx); k++) counts_out[p] += dev_ctx(ctx, k)->view_loads[p];
-    }
-    return EAGLE_OK;
-}
-
-static int reshape_fail(eagle_ctx* ctx, int code, const char* msg) {
-    if (ctx) return eagle_fail(ctx, code, msg);
-    snprintf(g_open_err, sizeof g_open_err, "%s", msg);
-    return code;
-}
-
-extern "C" int eagle_reshape_m(eagle_ctx* ctx, const char* fnameM, const char* fnameMt, const long* indxNA, long nNA, const long dims[2],
-                               int mode, long newdims_out[2]) {
-    if (!fnameM || !fnameMt || !dims || !newdims_out) return reshape_fail(ctx, EAGLE_ERR_ARG, "ReshapeM: NULL argument");
-    if (mode != EAGLE_RESHAPE_FILES && mode != EAGLE_RESHAPE_VIEW) return reshape_fail(ctx, EAGLE_ERR_ARG, "ReshapeM: unknown mode");
-    if (mode == EAGLE_RESHAPE_VIEW && !ctx) return reshape_fail(ctx, EAGLE_ERR_ARG, "ReshapeM: a VIEW needs a context");
-    std::vector<long> na;
-    if (const char* why = reshape_check_na(indxNA, nNA, dims[0], na)) return reshape_fail(ctx, EAGLE_ERR_ARG, why);
-    const std::string aM = std::string(fnameM) + "tmp", aMt = std::string(fnameMt) + "tmp";  // ReshapeM_rcpp.cpp:51,94
-    if (ctx) {
-        if (eagle_view_find(ctx, fnameM) || eagle_view_find(ctx, fnameMt)) return reshape_fail(ctx, EAGLE_ERR_ARG, "ReshapeM: the source is itself a view");
-        for (int k = 0; k < ndev_of(ctx); k++) { view_drop(dev_ctx(ctx, k), aM); view_drop(dev_ctx(ctx, k), aMt); }
-        (void)hipSetDevice(ctx->device);
-    }
-    if (mode == EAGLE_RESHAPE_FILES) {
-        std::string msg;
-        const int rc = reshape_write_files(fnameM, fnameMt, na, host_threads(), newdims_out, msg);
-        return rc ? reshape_fail(ctx, rc, msg.c_str()) : EAGLE_OK;
-    }
-    ViewAlias vm, vt;
-    long mlines, mfirst, mlast, tlines, tfirst, tlast;
-    if (!file_key(fnameM, &vm.src_size, &vm.src_mtime_ns) || !text_shape(fnameM, &mlines, &mfirst, &mlast))
-        return failf(ctx, EAGLE_ERR_OPEN, "ERROR: Could not open  %s", fnameM);
-    if (!file_key(fnameMt, &vt.src_size, &vt.src_mtime_ns) || !text_shape(fnameMt, &tlines, &tfirst, &tlast))
-        return failf(ctx, EAGLE_ERR_OPEN, "ERROR: Could not open  %s", fnameMt);
-    if (!na.empty() && tlines > 0 && tfirst <= na.back())
-        return failf(ctx, EAGLE_ERR_FORMAT, "ReshapeM: the lines of %s are shorter than the largest index of indxNA", fnameMt);
-    vm.alias = aM; vm.src = fnameM; vm.axis = 0; vm.keep = reshape_keep_list(mlines, na); vm.lines = (long)vm.keep.size();
-    vt.alias = aMt; vt.src = fnameMt; vt.axis = 1; vt.keep = reshape_keep_list(tfirst, na); vt.lines = tlines;
-    newdims_out[0] = vm.lines;   // lines written to M (:66-72), length of M's last line (:74)
-    newdims_out[1] = mlines > 0 ? mlast : 0;
-    for (int k = 0; k < ndev_of(ctx); k++) { dev_ctx(ctx, k)->views.push_back(vm); dev_ctx(ctx, k)->views.push_back(vt); }
-    return EAGLE_OK;
-}
-
 // Rows (multiple of 256) of a streamed chunk whose padded row length is `row_bytes`.
 static long stream_chunk_rows(long row_bytes, long total_rows_pad) {
-    return stream_chunk_rows_core(resident_budget(), row_bytes, total_rows_pad);  // eagle_host.h
+    return stream_chunk_rows_core(eagle_resident_budget(), row_bytes, total_rows_pad);  // eagle_host.h
 }
 
 // Out-of-core streaming: chunk k+1 is read (pread -> pinned -> H2D -> decode, all on ctx->load_stream) while the kernels
@@ -1421,12 +653,7 @@ extern "C" int eagle_read_block(eagle_ctx* ctx, const char* asciifname, long sta
     if (!ctx) return EAGLE_ERR_ARG;
     if (start_row < 0 || numcols < 0 || numrows < 0) return eagle_fail(ctx, EAGLE_ERR_ARG, "negative dimension");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (numcols == 0 || numrows == 0) {
-        off_t size; long mt;
-        if (eagle_view_find(ctx, asciifname)) return eagle_file_key(ctx, asciifname, &size, &mt);
-        FileInfo fi;
-        return open_file(ctx, asciifname, fi);
-    }
+    if (numcols == 0 || numrows == 0) return eagle_dev_load_ascii(ctx, asciifname, start_row, 0, 0, 0, nullptr, 0, 1.0, 4);  // the file must open
     const long ld = eagle_pad(numcols);
     DevBuf tile, dbl;
     HIPCHK(ctx, tile.alloc((size_t)numrows * ld));
@@ -2148,8 +1375,9 @@ static int scan_range(eagle_ctx* ctx, const char* f_name_ascii, long L, long n, 
                     if (e == hipSuccess) e = hipMemsetAsync(rows, 0, (size_t)((cnt + 127) / 128 * 128) * (size_t)np, ctx->stream);
                     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
                     if (e != hipSuccess) rc = eagle_fail_hip(ctx, e, "candidate list");
-                    for (long c = 0; c < cnt && !rc; c++)
-                        rc = eagle_dev_load_ascii(ctx, f_name_ascii, m0 + idx[(size_t)c], 1, 0, n, rows + c * np, np, max_memory_in_Gbytes, 1);
+                    std::vector<RowRun> runs((size_t)cnt);
+                    for (long c = 0; c < cnt; c++) runs[(size_t)c] = {m0 + idx[(size_t)c], 1};
+                    if (!rc) rc = eagle_load_rows(ctx, f_name_ascii, runs, 0, n, rows, np, max_memory_in_Gbytes, 1);
                     if (!rc) rc = eagle_dev_cert_reevaluate(ctx, nullptr, np, np, Wu, ctx->d_vara, cert, ctx->stream);
                 }
             }
@@ -2418,48 +1646,16 @@ extern "C" int eagle_extract_geno(eagle_ctx* ctx, const char* f_name_ascii, doub
                 return EAGLE_OK;
             }
     }
-    if (eagle_view_find(ctx, f_name_ascii)) {  // not resident, a VIEW alias: the column through the view's loader
-        DevBuf col;
-        HIPCHK(ctx, col.alloc((size_t)n * 16));
-        int rc = eagle_dev_load_ascii(ctx, f_name_ascii, 0, n, selected_locus, 1, col.as<int8_t>(), 16, max_memory_in_Gbytes, host_threads());
-        if (rc) return rc;
-        std::vector<int8_t> h((size_t)n * 16);
-        HIPCHK(ctx, hipMemcpyAsync(h.data(), col.p, h.size(), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        for (long r = 0; r < n; r++) column_out[r] = h[(size_t)r * 16];
-        return EAGLE_OK;
-    }
-    // not resident: one character per line straight from the file (no n x L parse)
-    FileInfo fi;
-    int rc = open_file(ctx, f_name_ascii, fi);
+    // not resident: the column through the loader (the file's sidecar, fixed-width text or the line scanner; a view's source)
+    DevBuf col;
+    HIPCHK(ctx, col.alloc((size_t)n * 16));
+    int rc = eagle_dev_load_ascii(ctx, f_name_ascii, 0, n, selected_locus, 1, col.as<int8_t>(), 16, max_memory_in_Gbytes, host_threads());
     if (rc) return rc;
-    if (fi.width >= 0) {
-        if (n > fi.nlines) return eagle_fail(ctx, EAGLE_ERR_FORMAT, "file has fewer lines than requested");
-        if (selected_locus >= fi.width) return eagle_fail(ctx, EAGLE_ERR_FORMAT, "line shorter than the requested columns");
-        for (long r = 0; r < n; r++) {
-            char c;
-            if (pread(fi.fd, &c, 1, (off_t)r * (fi.width + 1) + selected_locus) != 1) return eagle_fail(ctx, EAGLE_ERR_FORMAT, "short read");
-            if (c < '0' || c > '2') return eagle_fail(ctx, EAGLE_ERR_FORMAT, "character outside '0'..'2'");
-            column_out[r] = (c - '0') - 1;
-        }
-        return EAGLE_OK;
-    }
-    FILE* f = fdopen(dup(fi.fd), "r");
-    if (!f) return eagle_fail(ctx, EAGLE_ERR_OPEN, "fdopen failed");
-    rewind(f);
-    char* line = nullptr;
-    size_t cap = 0;
-    rc = EAGLE_OK;
-    for (long r = 0; r < n; r++) {
-        ssize_t len = getline(&line, &cap, f);
-        if (len <= selected_locus) { rc = eagle_fail(ctx, EAGLE_ERR_FORMAT, "file shorter than requested"); break; }
-        char c = line[selected_locus];
-        if (c < '0' || c > '2') { rc = eagle_fail(ctx, EAGLE_ERR_FORMAT, "character outside '0'..'2'"); break; }
-        column_out[r] = (c - '0') - 1;
-    }
-    free(line);
-    fclose(f);
-    return rc;
+    std::vector<int8_t> h((size_t)n * 16);
+    HIPCHK(ctx, hipMemcpyAsync(h.data(), col.p, h.size(), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (long r = 0; r < n; r++) column_out[r] = h[(size_t)r * 16];
+    return EAGLE_OK;
 }
 
 static int local_scan_argmax(eagle_ctx* ctx, eagle_best* h) {

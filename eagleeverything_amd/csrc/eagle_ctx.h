@@ -1,4 +1,4 @@
-// eagle_ctx.h -- the context object and small host helpers shared by eagle_api.cpp and eagle_ingest.cpp
+// eagle_ctx.h -- the context object and small host helpers shared by eagle_api.cpp, eagle_load.cpp and eagle_ingest.cpp
 // (private to libeaglehip.so; the public ABI only sees the opaque eagle_ctx*).
 #ifndef EAGLE_CTX_H
 #define EAGLE_CTX_H
@@ -8,6 +8,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <sys/types.h>
+#include <time.h>
 
 #include <condition_variable>
 #include <mutex>
@@ -43,7 +44,7 @@ struct ViewAlias {
     int axis = 0;
     std::vector<int32_t> keep;        // source line (axis 0) / character (axis 1) of every line / character of the alias, increasing
     long lines = 0;                   // lines of the alias
-    int32_t* d_keep = nullptr;        // the keep-map in HBM (axis 1; made on first use)
+    mutable int32_t* d_keep = nullptr;   // the keep-map in HBM (axis 1; made on first use)
 };
 
 struct eagle_ctx {
@@ -201,4 +202,27 @@ static inline const ViewAlias* eagle_view_find(const eagle_ctx* ctx, const char*
 // registration.  EAGLE_ERR_OPEN if the file is missing, EAGLE_ERR_FORMAT if an alias's source changed since.
 int eagle_file_key(eagle_ctx* ctx, const char* path, off_t* size, long* mtime_ns);
 size_t eagle_drop_f4_images(eagle_ctx* ctx);   // frees the fp4 MM^T operand images kept with resident files; bytes given back
+
+static inline double now_s() {
+    struct timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return ts.tv_sec + 1e-9 * ts.tv_nsec;
+}
+static inline int ndev_of(eagle_ctx* ctx) { return 1 + (int)ctx->peers.size(); }
+static inline eagle_ctx* dev_ctx(eagle_ctx* ctx, int k) { return k == 0 ? ctx : ctx->peers[k - 1]; }
+// this device's resident genotype copies only (safe from a per-device worker thread)
+static inline void drop_cache_local(eagle_ctx* ctx) {
+    (void)hipSetDevice(ctx->device);
+    for (auto& g : ctx->cache) { if (g.dev) (void)hipFree(g.dev); if (g.dev_s) (void)hipFree(g.dev_s); if (g.cshift) (void)hipFree(g.cshift); if (g.l1) (void)hipFree(g.l1); if (g.dev_f4) (void)hipFree(g.dev_f4); }
+    ctx->cache.clear();
+    if (ctx->f4_buf) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(ctx->f4_buf); ctx->f4_buf = nullptr; ctx->f4_cap = 0; }
+}
+#define EAGLE_STREAM 2
+// Resident int8 image of a window of a genotype file (eagle_load.cpp); reserve_bytes: HBM the caller still needs.
+int get_resident(eagle_ctx* ctx, const char* path, long row0, long rows, long col0, long cols, double max_mem_gb, int threads,
+                 GenoEntry** out, size_t reserve_bytes = (size_t)1 << 30);
+// The lines `runs` (disjoint, in any order) of the genotype file or VIEW alias `path`, characters [col0, col0 + ncols), to consecutive
+// rows of dst (eagle_dev_load_ascii is one run).
+int eagle_load_rows(eagle_ctx* ctx, const char* path, const std::vector<RowRun>& runs, long col0, long ncols, int8_t* dst, long ld,
+                    double max_mem_gb, int threads);
 #endif

@@ -1,10 +1,11 @@
 // eagle_host.h -- the HIP-free host pieces of libeaglehip.so: plain C++17, no device types, so that a CPU test binary can build
 // them with -fsanitize=address,undefined / -fsanitize=thread (tests/host/, run by tests/test_host_sanitizers.py; GPU sanitizers do
-// not exist on the target pool).  Everything here is used by eagle_api.cpp / eagle_ingest.cpp / eagle_i8mfma.hip as is.
+// not exist on the target pool).  Everything here is used by eagle_api.cpp / eagle_load.cpp / eagle_ingest.cpp / eagle_i8mfma.hip as is.
 #ifndef EAGLE_HOST_H
 #define EAGLE_HOST_H
 #include <math.h>
 #include <stddef.h>
+#include <stdint.h>
 #include <string.h>
 
 #include <algorithm>
@@ -28,7 +29,7 @@ enum : size_t {
     EAGLE_SCR_SYM = 0,             // int[2]: k_sym_check's verdict on S and V                      (eagle_kernels.hip)
     EAGLE_SCR_CERT_TOTALS = 256,   // long[4]: certification counters summed over marker blocks      (eagle_api.cpp scan_range)
     EAGLE_SCR_INGEST = 512,        // u64[2]: first third-allele / first missing position; double: trace  (eagle_ingest.cpp, eagle_linalg.cpp)
-    EAGLE_SCR_LOADER_BAD = 1024,   // int: invalid characters / codes seen by the tile loaders       (eagle_api.cpp, any stream)
+    EAGLE_SCR_LOADER_BAD = 1024,   // int: invalid characters / codes seen by the tile loaders       (eagle_load.cpp, any stream)
     EAGLE_SCR_SCACHE_FLAG = 2048,  // int: cached S differs from the caller's                        (eagle_api.cpp, load stream)
     EAGLE_SCR_DOT_PARTIALS = 4096, // double[256]: partial sums of eagle_dev_dot_matrices            (eagle_kernels.hip)
     EAGLE_SCR_BYTES = 8192
@@ -184,5 +185,33 @@ static inline long count_tokens(const char* p, const char* end) {
     long len, n = 0;
     while ((p = next_token(p, end, &tok, &len)) != nullptr) n++;
     return n;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Byte arithmetic of the genotype loader (eagle_load.cpp).
+// ------------------------------------------------------------------------------------------------
+// `count` consecutive source lines from `src_row`, loaded to consecutive destination rows.
+struct RowRun { long src_row, count; };
+// Runs of consecutive values of keep[0 .. n): the source lines of n consecutive lines of an M view.
+static inline void append_keep_runs(const int32_t* keep, long n, std::vector<RowRun>& runs) {
+    for (long i = 0; i < n;) {
+        long j = i + 1;
+        while (j < n && keep[j] == keep[j - 1] + 1) j++;
+        runs.push_back({(long)keep[i], j - i});
+        i = j;
+    }
+}
+// Bytes read of every line of fixed-width text (`width` characters + '\n') for the characters [c_first, c_last]: from c_first on.
+// A window that reaches the line end takes the '\n' along, and the decode kernels check it: that is what detects text that is not
+// fixed-width after all.
+static inline long text_window_bytes(long c_first, long c_last, long width, bool at_end) { return (at_end ? width + 1 : c_last + 1) - c_first; }
+// Bytes read of every row of the 2-bit sidecar (4 codes per byte, `cols` codes in `row_bytes` bytes) for the characters
+// [c_first, c_last]: nb bytes from byte b0, the first wanted code at 2-bit position `shift` of byte b0.  Whole rows are read
+// whole, so that consecutive rows are one contiguous byte range.
+struct SidecarWindow { long b0, nb; int shift; };
+static inline SidecarWindow sidecar_window(long c_first, long c_last, long cols, long row_bytes) {
+    const long b0 = c_first / 4;
+    const bool whole_rows = c_first == 0 && c_last + 1 == cols;
+    return {b0, whole_rows ? row_bytes : c_last / 4 + 1 - b0, (int)(c_first % 4)};
 }
 #endif

@@ -167,11 +167,49 @@ static void test_text() {
     CHECK(total == 1000);
 }
 
+// ---- loader byte arithmetic (eagle_load.cpp) --------------------------------------------------------------------------
+static void test_loader_windows() {
+    // runs of a keep list: consecutive source lines merge, gaps split
+    {
+        const int32_t keep[] = {0, 1, 2, 5, 6, 9, 11, 12};
+        std::vector<RowRun> runs;
+        append_keep_runs(keep, 8, runs);
+        CHECK(runs.size() == 4);
+        CHECK(runs[0].src_row == 0 && runs[0].count == 3 && runs[1].src_row == 5 && runs[1].count == 2);
+        CHECK(runs[2].src_row == 9 && runs[2].count == 1 && runs[3].src_row == 11 && runs[3].count == 2);
+        append_keep_runs(keep + 3, 2, runs);   // appends: the runs of a view window that starts inside the list
+        CHECK(runs.size() == 5 && runs[4].src_row == 5 && runs[4].count == 2);
+        std::vector<RowRun> none;
+        append_keep_runs(keep, 0, none);
+        CHECK(none.empty());
+    }
+    // fixed-width text, width 10: the line end goes along only at the end of the line
+    CHECK(text_window_bytes(0, 9, 10, true) == 11);
+    CHECK(text_window_bytes(3, 9, 10, true) == 8);
+    CHECK(text_window_bytes(3, 5, 10, false) == 3);
+    CHECK(text_window_bytes(2, 6, 10, true) == 9);    // a keep-map window that reaches the line end reads through it
+    CHECK(text_window_bytes(7, 7, 10, false) == 1);
+    // 2-bit sidecar, 37 codes in rows of 16 bytes
+    {
+        SidecarWindow w = sidecar_window(0, 36, 37, 16);  // whole rows: one contiguous range
+        CHECK(w.b0 == 0 && w.nb == 16 && w.shift == 0);
+        w = sidecar_window(0, 35, 37, 16);
+        CHECK(w.b0 == 0 && w.nb == 9 && w.shift == 0);
+        w = sidecar_window(5, 5, 37, 16);
+        CHECK(w.b0 == 1 && w.nb == 1 && w.shift == 1);
+        w = sidecar_window(7, 8, 37, 16);                 // straddles a byte boundary
+        CHECK(w.b0 == 1 && w.nb == 2 && w.shift == 3);
+        w = sidecar_window(4, 36, 37, 16);
+        CHECK(w.b0 == 1 && w.nb == 9 && w.shift == 0);
+    }
+}
+
 int main(int argc, char** argv) {
     const std::string what = argc > 1 ? argv[1] : "all";
     if (what == "all" || what == "rendezvous") test_rendezvous();
     if (what == "all" || what == "rules") test_small_rules();
     if (what == "all" || what == "text") test_text();
+    if (what == "all" || what == "loader") test_loader_windows();
     if (g_fail) { fprintf(stderr, "%d check(s) failed\n", g_fail); return 1; }
     printf("host checks passed (%s)\n", what.c_str());
     return 0;

@@ -182,19 +182,36 @@ def test_reduced_a(files, api, oracle):
     _close(np.delete(arm.ravel(), [5, 9]), np.delete(ref.ravel(), [5, 9]), scale=np.abs(ref).max())
 
 
-def test_extract_geno_resident_and_from_file(files, api, oracle):
+def test_extract_geno_resident_and_from_file(files, api, oracle, tmp_path):
+    import torch
+    from eagleeverything_amd import _lib
     g, geno = files["synth_203x1531"]
     n, L = g["M8"].shape
     api.drop_cache()
-    for c in (0, 17, L - 1):  # not resident: one character per line from the file
+    for c in (0, 17, L - 1):  # not resident: the column through the loader
         np.testing.assert_array_equal(api.extract_geno_rcpp(geno["asciifileM"], 8.0, c, (n, L)),
                                       oracle.extract_geno_rcpp(geno["asciifileM"], 8.0, c, (n, L)))
+    # the loader's other sources: a 2-bit sidecar (beside a text file of holes: only the sidecar can give the column) and text that
+    # is not fixed-width (the line scanner)
+    side = str(tmp_path / "side.ascii")
+    image = torch.zeros((n, (L + 255) // 256 * 256), dtype=torch.int8, device="cuda")
+    image[:, :L] = torch.from_numpy(np.ascontiguousarray(g["M8"], dtype=np.int8)).cuda()
+    synth.write_sidecar_from_device(_lib.load(), api.context(), image, n, L, side)
+    ragged = tmp_path / "ragged.ascii"
+    ragged.write_text("".join("".join(map(str, row + 1)) + "0" * (i % 3) + "\n" for i, row in enumerate(g["M8"])))
+    for path in (side, str(ragged)):
+        for c in (0, 17, L - 1):
+            np.testing.assert_array_equal(api.extract_geno_rcpp(path, 8.0, c, (n, L)), g["M8"][:, c].astype(np.int32))
     api.calculateMMt_rcpp(geno["asciifileM"], 8.0, 2, NA, (n, L))  # makes M.ascii resident in HBM
     for c in (0, 17, L - 1):
         np.testing.assert_array_equal(api.extract_geno_rcpp(geno["asciifileM"], 8.0, c, (n, L)), g["M8"][:, c].astype(np.int32))
     from eagleeverything_amd._lib import EagleError
     with pytest.raises(EagleError):
         api.extract_geno_rcpp(geno["asciifileM"], 8.0, L, (n, L))
+    bad = tmp_path / "bad.ascii"
+    bad.write_text("01a\n012\n")
+    with pytest.raises(EagleError, match="outside '0'..'2'"):
+        api.extract_geno_rcpp(str(bad), 8.0, 2, (2, 3))
 
 
 def test_find_qtl_mirror_selects_same_marker(files, api, oracle):
