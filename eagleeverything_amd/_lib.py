@@ -54,6 +54,9 @@ SIGNATURES = {
                                              C.c_int, c_dp, c_dp]),
     "eagle_spectral_prepare": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, c_dp, C.c_double]),
     "eagle_spectral_scan": (C.c_int, [C.c_void_p, c_dp, c_dp, c_dp, C.c_long, C.c_double, C.c_double, c_dp, C.c_long, c_dp, c_dp]),
+    "eagle_spectral_scan_traits": (C.c_int, [C.c_void_p, C.c_long, c_dp, C.POINTER(c_dp), c_lp, c_dp, c_dp, c_dp, c_dp, c_dp, c_lp, c_dp]),
+    "eagle_spectral_traits_passes": (C.c_int, [C.c_long, c_lp]),
+    "eagle_spectral_rows": (C.c_int, [C.c_void_p, c_lp, C.c_long, c_dp]),
     "eagle_scan_with_W": (C.c_int, [C.c_void_p, C.c_char_p, c_dp, C.c_long, c_dp, c_dp, C.c_double, c_lp, C.c_int, c_dp, c_dp]),
     "eagle_calculate_reduced_a": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double, c_dp, c_dp, C.c_double, c_lp, c_dp,
                                             C.c_long, C.c_int, c_dp]),
@@ -127,6 +130,8 @@ SIGNATURES = {
                                                C.c_void_p]),
     "eagle_dev_spectral_pass": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p]),
+    "eagle_dev_spectral_pass_traits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                                 C.c_void_p]),
     "eagle_dev_spectral_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_void_p, C.c_double,
                                             C.c_void_p, C.c_void_p, C.c_void_p]),
     "eagle_dev_zero_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_long,

@@ -176,6 +176,114 @@ def emma_MLE(y, X, K, ngrids=100, llim=-10, ulim=10, esp=1e-10, eig_L=None, eig_
     return {"ML": maxLL, "delta": maxdelta, "ve": maxva * maxdelta, "vg": maxva}
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# emma.REMLE / emma.MLE in the eigenbasis of K (K = U diag(lam) U^T, fixed for a whole run), the FaST-LMM identities: with
+# Ut = U^T X, ut = U^T y, w_k = 1/(lam_k + delta), A = Ut^T W Ut, b = Ut^T W ut,
+#     y^T P y = R = ut^T W ut - b^T A^-1 b,   P y = U r,  r = W (ut - Ut A^-1 b),
+#     sum log(eig_R + delta) = sum log(lam + delta) + log det A - log det Ut^T Ut,   tr P = sum w - sum_k w_k^2 (Ut A^-1 Ut^T)_kk,
+# so every likelihood evaluation costs O(n q^2) instead of the n^3 eigen() of S (K + I) S (emma_eigen_R_wo_Z).  The functions are
+# equal in exact arithmetic to _reml_ll / _reml_dll / _ml_ll / _ml_dll; grid, bracket rule and zeroin are emma_REMLE's / emma_MLE's.
+# ---------------------------------------------------------------------------------------------------------------------------
+def _eig_fit(lam, Ut, ut, delta):
+    """w, Ut^T W Ut, W-weighted residual r and R = y^T P y at one delta (R from the residual: no cancellation)."""
+    w = 1.0 / (lam + delta)
+    Uw = Ut * w[:, None]
+    A = Ut.T @ Uw
+    beta = np.linalg.solve(A, Uw.T @ ut)
+    e = ut - Ut @ beta
+    return w, Uw, A, w * e, float(np.sum(w * e * e))
+
+
+def _eig_ll(logdelta, lam, Ut, ut, reml, logdet_xtx):
+    n, q = Ut.shape
+    d = math.exp(logdelta)
+    _, _, A, _, R = _eig_fit(lam, Ut, ut, d)
+    m = n - q if reml else n
+    ll = m * (math.log(m / (2 * math.pi)) - 1 - math.log(R)) - np.sum(np.log(lam + d))
+    if reml:
+        ll -= np.linalg.slogdet(A)[1] - logdet_xtx
+    return 0.5 * ll
+
+
+def _eig_dll(logdelta, lam, Ut, ut, reml):
+    n, q = Ut.shape
+    d = math.exp(logdelta)
+    w, Uw, A, r, R = _eig_fit(lam, Ut, ut, d)
+    trP = np.sum(w)
+    if reml:
+        trP -= np.sum(np.linalg.inv(A) * (Uw.T @ Uw))   # sum_k w_k^2 (Ut A^-1 Ut^T)_kk = tr(A^-1 Ut^T W^2 Ut)
+    return 0.5 * ((n - q if reml else n) * np.sum(r * r) / R - trP)
+
+
+_grid_memo = []   # [(lam, delta, [W | W^2])]: the same lam and grids serve every trait and iteration of a run
+
+
+def _grid_weights(lam, delta):
+    for lm, dl, WW in _grid_memo:
+        if lm is lam and np.array_equal(dl, delta):
+            return WW
+    Wg = 1.0 / (lam[:, None] + delta[None, :])
+    WW = np.hstack([Wg, Wg * Wg])
+    _grid_memo[:] = ([e for e in _grid_memo if e[0] is lam] + [(lam, delta, WW)])[-2:]
+    return WW
+
+
+def _eig_grid_dll(lam, Ut, ut, delta, reml):
+    """dLL/dlogdelta on the whole grid from one GEMM: the n x (q+1)(q+2)/2 products of [Ut | ut] row entries times the n x 2m
+    weights [W | W^2], then (q+1) x (q+1) algebra per grid point."""
+    n, q = Ut.shape
+    B = np.column_stack([Ut, ut])
+    iu, ju = np.triu_indices(q + 1)
+    WW = _grid_weights(lam, delta)
+    S = (B[:, iu] * B[:, ju]).T @ WW                                 # ((q+1)(q+2)/2) x 2m
+    m = delta.size
+    M = np.empty((2 * m, q + 1, q + 1))
+    M[:, iu, ju] = S.T
+    M[:, ju, iu] = S.T
+    S1, S2 = M[:m], M[m:]
+    A, b = S1[:, :q, :q], S1[:, :q, q]
+    beta = np.linalg.solve(A, b[..., None])[..., 0]
+    R = S1[:, q, q] - np.einsum("gi,gi->g", b, beta)
+    r2 = S2[:, q, q] - 2 * np.einsum("gi,gi->g", beta, S2[:, :q, q]) + np.einsum("gi,gij,gj->g", beta, S2[:, :q, :q], beta)
+    trP = WW[:, :m].sum(axis=0)
+    if reml:
+        trP = trP - np.einsum("gij,gji->g", np.linalg.inv(A), S2[:, :q, :q])
+    return 0.5 * delta * ((n - q if reml else n) * r2 / R - trP)
+
+
+def _emma_eig(lam, UtX, Uty, ngrids, llim, ulim, esp, reml):
+    lam = np.asarray(lam, dtype=np.float64).ravel()
+    Ut = np.asarray(UtX, dtype=np.float64).reshape(lam.size, -1)
+    ut = np.asarray(Uty, dtype=np.float64).ravel()
+    n, q = Ut.shape
+    xtx = Ut.T @ Ut                                  # = X^T X (U orthogonal)
+    if np.linalg.det(xtx) == 0:
+        return None
+    logdet_xtx = np.linalg.slogdet(xtx)[1]
+    logdelta, delta = _grid(ngrids, llim, ulim)
+    dLL = _eig_grid_dll(lam, Ut, ut, delta, reml)
+    maxdelta, maxLL = _optimise(dLL, logdelta, llim, ulim, esp, lambda ld: _eig_ll(ld, lam, Ut, ut, reml, logdet_xtx),
+                                lambda ld: _eig_dll(ld, lam, Ut, ut, reml))
+    maxva = _eig_fit(lam, Ut, ut, maxdelta)[4] / (n - q if reml else n)
+    return maxLL, maxdelta, maxva
+
+
+def emma_REMLE_eig(lam, UtX, Uty, ngrids=100, llim=-10, ulim=10, esp=1e-10):
+    """emma_REMLE(y, X, K) from lam, U = eigh(K): UtX = U^T X (n x q), Uty = U^T y.  No n^3 work."""
+    r = _emma_eig(lam, UtX, Uty, ngrids, llim, ulim, esp, True)
+    if r is None:
+        return {"REML": 0, "delta": 0, "ve": 0, "vg": 0}
+    return {"REML": r[0], "delta": r[1], "ve": r[2] * r[1], "vg": r[2]}
+
+
+def emma_MLE_eig(lam, UtX, Uty, ngrids=100, llim=-10, ulim=10, esp=1e-10):
+    """emma_MLE(y, X, K) from lam, U = eigh(K) (the xi of emma_MLE are lam)."""
+    r = _emma_eig(lam, UtX, Uty, ngrids, llim, ulim, esp, False)
+    if r is None:
+        return {"ML": 0, "delta": 0, "ve": 0, "vg": 0}
+    return {"ML": r[0], "delta": r[1], "ve": r[2] * r[1], "vg": r[2]}
+
+
 def calcVC(trait, currentX, MMt, eig_R=None):
     r = emma_REMLE(trait, currentX, MMt, eig_R=eig_R)
     return {"vg": r["vg"], "ve": r["ve"]}
@@ -313,3 +421,83 @@ def AM(trait, X, geno, availmemGb=8, ncpu=1, maxit=20, quiet=True, backend=None,
         ext = [v for i, v in enumerate(extBIC) if i != len(selected_loci) - 1]
     return {"selected_loci": loci, "all_picks": picks, "extBIC": ext, "extBIC_trace": list(extBIC), "ve": best.get("ve"),
             "vg": best.get("vg"), "indxNA": indxNA, "dim_of_ascii_M": list(geno["dim_of_ascii_M"])}
+
+
+def AM_traits(Y, X, geno, availmemGb=8, maxit=20, quiet=True, message=None, algebra=None, device=0):
+    """AM() for the T columns of Y (n x T) with one design matrix X (n x q) on one genotype panel, in one run: calcMMt and
+    lam, U = eigh(MM^T) once, Z = Mt U once (spectral_prepare), then the traits in lockstep -- each round one spectral_scan_traits
+    call for every trait still running, and per trait emma_REMLE_eig / emma_MLE_eig in the eigenbasis (no n^3 work per trait or
+    iteration).  Each trait follows AM()'s loop (stop rule AM.R:448, maxit, result assembly AM.R:476-499) and gets a dict with
+    AM()'s keys.
+
+    A row with NaN in ANY trait or in X is dropped for ALL traits (one VIEW reshape of the genotypes): with different NA patterns
+    the result differs from separate AM() runs, which drop each trait's own NA rows only.  A pick adds its row of Z (U^T m_j,
+    spectral_rows) to that trait's U^T X."""
+    from . import r_api, rcpp_api
+    Y = np.asarray(Y, dtype=np.float64)
+    Y = Y.reshape(Y.shape[0], -1).copy()
+    currentX = np.asarray(X, dtype=np.float64).reshape(Y.shape[0], -1)
+    T, q = Y.shape[1], currentX.shape[1]
+    if q + maxit - 1 > 31:
+        raise ValueError("AM_traits: q + maxit - 1 = %d fixed-effect columns in the last scan; the spectral scan takes at most 31"
+                         % (q + maxit - 1))
+    if algebra is not None:
+        host_model.set_algebra(algebra)
+    say = message or (lambda *_: None)
+    na_row = np.isnan(Y).any(axis=1) | np.isnan(currentX).any(axis=1)
+    indxNA = r_api.check_for_NA_in_trait(np.where(na_row, np.nan, 0.0))
+    if indxNA.size:
+        keep = ~na_row
+        Y, currentX = Y[keep], currentX[keep]
+        say(" The following rows are being removed from pheno due to missing data: %s" % " ".join(str(int(i)) for i in indxNA))
+        geno = reshape_geno(geno, indxNA, view=True, device=device)
+    n, nmarkers = geno["dim_of_ascii_M"]
+    MMt = r_api.calcMMt(geno, availmemGb, 1, np.array([np.nan]), quiet, device=device)
+    lam, U = host_model.algebra().eigh(MMt)
+    lam = np.ascontiguousarray(lam)
+    del MMt
+    rcpp_api.spectral_prepare(geno["asciifileMt"], (nmarkers, n), U, availmemGb, device=device)
+    UtY = U.T @ Y
+    UtX0 = U.T @ currentX
+    del U
+    st = [{"UtX": UtX0, "sel": [np.nan], "ext": [], "best": {}, "itnum": 1, "cont": True} for _ in range(T)]
+    while any(s["cont"] for s in st):
+        active = [s for s in st if s["cont"]]
+        scan = []
+        for t, s in enumerate(st):
+            if not s["cont"]:
+                continue
+            say("Trait %d, iteration %d: Searching for most significant marker-trait association" % (t + 1, s["itnum"]))
+            r = emma_REMLE_eig(lam, s["UtX"], UtY[:, t])                                         # calcVC
+            s["best"] = {"vg": r["vg"], "ve": r["ve"]}
+            ml = emma_MLE_eig(lam, s["UtX"], UtY[:, t], llim=-100, ulim=100)                     # calc_extBIC
+            k = s["UtX"].shape[1]
+            s["ext"].append(-2 * ml["ML"] + (k + 1) * math.log(n) + 2 * _lchoose(nmarkers, k - 1))
+            if int(np.flatnonzero(np.asarray(s["ext"]) == min(s["ext"]))[0]) == len(s["ext"]) - 1:   # AM.R:448
+                scan.append(t)
+            else:
+                s["cont"] = False
+        if scan:
+            res = rcpp_api.spectral_scan_traits(lam, [st[t]["UtX"] for t in scan], UtY[:, scan], [st[t]["best"]["ve"] for t in scan],
+                                                [st[t]["best"]["vg"] for t in scan], nmarkers, device=device)
+            if np.any(res["index"] < 1):
+                raise RuntimeError("AM_traits: every tsq of a scan is NaN")
+            rows = rcpp_api.spectral_rows(res["index"] - 1, device=device)
+            for j, t in enumerate(scan):
+                st[t]["sel"].append(int(res["index"][j]))
+                st[t]["UtX"] = np.column_stack([st[t]["UtX"], rows[:, j]])
+        for s in active:
+            s["itnum"] += 1
+            if s["itnum"] > maxit:                                                                # AM.R:463-470
+                s["cont"] = False
+    out = []
+    for s in st:   # AM.R:476-499, as in AM()
+        picks = [int(v) for v in s["sel"][1:]]
+        if s["itnum"] > maxit or len(s["sel"]) <= 1:
+            loci, ext = picks, list(s["ext"])
+        else:
+            loci = picks[:-1]
+            ext = [v for i, v in enumerate(s["ext"]) if i != len(s["sel"]) - 1]
+        out.append({"selected_loci": loci, "all_picks": picks, "extBIC": ext, "extBIC_trace": list(s["ext"]), "ve": s["best"].get("ve"),
+                    "vg": s["best"].get("vg"), "indxNA": indxNA, "dim_of_ascii_M": list(geno["dim_of_ascii_M"])})
+    return out

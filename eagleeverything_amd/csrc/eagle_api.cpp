@@ -1816,3 +1816,105 @@ extern "C" int eagle_spectral_scan(eagle_ctx* ctx, const double* lambda, const d
         return eagle_spectral_scan_range(c, d.data(), G.data(), NC, Cm.data(), c1.data(), p, varG, sel.data(), (long)sel.size(), a_out, vara_out);
     });
 }
+
+// Many traits over one Z (section 1d).  The per-trait host operands (eagle_spectral_host_operands: d_t, G_t, C_t, c1_t; the
+// long-double p^2 n loops) run on up to 16 host threads, one trait at a time each; the traits are then packed into column groups
+// (spectral_trait_groups, eagle_host.h), each group's columns built once for every device.
+extern "C" int eagle_spectral_traits_passes(long T, const long* p) {
+    if (T < 1 || !p) return EAGLE_ERR_ARG;
+    for (long t = 0; t < T; t++) if (p[t] < 1 || p[t] > 31) return EAGLE_ERR_ARG;
+    std::vector<SpectralGroup> groups;
+    spectral_trait_groups(T, p, SPT_MAX_TILES, groups);
+    return (int)groups.size();
+}
+extern "C" int eagle_spectral_scan_traits(eagle_ctx* ctx, long T, const double* lambda, const double* const* UtX, const long* p, const double* Uty,
+                                          const double* varE, const double* varG, double* a_out, double* vara_out, long* index_out,
+                                          double* tsqmax_out) {
+    if (!ctx) return EAGLE_ERR_ARG;
+    if (ctx->spectral_L <= 0) return eagle_fail(ctx, EAGLE_ERR_ARG, "spectral_scan_traits: eagle_spectral_prepare has not run");
+    if (T < 1) return eagle_fail(ctx, EAGLE_ERR_ARG, "spectral_scan_traits: T >= 1 traits");
+    if (!lambda || !UtX || !p || !Uty || !varE || !varG || !index_out || (!a_out) != (!vara_out))
+        return eagle_fail(ctx, EAGLE_ERR_ARG, "spectral_scan_traits: NULL argument (a_out and vara_out: both or neither)");
+    char msg[256];
+    for (long t = 0; t < T; t++) {
+        if (p[t] < 1 || p[t] > 31) {
+            snprintf(msg, sizeof msg, "spectral_scan_traits: trait %ld: 1 <= p <= 31 fixed-effect columns (got %ld)", t + 1, p[t]);
+            return eagle_fail(ctx, EAGLE_ERR_ARG, msg);
+        }
+        if (!UtX[t]) return eagle_fail(ctx, EAGLE_ERR_ARG, "spectral_scan_traits: NULL UtX[t]");
+    }
+    const long L = ctx->spectral_L, n = ctx->z_n, np = eagle_pad(n);
+    std::vector<std::vector<double>> d(T), Gt(T), Cm(T), c1(T);
+    std::vector<int> rct(T, 0);
+    std::atomic<long> next(0);
+    auto work = [&] {
+        for (long t; (t = next++) < T;) {
+            d[t].resize(np); Gt[t].resize((size_t)np * (p[t] + 1)); Cm[t].resize((size_t)p[t] * p[t]); c1[t].resize(p[t]);
+            rct[t] = eagle_spectral_host_operands(nullptr, n, lambda, UtX[t], Uty + t * n, p[t], varE[t], varG[t], (int)(p[t] + 1), d[t].data(),
+                                                  Gt[t].data(), Cm[t].data(), c1[t].data());
+        }
+    };
+    {
+        std::vector<std::thread> pool;
+        for (long w = 1; w < std::min<long>(host_threads(), T); w++) pool.emplace_back(work);
+        work();
+        for (auto& th : pool) th.join();
+    }
+    for (long t = 0; t < T; t++)
+        if (rct[t]) {  // again on this thread, for the message
+            std::vector<double> dd(np), gg((size_t)np * (p[t] + 1)), cc((size_t)p[t] * p[t]), c(p[t]);
+            eagle_spectral_host_operands(ctx, n, lambda, UtX[t], Uty + t * n, p[t], varE[t], varG[t], (int)(p[t] + 1), dd.data(), gg.data(), cc.data(), c.data());
+            snprintf(msg, sizeof msg, "trait %ld: %s", t + 1, ctx->err);
+            return eagle_fail(ctx, rct[t], msg);
+        }
+    std::vector<SpectralGroup> groups;
+    spectral_trait_groups(T, p, SPT_MAX_TILES, groups);
+    std::vector<SpectralTraitDesc> desc(T);
+    std::vector<double> par;
+    std::vector<std::vector<double>> G(groups.size());
+    for (size_t k = 0; k < groups.size(); k++) {
+        const SpectralGroup& gr = groups[k];
+        const long NC = 16L * gr.nt;
+        G[k].assign((size_t)np * NC, 0.0);
+        int off = 0;
+        for (long t = gr.t0; t < gr.t1; t++) {
+            const int pt = (int)p[t], qcol = gr.ntl * 16 + (int)(t - gr.t0);
+            desc[t] = {off, pt, qcol, (int)t, (long)par.size(), varG[t]};
+            par.insert(par.end(), Cm[t].begin(), Cm[t].end());
+            par.insert(par.end(), c1[t].begin(), c1[t].end());
+            double* Gk = G[k].data();
+            for (long r = 0; r < n; r++) {
+                memcpy(Gk + r * NC + off, Gt[t].data() + r * (pt + 1), sizeof(double) * (pt + 1));
+                Gk[r * NC + qcol] = d[t][r];
+            }
+            off += pt + 1;
+        }
+    }
+    const int nd = ndev_of(ctx);
+    std::vector<std::vector<eagle_best>> best((size_t)nd, std::vector<eagle_best>(T));
+    int rc = run_on_devices(ctx, [&](int k, eagle_ctx* c) -> int {
+        return eagle_spectral_traits_range(c, T, groups, G, desc.data(), par.data(), (long)par.size(), L, a_out, vara_out, best[k].data());
+    });
+    if (rc) return rc;
+    // the devices' maxima merged: the largest tsq, ties -> the smallest global index (which(tsq == max(tsq))[1], find_qtl.R:76-80)
+    for (long t = 0; t < T; t++) {
+        double bv = 0.0;
+        long bi = -1;
+        for (int k = 0; k < nd; k++) {
+            const eagle_best& b = best[k][t];
+            if (b.index0 >= 0 && (bi < 0 || b.tsqmax > bv || (b.tsqmax == bv && b.index0 < bi))) { bv = b.tsqmax; bi = b.index0; }
+        }
+        index_out[t] = bi + 1;
+        if (tsqmax_out) tsqmax_out[t] = bi >= 0 ? bv : NAN;
+    }
+    return EAGLE_OK;
+}
+extern "C" int eagle_spectral_rows(eagle_ctx* ctx, const long* idx, long k, double* out) {
+    if (!ctx) return EAGLE_ERR_ARG;
+    if (ctx->spectral_L <= 0) return eagle_fail(ctx, EAGLE_ERR_ARG, "spectral_rows: eagle_spectral_prepare has not run");
+    if (k < 0 || (k > 0 && (!idx || !out))) return eagle_fail(ctx, EAGLE_ERR_ARG, "spectral_rows: bad arguments");
+    for (long j = 0; j < k; j++)
+        if (idx[j] < 0 || idx[j] >= ctx->spectral_L) return eagle_fail(ctx, EAGLE_ERR_ARG, "spectral_rows: marker index out of range");
+    if (k == 0) return EAGLE_OK;
+    return run_on_devices(ctx, [&](int, eagle_ctx* c) -> int { return eagle_spectral_rows_range(c, idx, k, out); });
+}

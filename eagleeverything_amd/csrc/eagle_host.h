@@ -84,6 +84,31 @@ static inline void split_markers(long L, int ndev, std::vector<long>& edge) {
     edge[(size_t)ndev] = L;
 }
 
+// Column groups of eagle_spectral_scan_traits, one pass over Z each: whole traits in order, as many as fit in max_tiles MFMA tiles
+// of 16 columns.  A group's lin columns (p_t + 1 per trait) are packed densely and padded to 16 once (ntl tiles); its quad columns
+// (one d_t per trait) follow, padded to 16 (nt - ntl tiles).  A trait with p_t <= 31 always fits a group of its own.
+#define SPT_MAX_TILES 8
+struct SpectralGroup { long t0, t1; int ntl, nt; };
+static inline void spectral_trait_groups(long T, const long* p, int max_tiles, std::vector<SpectralGroup>& out) {
+    out.clear();
+    long t0 = 0, lin = 0;
+    auto close = [&](long t1) { out.push_back({t0, t1, (int)((lin + 15) / 16), (int)((lin + 15) / 16 + (t1 - t0 + 15) / 16)}); };
+    for (long t = 0; t < T; t++) {
+        const long lin2 = lin + p[t] + 1;
+        if (t > t0 && (lin2 + 15) / 16 + (t - t0 + 1 + 15) / 16 > max_tiles) {
+            close(t);
+            t0 = t;
+            lin = p[t] + 1;
+        } else {
+            lin = lin2;
+        }
+    }
+    if (T > 0) close(T);
+}
+// What k_spectral_finish_traits needs of trait t: its lin columns [off, off + p] and quad column qcol in the pass output of its
+// group, C (p x p, row-major) and c1 (p) at par + poff, varG.
+struct SpectralTraitDesc { int off, p, qcol, t; long poff; double varG; };
+
 // selected_loci rule (calculateMMt_rcpp.cpp:88; calculate_a_and_vara_rcpp.cpp:79; calculate_reduced_a_rcpp.cpp:74): masking fires
 // iff element 0 is not NA (NA arrives as NaN).  Returns nullptr, or the message of the argument error.
 static inline const char* parse_selected_core(const double* sel, long nsel, long bound, std::vector<long>& out) {

@@ -80,8 +80,13 @@ int eagle_spectral_scan_range(eagle_ctx* ctx, const double* d, const double* G, 
 int eagle_dev_extract_col(eagle_ctx* ctx, const int8_t* M8, long n, long ld, long col, int* out, void* stream);
 #ifdef __cplusplus
 }
+#include "eagle_host.h"
 struct eagle_ctx;
 bool eagle_w8_wanted(const eagle_ctx* ctx, long n_pad);
 void eagle_w8_release(eagle_ctx* ctx);
+int eagle_spectral_traits_range(eagle_ctx* ctx, long T, const std::vector<SpectralGroup>& groups, const std::vector<std::vector<double>>& G,
+                                const SpectralTraitDesc* desc, const double* par, long npar, long L_total, double* a_out, double* vara_out,
+                                eagle_best* best);
+int eagle_spectral_rows_range(eagle_ctx* ctx, const long* idx, long k, double* out);
 #endif
 #endif

@@ -15,6 +15,7 @@
 //   k_spectral_scan ..... lin[i][0..p] = z_i^T G (G = [D U^T y | D U^T X]) on v_mfma_f64_16x16x4_f64, quad_i = sum_k z_ik^2 d_k on the VALU,
 //                         one streaming read of Z                                                          (bound: HBM)
 //   k_spectral_finish ... the p x p form per marker, a and vara
+//   k_spectral_scan_traits / k_spectral_finish_traits ... the same for a packed group of traits in one pass over Z, quad on the MFMA
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -189,6 +190,84 @@ __global__ __launch_bounds__(256) void k_spectral_finish(const double* __restric
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// Many traits per pass over Z (eagle_spectral_scan_traits).  The same workgroup shape, Z fragment and k permutation as
+// k_spectral_scan, with NT MFMA tiles of 16 columns: the first ntl take z_i as the A operand against the packed lin columns
+// [d_t o U^T y_t | d_t o U^T X_t] of every trait of the group, the rest take z_i o z_i against the columns d_t, so
+// quad[i][t] = sum_k z_ik^2 d_t[k] runs on the MFMA as well.  out[L_pad][16 NT] row-major.  LDS: two buffers of KC x 16 NT
+// doubles, KC NT <= 512 (128 KiB at NT = 2, 4, 8; the group width is at most SPT_MAX_TILES tiles, eagle_host.h).
+// ---------------------------------------------------------------------------------------------------------------
+template <int NT>
+__global__ __launch_bounds__(1024) void k_spectral_scan_traits(const double* __restrict__ Z, long ldz, long K, const double* __restrict__ G, int ntl,
+                                                               double* __restrict__ out) {
+    constexpr int NC = 16 * NT;
+    constexpr int KC = NT <= 2 ? 256 : (NT <= 4 ? 128 : 64);
+    __shared__ __attribute__((aligned(16))) double ldsG[2][KC * NC];
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int i16 = lane & 15, g = lane >> 4;
+    const long row0 = (long)blockIdx.x * 256 + wv * 16;
+    const double* zrow = Z + (row0 + i16) * ldz + 4 * g;
+    f64x4 acc[NT];
+#pragma unroll
+    for (int n = 0; n < NT; n++) acc[n] = (f64x4){0.0, 0.0, 0.0, 0.0};
+    const long nchunks = K / KC;
+    auto stage = [&](long c, int buf) {
+        const double* src = G + c * KC * NC;
+        for (int e = t * 2; e < KC * NC; e += 2048) *(f64x2*)(&ldsG[buf][e]) = *(const f64x2*)(src + e);
+    };
+    stage(0, 0);
+    __syncthreads();
+    for (long c = 0; c < nchunks; c++) {
+        const int buf = (int)(c & 1);
+        if (c + 1 < nchunks) stage(c + 1, buf ^ 1);
+        const double* zc = zrow + c * KC;
+#pragma unroll 2
+        for (int ks = 0; ks < KC / 16; ks++) {
+            const f64x2 z01 = *(const f64x2*)(zc + ks * 16);
+            const f64x2 z23 = *(const f64x2*)(zc + ks * 16 + 2);
+            const double zz[4] = {z01[0], z01[1], z23[0], z23[1]};
+#pragma unroll
+            for (int s = 0; s < 4; s++) {
+                const int kk = ks * 16 + 4 * g + s;
+                const double zq = zz[s] * zz[s];
+#pragma unroll
+                for (int n = 0; n < NT; n++)
+                    acc[n] = __builtin_amdgcn_mfma_f64_16x16x4f64(n < ntl ? zz[s] : zq, ldsG[buf][kk * NC + n * 16 + i16], acc[n], 0, 0, 0);
+            }
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int n = 0; n < NT; n++)
+#pragma unroll
+        for (int q = 0; q < 4; q++) out[(row0 + g + 4 * q) * NC + n * 16 + i16] = acc[n][q];
+}
+
+// One thread per (marker i, trait blockIdx.y of the group): k_spectral_finish on that trait's columns; a, vara [T][L].
+__global__ __launch_bounds__(256) void k_spectral_finish_traits(const double* __restrict__ lin, int NC, long L, const SpectralTraitDesc* __restrict__ desc,
+                                                                const double* __restrict__ par, double* __restrict__ a, double* __restrict__ vara) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= L) return;
+    const SpectralTraitDesc ds = desc[blockIdx.y];
+    const int p = ds.p;
+    const double* li = lin + i * NC + ds.off;
+    const double* Cm = par + ds.poff;
+    const double* c1 = Cm + (long)p * p;
+    double qc1 = 0.0, qCq = 0.0;
+    for (int j = 0; j < p; j++) {
+        const double qj = li[1 + j];
+        qc1 += qj * c1[j];
+        double r = 0.0;
+        for (int l = 0; l < p; l++) r += Cm[j * p + l] * li[1 + l];
+        qCq += qj * r;
+    }
+    const double quad = lin[i * NC + ds.qcol];
+    const double r = quad - qCq;
+    const bool in_model = !(r > 1e-12 * quad);   // the rule of k_spectral_finish
+    a[(long)ds.t * L + i] = in_model ? 0.0 : ds.varG * (li[0] - qc1);
+    vara[(long)ds.t * L + i] = in_model ? 0.0 : ds.varG * ds.varG * r;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // Entry points
 // ---------------------------------------------------------------------------------------------------------------
 #define SP_LAUNCH_CHECK(ctx, what)                                            \
@@ -226,6 +305,26 @@ extern "C" int eagle_dev_spectral_finish(eagle_ctx* ctx, const double* lin, int 
     if (L <= 0) return EAGLE_OK;
     hipLaunchKernelGGL(k_spectral_finish, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, (hipStream_t)stream, lin, NC, quad, L, (int)p, Cm, c1, varG, a, vara);
     SP_LAUNCH_CHECK(ctx, "k_spectral_finish");
+    return EAGLE_OK;
+}
+
+extern "C" int eagle_dev_spectral_pass_traits(eagle_ctx* ctx, const double* Z, long L_pad, long n_pad, const double* G, int nt, int ntl, double* out,
+                                              void* stream) {
+    if (L_pad % 256 || n_pad % 256 || nt < 2 || nt > SPT_MAX_TILES || ntl < 1 || ntl >= nt)
+        return eagle_fail(ctx, EAGLE_ERR_ARG, "spectral_pass_traits: layout contract violated");
+    if (L_pad == 0) return EAGLE_OK;
+    const dim3 grid((unsigned)(L_pad / 256));
+    hipStream_t s = (hipStream_t)stream;
+    switch (nt) {
+        case 2: hipLaunchKernelGGL((k_spectral_scan_traits<2>), grid, dim3(1024), 0, s, Z, n_pad, n_pad, G, ntl, out); break;
+        case 3: hipLaunchKernelGGL((k_spectral_scan_traits<3>), grid, dim3(1024), 0, s, Z, n_pad, n_pad, G, ntl, out); break;
+        case 4: hipLaunchKernelGGL((k_spectral_scan_traits<4>), grid, dim3(1024), 0, s, Z, n_pad, n_pad, G, ntl, out); break;
+        case 5: hipLaunchKernelGGL((k_spectral_scan_traits<5>), grid, dim3(1024), 0, s, Z, n_pad, n_pad, G, ntl, out); break;
+        case 6: hipLaunchKernelGGL((k_spectral_scan_traits<6>), grid, dim3(1024), 0, s, Z, n_pad, n_pad, G, ntl, out); break;
+        case 7: hipLaunchKernelGGL((k_spectral_scan_traits<7>), grid, dim3(1024), 0, s, Z, n_pad, n_pad, G, ntl, out); break;
+        default: hipLaunchKernelGGL((k_spectral_scan_traits<8>), grid, dim3(1024), 0, s, Z, n_pad, n_pad, G, ntl, out); break;
+    }
+    SP_LAUNCH_CHECK(ctx, "k_spectral_scan_traits");
     return EAGLE_OK;
 }
 
@@ -379,6 +478,69 @@ extern "C" int eagle_spectral_scan_range(eagle_ctx* ctx, const double* d, const 
     }
     HIPCHK(ctx, hipMemcpyAsync(a_out + m0, da.p, sizeof(double) * L, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(vara_out + m0, dv.p, sizeof(double) * L, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return EAGLE_OK;
+}
+
+// One device's share of eagle_spectral_scan_traits: one pass over its shard of Z per column group, the finish of every trait of the
+// group, then the per-trait arg-max of tsq on the device.  G[g]: group g's packed columns (n_pad x 16 nt row-major, eagle_api.cpp);
+// desc: T trait descriptors, par: the C / c1 blocks they point into.  best[t]: the shard's maximum with a GLOBAL marker index (-1:
+// every tsq NaN or an empty shard); a_out / vara_out (L_total x T column-major) get the shard's rows, or are both NULL.
+int eagle_spectral_traits_range(eagle_ctx* ctx, long T, const std::vector<SpectralGroup>& groups, const std::vector<std::vector<double>>& G,
+                                const SpectralTraitDesc* desc, const double* par, long npar, long L_total, double* a_out, double* vara_out,
+                                eagle_best* best) {
+    for (long t = 0; t < T; t++) { best[t].tsqmax = 0.0; best[t].index0 = -1; best[t].near_ties = 0; }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const long L = ctx->z_L, n = ctx->z_n, m0 = ctx->z_first;
+    if (L <= 0) return EAGLE_OK;
+    const long np = eagle_pad(n), Lp = eagle_pad(L);
+    int ncmax = 0;
+    for (auto& gr : groups) ncmax = gr.nt * 16 > ncmax ? gr.nt * 16 : ncmax;
+    DevBuf dG, dout, ddesc, dpar, da, dv, dws;
+    HIPCHK(ctx, dG.alloc(sizeof(double) * (size_t)np * ncmax));
+    HIPCHK(ctx, dout.alloc(sizeof(double) * (size_t)Lp * ncmax));
+    HIPCHK(ctx, ddesc.alloc(sizeof(SpectralTraitDesc) * T));
+    HIPCHK(ctx, dpar.alloc(sizeof(double) * npar));
+    HIPCHK(ctx, da.alloc(sizeof(double) * (size_t)L * T));
+    HIPCHK(ctx, dv.alloc(sizeof(double) * (size_t)L * T));
+    HIPCHK(ctx, dws.alloc(sizeof(double) * 3 * 1024 + sizeof(eagle_best) * T));
+    HIPCHK(ctx, hipMemcpyAsync(ddesc.p, desc, sizeof(SpectralTraitDesc) * T, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(dpar.p, par, sizeof(double) * npar, hipMemcpyHostToDevice, ctx->stream));
+    hipStream_t s = ctx->stream;
+    for (size_t k = 0; k < groups.size(); k++) {
+        const SpectralGroup& gr = groups[k];
+        const int NC = 16 * gr.nt;
+        if (G[k].size() != (size_t)np * NC) return eagle_fail(ctx, EAGLE_ERR_ARG, "spectral_scan_traits: bad column group");
+        HIPCHK(ctx, hipMemcpyAsync(dG.p, G[k].data(), sizeof(double) * (size_t)np * NC, hipMemcpyHostToDevice, s));
+        double* od = dout.as<double>();
+        int rc = eagle_dev_spectral_pass_traits(ctx, ctx->d_Z, Lp, np, dG.as<double>(), gr.nt, gr.ntl, od, s);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_spectral_finish_traits, dim3((unsigned)((L + 255) / 256), (unsigned)(gr.t1 - gr.t0)), dim3(256), 0, s, od, NC, L,
+                           ddesc.as<SpectralTraitDesc>() + gr.t0, dpar.as<double>(), da.as<double>(), dv.as<double>());
+        SP_LAUNCH_CHECK(ctx, "k_spectral_finish_traits");   // dG and dout are reused by the next group: stream order protects them
+    }
+    eagle_best* dbest = (eagle_best*)(dws.as<double>() + 3 * 1024);
+    for (long t = 0; t < T; t++) {
+        int rc = eagle_dev_tsq_argmax(ctx, da.as<double>() + t * L, dv.as<double>() + t * L, L, nullptr, dbest + t, dws.as<double>(), s);
+        if (rc) return rc;
+    }
+    HIPCHK(ctx, hipMemcpyAsync(best, dbest, sizeof(eagle_best) * T, hipMemcpyDeviceToHost, s));
+    if (a_out) {
+        HIPCHK(ctx, hipMemcpy2DAsync(a_out + m0, sizeof(double) * L_total, da.p, sizeof(double) * L, sizeof(double) * L, T, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipMemcpy2DAsync(vara_out + m0, sizeof(double) * L_total, dv.p, sizeof(double) * L, sizeof(double) * L, T, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    for (long t = 0; t < T; t++) if (best[t].index0 >= 0) best[t].index0 += m0;
+    return EAGLE_OK;
+}
+
+// U^T m_j of the markers idx[] this device holds: rows of its shard of Z, n each, to out[j * n] (n x k column-major).
+int eagle_spectral_rows_range(eagle_ctx* ctx, const long* idx, long k, double* out) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const long L = ctx->z_L, n = ctx->z_n, m0 = ctx->z_first, np = eagle_pad(n);
+    for (long j = 0; j < k; j++)
+        if (idx[j] >= m0 && idx[j] < m0 + L)
+            HIPCHK(ctx, hipMemcpyAsync(out + j * n, ctx->d_Z + (idx[j] - m0) * np, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return EAGLE_OK;
 }

@@ -24,6 +24,7 @@ from ._lib import EagleError, c_dp, c_lp
 
 _ctx = {}
 _callbacks = {}
+_spectral_n = {}   # device -> n of the Z its last spectral_prepare made
 
 
 def context(device=0):
@@ -50,6 +51,7 @@ def close_all():
     _ctx.clear()
     _views.clear()
     _callbacks.clear()
+    _spectral_n.clear()
 
 
 def _check(ctx, rc, soft_ok=False):
@@ -243,7 +245,9 @@ def spectral_prepare(f_name_ascii, dims, U, max_memory_in_Gbytes=8.0, device=0):
     n = int(dims[1])
     if Um.shape != (n, n):
         raise ValueError("U must be n x n")
+    _spectral_n.pop(device, None)
     _check(ctx, L.eagle_spectral_prepare(ctx, os.fsencode(f_name_ascii), _dims(dims), _dp(Um), float(max_memory_in_Gbytes)))
+    _spectral_n[device] = n
 
 
 def spectral_scan(lam, UtX, Uty, varE, varG, n_markers, selected_loci=np.nan, device=0):
@@ -259,6 +263,61 @@ def spectral_scan(lam, UtX, Uty, varE, varG, n_markers, selected_loci=np.nan, de
     v_out = np.zeros(int(n_markers))
     _check(ctx, L.eagle_spectral_scan(ctx, _dp(lam), _dp(UtX), _dp(Uty), p, float(varE), float(varG), sp, ns, _dp(a_out), _dp(v_out)))
     return {"a": a_out.reshape(-1, 1), "vara": v_out.reshape(-1, 1)}
+
+
+def spectral_traits_passes(p):
+    """eagle_spectral_traits_passes: passes over Z one spectral_scan_traits call makes for traits with these p[t] columns."""
+    pv = np.ascontiguousarray(np.atleast_1d(p), dtype=np.int64)
+    rc = _lib.load().eagle_spectral_traits_passes(pv.size, pv.ctypes.data_as(c_lp))
+    if rc < 0:
+        raise ValueError("1 <= p[t] <= 31 and at least one trait")
+    return rc
+
+
+def _cols(a, n):
+    a = np.asarray(a, dtype=np.float64)
+    return _f64F(a.reshape(n, -1) if a.size else np.zeros((n, 0)))
+
+
+def spectral_scan_traits(lam, UtX_list, UtY, varE, varG, n_markers, full=False, device=0):
+    """eagle_spectral_scan_traits: T traits from as few passes over Z as the column groups allow (include/eagle_hip.h section 1d).
+    UtX_list: T arrays n x p_t, UtY: n x T, varE / varG: T each.  Returns index (T, 1-based arg-max of tsq, 0 = every tsq NaN) and
+    tsqmax (T); with full=True also a and vara (n_markers x T)."""
+    L = _lib.load()
+    ctx = context(device)
+    lam = _f64F(np.ravel(lam))
+    n = lam.size
+    UtY = _cols(UtY, n)
+    T = UtY.shape[1]
+    UtX = [_cols(x, n) for x in UtX_list]
+    if len(UtX) != T:
+        raise ValueError("one U^T X per trait")
+    p = np.array([x.shape[1] for x in UtX], dtype=np.int64)
+    ptrs = (c_dp * max(T, 1))(*[_dp(x) for x in UtX])
+    vE = np.ascontiguousarray(np.broadcast_to(np.asarray(varE, dtype=np.float64), (T,)))
+    vG = np.ascontiguousarray(np.broadcast_to(np.asarray(varG, dtype=np.float64), (T,)))
+    idx = np.zeros(max(T, 1), dtype=np.int64)
+    mx = np.zeros(max(T, 1))
+    a_out = np.zeros((int(n_markers), T), order="F") if full else None
+    v_out = np.zeros((int(n_markers), T), order="F") if full else None
+    _check(ctx, L.eagle_spectral_scan_traits(ctx, T, _dp(lam), ptrs, p.ctypes.data_as(c_lp), _dp(UtY), _dp(vE), _dp(vG),
+                                             _dp(a_out) if full else None, _dp(v_out) if full else None,
+                                             idx.ctypes.data_as(c_lp), _dp(mx)))
+    res = {"index": idx[:T], "tsqmax": mx[:T]}
+    if full:
+        res["a"], res["vara"] = a_out, v_out
+    return res
+
+
+def spectral_rows(idx, device=0):
+    """eagle_spectral_rows: U^T m_j of the markers idx (0-based) from the resident Z, n x k."""
+    L = _lib.load()
+    ctx = context(device)
+    iv = np.ascontiguousarray(np.atleast_1d(idx), dtype=np.int64)
+    n = _spectral_n.get(device, 0)
+    out = np.zeros((n, iv.size), order="F")
+    _check(ctx, L.eagle_spectral_rows(ctx, iv.ctypes.data_as(c_lp), iv.size, _dp(out)))
+    return out
 
 
 def calculate_reduced_a_rcpp(f_name_ascii, varG, P, y, max_memory_in_Gbytes, dims, selected_loci, quiet=True,

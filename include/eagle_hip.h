@@ -297,6 +297,19 @@ int eagle_spectral_prepare(eagle_ctx* ctx, const char* f_name_ascii, const long 
  * selected_loci: the reference's masking rule (element 0 NA: none). */
 int eagle_spectral_scan(eagle_ctx* ctx, const double* lambda, const double* UtX, const double* Uty, long p, double varE, double varG,
                         const double* selected_loci, long n_selected, double* a_out, double* vara_out);
+/* T traits over the Z of the last eagle_spectral_prepare, in as few passes over Z as the column groups allow (whole traits packed
+ * into at most 128 MFMA columns: p[t] + 1 per trait plus one per trait for sum_k z_ik^2 d_t[k]; eagle_spectral_traits_passes).
+ * UtX[t]: n x p[t] column-major (1 <= p[t] <= 31), Uty: n x T column-major, varE/varG: T each.  a_out, vara_out: L x T
+ * column-major, the values T eagle_spectral_scan calls return (no selected_loci masking), or both NULL (then only the arg-max
+ * crosses PCIe).  index_out: T 1-based arg-max indices of tsq = a^2/vara, first index of the maximum, NaN skipped (0 = every
+ * tsq NaN); tsqmax_out: T values (may be NULL).  EAGLE_ERR_ARG with a message: no prepare, T < 1, p[t] outside 1..31,
+ * varE + varG lambda <= 0, X^T H^-1 X not positive definite. */
+int eagle_spectral_scan_traits(eagle_ctx* ctx, long T, const double* lambda, const double* const* UtX, const long* p, const double* Uty,
+                               const double* varE, const double* varG, double* a_out, double* vara_out, long* index_out, double* tsqmax_out);
+/* Passes over Z eagle_spectral_scan_traits makes for these p[0..T-1] (EAGLE_ERR_ARG for T < 1 or a p[t] outside 1..31). */
+int eagle_spectral_traits_passes(long T, const long* p);
+/* U^T m_j for k markers (0-based idx): the rows of the resident Z, n x k column-major -- the U^T X column a pick adds. */
+int eagle_spectral_rows(eagle_ctx* ctx, const long* idx, long k, double* out);
 
 /* Replaces the R tail of .find_qtl:  tsq <- a^2/vara ; which(tsq == max(tsq, na.rm=TRUE))[1]
  *                                                E/R/find_qtl.R:71-83
@@ -544,6 +557,10 @@ int eagle_dev_spectral_zbuild_i8(eagle_ctx* ctx, const int8_t* Mt8, long L_pad, 
                                  int nslices, void* stream);
 int eagle_dev_spectral_pass(eagle_ctx* ctx, const double* Z, long L_pad, long n_pad, const double* G, int NC, const double* d, double* lin,
                             double* quad, void* stream);
+/* The pass of eagle_spectral_scan_traits for one column group: out[L_pad][16 nt] = Z G with the A operand z_i in the first ntl
+ * tiles of 16 columns and z_i o z_i in the rest (2 <= nt <= 8, 1 <= ntl < nt); G [n_pad][16 nt] row-major. */
+int eagle_dev_spectral_pass_traits(eagle_ctx* ctx, const double* Z, long L_pad, long n_pad, const double* G, int nt, int ntl, double* out,
+                                   void* stream);
 int eagle_dev_spectral_finish(eagle_ctx* ctx, const double* lin, int NC, const double* quad, long L, long p, const double* Cm, const double* c1,
                               double varG, double* a, double* vara, void* stream);
 /* zero a[i], vara[i] at the listed rows (row masking of calculate_a_and_vara_rcpp.cpp:79-84: a zeroed
