@@ -19,7 +19,7 @@ published zeroin algorithm, not from R's source.
 import math
 
 import numpy as np
-from scipy.special import gammaln
+from scipy.special import chdtr, gammaln
 
 from . import host_model
 
@@ -342,6 +342,11 @@ class SpectralBackend(HipBackend):
         self.rcpp_api.spectral_prepare(geno["asciifileMt"], (self.L, n), self.U, availmemGb, device=self.device)
         return MMt
 
+    @property
+    def eig(self):
+        """(lam, U) of the last run's K, what r_api.SummaryAM(..., eig=) takes instead of its own eigh; None before a run."""
+        return None if self.U is None else (self.lam, self.U)
+
     def find_qtl(self, geno, availmemGb, selected_loci, MMt, invMMt, best_ve, best_vg, currentX, ncpu, quiet, trait):
         res = self.rcpp_api.spectral_scan(self.lam, self.U.T @ currentX, self.U.T @ np.ravel(trait), best_ve, best_vg, self.L,
                                           selected_loci, device=self.device)
@@ -500,4 +505,135 @@ def AM_traits(Y, X, geno, availmemGb=8, maxit=20, quiet=True, message=None, alge
             ext = [v for i, v in enumerate(s["ext"]) if i != len(s["sel"]) - 1]
         out.append({"selected_loci": loci, "all_picks": picks, "extBIC": ext, "extBIC_trace": list(s["ext"]), "ve": s["best"].get("ve"),
                     "vg": s["best"].get("vg"), "indxNA": indxNA, "dim_of_ascii_M": list(geno["dim_of_ascii_M"])})
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# SummaryAM (E/R/summary_am.R:78-221) in the eigenbasis of K.  Every model of summary_am.R uses K = MMt/max(MMt) + 0.95 I
+# (.calcMMt, :140) or K'' = K/max(K) + 0.05 I (:186): with K = U diag(lam) U^T both share U, K'' having lam'' = lam/max(K) + 0.05.
+# So with F = [X | m_j1 .. m_jk] (constructX, :131-137), Ft = U^T F and ut = U^T y:
+#     H^-1 = U diag(D) U^T, D = 1/(vg lam + ve)   ->   F^T H^-1 F = Ft^T D Ft = A,   F^T H^-1 y = Ft^T D ut     (:149-151)
+#     W_j = beta_j^2 / (A^-1)_jj                                                                                   (:155-159)
+# and emma.REMLE (:143) / the k + 1 emma.MLE fits (:188, :205) are emma_REMLE_eig / emma_MLE_eig on leading column blocks of Ft.
+# One eigh of K (none when the caller holds lam, U) instead of solve(H) and 2k + 3 n x n eigen() calls.
+# ---------------------------------------------------------------------------------------------------------------------------
+_SUMMARY_NONE = (" No significant marker-trait associations have been found by AM. \n", " Nothing to summarize. \n")   # :117-121
+
+
+def _summary_names(q, xnames, map, L):
+    """colnames of baseX (xnames; default "intercept", "X2", ...) and a function j (1-based) -> marker name: map's names (a
+    sequence of L names, or a mapping with an "SNP" entry), by default M1 .. ML as summary_am.R:106-114."""
+    xn = ["intercept"] + ["X%d" % j for j in range(2, q + 1)] if xnames is None else [str(v) for v in xnames]
+    if len(xn) != q:
+        raise ValueError("SummaryAM: %d xnames for %d columns of X" % (len(xn), q))
+    if map is None:
+        return xn, lambda j: "M%d" % j
+    snp = list(map["SNP"]) if hasattr(map, "keys") else list(map)
+    if len(snp) != L:
+        raise ValueError("SummaryAM: map names %d markers, the genotypes hold %d" % (len(snp), L))
+    return xn, lambda j: str(snp[j - 1])
+
+
+def _summary_eig(lam, maxK, Ft, ut, q, names, say):
+    """summary_am.R:142-217 from lam (eigenvalues of K), max(K), Ft = U^T [X | m_j1 .. m_jk] (n x (q + k)) and ut = U^T y."""
+    lam = np.ascontiguousarray(lam, dtype=np.float64).ravel()
+    n, p = Ft.shape
+    eR = emma_REMLE_eig(lam, Ft, ut, llim=-100, ulim=100)                                         # :143
+    D = 1.0 / (eR["vg"] * lam + eR["ve"])                                                          # :149-150
+    FD = Ft * D[:, None]
+    Ainv = np.linalg.inv(Ft.T @ FD)
+    beta = Ainv @ (FD.T @ ut)                                                                      # :151
+    W = beta * beta / np.diag(Ainv)                                                                # :157-159
+    pval = 1.0 - chdtr(1, W)                                                                       # :160, 1 - pchisq(W, 1)
+    say(" ~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~ \n")
+    say("     Size and Significance of Effects in Final Model    \n")
+    say(" ~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~ \n")
+    say("%15s  %10s  %10s \n" % ("Name", "Additive effect", "p-value"))
+    for nm, b, pv in zip(names, beta, pval):
+        say("%15s  %10f         %.3E\n" % (nm, b, pv))
+    say("\n\n\n")
+    lam2 = lam / maxK + 0.05                                                                       # :186
+    base = emma_MLE_eig(lam2, Ft[:, :q], ut, llim=-100, ulim=100)["ML"]                            # :188
+    say(" ~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~ \n")
+    say(" Proportion of Phenotype Variance Explained by Multiple-locus \n")
+    say("             Association Mapping Model \n")
+    say("  Marker loci which were found by AM() are added one at a time    \n")
+    say(" ~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~~ \n")
+    say("   %15s      %10s \n" % ("Marker name", "Proportion"))
+    rnames, rsq = [], []
+    for k in range(q + 1, p + 1):                                                                  # :200-211
+        full = emma_MLE_eig(lam2, Ft[:, :k], ut, llim=-100, ulim=100)["ML"]
+        rsq.append(1.0 - math.exp(-2.0 / n * (full - base)))
+        say("  %+15s          %.3f\n" % ("+  " + names[k - 1], rsq[-1]))
+        rnames.append("+ " + names[k - 1])
+    pval = [float(v) for v in pval]
+    return {"pvalue": {"effects": list(names), "p_value": pval, "W": [float(v) for v in W]},
+            "size": {"effect_names": list(names), "estimate": [float(v) for v in beta], "p_value": list(pval)},
+            "R": {"Marker_name": rnames, "Prop_var_explained": rsq}}
+
+
+def _summary_K(backend, geno, availmemGb, eig):
+    """K by calcMMt with selected_loci = NA (summary_am.R:140; the masking never fires), max(K), and lam, U: eig
+    when given, else one eigh of K."""
+    n = geno["dim_of_ascii_M"][0]
+    K = backend.calcMMt(geno, availmemGb, 1, np.array([np.nan]), True)
+    maxK = float(np.max(K))
+    if eig is None:
+        lam, U = host_model.algebra().eigh(K)
+    else:
+        lam, U = eig
+        if np.size(lam) != n or np.shape(U) != (n, n):
+            raise ValueError("SummaryAM: eig holds %d eigenvalues, the genotypes %d individuals" % (np.size(lam), n))
+    return maxK, np.ascontiguousarray(lam, dtype=np.float64).ravel(), U
+
+
+def SummaryAM_traits(results, Y, X, geno, map=None, xnames=None, availmemGb=8, eig=None, backend=None, message=None, device=0):
+    """r_api.SummaryAM for every entry of AM_traits(Y, X, geno)'s result, with one calcMMt and one eigh (none with eig=) for
+    all traits.  The rows are AM_traits': a row with NaN in any trait or in X is dropped for all traits (backend.reshape, or
+    reshape_geno writing files for a backend without one).  The marker columns of U^T F come from the resident Z (spectral_rows)
+    when it was made from these genotypes with exactly this U -- the AM_traits run's context still open --, else from one
+    host_model.algebra().mm over the union of all traits' picks.  Returns a list of SummaryAM results (None for a trait with no
+    pick)."""
+    from . import r_api, rcpp_api
+    say = message or (lambda *_: None)
+    Y = np.asarray(Y, dtype=np.float64)
+    Y = Y.reshape(Y.shape[0], -1)
+    X = np.asarray(X, dtype=np.float64).reshape(Y.shape[0], -1)
+    if len(results) != Y.shape[1]:
+        raise ValueError("SummaryAM_traits: %d results for %d traits" % (len(results), Y.shape[1]))
+    picks = [[int(j) for j in r["selected_loci"]] for r in results]
+    if not any(picks):
+        for _ in picks:
+            for m in _SUMMARY_NONE:
+                say(m)
+        return [None] * len(picks)
+    backend = backend or HipBackend(device)
+    na_row = np.isnan(Y).any(axis=1) | np.isnan(X).any(axis=1)
+    indxNA = r_api.check_for_NA_in_trait(np.where(na_row, np.nan, 0.0))
+    if indxNA.size:
+        Y, X = Y[~na_row], X[~na_row]
+        geno = backend.reshape(geno, indxNA) if hasattr(backend, "reshape") else reshape_geno(geno, indxNA)
+    n, L = geno["dim_of_ascii_M"]
+    if Y.shape[0] != n:
+        raise ValueError("SummaryAM_traits: %d trait records for %d genotyped individuals" % (Y.shape[0], n))
+    q = X.shape[1]
+    xn, mname = _summary_names(q, xnames, map, L)
+    maxK, lam, U = _summary_K(backend, geno, availmemGb, eig)
+    la = host_model.algebra()
+    UtXY = la.mm(U.T, np.column_stack([X, Y]))
+    union = sorted({j for pk in picks for j in pk})
+    if rcpp_api.spectral_holds(geno["asciifileMt"], U, device=device):
+        UtM = rcpp_api.spectral_rows(np.asarray(union) - 1, device=device)
+    else:
+        UtM = la.mm(U.T, np.column_stack([backend.extract_geno(geno, j).astype(np.float64) for j in union]))
+    col = {j: i for i, j in enumerate(union)}
+    out = []
+    for t, pk in enumerate(picks):
+        if not pk:
+            for m in _SUMMARY_NONE:
+                say(m)
+            out.append(None)
+            continue
+        Ft = np.column_stack([UtXY[:, :q], UtM[:, [col[j] for j in pk]]])
+        out.append(_summary_eig(lam, maxK, Ft, UtXY[:, q + t], q, xn + [mname(j) for j in pk], say))
     return out

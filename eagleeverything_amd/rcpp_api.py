@@ -19,12 +19,13 @@ import os
 
 import numpy as np
 
-from . import _lib
+from . import _lib, host_model
 from ._lib import EagleError, c_dp, c_lp
 
 _ctx = {}
 _callbacks = {}
 _spectral_n = {}   # device -> n of the Z its last spectral_prepare made
+_spectral_key = {}  # device -> (Mt file name, content key of U) of that Z: what spectral_holds compares against
 
 
 def context(device=0):
@@ -52,6 +53,7 @@ def close_all():
     _views.clear()
     _callbacks.clear()
     _spectral_n.clear()
+    _spectral_key.clear()
 
 
 def _check(ctx, rc, soft_ok=False):
@@ -246,8 +248,17 @@ def spectral_prepare(f_name_ascii, dims, U, max_memory_in_Gbytes=8.0, device=0):
     if Um.shape != (n, n):
         raise ValueError("U must be n x n")
     _spectral_n.pop(device, None)
+    _spectral_key.pop(device, None)
     _check(ctx, L.eagle_spectral_prepare(ctx, os.fsencode(f_name_ascii), _dims(dims), _dp(Um), float(max_memory_in_Gbytes)))
     _spectral_n[device] = n
+    _spectral_key[device] = (str(f_name_ascii), host_model._content_key(Um))
+
+
+def spectral_holds(f_name_ascii, U, device=0):
+    """True when `device`'s resident Z is Mt U for this Mt file and exactly this U (same bytes), so that spectral_rows(j) is
+    U^T m_j.  Opens no context."""
+    key = _spectral_key.get(device)
+    return key is not None and key[0] == str(f_name_ascii) and key[1] == host_model._content_key(_f64F(U))
 
 
 def spectral_scan(lam, UtX, Uty, varE, varG, n_markers, selected_loci=np.nan, device=0):
