@@ -768,7 +768,8 @@ extern "C" int eagle_calculateMMt(eagle_ctx* ctx, const char* f_name_ascii, doub
         double p2 = sqrt(4.0 * (double)L * (double)L + 4.0 * max_memory_in_Gbytes * 1e9 / sizeof(double));
         long rows_in_block = (long)((-2.0 * (double)L + p2) / 2.2);
         if (rows_in_block <= 0) return eagle_fail(ctx, EAGLE_ERR_ARG, "availmemGb too small: zero rows per block");
-        if (!quiet) say(ctx, "number of rows in block is %ld", rows_in_block);  // :107
+        say(ctx, "number of rows in block is %ld", rows_in_block);  // :107-112, said whatever `quiet` is
+        say(ctx, " 1 ");
     }
     const int threads = num_cores > 0 ? num_cores : 1;
     const long np = eagle_pad(n);
@@ -1475,8 +1476,12 @@ extern "C" int eagle_calculate_a_and_vara(eagle_ctx* ctx, const char* f_name_asc
         say(ctx, " Increasing maxmemGb would improve performance... \n");
         long rows_in_block = (long)(max_memory_in_Gbytes * 1e9 / (double)(4UL * (unsigned long)n * sizeof(double)));
         if (rows_in_block < 0) {
+            say(ctx, "\n");  // calculate_a_and_vara_rcpp.cpp:134-139, line for line
             say(ctx, "Error:  availmemGb is set to %g", max_memory_in_Gbytes);
             say(ctx, "        Cannot even read in a single row of data into memory.");
+            say(ctx, "        Please increase availmemGb for this data set.");
+            say(ctx, "\n");
+            say(ctx, " multiple_locus_am has terminated with errors\n");
             a_out[0] = 0.0;
             vara_out[0] = 0.0;
             eagle_fail(ctx, EAGLE_SOFT_SENTINEL, "availmemGb: cannot even read in a single row of data into memory");
@@ -1770,7 +1775,12 @@ extern "C" int eagle_calculate_reduced_a(eagle_ctx* ctx, const char* f_name_asci
     }
     if (!(0.0 < max_memory_in_Gbytes)) {
         say(ctx, " Note:  Increasing availmemGb would improve performance... ");
+        say(ctx, "\n");  // calculate_reduced_a_rcpp.cpp:95-100, line for line
         say(ctx, "Error:  availmemGb is set to %g", max_memory_in_Gbytes);
+        say(ctx, "        Cannot even read in a single row of data into memory.");
+        say(ctx, "        Please increase availmemGb for this data set.");
+        say(ctx, "\n");
+        say(ctx, "AM has terminated with errors\n");
         ar_out[0] = 0.0;
         eagle_fail(ctx, EAGLE_SOFT_SENTINEL, "availmemGb: cannot even read in a single row of data into memory");
         return EAGLE_SOFT_SENTINEL;

@@ -6,16 +6,15 @@
  * "port" CPU baseline of bench.py; nothing under eagleeverything_amd/ may call into it.
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg load this library.
  *
- * PARITY STATUS: *** parity unpinned ***
- *   The reference (jcbowden/EagleEverything, Eagle 1.0.3) needs R + Rcpp + RcppEigen, none of
- *   which exist in the build container, so it cannot be compiled or run here, and it ships no
- *   test suite and no recorded expected outputs.  The arithmetic that
- *   lives in third-party code (Eigen dense products via RcppEigen, version unpinned in
- *   DESCRIPTION:42-43) is restated here from its published meaning (C = A*B in IEEE fp64).
- *   What pins this oracle: (i) exact int64 known answers for MM^T on the reference's own demo
- *   genotype files (tests/golden, derived from reference semantics, not from reference output),
- *   (ii) an independent numpy/OpenBLAS restatement (oracle/oracle_np.py) that must agree to
- *   1e-12 relative.  fp64 outputs (a, vara, tsq) therefore carry "parity unpinned".
+ * PARITY STATUS: pinned to the reference's own src/ files built on stand-in headers
+ *   The reference (jcbowden/EagleEverything, Eagle 1.0.3) ships no test suite and no recorded outputs.  Its src/ files
+ *   are compiled unmodified against oracle/refstub/ (a functional stand-in for the part of Rcpp and Eigen they use) into
+ *   oracle/_ref, and tests/test_oracle_vs_reference.py runs this file next to them: control flow, indices, parsing, branch
+ *   rules and texts are pinned; integer outputs exactly, fp64 outputs (a, vara, reduced a) within 4 x the distance of the
+ *   reference's own fp64 build from its long-double build.  What stays unpinned is Eigen's own summation order (restated here
+ *   as C = A*B in IEEE fp64) and all R-level code (eo_normalise_MMt, eo_tsq_argmax).  Also: (i) exact int64 known answers for
+ *   MM^T on the reference's demo genotype files (tests/golden), (ii) an independent numpy/OpenBLAS restatement
+ *   (oracle/oracle_np.py) that must agree to 1e-12 relative.
  *
  * Reference lines followed (E/ = /root/reference/MyPackage/Eagle/):
  *   eo_read_block ............ E/src/ReadBlock.cpp:47-58

@@ -2,7 +2,7 @@
 
 Mirrors the argument order of the reference's exported C++ functions
 (E/src/RcppExports.cpp:9,37,54,73) so parity tests read like calls into the reference.
-parity unpinned: see the header of eagle_oracle.c.
+Pinned by oracle_ref (the reference's own sources on stand-in headers): see the header of eagle_oracle.c.
 """
 import ctypes as C
 import os

@@ -1,5 +1,5 @@
-"""ReshapeM_rcpp (E/src/ReshapeM_rcpp.cpp) in FILES mode, on the host: eagle_reshape_m(NULL, ..., EAGLE_RESHAPE_FILES) against a
-Python restatement of the reference's rewrite, the same writer (csrc/eagle_reshape.h) under ASan + UBSan, and the AM() driver on a
+"""ReshapeM_rcpp (E/src/ReshapeM_rcpp.cpp) in FILES mode, on the host: eagle_reshape_m(NULL, ..., EAGLE_RESHAPE_FILES) against the
+reference's own ReshapeM_rcpp.cpp (oracle/_ref) and a Python restatement of its rewrite, the same writer (csrc/eagle_reshape.h) under ASan + UBSan, and the AM() driver on a
 trait with NaN against the complete-case run.  No GPU needed."""
 import os
 import subprocess
@@ -57,10 +57,22 @@ def _na_sets(n, seed=0):
 
 @pytest.mark.parametrize("case", GOLDEN_CASES)
 def test_files_mode_matches_reference_bytes(tmp_path, case):
+    from oracle import oracle_ref as ref   # the reference's own ReshapeM_rcpp.cpp on the stand-in headers (oracle/_ref)
+    # where no reference checkout was ever built the restatement stands alone, as before; this test never skips
+    assert ref.available() or not ref.sources_present(), "oracle/_ref is not built although the reference sources are present: run build()"
     geno = _pair(tmp_path, case)
     n, L = geno["dim_of_ascii_M"]
     for label, na in _na_sets(n).items():
         exp_m, exp_t, exp_dims = reference_reshape(geno["asciifileM"], geno["asciifileMt"], na)
+        # the reference wants indxNA in decreasing order (ReshapeM_rcpp.cpp:103), this project takes any order
+        if ref.available():
+            assert ref.ReshapeM_rcpp(geno["asciifileM"], geno["asciifileMt"], sorted(na, reverse=True), (n, L)) == exp_dims, label
+            with open(geno["asciifileM"] + "tmp", "rb") as f:
+                assert f.read() == exp_m, label
+            with open(geno["asciifileMt"] + "tmp", "rb") as f:
+                assert f.read() == exp_t, label
+            os.remove(geno["asciifileM"] + "tmp")
+            os.remove(geno["asciifileMt"] + "tmp")
         dims = rcpp_api.ReshapeM_rcpp(geno["asciifileM"], geno["asciifileMt"], na, (n, L))
         assert dims == exp_dims == [n - len(na), L], label
         with open(geno["asciifileM"] + "tmp", "rb") as f:
