@@ -186,6 +186,10 @@ static_assert(sizeof(E2bHeader) == 64, "E2bHeader is the 64-byte file header");
 extern "C" int eagle_dev_pack2b(eagle_ctx* ctx, const int8_t* in, long rows, long cols, long ld_in, uint8_t* out, long row_bytes, void* stream);
 extern "C" int eagle_dev_unpack2b(eagle_ctx* ctx, const uint8_t* raw, long rows, long cols, long stride, int shift, int8_t* out,
                                   long ld_out, int* bad_dev, void* stream);
+// `real` SNP-major .bed rows of ceil(n/4) bytes -> int8 tile (rows x ld, zero beyond real / n), sidecar rows at stride rb16 (or
+// null) and the count of missing genotypes added to *n_missing (or null); k_bed_decode in eagle_kernels.hip.
+extern "C" int eagle_dev_bed_decode(eagle_ctx* ctx, const uint8_t* bed, long real, long rows, long n, int8_t* tile, long ld, uint8_t* packed,
+                                    long rb16, unsigned long long* n_missing, void* stream);
 inline bool eagle_sidecar_enabled() { const char* e = getenv("EAGLE_HIP_SIDECAR"); return !(e && e[0] == '0'); }
 // Whole-file resident copy (loads it if needed); EAGLE_OK, 2 (too large for HBM: stream it) or an error.
 int eagle_get_resident(eagle_ctx* ctx, const char* path, long rows, long cols, double max_mem_gb, int threads, const GenoEntry** out);

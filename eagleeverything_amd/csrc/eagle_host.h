@@ -28,7 +28,7 @@
 enum : size_t {
     EAGLE_SCR_SYM = 0,             // int[2]: k_sym_check's verdict on S and V                      (eagle_kernels.hip)
     EAGLE_SCR_CERT_TOTALS = 256,   // long[4]: certification counters summed over marker blocks      (eagle_api.cpp scan_range)
-    EAGLE_SCR_INGEST = 512,        // u64[2]: first third-allele / first missing position; double: trace  (eagle_ingest.cpp, eagle_linalg.cpp)
+    EAGLE_SCR_INGEST = 512,        // u64[2]: first third-allele / first missing position (ped), missing count (bed); double: trace  (eagle_ingest.cpp, eagle_linalg.cpp)
     EAGLE_SCR_LOADER_BAD = 1024,   // int: invalid characters / codes seen by the tile loaders       (eagle_load.cpp, any stream)
     EAGLE_SCR_SCACHE_FLAG = 2048,  // int: cached S differs from the caller's                        (eagle_api.cpp, load stream)
     EAGLE_SCR_DOT_PARTIALS = 4096, // double[256]: partial sums of eagle_dev_dot_matrices            (eagle_kernels.hip)
@@ -211,6 +211,39 @@ static inline long count_tokens(const char* p, const char* end) {
     while ((p = next_token(p, end, &tok, &len)) != nullptr) n++;
     return n;
 }
+
+// ------------------------------------------------------------------------------------------------
+// PLINK binary genotypes (.bed) in front of the ingestion (eagle_create_ascii_from_bed): 3 header bytes, then in SNP-major mode
+// one row per marker of ceil(n/4) bytes, individual 4b+q at bits 2q of byte b; codes 00 hom A1, 01 missing, 10 het, 11 hom A2.
+// ------------------------------------------------------------------------------------------------
+enum { BED_HEADER_OK = 0, BED_HEADER_SHORT = 1, BED_HEADER_MAGIC = 2, BED_HEADER_INDIVIDUAL_MAJOR = 3, BED_HEADER_MODE = 4 };
+#define BED_HEADER_BYTES 3
+// verdict on the first `got` bytes of the file (got < 3: the file ends inside its header)
+static inline int bed_check_header(const unsigned char* h, long got) {
+    if (got < BED_HEADER_BYTES) return BED_HEADER_SHORT;
+    if (h[0] != 0x6c || h[1] != 0x1b) return BED_HEADER_MAGIC;
+    if (h[2] == 0x00) return BED_HEADER_INDIVIDUAL_MAJOR;
+    return h[2] == 0x01 ? BED_HEADER_OK : BED_HEADER_MODE;
+}
+static inline long bed_row_bytes(long n) { return (n + 3) / 4; }
+static inline long long bed_expected_size(long n, long L) { return BED_HEADER_BYTES + (long long)L * bed_row_bytes(n); }
+// Row stride of the 2-bit sidecar of a text file of `cols` characters per line: the packed bytes padded to 16.
+static inline long sidecar_row_bytes(long cols) { return ((cols + 3) / 4 + 15) / 16 * 16; }
+// Marker windows of the bed ingestion: w markers (a multiple of 256, at least 256, at most L_pad) whose text, w x (n + 1) bytes,
+// fits `text_cap` bytes and whose int8 tile, w x n_pad, obeys `budget` ((size_t)-1: none).  Window k starts at marker k * w and
+// holds `real` markers of the file in `padded` tile rows: the last window reaches L_pad, so that the windows tile the padded image.
+static inline long bed_window_markers(long n, long n_pad, long L_pad, size_t text_cap, size_t budget) {
+    long w = (long)(text_cap / (size_t)(n + 1)) / 256 * 256;
+    if (budget != (size_t)-1) w = std::min(w, (long)(budget / (size_t)n_pad) / 256 * 256);
+    if (w < 256) w = 256;
+    return w > L_pad ? L_pad : w;
+}
+struct BedWindow { long c0, real, padded; };
+static inline BedWindow bed_window(long k, long w, long L, long L_pad) {
+    const long c0 = k * w;
+    return {c0, std::min(w, L - c0), std::min(w, L_pad - c0)};
+}
+static inline long bed_window_count(long w, long L) { return (L + w - 1) / w; }
 
 // ------------------------------------------------------------------------------------------------
 // Byte arithmetic of the genotype loader (eagle_load.cpp).

@@ -5,6 +5,7 @@
 //   eagle_create_M_ascii ...... E/src/createM_ASCII_rcpp.cpp:18-106 -> CreateASCIInospace.cpp:17-163 (text)
 //                                                                   -> CreateASCIInospace_PLINK.cpp:16-249 (PLINK ped)
 //   eagle_create_Mt_ascii ..... E/src/createMt_ASCII_rcpp.cpp:14-247
+//   eagle_create_ascii_from_bed  both of them at once from a PLINK binary .bed file (no counterpart in the reference)
 //
 // The reference tokenises one line at a time through istringstream, and builds Mt.ascii by re-reading M.ascii once per
 // column block.  Here the input is mmap()ed, its lines are indexed and tokenised by `host_threads()` workers straight
@@ -61,6 +62,18 @@ bool map_file(const char* path, MappedFile& m) {
 // parallel_for, LineIndex, index_lines_buf, next_token, count_tokens: eagle_host.h (HIP-free, built under the CPU sanitizers)
 void index_lines(const MappedFile& m, int threads, LineIndex& ix) { index_lines_buf(m.p, m.size, threads, ix); }
 
+bool pread_all(int fd, char* dst, size_t bytes, off_t off, int threads) {
+    std::atomic<bool> ok{true};
+    parallel_for((long)bytes, bytes < ((size_t)8 << 20) ? 1 : threads, [&](long a, long b, int) {
+        while (a < b) {
+            ssize_t r = pread(fd, dst + a, (size_t)(b - a), off + a);
+            if (r <= 0) { ok = false; return; }
+            a += r;
+        }
+    });
+    return ok;
+}
+
 bool pwrite_all(int fd, const char* src, size_t bytes, off_t off, int threads) {
     std::atomic<bool> ok{true};
     parallel_for((long)bytes, bytes < ((size_t)8 << 20) ? 1 : threads, [&](long a, long b, int) {
@@ -85,6 +98,31 @@ void say_head(eagle_ctx* ctx, const MappedFile& m, const LineIndex& ix, long nro
         for (long c = 0; c < ncolsp && (p = next_token(p, e, &tok, &len)) != nullptr; c++) { row.append(tok, (size_t)len); row.push_back(' '); }
         say(ctx, "%s", row.c_str());
     }
+}
+
+// CreateASCIInospace_PLINK.cpp:112-121
+void say_missing_alleles(eagle_ctx* ctx) {
+    say(ctx, "\n");
+    say(ctx, " Warning:  PLINK file contains missing alleles (i.e. 0 or - ) ");
+    say(ctx, "           These missing genotypes should be imputed before running Eagle.");
+    say(ctx, "           As an approximation, AMpus has set these missing genotypes to heterozygotes. ");
+    say(ctx, "           Since Eagle assumes an additive model, heterozygote genotypes do not contribute to the estimation of ");
+    say(ctx, "           the additive effects.  ");
+    say(ctx, "\n");
+}
+
+// createMt_ASCII_rcpp.cpp:227-243
+void say_summary(eagle_ctx* ctx, const char* type, const char* f_name, long n, long L, double max_memory_in_Gbytes) {
+    say(ctx, "\n\n                    Summary of Marker File  ");
+    say(ctx, "                   ~~~~~~~~~~~~~~~~~~~~~~~~   ");
+    say(ctx, " File type:                   %s", type ? type : "");
+    say(ctx, " Reformatted ASCII file name:  %s", f_name);
+    say(ctx, " Number of individuals:        %ld", n);
+    say(ctx, " Number of loci:               %ld", L);
+    say(ctx, " File size (gigabytes):       %g", 3.5 * (double)n * (double)L * 3.0 / 1000000000.0);  // bits_in_int/8 = 31/8 = 3 (integer division)
+    say(ctx, " Available memory (gigabytes): %g", max_memory_in_Gbytes);
+    say(ctx, "\n\n");
+    say(ctx, " The marker file has been Uploaded");
 }
 
 struct RowError {  // first failing row of a chunk (smallest row wins)
@@ -121,7 +159,7 @@ struct SidecarWriter {
     bool open_for(eagle_ctx* c, const char* text_path, long nrows, long ncols, long max_rows_per_call) {
         if (!eagle_sidecar_enabled() || nrows <= 0 || ncols <= 0) return false;
         ctx = c; rows = nrows; cols = ncols; cap_rows = std::max(1L, max_rows_per_call);
-        row_bytes = ((ncols + 3) / 4 + 15) / 16 * 16;
+        row_bytes = sidecar_row_bytes(ncols);
         final_path = std::string(text_path) + ".e2b";
         tmp_path = final_path + ".tmp";
         (void)unlink(final_path.c_str());  // a sidecar of an older text file of that name must not survive a failed run
@@ -136,7 +174,14 @@ struct SidecarWriter {
         if (!active() || nrows <= 0) return EAGLE_OK;
         if (nrows > cap_rows) return eagle_fail(ctx, EAGLE_ERR_ARG, "sidecar: chunk larger than announced");
         int rc = eagle_dev_pack2b(ctx, tile, nrows, cols, ld, dev[b].as<uint8_t>(), row_bytes, ctx->stream);
-        if (rc) return rc;
+        return rc ? rc : fetch(b, nrows);
+    }
+    // for a producer that packs the rows itself (k_bed_decode): where rows of chunk b go on the device (null: no sidecar) ...
+    uint8_t* packed(int b) { return active() ? dev[b].as<uint8_t>() : nullptr; }
+    // ... and, enqueued behind that producer, their copy to pinned buffer b
+    int fetch(int b, long nrows) {
+        if (!active() || nrows <= 0) return EAGLE_OK;
+        if (nrows > cap_rows) return eagle_fail(ctx, EAGLE_ERR_ARG, "sidecar: chunk larger than announced");
         hipError_t e = hipMemcpyAsync(pin[b].p, dev[b].p, (size_t)nrows * row_bytes, hipMemcpyDeviceToHost, ctx->stream);
         return e == hipSuccess ? EAGLE_OK : eagle_fail_hip(ctx, e, "sidecar D2H");
     }
@@ -410,15 +455,7 @@ static int create_M_plink(eagle_ctx* ctx, const char* fname, const char* asciifn
     }
     const bool allele_err = h_flags[0] != ~0ull;
     const unsigned long long stop = allele_err ? h_flags[0] : (err.row >= 0 ? (unsigned long long)err.row * (unsigned long long)L : ~0ull);
-    if (h_flags[1] != ~0ull && h_flags[1] < stop) {                                              // :112-121, printed once
-        say(ctx, "\n");
-        say(ctx, " Warning:  PLINK file contains missing alleles (i.e. 0 or - ) ");
-        say(ctx, "           These missing genotypes should be imputed before running Eagle.");
-        say(ctx, "           As an approximation, AMpus has set these missing genotypes to heterozygotes. ");
-        say(ctx, "           Since Eagle assumes an additive model, heterozygote genotypes do not contribute to the estimation of ");
-        say(ctx, "           the additive effects.  ");
-        say(ctx, "\n");
-    }
+    if (h_flags[1] != ~0ull && h_flags[1] < stop) say_missing_alleles(ctx);                      // :112-121, printed once
     if (allele_err) {                                                                            // :155-161
         const long row = (long)(h_flags[0] / (unsigned long long)L), locus = (long)(h_flags[0] % (unsigned long long)L);
         say(ctx, "\n");
@@ -556,17 +593,7 @@ extern "C" int eagle_create_Mt_ascii(eagle_ctx* ctx, const char* f_name, const c
     rc = flush();
     if (rc) return rc;
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    // createMt_ASCII_rcpp.cpp:227-243
-    say(ctx, "\n\n                    Summary of Marker File  ");
-    say(ctx, "                   ~~~~~~~~~~~~~~~~~~~~~~~~   ");
-    say(ctx, " File type:                   %s", type ? type : "");
-    say(ctx, " Reformatted ASCII file name:  %s", f_name);
-    say(ctx, " Number of individuals:        %ld", n);
-    say(ctx, " Number of loci:               %ld", L);
-    say(ctx, " File size (gigabytes):       %g", 3.5 * (double)n * (double)L * 3.0 / 1000000000.0);  // bits_in_int/8 = 31/8 = 3 (integer division)
-    say(ctx, " Available memory (gigabytes): %g", max_memory_in_Gbytes);
-    say(ctx, "\n\n");
-    say(ctx, " The marker file has been Uploaded");
+    say_summary(ctx, type, f_name, n, L, max_memory_in_Gbytes);
     close(closer.fd);
     closer.fd = -1;  // the text file is final: its size and mtime key the sidecar and the cache entry
     sc.finish(f_name_ascii);
@@ -574,6 +601,199 @@ extern "C" int eagle_create_Mt_ascii(eagle_ctx* ctx, const char* f_name, const c
         int8_t* give = mt.as<int8_t>();
         mt.p = nullptr;
         return eagle_cache_adopt(ctx, f_name_ascii, L, n, L_pad, ldn, give);
+    }
+    return EAGLE_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// PLINK binary (.bed, SNP-major) -> M.ascii + Mt.ascii
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+
+// an output text file: pre-sized when opened, and cut back to nothing unless the call gets as far as finish()
+struct TextOut {
+    int fd = -1;
+    ~TextOut() {
+        if (fd >= 0) { (void)ftruncate(fd, 0); close(fd); }
+    }
+    bool open_sized(const char* path, off_t bytes) {
+        fd = open(path, O_CREAT | O_TRUNC | O_WRONLY, 0644);
+        return fd >= 0 && ftruncate(fd, bytes) == 0;
+    }
+    void finish() { close(fd); fd = -1; }
+};
+
+// Lines [r0, r0 + nrows) of a text file of `cols` characters per line from the rows of an int8 image (`img`: the first of them), with their
+// sidecar rows: encode + pack on the stream into staging buffer k & 1, the pwrite of chunk k - 1 under the device work of chunk k.
+int write_lines_from_image(eagle_ctx* ctx, int fd, const char* path, const int8_t* img, long ld, long r0, long nrows, long cols, long chunk_rows,
+                           SidecarWriter& sc, hipEvent_t* done, int threads) {
+    const long stride = cols + 1;
+    long pend_r = -1, pend_n = 0;
+    int pend_b = 0;
+    auto flush = [&]() -> int {
+        if (pend_r < 0) return EAGLE_OK;
+        hipError_t e = hipEventSynchronize(done[pend_b]);
+        if (e != hipSuccess) return eagle_fail_hip(ctx, e, "hipEventSynchronize");
+        if (!pwrite_all(fd, (const char*)ctx->stage_pin[pend_b], (size_t)pend_n * stride, (off_t)pend_r * stride, threads))
+            return failf(ctx, EAGLE_ERR_OPEN, "ERROR: could not write %s", path);
+        sc.write(pend_b, pend_r, pend_n, threads);
+        pend_r = -1;
+        return EAGLE_OK;
+    };
+    long k = 0;
+    for (long r = 0; r < nrows; r += chunk_rows, k++) {
+        const int b = (int)(k & 1);  // free: chunk k - 2 went to disk while chunk k - 1 was enqueued
+        const long nr = std::min(chunk_rows, nrows - r);
+        int rc = eagle_dev_encode_ascii(ctx, img + r * ld, nr, cols, ld, (uint8_t*)ctx->stage_raw[b], ctx->stream);
+        if (rc) return rc;
+        HIPCHK(ctx, hipMemcpyAsync(ctx->stage_pin[b], ctx->stage_raw[b], (size_t)nr * stride, hipMemcpyDeviceToHost, ctx->stream));
+        rc = sc.pack(b, img + r * ld, nr, ld);
+        if (rc) return rc;
+        HIPCHK(ctx, hipEventRecord(done[b], ctx->stream));
+        rc = flush();
+        if (rc) return rc;
+        pend_r = r0 + r; pend_n = nr; pend_b = b;
+    }
+    return flush();
+}
+
+}  // namespace
+
+// Mt.ascii is the bed file's own order: every marker window is decoded by k_bed_decode into its int8 tile and its sidecar rows, encoded
+// to text and written while the next window is on the device.  M.ascii is the other order, so every window's tile is also transposed
+// into an image of M: the whole of it when it fits (kept as the resident copy), else a band of individuals per PASS over the bed file --
+// the first pass writes Mt.ascii as well, the later ones only decode (or, with Mt resident, transpose from its image) -- and M.ascii
+// and its sidecar are written from the finished image or band in row chunks, in file order, by the same code either way.
+extern "C" int eagle_create_ascii_from_bed(eagle_ctx* ctx, const char* bed_path, const char* f_name_ascii_M, const char* f_name_ascii_Mt,
+                                           double max_memory_in_Gbytes, const long dims[2], int quiet, long* n_missing_out) {
+    if (!ctx || !bed_path || !f_name_ascii_M || !f_name_ascii_Mt || !dims) return EAGLE_ERR_ARG;
+    const long n = dims[0], L = dims[1];
+    if (n <= 0 || L <= 0) return eagle_fail(ctx, EAGLE_ERR_ARG, "create_ascii_from_bed: dims must be positive");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int fdin = open(bed_path, O_RDONLY);
+    if (fdin < 0) return failf(ctx, EAGLE_ERR_OPEN, "ERROR: Could not open  %s", bed_path);
+    struct Closer { int fd; ~Closer() { if (fd >= 0) close(fd); } } closer{fdin};
+    struct stat st;
+    if (fstat(fdin, &st) != 0) return failf(ctx, EAGLE_ERR_OPEN, "ERROR: Could not open  %s", bed_path);
+    unsigned char head[BED_HEADER_BYTES];
+    const ssize_t got = pread(fdin, head, sizeof head, 0);
+    switch (bed_check_header(head, got < 0 ? 0 : (long)got)) {
+        case BED_HEADER_OK: break;
+        case BED_HEADER_INDIVIDUAL_MAJOR:
+            return failf(ctx, EAGLE_ERR_FORMAT, "%s is an individual-major .bed file (third byte 0x00); only SNP-major files are read", bed_path);
+        case BED_HEADER_MODE:
+            return failf(ctx, EAGLE_ERR_FORMAT, "%s: third byte 0x%02x is not a .bed mode (0x01 SNP-major)", bed_path, (unsigned)head[2]);
+        default:
+            return failf(ctx, EAGLE_ERR_FORMAT, "%s is not a PLINK .bed file (it does not start with 0x6c 0x1b)", bed_path);
+    }
+    if ((long long)st.st_size != bed_expected_size(n, L))
+        return failf(ctx, EAGLE_ERR_FORMAT, "%s holds %lld bytes, but %ld markers of %ld individuals take %lld", bed_path, (long long)st.st_size, L,
+                     n, bed_expected_size(n, L));
+
+    const int threads = host_threads();
+    const long rb = bed_row_bytes(n), n_pad = eagle_pad(n), ldn = n_pad, L_pad = eagle_pad(L);
+    const size_t budget = eagle_resident_budget();
+    const long w = bed_window_markers(n, n_pad, L_pad, (size_t)67108864, budget), nwin = bed_window_count(w, L);
+    const long mt_stride = n + 1, bed_off = ((w * mt_stride + 255) / 256) * 256;   // staging buffer: the window's text, then its bed bytes
+    const long m_chunk = std::max(1L, std::min(n, (long)(67108864 / (L + 1))));
+    int rc = eagle_stage_ensure(ctx, std::max((size_t)bed_off + (size_t)w * rb, (size_t)m_chunk * (L + 1)));
+    if (rc) return rc;
+    if (!quiet) { say(ctx, ""); say(ctx, " Reading PLINK binary File  "); say(ctx, ""); say(ctx, " Loading file "); }
+
+    const bool keepMt = fits_resident((size_t)L_pad * ldn);
+    DevBuf mt, mimg;
+    HIPCHK(ctx, mt.alloc(keepMt ? (size_t)L_pad * ldn : (size_t)w * ldn));
+    const bool keepM = fits_resident((size_t)n_pad * L_pad);
+    const long band = keepM ? n_pad : stream_chunk_rows_core(budget, L_pad, n_pad);   // individuals per pass over the bed file
+    HIPCHK(ctx, mimg.alloc((size_t)band * L_pad));
+    hipEvent_t done[2] = {nullptr, nullptr};
+    for (int b = 0; b < 2; b++) HIPCHK(ctx, hipEventCreateWithFlags(&done[b], hipEventDisableTiming));
+    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int b = 0; b < 2; b++) if (e[b]) (void)hipEventDestroy(e[b]); } } evg{done};
+    unsigned long long* d_missing = (unsigned long long*)((char*)eagle_ctx_scratch(ctx) + EAGLE_SCR_INGEST);
+    HIPCHK(ctx, hipMemsetAsync(d_missing, 0, sizeof(unsigned long long), ctx->stream));
+
+    TextOut outM, outMt;
+    if (!outMt.open_sized(f_name_ascii_Mt, (off_t)L * mt_stride)) return failf(ctx, EAGLE_ERR_OPEN, "ERROR: Could not open  %s", f_name_ascii_Mt);
+    if (!outM.open_sized(f_name_ascii_M, (off_t)n * (L + 1))) return failf(ctx, EAGLE_ERR_OPEN, "ERROR: Could not open  %s", f_name_ascii_M);
+    SidecarWriter scM, scMt;
+    (void)scMt.open_for(ctx, f_name_ascii_Mt, L, n, w);
+    (void)scM.open_for(ctx, f_name_ascii_M, n, L, m_chunk);
+    unsigned long long n_missing = 0;
+
+    for (long r0 = 0; r0 < n; r0 += band) {
+        const bool first = r0 == 0;                       // the pass that writes Mt.ascii
+        const bool decode = first || !keepMt;             // later passes find the tiles in Mt's resident image
+        const long bcols = std::min(band, n_pad - r0);    // individuals (padded) of this pass's image of M
+        long pend_c0 = -1, pend_rows = 0;
+        int pend_b = 0;
+        auto flush = [&]() -> int {
+            if (pend_c0 < 0) return EAGLE_OK;
+            hipError_t e = hipEventSynchronize(done[pend_b]);
+            if (e != hipSuccess) return eagle_fail_hip(ctx, e, "hipEventSynchronize");
+            if (!pwrite_all(outMt.fd, (const char*)ctx->stage_pin[pend_b], (size_t)pend_rows * mt_stride, (off_t)pend_c0 * mt_stride, threads))
+                return failf(ctx, EAGLE_ERR_OPEN, "ERROR: could not write %s", f_name_ascii_Mt);
+            scMt.write(pend_b, pend_c0, pend_rows, threads);
+            pend_c0 = -1;
+            return EAGLE_OK;
+        };
+        for (long k = 0; k < nwin; k++) {
+            const int b = (int)(k & 1);
+            const BedWindow bw = bed_window(k, w, L, L_pad);
+            int8_t* tile = mt.as<int8_t>() + (keepMt ? bw.c0 * ldn : 0);
+            if (decode) {
+                if (k >= 2) HIPCHK(ctx, hipEventSynchronize(done[b]));  // window k - 2 has left staging buffer b
+                char* pin = (char*)ctx->stage_pin[b] + bed_off;
+                uint8_t* raw = (uint8_t*)ctx->stage_raw[b] + bed_off;
+                if (!pread_all(fdin, pin, (size_t)bw.real * rb, (off_t)BED_HEADER_BYTES + (off_t)bw.c0 * rb, threads))
+                    return failf(ctx, EAGLE_ERR_FORMAT, "%s: could not read markers %ld to %ld", bed_path, bw.c0 + 1, bw.c0 + bw.real);
+                HIPCHK(ctx, hipMemcpyAsync(raw, pin, (size_t)bw.real * rb, hipMemcpyHostToDevice, ctx->stream));
+                rc = eagle_dev_bed_decode(ctx, raw, bw.real, bw.padded, n, tile, ldn, first ? scMt.packed(b) : nullptr, scMt.row_bytes,
+                                          first ? d_missing : nullptr, ctx->stream);
+                if (rc) return rc;
+            }
+            rc = eagle_dev_transpose_i8(ctx, tile + r0, bw.padded, bcols, ldn, mimg.as<int8_t>() + bw.c0, L_pad, ctx->stream);
+            if (rc) return rc;
+            if (first) {
+                rc = eagle_dev_encode_ascii(ctx, tile, bw.real, n, ldn, (uint8_t*)ctx->stage_raw[b], ctx->stream);
+                if (rc) return rc;
+                HIPCHK(ctx, hipMemcpyAsync(ctx->stage_pin[b], ctx->stage_raw[b], (size_t)bw.real * mt_stride, hipMemcpyDeviceToHost, ctx->stream));
+                rc = scMt.fetch(b, bw.real);
+                if (rc) return rc;
+            }
+            HIPCHK(ctx, hipEventRecord(done[b], ctx->stream));
+            if (first) {
+                rc = flush();  // window k - 1 goes to disk while window k is on the device
+                if (rc) return rc;
+                pend_c0 = bw.c0; pend_rows = bw.real; pend_b = b;
+            }
+        }
+        if (first) {
+            rc = flush();
+            if (rc) return rc;
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            HIPCHK(ctx, hipMemcpy(&n_missing, d_missing, sizeof n_missing, hipMemcpyDeviceToHost));
+            if (n_missing) say_missing_alleles(ctx);
+            outMt.finish();  // Mt.ascii is final: its size and mtime key the sidecar and the cache entry
+            scMt.finish(f_name_ascii_Mt);
+        }
+        rc = write_lines_from_image(ctx, outM.fd, f_name_ascii_M, mimg.as<int8_t>(), L_pad, r0, std::min(band, n - r0), L, m_chunk, scM, done, threads);
+        if (rc) return rc;
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (n_missing_out) *n_missing_out = (long)n_missing;
+    say_summary(ctx, "PLINKbed", f_name_ascii_M, n, L, max_memory_in_Gbytes);
+    outM.finish();
+    scM.finish(f_name_ascii_M);
+    if (keepM) {
+        int8_t* give = mimg.as<int8_t>();
+        mimg.p = nullptr;
+        rc = eagle_cache_adopt(ctx, f_name_ascii_M, n, L, n_pad, L_pad, give);
+        if (rc) return rc;
+    }
+    if (keepMt) {
+        int8_t* give = mt.as<int8_t>();
+        mt.p = nullptr;
+        return eagle_cache_adopt(ctx, f_name_ascii_Mt, L, n, L_pad, ldn, give);
     }
     return EAGLE_OK;
 }

@@ -2123,6 +2123,70 @@ extern "C" int eagle_dev_unpack2b_cols(eagle_ctx* ctx, const uint8_t* raw, long 
 
 
 // ------------------------------------------------------------------------------------------------
+// PLINK binary genotypes (eagle_create_ascii_from_bed): a window of SNP-major .bed rows -> in one pass the int8 tile of Mt, the
+// window's rows of Mt.ascii's 2-bit sidecar, and the number of missing genotypes.
+//   bed    : `real` rows of rb = ceil(n/4) bytes, back to back as they lie in the file; individual 4b+q at bits 2q of byte b,
+//            codes 00 hom A1, 01 missing, 10 het, 11 hom A2.  The reference's rule "missing -> heterozygote"
+//            (CreateASCIInospace_PLINK.cpp:116-129,177-178) makes the genotype digit g = (x & 1) + (x >> 1) per field, which
+//            is the sidecar's code: four bed bytes x give the four sidecar bytes (x & 0x55555555) + ((x >> 1) & 0x55555555).
+//   tile   : rows x ld int8, g - 1; zero for the individuals n .. ld and for the rows real .. rows (what the transpose needs)
+//   packed : real rows at the sidecar's stride rb16 (rb padded to 16), pad fields and pad bytes zero; may be null
+// A lane owns four bed bytes of one row = 16 individuals = one 16-byte store of the tile (store16) and one dword of the sidecar.
+// The source is BYTE-LOADED: rb has no alignment, and re-striding the rows on the host would cost a pread per marker or a second
+// pass over the pinned buffer, while here a wave's 256 source bytes are contiguous (the loads of a wave touch four or five 64-byte
+// lines either way) and the kernel reads a fifth of what it writes.  One atomic per wave for the count.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_bed_decode(const uint8_t* __restrict__ bed, long rb, long real, long rows, long n,
+                                                    int8_t* __restrict__ tile, long ld, uint8_t* __restrict__ packed, long rb16,
+                                                    unsigned long long* __restrict__ n_missing, long lanes_per_row) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    int miss = 0;
+    if (t < rows * lanes_per_row) {
+        const long row = t / lanes_per_row, j = t - row * lanes_per_row, b0 = 4 * j;
+        const long left = row < real ? n - 16 * j : 0;  // individuals of the file among this lane's 16
+        uint32_t x = 0;
+        if (left > 0) {
+            const uint8_t* s = bed + row * rb;
+#pragma unroll
+            for (int q = 0; q < 4; q++)
+                if (b0 + q < rb) x |= (uint32_t)s[b0 + q] << (8 * q);
+            if (left < 16) x &= (1u << (2 * left)) - 1u;  // pad fields of the row's last byte
+        }
+        const uint32_t lo = x & 0x55555555u, hi = (x >> 1) & 0x55555555u;
+        const uint32_t g = lo + hi;
+        miss = __popc(lo & ~hi);
+        uint32_t w[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const uint32_t f = (g >> (8 * k)) & 0xffu;
+            const uint32_t v = (f & 3u) | ((f >> 2) & 3u) << 8 | ((f >> 4) & 3u) << 16 | (f >> 6) << 24;
+            const long valid = left - 4 * k;  // bytes of this word that are individuals of the file
+            const uint32_t m = valid >= 4 ? 0xffffffffu : (valid <= 0 ? 0u : (1u << (8 * valid)) - 1u);
+            w[k] = (((v | 0x80808080u) - 0x01010101u) ^ 0x80808080u) & m;  // g - 1 in every byte, no borrow between bytes
+        }
+        store16(tile + row * ld + 16 * j, 16 * j, ld, w);
+        if (packed && row < real && b0 < rb16) *(uint32_t*)(packed + row * rb16 + b0) = g;
+    }
+    for (int off = 32; off > 0; off >>= 1) miss += __shfl_down(miss, off);
+    if (n_missing && (threadIdx.x & 63) == 0 && miss) atomicAdd(n_missing, (unsigned long long)miss);
+}
+extern "C" int eagle_dev_bed_decode(eagle_ctx* ctx, const uint8_t* bed, long real, long rows, long n, int8_t* tile, long ld, uint8_t* packed,
+                                    long rb16, unsigned long long* n_missing, void* stream) {
+    if (rows <= 0) return EAGLE_OK;
+    if (n <= 0 || real < 0 || real > rows || ld % 16 || n > ld || ((uintptr_t)tile & 15))
+        return eagle_fail(ctx, EAGLE_ERR_ARG, "bed_decode: bad tile shape");
+    if (packed && (rb16 % 16 || rb16 < (n + 3) / 4 || rb16 > ld / 4 || ((uintptr_t)packed & 3)))
+        return eagle_fail(ctx, EAGLE_ERR_ARG, "bed_decode: bad sidecar stride");
+    const long lanes = ld / 16, blocks = (rows * lanes + 255) / 256;
+    if (blocks > 0x7fffffffL) return eagle_fail(ctx, EAGLE_ERR_ARG, "bed_decode: too many rows");
+    hipLaunchKernelGGL(k_bed_decode, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, bed, (n + 3) / 4, real, rows, n, tile, ld, packed,
+                       rb16, n_missing, lanes);
+    LAUNCH_CHECK(ctx);
+    return EAGLE_OK;
+}
+
+
+// ------------------------------------------------------------------------------------------------
 // Small fp64 helpers of the device model algebra (eagle_linalg.cpp).  Matrices are n x n inside a buffer of
 // leading dimension ld; "row-major" below is just the memory order (a symmetric matrix is layout-free).
 // ------------------------------------------------------------------------------------------------

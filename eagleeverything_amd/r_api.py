@@ -127,10 +127,65 @@ def create_ascii(file_genotype, type="text", AA=None, AB=None, BB=None, availmem
     return True
 
 
+def _count_lines(path):
+    """Lines of a text file as getline() counts them: an unterminated tail is a line too."""
+    lines, last = 0, b"\n"
+    with open(path, "rb") as f:
+        for buf in iter(lambda: f.read(1 << 24), b""):
+            lines += buf.count(b"\n")
+            last = buf[-1:]
+    return lines + (last != b"\n")
+
+
+def bed_fileset(filename):
+    """(.bed, .bim, .fam) paths of a PLINK binary fileset named by its .bed file or by the common prefix."""
+    prefix = filename[:-4] if str(filename).lower().endswith(".bed") else str(filename)
+    return prefix + ".bed", prefix + ".bim", prefix + ".fam"
+
+
+def ReadBim(path):
+    """The marker map of a PLINK .bim file (chromosome, name, genetic distance, position, allele 1, allele 2 per line) ->
+    {"SNP": names, "Chr": chromosomes, "Pos": base-pair positions}: usable as map= of SummaryAM / SummaryAM_traits."""
+    out = {"SNP": [], "Chr": [], "Pos": []}
+    with open(path) as f:
+        for ln, line in enumerate(f, 1):
+            t = line.split()
+            if not t:
+                continue
+            if len(t) < 4:
+                raise ValueError("%s line %d: a .bim line has 6 fields, found %d" % (path, ln, len(t)))
+            out["Chr"].append(t[0])
+            out["SNP"].append(t[1])
+            out["Pos"].append(int(t[3]))
+    return out
+
+
+def _read_marker_bed(filename, availmemGb, quiet, outdir, message, device):
+    say = message or (lambda s: None)
+    files = bed_fileset(filename) if filename is not None else (None,) * 3
+    for f, what in zip(files, ("PLINK bed", "PLINK bim", "PLINK fam")):
+        if f is None or not os.path.exists(f):
+            say(" The %s file %s could not be found. " % (what, f))
+            say(" ReadMarker has terminated with errors ")
+            return None
+    bed, bim, fam = (os.path.abspath(f) for f in files)
+    outdir = outdir or os.path.dirname(bed)
+    say(" Getting number of individuals and snp from file ... ")
+    dims = [_count_lines(fam), _count_lines(bim)]
+    say(" Beginning creation of reformatted file ... ")
+    asciiM, asciiMt = os.path.join(outdir, "M.ascii"), os.path.join(outdir, "Mt.ascii")
+    rcpp_api.create_ascii_from_bed(bed, asciiM, asciiMt, availmemGb, dims, quiet, message, device=device)
+    return {"asciifileM": asciiM, "asciifileMt": asciiMt, "dim_of_ascii_M": dims}
+
+
 def ReadMarker(filename=None, type="text", missing=None, AA=None, AB=None, BB=None, availmemGb=16, quiet=True, outdir=None,
                message=None, device=0):
-    """E/R/ReadMarker.R:194-318 -> geno dict {asciifileM, asciifileMt, dim_of_ascii_M} or None (the R list / NULL)."""
+    """E/R/ReadMarker.R:194-318 -> geno dict {asciifileM, asciifileMt, dim_of_ascii_M} or None (the R list / NULL).
+    type="PLINKbed" (not in the reference): `filename` is the .bed file of a PLINK binary fileset or its prefix; n and L are the
+    line counts of the .fam and .bim beside it, the genotypes go through rcpp_api.create_ascii_from_bed."""
     say = message or (lambda s: None)
+    if type == "PLINKbed":
+        return _read_marker_bed(filename, availmemGb, quiet, outdir, message, device)
     if type not in ("text", "PLINK"):                                               # :206-215
         say(' type must be set to "text" or "PLINK". \n')
         say(" ReadMarker has terminated with errors")

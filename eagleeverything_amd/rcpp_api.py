@@ -514,6 +514,18 @@ def createMt_ASCII_rcpp(f_name, f_name_ascii, type, max_memory_in_Gbytes, dims, 
                                         float(max_memory_in_Gbytes), _dims(dims), int(bool(quiet))))
 
 
+def create_ascii_from_bed(bed_path, f_name_ascii_M, f_name_ascii_Mt, max_memory_in_Gbytes, dims, quiet=True, message=None, device=0):
+    """-> number of missing genotypes (coded as heterozygotes).  M.ascii and Mt.ascii, their sidecars and resident images from a
+    SNP-major PLINK .bed file of dims = (n individuals, L markers): eagle_create_ascii_from_bed (include/eagle_hip.h section 1b)."""
+    L = _lib.load()
+    ctx = context(device)
+    _set_message(ctx, message)
+    n_missing = C.c_long(0)
+    _check(ctx, L.eagle_create_ascii_from_bed(ctx, os.fsencode(bed_path), os.fsencode(f_name_ascii_M), os.fsencode(f_name_ascii_Mt),
+                                              float(max_memory_in_Gbytes), _dims(dims), int(bool(quiet)), C.byref(n_missing)))
+    return int(n_missing.value)
+
+
 # ---- SURVEY 8 f-4: the dense model algebra on the device, through the C ABI (opt-in; include/eagle_hip.h section 1c) ----
 def _square_any_order(A):
     """(buffer, transposed): a float64 n x n array usable as a column-major matrix without a copy when it is contiguous in

@@ -62,6 +62,29 @@ def write_geno_pair(dirname, Mt8, stem=""):
     return {"asciifileM": fM, "asciifileMt": fMt, "dim_of_ascii_M": (n, L)}
 
 
+def write_bed(prefix, Mt8, missing=None):
+    """PLINK binary fileset prefix.bed / .bim / .fam of an int8 marker-major matrix (L x n, values -1/0/1 = hom A1 / het / hom A2);
+    `missing`: boolean L x n, genotypes written as the missing code.  SNP-major .bed: 0x6c 0x1b 0x01, then ceil(n/4) bytes per marker,
+    individual 4b+q at bits 2q of byte b, codes 00 hom A1, 01 missing, 10 het, 11 hom A2.  Returns the .bed path."""
+    Mt8 = np.asarray(Mt8, dtype=np.int8)
+    L, n = Mt8.shape
+    lut = np.array([0, 2, 3], dtype=np.uint8)
+    with open(prefix + ".bed", "wb") as f:
+        f.write(b"\x6c\x1b\x01")
+        for r0 in range(0, L, 8192):   # bounded working set at benchmark sizes
+            fields = np.zeros((min(8192, L - r0), (n + 3) // 4 * 4), dtype=np.uint8)
+            fields[:, :n] = lut[Mt8[r0:r0 + 8192] + 1]
+            if missing is not None:
+                fields[:, :n][np.asarray(missing[r0:r0 + 8192], dtype=bool)] = 1
+            fields = fields.reshape(fields.shape[0], -1, 4)
+            f.write((fields[:, :, 0] | fields[:, :, 1] << 2 | fields[:, :, 2] << 4 | fields[:, :, 3] << 6).astype(np.uint8).tobytes())
+    with open(prefix + ".bim", "w") as f:
+        f.writelines("1\tsnp%d\t0\t%d\tA\tB\n" % (j + 1, j + 1) for j in range(L))
+    with open(prefix + ".fam", "w") as f:
+        f.writelines("fam%d ind%d 0 0 0 -9\n" % (i + 1, i + 1) for i in range(n))
+    return prefix + ".bed"
+
+
 def write_sidecar_from_device(lib, ctx, image, rows, cols, path_text, block_rows=32768):
     """Benchmark-size genotype files without writing 8 bits per genotype of text: `<path_text>.e2b`, the 2-bit sidecar the
     converters leave beside every text file (csrc/eagle_ingest.cpp; layout E2bHeader in csrc/eagle_ctx.h), packed from the

@@ -243,6 +243,20 @@ int eagle_create_M_ascii(eagle_ctx* ctx, const char* f_name, const char* f_name_
 int eagle_create_Mt_ascii(eagle_ctx* ctx, const char* f_name, const char* f_name_ascii, const char* type,
                           double max_memory_in_Gbytes, const long dims[2], int quiet);
 
+/* PLINK binary genotypes (no counterpart in the reference, whose PLINK route reads ped text): bed_path is a .bed file in SNP-major
+ * mode -- 0x6c 0x1b 0x01, then one row of ceil(n/4) bytes per marker, individual 4b+q at bits 2q of byte b -- and dims = (n
+ * individuals, L markers), the line counts of its .fam and .bim.  Writes what eagle_create_M_ascii followed by
+ * eagle_create_Mt_ascii leave for the same genotypes: M.ascii (n lines of L characters), Mt.ascii (L lines of n characters), both
+ * sidecars, both resident images when they fit, the summary messages.  Code 00 (homozygous A1) -> '0', 10 (heterozygous) and 01
+ * (missing, the reference's missing -> heterozygote rule of CreateASCIInospace_PLINK.cpp:116-129) -> '1', 11 (homozygous A2) -> '2'.
+ * With any genotype missing, the reference's "PLINK file contains missing alleles" warning is sent once; *n_missing_out (may be
+ * NULL) = their number.  An image of M that does not fit the device (or EAGLE_HIP_MAX_RESIDENT_GB) costs one pass over the bed
+ * file per band of individuals; the files are the same bytes either way.
+ * EAGLE_ERR_OPEN: a file cannot be opened; EAGLE_ERR_FORMAT: not a .bed file, an individual-major one, or a size other than
+ * 3 + L * ceil(n/4); EAGLE_ERR_ARG: n <= 0 or L <= 0.  A failed call leaves neither sidecar and no text file of the full size. */
+int eagle_create_ascii_from_bed(eagle_ctx* ctx, const char* bed_path, const char* f_name_ascii_M, const char* f_name_ascii_Mt,
+                                double max_memory_in_Gbytes, const long dims[2], int quiet, long* n_missing_out);
+
 /* ---------------------------------------------------------------------------------------------
  * 1c. Dense n x n model algebra on the device (OPT-IN: north_star keeps calculateH / calculateP / emma.* on
  *     host LAPACK, and nothing above calls these).  Once the scan takes tens of milliseconds the ~10-15 O(n^3) base-R calls
