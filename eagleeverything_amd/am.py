@@ -12,7 +12,9 @@ Reference lines (E/ = MyPackage/Eagle/):
   emma.eigen.R.wo.Z / L.wo.Z ..... E/R/emma_eigen_R_wo_Z.R:2-21, E/R/emma_eigen_L_wo_Z.R:1-12
   constructX / extract_geno ...... E/R/constructX.R:1-24, E/R/extract_geno.R:1-19
 
-Only the no-Z model is restated: with a Z matrix the reference's own .find_qtl fails (SURVEY.md section 8a, config 5 note).
+With a Z matrix (AM(Zmat=), repeated measures) the variance components and extBIC restate the reference's emma_*_w_Z path in a
+reduced t x t form; its own .find_qtl takes no Z and fails (SURVEY.md section 8a, config 5 note), so the scan of that model is this
+project's definition.
 parity unpinned: the reference records no outputs, and R's uniroot (Brent, tol = eps^0.25) is restated from the
 published zeroin algorithm, not from R's source.
 """
@@ -138,10 +140,14 @@ def _optimise(dLL, logdelta, llim, ulim, esp, ll_fn, dll_fn):
     return math.exp(opt_ld[k]), opt_ll[k]
 
 
-def emma_REMLE(y, X, K, ngrids=100, llim=-10, ulim=10, esp=1e-10, eig_R=None):
+def emma_REMLE(y, X, K, Z=None, ngrids=100, llim=-10, ulim=10, esp=1e-10, eig_R=None, zmodel=None):
+    """Z: None, or the repeated-measures design as ind_of_obs (or the dense 0/1 matrix): the reduced form of _emma_z."""
     n, q = y.size, X.shape[1]
     if np.linalg.det(X.T @ X) == 0:
         return {"REML": 0, "delta": 0, "ve": 0, "vg": 0}
+    if Z is not None or zmodel is not None:
+        r = _emma_z(y, X, K, Z, zmodel, ngrids, llim, ulim, esp, True)
+        return {"REML": r[0], "delta": r[1], "ve": r[2] * r[1], "vg": r[2]}
     if eig_R is None:
         eig_R = emma_eigen_R_wo_Z(K, X)
     lam = eig_R["values"]
@@ -155,10 +161,13 @@ def emma_REMLE(y, X, K, ngrids=100, llim=-10, ulim=10, esp=1e-10, eig_R=None):
     return {"REML": maxLL, "delta": maxdelta, "ve": maxva * maxdelta, "vg": maxva}
 
 
-def emma_MLE(y, X, K, ngrids=100, llim=-10, ulim=10, esp=1e-10, eig_L=None, eig_R=None):
+def emma_MLE(y, X, K, Z=None, ngrids=100, llim=-10, ulim=10, esp=1e-10, eig_L=None, eig_R=None, zmodel=None):
     n = y.size
     if np.linalg.det(X.T @ X) == 0:
         return {"ML": 0, "delta": 0, "ve": 0, "vg": 0}
+    if Z is not None or zmodel is not None:
+        r = _emma_z(y, X, K, Z, zmodel, ngrids, llim, ulim, esp, False)
+        return {"ML": r[0], "delta": r[1], "ve": r[2] * r[1], "vg": r[2]}
     if eig_L is None:
         eig_L = emma_eigen_L_wo_Z(K)
     if eig_R is None:
@@ -284,8 +293,86 @@ def emma_MLE_eig(lam, UtX, Uty, ngrids=100, llim=-10, ulim=10, esp=1e-10):
     return {"ML": r[0], "delta": r[1], "ve": r[2] * r[1], "vg": r[2]}
 
 
-def calcVC(trait, currentX, MMt, eig_R=None):
-    r = emma_REMLE(trait, currentX, MMt, eig_R=eig_R)
+# ---------------------------------------------------------------------------------------------------------------------------
+# emma.REMLE / emma.MLE with a Z matrix (emma_REMLE.R:78-128, emma_MLE.R:58-105) in the reduced form of host_model.ZModel: with
+# lam, U = eigh(D^1/2 K D^1/2) -- lam are the eigenvalues of the reference's non-symmetric K Z^T Z (emma_eigen_L_w_Z.R:8) --,
+# Ut = U^T D^-1/2 Z^T X, ut likewise and Wn the Gram matrix of the rows of [X | y] centred within their individual, H/vg = delta I +
+# Z K Z^T has the eigenvalues lam + delta on t directions and delta on the other n - t, so
+#     A = X^T (H/vg)^-1 X = Ut^T W Ut + Wn_xx / delta,      R = y^T P y = sum w e^2 + [beta; -1]^T Wn [beta; -1] / delta,
+#     log det = sum log(lam + delta) + (n - t) log delta,    tr (H/vg)^-1 = sum w + (n - t) / delta
+# -- the etas.2.sq / delta and (n - t) / delta terms of emma_REMLE.R:92-94.  n is the number of records.  Grid, bracket rule, zeroin
+# and end-point rule are _optimise, as without Z.  The reference's eigen-route takes only t - q of the t eigenvalues of S Z K Z^T S,
+# which is the whole spectrum exactly when every column of X is constant within an individual (X in the column space of Z: the
+# intercept, a per-line covariate, a marker column Z m_j); there this equals it, otherwise this is the likelihood of the model and the
+# reference's route is not.
+# ---------------------------------------------------------------------------------------------------------------------------
+def as_ind_of_obs(Z):
+    """ind_of_obs (0-based int64) from either form of a Z matrix: the vector itself, or the dense n_obs x t 0/1 matrix."""
+    Z = np.asarray(Z)
+    if Z.ndim == 2:
+        from . import r_api
+        return r_api.zmat_index(Z)
+    return Z.astype(np.int64).ravel()
+
+
+def _z_fit(lam, Ut, ut, Wn, delta):
+    q = Ut.shape[1]
+    w = 1.0 / (lam + delta)
+    Uw = Ut * w[:, None]
+    A = Ut.T @ Uw + Wn[:q, :q] / delta
+    beta = np.linalg.solve(A, Uw.T @ ut + Wn[:q, q] / delta)
+    e = ut - Ut @ beta
+    c = np.append(beta, -1.0)
+    rw = max(float(c @ Wn @ c), 0.0)                  # the within-individual residual sum of squares at beta
+    return w, Uw, A, w * e, rw, float(np.sum(w * e * e)) + rw / delta
+
+
+def _z_ll(logdelta, lam, Ut, ut, Wn, n, reml, logdet_xtx):
+    t, q = Ut.shape
+    d = math.exp(logdelta)
+    _, _, A, _, _, R = _z_fit(lam, Ut, ut, Wn, d)
+    m = n - q if reml else n
+    ll = m * (math.log(m / (2 * math.pi)) - 1 - math.log(R)) - np.sum(np.log(lam + d)) - (n - t) * logdelta
+    if reml:
+        ll -= np.linalg.slogdet(A)[1] - logdet_xtx
+    return 0.5 * ll
+
+
+def _z_dll(logdelta, lam, Ut, ut, Wn, n, reml):
+    t, q = Ut.shape
+    d = math.exp(logdelta)
+    w, Uw, A, r, rw, R = _z_fit(lam, Ut, ut, Wn, d)
+    trP = np.sum(w) + (n - t) / d
+    if reml:
+        trP -= np.sum(np.linalg.inv(A) * (Uw.T @ Uw + Wn[:q, :q] / (d * d)))
+    return 0.5 * ((n - q if reml else n) * (np.sum(r * r) + rw / (d * d)) / R - trP)
+
+
+def _emma_z(y, X, K, Z, zmodel, ngrids, llim, ulim, esp, reml):
+    if zmodel is None:
+        ind = as_ind_of_obs(Z)
+        vids = np.bincount(ind, minlength=K.shape[0]) > 0            # complete == FALSE: individuals without a record leave K and Z
+        if not vids.all():
+            K = K[np.ix_(vids, vids)]
+            ind = (np.cumsum(vids) - 1)[ind]
+        zmodel = host_model.ZModel(K, ind)
+    lam = zmodel.lam
+    n = zmodel.n_obs
+    if np.size(y) != n or X.shape[0] != n:
+        raise ValueError("emma with Z: %d records in Z, %d in y, %d rows of X" % (n, np.size(y), X.shape[0]))
+    Ut, ut, Wn = zmodel.reduce(X, y)
+    q = Ut.shape[1]
+    logdet_xtx = np.linalg.slogdet(Ut.T @ Ut + Wn[:q, :q])[1]        # = log det X^T X
+    logdelta, delta = _grid(ngrids, llim, ulim)
+    dLL = np.array([dl * _z_dll(ld, lam, Ut, ut, Wn, n, reml) for ld, dl in zip(logdelta, delta)])
+    maxdelta, maxLL = _optimise(dLL, logdelta, llim, ulim, esp, lambda ld: _z_ll(ld, lam, Ut, ut, Wn, n, reml, logdet_xtx),
+                                lambda ld: _z_dll(ld, lam, Ut, ut, Wn, n, reml))
+    maxva = _z_fit(lam, Ut, ut, Wn, maxdelta)[5] / (n - q if reml else n)
+    return maxLL, maxdelta, maxva
+
+
+def calcVC(trait, currentX, MMt, eig_R=None, Z=None, zmodel=None):
+    r = emma_REMLE(trait, currentX, MMt, Z=Z, eig_R=eig_R, zmodel=zmodel)
     return {"vg": r["vg"], "ve": r["ve"]}
 
 
@@ -293,8 +380,8 @@ def _lchoose(n, k):
     return gammaln(n + 1) - gammaln(k + 1) - gammaln(n - k + 1)
 
 
-def calc_extBIC(trait, currentX, MMt, nmarkers, eig_L=None, eig_R=None):
-    res = emma_MLE(trait, currentX, MMt, llim=-100, ulim=100, eig_L=eig_L, eig_R=eig_R)
+def calc_extBIC(trait, currentX, MMt, nmarkers, eig_L=None, eig_R=None, Z=None, zmodel=None):
+    res = emma_MLE(trait, currentX, MMt, Z=Z, llim=-100, ulim=100, eig_L=eig_L, eig_R=eig_R, zmodel=zmodel)
     BIC = -2 * res["ML"] + (currentX.shape[1] + 1) * math.log(trait.size)
     return BIC + 2 * _lchoose(nmarkers, currentX.shape[1] - 1)
 
@@ -335,6 +422,15 @@ class SpectralBackend(HipBackend):
         self.lam = self.U = None
         self.L = None
 
+    calcMMt_plain = HipBackend.calcMMt    # K alone: what AM(Zmat=) asks for, followed by prepare_z
+
+    def prepare_z(self, geno, zmodel, availmemGb):
+        """Repeated measures: Z~ = Mt (D^1/2 U~ / sqrt(d_max)) for U~ of D^1/2 K D^1/2 (host_model.ZModel), once per run."""
+        self.lam = self.U = None
+        n, self.L = geno["dim_of_ascii_M"]
+        basis, _ = zmodel.spectral_basis()
+        self.rcpp_api.spectral_prepare(geno["asciifileMt"], (self.L, n), basis, availmemGb, device=self.device)
+
     def calcMMt(self, geno, availmemGb, ncpu, selected_loci, quiet):
         MMt = super().calcMMt(geno, availmemGb, ncpu, selected_loci, quiet)
         self.lam, self.U = np.linalg.eigh(MMt)                       # the decomposition emma.REMLE needs anyway
@@ -347,9 +443,14 @@ class SpectralBackend(HipBackend):
         """(lam, U) of the last run's K, what r_api.SummaryAM(..., eig=) takes instead of its own eigh; None before a run."""
         return None if self.U is None else (self.lam, self.U)
 
-    def find_qtl(self, geno, availmemGb, selected_loci, MMt, invMMt, best_ve, best_vg, currentX, ncpu, quiet, trait):
-        res = self.rcpp_api.spectral_scan(self.lam, self.U.T @ currentX, self.U.T @ np.ravel(trait), best_ve, best_vg, self.L,
-                                          selected_loci, device=self.device)
+    def find_qtl(self, geno, availmemGb, selected_loci, MMt, invMMt, best_ve, best_vg, currentX, ncpu, quiet, trait, Zmat=None):
+        if Zmat is not None:   # a host_model.ZModel whose basis prepare_z made resident
+            op = Zmat.spectral_operands(currentX, trait, best_ve, best_vg)
+            res = self.rcpp_api.spectral_scan_weights(op["d"], op["Gy"], op["GX"], op["C"], op["c1"], best_vg, self.L, selected_loci,
+                                                      device=self.device)
+        else:
+            res = self.rcpp_api.spectral_scan(self.lam, self.U.T @ currentX, self.U.T @ np.ravel(trait), best_ve, best_vg, self.L,
+                                              selected_loci, device=self.device)
         with np.errstate(all="ignore"):
             tsq = res["a"].ravel() ** 2 / res["vara"].ravel()
         return int(np.flatnonzero(tsq == np.nanmax(tsq))[0]) + 1         # find_qtl.R:71-83
@@ -363,7 +464,7 @@ def reshape_geno(geno, indxNA, view=False, device=0):
     return {"asciifileM": geno["asciifileM"] + "tmp", "asciifileMt": geno["asciifileMt"] + "tmp", "dim_of_ascii_M": newdims}
 
 
-def AM(trait, X, geno, availmemGb=8, ncpu=1, maxit=20, quiet=True, backend=None, message=None, algebra=None):
+def AM(trait, X, geno, availmemGb=8, ncpu=1, maxit=20, quiet=True, backend=None, message=None, algebra=None, Zmat=None):
     """E/R/AM.R:320-475 for a trait vector and a ready design matrix X (n x q, intercept included).
 
     Individuals whose trait or any column of X is NaN are dropped (AM.R:320-329: an NA covariate makes the trait NA): from trait
@@ -371,7 +472,12 @@ def AM(trait, X, geno, availmemGb=8, ncpu=1, maxit=20, quiet=True, backend=None,
     the backend has no `reshape`).  A trait without NaN makes no such call.
     Returns dict(selected_loci = 1-based marker columns in order of selection, extBIC = list, ve, vg of the last fit, indxNA = the
     dropped rows, 1-based and largest first, and dim_of_ascii_M of the genotypes the loop ran on).
-    selected_loci starts as [NA] exactly like AM.R:260, so the selected_loci masking never fires."""
+    selected_loci starts as [NA] exactly like AM.R:260, so the selected_loci masking never fires.
+
+    Zmat: repeated measures (several records per genotyped individual), as r_api.ReadZmat's matrix or as ind_of_obs
+    (r_api.zmat_index); trait and X then have one row per record -- see _AM_z."""
+    if Zmat is not None:
+        return _AM_z(trait, X, geno, Zmat, availmemGb, ncpu, maxit, quiet, backend, message, algebra)
     backend = backend or HipBackend()
     if algebra is not None:  # "host" (LAPACK, the reference's placement) or "device" (SURVEY 8 f-4: rocSOLVER / the fp64 MFMA GEMM through the C ABI)
         host_model.set_algebra(algebra)
@@ -428,7 +534,99 @@ def AM(trait, X, geno, availmemGb=8, ncpu=1, maxit=20, quiet=True, backend=None,
             "vg": best.get("vg"), "indxNA": indxNA, "dim_of_ascii_M": list(geno["dim_of_ascii_M"])}
 
 
-def AM_traits(Y, X, geno, availmemGb=8, maxit=20, quiet=True, message=None, algebra=None, device=0):
+def _AM_result(selected_loci, extBIC, itnum, maxit, best, indxNA, geno):
+    """AM.R:476-499 (see AM())."""
+    picks = [int(v) for v in selected_loci[1:]]
+    if itnum > maxit or len(selected_loci) <= 1:
+        loci, ext = picks, list(extBIC)
+    else:
+        loci = picks[:-1]
+        ext = [v for i, v in enumerate(extBIC) if i != len(selected_loci) - 1]
+    return {"selected_loci": loci, "all_picks": picks, "extBIC": ext, "extBIC_trace": list(extBIC), "ve": best.get("ve"),
+            "vg": best.get("vg"), "indxNA": indxNA, "dim_of_ascii_M": list(geno["dim_of_ascii_M"])}
+
+
+def _AM_z(trait, X, geno, Zmat, availmemGb, ncpu, maxit, quiet, backend, message, algebra):
+    """AM() for y = X b + Z g + e: trait and X hold one row per RECORD, Zmat says whose record each is.
+
+    Checks as check_inputs_mlam.R:122-145.  A record with NaN in trait or X is dropped (from trait, X and Z; the result's
+    indxNA_obs, 1-based, largest first); an individual left without any record is dropped from the genotypes through
+    backend.reshape (indxNA, as in AM(); the reference's complete == FALSE rule) and the others are renumbered.  Variance
+    components and extBIC are emma_REMLE / emma_MLE with Z, n = the number of records; the scan runs over the t individuals with
+    operands from Z^T P Z and Z^T P y (host_model.scan_operands_z), and a selected marker enters X as Z m_j.  The reference's own
+    AM() cannot run this model (its .find_qtl takes no Z): the scan is this project's definition."""
+    backend = backend or HipBackend()
+    if algebra is not None:
+        host_model.set_algebra(algebra)
+    say = message or (lambda *_: None)
+    trait = np.asarray(trait, dtype=np.float64).ravel().copy()
+    currentX = np.asarray(X, dtype=np.float64)
+    n_ind = int(geno["dim_of_ascii_M"][0])
+    Zm = np.asarray(Zmat)
+    if Zm.ndim == 2 and Zm.shape[1] != n_ind:                                        # check_inputs_mlam.R:124-130
+        raise ValueError("Error: the number of columns specified in the Z matrix file is %d\n"
+                         "       the number of rows specified in the genotype file is %d\n"
+                         "       The number of columns in the Z matrix should be the same as the number of rows in the genotype file."
+                         % (Zm.shape[1], n_ind))
+    if Zm.shape[0] != trait.size:                                                    # check_inputs_mlam.R:139-145
+        raise ValueError("Error: the number of rows specified in the Z matrix file is %d\n"
+                         "       the number of rows specified in the phenotype file is %d\n"
+                         "       The number of rows in the Z matrix file and phenotype file must be the same." % (Zm.shape[0], trait.size))
+    if currentX.shape[0] != trait.size:
+        raise ValueError("AM: %d rows of X for %d trait records" % (currentX.shape[0], trait.size))
+    ind = as_ind_of_obs(Zm)
+    if ind.min() < 0 or ind.max() >= n_ind:
+        raise ValueError("AM: Zmat names individual %d, the genotypes hold %d" % (int(ind.max()) + 1, n_ind))
+    currentX = currentX.reshape(trait.size, -1)
+    trait[np.isnan(currentX).any(axis=1)] = np.nan                                   # AM.R:320-329, per record
+    from . import r_api
+    indxNA_obs = r_api.check_for_NA_in_trait(trait)
+    if indxNA_obs.size:
+        keep = np.ones(trait.size, dtype=bool)
+        keep[indxNA_obs - 1] = False
+        trait, currentX, ind = trait[keep], currentX[keep], ind[keep]
+        say(" The following rows are being removed from pheno due to missing data: %s" % " ".join(str(int(i)) for i in indxNA_obs))
+    has = np.bincount(ind, minlength=n_ind) > 0
+    indxNA = (np.flatnonzero(~has) + 1)[::-1].copy()                                 # individuals, 1-based, largest first
+    if indxNA.size:
+        ind = (np.cumsum(has) - 1)[ind]
+        say(" The following individuals have no record and are being removed from the genotypes: %s" % " ".join(str(int(i)) for i in indxNA))
+        geno = backend.reshape(geno, indxNA) if hasattr(backend, "reshape") else reshape_geno(geno, indxNA)
+    nmarkers = geno["dim_of_ascii_M"][1]
+    selected_loci = [np.nan]
+    new_selected_locus = np.nan
+    extBIC = []
+    itnum, cont = 1, True
+    MMt = zm = None
+    best = {}
+    while cont:
+        say("Iteration %d: Searching for most significant marker-trait association" % itnum)
+        if not (isinstance(new_selected_locus, float) and math.isnan(new_selected_locus)):
+            m = backend.extract_geno(geno, int(new_selected_locus)).astype(np.float64)
+            currentX = np.column_stack([currentX, np.ravel(m)[ind]])                 # Z m_j
+        if itnum == 1:
+            MMt = getattr(backend, "calcMMt_plain", backend.calcMMt)(geno, availmemGb, ncpu, np.array(selected_loci), quiet)
+            zm = host_model.ZModel(MMt, ind)                                         # the one eigh of the run
+            if hasattr(backend, "prepare_z"):
+                backend.prepare_z(geno, zm, availmemGb)
+        best = calcVC(trait, currentX, MMt, zmodel=zm)
+        extBIC.append(calc_extBIC(trait, currentX, MMt, nmarkers, zmodel=zm))
+        if int(np.flatnonzero(np.asarray(extBIC) == min(extBIC))[0]) == len(extBIC) - 1:  # AM.R:448
+            new_selected_locus = backend.find_qtl(geno=geno, availmemGb=availmemGb, selected_loci=np.array(selected_loci), MMt=MMt,
+                                                  invMMt=None, best_ve=best["ve"], best_vg=best["vg"], currentX=currentX,
+                                                  ncpu=ncpu, quiet=quiet, trait=trait, Zmat=zm)
+            selected_loci.append(new_selected_locus)
+        else:
+            cont = False
+        itnum += 1
+        if itnum > maxit:
+            cont = False
+    out = _AM_result(selected_loci, extBIC, itnum, maxit, best, indxNA, geno)
+    out["indxNA_obs"] = indxNA_obs
+    return out
+
+
+def AM_traits(Y, X, geno, availmemGb=8, maxit=20, quiet=True, message=None, algebra=None, device=0, Zmat=None):
     """AM() for the T columns of Y (n x T) with one design matrix X (n x q) on one genotype panel, in one run: calcMMt and
     lam, U = eigh(MM^T) once, Z = Mt U once (spectral_prepare), then the traits in lockstep -- each round one spectral_scan_traits
     call for every trait still running, and per trait emma_REMLE_eig / emma_MLE_eig in the eigenbasis (no n^3 work per trait or
@@ -437,7 +635,12 @@ def AM_traits(Y, X, geno, availmemGb=8, maxit=20, quiet=True, message=None, alge
 
     A row with NaN in ANY trait or in X is dropped for ALL traits (one VIEW reshape of the genotypes): with different NA patterns
     the result differs from separate AM() runs, which drop each trait's own NA rows only.  A pick adds its row of Z (U^T m_j,
-    spectral_rows) to that trait's U^T X."""
+    spectral_rows) to that trait's U^T X.
+
+    Zmat (repeated measures) is not supported here: the per-trait EMMA in the eigenbasis and the batched kernel's own C would need
+    AM(Zmat=)'s within-individual terms.  Run AM(Zmat=) per trait."""
+    if Zmat is not None:
+        raise NotImplementedError("AM_traits: Zmat (repeated measures) is not supported; run AM(Zmat=) for each trait")
     from . import r_api, rcpp_api
     Y = np.asarray(Y, dtype=np.float64)
     Y = Y.reshape(Y.shape[0], -1).copy()

@@ -1810,21 +1810,44 @@ extern "C" int eagle_spectral_prepare(eagle_ctx* ctx, const char* f_name_ascii, 
     ctx->spectral_L = rc ? 0 : L;
     return rc;
 }
+// The one pass / finish / masking sequence behind eagle_spectral_scan and eagle_spectral_scan_weights: d (n_pad, zero padded), G = [Gy | GX]
+// (n_pad x NC row-major, zero padded), C (p x p), c1 (p) ready on the host, every device over its shard of Z.
+static int spectral_scan_operands(eagle_ctx* ctx, const double* d, const double* G, int NC, const double* Cm, const double* c1, long p, double varG,
+                                  const double* selected_loci, long n_selected, double* a_out, double* vara_out) {
+    std::vector<long> sel;
+    int rc = parse_selected(ctx, selected_loci, n_selected, ctx->spectral_L, sel);
+    if (rc) return rc;
+    return run_on_devices(ctx, [&](int, eagle_ctx* c) -> int {
+        return eagle_spectral_scan_range(c, d, G, NC, Cm, c1, p, varG, sel.data(), (long)sel.size(), a_out, vara_out);
+    });
+}
 extern "C" int eagle_spectral_scan(eagle_ctx* ctx, const double* lambda, const double* UtX, const double* Uty, long p, double varE, double varG,
                                    const double* selected_loci, long n_selected, double* a_out, double* vara_out) {
     if (!ctx || !lambda || !UtX || !Uty || !a_out || !vara_out) return EAGLE_ERR_ARG;
     if (ctx->spectral_L <= 0) return eagle_fail(ctx, EAGLE_ERR_ARG, "spectral_scan: eagle_spectral_prepare has not run");
     if (p < 1 || p > 31) return eagle_fail(ctx, EAGLE_ERR_ARG, "spectral_scan: 1 <= p <= 31 fixed-effect columns");
-    const long L = ctx->spectral_L, n = ctx->z_n, np = eagle_pad(n);
-    std::vector<long> sel;
-    int rc = parse_selected(ctx, selected_loci, n_selected, L, sel);
-    if (rc) return rc;
+    const long n = ctx->z_n, np = eagle_pad(n);
     const int NC = p + 1 <= 16 ? 16 : 32;
     std::vector<double> d(np), G((size_t)np * NC), Cm((size_t)p * p), c1(p);
-    if ((rc = eagle_spectral_host_operands(ctx, n, lambda, UtX, Uty, p, varE, varG, NC, d.data(), G.data(), Cm.data(), c1.data()))) return rc;
-    return run_on_devices(ctx, [&](int, eagle_ctx* c) -> int {
-        return eagle_spectral_scan_range(c, d.data(), G.data(), NC, Cm.data(), c1.data(), p, varG, sel.data(), (long)sel.size(), a_out, vara_out);
-    });
+    int rc = eagle_spectral_host_operands(ctx, n, lambda, UtX, Uty, p, varE, varG, NC, d.data(), G.data(), Cm.data(), c1.data());
+    if (rc) return rc;
+    return spectral_scan_operands(ctx, d.data(), G.data(), NC, Cm.data(), c1.data(), p, varG, selected_loci, n_selected, a_out, vara_out);
+}
+// The same scan with the operands made by the caller (a model whose C and c1 hold terms lambda and UtX alone do not give).
+extern "C" int eagle_spectral_scan_weights(eagle_ctx* ctx, const double* d, const double* Gy, const double* GX, long p, const double* C, const double* c1,
+                                           double varG, const double* selected_loci, long n_selected, double* a_out, double* vara_out) {
+    if (!ctx || !d || !Gy || !GX || !C || !c1 || !a_out || !vara_out) return EAGLE_ERR_ARG;
+    if (ctx->spectral_L <= 0) return eagle_fail(ctx, EAGLE_ERR_ARG, "spectral_scan_weights: eagle_spectral_prepare has not run");
+    if (p < 1 || p > 31) return eagle_fail(ctx, EAGLE_ERR_ARG, "spectral_scan_weights: 1 <= p <= 31 fixed-effect columns");
+    const long n = ctx->z_n, np = eagle_pad(n);
+    const int NC = p + 1 <= 16 ? 16 : 32;
+    std::vector<double> dp(np, 0.0), G((size_t)np * NC, 0.0);
+    for (long k = 0; k < n; k++) {
+        dp[k] = d[k];
+        G[(size_t)k * NC] = Gy[k];
+        for (long j = 0; j < p; j++) G[(size_t)k * NC + 1 + j] = GX[j * n + k];
+    }
+    return spectral_scan_operands(ctx, dp.data(), G.data(), NC, C, c1, p, varG, selected_loci, n_selected, a_out, vara_out);
 }
 
 // Many traits over one Z (section 1d).  The per-trait host operands (eagle_spectral_host_operands: d_t, G_t, C_t, c1_t; the

@@ -15,6 +15,8 @@ Reference lines (E/ = MyPackage/Eagle/):
   calculate_reduced_vara ............ E/R/calculate_reduced_vara.R:21-35
 No recorded outputs exist in the reference for any of these: parity unpinned.
 """
+import math
+
 import numpy as np
 import scipy.linalg as sla
 
@@ -204,3 +206,94 @@ def scan_operands(MMt_norm, X, y, varE, varG):
     invMMt = _chol2inv(MMt_norm)  # AM.R:422
     var_hat_a = calculate_reduced_vara(X, varE, varG, invMMt, sq["sqrt_MMt"])
     return {"S": sq["inverse_sqrt_MMt"], "Shalf": sq["sqrt_MMt"], "V": var_hat_a, "ahat": hat_a, "P": P}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Repeated measures: y = X b + Z g + e with n_obs records on t individuals, Z one-hot and held as the
+# vector ind_of_obs, D = Z^T Z = diag(records per individual).  With Kt = D^1/2 K D^1/2 = Ut diag(lam) Ut^T (ONE eigh per run) and
+# Q = Z D^-1/2 (orthonormal columns), Z K Z^T = (Q Ut) diag(lam) (Q Ut)^T, so H = varE I + varG Z K Z^T has the eigenvalues
+# varE + varG lam on the t columns of Q Ut and varE on the n_obs - t dimensional rest.  Every n_obs-sized quantity enters through
+# the segment sums Z^T [X | y] and the Gram matrix of the rows of [X | y] centred within their individual (a sum of squares, not a
+# difference).  No n_obs x n_obs matrix exists anywhere.  The scan of this model has no definition in the reference (its .find_qtl
+# takes no Z): parity unpinned by the reference for the Z scan.
+# ---------------------------------------------------------------------------------------------------------------------------
+def segment_sums(ind_of_obs, B, t):
+    """Z^T B for the one-hot Z of ind_of_obs: B is n_obs x k, the result t x k."""
+    B = np.asarray(B, dtype=np.float64).reshape(len(ind_of_obs), -1)
+    return np.column_stack([np.bincount(ind_of_obs, weights=B[:, j], minlength=t) for j in range(B.shape[1])])
+
+
+class ZModel:
+    """What one AM(Zmat=) run keeps of K and Z: counts = diag(D), lam and U = eigh(D^1/2 K D^1/2).  Every individual of K must
+    have a record (the caller drops the others first, the reference's complete == FALSE rule of emma_eigen_*_w_Z.R)."""
+
+    def __init__(self, K, ind_of_obs):
+        ind = np.asarray(ind_of_obs, dtype=np.int64).ravel()
+        t = K.shape[0]
+        if ind.size == 0 or ind.min() < 0 or ind.max() >= t:
+            raise ValueError("ind_of_obs must hold individual numbers 0 .. %d" % (t - 1))
+        counts = np.bincount(ind, minlength=t).astype(np.float64)
+        if counts.min() <= 0:
+            raise ValueError("every individual of K needs at least one record")
+        self.ind, self.t, self.n_obs, self.counts = ind, t, ind.size, counts
+        self.sd = np.sqrt(counts)
+        Kt = K * self.sd[:, None]
+        Kt *= self.sd[None, :]
+        self.lam, self.U = _la.eigh(Kt)
+        self.lam = np.ascontiguousarray(self.lam)
+
+    def reduce(self, X, y):
+        """Ut = U^T D^-1/2 Z^T X (t x q), ut = U^T D^-1/2 Z^T y (t) and Wn = Bc^T Bc, Bc the rows of [X | y] centred within
+        their individual ((q + 1) x (q + 1)): all the model needs of the n_obs-sized data."""
+        B = np.column_stack([np.asarray(X, dtype=np.float64).reshape(self.n_obs, -1), np.ravel(y)])
+        ZtB = segment_sums(self.ind, B, self.t)
+        Bc = B - (ZtB / self.counts[:, None])[self.ind]
+        T = self.U.T @ (ZtB / self.sd[:, None])
+        return np.ascontiguousarray(T[:, :-1]), np.ascontiguousarray(T[:, -1]), Bc.T @ Bc
+
+    def gls(self, X, y, varE, varG):
+        """h = 1/(varE + varG lam), Ut, ut, C = (X^T H^-1 X)^-1 and c1 = C X^T H^-1 y."""
+        if varE <= 0 or varG < 0:
+            raise ValueError("variance components cannot be negative (and varE must be positive with repeated measures)")
+        Ut, ut, Wn = self.reduce(X, y)
+        q = Ut.shape[1]
+        h = 1.0 / (varE + varG * self.lam)
+        Uh = Ut * h[:, None]
+        C = np.linalg.inv(Ut.T @ Uh + Wn[:q, :q] / varE)
+        C = 0.5 * (C + C.T)
+        c1 = C @ (Uh.T @ ut + Wn[:q, q] / varE)
+        return h, Ut, ut, C, c1
+
+    def spectral_basis(self):
+        """D^1/2 U / sqrt(d_max) (every entry within [-1, 1]) and d_max: the basis SpectralBackend hands to spectral_prepare."""
+        dmax = float(self.counts.max())
+        return self.U * (self.sd / math.sqrt(dmax))[:, None], dmax
+
+    def spectral_operands(self, X, y, varE, varG):
+        """The operands of rcpp_api.spectral_scan_weights over Z~ = Mt spectral_basis(): d, Gy, GX, C, c1."""
+        h, Ut, ut, C, c1 = self.gls(X, y, varE, varG)
+        dmax = float(self.counts.max())
+        r = math.sqrt(dmax)
+        return {"d": dmax * h, "Gy": r * h * ut, "GX": r * h[:, None] * Ut, "C": C, "c1": c1}
+
+
+def scan_operands_z(K, ind_of_obs, X, y, varE, varG, zmodel=None, reference_shaped=True):
+    """The operands of the marker scan for y = X b + Z g + e: W = varG^2 Z^T P Z (t x t) and v = varG Z^T P y (t), what
+    scan_with_W takes, and with reference_shaped the S = K^-1/2, V = varG^2 K^1/2 Z^T P Z K^1/2, ahat = varG K^1/2 Z^T P y that
+    calculate_a_and_vara takes (S V S = W, S ahat = v).  t x t algebra only; zmodel = ZModel(K, ind_of_obs) kept by the caller
+    saves the eigh."""
+    zm = zmodel if zmodel is not None else ZModel(K, ind_of_obs)
+    h, Ut, ut, C, c1 = zm.gls(X, y, varE, varG)
+    R = zm.U * zm.sd[:, None]                     # D^1/2 U:  Z^T H^-1 Z = R diag(h) R^T, positive weights, no subtraction
+    B = R @ (Ut * h[:, None])                     # Z^T H^-1 X
+    ZPZ = _la.mm(R * h[None, :], R.T)
+    ZPZ -= B @ C @ B.T
+    ZPZ = 0.5 * (ZPZ + ZPZ.T)
+    v = varG * (R @ (h * ut) - B @ c1)
+    out = {"W": varG * varG * ZPZ, "v": v}
+    if reference_shaped:
+        sq = calculateMMt_sqrt_and_sqrtinv(K, checkres=False)
+        Sh = sq["sqrt_MMt"]
+        V = _la.mm(_la.mm(Sh, out["W"]), Sh)
+        out.update({"S": sq["inverse_sqrt_MMt"], "Shalf": Sh, "V": 0.5 * (V + V.T), "ahat": Sh @ v})
+    return out

@@ -7,6 +7,7 @@
   extract_geno, constructX E/R/extract_geno.R:1-19, E/R/constructX.R:1-24
   ReshapeM ............... E/R/ReshapeM.R:1-11
   check_for_NA_in_trait .. E/R/check_for_NA_in_trait.R:1-25
+  ReadZmat ............... E/R/ReadZmat.R:34-111     (zmat_index: the matrix as the vector ind_of_obs)
   SummaryAM .............. E/R/summary_am.R:78-221   (in the eigenbasis of K; am._summary_eig)
 
 `geno` is the reference's list {asciifileM, asciifileMt, dim_of_ascii_M = (n, L)} (E/R/ReadMarker.R:306-307).
@@ -86,15 +87,75 @@ def constructX(fnameM, currentX, loci_indx, availmemGb=8, dim_of_ascii_M=None, d
     return np.column_stack([currentX, g.astype(np.float64)])
 
 
+def ReadZmat(filename=None, message=None):
+    """E/R/ReadZmat.R:34-111: the Z matrix of a repeated-measures design from a whitespace table of 0 and 1, one row per record and
+    one column per genotyped individual, every row holding exactly one 1.  Returns the dense n_obs x n_ind matrix (the reference's
+    return type; zmat_index turns it into the vector everything else takes), or None after the reference's messages."""
+    say = message or (lambda s: None)
+
+    def fail(*lines):
+        for ln in ("  ",) + lines + ("   ", "        ReadZmat has terminated with errors.", " "):
+            say(ln)
+        return None
+
+    if filename is None or not os.path.exists(filename):
+        say(" The marker file %s could not be found. " % filename)
+        say(" ReadZmat has terminated with errors.")
+        return None
+    with open(filename) as f:
+        rows = [ln.split() for ln in f if ln.strip()]
+    try:
+        Z = np.array([[float(v) for v in r] for r in rows], dtype=np.float64)
+    except ValueError:
+        Z = None
+    if Z is None or Z.ndim != 2 or Z.dtype == object or not np.isin(Z, (0.0, 1.0)).all():
+        return fail(" ERROR: The Z matrix file contains values other than 0 and 1.")
+    rs = Z.sum(axis=1)
+    if np.any(rs == 0):
+        return fail(" ERROR:  The rows %s in the Z matrix have only 0 values." % " ".join(str(i + 1) for i in np.flatnonzero(rs == 0)),
+                    "         Each row must contain a single 1 value. ")
+    if np.any(rs != 1):
+        return fail(" ERROR:  The rows %s in the Z matrix are incorrect." % " ".join(str(i + 1) for i in np.flatnonzero(rs != 1)),
+                    "         A row can only contains 0s and a single 1. ")
+    say("\n\n Loading Z matrix file ... \n\n")
+    say("                    Summary of Z matrix File  \n")
+    say("                   ~~~~~~~~~~~~~~~~~~~~~~~~~~~~ \n")
+    say(" File name:                   %s\n" % os.path.abspath(filename))
+    say(" Number of rows:              %d\n" % Z.shape[0])
+    say(" Number of columns:           %d\n" % Z.shape[1])
+    return Z
+
+
+def zmat_index(Zmat):
+    """ind_of_obs: for every row of a Z matrix the 0-based column of its 1 (int64).  The form AM(Zmat=), emma_*(Z=) and
+    host_model.scan_operands_z work on: n_obs numbers instead of n_obs x n_ind."""
+    Z = np.asarray(Zmat)
+    if Z.ndim != 2 or not np.isin(Z, (0, 1)).all() or not np.all(Z.sum(axis=1) == 1):
+        raise ValueError("a Z matrix holds 0 and 1 with exactly one 1 in every row")
+    return np.argmax(Z, axis=1).astype(np.int64)
+
+
 def find_qtl(geno, availmemGb, selected_loci, MMt, invMMt, best_ve, best_vg, currentX, ncpu, quiet, trait, ngpu=1,
-             device=0, return_stats=False):
+             device=0, return_stats=False, Zmat=None):
     """E/R/find_qtl.R:1-84.  Host algebra (H, P, MMt^{+-1/2}, a_hat, Var a_hat) on host LAPACK, the genome scan and
-    the arg-max on the GPU.  Returns the 1-based column of the selected marker."""
-    H = host_model.calculateH(MMt, best_ve, best_vg)
-    P = host_model.calculateP(H, currentX)
-    sq = host_model.calculateMMt_sqrt_and_sqrtinv(MMt, checkres=not quiet)
-    hat_a = host_model.calculate_reduced_a(best_vg, P, sq["sqrt_MMt"], trait)
-    var_hat_a = host_model.calculate_reduced_vara(currentX, best_ve, best_vg, invMMt, sq["sqrt_MMt"])
+    the arg-max on the GPU.  Returns the 1-based column of the selected marker.
+    Zmat (not in the reference's .find_qtl): the repeated-measures design as ind_of_obs, the dense matrix or a host_model.ZModel
+    kept by the caller; trait and currentX then have one row per record, MMt one per individual, and S, V, a_hat come from
+    host_model.scan_operands_z (invMMt is not used)."""
+    if Zmat is not None:
+        zm = Zmat if isinstance(Zmat, host_model.ZModel) else None
+        if zm is None:
+            from . import am
+            Zmat = am.as_ind_of_obs(Zmat)
+        op = host_model.scan_operands_z(MMt, Zmat, currentX, trait, best_ve, best_vg, zmodel=zm)
+        sq = {"inverse_sqrt_MMt": op["S"]}
+        hat_a, var_hat_a = op["ahat"], op["V"]
+    else:
+        H = host_model.calculateH(MMt, best_ve, best_vg)
+        P = host_model.calculateP(H, currentX)
+        sq = host_model.calculateMMt_sqrt_and_sqrtinv(MMt, checkres=not quiet)
+        hat_a = host_model.calculate_reduced_a(best_vg, P, sq["sqrt_MMt"], trait)
+        var_hat_a = host_model.calculate_reduced_vara(currentX, best_ve, best_vg, invMMt, sq["sqrt_MMt"])
     a_and_vara = calculate_a_and_vara(geno=geno, maxmemGb=availmemGb, selectedloci=selected_loci,
                                       invMMtsqrt=sq["inverse_sqrt_MMt"], transformed_a=hat_a,
                                       transformed_vara=var_hat_a, quiet=quiet, device=device)

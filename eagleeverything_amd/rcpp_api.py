@@ -276,6 +276,28 @@ def spectral_scan(lam, UtX, Uty, varE, varG, n_markers, selected_loci=np.nan, de
     return {"a": a_out.reshape(-1, 1), "vara": v_out.reshape(-1, 1)}
 
 
+def spectral_scan_weights(d, Gy, GX, C, c1, varG, n_markers, selected_loci=np.nan, device=0):
+    """eagle_spectral_scan_weights: the pass of spectral_scan with caller-made operands (include/eagle_hip.h section 1d):
+    a_i = varG (z_i . Gy - q_i . c1), vara_i = varG^2 (sum_k z_ik^2 d_k - q_i^T C q_i), q_i = z_i^T GX."""
+    L = _lib.load()
+    ctx = context(device)
+    d = _f64F(np.ravel(d))
+    n = _spectral_n.get(device, 0)
+    GX = _f64F(np.atleast_2d(GX).reshape(d.size, -1))
+    Gy = _f64F(np.ravel(Gy))
+    p = GX.shape[1]
+    Cm = _f64F(np.asarray(C, dtype=np.float64).reshape(p, p))
+    c1 = _f64F(np.ravel(c1))
+    if d.size != n or Gy.size != n or c1.size != p:
+        raise ValueError("spectral_scan_weights: d, Gy of length n = %d (the resident Z), GX n x p, C p x p, c1 of length p" % n)
+    s, sp, ns = _sel(selected_loci)
+    a_out = np.zeros(int(n_markers))
+    v_out = np.zeros(int(n_markers))
+    _check(ctx, L.eagle_spectral_scan_weights(ctx, _dp(d), _dp(Gy), _dp(GX), p, _dp(Cm), _dp(c1), float(varG), sp, ns, _dp(a_out),
+                                              _dp(v_out)))
+    return {"a": a_out.reshape(-1, 1), "vara": v_out.reshape(-1, 1)}
+
+
 def spectral_traits_passes(p):
     """eagle_spectral_traits_passes: passes over Z one spectral_scan_traits call makes for traits with these p[t] columns."""
     pv = np.ascontiguousarray(np.atleast_1d(p), dtype=np.int64)

@@ -311,6 +311,14 @@ int eagle_spectral_prepare(eagle_ctx* ctx, const char* f_name_ascii, const long 
  * selected_loci: the reference's masking rule (element 0 NA: none). */
 int eagle_spectral_scan(eagle_ctx* ctx, const double* lambda, const double* UtX, const double* Uty, long p, double varE, double varG,
                         const double* selected_loci, long n_selected, double* a_out, double* vara_out);
+/* The same pass with the operands made by the caller: a_i = varG (z_i . Gy - q_i . c1), vara_i = varG^2 (sum_k z_ik^2 d_k -
+ * q_i^T C q_i), q_i = z_i^T GX, z_i the row of the resident Z.  d, Gy: n; GX: n x p column-major (1 <= p <= 31); C: p x p
+ * symmetric; c1: p.  eagle_spectral_scan is this call with d = 1/(varE + varG lambda), Gy = d o Uty, GX = d o UtX,
+ * C = (UtX^T D UtX)^-1, c1 = C UtX^T D Uty.  For a model whose C and c1 hold terms that lambda and UtX alone do not give: the
+ * repeated-measures design y = X b + Z g + e of am.AM(Zmat=), where Z is made from the scaled eigenvectors of D^1/2 K D^1/2 and
+ * X^T H^-1 X carries the within-individual remainder.  Masking and errors as eagle_spectral_scan. */
+int eagle_spectral_scan_weights(eagle_ctx* ctx, const double* d, const double* Gy, const double* GX, long p, const double* C, const double* c1,
+                                double varG, const double* selected_loci, long n_selected, double* a_out, double* vara_out);
 /* T traits over the Z of the last eagle_spectral_prepare, in as few passes over Z as the column groups allow (whole traits packed
  * into at most 128 MFMA columns: p[t] + 1 per trait plus one per trait for sum_k z_ik^2 d_t[k]; eagle_spectral_traits_passes).
  * UtX[t]: n x p[t] column-major (1 <= p[t] <= 31), Uty: n x T column-major, varE/varG: T each.  a_out, vara_out: L x T
