@@ -294,6 +294,81 @@ def emma_MLE_eig(lam, UtX, Uty, ngrids=100, llim=-10, ulim=10, esp=1e-10):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+# The same for T traits at once (FPR4AM).  Trait t has the design [UtX | last[:, t]] (last = None: UtX
+# alone, the null fits of a permutation study) and the trait column UtY[:, t].  The weights [W | W^2] depend on lam only, so the
+# 101-point dLL grid of ALL traits is ONE product of the stacked (T (q+1)(q+2)/2) x n column products with them, through
+# host_model.algebra().mm (the fp64 GEMM of the device with algebra="device"); bracket rule, zeroin and end-point rule then run
+# per trait on the scalar functions of _emma_eig.
+# ---------------------------------------------------------------------------------------------------------------------------
+def _eig_grid_dll_batch(lam, B, delta, reml):
+    """_eig_grid_dll for B = T x n x (q+1), trait t's [Ut_t | ut_t]: T x m values of dLL/dlogdelta from one GEMM."""
+    T, n, q1 = B.shape
+    q = q1 - 1
+    iu, ju = np.triu_indices(q1)
+    WW = _grid_weights(lam, delta)
+    PT = np.ascontiguousarray((B[:, :, iu] * B[:, :, ju]).transpose(0, 2, 1)).reshape(T * iu.size, n)
+    S = np.asarray(host_model.algebra().mm(PT, WW)).reshape(T, iu.size, -1)      # (T (q+1)(q+2)/2) x 2m in one product
+    m = delta.size
+    M = np.empty((T, 2 * m, q1, q1))
+    M[:, :, iu, ju] = S.transpose(0, 2, 1)
+    M[:, :, ju, iu] = S.transpose(0, 2, 1)
+    S1, S2 = M[:, :m], M[:, m:]
+    A, b = S1[..., :q, :q], S1[..., :q, q]
+    beta = np.linalg.solve(A, b[..., None])[..., 0]
+    R = S1[..., q, q] - np.einsum("tgi,tgi->tg", b, beta)
+    r2 = S2[..., q, q] - 2 * np.einsum("tgi,tgi->tg", beta, S2[..., :q, q]) + np.einsum("tgi,tgij,tgj->tg", beta, S2[..., :q, :q], beta)
+    trP = WW[:, :m].sum(axis=0)[None, :]
+    if reml:
+        trP = trP - np.einsum("tgij,tgji->tg", np.linalg.inv(A), S2[..., :q, :q])
+    return 0.5 * delta[None, :] * ((n - q if reml else n) * r2 / R - trP)
+
+
+def _emma_eig_batch(lam, UtX, UtY, last, ngrids, llim, ulim, esp, reml):
+    """-> (LL, delta, va), T each; a trait whose X^T X is singular gets 0, 0, 0 (emma_REMLE.R:28-30)."""
+    lam = np.asarray(lam, dtype=np.float64).ravel()
+    n = lam.size
+    Ut0 = np.asarray(UtX, dtype=np.float64).reshape(n, -1)
+    UtY = np.asarray(UtY, dtype=np.float64).reshape(n, -1)
+    T, q0 = UtY.shape[1], Ut0.shape[1]
+    q = q0 if last is None else q0 + 1
+    B = np.empty((T, n, q + 1))
+    B[:, :, :q0] = Ut0[None]
+    if last is not None:
+        last = np.asarray(last, dtype=np.float64).reshape(n, -1)
+        if last.shape[1] != T:
+            raise ValueError("one last column per trait: %d for %d traits" % (last.shape[1], T))
+        B[:, :, q0] = last.T
+    B[:, :, q] = UtY.T
+    LL, dl, va = np.zeros(T), np.zeros(T), np.zeros(T)
+    xtx = [Ut0.T @ Ut0] * T if last is None else [B[t, :, :q].T @ B[t, :, :q] for t in range(T)]    # = X_t^T X_t (U orthogonal)
+    ok = [t for t in range(T) if np.linalg.det(xtx[t]) != 0]
+    if not ok:
+        return LL, dl, va
+    logdelta, delta = _grid(ngrids, llim, ulim)
+    dLL = _eig_grid_dll_batch(lam, B if len(ok) == T else B[ok], delta, reml)
+    for k, t in enumerate(ok):
+        Ut, ut = np.ascontiguousarray(B[t, :, :q]), np.ascontiguousarray(B[t, :, q])
+        logdet_xtx = np.linalg.slogdet(xtx[t])[1]
+        dl[t], LL[t] = _optimise(dLL[k], logdelta, llim, ulim, esp, lambda ld: _eig_ll(ld, lam, Ut, ut, reml, logdet_xtx),
+                                 lambda ld: _eig_dll(ld, lam, Ut, ut, reml))
+        va[t] = _eig_fit(lam, Ut, ut, dl[t])[4] / (n - q if reml else n)
+    return LL, dl, va
+
+
+def emma_REMLE_eig_batch(lam, UtX, UtY, last=None, ngrids=100, llim=-10, ulim=10, esp=1e-10):
+    """emma_REMLE_eig for the T columns of UtY (n x T): the design of trait t is UtX (n x q, shared), with last (n x T) given
+    [UtX | last[:, t]].  Returns {"REML", "delta", "ve", "vg"} of arrays of length T."""
+    LL, dl, va = _emma_eig_batch(lam, UtX, UtY, last, ngrids, llim, ulim, esp, True)
+    return {"REML": LL, "delta": dl, "ve": va * dl, "vg": va}
+
+
+def emma_MLE_eig_batch(lam, UtX, UtY, last=None, ngrids=100, llim=-10, ulim=10, esp=1e-10):
+    """emma_MLE_eig for the T columns of UtY; arguments as emma_REMLE_eig_batch.  Returns {"ML", "delta", "ve", "vg"}."""
+    LL, dl, va = _emma_eig_batch(lam, UtX, UtY, last, ngrids, llim, ulim, esp, False)
+    return {"ML": LL, "delta": dl, "ve": va * dl, "vg": va}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
 # emma.REMLE / emma.MLE with a Z matrix (emma_REMLE.R:78-128, emma_MLE.R:58-105) in the reduced form of host_model.ZModel: with
 # lam, U = eigh(D^1/2 K D^1/2) -- lam are the eigenvalues of the reference's non-symmetric K Z^T Z (emma_eigen_L_w_Z.R:8) --,
 # Ut = U^T D^-1/2 Z^T X, ut likewise and Wn the Gram matrix of the rows of [X | y] centred within their individual, H/vg = delta I +
@@ -380,10 +455,12 @@ def _lchoose(n, k):
     return gammaln(n + 1) - gammaln(k + 1) - gammaln(n - k + 1)
 
 
-def calc_extBIC(trait, currentX, MMt, nmarkers, eig_L=None, eig_R=None, Z=None, zmodel=None):
+def calc_extBIC(trait, currentX, MMt, nmarkers, eig_L=None, eig_R=None, Z=None, zmodel=None, gamma=1.0):
+    """calc_extBIC.R:1-12 with the weight gamma on the model-space term; gamma = 1 is the reference's
+    value bit for bit, 2 * 1.0 being exact."""
     res = emma_MLE(trait, currentX, MMt, Z=Z, llim=-100, ulim=100, eig_L=eig_L, eig_R=eig_R, zmodel=zmodel)
     BIC = -2 * res["ML"] + (currentX.shape[1] + 1) * math.log(trait.size)
-    return BIC + 2 * _lchoose(nmarkers, currentX.shape[1] - 1)
+    return BIC + 2 * gamma * _lchoose(nmarkers, currentX.shape[1] - 1)
 
 
 class HipBackend:
@@ -464,7 +541,7 @@ def reshape_geno(geno, indxNA, view=False, device=0):
     return {"asciifileM": geno["asciifileM"] + "tmp", "asciifileMt": geno["asciifileMt"] + "tmp", "dim_of_ascii_M": newdims}
 
 
-def AM(trait, X, geno, availmemGb=8, ncpu=1, maxit=20, quiet=True, backend=None, message=None, algebra=None, Zmat=None):
+def AM(trait, X, geno, availmemGb=8, ncpu=1, maxit=20, quiet=True, backend=None, message=None, algebra=None, Zmat=None, gamma=1.0):
     """E/R/AM.R:320-475 for a trait vector and a ready design matrix X (n x q, intercept included).
 
     Individuals whose trait or any column of X is NaN are dropped (AM.R:320-329: an NA covariate makes the trait NA): from trait
@@ -475,9 +552,12 @@ def AM(trait, X, geno, availmemGb=8, ncpu=1, maxit=20, quiet=True, backend=None,
     selected_loci starts as [NA] exactly like AM.R:260, so the selected_loci masking never fires.
 
     Zmat: repeated measures (several records per genotyped individual), as r_api.ReadZmat's matrix or as ind_of_obs
-    (r_api.zmat_index); trait and X then have one row per record -- see _AM_z."""
+    (r_api.zmat_index); trait and X then have one row per record -- see _AM_z.
+
+    gamma: the weight on extBIC's model-space term (calc_extBIC); 1 is the reference's rule, a smaller value selects more loci.
+    FPR4AM finds the gamma of a wanted false positive rate."""
     if Zmat is not None:
-        return _AM_z(trait, X, geno, Zmat, availmemGb, ncpu, maxit, quiet, backend, message, algebra)
+        return _AM_z(trait, X, geno, Zmat, availmemGb, ncpu, maxit, quiet, backend, message, algebra, gamma)
     backend = backend or HipBackend()
     if algebra is not None:  # "host" (LAPACK, the reference's placement) or "device" (SURVEY 8 f-4: rocSOLVER / the fp64 MFMA GEMM through the C ABI)
         host_model.set_algebra(algebra)
@@ -510,7 +590,7 @@ def AM(trait, X, geno, availmemGb=8, ncpu=1, maxit=20, quiet=True, backend=None,
             eig_L = emma_eigen_L_wo_Z(MMt)  # depends on MMt only; the reference recomputes it every iteration
         eig_R = emma_eigen_R_wo_Z(MMt, currentX)  # shared by REMLE and MLE of this iteration (same K, X)
         best = calcVC(trait, currentX, MMt, eig_R=eig_R)
-        extBIC.append(calc_extBIC(trait, currentX, MMt, nmarkers, eig_L=eig_L, eig_R=eig_R))
+        extBIC.append(calc_extBIC(trait, currentX, MMt, nmarkers, eig_L=eig_L, eig_R=eig_R, gamma=gamma))
         if int(np.flatnonzero(np.asarray(extBIC) == min(extBIC))[0]) == len(extBIC) - 1:  # AM.R:448
             new_selected_locus = backend.find_qtl(geno=geno, availmemGb=availmemGb, selected_loci=np.array(selected_loci), MMt=MMt,
                                                   invMMt=invMMt, best_ve=best["ve"], best_vg=best["vg"], currentX=currentX,
@@ -546,7 +626,7 @@ def _AM_result(selected_loci, extBIC, itnum, maxit, best, indxNA, geno):
             "vg": best.get("vg"), "indxNA": indxNA, "dim_of_ascii_M": list(geno["dim_of_ascii_M"])}
 
 
-def _AM_z(trait, X, geno, Zmat, availmemGb, ncpu, maxit, quiet, backend, message, algebra):
+def _AM_z(trait, X, geno, Zmat, availmemGb, ncpu, maxit, quiet, backend, message, algebra, gamma=1.0):
     """AM() for y = X b + Z g + e: trait and X hold one row per RECORD, Zmat says whose record each is.
 
     Checks as check_inputs_mlam.R:122-145.  A record with NaN in trait or X is dropped (from trait, X and Z; the result's
@@ -610,7 +690,7 @@ def _AM_z(trait, X, geno, Zmat, availmemGb, ncpu, maxit, quiet, backend, message
             if hasattr(backend, "prepare_z"):
                 backend.prepare_z(geno, zm, availmemGb)
         best = calcVC(trait, currentX, MMt, zmodel=zm)
-        extBIC.append(calc_extBIC(trait, currentX, MMt, nmarkers, zmodel=zm))
+        extBIC.append(calc_extBIC(trait, currentX, MMt, nmarkers, zmodel=zm, gamma=gamma))
         if int(np.flatnonzero(np.asarray(extBIC) == min(extBIC))[0]) == len(extBIC) - 1:  # AM.R:448
             new_selected_locus = backend.find_qtl(geno=geno, availmemGb=availmemGb, selected_loci=np.array(selected_loci), MMt=MMt,
                                                   invMMt=None, best_ve=best["ve"], best_vg=best["vg"], currentX=currentX,
@@ -626,7 +706,7 @@ def _AM_z(trait, X, geno, Zmat, availmemGb, ncpu, maxit, quiet, backend, message
     return out
 
 
-def AM_traits(Y, X, geno, availmemGb=8, maxit=20, quiet=True, message=None, algebra=None, device=0, Zmat=None):
+def AM_traits(Y, X, geno, availmemGb=8, maxit=20, quiet=True, message=None, algebra=None, device=0, Zmat=None, gamma=1.0):
     """AM() for the T columns of Y (n x T) with one design matrix X (n x q) on one genotype panel, in one run: calcMMt and
     lam, U = eigh(MM^T) once, Z = Mt U once (spectral_prepare), then the traits in lockstep -- each round one spectral_scan_traits
     call for every trait still running, and per trait emma_REMLE_eig / emma_MLE_eig in the eigenbasis (no n^3 work per trait or
@@ -638,7 +718,9 @@ def AM_traits(Y, X, geno, availmemGb=8, maxit=20, quiet=True, message=None, alge
     spectral_rows) to that trait's U^T X.
 
     Zmat (repeated measures) is not supported here: the per-trait EMMA in the eigenbasis and the batched kernel's own C would need
-    AM(Zmat=)'s within-individual terms.  Run AM(Zmat=) per trait."""
+    AM(Zmat=)'s within-individual terms.  Run AM(Zmat=) per trait.
+
+    gamma: the weight on extBIC's model-space term, as in AM()."""
     if Zmat is not None:
         raise NotImplementedError("AM_traits: Zmat (repeated measures) is not supported; run AM(Zmat=) for each trait")
     from . import r_api, rcpp_api
@@ -680,7 +762,7 @@ def AM_traits(Y, X, geno, availmemGb=8, maxit=20, quiet=True, message=None, alge
             s["best"] = {"vg": r["vg"], "ve": r["ve"]}
             ml = emma_MLE_eig(lam, s["UtX"], UtY[:, t], llim=-100, ulim=100)                     # calc_extBIC
             k = s["UtX"].shape[1]
-            s["ext"].append(-2 * ml["ML"] + (k + 1) * math.log(n) + 2 * _lchoose(nmarkers, k - 1))
+            s["ext"].append(-2 * ml["ML"] + (k + 1) * math.log(n) + 2 * gamma * _lchoose(nmarkers, k - 1))
             if int(np.flatnonzero(np.asarray(s["ext"]) == min(s["ext"]))[0]) == len(s["ext"]) - 1:   # AM.R:448
                 scan.append(t)
             else:
@@ -708,6 +790,130 @@ def AM_traits(Y, X, geno, availmemGb=8, maxit=20, quiet=True, message=None, alge
             ext = [v for i, v in enumerate(s["ext"]) if i != len(s["sel"]) - 1]
         out.append({"selected_loci": loci, "all_picks": picks, "extBIC": ext, "extBIC_trace": list(s["ext"]), "ve": s["best"].get("ve"),
                     "vg": s["best"].get("vg"), "indxNA": indxNA, "dim_of_ascii_M": list(geno["dim_of_ascii_M"])})
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# FPR4AM: the gamma of a wanted false positive rate, from permutations of the trait.  Not in the reference
+# tree (1.0.3); defined from the model.  For a permuted trait y_r AM() selects a (false) locus iff extBIC[1] < extBIC[0] (AM.R:448),
+# which with q = ncol(X) and c = lchoose(L, q) - lchoose(L, q - 1) is gamma < gamma_star_r = (2 (ML1_r - ML0_r) - log n) / (2 c).
+# ---------------------------------------------------------------------------------------------------------------------------
+def fpr_curve(gamma_star, gammas):
+    """FPR(gamma) = #{r : gamma_star_r > gamma} / R for every gamma of gammas: a step function that does not increase."""
+    gs = np.asarray(gamma_star, dtype=np.float64).ravel()
+    g = np.atleast_1d(np.asarray(gammas, dtype=np.float64))
+    return (gs[None, :] > g.reshape(-1, 1)).sum(axis=1).reshape(g.shape) / gs.size
+
+
+def choose_gamma(gamma_star, falseposrate):
+    """The smallest gamma >= 0 with FPR(gamma) <= falseposrate: the k-th largest gamma_star, k = floor(falseposrate R) + 1, clipped
+    below at 0.  k - 1 is found as the largest count m with m / R <= falseposrate, the comparison fpr_curve's values meet, so that
+    a product falseposrate R that rounds below its integer value does not move k."""
+    gs = np.asarray(gamma_star, dtype=np.float64).ravel()
+    R = gs.size
+    if R < 1 or not 0 < falseposrate < 1:
+        raise ValueError("choose_gamma: at least one gamma_star and 0 < falseposrate < 1")
+    m = int(math.floor(falseposrate * R))
+    while (m + 1) / R <= falseposrate:
+        m += 1
+    while m / R > falseposrate:
+        m -= 1
+    return max(float(np.sort(gs)[::-1][m]), 0.0)
+
+
+def _fpr_group(q):
+    """Traits with q fixed-effect columns that one pass over Z scores (eagle_spectral_traits_passes)."""
+    from . import rcpp_api
+    g = 1
+    while g < 128 and rcpp_api.spectral_traits_passes([q] * (g + 1)) == 1:
+        g += 1
+    return g
+
+
+def FPR4AM(trait, X, geno, falseposrate=0.05, numreps=200, seed=101, availmemGb=8, quiet=True, message=None, algebra=None, device=0,
+           eig=None, chunk=None):
+    """The weight gamma on extBIC's model-space term at which AM(trait, X, geno, gamma=...) returns a false positive for the share
+    falseposrate of traits without any association, estimated from numreps permutations of the trait.
+
+    Rows with NaN in trait or X are dropped first (AM()'s rule, one VIEW reshape).  Permutation r is y[pi_r] with
+    pi_r = rng.permutation(n), rng = numpy.random.default_rng(seed), drawn in order r = 0 .. numreps - 1; X and the genotypes stay.
+    For each: the null fit on X (REML -> ve, vg; ML -> ML0), the scan's pick j_r, the ML fit on [X | m_j] (ML1) -- iterations 1 and 2
+    of AM(y_r, X, geno, maxit=2) -- and gamma_star_r (above).  One calcMMt and one eigh (none with eig = (lam, U) of K, what
+    SpectralBackend().eig holds), one spectral_prepare (none when rcpp_api.spectral_holds this Z), then per chunk of `chunk`
+    permutations (default: whole column groups of the batched scan, as many as keep the stacked grid products within availmemGb / 8)
+    one U^T Y, the batched EMMA, one spectral_scan_traits and one spectral_rows.  Nothing of size numreps x L exists.
+
+    Returns dict(setgamma = choose_gamma(gamma_star, falseposrate), falseposrate = FPR(setgamma) achieved on these permutations,
+    gamma_star, picks (1-based), tsqmax, ML0, ML1, ve, vg: numreps each; indxNA, seed, numreps).  setgamma may exceed 1.
+    Permuting y against a structured K is an approximation under population structure (it breaks the trait's own covariance with K)."""
+    from . import r_api, rcpp_api
+    if not 0 < falseposrate < 1:
+        raise ValueError("FPR4AM: falseposrate must lie strictly between 0 and 1, got %r" % (falseposrate,))
+    numreps = int(numreps)
+    if numreps < 1:
+        raise ValueError("FPR4AM: numreps must be at least 1")
+    y = np.asarray(trait, dtype=np.float64).ravel().copy()
+    X0 = np.asarray(X, dtype=np.float64).reshape(y.size, -1)
+    q = X0.shape[1]
+    if q > 30:
+        raise ValueError("FPR4AM: %d columns of X; at most 30 (the pick makes 31, the most the spectral scan takes)" % q)
+    if chunk is not None and int(chunk) < 1:
+        raise ValueError("FPR4AM: chunk must be at least 1")
+    if algebra is not None:
+        host_model.set_algebra(algebra)
+    say = message or (lambda *_: None)
+    y[np.isnan(X0).any(axis=1)] = np.nan                                             # AM.R:320-329
+    indxNA = r_api.check_for_NA_in_trait(y)
+    if indxNA.size:
+        keep = ~np.isnan(y)
+        y, X0 = y[keep], X0[keep]
+        say(" The following rows are being removed from pheno due to missing data: %s" % " ".join(str(int(i)) for i in indxNA))
+        geno = reshape_geno(geno, indxNA, view=True, device=device)
+    n, L = (int(v) for v in geno["dim_of_ascii_M"])
+    if y.size != n:
+        raise ValueError("FPR4AM: %d trait records for %d genotyped individuals" % (y.size, n))
+    la = host_model.algebra()
+    if eig is None:
+        MMt = r_api.calcMMt(geno, availmemGb, 1, np.array([np.nan]), quiet, device=device)
+        lam, U = la.eigh(MMt)
+        del MMt
+    else:
+        lam, U = eig
+        if np.size(lam) != n or np.shape(U) != (n, n):
+            raise ValueError("FPR4AM: eig holds %d eigenvalues, the genotypes %d individuals" % (np.size(lam), n))
+    lam = np.ascontiguousarray(lam, dtype=np.float64).ravel()
+    if not rcpp_api.spectral_holds(geno["asciifileMt"], U, device=device):
+        rcpp_api.spectral_prepare(geno["asciifileMt"], (L, n), U, availmemGb, device=device)
+    UtX = la.mm(U.T, X0)
+    if chunk is None:
+        g = _fpr_group(q)
+        pairs = (q + 2) * (q + 3) // 2                                               # column products of [X | m_j | y]
+        chunk = max(g, int(availmemGb * 2.0 ** 30 / 8 / (8.0 * n * pairs)) // g * g)
+    chunk = int(chunk)
+    c = _lchoose(L, q) - _lchoose(L, q - 1)
+    rng = np.random.default_rng(seed)
+    out = {k: np.zeros(numreps) for k in ("gamma_star", "tsqmax", "ML0", "ML1", "ve", "vg")}
+    picks = np.zeros(numreps, dtype=np.int64)
+    for r0 in range(0, numreps, chunk):
+        r1 = min(r0 + chunk, numreps)
+        say("Permutations %d to %d of %d" % (r0 + 1, r1, numreps))
+        Yc = np.column_stack([y[rng.permutation(n)] for _ in range(r0, r1)])
+        UtY = la.mm(U.T, Yc)
+        vc = emma_REMLE_eig_batch(lam, UtX, UtY)                                     # calcVC of iteration 1
+        ml0 = emma_MLE_eig_batch(lam, UtX, UtY, llim=-100, ulim=100)                 # calc_extBIC of iteration 1
+        res = rcpp_api.spectral_scan_traits(lam, [UtX] * (r1 - r0), UtY, vc["ve"], vc["vg"], L, device=device)
+        if np.any(res["index"] < 1):
+            raise RuntimeError("FPR4AM: every tsq of a scan is NaN")
+        uniq, inv = np.unique(np.asarray(res["index"], dtype=np.int64) - 1, return_inverse=True)
+        rows = rcpp_api.spectral_rows(uniq, device=device)                           # U^T m_j of the distinct picks
+        ml1 = emma_MLE_eig_batch(lam, UtX, UtY, last=rows[:, inv], llim=-100, ulim=100)   # calc_extBIC of iteration 2
+        picks[r0:r1] = res["index"]
+        for k, v in (("tsqmax", res["tsqmax"]), ("ML0", ml0["ML"]), ("ML1", ml1["ML"]), ("ve", vc["ve"]), ("vg", vc["vg"])):
+            out[k][r0:r1] = v
+    out["gamma_star"] = (2.0 * (out["ML1"] - out["ML0"]) - math.log(n)) / (2.0 * c)
+    setgamma = choose_gamma(out["gamma_star"], falseposrate)
+    out.update({"setgamma": setgamma, "falseposrate": float(fpr_curve(out["gamma_star"], setgamma)[0]), "picks": picks,
+                "indxNA": indxNA, "seed": seed, "numreps": numreps})
     return out
 
 

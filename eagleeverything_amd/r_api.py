@@ -320,3 +320,12 @@ def SummaryAM(AMobj, trait, X, geno, map=None, xnames=None, availmemGb=8, eig=No
     F = np.column_stack([X] + [backend.extract_geno(geno, j).astype(np.float64) for j in picks] + [y])   # constructX, :131-137
     Ft = host_model.algebra().mm(U.T, F)
     return am._summary_eig(lam, maxK, Ft[:, :-1], Ft[:, -1], q, xn + [mname(j) for j in picks], say)
+
+
+def FPR4AM(trait, X, geno, falseposrate=0.05, numreps=200, seed=101, availmemGb=8, quiet=True, message=None, algebra=None, device=0,
+           eig=None, chunk=None):
+    """The gamma of AM(..., gamma=) for a wanted false positive rate, from numreps permutations of the trait: am.FPR4AM, under the
+    name later releases of the package give it (the reference tree has no such function; DESIGN.md section 4.7d defines it)."""
+    from . import am
+    return am.FPR4AM(trait, X, geno, falseposrate=falseposrate, numreps=numreps, seed=seed, availmemGb=availmemGb, quiet=quiet,
+                     message=message, algebra=algebra, device=device, eig=eig, chunk=chunk)
