@@ -24,443 +24,32 @@ import numpy as np
 from scipy.special import chdtr, gammaln
 
 from . import host_model
-
-_EPS25 = np.finfo(np.float64).eps ** 0.25  # uniroot's default tol
-
-
-def _zeroin(f, a, b, tol=_EPS25, maxit=1000):
-    """Brent's zeroin (Forsythe, Malcolm & Moler), the algorithm behind R's uniroot."""
-    fa, fb = f(a), f(b)
-    c, fc = a, fa
-    eps = np.finfo(np.float64).eps
-    if fa == 0.0:
-        return a
-    if fb == 0.0:
-        return b
-    for _ in range(maxit + 1):
-        prev_step = b - a
-        if abs(fc) < abs(fb):
-            a, b, c = b, c, b
-            fa, fb, fc = fb, fc, fb
-        tol_act = 2 * eps * abs(b) + tol / 2
-        new_step = (c - b) / 2
-        if abs(new_step) <= tol_act or fb == 0.0:
-            return b
-        if abs(prev_step) >= tol_act and abs(fa) > abs(fb):
-            cb = c - b
-            if a == c:
-                t1 = fb / fa
-                p = cb * t1
-                q = 1.0 - t1
-            else:
-                q = fa / fc
-                t1 = fb / fc
-                t2 = fb / fa
-                p = t2 * (cb * q * (q - t1) - (b - a) * (t1 - 1.0))
-                q = (q - 1.0) * (t1 - 1.0) * (t2 - 1.0)
-            if p > 0:
-                q = -q
-            else:
-                p = -p
-            if p < (0.75 * cb * q - abs(tol_act * q) / 2) and p < abs(prev_step * q / 2):
-                new_step = p / q
-        if abs(new_step) < tol_act:
-            new_step = tol_act if new_step > 0 else -tol_act
-        a, fa = b, fb
-        b += new_step
-        fb = f(b)
-        if (fb > 0 and fc > 0) or (fb < 0 and fc < 0):
-            c, fc = a, fa
-    return b
+from .emma import (_EPS25, _emma_eig, _emma_eig_batch, _emma_result, _emma_z, _eig_grid_dll, _eig_grid_dll_batch,  # noqa: F401
+                   _grid, _grid_memo, _grid_weights, _ml_dll, _ml_ll, _optimise, _optimum, _reml_dll, _reml_ll, _z_dll, _z_fit, _z_ll,
+                   _zeroin, as_ind_of_obs, emma_eigen_L_wo_Z, emma_eigen_R_wo_Z, emma_MLE, emma_MLE_eig, emma_MLE_eig_batch,
+                   emma_REMLE, emma_REMLE_eig, emma_REMLE_eig_batch)   # all of emma stays reachable as am.<name>
 
 
-def emma_eigen_L_wo_Z(K):
-    ev, U = host_model.algebra().eigh_desc(K)  # R's eigen(): decreasing order
-    return {"values": np.ascontiguousarray(ev), "vectors": U if U.flags.f_contiguous or U.flags.c_contiguous else U.copy()}
-
-
-def emma_eigen_R_wo_Z(K, X):
-    n, q = X.shape
-    la = host_model.algebra()
-    S = X @ np.linalg.solve(X.T @ X, X.T)      # S = diag(n) - X (X'X)^-1 X', without the n x n identity
-    np.negative(S, out=S)
-    S.flat[:: n + 1] += 1.0
-    K1 = K.copy()                              # K + diag(n)
-    K1.flat[:: n + 1] += 1.0
-    ev, U = la.eigh_desc(la.mm(la.mm(S, K1), S))
-    return {"values": ev[: n - q] - 1.0, "vectors": U[:, : n - q].copy()}
-
-
-def _grid(ngrids, llim, ulim):
-    logdelta = np.arange(ngrids + 1) / ngrids * (ulim - llim) + llim
-    return logdelta, np.exp(logdelta)
-
-
-def _reml_ll(logdelta, lam, etas):
-    nq = etas.size
-    d = math.exp(logdelta)
-    return 0.5 * (nq * (math.log(nq / (2 * math.pi)) - 1 - math.log(np.sum(etas * etas / (lam + d)))) - np.sum(np.log(lam + d)))
-
-
-def _reml_dll(logdelta, lam, etas):
-    nq = etas.size
-    d = math.exp(logdelta)
-    ld = lam + d
-    e2 = etas * etas
-    return 0.5 * (nq * np.sum(e2 / (ld * ld)) / np.sum(e2 / ld) - np.sum(1.0 / ld))
-
-
-def _ml_ll(logdelta, lam, etas, xi):
-    n = xi.size
-    d = math.exp(logdelta)
-    return 0.5 * (n * (math.log(n / (2 * math.pi)) - 1 - math.log(np.sum(etas * etas / (lam + d)))) - np.sum(np.log(xi + d)))
-
-
-def _ml_dll(logdelta, lam, etas, xi):
-    n = xi.size
-    d = math.exp(logdelta)
-    ld = lam + d
-    e2 = etas * etas
-    return 0.5 * (n * np.sum(e2 / (ld * ld)) / np.sum(e2 / ld) - np.sum(1.0 / (xi + d)))
-
-
-def _optimise(dLL, logdelta, llim, ulim, esp, ll_fn, dll_fn):
-    """The bracket rule shared by emma.REMLE (:60-76) and emma.MLE (:43-60)."""
-    m = logdelta.size
-    opt_ld, opt_ll = [], []
-    if dLL[0] < esp:
-        opt_ld.append(llim); opt_ll.append(ll_fn(llim))
-    if dLL[m - 2] > 0 - esp:
-        opt_ld.append(ulim); opt_ll.append(ll_fn(ulim))
-    for i in range(m - 1):
-        if dLL[i] * dLL[i + 1] < 0 - esp * esp and dLL[i] > 0 and dLL[i + 1] < 0:
-            r = _zeroin(dll_fn, logdelta[i], logdelta[i + 1])
-            opt_ld.append(r); opt_ll.append(ll_fn(r))
-    k = int(np.argmax(opt_ll))
-    return math.exp(opt_ld[k]), opt_ll[k]
-
-
-def emma_REMLE(y, X, K, Z=None, ngrids=100, llim=-10, ulim=10, esp=1e-10, eig_R=None, zmodel=None):
-    """Z: None, or the repeated-measures design as ind_of_obs (or the dense 0/1 matrix): the reduced form of _emma_z."""
-    n, q = y.size, X.shape[1]
-    if np.linalg.det(X.T @ X) == 0:
-        return {"REML": 0, "delta": 0, "ve": 0, "vg": 0}
-    if Z is not None or zmodel is not None:
-        r = _emma_z(y, X, K, Z, zmodel, ngrids, llim, ulim, esp, True)
-        return {"REML": r[0], "delta": r[1], "ve": r[2] * r[1], "vg": r[2]}
-    if eig_R is None:
-        eig_R = emma_eigen_R_wo_Z(K, X)
-    lam = eig_R["values"]
-    etas = eig_R["vectors"].T @ y
-    logdelta, delta = _grid(ngrids, llim, ulim)
-    Lam = lam[:, None] + delta[None, :]
-    E2 = (etas * etas)[:, None]
-    dLL = 0.5 * delta * ((n - q) * np.sum(E2 / (Lam * Lam), axis=0) / np.sum(E2 / Lam, axis=0) - np.sum(1.0 / Lam, axis=0))
-    maxdelta, maxLL = _optimise(dLL, logdelta, llim, ulim, esp, lambda ld: _reml_ll(ld, lam, etas), lambda ld: _reml_dll(ld, lam, etas))
-    maxva = np.sum(etas * etas / (lam + maxdelta)) / (n - q)
-    return {"REML": maxLL, "delta": maxdelta, "ve": maxva * maxdelta, "vg": maxva}
-
-
-def emma_MLE(y, X, K, Z=None, ngrids=100, llim=-10, ulim=10, esp=1e-10, eig_L=None, eig_R=None, zmodel=None):
-    n = y.size
-    if np.linalg.det(X.T @ X) == 0:
-        return {"ML": 0, "delta": 0, "ve": 0, "vg": 0}
-    if Z is not None or zmodel is not None:
-        r = _emma_z(y, X, K, Z, zmodel, ngrids, llim, ulim, esp, False)
-        return {"ML": r[0], "delta": r[1], "ve": r[2] * r[1], "vg": r[2]}
-    if eig_L is None:
-        eig_L = emma_eigen_L_wo_Z(K)
-    if eig_R is None:
-        eig_R = emma_eigen_R_wo_Z(K, X)
-    lam, xi = eig_R["values"], eig_L["values"]
-    etas = eig_R["vectors"].T @ y
-    logdelta, delta = _grid(ngrids, llim, ulim)
-    Lam = lam[:, None] + delta[None, :]
-    Xis = xi[:, None] + delta[None, :]
-    E2 = (etas * etas)[:, None]
-    dLL = 0.5 * delta * (n * np.sum(E2 / (Lam * Lam), axis=0) / np.sum(E2 / Lam, axis=0) - np.sum(1.0 / Xis, axis=0))
-    maxdelta, maxLL = _optimise(dLL, logdelta, llim, ulim, esp, lambda ld: _ml_ll(ld, lam, etas, xi),
-                                lambda ld: _ml_dll(ld, lam, etas, xi))
-    maxva = np.sum(etas * etas / (lam + maxdelta)) / n
-    return {"ML": maxLL, "delta": maxdelta, "ve": maxva * maxdelta, "vg": maxva}
-
-
-# ---------------------------------------------------------------------------------------------------------------------------
-# emma.REMLE / emma.MLE in the eigenbasis of K (K = U diag(lam) U^T, fixed for a whole run), the FaST-LMM identities: with
-# Ut = U^T X, ut = U^T y, w_k = 1/(lam_k + delta), A = Ut^T W Ut, b = Ut^T W ut,
-#     y^T P y = R = ut^T W ut - b^T A^-1 b,   P y = U r,  r = W (ut - Ut A^-1 b),
-#     sum log(eig_R + delta) = sum log(lam + delta) + log det A - log det Ut^T Ut,   tr P = sum w - sum_k w_k^2 (Ut A^-1 Ut^T)_kk,
-# so every likelihood evaluation costs O(n q^2) instead of the n^3 eigen() of S (K + I) S (emma_eigen_R_wo_Z).  The functions are
-# equal in exact arithmetic to _reml_ll / _reml_dll / _ml_ll / _ml_dll; grid, bracket rule and zeroin are emma_REMLE's / emma_MLE's.
-# ---------------------------------------------------------------------------------------------------------------------------
-def _eig_fit(lam, Ut, ut, delta):
-    """w, Ut^T W Ut, W-weighted residual r and R = y^T P y at one delta (R from the residual: no cancellation)."""
-    w = 1.0 / (lam + delta)
-    Uw = Ut * w[:, None]
-    A = Ut.T @ Uw
-    beta = np.linalg.solve(A, Uw.T @ ut)
-    e = ut - Ut @ beta
-    return w, Uw, A, w * e, float(np.sum(w * e * e))
-
-
-def _eig_ll(logdelta, lam, Ut, ut, reml, logdet_xtx):
-    n, q = Ut.shape
-    d = math.exp(logdelta)
-    _, _, A, _, R = _eig_fit(lam, Ut, ut, d)
-    m = n - q if reml else n
-    ll = m * (math.log(m / (2 * math.pi)) - 1 - math.log(R)) - np.sum(np.log(lam + d))
-    if reml:
-        ll -= np.linalg.slogdet(A)[1] - logdet_xtx
-    return 0.5 * ll
-
-
-def _eig_dll(logdelta, lam, Ut, ut, reml):
-    n, q = Ut.shape
-    d = math.exp(logdelta)
-    w, Uw, A, r, R = _eig_fit(lam, Ut, ut, d)
-    trP = np.sum(w)
-    if reml:
-        trP -= np.sum(np.linalg.inv(A) * (Uw.T @ Uw))   # sum_k w_k^2 (Ut A^-1 Ut^T)_kk = tr(A^-1 Ut^T W^2 Ut)
-    return 0.5 * ((n - q if reml else n) * np.sum(r * r) / R - trP)
-
-
-_grid_memo = []   # [(lam, delta, [W | W^2])]: the same lam and grids serve every trait and iteration of a run
-
-
-def _grid_weights(lam, delta):
-    for lm, dl, WW in _grid_memo:
-        if lm is lam and np.array_equal(dl, delta):
-            return WW
-    Wg = 1.0 / (lam[:, None] + delta[None, :])
-    WW = np.hstack([Wg, Wg * Wg])
-    _grid_memo[:] = ([e for e in _grid_memo if e[0] is lam] + [(lam, delta, WW)])[-2:]
-    return WW
-
-
-def _eig_grid_dll(lam, Ut, ut, delta, reml):
-    """dLL/dlogdelta on the whole grid from one GEMM: the n x (q+1)(q+2)/2 products of [Ut | ut] row entries times the n x 2m
-    weights [W | W^2], then (q+1) x (q+1) algebra per grid point."""
-    n, q = Ut.shape
-    B = np.column_stack([Ut, ut])
-    iu, ju = np.triu_indices(q + 1)
-    WW = _grid_weights(lam, delta)
-    S = (B[:, iu] * B[:, ju]).T @ WW                                 # ((q+1)(q+2)/2) x 2m
-    m = delta.size
-    M = np.empty((2 * m, q + 1, q + 1))
-    M[:, iu, ju] = S.T
-    M[:, ju, iu] = S.T
-    S1, S2 = M[:m], M[m:]
-    A, b = S1[:, :q, :q], S1[:, :q, q]
-    beta = np.linalg.solve(A, b[..., None])[..., 0]
-    R = S1[:, q, q] - np.einsum("gi,gi->g", b, beta)
-    r2 = S2[:, q, q] - 2 * np.einsum("gi,gi->g", beta, S2[:, :q, q]) + np.einsum("gi,gij,gj->g", beta, S2[:, :q, :q], beta)
-    trP = WW[:, :m].sum(axis=0)
-    if reml:
-        trP = trP - np.einsum("gij,gji->g", np.linalg.inv(A), S2[:, :q, :q])
-    return 0.5 * delta * ((n - q if reml else n) * r2 / R - trP)
-
-
-def _emma_eig(lam, UtX, Uty, ngrids, llim, ulim, esp, reml):
-    lam = np.asarray(lam, dtype=np.float64).ravel()
-    Ut = np.asarray(UtX, dtype=np.float64).reshape(lam.size, -1)
-    ut = np.asarray(Uty, dtype=np.float64).ravel()
-    n, q = Ut.shape
-    xtx = Ut.T @ Ut                                  # = X^T X (U orthogonal)
-    if np.linalg.det(xtx) == 0:
-        return None
-    logdet_xtx = np.linalg.slogdet(xtx)[1]
-    logdelta, delta = _grid(ngrids, llim, ulim)
-    dLL = _eig_grid_dll(lam, Ut, ut, delta, reml)
-    maxdelta, maxLL = _optimise(dLL, logdelta, llim, ulim, esp, lambda ld: _eig_ll(ld, lam, Ut, ut, reml, logdet_xtx),
-                                lambda ld: _eig_dll(ld, lam, Ut, ut, reml))
-    maxva = _eig_fit(lam, Ut, ut, maxdelta)[4] / (n - q if reml else n)
-    return maxLL, maxdelta, maxva
-
-
-def emma_REMLE_eig(lam, UtX, Uty, ngrids=100, llim=-10, ulim=10, esp=1e-10):
-    """emma_REMLE(y, X, K) from lam, U = eigh(K): UtX = U^T X (n x q), Uty = U^T y.  No n^3 work."""
-    r = _emma_eig(lam, UtX, Uty, ngrids, llim, ulim, esp, True)
-    if r is None:
-        return {"REML": 0, "delta": 0, "ve": 0, "vg": 0}
-    return {"REML": r[0], "delta": r[1], "ve": r[2] * r[1], "vg": r[2]}
-
-
-def emma_MLE_eig(lam, UtX, Uty, ngrids=100, llim=-10, ulim=10, esp=1e-10):
-    """emma_MLE(y, X, K) from lam, U = eigh(K) (the xi of emma_MLE are lam)."""
-    r = _emma_eig(lam, UtX, Uty, ngrids, llim, ulim, esp, False)
-    if r is None:
-        return {"ML": 0, "delta": 0, "ve": 0, "vg": 0}
-    return {"ML": r[0], "delta": r[1], "ve": r[2] * r[1], "vg": r[2]}
-
-
-# ---------------------------------------------------------------------------------------------------------------------------
-# The same for T traits at once (FPR4AM; DESIGN.md section 4.7d).  Trait t has the design [UtX | last[:, t]] (last = None: UtX
-# alone, the null fits of a permutation study) and the trait column UtY[:, t].  The weights [W | W^2] depend on lam only, so the
-# 101-point dLL grid of ALL traits is ONE product of the stacked (T (q+1)(q+2)/2) x n column products with them, through
-# host_model.algebra().mm (the fp64 GEMM of the device with algebra="device"); bracket rule, zeroin and end-point rule then run
-# per trait on the scalar functions of _emma_eig.
-# ---------------------------------------------------------------------------------------------------------------------------
-def _eig_grid_dll_batch(lam, B, delta, reml):
-    """_eig_grid_dll for B = T x n x (q+1), trait t's [Ut_t | ut_t]: T x m values of dLL/dlogdelta from one GEMM."""
-    T, n, q1 = B.shape
-    q = q1 - 1
-    iu, ju = np.triu_indices(q1)
-    WW = _grid_weights(lam, delta)
-    PT = np.ascontiguousarray((B[:, :, iu] * B[:, :, ju]).transpose(0, 2, 1)).reshape(T * iu.size, n)
-    S = np.asarray(host_model.algebra().mm(PT, WW)).reshape(T, iu.size, -1)      # (T (q+1)(q+2)/2) x 2m in one product
-    m = delta.size
-    M = np.empty((T, 2 * m, q1, q1))
-    M[:, :, iu, ju] = S.transpose(0, 2, 1)
-    M[:, :, ju, iu] = S.transpose(0, 2, 1)
-    S1, S2 = M[:, :m], M[:, m:]
-    A, b = S1[..., :q, :q], S1[..., :q, q]
-    beta = np.linalg.solve(A, b[..., None])[..., 0]
-    R = S1[..., q, q] - np.einsum("tgi,tgi->tg", b, beta)
-    r2 = S2[..., q, q] - 2 * np.einsum("tgi,tgi->tg", beta, S2[..., :q, q]) + np.einsum("tgi,tgij,tgj->tg", beta, S2[..., :q, :q], beta)
-    trP = WW[:, :m].sum(axis=0)[None, :]
-    if reml:
-        trP = trP - np.einsum("tgij,tgji->tg", np.linalg.inv(A), S2[..., :q, :q])
-    return 0.5 * delta[None, :] * ((n - q if reml else n) * r2 / R - trP)
-
-
-def _emma_eig_batch(lam, UtX, UtY, last, ngrids, llim, ulim, esp, reml):
-    """-> (LL, delta, va), T each; a trait whose X^T X is singular gets 0, 0, 0 (emma_REMLE.R:28-30)."""
-    lam = np.asarray(lam, dtype=np.float64).ravel()
-    n = lam.size
-    Ut0 = np.asarray(UtX, dtype=np.float64).reshape(n, -1)
-    UtY = np.asarray(UtY, dtype=np.float64).reshape(n, -1)
-    T, q0 = UtY.shape[1], Ut0.shape[1]
-    q = q0 if last is None else q0 + 1
-    B = np.empty((T, n, q + 1))
-    B[:, :, :q0] = Ut0[None]
-    if last is not None:
-        last = np.asarray(last, dtype=np.float64).reshape(n, -1)
-        if last.shape[1] != T:
-            raise ValueError("one last column per trait: %d for %d traits" % (last.shape[1], T))
-        B[:, :, q0] = last.T
-    B[:, :, q] = UtY.T
-    LL, dl, va = np.zeros(T), np.zeros(T), np.zeros(T)
-    xtx = [Ut0.T @ Ut0] * T if last is None else [B[t, :, :q].T @ B[t, :, :q] for t in range(T)]    # = X_t^T X_t (U orthogonal)
-    ok = [t for t in range(T) if np.linalg.det(xtx[t]) != 0]
-    if not ok:
-        return LL, dl, va
-    logdelta, delta = _grid(ngrids, llim, ulim)
-    dLL = _eig_grid_dll_batch(lam, B if len(ok) == T else B[ok], delta, reml)
-    for k, t in enumerate(ok):
-        Ut, ut = np.ascontiguousarray(B[t, :, :q]), np.ascontiguousarray(B[t, :, q])
-        logdet_xtx = np.linalg.slogdet(xtx[t])[1]
-        dl[t], LL[t] = _optimise(dLL[k], logdelta, llim, ulim, esp, lambda ld: _eig_ll(ld, lam, Ut, ut, reml, logdet_xtx),
-                                 lambda ld: _eig_dll(ld, lam, Ut, ut, reml))
-        va[t] = _eig_fit(lam, Ut, ut, dl[t])[4] / (n - q if reml else n)
-    return LL, dl, va
-
-
-def emma_REMLE_eig_batch(lam, UtX, UtY, last=None, ngrids=100, llim=-10, ulim=10, esp=1e-10):
-    """emma_REMLE_eig for the T columns of UtY (n x T): the design of trait t is UtX (n x q, shared), with last (n x T) given
-    [UtX | last[:, t]].  Returns {"REML", "delta", "ve", "vg"} of arrays of length T."""
-    LL, dl, va = _emma_eig_batch(lam, UtX, UtY, last, ngrids, llim, ulim, esp, True)
-    return {"REML": LL, "delta": dl, "ve": va * dl, "vg": va}
-
-
-def emma_MLE_eig_batch(lam, UtX, UtY, last=None, ngrids=100, llim=-10, ulim=10, esp=1e-10):
-    """emma_MLE_eig for the T columns of UtY; arguments as emma_REMLE_eig_batch.  Returns {"ML", "delta", "ve", "vg"}."""
-    LL, dl, va = _emma_eig_batch(lam, UtX, UtY, last, ngrids, llim, ulim, esp, False)
-    return {"ML": LL, "delta": dl, "ve": va * dl, "vg": va}
-
-
-# ---------------------------------------------------------------------------------------------------------------------------
-# emma.REMLE / emma.MLE with a Z matrix (emma_REMLE.R:78-128, emma_MLE.R:58-105) in the reduced form of host_model.ZModel: with
-# lam, U = eigh(D^1/2 K D^1/2) -- lam are the eigenvalues of the reference's non-symmetric K Z^T Z (emma_eigen_L_w_Z.R:8) --,
-# Ut = U^T D^-1/2 Z^T X, ut likewise and Wn the Gram matrix of the rows of [X | y] centred within their individual, H/vg = delta I +
-# Z K Z^T has the eigenvalues lam + delta on t directions and delta on the other n - t, so
-#     A = X^T (H/vg)^-1 X = Ut^T W Ut + Wn_xx / delta,      R = y^T P y = sum w e^2 + [beta; -1]^T Wn [beta; -1] / delta,
-#     log det = sum log(lam + delta) + (n - t) log delta,    tr (H/vg)^-1 = sum w + (n - t) / delta
-# -- the etas.2.sq / delta and (n - t) / delta terms of emma_REMLE.R:92-94.  n is the number of records.  Grid, bracket rule, zeroin
-# and end-point rule are _optimise, as without Z.  The reference's eigen-route takes only t - q of the t eigenvalues of S Z K Z^T S,
-# which is the whole spectrum exactly when every column of X is constant within an individual (X in the column space of Z: the
-# intercept, a per-line covariate, a marker column Z m_j); there this equals it, otherwise this is the likelihood of the model and the
-# reference's route is not (DESIGN.md section 4.7c).
-# ---------------------------------------------------------------------------------------------------------------------------
-def as_ind_of_obs(Z):
-    """ind_of_obs (0-based int64) from either form of a Z matrix: the vector itself, or the dense n_obs x t 0/1 matrix."""
-    Z = np.asarray(Z)
-    if Z.ndim == 2:
-        from . import r_api
-        return r_api.zmat_index(Z)
-    return Z.astype(np.int64).ravel()
-
-
-def _z_fit(lam, Ut, ut, Wn, delta):
-    q = Ut.shape[1]
-    w = 1.0 / (lam + delta)
-    Uw = Ut * w[:, None]
-    A = Ut.T @ Uw + Wn[:q, :q] / delta
-    beta = np.linalg.solve(A, Uw.T @ ut + Wn[:q, q] / delta)
-    e = ut - Ut @ beta
-    c = np.append(beta, -1.0)
-    rw = max(float(c @ Wn @ c), 0.0)                  # the within-individual residual sum of squares at beta
-    return w, Uw, A, w * e, rw, float(np.sum(w * e * e)) + rw / delta
-
-
-def _z_ll(logdelta, lam, Ut, ut, Wn, n, reml, logdet_xtx):
-    t, q = Ut.shape
-    d = math.exp(logdelta)
-    _, _, A, _, _, R = _z_fit(lam, Ut, ut, Wn, d)
-    m = n - q if reml else n
-    ll = m * (math.log(m / (2 * math.pi)) - 1 - math.log(R)) - np.sum(np.log(lam + d)) - (n - t) * logdelta
-    if reml:
-        ll -= np.linalg.slogdet(A)[1] - logdet_xtx
-    return 0.5 * ll
-
-
-def _z_dll(logdelta, lam, Ut, ut, Wn, n, reml):
-    t, q = Ut.shape
-    d = math.exp(logdelta)
-    w, Uw, A, r, rw, R = _z_fit(lam, Ut, ut, Wn, d)
-    trP = np.sum(w) + (n - t) / d
-    if reml:
-        trP -= np.sum(np.linalg.inv(A) * (Uw.T @ Uw + Wn[:q, :q] / (d * d)))
-    return 0.5 * ((n - q if reml else n) * (np.sum(r * r) + rw / (d * d)) / R - trP)
-
-
-def _emma_z(y, X, K, Z, zmodel, ngrids, llim, ulim, esp, reml):
-    if zmodel is None:
-        ind = as_ind_of_obs(Z)
-        vids = np.bincount(ind, minlength=K.shape[0]) > 0            # complete == FALSE: individuals without a record leave K and Z
-        if not vids.all():
-            K = K[np.ix_(vids, vids)]
-            ind = (np.cumsum(vids) - 1)[ind]
-        zmodel = host_model.ZModel(K, ind)
-    lam = zmodel.lam
-    n = zmodel.n_obs
-    if np.size(y) != n or X.shape[0] != n:
-        raise ValueError("emma with Z: %d records in Z, %d in y, %d rows of X" % (n, np.size(y), X.shape[0]))
-    Ut, ut, Wn = zmodel.reduce(X, y)
-    q = Ut.shape[1]
-    logdet_xtx = np.linalg.slogdet(Ut.T @ Ut + Wn[:q, :q])[1]        # = log det X^T X
-    logdelta, delta = _grid(ngrids, llim, ulim)
-    dLL = np.array([dl * _z_dll(ld, lam, Ut, ut, Wn, n, reml) for ld, dl in zip(logdelta, delta)])
-    maxdelta, maxLL = _optimise(dLL, logdelta, llim, ulim, esp, lambda ld: _z_ll(ld, lam, Ut, ut, Wn, n, reml, logdet_xtx),
-                                lambda ld: _z_dll(ld, lam, Ut, ut, Wn, n, reml))
-    maxva = _z_fit(lam, Ut, ut, Wn, maxdelta)[5] / (n - q if reml else n)
-    return maxLL, maxdelta, maxva
-
-
-def calcVC(trait, currentX, MMt, eig_R=None, Z=None, zmodel=None):
+def calcVC(trait, currentX, MMt, eig_R=None, Z=None, zmodel=None, eig_L=None):
+    """eig_L is not used: it is taken so that one set of keywords serves calcVC and calc_extBIC."""
     r = emma_REMLE(trait, currentX, MMt, Z=Z, eig_R=eig_R, zmodel=zmodel)
-    return {"vg": r["vg"], "ve": r["ve"]}
+    return {k: r[k] for k in ("vg", "ve")}
 
 
 def _lchoose(n, k):
     return gammaln(n + 1) - gammaln(k + 1) - gammaln(n - k + 1)
 
 
+def _extBIC(ML, k, n, nmarkers, gamma):
+    """calc_extBIC.R:7-9 for a model of k fixed-effect columns on n records, gamma weighting the model-space term."""
+    return -2 * ML + (k + 1) * math.log(n) + 2 * gamma * _lchoose(nmarkers, k - 1)
+
+
 def calc_extBIC(trait, currentX, MMt, nmarkers, eig_L=None, eig_R=None, Z=None, zmodel=None, gamma=1.0):
     """calc_extBIC.R:1-12 with the weight gamma on the model-space term; gamma = 1 is the reference's
     value bit for bit, 2 * 1.0 being exact."""
     res = emma_MLE(trait, currentX, MMt, Z=Z, llim=-100, ulim=100, eig_L=eig_L, eig_R=eig_R, zmodel=zmodel)
-    BIC = -2 * res["ML"] + (currentX.shape[1] + 1) * math.log(trait.size)
-    return BIC + 2 * gamma * _lchoose(nmarkers, currentX.shape[1] - 1)
+    return _extBIC(res["ML"], currentX.shape[1], trait.size, nmarkers, gamma)
 
 
 class HipBackend:
@@ -480,7 +69,6 @@ class HipBackend:
         """extract_geno.R:8-12: column colnum (1-based) of M.ascii, served from the HBM-resident copy calcMMt left."""
         return self.r_api.extract_geno(geno["asciifileM"], colnum, dim_of_ascii_M=geno["dim_of_ascii_M"],
                                        device=self.device).astype(np.int64)
-
 
     def reshape(self, geno, indxNA):
         """AM.R:345-366 in VIEW mode: drops the individuals indxNA (1-based) from both genotype files without writing either; the
@@ -541,106 +129,95 @@ def reshape_geno(geno, indxNA, view=False, device=0):
     return {"asciifileM": geno["asciifileM"] + "tmp", "asciifileMt": geno["asciifileMt"] + "tmp", "dim_of_ascii_M": newdims}
 
 
-def AM(trait, X, geno, availmemGb=8, ncpu=1, maxit=20, quiet=True, backend=None, message=None, algebra=None, Zmat=None, gamma=1.0):
-    """E/R/AM.R:320-475 for a trait vector and a ready design matrix X (n x q, intercept included).
+def _reshape(geno, indxNA, backend=None, device=0):
+    """geno without the individuals indxNA: backend.reshape, reshape_geno writing the files for a backend without one, or for a
+    caller that has no backend a view on `device`."""
+    if backend is None:
+        return reshape_geno(geno, indxNA, view=True, device=device)
+    return backend.reshape(geno, indxNA) if hasattr(backend, "reshape") else reshape_geno(geno, indxNA)
 
-    Individuals whose trait or any column of X is NaN are dropped (AM.R:320-329: an NA covariate makes the trait NA): from trait
-    and X, and from the genotype files through backend.reshape(geno, indxNA) (AM.R:345-366; reshape_geno writing the files when
-    the backend has no `reshape`).  A trait without NaN makes no such call.
-    Returns dict(selected_loci = 1-based marker columns in order of selection, extBIC = list, ve, vg of the last fit, indxNA = the
-    dropped rows, 1-based and largest first, and dim_of_ascii_M of the genotypes the loop ran on).
-    selected_loci starts as [NA] exactly like AM.R:260, so the selected_loci masking never fires (SURVEY 8a7).
 
-    Zmat: repeated measures (several records per genotyped individual), as r_api.ReadZmat's matrix or as ind_of_obs
-    (r_api.zmat_index); trait and X then have one row per record -- see _AM_z.
-
-    gamma: the weight on extBIC's model-space term (calc_extBIC); 1 is the reference's rule, a smaller value selects more loci.
-    FPR4AM finds the gamma of a wanted false positive rate."""
-    if Zmat is not None:
-        return _AM_z(trait, X, geno, Zmat, availmemGb, ncpu, maxit, quiet, backend, message, algebra, gamma)
-    backend = backend or HipBackend()
-    if algebra is not None:  # "host" (LAPACK, the reference's placement) or "device" (SURVEY 8 f-4: rocSOLVER / the fp64 MFMA GEMM through the C ABI)
-        host_model.set_algebra(algebra)
-    say = message or (lambda *_: None)
-    trait = np.asarray(trait, dtype=np.float64).ravel().copy()
-    currentX = np.asarray(X, dtype=np.float64)
-    trait[np.isnan(currentX).reshape(currentX.shape[0], -1).any(axis=1)] = np.nan   # AM.R:320-329
-    from . import r_api
-    indxNA = r_api.check_for_NA_in_trait(trait)                                     # AM.R:332
-    if indxNA.size:                                                                  # AM.R:337-366
-        keep = np.ones(trait.size, dtype=bool)
-        keep[indxNA - 1] = False
-        trait, currentX = trait[keep], currentX[keep]
+def _drop_na_rows(indxNA, arrays, geno=None, say=None, backend=None, device=0):
+    """AM.R:337-366: the rows indxNA (1-based) leave every one of `arrays`, `say` is told so, and a `geno` is reshaped (_reshape).
+    -> the arrays, geno.  Nothing happens for an empty indxNA."""
+    if not indxNA.size:
+        return arrays, geno
+    keep = np.ones(arrays[0].shape[0], dtype=bool)
+    keep[indxNA - 1] = False
+    if say is not None:
         say(" The following rows are being removed from pheno due to missing data: %s" % " ".join(str(int(i)) for i in indxNA))
-        geno = backend.reshape(geno, indxNA) if hasattr(backend, "reshape") else reshape_geno(geno, indxNA)
-    nmarkers = geno["dim_of_ascii_M"][1]
-    selected_loci = [np.nan]
-    new_selected_locus = np.nan
-    extBIC = []
-    itnum, cont = 1, True
-    MMt = invMMt = eig_L = None
-    best = {}
-    while cont:
-        say("Iteration %d: Searching for most significant marker-trait association" % itnum)
-        if not (isinstance(new_selected_locus, float) and math.isnan(new_selected_locus)):  # constructX.R:10-22
-            currentX = np.column_stack([currentX, backend.extract_geno(geno, int(new_selected_locus)).astype(np.float64)])
-        if itnum == 1:  # AM.R:414-422
-            MMt = backend.calcMMt(geno, availmemGb, ncpu, np.array(selected_loci), quiet)
-            invMMt = host_model._chol2inv(MMt)
-            eig_L = emma_eigen_L_wo_Z(MMt)  # depends on MMt only; the reference recomputes it every iteration
-        eig_R = emma_eigen_R_wo_Z(MMt, currentX)  # shared by REMLE and MLE of this iteration (same K, X)
-        best = calcVC(trait, currentX, MMt, eig_R=eig_R)
-        extBIC.append(calc_extBIC(trait, currentX, MMt, nmarkers, eig_L=eig_L, eig_R=eig_R, gamma=gamma))
-        if int(np.flatnonzero(np.asarray(extBIC) == min(extBIC))[0]) == len(extBIC) - 1:  # AM.R:448
-            new_selected_locus = backend.find_qtl(geno=geno, availmemGb=availmemGb, selected_loci=np.array(selected_loci), MMt=MMt,
-                                                  invMMt=invMMt, best_ve=best["ve"], best_vg=best["vg"], currentX=currentX,
-                                                  ncpu=ncpu, quiet=quiet, trait=trait)
-            selected_loci.append(new_selected_locus)
-        else:
-            cont = False
-        itnum += 1
-        if itnum > maxit:  # AM.R:463-470
-            cont = False
-    # AM.R:476-499.  Stopped by maxit: every pick is reported (the in-loop report that drops the last pick is
-    # overwritten by the one after the loop).  Stopped by extBIC: the last pick made extBIC worse and is dropped
-    # together with its extBIC entry.
-    picks = [int(v) for v in selected_loci[1:]]
-    if itnum > maxit or len(selected_loci) <= 1:
-        loci, ext = picks, list(extBIC)
+    return [a[keep] for a in arrays], geno if geno is None else _reshape(geno, indxNA, backend, device)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The forward-selection loop (AM.R:400-499), its rules stated once for AM() with and without Zmat and for AM_traits: a run's
+# state is a dict of sel (the picks after the leading NA of AM.R:260), ext (the extBIC trace), best (the last ve, vg), itnum, cont.
+# ---------------------------------------------------------------------------------------------------------------------------
+def _loop_state(**more):
+    return dict({"sel": [np.nan], "ext": [], "best": {}, "itnum": 1, "cont": True}, **more)
+
+
+def _still_improving(extBIC):
+    """AM.R:448: the search goes on while the newest extBIC is the first minimum of the trace."""
+    return int(np.flatnonzero(np.asarray(extBIC) == min(extBIC))[0]) == len(extBIC) - 1
+
+
+def _end_iteration(s, maxit):
+    s["itnum"] += 1
+    if s["itnum"] > maxit:  # AM.R:463-470
+        s["cont"] = False
+
+
+def _AM_result(s, maxit, indxNA, geno):
+    """AM.R:476-499.  Stopped by maxit: every pick is reported (the in-loop report that drops the last pick is overwritten by
+    the one after the loop).  Stopped by extBIC: the last pick made extBIC worse and is dropped together with its extBIC entry."""
+    picks = [int(v) for v in s["sel"][1:]]
+    if s["itnum"] > maxit or len(s["sel"]) <= 1:
+        loci, ext = picks, list(s["ext"])
     else:
         loci = picks[:-1]
-        ext = [v for i, v in enumerate(extBIC) if i != len(selected_loci) - 1]
-    return {"selected_loci": loci, "all_picks": picks, "extBIC": ext, "extBIC_trace": list(extBIC), "ve": best.get("ve"),
-            "vg": best.get("vg"), "indxNA": indxNA, "dim_of_ascii_M": list(geno["dim_of_ascii_M"])}
+        ext = [v for i, v in enumerate(s["ext"]) if i != len(s["sel"]) - 1]
+    return {"selected_loci": loci, "all_picks": picks, "extBIC": ext, "extBIC_trace": list(s["ext"]), "ve": s["best"].get("ve"),
+            "vg": s["best"].get("vg"), "indxNA": indxNA, "dim_of_ascii_M": list(geno["dim_of_ascii_M"])}
 
 
-def _AM_result(selected_loci, extBIC, itnum, maxit, best, indxNA, geno):
-    """AM.R:476-499 (see AM())."""
-    picks = [int(v) for v in selected_loci[1:]]
-    if itnum > maxit or len(selected_loci) <= 1:
-        loci, ext = picks, list(extBIC)
-    else:
-        loci = picks[:-1]
-        ext = [v for i, v in enumerate(extBIC) if i != len(selected_loci) - 1]
-    return {"selected_loci": loci, "all_picks": picks, "extBIC": ext, "extBIC_trace": list(extBIC), "ve": best.get("ve"),
-            "vg": best.get("vg"), "indxNA": indxNA, "dim_of_ascii_M": list(geno["dim_of_ascii_M"])}
+def _plain_model(backend):
+    """Where AM()'s loop depends on the model, for one record per individual -> prepare (the first iteration, AM.R:414-422; returns
+    MMt), fit_kw (X -> what calcVC and calc_extBIC of one iteration share), column (a marker column as it enters X), scan_kw (the
+    model's keywords of find_qtl)."""
+    k = {}
+
+    def prepare(geno, *args):
+        k["MMt"] = backend.calcMMt(geno, *args)
+        k["invMMt"] = host_model._chol2inv(k["MMt"])
+        k["eig_L"] = emma_eigen_L_wo_Z(k["MMt"])  # depends on MMt only; the reference recomputes it every iteration
+        return k["MMt"]
+
+    return (prepare, lambda X: {"eig_L": k["eig_L"], "eig_R": emma_eigen_R_wo_Z(k["MMt"], X)}, lambda m: m,
+            lambda: {"invMMt": k["invMMt"]})
 
 
-def _AM_z(trait, X, geno, Zmat, availmemGb, ncpu, maxit, quiet, backend, message, algebra, gamma=1.0):
-    """AM() for y = X b + Z g + e: trait and X hold one row per RECORD, Zmat says whose record each is.
+def _z_model(backend, ind):
+    """_plain_model for AM(Zmat=), ind = ind_of_obs: K alone, then the one eigh of the run (ZModel) and the backend's Z build; a marker
+    enters X as Z m_j."""
+    k = {}
+
+    def prepare(geno, availmemGb, *args):
+        MMt = getattr(backend, "calcMMt_plain", backend.calcMMt)(geno, availmemGb, *args)
+        k["zm"] = host_model.ZModel(MMt, ind)
+        if hasattr(backend, "prepare_z"):
+            backend.prepare_z(geno, k["zm"], availmemGb)
+        return MMt
+
+    return prepare, lambda X: {"zmodel": k["zm"]}, lambda m: np.ravel(m)[ind], lambda: {"invMMt": None, "Zmat": k["zm"]}
+
+
+def _z_rows(trait, currentX, geno, Zmat, backend, say):
+    """The checks and the NA handling of AM(Zmat=) -> trait, X, ind_of_obs, geno, indxNA, indxNA_obs.
 
     Checks as check_inputs_mlam.R:122-145.  A record with NaN in trait or X is dropped (from trait, X and Z; the result's
     indxNA_obs, 1-based, largest first); an individual left without any record is dropped from the genotypes through
-    backend.reshape (indxNA, as in AM(); the reference's complete == FALSE rule) and the others are renumbered.  Variance
-    components and extBIC are emma_REMLE / emma_MLE with Z, n = the number of records; the scan runs over the t individuals with
-    operands from Z^T P Z and Z^T P y (host_model.scan_operands_z), and a selected marker enters X as Z m_j.  The reference's own
-    AM() cannot run this model (its .find_qtl takes no Z): the scan is this project's definition."""
-    backend = backend or HipBackend()
-    if algebra is not None:
-        host_model.set_algebra(algebra)
-    say = message or (lambda *_: None)
-    trait = np.asarray(trait, dtype=np.float64).ravel().copy()
-    currentX = np.asarray(X, dtype=np.float64)
+    backend.reshape (indxNA, as in AM(); the reference's complete == FALSE rule) and the others are renumbered."""
     n_ind = int(geno["dim_of_ascii_M"][0])
     Zm = np.asarray(Zmat)
     if Zm.ndim == 2 and Zm.shape[1] != n_ind:                                        # check_inputs_mlam.R:124-130
@@ -661,49 +238,72 @@ def _AM_z(trait, X, geno, Zmat, availmemGb, ncpu, maxit, quiet, backend, message
     trait[np.isnan(currentX).any(axis=1)] = np.nan                                   # AM.R:320-329, per record
     from . import r_api
     indxNA_obs = r_api.check_for_NA_in_trait(trait)
-    if indxNA_obs.size:
-        keep = np.ones(trait.size, dtype=bool)
-        keep[indxNA_obs - 1] = False
-        trait, currentX, ind = trait[keep], currentX[keep], ind[keep]
-        say(" The following rows are being removed from pheno due to missing data: %s" % " ".join(str(int(i)) for i in indxNA_obs))
+    (trait, currentX, ind), _ = _drop_na_rows(indxNA_obs, (trait, currentX, ind), say=say)
     has = np.bincount(ind, minlength=n_ind) > 0
     indxNA = (np.flatnonzero(~has) + 1)[::-1].copy()                                 # individuals, 1-based, largest first
     if indxNA.size:
         ind = (np.cumsum(has) - 1)[ind]
         say(" The following individuals have no record and are being removed from the genotypes: %s" % " ".join(str(int(i)) for i in indxNA))
-        geno = backend.reshape(geno, indxNA) if hasattr(backend, "reshape") else reshape_geno(geno, indxNA)
+        geno = _reshape(geno, indxNA, backend)
+    return trait, currentX, ind, geno, indxNA, indxNA_obs
+
+
+def AM(trait, X, geno, availmemGb=8, ncpu=1, maxit=20, quiet=True, backend=None, message=None, algebra=None, Zmat=None, gamma=1.0):
+    """E/R/AM.R:320-475 for a trait vector and a ready design matrix X (n x q, intercept included).
+
+    Individuals whose trait or any column of X is NaN are dropped (AM.R:320-329: an NA covariate makes the trait NA): from trait
+    and X, and from the genotype files through backend.reshape(geno, indxNA) (AM.R:345-366; reshape_geno writing the files when
+    the backend has no `reshape`).  A trait without NaN makes no such call.
+    Returns dict(selected_loci = 1-based marker columns in order of selection, extBIC = list, ve, vg of the last fit, indxNA = the
+    dropped rows, 1-based and largest first, and dim_of_ascii_M of the genotypes the loop ran on).
+    selected_loci starts as [NA] exactly like AM.R:260, so the selected_loci masking never fires (SURVEY 8a7).
+
+    Zmat: repeated measures (several records per genotyped individual), y = X b + Z g + e, as r_api.ReadZmat's matrix or as
+    ind_of_obs (r_api.zmat_index); trait and X then have one row per RECORD and Zmat says whose record each is (DESIGN.md section
+    4.7c; checks and NA handling: _z_rows, the result also has indxNA_obs).  Variance components and extBIC are emma_REMLE /
+    emma_MLE with Z, n = the number of records; the scan runs over the t individuals with operands from Z^T P Z and Z^T P y
+    (host_model.scan_operands_z), and a selected marker enters X as Z m_j.  The reference's own AM() cannot run this model (its
+    .find_qtl takes no Z): the scan is this project's definition.
+
+    gamma: the weight on extBIC's model-space term (calc_extBIC); 1 is the reference's rule, a smaller value selects more loci.
+    FPR4AM finds the gamma of a wanted false positive rate."""
+    backend = backend or HipBackend()
+    if algebra is not None:  # "host" (LAPACK, the reference's placement) or "device" (SURVEY 8 f-4: rocSOLVER / the fp64 MFMA GEMM through the C ABI)
+        host_model.set_algebra(algebra)
+    say = message or (lambda *_: None)
+    trait = np.asarray(trait, dtype=np.float64).ravel().copy()
+    currentX = np.asarray(X, dtype=np.float64)
+    extra = {}
+    if Zmat is None:
+        trait[np.isnan(currentX).reshape(currentX.shape[0], -1).any(axis=1)] = np.nan   # AM.R:320-329
+        from . import r_api
+        indxNA = r_api.check_for_NA_in_trait(trait)                                     # AM.R:332
+        (trait, currentX), geno = _drop_na_rows(indxNA, (trait, currentX), geno, say, backend)
+        prepare, fit_kw, column, scan_kw = _plain_model(backend)
+    else:
+        trait, currentX, ind, geno, indxNA, extra["indxNA_obs"] = _z_rows(trait, currentX, geno, Zmat, backend, say)
+        prepare, fit_kw, column, scan_kw = _z_model(backend, ind)
     nmarkers = geno["dim_of_ascii_M"][1]
-    selected_loci = [np.nan]
-    new_selected_locus = np.nan
-    extBIC = []
-    itnum, cont = 1, True
-    MMt = zm = None
-    best = {}
-    while cont:
-        say("Iteration %d: Searching for most significant marker-trait association" % itnum)
-        if not (isinstance(new_selected_locus, float) and math.isnan(new_selected_locus)):
-            m = backend.extract_geno(geno, int(new_selected_locus)).astype(np.float64)
-            currentX = np.column_stack([currentX, np.ravel(m)[ind]])                 # Z m_j
-        if itnum == 1:
-            MMt = getattr(backend, "calcMMt_plain", backend.calcMMt)(geno, availmemGb, ncpu, np.array(selected_loci), quiet)
-            zm = host_model.ZModel(MMt, ind)                                         # the one eigh of the run
-            if hasattr(backend, "prepare_z"):
-                backend.prepare_z(geno, zm, availmemGb)
-        best = calcVC(trait, currentX, MMt, zmodel=zm)
-        extBIC.append(calc_extBIC(trait, currentX, MMt, nmarkers, zmodel=zm, gamma=gamma))
-        if int(np.flatnonzero(np.asarray(extBIC) == min(extBIC))[0]) == len(extBIC) - 1:  # AM.R:448
-            new_selected_locus = backend.find_qtl(geno=geno, availmemGb=availmemGb, selected_loci=np.array(selected_loci), MMt=MMt,
-                                                  invMMt=None, best_ve=best["ve"], best_vg=best["vg"], currentX=currentX,
-                                                  ncpu=ncpu, quiet=quiet, trait=trait, Zmat=zm)
-            selected_loci.append(new_selected_locus)
+    s = _loop_state()
+    MMt = None
+    while s["cont"]:
+        say("Iteration %d: Searching for most significant marker-trait association" % s["itnum"])
+        new = s["sel"][-1]
+        if not (isinstance(new, float) and math.isnan(new)):  # constructX.R:10-22: NA, no pick yet
+            currentX = np.column_stack([currentX, column(backend.extract_geno(geno, int(new)).astype(np.float64))])
+        if s["itnum"] == 1:
+            MMt = prepare(geno, availmemGb, ncpu, np.array(s["sel"]), quiet)
+        kw = fit_kw(currentX)  # shared by REMLE and MLE of this iteration (same K, X)
+        s["best"] = calcVC(trait, currentX, MMt, **kw)
+        s["ext"].append(calc_extBIC(trait, currentX, MMt, nmarkers, gamma=gamma, **kw))
+        if _still_improving(s["ext"]):
+            s["sel"].append(backend.find_qtl(geno=geno, availmemGb=availmemGb, selected_loci=np.array(s["sel"]), MMt=MMt,
+                                             best_ve=s["best"]["ve"], best_vg=s["best"]["vg"], currentX=currentX, ncpu=ncpu,
+                                             quiet=quiet, trait=trait, **scan_kw()))
         else:
-            cont = False
-        itnum += 1
-        if itnum > maxit:
-            cont = False
-    out = _AM_result(selected_loci, extBIC, itnum, maxit, best, indxNA, geno)
-    out["indxNA_obs"] = indxNA_obs
-    return out
+            s["cont"] = False
+        _end_iteration(s, maxit)
+    return dict(_AM_result(s, maxit, indxNA, geno), **extra)
 
 
 def AM_traits(Y, X, geno, availmemGb=8, maxit=20, quiet=True, message=None, algebra=None, device=0, Zmat=None, gamma=1.0):
@@ -736,11 +336,7 @@ def AM_traits(Y, X, geno, availmemGb=8, maxit=20, quiet=True, message=None, alge
     say = message or (lambda *_: None)
     na_row = np.isnan(Y).any(axis=1) | np.isnan(currentX).any(axis=1)
     indxNA = r_api.check_for_NA_in_trait(np.where(na_row, np.nan, 0.0))
-    if indxNA.size:
-        keep = ~na_row
-        Y, currentX = Y[keep], currentX[keep]
-        say(" The following rows are being removed from pheno due to missing data: %s" % " ".join(str(int(i)) for i in indxNA))
-        geno = reshape_geno(geno, indxNA, view=True, device=device)
+    (Y, currentX), geno = _drop_na_rows(indxNA, (Y, currentX), geno, say, device=device)
     n, nmarkers = geno["dim_of_ascii_M"]
     MMt = r_api.calcMMt(geno, availmemGb, 1, np.array([np.nan]), quiet, device=device)
     lam, U = host_model.algebra().eigh(MMt)
@@ -750,7 +346,7 @@ def AM_traits(Y, X, geno, availmemGb=8, maxit=20, quiet=True, message=None, alge
     UtY = U.T @ Y
     UtX0 = U.T @ currentX
     del U
-    st = [{"UtX": UtX0, "sel": [np.nan], "ext": [], "best": {}, "itnum": 1, "cont": True} for _ in range(T)]
+    st = [_loop_state(UtX=UtX0) for _ in range(T)]
     while any(s["cont"] for s in st):
         active = [s for s in st if s["cont"]]
         scan = []
@@ -759,11 +355,10 @@ def AM_traits(Y, X, geno, availmemGb=8, maxit=20, quiet=True, message=None, alge
                 continue
             say("Trait %d, iteration %d: Searching for most significant marker-trait association" % (t + 1, s["itnum"]))
             r = emma_REMLE_eig(lam, s["UtX"], UtY[:, t])                                         # calcVC
-            s["best"] = {"vg": r["vg"], "ve": r["ve"]}
+            s["best"] = {k: r[k] for k in ("vg", "ve")}
             ml = emma_MLE_eig(lam, s["UtX"], UtY[:, t], llim=-100, ulim=100)                     # calc_extBIC
-            k = s["UtX"].shape[1]
-            s["ext"].append(-2 * ml["ML"] + (k + 1) * math.log(n) + 2 * gamma * _lchoose(nmarkers, k - 1))
-            if int(np.flatnonzero(np.asarray(s["ext"]) == min(s["ext"]))[0]) == len(s["ext"]) - 1:   # AM.R:448
+            s["ext"].append(_extBIC(ml["ML"], s["UtX"].shape[1], n, nmarkers, gamma))
+            if _still_improving(s["ext"]):
                 scan.append(t)
             else:
                 s["cont"] = False
@@ -777,20 +372,8 @@ def AM_traits(Y, X, geno, availmemGb=8, maxit=20, quiet=True, message=None, alge
                 st[t]["sel"].append(int(res["index"][j]))
                 st[t]["UtX"] = np.column_stack([st[t]["UtX"], rows[:, j]])
         for s in active:
-            s["itnum"] += 1
-            if s["itnum"] > maxit:                                                                # AM.R:463-470
-                s["cont"] = False
-    out = []
-    for s in st:   # AM.R:476-499, as in AM()
-        picks = [int(v) for v in s["sel"][1:]]
-        if s["itnum"] > maxit or len(s["sel"]) <= 1:
-            loci, ext = picks, list(s["ext"])
-        else:
-            loci = picks[:-1]
-            ext = [v for i, v in enumerate(s["ext"]) if i != len(s["sel"]) - 1]
-        out.append({"selected_loci": loci, "all_picks": picks, "extBIC": ext, "extBIC_trace": list(s["ext"]), "ve": s["best"].get("ve"),
-                    "vg": s["best"].get("vg"), "indxNA": indxNA, "dim_of_ascii_M": list(geno["dim_of_ascii_M"])})
-    return out
+            _end_iteration(s, maxit)
+    return [_AM_result(s, maxit, indxNA, geno) for s in st]
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -864,11 +447,7 @@ def FPR4AM(trait, X, geno, falseposrate=0.05, numreps=200, seed=101, availmemGb=
     say = message or (lambda *_: None)
     y[np.isnan(X0).any(axis=1)] = np.nan                                             # AM.R:320-329
     indxNA = r_api.check_for_NA_in_trait(y)
-    if indxNA.size:
-        keep = ~np.isnan(y)
-        y, X0 = y[keep], X0[keep]
-        say(" The following rows are being removed from pheno due to missing data: %s" % " ".join(str(int(i)) for i in indxNA))
-        geno = reshape_geno(geno, indxNA, view=True, device=device)
+    (y, X0), geno = _drop_na_rows(indxNA, (y, X0), geno, say, device=device)
     n, L = (int(v) for v in geno["dim_of_ascii_M"])
     if y.size != n:
         raise ValueError("FPR4AM: %d trait records for %d genotyped individuals" % (y.size, n))
@@ -981,10 +560,22 @@ def _summary_eig(lam, maxK, Ft, ut, q, names, say):
             "R": {"Marker_name": rnames, "Prop_var_explained": rsq}}
 
 
-def _summary_K(backend, geno, availmemGb, eig):
-    """K by calcMMt with selected_loci = NA (summary_am.R:140; the masking never fires), max(K), and lam, U: eig
-    when given, else one eigh of K."""
-    n = geno["dim_of_ascii_M"][0]
+def _say_none(say):
+    """The two messages of a model without picks -> None, what its summary is."""
+    for m in _SUMMARY_NONE:
+        say(m)
+
+
+def _summary_setup(who, indxNA, arrays, geno, map, xnames, availmemGb, eig, backend):
+    """What SummaryAM and SummaryAM_traits share once a trait has a pick: the rows indxNA leave `arrays` (X first) and the genotypes
+    (backend.reshape, or reshape_geno writing files for a backend without one); the names; K by calcMMt with selected_loci = NA
+    (summary_am.R:140; the masking never fires), max(K), and lam, U: eig when given, else one eigh of K.
+    -> arrays, geno, colnames of X, j -> marker name, max(K), lam, U."""
+    arrays, geno = _drop_na_rows(indxNA, arrays, geno, backend=backend)
+    n, L = geno["dim_of_ascii_M"]
+    if arrays[0].shape[0] != n:
+        raise ValueError("%s: %d trait records for %d genotyped individuals" % (who, arrays[0].shape[0], n))
+    xn, mname = _summary_names(arrays[0].shape[1], xnames, map, L)
     K = backend.calcMMt(geno, availmemGb, 1, np.array([np.nan]), True)
     maxK = float(np.max(K))
     if eig is None:
@@ -993,7 +584,25 @@ def _summary_K(backend, geno, availmemGb, eig):
         lam, U = eig
         if np.size(lam) != n or np.shape(U) != (n, n):
             raise ValueError("SummaryAM: eig holds %d eigenvalues, the genotypes %d individuals" % (np.size(lam), n))
-    return maxK, np.ascontiguousarray(lam, dtype=np.float64).ravel(), U
+    return arrays, geno, xn, mname, maxK, np.ascontiguousarray(lam, dtype=np.float64).ravel(), U
+
+
+def SummaryAM(AMobj, trait, X, geno, map=None, xnames=None, availmemGb=8, eig=None, backend=None, message=None, device=0):
+    """summary_am.R:78-221 for the dict AM() returns; r_api.SummaryAM, which forwards here, documents arguments and result.  The
+    rows to drop are AMobj["indxNA"]; the marker columns come from extract_geno and enter one product U^T [X | m_j1 .. m_jk | y]."""
+    say = message or (lambda *_: None)
+    picks = [int(j) for j in AMobj["selected_loci"]]
+    if not picks:
+        return _say_none(say)
+    backend = backend or HipBackend(device)
+    y = np.asarray(trait, dtype=np.float64).ravel()
+    X = np.asarray(X, dtype=np.float64).reshape(y.size, -1)
+    indxNA = np.asarray(AMobj.get("indxNA", ()), dtype=np.int64).ravel()
+    (X, y), geno, xn, mname, maxK, lam, U = _summary_setup("SummaryAM", indxNA, (X, y), geno, map, xnames, availmemGb, eig, backend)
+    q = X.shape[1]
+    F = np.column_stack([X] + [backend.extract_geno(geno, j).astype(np.float64) for j in picks] + [y])   # constructX, :131-137
+    Ft = host_model.algebra().mm(U.T, F)
+    return _summary_eig(lam, maxK, Ft[:, :-1], Ft[:, -1], q, xn + [mname(j) for j in picks], say)
 
 
 def SummaryAM_traits(results, Y, X, geno, map=None, xnames=None, availmemGb=8, eig=None, backend=None, message=None, device=0):
@@ -1012,22 +621,12 @@ def SummaryAM_traits(results, Y, X, geno, map=None, xnames=None, availmemGb=8, e
         raise ValueError("SummaryAM_traits: %d results for %d traits" % (len(results), Y.shape[1]))
     picks = [[int(j) for j in r["selected_loci"]] for r in results]
     if not any(picks):
-        for _ in picks:
-            for m in _SUMMARY_NONE:
-                say(m)
-        return [None] * len(picks)
+        return [_say_none(say) for _ in picks]
     backend = backend or HipBackend(device)
     na_row = np.isnan(Y).any(axis=1) | np.isnan(X).any(axis=1)
     indxNA = r_api.check_for_NA_in_trait(np.where(na_row, np.nan, 0.0))
-    if indxNA.size:
-        Y, X = Y[~na_row], X[~na_row]
-        geno = backend.reshape(geno, indxNA) if hasattr(backend, "reshape") else reshape_geno(geno, indxNA)
-    n, L = geno["dim_of_ascii_M"]
-    if Y.shape[0] != n:
-        raise ValueError("SummaryAM_traits: %d trait records for %d genotyped individuals" % (Y.shape[0], n))
+    (X, Y), geno, xn, mname, maxK, lam, U = _summary_setup("SummaryAM_traits", indxNA, (X, Y), geno, map, xnames, availmemGb, eig, backend)
     q = X.shape[1]
-    xn, mname = _summary_names(q, xnames, map, L)
-    maxK, lam, U = _summary_K(backend, geno, availmemGb, eig)
     la = host_model.algebra()
     UtXY = la.mm(U.T, np.column_stack([X, Y]))
     union = sorted({j for pk in picks for j in pk})
@@ -1039,9 +638,7 @@ def SummaryAM_traits(results, Y, X, geno, map=None, xnames=None, availmemGb=8, e
     out = []
     for t, pk in enumerate(picks):
         if not pk:
-            for m in _SUMMARY_NONE:
-                say(m)
-            out.append(None)
+            out.append(_say_none(say))
             continue
         Ft = np.column_stack([UtXY[:, :q], UtM[:, [col[j] for j in pk]]])
         out.append(_summary_eig(lam, maxK, Ft, UtXY[:, q + t], q, xn + [mname(j) for j in pk], say))

@@ -8,7 +8,7 @@
   ReshapeM ............... E/R/ReshapeM.R:1-11
   check_for_NA_in_trait .. E/R/check_for_NA_in_trait.R:1-25
   ReadZmat ............... E/R/ReadZmat.R:34-111     (zmat_index: the matrix as the vector ind_of_obs)
-  SummaryAM .............. E/R/summary_am.R:78-221   (in the eigenbasis of K; am._summary_eig)
+  SummaryAM .............. E/R/summary_am.R:78-221   (in the eigenbasis of K; am.SummaryAM)
 
 `geno` is the reference's list {asciifileM, asciifileMt, dim_of_ascii_M = (n, L)} (E/R/ReadMarker.R:306-307).
 selected_loci follow R: 1-based, NA = numpy.nan.  The "-1 only if no NA anywhere" rule
@@ -280,7 +280,7 @@ def ReadMarker(filename=None, type="text", missing=None, AA=None, AB=None, BB=No
 
 
 def SummaryAM(AMobj, trait, X, geno, map=None, xnames=None, availmemGb=8, eig=None, backend=None, message=None, device=0):
-    """E/R/summary_am.R:78-221 for the dict am.AM() returns, in the eigenbasis of K (am._summary_eig): the Wald table of
+    """E/R/summary_am.R:78-221 for the dict am.AM() returns, in the eigenbasis of K (am.SummaryAM): the Wald table of
     [X | the picked markers] and the share of phenotype variance explained as the picks are added one at a time.
 
     trait, X and geno are what AM() was given, NaN included: the rows AMobj["indxNA"] are dropped from trait and X, and from the
@@ -296,30 +296,8 @@ def SummaryAM(AMobj, trait, X, geno, map=None, xnames=None, availmemGb=8, eig=No
     "Prop_var_explained"}} of plain lists.  p_value is 1 - pchisq(W, 1) as the reference computes it (0 once W passes ~75);
     W keeps the evidence of those effects."""
     from . import am
-    say = message or (lambda *_: None)
-    picks = [int(j) for j in AMobj["selected_loci"]]
-    if not picks:
-        for m in am._SUMMARY_NONE:
-            say(m)
-        return None
-    backend = backend or am.HipBackend(device)
-    y = np.asarray(trait, dtype=np.float64).ravel()
-    X = np.asarray(X, dtype=np.float64).reshape(y.size, -1)
-    indxNA = np.asarray(AMobj.get("indxNA", ()), dtype=np.int64).ravel()
-    if indxNA.size:
-        keep = np.ones(y.size, dtype=bool)
-        keep[indxNA - 1] = False
-        y, X = y[keep], X[keep]
-        geno = backend.reshape(geno, indxNA) if hasattr(backend, "reshape") else am.reshape_geno(geno, indxNA)
-    n, L = geno["dim_of_ascii_M"]
-    if y.size != n:
-        raise ValueError("SummaryAM: %d trait records for %d genotyped individuals" % (y.size, n))
-    q = X.shape[1]
-    xn, mname = am._summary_names(q, xnames, map, L)
-    maxK, lam, U = am._summary_K(backend, geno, availmemGb, eig)
-    F = np.column_stack([X] + [backend.extract_geno(geno, j).astype(np.float64) for j in picks] + [y])   # constructX, :131-137
-    Ft = host_model.algebra().mm(U.T, F)
-    return am._summary_eig(lam, maxK, Ft[:, :-1], Ft[:, -1], q, xn + [mname(j) for j in picks], say)
+    return am.SummaryAM(AMobj, trait, X, geno, map=map, xnames=xnames, availmemGb=availmemGb, eig=eig, backend=backend, message=message,
+                        device=device)
 
 
 def FPR4AM(trait, X, geno, falseposrate=0.05, numreps=200, seed=101, availmemGb=8, quiet=True, message=None, algebra=None, device=0,

@@ -25,7 +25,7 @@ SEED = 101
 
 def child(n, L, R, q):
     import torch
-    from eagleeverything_amd import am, host_model, r_api, rcpp_api, synth
+    from eagleeverything_amd import am, emma, host_model, r_api, rcpp_api, synth
     from eagleeverything_amd.sharded import DeviceShard
     sh = DeviceShard(n, L)
     sh.fill_synthetic(seed=2)
@@ -63,7 +63,7 @@ def child(n, L, R, q):
         setattr(obj, name, g)
 
     for obj, name, label in ((r_api, "calcMMt", "MM^T"), (la, "eigh", "eigh"), (la, "mm", None),
-                             (rcpp_api, "spectral_prepare", "Z build"), (am, "_emma_eig_batch", "EMMA, batched (3 fits per permutation)"),
+                             (rcpp_api, "spectral_prepare", "Z build"), (emma, "_emma_eig_batch", "EMMA, batched (3 fits per permutation)"),
                              (am, "emma_REMLE_eig", "EMMA REML, per trait"), (am, "emma_MLE_eig", "EMMA ML, per trait"),
                              (rcpp_api, "spectral_scan_traits", "scans"), (rcpp_api, "spectral_rows", "rows")):
         wrap(obj, name, label)
