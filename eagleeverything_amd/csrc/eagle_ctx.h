@@ -190,6 +190,13 @@ extern "C" int eagle_dev_unpack2b(eagle_ctx* ctx, const uint8_t* raw, long rows,
 // null) and the count of missing genotypes added to *n_missing (or null); k_bed_decode in eagle_kernels.hip.
 extern "C" int eagle_dev_bed_decode(eagle_ctx* ctx, const uint8_t* bed, long real, long rows, long n, int8_t* tile, long ld, uint8_t* packed,
                                     long rb16, unsigned long long* n_missing, void* stream);
+// Marker QC (eagle_qc.hip): per-marker genotype counts of an int8 Mt tile (counts[rows][3] = n0, n1, n2) and of raw SNP-major .bed rows
+// (counts[rows][4] = hom A1, het, hom A2, missing), and the rows map[0 .. nrows) of an image copied to consecutive rows of `out`
+// (zero rows up to rows_out).
+extern "C" int eagle_dev_marker_counts(eagle_ctx* ctx, const int8_t* Mt8, long rows, long n, long ld, int32_t* counts, void* stream);
+extern "C" int eagle_dev_bed_marker_counts(eagle_ctx* ctx, const uint8_t* bed, long rows, long n, int32_t* counts, void* stream);
+extern "C" int eagle_dev_gather_rows_i8(eagle_ctx* ctx, const int8_t* src, long ld_src, const int32_t* map, long nrows, long rows_out,
+                                        int8_t* out, long ld_out, void* stream);
 inline bool eagle_sidecar_enabled() { const char* e = getenv("EAGLE_HIP_SIDECAR"); return !(e && e[0] == '0'); }
 // Whole-file resident copy (loads it if needed); EAGLE_OK, 2 (too large for HBM: stream it) or an error.
 int eagle_get_resident(eagle_ctx* ctx, const char* path, long rows, long cols, double max_mem_gb, int threads, const GenoEntry** out);

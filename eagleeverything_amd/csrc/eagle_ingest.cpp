@@ -657,19 +657,8 @@ int write_lines_from_image(eagle_ctx* ctx, int fd, const char* path, const int8_
     return flush();
 }
 
-}  // namespace
-
-// Mt.ascii is the bed file's own order: every marker window is decoded by k_bed_decode into its int8 tile and its sidecar rows, encoded
-// to text and written while the next window is on the device.  M.ascii is the other order, so every window's tile is also transposed
-// into an image of M: the whole of it when it fits (kept as the resident copy), else a band of individuals per PASS over the bed file --
-// the first pass writes Mt.ascii as well, the later ones only decode (or, with Mt resident, transpose from its image) -- and M.ascii
-// and its sidecar are written from the finished image or band in row chunks, in file order, by the same code either way.
-extern "C" int eagle_create_ascii_from_bed(eagle_ctx* ctx, const char* bed_path, const char* f_name_ascii_M, const char* f_name_ascii_Mt,
-                                           double max_memory_in_Gbytes, const long dims[2], int quiet, long* n_missing_out) {
-    if (!ctx || !bed_path || !f_name_ascii_M || !f_name_ascii_Mt || !dims) return EAGLE_ERR_ARG;
-    const long n = dims[0], L = dims[1];
-    if (n <= 0 || L <= 0) return eagle_fail(ctx, EAGLE_ERR_ARG, "create_ascii_from_bed: dims must be positive");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+// A SNP-major .bed file of L markers of n individuals, opened and checked (header, size): *fd_out, or the call's error.
+int open_bed(eagle_ctx* ctx, const char* bed_path, long n, long L, int* fd_out) {
     const int fdin = open(bed_path, O_RDONLY);
     if (fdin < 0) return failf(ctx, EAGLE_ERR_OPEN, "ERROR: Could not open  %s", bed_path);
     struct Closer { int fd; ~Closer() { if (fd >= 0) close(fd); } } closer{fdin};
@@ -689,6 +678,27 @@ extern "C" int eagle_create_ascii_from_bed(eagle_ctx* ctx, const char* bed_path,
     if ((long long)st.st_size != bed_expected_size(n, L))
         return failf(ctx, EAGLE_ERR_FORMAT, "%s holds %lld bytes, but %ld markers of %ld individuals take %lld", bed_path, (long long)st.st_size, L,
                      n, bed_expected_size(n, L));
+    *fd_out = fdin;
+    closer.fd = -1;
+    return EAGLE_OK;
+}
+
+}  // namespace
+
+// Mt.ascii is the bed file's own order: every marker window is decoded by k_bed_decode into its int8 tile and its sidecar rows, encoded
+// to text and written while the next window is on the device.  M.ascii is the other order, so every window's tile is also transposed
+// into an image of M: the whole of it when it fits (kept as the resident copy), else a band of individuals per PASS over the bed file --
+// the first pass writes Mt.ascii as well, the later ones only decode (or, with Mt resident, transpose from its image) -- and M.ascii
+// and its sidecar are written from the finished image or band in row chunks, in file order, by the same code either way.
+extern "C" int eagle_create_ascii_from_bed(eagle_ctx* ctx, const char* bed_path, const char* f_name_ascii_M, const char* f_name_ascii_Mt,
+                                           double max_memory_in_Gbytes, const long dims[2], int quiet, long* n_missing_out) {
+    if (!ctx || !bed_path || !f_name_ascii_M || !f_name_ascii_Mt || !dims) return EAGLE_ERR_ARG;
+    const long n = dims[0], L = dims[1];
+    if (n <= 0 || L <= 0) return eagle_fail(ctx, EAGLE_ERR_ARG, "create_ascii_from_bed: dims must be positive");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int fdin = -1;
+    if (int orc = open_bed(ctx, bed_path, n, L, &fdin)) return orc;
+    struct Closer { int fd; ~Closer() { if (fd >= 0) close(fd); } } closer{fdin};
 
     const int threads = host_threads();
     const long rb = bed_row_bytes(n), n_pad = eagle_pad(n), ldn = n_pad, L_pad = eagle_pad(L);
@@ -795,5 +805,210 @@ extern "C" int eagle_create_ascii_from_bed(eagle_ctx* ctx, const char* bed_path,
         mt.p = nullptr;
         return eagle_cache_adopt(ctx, f_name_ascii_Mt, L, n, L_pad, ldn, give);
     }
+    return EAGLE_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Marker QC: per-marker genotype counts and filtered panels (no counterpart in the reference; kernels in eagle_qc.hip)
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+
+// argument errors are decided before the context is touched: without one the text goes where eagle_open_error() finds it
+int qc_fail(eagle_ctx* ctx, int code, const char* msg) {
+    if (ctx) return eagle_fail(ctx, code, msg);
+    snprintf(g_open_err, sizeof g_open_err, "%s", msg);
+    return code;
+}
+
+}  // namespace
+
+// The image of Mt.ascii is counted where it lies when it is (or can be made) resident; else in row windows of the size the streamed
+// scans use, each loaded through eagle_dev_load_ascii (sidecar, text, or a VIEW's source) and counted before the next one is read.
+extern "C" int eagle_marker_counts(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long dims[2], double max_memory_in_Gbytes,
+                                   int32_t* counts_out) {
+    if (!f_name_ascii_Mt || !dims || !counts_out) return qc_fail(ctx, EAGLE_ERR_ARG, "marker_counts: NULL argument");
+    const long n = dims[0], L = dims[1];
+    if (n <= 0 || L <= 0) return qc_fail(ctx, EAGLE_ERR_ARG, "marker_counts: dims must be positive");
+    if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "marker_counts: no context");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int threads = host_threads();
+    DevBuf counts;
+    HIPCHK(ctx, counts.alloc(sizeof(int32_t) * 3 * (size_t)L));
+    const GenoEntry* src = nullptr;
+    int rc = eagle_get_resident(ctx, f_name_ascii_Mt, L, n, max_memory_in_Gbytes, threads, &src);
+    if (rc != EAGLE_OK && rc != EAGLE_STREAM) return rc;
+    if (rc == EAGLE_OK) {
+        rc = eagle_dev_marker_counts(ctx, src->dev, L, n, src->ld, counts.as<int32_t>(), ctx->stream);
+        if (rc) return rc;
+    } else {
+        const long ld = eagle_pad(n), w = stream_chunk_rows_core(eagle_resident_budget(), ld, eagle_pad(L));
+        DevBuf win;
+        HIPCHK(ctx, win.alloc((size_t)w * ld));
+        for (long r0 = 0; r0 < L; r0 += w) {
+            const long nr = std::min(w, L - r0);
+            HIPCHK(ctx, hipMemsetAsync(win.p, 0, (size_t)w * ld, ctx->stream));
+            rc = eagle_dev_load_ascii(ctx, f_name_ascii_Mt, r0, nr, 0, n, win.as<int8_t>(), ld, max_memory_in_Gbytes, threads);
+            if (rc) return rc;
+            rc = eagle_dev_marker_counts(ctx, win.as<int8_t>(), nr, n, ld, counts.as<int32_t>() + 3 * r0, ctx->stream);
+            if (rc) return rc;
+        }
+    }
+    HIPCHK(ctx, hipMemcpyAsync(counts_out, counts.p, sizeof(int32_t) * 3 * (size_t)L, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return EAGLE_OK;
+}
+
+// The rows go through the pinned staging ring in windows of up to 64 MiB, as eagle_create_ascii_from_bed reads them: the pread of
+// window k + 1 runs under the copy and the kernel of window k.
+extern "C" int eagle_bed_marker_counts(eagle_ctx* ctx, const char* bed_path, const long dims[2], double max_memory_in_Gbytes,
+                                       int32_t* counts_out) {
+    if (!bed_path || !dims || !counts_out) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_marker_counts: NULL argument");
+    const long n = dims[0], L = dims[1];
+    if (n <= 0 || L <= 0) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_marker_counts: dims must be positive");
+    if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_marker_counts: no context");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int fdin = -1;
+    if (int orc = open_bed(ctx, bed_path, n, L, &fdin)) return orc;
+    struct Closer { int fd; ~Closer() { if (fd >= 0) close(fd); } } closer{fdin};
+    const int threads = host_threads();
+    const long rb = bed_row_bytes(n);
+    double cap = 67108864.0;
+    if (max_memory_in_Gbytes > 0) cap = std::min(cap, max_memory_in_Gbytes * 1e9 / 4.0);  // the loaders' staging rule
+    const long w = std::max(1L, std::min(L, (long)cap / rb));
+    int rc = eagle_stage_ensure(ctx, (size_t)w * rb);
+    if (rc) return rc;
+    DevBuf counts;
+    HIPCHK(ctx, counts.alloc(sizeof(int32_t) * 4 * (size_t)L));
+    hipEvent_t done[2] = {nullptr, nullptr};
+    for (int b = 0; b < 2; b++) HIPCHK(ctx, hipEventCreateWithFlags(&done[b], hipEventDisableTiming));
+    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int b = 0; b < 2; b++) if (e[b]) (void)hipEventDestroy(e[b]); } } evg{done};
+    long k = 0;
+    for (long r0 = 0; r0 < L; r0 += w, k++) {
+        const int b = (int)(k & 1);
+        const long nr = std::min(w, L - r0);
+        if (k >= 2) HIPCHK(ctx, hipEventSynchronize(done[b]));  // window k - 2 has left staging buffer b
+        if (!pread_all(fdin, (char*)ctx->stage_pin[b], (size_t)nr * rb, (off_t)BED_HEADER_BYTES + (off_t)r0 * rb, threads)) {
+            (void)hipStreamSynchronize(ctx->stream);
+            return failf(ctx, EAGLE_ERR_FORMAT, "%s: could not read markers %ld to %ld", bed_path, r0 + 1, r0 + nr);
+        }
+        HIPCHK(ctx, hipMemcpyAsync(ctx->stage_raw[b], ctx->stage_pin[b], (size_t)nr * rb, hipMemcpyHostToDevice, ctx->stream));
+        rc = eagle_dev_bed_marker_counts(ctx, (const uint8_t*)ctx->stage_raw[b], nr, n, counts.as<int32_t>() + 4 * r0, ctx->stream);
+        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+        HIPCHK(ctx, hipEventRecord(done[b], ctx->stream));
+    }
+    HIPCHK(ctx, hipMemcpyAsync(counts_out, counts.p, sizeof(int32_t) * 4 * (size_t)L, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return EAGLE_OK;
+}
+
+namespace {
+
+// One of the two output files of eagle_filter_markers: `rows` lines of `cols` characters with sidecar, made band by band of `band`
+// rows (a multiple of 256; one band when the image is kept) by fill(r0, nr, tile), which leaves the int8 rows [r0, r0 + nr) of the
+// subset at `tile` (leading dimension ld, every byte beyond the subset zero), and adopted as the resident copy when `keep`.
+template <class Fill>
+int filter_write(eagle_ctx* ctx, const char* path, long rows, long cols, long rows_pad, long ld, long band, bool keep, int threads, Fill fill) {
+    const long chunk = std::max(1L, std::min(rows, (long)(67108864 / (cols + 1))));
+    int rc = eagle_stage_ensure(ctx, (size_t)chunk * (cols + 1));
+    if (rc) return rc;
+    DevBuf img;
+    HIPCHK(ctx, img.alloc((size_t)(keep ? rows_pad : band) * ld));
+    hipEvent_t done[2] = {nullptr, nullptr};
+    for (int b = 0; b < 2; b++) HIPCHK(ctx, hipEventCreateWithFlags(&done[b], hipEventDisableTiming));
+    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int b = 0; b < 2; b++) if (e[b]) (void)hipEventDestroy(e[b]); } } evg{done};
+    TextOut out;
+    if (!out.open_sized(path, (off_t)rows * (cols + 1))) return failf(ctx, EAGLE_ERR_OPEN, "ERROR: Could not open  %s", path);
+    SidecarWriter sc;
+    (void)sc.open_for(ctx, path, rows, cols, chunk);
+    for (long r0 = 0; r0 < rows; r0 += band) {
+        const long nr = std::min(band, rows - r0);
+        int8_t* tile = img.as<int8_t>() + (keep ? r0 * ld : 0);
+        rc = fill(r0, nr, std::min(band, rows_pad - r0), tile);
+        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+        rc = write_lines_from_image(ctx, out.fd, path, tile, ld, r0, nr, cols, chunk, sc, done, threads);
+        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    out.finish();  // the text file is final: its size and mtime key the sidecar and the cache entry
+    sc.finish(path);
+    if (keep) {
+        int8_t* give = img.as<int8_t>();
+        img.p = nullptr;
+        return eagle_cache_adopt(ctx, path, rows, cols, rows_pad, ld, give);
+    }
+    return EAGLE_OK;
+}
+
+}  // namespace
+
+// Mt first (row copies of the kept markers), then M (the kept columns of every individual), each from the resident image of its source
+// when there is one -- k_gather_rows_i8 / k_gather_cols_i8, HBM to HBM -- and else from windows of the source: the kept lines of
+// Mt.ascii as runs through the staged reader, bands of whole lines of M.ascii gathered on the device.  Both outputs are written by the
+// code that writes the converters' files, from images with the padding a freshly loaded file of (n, nkeep) has.
+extern "C" int eagle_filter_markers(eagle_ctx* ctx, const char* fnameM, const char* fnameMt, const long dims[2], const long* keep, long nkeep,
+                                    const char* outM, const char* outMt, double max_memory_in_Gbytes, long newdims_out[2]) {
+    if (!fnameM || !fnameMt || !dims || !outM || !outMt || !newdims_out) return qc_fail(ctx, EAGLE_ERR_ARG, "filter_markers: NULL argument");
+    const long n = dims[0], L = dims[1];
+    if (n <= 0 || L <= 0 || L > 0x7fffffffL) return qc_fail(ctx, EAGLE_ERR_ARG, "filter_markers: bad dims");
+    if (!keep || nkeep <= 0) return qc_fail(ctx, EAGLE_ERR_ARG, "filter_markers: the keep-list is empty");
+    for (long i = 0; i < nkeep; i++) {
+        if (keep[i] < 0 || keep[i] >= L) return qc_fail(ctx, EAGLE_ERR_ARG, "filter_markers: keep-list entry outside [0, L)");
+        if (i > 0 && keep[i] <= keep[i - 1]) return qc_fail(ctx, EAGLE_ERR_ARG, "filter_markers: the keep-list must be strictly increasing");
+    }
+    const std::string sM = fnameM, sMt = fnameMt, oM = outM, oMt = outMt;
+    if (oM == sM || oM == sMt || oMt == sM || oMt == sMt || oM == oMt)
+        return qc_fail(ctx, EAGLE_ERR_ARG, "filter_markers: the output files must differ from the input files and from each other");
+    if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "filter_markers: no context");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int threads = host_threads();
+    const long Lk = nkeep, n_pad = eagle_pad(n), L_pad = eagle_pad(L), Lk_pad = eagle_pad(Lk);
+    std::vector<int32_t> keep32((size_t)Lk);
+    for (long i = 0; i < Lk; i++) keep32[(size_t)i] = (int32_t)keep[i];
+    DevBuf d_keep;
+    HIPCHK(ctx, d_keep.alloc(sizeof(int32_t) * (size_t)Lk));
+    HIPCHK(ctx, hipMemcpyAsync(d_keep.p, keep32.data(), sizeof(int32_t) * (size_t)Lk, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    const size_t budget = eagle_resident_budget();
+
+    {   // Mt: nkeep lines of n characters
+        const GenoEntry* g = nullptr;
+        int rc = eagle_get_resident(ctx, fnameMt, L, n, max_memory_in_Gbytes, threads, &g);
+        if (rc != EAGLE_OK && rc != EAGLE_STREAM) return rc;
+        const int8_t* src = g ? g->dev : nullptr;
+        const long ld_src = g ? g->ld : 0;
+        const bool keepimg = fits_resident((size_t)Lk_pad * n_pad);
+        const long band = keepimg ? Lk_pad : stream_chunk_rows_core(budget, n_pad, Lk_pad);
+        rc = filter_write(ctx, outMt, Lk, n, Lk_pad, n_pad, band, keepimg, threads, [&](long r0, long nr, long padded, int8_t* tile) -> int {
+            if (src) return eagle_dev_gather_rows_i8(ctx, src, ld_src, d_keep.as<int32_t>() + r0, nr, padded, tile, n_pad, ctx->stream);
+            HIPCHK(ctx, hipMemsetAsync(tile, 0, (size_t)padded * n_pad, ctx->stream));
+            std::vector<RowRun> runs;
+            append_keep_runs(keep32.data() + r0, nr, runs);
+            return eagle_load_rows(ctx, fnameMt, runs, 0, n, tile, n_pad, max_memory_in_Gbytes, threads);
+        });
+        if (rc) return rc;
+    }
+    {   // M: n lines of nkeep characters
+        const GenoEntry* g = nullptr;
+        int rc = eagle_get_resident(ctx, fnameM, n, L, max_memory_in_Gbytes, threads, &g);
+        if (rc != EAGLE_OK && rc != EAGLE_STREAM) return rc;
+        const int8_t* src = g ? g->dev : nullptr;
+        const long ld_src = g ? g->ld : L_pad;
+        const bool keepimg = src && fits_resident((size_t)n_pad * Lk_pad);
+        const long band = keepimg ? n_pad : stream_chunk_rows_core(budget, L_pad, n_pad);
+        DevBuf win;   // a band of whole lines of M.ascii when the source is not resident
+        if (!src) HIPCHK(ctx, win.alloc((size_t)band * L_pad));
+        rc = filter_write(ctx, outM, n, Lk, n_pad, Lk_pad, band, keepimg, threads, [&](long r0, long nr, long padded, int8_t* tile) -> int {
+            HIPCHK(ctx, hipMemsetAsync(tile, 0, (size_t)padded * Lk_pad, ctx->stream));
+            const int8_t* s = src ? src + r0 * ld_src : win.as<int8_t>();
+            if (!src) {
+                int r = eagle_dev_load_ascii(ctx, fnameM, r0, nr, 0, L, win.as<int8_t>(), L_pad, max_memory_in_Gbytes, threads);
+                if (r) return r;
+            }
+            return eagle_dev_gather_cols_i8(ctx, s, ld_src, d_keep.as<int32_t>(), 0, nr, Lk, tile, Lk_pad, ctx->stream);
+        });
+        if (rc) return rc;
+    }
+    newdims_out[0] = n;
+    newdims_out[1] = Lk;
     return EAGLE_OK;
 }

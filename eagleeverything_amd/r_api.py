@@ -9,6 +9,7 @@
   check_for_NA_in_trait .. E/R/check_for_NA_in_trait.R:1-25
   ReadZmat ............... E/R/ReadZmat.R:34-111     (zmat_index: the matrix as the vector ind_of_obs)
   SummaryAM .............. E/R/summary_am.R:78-221   (in the eigenbasis of K; am.SummaryAM)
+  MarkerStats, FilterMarkers, subset_map ... marker QC, not in the reference (counts on the device, rules on the host)
 
 `geno` is the reference's list {asciifileM, asciifileMt, dim_of_ascii_M = (n, L)} (E/R/ReadMarker.R:306-307).
 selected_loci follow R: 1-based, NA = numpy.nan.  The "-1 only if no NA anywhere" rule
@@ -240,11 +241,22 @@ def _read_marker_bed(filename, availmemGb, quiet, outdir, message, device):
 
 
 def ReadMarker(filename=None, type="text", missing=None, AA=None, AB=None, BB=None, availmemGb=16, quiet=True, outdir=None,
-               message=None, device=0):
+               message=None, device=0, maf=None, max_missing=None, drop_monomorphic=False):
     """E/R/ReadMarker.R:194-318 -> geno dict {asciifileM, asciifileMt, dim_of_ascii_M} or None (the R list / NULL).
     type="PLINKbed" (not in the reference): `filename` is the .bed file of a PLINK binary fileset or its prefix; n and L are the
-    line counts of the .fam and .bim beside it, the genotypes go through rcpp_api.create_ascii_from_bed."""
+    line counts of the .fam and .bim beside it, the genotypes go through rcpp_api.create_ascii_from_bed.
+    maf / max_missing / drop_monomorphic (not in the reference; all off by default, and then nothing here differs from the line
+    above): the converted panel goes through FilterMarkers -- with the .bed file's own counts for type="PLINKbed", so that
+    missingness is the file's, not the heterozygotes it became -- into <outdir>/qc, and the dict returned names those files and
+    carries marker_index (None when no marker passes)."""
     say = message or (lambda s: None)
+    if maf is not None or max_missing is not None or drop_monomorphic:
+        geno = ReadMarker(filename, type=type, missing=missing, AA=AA, AB=AB, BB=BB, availmemGb=availmemGb, quiet=quiet, outdir=outdir,
+                          message=message, device=device)
+        if geno is None:
+            return None
+        return FilterMarkers(geno, maf=maf, max_missing=max_missing, drop_monomorphic=drop_monomorphic,
+                             bed=bed_fileset(filename)[0] if type == "PLINKbed" else None, availmemGb=availmemGb, message=message, device=device)
     if type == "PLINKbed":
         return _read_marker_bed(filename, availmemGb, quiet, outdir, message, device)
     if type not in ("text", "PLINK"):                                               # :206-215
@@ -277,6 +289,112 @@ def ReadMarker(filename=None, type="text", missing=None, AA=None, AB=None, BB=No
     if not ok:
         return None
     return {"asciifileM": os.path.join(outdir, "M.ascii"), "asciifileMt": os.path.join(outdir, "Mt.ascii"), "dim_of_ascii_M": dims}
+
+
+def marker_stats_from_counts(n0, n1, n2, n_missing=None):
+    """Per-marker statistics from integer genotype counts, in numpy fp64 (nothing here touches a device): n0 / n1 / n2 = called
+    genotypes coded 0 / 1 / 2, n_missing = genotypes without a call (default none).  n = n0 + n1 + n2 + n_missing individuals,
+    n_called = n0 + n1 + n2;  freq = (2 n2 + n1) / (2 n_called), the frequency of the allele coded 2;  maf = the smaller of the two
+    allele counts over 2 n_called (PLINK's definitions: missing genotypes are in neither);  het = n1 / n_called;  call_rate =
+    n_called / n.  A marker without a called genotype has freq = maf = het = NaN and call_rate = 0."""
+    n0, n1, n2 = (np.asarray(v, dtype=np.int64).ravel() for v in (n0, n1, n2))
+    nm = np.zeros_like(n0) if n_missing is None else np.asarray(n_missing, dtype=np.int64).ravel()
+    called = n0 + n1 + n2
+    n = called + nm
+    a2 = 2 * n2 + n1
+    with np.errstate(divide="ignore", invalid="ignore"):
+        two = (2 * called).astype(np.float64)
+        freq = np.where(called > 0, a2 / two, np.nan)
+        maf = np.where(called > 0, np.minimum(a2, 2 * called - a2) / two, np.nan)
+        het = np.where(called > 0, n1 / called.astype(np.float64), np.nan)
+        call_rate = np.where(n > 0, called / np.maximum(n, 1).astype(np.float64), 0.0)
+    return {"n0": n0, "n1": n1, "n2": n2, "n_missing": nm, "freq": freq, "maf": maf, "het": het, "call_rate": call_rate}
+
+
+def marker_keep_mask(stats, maf=None, max_missing=None, drop_monomorphic=False):
+    """Which markers a filter keeps (boolean, length L), by PLINK's rules on the output of marker_stats_from_counts: keep
+    maf >= `maf`; drop n_missing / n > `max_missing`; drop_monomorphic drops maf == 0; a marker without a called genotype is dropped
+    by any of the three.  With no filter switched on every marker is kept."""
+    L = len(stats["n0"])
+    keep = np.ones(L, dtype=bool)
+    if maf is None and max_missing is None and not drop_monomorphic:
+        return keep
+    keep &= ~np.isnan(stats["maf"])
+    if maf is not None:
+        keep &= np.nan_to_num(stats["maf"], nan=-1.0) >= float(maf)
+    if max_missing is not None:
+        n = stats["n0"] + stats["n1"] + stats["n2"] + stats["n_missing"]
+        keep &= ~(stats["n_missing"] / np.maximum(n, 1).astype(np.float64) > float(max_missing))
+    if drop_monomorphic:
+        keep &= ~(np.nan_to_num(stats["maf"], nan=0.0) == 0.0)
+    return keep
+
+
+def MarkerStats(geno, bed=None, availmemGb=8, device=0):
+    """Per-marker QC statistics of a panel -> dict of length-L arrays n0, n1, n2, n_missing, freq, maf, het, call_rate
+    (marker_stats_from_counts); the counting runs on the device (rcpp_api.marker_counts on geno["asciifileMt"]: one pass over the
+    int8 image the scans read), the arithmetic on the host.
+    The text files of a panel no longer know which genotypes were missing: ingestion made them heterozygotes, so without `bed`
+    n_missing is zero, n1 includes them and call_rate is 1.  bed = the .bed file (or prefix) the panel was ingested from: the counts
+    are then the file's own (rcpp_api.bed_marker_counts), n0 / n1 / n2 and everything derived exclude the missing genotypes, and
+    n_missing is real.  n0 counts the genotype the files code '0' (homozygous A1 of a .bed file)."""
+    n, L = int(geno["dim_of_ascii_M"][0]), int(geno["dim_of_ascii_M"][1])
+    if bed is not None:
+        c = rcpp_api.bed_marker_counts(bed_fileset(bed)[0], (n, L), availmemGb, device=device)
+        return marker_stats_from_counts(c[:, 0], c[:, 1], c[:, 2], c[:, 3])
+    c = rcpp_api.marker_counts(geno["asciifileMt"], (n, L), availmemGb, device=device)
+    return marker_stats_from_counts(c[:, 0], c[:, 1], c[:, 2])
+
+
+def FilterMarkers(geno, maf=None, max_missing=None, drop_monomorphic=False, bed=None, stats=None, outdir=None, availmemGb=8,
+                  message=None, device=0):
+    """A panel without the markers a QC filter drops -> geno dict {asciifileM, asciifileMt, dim_of_ascii_M, marker_index}:
+    marker_index = int64, the kept markers' 0-based indices in the panel `geno` came from (composed with geno's own marker_index
+    when it is itself a filtered panel).  The rules are marker_keep_mask's on `stats` (default MarkerStats(geno, bed)).  The files
+    are written by rcpp_api.filter_markers into `outdir` (default: a qc/ directory beside the source files; it must not be the
+    source's directory) and are what ReadMarker leaves for a genotype file that holds only the kept markers.
+    Nothing dropped: the source dict with the identity marker_index, nothing written.  Nothing kept: None, after a message."""
+    say = message or (lambda s: None)
+    n, L = int(geno["dim_of_ascii_M"][0]), int(geno["dim_of_ascii_M"][1])
+    if stats is None:
+        stats = MarkerStats(geno, bed=bed, availmemGb=availmemGb, device=device)
+    if len(stats["n0"]) != L:
+        say(" Error: the marker statistics hold %d markers, the panel %d. " % (len(stats["n0"]), L))
+        say(" FilterMarkers has terminated with errors")
+        return None
+    idx = np.flatnonzero(marker_keep_mask(stats, maf=maf, max_missing=max_missing, drop_monomorphic=drop_monomorphic)).astype(np.int64)
+    base = np.asarray(geno["marker_index"], dtype=np.int64) if "marker_index" in geno else np.arange(L, dtype=np.int64)
+    if idx.size == L:
+        out = dict(geno)
+        out["marker_index"] = base
+        return out
+    if idx.size == 0:
+        say(" Error: no marker passes the filter (maf=%s, max_missing=%s, drop_monomorphic=%s). " % (maf, max_missing, drop_monomorphic))
+        say(" FilterMarkers has terminated with errors")
+        return None
+    srcdir = os.path.dirname(os.path.abspath(geno["asciifileM"]))
+    outdir = os.path.abspath(outdir) if outdir else os.path.join(srcdir, "qc")
+    if outdir == srcdir or outdir == os.path.dirname(os.path.abspath(geno["asciifileMt"])):
+        say(" Error: outdir %s holds the source panel; the filtered files need a directory of their own. " % outdir)
+        say(" FilterMarkers has terminated with errors")
+        return None
+    os.makedirs(outdir, exist_ok=True)
+    outM, outMt = os.path.join(outdir, "M.ascii"), os.path.join(outdir, "Mt.ascii")
+    dims = rcpp_api.filter_markers(geno["asciifileM"], geno["asciifileMt"], (n, L), idx, outM, outMt, availmemGb, device=device)
+    say(" %d of %d markers kept. " % (idx.size, L))
+    return {"asciifileM": outM, "asciifileMt": outMt, "dim_of_ascii_M": dims, "marker_index": base[idx]}
+
+
+def subset_map(map, geno):
+    """The marker map of a filtered panel: `map` (ReadBim's dict of SNP / Chr / Pos lists, or a list of names) indexed by
+    geno["marker_index"], so that SummaryAM(map=...) and a reader of AM()'s picks name the markers of the source panel.  A geno dict
+    without marker_index is an unfiltered panel: the map comes back as it is."""
+    if map is None or "marker_index" not in geno:
+        return map
+    idx = [int(i) for i in geno["marker_index"]]
+    if isinstance(map, dict):
+        return {k: [v[i] for i in idx] for k, v in map.items()}
+    return [map[i] for i in idx]
 
 
 def SummaryAM(AMobj, trait, X, geno, map=None, xnames=None, availmemGb=8, eig=None, backend=None, message=None, device=0):

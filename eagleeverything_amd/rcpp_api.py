@@ -548,6 +548,48 @@ def create_ascii_from_bed(bed_path, f_name_ascii_M, f_name_ascii_Mt, max_memory_
     return int(n_missing.value)
 
 
+# ---- marker QC (include/eagle_hip.h section 1b'): integer counts and filtered panels; the statistics are r_api's ----
+def marker_counts(f_name_ascii_Mt, dims, max_memory_in_Gbytes=8.0, device=0):
+    """eagle_marker_counts -> int32 (L, 3): the numbers of '0', '1', '2' characters of every line of Mt.ascii (dims = (n, L) of M).
+    A view alias gives the counts over its kept individuals."""
+    L = _lib.load()
+    ctx = context(device)
+    out = np.zeros((int(dims[1]), 3), dtype=np.int32)
+    _check(ctx, L.eagle_marker_counts(ctx, os.fsencode(f_name_ascii_Mt), _dims(dims), float(max_memory_in_Gbytes),
+                                      out.ctypes.data_as(C.POINTER(C.c_int32))))
+    return out
+
+
+def bed_marker_counts(bed_path, dims, max_memory_in_Gbytes=8.0, device=0):
+    """eagle_bed_marker_counts -> int32 (L, 4): homozygous A1, heterozygous, homozygous A2, missing of every marker of a SNP-major
+    PLINK .bed file of dims = (n individuals, L markers)."""
+    L = _lib.load()
+    ctx = context(device)
+    out = np.zeros((int(dims[1]), 4), dtype=np.int32)
+    _check(ctx, L.eagle_bed_marker_counts(ctx, os.fsencode(bed_path), _dims(dims), float(max_memory_in_Gbytes),
+                                          out.ctypes.data_as(C.POINTER(C.c_int32))))
+    return out
+
+
+def filter_markers(fnameM, fnameMt, dims, keep, outM, outMt, max_memory_in_Gbytes=8.0, device=0):
+    """eagle_filter_markers -> newdims [n, nkeep]: outM / outMt, their sidecars and resident images for the markers `keep` (0-based,
+    strictly increasing) of the panel (fnameM, fnameMt; dims = (n, L) of M).  The keep-list and the paths are checked by the library
+    before it needs a device: EagleError(-3, ...) then, without opening one."""
+    L = _lib.load()
+    kv = np.ascontiguousarray(np.atleast_1d(np.asarray(keep, dtype=np.int64)).ravel(), dtype=np.int64)
+    if kv.size and not np.all(np.asarray(keep).ravel() == kv):
+        raise ValueError("filter_markers: keep must hold whole numbers")
+    out = (C.c_long * 2)()
+    args = (os.fsencode(fnameM), os.fsencode(fnameMt), _dims(dims), kv.ctypes.data_as(c_lp), kv.size, os.fsencode(outM), os.fsencode(outMt),
+            float(max_memory_in_Gbytes), out)
+    if device not in _ctx:   # argument errors first: they need no context (text through eagle_open_error)
+        if L.eagle_filter_markers(None, *args) == -3 and b"no context" not in L.eagle_open_error():
+            raise EagleError(-3, L.eagle_open_error().decode())
+    ctx = context(device)
+    _check(ctx, L.eagle_filter_markers(ctx, *args))
+    return [int(out[0]), int(out[1])]
+
+
 # ---- SURVEY 8 f-4: the dense model algebra on the device, through the C ABI (opt-in; include/eagle_hip.h section 1c) ----
 def _square_any_order(A):
     """(buffer, transposed): a float64 n x n array usable as a column-major matrix without a copy when it is contiguous in

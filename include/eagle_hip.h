@@ -258,6 +258,39 @@ int eagle_create_ascii_from_bed(eagle_ctx* ctx, const char* bed_path, const char
                                 double max_memory_in_Gbytes, const long dims[2], int quiet, long* n_missing_out);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1b'. Marker QC (no counterpart in the reference, which leaves filtering to other tools): per-marker genotype counts from the
+ *     genotypes this library already holds, and panels restricted to a list of markers.  Integer results only; allele
+ *     frequencies, call rates and the filter rules are the caller's arithmetic on the counts (r_api.MarkerStats / FilterMarkers).
+ *     Single device: a multi-device context works on its first device.  Argument errors are decided before the context is
+ *     used; with ctx == NULL their text is in eagle_open_error().
+ * ------------------------------------------------------------------------------------------- */
+
+/* counts_out[3 i .. 3 i + 2] = the numbers of '0', '1' and '2' characters of line i of Mt.ascii (dims = (n, L) of M: L lines of n
+ * characters), from one HBM-bound pass over the int8 image (k_marker_counts: s = sum g, q = sum g^2 per row on v_dot4_i32_i8,
+ * n2 = (q + s) / 2, n0 = (q - s) / 2, n1 = n - n0 - n2).  The file is read as every loader of this library reads it: its resident
+ * image if there is one, else its 2-bit sidecar, else the text; the image stays resident when it fits, and a file that does not fit
+ * (or exceeds EAGLE_HIP_MAX_RESIDENT_GB) is counted in row windows.  A VIEW alias of eagle_reshape_m gives the counts over the kept
+ * individuals (dims[0] = their number).  Missing genotypes of the original data are heterozygotes by now and counted as such. */
+int eagle_marker_counts(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long dims[2], double max_memory_in_Gbytes, int32_t* counts_out);
+
+/* The same from a SNP-major PLINK .bed file (the format and the checks of eagle_create_ascii_from_bed; dims = (n, L)), where missing
+ * genotypes are still known: counts_out[4 i .. 4 i + 3] = homozygous A1 (code 00), heterozygous (10), homozygous A2 (11), missing
+ * (01) of marker i, by popcounts on the two bit planes (k_bed_marker_counts); the unused bit pairs of a row's last byte are not
+ * counted.  The rows are staged through pinned memory in windows of at most 64 MiB (a quarter of max_memory_in_Gbytes if less). */
+int eagle_bed_marker_counts(eagle_ctx* ctx, const char* bed_path, const long dims[2], double max_memory_in_Gbytes, int32_t* counts_out);
+
+/* The panel (fnameM, fnameMt; dims = (n, L) of M) restricted to the markers keep[0 .. nkeep) (0-based, strictly increasing): writes
+ * outM (n lines of nkeep characters) and outMt (nkeep lines of n characters), byte for byte what eagle_create_M_ascii followed by
+ * eagle_create_Mt_ascii leave for a genotype table that holds only those columns -- both sidecars, and both resident images under the
+ * OUTPUT paths when they fit.  From resident sources the subset is made in HBM (row copies for Mt, k_gather_cols_i8 for M); a source
+ * that is not resident is read in windows (the kept lines of Mt.ascii, bands of whole lines of M.ascii).  newdims_out = (n, nkeep).
+ * EAGLE_ERR_ARG: an empty keep-list, an entry outside [0, L), a list that is not strictly increasing, an output path equal to an
+ * input path or to the other output -- nothing has been written then.  A call that fails later leaves neither sidecar and no text
+ * file of the full size (the rule of eagle_create_ascii_from_bed). */
+int eagle_filter_markers(eagle_ctx* ctx, const char* fnameM, const char* fnameMt, const long dims[2], const long* keep, long nkeep,
+                         const char* outM, const char* outMt, double max_memory_in_Gbytes, long newdims_out[2]);
+
+/* ---------------------------------------------------------------------------------------------
  * 1c. Dense n x n model algebra on the device (OPT-IN: north_star keeps calculateH / calculateP / emma.* on
  *     host LAPACK, and nothing above calls these).  Once the scan takes tens of milliseconds the ~10-15 O(n^3) base-R calls
  *     of a find_qtl iteration are the whole run time (the author's note MyPackage/MyREADME:1 names eigen(); his MAGMA
