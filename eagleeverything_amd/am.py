@@ -587,6 +587,45 @@ def _summary_setup(who, indxNA, arrays, geno, map, xnames, availmemGb, eig, back
     return arrays, geno, xn, mname, maxK, np.ascontiguousarray(lam, dtype=np.float64).ravel(), U
 
 
+def tag_markers(AMobj, geno, r2=0.8, map=None, availmemGb=8, device=0):
+    """Which markers tag each locus AM() picked -> one dict per entry of AMobj["selected_loci"], in that order:
+    {"locus": the pick, "markers": the markers with r^2 >= r2 to it, the pick included (both 1-based, as AM() reports loci; int64,
+    increasing), "r2": their r^2}, and with a map (ReadBim's dict; names alone give only "names") "names", "chrom" (the pick's) and
+    "span" = (lowest, highest position of the tagging markers on that chromosome).  geno is what AM() was given: the individuals
+    AMobj["indxNA"] are left out as AM() left them out (a view on `device`).  The dot products run on the device (r_api.LDofLoci)."""
+    from . import r_api
+    picks = [int(j) for j in AMobj["selected_loci"]]
+    if not picks:
+        return []
+    indxNA = np.asarray(AMobj.get("indxNA", ()), dtype=np.int64).ravel()
+    if indxNA.size:
+        geno = _reshape(geno, indxNA, None, device)
+    ld = r_api.LDofLoci(geno, [j - 1 for j in picks], availmemGb=availmemGb, device=device)
+    L = ld["r2"].shape[0]
+    names = chrom = pos = None
+    if map is not None:
+        names = list(map["SNP"]) if hasattr(map, "keys") else list(map)
+        if len(names) != L:
+            raise ValueError("tag_markers: map names %d markers, the genotypes hold %d" % (len(names), L))
+        if hasattr(map, "keys") and "Chr" in map and "Pos" in map:
+            chrom, pos = np.asarray(map["Chr"]), np.asarray(map["Pos"])
+    out = []
+    for c, j in enumerate(picks):
+        col = ld["r2"][:, c]
+        hit = np.nan_to_num(col, nan=-1.0) >= float(r2)
+        hit[j - 1] = True
+        idx = np.flatnonzero(hit)
+        e = {"locus": j, "markers": idx.astype(np.int64) + 1, "r2": col[idx]}
+        if names is not None:
+            e["names"] = [str(names[i]) for i in idx]
+        if chrom is not None:
+            same = idx[chrom[idx] == chrom[j - 1]]
+            e["chrom"] = chrom[j - 1].item() if hasattr(chrom[j - 1], "item") else chrom[j - 1]
+            e["span"] = (pos[same].min().item(), pos[same].max().item())
+        out.append(e)
+    return out
+
+
 def SummaryAM(AMobj, trait, X, geno, map=None, xnames=None, availmemGb=8, eig=None, backend=None, message=None, device=0):
     """summary_am.R:78-221 for the dict AM() returns; r_api.SummaryAM, which forwards here, documents arguments and result.  The
     rows to drop are AMobj["indxNA"]; the marker columns come from extract_geno and enter one product U^T [X | m_j1 .. m_jk | y]."""

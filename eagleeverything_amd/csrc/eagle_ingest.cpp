@@ -1012,3 +1012,137 @@ extern "C" int eagle_filter_markers(eagle_ctx* ctx, const char* fnameM, const ch
     newdims_out[1] = Lk;
     return EAGLE_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// Linkage disequilibrium between markers (no counterpart in the reference; kernels in eagle_ld.hip)
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+
+// (s, q) of the `rows` markers of an int8 Mt tile: k_marker_counts, then k_ld_sq
+int ld_tile_sq(eagle_ctx* ctx, const int8_t* img, long rows, long n, long ld, int32_t* counts, int32_t* sq) {
+    int rc = eagle_dev_marker_counts(ctx, img, rows, n, ld, counts, ctx->stream);
+    if (rc) return rc;
+    return eagle_dev_ld_sq(ctx, counts, rows, sq, ctx->stream);
+}
+
+// Rows of a streamed window of Mt: the streamed scans' rule, and at least 512 so that windows overlapping by up to 256 rows advance.
+long ld_stream_rows(long ld, long L) { return std::max(512L, stream_chunk_rows_core(eagle_resident_budget(), ld, eagle_pad(L))); }
+
+}  // namespace
+
+// The mask of a resident image is one launch over it.  A file that is not resident is read in windows of w rows that start every
+// w - window rows: a window's launch writes the mask rows of all its markers, those of its last `window` markers without the partners
+// the window does not hold, and the next window, which starts on exactly those markers, writes them again in full (stream order).
+// Every marker's final words therefore come from a launch that held all of its partners: the bits of the resident pass.
+extern "C" int eagle_ld_window(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long dims[2], long window, double r2,
+                               double max_memory_in_Gbytes, uint64_t* mask_out, long* npairs_out) {
+    if (!f_name_ascii_Mt || !dims || !mask_out || !npairs_out) return qc_fail(ctx, EAGLE_ERR_ARG, "ld_window: NULL argument");
+    const long n = dims[0], L = dims[1];
+    if (n <= 0 || L <= 0) return qc_fail(ctx, EAGLE_ERR_ARG, "ld_window: dims must be positive");
+    if (window < 1 || window > 256) return qc_fail(ctx, EAGLE_ERR_ARG, "ld_window: window must be in [1, 256]");
+    if (!(r2 >= 0.0 && r2 <= 1.0)) return qc_fail(ctx, EAGLE_ERR_ARG, "ld_window: r2 must be in [0, 1]");
+    if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "ld_window: no context");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int threads = host_threads();
+    const long wpr = (window + 63) / 64;
+    const size_t mask_bytes = sizeof(uint64_t) * (size_t)L * (size_t)wpr;
+    DevBuf mask, counts, sq;
+    HIPCHK(ctx, mask.alloc(mask_bytes));
+    const GenoEntry* src = nullptr;
+    int rc = eagle_get_resident(ctx, f_name_ascii_Mt, L, n, max_memory_in_Gbytes, threads, &src);
+    if (rc != EAGLE_OK && rc != EAGLE_STREAM) return rc;
+    if (rc == EAGLE_OK) {
+        HIPCHK(ctx, counts.alloc(sizeof(int32_t) * 3 * (size_t)L));
+        HIPCHK(ctx, sq.alloc(sizeof(int32_t) * 2 * (size_t)L));
+        rc = ld_tile_sq(ctx, src->dev, L, n, src->ld, counts.as<int32_t>(), sq.as<int32_t>());
+        if (rc) return rc;
+        rc = eagle_dev_ld_band(ctx, src->dev, L, n, src->ld, sq.as<int32_t>(), window, r2, mask.as<uint64_t>(), wpr, ctx->stream);
+        if (rc) return rc;
+    } else {
+        const long ld = eagle_pad(n), w = ld_stream_rows(ld, L), step = w - window;
+        DevBuf win;
+        HIPCHK(ctx, win.alloc((size_t)w * ld));
+        HIPCHK(ctx, counts.alloc(sizeof(int32_t) * 3 * (size_t)w));
+        HIPCHK(ctx, sq.alloc(sizeof(int32_t) * 2 * (size_t)w));
+        for (long r0 = 0;; r0 += step) {
+            const long nr = std::min(w, L - r0);
+            HIPCHK(ctx, hipMemsetAsync(win.p, 0, (size_t)w * ld, ctx->stream));
+            rc = eagle_dev_load_ascii(ctx, f_name_ascii_Mt, r0, nr, 0, n, win.as<int8_t>(), ld, max_memory_in_Gbytes, threads);
+            if (rc) return rc;
+            rc = ld_tile_sq(ctx, win.as<int8_t>(), nr, n, ld, counts.as<int32_t>(), sq.as<int32_t>());
+            if (rc) return rc;
+            rc = eagle_dev_ld_band(ctx, win.as<int8_t>(), nr, n, ld, sq.as<int32_t>(), window, r2, mask.as<uint64_t>() + r0 * wpr, wpr, ctx->stream);
+            if (rc) return rc;
+            if (r0 + nr >= L) break;
+        }
+    }
+    HIPCHK(ctx, hipMemcpyAsync(mask_out, mask.p, mask_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    long pairs = 0;
+    for (size_t x = 0; x < (size_t)L * (size_t)wpr; x++) pairs += __builtin_popcountll(mask_out[x]);
+    *npairs_out = pairs;
+    return EAGLE_OK;
+}
+
+// The loci's rows are gathered into a 64-row image first (k_gather_rows_i8: from the resident image, else from their own lines of
+// the file, each distinct line read once), then every tile of Mt multiplies against it, where it lies or window by window.
+extern "C" int eagle_ld_dots(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long dims[2], const long* loci, long nloci,
+                             double max_memory_in_Gbytes, int32_t* dots_out) {
+    if (!f_name_ascii_Mt || !dims || !loci || !dots_out) return qc_fail(ctx, EAGLE_ERR_ARG, "ld_dots: NULL argument");
+    const long n = dims[0], L = dims[1];
+    if (n <= 0 || L <= 0 || L > 0x7fffffffL) return qc_fail(ctx, EAGLE_ERR_ARG, "ld_dots: bad dims");
+    if (nloci < 1 || nloci > 64) return qc_fail(ctx, EAGLE_ERR_ARG, "ld_dots: the number of loci must be in [1, 64]");
+    for (long i = 0; i < nloci; i++)
+        if (loci[i] < 0 || loci[i] >= L) return qc_fail(ctx, EAGLE_ERR_ARG, "ld_dots: locus outside [0, L)");
+    if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "ld_dots: no context");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int threads = host_threads();
+    const long k = nloci;
+    const GenoEntry* src = nullptr;
+    int rc = eagle_get_resident(ctx, f_name_ascii_Mt, L, n, max_memory_in_Gbytes, threads, &src);
+    if (rc != EAGLE_OK && rc != EAGLE_STREAM) return rc;
+    const long ld = src ? src->ld : eagle_pad(n);
+    std::vector<int32_t> map((size_t)k);
+    DevBuf d_map, B8, dots, uniq_img;
+    HIPCHK(ctx, d_map.alloc(sizeof(int32_t) * 64));
+    HIPCHK(ctx, B8.alloc((size_t)64 * ld));
+    HIPCHK(ctx, dots.alloc(sizeof(int32_t) * (size_t)L * (size_t)k));
+    const int8_t* from = src ? src->dev : nullptr;
+    if (src) {
+        for (long i = 0; i < k; i++) map[(size_t)i] = (int32_t)loci[i];
+    } else {
+        std::vector<int32_t> u(loci, loci + k);
+        std::sort(u.begin(), u.end());
+        u.erase(std::unique(u.begin(), u.end()), u.end());
+        for (long i = 0; i < k; i++) map[(size_t)i] = (int32_t)(std::lower_bound(u.begin(), u.end(), (int32_t)loci[i]) - u.begin());
+        HIPCHK(ctx, uniq_img.alloc((size_t)64 * ld));
+        HIPCHK(ctx, hipMemsetAsync(uniq_img.p, 0, (size_t)64 * ld, ctx->stream));
+        std::vector<RowRun> runs;
+        append_keep_runs(u.data(), (long)u.size(), runs);
+        rc = eagle_load_rows(ctx, f_name_ascii_Mt, runs, 0, n, uniq_img.as<int8_t>(), ld, max_memory_in_Gbytes, threads);
+        if (rc) return rc;
+        from = uniq_img.as<int8_t>();
+    }
+    HIPCHK(ctx, hipMemcpyAsync(d_map.p, map.data(), sizeof(int32_t) * (size_t)k, hipMemcpyHostToDevice, ctx->stream));
+    rc = eagle_dev_gather_rows_i8(ctx, from, ld, d_map.as<int32_t>(), k, 64, B8.as<int8_t>(), ld, ctx->stream);
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    if (src) {
+        rc = eagle_dev_ld_dots(ctx, src->dev, L, n, ld, B8.as<int8_t>(), k, dots.as<int32_t>(), ctx->stream);
+        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    } else {
+        const long w = ld_stream_rows(ld, L);
+        DevBuf win;
+        HIPCHK(ctx, win.alloc((size_t)w * ld));
+        for (long r0 = 0; r0 < L; r0 += w) {
+            const long nr = std::min(w, L - r0);
+            HIPCHK(ctx, hipMemsetAsync(win.p, 0, (size_t)w * ld, ctx->stream));
+            rc = eagle_dev_load_ascii(ctx, f_name_ascii_Mt, r0, nr, 0, n, win.as<int8_t>(), ld, max_memory_in_Gbytes, threads);
+            if (rc) return rc;
+            rc = eagle_dev_ld_dots(ctx, win.as<int8_t>(), nr, n, ld, B8.as<int8_t>(), k, dots.as<int32_t>() + r0 * k, ctx->stream);
+            if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+        }
+    }
+    HIPCHK(ctx, hipMemcpyAsync(dots_out, dots.p, sizeof(int32_t) * (size_t)L * (size_t)k, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return EAGLE_OK;
+}

@@ -78,6 +78,15 @@ int eagle_spectral_host_operands(eagle_ctx* ctx, long n, const double* lambda, c
 int eagle_spectral_scan_range(eagle_ctx* ctx, const double* d, const double* G, int NC, const double* Cm, const double* c1, long p, double varG,
                               const long* sel, long nsel, double* a_out, double* vara_out);
 int eagle_dev_extract_col(eagle_ctx* ctx, const int8_t* M8, long n, long ld, long col, int* out, void* stream);
+// Linkage disequilibrium (eagle_ld.hip) on an int8 Mt tile of `rows` markers x n individuals (ld % 16 == 0, zero from n on).
+// sq[r] = (sum g, sum g^2) of marker r from counts[r] = (n0, n1, n2) of eagle_dev_marker_counts.
+int eagle_dev_ld_sq(eagle_ctx* ctx, const int32_t* counts, long rows, int32_t* sq, void* stream);
+// bit o - 1 of mask[i] (words_per_row = ceil(window / 64) uint64 words per marker, every word of the rows [0, rows) written) is set iff
+// markers i and i + o, 1 <= o <= window <= 256, i + o < rows, are in LD at threshold t in [0, 1] (the rule at the head of eagle_ld.hip).
+int eagle_dev_ld_band(eagle_ctx* ctx, const int8_t* Mt8, long rows, long n, long ld, const int32_t* sq, long window, double t, uint64_t* mask,
+                      long words_per_row, void* stream);
+// dots[i * k + j] = sum over the individuals of marker i times row j of B8 (64 rows x ld, rows k .. 63 zero), 1 <= k <= 64
+int eagle_dev_ld_dots(eagle_ctx* ctx, const int8_t* Mt8, long rows, long n, long ld, const int8_t* B8, long k, int32_t* dots, void* stream);
 #ifdef __cplusplus
 }
 #include "eagle_host.h"

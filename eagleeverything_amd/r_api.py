@@ -385,6 +385,175 @@ def FilterMarkers(geno, maf=None, max_missing=None, drop_monomorphic=False, bed=
     return {"asciifileM": outM, "asciifileMt": outMt, "dim_of_ascii_M": dims, "marker_index": base[idx]}
 
 
+def _ld_sv(stats, n):
+    """s = sum g, q = sum g^2 and v = n q - s^2 per marker (int64) from the counts in `stats`, with g = -1 / 0 / +1 for '0' / '1' / '2'."""
+    n0, n2 = np.asarray(stats["n0"], dtype=np.int64).ravel(), np.asarray(stats["n2"], dtype=np.int64).ravel()
+    s, q = n2 - n0, n2 + n0
+    return s, int(n) * q - s * s
+
+
+def ld_r2_from_dots(dots, stats, loci, n):
+    """r^2 between every marker and the markers `loci` (0-based) -> fp64 (L, k), from dots = rcpp_api.ld_dots (int (L, k)), the
+    counts n0 / n2 in `stats` (MarkerStats without bed=: the counts of the int8 image) and the n individuals: c = n d - s_i s_j,
+    v = n q - s^2 in int64, r^2 = c^2 / (v_i v_j) in fp64.  NaN where either marker is monomorphic.  Pure numpy."""
+    d = np.asarray(dots, dtype=np.int64)
+    lv = np.atleast_1d(np.asarray(loci, dtype=np.int64)).ravel()
+    d = d.reshape(-1, lv.size)
+    s, v = _ld_sv(stats, n)
+    if s.size != d.shape[0]:
+        raise ValueError("ld_r2_from_dots: the statistics hold %d markers, dots %d" % (s.size, d.shape[0]))
+    c = (int(n) * d - s[:, None] * s[lv][None, :]).astype(np.float64)
+    den = v.astype(np.float64)[:, None] * v[lv].astype(np.float64)[None, :]
+    ok = (v[:, None] > 0) & (v[lv][None, :] > 0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(ok, c * c / np.where(ok, den, 1.0), np.nan)
+
+
+def _ld_pairs(mask, window, rows_per_block=1 << 16):
+    """(i, j), i < j: the pairs whose bit is set in an rcpp_api.ld_window mask, in row-major order."""
+    m = np.ascontiguousarray(mask, dtype="<u8")
+    L = m.shape[0]
+    if L == 0:
+        return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
+    m = m.reshape(L, -1)
+    if m.shape[1] != (int(window) + 63) // 64:
+        raise ValueError("ld_prune_keep: the mask has %d words per marker, window %d needs %d" % (m.shape[1], window, (int(window) + 63) // 64))
+    I, J = [], []
+    for r0 in range(0, L, rows_per_block):
+        bits = np.unpackbits(m[r0:r0 + rows_per_block].view(np.uint8), axis=1, bitorder="little")[:, :int(window)]
+        i, o = np.nonzero(bits)
+        I.append(i.astype(np.int64) + r0)
+        J.append(i.astype(np.int64) + r0 + o + 1)
+    I, J = np.concatenate(I), np.concatenate(J)
+    ok = J < L
+    return I[ok], J[ok]
+
+
+def ld_prune_keep(mask, window, priority=None, chrom=None, pos=None, kb=None):
+    """Greedy LD pruning on the host -> boolean keep vector (length L); pure numpy, no device.  mask = rcpp_api.ld_window's (L, W)
+    uint64 words for `window`.  A pair (i, j) counts iff its bit is set, chrom[i] == chrom[j] (when chrom is given) and
+    |pos[i] - pos[j]| <= 1000 kb (when pos and kb are given).  The markers are visited in index order, or with `priority` in descending
+    priority with ties broken by index (NaN last); a marker is kept unless a marker already kept is paired with it.  A marker in LD with
+    nothing -- every monomorphic one, which is FilterMarkers' business -- is always kept."""
+    I, J = _ld_pairs(mask, window)
+    L = np.asarray(mask).shape[0]
+    ok = np.ones(I.size, dtype=bool)
+    if chrom is not None:
+        ch = np.asarray(chrom)
+        if ch.size != L:
+            raise ValueError("ld_prune_keep: chrom names %d markers, the mask %d" % (ch.size, L))
+        ok &= ch[I] == ch[J]
+    if kb is not None:
+        if pos is None:
+            raise ValueError("ld_prune_keep: kb needs pos")
+        ps = np.asarray(pos, dtype=np.float64)
+        if ps.size != L:
+            raise ValueError("ld_prune_keep: pos holds %d markers, the mask %d" % (ps.size, L))
+        ok &= np.abs(ps[I] - ps[J]) <= 1000.0 * float(kb)
+    I, J = I[ok], J[ok]
+    keep = np.ones(L, dtype=bool)
+    if not I.size:
+        return keep
+    a, b = np.concatenate([I, J]), np.concatenate([J, I])      # both directions, as rows of a CSR adjacency
+    srt = np.argsort(a, kind="stable")
+    b = b[srt]
+    ptr = np.concatenate([[0], np.cumsum(np.bincount(a, minlength=L))])
+    if priority is None:
+        order = np.flatnonzero(np.diff(ptr) > 0)               # markers without a pair are kept whenever they are visited
+    else:
+        pr = np.asarray(priority, dtype=np.float64).ravel()
+        if pr.size != L:
+            raise ValueError("ld_prune_keep: priority holds %d markers, the mask %d" % (pr.size, L))
+        order = np.argsort(-np.where(np.isnan(pr), -np.inf, pr), kind="stable")
+    blocked = np.zeros(L, dtype=bool)
+    for i in order.tolist():
+        if blocked[i]:
+            keep[i] = False
+        else:
+            blocked[b[ptr[i]:ptr[i + 1]]] = True
+    return keep
+
+
+def _ld_map(who, map, geno, L, say):
+    """The map (ReadBim's dict) of the L markers of `geno`: as given, or the source panel's indexed by geno's marker_index."""
+    if map is None:
+        return None
+    if not hasattr(map, "keys") or "Chr" not in map or "Pos" not in map:
+        say(" Error: %s needs a map with Chr and Pos entries (ReadBim's). " % who)
+        return False
+    if len(map["Chr"]) != L and "marker_index" in geno and len(map["Chr"]) > int(np.max(geno["marker_index"])):
+        map = subset_map(map, geno)
+    if len(map["Chr"]) != L or len(map["Pos"]) != L:
+        say(" Error: the map names %d markers, the panel holds %d. " % (len(map["Chr"]), L))
+        return False
+    return map
+
+
+def LDPrune(geno, window=50, r2=0.2, prefer="position", map=None, kb=None, stats=None, outdir=None, availmemGb=8, message=None, device=0):
+    """A panel without the markers greedy LD pruning drops -> what FilterMarkers returns: {asciifileM, asciifileMt, dim_of_ascii_M,
+    marker_index}, marker_index composed with geno's own.  The pairs in LD come from the device (rcpp_api.ld_window: pairs at most
+    `window` <= 256 markers apart with r^2 > `r2`, the exact rule of include/eagle_hip.h section 1b''), the greedy choice is
+    ld_prune_keep's on the host, the files are rcpp_api.filter_markers'.  prefer="position" visits the markers in index order (the first
+    of a correlated run stays); prefer="maf" visits them by descending minor allele frequency (`stats`, default MarkerStats(geno)).
+    map (ReadBim's dict for this panel, or for its source panel when geno carries marker_index): pairs on different chromosomes do
+    not count, nor, with kb=, pairs more than kb kilobases apart.  outdir: default an ld/ directory beside the source files; it must
+    not be the source's directory.  Nothing dropped: the source dict with the identity marker_index, nothing written."""
+    say = message or (lambda s: None)
+    n, L = int(geno["dim_of_ascii_M"][0]), int(geno["dim_of_ascii_M"][1])
+
+    def fail(text):
+        say(text)
+        say(" LDPrune has terminated with errors")
+        return None
+    if prefer not in ("position", "maf"):
+        return fail(' Error: prefer must be "position" or "maf". ')
+    errs = []
+    map = _ld_map("LDPrune", map, geno, L, errs.append)
+    if map is False:
+        return fail(errs[0])
+    if kb is not None and map is None:
+        return fail(" Error: kb= needs a map with Chr and Pos entries. ")
+    priority = None
+    if prefer == "maf":
+        if stats is None:
+            stats = MarkerStats(geno, availmemGb=availmemGb, device=device)
+        if len(stats["maf"]) != L:
+            return fail(" Error: the marker statistics hold %d markers, the panel %d. " % (len(stats["maf"]), L))
+        priority = stats["maf"]
+    srcdir = os.path.dirname(os.path.abspath(geno["asciifileM"]))
+    outdir = os.path.abspath(outdir) if outdir else os.path.join(srcdir, "ld")
+    if outdir == srcdir or outdir == os.path.dirname(os.path.abspath(geno["asciifileMt"])):
+        return fail(" Error: outdir %s holds the source panel; the pruned files need a directory of their own. " % outdir)
+    mask, npairs = rcpp_api.ld_window(geno["asciifileMt"], (n, L), window, r2, availmemGb, device=device, return_pairs=True)
+    say(" %d pairs of markers within %d markers of each other have r2 above %s. " % (npairs, int(window), r2))
+    keep = ld_prune_keep(mask, window, priority=priority, chrom=None if map is None else map["Chr"],
+                         pos=None if map is None else map["Pos"], kb=kb)
+    idx = np.flatnonzero(keep).astype(np.int64)
+    base = np.asarray(geno["marker_index"], dtype=np.int64) if "marker_index" in geno else np.arange(L, dtype=np.int64)
+    if idx.size == L:
+        out = dict(geno)
+        out["marker_index"] = base
+        return out
+    os.makedirs(outdir, exist_ok=True)
+    outM, outMt = os.path.join(outdir, "M.ascii"), os.path.join(outdir, "Mt.ascii")
+    dims = rcpp_api.filter_markers(geno["asciifileM"], geno["asciifileMt"], (n, L), idx, outM, outMt, availmemGb, device=device)
+    say(" %d of %d markers kept. " % (idx.size, L))
+    return {"asciifileM": outM, "asciifileMt": outMt, "dim_of_ascii_M": dims, "marker_index": base[idx]}
+
+
+def LDofLoci(geno, loci, stats=None, availmemGb=8, device=0):
+    """LD of every marker of a panel with the markers `loci` (0-based, any number; repeats allowed) -> {"loci": int64 (k), "dots": int32
+    (L, k) = sum over the individuals of g_i g_j, "r2": fp64 (L, k)}.  The dot products run on the device (rcpp_api.ld_dots, 64 loci
+    to a pass), r^2 is ld_r2_from_dots on `stats` (default MarkerStats(geno): it must hold the counts of the files, not a .bed's)."""
+    n, L = int(geno["dim_of_ascii_M"][0]), int(geno["dim_of_ascii_M"][1])
+    lv = np.atleast_1d(np.asarray(loci, dtype=np.int64)).ravel()
+    if stats is None:
+        stats = MarkerStats(geno, availmemGb=availmemGb, device=device)
+    parts = [rcpp_api.ld_dots(geno["asciifileMt"], (n, L), lv[c0:c0 + 64], availmemGb, device=device) for c0 in range(0, max(lv.size, 1), 64)]
+    dots = np.concatenate(parts, axis=1)
+    return {"loci": lv, "dots": dots, "r2": ld_r2_from_dots(dots, stats, lv, n)}
+
+
 def subset_map(map, geno):
     """The marker map of a filtered panel: `map` (ReadBim's dict of SNP / Chr / Pos lists, or a list of names) indexed by
     geno["marker_index"], so that SummaryAM(map=...) and a reader of AM()'s picks name the markers of the source panel.  A geno dict

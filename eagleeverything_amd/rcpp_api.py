@@ -590,6 +590,41 @@ def filter_markers(fnameM, fnameMt, dims, keep, outM, outMt, max_memory_in_Gbyte
     return [int(out[0]), int(out[1])]
 
 
+# ---- linkage disequilibrium (include/eagle_hip.h section 1b''): integer masks and dot products; r^2 and the pruning are r_api's ----
+def _args_first(fn, device, args):
+    """Argument errors need no context (their text comes through eagle_open_error): a bad call does not open a device."""
+    L = _lib.load()
+    if device not in _ctx:
+        if fn(None, *args) == -3 and b"no context" not in L.eagle_open_error():
+            raise EagleError(-3, L.eagle_open_error().decode())
+    ctx = context(device)
+    _check(ctx, fn(ctx, *args))
+
+
+def ld_window(f_name_ascii_Mt, dims, window=50, r2=0.2, max_memory_in_Gbytes=8.0, device=0, return_pairs=False):
+    """eagle_ld_window -> uint64 (L, ceil(window / 64)): bit (o - 1) % 64 of word (o - 1) // 64 of row i is set iff markers i and
+    i + o, 1 <= o <= window, are in LD at r2 (the rule of include/eagle_hip.h section 1b'').  return_pairs: (mask, number of set bits)."""
+    L = _lib.load()
+    out = np.zeros((int(dims[1]), (int(window) + 63) // 64 if int(window) > 0 else 1), dtype=np.uint64)
+    pairs = C.c_long(0)
+    _args_first(L.eagle_ld_window, device, (os.fsencode(f_name_ascii_Mt), _dims(dims), int(window), float(r2), float(max_memory_in_Gbytes),
+                                            out.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(pairs)))
+    return (out, int(pairs.value)) if return_pairs else out
+
+
+def ld_dots(f_name_ascii_Mt, dims, loci, max_memory_in_Gbytes=8.0, device=0):
+    """eagle_ld_dots -> int32 (L, k): the sum over the individuals of g_i g_j for every marker i and the k <= 64 markers j = loci
+    (0-based, repeats allowed)."""
+    L = _lib.load()
+    lv = np.ascontiguousarray(np.atleast_1d(np.asarray(loci, dtype=np.int64)).ravel(), dtype=np.int64)
+    if lv.size and not np.all(np.asarray(loci).ravel() == lv):
+        raise ValueError("ld_dots: loci must hold whole numbers")
+    out = np.zeros((int(dims[1]), max(int(lv.size), 1)), dtype=np.int32)
+    _args_first(L.eagle_ld_dots, device, (os.fsencode(f_name_ascii_Mt), _dims(dims), lv.ctypes.data_as(c_lp), lv.size, float(max_memory_in_Gbytes),
+                                          out.ctypes.data_as(C.POINTER(C.c_int32))))
+    return out
+
+
 # ---- SURVEY 8 f-4: the dense model algebra on the device, through the C ABI (opt-in; include/eagle_hip.h section 1c) ----
 def _square_any_order(A):
     """(buffer, transposed): a float64 n x n array usable as a column-major matrix without a copy when it is contiguous in

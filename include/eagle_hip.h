@@ -291,6 +291,32 @@ int eagle_filter_markers(eagle_ctx* ctx, const char* fnameM, const char* fnameMt
                          const char* outM, const char* outMt, double max_memory_in_Gbytes, long newdims_out[2]);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1b''. Linkage disequilibrium between markers (no counterpart in the reference): which markers of a panel are correlated, from
+ *     integer dot products between rows of the int8 marker-major image on the int8 MFMA (csrc/eagle_ld.hip).  With g in
+ *     {-1, 0, +1} over the n individuals of Mt.ascii (the kept ones of a VIEW alias; missing genotypes are heterozygotes), all int64:
+ *         s_i = sum g,  q_i = sum g^2,  d_ij = sum g_i g_j,  c_ij = n d_ij - s_i s_j,  v_i = n q_i - s_i^2,  r^2_ij = c^2 / (v_i v_j).
+ *     Markers i, j are IN LD AT t iff v_i > 0, v_j > 0 and (double)c * (double)c > t * ((double)v_i * (double)v_j), evaluated in
+ *     exactly that order in fp64 (correctly rounded products, no sum): a restatement in numpy gives the same bits.  A monomorphic
+ *     marker is in LD with nothing.  The file is read as eagle_marker_counts reads it (resident image, else sidecar, else text; a
+ *     VIEW alias works); one that does not fit is processed in row windows with the bits of the resident pass.  Single device: a
+ *     multi-device context works on its first device.  Argument errors (EAGLE_ERR_ARG: a NULL pointer, dims <= 0, and those named
+ *     below) are decided before the context is used; with ctx == NULL their text is in eagle_open_error().
+ * ------------------------------------------------------------------------------------------- */
+
+/* mask_out[i * W + (o - 1) / 64], W = ceil(window / 64), has bit (o - 1) % 64 set iff markers i and i + o (1 <= o <= window,
+ * i + o < L) are in LD at r2; every other bit is clear.  *npairs_out = the number of set bits.  (s, q) come from k_marker_counts in
+ * the same call.  Streamed windows overlap by `window` rows, so that no pair is lost or counted twice.
+ * EAGLE_ERR_ARG: window outside [1, 256], r2 outside [0, 1] or NaN. */
+int eagle_ld_window(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long dims[2], long window, double r2, double max_memory_in_Gbytes,
+                    uint64_t* mask_out, long* npairs_out);
+
+/* dots_out[i * nloci + j] = d between marker i and marker loci[j] (0-based; repeats allowed), for every marker of the panel: L x nloci
+ * int32, row-major.  r^2 follows from the counts of eagle_marker_counts (r_api.ld_r2_from_dots).
+ * EAGLE_ERR_ARG: nloci outside [1, 64], a locus outside [0, L). */
+int eagle_ld_dots(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long dims[2], const long* loci, long nloci, double max_memory_in_Gbytes,
+                  int32_t* dots_out);
+
+/* ---------------------------------------------------------------------------------------------
  * 1c. Dense n x n model algebra on the device (OPT-IN: north_star keeps calculateH / calculateP / emma.* on
  *     host LAPACK, and nothing above calls these).  Once the scan takes tens of milliseconds the ~10-15 O(n^3) base-R calls
  *     of a find_qtl iteration are the whole run time (the author's note MyPackage/MyREADME:1 names eigen(); his MAGMA
