@@ -54,6 +54,10 @@ SIGNATURES = {
     "eagle_filter_markers": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, c_lp, c_lp, C.c_long, C.c_char_p, C.c_char_p, C.c_double, c_lp]),
     "eagle_ld_window": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, C.c_long, C.c_double, C.c_double, C.POINTER(C.c_uint64), c_lp]),
     "eagle_ld_dots": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, c_lp, C.c_long, C.c_double, C.POINTER(C.c_int32)]),
+    "eagle_sample_counts": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, C.c_double, C.POINTER(C.c_int32)]),
+    "eagle_bed_sample_counts": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, C.c_double, C.POINTER(C.c_int32)]),
+    "eagle_sample_ibs": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "eagle_hwe_exact": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_long, C.c_int, c_dp]),
     "eagle_read_block": (C.c_int, [C.c_void_p, C.c_char_p, C.c_long, C.c_long, C.c_long, c_dp]),
     "eagle_calculateMMt": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double, C.c_int, c_dp, C.c_long, c_lp, C.c_int, c_dp]),
     "eagle_calculate_a_and_vara": (C.c_int, [C.c_void_p, C.c_char_p, c_dp, C.c_long, c_dp, c_dp, C.c_double, c_lp, c_dp,

@@ -750,6 +750,79 @@ static int mmt_range(eagle_ctx* ctx, const char* path, long n, long L, long c0, 
 }
 
 static int download_big(eagle_ctx* ctx, void* host_dst, const void* dev_src, size_t bytes);   // below, with the other result paths
+
+// Sample QC (eagle_sample_ibs, eagle_ingest.cpp): the two exact Gram products over all L markers of M.ascii, D = M M^T into ctx->d_c32
+// and Q = (M o M)(M o M)^T into an accumulator of its own, by mmt_range's rules -- the resident image and its cached fp4 operand when
+// the file fits, marker windows through the ChunkRing when it does not -- then k_ibs_finish.  Q's operand is never the cached image:
+// a resident file's fp4 image is copied, sign bits cleared, window by window into the ctx-owned fp4 buffer (at most 1 GiB of it); a
+// streamed window is packed into that buffer, multiplied for D, cleared in place and multiplied again for Q.
+int eagle_ibs_counts(eagle_ctx* ctx, const char* path, long n, long L, double mem_gb, int threads, int32_t* ibs0_out, int32_t* hethet_out) {
+    const long np = eagle_pad(n), Lp = eagle_pad(L);
+    const size_t accb = sizeof(int32_t) * (size_t)np * np;
+    int rc = ensure_buf(ctx, &ctx->d_c32, &ctx->c32_cap, accb, "MM^T accumulator hipMalloc");
+    if (rc) return rc;
+    DevBuf q32;
+    HIPCHK(ctx, q32.alloc(accb));
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_c32, 0, accb, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(q32.p, 0, accb, ctx->stream));
+    GenoEntry* g = nullptr;
+    rc = get_resident(ctx, path, 0, n, 0, L, mem_gb, threads, &g, 2 * accb);
+    if (rc < 0) return rc;
+    if (rc == EAGLE_OK) {
+        if (!g->dev_f4) {   // as mmt_range makes it: a later calculateMMt on the file finds the image it would have made itself
+            hipError_t e = hipMalloc(&g->dev_f4, (size_t)np * (size_t)(Lp / 2));
+            if (e != hipSuccess) { g->dev_f4 = nullptr; (void)hipGetLastError(); }
+            else if ((rc = eagle_dev_pack_fp4(ctx, g->dev, np, Lp, g->ld, g->dev_f4, ctx->stream))) { (void)hipFree(g->dev_f4); g->dev_f4 = nullptr; return rc; }
+        }
+        if (g->dev_f4 && (rc = eagle_dev_mmt_accumulate_f4(ctx, g->dev_f4, np, Lp, Lp / 2, ctx->d_c32, ctx->stream))) return rc;
+        const long Lq = std::min(Lp, std::max(256L, (long)(((size_t)2 << 30) / (size_t)np) / 256 * 256));   // markers per window of Q's operand
+        void* buf = eagle_ctx_f4_buffer(ctx, (size_t)np * (size_t)(Lq / 2));
+        if (!buf) return EAGLE_ERR_HIP;
+        for (long w0 = 0; w0 < Lp; w0 += Lq) {
+            const long nc = std::min(Lq, Lp - w0);
+            if (g->dev_f4) {
+                rc = eagle_dev_f4_abs(ctx, (const uint8_t*)g->dev_f4 + w0 / 2, Lp / 2, np, nc / 2, buf, nc / 2, ctx->stream);
+            } else {            // no room for the cached image: pack the window, use it for D, then clear the signs where it lies
+                rc = eagle_dev_pack_fp4(ctx, g->dev + w0, np, nc, g->ld, buf, ctx->stream);
+                if (!rc) rc = eagle_dev_mmt_accumulate_f4(ctx, buf, np, nc, nc / 2, ctx->d_c32, ctx->stream);
+                if (!rc) rc = eagle_dev_f4_abs(ctx, buf, nc / 2, np, nc / 2, buf, nc / 2, ctx->stream);
+            }
+            if (!rc) rc = eagle_dev_mmt_accumulate_f4(ctx, buf, np, nc, nc / 2, q32.as<int32_t>(), ctx->stream);
+            if (rc) return rc;
+        }
+    } else {
+        const long Lw = stream_chunk_rows(np, Lp);  // window width in markers; rows of the window = np
+        DevBuf win;
+        HIPCHK(ctx, win.alloc((size_t)2 * np * Lw));
+        void* buf = eagle_ctx_f4_buffer(ctx, (size_t)np * (size_t)(Lw / 2));
+        if (!buf) return EAGLE_ERR_HIP;
+        ChunkRing ring;
+        if ((rc = ring.init(ctx))) return rc;
+        ring.buf[0] = win.as<int8_t>();
+        ring.buf[1] = win.as<int8_t>() + (size_t)np * Lw;
+        for (long w0 = 0; w0 < L; w0 += Lw) {
+            const long nc = std::min(Lw, L - w0);
+            int8_t* wtile = nullptr;
+            rc = ring.load(ctx, path, 0, n, w0, nc, Lw, (size_t)np * Lw, mem_gb, threads, &wtile);
+            if (!rc) rc = eagle_dev_pack_fp4(ctx, wtile, np, Lw, Lw, buf, ctx->stream);
+            if (!rc) rc = eagle_dev_mmt_accumulate_f4(ctx, buf, np, Lw, Lw / 2, ctx->d_c32, ctx->stream);
+            if (!rc) rc = eagle_dev_f4_abs(ctx, buf, Lw / 2, np, Lw / 2, buf, Lw / 2, ctx->stream);
+            if (!rc) rc = eagle_dev_mmt_accumulate_f4(ctx, buf, np, Lw, Lw / 2, q32.as<int32_t>(), ctx->stream);
+            if (!rc) rc = ring.computed(ctx);
+            if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+        }
+        ring.finish(ctx);
+    }
+    DevBuf out;
+    const size_t outb = sizeof(int32_t) * (size_t)n * n;
+    HIPCHK(ctx, out.alloc(2 * outb));
+    rc = eagle_dev_ibs_finish(ctx, ctx->d_c32, q32.as<int32_t>(), n, np, L, out.as<int32_t>(), out.as<int32_t>() + (size_t)n * n, ctx->stream);
+    if (rc) return rc;
+    rc = download_big(ctx, ibs0_out, out.p, outb);
+    if (rc) return rc;
+    return download_big(ctx, hethet_out, (const char*)out.p + outb, outb);
+}
+
 extern "C" int eagle_calculateMMt(eagle_ctx* ctx, const char* f_name_ascii, double max_memory_in_Gbytes, int num_cores,
                                   const double* selected_loci, long n_selected, const long dims[2], int quiet,
                                   double* MMt_out) {

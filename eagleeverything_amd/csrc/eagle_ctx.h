@@ -197,6 +197,17 @@ extern "C" int eagle_dev_marker_counts(eagle_ctx* ctx, const int8_t* Mt8, long r
 extern "C" int eagle_dev_bed_marker_counts(eagle_ctx* ctx, const uint8_t* bed, long rows, long n, int32_t* counts, void* stream);
 extern "C" int eagle_dev_gather_rows_i8(eagle_ctx* ctx, const int8_t* src, long ld_src, const int32_t* map, long nrows, long rows_out,
                                         int8_t* out, long ld_out, void* stream);
+// Sample QC.  eagle_qc.hip: counts[n][4] (hom A1, het, hom A2, missing per INDIVIDUAL; zeroed by the caller before a file's first
+// window) += the counts over `rows` raw .bed rows; ibs0 / hethet (n x n int32, full and symmetric) from the Gram accumulators D32, Q32
+// (n_pad x n_pad, upper 256-tiles live) and the marker count L; p[L] = the Hardy-Weinberg exact test of counts[L][stride] (stride 3
+// or 4, the first three columns used).  eagle_i8mfma.hip: rows x row_bytes of an fp4 image copied with every code's sign bit cleared.
+// eagle_api.cpp: both Gram products of M.ascii and the finish, resident or streamed (the host side of eagle_sample_ibs).
+extern "C" int eagle_dev_bed_sample_counts(eagle_ctx* ctx, const uint8_t* bed, long rows, long n, int32_t* counts, void* stream);
+extern "C" int eagle_dev_ibs_finish(eagle_ctx* ctx, const int32_t* D32, const int32_t* Q32, long n, long n_pad, long L, int32_t* ibs0,
+                                    int32_t* hethet, void* stream);
+extern "C" int eagle_dev_hwe_exact(eagle_ctx* ctx, const int32_t* counts, long L, int stride, double* p, void* stream);
+extern "C" int eagle_dev_f4_abs(eagle_ctx* ctx, const void* src4, long ld4_src, long rows, long row_bytes, void* dst4, long ld4_dst, void* stream);
+int eagle_ibs_counts(eagle_ctx* ctx, const char* path, long n, long L, double mem_gb, int threads, int32_t* ibs0_out, int32_t* hethet_out);
 inline bool eagle_sidecar_enabled() { const char* e = getenv("EAGLE_HIP_SIDECAR"); return !(e && e[0] == '0'); }
 // Whole-file resident copy (loads it if needed); EAGLE_OK, 2 (too large for HBM: stream it) or an error.
 int eagle_get_resident(eagle_ctx* ctx, const char* path, long rows, long cols, double max_mem_gb, int threads, const GenoEntry** out);

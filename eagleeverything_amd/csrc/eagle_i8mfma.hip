@@ -2047,6 +2047,31 @@ extern "C" int eagle_dev_pack_fp4(eagle_ctx* ctx, const int8_t* Mt8, long L_pad,
     return EAGLE_OK;
 }
 
+// The operand image of Q = (M o M)(M o M)^T (sample QC, eagle_hip.h section 1b'''): the e2m1 codes of -1, 0, +1 are 0xA, 0x0, 0x2, so
+// clearing every code's sign bit (byte & 0x77) squares the genotype.  Copies `rows` rows of `row_bytes` bytes (a multiple of 16)
+// from one fp4 image into ANOTHER buffer, 16 bytes per thread; src == dst with equal strides is allowed (the ctx-owned scratch image
+// of a streamed window), the cached image of a resident file is only ever the source.
+__global__ __launch_bounds__(256) void k_f4_abs(const uint8_t* src, long ld_src, long rows, long chunks, uint8_t* dst, long ld_dst) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= rows * chunks) return;
+    const long r = t / chunks, c = (t - r * chunks) * 16;
+    i32x4 v = *(const i32x4*)(src + r * ld_src + c);
+#pragma unroll
+    for (int i = 0; i < 4; i++) v[i] &= 0x77777777;
+    *(i32x4*)(dst + r * ld_dst + c) = v;
+}
+extern "C" int eagle_dev_f4_abs(eagle_ctx* ctx, const void* src4, long ld4_src, long rows, long row_bytes, void* dst4, long ld4_dst, void* stream) {
+    if (rows <= 0 || row_bytes <= 0) return EAGLE_OK;
+    if (row_bytes % 16 || ld4_src % 16 || ld4_dst % 16 || row_bytes > ld4_src || row_bytes > ld4_dst || (((uintptr_t)src4 | (uintptr_t)dst4) & 15))
+        return eagle_fail(ctx, EAGLE_ERR_ARG, "f4_abs: layout contract violated");
+    const long chunks = row_bytes / 16, blocks = (rows * chunks + 255) / 256;
+    if (blocks > 0x7fffffffL) return eagle_fail(ctx, EAGLE_ERR_ARG, "f4_abs: image too large for one launch");
+    hipLaunchKernelGGL(k_f4_abs, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)src4, ld4_src, rows, chunks, (uint8_t*)dst4, ld4_dst);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return eagle_fail_hip(ctx, e, "k_f4_abs");
+    return EAGLE_OK;
+}
+
 // The operand image of the MM^T kernel straight from the marker-major genotypes: M4[individual][marker / 2] (fp4, two per byte,
 // the even marker in the low nibble) from Mt8[marker][individual] in ONE pass -- a 256-marker x 128-individual tile goes through LDS,
 // each thread gathers 128 markers of its individual (all lanes of a wave read one LDS row: 64 consecutive bytes, conflict

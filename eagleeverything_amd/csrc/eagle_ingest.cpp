@@ -822,14 +822,10 @@ int qc_fail(eagle_ctx* ctx, int code, const char* msg) {
 
 }  // namespace
 
-// The image of Mt.ascii is counted where it lies when it is (or can be made) resident; else in row windows of the size the streamed
+// counts_out[3 i .. 3 i + 2] = the numbers of '0', '1', '2' characters of line i of a genotype file of L lines of n characters.
+// The image is counted where it lies when it is (or can be made) resident; else in row windows of the size the streamed
 // scans use, each loaded through eagle_dev_load_ascii (sidecar, text, or a VIEW's source) and counted before the next one is read.
-extern "C" int eagle_marker_counts(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long dims[2], double max_memory_in_Gbytes,
-                                   int32_t* counts_out) {
-    if (!f_name_ascii_Mt || !dims || !counts_out) return qc_fail(ctx, EAGLE_ERR_ARG, "marker_counts: NULL argument");
-    const long n = dims[0], L = dims[1];
-    if (n <= 0 || L <= 0) return qc_fail(ctx, EAGLE_ERR_ARG, "marker_counts: dims must be positive");
-    if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "marker_counts: no context");
+static int line_counts(eagle_ctx* ctx, const char* f_name_ascii_Mt, long n, long L, double max_memory_in_Gbytes, int32_t* counts_out) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const int threads = host_threads();
     DevBuf counts;
@@ -856,6 +852,15 @@ extern "C" int eagle_marker_counts(eagle_ctx* ctx, const char* f_name_ascii_Mt, 
     HIPCHK(ctx, hipMemcpyAsync(counts_out, counts.p, sizeof(int32_t) * 3 * (size_t)L, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return EAGLE_OK;
+}
+
+extern "C" int eagle_marker_counts(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long dims[2], double max_memory_in_Gbytes,
+                                   int32_t* counts_out) {
+    if (!f_name_ascii_Mt || !dims || !counts_out) return qc_fail(ctx, EAGLE_ERR_ARG, "marker_counts: NULL argument");
+    const long n = dims[0], L = dims[1];
+    if (n <= 0 || L <= 0) return qc_fail(ctx, EAGLE_ERR_ARG, "marker_counts: dims must be positive");
+    if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "marker_counts: no context");
+    return line_counts(ctx, f_name_ascii_Mt, n, L, max_memory_in_Gbytes, counts_out);
 }
 
 // The rows go through the pinned staging ring in windows of up to 64 MiB, as eagle_create_ascii_from_bed reads them: the pread of
@@ -1143,6 +1148,97 @@ extern "C" int eagle_ld_dots(eagle_ctx* ctx, const char* f_name_ascii_Mt, const 
         }
     }
     HIPCHK(ctx, hipMemcpyAsync(dots_out, dots.p, sizeof(int32_t) * (size_t)L * (size_t)k, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return EAGLE_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Sample QC: per-individual counts, pairwise IBS counts, the Hardy-Weinberg exact test (no counterpart in the reference; kernels in
+// eagle_qc.hip, Q's operand pass in eagle_i8mfma.hip, the two Gram products in eagle_api.cpp)
+// ---------------------------------------------------------------------------------------------------------------
+
+// A line of M.ascii is an individual: k_marker_counts on the individual-major image, where it lies or in bands of whole lines.
+extern "C" int eagle_sample_counts(eagle_ctx* ctx, const char* f_name_ascii_M, const long dims[2], double max_memory_in_Gbytes,
+                                   int32_t* counts_out) {
+    if (!f_name_ascii_M || !dims || !counts_out) return qc_fail(ctx, EAGLE_ERR_ARG, "sample_counts: NULL argument");
+    const long n = dims[0], L = dims[1];
+    if (n <= 0 || L <= 0) return qc_fail(ctx, EAGLE_ERR_ARG, "sample_counts: dims must be positive");
+    if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "sample_counts: no context");
+    return line_counts(ctx, f_name_ascii_M, L, n, max_memory_in_Gbytes, counts_out);
+}
+
+// The windows of eagle_bed_marker_counts through the same staging ring; every window's counts are added to the n x 4 array in HBM.
+extern "C" int eagle_bed_sample_counts(eagle_ctx* ctx, const char* bed_path, const long dims[2], double max_memory_in_Gbytes,
+                                       int32_t* counts_out) {
+    if (!bed_path || !dims || !counts_out) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_sample_counts: NULL argument");
+    const long n = dims[0], L = dims[1];
+    if (n <= 0 || L <= 0 || L > 0x7fffffffL) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_sample_counts: bad dims");
+    if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_sample_counts: no context");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int fdin = -1;
+    if (int orc = open_bed(ctx, bed_path, n, L, &fdin)) return orc;
+    struct Closer { int fd; ~Closer() { if (fd >= 0) close(fd); } } closer{fdin};
+    const int threads = host_threads();
+    const long rb = bed_row_bytes(n);
+    double cap = 67108864.0;
+    if (max_memory_in_Gbytes > 0) cap = std::min(cap, max_memory_in_Gbytes * 1e9 / 4.0);  // the loaders' staging rule
+    const long w = std::max(1L, std::min(std::min(L, 1L << 25), (long)cap / rb));
+    int rc = eagle_stage_ensure(ctx, (size_t)w * rb);
+    if (rc) return rc;
+    DevBuf counts;
+    HIPCHK(ctx, counts.alloc(sizeof(int32_t) * 4 * (size_t)n));
+    HIPCHK(ctx, hipMemsetAsync(counts.p, 0, sizeof(int32_t) * 4 * (size_t)n, ctx->stream));
+    hipEvent_t done[2] = {nullptr, nullptr};
+    for (int b = 0; b < 2; b++) HIPCHK(ctx, hipEventCreateWithFlags(&done[b], hipEventDisableTiming));
+    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int b = 0; b < 2; b++) if (e[b]) (void)hipEventDestroy(e[b]); } } evg{done};
+    long k = 0;
+    for (long r0 = 0; r0 < L; r0 += w, k++) {
+        const int b = (int)(k & 1);
+        const long nr = std::min(w, L - r0);
+        if (k >= 2) HIPCHK(ctx, hipEventSynchronize(done[b]));  // window k - 2 has left staging buffer b
+        if (!pread_all(fdin, (char*)ctx->stage_pin[b], (size_t)nr * rb, (off_t)BED_HEADER_BYTES + (off_t)r0 * rb, threads)) {
+            (void)hipStreamSynchronize(ctx->stream);
+            return failf(ctx, EAGLE_ERR_FORMAT, "%s: could not read markers %ld to %ld", bed_path, r0 + 1, r0 + nr);
+        }
+        HIPCHK(ctx, hipMemcpyAsync(ctx->stage_raw[b], ctx->stage_pin[b], (size_t)nr * rb, hipMemcpyHostToDevice, ctx->stream));
+        rc = eagle_dev_bed_sample_counts(ctx, (const uint8_t*)ctx->stage_raw[b], nr, n, counts.as<int32_t>(), ctx->stream);
+        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+        HIPCHK(ctx, hipEventRecord(done[b], ctx->stream));
+    }
+    HIPCHK(ctx, hipMemcpyAsync(counts_out, counts.p, sizeof(int32_t) * 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return EAGLE_OK;
+}
+
+extern "C" int eagle_sample_ibs(eagle_ctx* ctx, const char* f_name_ascii_M, const long dims[2], double max_memory_in_Gbytes, int32_t* ibs0_out,
+                                int32_t* hethet_out) {
+    if (!f_name_ascii_M || !dims || !ibs0_out || !hethet_out) return qc_fail(ctx, EAGLE_ERR_ARG, "sample_ibs: NULL argument");
+    const long n = dims[0], L = dims[1];
+    if (n <= 0 || L <= 0 || L > 0x7fffffffL) return qc_fail(ctx, EAGLE_ERR_ARG, "sample_ibs: bad dims");
+    if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "sample_ibs: no context");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return eagle_ibs_counts(ctx, f_name_ascii_M, n, L, max_memory_in_Gbytes, host_threads(), ibs0_out, hethet_out);
+}
+
+extern "C" int eagle_hwe_exact(eagle_ctx* ctx, const int32_t* counts, long L, int stride, double* p_out) {
+    if (!counts || !p_out) return qc_fail(ctx, EAGLE_ERR_ARG, "hwe_exact: NULL argument");
+    if (L <= 0) return qc_fail(ctx, EAGLE_ERR_ARG, "hwe_exact: the number of markers must be positive");
+    if (stride != 3 && stride != 4) return qc_fail(ctx, EAGLE_ERR_ARG, "hwe_exact: stride must be 3 or 4");
+    for (long i = 0; i < L; i++) {
+        const int32_t* c = counts + i * stride;
+        if (c[0] < 0 || c[1] < 0 || c[2] < 0 || (long)c[0] + c[1] + c[2] > (1L << 30))
+            return qc_fail(ctx, EAGLE_ERR_ARG, "hwe_exact: a count is negative or a marker has more than 2^30 genotypes");
+    }
+    if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "hwe_exact: no context");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    DevBuf dc, dp;
+    const size_t cb = sizeof(int32_t) * (size_t)L * (size_t)stride;
+    HIPCHK(ctx, dc.alloc(cb));
+    HIPCHK(ctx, dp.alloc(sizeof(double) * (size_t)L));
+    HIPCHK(ctx, hipMemcpyAsync(dc.p, counts, cb, hipMemcpyHostToDevice, ctx->stream));
+    int rc = eagle_dev_hwe_exact(ctx, dc.as<int32_t>(), L, stride, dp.as<double>(), ctx->stream);
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    HIPCHK(ctx, hipMemcpyAsync(p_out, dp.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return EAGLE_OK;
 }

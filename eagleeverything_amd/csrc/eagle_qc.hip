@@ -1,5 +1,6 @@
-// eagle_qc.hip -- marker QC on the device: per-marker genotype counts and the row compaction of a marker subset.  All three kernels
-// are HBM-bound streaming passes with integer arithmetic only (the statistics are made from the counts on the host, in fp64).
+// eagle_qc.hip -- marker and sample QC on the device: genotype counts per marker and per individual, the row compaction of a marker
+// subset, the finish of the pairwise IBS counts and the Hardy-Weinberg exact test.  The counting kernels are HBM-bound streaming passes
+// with integer arithmetic only (the statistics are made from the counts on the host, in fp64); k_hwe_exact is the one fp64 kernel.
 //
 //   k_marker_counts ....... the int8 marker-major image Mt8 (rows x ld, values -1/0/+1, zero padding) -> int32 counts[rows][3] =
 //                           (n0, n1, n2), the numbers of '0', '1', '2' characters of the marker's line.  Per row s = sum g and
@@ -8,6 +9,11 @@
 //   k_bed_marker_counts ... raw SNP-major .bed rows (ceil(n/4) bytes per marker, individual 4b+q at bits 2q of byte b) -> int32
 //                           counts[rows][4] = (hom A1, het, hom A2, missing), popcounts on dwords of the two bit planes.
 //   k_gather_rows_i8 ...... out[r] = src[map[r]] for r < nrows, zero rows up to rows_out: the Mt image of a marker subset.
+//   k_bed_sample_counts ... the same raw .bed rows -> int32 counts[n][4] per INDIVIDUAL, added to what the array holds (the column
+//                           reduction of the rows k_bed_marker_counts reduces along).
+//   k_ibs_finish .......... the int32 Gram accumulators D = M M^T and Q = (M o M)(M o M)^T (upper 256-tiles live) and L -> the full
+//                           symmetric int32 matrices ibs0 = (Q - D) / 2 and hethet = L - Q_ii - Q_jj + Q_ij.
+//   k_hwe_exact ........... int32 counts[L][stride] -> the exact Hardy-Weinberg p-value of every marker, one marker per thread.
 //
 // A row is owned by G = 16, 32 or 64 consecutive lanes of one wave (16 for the shortest rows, so that a 256-byte row does not idle
 // three quarters of a wave); the G partial sums meet in a butterfly (__shfl_xor), after which every lane of the group holds the
@@ -162,6 +168,170 @@ extern "C" int eagle_dev_gather_rows_i8(eagle_ctx* ctx, const int8_t* src, long 
     if (blocks > 0x7fffffffL) return eagle_fail(ctx, EAGLE_ERR_ARG, "gather_rows_i8: too many rows");
     hipLaunchKernelGGL(k_gather_rows_i8, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, src, ld_src, map, nrows, rows_out, out,
                        ld_out, lanes16);
+    QC_LAUNCH_CHECK(ctx);
+    return EAGLE_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Per-individual counts of raw .bed rows.  A thread owns one byte column (four individuals) of a chunk of BSC_ROWS rows: consecutive
+// lanes read consecutive bytes of a row (byte loads: rows have no alignment).  The three code planes of a byte -- bits 0, 2, 4, 6 of
+// lo & ~hi (missing), hi & ~lo (het), lo & hi (hom A2) -- are spread to bits 0, 8, 16, 24 of a dword and added there, four 8-bit
+// counters per plane, which are flushed into 32-bit counters every 255 rows.  hom A1 = rows of the chunk - the other three.  The
+// chunk's sixteen totals are added to counts[n][4] with integer atomics: integer sums, so the result does not depend on the order.
+// ------------------------------------------------------------------------------------------------------------------------------
+#define BSC_ROWS 1020   // rows per block: 4 x 255
+__device__ __forceinline__ uint32_t bsc_spread(uint32_t x) { return (x | (x << 6) | (x << 12) | (x << 18)) & 0x01010101u; }
+
+__global__ __launch_bounds__(256) void k_bed_sample_counts(const uint8_t* __restrict__ bed, long rb, long rows, long n,
+                                                           int32_t* __restrict__ counts) {
+    const long b = (long)blockIdx.x * 256 + threadIdx.x;     // byte column
+    if (b >= rb) return;
+    const long r0 = (long)blockIdx.y * BSC_ROWS, r1 = r0 + BSC_ROWS < rows ? r0 + BSC_ROWS : rows;
+    const long left = n - 4 * b;                              // individuals of the file among this byte's four fields (> 0)
+    const uint32_t keep = left < 4 ? (1u << (2 * left)) - 1u : 0xffu;   // the unused bit pairs of a row's last byte are cleared
+    int het[4] = {0, 0, 0, 0}, hom2[4] = {0, 0, 0, 0}, miss[4] = {0, 0, 0, 0};
+    for (long ra = r0; ra < r1; ra += 255) {
+        const long rbnd = ra + 255 < r1 ? ra + 255 : r1;
+        uint32_t ph = 0, p2 = 0, pm = 0;
+        const uint8_t* s = bed + ra * rb + b;
+        for (long r = ra; r < rbnd; r++, s += rb) {
+            const uint32_t x = (uint32_t)*s & keep;
+            const uint32_t lo = x & 0x55u, hi = (x >> 1) & 0x55u;
+            pm += bsc_spread(lo & ~hi);
+            ph += bsc_spread(hi & ~lo);
+            p2 += bsc_spread(lo & hi);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            het[q] += (int)((ph >> (8 * q)) & 0xffu);
+            hom2[q] += (int)((p2 >> (8 * q)) & 0xffu);
+            miss[q] += (int)((pm >> (8 * q)) & 0xffu);
+        }
+    }
+    const int nr = (int)(r1 - r0);
+#pragma unroll
+    for (int q = 0; q < 4; q++)
+        if (q < left) {
+            int32_t* c = counts + (4 * b + q) * 4;
+            atomicAdd(c + 0, nr - het[q] - hom2[q] - miss[q]);
+            atomicAdd(c + 1, het[q]);
+            atomicAdd(c + 2, hom2[q]);
+            atomicAdd(c + 3, miss[q]);
+        }
+}
+
+// counts[n][4] (caller-zeroed before the first window of a file) += the counts of the individuals over `rows` raw .bed rows
+extern "C" int eagle_dev_bed_sample_counts(eagle_ctx* ctx, const uint8_t* bed, long rows, long n, int32_t* counts, void* stream) {
+    if (rows <= 0) return EAGLE_OK;
+    if (n <= 0 || n > 0x3fffffffL) return eagle_fail(ctx, EAGLE_ERR_ARG, "bed_sample_counts: bad shape");
+    const long rb = bed_row_bytes(n), chunks = (rows + BSC_ROWS - 1) / BSC_ROWS;
+    if (chunks > 65535) return eagle_fail(ctx, EAGLE_ERR_ARG, "bed_sample_counts: too many rows in one window");
+    hipLaunchKernelGGL(k_bed_sample_counts, dim3((unsigned)((rb + 255) / 256), (unsigned)chunks), dim3(256), 0, (hipStream_t)stream, bed, rb,
+                       rows, n, counts);
+    QC_LAUNCH_CHECK(ctx);
+    return EAGLE_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// One block per 32 x 32 tile on or above the diagonal (the tiling of k_mmt_finish): coalesced reads of the two int32 accumulators,
+// coalesced writes of the two results and, through LDS, of their mirror images.  q_i = Q_ii lies in a diagonal 256-tile, which is live.
+// ------------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_ibs_finish(const int32_t* __restrict__ D, const int32_t* __restrict__ Q, long n, long ldc, int L,
+                                                    int32_t* __restrict__ ibs0, int32_t* __restrict__ hethet) {
+    const long bi = (long)blockIdx.y * 32, bj = (long)blockIdx.x * 32;
+    if (bj < bi) return;
+    __shared__ int32_t t0[32][33], t1[32][33];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const long j = bj + tx;
+    const int qj = j < n ? Q[j * ldc + j] : 0;
+    for (int r = ty; r < 32; r += 8) {
+        const long i = bi + r;
+        int a = 0, h = 0;
+        if (i < n && j < n) {
+            const int q = Q[i * ldc + j], d = D[i * ldc + j];
+            a = (q - d) >> 1;                       // opposite homozygotes: the difference is even and not negative
+            h = L - Q[i * ldc + i] - qj + q;        // both heterozygous
+            ibs0[i * n + j] = a;
+            hethet[i * n + j] = h;
+        }
+        t0[r][tx] = a;
+        t1[r][tx] = h;
+    }
+    __syncthreads();
+    if (bj > bi)
+        for (int r = ty; r < 32; r += 8) {
+            const long jj = bj + r, ii = bi + tx;   // out[jj][ii] = the value at (ii, jj)
+            if (ii < n && jj < n) {
+                ibs0[jj * n + ii] = t0[tx][r];
+                hethet[jj * n + ii] = t1[tx][r];
+            }
+        }
+}
+
+extern "C" int eagle_dev_ibs_finish(eagle_ctx* ctx, const int32_t* D32, const int32_t* Q32, long n, long n_pad, long L, int32_t* ibs0,
+                                    int32_t* hethet, void* stream) {
+    if (n <= 0 || n > n_pad || n_pad % 256 || L <= 0 || L > 0x7fffffffL) return eagle_fail(ctx, EAGLE_ERR_ARG, "ibs_finish: bad shape");
+    const unsigned nb = (unsigned)((n + 31) / 32);
+    hipLaunchKernelGGL(k_ibs_finish, dim3(nb, nb), dim3(256), 0, (hipStream_t)stream, D32, Q32, n, n_pad, (int)L, ibs0, hethet);
+    QC_LAUNCH_CHECK(ctx);
+    return EAGLE_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Hardy-Weinberg exact test, in the order the sample-QC section of eagle_hip.h fixes: every product, quotient and sum below is one
+// correctly rounded fp64 operation (__dmul_rn / __ddiv_rn / __dadd_rn: nothing is contracted into an FMA), the integer factors are
+// exact int64 products converted once.  hwe_walk visits mid first, then the leg below it (h = mid - 2, mid - 4, ...), then the leg
+// above: with cut < 0 it returns the total and leaves P(n_AB) in *p_obs; with cut >= 0 it returns the sum of the terms <= cut, in the
+// same order.  Two walks per marker and no array.  One marker per thread: the lanes of a wave run as long as their longest marker.
+// ------------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double hwe_walk(long mid, long hr0, long hc0, long r, long n_ab, double cut, double* p_obs) {
+    const bool tail = cut >= 0.0;
+    double sum = (!tail || 1.0 <= cut) ? 1.0 : 0.0;
+    double pobs = 1.0;                                   // P(mid): the value if n_AB == mid
+    double p = 1.0;
+    long a = hr0, b = hc0;
+    for (long h = mid; h >= 2; h -= 2) {                 // P(h - 2) = P(h) h (h - 1) / (4 (hr + 1) (hc + 1))
+        p = __ddiv_rn(__dmul_rn(p, (double)(h * (h - 1))), (double)(4 * (a + 1) * (b + 1)));
+        a++; b++;
+        if (h - 2 == n_ab) pobs = p;
+        if (!tail || p <= cut) sum = __dadd_rn(sum, p);
+    }
+    p = 1.0; a = hr0; b = hc0;
+    for (long h = mid; h <= r - 2; h += 2) {             // P(h + 2) = P(h) 4 hr hc / ((h + 2) (h + 1))
+        p = __ddiv_rn(__dmul_rn(p, (double)(4 * a * b)), (double)((h + 2) * (h + 1)));
+        a--; b--;
+        if (h + 2 == n_ab) pobs = p;
+        if (!tail || p <= cut) sum = __dadd_rn(sum, p);
+    }
+    if (p_obs) *p_obs = pobs;
+    return sum;
+}
+
+__global__ __launch_bounds__(256) void k_hwe_exact(const int32_t* __restrict__ counts, long L, int stride, double* __restrict__ pout) {
+    const long m = (long)blockIdx.x * 256 + threadIdx.x;
+    if (m >= L) return;
+    const long n_aa = counts[m * stride], n_ab = counts[m * stride + 1], n_bb = counts[m * stride + 2];
+    const long N = n_aa + n_ab + n_bb;
+    if (N == 0) { pout[m] = 1.0; return; }
+    const long hr = n_aa < n_bb ? n_aa : n_bb;
+    const long r = 2 * hr + n_ab;                        // copies of the rare allele
+    long mid = r * (2 * N - r) / (2 * N);                // floor of the expected heterozygotes, then up to the parity of r
+    if ((mid ^ r) & 1) mid++;
+    const long hr0 = (r - mid) / 2, hc0 = N - mid - hr0;
+    double pobs;
+    const double total = hwe_walk(mid, hr0, hc0, r, n_ab, -1.0, &pobs);
+    const double tail = hwe_walk(mid, hr0, hc0, r, n_ab, pobs, nullptr);
+    const double pv = __ddiv_rn(tail, total);
+    pout[m] = pv > 1.0 ? 1.0 : pv;
+}
+
+// counts: device int32 [L][stride], stride 3 or 4, every count >= 0 and every row sum <= 2^30 (the caller's check)
+extern "C" int eagle_dev_hwe_exact(eagle_ctx* ctx, const int32_t* counts, long L, int stride, double* p, void* stream) {
+    if (L <= 0) return EAGLE_OK;
+    if (stride != 3 && stride != 4) return eagle_fail(ctx, EAGLE_ERR_ARG, "hwe_exact: stride must be 3 or 4");
+    const long blocks = (L + 255) / 256;
+    if (blocks > 0x7fffffffL) return eagle_fail(ctx, EAGLE_ERR_ARG, "hwe_exact: too many markers");
+    hipLaunchKernelGGL(k_hwe_exact, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, counts, L, stride, p);
     QC_LAUNCH_CHECK(ctx);
     return EAGLE_OK;
 }

@@ -311,12 +311,17 @@ def marker_stats_from_counts(n0, n1, n2, n_missing=None):
     return {"n0": n0, "n1": n1, "n2": n2, "n_missing": nm, "freq": freq, "maf": maf, "het": het, "call_rate": call_rate}
 
 
-def marker_keep_mask(stats, maf=None, max_missing=None, drop_monomorphic=False):
+def marker_keep_mask(stats, maf=None, max_missing=None, drop_monomorphic=False, hwe=None):
     """Which markers a filter keeps (boolean, length L), by PLINK's rules on the output of marker_stats_from_counts: keep
     maf >= `maf`; drop n_missing / n > `max_missing`; drop_monomorphic drops maf == 0; a marker without a called genotype is dropped
-    by any of the three.  With no filter switched on every marker is kept."""
+    by any of the three.  hwe drops the markers whose Hardy-Weinberg exact test has p < `hwe` (stats["hwe_p"]: MarkerStats(..., hwe=True)
+    or HWE(stats)); it drops nothing else.  With no filter switched on every marker is kept."""
     L = len(stats["n0"])
     keep = np.ones(L, dtype=bool)
+    if hwe is not None:
+        if "hwe_p" not in stats:
+            raise ValueError("marker_keep_mask: hwe= needs stats[\"hwe_p\"] (MarkerStats(..., hwe=True))")
+        keep &= ~(np.asarray(stats["hwe_p"], dtype=np.float64) < float(hwe))
     if maf is None and max_missing is None and not drop_monomorphic:
         return keep
     keep &= ~np.isnan(stats["maf"])
@@ -330,9 +335,9 @@ def marker_keep_mask(stats, maf=None, max_missing=None, drop_monomorphic=False):
     return keep
 
 
-def MarkerStats(geno, bed=None, availmemGb=8, device=0):
+def MarkerStats(geno, bed=None, availmemGb=8, device=0, hwe=False):
     """Per-marker QC statistics of a panel -> dict of length-L arrays n0, n1, n2, n_missing, freq, maf, het, call_rate
-    (marker_stats_from_counts); the counting runs on the device (rcpp_api.marker_counts on geno["asciifileMt"]: one pass over the
+    (marker_stats_from_counts), with hwe=True also hwe_p, the Hardy-Weinberg exact test of (n0, n1, n2) (HWE); the counting runs on the device (rcpp_api.marker_counts on geno["asciifileMt"]: one pass over the
     int8 image the scans read), the arithmetic on the host.
     The text files of a panel no longer know which genotypes were missing: ingestion made them heterozygotes, so without `bed`
     n_missing is zero, n1 includes them and call_rate is 1.  bed = the .bed file (or prefix) the panel was ingested from: the counts
@@ -341,35 +346,43 @@ def MarkerStats(geno, bed=None, availmemGb=8, device=0):
     n, L = int(geno["dim_of_ascii_M"][0]), int(geno["dim_of_ascii_M"][1])
     if bed is not None:
         c = rcpp_api.bed_marker_counts(bed_fileset(bed)[0], (n, L), availmemGb, device=device)
-        return marker_stats_from_counts(c[:, 0], c[:, 1], c[:, 2], c[:, 3])
-    c = rcpp_api.marker_counts(geno["asciifileMt"], (n, L), availmemGb, device=device)
-    return marker_stats_from_counts(c[:, 0], c[:, 1], c[:, 2])
+        stats = marker_stats_from_counts(c[:, 0], c[:, 1], c[:, 2], c[:, 3])
+    else:
+        c = rcpp_api.marker_counts(geno["asciifileMt"], (n, L), availmemGb, device=device)
+        stats = marker_stats_from_counts(c[:, 0], c[:, 1], c[:, 2])
+    if hwe:
+        stats["hwe_p"] = rcpp_api.hwe_exact(c, device=device)
+    return stats
 
 
 def FilterMarkers(geno, maf=None, max_missing=None, drop_monomorphic=False, bed=None, stats=None, outdir=None, availmemGb=8,
-                  message=None, device=0):
+                  message=None, device=0, hwe=None):
     """A panel without the markers a QC filter drops -> geno dict {asciifileM, asciifileMt, dim_of_ascii_M, marker_index}:
     marker_index = int64, the kept markers' 0-based indices in the panel `geno` came from (composed with geno's own marker_index
-    when it is itself a filtered panel).  The rules are marker_keep_mask's on `stats` (default MarkerStats(geno, bed)).  The files
+    when it is itself a filtered panel).  The rules are marker_keep_mask's on `stats` (default MarkerStats(geno, bed); with hwe= the
+    exact-test p-values are added to statistics that do not hold them).  The files
     are written by rcpp_api.filter_markers into `outdir` (default: a qc/ directory beside the source files; it must not be the
     source's directory) and are what ReadMarker leaves for a genotype file that holds only the kept markers.
     Nothing dropped: the source dict with the identity marker_index, nothing written.  Nothing kept: None, after a message."""
     say = message or (lambda s: None)
     n, L = int(geno["dim_of_ascii_M"][0]), int(geno["dim_of_ascii_M"][1])
     if stats is None:
-        stats = MarkerStats(geno, bed=bed, availmemGb=availmemGb, device=device)
+        stats = MarkerStats(geno, bed=bed, availmemGb=availmemGb, device=device, hwe=hwe is not None)
     if len(stats["n0"]) != L:
         say(" Error: the marker statistics hold %d markers, the panel %d. " % (len(stats["n0"]), L))
         say(" FilterMarkers has terminated with errors")
         return None
-    idx = np.flatnonzero(marker_keep_mask(stats, maf=maf, max_missing=max_missing, drop_monomorphic=drop_monomorphic)).astype(np.int64)
+    if hwe is not None and "hwe_p" not in stats:
+        stats = dict(stats, hwe_p=HWE(stats, device=device))
+    idx = np.flatnonzero(marker_keep_mask(stats, maf=maf, max_missing=max_missing, drop_monomorphic=drop_monomorphic, hwe=hwe)).astype(np.int64)
     base = np.asarray(geno["marker_index"], dtype=np.int64) if "marker_index" in geno else np.arange(L, dtype=np.int64)
     if idx.size == L:
         out = dict(geno)
         out["marker_index"] = base
         return out
     if idx.size == 0:
-        say(" Error: no marker passes the filter (maf=%s, max_missing=%s, drop_monomorphic=%s). " % (maf, max_missing, drop_monomorphic))
+        say(" Error: no marker passes the filter (maf=%s, max_missing=%s, drop_monomorphic=%s%s). "
+            % (maf, max_missing, drop_monomorphic, "" if hwe is None else ", hwe=%s" % hwe))
         say(" FilterMarkers has terminated with errors")
         return None
     srcdir = os.path.dirname(os.path.abspath(geno["asciifileM"]))
@@ -383,6 +396,164 @@ def FilterMarkers(geno, maf=None, max_missing=None, drop_monomorphic=False, bed=
     dims = rcpp_api.filter_markers(geno["asciifileM"], geno["asciifileMt"], (n, L), idx, outM, outMt, availmemGb, device=device)
     say(" %d of %d markers kept. " % (idx.size, L))
     return {"asciifileM": outM, "asciifileMt": outMt, "dim_of_ascii_M": dims, "marker_index": base[idx]}
+
+
+def HWE(stats_or_counts, device=0):
+    """Hardy-Weinberg exact test per marker -> fp64 p (length L), on the device (rcpp_api.hwe_exact: one marker per thread, the order
+    of operations of include/eagle_hip.h section 1b''').  stats_or_counts: the dict of MarkerStats / marker_stats_from_counts (its
+    n0, n1, n2), or an integer (L, 3) or (L, 4) array of (n_AA, n_AB, n_BB[, unused]) rows."""
+    if hasattr(stats_or_counts, "keys"):
+        c = np.stack([np.asarray(stats_or_counts[k], dtype=np.int64).ravel() for k in ("n0", "n1", "n2")], axis=1)
+    else:
+        c = np.asarray(stats_or_counts)
+    return rcpp_api.hwe_exact(c, device=device)
+
+
+def sample_stats_from_counts(n0, n1, n2, n_missing=None, marker_stats=None):
+    """Per-individual statistics from integer genotype counts over the markers of a panel, in numpy fp64 (nothing here touches a
+    device): n0 / n1 / n2 = the individual's called genotypes coded 0 / 1 / 2, n_missing = its genotypes without a call (default
+    none).  het_rate = n1 / (n0 + n1 + n2);  hom_count = n0 + n2;  call_rate = called / (called + n_missing).  With marker_stats (the
+    dict of MarkerStats for the same panel) also the method-of-moments inbreeding coefficient F = (O - E) / (L_i - E):  O = hom_count,
+    L_i = the individual's called genotypes (L without missing genotypes) and E = sum over the markers with a called genotype of
+    1 - 2 p (1 - p) 2m / (2m - 1), p = the marker's allele frequency and m its called genotypes (the number of individuals without
+    missing genotypes): the homozygotes expected of an outbred individual.  F = NaN when L_i = E."""
+    n0, n1, n2 = (np.asarray(v, dtype=np.int64).ravel() for v in (n0, n1, n2))
+    nm = np.zeros_like(n0) if n_missing is None else np.asarray(n_missing, dtype=np.int64).ravel()
+    called = n0 + n1 + n2
+    with np.errstate(divide="ignore", invalid="ignore"):
+        het_rate = np.where(called > 0, n1 / called.astype(np.float64), np.nan)
+        call_rate = np.where(called + nm > 0, called / np.maximum(called + nm, 1).astype(np.float64), 0.0)
+    out = {"n0": n0, "n1": n1, "n2": n2, "n_missing": nm, "het_rate": het_rate, "hom_count": n0 + n2, "call_rate": call_rate}
+    if marker_stats is not None:
+        p = np.asarray(marker_stats["freq"], dtype=np.float64)
+        m = (np.asarray(marker_stats["n0"], dtype=np.int64) + np.asarray(marker_stats["n1"], dtype=np.int64)
+             + np.asarray(marker_stats["n2"], dtype=np.int64)).astype(np.float64)
+        ok = m > 0
+        two_m = 2.0 * m[ok]
+        E = float(np.sum(1.0 - 2.0 * p[ok] * (1.0 - p[ok]) * two_m / (two_m - 1.0)))
+        den = called.astype(np.float64) - E
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out["F"] = np.where(den != 0.0, ((n0 + n2).astype(np.float64) - E) / np.where(den != 0.0, den, 1.0), np.nan)
+        out["expected_hom"] = E
+    return out
+
+
+def SampleStats(geno, bed=None, marker_stats=None, availmemGb=8, device=0):
+    """Per-individual QC statistics of a panel -> dict of length-n arrays n0, n1, n2, het_rate, hom_count, F (and expected_hom, the E
+    of F): sample_stats_from_counts on the device's counts (rcpp_api.sample_counts on geno["asciifileM"]: k_marker_counts on the
+    individual-major image) and on marker_stats (default MarkerStats(geno, bed)).  The text files no longer know which genotypes were
+    missing, so without `bed` n1 includes them.  bed = the .bed file (or prefix) the panel was ingested from: the counts are then the
+    file's own (rcpp_api.bed_sample_counts), and the dict also holds n_missing and call_rate."""
+    n, L = int(geno["dim_of_ascii_M"][0]), int(geno["dim_of_ascii_M"][1])
+    if marker_stats is None:
+        marker_stats = MarkerStats(geno, bed=bed, availmemGb=availmemGb, device=device)
+    if bed is not None:
+        c = rcpp_api.bed_sample_counts(bed_fileset(bed)[0], (n, L), availmemGb, device=device)
+        return sample_stats_from_counts(c[:, 0], c[:, 1], c[:, 2], c[:, 3], marker_stats=marker_stats)
+    c = rcpp_api.sample_counts(geno["asciifileM"], (n, L), availmemGb, device=device)
+    out = sample_stats_from_counts(c[:, 0], c[:, 1], c[:, 2], marker_stats=marker_stats)
+    del out["n_missing"], out["call_rate"]
+    return out
+
+
+def sample_keep_mask(stats, min_call_rate=None, het_sd=None):
+    """Which individuals a filter keeps (boolean, length n) on the output of SampleStats: keep call_rate >= `min_call_rate` (needs
+    SampleStats(bed=)); het_sd drops the individuals whose het_rate lies more than that many standard deviations (n - 1 in the
+    denominator) from the mean over the individuals, and those without a called genotype.  sample_drop_index turns the mask into
+    what ReshapeM / am.reshape_geno take."""
+    n = len(stats["n0"])
+    keep = np.ones(n, dtype=bool)
+    if min_call_rate is not None:
+        if "call_rate" not in stats:
+            raise ValueError("sample_keep_mask: min_call_rate needs call rates (SampleStats(..., bed=))")
+        keep &= np.asarray(stats["call_rate"], dtype=np.float64) >= float(min_call_rate)
+    if het_sd is not None:
+        h = np.asarray(stats["het_rate"], dtype=np.float64)
+        ok = ~np.isnan(h)
+        keep &= ok
+        if ok.sum() > 1:
+            mean, sd = h[ok].mean(), h[ok].std(ddof=1)
+            keep &= ~(np.abs(np.where(ok, h, mean) - mean) > float(het_sd) * sd)
+    return keep
+
+
+def sample_drop_index(keep):
+    """The individuals a keep mask drops, 1-based and increasing: the indxNA of ReshapeM and am.reshape_geno."""
+    return np.flatnonzero(~np.asarray(keep, dtype=bool)).astype(np.int64) + 1
+
+
+def king_from_counts(ibs0, hethet):
+    """KING-robust kinship (Manichaikul et al. 2010) from rcpp_api.sample_ibs' integer matrices -> fp64 (n, n), pure numpy:
+    phi_ij = (double)(hethet_ij - 2 ibs0_ij) / (double)(h_i + h_j), h = diag(hethet) = the individuals' heterozygous genotypes;
+    NaN where h_i + h_j = 0.  The diagonal and every duplicate pair are 0.5 exactly."""
+    a, hh = np.asarray(ibs0, dtype=np.int64), np.asarray(hethet, dtype=np.int64)
+    h = np.diagonal(hh)
+    num = (hh - 2 * a).astype(np.float64)
+    den = (h[:, None] + h[None, :]).astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(den != 0.0, num / np.where(den != 0.0, den, 1.0), np.nan)
+
+
+KING_DEGREES = (("duplicate", 0.354), ("first", 0.177), ("second", 0.0884), ("third", 0.0442))
+
+
+def king_degree(phi):
+    """"duplicate" for phi > 0.354, "first" for phi > 0.177, "second" for phi > 0.0884, "third" for phi > 0.0442, else "unrelated"
+    (NaN included) -> list of str."""
+    out = []
+    for v in np.atleast_1d(np.asarray(phi, dtype=np.float64)).ravel().tolist():
+        out.append(next((name for name, cut in KING_DEGREES if v > cut), "unrelated"))
+    return out
+
+
+def Relatedness(geno, threshold=0.0884, availmemGb=8, device=0):
+    """Duplicated and closely related individuals of a panel -> {"kinship": fp64 (n, n) KING-robust phi (king_from_counts),
+    "pairs": int64 (k, 2), 0-based, i < j, sorted: the pairs with phi > threshold (a NaN pair is never one), "phi": their phi,
+    "degree": king_degree of it, "ibs0", "hethet": the integer matrices}.  The counts come from the device (rcpp_api.sample_ibs: two
+    exact Gram products on the fp4 MFMA over all markers of geno["asciifileM"]); missing genotypes count as heterozygotes, so drop
+    low-call-rate individuals first (SampleStats(bed=), sample_keep_mask).  related_drop chooses whom to drop."""
+    n, L = int(geno["dim_of_ascii_M"][0]), int(geno["dim_of_ascii_M"][1])
+    ibs0, hethet = rcpp_api.sample_ibs(geno["asciifileM"], (n, L), availmemGb, device=device)
+    phi = king_from_counts(ibs0, hethet)
+    with np.errstate(invalid="ignore"):
+        i, j = np.nonzero(np.triu(phi > float(threshold), k=1))
+    pairs = np.stack([i, j], axis=1).astype(np.int64).reshape(-1, 2)
+    return {"kinship": phi, "pairs": pairs, "phi": phi[i, j], "degree": king_degree(phi[i, j]), "ibs0": ibs0, "hethet": hethet}
+
+
+def related_drop(pairs, n, priority=None):
+    """Whom to drop so that no pair of `pairs` (int (k, 2), 0-based, as Relatedness returns them) remains -> the dropped individuals,
+    1-BASED and increasing: the indxNA of ReshapeM / am.reshape_geno (by file or VIEW).  Greedy: drop the individual in the most
+    remaining pairs, until none remains; ties go to the lower `priority` (length n, e.g. call rates; NaN lowest) when one is given,
+    then to the higher index.  Pure numpy."""
+    pr = np.atleast_2d(np.asarray(pairs, dtype=np.int64)).reshape(-1, 2)
+    n = int(n)
+    if pr.size and (pr.min() < 0 or pr.max() >= n or np.any(pr[:, 0] == pr[:, 1])):
+        raise ValueError("related_drop: pairs must name two different individuals in [0, n)")
+    prio = None
+    if priority is not None:
+        prio = np.asarray(priority, dtype=np.float64).ravel()
+        if prio.size != n:
+            raise ValueError("related_drop: priority holds %d individuals, n = %d" % (prio.size, n))
+        prio = np.where(np.isnan(prio), -np.inf, prio)
+    adj = [set() for _ in range(n)]
+    for i, j in pr.tolist():
+        adj[i].add(j)
+        adj[j].add(i)
+    deg = np.array([len(a) for a in adj], dtype=np.int64)
+    dropped = []
+    while deg.max(initial=0) > 0:
+        cand = np.flatnonzero(deg == deg.max())
+        if prio is not None:
+            cand = cand[prio[cand] == prio[cand].min()]
+        d = int(cand.max())
+        for j in adj[d]:
+            adj[j].discard(d)
+            deg[j] -= 1
+        adj[d].clear()
+        deg[d] = 0
+        dropped.append(d)
+    return np.sort(np.asarray(dropped, dtype=np.int64)) + 1
 
 
 def _ld_sv(stats, n):

@@ -625,6 +625,54 @@ def ld_dots(f_name_ascii_Mt, dims, loci, max_memory_in_Gbytes=8.0, device=0):
     return out
 
 
+# ---- sample QC (include/eagle_hip.h section 1b'''): integer counts and exact-test p-values; kinship and the filters are r_api's ----
+_c_i32p = C.POINTER(C.c_int32)
+
+
+def sample_counts(f_name_ascii_M, dims, max_memory_in_Gbytes=8.0, device=0):
+    """eagle_sample_counts -> int32 (n, 3): the numbers of '0', '1', '2' characters of every line of M.ascii (dims = (n, L) of M), the
+    genotype counts of every individual.  A view alias gives the counts of its kept individuals."""
+    L = _lib.load()
+    out = np.zeros((int(dims[0]), 3), dtype=np.int32)
+    _args_first(L.eagle_sample_counts, device, (os.fsencode(f_name_ascii_M), _dims(dims), float(max_memory_in_Gbytes), out.ctypes.data_as(_c_i32p)))
+    return out
+
+
+def bed_sample_counts(bed_path, dims, max_memory_in_Gbytes=8.0, device=0):
+    """eagle_bed_sample_counts -> int32 (n, 4): homozygous A1, heterozygous, homozygous A2, missing of every individual of a SNP-major
+    PLINK .bed file of dims = (n individuals, L markers)."""
+    L = _lib.load()
+    out = np.zeros((int(dims[0]), 4), dtype=np.int32)
+    _args_first(L.eagle_bed_sample_counts, device, (os.fsencode(bed_path), _dims(dims), float(max_memory_in_Gbytes), out.ctypes.data_as(_c_i32p)))
+    return out
+
+
+def sample_ibs(f_name_ascii_M, dims, max_memory_in_Gbytes=8.0, device=0):
+    """eagle_sample_ibs -> (ibs0, hethet), int32 (n, n) each: for every pair of individuals the markers where they are opposite
+    homozygotes and the markers where both are heterozygous (diagonal: 0 and the individual's heterozygous genotypes)."""
+    L = _lib.load()
+    n = int(dims[0])
+    ibs0, hethet = np.zeros((n, n), dtype=np.int32), np.zeros((n, n), dtype=np.int32)
+    _args_first(L.eagle_sample_ibs, device, (os.fsencode(f_name_ascii_M), _dims(dims), float(max_memory_in_Gbytes), ibs0.ctypes.data_as(_c_i32p),
+                                             hethet.ctypes.data_as(_c_i32p)))
+    return ibs0, hethet
+
+
+def hwe_exact(counts, device=0):
+    """eagle_hwe_exact -> fp64 (L): the Hardy-Weinberg exact test of counts = int (L, 3) or (L, 4) rows (n_AA, n_AB, n_BB[, unused]):
+    what marker_counts and bed_marker_counts return."""
+    L = _lib.load()
+    c = np.asarray(counts)
+    if c.ndim != 2 or c.shape[1] not in (3, 4):
+        raise ValueError("hwe_exact: counts must be (L, 3) or (L, 4)")
+    c32 = np.ascontiguousarray(c, dtype=np.int32)
+    if not np.array_equal(c32, c):
+        raise ValueError("hwe_exact: counts must hold whole numbers that fit int32")
+    out = np.zeros(c32.shape[0], dtype=np.float64)
+    _args_first(L.eagle_hwe_exact, device, (c32.ctypes.data_as(_c_i32p), c32.shape[0], c32.shape[1], _dp(out)))
+    return out
+
+
 # ---- SURVEY 8 f-4: the dense model algebra on the device, through the C ABI (opt-in; include/eagle_hip.h section 1c) ----
 def _square_any_order(A):
     """(buffer, transposed): a float64 n x n array usable as a column-major matrix without a copy when it is contiguous in

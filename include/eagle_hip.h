@@ -317,6 +317,61 @@ int eagle_ld_dots(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long dims[2
                   int32_t* dots_out);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1b'''. Sample QC (no counterpart in the reference): per-individual genotype counts, the pairwise identity-by-state counts that
+ *     KING-robust kinship is made of, and the Hardy-Weinberg exact test per marker.  Genotypes are g in {-1, 0, +1} = AA, AB, BB as
+ *     everywhere in this library; missing genotypes of the source are heterozygotes after ingestion.  L = the number of markers.  With
+ *         D_ij = sum g_i g_j,   Q_ij = sum g_i^2 g_j^2,   q_i = Q_ii (homozygous genotypes of i),   h_i = L - q_i (heterozygous),
+ *     all exact integers from two Gram products on the block-scaled fp4 MFMA (D = M M^T is eagle_calculateMMt's product; the operand
+ *     of Q is the fp4 image of M with every code's sign bit cleared, byte & 0x77, written to a buffer of its own: the image cached
+ *     with a resident file is never modified):
+ *         ibs0_ij   = (Q_ij - D_ij) / 2          markers where i and j are opposite homozygotes (the difference is even)
+ *         hethet_ij = L - q_i - q_j + Q_ij       markers where both are heterozygous
+ *     and on the diagonal ibs0_ii = 0, hethet_ii = h_i.  KING-robust kinship is the caller's arithmetic (r_api.king_from_counts), in
+ *     fp64 in exactly this order:  phi_ij = (double)(hethet_ij - 2 ibs0_ij) / (double)(h_i + h_j),  NaN when h_i + h_j = 0; a
+ *     duplicate pair has phi = 0.5 exactly.
+ *
+ *     Hardy-Weinberg exact test (Wigginton, Cutler and Abecasis 2005) of the counts (n_AA, n_AB, n_BB):  N = their sum;  N = 0 gives
+ *     p = 1.  hr = min(n_AA, n_BB), r = 2 hr + n_AB (copies of the rare allele).  The heterozygote counts h are those of the parity
+ *     of r in [r mod 2, r];  mid = the one nearest to r (2N - r) / (2N), the larger of two equally near ones: in integers
+ *     mid = floor(r (2N - r) / (2N)), plus 1 if its parity is not r's.  With h go the homozygote counts (r - h) / 2 (rare) and
+ *     N - h - (r - h) / 2 (common).  Unnormalised probabilities start from P(mid) = 1 and follow
+ *         P(h - 2) = P(h) * h (h - 1) / (4 (hr + 1) (hc + 1)),        P(h + 2) = P(h) * 4 hr hc / ((h + 2) (h + 1)),
+ *     hr, hc the homozygote counts that go with h.  Each step is  P' = fl(fl(P * (double)num) / (double)den):  num and den are exact
+ *     int64 products converted to fp64 once, the product and the quotient are rounded separately.  The terms are visited in ONE
+ *     order: mid, then the lower leg mid - 2, mid - 4, ..., then the upper leg mid + 2, mid + 4, ..., r.  First walk:
+ *     total = 1.0, then total = fl(total + P) for every further term in that order; P(n_AB) is picked up on the way.  Second walk, the
+ *     same steps in the same order:  tail = (1.0 <= P(n_AB) ? 1.0 : 0.0), then tail = fl(tail + P) for every term with P <= P(n_AB).
+ *     p = min(1, fl(tail / total)).  Nothing is contracted into an FMA and no array is kept per marker, so a scalar restatement in
+ *     any IEEE-754 language gives the same bits.
+ *
+ *     Files are read as eagle_marker_counts reads them (resident image, else sidecar, else text; a VIEW alias works).  Single device:
+ *     a multi-device context works on its first device.  Argument errors (EAGLE_ERR_ARG: a NULL pointer, dims <= 0, and those named
+ *     below) are decided before the context is used; with ctx == NULL their text is in eagle_open_error().
+ * ------------------------------------------------------------------------------------------- */
+
+/* counts_out[3 i .. 3 i + 2] = the numbers of '0', '1' and '2' characters of line i of M.ascii (dims = (n, L) of M: n lines of L
+ * characters): the genotype counts (n0, n1, n2) of individual i, by k_marker_counts on the individual-major image. */
+int eagle_sample_counts(eagle_ctx* ctx, const char* f_name_ascii_M, const long dims[2], double max_memory_in_Gbytes, int32_t* counts_out);
+
+/* The same from a SNP-major PLINK .bed file (the format and the checks of eagle_create_ascii_from_bed; dims = (n, L)), where missing
+ * genotypes are still known: counts_out[4 i .. 4 i + 3] = homozygous A1 (code 00), heterozygous (10), homozygous A2 (11), missing
+ * (01) of INDIVIDUAL i over all markers (k_bed_sample_counts: the column sums of what eagle_bed_marker_counts sums along the rows).
+ * The rows are staged as eagle_bed_marker_counts stages them; the windows' counts are added in HBM. */
+int eagle_bed_sample_counts(eagle_ctx* ctx, const char* bed_path, const long dims[2], double max_memory_in_Gbytes, int32_t* counts_out);
+
+/* ibs0_out, hethet_out: n x n int32 each, row-major (symmetric), as defined above, over all L markers of M.ascii (dims = (n, L)).
+ * A file that is not resident, does not fit, or exceeds EAGLE_HIP_MAX_RESIDENT_GB is processed in marker windows and both integer
+ * accumulators are summed across the windows: the same integers either way.  A later eagle_calculateMMt on the same resident file
+ * returns the bits it returned before.  EAGLE_ERR_ARG: L >= 2^31. */
+int eagle_sample_ibs(eagle_ctx* ctx, const char* f_name_ascii_M, const long dims[2], double max_memory_in_Gbytes, int32_t* ibs0_out,
+                     int32_t* hethet_out);
+
+/* p_out[i] = the exact test above on counts[i * stride .. i * stride + 2] = (n_AA, n_AB, n_BB), i < L; stride = 3 (the rows of
+ * eagle_marker_counts) or 4 (those of eagle_bed_marker_counts, whose fourth column is not used).  One marker per device thread
+ * (k_hwe_exact).  EAGLE_ERR_ARG: L <= 0, another stride, a negative count, a marker with more than 2^30 genotypes. */
+int eagle_hwe_exact(eagle_ctx* ctx, const int32_t* counts, long L, int stride, double* p_out);
+
+/* ---------------------------------------------------------------------------------------------
  * 1c. Dense n x n model algebra on the device (OPT-IN: north_star keeps calculateH / calculateP / emma.* on
  *     host LAPACK, and nothing above calls these).  Once the scan takes tens of milliseconds the ~10-15 O(n^3) base-R calls
  *     of a find_qtl iteration are the whole run time (the author's note MyPackage/MyREADME:1 names eigen(); his MAGMA
