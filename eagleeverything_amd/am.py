@@ -129,6 +129,21 @@ def reshape_geno(geno, indxNA, view=False, device=0):
     return {"asciifileM": geno["asciifileM"] + "tmp", "asciifileMt": geno["asciifileMt"] + "tmp", "dim_of_ascii_M": newdims}
 
 
+def add_pcs(X, pca, k=None):
+    """X with the first k (default all) columns of r_api.PCA()'s "pcs" appended: the design matrix of AM(trait, X, geno) with
+    principal components as fixed effects (the reference's documented fformula = "pc1 + pc2").  X and pcs must hold the same
+    individuals, in the order of the panel."""
+    X = np.asarray(X, dtype=np.float64)
+    X = X.reshape(-1, 1) if X.ndim == 1 else X
+    pcs = np.asarray(pca["pcs"], dtype=np.float64)
+    k = pcs.shape[1] if k is None else int(k)
+    if k < 0 or k > pcs.shape[1]:
+        raise ValueError("add_pcs: k = %d of %d components" % (k, pcs.shape[1]))
+    if X.shape[0] != pcs.shape[0]:
+        raise ValueError("add_pcs: X holds %d individuals, the components %d" % (X.shape[0], pcs.shape[0]))
+    return np.concatenate([X, pcs[:, :k]], axis=1)
+
+
 def _reshape(geno, indxNA, backend=None, device=0):
     """geno without the individuals indxNA: backend.reshape, reshape_geno writing the files for a backend without one, or for a
     caller that has no backend a view on `device`."""

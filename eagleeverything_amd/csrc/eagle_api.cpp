@@ -823,6 +823,96 @@ int eagle_ibs_counts(eagle_ctx* ctx, const char* path, long n, long L, double me
     return download_big(ctx, hethet_out, (const char*)out.p + outb, outb);
 }
 
+// GRM (eagle_weighted_gram, eagle_ingest.cpp): Q = sum_m q_m g_m g_m^T over all L markers of M.ascii by eagle_ibs_counts' rules -- the
+// resident image when the file fits, marker windows through the ChunkRing when it does not.  q is cut into three base-128 digit planes
+// on the host; per window of at most about 1 GiB and per plane that is not zero there, k_scale_cols_i8 writes digit x genotype into the
+// ctx-owned operand buffer and k_gram_i8ab multiplies the window with it into that plane's int32 accumulator; k_wgram_finish sums the
+// planes.  The genotype image is only ever read.
+struct WgramPlanes {
+    std::vector<uint8_t> h[3];     // digit planes, zero beyond L
+    DevBuf d[3], c32;              // their device copies; the accumulators of the live planes, side by side
+    int32_t* acc[3] = {nullptr, nullptr, nullptr};
+    bool live(int p, long c0, long c1) const {
+        const uint8_t* b = h[p].data();
+        for (long c = c0; c < c1; c++) if (b[c]) return true;
+        return false;
+    }
+};
+// the columns [c0, c0 + cols) of the markers (cols % 256 == 0) lie at A (np rows, leading dimension ldA): every live plane's product
+static int wgram_window(eagle_ctx* ctx, WgramPlanes& P, const int8_t* A, long ldA, long n, long np, long c0, long cols, long L) {
+    const long Lq = std::min(cols, std::max(256L, (long)(((size_t)1 << 30) / (size_t)np) / 256 * 256));   // markers per operand window
+    const bool wide = (double)ldA * 256.0 >= 2147483648.0;   // a line too long for the tile engine's 32-bit offsets: copy the window out first
+    int8_t* buf = (int8_t*)eagle_ctx_f4_buffer(ctx, (size_t)np * (size_t)Lq * (wide ? 2 : 1));
+    if (!buf) return EAGLE_ERR_HIP;
+    for (long w0 = 0; w0 < cols; w0 += Lq) {
+        const long nc = std::min(Lq, cols - w0), m0 = c0 + w0, m1 = std::min(m0 + nc, L);
+        const int8_t* Aw = A + w0;
+        long ldw = ldA;
+        bool copied = false;
+        for (int p = 0; p < 3; p++) {
+            if (!P.acc[p] || m0 >= m1 || !P.live(p, m0, m1)) continue;
+            if (wide && !copied) {
+                int8_t* a2 = buf + (size_t)np * (size_t)Lq;
+                HIPCHK(ctx, hipMemcpy2DAsync(a2, (size_t)nc, A + w0, (size_t)ldA, (size_t)nc, (size_t)np, hipMemcpyDeviceToDevice, ctx->stream));
+                Aw = a2; ldw = nc; copied = true;
+            }
+            int rc = eagle_dev_scale_cols_i8(ctx, Aw, ldw, n, np, nc, P.d[p].as<uint8_t>() + m0, buf, nc, ctx->stream);
+            if (!rc) rc = eagle_dev_gram_i8ab(ctx, Aw, ldw, buf, nc, np, nc, P.acc[p], ctx->stream);
+            if (rc) return rc;
+        }
+    }
+    return EAGLE_OK;
+}
+int eagle_wgram(eagle_ctx* ctx, const char* path, long n, long L, const uint32_t* q, double mem_gb, int threads, int64_t* Q_out) {
+    const long np = eagle_pad(n), Lp = eagle_pad(L);
+    const size_t accb = sizeof(int32_t) * (size_t)np * np, outb = sizeof(int64_t) * (size_t)n * n;
+    GenoEntry* g = nullptr;
+    int rc = get_resident(ctx, path, 0, n, 0, L, mem_gb, threads, &g, 3 * accb + outb + ((size_t)1 << 30));
+    if (rc < 0) return rc;
+    const bool resident = rc == EAGLE_OK;
+    const long Lw = resident ? Lp : stream_chunk_rows(np, Lp);   // window width in markers; rows of the window = np
+    const long Ld = (Lp + Lw - 1) / Lw * Lw;                     // the digit planes cover every window in full
+    WgramPlanes P;
+    int nlive = 0;
+    for (int p = 0; p < 3; p++) {
+        P.h[p].assign((size_t)Ld, 0);
+        for (long m = 0; m < L; m++) P.h[p][(size_t)m] = (uint8_t)((q[m] >> (7 * p)) & 127u);
+        if (P.live(p, 0, L)) nlive++; else P.h[p].clear();
+    }
+    HIPCHK(ctx, P.c32.alloc(accb * (size_t)std::max(nlive, 1)));
+    if (nlive) HIPCHK(ctx, hipMemsetAsync(P.c32.p, 0, accb * (size_t)nlive, ctx->stream));
+    for (int p = 0, k = 0; p < 3; p++) {
+        if (P.h[p].empty()) continue;
+        P.acc[p] = (int32_t*)((char*)P.c32.p + accb * (size_t)k++);
+        HIPCHK(ctx, P.d[p].alloc((size_t)Ld));
+        HIPCHK(ctx, hipMemcpyAsync(P.d[p].p, P.h[p].data(), (size_t)Ld, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (nlive && resident) {   // (q = 0 everywhere: no product)
+        if ((rc = wgram_window(ctx, P, g->dev, g->ld, n, np, 0, Lp, L))) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    } else if (nlive) {
+        DevBuf win;
+        HIPCHK(ctx, win.alloc((size_t)2 * np * Lw));
+        ChunkRing ring;
+        if ((rc = ring.init(ctx))) return rc;
+        ring.buf[0] = win.as<int8_t>();
+        ring.buf[1] = win.as<int8_t>() + (size_t)np * Lw;
+        for (long w0 = 0; w0 < L; w0 += Lw) {
+            const long nc = std::min(Lw, L - w0);
+            int8_t* wtile = nullptr;
+            rc = ring.load(ctx, path, 0, n, w0, nc, Lw, (size_t)np * Lw, mem_gb, threads, &wtile);
+            if (!rc) rc = wgram_window(ctx, P, wtile, Lw, n, np, w0, Lw, L);
+            if (!rc) rc = ring.computed(ctx);
+            if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+        }
+        ring.finish(ctx);
+    }
+    DevBuf out;
+    HIPCHK(ctx, out.alloc(outb));
+    rc = eagle_dev_wgram_finish(ctx, P.acc[0], P.acc[1], P.acc[2], n, np, out.as<int64_t>(), ctx->stream);
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    return download_big(ctx, Q_out, out.p, outb);
+}
+
 extern "C" int eagle_calculateMMt(eagle_ctx* ctx, const char* f_name_ascii, double max_memory_in_Gbytes, int num_cores,
                                   const double* selected_loci, long n_selected, const long dims[2], int quiet,
                                   double* MMt_out) {

@@ -208,6 +208,19 @@ extern "C" int eagle_dev_ibs_finish(eagle_ctx* ctx, const int32_t* D32, const in
 extern "C" int eagle_dev_hwe_exact(eagle_ctx* ctx, const int32_t* counts, long L, int stride, double* p, void* stream);
 extern "C" int eagle_dev_f4_abs(eagle_ctx* ctx, const void* src4, long ld4_src, long rows, long row_bytes, void* dst4, long ld4_dst, void* stream);
 int eagle_ibs_counts(eagle_ctx* ctx, const char* path, long n, long L, double mem_gb, int threads, int32_t* ibs0_out, int32_t* hethet_out);
+// GRM (eagle_grm.hip; include/eagle_hip.h section 1b'''').  B[r][c] = digit[c] * A[r][c] for the rows [0, rows) and 16-byte column groups of
+// an individual-major int8 window (A in {-1, 0, +1}, digit in [0, 127]; rows [n, rows) of B are written as zeros); the NT product
+// C32[i][j] += sum_k A[i][k] B[j][k] on the tile engine of k_syrk_i8 (upper 256-tiles live); Q = C0 + 128 C1 + 128^2 C2 (a NULL plane
+// is zero) as the full symmetric n x n int64 matrix.  eagle_api.cpp: the windows of M.ascii, resident or streamed (eagle_weighted_gram).
+extern "C" int eagle_dev_scale_cols_i8(eagle_ctx* ctx, const int8_t* A, long ldA, long n, long rows, long cols, const uint8_t* digit, int8_t* B,
+                                       long ldB, void* stream);
+extern "C" int eagle_dev_gram_i8ab(eagle_ctx* ctx, const int8_t* A, long ldA, const int8_t* B, long ldB, long n_pad, long K_pad, int32_t* C32,
+                                   void* stream);
+extern "C" int eagle_dev_wgram_finish(eagle_ctx* ctx, const int32_t* C0, const int32_t* C1, const int32_t* C2, long n, long n_pad, int64_t* Q,
+                                      void* stream);
+int eagle_wgram(eagle_ctx* ctx, const char* path, long n, long L, const uint32_t* q, double mem_gb, int threads, int64_t* Q_out);
+// eagle_i8mfma.hip: the upper-triangular 256-tile pairs (ti << 16 | tj) of an nt x nt tile grid in super-tile order, cached per device
+int syrk_pair_table(eagle_ctx* ctx, int nt, const int** out, hipStream_t stream);
 inline bool eagle_sidecar_enabled() { const char* e = getenv("EAGLE_HIP_SIDECAR"); return !(e && e[0] == '0'); }
 // Whole-file resident copy (loads it if needed); EAGLE_OK, 2 (too large for HBM: stream it) or an error.
 int eagle_get_resident(eagle_ctx* ctx, const char* path, long rows, long cols, double max_mem_gb, int threads, const GenoEntry** out);

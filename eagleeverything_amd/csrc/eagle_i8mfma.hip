@@ -30,53 +30,7 @@ __global__ __launch_bounds__(512, 2) void k_syrk_i8(const int8_t* __restrict__ M
                                                     int npairs, int nblocks, long nstages, long stages_per_split,
                                                     int32_t* __restrict__ C, long ldc) {
     __shared__ __attribute__((aligned(1024))) int8_t lds[2][2][TILE_BYTES];
-    // XCD-aware order (speed only): workgroup b runs on XCD b%8 (observed dealing); give each XCD a contiguous range
-    // of the logical work list, which is ordered K-split major and, inside a split, by G x G super-tiles of the
-    // upper triangle, so the ~32 workgroups resident on one XCD stream the same few row/column panels of M8.
-    const int cpx = (gridDim.x + 7) / 8;
-    const int lid = (blockIdx.x & 7) * cpx + (blockIdx.x >> 3);
-    if (lid >= nblocks) return;
-    const int split = lid / npairs;
-    const int pr = pairs[lid - split * npairs];
-    const int ti = pr >> 16, tj = pr & 0xffff;
-    const long s0 = (long)split * stages_per_split;
-    long s1 = s0 + stages_per_split;
-    if (s1 > nstages) s1 = nstages;
-    if (s0 >= s1) return;
-    const int t = threadIdx.x, lane = t & 63;
-    const int w = __builtin_amdgcn_readfirstlane(t >> 6);
-    const int wr = w >> 2, wc = w & 3;
-    const int ldi = (int)ld;
-    const T8Lane ln = t8_lane(lane, ldi);
-    const __amdgpu_buffer_rsrc_t rsA = t8_rsrc(M8 + (long)ti * T8 * ld, ldi);
-    const __amdgpu_buffer_rsrc_t rsB = t8_rsrc(M8 + (long)tj * T8 * ld, ldi);
-    i32x16 acc[4][2];
-    t8_zero(acc);
-    t8_stage(rsA, ln, ldi, (int)(s0 * BK8), lds[0][0], w);
-    t8_stage(rsB, ln, ldi, (int)(s0 * BK8), lds[0][1], w);
-    __syncthreads();
-    int cur = 0;
-    const T8Read rd = t8_read_init(wr, wc, lane);
-    for (long s = s0; s < s1; s++) {
-        const int kn = (int)((s + 1) * BK8);
-        t8_stage_compute<TUNE>(acc, lds[cur][0], lds[cur][1], rd, s + 1 < s1, rsA, ln, ldi, kn, lds[cur ^ 1][0], rsB, ln, ldi, kn,
-                               lds[cur ^ 1][1], w);
-        __syncthreads();
-        cur ^= 1;
-    }
-    // C/D map of the 32x32 MFMA: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
-    const int col = lane & 31, rq = 4 * (lane >> 5);
-#pragma unroll
-    for (int m = 0; m < 4; m++)
-#pragma unroll
-        for (int n = 0; n < 2; n++)
-#pragma unroll
-            for (int q = 0; q < 16; q++) {
-                long i = (long)ti * T8 + wr * 128 + m * 32 + (q & 3) + 8 * (q >> 2) + rq;
-                long j = (long)tj * T8 + wc * 64 + n * 32 + col;
-                int v = acc[m][n][q];
-                if (v) atomicAdd(&C[i * ldc + j], v);
-            }
+    t8_gram_tiles<TUNE>(lds, M8, ld, M8, ld, pairs, npairs, nblocks, nstages, stages_per_split, C, ldc);
 }
 
 // Upper-triangular tile pairs (ti<<16 | tj) in super-tile order, cached on the device per tile count.
@@ -85,7 +39,7 @@ __global__ __launch_bounds__(512, 2) void k_syrk_i8(const int8_t* __restrict__ M
 #include <vector>
 static std::map<std::pair<int, int>, int*> g_pair_tables;  // (device, nt) -> device table
 static std::mutex g_pair_mutex;                             // one worker thread per device may come through here
-static int syrk_pair_table(eagle_ctx* ctx, int nt, const int** out, hipStream_t stream) {
+int syrk_pair_table(eagle_ctx* ctx, int nt, const int** out, hipStream_t stream) {
     std::lock_guard<std::mutex> lock(g_pair_mutex);
     int dev = 0;
     (void)hipGetDevice(&dev);

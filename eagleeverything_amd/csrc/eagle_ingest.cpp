@@ -1242,3 +1242,21 @@ extern "C" int eagle_hwe_exact(eagle_ctx* ctx, const int32_t* counts, long L, in
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return EAGLE_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// GRM: the per-marker weighted Gram product (no counterpart in the reference; kernels in eagle_grm.hip, the windows in eagle_api.cpp)
+// ---------------------------------------------------------------------------------------------------------------
+extern "C" int eagle_weighted_gram(eagle_ctx* ctx, const char* f_name_ascii_M, const long dims[2], const uint32_t* q,
+                                   double max_memory_in_Gbytes, int64_t* Q_out) {
+    if (!f_name_ascii_M || !dims || !q || !Q_out) return qc_fail(ctx, EAGLE_ERR_ARG, "weighted_gram: NULL argument");
+    const long n = dims[0], L = dims[1];
+    if (n <= 0 || L <= 0) return qc_fail(ctx, EAGLE_ERR_ARG, "weighted_gram: dims must be positive");
+    if (L > 0x7fffffffL) return qc_fail(ctx, EAGLE_ERR_ARG, "weighted_gram: 2^31 markers or more");
+    if (L > EAGLE_WGRAM_MAX_MARKERS)
+        return qc_fail(ctx, EAGLE_ERR_ARG, "weighted_gram: more than 16,909,320 markers (the int32 accumulator of a digit plane holds 127 L)");
+    for (long m = 0; m < L; m++)
+        if (q[m] >= (1u << 21)) return qc_fail(ctx, EAGLE_ERR_ARG, "weighted_gram: a weight is 2^21 or more");
+    if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "weighted_gram: no context");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return eagle_wgram(ctx, f_name_ascii_M, n, L, q, max_memory_in_Gbytes, host_threads(), Q_out);
+}

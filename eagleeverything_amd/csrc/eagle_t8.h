@@ -115,6 +115,62 @@ __device__ __forceinline__ void t8_zero(i32x16 (&acc)[4][2]) {
 #pragma unroll
             for (int q = 0; q < 16; q++) acc[m][n][q] = 0;
 }
+// The body of the Gram kernels on this engine (k_syrk_i8: A = B = M8; k_gram_i8ab of eagle_grm.hip: A = a genotype window, B = the
+// same window with every column scaled):  C[i][j] += sum_k A[i][k] B[j][k]  over the upper-triangular 256-tile pairs of `pairs`
+// (grid.x = pairs x K splits), a tile on the diagonal in full.  Integer atomics: exact, any order.  `lds` is the kernel's 128 KiB.
+template <int TUNE>
+__device__ __forceinline__ void t8_gram_tiles(int8_t (*lds)[2][TILE_BYTES], const int8_t* __restrict__ A, long ldA_, const int8_t* __restrict__ B,
+                                              long ldB_, const int* __restrict__ pairs, int npairs, int nblocks, long nstages,
+                                              long stages_per_split, int32_t* __restrict__ C, long ldc) {
+    // XCD-aware order (speed only): workgroup b runs on XCD b%8 (observed dealing); give each XCD a contiguous range
+    // of the logical work list, which is ordered K-split major and, inside a split, by G x G super-tiles of the
+    // upper triangle, so the ~32 workgroups resident on one XCD stream the same few row/column panels of the operands.
+    const int cpx = (gridDim.x + 7) / 8;
+    const int lid = (blockIdx.x & 7) * cpx + (blockIdx.x >> 3);
+    if (lid >= nblocks) return;
+    const int split = lid / npairs;
+    const int pr = pairs[lid - split * npairs];
+    const int ti = pr >> 16, tj = pr & 0xffff;
+    const long s0 = (long)split * stages_per_split;
+    long s1 = s0 + stages_per_split;
+    if (s1 > nstages) s1 = nstages;
+    if (s0 >= s1) return;
+    const int t = threadIdx.x, lane = t & 63;
+    const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int wr = w >> 2, wc = w & 3;
+    const int ldA = (int)ldA_, ldB = (int)ldB_;
+    const T8Lane lnA = t8_lane(lane, ldA), lnB = t8_lane(lane, ldB);
+    const __amdgpu_buffer_rsrc_t rsA = t8_rsrc(A + (long)ti * T8 * ldA_, ldA);
+    const __amdgpu_buffer_rsrc_t rsB = t8_rsrc(B + (long)tj * T8 * ldB_, ldB);
+    i32x16 acc[4][2];
+    t8_zero(acc);
+    t8_stage(rsA, lnA, ldA, (int)(s0 * BK8), lds[0][0], w);
+    t8_stage(rsB, lnB, ldB, (int)(s0 * BK8), lds[0][1], w);
+    __syncthreads();
+    int cur = 0;
+    const T8Read rd = t8_read_init(wr, wc, lane);
+    for (long s = s0; s < s1; s++) {
+        const int kn = (int)((s + 1) * BK8);
+        t8_stage_compute<TUNE>(acc, lds[cur][0], lds[cur][1], rd, s + 1 < s1, rsA, lnA, ldA, kn, lds[cur ^ 1][0], rsB, lnB, ldB, kn,
+                               lds[cur ^ 1][1], w);
+        __syncthreads();
+        cur ^= 1;
+    }
+    // C/D map of the 32x32 MFMA: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
+    const int col = lane & 31, rq = 4 * (lane >> 5);
+#pragma unroll
+    for (int m = 0; m < 4; m++)
+#pragma unroll
+        for (int n = 0; n < 2; n++)
+#pragma unroll
+            for (int q = 0; q < 16; q++) {
+                long i = (long)ti * T8 + wr * 128 + m * 32 + (q & 3) + 8 * (q >> 2) + rq;
+                long j = (long)tj * T8 + wc * 64 + n * 32 + col;
+                int v = acc[m][n][q];
+                if (v) atomicAdd(&C[i * ldc + j], v);
+            }
+}
+
 // Scale exponent of the digits: max|Wu_jk| (j != k) < 2^e, lowered by one when the mantissa leaves room (round 3) -- a balanced S-digit
 // number reaches 127 (256^S - 1)/255 = 0.498 * 256^S, and |Q| <= max|Wu| 2^(8S-e-2) + 1 stays below 0.49 * 256^S + 1 for a mantissa up
 // to 0.98: one more bit of resolution for the same digits on 96 % of all scales (rounds 1-2 always kept the leading digit inside

@@ -556,6 +556,167 @@ def related_drop(pairs, n, priority=None):
     return np.sort(np.asarray(dropped, dtype=np.int64)) + 1
 
 
+# ---- GRM and PCA (include/eagle_hip.h section 1b''''): the exact weighted Gram product on the device, fp64 arithmetic on the host ----
+GRM_QMAX = 2097151    # 2^21 - 1: the largest weight rcpp_api.weighted_gram takes
+
+
+def grm_weights(n0, n1, n2, method="standardized", maf=0.0, include=None):
+    """The integer marker weights of a relationship matrix from genotype counts -> (q uint32 (L), scale fp64, used bool (L)), in
+    numpy (nothing here touches a device).  Per marker, in int64:  N = n0 + n1 + n2,  c = 2 n2 + n1 (copies of the allele coded 2),
+    den = c (2N - c).  A marker is USED iff den > 0 (it is polymorphic), (double)min(c, 2N - c) >= maf * (double)(2N), and `include`
+    (bool, length L) is None or true for it.  Unused markers get q = 0.
+    "standardized" (EIGENSTRAT / PLINK / GCTA): the weight is w = 1 / (2 p (1 - p)), p = c / (2N), evaluated as
+    w = ((2.0 * (double)N) * (double)N) / (double)den;  scale = 2097151.0 / max(w over the used markers);  q = rint(w * scale).
+    Every operation is one correctly rounded fp64 operation in that order, so a scalar restatement gives the same bits.
+    "vanraden1": q = 1 on the used markers, scale = 1.0 (the weights are exact).
+    q / scale stands for w with an absolute error of at most 0.5 / scale, so the RELATIVE error of a marker's weight is at most
+    w_max / (w_m (2^22 - 2)), about w_max / (w_m 2^22): 2.4e-6 at worst on a panel with allele frequencies in 0.1 .. 0.9, but a marker
+    at p = 0.5 beside one with a single copy of the rare allele among 10,000 individuals loses all but a few bits.  That is why PCA
+    defaults to maf = 0.01.  With no used marker q = 0 and scale = 1.0."""
+    n0, n1, n2 = (np.asarray(v, dtype=np.int64).ravel() for v in (n0, n1, n2))
+    if method not in ("standardized", "vanraden1"):
+        raise ValueError("grm_weights: method must be \"standardized\" or \"vanraden1\"")
+    N = n0 + n1 + n2
+    c = 2 * n2 + n1
+    den = c * (2 * N - c)
+    used = (den > 0) & (np.minimum(c, 2 * N - c).astype(np.float64) >= float(maf) * (2 * N).astype(np.float64))
+    if include is not None:
+        inc = np.asarray(include, dtype=bool).ravel()
+        if inc.size != N.size:
+            raise ValueError("grm_weights: include holds %d markers, the counts %d" % (inc.size, N.size))
+        used &= inc
+    q = np.zeros(N.size, dtype=np.uint32)
+    if not used.any():
+        return q, 1.0, used
+    if method == "vanraden1":
+        q[used] = 1
+        return q, 1.0, used
+    Nf = N[used].astype(np.float64)
+    w = ((2.0 * Nf) * Nf) / den[used].astype(np.float64)
+    scale = float(GRM_QMAX) / float(w.max())
+    q[used] = np.rint(w * scale).astype(np.uint32)
+    return q, scale, used
+
+
+def _grm_reference(reference, n):
+    """The individuals R of a relationship matrix's centring: int64 0-based indices, distinct and increasing; None = everyone."""
+    if reference is None:
+        return np.arange(n, dtype=np.int64)
+    R = np.atleast_1d(np.asarray(reference))
+    if R.dtype == bool:
+        if R.size != n:
+            raise ValueError("reference: a mask of %d individuals, n = %d" % (R.size, n))
+        R = np.flatnonzero(R)
+    R = np.unique(R.astype(np.int64).ravel())
+    if R.size == 0 or R[0] < 0 or R[-1] >= n:
+        raise ValueError("reference: individuals must lie in [0, %d) and one at least is needed" % n)
+    return R
+
+
+def grm_from_gram(Q, q_info, reference=None):
+    """The relationship matrix from the integer Gram product Q = rcpp_api.weighted_gram(..., q) -> fp64 (n, n), host numpy.
+    q_info = {"method", "scale", "used"} of grm_weights, for "vanraden1" also "n0", "n1", "n2", the counts the weights came from (those
+    over R).  R = `reference` (0-based individuals, default all).  With r_i = (1/|R|) sum_{j in R} Q_ij and
+    kappa = (1/|R|^2) sum_{i, j in R} Q_ij,
+        Gc = Q - r 1^T - 1 r^T + kappa        ( = sum_m q_m (g_im - mu_m)(g_jm - mu_m), mu_m the mean of g_.m over R, because
+                                                sum_m q_m mu_m g_im = r_i: centring every marker over R is double-centring Q over R )
+        G = Gc / (scale * L_used)             "standardized":  (1 / L_used) sum_m (x_im - 2 p_m)(x_jm - 2 p_m) / (2 p_m (1 - p_m))
+        G = Gc / sum_used 2 p_m (1 - p_m)     "vanraden1", 2 p (1 - p) = den / (2 N^2) in grm_weights' terms
+    x = g + 1 the allele count, p_m its frequency over R when the counts are R's."""
+    Qf = np.asarray(Q).astype(np.float64)       # |Q| < 2^52: exact
+    n = Qf.shape[0]
+    if Qf.ndim != 2 or Qf.shape[1] != n:
+        raise ValueError("grm_from_gram: Q must be square")
+    R = _grm_reference(reference, n)
+    used = np.asarray(q_info["used"], dtype=bool).ravel()
+    L_used = int(used.sum())
+    if L_used == 0:
+        raise ValueError("grm_from_gram: no marker is used")
+    r = Qf[:, R].sum(axis=1) / float(R.size)
+    kappa = float(r[R].sum()) / float(R.size)
+    Gc = Qf - r[:, None] - r[None, :] + kappa
+    if q_info["method"] == "standardized":
+        return Gc / (float(q_info["scale"]) * float(L_used))
+    if q_info["method"] != "vanraden1":
+        raise ValueError("grm_from_gram: unknown method %r" % (q_info["method"],))
+    n0, n1, n2 = (np.asarray(q_info[k], dtype=np.int64).ravel()[used] for k in ("n0", "n1", "n2"))
+    N = n0 + n1 + n2
+    c = 2 * n2 + n1
+    Nf = N.astype(np.float64)
+    return Gc / float(np.sum((c * (2 * N - c)).astype(np.float64) / ((2.0 * Nf) * Nf)))
+
+
+def GRM(geno, method="standardized", maf=0.0, include=None, reference=None, stats=None, availmemGb=8, device=0):
+    """The genomic relationship matrix of a panel -> {"G": fp64 (n, n) (grm_from_gram), "Q": int64 (n, n), the exact weighted Gram
+    product over ALL n individuals (rcpp_api.weighted_gram: base-128 digit planes of the weights on the int8 MFMA), "q", "scale",
+    "used" (grm_weights), "method", "n0", "n1", "n2" (the counts behind the weights), "reference" (int64, 0-based),
+    "weight_rel_error": the largest relative error |q / scale - w| / w of a used marker's weight (0 for "vanraden1")}.
+    reference = the individuals (0-based indices or a mask) whose allele frequencies centre and scale the markers, default all: the
+    counts then come from them alone (MarkerStats on a view of the panel without the others, nothing written), and everyone else is
+    placed relative to them -- what PCA(reference=) projects.  stats = a MarkerStats dict of exactly those individuals replaces the
+    counting pass.  include = a boolean mask of markers (one chromosome, one MAF bin): the matrix of that subset from the resident
+    image, without writing a filtered panel."""
+    n, L = int(geno["dim_of_ascii_M"][0]), int(geno["dim_of_ascii_M"][1])
+    R = _grm_reference(reference, n)
+    if stats is None:
+        if R.size == n:
+            stats = MarkerStats(geno, availmemGb=availmemGb, device=device)
+        else:
+            from . import am
+            drop = np.setdiff1d(np.arange(n, dtype=np.int64), R) + 1
+            stats = MarkerStats(am.reshape_geno(geno, drop, view=True, device=device), availmemGb=availmemGb, device=device)
+    n0, n1, n2 = (np.asarray(stats[k], dtype=np.int64).ravel() for k in ("n0", "n1", "n2"))
+    if n0.size != L:
+        raise ValueError("GRM: the marker statistics hold %d markers, the panel %d" % (n0.size, L))
+    q, scale, used = grm_weights(n0, n1, n2, method=method, maf=maf, include=include)
+    if not used.any():
+        raise ValueError("GRM: no marker is used (maf=%s%s)" % (maf, "" if include is None else ", include given"))
+    Q = rcpp_api.weighted_gram(geno["asciifileM"], (n, L), q, availmemGb, device=device)
+    out = {"Q": Q, "q": q, "scale": scale, "used": used, "method": method, "n0": n0, "n1": n1, "n2": n2, "reference": R}
+    out["G"] = grm_from_gram(Q, out, reference=R)
+    out["weight_rel_error"] = 0.0
+    if method == "standardized":
+        Nf = (n0 + n1 + n2)[used].astype(np.float64)
+        w = ((2.0 * Nf) * Nf) / ((2 * n2 + n1) * (2 * (n0 + n1 + n2) - (2 * n2 + n1)))[used].astype(np.float64)
+        out["weight_rel_error"] = float(np.max(np.abs(q[used].astype(np.float64) / scale - w) / w))
+    return out
+
+
+def PCA(geno, k=10, method="standardized", maf=0.01, reference=None, grm=None, eig=None, include=None, stats=None, availmemGb=8, device=0):
+    """Principal components of the relationship matrix, the covariates of AM(trait, am.add_pcs(X, pca), geno) ->
+    {"values": the top k eigenvalues of G[R, R], decreasing, "pcs": fp64 (n, k), "explained": values / trace(G[R, R]), "reference":
+    R, "grm": the GRM dict}.  grm = a dict of GRM() (then geno may be None and method / maf / include / stats are not used; its
+    reference is R unless `reference` names the same individuals), else GRM(geno, method, maf, include, reference, stats) is run.
+    One eigh of G[R, R]: eig = a callable A -> (values, vectors in columns), in either order of the values (default
+    host_model.algebra().eigh: host LAPACK unless host_model.set_algebra("device"); rcpp_api.sym_eig runs it on the device).
+    The sign of every vector is fixed so that its component of largest magnitude (the first of equals) is positive.
+    Row i of pcs:  for i in R the entries of the unit-norm eigenvectors U;  for i outside R the projection
+    (1 / lambda_a) sum_{j in R} G_ij U_ja, which for a member of R is its eigenvector entry exactly (G[R, R] U = U diag(lambda)), so
+    a duplicate of a reference individual lands on it.  It is the usual projection and is NOT corrected for shrinkage: with few
+    individuals per marker projected individuals sit nearer the origin than reference ones (Lee et al. 2010).
+    ValueError for k < 1 or k > |R| - 1 (centring takes one dimension)."""
+    if grm is None:
+        grm = GRM(geno, method=method, maf=maf, include=include, reference=reference, stats=stats, availmemGb=availmemGb, device=device)
+    G = np.asarray(grm["G"], dtype=np.float64)
+    n = G.shape[0]
+    R = np.asarray(grm["reference"], dtype=np.int64)
+    if reference is not None and not np.array_equal(_grm_reference(reference, n), R):
+        raise ValueError("PCA: reference differs from the one the relationship matrix was centred on")
+    k = int(k)
+    if k < 1 or k > R.size - 1:
+        raise ValueError("PCA: k = %d components of %d reference individuals (1 <= k <= |R| - 1)" % (k, R.size))
+    GR = np.ascontiguousarray(G[np.ix_(R, R)])
+    lam, U = (eig or host_model.algebra().eigh)(GR)
+    lam, U = np.asarray(lam, dtype=np.float64).ravel(), np.asarray(U, dtype=np.float64)
+    top = np.argsort(-lam, kind="stable")[:k]
+    lam, U = lam[top], U[:, top]
+    big = np.argmax(np.abs(U), axis=0)
+    U = U * np.where(U[big, np.arange(k)] < 0, -1.0, 1.0)[None, :]
+    pcs = (G[:, R] @ U) / lam[None, :]
+    pcs[R] = U
+    return {"values": lam, "pcs": pcs, "explained": lam / float(np.trace(GR)), "reference": R, "grm": grm}
+
+
 def _ld_sv(stats, n):
     """s = sum g, q = sum g^2 and v = n q - s^2 per marker (int64) from the counts in `stats`, with g = -1 / 0 / +1 for '0' / '1' / '2'."""
     n0, n2 = np.asarray(stats["n0"], dtype=np.int64).ravel(), np.asarray(stats["n2"], dtype=np.int64).ravel()

@@ -673,6 +673,36 @@ def hwe_exact(counts, device=0):
     return out
 
 
+# ---- GRM (include/eagle_hip.h section 1b''''): the exact weighted Gram product; weights, centring and PCA are r_api's ----
+WGRAM_MAX_WEIGHT = (1 << 21) - 1
+
+
+def weighted_gram(f_name_ascii_M, dims, q, max_memory_in_Gbytes=8.0, device=0):
+    """eagle_weighted_gram -> int64 (n, n): Q_ij = sum over the markers m of q_m g_im g_jm with g in {-1, 0, +1}, exact, for integer
+    weights 0 <= q_m <= WGRAM_MAX_WEIGHT = 2^21 - 1, one per marker of M.ascii (dims = (n, L) of M).  ValueError for a q of another
+    length, a negative, fractional or too large weight, before the library is called.  A view alias gives the matrix of its kept
+    individuals."""
+    L = _lib.load()
+    n, nm = int(dims[0]), int(dims[1])
+    qa = np.atleast_1d(np.asarray(q)).ravel()
+    if qa.size != nm:
+        raise ValueError("weighted_gram: q holds %d weights, the panel %d markers" % (qa.size, nm))
+    if qa.dtype == bool:
+        qa = qa.astype(np.int64)
+    if qa.dtype.kind not in "iu":
+        if qa.dtype.kind != "f" or not np.all(qa == np.floor(qa)):   # (a NaN fails the comparison)
+            raise ValueError("weighted_gram: q must hold whole numbers")
+    if qa.size and qa.min() < 0:
+        raise ValueError("weighted_gram: a weight is negative")
+    if qa.size and qa.max() > WGRAM_MAX_WEIGHT:
+        raise ValueError("weighted_gram: a weight is 2^21 or more")
+    q32 = np.ascontiguousarray(qa, dtype=np.uint32)
+    out = np.zeros((n, n), dtype=np.int64)
+    _args_first(L.eagle_weighted_gram, device, (os.fsencode(f_name_ascii_M), _dims(dims), q32.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                float(max_memory_in_Gbytes), out.ctypes.data_as(C.POINTER(C.c_int64))))
+    return out
+
+
 # ---- SURVEY 8 f-4: the dense model algebra on the device, through the C ABI (opt-in; include/eagle_hip.h section 1c) ----
 def _square_any_order(A):
     """(buffer, transposed): a float64 n x n array usable as a column-major matrix without a copy when it is contiguous in

@@ -372,6 +372,39 @@ int eagle_sample_ibs(eagle_ctx* ctx, const char* f_name_ascii_M, const long dims
 int eagle_hwe_exact(eagle_ctx* ctx, const int32_t* counts, long L, int stride, double* p_out);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1b''''. Genomic relationship matrix (no counterpart that the reference calls: its VanRaden G, E/R/GenomicRel.R, is unused): the one
+ *     Gram product the matrices of EIGENSTRAT / PLINK / GCTA and their principal components need, with a weight per marker.  With
+ *     g in {-1, 0, +1} = AA, AB, BB as everywhere in this library and integer weights q_m < 2^21,
+ *         Q_ij = sum_m q_m g_im g_jm                       (int64, exact, |Q_ij| < 2^52, symmetric).
+ *     q_m = d0 + 128 d1 + 128^2 d2 with digits d in [0, 127]; each digit plane is one exact int8 x int8 product on the int8 MFMA,
+ *     C^(p)_ij = sum_m g_im (d^(p)_m g_jm): the second operand is written per marker window and plane into a buffer of the context
+ *     (k_scale_cols_i8, at most about 1 GiB; never an n x L temporary), the product is k_syrk_i8's tile engine with two operand images
+ *     (k_gram_i8ab, upper-triangular tile pairs only: the result is symmetric), and Q = C^(0) + 128 C^(1) + 128^2 C^(2) in int64
+ *     (k_wgram_finish).  A plane whose digits are all zero costs nothing: weights in {0, 1} (the Gram product of a marker subset) are
+ *     one product, q = 0 everywhere is none.  The cached int8 and fp4 images of a resident file are only read: a later
+ *     eagle_calculateMMt on the same file returns the bits it returned before.
+ *
+ *     What a relationship matrix is made of from Q is the caller's fp64 arithmetic (r_api.grm_weights, r_api.grm_from_gram).
+ *     Centring needs no second pass over the genotypes: with mu_m the mean of g_.m over a set R of individuals,
+ *         sum_m q_m (g_im - mu_m)(g_jm - mu_m) = Q_ij - r_i - r_j + kappa,   r_i = (1/|R|) sum_{j in R} Q_ij,   kappa = (1/|R|) sum_{i in R} r_i,
+ *     because sum_m q_m mu_m g_im = r_i: centring every marker at its mean over R is double-centring Q over R.
+ *
+ *     The file is read as eagle_sample_ibs reads it (resident image when it fits, else marker windows from the sidecar or the text;
+ *     a VIEW alias works) and streamed and resident runs give the same integers.  Single device: a multi-device context works on its
+ *     first device.  Argument errors (EAGLE_ERR_ARG: a NULL pointer, dims <= 0, and those named below) are decided before the context
+ *     is used; with ctx == NULL their text is in eagle_open_error().
+ * ------------------------------------------------------------------------------------------- */
+
+/* The int32 accumulator of a digit plane holds |sum| <= 127 L.  The accumulators are NOT folded into the int64 result between
+ * windows: a panel with more markers than this, floor((2^31 - 1) / 127), is refused, so that nothing can wrap. */
+#define EAGLE_WGRAM_MAX_MARKERS 16909320L
+
+/* Q_out: n x n int64, row-major, as defined above, over all L markers of M.ascii (dims = (n, L)); q[m] < 2^21 for every marker m.
+ * EAGLE_ERR_ARG: L >= 2^31, L > EAGLE_WGRAM_MAX_MARKERS, a q[m] >= 2^21. */
+int eagle_weighted_gram(eagle_ctx* ctx, const char* f_name_ascii_M, const long dims[2], const uint32_t* q, double max_memory_in_Gbytes,
+                        int64_t* Q_out);
+
+/* ---------------------------------------------------------------------------------------------
  * 1c. Dense n x n model algebra on the device (OPT-IN: north_star keeps calculateH / calculateP / emma.* on
  *     host LAPACK, and nothing above calls these).  Once the scan takes tens of milliseconds the ~10-15 O(n^3) base-R calls
  *     of a find_qtl iteration are the whole run time (the author's note MyPackage/MyREADME:1 names eigen(); his MAGMA
