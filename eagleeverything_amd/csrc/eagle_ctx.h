@@ -106,7 +106,7 @@ struct eagle_ctx {
     void* stage_pin[2] = {nullptr, nullptr}; void* stage_raw[2] = {nullptr, nullptr}; size_t stage_cap = 0;  // tile streamer
     // per-device launch state (a process may hold one ctx per GPU): dynamic-LDS attributes set on this device, schedule
     // experiment switch of tools/bench_i8_engine.py (0 = shipped)
-    bool attr_vara_i8 = false, attr_vara_i8w = false, attr_vara_i8p = false, attr_vara_i8pp = false, attr_vara_i8px = false, attr_syrk_f4w = false, attr_zbuild_i8 = false, attr_vara_f6 = false, attr_gemv = false, attr_w8_gemm = false;
+    bool attr_vara_i8 = false, attr_vara_i8w = false, attr_vara_i8p = false, attr_vara_i8pp = false, attr_vara_i8px = false, attr_syrk_f4w = false, attr_zbuild_i8 = false, attr_vara_f6 = false, attr_gemv = false, attr_w8_gemm = false, attr_knn_rows = false;
     int tune = 0;
     // W = S (V S) on the int8 engine (eagle_w8.hip): workspace, and what the last call left for the scan that follows it
     int w_mode = 1;            // 0 = always the fp64 GEMM, 1 = int8 digit slices from 4,096 padded individuals up, 2 = int8 at any size (tests)
@@ -208,6 +208,13 @@ extern "C" int eagle_dev_ibs_finish(eagle_ctx* ctx, const int32_t* D32, const in
 extern "C" int eagle_dev_hwe_exact(eagle_ctx* ctx, const int32_t* counts, long L, int stride, double* p, void* stream);
 extern "C" int eagle_dev_f4_abs(eagle_ctx* ctx, const void* src4, long ld4_src, long rows, long row_bytes, void* dst4, long ld4_dst, void* stream);
 int eagle_ibs_counts(eagle_ctx* ctx, const char* path, long n, long L, double mem_gb, int threads, int32_t* ibs0_out, int32_t* hethet_out);
+// kNN imputation (eagle_impute.hip; include/eagle_hip.h section 1b'''i), device pointers throughout.  nbr[n][K] from the n x n int32 matrices
+// of eagle_dev_ibs_finish.  out = `rows` raw .bed rows with every missing genotype filled, counts[rows][2] = (by vote, by fallback), from
+// the rows, their counts mcounts[rows][4] (eagle_dev_bed_marker_counts) and a neighbour table whose entries the CALLER has checked to lie
+// in [-1, n): the kernel indexes the staged rows with them.
+extern "C" int eagle_dev_knn_rows(eagle_ctx* ctx, const int32_t* ibs0, const int32_t* hethet, long n, int K, int32_t* nbr, void* stream);
+extern "C" int eagle_dev_bed_impute(eagle_ctx* ctx, const uint8_t* bed, long rows, long n, const int32_t* nbr, int K, int k, int min_votes,
+                                    const int32_t* mcounts, uint8_t* out, int32_t* counts, void* stream);
 // GRM (eagle_grm.hip; include/eagle_hip.h section 1b'''').  B[r][c] = digit[c] * A[r][c] for the rows [0, rows) and 16-byte column groups of
 // an individual-major int8 window (A in {-1, 0, +1}, digit in [0, 127]; rows [n, rows) of B are written as zeros); the NT product
 // C32[i][j] += sum_k A[i][k] B[j][k] on the tile engine of k_syrk_i8 (upper 256-tiles live); Q = C0 + 128 C1 + 128^2 C2 (a NULL plane

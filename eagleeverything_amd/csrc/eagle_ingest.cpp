@@ -906,6 +906,110 @@ extern "C" int eagle_bed_marker_counts(eagle_ctx* ctx, const char* bed_path, con
     return EAGLE_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// kNN imputation of a .bed file (no counterpart in the reference; kernels in eagle_impute.hip)
+// ---------------------------------------------------------------------------------------------------------------
+extern "C" int eagle_knn_rows(eagle_ctx* ctx, const int32_t* ibs0, const int32_t* hethet, long n, int K, int32_t* nbr_out) {
+    if (!ibs0 || !hethet || !nbr_out) return qc_fail(ctx, EAGLE_ERR_ARG, "knn_rows: NULL argument");
+    if (n <= 0) return qc_fail(ctx, EAGLE_ERR_ARG, "knn_rows: n must be positive");
+    if (n > EAGLE_KNN_MAX_N) return qc_fail(ctx, EAGLE_ERR_ARG, "knn_rows: more than EAGLE_KNN_MAX_N individuals");
+    if (K < 1 || K > EAGLE_KNN_MAX_K) return qc_fail(ctx, EAGLE_ERR_ARG, "knn_rows: K outside [1, 256]");
+    if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "knn_rows: no context");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t mb = sizeof(int32_t) * (size_t)n * (size_t)n, nb = sizeof(int32_t) * (size_t)n * (size_t)K;
+    DevBuf d0, dh, dn;
+    HIPCHK(ctx, d0.alloc(mb));
+    HIPCHK(ctx, dh.alloc(mb));
+    HIPCHK(ctx, dn.alloc(nb));
+    HIPCHK(ctx, hipMemcpyAsync(d0.p, ibs0, mb, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(dh.p, hethet, mb, hipMemcpyHostToDevice, ctx->stream));
+    int rc = eagle_dev_knn_rows(ctx, d0.as<int32_t>(), dh.as<int32_t>(), n, K, dn.as<int32_t>(), ctx->stream);
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    HIPCHK(ctx, hipMemcpyAsync(nbr_out, dn.p, nb, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return EAGLE_OK;
+}
+
+// The windows of eagle_bed_marker_counts through the same staging ring.  Window k: pread into pinned buffer k & 1, copy to the device,
+// count (the fallback genotypes), patch into `patched`, copy back into the SAME pinned buffer (stream order: behind its upload); the
+// pwrite of window k - 1 runs under the device work of window k.
+extern "C" int eagle_bed_impute_knn(eagle_ctx* ctx, const char* bed_path, const long dims[2], const int32_t* nbr, int K, int k, int min_votes,
+                                    const char* out_bed_path, double max_memory_in_Gbytes, int32_t* counts_out) {
+    if (!bed_path || !dims || !nbr || !out_bed_path) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_impute_knn: NULL argument");
+    const long n = dims[0], L = dims[1];
+    if (n <= 0 || L <= 0) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_impute_knn: dims must be positive");
+    if (n > EAGLE_IMPUTE_MAX_N) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_impute_knn: more than EAGLE_IMPUTE_MAX_N individuals");
+    if (K < 1 || K > EAGLE_KNN_MAX_K) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_impute_knn: K outside [1, 256]");
+    if (k < 1 || k > K) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_impute_knn: k outside [1, K]");
+    if (min_votes < 1) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_impute_knn: min_votes must be at least 1");
+    if (std::string(bed_path) == out_bed_path) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_impute_knn: the output file must differ from the input file");
+    const size_t nn = (size_t)n * (size_t)K;
+    for (size_t i = 0; i < nn; i++)
+        if (nbr[i] < -1 || nbr[i] >= n) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_impute_knn: a neighbour outside [-1, n)");
+    if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_impute_knn: no context");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int fdin = -1;
+    if (int orc = open_bed(ctx, bed_path, n, L, &fdin)) return orc;
+    struct Closer { int fd; ~Closer() { if (fd >= 0) close(fd); } } closer{fdin};
+    const int threads = host_threads();
+    const long rb = bed_row_bytes(n);
+    double cap = 67108864.0;
+    if (max_memory_in_Gbytes > 0) cap = std::min(cap, max_memory_in_Gbytes * 1e9 / 4.0);  // the loaders' staging rule
+    const long w = std::max(1L, std::min(L, (long)cap / rb));
+    int rc = eagle_stage_ensure(ctx, (size_t)w * rb);
+    if (rc) return rc;
+    DevBuf d_nbr, mcounts, counts, patched;
+    HIPCHK(ctx, d_nbr.alloc(sizeof(int32_t) * nn));
+    HIPCHK(ctx, mcounts.alloc(sizeof(int32_t) * 4 * (size_t)w));
+    HIPCHK(ctx, counts.alloc(sizeof(int32_t) * 2 * (size_t)L));
+    HIPCHK(ctx, patched.alloc((size_t)w * rb));
+    HIPCHK(ctx, hipMemcpyAsync(d_nbr.p, nbr, sizeof(int32_t) * nn, hipMemcpyHostToDevice, ctx->stream));
+    hipEvent_t done[2] = {nullptr, nullptr};
+    for (int b = 0; b < 2; b++) HIPCHK(ctx, hipEventCreateWithFlags(&done[b], hipEventDisableTiming));
+    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int b = 0; b < 2; b++) if (e[b]) (void)hipEventDestroy(e[b]); } } evg{done};
+    TextOut out;   // cut back to nothing unless the call gets as far as finish()
+    static const char head[BED_HEADER_BYTES] = {0x6c, 0x1b, 0x01};
+    if (!out.open_sized(out_bed_path, (off_t)bed_expected_size(n, L)) || !pwrite_all(out.fd, head, sizeof head, 0, 1))
+        return failf(ctx, EAGLE_ERR_OPEN, "ERROR: Could not open  %s", out_bed_path);
+    long pend_r = -1, pend_n = 0;
+    int pend_b = 0;
+    auto flush = [&]() -> int {
+        if (pend_r < 0) return EAGLE_OK;
+        hipError_t e = hipEventSynchronize(done[pend_b]);
+        if (e != hipSuccess) return eagle_fail_hip(ctx, e, "hipEventSynchronize");
+        if (!pwrite_all(out.fd, (const char*)ctx->stage_pin[pend_b], (size_t)pend_n * rb, (off_t)BED_HEADER_BYTES + (off_t)pend_r * rb, threads))
+            return failf(ctx, EAGLE_ERR_OPEN, "ERROR: could not write %s", out_bed_path);
+        pend_r = -1;
+        return EAGLE_OK;
+    };
+    long wk = 0;
+    for (long r0 = 0; r0 < L; r0 += w, wk++) {
+        const int b = (int)(wk & 1);  // free: window wk - 2 went to disk while window wk - 1 was enqueued
+        const long nr = std::min(w, L - r0);
+        if (!pread_all(fdin, (char*)ctx->stage_pin[b], (size_t)nr * rb, (off_t)BED_HEADER_BYTES + (off_t)r0 * rb, threads)) {
+            (void)hipStreamSynchronize(ctx->stream);
+            return failf(ctx, EAGLE_ERR_FORMAT, "%s: could not read markers %ld to %ld", bed_path, r0 + 1, r0 + nr);
+        }
+        const uint8_t* raw = (const uint8_t*)ctx->stage_raw[b];
+        HIPCHK(ctx, hipMemcpyAsync(ctx->stage_raw[b], ctx->stage_pin[b], (size_t)nr * rb, hipMemcpyHostToDevice, ctx->stream));
+        rc = eagle_dev_bed_marker_counts(ctx, raw, nr, n, mcounts.as<int32_t>(), ctx->stream);
+        if (!rc) rc = eagle_dev_bed_impute(ctx, raw, nr, n, d_nbr.as<int32_t>(), K, k, min_votes, mcounts.as<int32_t>(), patched.as<uint8_t>(),
+                                           counts.as<int32_t>() + 2 * r0, ctx->stream);
+        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+        HIPCHK(ctx, hipMemcpyAsync(ctx->stage_pin[b], patched.p, (size_t)nr * rb, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipEventRecord(done[b], ctx->stream));
+        rc = flush();
+        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+        pend_r = r0; pend_n = nr; pend_b = b;
+    }
+    rc = flush();
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    if (counts_out) HIPCHK(ctx, hipMemcpyAsync(counts_out, counts.p, sizeof(int32_t) * 2 * (size_t)L, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    out.finish();
+    return EAGLE_OK;
+}
+
 namespace {
 
 // One of the two output files of eagle_filter_markers: `rows` lines of `cols` characters with sidecar, made band by band of `band`

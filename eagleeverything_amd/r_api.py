@@ -241,24 +241,37 @@ def _read_marker_bed(filename, availmemGb, quiet, outdir, message, device):
 
 
 def ReadMarker(filename=None, type="text", missing=None, AA=None, AB=None, BB=None, availmemGb=16, quiet=True, outdir=None,
-               message=None, device=0, maf=None, max_missing=None, drop_monomorphic=False):
+               message=None, device=0, maf=None, max_missing=None, drop_monomorphic=False, impute=None):
     """E/R/ReadMarker.R:194-318 -> geno dict {asciifileM, asciifileMt, dim_of_ascii_M} or None (the R list / NULL).
     type="PLINKbed" (not in the reference): `filename` is the .bed file of a PLINK binary fileset or its prefix; n and L are the
     line counts of the .fam and .bim beside it, the genotypes go through rcpp_api.create_ascii_from_bed.
     maf / max_missing / drop_monomorphic (not in the reference; all off by default, and then nothing here differs from the line
     above): the converted panel goes through FilterMarkers -- with the .bed file's own counts for type="PLINKbed", so that
     missingness is the file's, not the heterozygotes it became -- into <outdir>/qc, and the dict returned names those files and
-    carries marker_index (None when no marker passes)."""
+    carries marker_index (None when no marker passes).
+    impute=k (not in the reference; type="PLINKbed" only; default None, and then nothing here differs from the lines above): after the
+    ingestion the missing genotypes of the fileset are filled by ImputeBed(k=k) into <outdir>/imputed/panel.bed / .bim / .fam, that
+    fileset is ingested into <outdir>/imputed, and the dict returned names ITS files.  With a filter as well, the imputed panel is
+    filtered, on the statistics of the original file's called genotypes."""
     say = message or (lambda s: None)
+    if impute is not None and type != "PLINKbed":
+        say(' impute needs type = "PLINKbed": only a .bed file still knows which genotypes are missing. \n')
+        say(" ReadMarker has terminated with errors")
+        return None
     if maf is not None or max_missing is not None or drop_monomorphic:
         geno = ReadMarker(filename, type=type, missing=missing, AA=AA, AB=AB, BB=BB, availmemGb=availmemGb, quiet=quiet, outdir=outdir,
-                          message=message, device=device)
+                          message=message, device=device, impute=impute)
         if geno is None:
             return None
         return FilterMarkers(geno, maf=maf, max_missing=max_missing, drop_monomorphic=drop_monomorphic,
                              bed=bed_fileset(filename)[0] if type == "PLINKbed" else None, availmemGb=availmemGb, message=message, device=device)
     if type == "PLINKbed":
-        return _read_marker_bed(filename, availmemGb, quiet, outdir, message, device)
+        geno = _read_marker_bed(filename, availmemGb, quiet, outdir, message, device)
+        if geno is None or impute is None:
+            return geno
+        imputed = os.path.join(os.path.dirname(geno["asciifileM"]), "imputed")
+        res = ImputeBed(filename, geno, os.path.join(imputed, "panel"), k=int(impute), availmemGb=availmemGb, message=message, device=device)
+        return _read_marker_bed(res["bed"], availmemGb, quiet, imputed, message, device)
     if type not in ("text", "PLINK"):                                               # :206-215
         say(' type must be set to "text" or "PLINK". \n')
         say(" ReadMarker has terminated with errors")
@@ -289,6 +302,121 @@ def ReadMarker(filename=None, type="text", missing=None, AA=None, AB=None, BB=No
     if not ok:
         return None
     return {"asciifileM": os.path.join(outdir, "M.ascii"), "asciifileMt": os.path.join(outdir, "Mt.ascii"), "dim_of_ascii_M": dims}
+
+
+# ---- kNN imputation of a PLINK .bed fileset (include/eagle_hip.h section 1b'''i): the restatements in numpy and the interface ----
+KNN_MAX_K = 256
+_DOSAGE_OF_CODE = np.array([0, 0, 1, 2], dtype=np.int64)     # 2-bit code -> dosage (code 1, missing, has none)
+_CODE_OF_DOSAGE = np.array([0, 2, 3], dtype=np.uint8)
+
+
+def read_bed_codes(bed, dims):
+    """The 2-bit codes of a SNP-major .bed file (or fileset prefix) -> uint8 (L, n): 0 hom A1, 1 missing, 2 het, 3 hom A2.  Host only."""
+    n, L = int(dims[0]), int(dims[1])
+    rb = (n + 3) // 4
+    raw = np.fromfile(bed_fileset(bed)[0], dtype=np.uint8)
+    if raw.size != 3 + L * rb or bytes(raw[:3]) != b"\x6c\x1b\x01":
+        raise ValueError("%s is not a SNP-major .bed file of %d markers of %d individuals" % (bed, L, n))
+    rows = raw[3:].reshape(L, rb)
+    return np.stack([(rows >> s) & 3 for s in (0, 2, 4, 6)], axis=2).reshape(L, 4 * rb)[:, :n].copy()
+
+
+def pack_bed_codes(codes):
+    """uint8 (L, n) 2-bit codes -> uint8 (L, ceil(n/4)): the rows of a SNP-major .bed file, pad bit pairs 00."""
+    codes = np.asarray(codes, dtype=np.uint8)
+    L, n = codes.shape
+    f = np.zeros((L, (n + 3) // 4 * 4), dtype=np.uint8)
+    f[:, :n] = codes
+    f = f.reshape(L, -1, 4)
+    return (f[:, :, 0] | f[:, :, 1] << 2 | f[:, :, 2] << 4 | f[:, :, 3] << 6).astype(np.uint8)
+
+
+def knn_distance(ibs0, hethet):
+    """d_ij = 4 ibs0_ij + h_i + h_j - 2 hethet_ij, h = diag(hethet), -> int32 (n, n): the sum over the markers of (g_i - g_j)^2 for
+    g in {-1, 0, +1}, from rcpp_api.sample_ibs' matrices (int32 arithmetic as on the device: exact while 4 L < 2^31)."""
+    a, hh = np.asarray(ibs0, dtype=np.int64), np.asarray(hethet, dtype=np.int64)
+    h = np.diagonal(hh)
+    return (4 * a + h[:, None] + h[None, :] - 2 * hh).astype(np.int32)
+
+
+def knn_rows_host(d, K):
+    """rcpp_api.knn_rows restated in numpy: d = knn_distance(...) -> int32 (n, K).  Row i = the min(K, n - 1) individuals j != i with
+    the smallest keys (uint64)(uint32)d_ij << 32 | j in increasing order, then -1."""
+    d = np.asarray(d, dtype=np.int32)
+    n, K = d.shape[0], int(K)
+    if d.shape != (n, n) or not 1 <= K <= KNN_MAX_K:
+        raise ValueError("knn_rows_host: d must be square and K in [1, %d]" % KNN_MAX_K)
+    keys = (d.view(np.uint32).astype(np.uint64) << np.uint64(32)) | np.arange(n, dtype=np.uint64)[None, :]
+    np.fill_diagonal(keys, np.iinfo(np.uint64).max)
+    keff = min(K, n - 1)
+    out = np.full((n, K), -1, dtype=np.int32)
+    if keff:
+        part = np.partition(keys, keff - 1, axis=1)[:, :keff] if keff < n - 1 else keys
+        out[:, :keff] = (np.sort(part, axis=1)[:, :keff] & np.uint64(0xffffffff)).astype(np.int32)
+    return out
+
+
+def impute_knn_host(codes, nbr, k, min_votes):
+    """rcpp_api.bed_impute_knn restated in numpy: codes = uint8 (L, n) 2-bit codes of the input (read_bed_codes), nbr = int32 (n, K)
+    -> (rows, counts): rows = uint8 (L, ceil(n/4)), the marker rows of the output .bed file (everything after its three header bytes),
+    counts = int32 (L, 2), genotypes imputed by vote and by fallback.  The rule is the header's: the first k neighbours of the list
+    that are called at the marker vote, the dosage is (2 s + c) // (2 c), and with fewer than min_votes voters the marker's own calls
+    give it (heterozygous when it has none)."""
+    codes = np.asarray(codes, dtype=np.uint8)
+    nbr = np.asarray(nbr, dtype=np.int64)
+    L, n = codes.shape
+    k, min_votes = int(k), int(min_votes)
+    if nbr.ndim != 2 or nbr.shape[0] != n or not 1 <= nbr.shape[1] <= KNN_MAX_K or not 1 <= k <= nbr.shape[1] or min_votes < 1:
+        raise ValueError("impute_knn_host: nbr must be (n, K), 1 <= K <= %d, 1 <= k <= K, min_votes >= 1" % KNN_MAX_K)
+    if nbr.size and (nbr.min() < -1 or nbr.max() >= n):
+        raise ValueError("impute_knn_host: a neighbour outside [-1, n)")
+    miss = codes == 1
+    c = np.zeros((L, n), dtype=np.int64)
+    s = np.zeros((L, n), dtype=np.int64)
+    for t in range(nbr.shape[1]):
+        j = nbr[:, t]
+        cj = codes[:, np.maximum(j, 0)]                             # (L, n): the code of i's t-th neighbour at every marker
+        vote = miss & (j >= 0)[None, :] & (cj != 1) & (c < k)
+        c += vote
+        s += np.where(vote, _DOSAGE_OF_CODE[cj], 0)
+    called = (~miss).sum(axis=1)
+    dose = np.where(miss, 0, _DOSAGE_OF_CODE[codes]).sum(axis=1)
+    fb = np.where(called > 0, _CODE_OF_DOSAGE[(2 * dose + called) // np.maximum(2 * called, 1)], 2).astype(np.uint8)
+    by_vote = miss & (c >= min_votes)
+    voted = _CODE_OF_DOSAGE[np.where(by_vote, (2 * s + c) // np.maximum(2 * c, 1), 0)]
+    out = np.where(by_vote, voted, np.where(miss, fb[:, None], codes)).astype(np.uint8)
+    counts = np.stack([by_vote.sum(axis=1), (miss & ~by_vote).sum(axis=1)], axis=1).astype(np.int32)
+    return pack_bed_codes(out), counts
+
+
+def ImputeBed(bed, geno, out_prefix, k=10, K=64, min_votes=1, availmemGb=8, message=None, device=0):
+    """kNN imputation of the missing genotypes of a PLINK binary fileset -> {"bed": the new .bed file, "n_missing", "by_vote",
+    "by_fallback": totals, "counts": int32 (L, 2) per marker}.  bed = the .bed file (or prefix) that `geno` was ingested from.
+    The neighbours come from the ingested panel (rcpp_api.sample_ibs on geno["asciifileM"], knn_distance, rcpp_api.knn_rows: the K
+    nearest individuals genome-wide, missing genotypes counted as the heterozygotes ingestion made of them); every missing genotype
+    then takes the rounded mean dosage of the first k of them that are called at its marker (rcpp_api.bed_impute_knn; the marker's
+    own mean with fewer than min_votes voters).  Writes <out_prefix>.bed and byte-for-byte copies of the .bim and .fam; the new
+    fileset has no missing code and ReadMarker(type="PLINKbed") ingests it."""
+    say = message or (lambda s: None)
+    src_bed, src_bim, src_fam = bed_fileset(bed)
+    n, L = int(geno["dim_of_ascii_M"][0]), int(geno["dim_of_ascii_M"][1])
+    out_bed, out_bim, out_fam = bed_fileset(str(out_prefix))
+    if os.path.abspath(out_bed) == os.path.abspath(src_bed):
+        raise ValueError("ImputeBed: out_prefix names the input fileset")
+    K = max(1, min(int(K), KNN_MAX_K))
+    k = max(1, min(int(k), K))
+    ibs0, hethet = rcpp_api.sample_ibs(geno["asciifileM"], (n, L), availmemGb, device=device)
+    nbr = rcpp_api.knn_rows(ibs0, hethet, K, device=device)
+    os.makedirs(os.path.dirname(os.path.abspath(out_bed)), exist_ok=True)
+    counts = rcpp_api.bed_impute_knn(src_bed, (n, L), nbr, k, int(min_votes), out_bed, availmemGb, device=device)
+    for src, dst in ((src_bim, out_bim), (src_fam, out_fam)):
+        with open(src, "rb") as fi, open(dst, "wb") as fo:
+            for buf in iter(lambda: fi.read(1 << 24), b""):
+                fo.write(buf)
+    by_vote, by_fallback = int(counts[:, 0].sum(dtype=np.int64)), int(counts[:, 1].sum(dtype=np.int64))
+    say(" Imputed %d missing genotypes: %d from their %d nearest called neighbours, %d from the marker's own mean. "
+        % (by_vote + by_fallback, by_vote, k, by_fallback))
+    return {"bed": out_bed, "n_missing": by_vote + by_fallback, "by_vote": by_vote, "by_fallback": by_fallback, "counts": counts}
 
 
 def marker_stats_from_counts(n0, n1, n2, n_missing=None):
@@ -339,7 +467,8 @@ def MarkerStats(geno, bed=None, availmemGb=8, device=0, hwe=False):
     """Per-marker QC statistics of a panel -> dict of length-L arrays n0, n1, n2, n_missing, freq, maf, het, call_rate
     (marker_stats_from_counts), with hwe=True also hwe_p, the Hardy-Weinberg exact test of (n0, n1, n2) (HWE); the counting runs on the device (rcpp_api.marker_counts on geno["asciifileMt"]: one pass over the
     int8 image the scans read), the arithmetic on the host.
-    The text files of a panel no longer know which genotypes were missing: ingestion made them heterozygotes, so without `bed`
+    The text files of a panel no longer know which genotypes were missing: ingestion made them heterozygotes (unless the fileset went
+    through ImputeBed first, which leaves none), so without `bed`
     n_missing is zero, n1 includes them and call_rate is 1.  bed = the .bed file (or prefix) the panel was ingested from: the counts
     are then the file's own (rcpp_api.bed_marker_counts), n0 / n1 / n2 and everything derived exclude the missing genotypes, and
     n_missing is real.  n0 counts the genotype the files code '0' (homozygous A1 of a .bed file)."""
@@ -510,8 +639,9 @@ def Relatedness(geno, threshold=0.0884, availmemGb=8, device=0):
     """Duplicated and closely related individuals of a panel -> {"kinship": fp64 (n, n) KING-robust phi (king_from_counts),
     "pairs": int64 (k, 2), 0-based, i < j, sorted: the pairs with phi > threshold (a NaN pair is never one), "phi": their phi,
     "degree": king_degree of it, "ibs0", "hethet": the integer matrices}.  The counts come from the device (rcpp_api.sample_ibs: two
-    exact Gram products on the fp4 MFMA over all markers of geno["asciifileM"]); missing genotypes count as heterozygotes, so drop
-    low-call-rate individuals first (SampleStats(bed=), sample_keep_mask).  related_drop chooses whom to drop."""
+    exact Gram products on the fp4 MFMA over all markers of geno["asciifileM"]); missing genotypes count as heterozygotes, so impute
+    them first (ImputeBed, ReadMarker(impute=)) or drop low-call-rate individuals (SampleStats(bed=), sample_keep_mask).
+    related_drop chooses whom to drop."""
     n, L = int(geno["dim_of_ascii_M"][0]), int(geno["dim_of_ascii_M"][1])
     ibs0, hethet = rcpp_api.sample_ibs(geno["asciifileM"], (n, L), availmemGb, device=device)
     phi = king_from_counts(ibs0, hethet)

@@ -673,6 +673,42 @@ def hwe_exact(counts, device=0):
     return out
 
 
+# ---- kNN imputation (include/eagle_hip.h section 1b'''i): the neighbour table and the patched .bed file; r_api holds the restatements ----
+def _i32_matrix(a, what):
+    m = np.asarray(a)
+    m32 = np.ascontiguousarray(m, dtype=np.int32)
+    if m32.ndim != 2 or not np.array_equal(m32, m):
+        raise ValueError("%s must be a matrix of whole numbers that fit int32" % what)
+    return m32
+
+
+def knn_rows(ibs0, hethet, K, device=0):
+    """eagle_knn_rows -> int32 (n, K): row i = the min(K, n - 1) individuals j != i with the smallest distance
+    d_ij = 4 ibs0_ij + h_i + h_j - 2 hethet_ij (h = diag(hethet)), nearest first, ties to the smaller index; -1 beyond them.
+    ibs0, hethet: the (n, n) matrices of sample_ibs."""
+    L = _lib.load()
+    a, h = _i32_matrix(ibs0, "knn_rows: ibs0"), _i32_matrix(hethet, "knn_rows: hethet")
+    if a.shape[0] != a.shape[1] or a.shape != h.shape:
+        raise ValueError("knn_rows: ibs0 and hethet must be square and of one shape")
+    out = np.zeros((a.shape[0], max(int(K), 1)), dtype=np.int32)
+    _args_first(L.eagle_knn_rows, device, (a.ctypes.data_as(_c_i32p), h.ctypes.data_as(_c_i32p), a.shape[0], int(K), out.ctypes.data_as(_c_i32p)))
+    return out
+
+
+def bed_impute_knn(bed_path, dims, nbr, k, min_votes, out_bed_path, max_memory_in_Gbytes=8.0, device=0):
+    """eagle_bed_impute_knn -> int32 (L, 2): the genotypes of every marker imputed by vote and by fallback.  Writes out_bed_path, the
+    SNP-major .bed file bed_path (dims = (n individuals, L markers)) with every missing genotype filled from the first k called
+    neighbours of nbr ((n, K) int32: knn_rows), or from the marker's own calls when fewer than min_votes of them are called."""
+    L = _lib.load()
+    nb = _i32_matrix(nbr, "bed_impute_knn: nbr")
+    if nb.shape[0] != int(dims[0]):
+        raise ValueError("bed_impute_knn: nbr holds %d rows, the file %d individuals" % (nb.shape[0], int(dims[0])))
+    out = np.zeros((max(int(dims[1]), 0), 2), dtype=np.int32)
+    _args_first(L.eagle_bed_impute_knn, device, (os.fsencode(bed_path), _dims(dims), nb.ctypes.data_as(_c_i32p), nb.shape[1], int(k), int(min_votes),
+                                                 os.fsencode(out_bed_path), float(max_memory_in_Gbytes), out.ctypes.data_as(_c_i32p)))
+    return out
+
+
 # ---- GRM (include/eagle_hip.h section 1b''''): the exact weighted Gram product; weights, centring and PCA are r_api's ----
 WGRAM_MAX_WEIGHT = (1 << 21) - 1
 

@@ -372,6 +372,58 @@ int eagle_sample_ibs(eagle_ctx* ctx, const char* f_name_ascii_M, const long dims
 int eagle_hwe_exact(eagle_ctx* ctx, const int32_t* counts, long L, int stride, double* p_out);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1b'''i. kNN imputation of missing genotypes (no counterpart in the reference, which makes every missing genotype a heterozygote):
+ *     the kNNi of TASSEL over individuals.  Neighbours are ranked genome-wide, the vote on a genotype is taken among the nearest
+ *     neighbours that are called at its marker, and the result is a new SNP-major .bed file without a missing code, which
+ *     eagle_create_ascii_from_bed ingests like any other.  Integer arithmetic in a fixed order: a restatement in numpy gives the same
+ *     bytes (r_api.knn_rows_host, r_api.impute_knn_host).
+ *
+ *     2-bit codes: 0 = homozygous A1, 1 = missing, 2 = heterozygous, 3 = homozygous A2; individual 4b+q at bits 2q of byte b of a
+ *     marker's row of rb = ceil(n/4) bytes.  Dosage t(0) = 0, t(2) = 1, t(3) = 2.
+ *
+ *     Distance, on the INGESTED panel (missing = heterozygous), from eagle_sample_ibs' matrices, with h_i = hethet_ii:
+ *         d_ij = 4 ibs0_ij + h_i + h_j - 2 hethet_ij        = sum_m (g_im - g_jm)^2 for g in {-1, 0, +1},
+ *     in int32 arithmetic (exact while 4 L < 2^31).
+ *
+ *     Neighbour table nbr[n][K], int32, 1 <= K <= EAGLE_KNN_MAX_K: row i holds the K_eff = min(K, n - 1) individuals j != i with the
+ *     smallest keys (uint64)(uint32)d_ij << 32 | j, in increasing key order (ties in d go to the smaller index); the entries beyond
+ *     K_eff are -1.
+ *
+ *     Vote for a missing genotype of individual i at marker m: walk nbr[i][0 .. K) in order, passing over entries that are -1, and
+ *     take the first k (1 <= k <= K) neighbours whose code at m IN THE INPUT FILE is not 1.  With c voters (c <= k) and s the sum of
+ *     their dosages:  if c >= min_votes (>= 1) the dosage written is (2 s + c) / (2 c) in integer division, the mean rounded half up.
+ *     Fallback otherwise: the same formula on the marker's own called genotypes, c = n0 + n1 + n2, s = n1 + 2 n2 (the counts of
+ *     eagle_bed_marker_counts); a marker without any call becomes heterozygous, the ingestion's rule.
+ *
+ *     Votes read original codes only, so the result does not depend on the order in which genotypes are filled.  Called genotypes are
+ *     copied; the unused bit pairs of a row's last byte are written as 00.
+ *
+ *     Single device: a multi-device context works on its first device.  Argument errors (EAGLE_ERR_ARG: a NULL pointer, dims <= 0,
+ *     and those named below) are decided before the context is used; with ctx == NULL their text is in eagle_open_error().
+ * ------------------------------------------------------------------------------------------- */
+
+#define EAGLE_KNN_MAX_K 256
+/* k_knn_rows keeps a row of d in LDS, one dword per individual (128 KiB at most); the two n x n int32 matrices take 8 GiB there. */
+#define EAGLE_KNN_MAX_N 32768L
+/* k_bed_impute stages whole marker rows in LDS, 60 KiB per block (two blocks per CU): a row of more individuals is refused. */
+#define EAGLE_IMPUTE_MAX_N 245760L
+
+/* nbr_out: n x K int32 as defined above, from ibs0 and hethet (n x n int32, row-major: eagle_sample_ibs' outputs), one block per
+ * individual (k_knn_rows).  EAGLE_ERR_ARG: n > EAGLE_KNN_MAX_N, K outside [1, EAGLE_KNN_MAX_K]. */
+int eagle_knn_rows(eagle_ctx* ctx, const int32_t* ibs0, const int32_t* hethet, long n, int K, int32_t* nbr_out);
+
+/* Writes out_bed_path: the SNP-major .bed file bed_path (the format, the checks and the error codes of eagle_create_ascii_from_bed;
+ * dims = (n, L)) with every missing genotype filled as defined above from nbr (n x K int32, host memory) -- the three header bytes,
+ * then the L patched rows.  counts_out (may be NULL): L x 2 int32, the genotypes of marker i imputed by vote and by fallback; their sum
+ * is the marker's missing count.  The rows are staged through pinned memory in the windows of eagle_bed_marker_counts; each window
+ * is counted by that call's kernel (the fallback genotypes), patched by k_bed_impute, copied back and written while the next window
+ * is on the device.  The result does not depend on the window size.
+ * EAGLE_ERR_ARG: n > EAGLE_IMPUTE_MAX_N, K outside [1, EAGLE_KNN_MAX_K], k outside [1, K], min_votes < 1, an nbr entry outside
+ * [-1, n), out_bed_path equal to bed_path -- nothing has been written then.  A failed call leaves no output file of the full size. */
+int eagle_bed_impute_knn(eagle_ctx* ctx, const char* bed_path, const long dims[2], const int32_t* nbr, int K, int k, int min_votes,
+                         const char* out_bed_path, double max_memory_in_Gbytes, int32_t* counts_out);
+
+/* ---------------------------------------------------------------------------------------------
  * 1b''''. Genomic relationship matrix (no counterpart that the reference calls: its VanRaden G, E/R/GenomicRel.R, is unused): the one
  *     Gram product the matrices of EIGENSTRAT / PLINK / GCTA and their principal components need, with a weight per marker.  With
  *     g in {-1, 0, +1} = AA, AB, BB as everywhere in this library and integer weights q_m < 2^21,
