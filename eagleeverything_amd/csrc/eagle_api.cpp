@@ -823,6 +823,24 @@ int eagle_ibs_counts(eagle_ctx* ctx, const char* path, long n, long L, double me
     return download_big(ctx, hethet_out, (const char*)out.p + outb, outb);
 }
 
+// The tail of eagle_bed_sample_ibs (eagle_ingest.cpp, which runs the windows): k_bed_ibs_finish on the four accumulators and the
+// results' way to the host, by eagle_ibs_counts' path.
+int eagle_bed_ibs_results(eagle_ctx* ctx, const int32_t* acc4, long n, long linc, int min_overlap, int32_t* ncalled_out, int32_t* ibs0_out,
+                          int32_t* hethet_out, int32_t* hetsum_out, uint32_t* dist_out) {
+    const long np = eagle_pad(n);
+    const size_t acc = (size_t)np * np, outn = (size_t)n * n, outb = sizeof(int32_t) * outn;
+    DevBuf out;
+    HIPCHK(ctx, out.alloc((dist_out ? 5 : 4) * outb));
+    int32_t* o = out.as<int32_t>();
+    int rc = eagle_dev_bed_ibs_finish(ctx, acc4, acc4 + acc, acc4 + 2 * acc, acc4 + 3 * acc, n, np, linc, min_overlap, o, o + outn, o + 2 * outn,
+                                      o + 3 * outn, dist_out ? (uint32_t*)(o + 4 * outn) : nullptr, ctx->stream);
+    if (rc) return rc;
+    void* host[5] = {ncalled_out, ibs0_out, hethet_out, hetsum_out, dist_out};
+    for (int k = 0; k < (dist_out ? 5 : 4); k++)
+        if ((rc = download_big(ctx, host[k], o + (size_t)k * outn, outb))) return rc;
+    return EAGLE_OK;
+}
+
 // GRM (eagle_weighted_gram, eagle_ingest.cpp): Q = sum_m q_m g_m g_m^T over all L markers of M.ascii by eagle_ibs_counts' rules -- the
 // resident image when the file fits, marker windows through the ChunkRing when it does not.  q is cut into three base-128 digit planes
 // on the host; per window of at most about 1 GiB and per plane that is not zero there, k_scale_cols_i8 writes digit x genotype into the

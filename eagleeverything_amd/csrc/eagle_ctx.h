@@ -106,7 +106,7 @@ struct eagle_ctx {
     void* stage_pin[2] = {nullptr, nullptr}; void* stage_raw[2] = {nullptr, nullptr}; size_t stage_cap = 0;  // tile streamer
     // per-device launch state (a process may hold one ctx per GPU): dynamic-LDS attributes set on this device, schedule
     // experiment switch of tools/bench_i8_engine.py (0 = shipped)
-    bool attr_vara_i8 = false, attr_vara_i8w = false, attr_vara_i8p = false, attr_vara_i8pp = false, attr_vara_i8px = false, attr_syrk_f4w = false, attr_zbuild_i8 = false, attr_vara_f6 = false, attr_gemv = false, attr_w8_gemm = false, attr_knn_rows = false;
+    bool attr_vara_i8 = false, attr_vara_i8w = false, attr_vara_i8p = false, attr_vara_i8pp = false, attr_vara_i8px = false, attr_syrk_f4w = false, attr_zbuild_i8 = false, attr_vara_f6 = false, attr_gemv = false, attr_w8_gemm = false, attr_knn_rows = false, attr_knn_rows_dist = false;
     int tune = 0;
     // W = S (V S) on the int8 engine (eagle_w8.hip): workspace, and what the last call left for the scan that follows it
     int w_mode = 1;            // 0 = always the fp64 GEMM, 1 = int8 digit slices from 4,096 padded individuals up, 2 = int8 at any size (tests)
@@ -213,8 +213,21 @@ int eagle_ibs_counts(eagle_ctx* ctx, const char* path, long n, long L, double me
 // the rows, their counts mcounts[rows][4] (eagle_dev_bed_marker_counts) and a neighbour table whose entries the CALLER has checked to lie
 // in [-1, n): the kernel indexes the staged rows with them.
 extern "C" int eagle_dev_knn_rows(eagle_ctx* ctx, const int32_t* ibs0, const int32_t* hethet, long n, int K, int32_t* nbr, void* stream);
+extern "C" int eagle_dev_knn_rows_dist(eagle_ctx* ctx, const uint32_t* dist, long n, int K, int32_t* nbr, void* stream);
 extern "C" int eagle_dev_bed_impute(eagle_ctx* ctx, const uint8_t* bed, long rows, long n, const int32_t* nbr, int K, int k, int min_votes,
                                     const int32_t* mcounts, uint8_t* out, int32_t* counts, void* stream);
+// Pairwise-complete IBS counts from a .bed file (eagle_bedibs.hip; include/eagle_hip.h section 1b'''ii), device pointers throughout.  The
+// four fp4 operand images (g, u, h, c; plane p at M4 + p * plane_bytes, n_pad rows of ld4 bytes, L_pad markers written) of `rows` raw
+// .bed rows, `include` one byte per row or null; the four n x n int32 results and dist (or null) from the four Gram accumulators
+// (n_pad x n_pad, upper 256-tiles live).  eagle_api.cpp: the finish and the download of the results from the accumulators acc4 (D, Q, H,
+// N side by side, pad256(n)^2 int32 each): the tail of eagle_bed_sample_ibs.
+extern "C" int eagle_dev_bed_pack_fp4(eagle_ctx* ctx, const uint8_t* bed, long rows, long n, const uint8_t* include, long n_pad, long L_pad,
+                                      void* M4, long ld4, long plane_bytes, void* stream);
+extern "C" int eagle_dev_bed_ibs_finish(eagle_ctx* ctx, const int32_t* D32, const int32_t* Q32, const int32_t* H32, const int32_t* N32, long n,
+                                        long n_pad, long linc, int min_overlap, int32_t* ncalled, int32_t* ibs0, int32_t* hethet, int32_t* hetsum,
+                                        uint32_t* dist, void* stream);
+int eagle_bed_ibs_results(eagle_ctx* ctx, const int32_t* acc4, long n, long linc, int min_overlap, int32_t* ncalled_out, int32_t* ibs0_out,
+                          int32_t* hethet_out, int32_t* hetsum_out, uint32_t* dist_out);
 // GRM (eagle_grm.hip; include/eagle_hip.h section 1b'''').  B[r][c] = digit[c] * A[r][c] for the rows [0, rows) and 16-byte column groups of
 // an individual-major int8 window (A in {-1, 0, +1}, digit in [0, 127]; rows [n, rows) of B are written as zeros); the NT product
 // C32[i][j] += sum_k A[i][k] B[j][k] on the tile engine of k_syrk_i8 (upper 256-tiles live); Q = C0 + 128 C1 + 128^2 C2 (a NULL plane

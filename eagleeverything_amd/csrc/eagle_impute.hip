@@ -9,7 +9,8 @@
 //                    K_eff = min(K, n - 1) rounds of a block-wide minimum (a 64-bit butterfly in the wave, four wave minima through
 //                    LDS) pick the neighbours in increasing key order.  Only the owner of a round's winner marks it taken and scans
 //                    its entries again: a thread touches no other thread's entries, so a round needs one barrier, the reduction's (the
-//                    wave minima alternate between two LDS slots).
+//                    wave minima alternate between two LDS slots).  k_knn_rows_dist is the same selection on a uint32 matrix whose
+//                    dwords are the keys' high halves as they stand (eagle_bed_sample_ibs' dist, section 1b'''ii).
 //   k_bed_impute ... raw .bed rows + nbr + the rows' counts (k_bed_marker_counts) -> patched rows and (by vote, by fallback) per row.
 //                    A block owns a group of whole rows: their original bytes are staged in LDS with byte loads (rb = ceil(n/4) has no
 //                    alignment and the rows lie back to back), every vote reads original codes from that copy, so the result does
@@ -65,18 +66,24 @@ __device__ __forceinline__ unsigned long long knn_scan(const uint32_t* d, int n,
     return best;
 }
 
-__global__ __launch_bounds__(256) void k_knn_rows(const int32_t* __restrict__ ibs0, const int32_t* __restrict__ hethet, int n, int K, int keff,
-                                                  int32_t* __restrict__ nbr) {
+// DIST: the row's dwords are read as they are from a uint32 matrix (`ibs0` is that matrix, `hethet` is not used): k_knn_rows_dist
+template <bool DIST>
+__device__ __forceinline__ void knn_rows_body(const int32_t* __restrict__ ibs0, const int32_t* __restrict__ hethet, int n, int K, int keff,
+                                              int32_t* __restrict__ nbr) {
     extern __shared__ uint32_t knn_d[];          // n dwords: d of the row; KNN_TAKEN for i itself and for the neighbours picked so far
     __shared__ unsigned long long wmin[2][4];    // by the round's parity: one barrier per round
     const int i = blockIdx.x, tid = threadIdx.x;
     const long row = (long)i * n;
-    const uint32_t hi = (uint32_t)hethet[row + i];
-    for (int j = tid; j < n; j += 256) {
-        const uint32_t hj = (uint32_t)hethet[(long)j * n + j];
-        // int32 arithmetic (unsigned, so that it is defined): exact while 4 L < 2^31
-        const uint32_t dij = 4u * (uint32_t)ibs0[row + j] + hi + hj - 2u * (uint32_t)hethet[row + j];
-        knn_d[j] = j == i ? KNN_TAKEN : dij;
+    if constexpr (DIST) {
+        for (int j = tid; j < n; j += 256) knn_d[j] = j == i ? KNN_TAKEN : (uint32_t)ibs0[row + j];
+    } else {
+        const uint32_t hi = (uint32_t)hethet[row + i];
+        for (int j = tid; j < n; j += 256) {
+            const uint32_t hj = (uint32_t)hethet[(long)j * n + j];
+            // int32 arithmetic (unsigned, so that it is defined): exact while 4 L < 2^31
+            const uint32_t dij = 4u * (uint32_t)ibs0[row + j] + hi + hj - 2u * (uint32_t)hethet[row + j];
+            knn_d[j] = j == i ? KNN_TAKEN : dij;
+        }
     }
     // every thread reads back only what it wrote: no barrier before the scan
     unsigned long long best = knn_scan(knn_d, n, tid);
@@ -97,6 +104,16 @@ __global__ __launch_bounds__(256) void k_knn_rows(const int32_t* __restrict__ ib
     for (int t = keff + tid; t < K; t += 256) nbr[(long)i * K + t] = -1;
 }
 
+__global__ __launch_bounds__(256) void k_knn_rows(const int32_t* __restrict__ ibs0, const int32_t* __restrict__ hethet, int n, int K, int keff,
+                                                  int32_t* __restrict__ nbr) {
+    knn_rows_body<false>(ibs0, hethet, n, K, keff, nbr);
+}
+// the same selection with the key's high dword read from dist (n x n uint32): a distance of 0xffffffff would read as taken, and
+// eagle_bed_sample_ibs writes none above 0xfffffffe
+__global__ __launch_bounds__(256) void k_knn_rows_dist(const uint32_t* __restrict__ dist, int n, int K, int keff, int32_t* __restrict__ nbr) {
+    knn_rows_body<true>((const int32_t*)dist, nullptr, n, K, keff, nbr);
+}
+
 extern "C" int eagle_dev_knn_rows(eagle_ctx* ctx, const int32_t* ibs0, const int32_t* hethet, long n, int K, int32_t* nbr, void* stream) {
     if (n <= 0 || n > EAGLE_KNN_MAX_N || K < 1 || K > EAGLE_KNN_MAX_K) return eagle_fail(ctx, EAGLE_ERR_ARG, "knn_rows: bad shape");
     if (!ctx->attr_knn_rows) {  // per device
@@ -106,6 +123,19 @@ extern "C" int eagle_dev_knn_rows(eagle_ctx* ctx, const int32_t* ibs0, const int
     }
     const int keff = (int)std::min((long)K, n - 1);
     hipLaunchKernelGGL(k_knn_rows, dim3((unsigned)n), dim3(256), (size_t)(4 * n), (hipStream_t)stream, ibs0, hethet, (int)n, K, keff, nbr);
+    IMP_LAUNCH_CHECK(ctx);
+    return EAGLE_OK;
+}
+
+extern "C" int eagle_dev_knn_rows_dist(eagle_ctx* ctx, const uint32_t* dist, long n, int K, int32_t* nbr, void* stream) {
+    if (n <= 0 || n > EAGLE_KNN_MAX_N || K < 1 || K > EAGLE_KNN_MAX_K) return eagle_fail(ctx, EAGLE_ERR_ARG, "knn_rows_dist: bad shape");
+    if (!ctx->attr_knn_rows_dist) {  // per device
+        hipError_t e = hipFuncSetAttribute((const void*)k_knn_rows_dist, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (int)EAGLE_KNN_MAX_N);
+        if (e != hipSuccess) return eagle_fail_hip(ctx, e, "hipFuncSetAttribute(k_knn_rows_dist)");
+        ctx->attr_knn_rows_dist = true;
+    }
+    const int keff = (int)std::min((long)K, n - 1);
+    hipLaunchKernelGGL(k_knn_rows_dist, dim3((unsigned)n), dim3(256), (size_t)(4 * n), (hipStream_t)stream, dist, (int)n, K, keff, nbr);
     IMP_LAUNCH_CHECK(ctx);
     return EAGLE_OK;
 }

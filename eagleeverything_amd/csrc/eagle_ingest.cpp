@@ -1324,6 +1324,89 @@ extern "C" int eagle_sample_ibs(eagle_ctx* ctx, const char* f_name_ascii_M, cons
     return eagle_ibs_counts(ctx, f_name_ascii_M, n, L, max_memory_in_Gbytes, host_threads(), ibs0_out, hethet_out);
 }
 
+// Pairwise-complete counts from the .bed file itself (include/eagle_hip.h section 1b'''ii).  The windows of eagle_bed_marker_counts
+// through the same staging ring -- cut further only where padding n to 256 rows would let one operand plane pass 128 MiB -- and per
+// window ONE k_bed_pack_fp4 launch that writes the four operand planes side by side into the ctx-owned operand buffer (at most 512 MiB),
+// then the four SYRKs into four accumulators that live for the whole call.  The window's marker count is padded to 256 with zero nibbles.
+extern "C" int eagle_bed_sample_ibs(eagle_ctx* ctx, const char* bed_path, const long dims[2], const uint8_t* include, int min_overlap,
+                                    double max_memory_in_Gbytes, int32_t* ncalled_out, int32_t* ibs0_out, int32_t* hethet_out,
+                                    int32_t* hetsum_out, uint32_t* dist_out) {
+    if (!bed_path || !dims || !ncalled_out || !ibs0_out || !hethet_out || !hetsum_out) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_sample_ibs: NULL argument");
+    const long n = dims[0], L = dims[1];
+    if (n <= 0 || L <= 0) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_sample_ibs: dims must be positive");
+    if (L >= (1L << 29)) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_sample_ibs: 2^29 markers or more");
+    if (min_overlap < 1) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_sample_ibs: min_overlap must be at least 1");
+    if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_sample_ibs: no context");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int fdin = -1;
+    if (int orc = open_bed(ctx, bed_path, n, L, &fdin)) return orc;
+    struct Closer { int fd; ~Closer() { if (fd >= 0) close(fd); } } closer{fdin};
+    const int threads = host_threads();
+    const long rb = bed_row_bytes(n), np = eagle_pad(n);
+    double cap = 67108864.0;
+    if (max_memory_in_Gbytes > 0) cap = std::min(cap, max_memory_in_Gbytes * 1e9 / 4.0);  // the loaders' staging rule
+    const long wplane = std::max(256L, (long)(((size_t)1 << 28) / (size_t)np) / 256 * 256);   // markers of a 128 MiB operand plane
+    const long w = std::max(1L, std::min(std::min(L, wplane), (long)cap / rb));
+    int rc = eagle_stage_ensure(ctx, (size_t)w * rb);
+    if (rc) return rc;
+    const long wp = eagle_pad(w), ld4 = wp / 2;
+    const size_t plane = (size_t)np * (size_t)ld4, accn = (size_t)np * np;
+    uint8_t* m4 = (uint8_t*)eagle_ctx_f4_buffer(ctx, 4 * plane);
+    if (!m4) return EAGLE_ERR_HIP;
+    DevBuf acc, dinc;
+    HIPCHK(ctx, acc.alloc(sizeof(int32_t) * 4 * accn));
+    HIPCHK(ctx, hipMemsetAsync(acc.p, 0, sizeof(int32_t) * 4 * accn, ctx->stream));
+    long linc = L;
+    if (include) {
+        linc = 0;
+        for (long m = 0; m < L; m++) linc += include[m] != 0;
+        HIPCHK(ctx, dinc.alloc((size_t)L));
+        HIPCHK(ctx, hipMemcpyAsync(dinc.p, include, (size_t)L, hipMemcpyHostToDevice, ctx->stream));
+    }
+    hipEvent_t done[2] = {nullptr, nullptr};
+    for (int b = 0; b < 2; b++) HIPCHK(ctx, hipEventCreateWithFlags(&done[b], hipEventDisableTiming));
+    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int b = 0; b < 2; b++) if (e[b]) (void)hipEventDestroy(e[b]); } } evg{done};
+    long k = 0;
+    for (long r0 = 0; r0 < L; r0 += w, k++) {
+        const int b = (int)(k & 1);
+        const long nr = std::min(w, L - r0), nrp = eagle_pad(nr);
+        if (k >= 2) HIPCHK(ctx, hipEventSynchronize(done[b]));  // window k - 2 has left staging buffer b
+        if (!pread_all(fdin, (char*)ctx->stage_pin[b], (size_t)nr * rb, (off_t)BED_HEADER_BYTES + (off_t)r0 * rb, threads)) {
+            (void)hipStreamSynchronize(ctx->stream);
+            return failf(ctx, EAGLE_ERR_FORMAT, "%s: could not read markers %ld to %ld", bed_path, r0 + 1, r0 + nr);
+        }
+        HIPCHK(ctx, hipMemcpyAsync(ctx->stage_raw[b], ctx->stage_pin[b], (size_t)nr * rb, hipMemcpyHostToDevice, ctx->stream));
+        rc = eagle_dev_bed_pack_fp4(ctx, (const uint8_t*)ctx->stage_raw[b], nr, n, include ? dinc.as<uint8_t>() + r0 : nullptr, np, nrp, m4, ld4,
+                                    (long)plane, ctx->stream);
+        HIPCHK(ctx, hipEventRecord(done[b], ctx->stream));     // the staging buffer is free once the pack has read it
+        for (int p = 0; p < 4 && !rc; p++)
+            rc = eagle_dev_mmt_accumulate_f4(ctx, m4 + (size_t)p * plane, np, nrp, ld4, acc.as<int32_t>() + (size_t)p * accn, ctx->stream);
+        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    }
+    rc = eagle_bed_ibs_results(ctx, acc.as<int32_t>(), n, linc, min_overlap, ncalled_out, ibs0_out, hethet_out, hetsum_out, dist_out);
+    if (rc) (void)hipStreamSynchronize(ctx->stream);
+    return rc;
+}
+
+extern "C" int eagle_knn_rows_dist(eagle_ctx* ctx, const uint32_t* dist, long n, int K, int32_t* nbr_out) {
+    if (!dist || !nbr_out) return qc_fail(ctx, EAGLE_ERR_ARG, "knn_rows_dist: NULL argument");
+    if (n <= 0) return qc_fail(ctx, EAGLE_ERR_ARG, "knn_rows_dist: n must be positive");
+    if (n > EAGLE_KNN_MAX_N) return qc_fail(ctx, EAGLE_ERR_ARG, "knn_rows_dist: more than EAGLE_KNN_MAX_N individuals");
+    if (K < 1 || K > EAGLE_KNN_MAX_K) return qc_fail(ctx, EAGLE_ERR_ARG, "knn_rows_dist: K outside [1, 256]");
+    if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "knn_rows_dist: no context");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t mb = sizeof(uint32_t) * (size_t)n * (size_t)n, nb = sizeof(int32_t) * (size_t)n * (size_t)K;
+    DevBuf dd, dn;
+    HIPCHK(ctx, dd.alloc(mb));
+    HIPCHK(ctx, dn.alloc(nb));
+    HIPCHK(ctx, hipMemcpyAsync(dd.p, dist, mb, hipMemcpyHostToDevice, ctx->stream));
+    int rc = eagle_dev_knn_rows_dist(ctx, dd.as<uint32_t>(), n, K, dn.as<int32_t>(), ctx->stream);
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    HIPCHK(ctx, hipMemcpyAsync(nbr_out, dn.p, nb, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return EAGLE_OK;
+}
+
 extern "C" int eagle_hwe_exact(eagle_ctx* ctx, const int32_t* counts, long L, int stride, double* p_out) {
     if (!counts || !p_out) return qc_fail(ctx, EAGLE_ERR_ARG, "hwe_exact: NULL argument");
     if (L <= 0) return qc_fail(ctx, EAGLE_ERR_ARG, "hwe_exact: the number of markers must be positive");

@@ -389,14 +389,60 @@ def impute_knn_host(codes, nbr, k, min_votes):
     return pack_bed_codes(out), counts
 
 
-def ImputeBed(bed, geno, out_prefix, k=10, K=64, min_votes=1, availmemGb=8, message=None, device=0):
+DIST_NO_OVERLAP = 0xFFFFFFFE
+
+
+def _bed_include_mask(include, L, who):
+    """None, a bool mask of length L or a list of 0-based marker indices -> None or a bool mask of length L."""
+    if include is None:
+        return None
+    a = np.atleast_1d(np.asarray(include)).ravel()
+    if a.dtype == bool:
+        if a.size != L:
+            raise ValueError("%s: the include mask holds %d entries, the .bed file %d markers" % (who, a.size, L))
+        return a.copy()
+    idx = a.astype(np.int64)
+    if not np.array_equal(idx, a) or (idx.size and (idx.min() < 0 or idx.max() >= L)):
+        raise ValueError("%s: include must be a bool mask or whole marker indices in [0, %d)" % (who, L))
+    m = np.zeros(L, dtype=bool)
+    m[idx] = True
+    return m
+
+
+def bed_ibs_host(codes, include=None, min_overlap=1):
+    """rcpp_api.bed_sample_ibs restated in numpy (include/eagle_hip.h section 1b'''ii): codes = uint8 (L, n) 2-bit codes (read_bed_codes),
+    include = None, a bool mask of length L or marker indices -> (ncalled, ibs0, hethet, hetsum, dist), int32 (n, n) x 4 and uint32
+    (n, n).  g = -1, 0, 0, +1, u = |g|, h = [code == 2], c = [code != 1] per genotype, zero at excluded markers; D = g g^T, Q = u u^T,
+    H = h h^T, N = c c^T; ncalled = N, ibs0 = (Q - D) / 2, hethet = H, hetsum = H + N - Q; dist = (4 ibs0 + hetsum - 2 hethet) * Linc
+    // N, DIST_NO_OVERLAP where N < min_overlap."""
+    codes = np.asarray(codes, dtype=np.uint8)
+    L = codes.shape[0]
+    min_overlap = int(min_overlap)
+    if min_overlap < 1:
+        raise ValueError("bed_ibs_host: min_overlap must be at least 1")
+    inc = _bed_include_mask(include, L, "bed_ibs_host")
+    if inc is not None:
+        codes = codes[inc]
+    linc = codes.shape[0]
+    g = np.array([-1.0, 0.0, 0.0, 1.0])[codes]            # fp64 products of 0 / +-1 summed over L < 2^53 markers: exact integers
+    u, h, c = np.abs(g), (codes == 2).astype(np.float64), (codes != 1).astype(np.float64)
+    D, Q, H, N = (np.rint(x.T @ x).astype(np.int64) for x in (g, u, h, c))
+    ibs0, hetsum = (Q - D) // 2, H + N - Q
+    d = 4 * ibs0 + hetsum - 2 * H
+    dist = np.where(N >= min_overlap, d * linc // np.maximum(N, 1), DIST_NO_OVERLAP).astype(np.uint32)
+    return N.astype(np.int32), ibs0.astype(np.int32), H.astype(np.int32), hetsum.astype(np.int32), dist
+
+
+def ImputeBed(bed, geno, out_prefix, k=10, K=64, min_votes=1, availmemGb=8, message=None, device=0, pairwise=False, min_overlap=1):
     """kNN imputation of the missing genotypes of a PLINK binary fileset -> {"bed": the new .bed file, "n_missing", "by_vote",
     "by_fallback": totals, "counts": int32 (L, 2) per marker}.  bed = the .bed file (or prefix) that `geno` was ingested from.
     The neighbours come from the ingested panel (rcpp_api.sample_ibs on geno["asciifileM"], knn_distance, rcpp_api.knn_rows: the K
     nearest individuals genome-wide, missing genotypes counted as the heterozygotes ingestion made of them); every missing genotype
     then takes the rounded mean dosage of the first k of them that are called at its marker (rcpp_api.bed_impute_knn; the marker's
-    own mean with fewer than min_votes voters).  Writes <out_prefix>.bed and byte-for-byte copies of the .bim and .fam; the new
-    fileset has no missing code and ReadMarker(type="PLINKbed") ingests it."""
+    own mean with fewer than min_votes voters).  pairwise=True ranks the neighbours by the .bed file's own pairwise-complete distance
+    instead (rcpp_api.bed_sample_ibs, rcpp_api.knn_rows_dist: every pair is compared over the markers where both are called, at
+    least min_overlap of them, so shared missingness does not make two individuals look alike).  Writes <out_prefix>.bed and
+    byte-for-byte copies of the .bim and .fam; the new fileset has no missing code and ReadMarker(type="PLINKbed") ingests it."""
     say = message or (lambda s: None)
     src_bed, src_bim, src_fam = bed_fileset(bed)
     n, L = int(geno["dim_of_ascii_M"][0]), int(geno["dim_of_ascii_M"][1])
@@ -405,8 +451,12 @@ def ImputeBed(bed, geno, out_prefix, k=10, K=64, min_votes=1, availmemGb=8, mess
         raise ValueError("ImputeBed: out_prefix names the input fileset")
     K = max(1, min(int(K), KNN_MAX_K))
     k = max(1, min(int(k), K))
-    ibs0, hethet = rcpp_api.sample_ibs(geno["asciifileM"], (n, L), availmemGb, device=device)
-    nbr = rcpp_api.knn_rows(ibs0, hethet, K, device=device)
+    if pairwise:
+        dist = rcpp_api.bed_sample_ibs(src_bed, (n, L), None, int(min_overlap), availmemGb, device=device)[4]
+        nbr = rcpp_api.knn_rows_dist(dist, K, device=device)
+    else:
+        ibs0, hethet = rcpp_api.sample_ibs(geno["asciifileM"], (n, L), availmemGb, device=device)
+        nbr = rcpp_api.knn_rows(ibs0, hethet, K, device=device)
     os.makedirs(os.path.dirname(os.path.abspath(out_bed)), exist_ok=True)
     counts = rcpp_api.bed_impute_knn(src_bed, (n, L), nbr, k, int(min_votes), out_bed, availmemGb, device=device)
     for src, dst in ((src_bim, out_bim), (src_fam, out_fam)):
@@ -623,6 +673,16 @@ def king_from_counts(ibs0, hethet):
         return np.where(den != 0.0, num / np.where(den != 0.0, den, 1.0), np.nan)
 
 
+def king_from_pair_counts(ibs0, hethet, hetsum):
+    """KING-robust kinship over the markers where both individuals are called, from rcpp_api.bed_sample_ibs' (or bed_ibs_host's) integer
+    matrices -> fp64 (n, n), pure numpy: phi_ij = (double)(hethet_ij - 2 ibs0_ij) / (double)hetsum_ij, NaN where hetsum_ij = 0.  Two
+    copies of one individual are 0.5 exactly, whatever genotypes are missing in either."""
+    a, hh, hs = np.asarray(ibs0, dtype=np.int64), np.asarray(hethet, dtype=np.int64), np.asarray(hetsum, dtype=np.int64)
+    num, den = (hh - 2 * a).astype(np.float64), hs.astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(den != 0.0, num / np.where(den != 0.0, den, 1.0), np.nan)
+
+
 KING_DEGREES = (("duplicate", 0.354), ("first", 0.177), ("second", 0.0884), ("third", 0.0442))
 
 
@@ -635,20 +695,40 @@ def king_degree(phi):
     return out
 
 
-def Relatedness(geno, threshold=0.0884, availmemGb=8, device=0):
+def Relatedness(geno, threshold=0.0884, availmemGb=8, device=0, bed=None, include=None, min_overlap=1):
     """Duplicated and closely related individuals of a panel -> {"kinship": fp64 (n, n) KING-robust phi (king_from_counts),
     "pairs": int64 (k, 2), 0-based, i < j, sorted: the pairs with phi > threshold (a NaN pair is never one), "phi": their phi,
     "degree": king_degree of it, "ibs0", "hethet": the integer matrices}.  The counts come from the device (rcpp_api.sample_ibs: two
     exact Gram products on the fp4 MFMA over all markers of geno["asciifileM"]); missing genotypes count as heterozygotes, so impute
-    them first (ImputeBed, ReadMarker(impute=)) or drop low-call-rate individuals (SampleStats(bed=), sample_keep_mask).
+    them first (ImputeBed, ReadMarker(impute=)) or drop low-call-rate individuals (SampleStats(bed=), sample_keep_mask) -- or give
+    bed = the .bed file (or prefix) the panel was ingested from: the counts then come from the file itself, every pair over the markers
+    where both are called (rcpp_api.bed_sample_ibs, king_from_pair_counts; a pair with fewer than min_overlap such markers is NaN), and
+    the dict also carries "ncalled" and "hetsum".  include = the markers of the .bed file that `geno` holds (a bool mask or 0-based
+    indices, e.g. FilterMarkers' or LDPrune's keep-list) when geno is a filtered panel; without it the marker counts must agree.
     related_drop chooses whom to drop."""
     n, L = int(geno["dim_of_ascii_M"][0]), int(geno["dim_of_ascii_M"][1])
-    ibs0, hethet = rcpp_api.sample_ibs(geno["asciifileM"], (n, L), availmemGb, device=device)
-    phi = king_from_counts(ibs0, hethet)
+    extra = {}
+    if bed is None:
+        ibs0, hethet = rcpp_api.sample_ibs(geno["asciifileM"], (n, L), availmemGb, device=device)
+        phi = king_from_counts(ibs0, hethet)
+    else:
+        src_bed, src_bim, _ = bed_fileset(bed)
+        Lbed = _count_lines(src_bim) if os.path.isfile(src_bim) else (os.path.getsize(src_bed) - 3) // ((n + 3) // 4)
+        if include is None and Lbed != L:
+            raise ValueError("Relatedness: %s holds %d markers, the panel %d: give include=, the panel's markers in the .bed file" % (src_bed, Lbed, L))
+        inc = _bed_include_mask(include, Lbed, "Relatedness")
+        if inc is not None and int(inc.sum()) != L:
+            raise ValueError("Relatedness: include names %d markers, the panel holds %d" % (int(inc.sum()), L))
+        ncalled, ibs0, hethet, hetsum, _ = rcpp_api.bed_sample_ibs(src_bed, (n, Lbed), inc, int(min_overlap), availmemGb, device=device)
+        phi = king_from_pair_counts(ibs0, hethet, hetsum)
+        phi[ncalled < int(min_overlap)] = np.nan
+        extra = {"ncalled": ncalled, "hetsum": hetsum}
     with np.errstate(invalid="ignore"):
         i, j = np.nonzero(np.triu(phi > float(threshold), k=1))
     pairs = np.stack([i, j], axis=1).astype(np.int64).reshape(-1, 2)
-    return {"kinship": phi, "pairs": pairs, "phi": phi[i, j], "degree": king_degree(phi[i, j]), "ibs0": ibs0, "hethet": hethet}
+    out = {"kinship": phi, "pairs": pairs, "phi": phi[i, j], "degree": king_degree(phi[i, j]), "ibs0": ibs0, "hethet": hethet}
+    out.update(extra)
+    return out
 
 
 def related_drop(pairs, n, priority=None):

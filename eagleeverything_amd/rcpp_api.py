@@ -695,6 +695,44 @@ def knn_rows(ibs0, hethet, K, device=0):
     return out
 
 
+DIST_NO_OVERLAP = 0xFFFFFFFE    # bed_sample_ibs' dist of a pair with fewer than min_overlap markers where both are called
+
+
+def bed_sample_ibs(bed_path, dims, include=None, min_overlap=1, max_memory_in_Gbytes=8.0, device=0):
+    """eagle_bed_sample_ibs -> (ncalled, ibs0, hethet, hetsum, dist): int32 (n, n) x 4 and uint32 (n, n), the pairwise-complete counts
+    of include/eagle_hip.h section 1b'''ii from a SNP-major PLINK .bed file of dims = (n individuals, L markers) -- for every pair the
+    markers where both are called, where they are opposite homozygotes, where both are heterozygous, the heterozygous genotypes of
+    either where the other is called -- and the distance sum (g_i - g_j)^2 over the both-called markers scaled to the included markers
+    (DIST_NO_OVERLAP below min_overlap).  include: None, or a bool / 0-1 mask of length L; r_api.bed_ibs_host is the numpy restatement."""
+    L = _lib.load()
+    n, nm = int(dims[0]), int(dims[1])
+    inc = None
+    if include is not None:
+        inc = np.ascontiguousarray(np.atleast_1d(np.asarray(include)).ravel() != 0, dtype=np.uint8)
+        if inc.size != nm:
+            raise ValueError("bed_sample_ibs: include holds %d entries, the file %d markers" % (inc.size, nm))
+    out = [np.zeros((max(n, 0), max(n, 0)), dtype=np.int32) for _ in range(4)]
+    dist = np.zeros((max(n, 0), max(n, 0)), dtype=np.uint32)
+    _args_first(L.eagle_bed_sample_ibs, device, (os.fsencode(bed_path), _dims(dims), inc.ctypes.data_as(C.c_void_p) if inc is not None else None,
+                                                 int(min_overlap), float(max_memory_in_Gbytes), out[0].ctypes.data_as(_c_i32p),
+                                                 out[1].ctypes.data_as(_c_i32p), out[2].ctypes.data_as(_c_i32p), out[3].ctypes.data_as(_c_i32p),
+                                                 dist.ctypes.data_as(C.c_void_p)))
+    return out[0], out[1], out[2], out[3], dist
+
+
+def knn_rows_dist(dist, K, device=0):
+    """eagle_knn_rows_dist -> int32 (n, K): row i = the min(K, n - 1) individuals j != i with the smallest dist_ij, nearest first, ties
+    to the smaller index; -1 beyond them.  dist: the uint32 (n, n) matrix of bed_sample_ibs."""
+    L = _lib.load()
+    m = np.asarray(dist)
+    d = np.ascontiguousarray(m, dtype=np.uint32)
+    if d.ndim != 2 or d.shape[0] != d.shape[1] or not np.array_equal(d, m):
+        raise ValueError("knn_rows_dist: dist must be a square matrix of whole numbers that fit uint32")
+    out = np.zeros((d.shape[0], max(int(K), 1)), dtype=np.int32)
+    _args_first(L.eagle_knn_rows_dist, device, (d.ctypes.data_as(C.c_void_p), d.shape[0], int(K), out.ctypes.data_as(_c_i32p)))
+    return out
+
+
 def bed_impute_knn(bed_path, dims, nbr, k, min_votes, out_bed_path, max_memory_in_Gbytes=8.0, device=0):
     """eagle_bed_impute_knn -> int32 (L, 2): the genotypes of every marker imputed by vote and by fallback.  Writes out_bed_path, the
     SNP-major .bed file bed_path (dims = (n individuals, L markers)) with every missing genotype filled from the first k called

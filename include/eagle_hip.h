@@ -424,6 +424,57 @@ int eagle_bed_impute_knn(eagle_ctx* ctx, const char* bed_path, const long dims[2
                          const char* out_bed_path, double max_memory_in_Gbytes, int32_t* counts_out);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1b'''ii. Pairwise-complete IBS counts, KING kinship and kNN distances from the .bed file (no counterpart in the reference).  The
+ *     ingested panel has made every missing genotype a heterozygote, so section 1b''' counts a pair's missing calls as shared or
+ *     unshared heterozygotes.  Here a marker counts for a pair only where BOTH individuals are called, as in PLINK --make-king and
+ *     KING: the .bed file is read itself, where the missing code is still known.
+ *
+ *     Codes as in 1b'''i: 0 = homozygous A1, 1 = missing, 2 = heterozygous, 3 = homozygous A2.  Per individual i and marker m:
+ *         g = -1, 0, 0, +1 for the codes 0, 1, 2, 3;    u = |g|;    h = [code == 2];    c = [code != 1].
+ *     An optional include[m] (one byte per marker; zero = excluded) zeroes all four at the excluded markers.  The unused bit pairs of
+ *     a row's last byte belong to nobody, whatever bits they hold.
+ *
+ *     Four Gram products over the included markers, int32 and symmetric, each one exact product on the fp4 MFMA (k_syrk_f4*):
+ *         D = g g^T,    Q = u u^T,    H = h h^T,    N = c c^T.
+ *     Results, n x n int32 each, row-major:
+ *         ncalled_ij = N_ij                    markers where both are called (diagonal: i's called genotypes)
+ *         ibs0_ij    = (Q_ij - D_ij) / 2       both called, opposite homozygotes (diagonal 0)
+ *         hethet_ij  = H_ij                    both heterozygous (diagonal h_i)
+ *         hetsum_ij  = H_ij + N_ij - Q_ij      heterozygous genotypes of i where j is called plus those of j where i is called
+ *                                              (N - Q counts the both-called markers with at least one heterozygote; diagonal 2 h_i)
+ *
+ *     Kinship is the caller's fp64 arithmetic (r_api.king_from_pair_counts):
+ *         phi_ij = (double)(hethet_ij - 2 ibs0_ij) / (double)hetsum_ij,   NaN where hetsum_ij == 0;
+ *     two copies of one individual have phi = 0.5 exactly, whatever their missing patterns.
+ *
+ *     Distance for the neighbour table:  d_ij = 4 ibs0_ij + hetsum_ij - 2 hethet_ij = the sum of (g_i - g_j)^2 over the both-called
+ *     markers, normalised to the panel length:
+ *         dist_ij = (uint32)((int64)d_ij * Linc / N_ij)   (integer division; Linc = the number of included markers)
+ *         dist_ij = 0xFFFFFFFE                            where N_ij < min_overlap (min_overlap >= 1)
+ *     The diagonal is written by the same rule and not used.  L < 2^29 keeps every term in range.
+ *
+ *     Single device: a multi-device context works on its first device.  Argument errors (EAGLE_ERR_ARG: a NULL pointer, dims <= 0,
+ *     and those named below) are decided before the context is used; with ctx == NULL their text is in eagle_open_error().
+ * ------------------------------------------------------------------------------------------- */
+
+/* ncalled_out, ibs0_out, hethet_out, hetsum_out: n x n int32 each; dist_out: n x n uint32 or NULL; as defined above, from the
+ * SNP-major .bed file bed_path (the format, the checks and the error codes of eagle_create_ascii_from_bed; dims = (n, L)).  include:
+ * L bytes or NULL (every marker).  The rows go through the pinned staging ring in the windows of eagle_bed_marker_counts (cut further
+ * only where padding n to 256 rows would make one operand plane pass 128 MiB); per window k_bed_pack_fp4 writes the four
+ * individual-major fp4 operand images from one read of the rows (the window's marker count padded to a multiple of 256 with zero
+ * nibbles) and four SYRKs add to four int32 accumulators, so the result does not depend on the window size; k_bed_ibs_finish makes
+ * the results.  EAGLE_ERR_ARG: L >= 2^29, min_overlap < 1. */
+int eagle_bed_sample_ibs(eagle_ctx* ctx, const char* bed_path, const long dims[2], const uint8_t* include, int min_overlap,
+                         double max_memory_in_Gbytes, int32_t* ncalled_out, int32_t* ibs0_out, int32_t* hethet_out, int32_t* hetsum_out,
+                         uint32_t* dist_out);
+
+/* eagle_knn_rows with the key's high dword read from dist (n x n uint32, row-major: eagle_bed_sample_ibs' dist_out): row i of nbr_out
+ * holds the min(K, n - 1) individuals j != i with the smallest keys (uint64)dist_ij << 32 | j in increasing order, then -1.  A pair
+ * below min_overlap (0xFFFFFFFE) comes after every other.  A dist of 0xFFFFFFFF is not a distance (the kernel's own mark): -1 is
+ * written in its place at the end of the row.  EAGLE_ERR_ARG: n > EAGLE_KNN_MAX_N, K outside [1, EAGLE_KNN_MAX_K]. */
+int eagle_knn_rows_dist(eagle_ctx* ctx, const uint32_t* dist, long n, int K, int32_t* nbr_out);
+
+/* ---------------------------------------------------------------------------------------------
  * 1b''''. Genomic relationship matrix (no counterpart that the reference calls: its VanRaden G, E/R/GenomicRel.R, is unused): the one
  *     Gram product the matrices of EIGENSTRAT / PLINK / GCTA and their principal components need, with a weight per marker.  With
  *     g in {-1, 0, +1} = AA, AB, BB as everywhere in this library and integer weights q_m < 2^21,
