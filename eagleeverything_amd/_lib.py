@@ -64,6 +64,10 @@ SIGNATURES = {
     "eagle_bed_sample_ibs": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, C.c_void_p, C.c_int, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                        C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]),
     "eagle_knn_rows_dist": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.POINTER(C.c_int32)]),
+    "eagle_ld_partners": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, C.c_long, C.c_int, C.c_double, C.POINTER(C.c_int32), C.c_double,
+                                    C.POINTER(C.c_int32), c_dp]),
+    "eagle_bed_impute_ldknn": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p,
+                                         C.c_double, C.POINTER(C.c_int32)]),
     "eagle_weighted_gram": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, C.POINTER(C.c_uint32), C.c_double, C.POINTER(C.c_int64)]),
     "eagle_read_block": (C.c_int, [C.c_void_p, C.c_char_p, C.c_long, C.c_long, C.c_long, c_dp]),
     "eagle_calculateMMt": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double, C.c_int, c_dp, C.c_long, c_lp, C.c_int, c_dp]),

@@ -106,7 +106,7 @@ struct eagle_ctx {
     void* stage_pin[2] = {nullptr, nullptr}; void* stage_raw[2] = {nullptr, nullptr}; size_t stage_cap = 0;  // tile streamer
     // per-device launch state (a process may hold one ctx per GPU): dynamic-LDS attributes set on this device, schedule
     // experiment switch of tools/bench_i8_engine.py (0 = shipped)
-    bool attr_vara_i8 = false, attr_vara_i8w = false, attr_vara_i8p = false, attr_vara_i8pp = false, attr_vara_i8px = false, attr_syrk_f4w = false, attr_zbuild_i8 = false, attr_vara_f6 = false, attr_gemv = false, attr_w8_gemm = false, attr_knn_rows = false, attr_knn_rows_dist = false;
+    bool attr_vara_i8 = false, attr_vara_i8w = false, attr_vara_i8p = false, attr_vara_i8pp = false, attr_vara_i8px = false, attr_syrk_f4w = false, attr_zbuild_i8 = false, attr_vara_f6 = false, attr_gemv = false, attr_w8_gemm = false, attr_knn_rows = false, attr_knn_rows_dist = false, attr_ldknn = false;
     int tune = 0;
     // W = S (V S) on the int8 engine (eagle_w8.hip): workspace, and what the last call left for the scan that follows it
     int w_mode = 1;            // 0 = always the fp64 GEMM, 1 = int8 digit slices from 4,096 padded individuals up, 2 = int8 at any size (tests)
@@ -216,6 +216,13 @@ extern "C" int eagle_dev_knn_rows(eagle_ctx* ctx, const int32_t* ibs0, const int
 extern "C" int eagle_dev_knn_rows_dist(eagle_ctx* ctx, const uint32_t* dist, long n, int K, int32_t* nbr, void* stream);
 extern "C" int eagle_dev_bed_impute(eagle_ctx* ctx, const uint8_t* bed, long rows, long n, const int32_t* nbr, int K, int k, int min_votes,
                                     const int32_t* mcounts, uint8_t* out, int32_t* counts, void* stream);
+// LD-kNNi (eagle_ldknn.hip; the header's section on LD-kNNi), device pointers throughout.  `bed` holds `staged` raw rows from marker h_lo of the
+// file on; the `rows` rows from row `first` of them (marker m0 = h_lo + first) are patched into out, counts[rows][2] = (by vote, by
+// fallback), mcounts[rows][4] their counts.  partners = L x l by the file's marker; the CALLER has checked that every entry of the rows
+// patched is -1 or names a staged row: the kernel indexes the staged rows with them.
+extern "C" int eagle_dev_bed_impute_ldknn(eagle_ctx* ctx, const uint8_t* bed, long staged, long first, long rows, long m0, long h_lo, long n,
+                                          const int32_t* partners, int l, int k, int min_votes, int min_overlap, const int32_t* mcounts,
+                                          uint8_t* out, int32_t* counts, void* stream);
 // Pairwise-complete IBS counts from a .bed file (eagle_bedibs.hip; include/eagle_hip.h section 1b'''ii), device pointers throughout.  The
 // four fp4 operand images (g, u, h, c; plane p at M4 + p * plane_bytes, n_pad rows of ld4 bytes, L_pad markers written) of `rows` raw
 // .bed rows, `include` one byte per row or null; the four n x n int32 results and dist (or null) from the four Gram accumulators

@@ -1010,6 +1010,95 @@ extern "C" int eagle_bed_impute_knn(eagle_ctx* ctx, const char* bed_path, const 
     return EAGLE_OK;
 }
 
+// LD-kNNi (kernel in eagle_ldknn.hip).  The ring and the write-behind of eagle_bed_impute_knn; the rows staged for window [r0, r0 + nr) are
+// [max(0, r0 - 256), min(L, r0 + nr + 256)): every partner of every marker of the window (checked below to lie within 256 rows of it) is
+// among them.  The halo is read again with the next window -- from the page cache -- so that a window is one pread and one upload.
+#define LDKNN_HALO 256L
+extern "C" int eagle_bed_impute_ldknn(eagle_ctx* ctx, const char* bed_path, const long dims[2], const int32_t* partners, int l, int k, int min_votes,
+                                      int min_overlap, const char* out_bed_path, double max_memory_in_Gbytes, int32_t* counts_out) {
+    if (!bed_path || !dims || !partners || !out_bed_path) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_impute_ldknn: NULL argument");
+    const long n = dims[0], L = dims[1];
+    if (n <= 0 || L <= 0 || L > 0x7fffffffL) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_impute_ldknn: dims must be positive (L below 2^31)");
+    if (n > EAGLE_LDKNN_MAX_N) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_impute_ldknn: more than EAGLE_LDKNN_MAX_N individuals");
+    if (l < 1 || l > EAGLE_LDKNN_MAX_PARTNERS) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_impute_ldknn: l outside [1, 32]");
+    if (k < 1 || k > EAGLE_LDKNN_MAX_K) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_impute_ldknn: k outside [1, 64]");
+    if (min_votes < 1) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_impute_ldknn: min_votes must be at least 1");
+    if (min_overlap < 1 || min_overlap > EAGLE_LDKNN_MAX_PARTNERS) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_impute_ldknn: min_overlap outside [1, 32]");
+    if (std::string(bed_path) == out_bed_path) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_impute_ldknn: the output file must differ from the input file");
+    for (long m = 0; m < L; m++)
+        for (int t = 0; t < l; t++) {
+            const long p = partners[(size_t)m * (size_t)l + (size_t)t];
+            if (p < -1 || p >= L) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_impute_ldknn: a partner outside [-1, L)");
+            if (p >= 0 && (p - m > LDKNN_HALO || m - p > LDKNN_HALO))
+                return qc_fail(ctx, EAGLE_ERR_ARG, "bed_impute_ldknn: a partner more than 256 rows from its marker");
+        }
+    if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_impute_ldknn: no context");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int fdin = -1;
+    if (int orc = open_bed(ctx, bed_path, n, L, &fdin)) return orc;
+    struct Closer { int fd; ~Closer() { if (fd >= 0) close(fd); } } closer{fdin};
+    const int threads = host_threads();
+    const long rb = bed_row_bytes(n);
+    double cap = 67108864.0;
+    if (max_memory_in_Gbytes > 0) cap = std::min(cap, max_memory_in_Gbytes * 1e9 / 4.0);  // the loaders' staging rule
+    const long w = std::max(1L, std::min(L, (long)cap / rb));
+    const long wmax = std::min(L, w + 2 * LDKNN_HALO);                                     // rows staged for a window, at most
+    int rc = eagle_stage_ensure(ctx, (size_t)wmax * rb);
+    if (rc) return rc;
+    const size_t np = (size_t)L * (size_t)l;
+    DevBuf d_part, mcounts, counts, patched;
+    HIPCHK(ctx, d_part.alloc(sizeof(int32_t) * np));
+    HIPCHK(ctx, mcounts.alloc(sizeof(int32_t) * 4 * (size_t)w));
+    HIPCHK(ctx, counts.alloc(sizeof(int32_t) * 2 * (size_t)L));
+    HIPCHK(ctx, patched.alloc((size_t)w * rb));
+    HIPCHK(ctx, hipMemcpyAsync(d_part.p, partners, sizeof(int32_t) * np, hipMemcpyHostToDevice, ctx->stream));
+    hipEvent_t done[2] = {nullptr, nullptr};
+    for (int b = 0; b < 2; b++) HIPCHK(ctx, hipEventCreateWithFlags(&done[b], hipEventDisableTiming));
+    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int b = 0; b < 2; b++) if (e[b]) (void)hipEventDestroy(e[b]); } } evg{done};
+    TextOut out;   // cut back to nothing unless the call gets as far as finish()
+    static const char head[BED_HEADER_BYTES] = {0x6c, 0x1b, 0x01};
+    if (!out.open_sized(out_bed_path, (off_t)bed_expected_size(n, L)) || !pwrite_all(out.fd, head, sizeof head, 0, 1))
+        return failf(ctx, EAGLE_ERR_OPEN, "ERROR: Could not open  %s", out_bed_path);
+    long pend_r = -1, pend_n = 0;
+    int pend_b = 0;
+    auto flush = [&]() -> int {
+        if (pend_r < 0) return EAGLE_OK;
+        hipError_t e = hipEventSynchronize(done[pend_b]);
+        if (e != hipSuccess) return eagle_fail_hip(ctx, e, "hipEventSynchronize");
+        if (!pwrite_all(out.fd, (const char*)ctx->stage_pin[pend_b], (size_t)pend_n * rb, (off_t)BED_HEADER_BYTES + (off_t)pend_r * rb, threads))
+            return failf(ctx, EAGLE_ERR_OPEN, "ERROR: could not write %s", out_bed_path);
+        pend_r = -1;
+        return EAGLE_OK;
+    };
+    long wk = 0;
+    for (long r0 = 0; r0 < L; r0 += w, wk++) {
+        const int b = (int)(wk & 1);  // free: window wk - 2 went to disk while window wk - 1 was enqueued
+        const long nr = std::min(w, L - r0);
+        const long h_lo = std::max(0L, r0 - LDKNN_HALO), h_hi = std::min(L, r0 + nr + LDKNN_HALO), staged = h_hi - h_lo;
+        if (!pread_all(fdin, (char*)ctx->stage_pin[b], (size_t)staged * rb, (off_t)BED_HEADER_BYTES + (off_t)h_lo * rb, threads)) {
+            (void)hipStreamSynchronize(ctx->stream);
+            return failf(ctx, EAGLE_ERR_FORMAT, "%s: could not read markers %ld to %ld", bed_path, h_lo + 1, h_hi);
+        }
+        const uint8_t* raw = (const uint8_t*)ctx->stage_raw[b];
+        HIPCHK(ctx, hipMemcpyAsync(ctx->stage_raw[b], ctx->stage_pin[b], (size_t)staged * rb, hipMemcpyHostToDevice, ctx->stream));
+        rc = eagle_dev_bed_marker_counts(ctx, raw + (r0 - h_lo) * rb, nr, n, mcounts.as<int32_t>(), ctx->stream);
+        if (!rc) rc = eagle_dev_bed_impute_ldknn(ctx, raw, staged, r0 - h_lo, nr, r0, h_lo, n, d_part.as<int32_t>(), l, k, min_votes, min_overlap,
+                                                 mcounts.as<int32_t>(), patched.as<uint8_t>(), counts.as<int32_t>() + 2 * r0, ctx->stream);
+        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+        HIPCHK(ctx, hipMemcpyAsync(ctx->stage_pin[b], patched.p, (size_t)nr * rb, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipEventRecord(done[b], ctx->stream));
+        rc = flush();
+        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+        pend_r = r0; pend_n = nr; pend_b = b;
+    }
+    rc = flush();
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    if (counts_out) HIPCHK(ctx, hipMemcpyAsync(counts_out, counts.p, sizeof(int32_t) * 2 * (size_t)L, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    out.finish();
+    return EAGLE_OK;
+}
+
 namespace {
 
 // One of the two output files of eagle_filter_markers: `rows` lines of `cols` characters with sidecar, made band by band of `band`
@@ -1190,6 +1279,66 @@ extern "C" int eagle_ld_window(eagle_ctx* ctx, const char* f_name_ascii_Mt, cons
     long pairs = 0;
     for (size_t x = 0; x < (size_t)L * (size_t)wpr; x++) pairs += __builtin_popcountll(mask_out[x]);
     *npairs_out = pairs;
+    return EAGLE_OK;
+}
+
+// Ranked partner lists.  The panel is worked on in CORE ranges of markers: the rows held for a core [c0, c1) are [max(0, c0 - window),
+// min(L, c1 + window)) -- all candidates of its markers on both sides -- the tile kernel writes the r^2 band of the rows held, and
+// k_ld_partners the partner rows of the core alone, so every output word is written once, from a band that held all of the marker's
+// candidates: the result does not depend on the cores' size.  A resident image is cut only where its band would pass 256 MiB; a file
+// that is not resident is read in row windows of the streamed scans' size (at least 1,024 rows: twice the widest overlap and a core).
+extern "C" int eagle_ld_partners(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long dims[2], long window, int l, double min_r2,
+                                 const int32_t* chrom, double max_memory_in_Gbytes, int32_t* partners_out, double* r2_out) {
+    if (!f_name_ascii_Mt || !dims || !partners_out) return qc_fail(ctx, EAGLE_ERR_ARG, "ld_partners: NULL argument");
+    const long n = dims[0], L = dims[1];
+    if (n <= 0 || L <= 0) return qc_fail(ctx, EAGLE_ERR_ARG, "ld_partners: dims must be positive");
+    if (L > 0x7fffffffL) return qc_fail(ctx, EAGLE_ERR_ARG, "ld_partners: 2^31 markers or more");
+    if (window < 1 || window > 256) return qc_fail(ctx, EAGLE_ERR_ARG, "ld_partners: window must be in [1, 256]");
+    if (l < 1 || l > EAGLE_LDKNN_MAX_PARTNERS) return qc_fail(ctx, EAGLE_ERR_ARG, "ld_partners: l outside [1, 32]");
+    if (!(min_r2 >= 0.0 && min_r2 <= 1.0)) return qc_fail(ctx, EAGLE_ERR_ARG, "ld_partners: min_r2 must be in [0, 1]");
+    if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "ld_partners: no context");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int threads = host_threads();
+    const size_t cells = (size_t)L * (size_t)l;
+    DevBuf part, r2, d_chrom, counts, sq, band, win;
+    HIPCHK(ctx, part.alloc(sizeof(int32_t) * cells));
+    HIPCHK(ctx, r2.alloc(sizeof(double) * cells));
+    if (chrom) {
+        HIPCHK(ctx, d_chrom.alloc(sizeof(int32_t) * (size_t)L));
+        HIPCHK(ctx, hipMemcpyAsync(d_chrom.p, chrom, sizeof(int32_t) * (size_t)L, hipMemcpyHostToDevice, ctx->stream));
+    }
+    const GenoEntry* src = nullptr;
+    int rc = eagle_get_resident(ctx, f_name_ascii_Mt, L, n, max_memory_in_Gbytes, threads, &src);
+    if (rc != EAGLE_OK && rc != EAGLE_STREAM) return rc;
+    const long ld = src ? src->ld : eagle_pad(n);
+    long held_max;   // rows held for a core, at most
+    if (src) held_max = std::max(1024L, (long)(((size_t)256 << 20) / (sizeof(double) * (size_t)window)));
+    else held_max = std::max(1024L, stream_chunk_rows_core(eagle_resident_budget(), ld, eagle_pad(L)));
+    held_max = std::min(held_max, L);
+    const long core = held_max >= L ? L : held_max - 2 * window;
+    if (!src) HIPCHK(ctx, win.alloc((size_t)held_max * ld));
+    HIPCHK(ctx, counts.alloc(sizeof(int32_t) * 3 * (size_t)held_max));
+    HIPCHK(ctx, sq.alloc(sizeof(int32_t) * 2 * (size_t)held_max));
+    HIPCHK(ctx, band.alloc(sizeof(double) * (size_t)held_max * (size_t)window));
+    for (long c0 = 0; c0 < L; c0 += core) {
+        const long c1 = std::min(L, c0 + core), lo = std::max(0L, c0 - window), hi = std::min(L, c1 + window), nr = hi - lo;
+        const int8_t* img;
+        if (src) img = src->dev + lo * ld;
+        else {
+            HIPCHK(ctx, hipMemsetAsync(win.p, 0, (size_t)held_max * ld, ctx->stream));
+            rc = eagle_dev_load_ascii(ctx, f_name_ascii_Mt, lo, nr, 0, n, win.as<int8_t>(), ld, max_memory_in_Gbytes, threads);
+            if (rc) return rc;
+            img = win.as<int8_t>();
+        }
+        rc = ld_tile_sq(ctx, img, nr, n, ld, counts.as<int32_t>(), sq.as<int32_t>());
+        if (!rc) rc = eagle_dev_ld_r2band(ctx, img, nr, n, ld, sq.as<int32_t>(), window, band.as<double>(), ctx->stream);
+        if (!rc) rc = eagle_dev_ld_partners(ctx, band.as<double>(), nr, window, c0 - lo, c1 - lo, lo, chrom ? d_chrom.as<int32_t>() : nullptr, min_r2, l,
+                                            part.as<int32_t>(), r2.as<double>(), ctx->stream);
+        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    }
+    HIPCHK(ctx, hipMemcpyAsync(partners_out, part.p, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, ctx->stream));
+    if (r2_out) HIPCHK(ctx, hipMemcpyAsync(r2_out, r2.p, sizeof(double) * cells, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return EAGLE_OK;
 }
 

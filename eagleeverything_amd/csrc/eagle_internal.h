@@ -87,6 +87,13 @@ int eagle_dev_ld_band(eagle_ctx* ctx, const int8_t* Mt8, long rows, long n, long
                       long words_per_row, void* stream);
 // dots[i * k + j] = sum over the individuals of marker i times row j of B8 (64 rows x ld, rows k .. 63 zero), 1 <= k <= 64
 int eagle_dev_ld_dots(eagle_ctx* ctx, const int8_t* Mt8, long rows, long n, long ld, const int8_t* B8, long k, int32_t* dots, void* stream);
+// band[i * window + o - 1] (rows x window fp64, every entry written) = r^2 between markers i and i + o of the tile in the fp64 order of
+// the header's LD-kNNi section, -1.0 where i + o >= rows or one of the two is monomorphic.
+int eagle_dev_ld_r2band(eagle_ctx* ctx, const int8_t* Mt8, long rows, long n, long ld, const int32_t* sq, long window, double* band, void* stream);
+// The ranked partner rows of the markers g0 + [c_lo, c_hi) of the panel from a band whose row 0 is marker g0 (a marker's candidates on
+// both sides must lie among the band's rows, or beyond the panel's ends).  partners / r2: L x l by the panel's marker; chrom: L or null.
+int eagle_dev_ld_partners(eagle_ctx* ctx, const double* band, long rows, long window, long c_lo, long c_hi, long g0, const int32_t* chrom,
+                          double min_r2, int l, int32_t* partners, double* r2, void* stream);
 #ifdef __cplusplus
 }
 #include "eagle_host.h"

@@ -1,5 +1,5 @@
 // eagle_ld.hip -- linkage disequilibrium between markers: integer dot products between rows of the int8 marker-major image on the int8
-// MFMA (v_mfma_i32_32x32x32_i8), in two modes of one tile kernel.  Every number below is an exact integer until the one fp64 test.
+// MFMA (v_mfma_i32_32x32x32_i8), in three modes of one tile kernel.  Every number below is an exact integer until the one fp64 test.
 //
 //   s_i = sum g, q_i = sum g^2 (from k_marker_counts: s = n2 - n0, q = n2 + n0), d_ij = sum g_i g_j (int32, the MFMA),
 //   c_ij = n d_ij - s_i s_j, v_i = n q_i - s_i^2 (int64);  r^2_ij = c^2 / (v_i v_j).
@@ -10,6 +10,12 @@
 //                                        in LD at t; mask is rows x ceil(window / 64) uint64 words.
 //   picks mode (k_ld_tile<2, true>) .... dots[i][j] = d between marker i and row j of a gathered image B8 of k <= 64 rows (64 x ld, zero rows
 //                                        beyond k; k_gather_rows_i8 makes it), int32 rows x k.
+//
+//   r2 mode (k_ld_tile<NB, false, true>) band[i * window + o - 1] = r^2 between markers i and i + o as an fp64 number,
+//                                        fl(fl((double)c * (double)c) / fl((double)v_i * (double)v_j)), or -1.0 where i + o >= rows or one of
+//                                        the two is monomorphic: the band mode's tile with another epilogue.  k_ld_partners then ranks, per
+//                                        marker, its forward entries and the backward entries of the `window` markers before it (include/
+//                                        eagle_hip.h section 1b'''iii).
 //
 // Tile.  A workgroup (256 threads, 4 waves) owns TM = 128 consecutive markers.  Per K chunk of 128 individuals it stages TB rows x 128 B
 // in LDS once: in band mode TB = 128 + 32 (NB - 1) rows of the SAME image from the tile's first row on, NB - 1 = pad32(window) / 32, so that
@@ -57,11 +63,12 @@ __global__ __launch_bounds__(256) void k_ld_sq(const int32_t* __restrict__ count
 }
 
 // kbytes = ceil16(n): the bytes of a row that hold individuals (the image is zero from n on).  B8 / ldB / k / dots: picks mode only;
-// sq / window / t / mask / wpr: band mode only.
-template <int NB, bool PICKS>
+// sq / window: band and r2 mode; t / mask / wpr: band mode only; band: r2 mode only (rows x window fp64).
+template <int NB, bool PICKS, bool R2 = false>
 __global__ __launch_bounds__(256) void k_ld_tile(const int8_t* __restrict__ Mt8, long rows, long n, long ld, long kbytes,
                                                  const int8_t* __restrict__ B8, long ldB, int k, const int32_t* __restrict__ sq, int window,
-                                                 double t, uint64_t* __restrict__ mask, int wpr, int32_t* __restrict__ dots) {
+                                                 double t, uint64_t* __restrict__ mask, int wpr, int32_t* __restrict__ dots,
+                                                 double* __restrict__ band) {
     constexpr int TB = PICKS ? LD_TM + 32 * NB : LD_TM + 32 * (NB - 1);
     constexpr int NCH = TB / 32;   // 16-byte pieces per thread and chunk: TB * 8 / 256
     __shared__ __attribute__((aligned(16))) int8_t tile[TB * LD_BK];
@@ -146,8 +153,35 @@ __global__ __launch_bounds__(256) void k_ld_tile(const int8_t* __restrict__ Mt8,
         sS[x] = s;
         sV[x] = v;
     }
-    for (int x = tid; x < LD_TM * 8; x += 256) sM[x] = 0u;
+    if (!R2)
+        for (int x = tid; x < LD_TM * 8; x += 256) sM[x] = 0u;
     __syncthreads();
+    if (R2) {
+        // every (i, o), i < rows, 1 <= o <= window, lies in exactly one block pair: each entry of the band is written once, by the 32
+        // lanes of a half wave as 32 consecutive doubles (o = jl - il runs with the lane)
+#pragma unroll
+        for (int b = 0; b < NB; b++) {
+            const int jl = 32 * (w + b) + r;
+            const int sj = sS[jl];
+            const long long vj = sV[jl];
+            const bool jok = row0 + jl < rows && vj > 0;
+#pragma unroll
+            for (int e = 0; e < 16; e++) {
+                const int il = 32 * w + (e & 3) + 8 * (e >> 2) + 4 * h, o = jl - il;
+                const long gi = row0 + il;
+                if (o < 1 || o > window || gi >= rows) continue;
+                const long long vi = sV[il];
+                double val = -1.0;
+                if (jok && vi > 0) {
+                    const long long c = (long long)n * acc[b][e] - (long long)sS[il] * sj;
+                    const double dc = (double)c;
+                    val = (dc * dc) / ((double)vi * (double)vj);
+                }
+                band[gi * window + (o - 1)] = val;
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int b = 0; b < NB; b++) {
         const int jl = 32 * (w + b) + r;
@@ -201,7 +235,7 @@ extern "C" int eagle_dev_ld_band(eagle_ctx* ctx, const int8_t* Mt8, long rows, l
 #define LD_BAND_CASE(NB)                                                                                                              \
     case NB:                                                                                                                          \
         hipLaunchKernelGGL((k_ld_tile<NB, false>), grid, blk, 0, s, Mt8, rows, n, ld, kbytes, (const int8_t*)nullptr, 0L, 0, sq, (int)window, \
-                           t, mask, (int)words_per_row, (int32_t*)nullptr);                                                           \
+                           t, mask, (int)words_per_row, (int32_t*)nullptr, (double*)nullptr);                                         \
         break;
     switch (nb) {
         LD_BAND_CASE(2) LD_BAND_CASE(3) LD_BAND_CASE(4) LD_BAND_CASE(5) LD_BAND_CASE(6) LD_BAND_CASE(7) LD_BAND_CASE(8) LD_BAND_CASE(9)
@@ -220,7 +254,107 @@ extern "C" int eagle_dev_ld_dots(eagle_ctx* ctx, const int8_t* Mt8, long rows, l
     const long blocks = (rows + LD_TM - 1) / LD_TM;
     if (blocks > 0x7fffffffL) return eagle_fail(ctx, EAGLE_ERR_ARG, "ld_dots: too many rows");
     hipLaunchKernelGGL((k_ld_tile<2, true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, Mt8, rows, n, ld, (n + 15) / 16 * 16,
-                       B8, ld, (int)k, (const int32_t*)nullptr, 0, 0.0, (uint64_t*)nullptr, 0, dots);
+                       B8, ld, (int)k, (const int32_t*)nullptr, 0, 0.0, (uint64_t*)nullptr, 0, dots, (double*)nullptr);
+    LD_LAUNCH_CHECK(ctx);
+    return EAGLE_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// ranked partner lists (include/eagle_hip.h section 1b'''iii)
+// ------------------------------------------------------------------------------------------------------------------------------
+// One wave per marker i of [c_lo, c_hi) (rows of `band`, whose row 0 is marker g0 of the panel).  Candidate t = 2 (|o| - 1) + (o > 0),
+// 0 <= t < 2 window, is marker j = i + o: t is the rank of a tie in r^2 (the smaller |j - i|, then the smaller j).  Lane x holds the
+// candidates t = x, x + 64, ... (at most 8) in registers: the forward entry band[i][o - 1], or the backward entry band[j][|o| - 1] of
+// the marker before it.  l rounds of a wave-wide maximum of (r^2, then the smaller t) write the list in order; the winner's owner
+// retires it.  Lane 0 stores: every word of partners / r2 has one owner.
+__global__ __launch_bounds__(256) void k_ld_partners(const double* __restrict__ band, long rows, int window, long c_lo, long c_hi, long g0,
+                                                     const int32_t* __restrict__ chrom, double min_r2, int l, int32_t* __restrict__ partners,
+                                                     double* __restrict__ r2) {
+    const int lane = threadIdx.x & 63;
+    const long i = c_lo + (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= c_hi) return;                                          // a whole wave: the shuffles below see all 64 lanes or none
+    const long gi = g0 + i;
+    const int ci = chrom ? chrom[gi] : 0;
+    double val[8];
+#pragma unroll
+    for (int s = 0; s < 8; s++) {
+        const int t = lane + 64 * s, o = (t >> 1) + 1;
+        val[s] = -1.0;
+        if (t < 2 * window) {
+            const long j = (t & 1) ? i + o : i - o;
+            if (j >= 0 && j < rows) {
+                const double v = (t & 1) ? band[i * window + (o - 1)] : band[j * window + (o - 1)];
+                if (v >= min_r2 && (!chrom || chrom[g0 + j] == ci)) val[s] = v;      // -1.0 (no pair, monomorphic) is below every min_r2
+            }
+        }
+    }
+    int32_t* prow = partners + gi * l;
+    double* rrow = r2 + gi * l;
+    int t = 0;
+    for (; t < l; t++) {
+        double best = -1.0;
+        int bt = 0x7fffffff;
+#pragma unroll
+        for (int s = 0; s < 8; s++)
+            if (val[s] > best) { best = val[s]; bt = lane + 64 * s; }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const double ob = __shfl_xor(best, off);
+            const int ot = __shfl_xor(bt, off);
+            if (ob > best || (ob == best && ot < bt)) { best = ob; bt = ot; }
+        }
+        if (best < 0.0) break;                                      // the same value in every lane
+        if (lane == 0) {
+            const int o = (bt >> 1) + 1;
+            prow[t] = (int32_t)(gi + ((bt & 1) ? o : -o));
+            rrow[t] = best;
+        }
+#pragma unroll
+        for (int s = 0; s < 8; s++)
+            if (bt == lane + 64 * s) val[s] = -1.0;
+    }
+    for (int x = t + lane; x < l; x += 64) {
+        prow[x] = -1;
+        rrow[x] = 0.0;
+    }
+}
+
+// band: rows x window fp64, every entry written
+extern "C" int eagle_dev_ld_r2band(eagle_ctx* ctx, const int8_t* Mt8, long rows, long n, long ld, const int32_t* sq, long window, double* band,
+                                   void* stream) {
+    if (rows <= 0) return EAGLE_OK;
+    if (ld_bad_image(Mt8, n, ld)) return eagle_fail(ctx, EAGLE_ERR_ARG, "ld_r2band: bad image shape");
+    if (window < 1 || window > 256) return eagle_fail(ctx, EAGLE_ERR_ARG, "ld_r2band: bad window");
+    const long blocks = (rows + LD_TM - 1) / LD_TM;
+    if (blocks > 0x7fffffffL) return eagle_fail(ctx, EAGLE_ERR_ARG, "ld_r2band: too many rows");
+    const dim3 grid((unsigned)blocks), blk(256);
+    hipStream_t s = (hipStream_t)stream;
+    const long kbytes = (n + 15) / 16 * 16;
+    const int nb = (int)((window + 31) / 32) + 1;
+#define LD_R2_CASE(NB)                                                                                                                \
+    case NB:                                                                                                                          \
+        hipLaunchKernelGGL((k_ld_tile<NB, false, true>), grid, blk, 0, s, Mt8, rows, n, ld, kbytes, (const int8_t*)nullptr, 0L, 0, sq, \
+                           (int)window, 0.0, (uint64_t*)nullptr, 0, (int32_t*)nullptr, band);                                          \
+        break;
+    switch (nb) {
+        LD_R2_CASE(2) LD_R2_CASE(3) LD_R2_CASE(4) LD_R2_CASE(5) LD_R2_CASE(6) LD_R2_CASE(7) LD_R2_CASE(8) LD_R2_CASE(9)
+    }
+#undef LD_R2_CASE
+    LD_LAUNCH_CHECK(ctx);
+    return EAGLE_OK;
+}
+
+// partners / r2: rows of l entries indexed by the PANEL's marker, of which the rows g0 + [c_lo, c_hi) are written; chrom: by the panel's
+// marker, or null
+extern "C" int eagle_dev_ld_partners(eagle_ctx* ctx, const double* band, long rows, long window, long c_lo, long c_hi, long g0, const int32_t* chrom,
+                                     double min_r2, int l, int32_t* partners, double* r2, void* stream) {
+    if (c_hi <= c_lo) return EAGLE_OK;
+    if (c_lo < 0 || c_hi > rows || window < 1 || window > 256 || l < 1 || l > EAGLE_LDKNN_MAX_PARTNERS || !(min_r2 >= 0.0 && min_r2 <= 1.0))
+        return eagle_fail(ctx, EAGLE_ERR_ARG, "ld_partners: bad shape");
+    const long blocks = (c_hi - c_lo + 3) / 4;
+    if (blocks > 0x7fffffffL) return eagle_fail(ctx, EAGLE_ERR_ARG, "ld_partners: too many rows");
+    hipLaunchKernelGGL(k_ld_partners, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, band, rows, (int)window, c_lo, c_hi, g0, chrom, min_r2,
+                       l, partners, r2);
     LD_LAUNCH_CHECK(ctx);
     return EAGLE_OK;
 }

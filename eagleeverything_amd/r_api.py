@@ -241,7 +241,7 @@ def _read_marker_bed(filename, availmemGb, quiet, outdir, message, device):
 
 
 def ReadMarker(filename=None, type="text", missing=None, AA=None, AB=None, BB=None, availmemGb=16, quiet=True, outdir=None,
-               message=None, device=0, maf=None, max_missing=None, drop_monomorphic=False, impute=None):
+               message=None, device=0, maf=None, max_missing=None, drop_monomorphic=False, impute=None, impute_local=None):
     """E/R/ReadMarker.R:194-318 -> geno dict {asciifileM, asciifileMt, dim_of_ascii_M} or None (the R list / NULL).
     type="PLINKbed" (not in the reference): `filename` is the .bed file of a PLINK binary fileset or its prefix; n and L are the
     line counts of the .fam and .bim beside it, the genotypes go through rcpp_api.create_ascii_from_bed.
@@ -252,7 +252,9 @@ def ReadMarker(filename=None, type="text", missing=None, AA=None, AB=None, BB=No
     impute=k (not in the reference; type="PLINKbed" only; default None, and then nothing here differs from the lines above): after the
     ingestion the missing genotypes of the fileset are filled by ImputeBed(k=k) into <outdir>/imputed/panel.bed / .bim / .fam, that
     fileset is ingested into <outdir>/imputed, and the dict returned names ITS files.  With a filter as well, the imputed panel is
-    filtered, on the statistics of the original file's called genotypes."""
+    filtered, on the statistics of the original file's called genotypes.
+    impute_local=l (with impute=k; default None, and then nothing here differs from the lines above): ImputeBed(k=k, local=l), LD-kNNi
+    with the chromosomes of the fileset's .bim file."""
     say = message or (lambda s: None)
     if impute is not None and type != "PLINKbed":
         say(' impute needs type = "PLINKbed": only a .bed file still knows which genotypes are missing. \n')
@@ -260,7 +262,7 @@ def ReadMarker(filename=None, type="text", missing=None, AA=None, AB=None, BB=No
         return None
     if maf is not None or max_missing is not None or drop_monomorphic:
         geno = ReadMarker(filename, type=type, missing=missing, AA=AA, AB=AB, BB=BB, availmemGb=availmemGb, quiet=quiet, outdir=outdir,
-                          message=message, device=device, impute=impute)
+                          message=message, device=device, impute=impute, impute_local=impute_local)
         if geno is None:
             return None
         return FilterMarkers(geno, maf=maf, max_missing=max_missing, drop_monomorphic=drop_monomorphic,
@@ -270,7 +272,11 @@ def ReadMarker(filename=None, type="text", missing=None, AA=None, AB=None, BB=No
         if geno is None or impute is None:
             return geno
         imputed = os.path.join(os.path.dirname(geno["asciifileM"]), "imputed")
-        res = ImputeBed(filename, geno, os.path.join(imputed, "panel"), k=int(impute), availmemGb=availmemGb, message=message, device=device)
+        if impute_local is None:
+            res = ImputeBed(filename, geno, os.path.join(imputed, "panel"), k=int(impute), availmemGb=availmemGb, message=message, device=device)
+        else:
+            res = ImputeBed(filename, geno, os.path.join(imputed, "panel"), k=int(impute), availmemGb=availmemGb, message=message, device=device,
+                            local=int(impute_local), map=ReadBim(bed_fileset(filename)[1]))
         return _read_marker_bed(res["bed"], availmemGb, quiet, imputed, message, device)
     if type not in ("text", "PLINK"):                                               # :206-215
         say(' type must be set to "text" or "PLINK". \n')
@@ -433,7 +439,105 @@ def bed_ibs_host(codes, include=None, min_overlap=1):
     return N.astype(np.int32), ibs0.astype(np.int32), H.astype(np.int32), hetsum.astype(np.int32), dist
 
 
-def ImputeBed(bed, geno, out_prefix, k=10, K=64, min_votes=1, availmemGb=8, message=None, device=0, pairwise=False, min_overlap=1):
+# ---- LD-kNNi (include/eagle_hip.h section 1b'''iii): the restatements in numpy ----
+LDKNN_MAX_PARTNERS = 32
+LDKNN_MAX_K = 64
+
+
+def ld_partners_host(Mt8, window, l, min_r2, chrom=None):
+    """rcpp_api.ld_partners restated in numpy: Mt8 = int8 (L, n) marker-major genotypes in {-1, 0, +1} (the ingested panel: missing
+    genotypes are heterozygotes) -> (partners int32 (L, l), r2 fp64 (L, l)).  r2_ij = fl(fl((double)c * (double)c) / fl((double)v_i *
+    (double)v_j)) for v_i, v_j > 0; row i lists the j with 1 <= |j - i| <= window, r2_ij >= min_r2 and chrom[j] == chrom[i] by
+    decreasing r2, ties to the smaller |j - i|, then the smaller j; -1 (r2 0.0) beyond them."""
+    G = np.asarray(Mt8)
+    L, n = G.shape
+    window, l, min_r2 = int(window), int(l), float(min_r2)
+    if not 1 <= window <= 256 or not 1 <= l <= LDKNN_MAX_PARTNERS or not 0.0 <= min_r2 <= 1.0:
+        raise ValueError("ld_partners_host: 1 <= window <= 256, 1 <= l <= %d, 0 <= min_r2 <= 1" % LDKNN_MAX_PARTNERS)
+    ch = None if chrom is None else np.asarray(chrom).ravel()
+    if ch is not None and ch.size != L:
+        raise ValueError("ld_partners_host: chrom holds %d entries, the panel %d markers" % (ch.size, L))
+    F = G.astype(np.float64)                                   # products and sums of small integers: exact in fp64 below 2^53
+    Gi = G.astype(np.int64)
+    s, q = Gi.sum(axis=1), (Gi * Gi).sum(axis=1)
+    v = n * q - s * s
+    vf = v.astype(np.float64)
+    # column t = 2 (o - 1) + (j > i) holds r2 between i and j = i -+ o: the column index is the rank of a tie
+    cols = max(2 * window, l)
+    R = np.full((L, cols), -1.0)
+    J = np.full((L, cols), -1, dtype=np.int64)
+    for o in range(1, min(window, L - 1) + 1):
+        d = np.rint(np.einsum("ij,ij->i", F[:-o], F[o:])).astype(np.int64)          # markers i = 0 .. L - o - 1 with j = i + o
+        c = (n * d - s[:-o] * s[o:]).astype(np.float64)
+        ok = (v[:-o] > 0) & (v[o:] > 0)
+        if ch is not None:
+            ok &= ch[:-o] == ch[o:]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            r2 = (c * c) / (vf[:-o] * vf[o:])
+        r2 = np.where(ok & (r2 >= min_r2), r2, -1.0)
+        R[:-o, 2 * (o - 1) + 1] = r2                                                  # forward: j = i + o
+        J[:-o, 2 * (o - 1) + 1] = np.arange(o, L)
+        R[o:, 2 * (o - 1)] = r2                                                       # backward: the same pair seen from j
+        J[o:, 2 * (o - 1)] = np.arange(0, L - o)
+    order = np.argsort(-R, axis=1, kind="stable")[:, :l]                              # stable: equal r2 stay in column order
+    r2 = np.take_along_axis(R, order, axis=1)
+    part = np.take_along_axis(J, order, axis=1)
+    return np.where(r2 >= 0.0, part, -1).astype(np.int32), np.where(r2 >= 0.0, r2, 0.0)
+
+
+def impute_ldknn_host(codes, partners, k, min_votes, min_overlap):
+    """rcpp_api.bed_impute_ldknn restated in numpy: codes = uint8 (L, n) 2-bit codes of the input (read_bed_codes), partners = int32
+    (L, l) -> (rows, counts) as impute_knn_host returns them.  For a missing (i, m) the candidates are the j called at m with at least
+    min_overlap of m's partners called in both; dist = (d * 4096) // ov over those partners, d = sum (g_i - g_j)^2; the k smallest keys
+    dist << 32 | j vote; (2 s + c) // (2 c) with c >= min_votes voters, else the marker's own mean (heterozygous without a call)."""
+    codes = np.asarray(codes, dtype=np.uint8)
+    P = np.asarray(partners, dtype=np.int64)
+    L, n = codes.shape
+    k, min_votes, min_overlap = int(k), int(min_votes), int(min_overlap)
+    if P.ndim != 2 or P.shape[0] != L or not 1 <= P.shape[1] <= LDKNN_MAX_PARTNERS or not 1 <= k <= LDKNN_MAX_K or min_votes < 1 \
+            or not 1 <= min_overlap <= 32:
+        raise ValueError("impute_ldknn_host: partners must be (L, l), 1 <= l <= %d, 1 <= k <= %d, min_votes >= 1, 1 <= min_overlap <= 32"
+                         % (LDKNN_MAX_PARTNERS, LDKNN_MAX_K))
+    if P.size and (P.min() < -1 or P.max() >= L or np.any((P >= 0) & (np.abs(P - np.arange(L)[:, None]) > 256))):
+        raise ValueError("impute_ldknn_host: a partner outside [-1, L) or more than 256 rows from its marker")
+    gval = np.array([-1.0, 0.0, 0.0, 1.0])
+    out = codes.copy()
+    counts = np.zeros((L, 2), dtype=np.int32)
+    none = np.iinfo(np.uint64).max
+    jj = np.arange(n, dtype=np.uint64)
+    for m in np.flatnonzero((codes == 1).any(axis=1)):
+        row = codes[m]
+        I = np.flatnonzero(row == 1)
+        called = np.flatnonzero(row != 1)
+        fb = _CODE_OF_DOSAGE[(2 * int(_DOSAGE_OF_CODE[row[called]].sum()) + called.size) // (2 * called.size)] if called.size else 2
+        Gp = codes[P[m][P[m] >= 0]]                                                  # (partners, n); a repeated partner counts again
+        c = (Gp != 1).astype(np.float64)
+        g = gval[Gp]
+        q = g * g
+        ov = np.rint(c[:, I].T @ c).astype(np.int64)                                  # (missing, n)
+        d = np.rint(q[:, I].T @ c + c[:, I].T @ q - 2.0 * (g[:, I].T @ g)).astype(np.int64)
+        ok = (ov >= min_overlap) & (row != 1)[None, :]
+        dist = (d * 4096 // np.maximum(ov, 1)).astype(np.uint64)
+        keys = np.where(ok, (dist << np.uint64(32)) | jj[None, :], none)
+        keys = np.sort(keys, axis=1)[:, :k]
+        voter = keys != none
+        cnt = voter.sum(axis=1)
+        dose = np.where(voter, _DOSAGE_OF_CODE[row[(keys & np.uint64(0xffffffff)).astype(np.int64) % n]], 0).sum(axis=1)
+        by_vote = cnt >= min_votes
+        out[m, I] = np.where(by_vote, _CODE_OF_DOSAGE[np.where(by_vote, (2 * dose + cnt) // np.maximum(2 * cnt, 1), 0)], fb)
+        counts[m] = (int(by_vote.sum()), int((~by_vote).sum()))
+    return pack_bed_codes(out), counts
+
+
+def _copy_bim_fam(src_bim, out_bim, src_fam, out_fam):
+    for src, dst in ((src_bim, out_bim), (src_fam, out_fam)):
+        with open(src, "rb") as fi, open(dst, "wb") as fo:
+            for buf in iter(lambda: fi.read(1 << 24), b""):
+                fo.write(buf)
+
+
+def ImputeBed(bed, geno, out_prefix, k=10, K=64, min_votes=1, availmemGb=8, message=None, device=0, pairwise=False, min_overlap=1,
+              local=None, window=50, min_r2=0.0, local_min_overlap=4, map=None):
     """kNN imputation of the missing genotypes of a PLINK binary fileset -> {"bed": the new .bed file, "n_missing", "by_vote",
     "by_fallback": totals, "counts": int32 (L, 2) per marker}.  bed = the .bed file (or prefix) that `geno` was ingested from.
     The neighbours come from the ingested panel (rcpp_api.sample_ibs on geno["asciifileM"], knn_distance, rcpp_api.knn_rows: the K
@@ -442,13 +546,37 @@ def ImputeBed(bed, geno, out_prefix, k=10, K=64, min_votes=1, availmemGb=8, mess
     own mean with fewer than min_votes voters).  pairwise=True ranks the neighbours by the .bed file's own pairwise-complete distance
     instead (rcpp_api.bed_sample_ibs, rcpp_api.knn_rows_dist: every pair is compared over the markers where both are called, at
     least min_overlap of them, so shared missingness does not make two individuals look alike).  Writes <out_prefix>.bed and
-    byte-for-byte copies of the .bim and .fam; the new fileset has no missing code and ReadMarker(type="PLINKbed") ingests it."""
+    byte-for-byte copies of the .bim and .fam; the new fileset has no missing code and ReadMarker(type="PLINKbed") ingests it.
+    local=l (default None, and then nothing here differs from the lines above) switches to LD-kNNi (include/eagle_hip.h section
+    1b'''iii): every marker's l <= 32 partners in local LD come from the ingested panel (rcpp_api.ld_partners on geno["asciifileMt"]:
+    the markers at most `window` away with r2 >= min_r2, on the marker's chromosome when map -- ReadBim's dict -- is given), and a
+    missing genotype takes the rounded mean dosage of the k <= 64 individuals called at its marker that are nearest over those
+    partners, among the individuals compared over at least local_min_overlap of them (rcpp_api.bed_impute_ldknn).  For panels whose
+    members are all about equally related genome-wide (MAGIC, NAM, diversity panels), where the close relative changes from segment
+    to segment.  K, pairwise and min_overlap are ignored in this mode; the result carries "partners" as well."""
     say = message or (lambda s: None)
     src_bed, src_bim, src_fam = bed_fileset(bed)
     n, L = int(geno["dim_of_ascii_M"][0]), int(geno["dim_of_ascii_M"][1])
     out_bed, out_bim, out_fam = bed_fileset(str(out_prefix))
     if os.path.abspath(out_bed) == os.path.abspath(src_bed):
         raise ValueError("ImputeBed: out_prefix names the input fileset")
+    if local is not None:
+        errs = []
+        map = _ld_map("ImputeBed", map, geno, L, errs.append)
+        if map is False:
+            raise ValueError("ImputeBed:" + errs[0])
+        chrom = None if map is None else np.unique(np.asarray([str(c) for c in map["Chr"]]), return_inverse=True)[1].astype(np.int32)
+        l = max(1, min(int(local), LDKNN_MAX_PARTNERS))
+        k = max(1, min(int(k), LDKNN_MAX_K))
+        partners = rcpp_api.ld_partners(geno["asciifileMt"], (n, L), int(window), l, float(min_r2), chrom, availmemGb, device=device)
+        os.makedirs(os.path.dirname(os.path.abspath(out_bed)), exist_ok=True)
+        counts = rcpp_api.bed_impute_ldknn(src_bed, (n, L), partners, k, int(min_votes), int(local_min_overlap), out_bed, availmemGb, device=device)
+        _copy_bim_fam(src_bim, out_bim, src_fam, out_fam)
+        by_vote, by_fallback = int(counts[:, 0].sum(dtype=np.int64)), int(counts[:, 1].sum(dtype=np.int64))
+        say(" Imputed %d missing genotypes: %d from their %d nearest called neighbours over %d markers in local LD, %d from the marker's own mean. "
+            % (by_vote + by_fallback, by_vote, k, l, by_fallback))
+        return {"bed": out_bed, "n_missing": by_vote + by_fallback, "by_vote": by_vote, "by_fallback": by_fallback, "counts": counts,
+                "partners": partners}
     K = max(1, min(int(K), KNN_MAX_K))
     k = max(1, min(int(k), K))
     if pairwise:
@@ -459,10 +587,7 @@ def ImputeBed(bed, geno, out_prefix, k=10, K=64, min_votes=1, availmemGb=8, mess
         nbr = rcpp_api.knn_rows(ibs0, hethet, K, device=device)
     os.makedirs(os.path.dirname(os.path.abspath(out_bed)), exist_ok=True)
     counts = rcpp_api.bed_impute_knn(src_bed, (n, L), nbr, k, int(min_votes), out_bed, availmemGb, device=device)
-    for src, dst in ((src_bim, out_bim), (src_fam, out_fam)):
-        with open(src, "rb") as fi, open(dst, "wb") as fo:
-            for buf in iter(lambda: fi.read(1 << 24), b""):
-                fo.write(buf)
+    _copy_bim_fam(src_bim, out_bim, src_fam, out_fam)
     by_vote, by_fallback = int(counts[:, 0].sum(dtype=np.int64)), int(counts[:, 1].sum(dtype=np.int64))
     say(" Imputed %d missing genotypes: %d from their %d nearest called neighbours, %d from the marker's own mean. "
         % (by_vote + by_fallback, by_vote, k, by_fallback))

@@ -747,6 +747,49 @@ def bed_impute_knn(bed_path, dims, nbr, k, min_votes, out_bed_path, max_memory_i
     return out
 
 
+# ---- LD-kNNi (include/eagle_hip.h section 1b'''iii): ranked LD partners per marker and the .bed file patched from them ----
+LDKNN_MAX_PARTNERS = 32
+LDKNN_MAX_K = 64
+LDKNN_MAX_N = 12288
+
+
+def ld_partners(f_name_ascii_Mt, dims, window=50, l=16, min_r2=0.0, chrom=None, max_memory_in_Gbytes=8.0, device=0, return_r2=False):
+    """eagle_ld_partners -> int32 (L, l): row i = the markers j, 1 <= |j - i| <= window, on i's chromosome when chrom (L whole numbers)
+    is given, with r2_ij >= min_r2, by decreasing r2 (ties to the smaller |j - i|, then the smaller j); -1 beyond them.  r2 is the fp64
+    number of include/eagle_hip.h section 1b'''iii.  return_r2: (partners, fp64 (L, l) with 0.0 beside -1).  r_api.ld_partners_host is
+    the numpy restatement."""
+    L = _lib.load()
+    nm = max(int(dims[1]), 0)
+    ch = None
+    if chrom is not None:
+        c = np.atleast_1d(np.asarray(chrom)).ravel()
+        ch = np.ascontiguousarray(c, dtype=np.int32)
+        if ch.size != nm or not np.array_equal(ch, c):
+            raise ValueError("ld_partners: chrom must hold one whole number that fits int32 per marker")
+    out = np.zeros((nm, max(int(l), 1)), dtype=np.int32)
+    r2 = np.zeros(out.shape, dtype=np.float64) if return_r2 else None
+    _args_first(L.eagle_ld_partners, device, (os.fsencode(f_name_ascii_Mt), _dims(dims), int(window), int(l), float(min_r2),
+                                              ch.ctypes.data_as(_c_i32p) if ch is not None else None, float(max_memory_in_Gbytes),
+                                              out.ctypes.data_as(_c_i32p), _dp(r2) if return_r2 else None))
+    return (out, r2) if return_r2 else out
+
+
+def bed_impute_ldknn(bed_path, dims, partners, k, min_votes, min_overlap, out_bed_path, max_memory_in_Gbytes=8.0, device=0):
+    """eagle_bed_impute_ldknn -> int32 (L, 2): the genotypes of every marker imputed by vote and by fallback.  Writes out_bed_path, the
+    SNP-major .bed file bed_path (dims = (n individuals, L markers)) with every missing genotype filled from the k individuals that
+    are called at its marker and nearest over the marker's partners ((L, l) int32: ld_partners), among those compared over at least
+    min_overlap partners; from the marker's own calls when fewer than min_votes of them exist."""
+    L = _lib.load()
+    pt = _i32_matrix(partners, "bed_impute_ldknn: partners")
+    if pt.shape[0] != int(dims[1]):
+        raise ValueError("bed_impute_ldknn: partners holds %d rows, the file %d markers" % (pt.shape[0], int(dims[1])))
+    out = np.zeros((max(int(dims[1]), 0), 2), dtype=np.int32)
+    _args_first(L.eagle_bed_impute_ldknn, device, (os.fsencode(bed_path), _dims(dims), pt.ctypes.data_as(_c_i32p), pt.shape[1], int(k), int(min_votes),
+                                                   int(min_overlap), os.fsencode(out_bed_path), float(max_memory_in_Gbytes),
+                                                   out.ctypes.data_as(_c_i32p)))
+    return out
+
+
 # ---- GRM (include/eagle_hip.h section 1b''''): the exact weighted Gram product; weights, centring and PCA are r_api's ----
 WGRAM_MAX_WEIGHT = (1 << 21) - 1
 

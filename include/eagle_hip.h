@@ -475,6 +475,67 @@ int eagle_bed_sample_ibs(eagle_ctx* ctx, const char* bed_path, const long dims[2
 int eagle_knn_rows_dist(eagle_ctx* ctx, const uint32_t* dist, long n, int K, int32_t* nbr_out);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1b'''iii. LD-kNNi: imputation from neighbours ranked in local LD (no counterpart in the reference; Money et al. 2015, the successor
+ *     of the kNNi of 1b'''i).  1b'''i ranks an individual's neighbours once, genome-wide.  In a panel whose members are all about
+ *     equally related genome-wide (MAGIC, NAM, diversity panels) the close relative changes from one segment to the next: here the
+ *     neighbours of a missing genotype are ranked per marker, over the marker's partners in local LD.  Integer arithmetic, or fp64 in
+ *     a fixed order with no FMA contraction: a restatement in numpy gives the same bytes (r_api.ld_partners_host,
+ *     r_api.impute_ldknn_host).
+ *
+ *     LD partners.  Notation of 1b'' (s, q, d, c, v from the ingested marker-major image; missing genotypes are heterozygotes there).
+ *     For markers i != j with v_i > 0 and v_j > 0, in fp64 in exactly this order (two products, one quotient, each correctly rounded):
+ *         r2_ij = fl( fl((double)c * (double)c) / fl((double)v_i * (double)v_j) )
+ *     Marker j is a CANDIDATE for i when 1 <= |j - i| <= window, 0 <= j < L, r2_ij >= min_r2, and chrom[j] == chrom[i] when chrom is
+ *     given.  partners[i][0 .. l) holds the l_i = min(l, #candidates) candidates by decreasing r2, ties to the smaller |j - i|, then to
+ *     the smaller j; then -1.  A monomorphic marker has a row of -1.  1 <= window <= 256 (the band of eagle_ld_window),
+ *     1 <= l <= EAGLE_LDKNN_MAX_PARTNERS, 0 <= min_r2 <= 1.
+ *
+ *     Local distance.  Codes and dosages are those of 1b'''i, read from the INPUT .bed file, where the missing code is still known.  For
+ *     target marker m with partner set P = partners[m] (entries -1 passed over) and individuals i != j, over the p in P where both are
+ *     called:
+ *         ov_ij = #{p},    d_ij = sum_p (g_ip - g_jp)^2 with g = -1, 0, +1,    dist_ij = (d_ij * 4096) / ov_ij in integer division.
+ *     d <= 128 and ov <= 32: two different ratios d / ov differ by at least 1/1024, so the floor keeps their order.  j is ELIGIBLE for
+ *     (i, m) when j != i, j is called at m, and ov_ij >= min_overlap (1 <= min_overlap <= 32).
+ *
+ *     Vote for a missing (i, m): the k eligible j with the smallest keys (uint64)dist_ij << 32 | j, 1 <= k <= EAGLE_LDKNN_MAX_K.  With c
+ *     voters of dosage sum s and c >= min_votes (>= 1) the dosage written is (2 s + c) / (2 c), the rule of 1b'''i; otherwise 1b'''i's
+ *     fallback: the same formula on the marker's own calls, a heterozygote when the marker has no call.
+ *
+ *     Votes read original codes only, so the result does not depend on the order in which genotypes are filled.  Called genotypes are
+ *     copied; the unused bit pairs of a row's last byte are written as 00.
+ *
+ *     Single device: a multi-device context works on its first device.  Argument errors (EAGLE_ERR_ARG: a NULL pointer, dims <= 0,
+ *     and those named below) are decided before the context is used; with ctx == NULL their text is in eagle_open_error().
+ * ------------------------------------------------------------------------------------------- */
+
+#define EAGLE_LDKNN_MAX_PARTNERS 32
+#define EAGLE_LDKNN_MAX_K 64
+/* k_bed_impute_ldknn keeps three 32-bit words per individual (bit p = partner p) and two copies of the target row in the 160 KiB of
+ * LDS of a compute unit: 12.5 bytes per individual, 150 KiB at this n, the rest left to the kernel's own arrays. */
+#define EAGLE_LDKNN_MAX_N 12288L
+
+/* partners_out: L x l int32 as defined above, row-major; r2_out (may be NULL): L x l fp64, the r2 of every partner, 0.0 beside -1.
+ * f_name_ascii_Mt is read as eagle_ld_window reads it (dims = (n, L); resident image, else sidecar, else text; a VIEW alias works).
+ * The dot products are those of eagle_ld_window's band, on the same tile of the int8 MFMA, kept as fp64 r2 values (k_ld_tile's r2
+ * mode); k_ld_partners ranks, per marker, its forward entries and the backward entries of the `window` markers before it.  chrom: L
+ * int32 (any coding) or NULL.  Row windows -- a file that is not resident, and a resident one whose band would pass 256 MiB -- overlap
+ * by `window` rows on each side: the result does not depend on the window size.
+ * EAGLE_ERR_ARG: L >= 2^31, window outside [1, 256], l outside [1, EAGLE_LDKNN_MAX_PARTNERS], min_r2 outside [0, 1] or NaN. */
+int eagle_ld_partners(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long dims[2], long window, int l, double min_r2, const int32_t* chrom,
+                      double max_memory_in_Gbytes, int32_t* partners_out, double* r2_out);
+
+/* Writes out_bed_path: the SNP-major .bed file bed_path (the format, the checks and the error codes of eagle_create_ascii_from_bed;
+ * dims = (n, L)) with every missing genotype filled as defined above from partners (L x l int32, host memory: eagle_ld_partners'
+ * output, or any table within the limits below).  counts_out (may be NULL): L x 2 int32, the genotypes of marker i imputed by vote and
+ * by fallback.  The staging ring and the write-behind of eagle_bed_impute_knn; a staged window carries a halo of up to 256 marker rows
+ * on each side, because a marker's partners can lie in the neighbouring window.  The result does not depend on the window size.
+ * EAGLE_ERR_ARG: n > EAGLE_LDKNN_MAX_N, l outside [1, EAGLE_LDKNN_MAX_PARTNERS], k outside [1, EAGLE_LDKNN_MAX_K], min_votes < 1,
+ * min_overlap outside [1, 32], a partners entry outside [-1, L) or more than 256 rows from its marker, out_bed_path equal to bed_path
+ * -- nothing has been written then.  A failed call leaves no output file of the full size. */
+int eagle_bed_impute_ldknn(eagle_ctx* ctx, const char* bed_path, const long dims[2], const int32_t* partners, int l, int k, int min_votes,
+                           int min_overlap, const char* out_bed_path, double max_memory_in_Gbytes, int32_t* counts_out);
+
+/* ---------------------------------------------------------------------------------------------
  * 1b''''. Genomic relationship matrix (no counterpart that the reference calls: its VanRaden G, E/R/GenomicRel.R, is unused): the one
  *     Gram product the matrices of EIGENSTRAT / PLINK / GCTA and their principal components need, with a weight per marker.  With
  *     g in {-1, 0, +1} = AA, AB, BB as everywhere in this library and integer weights q_m < 2^21,
