@@ -107,6 +107,7 @@ struct eagle_ctx {
     // per-device launch state (a process may hold one ctx per GPU): dynamic-LDS attributes set on this device, schedule
     // experiment switch of tools/bench_i8_engine.py (0 = shipped)
     bool attr_vara_i8 = false, attr_vara_i8w = false, attr_vara_i8p = false, attr_vara_i8pp = false, attr_vara_i8px = false, attr_syrk_f4w = false, attr_zbuild_i8 = false, attr_vara_f6 = false, attr_gemv = false, attr_w8_gemm = false, attr_knn_rows = false, attr_knn_rows_dist = false, attr_ldknn = false;
+    uint32_t attr_bedld = 0;   // k_bedld_tile<NB, R2>: bit 2 (NB - 2) + R2
     int tune = 0;
     // W = S (V S) on the int8 engine (eagle_w8.hip): workspace, and what the last call left for the scan that follows it
     int w_mode = 1;            // 0 = always the fp64 GEMM, 1 = int8 digit slices from 4,096 padded individuals up, 2 = int8 at any size (tests)
@@ -223,6 +224,16 @@ extern "C" int eagle_dev_bed_impute(eagle_ctx* ctx, const uint8_t* bed, long row
 extern "C" int eagle_dev_bed_impute_ldknn(eagle_ctx* ctx, const uint8_t* bed, long staged, long first, long rows, long m0, long h_lo, long n,
                                           const int32_t* partners, int l, int k, int min_votes, int min_overlap, const int32_t* mcounts,
                                           uint8_t* out, int32_t* counts, void* stream);
+// Pairwise-complete LD from a .bed file (eagle_bedld.hip; include/eagle_hip.h section 1b'''iv), device pointers throughout.  X / C / U: the
+// three marker-major int8 operand images (P x ld, ld % 16 == 0, zero from individual n on) of the staged rows offsets[0 .. P) of `bed`
+// (`staged` raw rows; offsets null: rows 0 .. P - 1), each checked by the CALLER to lie in [0, staged).  band / r2band: k_ld_tile's two
+// outputs for `rows` consecutive panel markers from the six pairwise-complete sums; min_overlap >= 1.
+extern "C" int eagle_dev_bed_ld_pack(eagle_ctx* ctx, const uint8_t* bed, long staged, const long* offsets, long P, long n, long ld, int8_t* X,
+                                     int8_t* C, int8_t* U, void* stream);
+extern "C" int eagle_dev_bedld_band(eagle_ctx* ctx, const int8_t* X, const int8_t* C, const int8_t* U, long rows, long n, long ld, long window,
+                                    double t, long min_overlap, uint64_t* mask, long words_per_row, void* stream);
+extern "C" int eagle_dev_bedld_r2band(eagle_ctx* ctx, const int8_t* X, const int8_t* C, const int8_t* U, long rows, long n, long ld, long window,
+                                      long min_overlap, double* band, void* stream);
 // Pairwise-complete IBS counts from a .bed file (eagle_bedibs.hip; include/eagle_hip.h section 1b'''ii), device pointers throughout.  The
 // four fp4 operand images (g, u, h, c; plane p at M4 + p * plane_bytes, n_pad rows of ld4 bytes, L_pad markers written) of `rows` raw
 // .bed rows, `include` one byte per row or null; the four n x n int32 results and dist (or null) from the four Gram accumulators

@@ -1342,6 +1342,205 @@ extern "C" int eagle_ld_partners(eagle_ctx* ctx, const char* f_name_ascii_Mt, co
     return EAGLE_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Pairwise-complete LD from the .bed file (include/eagle_hip.h section 1b'''iv; kernels in eagle_bedld.hip)
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+
+// The panel of a call (the included markers of the file, in file order), the window rule of the header, and the staging of one window:
+// the span of file rows that holds the panel markers [lo, hi) goes through pinned buffer b to the device, and k_bed_ld_pack writes
+// the three operand images of those markers.
+struct BedLdPanel {
+    eagle_ctx* ctx = nullptr;
+    const char* path = nullptr;
+    int fd = -1, threads = 1;
+    long n = 0, L = 0, linc = 0, rb = 0, ld = 0;
+    long S = 0;      // file rows the staging budget holds
+    long wmax = 0;   // panel markers of a window, at most
+    std::vector<long> fidx;   // panel marker -> file row; empty: the identity
+    std::vector<long> offs[2];
+    DevBuf d_offs[2], X, C, U;
+    hipEvent_t done[2] = {nullptr, nullptr};
+    long windows = 0;
+    ~BedLdPanel() {
+        for (int b = 0; b < 2; b++) if (done[b]) (void)hipEventDestroy(done[b]);
+        if (fd >= 0) close(fd);
+    }
+    long file_row(long p) const { return fidx.empty() ? p : fidx[(size_t)p]; }
+    // the end of the window that starts at panel marker lo: as many markers as wmax and the staging budget allow, never fewer than
+    // `need` (what the call needs to advance), never beyond the panel
+    long window_end(long lo, long need) const {
+        const long floor_hi = std::min(linc, lo + need);
+        long hi = std::min(linc, lo + wmax);
+        if (fidx.empty()) hi = std::min(hi, lo + S);
+        else hi = (long)(std::upper_bound(fidx.begin() + lo, fidx.begin() + hi, fidx[(size_t)lo] + S - 1) - fidx.begin());
+        return std::max(hi, floor_hi);
+    }
+    int stage(long lo, long hi) {
+        const int b = (int)(windows & 1);
+        if (windows >= 2) HIPCHK(ctx, hipEventSynchronize(done[b]));  // window - 2 has left staging buffer b and its offsets
+        windows++;
+        const long f0 = file_row(lo), span = file_row(hi - 1) - f0 + 1, P = hi - lo;
+        if (!pread_all(fd, (char*)ctx->stage_pin[b], (size_t)span * rb, (off_t)BED_HEADER_BYTES + (off_t)f0 * rb, threads)) {
+            (void)hipStreamSynchronize(ctx->stream);
+            return failf(ctx, EAGLE_ERR_FORMAT, "%s: could not read markers %ld to %ld", path, f0 + 1, f0 + span);
+        }
+        HIPCHK(ctx, hipMemcpyAsync(ctx->stage_raw[b], ctx->stage_pin[b], (size_t)span * rb, hipMemcpyHostToDevice, ctx->stream));
+        const long* d_off = nullptr;
+        if (!fidx.empty()) {
+            offs[b].resize((size_t)P);
+            for (long p = 0; p < P; p++) offs[b][(size_t)p] = fidx[(size_t)(lo + p)] - f0;   // in [0, span): fidx increases
+            HIPCHK(ctx, hipMemcpyAsync(d_offs[b].p, offs[b].data(), sizeof(long) * (size_t)P, hipMemcpyHostToDevice, ctx->stream));
+            d_off = d_offs[b].as<long>();
+        }
+        int rc = eagle_dev_bed_ld_pack(ctx, (const uint8_t*)ctx->stage_raw[b], span, d_off, P, n, ld, X.as<int8_t>(), C.as<int8_t>(), U.as<int8_t>(),
+                                       ctx->stream);
+        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+        HIPCHK(ctx, hipEventRecord(done[b], ctx->stream));            // the staging buffer is free once the pack has read it
+        return EAGLE_OK;
+    }
+};
+
+// Linc of an include mask (L when it is NULL)
+long bedld_count(const uint8_t* include, long L) {
+    if (!include) return L;
+    long c = 0;
+    for (long m = 0; m < L; m++) c += include[m] != 0;
+    return c;
+}
+
+// Opens the file and sizes everything a call needs; band_rows_max caps the window further (the partners call's band), 0 = no cap.
+// need = the markers a window must hold for the call to advance; next_of(hi) = the start of the window after one that ends at hi, or
+// linc when that was the last one.  The caller walks the same windows again: they are a function of the arguments alone.
+template <class Next>
+int bedld_open(BedLdPanel& pl, eagle_ctx* ctx, const char* bed_path, long n, long L, const uint8_t* include, long linc, double mem_gb,
+               long band_rows_max, long need, Next next_of) {
+    pl.ctx = ctx; pl.path = bed_path; pl.n = n; pl.L = L; pl.linc = linc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (int orc = open_bed(ctx, bed_path, n, L, &pl.fd)) return orc;
+    pl.threads = host_threads();
+    pl.rb = bed_row_bytes(n);
+    pl.ld = (n + 15) / 16 * 16;
+    double cap = 67108864.0;
+    if (mem_gb > 0) cap = std::min(cap, mem_gb * 1e9 / 4.0);  // the loaders' staging rule
+    pl.S = std::max(1L, (long)cap / pl.rb);
+    pl.wmax = std::max(1024L, (long)(((size_t)1 << 27) / (size_t)pl.ld));   // one operand image stays under 128 MiB
+    if (band_rows_max > 0) pl.wmax = std::min(pl.wmax, band_rows_max);
+    if (include) {
+        pl.fidx.reserve((size_t)linc);
+        for (long m = 0; m < L; m++) if (include[m]) pl.fidx.push_back(m);
+    }
+    long span_max = 1, p_max = 1;
+    for (long lo = 0; lo < linc;) {
+        const long hi = pl.window_end(lo, need);
+        span_max = std::max(span_max, pl.file_row(hi - 1) - pl.file_row(lo) + 1);
+        p_max = std::max(p_max, hi - lo);
+        lo = next_of(hi);
+    }
+    int rc = eagle_stage_ensure(ctx, (size_t)span_max * pl.rb);
+    if (rc) return rc;
+    HIPCHK(ctx, pl.X.alloc((size_t)p_max * pl.ld));
+    HIPCHK(ctx, pl.C.alloc((size_t)p_max * pl.ld));
+    HIPCHK(ctx, pl.U.alloc((size_t)p_max * pl.ld));
+    if (include) for (int b = 0; b < 2; b++) HIPCHK(ctx, pl.d_offs[b].alloc(sizeof(long) * (size_t)p_max));
+    for (int b = 0; b < 2; b++) HIPCHK(ctx, hipEventCreateWithFlags(&pl.done[b], hipEventDisableTiming));
+    pl.wmax = std::min(pl.wmax, p_max);
+    return EAGLE_OK;
+}
+
+}  // namespace
+
+// eagle_ld_window's streamed pass over panel markers: a window [lo, hi) writes the mask rows of all its markers, those of its last
+// `window` markers without the partners it does not hold, and the next window, which starts on exactly those markers, writes them again
+// in full (stream order).
+extern "C" int eagle_bed_ld_window(eagle_ctx* ctx, const char* bed_path, const long dims[2], const uint8_t* include, long window, double r2,
+                                   int min_overlap, double max_memory_in_Gbytes, uint64_t* mask_out, long* npairs_out) {
+    if (!bed_path || !dims || !mask_out || !npairs_out) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_ld_window: NULL argument");
+    const long n = dims[0], L = dims[1];
+    if (n <= 0 || L <= 0) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_ld_window: dims must be positive");
+    if (n > 0x3fffffffL) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_ld_window: 2^30 individuals or more");
+    if (window < 1 || window > 256) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_ld_window: window must be in [1, 256]");
+    if (!(r2 >= 0.0 && r2 <= 1.0)) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_ld_window: r2 must be in [0, 1]");
+    if (min_overlap < 1) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_ld_window: min_overlap must be at least 1");
+    const long linc = bedld_count(include, L);
+    if (linc < 1) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_ld_window: include selects no marker");
+    if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_ld_window: no context");
+    BedLdPanel pl;
+    const long need = window + 1;
+    auto next_of = [&](long hi) { return hi >= linc ? linc : hi - window; };
+    int rc = bedld_open(pl, ctx, bed_path, n, L, include, linc, max_memory_in_Gbytes, 0, need, next_of);
+    if (rc) return rc;
+    const long wpr = (window + 63) / 64;
+    const size_t mask_bytes = sizeof(uint64_t) * (size_t)linc * (size_t)wpr;
+    DevBuf mask;
+    HIPCHK(ctx, mask.alloc(mask_bytes));
+    for (long lo = 0; lo < linc;) {
+        const long hi = pl.window_end(lo, need);
+        rc = pl.stage(lo, hi);
+        if (!rc) rc = eagle_dev_bedld_band(ctx, pl.X.as<int8_t>(), pl.C.as<int8_t>(), pl.U.as<int8_t>(), hi - lo, n, pl.ld, window, r2, min_overlap,
+                                           mask.as<uint64_t>() + lo * wpr, wpr, ctx->stream);
+        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+        lo = next_of(hi);
+    }
+    HIPCHK(ctx, hipMemcpyAsync(mask_out, mask.p, mask_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    long pairs = 0;
+    for (size_t x = 0; x < (size_t)linc * (size_t)wpr; x++) pairs += __builtin_popcountll(mask_out[x]);
+    *npairs_out = pairs;
+    return EAGLE_OK;
+}
+
+// eagle_ld_partners' cores over panel markers: the window held for a core [c0, c1) is [lo, hi) = [max(0, c0 - window), min(Linc,
+// c1 + window)); the tile kernel writes the r2 band of the markers held and k_ld_partners the partner rows of the core alone.  The
+// first core starts at 0 = lo, every later one at lo + window; a window holds at least 2 window + 1 markers (or the rest of the panel),
+// so that the next one starts after it did.
+extern "C" int eagle_bed_ld_partners(eagle_ctx* ctx, const char* bed_path, const long dims[2], const uint8_t* include, long window, int l,
+                                     double min_r2, int min_overlap, const int32_t* chrom, double max_memory_in_Gbytes, int32_t* partners_out,
+                                     double* r2_out) {
+    if (!bed_path || !dims || !partners_out) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_ld_partners: NULL argument");
+    const long n = dims[0], L = dims[1];
+    if (n <= 0 || L <= 0) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_ld_partners: dims must be positive");
+    if (n > 0x3fffffffL) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_ld_partners: 2^30 individuals or more");
+    if (window < 1 || window > 256) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_ld_partners: window must be in [1, 256]");
+    if (l < 1 || l > EAGLE_LDKNN_MAX_PARTNERS) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_ld_partners: l outside [1, 32]");
+    if (!(min_r2 >= 0.0 && min_r2 <= 1.0)) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_ld_partners: min_r2 must be in [0, 1]");
+    if (min_overlap < 1) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_ld_partners: min_overlap must be at least 1");
+    const long linc = bedld_count(include, L);
+    if (linc < 1) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_ld_partners: include selects no marker");
+    if (linc > 0x7fffffffL) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_ld_partners: 2^31 markers or more");
+    if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_ld_partners: no context");
+    BedLdPanel pl;
+    const long need = 2 * window + 1;
+    auto next_of = [&](long hi) { return hi >= linc ? linc : hi - 2 * window; };              // c1 = hi - window; the next window starts at c1 - window
+    const long band_rows = std::max(1024L, (long)(((size_t)256 << 20) / (sizeof(double) * (size_t)window)));   // eagle_ld_partners' cap
+    int rc = bedld_open(pl, ctx, bed_path, n, L, include, linc, max_memory_in_Gbytes, band_rows, need, next_of);
+    if (rc) return rc;
+    const size_t cells = (size_t)linc * (size_t)l;
+    DevBuf part, r2, d_chrom, band;
+    HIPCHK(ctx, part.alloc(sizeof(int32_t) * cells));
+    HIPCHK(ctx, r2.alloc(sizeof(double) * cells));
+    HIPCHK(ctx, band.alloc(sizeof(double) * (size_t)pl.wmax * (size_t)window));
+    if (chrom) {
+        HIPCHK(ctx, d_chrom.alloc(sizeof(int32_t) * (size_t)linc));
+        HIPCHK(ctx, hipMemcpyAsync(d_chrom.p, chrom, sizeof(int32_t) * (size_t)linc, hipMemcpyHostToDevice, ctx->stream));
+    }
+    for (long lo = 0; lo < linc;) {
+        const long hi = pl.window_end(lo, need), nr = hi - lo;
+        const long c0 = lo == 0 ? 0 : lo + window, c1 = hi >= linc ? linc : hi - window;
+        rc = pl.stage(lo, hi);
+        if (!rc) rc = eagle_dev_bedld_r2band(ctx, pl.X.as<int8_t>(), pl.C.as<int8_t>(), pl.U.as<int8_t>(), nr, n, pl.ld, window, min_overlap,
+                                             band.as<double>(), ctx->stream);
+        if (!rc) rc = eagle_dev_ld_partners(ctx, band.as<double>(), nr, window, c0 - lo, c1 - lo, lo, chrom ? d_chrom.as<int32_t>() : nullptr, min_r2, l,
+                                            part.as<int32_t>(), r2.as<double>(), ctx->stream);
+        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+        lo = next_of(hi);
+    }
+    HIPCHK(ctx, hipMemcpyAsync(partners_out, part.p, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, ctx->stream));
+    if (r2_out) HIPCHK(ctx, hipMemcpyAsync(r2_out, r2.p, sizeof(double) * cells, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return EAGLE_OK;
+}
+
 // The loci's rows are gathered into a 64-row image first (k_gather_rows_i8: from the resident image, else from their own lines of
 // the file, each distinct line read once), then every tile of Mt multiplies against it, where it lies or window by window.
 extern "C" int eagle_ld_dots(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long dims[2], const long* loci, long nloci,

@@ -241,7 +241,8 @@ def _read_marker_bed(filename, availmemGb, quiet, outdir, message, device):
 
 
 def ReadMarker(filename=None, type="text", missing=None, AA=None, AB=None, BB=None, availmemGb=16, quiet=True, outdir=None,
-               message=None, device=0, maf=None, max_missing=None, drop_monomorphic=False, impute=None, impute_local=None):
+               message=None, device=0, maf=None, max_missing=None, drop_monomorphic=False, impute=None, impute_local=None,
+               impute_ld_from="panel"):
     """E/R/ReadMarker.R:194-318 -> geno dict {asciifileM, asciifileMt, dim_of_ascii_M} or None (the R list / NULL).
     type="PLINKbed" (not in the reference): `filename` is the .bed file of a PLINK binary fileset or its prefix; n and L are the
     line counts of the .fam and .bim beside it, the genotypes go through rcpp_api.create_ascii_from_bed.
@@ -254,7 +255,8 @@ def ReadMarker(filename=None, type="text", missing=None, AA=None, AB=None, BB=No
     fileset is ingested into <outdir>/imputed, and the dict returned names ITS files.  With a filter as well, the imputed panel is
     filtered, on the statistics of the original file's called genotypes.
     impute_local=l (with impute=k; default None, and then nothing here differs from the lines above): ImputeBed(k=k, local=l), LD-kNNi
-    with the chromosomes of the fileset's .bim file."""
+    with the chromosomes of the fileset's .bim file.  impute_ld_from="bed" (default "panel": nothing differs) passes ld_from="bed": the
+    partners in local LD come from the .bed file's own pairwise-complete r2."""
     say = message or (lambda s: None)
     if impute is not None and type != "PLINKbed":
         say(' impute needs type = "PLINKbed": only a .bed file still knows which genotypes are missing. \n')
@@ -262,7 +264,7 @@ def ReadMarker(filename=None, type="text", missing=None, AA=None, AB=None, BB=No
         return None
     if maf is not None or max_missing is not None or drop_monomorphic:
         geno = ReadMarker(filename, type=type, missing=missing, AA=AA, AB=AB, BB=BB, availmemGb=availmemGb, quiet=quiet, outdir=outdir,
-                          message=message, device=device, impute=impute, impute_local=impute_local)
+                          message=message, device=device, impute=impute, impute_local=impute_local, impute_ld_from=impute_ld_from)
         if geno is None:
             return None
         return FilterMarkers(geno, maf=maf, max_missing=max_missing, drop_monomorphic=drop_monomorphic,
@@ -276,7 +278,7 @@ def ReadMarker(filename=None, type="text", missing=None, AA=None, AB=None, BB=No
             res = ImputeBed(filename, geno, os.path.join(imputed, "panel"), k=int(impute), availmemGb=availmemGb, message=message, device=device)
         else:
             res = ImputeBed(filename, geno, os.path.join(imputed, "panel"), k=int(impute), availmemGb=availmemGb, message=message, device=device,
-                            local=int(impute_local), map=ReadBim(bed_fileset(filename)[1]))
+                            local=int(impute_local), map=ReadBim(bed_fileset(filename)[1]), ld_from=impute_ld_from)
         return _read_marker_bed(res["bed"], availmemGb, quiet, imputed, message, device)
     if type not in ("text", "PLINK"):                                               # :206-215
         say(' type must be set to "text" or "PLINK". \n')
@@ -462,19 +464,31 @@ def ld_partners_host(Mt8, window, l, min_r2, chrom=None):
     s, q = Gi.sum(axis=1), (Gi * Gi).sum(axis=1)
     v = n * q - s * s
     vf = v.astype(np.float64)
+    band = np.full((L, window), -1.0)                          # band[i, o - 1] = r2 between i and i + o, -1.0 without one
+    for o in range(1, min(window, L - 1) + 1):
+        d = np.rint(np.einsum("ij,ij->i", F[:-o], F[o:])).astype(np.int64)          # markers i = 0 .. L - o - 1 with j = i + o
+        c = (n * d - s[:-o] * s[o:]).astype(np.float64)
+        ok = (v[:-o] > 0) & (v[o:] > 0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            r2 = (c * c) / (vf[:-o] * vf[o:])
+        band[:-o, o - 1] = np.where(ok, r2, -1.0)
+    return _ld_rank_band(band, l, min_r2, ch)
+
+
+def _ld_rank_band(band, l, min_r2, ch):
+    """The ranking rule of include/eagle_hip.h section 1b'''iii on band[i, o - 1] = r2 between markers i and i + o (-1.0: no pair) ->
+    (partners int32 (L, l), r2 fp64 (L, l))."""
+    L, window = band.shape
     # column t = 2 (o - 1) + (j > i) holds r2 between i and j = i -+ o: the column index is the rank of a tie
     cols = max(2 * window, l)
     R = np.full((L, cols), -1.0)
     J = np.full((L, cols), -1, dtype=np.int64)
     for o in range(1, min(window, L - 1) + 1):
-        d = np.rint(np.einsum("ij,ij->i", F[:-o], F[o:])).astype(np.int64)          # markers i = 0 .. L - o - 1 with j = i + o
-        c = (n * d - s[:-o] * s[o:]).astype(np.float64)
-        ok = (v[:-o] > 0) & (v[o:] > 0)
+        r2 = band[:-o, o - 1]
+        ok = r2 >= min_r2                                                             # -1.0 is below every min_r2
         if ch is not None:
             ok &= ch[:-o] == ch[o:]
-        with np.errstate(divide="ignore", invalid="ignore"):
-            r2 = (c * c) / (vf[:-o] * vf[o:])
-        r2 = np.where(ok & (r2 >= min_r2), r2, -1.0)
+        r2 = np.where(ok, r2, -1.0)
         R[:-o, 2 * (o - 1) + 1] = r2                                                  # forward: j = i + o
         J[:-o, 2 * (o - 1) + 1] = np.arange(o, L)
         R[o:, 2 * (o - 1)] = r2                                                       # backward: the same pair seen from j
@@ -483,6 +497,70 @@ def ld_partners_host(Mt8, window, l, min_r2, chrom=None):
     r2 = np.take_along_axis(R, order, axis=1)
     part = np.take_along_axis(J, order, axis=1)
     return np.where(r2 >= 0.0, part, -1).astype(np.int32), np.where(r2 >= 0.0, r2, 0.0)
+
+
+# ---- pairwise-complete LD from the .bed file (include/eagle_hip.h section 1b'''iv): the restatements in numpy ----
+def bed_ld_host(codes, window, include=None, min_overlap=1):
+    """The six sums and r2 of include/eagle_hip.h section 1b'''iv in numpy: codes = uint8 (L, n) 2-bit codes (read_bed_codes), include =
+    None, a bool mask of length L or marker indices (the panel) -> (N, D, Si, Sj, Qi, Qj, r2): int64 (Linc, window) x 6 and fp64 (Linc,
+    window), entry [i, o - 1] for the panel markers i and j = i + o.  x = -1, 0, 0, +1, c = [code != 1], u = |x|; N = sum c_i c_j,
+    D = sum x_i x_j, Si = sum x_i c_j, Sj = sum c_i x_j, Qi = sum u_i c_j, Qj = sum c_i u_j; cov = N D - Si Sj, vi = N Qi - Si^2,
+    vj = N Qj - Sj^2; r2 = fl(fl(dc * dc) / fl(dvi * dvj)) where N >= min_overlap, vi > 0 and vj > 0, else -1.0 (and where i + o >= Linc,
+    with zero sums)."""
+    codes = np.asarray(codes, dtype=np.uint8)
+    window, min_overlap = int(window), int(min_overlap)
+    if not 1 <= window <= 256 or min_overlap < 1:
+        raise ValueError("bed_ld_host: 1 <= window <= 256, min_overlap >= 1")
+    inc = _bed_include_mask(include, codes.shape[0], "bed_ld_host")
+    if inc is not None:
+        codes = codes[inc]
+    L = codes.shape[0]
+    if L < 1:
+        raise ValueError("bed_ld_host: include selects no marker")
+    x = np.array([-1.0, 0.0, 0.0, 1.0])[codes]                # fp64 sums of products of 0 / +-1 over n < 2^53 individuals: exact integers
+    c, u = (codes != 1).astype(np.float64), np.abs(x)
+    out = [np.zeros((L, window), dtype=np.int64) for _ in range(6)]
+    r2 = np.full((L, window), -1.0)
+    for o in range(1, min(window, L - 1) + 1):
+        sums = [np.rint(np.einsum("ij,ij->i", a[:-o], b[o:])).astype(np.int64)
+                for a, b in ((c, c), (x, x), (x, c), (c, x), (u, c), (c, u))]
+        for dst, v in zip(out, sums):
+            dst[:-o, o - 1] = v
+        N, D, Si, Sj, Qi, Qj = sums
+        cov, vi, vj = N * D - Si * Sj, N * Qi - Si * Si, N * Qj - Sj * Sj
+        ok = (N >= min_overlap) & (vi > 0) & (vj > 0)
+        dc = cov.astype(np.float64)
+        den = np.where(ok, vi.astype(np.float64) * vj.astype(np.float64), 1.0)
+        r2[:-o, o - 1] = np.where(ok, (dc * dc) / den, -1.0)
+    return (*out, r2)
+
+
+def bed_ld_mask_host(codes, window, r2, include=None, min_overlap=1):
+    """rcpp_api.bed_ld_window restated in numpy -> uint64 (Linc, ceil(window / 64)): bit o - 1 of panel marker i is set iff the pair
+    (i, i + o) is comparable and (double)cov * (double)cov > r2 * ((double)vi * (double)vj) (bed_ld_host's sums)."""
+    t = np.float64(r2)
+    if not 0.0 <= t <= 1.0:
+        raise ValueError("bed_ld_mask_host: r2 must be in [0, 1]")
+    N, D, Si, Sj, Qi, Qj, _ = bed_ld_host(codes, window, include, min_overlap)
+    cov, vi, vj = N * D - Si * Sj, N * Qi - Si * Si, N * Qj - Sj * Sj
+    dc = cov.astype(np.float64)
+    hit = (N >= int(min_overlap)) & (vi > 0) & (vj > 0) & (dc * dc > t * (vi.astype(np.float64) * vj.astype(np.float64)))
+    bits = np.zeros((N.shape[0], (int(window) + 63) // 64 * 64), dtype=np.uint8)
+    bits[:, :int(window)] = hit
+    return np.ascontiguousarray(np.packbits(bits, axis=1, bitorder="little")).view("<u8").astype(np.uint64)
+
+
+def bed_ld_partners_host(codes, window, l, min_r2, include=None, min_overlap=1, chrom=None):
+    """rcpp_api.bed_ld_partners restated in numpy -> (partners int32 (Linc, l), r2 fp64 (Linc, l)): ld_partners_host's ranking on
+    bed_ld_host's r2 band; chrom by panel marker."""
+    l, min_r2 = int(l), float(min_r2)
+    if not 1 <= l <= LDKNN_MAX_PARTNERS or not 0.0 <= min_r2 <= 1.0:
+        raise ValueError("bed_ld_partners_host: 1 <= l <= %d, 0 <= min_r2 <= 1" % LDKNN_MAX_PARTNERS)
+    band = bed_ld_host(codes, window, include, min_overlap)[6]
+    ch = None if chrom is None else np.asarray(chrom).ravel()
+    if ch is not None and ch.size != band.shape[0]:
+        raise ValueError("bed_ld_partners_host: chrom holds %d entries, the panel %d markers" % (ch.size, band.shape[0]))
+    return _ld_rank_band(band, l, min_r2, ch)
 
 
 def impute_ldknn_host(codes, partners, k, min_votes, min_overlap):
@@ -537,7 +615,7 @@ def _copy_bim_fam(src_bim, out_bim, src_fam, out_fam):
 
 
 def ImputeBed(bed, geno, out_prefix, k=10, K=64, min_votes=1, availmemGb=8, message=None, device=0, pairwise=False, min_overlap=1,
-              local=None, window=50, min_r2=0.0, local_min_overlap=4, map=None):
+              local=None, window=50, min_r2=0.0, local_min_overlap=4, map=None, ld_from="panel", ld_min_overlap=None):
     """kNN imputation of the missing genotypes of a PLINK binary fileset -> {"bed": the new .bed file, "n_missing", "by_vote",
     "by_fallback": totals, "counts": int32 (L, 2) per marker}.  bed = the .bed file (or prefix) that `geno` was ingested from.
     The neighbours come from the ingested panel (rcpp_api.sample_ibs on geno["asciifileM"], knn_distance, rcpp_api.knn_rows: the K
@@ -553,13 +631,19 @@ def ImputeBed(bed, geno, out_prefix, k=10, K=64, min_votes=1, availmemGb=8, mess
     missing genotype takes the rounded mean dosage of the k <= 64 individuals called at its marker that are nearest over those
     partners, among the individuals compared over at least local_min_overlap of them (rcpp_api.bed_impute_ldknn).  For panels whose
     members are all about equally related genome-wide (MAGIC, NAM, diversity panels), where the close relative changes from segment
-    to segment.  K, pairwise and min_overlap are ignored in this mode; the result carries "partners" as well."""
+    to segment.  K, pairwise and min_overlap are ignored in this mode; the result carries "partners" as well.
+    ld_from="bed" (with local=; default "panel", and then nothing here differs from the lines above) takes the partner lists from the
+    input .bed file itself instead, over the whole file: r2 of every pair of markers over the individuals called at both, at least
+    ld_min_overlap of them (default max(2, n // 10)) -- rcpp_api.bed_ld_partners, include/eagle_hip.h section 1b'''iv -- so that the
+    missing genotypes being imputed do not pull the ranking of the partners towards the heterozygote."""
     say = message or (lambda s: None)
     src_bed, src_bim, src_fam = bed_fileset(bed)
     n, L = int(geno["dim_of_ascii_M"][0]), int(geno["dim_of_ascii_M"][1])
     out_bed, out_bim, out_fam = bed_fileset(str(out_prefix))
     if os.path.abspath(out_bed) == os.path.abspath(src_bed):
         raise ValueError("ImputeBed: out_prefix names the input fileset")
+    if ld_from not in ("panel", "bed"):
+        raise ValueError('ImputeBed: ld_from must be "panel" or "bed"')
     if local is not None:
         errs = []
         map = _ld_map("ImputeBed", map, geno, L, errs.append)
@@ -568,7 +652,11 @@ def ImputeBed(bed, geno, out_prefix, k=10, K=64, min_votes=1, availmemGb=8, mess
         chrom = None if map is None else np.unique(np.asarray([str(c) for c in map["Chr"]]), return_inverse=True)[1].astype(np.int32)
         l = max(1, min(int(local), LDKNN_MAX_PARTNERS))
         k = max(1, min(int(k), LDKNN_MAX_K))
-        partners = rcpp_api.ld_partners(geno["asciifileMt"], (n, L), int(window), l, float(min_r2), chrom, availmemGb, device=device)
+        if ld_from == "bed":
+            mo = max(2, n // 10) if ld_min_overlap is None else int(ld_min_overlap)
+            partners = rcpp_api.bed_ld_partners(src_bed, (n, L), int(window), l, float(min_r2), None, mo, chrom, availmemGb, device=device)
+        else:
+            partners = rcpp_api.ld_partners(geno["asciifileMt"], (n, L), int(window), l, float(min_r2), chrom, availmemGb, device=device)
         os.makedirs(os.path.dirname(os.path.abspath(out_bed)), exist_ok=True)
         counts = rcpp_api.bed_impute_ldknn(src_bed, (n, L), partners, k, int(min_votes), int(local_min_overlap), out_bed, availmemGb, device=device)
         _copy_bim_fam(src_bim, out_bim, src_fam, out_fam)
@@ -1156,7 +1244,8 @@ def _ld_map(who, map, geno, L, say):
     return map
 
 
-def LDPrune(geno, window=50, r2=0.2, prefer="position", map=None, kb=None, stats=None, outdir=None, availmemGb=8, message=None, device=0):
+def LDPrune(geno, window=50, r2=0.2, prefer="position", map=None, kb=None, stats=None, outdir=None, availmemGb=8, message=None, device=0,
+            bed=None, min_overlap=None):
     """A panel without the markers greedy LD pruning drops -> what FilterMarkers returns: {asciifileM, asciifileMt, dim_of_ascii_M,
     marker_index}, marker_index composed with geno's own.  The pairs in LD come from the device (rcpp_api.ld_window: pairs at most
     `window` <= 256 markers apart with r^2 > `r2`, the exact rule of include/eagle_hip.h section 1b''), the greedy choice is
@@ -1164,7 +1253,12 @@ def LDPrune(geno, window=50, r2=0.2, prefer="position", map=None, kb=None, stats
     of a correlated run stays); prefer="maf" visits them by descending minor allele frequency (`stats`, default MarkerStats(geno)).
     map (ReadBim's dict for this panel, or for its source panel when geno carries marker_index): pairs on different chromosomes do
     not count, nor, with kb=, pairs more than kb kilobases apart.  outdir: default an ld/ directory beside the source files; it must
-    not be the source's directory.  Nothing dropped: the source dict with the identity marker_index, nothing written."""
+    not be the source's directory.  Nothing dropped: the source dict with the identity marker_index, nothing written.
+    bed = the .bed file (or prefix) the panel was ingested from (default None, and then nothing here differs from the lines above): the
+    pairs come from the file itself, every pair of markers counted over the individuals called at both, as PLINK --indep-pairwise
+    counts them (rcpp_api.bed_ld_window, include/eagle_hip.h section 1b'''iv), so that an un-imputed panel can be pruned before it is
+    imputed.  A filtered panel's markers in the file are its marker_index; a pair with fewer than min_overlap both-called individuals
+    (default max(2, n // 10)) is not in LD.  The .fam file must name the panel's n individuals."""
     say = message or (lambda s: None)
     n, L = int(geno["dim_of_ascii_M"][0]), int(geno["dim_of_ascii_M"][1])
 
@@ -1191,7 +1285,27 @@ def LDPrune(geno, window=50, r2=0.2, prefer="position", map=None, kb=None, stats
     outdir = os.path.abspath(outdir) if outdir else os.path.join(srcdir, "ld")
     if outdir == srcdir or outdir == os.path.dirname(os.path.abspath(geno["asciifileMt"])):
         return fail(" Error: outdir %s holds the source panel; the pruned files need a directory of their own. " % outdir)
-    mask, npairs = rcpp_api.ld_window(geno["asciifileMt"], (n, L), window, r2, availmemGb, device=device, return_pairs=True)
+    if bed is None:
+        mask, npairs = rcpp_api.ld_window(geno["asciifileMt"], (n, L), window, r2, availmemGb, device=device, return_pairs=True)
+    else:
+        src_bed, src_bim, src_fam = bed_fileset(bed)
+        for f in (src_bed, src_bim, src_fam):
+            if not os.path.isfile(f):
+                return fail(" Error: the file %s could not be found. " % f)
+        nfam, Lbed = _count_lines(src_fam), _count_lines(src_bim)
+        if nfam != n:
+            return fail(" Error: %s names %d individuals, the panel holds %d. " % (src_fam, nfam, n))
+        include = None
+        if "marker_index" in geno:
+            idx0 = np.asarray(geno["marker_index"], dtype=np.int64).ravel()
+            if idx0.size != L or (L and (idx0.min() < 0 or idx0.max() >= Lbed or np.any(np.diff(idx0) <= 0))):
+                return fail(" Error: the panel's marker_index does not name %d markers of %s in file order. " % (L, src_bed))
+            include = np.zeros(Lbed, dtype=bool)
+            include[idx0] = True
+        elif Lbed != L:
+            return fail(" Error: %s holds %d markers, the panel %d and no marker_index. " % (src_bed, Lbed, L))
+        mo = max(2, n // 10) if min_overlap is None else int(min_overlap)
+        mask, npairs = rcpp_api.bed_ld_window(src_bed, (n, Lbed), window, r2, include, mo, availmemGb, device=device, return_pairs=True)
     say(" %d pairs of markers within %d markers of each other have r2 above %s. " % (npairs, int(window), r2))
     keep = ld_prune_keep(mask, window, priority=priority, chrom=None if map is None else map["Chr"],
                          pos=None if map is None else map["Pos"], kb=kb)

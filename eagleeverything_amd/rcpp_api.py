@@ -790,6 +790,58 @@ def bed_impute_ldknn(bed_path, dims, partners, k, min_votes, min_overlap, out_be
     return out
 
 
+# ---- pairwise-complete LD from the .bed file (include/eagle_hip.h section 1b'''iv): ld_window / ld_partners over the both-called individuals ----
+def _bed_ld_include(include, nm, who):
+    if include is None:
+        return None
+    inc = np.ascontiguousarray(np.atleast_1d(np.asarray(include)).ravel() != 0, dtype=np.uint8)
+    if inc.size != nm:
+        raise ValueError("%s: include holds %d entries, the file %d markers" % (who, inc.size, nm))
+    return inc
+
+
+def bed_ld_window(bed_path, dims, window=50, r2=0.2, include=None, min_overlap=1, availmemGb=8.0, device=0, return_pairs=False):
+    """eagle_bed_ld_window -> uint64 (Linc, ceil(window / 64)): ld_window's mask from a SNP-major PLINK .bed file of dims = (n individuals,
+    L markers), every pair of markers counted over the individuals called at both (at least min_overlap of them; the rule of
+    include/eagle_hip.h section 1b'''iv).  include: None, or a bool / 0-1 mask of length L that selects the panel; rows and offsets are
+    panel indices.  return_pairs: (mask, number of set bits).  r_api.bed_ld_mask_host is the numpy restatement."""
+    L = _lib.load()
+    nm = max(int(dims[1]), 0)
+    inc = _bed_ld_include(include, nm, "bed_ld_window")
+    linc = nm if inc is None else int(inc.sum())
+    out = np.zeros((linc, (int(window) + 63) // 64 if int(window) > 0 else 1), dtype=np.uint64)
+    pairs = C.c_long(0)
+    _args_first(L.eagle_bed_ld_window, device, (os.fsencode(bed_path), _dims(dims), inc.ctypes.data_as(C.c_void_p) if inc is not None else None,
+                                                int(window), float(r2), int(min_overlap), float(availmemGb),
+                                                out.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(pairs)))
+    return (out, int(pairs.value)) if return_pairs else out
+
+
+def bed_ld_partners(bed_path, dims, window=50, l=16, min_r2=0.0, include=None, min_overlap=1, chrom=None, availmemGb=8.0, device=0,
+                    return_r2=False):
+    """eagle_bed_ld_partners -> int32 (Linc, l): ld_partners' table from a SNP-major PLINK .bed file, r2 of every pair over the individuals
+    called at both markers (at least min_overlap of them, and both markers polymorphic over them; include/eagle_hip.h section 1b'''iv).
+    include as in bed_ld_window; chrom: one whole number per PANEL marker.  return_r2: (partners, fp64 (Linc, l) with 0.0 beside -1).
+    r_api.bed_ld_partners_host is the numpy restatement."""
+    L = _lib.load()
+    nm = max(int(dims[1]), 0)
+    inc = _bed_ld_include(include, nm, "bed_ld_partners")
+    linc = nm if inc is None else int(inc.sum())
+    ch = None
+    if chrom is not None:
+        c = np.atleast_1d(np.asarray(chrom)).ravel()
+        ch = np.ascontiguousarray(c, dtype=np.int32)
+        if ch.size != linc or not np.array_equal(ch, c):
+            raise ValueError("bed_ld_partners: chrom must hold one whole number that fits int32 per panel marker")
+    out = np.zeros((linc, max(int(l), 1)), dtype=np.int32)
+    r2 = np.zeros(out.shape, dtype=np.float64) if return_r2 else None
+    _args_first(L.eagle_bed_ld_partners, device, (os.fsencode(bed_path), _dims(dims), inc.ctypes.data_as(C.c_void_p) if inc is not None else None,
+                                                  int(window), int(l), float(min_r2), int(min_overlap),
+                                                  ch.ctypes.data_as(_c_i32p) if ch is not None else None, float(availmemGb),
+                                                  out.ctypes.data_as(_c_i32p), _dp(r2) if return_r2 else None))
+    return (out, r2) if return_r2 else out
+
+
 # ---- GRM (include/eagle_hip.h section 1b''''): the exact weighted Gram product; weights, centring and PCA are r_api's ----
 WGRAM_MAX_WEIGHT = (1 << 21) - 1
 

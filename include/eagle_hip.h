@@ -536,6 +536,72 @@ int eagle_bed_impute_ldknn(eagle_ctx* ctx, const char* bed_path, const long dims
                            int min_overlap, const char* out_bed_path, double max_memory_in_Gbytes, int32_t* counts_out);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1b'''iv. Pairwise-complete LD between markers from the .bed file (no counterpart in the reference).  The ingested panel has made
+ *     every missing genotype a heterozygote, so 1b'' and the partner lists of 1b'''iii pull r2 towards the heterozygote: two markers in
+ *     perfect LD on inbred lines (x = +-1, p = 1/2) with a share m of each marker's calls missing at random have r2 = (1 - m)^2 there.
+ *     Here a pair of markers is counted over the individuals called at BOTH, as PLINK --indep-pairwise and --r2 count it: the .bed
+ *     file is read itself, where the missing code is still known.
+ *
+ *     Codes as in 1b'''i: 0 = homozygous A1, 1 = missing, 2 = heterozygous, 3 = homozygous A2; individual 4b+q at bits 2q of byte b.
+ *     The unused bit pairs of a row's last byte belong to nobody, whatever bits they hold.  Per marker m and individual a:
+ *         x = -1, 0, 0, +1 for the codes 0, 1, 2, 3;    c = [code != 1];    u = |x|.
+ *     An optional include (L bytes; zero = excluded) selects the PANEL: the Linc included markers in file order.  Every index below
+ *     (i, j, the outputs, chrom) is a panel index, and `window` counts panel markers.  include == NULL is the whole file.
+ *
+ *     For panel markers i != j, six sums over the n individuals, each an exact int32 (k_bedld_tile on the int8 MFMA):
+ *         N  = sum c_i c_j      D  = sum x_i x_j
+ *         Si = sum x_i c_j      Sj = sum c_i x_j
+ *         Qi = sum u_i c_j      Qj = sum c_i u_j
+ *     then in int64:   cov = N D - Si Sj,    vi = N Qi - Si^2,    vj = N Qj - Sj^2.
+ *     The pair is COMPARABLE iff N >= min_overlap, vi > 0 and vj > 0.  vi and vj belong to the PAIR: a marker that is polymorphic over
+ *     everybody can be monomorphic over the individuals it shares with j.  For a comparable pair, in fp64 in exactly the order of 1b''
+ *     and 1b'''iii (correctly rounded products and one quotient, no sum, so nothing contracts into an FMA):
+ *         IN LD AT t  iff  (double)cov * (double)cov > t * ((double)vi * (double)vj)
+ *         r2 = fl( fl(dc * dc) / fl(dvi * dvj) ),   dc = (double)cov, dvi = (double)vi, dvj = (double)vj.
+ *     A pair that is not comparable is in LD with nothing, and its r2 entry is -1.0.
+ *
+ *     When the file holds no missing code, N = n, Si = s_i and Qi = q_i of 1b'': mask and r2 are then bit for bit those of
+ *     eagle_ld_window and eagle_ld_partners on the ingested panel (with min_overlap <= n).
+ *
+ *     Limits: n <= 0x3fffffff (every int64 term then stays below 2^61), window in [1, 256], min_overlap >= 1, Linc >= 1, and
+ *     Linc < 2^31 for the partners call.
+ *
+ *     Windows.  The rows go through the pinned staging ring of eagle_bed_marker_counts.  With rb = ceil(n / 4) bytes per row and
+ *     ld = 16 ceil(n / 16):
+ *         S    = max(1, floor(min(64 MiB, max_memory_in_Gbytes * 1e9 / 4) / rb))   file rows the staging budget holds
+ *         Wmax = max(1024, floor(2^27 / ld))                                        so that one operand image stays under 128 MiB
+ *                (the partners call: also at most max(1024, floor(2^28 / (8 window))) markers, the band cap of eagle_ld_partners)
+ *     A window that starts at panel marker lo ends at the largest hi <= Linc with hi - lo <= Wmax whose file rows span at most S rows
+ *     (file row of marker hi - 1, minus that of marker lo, plus 1) -- but it holds at least `need` markers (or the rest of the panel),
+ *     need = window + 1 for eagle_bed_ld_window and 2 window + 1 for eagle_bed_ld_partners; the staging buffer grows to the widest such
+ *     span when include is sparse.  The window is staged as that span of file rows, and k_bed_ld_pack writes three marker-major int8
+ *     operand images X, C, U of its panel markers alone.  The next window starts at hi - window (eagle_bed_ld_window: it writes the
+ *     mask rows of the last `window` markers again, now with all their partners) or at hi - 2 window (eagle_bed_ld_partners: partner
+ *     rows are written for the markers that have `window` held markers, or the panel's end, on both sides); the last window is the one
+ *     with hi = Linc.  Consecutive windows thus overlap as those of eagle_ld_window and eagle_ld_partners do, and the result does
+ *     not depend on the window size.
+ *
+ *     Single device: a multi-device context works on its first device.  Argument errors (EAGLE_ERR_ARG: a NULL pointer, dims <= 0,
+ *     and those named below) are decided before the context is used; with ctx == NULL their text is in eagle_open_error().
+ * ------------------------------------------------------------------------------------------- */
+
+/* mask_out (Linc x W uint64, W = ceil(window / 64)) and *npairs_out as those of eagle_ld_window, by panel marker, under the rule
+ * above, from the SNP-major .bed file bed_path (the format, the checks and the error codes of eagle_create_ascii_from_bed;
+ * dims = (n, L)).  include: L bytes or NULL (may be NULL; every other pointer may not).
+ * EAGLE_ERR_ARG: n > 0x3fffffff, window outside [1, 256], r2 outside [0, 1] or NaN, min_overlap < 1, an include that selects no marker. */
+int eagle_bed_ld_window(eagle_ctx* ctx, const char* bed_path, const long dims[2], const uint8_t* include, long window, double r2,
+                        int min_overlap, double max_memory_in_Gbytes, uint64_t* mask_out, long* npairs_out);
+
+/* partners_out (Linc x l int32) and r2_out (Linc x l fp64, may be NULL) as those of eagle_ld_partners, by panel marker: the candidates of
+ * i are the panel markers j, 1 <= |j - i| <= window, whose pair with i is comparable with r2 >= min_r2, on i's chromosome when chrom
+ * (Linc int32, by panel marker; may be NULL) is given; ranked by k_ld_partners under the rule of 1b'''iii on the fp64 band of
+ * k_bedld_tile's r2 mode.
+ * EAGLE_ERR_ARG: n > 0x3fffffff, window outside [1, 256], l outside [1, EAGLE_LDKNN_MAX_PARTNERS], min_r2 outside [0, 1] or NaN,
+ * min_overlap < 1, an include that selects no marker, Linc >= 2^31. */
+int eagle_bed_ld_partners(eagle_ctx* ctx, const char* bed_path, const long dims[2], const uint8_t* include, long window, int l, double min_r2,
+                          int min_overlap, const int32_t* chrom, double max_memory_in_Gbytes, int32_t* partners_out, double* r2_out);
+
+/* ---------------------------------------------------------------------------------------------
  * 1b''''. Genomic relationship matrix (no counterpart that the reference calls: its VanRaden G, E/R/GenomicRel.R, is unused): the one
  *     Gram product the matrices of EIGENSTRAT / PLINK / GCTA and their principal components need, with a weight per marker.  With
  *     g in {-1, 0, +1} = AA, AB, BB as everywhere in this library and integer weights q_m < 2^21,
