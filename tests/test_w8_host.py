@@ -7,6 +7,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import exact_w8
+
 from eagleeverything_amd import _lib
 
 KMAX = 6
@@ -68,18 +70,12 @@ def test_work_list_covers_every_tile_of_every_group_once(nt, k, T, maxp, upper, 
 
 
 def _slices(F, k=KMAX):
-    mx = np.abs(F).max(axis=1)
-    f, e = np.frexp(mx)
-    e = np.where(mx > 0, np.where(f <= 0.98, e - 1, e), 0).astype(np.int64)
-    Q = np.rint(np.ldexp(F, (8 * k - e - 2)[:, None])).astype(np.int64)
-    Q[mx == 0] = 0
-    digs = []
-    for _ in range(k):
-        d = ((Q + 128) & 255) - 128
-        Q = (Q - d) >> 8
-        digs.append(d.astype(np.float64))
-    assert np.all(Q == 0)
-    return e, digs[::-1], mx
+    """(e_i, digit planes as float64, row maxima) of the off-diagonal part: the slicer of tests/exact_w8.py, rounding as llrint does."""
+    assert k == KMAX
+    e, digs = exact_w8.planes(F, exact=False)
+    Fo = np.array(F, dtype=np.float64)
+    np.fill_diagonal(Fo, 0.0)
+    return e, [d.astype(np.float64) for d in digs], np.abs(Fo).max(axis=1)
 
 
 def _stats(M):
