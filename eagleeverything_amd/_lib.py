@@ -69,6 +69,11 @@ SIGNATURES = {
     "eagle_bed_ld_window": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, C.c_void_p, C.c_long, C.c_double, C.c_int, C.c_double, C.POINTER(C.c_uint64), c_lp]),
     "eagle_bed_ld_partners": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, C.c_void_p, C.c_long, C.c_int, C.c_double, C.c_int, C.POINTER(C.c_int32),
                                         C.c_double, C.POINTER(C.c_int32), c_dp]),
+    "eagle_ld_stats": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, C.c_long, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_long, C.POINTER(C.c_int64),
+                                 C.c_long, C.c_double, C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.POINTER(C.c_int64)]),
+    "eagle_bed_ld_stats": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, C.c_void_p, C.c_long, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_long,
+                                     C.POINTER(C.c_int64), C.c_long, C.c_double, C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_uint64),
+                                     C.POINTER(C.c_int64)]),
     "eagle_bed_impute_ldknn": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p,
                                          C.c_double, C.POINTER(C.c_int32)]),
     "eagle_weighted_gram": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, C.POINTER(C.c_uint32), C.c_double, C.POINTER(C.c_int64)]),

@@ -272,4 +272,25 @@ static inline SidecarWindow sidecar_window(long c_first, long c_last, long cols,
     const bool whole_rows = c_first == 0 && c_last + 1 == cols;
     return {b0, whole_rows ? row_bytes : c_last / 4 + 1 - b0, (int)(c_first % 4)};
 }
+
+// ------------------------------------------------------------------------------------------------
+// LD scores and the LD decay curve (include/eagle_hip.h section 1b'''v): the argument rule of eagle_ld_stats / eagle_bed_ld_stats.
+// ------------------------------------------------------------------------------------------------
+// What is wrong with a call over `markers` panel markers, or NULL: window in [1, 256]; markers < 2^31; markers * window <= 2^33 (at
+// most that many pairs of at most 2^30 each: no bin sum passes 2^63); max_dist > 0 needs pos; nbins in [0, 512]; with edges and
+// nbins > 0 the nbins + 1 edges increase strictly and both bin outputs are given.  Reads edges[0 .. nbins] and nothing else.
+static inline const char* ld_stats_arg_error(long markers, long window, bool has_pos, long max_dist, const int64_t* edges, long nbins,
+                                             bool has_bin_outputs) {
+    if (window < 1 || window > 256) return "window must be in [1, 256]";
+    if (markers > 0x7fffffffL) return "2^31 markers or more";
+    if (markers * window > (1L << 33)) return "markers x window above 2^33 (a bin sum could pass 2^63)";
+    if (max_dist > 0 && !has_pos) return "max_dist needs pos";
+    if (nbins < 0 || nbins > 512) return "nbins outside [0, 512]";
+    if (edges && nbins > 0) {
+        if (!has_bin_outputs) return "NULL argument (the bin outputs, with edges given)";
+        for (long b = 0; b < nbins; b++)
+            if (!(edges[b] < edges[b + 1])) return "edges must be strictly increasing";
+    }
+    return nullptr;
+}
 #endif

@@ -1282,31 +1282,19 @@ extern "C" int eagle_ld_window(eagle_ctx* ctx, const char* f_name_ascii_Mt, cons
     return EAGLE_OK;
 }
 
-// Ranked partner lists.  The panel is worked on in CORE ranges of markers: the rows held for a core [c0, c1) are [max(0, c0 - window),
-// min(L, c1 + window)) -- all candidates of its markers on both sides -- the tile kernel writes the r^2 band of the rows held, and
-// k_ld_partners the partner rows of the core alone, so every output word is written once, from a band that held all of the marker's
-// candidates: the result does not depend on the cores' size.  A resident image is cut only where its band would pass 256 MiB; a file
-// that is not resident is read in row windows of the streamed scans' size (at least 1,024 rows: twice the widest overlap and a core).
-extern "C" int eagle_ld_partners(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long dims[2], long window, int l, double min_r2,
-                                 const int32_t* chrom, double max_memory_in_Gbytes, int32_t* partners_out, double* r2_out) {
-    if (!f_name_ascii_Mt || !dims || !partners_out) return qc_fail(ctx, EAGLE_ERR_ARG, "ld_partners: NULL argument");
-    const long n = dims[0], L = dims[1];
-    if (n <= 0 || L <= 0) return qc_fail(ctx, EAGLE_ERR_ARG, "ld_partners: dims must be positive");
-    if (L > 0x7fffffffL) return qc_fail(ctx, EAGLE_ERR_ARG, "ld_partners: 2^31 markers or more");
-    if (window < 1 || window > 256) return qc_fail(ctx, EAGLE_ERR_ARG, "ld_partners: window must be in [1, 256]");
-    if (l < 1 || l > EAGLE_LDKNN_MAX_PARTNERS) return qc_fail(ctx, EAGLE_ERR_ARG, "ld_partners: l outside [1, 32]");
-    if (!(min_r2 >= 0.0 && min_r2 <= 1.0)) return qc_fail(ctx, EAGLE_ERR_ARG, "ld_partners: min_r2 must be in [0, 1]");
-    if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "ld_partners: no context");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+// Ranked partner lists, LD scores and the decay curve.  The panel is worked on in CORE ranges of markers: the rows held for a core
+// [c0, c1) are [max(0, c0 - window), min(L, c1 + window)) -- all candidates of its markers on both sides -- the tile kernel writes the
+// r^2 band of the rows held, and consume(band, rows held, c0 - lo, c1 - lo, lo) works on the core alone (k_ld_partners: the partner
+// rows; k_ld_reduce: the sums), so every output word is written once, from a band that held all of the marker's candidates, and every
+// pair belongs to one core: the result does not depend on the cores' size.  A resident image is cut only where its band would pass
+// 256 MiB; a file that is not resident is read in row windows of the streamed scans' size (at least 1,024 rows: twice the widest
+// overlap and a core).
+namespace {
+
+template <class Consume>
+int ld_panel_cores(eagle_ctx* ctx, const char* f_name_ascii_Mt, long n, long L, long window, double max_memory_in_Gbytes, Consume consume) {
     const int threads = host_threads();
-    const size_t cells = (size_t)L * (size_t)l;
-    DevBuf part, r2, d_chrom, counts, sq, band, win;
-    HIPCHK(ctx, part.alloc(sizeof(int32_t) * cells));
-    HIPCHK(ctx, r2.alloc(sizeof(double) * cells));
-    if (chrom) {
-        HIPCHK(ctx, d_chrom.alloc(sizeof(int32_t) * (size_t)L));
-        HIPCHK(ctx, hipMemcpyAsync(d_chrom.p, chrom, sizeof(int32_t) * (size_t)L, hipMemcpyHostToDevice, ctx->stream));
-    }
+    DevBuf counts, sq, band, win;
     const GenoEntry* src = nullptr;
     int rc = eagle_get_resident(ctx, f_name_ascii_Mt, L, n, max_memory_in_Gbytes, threads, &src);
     if (rc != EAGLE_OK && rc != EAGLE_STREAM) return rc;
@@ -1332,14 +1320,122 @@ extern "C" int eagle_ld_partners(eagle_ctx* ctx, const char* f_name_ascii_Mt, co
         }
         rc = ld_tile_sq(ctx, img, nr, n, ld, counts.as<int32_t>(), sq.as<int32_t>());
         if (!rc) rc = eagle_dev_ld_r2band(ctx, img, nr, n, ld, sq.as<int32_t>(), window, band.as<double>(), ctx->stream);
-        if (!rc) rc = eagle_dev_ld_partners(ctx, band.as<double>(), nr, window, c0 - lo, c1 - lo, lo, chrom ? d_chrom.as<int32_t>() : nullptr, min_r2, l,
-                                            part.as<int32_t>(), r2.as<double>(), ctx->stream);
+        if (!rc) rc = consume(band.as<double>(), nr, c0 - lo, c1 - lo, lo);
         if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
     }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // the band and the window leave with this frame
+    return EAGLE_OK;
+}
+
+// What eagle_ld_stats and eagle_bed_ld_stats hold on the device besides the band, and the argument checks they share (include/
+// eagle_hip.h section 1b'''v; lp = the panel's markers; the rule itself is eagle_host.h's ld_stats_arg_error).
+struct LdStatsBufs {
+    DevBuf U, cnt, chrom, pos, edges, bsum, bpairs;
+    int nbins = 0;
+    long lp = 0;
+};
+
+int ld_stats_check(eagle_ctx* ctx, const char* who, long lp, long window, const int64_t* pos, long max_dist, const int64_t* edges, long nbins,
+                   const void* bin_sum_out, const void* bin_pairs_out) {
+    const char* bad = ld_stats_arg_error(lp, window, pos != nullptr, max_dist, edges, nbins, bin_sum_out && bin_pairs_out);
+    if (!bad) return EAGLE_OK;
+    char msg[160];
+    snprintf(msg, sizeof msg, "%s: %s", who, bad);
+    return qc_fail(ctx, EAGLE_ERR_ARG, msg);
+}
+
+int ld_stats_begin(eagle_ctx* ctx, LdStatsBufs& b, long lp, const int32_t* chrom, const int64_t* pos, const int64_t* edges, long nbins) {
+    b.lp = lp;
+    b.nbins = edges ? (int)nbins : 0;
+    HIPCHK(ctx, b.U.alloc(sizeof(uint64_t) * (size_t)lp));
+    HIPCHK(ctx, b.cnt.alloc(sizeof(int32_t) * (size_t)lp));
+    if (chrom) {
+        HIPCHK(ctx, b.chrom.alloc(sizeof(int32_t) * (size_t)lp));
+        HIPCHK(ctx, hipMemcpyAsync(b.chrom.p, chrom, sizeof(int32_t) * (size_t)lp, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (pos) {
+        HIPCHK(ctx, b.pos.alloc(sizeof(int64_t) * (size_t)lp));
+        HIPCHK(ctx, hipMemcpyAsync(b.pos.p, pos, sizeof(int64_t) * (size_t)lp, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (b.nbins) {
+        HIPCHK(ctx, b.edges.alloc(sizeof(int64_t) * (size_t)(b.nbins + 1)));
+        HIPCHK(ctx, b.bsum.alloc(sizeof(uint64_t) * (size_t)b.nbins));
+        HIPCHK(ctx, b.bpairs.alloc(sizeof(int64_t) * (size_t)b.nbins));
+        HIPCHK(ctx, hipMemcpyAsync(b.edges.p, edges, sizeof(int64_t) * (size_t)(b.nbins + 1), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(b.bsum.p, 0, sizeof(uint64_t) * (size_t)b.nbins, ctx->stream));   // once, before the first core
+        HIPCHK(ctx, hipMemsetAsync(b.bpairs.p, 0, sizeof(int64_t) * (size_t)b.nbins, ctx->stream));
+    }
+    return EAGLE_OK;
+}
+
+int ld_stats_core(eagle_ctx* ctx, LdStatsBufs& b, const double* band, long nr, long window, long c_lo, long c_hi, long g0, long max_dist) {
+    return eagle_dev_ld_reduce(ctx, band, nr, window, c_lo, c_hi, g0, b.chrom.p ? b.chrom.as<int32_t>() : nullptr,
+                               b.pos.p ? b.pos.as<int64_t>() : nullptr, max_dist, b.nbins ? b.edges.as<int64_t>() : nullptr, b.nbins,
+                               b.U.as<uint64_t>(), b.cnt.as<int32_t>(), b.nbins ? b.bsum.as<uint64_t>() : nullptr,
+                               b.nbins ? b.bpairs.as<int64_t>() : nullptr, ctx->stream);
+}
+
+int ld_stats_end(eagle_ctx* ctx, LdStatsBufs& b, uint64_t* U_out, int32_t* cnt_out, uint64_t* bin_sum_out, int64_t* bin_pairs_out) {
+    HIPCHK(ctx, hipMemcpyAsync(U_out, b.U.p, sizeof(uint64_t) * (size_t)b.lp, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(cnt_out, b.cnt.p, sizeof(int32_t) * (size_t)b.lp, hipMemcpyDeviceToHost, ctx->stream));
+    if (b.nbins) {
+        HIPCHK(ctx, hipMemcpyAsync(bin_sum_out, b.bsum.p, sizeof(uint64_t) * (size_t)b.nbins, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(bin_pairs_out, b.bpairs.p, sizeof(int64_t) * (size_t)b.nbins, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return EAGLE_OK;
+}
+
+}  // namespace
+
+extern "C" int eagle_ld_partners(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long dims[2], long window, int l, double min_r2,
+                                 const int32_t* chrom, double max_memory_in_Gbytes, int32_t* partners_out, double* r2_out) {
+    if (!f_name_ascii_Mt || !dims || !partners_out) return qc_fail(ctx, EAGLE_ERR_ARG, "ld_partners: NULL argument");
+    const long n = dims[0], L = dims[1];
+    if (n <= 0 || L <= 0) return qc_fail(ctx, EAGLE_ERR_ARG, "ld_partners: dims must be positive");
+    if (L > 0x7fffffffL) return qc_fail(ctx, EAGLE_ERR_ARG, "ld_partners: 2^31 markers or more");
+    if (window < 1 || window > 256) return qc_fail(ctx, EAGLE_ERR_ARG, "ld_partners: window must be in [1, 256]");
+    if (l < 1 || l > EAGLE_LDKNN_MAX_PARTNERS) return qc_fail(ctx, EAGLE_ERR_ARG, "ld_partners: l outside [1, 32]");
+    if (!(min_r2 >= 0.0 && min_r2 <= 1.0)) return qc_fail(ctx, EAGLE_ERR_ARG, "ld_partners: min_r2 must be in [0, 1]");
+    if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "ld_partners: no context");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t cells = (size_t)L * (size_t)l;
+    DevBuf part, r2, d_chrom;
+    HIPCHK(ctx, part.alloc(sizeof(int32_t) * cells));
+    HIPCHK(ctx, r2.alloc(sizeof(double) * cells));
+    if (chrom) {
+        HIPCHK(ctx, d_chrom.alloc(sizeof(int32_t) * (size_t)L));
+        HIPCHK(ctx, hipMemcpyAsync(d_chrom.p, chrom, sizeof(int32_t) * (size_t)L, hipMemcpyHostToDevice, ctx->stream));
+    }
+    int rc = ld_panel_cores(ctx, f_name_ascii_Mt, n, L, window, max_memory_in_Gbytes, [&](const double* band, long nr, long c_lo, long c_hi, long g0) {
+        return eagle_dev_ld_partners(ctx, band, nr, window, c_lo, c_hi, g0, chrom ? d_chrom.as<int32_t>() : nullptr, min_r2, l, part.as<int32_t>(),
+                                     r2.as<double>(), ctx->stream);
+    });
+    if (rc) return rc;
     HIPCHK(ctx, hipMemcpyAsync(partners_out, part.p, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, ctx->stream));
     if (r2_out) HIPCHK(ctx, hipMemcpyAsync(r2_out, r2.p, sizeof(double) * cells, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return EAGLE_OK;
+}
+
+// eagle_ld_partners' cores with k_ld_reduce in k_ld_partners' place (include/eagle_hip.h section 1b'''v)
+extern "C" int eagle_ld_stats(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long dims[2], long window, const int32_t* chrom, const int64_t* pos,
+                              long max_dist, const int64_t* edges, long nbins, double max_memory_in_Gbytes, uint64_t* U_out, int32_t* cnt_out,
+                              uint64_t* bin_sum_out, int64_t* bin_pairs_out) {
+    if (!f_name_ascii_Mt || !dims || !U_out || !cnt_out) return qc_fail(ctx, EAGLE_ERR_ARG, "ld_stats: NULL argument");
+    const long n = dims[0], L = dims[1];
+    if (n <= 0 || L <= 0) return qc_fail(ctx, EAGLE_ERR_ARG, "ld_stats: dims must be positive");
+    if (int rc = ld_stats_check(ctx, "ld_stats", L, window, pos, max_dist, edges, nbins, bin_sum_out, bin_pairs_out)) return rc;
+    if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "ld_stats: no context");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    LdStatsBufs b;
+    int rc = ld_stats_begin(ctx, b, L, chrom, pos, edges, nbins);
+    if (rc) return rc;
+    rc = ld_panel_cores(ctx, f_name_ascii_Mt, n, L, window, max_memory_in_Gbytes, [&](const double* band, long nr, long c_lo, long c_hi, long g0) {
+        return ld_stats_core(ctx, b, band, nr, window, c_lo, c_hi, g0, max_dist);
+    });
+    if (rc) return rc;
+    return ld_stats_end(ctx, b, U_out, cnt_out, bin_sum_out, bin_pairs_out);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1491,9 +1587,38 @@ extern "C" int eagle_bed_ld_window(eagle_ctx* ctx, const char* bed_path, const l
 }
 
 // eagle_ld_partners' cores over panel markers: the window held for a core [c0, c1) is [lo, hi) = [max(0, c0 - window), min(Linc,
-// c1 + window)); the tile kernel writes the r2 band of the markers held and k_ld_partners the partner rows of the core alone.  The
-// first core starts at 0 = lo, every later one at lo + window; a window holds at least 2 window + 1 markers (or the rest of the panel),
-// so that the next one starts after it did.
+// c1 + window)); the tile kernel writes the r2 band of the markers held and consume(band, markers held, c0 - lo, c1 - lo, lo) works
+// on the core alone (k_ld_partners: the partner rows; k_ld_reduce: the sums).  The first core starts at 0 = lo, every later one at
+// lo + window; a window holds at least 2 window + 1 markers (or the rest of the panel), so that the next one starts after it did.
+namespace {
+
+template <class Consume>
+int bedld_panel_cores(eagle_ctx* ctx, const char* bed_path, long n, long L, const uint8_t* include, long linc, long window, int min_overlap,
+                      double max_memory_in_Gbytes, Consume consume) {
+    BedLdPanel pl;
+    const long need = 2 * window + 1;
+    auto next_of = [&](long hi) { return hi >= linc ? linc : hi - 2 * window; };              // c1 = hi - window; the next window starts at c1 - window
+    const long band_rows = std::max(1024L, (long)(((size_t)256 << 20) / (sizeof(double) * (size_t)window)));   // eagle_ld_partners' cap
+    int rc = bedld_open(pl, ctx, bed_path, n, L, include, linc, max_memory_in_Gbytes, band_rows, need, next_of);
+    if (rc) return rc;
+    DevBuf band;
+    HIPCHK(ctx, band.alloc(sizeof(double) * (size_t)pl.wmax * (size_t)window));
+    for (long lo = 0; lo < linc;) {
+        const long hi = pl.window_end(lo, need), nr = hi - lo;
+        const long c0 = lo == 0 ? 0 : lo + window, c1 = hi >= linc ? linc : hi - window;
+        rc = pl.stage(lo, hi);
+        if (!rc) rc = eagle_dev_bedld_r2band(ctx, pl.X.as<int8_t>(), pl.C.as<int8_t>(), pl.U.as<int8_t>(), nr, n, pl.ld, window, min_overlap,
+                                             band.as<double>(), ctx->stream);
+        if (!rc) rc = consume(band.as<double>(), nr, c0 - lo, c1 - lo, lo);
+        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+        lo = next_of(hi);
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // the operand images and the band leave with this frame
+    return EAGLE_OK;
+}
+
+}  // namespace
+
 extern "C" int eagle_bed_ld_partners(eagle_ctx* ctx, const char* bed_path, const long dims[2], const uint8_t* include, long window, int l,
                                      double min_r2, int min_overlap, const int32_t* chrom, double max_memory_in_Gbytes, int32_t* partners_out,
                                      double* r2_out) {
@@ -1509,36 +1634,50 @@ extern "C" int eagle_bed_ld_partners(eagle_ctx* ctx, const char* bed_path, const
     if (linc < 1) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_ld_partners: include selects no marker");
     if (linc > 0x7fffffffL) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_ld_partners: 2^31 markers or more");
     if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_ld_partners: no context");
-    BedLdPanel pl;
-    const long need = 2 * window + 1;
-    auto next_of = [&](long hi) { return hi >= linc ? linc : hi - 2 * window; };              // c1 = hi - window; the next window starts at c1 - window
-    const long band_rows = std::max(1024L, (long)(((size_t)256 << 20) / (sizeof(double) * (size_t)window)));   // eagle_ld_partners' cap
-    int rc = bedld_open(pl, ctx, bed_path, n, L, include, linc, max_memory_in_Gbytes, band_rows, need, next_of);
-    if (rc) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t cells = (size_t)linc * (size_t)l;
-    DevBuf part, r2, d_chrom, band;
+    DevBuf part, r2, d_chrom;
     HIPCHK(ctx, part.alloc(sizeof(int32_t) * cells));
     HIPCHK(ctx, r2.alloc(sizeof(double) * cells));
-    HIPCHK(ctx, band.alloc(sizeof(double) * (size_t)pl.wmax * (size_t)window));
     if (chrom) {
         HIPCHK(ctx, d_chrom.alloc(sizeof(int32_t) * (size_t)linc));
         HIPCHK(ctx, hipMemcpyAsync(d_chrom.p, chrom, sizeof(int32_t) * (size_t)linc, hipMemcpyHostToDevice, ctx->stream));
     }
-    for (long lo = 0; lo < linc;) {
-        const long hi = pl.window_end(lo, need), nr = hi - lo;
-        const long c0 = lo == 0 ? 0 : lo + window, c1 = hi >= linc ? linc : hi - window;
-        rc = pl.stage(lo, hi);
-        if (!rc) rc = eagle_dev_bedld_r2band(ctx, pl.X.as<int8_t>(), pl.C.as<int8_t>(), pl.U.as<int8_t>(), nr, n, pl.ld, window, min_overlap,
-                                             band.as<double>(), ctx->stream);
-        if (!rc) rc = eagle_dev_ld_partners(ctx, band.as<double>(), nr, window, c0 - lo, c1 - lo, lo, chrom ? d_chrom.as<int32_t>() : nullptr, min_r2, l,
-                                            part.as<int32_t>(), r2.as<double>(), ctx->stream);
-        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-        lo = next_of(hi);
-    }
+    int rc = bedld_panel_cores(ctx, bed_path, n, L, include, linc, window, min_overlap, max_memory_in_Gbytes,
+                               [&](const double* band, long nr, long c_lo, long c_hi, long g0) {
+        return eagle_dev_ld_partners(ctx, band, nr, window, c_lo, c_hi, g0, chrom ? d_chrom.as<int32_t>() : nullptr, min_r2, l, part.as<int32_t>(),
+                                     r2.as<double>(), ctx->stream);
+    });
+    if (rc) return rc;
     HIPCHK(ctx, hipMemcpyAsync(partners_out, part.p, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, ctx->stream));
     if (r2_out) HIPCHK(ctx, hipMemcpyAsync(r2_out, r2.p, sizeof(double) * cells, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return EAGLE_OK;
+}
+
+// eagle_bed_ld_partners' cores with k_ld_reduce in k_ld_partners' place (include/eagle_hip.h section 1b'''v); chrom / pos by panel marker
+extern "C" int eagle_bed_ld_stats(eagle_ctx* ctx, const char* bed_path, const long dims[2], const uint8_t* include, long window, int min_overlap,
+                                  const int32_t* chrom, const int64_t* pos, long max_dist, const int64_t* edges, long nbins,
+                                  double max_memory_in_Gbytes, uint64_t* U_out, int32_t* cnt_out, uint64_t* bin_sum_out, int64_t* bin_pairs_out) {
+    if (!bed_path || !dims || !U_out || !cnt_out) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_ld_stats: NULL argument");
+    const long n = dims[0], L = dims[1];
+    if (n <= 0 || L <= 0) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_ld_stats: dims must be positive");
+    if (n > 0x3fffffffL) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_ld_stats: 2^30 individuals or more");
+    if (min_overlap < 1) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_ld_stats: min_overlap must be at least 1");
+    const long linc = bedld_count(include, L);
+    if (linc < 1) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_ld_stats: include selects no marker");
+    if (int rc = ld_stats_check(ctx, "bed_ld_stats", linc, window, pos, max_dist, edges, nbins, bin_sum_out, bin_pairs_out)) return rc;
+    if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_ld_stats: no context");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    LdStatsBufs b;
+    int rc = ld_stats_begin(ctx, b, linc, chrom, pos, edges, nbins);
+    if (rc) return rc;
+    rc = bedld_panel_cores(ctx, bed_path, n, L, include, linc, window, min_overlap, max_memory_in_Gbytes,
+                           [&](const double* band, long nr, long c_lo, long c_hi, long g0) {
+        return ld_stats_core(ctx, b, band, nr, window, c_lo, c_hi, g0, max_dist);
+    });
+    if (rc) return rc;
+    return ld_stats_end(ctx, b, U_out, cnt_out, bin_sum_out, bin_pairs_out);
 }
 
 // The loci's rows are gathered into a 64-row image first (k_gather_rows_i8: from the resident image, else from their own lines of

@@ -94,6 +94,13 @@ int eagle_dev_ld_r2band(eagle_ctx* ctx, const int8_t* Mt8, long rows, long n, lo
 // both sides must lie among the band's rows, or beyond the panel's ends).  partners / r2: L x l by the panel's marker; chrom: L or null.
 int eagle_dev_ld_partners(eagle_ctx* ctx, const double* band, long rows, long window, long c_lo, long c_hi, long g0, const int32_t* chrom,
                           double min_r2, int l, int32_t* partners, double* r2, void* stream);
+// LD scores and the decay histogram of the markers g0 + [c_lo, c_hi) from the same band (include/eagle_hip.h section 1b'''v): U / cnt by
+// the panel's marker, written; bin_sum / bin_pairs (nbins words) ADDED to -- zero them before the first core.  Forward pairs are binned
+// with their smaller marker, so cores that partition the panel count every pair once.  chrom / pos: L or null; edges: nbins + 1 int64 on
+// the device, strictly increasing, 0 <= nbins <= 512 (0: no histogram, the three pointers unused).
+int eagle_dev_ld_reduce(eagle_ctx* ctx, const double* band, long rows, long window, long c_lo, long c_hi, long g0, const int32_t* chrom,
+                        const int64_t* pos, long max_dist, const int64_t* edges, int nbins, uint64_t* U, int32_t* cnt, uint64_t* bin_sum,
+                        int64_t* bin_pairs, void* stream);
 #ifdef __cplusplus
 }
 #include "eagle_host.h"

@@ -15,7 +15,8 @@
 //                                        fl(fl((double)c * (double)c) / fl((double)v_i * (double)v_j)), or -1.0 where i + o >= rows or one of
 //                                        the two is monomorphic: the band mode's tile with another epilogue.  k_ld_partners then ranks, per
 //                                        marker, its forward entries and the backward entries of the `window` markers before it (include/
-//                                        eagle_hip.h section 1b'''iii).
+//                                        eagle_hip.h section 1b'''iii); k_ld_reduce sums them all, quantised to integers, per marker and
+//                                        per distance bin (section 1b'''v).
 //
 // Tile.  A workgroup (256 threads, 4 waves) owns TM = 128 consecutive markers.  Per K chunk of 128 individuals it stages TB rows x 128 B
 // in LDS once: in band mode TB = 128 + 32 (NB - 1) rows of the SAME image from the tile's first row on, NB - 1 = pad32(window) / 32, so that
@@ -355,6 +356,105 @@ extern "C" int eagle_dev_ld_partners(eagle_ctx* ctx, const double* band, long ro
     if (blocks > 0x7fffffffL) return eagle_fail(ctx, EAGLE_ERR_ARG, "ld_partners: too many rows");
     hipLaunchKernelGGL(k_ld_partners, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, band, rows, (int)window, c_lo, c_hi, g0, chrom, min_r2,
                        l, partners, r2);
+    LD_LAUNCH_CHECK(ctx);
+    return EAGLE_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// LD scores and the LD decay curve (include/eagle_hip.h section 1b'''v)
+// ------------------------------------------------------------------------------------------------------------------------------
+#define LD_REDUCE_MAX_BINS 512
+#define LD_REDUCE_MAX_BLOCKS 2048   /* 8 workgroups of 4 waves on each of 256 compute units: what bounds the flush below */
+
+// k_ld_partners' shape: one wave per marker i of [c_lo, c_hi), lane x holds the candidates t = x, x + 64, ... (at most 8), the forward
+// entry band[i][o - 1] or the backward entry band[j][|o| - 1].  Every eligible candidate adds u = (uint64)(r2 * 2^30) and 1 to the lane's
+// totals; a wave-wide integer sum gives U and cnt, lane 0 stores them: every word has one owner.  FORWARD candidates alone (the pair
+// belongs to its smaller marker, and that marker to one core) also add u and 1 to the bin of their distance in the workgroup's
+// histogram in LDS (64-bit integer LDS atomics; the edges sit in LDS too, the bin is found by binary search).  A workgroup walks its
+// markers with the grid's stride -- at most LD_REDUCE_MAX_BLOCKS workgroups, however long the core -- and adds its non-zero bins to the
+// global histogram once, after a barrier, with 64-bit vector atomic adds: consecutive lanes add consecutive words, at most 2,048 x 512
+// x 2 adds of 8 bytes per launch (16 MiB of added bytes whatever L is; every workgroup adds into the same two arrays of at most 4 KB,
+// and the rate of 64-bit integer adds under that contention has not been measured), and integer adds in any order give one result.
+// A wave without a marker skips the work and still meets the barrier.
+__global__ __launch_bounds__(256) void k_ld_reduce(const double* __restrict__ band, long rows, int window, long c_lo, long c_hi, long g0,
+                                                   const int32_t* __restrict__ chrom, const int64_t* __restrict__ pos, long max_dist,
+                                                   const int64_t* __restrict__ edges, int nbins, unsigned long long* __restrict__ U,
+                                                   int32_t* __restrict__ cnt, unsigned long long* __restrict__ bin_sum,
+                                                   unsigned long long* __restrict__ bin_pairs) {
+    __shared__ unsigned long long hS[LD_REDUCE_MAX_BINS], hP[LD_REDUCE_MAX_BINS];
+    __shared__ long long eS[LD_REDUCE_MAX_BINS + 1];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    for (int x = tid; x < nbins; x += 256) hS[x] = hP[x] = 0ull;
+    for (int x = tid; x <= nbins && nbins > 0; x += 256) eS[x] = edges[x];
+    __syncthreads();
+    const long groups = (c_hi - c_lo + 3) / 4;
+    for (long g = blockIdx.x; g < groups; g += gridDim.x) {         // the same trip count in every wave of the workgroup
+        const long i = c_lo + 4 * g + w;
+        if (i >= c_hi) continue;                                    // a whole wave: the shuffles below see all 64 lanes or none
+        const long gi = g0 + i;
+        const int ci = chrom ? chrom[gi] : 0;
+        const long long pi = pos ? pos[gi] : 0;
+        unsigned long long usum = 0ull;
+        int c = 0;
+#pragma unroll
+        for (int s = 0; s < 8; s++) {
+            const int t = lane + 64 * s, o = (t >> 1) + 1;
+            if (t >= 2 * window) continue;
+            const long j = (t & 1) ? i + o : i - o;
+            if (j < 0 || j >= rows) continue;
+            const double v = (t & 1) ? band[i * window + (o - 1)] : band[j * window + (o - 1)];
+            if (!(v >= 0.0) || (chrom && chrom[g0 + j] != ci)) continue;         // -1.0: no pair
+            long long d = o;
+            if (pos) {
+                const long long pj = pos[g0 + j];
+                d = pj > pi ? pj - pi : pi - pj;
+                if (max_dist > 0 && d > max_dist) continue;
+            }
+            const unsigned long long u = (unsigned long long)(v * 1073741824.0);   // exact product, truncating conversion
+            usum += u;
+            c++;
+            if ((t & 1) && nbins > 0 && d >= eS[0] && d < eS[nbins]) {
+                int lo = 0, hi = nbins;                             // eS[lo] <= d < eS[hi]
+                while (hi - lo > 1) {
+                    const int mid = (lo + hi) >> 1;
+                    if (d >= eS[mid]) lo = mid;
+                    else hi = mid;
+                }
+                atomicAdd(&hS[lo], u);
+                atomicAdd(&hP[lo], 1ull);
+            }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            usum += __shfl_xor(usum, off);
+            c += __shfl_xor(c, off);
+        }
+        if (lane == 0) {
+            U[gi] = usum;
+            cnt[gi] = c;
+        }
+    }
+    __syncthreads();
+    for (int x = tid; x < nbins; x += 256) {
+        if (!hP[x]) continue;                                       // no pair, no sum
+        atomicAdd(&bin_pairs[x], hP[x]);
+        if (hS[x]) atomicAdd(&bin_sum[x], hS[x]);
+    }
+}
+
+// U / cnt: by the PANEL's marker, of which the entries g0 + [c_lo, c_hi) are written; chrom / pos: by the panel's marker, or null;
+// edges (nbins + 1 int64, increasing) / bin_sum / bin_pairs (nbins words each, ADDED to): device memory, unused when nbins == 0
+extern "C" int eagle_dev_ld_reduce(eagle_ctx* ctx, const double* band, long rows, long window, long c_lo, long c_hi, long g0, const int32_t* chrom,
+                                   const int64_t* pos, long max_dist, const int64_t* edges, int nbins, uint64_t* U, int32_t* cnt,
+                                   uint64_t* bin_sum, int64_t* bin_pairs, void* stream) {
+    if (c_hi <= c_lo) return EAGLE_OK;
+    if (c_lo < 0 || c_hi > rows || window < 1 || window > 256 || nbins < 0 || nbins > LD_REDUCE_MAX_BINS || !band || !U || !cnt ||
+        (nbins > 0 && (!edges || !bin_sum || !bin_pairs)) || (max_dist > 0 && !pos))
+        return eagle_fail(ctx, EAGLE_ERR_ARG, "ld_reduce: bad shape");
+    const long groups = (c_hi - c_lo + 3) / 4;
+    const long blocks = groups < LD_REDUCE_MAX_BLOCKS ? groups : LD_REDUCE_MAX_BLOCKS;
+    hipLaunchKernelGGL(k_ld_reduce, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, band, rows, (int)window, c_lo, c_hi, g0, chrom, pos,
+                       max_dist, edges, nbins, (unsigned long long*)U, cnt, (unsigned long long*)bin_sum, (unsigned long long*)bin_pairs);
     LD_LAUNCH_CHECK(ctx);
     return EAGLE_OK;
 }

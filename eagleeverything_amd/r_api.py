@@ -446,19 +446,15 @@ LDKNN_MAX_PARTNERS = 32
 LDKNN_MAX_K = 64
 
 
-def ld_partners_host(Mt8, window, l, min_r2, chrom=None):
-    """rcpp_api.ld_partners restated in numpy: Mt8 = int8 (L, n) marker-major genotypes in {-1, 0, +1} (the ingested panel: missing
-    genotypes are heterozygotes) -> (partners int32 (L, l), r2 fp64 (L, l)).  r2_ij = fl(fl((double)c * (double)c) / fl((double)v_i *
-    (double)v_j)) for v_i, v_j > 0; row i lists the j with 1 <= |j - i| <= window, r2_ij >= min_r2 and chrom[j] == chrom[i] by
-    decreasing r2, ties to the smaller |j - i|, then the smaller j; -1 (r2 0.0) beyond them."""
+def ld_band_host(Mt8, window):
+    """The fp64 r2 band of the ingested panel (include/eagle_hip.h section 1b'''iii) in numpy: Mt8 = int8 (L, n) marker-major genotypes
+    in {-1, 0, +1} -> fp64 (L, window), band[i, o - 1] = r2 between markers i and i + o = fl(fl((double)c * (double)c) / fl((double)v_i *
+    (double)v_j)), -1.0 where i + o >= L or one of the two is monomorphic: what k_ld_tile's r2 mode writes."""
     G = np.asarray(Mt8)
     L, n = G.shape
-    window, l, min_r2 = int(window), int(l), float(min_r2)
-    if not 1 <= window <= 256 or not 1 <= l <= LDKNN_MAX_PARTNERS or not 0.0 <= min_r2 <= 1.0:
-        raise ValueError("ld_partners_host: 1 <= window <= 256, 1 <= l <= %d, 0 <= min_r2 <= 1" % LDKNN_MAX_PARTNERS)
-    ch = None if chrom is None else np.asarray(chrom).ravel()
-    if ch is not None and ch.size != L:
-        raise ValueError("ld_partners_host: chrom holds %d entries, the panel %d markers" % (ch.size, L))
+    window = int(window)
+    if not 1 <= window <= 256:
+        raise ValueError("ld_band_host: 1 <= window <= 256")
     F = G.astype(np.float64)                                   # products and sums of small integers: exact in fp64 below 2^53
     Gi = G.astype(np.int64)
     s, q = Gi.sum(axis=1), (Gi * Gi).sum(axis=1)
@@ -472,6 +468,23 @@ def ld_partners_host(Mt8, window, l, min_r2, chrom=None):
         with np.errstate(divide="ignore", invalid="ignore"):
             r2 = (c * c) / (vf[:-o] * vf[o:])
         band[:-o, o - 1] = np.where(ok, r2, -1.0)
+    return band
+
+
+def ld_partners_host(Mt8, window, l, min_r2, chrom=None):
+    """rcpp_api.ld_partners restated in numpy: Mt8 = int8 (L, n) marker-major genotypes in {-1, 0, +1} (the ingested panel: missing
+    genotypes are heterozygotes) -> (partners int32 (L, l), r2 fp64 (L, l)).  r2_ij = fl(fl((double)c * (double)c) / fl((double)v_i *
+    (double)v_j)) for v_i, v_j > 0; row i lists the j with 1 <= |j - i| <= window, r2_ij >= min_r2 and chrom[j] == chrom[i] by
+    decreasing r2, ties to the smaller |j - i|, then the smaller j; -1 (r2 0.0) beyond them."""
+    G = np.asarray(Mt8)
+    L, n = G.shape
+    window, l, min_r2 = int(window), int(l), float(min_r2)
+    if not 1 <= window <= 256 or not 1 <= l <= LDKNN_MAX_PARTNERS or not 0.0 <= min_r2 <= 1.0:
+        raise ValueError("ld_partners_host: 1 <= window <= 256, 1 <= l <= %d, 0 <= min_r2 <= 1" % LDKNN_MAX_PARTNERS)
+    ch = None if chrom is None else np.asarray(chrom).ravel()
+    if ch is not None and ch.size != L:
+        raise ValueError("ld_partners_host: chrom holds %d entries, the panel %d markers" % (ch.size, L))
+    band = ld_band_host(G, window)
     return _ld_rank_band(band, l, min_r2, ch)
 
 
@@ -979,11 +992,167 @@ def related_drop(pairs, n, priority=None):
     return np.sort(np.asarray(dropped, dtype=np.int64)) + 1
 
 
+# ---- LD scores and the LD decay curve (include/eagle_hip.h section 1b'''v): the restatement in numpy and the interface ----
+LD_STATS_MAX_BINS = 512
+LD_SCALE = 1073741824.0      # 2^30: u = (uint64)(r2 * LD_SCALE)
+
+
+def ld_stats_host(band, chrom=None, pos=None, max_dist=0, edges=None):
+    """rcpp_api.ld_stats / bed_ld_stats restated in numpy on any r2 band (ld_band_host(Mt8, window) for the ingested panel,
+    bed_ld_host(...)[6] for the .bed file): band = fp64 (L, window), band[i, o - 1] = r2 between markers i and i + o, -1.0 without a pair
+    -> (U uint64 (L), cnt int32 (L)), with edges also (bin_sum uint64 (B), bin_pairs int64 (B)).  A pair (i, j = i + o) is eligible iff
+    r2 >= 0, chrom[i] == chrom[j] (chrom given) and |pos[j] - pos[i]| <= max_dist (pos given, max_dist > 0); u = (uint64)(r2 * 2^30)
+    goes to U_i and U_j, 1 to cnt_i and cnt_j, and u and 1 to the bin b with edges[b] <= d < edges[b + 1], d = |pos[j] - pos[i]| with
+    pos and o without.  Integer sums: no order of summation changes a bit."""
+    band = np.asarray(band, dtype=np.float64)
+    L, window = band.shape
+    max_dist = int(max_dist)
+    ch = None if chrom is None else np.asarray(chrom).ravel()
+    ps = None if pos is None else np.asarray(pos).ravel().astype(np.int64)
+    if (ch is not None and ch.size != L) or (ps is not None and ps.size != L):
+        raise ValueError("ld_stats_host: chrom and pos hold one entry per marker of the band (%d)" % L)
+    if max_dist > 0 and ps is None:
+        raise ValueError("ld_stats_host: max_dist needs pos")
+    if not 1 <= window <= 256 or L * window > 1 << 33:
+        raise ValueError("ld_stats_host: 1 <= window <= 256 and markers x window <= 2^33")
+    ed = None
+    if edges is not None:
+        ed = np.asarray(edges).ravel().astype(np.int64)
+        if not 2 <= ed.size <= LD_STATS_MAX_BINS + 1 or np.any(np.diff(ed) <= 0):
+            raise ValueError("ld_stats_host: edges must be 2 to %d strictly increasing whole numbers" % (LD_STATS_MAX_BINS + 1))
+    U, cnt = np.zeros(L, dtype=np.uint64), np.zeros(L, dtype=np.int64)
+    nb = 0 if ed is None else ed.size - 1
+    bsum, bpairs = np.zeros(nb, dtype=np.uint64), np.zeros(nb, dtype=np.int64)
+    for o in range(1, min(window, L - 1) + 1):
+        r2 = band[:-o, o - 1]
+        ok = r2 >= 0.0
+        if ch is not None:
+            ok &= ch[:-o] == ch[o:]
+        d = np.full(L - o, o, dtype=np.int64)
+        if ps is not None:
+            d = np.abs(ps[o:] - ps[:-o])
+            if max_dist > 0:
+                ok &= d <= max_dist
+        u = np.where(ok, r2 * LD_SCALE, 0.0).astype(np.uint64)              # an exact product, a truncating conversion
+        U[:-o] += u
+        U[o:] += u
+        cnt[:-o] += ok
+        cnt[o:] += ok
+        if nb:
+            b = np.searchsorted(ed, d, side="right") - 1                        # edges[b] <= d < edges[b + 1]
+            inb = ok & (b >= 0) & (b < nb)
+            np.add.at(bsum, b[inb], u[inb])
+            np.add.at(bpairs, b[inb], 1)
+    out = (U, cnt.astype(np.int32))
+    return out + (bsum, bpairs) if nb else out
+
+
+def ld_half_decay(edges, pairs, mean_r2):
+    """The distance at which LD has halved, off a decay curve: the lower edge of the first non-empty bin whose mean r2 is at most half
+    the mean of the first non-empty bin, or None when no bin is (or every bin is empty).  Host numpy."""
+    ed, pr, mr = np.asarray(edges).ravel(), np.asarray(pairs).ravel(), np.asarray(mean_r2, dtype=np.float64).ravel()
+    if ed.size != pr.size + 1 or mr.size != pr.size:
+        raise ValueError("ld_half_decay: B + 1 edges for B bins")
+    full = np.flatnonzero(pr > 0)
+    if not full.size:
+        return None
+    hit = full[mr[full] <= 0.5 * mr[full[0]]]              # the first non-empty bin itself only when its mean is 0: no LD to halve
+    return ed[hit[0]].item() if hit.size else None
+
+
+def _ld_stats_source(who, geno, map, bed, include):
+    """What LDScore and LDDecay share: (n, L, chrom int32 or None, pos int64 or None, bed file or None, (n, Lbed), include mask or None)."""
+    n, L = int(geno["dim_of_ascii_M"][0]), int(geno["dim_of_ascii_M"][1])
+    errs = []
+    map = _ld_map(who, map, geno, L, errs.append)
+    if map is False:
+        raise ValueError(who + ":" + errs[0])
+    chrom = pos = None
+    if map is not None:
+        chrom = np.unique(np.asarray([str(c) for c in map["Chr"]]), return_inverse=True)[1].astype(np.int32)
+        pos = np.asarray(map["Pos"]).ravel()
+        if not np.array_equal(pos.astype(np.int64), pos):
+            raise ValueError("%s: the map's positions must be whole numbers of base pairs" % who)
+        pos = pos.astype(np.int64)
+    if bed is None:
+        if include is not None:
+            raise ValueError("%s: include= needs bed=" % who)
+        return n, L, chrom, pos, None, None, None
+    src_bed, src_bim, src_fam = bed_fileset(bed)
+    for f in (src_bed, src_bim, src_fam):
+        if not os.path.isfile(f):
+            raise ValueError("%s: the file %s could not be found" % (who, f))
+    nfam, Lbed = _count_lines(src_fam), _count_lines(src_bim)
+    if nfam != n:
+        raise ValueError("%s: %s names %d individuals, the panel holds %d" % (who, src_fam, nfam, n))
+    if include is None and "marker_index" in geno:
+        include = np.asarray(geno["marker_index"], dtype=np.int64).ravel()
+    inc = _bed_include_mask(include, Lbed, who)
+    if (Lbed if inc is None else int(inc.sum())) != L:
+        raise ValueError("%s: include selects %d markers of %s, the panel holds %d" % (who, Lbed if inc is None else int(inc.sum()), src_bed, L))
+    return n, L, chrom, pos, src_bed, (n, Lbed), inc
+
+
+def _ld_stats_call(src, window, max_dist, edges, min_overlap, availmemGb, device, geno):
+    n, L, chrom, pos, src_bed, bdims, inc = src
+    if src_bed is None:
+        return rcpp_api.ld_stats(geno["asciifileMt"], (n, L), int(window), chrom, pos, max_dist, edges, availmemGb, device=device)
+    return rcpp_api.bed_ld_stats(src_bed, bdims, int(window), inc, int(min_overlap), chrom, pos, max_dist, edges, availmemGb, device=device)
+
+
+def LDScore(geno, window=50, map=None, kb=None, bed=None, include=None, min_overlap=1, availmemGb=8, device=0):
+    """The LD score of every marker of a panel -> {"score": fp64 (L) = 1.0 + u * 2^-30, "partners": int32 (L), the markers summed over,
+    "u": uint64 (L), the exact integer sum}: l_i = 1 + the sum of r2_ij over the markers j at most `window` <= 256 markers from i
+    (include/eagle_hip.h section 1b'''v; rcpp_api.ld_stats, the r2 of LDPrune and ImputeBed).  It shows how unevenly the panel tags
+    the genome, and is the weight GRM(..., ld_score=) and PCA(..., ld_score=) divide by.  map (ReadBim's dict, as LDPrune takes it):
+    markers on other chromosomes are left out, and with kb= those more than kb kilobases away (kb needs a map).  bed = the .bed file
+    (or prefix) the panel was ingested from: r2 counted over the individuals called at both markers, at least min_overlap of them
+    (rcpp_api.bed_ld_stats, section 1b'''iv); include = the panel's markers in the file, default geno's marker_index.  A monomorphic
+    marker has score 1.0."""
+    src = _ld_stats_source("LDScore", geno, map, bed, include)
+    if kb is not None and src[3] is None:
+        raise ValueError("LDScore: kb= needs a map with Chr and Pos entries")
+    max_dist = 0 if kb is None else int(round(float(kb) * 1000.0))
+    if kb is not None and max_dist < 1:
+        raise ValueError("LDScore: kb must be at least 0.001")
+    U, cnt = _ld_stats_call(src, window, max_dist, None, min_overlap, availmemGb, device, geno)
+    return {"score": 1.0 + U.astype(np.float64) * (1.0 / LD_SCALE), "partners": cnt, "u": U}
+
+
+def LDDecay(geno, window=256, map=None, bins=None, kb=None, bed=None, include=None, min_overlap=1, availmemGb=8, device=0):
+    """The LD decay curve of a panel -> {"edges": int64 (B + 1), "pairs": int64 (B), "mean_r2": fp64 (B), NaN for an empty bin,
+    "half_decay": ld_half_decay's distance or None, "sum": uint64 (B), the exact integer sums}: the mean r2 of the pairs of markers at
+    most `window` <= 256 markers apart per distance bin (include/eagle_hip.h section 1b'''v) -- what window=, kb= and r2= of LDPrune,
+    ImputeBed and tag_markers are read off.  Without a map the distance is the marker offset and the default bins are one per offset,
+    edges 1 .. window + 1.  With a map (ReadBim's dict) pairs on different chromosomes do not count, the distance is in base pairs, kb=
+    is required (pairs further apart do not count) and the default bins are 50 equal ones up to kb.  bins = the edges themselves (2 to
+    513 increasing whole numbers, in markers or base pairs).  bed, include, min_overlap as in LDScore."""
+    src = _ld_stats_source("LDDecay", geno, map, bed, include)
+    max_dist = 0
+    if src[3] is None:
+        if kb is not None:
+            raise ValueError("LDDecay: kb= needs a map with Chr and Pos entries")
+        edges = np.arange(1, int(window) + 2, dtype=np.int64) if bins is None else bins
+    else:
+        if kb is None:
+            raise ValueError("LDDecay: a map needs kb=, the largest distance of a pair in kilobases")
+        max_dist = int(round(float(kb) * 1000.0))
+        if max_dist < 1:
+            raise ValueError("LDDecay: kb must be at least 0.001")
+        edges = np.unique(np.rint(np.linspace(0.0, float(max_dist) + 1.0, 51)).astype(np.int64)) if bins is None else bins
+    edges = np.asarray(edges).ravel()
+    _, _, bsum, pairs = _ld_stats_call(src, window, max_dist, edges, min_overlap, availmemGb, device, geno)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean = np.where(pairs > 0, bsum.astype(np.float64) / pairs.astype(np.float64) * (1.0 / LD_SCALE), np.nan)
+    edges = edges.astype(np.int64)
+    return {"edges": edges, "pairs": pairs, "mean_r2": mean, "half_decay": ld_half_decay(edges, pairs, mean), "sum": bsum}
+
+
 # ---- GRM and PCA (include/eagle_hip.h section 1b''''): the exact weighted Gram product on the device, fp64 arithmetic on the host ----
 GRM_QMAX = 2097151    # 2^21 - 1: the largest weight rcpp_api.weighted_gram takes
 
 
-def grm_weights(n0, n1, n2, method="standardized", maf=0.0, include=None):
+def grm_weights(n0, n1, n2, method="standardized", maf=0.0, include=None, ld_score=None):
     """The integer marker weights of a relationship matrix from genotype counts -> (q uint32 (L), scale fp64, used bool (L)), in
     numpy (nothing here touches a device).  Per marker, in int64:  N = n0 + n1 + n2,  c = 2 n2 + n1 (copies of the allele coded 2),
     den = c (2N - c).  A marker is USED iff den > 0 (it is polymorphic), (double)min(c, 2N - c) >= maf * (double)(2N), and `include`
@@ -995,10 +1164,21 @@ def grm_weights(n0, n1, n2, method="standardized", maf=0.0, include=None):
     q / scale stands for w with an absolute error of at most 0.5 / scale, so the RELATIVE error of a marker's weight is at most
     w_max / (w_m (2^22 - 2)), about w_max / (w_m 2^22): 2.4e-6 at worst on a panel with allele frequencies in 0.1 .. 0.9, but a marker
     at p = 0.5 beside one with a single copy of the rare allele among 10,000 individuals loses all but a few bits.  That is why PCA
-    defaults to maf = 0.01.  With no used marker q = 0 and scale = 1.0."""
+    defaults to maf = 0.01.  With no used marker q = 0 and scale = 1.0.
+    ld_score (default None, and then every bit is as described above): fp64 (L), every entry >= 1 (LDScore(...)["score"]).  Markers in
+    LD-dense regions count for less, the LDAK / GCTA-LDMS idea in its simplest form: "standardized" becomes
+    w = (((2.0 * (double)N) * (double)N) / (double)den) / ld_score, one more correctly rounded operation, then scale and q as above;
+    "vanraden1" becomes w = 1.0 / ld_score with scale = 2097151.0 / max(w over the used markers) and q = rint(w * scale) in the place of
+    q = 1 (grm_from_gram then weights its denominator by q / scale as well).  An LD score lies in [1, 1 + 2 * 256], so
+    it widens the dynamic range w_max / w_m of the relative error above by a factor of up to 513."""
     n0, n1, n2 = (np.asarray(v, dtype=np.int64).ravel() for v in (n0, n1, n2))
     if method not in ("standardized", "vanraden1"):
         raise ValueError("grm_weights: method must be \"standardized\" or \"vanraden1\"")
+    ls = None
+    if ld_score is not None:
+        ls = np.asarray(ld_score, dtype=np.float64).ravel()
+        if ls.size != n0.size or not np.all(ls >= 1.0) or not np.all(np.isfinite(ls)):
+            raise ValueError("grm_weights: ld_score must hold one finite number >= 1 per marker (%d)" % n0.size)
     N = n0 + n1 + n2
     c = 2 * n2 + n1
     den = c * (2 * N - c)
@@ -1012,10 +1192,15 @@ def grm_weights(n0, n1, n2, method="standardized", maf=0.0, include=None):
     if not used.any():
         return q, 1.0, used
     if method == "vanraden1":
-        q[used] = 1
-        return q, 1.0, used
-    Nf = N[used].astype(np.float64)
-    w = ((2.0 * Nf) * Nf) / den[used].astype(np.float64)
+        if ls is None:
+            q[used] = 1
+            return q, 1.0, used
+        w = 1.0 / ls[used]
+    else:
+        Nf = N[used].astype(np.float64)
+        w = ((2.0 * Nf) * Nf) / den[used].astype(np.float64)
+        if ls is not None:
+            w = w / ls[used]
     scale = float(GRM_QMAX) / float(w.max())
     q[used] = np.rint(w * scale).astype(np.uint32)
     return q, scale, used
@@ -1045,7 +1230,9 @@ def grm_from_gram(Q, q_info, reference=None):
                                                 sum_m q_m mu_m g_im = r_i: centring every marker over R is double-centring Q over R )
         G = Gc / (scale * L_used)             "standardized":  (1 / L_used) sum_m (x_im - 2 p_m)(x_jm - 2 p_m) / (2 p_m (1 - p_m))
         G = Gc / sum_used 2 p_m (1 - p_m)     "vanraden1", 2 p (1 - p) = den / (2 N^2) in grm_weights' terms
-    x = g + 1 the allele count, p_m its frequency over R when the counts are R's."""
+    x = g + 1 the allele count, p_m its frequency over R when the counts are R's.  "vanraden1" weights from grm_weights(ld_score=)
+    (scale != 1.0; q_info then needs "q" too):  G = Gc / (scale * sum_used (q_m / scale) 2 p_m (1 - p_m)), the same ratio with every
+    marker weighted by what stands for 1 / ld_score in Q."""
     Qf = np.asarray(Q).astype(np.float64)       # |Q| < 2^52: exact
     n = Qf.shape[0]
     if Qf.ndim != 2 or Qf.shape[1] != n:
@@ -1066,10 +1253,14 @@ def grm_from_gram(Q, q_info, reference=None):
     N = n0 + n1 + n2
     c = 2 * n2 + n1
     Nf = N.astype(np.float64)
-    return Gc / float(np.sum((c * (2 * N - c)).astype(np.float64) / ((2.0 * Nf) * Nf)))
+    scale = float(q_info.get("scale", 1.0))
+    if scale == 1.0:
+        return Gc / float(np.sum((c * (2 * N - c)).astype(np.float64) / ((2.0 * Nf) * Nf)))
+    wq = np.asarray(q_info["q"]).ravel()[used].astype(np.float64) / scale
+    return Gc / (scale * float(np.sum(wq * ((c * (2 * N - c)).astype(np.float64) / ((2.0 * Nf) * Nf)))))
 
 
-def GRM(geno, method="standardized", maf=0.0, include=None, reference=None, stats=None, availmemGb=8, device=0):
+def GRM(geno, method="standardized", maf=0.0, include=None, reference=None, stats=None, availmemGb=8, device=0, ld_score=None):
     """The genomic relationship matrix of a panel -> {"G": fp64 (n, n) (grm_from_gram), "Q": int64 (n, n), the exact weighted Gram
     product over ALL n individuals (rcpp_api.weighted_gram: base-128 digit planes of the weights on the int8 MFMA), "q", "scale",
     "used" (grm_weights), "method", "n0", "n1", "n2" (the counts behind the weights), "reference" (int64, 0-based),
@@ -1078,7 +1269,8 @@ def GRM(geno, method="standardized", maf=0.0, include=None, reference=None, stat
     counts then come from them alone (MarkerStats on a view of the panel without the others, nothing written), and everyone else is
     placed relative to them -- what PCA(reference=) projects.  stats = a MarkerStats dict of exactly those individuals replaces the
     counting pass.  include = a boolean mask of markers (one chromosome, one MAF bin): the matrix of that subset from the resident
-    image, without writing a filtered panel."""
+    image, without writing a filtered panel.  ld_score = fp64 (L), LDScore(geno)["score"]: every marker's weight is divided by it
+    (grm_weights(ld_score=)), so that LD-dense regions do not dominate the matrix; the dict then carries "ld_score" too."""
     n, L = int(geno["dim_of_ascii_M"][0]), int(geno["dim_of_ascii_M"][1])
     R = _grm_reference(reference, n)
     if stats is None:
@@ -1091,25 +1283,34 @@ def GRM(geno, method="standardized", maf=0.0, include=None, reference=None, stat
     n0, n1, n2 = (np.asarray(stats[k], dtype=np.int64).ravel() for k in ("n0", "n1", "n2"))
     if n0.size != L:
         raise ValueError("GRM: the marker statistics hold %d markers, the panel %d" % (n0.size, L))
-    q, scale, used = grm_weights(n0, n1, n2, method=method, maf=maf, include=include)
+    q, scale, used = grm_weights(n0, n1, n2, method=method, maf=maf, include=include, ld_score=ld_score)
     if not used.any():
         raise ValueError("GRM: no marker is used (maf=%s%s)" % (maf, "" if include is None else ", include given"))
     Q = rcpp_api.weighted_gram(geno["asciifileM"], (n, L), q, availmemGb, device=device)
     out = {"Q": Q, "q": q, "scale": scale, "used": used, "method": method, "n0": n0, "n1": n1, "n2": n2, "reference": R}
     out["G"] = grm_from_gram(Q, out, reference=R)
     out["weight_rel_error"] = 0.0
-    if method == "standardized":
-        Nf = (n0 + n1 + n2)[used].astype(np.float64)
-        w = ((2.0 * Nf) * Nf) / ((2 * n2 + n1) * (2 * (n0 + n1 + n2) - (2 * n2 + n1)))[used].astype(np.float64)
+    if ld_score is not None:
+        out["ld_score"] = np.asarray(ld_score, dtype=np.float64).ravel()
+    if method == "standardized" or ld_score is not None:
+        if method == "standardized":
+            Nf = (n0 + n1 + n2)[used].astype(np.float64)
+            w = ((2.0 * Nf) * Nf) / ((2 * n2 + n1) * (2 * (n0 + n1 + n2) - (2 * n2 + n1)))[used].astype(np.float64)
+        else:
+            w = np.ones(int(used.sum()))
+        if ld_score is not None:
+            w = w / out["ld_score"][used]
         out["weight_rel_error"] = float(np.max(np.abs(q[used].astype(np.float64) / scale - w) / w))
     return out
 
 
-def PCA(geno, k=10, method="standardized", maf=0.01, reference=None, grm=None, eig=None, include=None, stats=None, availmemGb=8, device=0):
+def PCA(geno, k=10, method="standardized", maf=0.01, reference=None, grm=None, eig=None, include=None, stats=None, availmemGb=8, device=0,
+        ld_score=None):
     """Principal components of the relationship matrix, the covariates of AM(trait, am.add_pcs(X, pca), geno) ->
     {"values": the top k eigenvalues of G[R, R], decreasing, "pcs": fp64 (n, k), "explained": values / trace(G[R, R]), "reference":
     R, "grm": the GRM dict}.  grm = a dict of GRM() (then geno may be None and method / maf / include / stats are not used; its
-    reference is R unless `reference` names the same individuals), else GRM(geno, method, maf, include, reference, stats) is run.
+    reference is R unless `reference` names the same individuals), else GRM(geno, method, maf, include, reference, stats, ld_score=)
+    is run (ld_score: LDScore(geno)["score"], the weight of every marker divided by it).
     One eigh of G[R, R]: eig = a callable A -> (values, vectors in columns), in either order of the values (default
     host_model.algebra().eigh: host LAPACK unless host_model.set_algebra("device"); rcpp_api.sym_eig runs it on the device).
     The sign of every vector is fixed so that its component of largest magnitude (the first of equals) is positive.
@@ -1119,7 +1320,8 @@ def PCA(geno, k=10, method="standardized", maf=0.01, reference=None, grm=None, e
     individuals per marker projected individuals sit nearer the origin than reference ones (Lee et al. 2010).
     ValueError for k < 1 or k > |R| - 1 (centring takes one dimension)."""
     if grm is None:
-        grm = GRM(geno, method=method, maf=maf, include=include, reference=reference, stats=stats, availmemGb=availmemGb, device=device)
+        grm = GRM(geno, method=method, maf=maf, include=include, reference=reference, stats=stats, availmemGb=availmemGb, device=device,
+                  ld_score=ld_score)
     G = np.asarray(grm["G"], dtype=np.float64)
     n = G.shape[0]
     R = np.asarray(grm["reference"], dtype=np.int64)

@@ -842,6 +842,79 @@ def bed_ld_partners(bed_path, dims, window=50, l=16, min_r2=0.0, include=None, m
     return (out, r2) if return_r2 else out
 
 
+# ---- LD scores and the LD decay curve (include/eagle_hip.h section 1b'''v): the r2 band summed as exact integers ----
+LD_STATS_MAX_BINS = 512
+_c_i64p = C.POINTER(C.c_int64)
+_c_u64p = C.POINTER(C.c_uint64)
+
+
+def _ld_stats_args(who, nm, chrom, pos, max_dist, edges):
+    """The per-marker arrays and the bin edges of an ld_stats call as the C side takes them; ValueError before the library is called."""
+    ch = ps = ed = None
+    if chrom is not None:
+        c = np.atleast_1d(np.asarray(chrom)).ravel()
+        ch = np.ascontiguousarray(c, dtype=np.int32)
+        if ch.size != nm or not np.array_equal(ch, c):
+            raise ValueError("%s: chrom must hold one whole number that fits int32 per panel marker" % who)
+    if pos is not None:
+        c = np.atleast_1d(np.asarray(pos)).ravel()
+        ps = np.ascontiguousarray(c, dtype=np.int64)
+        if ps.size != nm or not np.array_equal(ps, c):
+            raise ValueError("%s: pos must hold one whole number of base pairs per panel marker" % who)
+    if int(max_dist) > 0 and ps is None:
+        raise ValueError("%s: max_dist needs pos" % who)
+    if edges is not None:
+        c = np.atleast_1d(np.asarray(edges)).ravel()
+        ed = np.ascontiguousarray(c, dtype=np.int64)
+        if not 2 <= ed.size <= LD_STATS_MAX_BINS + 1 or not np.array_equal(ed, c) or np.any(np.diff(ed) <= 0):
+            raise ValueError("%s: edges must be 2 to %d strictly increasing whole numbers" % (who, LD_STATS_MAX_BINS + 1))
+    return ch, ps, ed
+
+
+def ld_stats(f_name_ascii_Mt, dims, window=50, chrom=None, pos=None, max_dist=0, edges=None, max_memory_in_Gbytes=8.0, device=0):
+    """eagle_ld_stats -> (U uint64 (L), cnt int32 (L)), with edges also (bin_sum uint64 (B), bin_pairs int64 (B)), B = len(edges) - 1:
+    the sums of include/eagle_hip.h section 1b'''v over the r2 band of the ingested panel.  U_i = the sum of u_ij = (uint64)(r2_ij * 2^30)
+    over the markers j with 1 <= |j - i| <= window, r2_ij >= 0, chrom[j] == chrom[i] (chrom: L whole numbers) and |pos[j] - pos[i]| <=
+    max_dist (pos: L whole numbers of base pairs, max_dist > 0); cnt_i their number; the LD score is 1 + U / 2^30.  Every such pair
+    i < j adds u_ij and 1 to the bin b with edges[b] <= d_ij < edges[b + 1], d = |pos[j] - pos[i]| with pos and j - i without.
+    r_api.ld_stats_host(r_api.ld_band_host(Mt8, window), ...) is the numpy restatement."""
+    L = _lib.load()
+    nm = max(int(dims[1]), 0)
+    ch, ps, ed = _ld_stats_args("ld_stats", nm, chrom, pos, max_dist, edges)
+    nb = 0 if ed is None else ed.size - 1
+    U, cnt = np.zeros(nm, dtype=np.uint64), np.zeros(nm, dtype=np.int32)
+    bsum, bpairs = np.zeros(nb, dtype=np.uint64), np.zeros(nb, dtype=np.int64)
+    _args_first(L.eagle_ld_stats, device, (os.fsencode(f_name_ascii_Mt), _dims(dims), int(window),
+                                           ch.ctypes.data_as(_c_i32p) if ch is not None else None,
+                                           ps.ctypes.data_as(_c_i64p) if ps is not None else None, int(max_dist),
+                                           ed.ctypes.data_as(_c_i64p) if ed is not None else None, nb, float(max_memory_in_Gbytes),
+                                           U.ctypes.data_as(_c_u64p), cnt.ctypes.data_as(_c_i32p),
+                                           bsum.ctypes.data_as(_c_u64p) if nb else None, bpairs.ctypes.data_as(_c_i64p) if nb else None))
+    return (U, cnt, bsum, bpairs) if nb else (U, cnt)
+
+
+def bed_ld_stats(bed_path, dims, window=50, include=None, min_overlap=1, chrom=None, pos=None, max_dist=0, edges=None, availmemGb=8.0,
+                 device=0):
+    """eagle_bed_ld_stats -> ld_stats' tuple by PANEL marker from a SNP-major PLINK .bed file, r2 of every pair over the individuals
+    called at both markers (at least min_overlap of them; include/eagle_hip.h section 1b'''iv).  include as in bed_ld_window; chrom and
+    pos: one whole number per panel marker.  r_api.ld_stats_host(r_api.bed_ld_host(...)[6], ...) is the numpy restatement."""
+    L = _lib.load()
+    nm = max(int(dims[1]), 0)
+    inc = _bed_ld_include(include, nm, "bed_ld_stats")
+    linc = nm if inc is None else int(inc.sum())
+    ch, ps, ed = _ld_stats_args("bed_ld_stats", linc, chrom, pos, max_dist, edges)
+    nb = 0 if ed is None else ed.size - 1
+    U, cnt = np.zeros(linc, dtype=np.uint64), np.zeros(linc, dtype=np.int32)
+    bsum, bpairs = np.zeros(nb, dtype=np.uint64), np.zeros(nb, dtype=np.int64)
+    _args_first(L.eagle_bed_ld_stats, device, (os.fsencode(bed_path), _dims(dims), inc.ctypes.data_as(C.c_void_p) if inc is not None else None,
+                                               int(window), int(min_overlap), ch.ctypes.data_as(_c_i32p) if ch is not None else None,
+                                               ps.ctypes.data_as(_c_i64p) if ps is not None else None, int(max_dist),
+                                               ed.ctypes.data_as(_c_i64p) if ed is not None else None, nb, float(availmemGb),
+                                               U.ctypes.data_as(_c_u64p), cnt.ctypes.data_as(_c_i32p),
+                                               bsum.ctypes.data_as(_c_u64p) if nb else None, bpairs.ctypes.data_as(_c_i64p) if nb else None))
+    return (U, cnt, bsum, bpairs) if nb else (U, cnt)
+
+
 # ---- GRM (include/eagle_hip.h section 1b''''): the exact weighted Gram product; weights, centring and PCA are r_api's ----
 WGRAM_MAX_WEIGHT = (1 << 21) - 1
 

@@ -602,6 +602,58 @@ int eagle_bed_ld_partners(eagle_ctx* ctx, const char* bed_path, const long dims[
                           int min_overlap, const int32_t* chrom, double max_memory_in_Gbytes, int32_t* partners_out, double* r2_out);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1b'''v. LD scores and the LD decay curve (no counterpart in the reference): the sums of the r2 band that 1b'''iii ranks, per marker
+ *     and per distance bin, as exact integers.  What LDPrune(window, r2, kb), ImputeBed(local, window) and tag_markers(r2) ask the user
+ *     to choose is read off these two statistics.
+ *
+ *     1. r2.  r2_ij is the fp64 number of 1b'''iii (the ingested panel: eagle_ld_stats) or of 1b'''iv (the .bed file with include and
+ *        min_overlap: eagle_bed_ld_stats), unchanged; -1.0 where there is no pair (a monomorphic marker; a pair that is not comparable).
+ *        0 <= r2_ij <= 1 holds in fp64: c^2 <= v_i v_j in integers (Cauchy-Schwarz on the centred rows), the conversions to fp64 are
+ *        exact while n^2 <= 2^53 (|c| and v are at most n^2), rounding is monotone -- a <= b gives fl(a) <= fl(b), so fl(c c) <=
+ *        fl(v_i v_j) and the quotient of x <= y rounds to at most 1 -- and equal products round equally, so two identical markers
+ *        have r2 = 1.0 exactly.
+ *     2. Quantised r2.  u_ij = (uint64)(r2_ij * 1073741824.0), 2^30: the multiplication by a power of two is exact and the conversion
+ *        truncates, 0 <= u_ij <= 2^30.  Integer sums of u do not depend on the order of summation: the device, whatever its
+ *        reduction tree and the order of its atomic adds, and numpy (r_api.ld_stats_host) agree bit for bit.
+ *     3. Eligible pair (i, j):  1 <= |j - i| <= window <= 256;  r2_ij >= 0;  chrom[i] == chrom[j] when chrom (int32 per panel marker,
+ *        any coding) is given;  |pos[j] - pos[i]| <= max_dist when pos (int64 per panel marker, base pairs, need not be sorted) is given
+ *        and max_dist > 0.  The distance d_ij is |pos[j] - pos[i]| with pos and |j - i| without.
+ *     4. Per marker.  U_i = sum of u_ij over the eligible j (uint64) and cnt_i = their number (int32), over both sides.  The LD score is
+ *        1.0 + (double)U_i * 2^-30, the caller's arithmetic: the leading 1 is the marker with itself.  A monomorphic or isolated
+ *        marker has U = 0, cnt = 0 and score 1.0.
+ *     5. Decay.  Bin edges edges[0] < edges[1] < ... < edges[B], int64, 1 <= B <= 512.  Every eligible pair with i < j is counted
+ *        once, in bin b iff edges[b] <= d_ij < edges[b + 1]; a pair outside [edges[0], edges[B]) is in no bin but still counts in the
+ *        scores.  pairs[b] (int64) is the number of pairs of the bin and sum[b] (uint64) the sum of their u_ij; the mean r2 of a bin,
+ *        (double)sum / (double)pairs * 2^-30, is the caller's arithmetic.
+ *     6. Limit.  markers * window <= 2^33 (markers = L, or Linc for the .bed file), so that no bin sum can pass 2^63: at most
+ *        markers * window pairs of at most 2^30 each.
+ *
+ *     k_ld_reduce works in the place of k_ld_partners, on the same band, in the same cores of markers with a halo of `window` rows on
+ *     both sides (resident, sidecar or text source, a VIEW alias; the .bed file's windows of 1b'''iv): a pair is binned with its smaller
+ *     marker and every marker belongs to one core, so the result does not depend on the window size.
+ *
+ *     Single device: a multi-device context works on its first device.  Argument errors (EAGLE_ERR_ARG: a NULL pointer, dims <= 0,
+ *     and those named below) are decided before the context is used; with ctx == NULL their text is in eagle_open_error().
+ * ------------------------------------------------------------------------------------------- */
+
+/* U_out (L uint64) and cnt_out (L int32) of definition 4; bin_sum_out (nbins uint64) and bin_pairs_out (nbins int64) of definition 5,
+ * B = nbins.  chrom (L int32), pos (L int64) and edges (nbins + 1 int64) may be NULL; edges == NULL or nbins == 0 means no decay, and
+ * the two bin outputs may then be NULL.  f_name_ascii_Mt is read as eagle_ld_partners reads it (dims = (n, L)).
+ * EAGLE_ERR_ARG: window outside [1, 256], L >= 2^31, L * window > 2^33, max_dist > 0 without pos, nbins outside [0, 512], edges not
+ * strictly increasing, edges given without the bin outputs. */
+int eagle_ld_stats(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long dims[2], long window, const int32_t* chrom, const int64_t* pos,
+                   long max_dist, const int64_t* edges, long nbins, double max_memory_in_Gbytes, uint64_t* U_out, int32_t* cnt_out,
+                   uint64_t* bin_sum_out, int64_t* bin_pairs_out);
+
+/* The same four outputs by PANEL marker (Linc entries; chrom and pos by panel marker too) from the SNP-major .bed file bed_path, r2 under
+ * the rule of 1b'''iv (include: L bytes or NULL; min_overlap), in the windows of eagle_bed_ld_partners.
+ * EAGLE_ERR_ARG: those of eagle_ld_stats with Linc in the place of L, and n > 0x3fffffff, min_overlap < 1, an include that selects no
+ * marker. */
+int eagle_bed_ld_stats(eagle_ctx* ctx, const char* bed_path, const long dims[2], const uint8_t* include, long window, int min_overlap,
+                       const int32_t* chrom, const int64_t* pos, long max_dist, const int64_t* edges, long nbins, double max_memory_in_Gbytes,
+                       uint64_t* U_out, int32_t* cnt_out, uint64_t* bin_sum_out, int64_t* bin_pairs_out);
+
+/* ---------------------------------------------------------------------------------------------
  * 1b''''. Genomic relationship matrix (no counterpart that the reference calls: its VanRaden G, E/R/GenomicRel.R, is unused): the one
  *     Gram product the matrices of EIGENSTRAT / PLINK / GCTA and their principal components need, with a weight per marker.  With
  *     g in {-1, 0, +1} = AA, AB, BB as everywhere in this library and integer weights q_m < 2^21,
