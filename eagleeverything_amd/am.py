@@ -697,3 +697,86 @@ def SummaryAM_traits(results, Y, X, geno, map=None, xnames=None, availmemGb=8, e
         Ft = np.column_stack([UtXY[:, :q], UtM[:, [col[j] for j in pk]]])
         out.append(_summary_eig(lam, maxK, Ft, UtXY[:, q + t], q, xn + [mname(j) for j in pk], say))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Using the fitted model (no counterpart in the reference, which stops at the loci): BLUPs of the marker effects from one exact
+# M^T (P y) on the device (include/eagle_hip.h section 1b''''i) and predictions for any panel with the same markers.
+# ---------------------------------------------------------------------------------------------------------------------------
+def blup_operands(y, X, K, ve, vg):
+    """The mixed-model solutions of y = X b + g + e, g ~ N(0, vg K), e ~ N(0, ve I) -> {"beta", "Py", "ghat"}, host algebra only.
+    H = ve I + vg K (host_model.calculateH);  P = H^-1 - H^-1 X (X^T H^-1 X)^-1 X^T H^-1 (host_model.calculateP);
+    beta = (X^T H^-1 X)^-1 X^T H^-1 y;  ghat = vg K P y.  They satisfy y - X beta = vg K P y + ve P y  (H P y = y - X beta)."""
+    y = np.asarray(y, dtype=np.float64).ravel()
+    X = np.asarray(X, dtype=np.float64).reshape(y.size, -1)
+    K = np.asarray(K, dtype=np.float64)
+    H = host_model.calculateH(K, ve, vg)
+    Py = host_model.calculateP(H, X) @ y
+    HiX = np.linalg.solve(H, X)
+    beta = np.linalg.solve(X.T @ HiX, HiX.T @ y)
+    return {"beta": beta, "Py": Py, "ghat": vg * (K @ Py)}
+
+
+def MarkerEffects(AMobj, trait, X, geno, availmemGb=8, backend=None, device=0):
+    """The model AM() selected, refitted and turned into per-marker effects -> {"beta": the fixed effects of [X | the reported loci],
+    "loci": AMobj["selected_loci"] (1-based), "u": fp64 (L), the BLUPs of the polygenic marker effects, "weights": u with each locus'
+    fixed effect added at its marker (what Predict scores for "genetic"), "ve", "vg", "c", "Py", "ghat", "bound", "nX": the columns of X}.
+
+    trait, X and geno are what AM() was given, NaN included: the rows AMobj["indxNA"] leave trait and X and, as a VIEW, the genotypes
+    (SummaryAM's rule).  X gets the reported loci as columns (extract_geno) and the variance components are REFITTED on that model
+    (calcVC): after an extBIC stop AMobj["ve"] / ["vg"] belong to the model that still held the dropped last pick.
+    AM()'s K is MM^T / max(MM^T) + 0.95 I (calcMMt).  With c = 1 / max(MM^T) and P y of blup_operands,
+        ghat = vg K P y = M u + 0.95 vg P y,        u = vg c M^T (P y):
+    u is one rcpp_api.marker_scores call of the quantised P y (r_api.quantise_weights, scale s) on the VIEW's Mt file, so every u_m
+    errs by at most "bound" = vg c 0.5 n / s.  The 0.95 vg P y term is the part of a TRAINING individual's genetic value that the
+    ridge on K's diagonal assigns to that individual alone; it is no function of the genotypes and not part of a prediction."""
+    from . import r_api, rcpp_api
+    backend = backend or HipBackend(device)
+    y = np.asarray(trait, dtype=np.float64).ravel()
+    X = np.asarray(X, dtype=np.float64).reshape(y.size, -1)
+    indxNA = np.asarray(AMobj.get("indxNA", ()), dtype=np.int64).ravel()
+    (X, y), geno = _drop_na_rows(indxNA, (X, y), geno, backend=backend, device=device)
+    n, L = int(geno["dim_of_ascii_M"][0]), int(geno["dim_of_ascii_M"][1])
+    if y.size != n:
+        raise ValueError("MarkerEffects: %d trait records for %d genotyped individuals" % (y.size, n))
+    loci = [int(j) for j in AMobj["selected_loci"]]
+    q = X.shape[1]
+    Xl = np.column_stack([X] + [backend.extract_geno(geno, j).astype(np.float64) for j in loci])
+    K = backend.calcMMt(geno, availmemGb, 1, np.array([np.nan]), True)
+    _, mx = rcpp_api.last_mmt_normalised(n, device=device)      # max(MM^T) of the product calcMMt just made
+    c = 1.0 / float(mx)
+    vc = calcVC(y, Xl, K, eig_R=emma_eigen_R_wo_Z(K, Xl))
+    ve, vg = float(vc["ve"]), float(vc["vg"])
+    op = blup_operands(y, Xl, K, ve, vg)
+    pq, s = r_api.quantise_weights(op["Py"])
+    S = rcpp_api.marker_scores(geno["asciifileMt"], (n, L), pq, availmemGb, device=device)[:, 0]
+    u = (vg * c) * (S.astype(np.float64) / s)
+    w = u.copy()
+    for i, j in enumerate(loci):
+        w[j - 1] += op["beta"][q + i]
+    return {"beta": op["beta"], "loci": loci, "u": u, "weights": w, "ve": ve, "vg": vg, "c": c, "Py": op["Py"], "ghat": op["ghat"],
+            "bound": vg * c * 0.5 * float(n) / s, "nX": q}
+
+
+def Predict(effects, geno, X=None, availmemGb=8, device=0):
+    """Genetic values from MarkerEffects' result for the individuals of ANY panel with the same markers in the same order -- the full
+    file AM() was given, whose NaN-trait individuals are the selection candidates, or new genotypes -> {"polygenic": M u, "genetic":
+    M weights (the polygenic value plus the reported loci's fixed effects)} and, with X (the candidates' rows of the design matrix AM()
+    was given, the loci not included), "yhat": X beta_X + genetic.  Two columns of one r_api.Score call.
+    For a training individual the model's ghat is polygenic + 0.95 vg P y: that second term belongs to the individual's own record
+    (MarkerEffects' docstring) and is not part of a prediction."""
+    from . import r_api
+    u = np.asarray(effects["u"], dtype=np.float64).ravel()
+    L = int(geno["dim_of_ascii_M"][1])
+    if u.size != L:
+        raise ValueError("Predict: the effects hold %d markers, the panel %d" % (u.size, L))
+    sc = r_api.Score(geno, np.column_stack([u, np.asarray(effects["weights"], dtype=np.float64).ravel()]), availmemGb=availmemGb,
+                     device=device)
+    out = {"polygenic": sc["score"][:, 0], "genetic": sc["score"][:, 1], "bound": sc["bound"]}
+    if X is not None:
+        X = np.asarray(X, dtype=np.float64).reshape(out["genetic"].size, -1)
+        nX = int(effects.get("nX", X.shape[1]))
+        if X.shape[1] != nX:
+            raise ValueError("Predict: X holds %d columns, the model's design matrix %d" % (X.shape[1], nX))
+        out["yhat"] = X @ np.asarray(effects["beta"], dtype=np.float64)[:nX] + out["genetic"]
+    return out

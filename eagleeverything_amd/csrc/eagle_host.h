@@ -293,4 +293,55 @@ static inline const char* ld_stats_arg_error(long markers, long window, bool has
     }
     return nullptr;
 }
+
+// ------------------------------------------------------------------------------------------------
+// The exact line-score pass (include/eagle_hip.h section 1b''''i): the argument rule of eagle_sample_scores / eagle_marker_scores and
+// the balanced base-256 digits of a weight.
+// ------------------------------------------------------------------------------------------------
+#define SCORES_MAX_COLUMNS 64L
+#define SCORES_MAX_WEIGHT 1073741824L   /* 2^30 */
+#define SCORES_MAX_LINE 8388480L        /* the largest multiple of 128 below 2^23 */
+// Digit p (0 .. 3) of w = d0 + 256 d1 + 256^2 d2 + 256^3 d3, d in [-128, 127]:  d_p = ((w_p + 128) & 255) - 128,  w_{p+1} = (w_p - d_p) >> 8
+// (the difference is a multiple of 256, so the shift is exact).  Four digits hold every |w| <= 2^30: the largest four-digit number is
+// 127 (256^4 - 1) / 255 > 2^30 and the smallest -128 (256^4 - 1) / 255 < -2^30.
+EAGLE_HD static inline int score_digit(int32_t w, int p) {
+    int32_t x = w, d = 0;
+    for (int q = 0; q <= p; q++) {
+        d = ((x + 128) & 255) - 128;
+        x = (x - d) >> 8;
+    }
+    return d;
+}
+// The four digits of w; returns what is left of w behind them (0 for every |w| <= 2^30).
+static inline int32_t score_digits(int32_t w, int8_t d[4]) {
+    int32_t x = w;
+    for (int p = 0; p < 4; p++) {
+        const int32_t dp = ((x + 128) & 255) - 128;
+        d[p] = (int8_t)dp;
+        x = (x - dp) >> 8;
+    }
+    return x;
+}
+// What is wrong with a call over `lines` lines of `line_len` characters, T weight columns and the T x line_len weights w (may be NULL: not
+// checked), or NULL.  plane_mask (may be NULL): bit p set iff digit plane p is not zero over all the weights.
+static inline const char* scores_arg_error(long lines, long line_len, long T, const int32_t* w, int* plane_mask) {
+    if (lines <= 0 || line_len <= 0) return "dims must be positive";
+    if (T < 1 || T > SCORES_MAX_COLUMNS) return "T outside [1, 64]";
+    if (line_len > SCORES_MAX_LINE) return "a line longer than EAGLE_SCORES_MAX_LINE = 8,388,480 characters";
+    if (lines > 0x7fffffffL) return "2^31 lines or more";
+    int mask = 0;
+    if (w) {
+        const long count = T * line_len;
+        for (long i = 0; i < count; i++) {
+            const int32_t x = w[i];
+            if (x > SCORES_MAX_WEIGHT || x < -SCORES_MAX_WEIGHT) return "a weight beyond +-2^30";
+            if (x == 0 || mask == 15) continue;
+            int8_t d[4];
+            (void)score_digits(x, d);
+            for (int p = 0; p < 4; p++) if (d[p]) mask |= 1 << p;
+        }
+    }
+    if (plane_mask) *plane_mask = mask;
+    return nullptr;
+}
 #endif

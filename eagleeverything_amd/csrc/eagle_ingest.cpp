@@ -1934,3 +1934,82 @@ extern "C" int eagle_weighted_gram(eagle_ctx* ctx, const char* f_name_ascii_M, c
     HIPCHK(ctx, hipSetDevice(ctx->device));
     return eagle_wgram(ctx, f_name_ascii_M, n, L, q, max_memory_in_Gbytes, host_threads(), Q_out);
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// Line scores (no counterpart in the reference; include/eagle_hip.h section 1b''''i, kernels in eagle_score.hip)
+// ---------------------------------------------------------------------------------------------------------------
+// out[r * T + t] = sum_c w[t * cols + c] g[r][c] for the `rows` lines of `cols` characters of a genotype file, read as line_counts reads
+// it: the resident image where it lies, else bands of whole lines through eagle_dev_load_ascii.  The weights become one digit image per
+// call; every band's rows are finished before the next band is read.
+static int line_scores(eagle_ctx* ctx, const char* path, long rows, long cols, const int32_t* w, long T, int plane_mask,
+                       double max_memory_in_Gbytes, int64_t* out) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int threads = host_threads();
+    const size_t outb = sizeof(int64_t) * (size_t)rows * (size_t)T;
+    if (!plane_mask) {   // every weight is zero: no product, and the file is not read
+        memset(out, 0, outb);
+        return EAGLE_OK;
+    }
+    // a resident image has 256-padded lines; the longest lines the engine addresses fit it only at the 128-padding of a band
+    const bool narrow = (double)eagle_pad(cols) * 256.0 >= 2147483648.0;
+    const GenoEntry* src = nullptr;
+    int rc = narrow ? EAGLE_STREAM : eagle_get_resident(ctx, path, rows, cols, max_memory_in_Gbytes, threads, &src);
+    if (rc != EAGLE_OK && rc != EAGLE_STREAM) return rc;
+    const bool resident = rc == EAGLE_OK;
+    const long ld = resident ? src->ld : (cols + 127) / 128 * 128;
+    const long band = resident ? rows : std::min(rows, stream_chunk_rows_core(eagle_resident_budget(), ld, eagle_pad(rows)));
+    DevBuf dw, dB, c32, dout, win;
+    HIPCHK(ctx, dout.alloc(outb));
+    HIPCHK(ctx, dw.alloc(sizeof(int32_t) * (size_t)T * (size_t)cols));
+    HIPCHK(ctx, dB.alloc((size_t)eagle_score_b_rows(T, plane_mask) * (size_t)ld));
+    HIPCHK(ctx, c32.alloc(eagle_line_scores_ws_bytes(band, T, plane_mask)));
+    HIPCHK(ctx, hipMemcpyAsync(dw.p, w, sizeof(int32_t) * (size_t)T * (size_t)cols, hipMemcpyHostToDevice, ctx->stream));
+    rc = eagle_dev_score_digits(ctx, dw.as<int32_t>(), T, cols, ld, plane_mask, dB.as<int8_t>(), ctx->stream);
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    if (resident) {
+        rc = eagle_dev_line_scores(ctx, src->dev, rows, cols, ld, dB.as<int8_t>(), T, plane_mask, c32.as<int32_t>(), dout.as<int64_t>(), ctx->stream);
+        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    } else {
+        const long wrows = eagle_pad(band);
+        HIPCHK(ctx, win.alloc((size_t)wrows * (size_t)ld));
+        for (long r0 = 0; r0 < rows; r0 += band) {
+            const long nr = std::min(band, rows - r0);
+            HIPCHK(ctx, hipMemsetAsync(win.p, 0, (size_t)wrows * (size_t)ld, ctx->stream));
+            rc = eagle_dev_load_ascii(ctx, path, r0, nr, 0, cols, win.as<int8_t>(), ld, max_memory_in_Gbytes, threads);
+            if (!rc) rc = eagle_dev_line_scores(ctx, win.as<int8_t>(), nr, cols, ld, dB.as<int8_t>(), T, plane_mask, c32.as<int32_t>(),
+                                                dout.as<int64_t>() + r0 * T, ctx->stream);
+            if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+        }
+    }
+    HIPCHK(ctx, hipMemcpyAsync(out, dout.p, outb, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return EAGLE_OK;
+}
+
+static_assert(SCORES_MAX_COLUMNS == EAGLE_SCORES_MAX_COLUMNS && SCORES_MAX_WEIGHT == EAGLE_SCORES_MAX_WEIGHT && SCORES_MAX_LINE == EAGLE_SCORES_MAX_LINE,
+              "eagle_host.h restates the limits of include/eagle_hip.h");
+static int scores_entry(eagle_ctx* ctx, const char* who, const char* path, const long dims[2], bool by_marker, const int32_t* w, long T,
+                        double max_memory_in_Gbytes, int64_t* out) {
+    char msg[160];
+    if (!path || !dims || !w || !out) { snprintf(msg, sizeof msg, "%s: NULL argument", who); return qc_fail(ctx, EAGLE_ERR_ARG, msg); }
+    const long n = dims[0], L = dims[1];
+    const long rows = by_marker ? L : n, cols = by_marker ? n : L;
+    int plane_mask = 0;
+    if (n <= 0 || L <= 0) { snprintf(msg, sizeof msg, "%s: dims must be positive", who); return qc_fail(ctx, EAGLE_ERR_ARG, msg); }
+    if (const char* bad = scores_arg_error(rows, cols, T, w, &plane_mask)) {
+        snprintf(msg, sizeof msg, "%s: %s", who, bad);
+        return qc_fail(ctx, EAGLE_ERR_ARG, msg);
+    }
+    if (!ctx) { snprintf(msg, sizeof msg, "%s: no context", who); return qc_fail(ctx, EAGLE_ERR_ARG, msg); }
+    return line_scores(ctx, path, rows, cols, w, T, plane_mask, max_memory_in_Gbytes, out);
+}
+
+extern "C" int eagle_sample_scores(eagle_ctx* ctx, const char* f_name_ascii_M, const long dims[2], const int32_t* w, long T,
+                                   double max_memory_in_Gbytes, int64_t* out) {
+    return scores_entry(ctx, "sample_scores", f_name_ascii_M, dims, false, w, T, max_memory_in_Gbytes, out);
+}
+
+extern "C" int eagle_marker_scores(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long dims[2], const int32_t* v, long T,
+                                   double max_memory_in_Gbytes, int64_t* out) {
+    return scores_entry(ctx, "marker_scores", f_name_ascii_Mt, dims, true, v, T, max_memory_in_Gbytes, out);
+}

@@ -101,6 +101,16 @@ int eagle_dev_ld_partners(eagle_ctx* ctx, const double* band, long rows, long wi
 int eagle_dev_ld_reduce(eagle_ctx* ctx, const double* band, long rows, long window, long c_lo, long c_hi, long g0, const int32_t* chrom,
                         const int64_t* pos, long max_dist, const int64_t* edges, int nbins, uint64_t* U, int32_t* cnt, uint64_t* bin_sum,
                         int64_t* bin_pairs, void* stream);
+// The exact line-score pass (eagle_score.hip; include/eagle_hip.h section 1b''''i), device pointers throughout.  B = the int8 digit image of
+// the T x cols int32 weights w: eagle_score_b_rows(T, plane_mask) rows of ld bytes (ld % 128 == 0), row rank(p) T + t = digit plane p of
+// column t for the planes p of plane_mask in increasing order, zero elsewhere.  out[r T + t] = sum_c w[t cols + c] img[r ld + c] for the
+// lines [0, rows) of an image whose rows up to the next multiple of 256 are allocated (pad128(cols) <= ld, ld * 256 < 2^31); c32:
+// eagle_line_scores_ws_bytes(rows, T, plane_mask) bytes of workspace.  The image is only read.
+long eagle_score_b_rows(long T, int plane_mask);
+size_t eagle_line_scores_ws_bytes(long rows, long T, int plane_mask);
+int eagle_dev_score_digits(eagle_ctx* ctx, const int32_t* w, long T, long cols, long ld, int plane_mask, int8_t* B, void* stream);
+int eagle_dev_line_scores(eagle_ctx* ctx, const int8_t* img, long rows, long cols, long ld, const int8_t* B, long T, int plane_mask,
+                          int32_t* c32, int64_t* out, void* stream);
 #ifdef __cplusplus
 }
 #include "eagle_host.h"

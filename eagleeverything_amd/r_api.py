@@ -1221,6 +1221,25 @@ def _grm_reference(reference, n):
     return R
 
 
+def _grm_denominator(q_info):
+    """D of G = Gc / D (grm_from_gram's docstring), one fp64 number from q_info."""
+    used = np.asarray(q_info["used"], dtype=bool).ravel()
+    L_used = int(used.sum())
+    if q_info["method"] == "standardized":
+        return float(q_info["scale"]) * float(L_used)
+    if q_info["method"] != "vanraden1":
+        raise ValueError("grm_from_gram: unknown method %r" % (q_info["method"],))
+    n0, n1, n2 = (np.asarray(q_info[k], dtype=np.int64).ravel()[used] for k in ("n0", "n1", "n2"))
+    N = n0 + n1 + n2
+    c = 2 * n2 + n1
+    Nf = N.astype(np.float64)
+    scale = float(q_info.get("scale", 1.0))
+    if scale == 1.0:
+        return float(np.sum((c * (2 * N - c)).astype(np.float64) / ((2.0 * Nf) * Nf)))
+    wq = np.asarray(q_info["q"]).ravel()[used].astype(np.float64) / scale
+    return scale * float(np.sum(wq * ((c * (2 * N - c)).astype(np.float64) / ((2.0 * Nf) * Nf))))
+
+
 def grm_from_gram(Q, q_info, reference=None):
     """The relationship matrix from the integer Gram product Q = rcpp_api.weighted_gram(..., q) -> fp64 (n, n), host numpy.
     q_info = {"method", "scale", "used"} of grm_weights, for "vanraden1" also "n0", "n1", "n2", the counts the weights came from (those
@@ -1245,19 +1264,7 @@ def grm_from_gram(Q, q_info, reference=None):
     r = Qf[:, R].sum(axis=1) / float(R.size)
     kappa = float(r[R].sum()) / float(R.size)
     Gc = Qf - r[:, None] - r[None, :] + kappa
-    if q_info["method"] == "standardized":
-        return Gc / (float(q_info["scale"]) * float(L_used))
-    if q_info["method"] != "vanraden1":
-        raise ValueError("grm_from_gram: unknown method %r" % (q_info["method"],))
-    n0, n1, n2 = (np.asarray(q_info[k], dtype=np.int64).ravel()[used] for k in ("n0", "n1", "n2"))
-    N = n0 + n1 + n2
-    c = 2 * n2 + n1
-    Nf = N.astype(np.float64)
-    scale = float(q_info.get("scale", 1.0))
-    if scale == 1.0:
-        return Gc / float(np.sum((c * (2 * N - c)).astype(np.float64) / ((2.0 * Nf) * Nf)))
-    wq = np.asarray(q_info["q"]).ravel()[used].astype(np.float64) / scale
-    return Gc / (scale * float(np.sum(wq * ((c * (2 * N - c)).astype(np.float64) / ((2.0 * Nf) * Nf)))))
+    return Gc / _grm_denominator(q_info)
 
 
 def GRM(geno, method="standardized", maf=0.0, include=None, reference=None, stats=None, availmemGb=8, device=0, ld_score=None):
@@ -1305,7 +1312,7 @@ def GRM(geno, method="standardized", maf=0.0, include=None, reference=None, stat
 
 
 def PCA(geno, k=10, method="standardized", maf=0.01, reference=None, grm=None, eig=None, include=None, stats=None, availmemGb=8, device=0,
-        ld_score=None):
+        ld_score=None, loadings=False):
     """Principal components of the relationship matrix, the covariates of AM(trait, am.add_pcs(X, pca), geno) ->
     {"values": the top k eigenvalues of G[R, R], decreasing, "pcs": fp64 (n, k), "explained": values / trace(G[R, R]), "reference":
     R, "grm": the GRM dict}.  grm = a dict of GRM() (then geno may be None and method / maf / include / stats are not used; its
@@ -1318,7 +1325,15 @@ def PCA(geno, k=10, method="standardized", maf=0.01, reference=None, grm=None, e
     (1 / lambda_a) sum_{j in R} G_ij U_ja, which for a member of R is its eigenvector entry exactly (G[R, R] U = U diag(lambda)), so
     a duplicate of a reference individual lands on it.  It is the usual projection and is NOT corrected for shrinkage: with few
     individuals per marker projected individuals sit nearer the origin than reference ones (Lee et al. 2010).
-    ValueError for k < 1 or k > |R| - 1 (centring takes one dimension)."""
+    ValueError for k < 1 or k > |R| - 1 (centring takes one dimension).
+    loadings=True (geno is then needed also with grm=): the result also carries the marker loadings that place ANY panel with these
+    markers on the components (ProjectPCA), "loadings" fp64 (L, k), "offset" fp64 (k) and "loadings_bound" fp64 (k):
+        l_ma = q_m (sum_{j in R} g_jm U_ja) / (D lambda_a),      offset_a = sum_m l_ma mu_m,      mu_m = (n2 - n0) / N over R,
+    D the denominator grm_from_gram divides by, so that sum_m l_ma g_im - offset_a is the projection above (no centring term is needed
+    inside the sum: sum_{j in R} U_ja = 0 for lambda_a > 0, the constant vector being an eigenvector of the double-centred G[R, R] at
+    0).  The inner sums are ONE rcpp_api.marker_scores call: the k eigenvectors, zero outside R, quantised by quantise_weights (scale
+    s_a), so every inner sum errs by at most 0.5 |R| / s_a and loadings_bound[a] = max_m q_m 0.5 |R| / (s_a D lambda_a) bounds the error
+    of every l_ma.  The default False leaves every result and every call as it was."""
     if grm is None:
         grm = GRM(geno, method=method, maf=maf, include=include, reference=reference, stats=stats, availmemGb=availmemGb, device=device,
                   ld_score=ld_score)
@@ -1339,7 +1354,115 @@ def PCA(geno, k=10, method="standardized", maf=0.01, reference=None, grm=None, e
     U = U * np.where(U[big, np.arange(k)] < 0, -1.0, 1.0)[None, :]
     pcs = (G[:, R] @ U) / lam[None, :]
     pcs[R] = U
-    return {"values": lam, "pcs": pcs, "explained": lam / float(np.trace(GR)), "reference": R, "grm": grm}
+    out = {"values": lam, "pcs": pcs, "explained": lam / float(np.trace(GR)), "reference": R, "grm": grm}
+    if loadings:
+        if geno is None:
+            raise ValueError("PCA: loadings=True needs geno")
+        out.update(_pca_loadings(lambda v: rcpp_api.marker_scores(geno["asciifileMt"], geno["dim_of_ascii_M"], v, availmemGb, device=device),
+                                 grm, R, lam, U))
+    return out
+
+
+def _pca_loadings(marker_scores, grm, R, lam, U):
+    """PCA(loadings=True)'s three entries; marker_scores: int (k, n) -> int64 (L, k), the exact M^T V."""
+    n = np.asarray(grm["G"]).shape[0]
+    V = np.zeros((n, U.shape[1]))
+    V[R] = U
+    vq, sc = quantise_weights(V)
+    S = np.asarray(marker_scores(np.ascontiguousarray(vq.T))).astype(np.float64)          # |S| < 2^53: exact
+    q = np.asarray(grm["q"]).astype(np.float64).ravel()
+    D = _grm_denominator(grm)
+    load = q[:, None] * (S / sc[None, :]) / (D * lam[None, :])
+    n0, n1, n2 = (np.asarray(grm[key], dtype=np.int64).ravel() for key in ("n0", "n1", "n2"))
+    N = np.maximum(n0 + n1 + n2, 1).astype(np.float64)
+    mu = (n2 - n0).astype(np.float64) / N
+    return {"loadings": load, "offset": mu @ load, "loadings_bound": float(q.max()) * 0.5 * float(R.size) / (sc * D * lam)}
+
+
+def ProjectPCA(pca, geno, availmemGb=8, device=0):
+    """The individuals of ANY panel with the markers of the PCA's panel, in the same order, on its components -> fp64 (n_new, k):
+    Score(geno, pca["loadings"])["score"] - pca["offset"] with pca = PCA(..., loadings=True).  For the PCA's own panel this reproduces
+    pca["pcs"] up to the two quantisation bounds (the loadings', times the markers used, twice: score and offset; and Score's own).
+    The scores are exact integer sums, so an individual's coordinates depend on its genotypes alone: a duplicate lands on its original
+    bit for bit, in whatever panel and order.  Not corrected for shrinkage (PCA's docstring).  ValueError for a panel of another L."""
+    if "loadings" not in pca:
+        raise ValueError("ProjectPCA: the PCA carries no loadings (PCA(..., loadings=True))")
+    load = np.asarray(pca["loadings"], dtype=np.float64)
+    L = int(geno["dim_of_ascii_M"][1])
+    if load.shape[0] != L:
+        raise ValueError("ProjectPCA: the loadings hold %d markers, the panel %d" % (load.shape[0], L))
+    return Score(geno, load, availmemGb=availmemGb, device=device)["score"] - np.asarray(pca["offset"], dtype=np.float64)[None, :]
+
+
+# ---- line scores (include/eagle_hip.h section 1b''''i): exact integer M w and M^T V on the device, quantising and scaling on the host ----
+def line_scores_host(G8, w):
+    """The numpy restatement of rcpp_api.sample_scores / marker_scores -> int64 (R, T): G8.astype(int64) @ w.T for an image G8 (R, C)
+    in {-1, 0, +1} and integer weights w (C,) or (T, C)."""
+    w = np.asarray(w)
+    w = w[None, :] if w.ndim == 1 else w
+    return np.asarray(G8).astype(np.int64) @ w.astype(np.int64).T
+
+
+def score_digits_host(w):
+    """The four balanced base-256 digit planes of integer weights |w| <= 2^30 -> int8 (4,) + w.shape with
+    w = d0 + 256 d1 + 256^2 d2 + 256^3 d3, d in [-128, 127]:  d_p = ((w_p + 128) & 255) - 128,  w_{p+1} = (w_p - d_p) >> 8."""
+    x = np.asarray(w).astype(np.int64)
+    if x.size and np.abs(x).max() > rcpp_api.SCORES_MAX_WEIGHT:
+        raise ValueError("score_digits_host: a weight is beyond +-2^30")
+    planes = np.zeros((4,) + x.shape, dtype=np.int8)
+    for p in range(4):
+        d = ((x + 128) & 255) - 128
+        planes[p] = d
+        x = (x - d) >> 8
+    return planes
+
+
+def quantise_weights(w, bits=30):
+    """Real weights as integers for the exact score pass -> (wq int32, scale), per column of w (C,) or (C, T); scale is a float for
+    a vector and fp64 (T,) for a matrix.  scale = 2^e, the largest power of two with max|w| * scale <= 2^bits (so the product is
+    exact and rint rounds the true value), wq = rint(w * scale); a zero column gives scale 1.0; a non-finite entry raises ValueError.
+    |w - wq / scale| <= 0.5 / scale, so a score over C characters g in {-1, 0, +1} errs by at most 0.5 C / scale < C max|w| 2^-29 at
+    the default bits = 30 (scale > 2^29 / max|w|)."""
+    wa = np.asarray(w, dtype=np.float64)
+    if wa.ndim not in (1, 2) or not 1 <= int(bits) <= 30:
+        raise ValueError("quantise_weights: w must be (C,) or (C, T) and 1 <= bits <= 30")
+    if not np.all(np.isfinite(wa)):
+        raise ValueError("quantise_weights: a weight is not finite")
+    cols = wa.reshape(wa.shape[0], -1)
+    mx = np.abs(cols).max(axis=0) if cols.shape[0] else np.zeros(cols.shape[1])
+    f, x = np.frexp(mx)                                   # mx = f 2^x, 0.5 <= f < 1
+    e = np.clip(int(bits) - x + (f == 0.5), -1022, 1023)
+    scale = np.where(mx > 0, np.ldexp(1.0, e.astype(np.int64)), 1.0)
+    wq = np.rint(cols * scale[None, :]).astype(np.int32)
+    return (wq.ravel(), float(scale[0])) if wa.ndim == 1 else (wq, scale)
+
+
+def Score(geno, weights, include=None, dosage=False, availmemGb=8, device=0):
+    """A weighted allele sum per individual, what PLINK --score computes -> {"score": fp64 (n, T) = S / scale, "S": int64 (n, T), the
+    exact sums sum_m wq_tm g_im (rcpp_api.sample_scores: balanced base-256 digit planes of the weights on the int8 MFMA), "wq" int32
+    (L, T), "scale" fp64 (T,) (quantise_weights), "bound" fp64 (T,)}.  weights: fp64 (L,) or (L, T), one column per score.
+    include = a boolean mask of markers: the other markers' weights are zero.  g in {-1, 0, +1} = AA, AB, BB; dosage=True scores the
+    0 / 1 / 2 allele count instead, S + sum_m wq_m per column (host arithmetic on wq).
+    |score - the fp64 product| <= bound = 0.5 (used markers) / scale, twice that with dosage (an allele count reaches 2), plus the
+    rounding of the fp64 product itself."""
+    n, L = int(geno["dim_of_ascii_M"][0]), int(geno["dim_of_ascii_M"][1])
+    wa = np.asarray(weights, dtype=np.float64)
+    wa = wa.reshape(-1, 1) if wa.ndim == 1 else wa
+    if wa.ndim != 2 or wa.shape[0] != L:
+        raise ValueError("Score: the weights hold %s entries, the panel %d markers" % (wa.shape[0] if wa.ndim else 0, L))
+    used = L
+    if include is not None:
+        inc = np.asarray(include, dtype=bool).ravel()
+        if inc.size != L:
+            raise ValueError("Score: include holds %d markers, the panel %d" % (inc.size, L))
+        wa = np.where(inc[:, None], wa, 0.0)
+        used = int(inc.sum())
+    wq, scale = quantise_weights(wa)
+    S = rcpp_api.sample_scores(geno["asciifileM"], (n, L), np.ascontiguousarray(wq.T), availmemGb, device=device)
+    if dosage:
+        S = S + wq.astype(np.int64).sum(axis=0)[None, :]
+    return {"score": S.astype(np.float64) / scale[None, :], "S": S, "wq": wq, "scale": scale,
+            "bound": (1.0 if dosage else 0.5) * float(used) / scale}
 
 
 def _ld_sv(stats, n):
@@ -1577,3 +1700,15 @@ def FPR4AM(trait, X, geno, falseposrate=0.05, numreps=200, seed=101, availmemGb=
     from . import am
     return am.FPR4AM(trait, X, geno, falseposrate=falseposrate, numreps=numreps, seed=seed, availmemGb=availmemGb, quiet=quiet,
                      message=message, algebra=algebra, device=device, eig=eig, chunk=chunk)
+
+
+def MarkerEffects(AMobj, trait, X, geno, availmemGb=8, backend=None, device=0):
+    """The fitted model of am.AM() as per-marker effects (am.MarkerEffects, which documents arguments and result)."""
+    from . import am
+    return am.MarkerEffects(AMobj, trait, X, geno, availmemGb=availmemGb, backend=backend, device=device)
+
+
+def Predict(effects, geno, X=None, availmemGb=8, device=0):
+    """Genetic values of the individuals of any panel with the model's markers from MarkerEffects' result (am.Predict)."""
+    from . import am
+    return am.Predict(effects, geno, X=X, availmemGb=availmemGb, device=device)

@@ -945,6 +945,59 @@ def weighted_gram(f_name_ascii_M, dims, q, max_memory_in_Gbytes=8.0, device=0):
     return out
 
 
+# ---- line scores (include/eagle_hip.h section 1b''''i): M w and M^T V as exact integers; quantising and scaling are r_api's ----
+SCORES_MAX_COLUMNS = 64
+SCORES_MAX_WEIGHT = 1 << 30
+SCORES_MAX_LINE = 8388480
+
+
+def _score_weights(who, w, length):
+    """The weights of a scores call as int64 (T, length); ValueError before the library is called."""
+    wa = np.asarray(w)
+    if wa.ndim == 1:
+        wa = wa[None, :]
+    if wa.ndim != 2 or wa.shape[0] < 1 or wa.shape[1] != length:
+        raise ValueError("%s: the weights must be (%d,) or (T, %d), got %s" % (who, length, length, np.shape(w)))
+    if wa.dtype == bool:
+        wa = wa.astype(np.int64)
+    if wa.dtype.kind not in "iu":
+        if wa.dtype.kind != "f" or not np.all(wa == np.floor(wa)):   # (a NaN fails the comparison)
+            raise ValueError("%s: the weights must hold whole numbers" % who)
+    if wa.size and (wa.max() > SCORES_MAX_WEIGHT or wa.min() < -SCORES_MAX_WEIGHT):
+        raise ValueError("%s: a weight is beyond +-2^30" % who)
+    return wa.astype(np.int64)
+
+
+def _line_scores(fn, who, path, dims, rows, length, w, max_memory_in_Gbytes, device):
+    wa = _score_weights(who, w, length)
+    out = np.zeros((rows, wa.shape[0]), dtype=np.int64)
+    for t0 in range(0, wa.shape[0], SCORES_MAX_COLUMNS):   # more than 64 columns: calls of 64
+        w32 = np.ascontiguousarray(wa[t0:t0 + SCORES_MAX_COLUMNS], dtype=np.int32)
+        part = np.zeros((rows, w32.shape[0]), dtype=np.int64)
+        _args_first(fn, device, (os.fsencode(path), _dims(dims), w32.ctypes.data_as(_c_i32p), w32.shape[0], float(max_memory_in_Gbytes),
+                                 part.ctypes.data_as(_c_i64p)))
+        out[:, t0:t0 + w32.shape[0]] = part
+    return out
+
+
+def sample_scores(f_name_ascii_M, dims, w, max_memory_in_Gbytes=8.0, device=0):
+    """eagle_sample_scores -> int64 (n, T): S[i, t] = sum over the markers m of w[t, m] g_im with g in {-1, 0, +1}, exact, for integer
+    weights |w| <= SCORES_MAX_WEIGHT = 2^30; w is (L,) (T = 1) or (T, L) of any integer dtype (dims = (n, L) of M).  ValueError for a
+    wrong length, a fractional value or a weight beyond 2^30, before the library is called.  More than SCORES_MAX_COLUMNS columns run
+    as calls of 64.  A view alias gives the scores of its kept individuals.  r_api.line_scores_host is the numpy restatement."""
+    L = _lib.load()
+    return _line_scores(L.eagle_sample_scores, "sample_scores", f_name_ascii_M, dims, max(int(dims[0]), 0), max(int(dims[1]), 0), w,
+                        max_memory_in_Gbytes, device)
+
+
+def marker_scores(f_name_ascii_Mt, dims, v, max_memory_in_Gbytes=8.0, device=0):
+    """eagle_marker_scores -> int64 (L, T): the exact M^T V, out[m, t] = sum over the individuals i of v[t, i] g_im, for integer weights
+    |v| <= 2^30; v is (n,) or (T, n) (dims = (n, L) of M).  For a view alias n = dims[0] is the number of kept individuals."""
+    L = _lib.load()
+    return _line_scores(L.eagle_marker_scores, "marker_scores", f_name_ascii_Mt, dims, max(int(dims[1]), 0), max(int(dims[0]), 0), v,
+                        max_memory_in_Gbytes, device)
+
+
 # ---- SURVEY 8 f-4: the dense model algebra on the device, through the C ABI (opt-in; include/eagle_hip.h section 1c) ----
 def _square_any_order(A):
     """(buffer, transposed): a float64 n x n array usable as a column-major matrix without a copy when it is contiguous in

@@ -687,6 +687,50 @@ int eagle_weighted_gram(eagle_ctx* ctx, const char* f_name_ascii_M, const long d
                         int64_t* Q_out);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1b''''i. Line scores (no counterpart in the reference, which stops at the fitted model): the two products that use a model on a panel,
+ *     as one exact integer pass over either genotype file.  For a file of R lines of C characters and T columns of integer weights,
+ *         out[r * T + t] = sum_c w[t * C + c] * g[r][c]          (int64, exact, |out| <= 2^30 * C < 2^61).
+ *     On M.ascii a line is an individual and the weights are per marker: the result is M w, a polygenic or genomic score per
+ *     individual (eagle_sample_scores).  On Mt.ascii a line is a marker and the weights are per individual: the result is M^T V, one
+ *     number per marker from one number per individual, for T vectors at once (eagle_marker_scores) -- marker BLUPs, PCA loadings.
+ *
+ *     1. Genotypes and weights.  g in {-1, 0, +1} = AA, AB, BB as everywhere in this library; a missing genotype of the source is a
+ *        heterozygote by now.  Weights are int32 with |w| <= 2^30 = EAGLE_SCORES_MAX_WEIGHT; 1 <= T <= 64 = EAGLE_SCORES_MAX_COLUMNS.
+ *     2. Digits.  w = d0 + 256 d1 + 256^2 d2 + 256^3 d3 with balanced digits d in [-128, 127]:  d_p = ((w_p + 128) & 255) - 128 and
+ *        w_{p+1} = (w_p - d_p) >> 8, from w_0 = w.  Four digits hold every |w| <= 2^30.  Each digit plane of each column is one int8
+ *        operand row, d * g is an int8 x int8 product accumulated in int32, and out = sum_p 256^p C^(p) in int64.  A plane whose
+ *        digits are all zero over the call costs nothing: weights with |w| <= 127 are one plane, w = 0 everywhere is no product.
+ *     3. Line length.  C <= EAGLE_SCORES_MAX_LINE = 8,388,480, the largest multiple of 128 below 2^23 (the addressing contract of the
+ *        tile engine, ld * 256 < 2^31).  A plane's int32 accumulator holds at most 128 C < 2^31: nothing wraps and no fold is needed.
+ *     4. Order.  Integer sums do not depend on the order of summation: the device, whatever its K splits and the order of its atomic
+ *        adds, and numpy's int64 product (r_api.line_scores_host) agree bit for bit.
+ *
+ *     k_score_digits writes the digit image (at most 256 live rows of the line's padded length; T <= 64 is 256 rows at four planes),
+ *     k_line_scores_i8 is the stage loop of k_syrk_i8's tile engine over a rectangular work list (row tile, 0) x K splits -- one pass
+ *     over the image per call, no temporary of image size -- and k_scores_finish sums the planes.  The cached int8 and fp4 images of a
+ *     resident file are only read: a later eagle_calculateMMt on the same file returns the bits it returned before.
+ *
+ *     The file is read as eagle_marker_counts reads it: the resident image where it lies, otherwise bands of whole lines from the
+ *     sidecar, the text or a VIEW alias's source.  Rows are independent, so bands need no accumulation across windows, and streamed and
+ *     resident runs give the same integers.  With a VIEW alias of eagle_reshape_m the M file has the kept individuals as lines and the
+ *     Mt file has them as columns (v then has dims[0] = kept entries per column).  Single device: a multi-device context works on
+ *     its first device.  Argument errors (EAGLE_ERR_ARG: a NULL pointer, dims <= 0, T outside [1, 64], a line longer than
+ *     EAGLE_SCORES_MAX_LINE, more than 2^31 - 1 lines, a weight beyond +-2^30) are decided before the context is used; with ctx == NULL
+ *     their text is in eagle_open_error().
+ * ------------------------------------------------------------------------------------------- */
+#define EAGLE_SCORES_MAX_COLUMNS 64L
+#define EAGLE_SCORES_MAX_WEIGHT 1073741824L
+#define EAGLE_SCORES_MAX_LINE 8388480L
+
+/* out: n x T int64, row-major: the scores of the n lines of M.ascii (dims = (n, L)) under the T x L weights w (row-major, one row per
+ * column of the result). */
+int eagle_sample_scores(eagle_ctx* ctx, const char* f_name_ascii_M, const long dims[2], const int32_t* w, long T, double max_memory_in_Gbytes,
+                        int64_t* out);
+/* out: L x T int64, row-major: M^T V for the L lines of Mt.ascii (dims = (n, L) of M) and the T x n weights v (row-major). */
+int eagle_marker_scores(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long dims[2], const int32_t* v, long T, double max_memory_in_Gbytes,
+                        int64_t* out);
+
+/* ---------------------------------------------------------------------------------------------
  * 1c. Dense n x n model algebra on the device (OPT-IN: north_star keeps calculateH / calculateP / emma.* on
  *     host LAPACK, and nothing above calls these).  Once the scan takes tens of milliseconds the ~10-15 O(n^3) base-R calls
  *     of a find_qtl iteration are the whole run time (the author's note MyPackage/MyREADME:1 names eigen(); his MAGMA
