@@ -234,6 +234,19 @@ extern "C" int eagle_dev_bedld_band(eagle_ctx* ctx, const int8_t* X, const int8_
                                     double t, long min_overlap, uint64_t* mask, long words_per_row, void* stream);
 extern "C" int eagle_dev_bedld_r2band(eagle_ctx* ctx, const int8_t* X, const int8_t* C, const int8_t* U, long rows, long n, long ld, long window,
                                       long min_overlap, double* band, void* stream);
+// Runs of homozygosity (eagle_roh.hip; include/eagle_hip.h section 1b'''vi), device pointers throughout.  planes: 3 x markers x ceil(n / 64)
+// uint64 (flagged, het, miss), marker-major; blk: the nb + 1 block bounds of rule 2.  The flags calls write the planes' rows of the panel
+// markers [c0, c1) from a source whose row 0 is panel marker g0 and which holds the markers [max(0, c0 - (w - 1)), min(markers, c1 + w -
+// 1)) at least: an int8 Mt image, or raw .bed rows (the row of marker g0 + p at offsets[p], null: row p; checked by the CALLER).  The
+// segments call is the count pass (fill == 0: cnt n x nb written, ind n x 4 added to -- zero it first) or the fill pass (rows of seg from
+// the exclusive scan offs of cnt).
+extern "C" int eagle_dev_roh_flags_i8(eagle_ctx* ctx, const int8_t* Mt8, long ld, long n, long g0, long c0, long c1, const int32_t* blk, long nb,
+                                      const eagle_roh_params* prm, uint64_t* planes, long markers, void* stream);
+extern "C" int eagle_dev_roh_flags_bed(eagle_ctx* ctx, const uint8_t* bed, const long* offsets, long n, long g0, long c0, long c1,
+                                       const int32_t* blk, long nb, const eagle_roh_params* prm, uint64_t* planes, long markers, void* stream);
+extern "C" int eagle_dev_roh_segments(eagle_ctx* ctx, const uint64_t* planes, long markers, long n, const int32_t* blk, long nb, const int64_t* pos,
+                                      const eagle_roh_params* prm, int fill, int32_t* cnt, int64_t* ind, const int64_t* offs, int32_t* seg,
+                                      void* stream);
 // Pairwise-complete IBS counts from a .bed file (eagle_bedibs.hip; include/eagle_hip.h section 1b'''ii), device pointers throughout.  The
 // four fp4 operand images (g, u, h, c; plane p at M4 + p * plane_bytes, n_pad rows of ld4 bytes, L_pad markers written) of `rows` raw
 // .bed rows, `include` one byte per row or null; the four n x n int32 results and dist (or null) from the four Gram accumulators

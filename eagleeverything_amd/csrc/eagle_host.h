@@ -344,4 +344,50 @@ static inline const char* scores_arg_error(long lines, long line_len, long T, co
     if (plane_mask) *plane_mask = mask;
     return nullptr;
 }
+
+// ------------------------------------------------------------------------------------------------
+// Runs of homozygosity (include/eagle_hip.h section 1b'''vi): the argument rule of eagle_roh / eagle_bed_roh, the block table of rule 2
+// and the check of pos.
+// ------------------------------------------------------------------------------------------------
+#define ROH_MAX_WINDOW 64L
+#define ROH_MAX_DENSITY 2147483648L   /* 2^31 */
+// The nine fields of eagle_roh_params in their order: w, win_het, win_miss, thr16, min_snp, min_len, max_gap, max_density, max_het.
+// What is wrong with a call over `markers` panel markers, or NULL.
+static inline const char* roh_arg_error(const int64_t p[9], long markers, long seg_cap, bool has_seg_out) {
+    if (p[0] < 1 || p[0] > ROH_MAX_WINDOW) return "w must be in [1, 64]";
+    if (p[1] < 0) return "win_het must not be negative";
+    if (p[2] < 0) return "win_miss must not be negative";
+    if (p[3] < 0 || p[3] > 65536) return "thr16 must be in [0, 65536]";
+    if (p[4] < 1) return "min_snp must be at least 1";
+    if (p[5] < 0) return "min_len must not be negative";
+    if (p[6] < 0) return "max_gap must not be negative";
+    if (p[7] < 0 || p[7] > ROH_MAX_DENSITY) return "max_density must be in [0, 2^31]";
+    if (markers > 0x7fffffffL) return "2^31 markers or more";
+    if (seg_cap < 0) return "seg_cap must not be negative";
+    if (seg_cap > 0 && !has_seg_out) return "NULL argument (seg_out, with seg_cap > 0)";
+    return nullptr;
+}
+// Block bounds of rule 2: blk[0] = 0 < blk[1] < ... < blk[nb] = markers, a block a maximal run of equal chrom (NULL: one block).
+static inline void roh_block_table(const int32_t* chrom, long markers, std::vector<int32_t>& blk) {
+    blk.clear();
+    blk.push_back(0);
+    if (chrom)
+        for (long m = 1; m < markers; m++)
+            if (chrom[m] != chrom[m - 1]) blk.push_back((int32_t)m);
+    blk.push_back((int32_t)markers);
+}
+// The first marker m with pos[m] < pos[m - 1] inside a block, or -1 (pos NULL: -1).  Block edges are not compared across.
+static inline long roh_pos_check(const int64_t* pos, const std::vector<int32_t>& blk) {
+    if (!pos) return -1;
+    for (size_t b = 0; b + 1 < blk.size(); b++)
+        for (long m = (long)blk[b] + 1; m < (long)blk[b + 1]; m++)
+            if (pos[m] < pos[m - 1]) return m;
+    return -1;
+}
+// Exclusive scan of the segment counts by (individual, block), in that order; returns the total.
+static inline int64_t roh_offsets(const int32_t* cnt, size_t cells, int64_t* offs) {
+    int64_t t = 0;
+    for (size_t c = 0; c < cells; c++) { offs[c] = t; t += cnt[c]; }
+    return t;
+}
 #endif

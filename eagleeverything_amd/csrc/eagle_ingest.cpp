@@ -1458,6 +1458,9 @@ struct BedLdPanel {
     DevBuf d_offs[2], X, C, U;
     hipEvent_t done[2] = {nullptr, nullptr};
     long windows = 0;
+    bool pack = true;               // false (eagle_bed_roh): no operand images; the caller works on the staged rows and calls release()
+    const uint8_t* raw = nullptr;   // the rows staged last, and their offsets (null: the identity)
+    const long* raw_off = nullptr;
     ~BedLdPanel() {
         for (int b = 0; b < 2; b++) if (done[b]) (void)hipEventDestroy(done[b]);
         if (fd >= 0) close(fd);
@@ -1489,10 +1492,18 @@ struct BedLdPanel {
             HIPCHK(ctx, hipMemcpyAsync(d_offs[b].p, offs[b].data(), sizeof(long) * (size_t)P, hipMemcpyHostToDevice, ctx->stream));
             d_off = d_offs[b].as<long>();
         }
+        raw = (const uint8_t*)ctx->stage_raw[b];
+        raw_off = d_off;
+        if (!pack) return EAGLE_OK;
         int rc = eagle_dev_bed_ld_pack(ctx, (const uint8_t*)ctx->stage_raw[b], span, d_off, P, n, ld, X.as<int8_t>(), C.as<int8_t>(), U.as<int8_t>(),
                                        ctx->stream);
         if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
         HIPCHK(ctx, hipEventRecord(done[b], ctx->stream));            // the staging buffer is free once the pack has read it
+        return EAGLE_OK;
+    }
+    // pack == false: the kernels that read the rows staged last have been launched
+    int release() {
+        HIPCHK(ctx, hipEventRecord(done[(int)((windows - 1) & 1)], ctx->stream));
         return EAGLE_OK;
     }
 };
@@ -1535,9 +1546,11 @@ int bedld_open(BedLdPanel& pl, eagle_ctx* ctx, const char* bed_path, long n, lon
     }
     int rc = eagle_stage_ensure(ctx, (size_t)span_max * pl.rb);
     if (rc) return rc;
-    HIPCHK(ctx, pl.X.alloc((size_t)p_max * pl.ld));
-    HIPCHK(ctx, pl.C.alloc((size_t)p_max * pl.ld));
-    HIPCHK(ctx, pl.U.alloc((size_t)p_max * pl.ld));
+    if (pl.pack) {
+        HIPCHK(ctx, pl.X.alloc((size_t)p_max * pl.ld));
+        HIPCHK(ctx, pl.C.alloc((size_t)p_max * pl.ld));
+        HIPCHK(ctx, pl.U.alloc((size_t)p_max * pl.ld));
+    }
     if (include) for (int b = 0; b < 2; b++) HIPCHK(ctx, pl.d_offs[b].alloc(sizeof(long) * (size_t)p_max));
     for (int b = 0; b < 2; b++) HIPCHK(ctx, hipEventCreateWithFlags(&pl.done[b], hipEventDisableTiming));
     pl.wmax = std::min(pl.wmax, p_max);
@@ -1678,6 +1691,168 @@ extern "C" int eagle_bed_ld_stats(eagle_ctx* ctx, const char* bed_path, const lo
     });
     if (rc) return rc;
     return ld_stats_end(ctx, b, U_out, cnt_out, bin_sum_out, bin_pairs_out);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Runs of homozygosity (include/eagle_hip.h section 1b'''vi; kernels in eagle_roh.hip)
+// ---------------------------------------------------------------------------------------------------------------
+static_assert(ROH_MAX_WINDOW == EAGLE_ROH_MAX_WINDOW, "eagle_host.h restates the public limit");
+namespace {
+
+// What both entry points hold on the device: the three bit planes of the panel, the block table, pos, and the segment passes' arrays.
+struct RohBufs {
+    DevBuf planes, blk, pos, cnt, offs, ind, seg;
+    std::vector<int32_t> h_blk;
+    long lp = 0, n = 0;
+    long nb() const { return (long)h_blk.size() - 1; }
+};
+
+// The argument rule of eagle_host.h, the block table and the check of pos: everything that is decided before the context is used.
+int roh_check(eagle_ctx* ctx, const char* who, long lp, const int32_t* chrom, const int64_t* pos, const eagle_roh_params* prm, const void* seg_out,
+              long seg_cap, std::vector<int32_t>& blk) {
+    const int64_t f[9] = {prm->w, prm->win_het, prm->win_miss, prm->thr16, prm->min_snp, prm->min_len, prm->max_gap, prm->max_density, prm->max_het};
+    char msg[160];
+    if (const char* bad = roh_arg_error(f, lp, seg_cap, seg_out != nullptr)) {
+        snprintf(msg, sizeof msg, "%s: %s", who, bad);
+        return qc_fail(ctx, EAGLE_ERR_ARG, msg);
+    }
+    roh_block_table(chrom, lp, blk);
+    const long m = roh_pos_check(pos, blk);
+    if (m >= 0) {
+        snprintf(msg, sizeof msg, "%s: pos decreases inside a block (panel marker %ld)", who, m);
+        return qc_fail(ctx, EAGLE_ERR_ARG, msg);
+    }
+    return EAGLE_OK;
+}
+
+// The planes against the memory budget (rule 8), then the allocations and uploads; no kernel has run when this fails.
+int roh_begin(eagle_ctx* ctx, const char* who, RohBufs& b, long n, long lp, const int64_t* pos) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    b.n = n;
+    b.lp = lp;
+    const size_t nw = (size_t)((n + 63) / 64), plane_bytes = sizeof(uint64_t) * 3 * (size_t)lp * nw;
+    size_t budget = eagle_resident_budget();
+    if (budget == (size_t)-1) {
+        size_t freeb = 0, totalb = 0;
+        HIPCHK(ctx, hipMemGetInfo(&freeb, &totalb));
+        budget = freeb > ((size_t)1 << 30) ? freeb - ((size_t)1 << 30) : 0;
+    }
+    if (plane_bytes > budget) return failf(ctx, EAGLE_ERR_NOMEM, "%s: the three bit planes (%zu bytes) do not fit the memory budget", who, plane_bytes);
+    const size_t cells = (size_t)n * (size_t)b.nb();
+    HIPCHK(ctx, b.planes.alloc(plane_bytes));
+    HIPCHK(ctx, b.blk.alloc(sizeof(int32_t) * b.h_blk.size()));
+    HIPCHK(ctx, b.cnt.alloc(sizeof(int32_t) * cells));
+    HIPCHK(ctx, b.offs.alloc(sizeof(int64_t) * cells));
+    HIPCHK(ctx, b.ind.alloc(sizeof(int64_t) * 4 * (size_t)n));
+    HIPCHK(ctx, hipMemcpyAsync(b.blk.p, b.h_blk.data(), sizeof(int32_t) * b.h_blk.size(), hipMemcpyHostToDevice, ctx->stream));
+    if (pos) {
+        HIPCHK(ctx, b.pos.alloc(sizeof(int64_t) * (size_t)lp));
+        HIPCHK(ctx, hipMemcpyAsync(b.pos.p, pos, sizeof(int64_t) * (size_t)lp, hipMemcpyHostToDevice, ctx->stream));
+    }
+    return EAGLE_OK;
+}
+
+// The count pass, the exclusive scan of the counts by (individual, block) on the host, and the fill pass when the rows fit seg_cap.
+int roh_end(eagle_ctx* ctx, RohBufs& b, const eagle_roh_params* prm, int64_t* ind_out, int32_t* seg_out, long seg_cap, long* nseg_out) {
+    const size_t cells = (size_t)b.n * (size_t)b.nb();
+    const int64_t* d_pos = b.pos.p ? b.pos.as<int64_t>() : nullptr;
+    HIPCHK(ctx, hipMemsetAsync(b.ind.p, 0, sizeof(int64_t) * 4 * (size_t)b.n, ctx->stream));
+    int rc = eagle_dev_roh_segments(ctx, b.planes.as<uint64_t>(), b.lp, b.n, b.blk.as<int32_t>(), b.nb(), d_pos, prm, 0, b.cnt.as<int32_t>(),
+                                    b.ind.as<int64_t>(), nullptr, nullptr, ctx->stream);
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    std::vector<int32_t> h_cnt(cells);
+    std::vector<int64_t> h_offs(cells);
+    HIPCHK(ctx, hipMemcpyAsync(h_cnt.data(), b.cnt.p, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ind_out, b.ind.p, sizeof(int64_t) * 4 * (size_t)b.n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    const int64_t total = roh_offsets(h_cnt.data(), cells, h_offs.data());
+    *nseg_out = (long)total;
+    if (total == 0 || total > seg_cap) return EAGLE_OK;
+    HIPCHK(ctx, b.seg.alloc(sizeof(int32_t) * 6 * (size_t)total));
+    HIPCHK(ctx, hipMemcpyAsync(b.offs.p, h_offs.data(), sizeof(int64_t) * cells, hipMemcpyHostToDevice, ctx->stream));
+    rc = eagle_dev_roh_segments(ctx, b.planes.as<uint64_t>(), b.lp, b.n, b.blk.as<int32_t>(), b.nb(), d_pos, prm, 1, nullptr, nullptr,
+                                b.offs.as<int64_t>(), b.seg.as<int32_t>(), ctx->stream);
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    HIPCHK(ctx, hipMemcpyAsync(seg_out, b.seg.p, sizeof(int32_t) * 6 * (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // h_offs leaves with this frame
+    return EAGLE_OK;
+}
+
+}  // namespace
+
+// The flags pass over a resident image is one launch.  A file that is not resident is read in row windows of the streamed size, each a
+// CORE of markers held with w - 1 rows of overlap on both sides (ld_panel_cores' scheme): the launch writes the plane rows of the core
+// alone, from rows that hold every window of its markers, so every plane word is written once.
+extern "C" int eagle_roh(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long dims[2], const int32_t* chrom, const int64_t* pos,
+                         const eagle_roh_params* params, double max_memory_in_Gbytes, int64_t* ind_out, int32_t* seg_out, long seg_cap,
+                         long* nseg_out) {
+    if (!f_name_ascii_Mt || !dims || !params || !ind_out || !nseg_out) return qc_fail(ctx, EAGLE_ERR_ARG, "roh: NULL argument");
+    const long n = dims[0], L = dims[1];
+    if (n <= 0 || L <= 0) return qc_fail(ctx, EAGLE_ERR_ARG, "roh: dims must be positive");
+    RohBufs b;
+    if (int rc = roh_check(ctx, "roh", L, chrom, pos, params, seg_out, seg_cap, b.h_blk)) return rc;
+    if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "roh: no context");
+    int rc = roh_begin(ctx, "roh", b, n, L, pos);
+    if (rc) return rc;
+    const int threads = host_threads();
+    const GenoEntry* src = nullptr;
+    rc = eagle_get_resident(ctx, f_name_ascii_Mt, L, n, max_memory_in_Gbytes, threads, &src);
+    if (rc != EAGLE_OK && rc != EAGLE_STREAM) return rc;
+    if (rc == EAGLE_OK) {
+        rc = eagle_dev_roh_flags_i8(ctx, src->dev, src->ld, n, 0, 0, L, b.blk.as<int32_t>(), b.nb(), params, b.planes.as<uint64_t>(), L, ctx->stream);
+        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    } else {
+        const long ld = eagle_pad(n), h = params->w - 1;
+        const long held_max = std::min(L, std::max(256L, stream_chunk_rows_core(eagle_resident_budget(), ld, eagle_pad(L))));
+        const long core = held_max >= L ? L : held_max - 2 * h;
+        DevBuf win;
+        HIPCHK(ctx, win.alloc((size_t)held_max * ld));
+        for (long c0 = 0; c0 < L; c0 += core) {
+            const long c1 = std::min(L, c0 + core), lo = std::max(0L, c0 - h), hi = std::min(L, c1 + h), nr = hi - lo;
+            HIPCHK(ctx, hipMemsetAsync(win.p, 0, (size_t)held_max * ld, ctx->stream));
+            rc = eagle_dev_load_ascii(ctx, f_name_ascii_Mt, lo, nr, 0, n, win.as<int8_t>(), ld, max_memory_in_Gbytes, threads);
+            if (!rc) rc = eagle_dev_roh_flags_i8(ctx, win.as<int8_t>(), ld, n, lo, c0, c1, b.blk.as<int32_t>(), b.nb(), params,
+                                                 b.planes.as<uint64_t>(), L, ctx->stream);
+            if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+        }
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // the window leaves with this scope
+    }
+    return roh_end(ctx, b, params, ind_out, seg_out, seg_cap, nseg_out);
+}
+
+// The .bed rows go through the pinned ring in eagle_bed_ld_partners' windows of panel markers, with w - 1 markers in the place of its
+// `window`: the window held for the core [c0, c1) is [lo, hi) = [max(0, c0 - (w - 1)), min(Linc, c1 + w - 1)).
+extern "C" int eagle_bed_roh(eagle_ctx* ctx, const char* bed_path, const long dims[2], const uint8_t* include, const int32_t* chrom,
+                             const int64_t* pos, const eagle_roh_params* params, double max_memory_in_Gbytes, int64_t* ind_out, int32_t* seg_out,
+                             long seg_cap, long* nseg_out) {
+    if (!bed_path || !dims || !params || !ind_out || !nseg_out) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_roh: NULL argument");
+    const long n = dims[0], L = dims[1];
+    if (n <= 0 || L <= 0) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_roh: dims must be positive");
+    if (n > 0x3fffffffL) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_roh: 2^30 individuals or more");
+    const long linc = bedld_count(include, L);
+    if (linc < 1) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_roh: include selects no marker");
+    RohBufs b;
+    if (int rc = roh_check(ctx, "bed_roh", linc, chrom, pos, params, seg_out, seg_cap, b.h_blk)) return rc;
+    if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_roh: no context");
+    int rc = roh_begin(ctx, "bed_roh", b, n, linc, pos);
+    if (rc) return rc;
+    BedLdPanel pl;
+    pl.pack = false;
+    const long h = params->w - 1, need = 2 * h + 1;
+    auto next_of = [&](long hi) { return hi >= linc ? linc : hi - 2 * h; };
+    rc = bedld_open(pl, ctx, bed_path, n, L, include, linc, max_memory_in_Gbytes, 0, need, next_of);
+    if (rc) return rc;
+    for (long lo = 0; lo < linc;) {
+        const long hi = pl.window_end(lo, need);
+        const long c0 = lo == 0 ? 0 : lo + h, c1 = hi >= linc ? linc : hi - h;
+        rc = pl.stage(lo, hi);
+        if (!rc) rc = eagle_dev_roh_flags_bed(ctx, pl.raw, pl.raw_off, n, lo, c0, c1, b.blk.as<int32_t>(), b.nb(), params, b.planes.as<uint64_t>(),
+                                              linc, ctx->stream);
+        if (!rc) rc = pl.release();
+        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+        lo = next_of(hi);
+    }
+    return roh_end(ctx, b, params, ind_out, seg_out, seg_cap, nseg_out);
 }
 
 // The loci's rows are gathered into a 64-row image first (k_gather_rows_i8: from the resident image, else from their own lines of

@@ -1148,6 +1148,155 @@ def LDDecay(geno, window=256, map=None, bins=None, kb=None, bed=None, include=No
     return {"edges": edges, "pairs": pairs, "mean_r2": mean, "half_decay": ld_half_decay(edges, pairs, mean), "sum": bsum}
 
 
+# ---- runs of homozygosity (include/eagle_hip.h section 1b'''vi): the restatement in numpy and the interface ----
+def roh_classes_mt8(Mt8):
+    """The classes of rule 1 from the int8 marker-major image (L, n), values -1 / 0 / +1 -> uint8 (L, n): 0 hom, 1 het (never 2)."""
+    return (np.asarray(Mt8) == 0).astype(np.uint8)
+
+
+def roh_classes_bed(codes):
+    """The classes of rule 1 from the 2-bit codes of a .bed file (read_bed_codes: 0 hom A1, 1 missing, 2 het, 3 hom A2) -> uint8:
+    0 hom, 1 het, 2 miss."""
+    return np.array([0, 2, 1, 0], dtype=np.uint8)[np.asarray(codes, dtype=np.uint8)]
+
+
+def roh_host(classes, chrom=None, pos=None, **params):
+    """rcpp_api.roh / bed_roh restated in numpy: classes = uint8 (L, n) with 0 hom, 1 het, 2 miss (roh_classes_mt8, roh_classes_bed) ->
+    (ind int64 (n, 4), seg int32 (S, 6)), rules 2 to 7 of include/eagle_hip.h section 1b'''vi with the parameters of rcpp_api.roh_params.
+    Window counts are differences of cumulative sums along every block; runs are read off the flags' edges.  Integers throughout."""
+    cl = np.asarray(classes)
+    if cl.ndim != 2 or cl.shape[0] < 1 or cl.shape[1] < 1 or cl.min() < 0 or cl.max() > 2:
+        raise ValueError("roh_host: classes must be (L, n) with values 0, 1, 2")
+    L, n = cl.shape
+    p = rcpp_api.roh_params("roh_host", **params)
+    ch = None if chrom is None else np.asarray(chrom).ravel()
+    ps = np.arange(L, dtype=np.int64) if pos is None else np.asarray(pos).ravel().astype(np.int64)
+    if (ch is not None and ch.size != L) or ps.size != L:
+        raise ValueError("roh_host: chrom and pos hold one entry per marker (%d)" % L)
+    blk = rcpp_api.roh_blocks(ch, L)
+    nb = blk.size - 1
+    down = np.diff(ps) < 0
+    down[blk[1:-1] - 1] = False
+    if down.any():
+        raise ValueError("roh_host: pos decreases inside a block (panel marker %d)" % (int(np.flatnonzero(down)[0]) + 1))
+    w = p["w"]
+    het, miss = cl == 1, cl == 2
+    flagged = np.zeros((L, n), dtype=bool)
+    for a, e in zip(blk[:-1], blk[1:]):
+        lb = int(e - a)
+        if lb < w:
+            continue
+        zero = np.zeros((1, n), dtype=np.int64)
+        chet = np.concatenate((zero, np.cumsum(het[a:e], axis=0, dtype=np.int64)))
+        cmis = np.concatenate((zero, np.cumsum(miss[a:e], axis=0, dtype=np.int64)))
+        homw = ((chet[w:] - chet[:-w]) <= p["win_het"]) & ((cmis[w:] - cmis[:-w]) <= p["win_miss"])      # by window start, lb - w + 1 rows
+        cw = np.concatenate((zero, np.cumsum(homw, axis=0, dtype=np.int64)))
+        j = np.arange(lb)
+        s_lo, s_hi = np.maximum(0, j - w + 1), np.minimum(j, lb - w)
+        cover = s_hi - s_lo + 1
+        hom = cw[s_hi + 1] - cw[s_lo]
+        flagged[a:e] = (hom >= 1) & (hom * 65536 >= p["thr16"] * cover[:, None])
+    brk = np.zeros(L + 1, dtype=bool)                      # brk[m]: a run cannot continue from marker m - 1 to m
+    brk[blk] = True
+    if p["max_gap"] > 0 and L > 1:
+        brk[1:L] |= np.diff(ps) > p["max_gap"]
+    prev = np.concatenate((np.zeros((1, n), dtype=bool), flagged[:-1]))
+    nxt = np.concatenate((flagged[1:], np.zeros((1, n), dtype=bool)))
+    first = flagged & (brk[:L, None] | ~prev)
+    last = flagged & (brk[1:, None] | ~nxt)
+    ii, s = np.nonzero(first.T)                             # sorted by (individual, s); the k-th start pairs with the k-th end
+    _, e = np.nonzero(last.T)
+    zero = np.zeros((1, n), dtype=np.int64)
+    chet = np.concatenate((zero, np.cumsum(het, axis=0, dtype=np.int64)))
+    cmis = np.concatenate((zero, np.cumsum(miss, axis=0, dtype=np.int64)))
+    nsnp, length = e - s + 1, ps[e] - ps[s]
+    nhet, nmiss = chet[e + 1, ii] - chet[s, ii], cmis[e + 1, ii] - cmis[s, ii]
+    ok = (nsnp >= p["min_snp"]) & (length >= p["min_len"])
+    if p["max_density"] > 0:
+        ok &= length <= p["max_density"] * nsnp
+    if p["max_het"] >= 0:
+        ok &= nhet <= p["max_het"]
+    ii, s, e, nsnp, length, nhet, nmiss = (x[ok] for x in (ii, s, e, nsnp, length, nhet, nmiss))
+    seg = np.stack([ii, s, e, nhet, nmiss, np.searchsorted(blk, s, side="right") - 1], axis=1).astype(np.int32).reshape(-1, 6)
+    ind = np.zeros((n, 4), dtype=np.int64)
+    np.add.at(ind[:, 0], ii, 1)
+    np.add.at(ind[:, 1], ii, nsnp)
+    np.add.at(ind[:, 2], ii, length)
+    np.maximum.at(ind[:, 3], ii, length)
+    return ind, seg
+
+
+def roh_incidence(seg, L):
+    """The ROH incidence of every marker -> int64 (L): the number of individuals with the marker inside one of their segments (rows of
+    rcpp_api.roh's table; an individual's segments do not overlap), by a difference array.  Peaks are the "ROH islands"."""
+    seg = np.asarray(seg, dtype=np.int64).reshape(-1, 6)
+    L = int(L)
+    if seg.size and (seg[:, 1].min() < 0 or seg[:, 2].max() >= L or np.any(seg[:, 2] < seg[:, 1])):
+        raise ValueError("roh_incidence: a segment outside [0, %d)" % L)
+    d = np.zeros(L + 1, dtype=np.int64)
+    np.add.at(d, seg[:, 1], 1)
+    np.add.at(d, seg[:, 2] + 1, -1)
+    return np.cumsum(d[:L])
+
+
+def roh_thr16(threshold):
+    """thr16 of rule 4 from a fraction in [0, 1]: (int)(threshold * 65536 + 0.5)."""
+    t = float(threshold)
+    if not 0.0 <= t <= 1.0:
+        raise ValueError("ROH: threshold must be in [0, 1]")
+    return int(t * 65536.0 + 0.5)
+
+
+def ROH(geno, map=None, bed=None, include=None, window=50, window_het=1, window_missing=5, threshold=0.05, min_snp=100, min_kb=1000,
+        max_density_kb=50, max_gap_kb=1000, max_het=None, availmemGb=8, device=0):
+    """Runs of homozygosity of every individual of a panel (include/eagle_hip.h section 1b'''vi; rcpp_api.roh) -> {"segments": the table
+    as a dict of arrays (individual, first, last, nsnp, nhet, nmiss, block, pos_first, pos_last, length), "nseg", "total_length",
+    "longest": int64 (n), "F_ROH": fp64 (n) = total_length / the sum over the blocks of pos[last] - pos[first] (NaN when that is 0),
+    "incidence": int64 (L), roh_incidence's count per marker, "ind", "seg": the integer outputs as returned}.  The rule follows PLINK
+    --homozyg as documented -- windows of `window` <= 64 markers with at most window_het heterozygous and window_missing missing calls, a
+    marker flagged when at least `threshold` of the windows over it are homozygous, then the segment filters -- and its parameter names;
+    agreement with the PLINK program is not claimed.  map (ReadBim's dict, as LDPrune takes it): chromosomes are blocks, lengths are base
+    pairs and min_kb, max_density_kb (at most one marker per that many kb), max_gap_kb are converted to base pairs (None: filter off).
+    Without a map the position is the marker index and the three kb arguments must be passed as None.  bed = the .bed file (or prefix)
+    the panel was ingested from: its missing calls count against window_missing instead of being heterozygotes (rcpp_api.bed_roh);
+    include = the panel's markers in the file, default geno's marker_index."""
+    src = _ld_stats_source("ROH", geno, map, bed, include)
+    n, L, chrom, pos, src_bed, bdims, inc = src
+    kb = {"min_kb": min_kb, "max_density_kb": max_density_kb, "max_gap_kb": max_gap_kb}
+    if pos is None:
+        given = [k for k, v in kb.items() if v is not None]
+        if given:
+            raise ValueError("ROH: %s needs a map with Chr and Pos entries; without one pass min_kb, max_density_kb and max_gap_kb as None"
+                             % ", ".join(given))
+    bp = {}
+    for k, v in kb.items():
+        bp[k] = 0 if v is None else int(round(float(v) * 1000.0))
+        if v is not None and bp[k] < 1:
+            raise ValueError("ROH: %s must be at least 0.001" % k)
+    prm = dict(w=int(window), win_het=int(window_het), win_miss=int(window_missing), thr16=roh_thr16(threshold), min_snp=int(min_snp),
+               min_len=bp["min_kb"], max_gap=bp["max_gap_kb"], max_density=bp["max_density_kb"], max_het=-1 if max_het is None else int(max_het))
+    if src_bed is None:
+        ind, seg = rcpp_api.roh(geno["asciifileMt"], (n, L), chrom, pos, availmemGb, device=device, **prm)
+    else:
+        ind, seg = rcpp_api.bed_roh(src_bed, bdims, inc, chrom, pos, availmemGb, device=device, **prm)
+    return roh_summary(ind, seg, L, chrom, pos)
+
+
+def roh_summary(ind, seg, L, chrom=None, pos=None):
+    """ROH's result from the integer outputs (host arithmetic; F_ROH is the one fp64 division)."""
+    ps = np.arange(L, dtype=np.int64) if pos is None else np.asarray(pos, dtype=np.int64)
+    blk = rcpp_api.roh_blocks(chrom, L)
+    genome = int(np.sum(ps[blk[1:] - 1] - ps[blk[:-1]]))
+    s, e = seg[:, 1].astype(np.int64), seg[:, 2].astype(np.int64)
+    table = {"individual": seg[:, 0].copy(), "first": seg[:, 1].copy(), "last": seg[:, 2].copy(), "nsnp": (e - s + 1).astype(np.int32),
+             "nhet": seg[:, 3].copy(), "nmiss": seg[:, 4].copy(), "block": seg[:, 5].copy(), "pos_first": ps[s], "pos_last": ps[e],
+             "length": ps[e] - ps[s]}
+    with np.errstate(divide="ignore", invalid="ignore"):
+        f = ind[:, 2].astype(np.float64) / np.float64(genome) if genome > 0 else np.full(ind.shape[0], np.nan)
+    return {"segments": table, "nseg": ind[:, 0].copy(), "total_length": ind[:, 2].copy(), "longest": ind[:, 3].copy(), "F_ROH": f,
+            "incidence": roh_incidence(seg, L), "ind": ind, "seg": seg}
+
+
 # ---- GRM and PCA (include/eagle_hip.h section 1b''''): the exact weighted Gram product on the device, fp64 arithmetic on the host ----
 GRM_QMAX = 2097151    # 2^21 - 1: the largest weight rcpp_api.weighted_gram takes
 

@@ -915,6 +915,110 @@ def bed_ld_stats(bed_path, dims, window=50, include=None, min_overlap=1, chrom=N
     return (U, cnt, bsum, bpairs) if nb else (U, cnt)
 
 
+# ---- runs of homozygosity (include/eagle_hip.h section 1b'''vi): the window scan and the segment table as exact integers ----
+ROH_MAX_WINDOW = 64
+ROH_MAX_DENSITY = 1 << 31
+ROH_DEFAULTS = dict(w=50, win_het=1, win_miss=5, thr16=3277, min_snp=100, min_len=0, max_gap=0, max_density=0, max_het=-1)
+_ROH_FIELDS = ("w", "win_het", "win_miss", "thr16", "min_snp", "min_len", "max_gap", "max_density", "max_het")
+
+
+def roh_params(who="roh", **params):
+    """The nine integers of eagle_roh_params as a dict, defaults ROH_DEFAULTS; ValueError for an unknown name, a value that is not a whole
+    number, or one outside the header's rule: w in [1, 64], thr16 in [0, 65536], min_snp >= 1, max_density in [0, 2^31], win_het,
+    win_miss, min_len and max_gap >= 0 (max_het: any negative number switches the filter off)."""
+    p = dict(ROH_DEFAULTS)
+    for k, v in params.items():
+        if k not in p:
+            raise ValueError("%s: unknown parameter %s" % (who, k))
+        try:
+            iv = int(v)
+        except (TypeError, ValueError):
+            raise ValueError("%s: %s must be a whole number" % (who, k))
+        if iv != v or not -(1 << 63) <= iv < 1 << 63:
+            raise ValueError("%s: %s must be a whole number that fits int64" % (who, k))
+        p[k] = iv
+    if not 1 <= p["w"] <= ROH_MAX_WINDOW:
+        raise ValueError("%s: w must be in [1, %d]" % (who, ROH_MAX_WINDOW))
+    if not 0 <= p["thr16"] <= 65536:
+        raise ValueError("%s: thr16 must be in [0, 65536]" % who)
+    if p["min_snp"] < 1:
+        raise ValueError("%s: min_snp must be at least 1" % who)
+    if not 0 <= p["max_density"] <= ROH_MAX_DENSITY:
+        raise ValueError("%s: max_density must be in [0, 2^31]" % who)
+    for k in ("win_het", "win_miss", "min_len", "max_gap"):
+        if p[k] < 0:
+            raise ValueError("%s: %s must not be negative" % (who, k))
+    return p
+
+
+def roh_blocks(chrom, nm):
+    """The block bounds of rule 2 -> int64 (nb + 1): 0 = blk[0] < ... < blk[nb] = nm, a block a maximal run of equal chrom."""
+    if chrom is None or nm < 2:
+        return np.array([0, nm], dtype=np.int64)
+    c = np.asarray(chrom).ravel()
+    return np.concatenate(([0], np.flatnonzero(c[1:] != c[:-1]) + 1, [nm])).astype(np.int64)
+
+
+def _roh_args(who, nm, chrom, pos, params):
+    ch, ps, _ = _ld_stats_args(who, nm, chrom, pos, 0, None)
+    p = roh_params(who, **params)
+    if nm >= 1 << 31:
+        raise ValueError("%s: 2^31 markers or more" % who)
+    if ps is not None:
+        blk = roh_blocks(ch, nm)
+        d = np.diff(ps) < 0
+        d[blk[1:-1] - 1] = False                         # block edges are not compared across
+        if d.any():
+            raise ValueError("%s: pos decreases inside a block (panel marker %d)" % (who, int(np.flatnonzero(d)[0]) + 1))
+    return ch, ps, _lib.RohParams(*[p[f] for f in _ROH_FIELDS])
+
+
+def _roh_call(fn, device, head, ch, ps, prm, mem, n, seg_cap):
+    ind = np.zeros((n, 4), dtype=np.int64)
+    while True:
+        seg = np.zeros((seg_cap, 6), dtype=np.int32)
+        total = C.c_long(0)
+        _args_first(fn, device, head + (ch.ctypes.data_as(_c_i32p) if ch is not None else None,
+                                        ps.ctypes.data_as(_c_i64p) if ps is not None else None, C.addressof(prm), float(mem),
+                                        ind.ctypes.data_as(_c_i64p), seg.ctypes.data_as(_c_i32p) if seg_cap else None, seg_cap, C.byref(total)))
+        if total.value <= seg_cap:
+            return ind, seg[:total.value].copy()
+        seg_cap = int(total.value)
+
+
+def roh(f_name_ascii_Mt, dims, chrom=None, pos=None, max_memory_in_Gbytes=8.0, device=0, seg_cap=None, **params):
+    """eagle_roh -> (ind int64 (n, 4), seg int32 (S, 6)): the runs of homozygosity of include/eagle_hip.h section 1b'''vi on the ingested
+    panel (dims = (n, L) of M).  ind = (segments, sum of nsnp, sum of len, longest len) per individual; seg rows = (individual, first
+    marker, last marker, nhet, nmiss, block ordinal), sorted by (individual, first marker).  chrom, pos: one whole number per marker or
+    None (one block; pos = the marker index).  params: w, win_het, win_miss, thr16, min_snp, min_len, max_gap, max_density, max_het
+    (ROH_DEFAULTS).  The library is called once with a capacity guess (seg_cap, default 4 n) and once more if that was short.  ValueError
+    for bad arguments before the library is called.  r_api.roh_host(r_api.roh_classes_mt8(Mt8), ...) is the numpy restatement."""
+    L = _lib.load()
+    n, nm = max(int(dims[0]), 0), max(int(dims[1]), 0)
+    ch, ps, prm = _roh_args("roh", nm, chrom, pos, params)
+    cap = 4 * n if seg_cap is None else int(seg_cap)
+    if cap < 0:
+        raise ValueError("roh: seg_cap must not be negative")
+    return _roh_call(L.eagle_roh, device, (os.fsencode(f_name_ascii_Mt), _dims(dims)), ch, ps, prm, max_memory_in_Gbytes, n, cap)
+
+
+def bed_roh(bed_path, dims, include=None, chrom=None, pos=None, availmemGb=8.0, device=0, seg_cap=None, **params):
+    """eagle_bed_roh -> roh's pair by PANEL marker from a SNP-major PLINK .bed file of dims = (n individuals, L markers), which still
+    knows its missing calls (code 01 is the class miss, counted against win_miss and in nmiss).  include as in bed_ld_window; chrom and
+    pos: one whole number per panel marker.  r_api.roh_host(r_api.roh_classes_bed(read_bed_codes(...)[include]), ...) is the numpy
+    restatement."""
+    L = _lib.load()
+    n, nm = max(int(dims[0]), 0), max(int(dims[1]), 0)
+    inc = _bed_ld_include(include, nm, "bed_roh")
+    linc = nm if inc is None else int(inc.sum())
+    ch, ps, prm = _roh_args("bed_roh", linc, chrom, pos, params)
+    cap = 4 * n if seg_cap is None else int(seg_cap)
+    if cap < 0:
+        raise ValueError("bed_roh: seg_cap must not be negative")
+    head = (os.fsencode(bed_path), _dims(dims), inc.ctypes.data_as(C.c_void_p) if inc is not None else None)
+    return _roh_call(L.eagle_bed_roh, device, head, ch, ps, prm, availmemGb, n, cap)
+
+
 # ---- GRM (include/eagle_hip.h section 1b''''): the exact weighted Gram product; weights, centring and PCA are r_api's ----
 WGRAM_MAX_WEIGHT = (1 << 21) - 1
 

@@ -654,6 +654,64 @@ int eagle_bed_ld_stats(eagle_ctx* ctx, const char* bed_path, const long dims[2],
                        uint64_t* U_out, int32_t* cnt_out, uint64_t* bin_sum_out, int64_t* bin_pairs_out);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1b'''vi. Runs of homozygosity (no counterpart in the reference): where the autozygous segments of every individual lie, the numbers
+ *     F_ROH and the per-marker ROH incidence are made of.  The rule follows PLINK --homozyg AS DOCUMENTED -- a window scan, a per-SNP
+ *     threshold, then segment filters.  Agreement with the PLINK program itself is neither claimed nor tested.  Everything is integers,
+ *     so the device and numpy (r_api.roh_host) agree with ==.
+ *
+ *     1. Class of individual i at panel marker m.  hom: image value +-1, .bed codes 00 and 11.  het: image value 0, .bed code 10.
+ *        miss: .bed code 01 only -- on the ingested image a missing call of the original data is a het, as for the counts of 1b'.
+ *     2. Blocks.  A block [a, e) is a maximal run of panel markers with equal chrom[m] (int32 by panel marker; NULL: one block).  pos is
+ *        int64 by panel marker (NULL: pos[m] = m) and must be non-decreasing inside every block, else EAGLE_ERR_ARG.
+ *     3. Window.  1 <= w <= 64.  The window that starts at s is VALID iff a <= s and s + w <= e for the block of s, and HOMOZYGOUS iff
+ *        its het count is <= win_het and its miss count is <= win_miss.
+ *     4. Marker flag.  cover = the number of valid windows that contain m, hom = the number of those that are homozygous; m is FLAGGED
+ *        iff hom >= 1 and hom * 65536 >= thr16 * cover, 0 <= thr16 <= 65536.  A block shorter than w has no flagged marker.
+ *     5. Run.  A maximal sequence s .. e of consecutive flagged markers of one block; with max_gap > 0 it is also broken between m and
+ *        m + 1 where pos[m + 1] - pos[m] > max_gap.
+ *     6. Reported segment.  A run with  nsnp = e - s + 1 >= min_snp,  len = pos[e] - pos[s] >= min_len,  max_density == 0 or
+ *        len <= max_density * nsnp (max_density <= 2^31: the product stays in int64),  max_het < 0 or nhet <= max_het.  nhet and nmiss
+ *        are the individual's het and miss markers in s .. e.
+ *     7. Outputs.  ind_out: n x 4 int64 = (number of segments, sum of nsnp, sum of len, longest len) per individual.  seg_out: rows of
+ *        six int32 (individual, s, e, nhet, nmiss, block ordinal), sorted by (individual, s); s and e are panel marker indices.
+ *        *nseg_out is always the total.  seg_out has room for seg_cap rows (it may be NULL when seg_cap is 0); it is written iff the
+ *        total is <= seg_cap and untouched otherwise.  The call returns EAGLE_OK either way.
+ *     8. Limits.  Panel markers < 2^31; n <= 0x3fffffff for the .bed file.  The three bit planes below (3 x markers x ceil(n / 64) x 8
+ *        bytes) stay on the device for the whole call: where they do not fit the memory budget (EAGLE_HIP_MAX_RESIDENT_GB when it is set,
+ *        else the free HBM less 1 GiB) the call returns EAGLE_ERR_NOMEM, decided before any kernel runs.
+ *
+ *     k_roh_flags walks chunks of EAGLE_ROH_CHUNK markers with a halo of w - 1 rows on either side, one lane per four individuals,
+ *     three 64-bit shift registers per individual, every row of a chunk read once, and writes three marker-major bit planes (flagged,
+ *     het, miss).  k_roh_segments walks the planes, one lane per individual and one wave per 64 individuals x block: a count pass, an
+ *     exclusive scan of the counts by (individual, block) on the host, and a fill pass that is skipped when the total exceeds seg_cap.
+ *     The ingested panel is read as eagle_marker_counts reads it (the resident image, else row windows of the streamed size from the
+ *     sidecar, the text or a VIEW alias's source; a VIEW alias gives the kept individuals), the .bed file through the pinned ring as
+ *     eagle_bed_marker_counts reads it, with the panel selection of 1b'''iv.  Windows are cores of markers held with w - 1 markers of
+ *     overlap on both sides: every plane word is written once and the result does not depend on the window size.
+ *
+ *     Single device: a multi-device context works on its first device.  Argument errors (EAGLE_ERR_ARG: a NULL pointer, dims <= 0,
+ *     and those named below) are decided before the context is used; with ctx == NULL their text is in eagle_open_error().
+ * ------------------------------------------------------------------------------------------- */
+#define EAGLE_ROH_CHUNK 1024L
+#define EAGLE_ROH_MAX_WINDOW 64L
+
+typedef struct eagle_roh_params {
+    int64_t w, win_het, win_miss, thr16, min_snp, min_len, max_gap, max_density, max_het;
+} eagle_roh_params;
+
+/* Rules 1 to 7 on the ingested panel Mt.ascii (dims = (n, L) of M); chrom (L int32) and pos (L int64) may be NULL.
+ * EAGLE_ERR_ARG: w outside [1, 64], win_het / win_miss / min_len / max_gap < 0, thr16 outside [0, 65536], min_snp < 1, max_density
+ * outside [0, 2^31], L >= 2^31, seg_cap < 0, seg_out NULL with seg_cap > 0, pos decreasing inside a block. */
+int eagle_roh(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long dims[2], const int32_t* chrom, const int64_t* pos,
+              const eagle_roh_params* params, double max_memory_in_Gbytes, int64_t* ind_out, int32_t* seg_out, long seg_cap, long* nseg_out);
+
+/* The same by PANEL marker (the Linc markers include selects, L bytes or NULL; chrom and pos by panel marker) from the SNP-major .bed
+ * file bed_path (dims = (n, L) of the file), which still knows its missing calls.
+ * EAGLE_ERR_ARG: those of eagle_roh with Linc in the place of L, and n > 0x3fffffff, an include that selects no marker. */
+int eagle_bed_roh(eagle_ctx* ctx, const char* bed_path, const long dims[2], const uint8_t* include, const int32_t* chrom, const int64_t* pos,
+                  const eagle_roh_params* params, double max_memory_in_Gbytes, int64_t* ind_out, int32_t* seg_out, long seg_cap, long* nseg_out);
+
+/* ---------------------------------------------------------------------------------------------
  * 1b''''. Genomic relationship matrix (no counterpart that the reference calls: its VanRaden G, E/R/GenomicRel.R, is unused): the one
  *     Gram product the matrices of EIGENSTRAT / PLINK / GCTA and their principal components need, with a weight per marker.  With
  *     g in {-1, 0, +1} = AA, AB, BB as everywhere in this library and integer weights q_m < 2^21,
