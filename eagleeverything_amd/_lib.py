@@ -23,6 +23,11 @@ class RohParams(C.Structure):
     _fields_ = [(f, C.c_int64) for f in ("w", "win_het", "win_miss", "thr16", "min_snp", "min_len", "max_gap", "max_density", "max_het")]
 
 
+class IbdParams(C.Structure):
+    """eagle_ibd_params of include/eagle_hip.h section 1b'''vii."""
+    _fields_ = [(f, C.c_int64) for f in ("mode", "min_snp", "min_len", "max_gap", "merge_min")]
+
+
 # name -> (restype, argtypes); must list every symbol include/eagle_hip.h declares
 SIGNATURES = {
     "eagle_open": (C.c_void_p, [C.c_int]),
@@ -85,6 +90,10 @@ SIGNATURES = {
                             C.POINTER(C.c_int32), C.c_long, c_lp]),
     "eagle_bed_roh": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_void_p, C.c_double,
                                 C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_long, c_lp]),
+    "eagle_ibd": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, C.POINTER(C.c_int32), C.c_long, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_void_p,
+                            C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_long, c_lp]),
+    "eagle_bed_ibd": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, C.c_void_p, C.POINTER(C.c_int32), C.c_long, C.POINTER(C.c_int32),
+                                C.POINTER(C.c_int64), C.c_void_p, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_long, c_lp]),
     "eagle_weighted_gram": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, C.POINTER(C.c_uint32), C.c_double, C.POINTER(C.c_int64)]),
     "eagle_sample_scores": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, C.POINTER(C.c_int32), C.c_long, C.c_double, C.POINTER(C.c_int64)]),
     "eagle_marker_scores": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, C.POINTER(C.c_int32), C.c_long, C.c_double, C.POINTER(C.c_int64)]),

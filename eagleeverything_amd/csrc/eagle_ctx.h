@@ -247,6 +247,19 @@ extern "C" int eagle_dev_roh_flags_bed(eagle_ctx* ctx, const uint8_t* bed, const
 extern "C" int eagle_dev_roh_segments(eagle_ctx* ctx, const uint64_t* planes, long markers, long n, const int32_t* blk, long nb, const int64_t* pos,
                                       const eagle_roh_params* prm, int fill, int32_t* cnt, int64_t* ind, const int64_t* offs, int32_t* seg,
                                       void* stream);
+// Pairwise IBD-type segments (eagle_ibd.hip; include/eagle_hip.h section 1b'''vii), device pointers throughout.  planes: A (hom A1), B (hom
+// A2) and from the .bed file C (called), each ceil(markers / 64) x np uint64 with np = n rounded up to 64, WORD-MAJOR: word w of individual i
+// at w * np + i.  The planes calls write the words of the individuals [r0, r0 + nr) from an individual-major int8 image whose row 0 is
+// individual r0, or the words [w0, w1) of everybody from raw .bed rows (the row of panel marker g0 + p at offsets[p], null: row p; checked
+// by the CALLER).  The walk is the count pass (fill == 0: tot P x 4 written) or the fill pass (rows of seg from the exclusive scan offs of
+// the counts); pairs null = all pairs, P = n (n - 1) / 2; cut = the cut plane of rule 3 (ibd_cut_plane).
+extern "C" int eagle_dev_ibd_planes_i8(eagle_ctx* ctx, const int8_t* img, long ld, long r0, long nr, long n, long L, uint64_t* planes,
+                                       void* stream);
+extern "C" int eagle_dev_ibd_planes_bed(eagle_ctx* ctx, const uint8_t* bed, const long* offsets, long n, long g0, long w0, long w1, long L,
+                                        uint64_t* planes, void* stream);
+extern "C" int eagle_dev_ibd_walk(eagle_ctx* ctx, const uint64_t* planes, int nplanes, const uint64_t* cut, long n, long L, const int32_t* pairs,
+                                  long P, const int32_t* blk, long nb, const int64_t* pos, const eagle_ibd_params* prm, int fill, int64_t* tot,
+                                  const int64_t* offs, int32_t* seg, void* stream);
 // Pairwise-complete IBS counts from a .bed file (eagle_bedibs.hip; include/eagle_hip.h section 1b'''ii), device pointers throughout.  The
 // four fp4 operand images (g, u, h, c; plane p at M4 + p * plane_bytes, n_pad rows of ld4 bytes, L_pad markers written) of `rows` raw
 // .bed rows, `include` one byte per row or null; the four n x n int32 results and dist (or null) from the four Gram accumulators

@@ -390,4 +390,58 @@ static inline int64_t roh_offsets(const int32_t* cnt, size_t cells, int64_t* off
     for (size_t c = 0; c < cells; c++) { offs[c] = t; t += cnt[c]; }
     return t;
 }
+
+// ------------------------------------------------------------------------------------------------
+// Pairwise IBD-type segments (include/eagle_hip.h section 1b'''vii): the argument rule of eagle_ibd / eagle_bed_ibd, the check of a pair
+// list and the scan of the per-pair counts.  Blocks and pos are those of ROH (roh_block_table, roh_pos_check).
+// ------------------------------------------------------------------------------------------------
+#define IBD_MAX_PAIRS 134217728L   /* 2^27 */
+// The five fields of eagle_ibd_params in their order: mode, min_snp, min_len, max_gap, merge_min.  npairs counts the list, or is ignored
+// when has_pairs is false (all pairs of n individuals).  What is wrong with a call over `markers` panel markers, or NULL.
+static inline const char* ibd_arg_error(const int64_t p[5], long n, long markers, bool has_pairs, long npairs, long seg_cap, bool has_seg_out) {
+    if (p[0] != 1 && p[0] != 2) return "mode must be 1 (ibs1) or 2 (ibs2)";
+    if (p[1] < 1) return "min_snp must be at least 1";
+    if (p[2] < 0) return "min_len must not be negative";
+    if (p[3] < 0) return "max_gap must not be negative";
+    if (p[4] < 0) return "merge_min must not be negative";
+    if (markers > 0x7fffffffL) return "2^31 markers or more";
+    if (has_pairs) {
+        if (npairs < 1 || npairs > IBD_MAX_PAIRS) return "the number of pairs must be in [1, 2^27]";
+    } else {
+        if (n < 2) return "all pairs need at least two individuals";
+        if (n > 16385L) return "more than 2^27 pairs: give a list";   /* 16385 * 16384 / 2 == 2^27 + 8192 > 2^27 >= 16384 * 16383 / 2 */
+        if (n * (n - 1) / 2 > IBD_MAX_PAIRS) return "more than 2^27 pairs: give a list";
+    }
+    if (seg_cap < 0) return "seg_cap must not be negative";
+    if (seg_cap > 0 && !has_seg_out) return "NULL argument (seg_out, with seg_cap > 0)";
+    return nullptr;
+}
+// The number of pairs of a call: the list's, or n (n - 1) / 2.
+static inline long ibd_pair_count(long n, bool has_pairs, long npairs) { return has_pairs ? npairs : n * (n - 1) / 2; }
+// The ordinal of (i, j), 0 <= i < j < n, among all pairs in row-major upper-triangle order.
+static inline long ibd_pair_ordinal(long n, long i, long j) { return i * n - i * (i + 1) / 2 + (j - i - 1); }
+// The first list entry that is not 0 <= i < j < n, or -1.
+static inline long ibd_pairs_check(const int32_t* pairs, long npairs, long n) {
+    for (long k = 0; k < npairs; k++) {
+        const long i = pairs[2 * k], j = pairs[2 * k + 1];
+        if (i < 0 || i >= j || j >= n) return k;
+    }
+    return -1;
+}
+// Exclusive scan of the segment counts (column 0 of the P x 4 pair table) by pair ordinal; returns the total.
+static inline int64_t ibd_offsets(const int64_t* pair_tab, size_t P, int64_t* offs) {
+    int64_t t = 0;
+    for (size_t k = 0; k < P; k++) { offs[k] = t; t += pair_tab[4 * k]; }
+    return t;
+}
+// The cut plane of rule 3 (the device builds the same in k_ibd_cuts): bit m set where a piece starts.
+static inline void ibd_cut_plane(const int32_t* chrom, const int64_t* pos, long max_gap, long markers, std::vector<uint64_t>& cut) {
+    cut.assign((size_t)((markers + 63) / 64), 0);
+    for (long m = 0; m < markers; m++) {
+        bool c = m == 0;
+        if (m > 0 && chrom && chrom[m] != chrom[m - 1]) c = true;
+        if (m > 0 && pos && max_gap > 0 && pos[m] - pos[m - 1] > max_gap) c = true;
+        if (c) cut[(size_t)(m >> 6)] |= 1ull << (m & 63);
+    }
+}
 #endif

@@ -1855,6 +1855,183 @@ extern "C" int eagle_bed_roh(eagle_ctx* ctx, const char* bed_path, const long di
     return roh_end(ctx, b, params, ind_out, seg_out, seg_cap, nseg_out);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Pairwise IBD-type segments (include/eagle_hip.h section 1b'''vii; kernels in eagle_ibd.hip)
+// ---------------------------------------------------------------------------------------------------------------
+static_assert(IBD_MAX_PAIRS == EAGLE_IBD_MAX_PAIRS, "eagle_host.h restates the public limit");
+namespace {
+
+// What both entry points hold on the device: the bit planes of the panel, the cut plane, the block table, pos, the pair list and the
+// walk's arrays.
+struct IbdBufs {
+    DevBuf planes, cut, blk, pos, pairs, tot, offs, seg;
+    std::vector<int32_t> h_blk;
+    long lp = 0, n = 0, P = 0;
+    int nplanes = 2;
+    long nb() const { return (long)h_blk.size() - 1; }
+};
+
+// The argument rule of eagle_host.h, the pair list, the block table and the check of pos: everything that is decided before the
+// context is used.
+int ibd_check(eagle_ctx* ctx, const char* who, long n, long lp, const int32_t* pairs, long npairs, const int32_t* chrom, const int64_t* pos,
+              const eagle_ibd_params* prm, const void* seg_out, long seg_cap, std::vector<int32_t>& blk) {
+    const int64_t f[5] = {prm->mode, prm->min_snp, prm->min_len, prm->max_gap, prm->merge_min};
+    char msg[160];
+    if (const char* bad = ibd_arg_error(f, n, lp, pairs != nullptr, npairs, seg_cap, seg_out != nullptr)) {
+        snprintf(msg, sizeof msg, "%s: %s", who, bad);
+        return qc_fail(ctx, EAGLE_ERR_ARG, msg);
+    }
+    if (pairs) {
+        const long k = ibd_pairs_check(pairs, npairs, n);
+        if (k >= 0) {
+            snprintf(msg, sizeof msg, "%s: pair %ld is not 0 <= i < j < n", who, k);
+            return qc_fail(ctx, EAGLE_ERR_ARG, msg);
+        }
+    }
+    roh_block_table(chrom, lp, blk);
+    const long m = roh_pos_check(pos, blk);
+    if (m >= 0) {
+        snprintf(msg, sizeof msg, "%s: pos decreases inside a block (panel marker %ld)", who, m);
+        return qc_fail(ctx, EAGLE_ERR_ARG, msg);
+    }
+    return EAGLE_OK;
+}
+
+// The planes and the per-pair arrays against the memory budget (rule 9), then the allocations and uploads; no kernel has run when this
+// fails.
+int ibd_begin(eagle_ctx* ctx, const char* who, IbdBufs& b, long n, long lp, int nplanes, const int32_t* pairs, long npairs, const int32_t* chrom,
+              const int64_t* pos, const eagle_ibd_params* prm) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    b.n = n;
+    b.lp = lp;
+    b.nplanes = nplanes;
+    b.P = ibd_pair_count(n, pairs != nullptr, npairs);
+    const size_t np = (size_t)((n + 63) / 64 * 64), nwords = (size_t)((lp + 63) / 64);
+    const size_t plane_bytes = sizeof(uint64_t) * (size_t)nplanes * nwords * np, pair_bytes = (size_t)40 * (size_t)b.P;
+    size_t budget = eagle_resident_budget();
+    if (budget == (size_t)-1) {
+        size_t freeb = 0, totalb = 0;
+        HIPCHK(ctx, hipMemGetInfo(&freeb, &totalb));
+        budget = freeb > ((size_t)1 << 30) ? freeb - ((size_t)1 << 30) : 0;
+    }
+    if (plane_bytes > budget || pair_bytes > budget - plane_bytes)
+        return failf(ctx, EAGLE_ERR_NOMEM, "%s: the bit planes (%zu bytes) and the per-pair arrays (%zu bytes) do not fit the memory budget", who,
+                     plane_bytes, pair_bytes);
+    std::vector<uint64_t> h_cut;
+    ibd_cut_plane(chrom, pos, prm->max_gap, lp, h_cut);
+    HIPCHK(ctx, b.planes.alloc(plane_bytes));
+    HIPCHK(ctx, b.cut.alloc(sizeof(uint64_t) * nwords));
+    HIPCHK(ctx, b.blk.alloc(sizeof(int32_t) * b.h_blk.size()));
+    HIPCHK(ctx, b.tot.alloc(sizeof(int64_t) * 4 * (size_t)b.P));
+    HIPCHK(ctx, b.offs.alloc(sizeof(int64_t) * (size_t)b.P));
+    HIPCHK(ctx, hipMemcpyAsync(b.cut.p, h_cut.data(), sizeof(uint64_t) * nwords, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(b.blk.p, b.h_blk.data(), sizeof(int32_t) * b.h_blk.size(), hipMemcpyHostToDevice, ctx->stream));
+    if (pos) {
+        HIPCHK(ctx, b.pos.alloc(sizeof(int64_t) * (size_t)lp));
+        HIPCHK(ctx, hipMemcpyAsync(b.pos.p, pos, sizeof(int64_t) * (size_t)lp, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (pairs) {
+        HIPCHK(ctx, b.pairs.alloc(sizeof(int32_t) * 2 * (size_t)b.P));
+        HIPCHK(ctx, hipMemcpyAsync(b.pairs.p, pairs, sizeof(int32_t) * 2 * (size_t)b.P, hipMemcpyHostToDevice, ctx->stream));
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // h_cut leaves with this frame
+    return EAGLE_OK;
+}
+
+// The count pass, the exclusive scan of the per-pair counts on the host, and the fill pass when the rows fit seg_cap.
+int ibd_end(eagle_ctx* ctx, IbdBufs& b, const eagle_ibd_params* prm, int64_t* pair_out, int32_t* seg_out, long seg_cap, long* nseg_out) {
+    const int64_t* d_pos = b.pos.p ? b.pos.as<int64_t>() : nullptr;
+    const int32_t* d_pairs = b.pairs.p ? b.pairs.as<int32_t>() : nullptr;
+    int rc = eagle_dev_ibd_walk(ctx, b.planes.as<uint64_t>(), b.nplanes, b.cut.as<uint64_t>(), b.n, b.lp, d_pairs, b.P, b.blk.as<int32_t>(), b.nb(),
+                                d_pos, prm, 0, b.tot.as<int64_t>(), nullptr, nullptr, ctx->stream);
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    HIPCHK(ctx, hipMemcpyAsync(pair_out, b.tot.p, sizeof(int64_t) * 4 * (size_t)b.P, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<int64_t> h_offs((size_t)b.P);
+    const int64_t total = ibd_offsets(pair_out, (size_t)b.P, h_offs.data());
+    *nseg_out = (long)total;
+    if (total == 0 || total > seg_cap) return EAGLE_OK;
+    HIPCHK(ctx, b.seg.alloc(sizeof(int32_t) * 6 * (size_t)total));
+    HIPCHK(ctx, hipMemcpyAsync(b.offs.p, h_offs.data(), sizeof(int64_t) * (size_t)b.P, hipMemcpyHostToDevice, ctx->stream));
+    rc = eagle_dev_ibd_walk(ctx, b.planes.as<uint64_t>(), b.nplanes, b.cut.as<uint64_t>(), b.n, b.lp, d_pairs, b.P, b.blk.as<int32_t>(), b.nb(), d_pos,
+                            prm, 1, nullptr, b.offs.as<int64_t>(), b.seg.as<int32_t>(), ctx->stream);
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    HIPCHK(ctx, hipMemcpyAsync(seg_out, b.seg.p, sizeof(int32_t) * 6 * (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // h_offs leaves with this frame
+    return EAGLE_OK;
+}
+
+}  // namespace
+
+// A line of M.ascii is an individual.  The planes pass over a resident image is one launch; a file that is not resident is read in bands
+// of whole lines of the streamed size, and a band writes the plane words of its own individuals: every word is written once.
+extern "C" int eagle_ibd(eagle_ctx* ctx, const char* f_name_ascii_M, const long dims[2], const int32_t* pairs, long npairs, const int32_t* chrom,
+                         const int64_t* pos, const eagle_ibd_params* params, double max_memory_in_Gbytes, int64_t* pair_out, int32_t* seg_out,
+                         long seg_cap, long* nseg_out) {
+    if (!f_name_ascii_M || !dims || !params || !pair_out || !nseg_out) return qc_fail(ctx, EAGLE_ERR_ARG, "ibd: NULL argument");
+    const long n = dims[0], L = dims[1];
+    if (n <= 0 || L <= 0) return qc_fail(ctx, EAGLE_ERR_ARG, "ibd: dims must be positive");
+    IbdBufs b;
+    if (int rc = ibd_check(ctx, "ibd", n, L, pairs, npairs, chrom, pos, params, seg_out, seg_cap, b.h_blk)) return rc;
+    if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "ibd: no context");
+    int rc = ibd_begin(ctx, "ibd", b, n, L, 2, pairs, npairs, chrom, pos, params);
+    if (rc) return rc;
+    const int threads = host_threads();
+    const GenoEntry* src = nullptr;
+    rc = eagle_get_resident(ctx, f_name_ascii_M, n, L, max_memory_in_Gbytes, threads, &src);
+    if (rc != EAGLE_OK && rc != EAGLE_STREAM) return rc;
+    if (rc == EAGLE_OK) {
+        rc = eagle_dev_ibd_planes_i8(ctx, src->dev, src->ld, 0, n, n, L, b.planes.as<uint64_t>(), ctx->stream);
+        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    } else {
+        const long ld = eagle_pad(L), w = std::min(n, stream_chunk_rows_core(eagle_resident_budget(), ld, eagle_pad(n)));
+        DevBuf win;
+        HIPCHK(ctx, win.alloc((size_t)w * ld));
+        for (long r0 = 0; r0 < n; r0 += w) {
+            const long nr = std::min(w, n - r0);
+            HIPCHK(ctx, hipMemsetAsync(win.p, 0, (size_t)w * ld, ctx->stream));
+            rc = eagle_dev_load_ascii(ctx, f_name_ascii_M, r0, nr, 0, L, win.as<int8_t>(), ld, max_memory_in_Gbytes, threads);
+            if (!rc) rc = eagle_dev_ibd_planes_i8(ctx, win.as<int8_t>(), ld, r0, nr, n, L, b.planes.as<uint64_t>(), ctx->stream);
+            if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+        }
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // the window leaves with this scope
+    }
+    return ibd_end(ctx, b, params, pair_out, seg_out, seg_cap, nseg_out);
+}
+
+// The .bed rows go through the pinned ring in eagle_bed_roh's windows of panel markers.  A window that is not the last is cut back to a
+// multiple of 64 markers (it holds at least 64), and the next one starts there: a window writes whole plane words.
+extern "C" int eagle_bed_ibd(eagle_ctx* ctx, const char* bed_path, const long dims[2], const uint8_t* include, const int32_t* pairs, long npairs,
+                             const int32_t* chrom, const int64_t* pos, const eagle_ibd_params* params, double max_memory_in_Gbytes,
+                             int64_t* pair_out, int32_t* seg_out, long seg_cap, long* nseg_out) {
+    if (!bed_path || !dims || !params || !pair_out || !nseg_out) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_ibd: NULL argument");
+    const long n = dims[0], L = dims[1];
+    if (n <= 0 || L <= 0) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_ibd: dims must be positive");
+    if (n > 0x3fffffffL) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_ibd: 2^30 individuals or more");
+    const long linc = bedld_count(include, L);
+    if (linc < 1) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_ibd: include selects no marker");
+    IbdBufs b;
+    if (int rc = ibd_check(ctx, "bed_ibd", n, linc, pairs, npairs, chrom, pos, params, seg_out, seg_cap, b.h_blk)) return rc;
+    if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_ibd: no context");
+    int rc = ibd_begin(ctx, "bed_ibd", b, n, linc, 3, pairs, npairs, chrom, pos, params);
+    if (rc) return rc;
+    BedLdPanel pl;
+    pl.pack = false;
+    const long need = 64;
+    auto next_of = [&](long hi) { return hi >= linc ? linc : hi / 64 * 64; };
+    rc = bedld_open(pl, ctx, bed_path, n, L, include, linc, max_memory_in_Gbytes, 0, need, next_of);
+    if (rc) return rc;
+    for (long lo = 0; lo < linc;) {
+        const long hi = pl.window_end(lo, need), nxt = next_of(hi);
+        rc = pl.stage(lo, hi);
+        if (!rc) rc = eagle_dev_ibd_planes_bed(ctx, pl.raw, pl.raw_off, n, lo, lo / 64, (nxt + 63) / 64, linc, b.planes.as<uint64_t>(), ctx->stream);
+        if (!rc) rc = pl.release();
+        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+        lo = nxt;
+    }
+    return ibd_end(ctx, b, params, pair_out, seg_out, seg_cap, nseg_out);
+}
+
 // The loci's rows are gathered into a 64-row image first (k_gather_rows_i8: from the resident image, else from their own lines of
 // the file, each distinct line read once), then every tile of Mt multiplies against it, where it lies or window by window.
 extern "C" int eagle_ld_dots(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long dims[2], const long* loci, long nloci,

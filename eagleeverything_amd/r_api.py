@@ -1297,6 +1297,167 @@ def roh_summary(ind, seg, L, chrom=None, pos=None):
             "incidence": roh_incidence(seg, L), "ind": ind, "seg": seg}
 
 
+# ---- pairwise IBD-type segments (include/eagle_hip.h section 1b'''vii): the restatement in numpy and the interface ----
+def ibd_genotypes_bed(codes):
+    """(g int8, called bool), both (L, n), from the 2-bit codes of a .bed file (read_bed_codes: 0 hom A1, 1 missing, 2 het, 3 hom A2):
+    g = -1 / 0 / +1 as on the ingested image, 0 where the call is missing."""
+    c = np.asarray(codes, dtype=np.uint8)
+    return np.array([-1, 0, 0, 1], dtype=np.int8)[c], c != 1
+
+
+def ibd_all_pairs(n):
+    """All pairs 0 <= i < j < n in row-major upper-triangle order -> int32 (n (n - 1) / 2, 2)."""
+    i, j = np.triu_indices(int(n), k=1)
+    return np.stack([i, j], axis=1).astype(np.int32).reshape(-1, 2)
+
+
+def ibd_host(g, called=None, pairs=None, chrom=None, pos=None, **params):
+    """rcpp_api.ibd / bed_ibd restated in numpy: g = int8 (L, n) with -1 hom A1, 0 het, +1 hom A2 (the marker-major image), called =
+    bool (L, n) or None (everything called; ibd_genotypes_bed gives both from .bed codes) -> (pair int64 (P, 4), seg int32 (S, 6)),
+    rules 2 to 8 of include/eagle_hip.h section 1b'''vii with the parameters of rcpp_api.ibd_params.  Pure runs are read off the edges
+    of the break matrix of a batch of pairs; chains are runs of linked neighbours (both eligible, one break between, no cut).  Integers
+    throughout."""
+    G = np.asarray(g)
+    if G.ndim != 2 or G.shape[0] < 1 or G.shape[1] < 1 or G.min() < -1 or G.max() > 1:
+        raise ValueError("ibd_host: g must be (L, n) with values -1, 0, +1")
+    G = G.astype(np.int8)
+    L, n = G.shape
+    Cm = None if called is None else np.asarray(called, dtype=bool)
+    if Cm is not None and Cm.shape != G.shape:
+        raise ValueError("ibd_host: called must have the shape of g")
+    p = rcpp_api.ibd_params("ibd_host", **params)
+    pr = rcpp_api.ibd_pairs("ibd_host", pairs, n)
+    if pr is None:
+        pr = ibd_all_pairs(n)
+    ch = None if chrom is None else np.asarray(chrom).ravel()
+    ps = np.arange(L, dtype=np.int64) if pos is None else np.asarray(pos).ravel().astype(np.int64)
+    if (ch is not None and ch.size != L) or ps.size != L:
+        raise ValueError("ibd_host: chrom and pos hold one entry per marker (%d)" % L)
+    blk = rcpp_api.roh_blocks(ch, L)
+    down = np.diff(ps) < 0
+    down[blk[1:-1] - 1] = False
+    if down.any():
+        raise ValueError("ibd_host: pos decreases inside a block (panel marker %d)" % (int(np.flatnonzero(down)[0]) + 1))
+    cut = np.zeros(L + 2, dtype=bool)                      # cut[m]: a piece starts at marker m; L and L + 1 stand for the end
+    cut[blk] = True
+    cut[L + 1] = True
+    if p["max_gap"] > 0 and L > 1:
+        cut[1:L] |= np.diff(ps) > p["max_gap"]
+    P = pr.shape[0]
+    tab = np.zeros((P, 4), dtype=np.int64)
+    rows = []
+    step = max(1, (1 << 22) // L)
+    for k0 in range(0, P, step):
+        ii, jj = pr[k0:k0 + step, 0], pr[k0:k0 + step, 1]
+        gi, gj = G[:, ii].T, G[:, jj].T                    # (pairs, L)
+        brk = (gi * gj == -1) if p["mode"] == 1 else (gi != gj)
+        if Cm is not None:
+            brk &= Cm[:, ii].T & Cm[:, jj].T
+        clean = ~brk
+        edge = np.ones((brk.shape[0], 1), dtype=bool)
+        first = clean & (cut[None, :L] | np.concatenate((edge, brk[:, :-1]), axis=1))
+        last = clean & (cut[None, 1:L + 1] | np.concatenate((brk[:, 1:], edge), axis=1))
+        q, rs = np.nonzero(first)                          # sorted by (pair, start); the k-th start pairs with the k-th end
+        _, re = np.nonzero(last)
+        if q.size == 0:
+            continue
+        el = (re - rs + 1 >= p["merge_min"]) if p["merge_min"] >= 1 else np.zeros(q.size, dtype=bool)
+        link = (q[1:] == q[:-1]) & (rs[1:] == re[:-1] + 2) & ~cut[re[:-1] + 1] & ~cut[re[:-1] + 2] & el[1:] & el[:-1]
+        head = np.concatenate(([True], ~link))
+        tail = np.concatenate((~link, [True]))
+        hq, cs, ce = q[head], rs[head], re[tail]
+        runs = np.diff(np.concatenate((np.flatnonzero(head), [q.size])))
+        nsnp, length = ce - cs + 1, ps[ce] - ps[cs]
+        ok = (nsnp >= p["min_snp"]) & (length >= p["min_len"])
+        hq, cs, ce, runs, nsnp, length = (x[ok] for x in (hq, cs, ce, runs, nsnp, length))
+        rows.append(np.stack([ii[hq], jj[hq], cs, ce, runs - 1, np.searchsorted(blk, cs, side="right") - 1], axis=1))
+        t = tab[k0:k0 + step]
+        np.add.at(t[:, 0], hq, 1)
+        np.add.at(t[:, 1], hq, nsnp)
+        np.add.at(t[:, 2], hq, length)
+        np.maximum.at(t[:, 3], hq, length)
+    seg = np.concatenate(rows).astype(np.int32).reshape(-1, 6) if rows else np.zeros((0, 6), dtype=np.int32)
+    return tab, seg
+
+
+def ibd_incidence(seg, L):
+    """The number of reported segments over every marker -> int64 (L), from the rows of rcpp_api.ibd's table (a pair listed twice counts
+    twice), by a difference array.  Peaks are stretches many pairs share: sweeps and low-diversity regions, the pairwise twin of the ROH
+    islands."""
+    seg = np.asarray(seg, dtype=np.int64).reshape(-1, 6)
+    L = int(L)
+    if seg.size and (seg[:, 2].min() < 0 or seg[:, 3].max() >= L or np.any(seg[:, 3] < seg[:, 2])):
+        raise ValueError("ibd_incidence: a segment outside [0, %d)" % L)
+    d = np.zeros(L + 1, dtype=np.int64)
+    np.add.at(d, seg[:, 2], 1)
+    np.add.at(d, seg[:, 3] + 1, -1)
+    return np.cumsum(d[:L])
+
+
+def ibd_summary(pairs, tab, seg, L, chrom=None, pos=None):
+    """IBD's result from the integer outputs (host arithmetic; `shared` is the one fp64 division, over F_ROH's genome length)."""
+    ps = np.arange(L, dtype=np.int64) if pos is None else np.asarray(pos, dtype=np.int64)
+    blk = rcpp_api.roh_blocks(chrom, L)
+    genome = int(np.sum(ps[blk[1:] - 1] - ps[blk[:-1]]))
+    s, e = seg[:, 2].astype(np.int64), seg[:, 3].astype(np.int64)
+    table = {"i": seg[:, 0].copy(), "j": seg[:, 1].copy(), "first": seg[:, 2].copy(), "last": seg[:, 3].copy(), "nsnp": (e - s + 1).astype(np.int32),
+             "nbreak": seg[:, 4].copy(), "block": seg[:, 5].copy(), "pos_first": ps[s], "pos_last": ps[e], "length": ps[e] - ps[s]}
+    with np.errstate(divide="ignore", invalid="ignore"):
+        f = tab[:, 2].astype(np.float64) / np.float64(genome) if genome > 0 else np.full(tab.shape[0], np.nan)
+    return {"segments": table, "pairs": pairs, "nseg": tab[:, 0].copy(), "total_length": tab[:, 2].copy(), "longest": tab[:, 3].copy(),
+            "shared": f, "ibd_incidence": ibd_incidence(seg, L), "pair": tab, "seg": seg}
+
+
+def IBD(geno, map=None, bed=None, include=None, pairs=None, mode="ibs1", min_snp=200, min_kb=1000, max_gap_kb=1000, merge_min_snp=100,
+        availmemGb=8, device=0):
+    """Where two individuals of a panel share their genome (include/eagle_hip.h section 1b'''vii; rcpp_api.ibd) -> {"segments": the
+    table as a dict of arrays (i, j, first, last, nsnp, nbreak, block, pos_first, pos_last, length), "pairs": int32 (P, 2), "nseg",
+    "total_length", "longest": int64 (P), "shared": fp64 (P) = total_length / the genome length F_ROH uses (NaN when that is 0),
+    "ibd_incidence": int64 (L), the number of reported segments over each marker, "pair", "seg": the integer outputs as returned}.
+    mode "ibs1": runs without opposite homozygotes, where the pair can share one haplotype (IBD1-type); mode "ibs2": runs of equal
+    genotypes, where it can share both (IBD2-type) -- the way IBIS and TRUFFLE work on unphased genotypes; agreement with those programs
+    is not claimed.  Pure runs of at least merge_min_snp markers are merged across a single break marker (0: no merging); a segment needs
+    min_snp markers and min_kb.  These are IBS runs, so they bound IBD from above: short thresholds report chance sharing.  pairs = int
+    (P, 2), 0 <= i < j < n (e.g. Relatedness(...)["pairs"]); None = all pairs.  map (ReadBim's dict, as LDPrune takes it): chromosomes
+    are blocks, lengths are base pairs, and min_kb, max_gap_kb are converted to base pairs (None: off).  Without a map the position is
+    the marker index and both kb arguments must be passed as None.  On the ingested (het-filled) panel a missing call is a het: it can
+    never be an opposite homozygote, so missing calls INFLATE mode "ibs1", and it differs from every called homozygote, so they CUT
+    mode "ibs2".  bed = the .bed file (or prefix) the panel was ingested from is the route for un-imputed panels: a marker where either
+    individual is not called is never a break (rcpp_api.bed_ibd); include = the panel's markers in the file, default geno's
+    marker_index."""
+    src = _ld_stats_source("IBD", geno, map, bed, include)
+    n, L, chrom, pos, src_bed, bdims, inc = src
+    kb = {"min_kb": min_kb, "max_gap_kb": max_gap_kb}
+    if pos is None:
+        given = [k for k, v in kb.items() if v is not None]
+        if given:
+            raise ValueError("IBD: %s needs a map with Chr and Pos entries; without one pass min_kb and max_gap_kb as None" % ", ".join(given))
+    bp = {}
+    for k, v in kb.items():
+        bp[k] = 0 if v is None else int(round(float(v) * 1000.0))
+        if v is not None and bp[k] < 1:
+            raise ValueError("IBD: %s must be at least 0.001" % k)
+    prm = dict(mode=mode, min_snp=int(min_snp), min_len=bp["min_kb"], max_gap=bp["max_gap_kb"], merge_min=int(merge_min_snp))
+    pr = rcpp_api.ibd_pairs("IBD", pairs, n)
+    if src_bed is None:
+        tab, seg = rcpp_api.ibd(geno["asciifileM"], (n, L), pr, chrom, pos, availmemGb, device=device, **prm)
+    else:
+        tab, seg = rcpp_api.bed_ibd(src_bed, bdims, inc, pr, chrom, pos, availmemGb, device=device, **prm)
+    return ibd_summary(ibd_all_pairs(n) if pr is None else pr, tab, seg, L, chrom, pos)
+
+
+def ibd_kinship(ibs1, ibs2):
+    """A kinship estimate that needs no allele frequencies -> fp64 (P): (shared_1 + shared_2) / 4 from the `shared` fractions of
+    IBD(mode="ibs1") and IBD(mode="ibs2") over the same pairs (the dicts IBD returns, or the arrays).  An ibs2 run lies inside an ibs1
+    run, so with k2 = shared_2 and k1 = shared_1 - shared_2 this is k1 / 4 + k2 / 2; two copies of one individual give 0.5.  IBS runs
+    bound IBD from above, so this bounds the kinship from above: it is as good as the thresholds are strict."""
+    a = np.asarray(ibs1["shared"] if isinstance(ibs1, dict) else ibs1, dtype=np.float64)
+    b = np.asarray(ibs2["shared"] if isinstance(ibs2, dict) else ibs2, dtype=np.float64)
+    if a.shape != b.shape:
+        raise ValueError("ibd_kinship: the two results are over different pairs")
+    return (a + b) / 4.0
+
+
 # ---- GRM and PCA (include/eagle_hip.h section 1b''''): the exact weighted Gram product on the device, fp64 arithmetic on the host ----
 GRM_QMAX = 2097151    # 2^21 - 1: the largest weight rcpp_api.weighted_gram takes
 

@@ -1019,6 +1019,128 @@ def bed_roh(bed_path, dims, include=None, chrom=None, pos=None, availmemGb=8.0, 
     return _roh_call(L.eagle_bed_roh, device, head, ch, ps, prm, availmemGb, n, cap)
 
 
+# ---- pairwise IBD-type segments (include/eagle_hip.h section 1b'''vii): shared-genotype runs between individuals as exact integers ----
+IBD_MAX_PAIRS = 1 << 27
+IBD_DEFAULTS = dict(mode=1, min_snp=200, min_len=0, max_gap=0, merge_min=100)
+IBD_MODES = {"ibs1": 1, "ibs2": 2}
+_IBD_FIELDS = ("mode", "min_snp", "min_len", "max_gap", "merge_min")
+
+
+def ibd_params(who="ibd", **params):
+    """The five integers of eagle_ibd_params as a dict, defaults IBD_DEFAULTS; mode may be "ibs1" / "ibs2".  ValueError for an unknown
+    name, a value that is not a whole number, or one outside the header's rule: mode 1 or 2, min_snp >= 1, min_len, max_gap and
+    merge_min >= 0."""
+    p = dict(IBD_DEFAULTS)
+    for k, v in params.items():
+        if k not in p:
+            raise ValueError("%s: unknown parameter %s" % (who, k))
+        if k == "mode" and isinstance(v, str):
+            if v not in IBD_MODES:
+                raise ValueError("%s: mode must be 1 (ibs1) or 2 (ibs2)" % who)
+            v = IBD_MODES[v]
+        try:
+            iv = int(v)
+        except (TypeError, ValueError):
+            raise ValueError("%s: %s must be a whole number" % (who, k))
+        if iv != v or not -(1 << 63) <= iv < 1 << 63:
+            raise ValueError("%s: %s must be a whole number that fits int64" % (who, k))
+        p[k] = iv
+    if p["mode"] not in (1, 2):
+        raise ValueError("%s: mode must be 1 (ibs1) or 2 (ibs2)" % who)
+    if p["min_snp"] < 1:
+        raise ValueError("%s: min_snp must be at least 1" % who)
+    for k in ("min_len", "max_gap", "merge_min"):
+        if p[k] < 0:
+            raise ValueError("%s: %s must not be negative" % (who, k))
+    return p
+
+
+def ibd_pairs(who, pairs, n):
+    """A pair list as contiguous int32 (P, 2), or None for all pairs; ValueError for a pair outside 0 <= i < j < n or a count outside
+    [1, 2^27] (all pairs: n >= 2 and n (n - 1) / 2 <= 2^27)."""
+    if pairs is None:
+        if n < 2:
+            raise ValueError("%s: all pairs need at least two individuals" % who)
+        if n * (n - 1) // 2 > IBD_MAX_PAIRS:
+            raise ValueError("%s: more than 2^27 pairs: give a list" % who)
+        return None
+    a = np.asarray(pairs)
+    if a.size == 0 or a.ndim != 2 or a.shape[1] != 2 or a.shape[0] > IBD_MAX_PAIRS:
+        raise ValueError("%s: the number of pairs must be in [1, 2^27]" % who)
+    if not np.array_equal(a.astype(np.int64), a):
+        raise ValueError("%s: pairs must be whole numbers" % who)
+    a = a.astype(np.int64)
+    bad = np.flatnonzero((a[:, 0] < 0) | (a[:, 0] >= a[:, 1]) | (a[:, 1] >= n))
+    if bad.size:
+        raise ValueError("%s: pair %d is not 0 <= i < j < n" % (who, int(bad[0])))
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _ibd_args(who, n, nm, pairs, chrom, pos, params):
+    ch, ps, _ = _ld_stats_args(who, nm, chrom, pos, 0, None)
+    p = ibd_params(who, **params)
+    if nm >= 1 << 31:
+        raise ValueError("%s: 2^31 markers or more" % who)
+    pr = ibd_pairs(who, pairs, n)
+    if ps is not None:
+        blk = roh_blocks(ch, nm)
+        d = np.diff(ps) < 0
+        d[blk[1:-1] - 1] = False                         # block edges are not compared across
+        if d.any():
+            raise ValueError("%s: pos decreases inside a block (panel marker %d)" % (who, int(np.flatnonzero(d)[0]) + 1))
+    return pr, ch, ps, _lib.IbdParams(*[p[f] for f in _IBD_FIELDS])
+
+
+def _ibd_call(fn, device, head, pr, ch, ps, prm, mem, n, seg_cap):
+    P = n * (n - 1) // 2 if pr is None else pr.shape[0]
+    tab = np.zeros((P, 4), dtype=np.int64)
+    while True:
+        seg = np.zeros((seg_cap, 6), dtype=np.int32)
+        total = C.c_long(0)
+        _args_first(fn, device, head + (pr.ctypes.data_as(_c_i32p) if pr is not None else None, P if pr is not None else 0,
+                                        ch.ctypes.data_as(_c_i32p) if ch is not None else None,
+                                        ps.ctypes.data_as(_c_i64p) if ps is not None else None, C.addressof(prm), float(mem),
+                                        tab.ctypes.data_as(_c_i64p), seg.ctypes.data_as(_c_i32p) if seg_cap else None, seg_cap, C.byref(total)))
+        if total.value <= seg_cap:
+            return tab, seg[:total.value].copy()
+        seg_cap = int(total.value)
+
+
+def ibd(f_name_ascii_M, dims, pairs=None, chrom=None, pos=None, max_memory_in_Gbytes=8.0, device=0, seg_cap=None, **params):
+    """eagle_ibd -> (pair int64 (P, 4), seg int32 (S, 6)): the shared-genotype runs of include/eagle_hip.h section 1b'''vii on the
+    ingested panel M.ascii (dims = (n, L) of M).  pair = (segments, sum of nsnp, sum of len, longest len) per pair; seg rows = (i, j,
+    first marker, last marker, nbreak, block ordinal), sorted by (pair ordinal, first marker).  pairs: int (P, 2) with 0 <= i < j < n,
+    duplicates allowed, or None for all pairs in row-major upper-triangle order.  chrom, pos: one whole number per marker or None (one
+    block; pos = the marker index).  params: mode (1 / "ibs1", 2 / "ibs2"), min_snp, min_len, max_gap, merge_min (IBD_DEFAULTS).  The
+    library is called once with a capacity guess (seg_cap, default 4 P) and once more if that was short.  ValueError for bad arguments
+    before the library is called.  r_api.ibd_host is the numpy restatement."""
+    L = _lib.load()
+    n, nm = max(int(dims[0]), 0), max(int(dims[1]), 0)
+    pr, ch, ps, prm = _ibd_args("ibd", n, nm, pairs, chrom, pos, params)
+    P = n * (n - 1) // 2 if pr is None else pr.shape[0]
+    cap = 4 * P if seg_cap is None else int(seg_cap)
+    if cap < 0:
+        raise ValueError("ibd: seg_cap must not be negative")
+    return _ibd_call(L.eagle_ibd, device, (os.fsencode(f_name_ascii_M), _dims(dims)), pr, ch, ps, prm, max_memory_in_Gbytes, n, cap)
+
+
+def bed_ibd(bed_path, dims, include=None, pairs=None, chrom=None, pos=None, availmemGb=8.0, device=0, seg_cap=None, **params):
+    """eagle_bed_ibd -> ibd's pair of tables by PANEL marker from a SNP-major PLINK .bed file of dims = (n individuals, L markers), which
+    still knows its missing calls: a marker where either individual is not called (code 01) is never a break.  include as in
+    bed_ld_window; chrom and pos: one whole number per panel marker."""
+    L = _lib.load()
+    n, nm = max(int(dims[0]), 0), max(int(dims[1]), 0)
+    inc = _bed_ld_include(include, nm, "bed_ibd")
+    linc = nm if inc is None else int(inc.sum())
+    pr, ch, ps, prm = _ibd_args("bed_ibd", n, linc, pairs, chrom, pos, params)
+    P = n * (n - 1) // 2 if pr is None else pr.shape[0]
+    cap = 4 * P if seg_cap is None else int(seg_cap)
+    if cap < 0:
+        raise ValueError("bed_ibd: seg_cap must not be negative")
+    head = (os.fsencode(bed_path), _dims(dims), inc.ctypes.data_as(C.c_void_p) if inc is not None else None)
+    return _ibd_call(L.eagle_bed_ibd, device, head, pr, ch, ps, prm, availmemGb, n, cap)
+
+
 # ---- GRM (include/eagle_hip.h section 1b''''): the exact weighted Gram product; weights, centring and PCA are r_api's ----
 WGRAM_MAX_WEIGHT = (1 << 21) - 1
 

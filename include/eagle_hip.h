@@ -712,6 +712,70 @@ int eagle_bed_roh(eagle_ctx* ctx, const char* bed_path, const long dims[2], cons
                   const eagle_roh_params* params, double max_memory_in_Gbytes, int64_t* ind_out, int32_t* seg_out, long seg_cap, long* nseg_out);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1b'''vii. Pairwise IBD-type segments (no counterpart in the reference): where two individuals share their genome.  On unphased
+ *     genotypes a pair can share one haplotype only where it has no opposite homozygotes, and both only where its genotypes are equal
+ *     -- the observation IBIS and TRUFFLE build on.  The runs below are IBS runs: they bound IBD from above.  Agreement with the IBIS or
+ *     TRUFFLE programs is neither claimed nor tested.  Everything is integers, so the device and numpy (r_api.ibd_host) agree with ==.
+ *
+ *     1. Genotype and called.  Image value -1 / 0 / +1 is hom A1 / het / hom A2, always called: a missing call of the original data is
+ *        a het by now.  .bed codes 00 / 10 / 11 are hom A1 / het / hom A2; code 01 is not called.
+ *     2. Break marker of the pair (i, j).  Both are called at m, and  mode = 1 ("ibs1"): g_i * g_j = -1, opposite homozygotes;
+ *        mode = 2 ("ibs2"): g_i != g_j.  A marker where either is not called is never a break.
+ *     3. Blocks and pieces.  Blocks are those of ROH rule 2 (chrom, int32 by panel marker; NULL: one block).  pos is int64 by panel
+ *        marker (NULL: pos[m] = m) and must be non-decreasing inside every block, else EAGLE_ERR_ARG.  With max_gap > 0 a block is cut
+ *        further between m and m + 1 where pos[m + 1] - pos[m] > max_gap.  The results are PIECES.
+ *     4. Pure run.  A maximal sequence of consecutive non-break markers inside one piece.
+ *     5. Merging.  With merge_min = 0 every pure run is a candidate on its own.  With merge_min >= 1 a pure run is ELIGIBLE iff it has
+ *        at least merge_min markers, and a candidate is a maximal chain R_1 .. R_k of pure runs of one piece in which, whenever k >= 2,
+ *        every run is eligible and consecutive runs are separated by exactly one marker (a single break).  An ineligible run is a
+ *        chain of its own; two breaks in a row, or a cut, end a chain.  The condition is on each pure run alone, so the chains do not
+ *        depend on the walking order.
+ *     6. Reported segment.  A candidate s .. e (the break markers inside included) with  nsnp = e - s + 1 >= min_snp  and
+ *        len = pos[e] - pos[s] >= min_len.  nbreak = k - 1.
+ *     7. Pairs.  pairs is P x 2 int32 with 0 <= i < j < n, duplicates allowed; NULL: all pairs in row-major upper-triangle order,
+ *        k = i n - i (i + 1) / 2 + (j - i - 1), and npairs is ignored.  P <= EAGLE_IBD_MAX_PAIRS = 2^27.
+ *     8. Outputs.  pair_out: P x 4 int64 = (number of segments, sum of nsnp, sum of len, longest len) by pair ordinal.  seg_out: rows of
+ *        six int32 (i, j, s, e, nbreak, block ordinal), sorted by (pair ordinal, s); s and e are panel marker indices.  *nseg_out is
+ *        always the total.  seg_out has room for seg_cap rows (it may be NULL when seg_cap is 0); it is written iff the total is
+ *        <= seg_cap and untouched otherwise.  The call returns EAGLE_OK either way (eagle_roh's semantics, rule 7 there).
+ *     9. Limits.  Panel markers < 2^31; n <= 0x3fffffff for the .bed file.  The bit planes below (2, from the .bed file 3, x
+ *        ceil(markers / 64) x n rounded up to 64 x 8 bytes) and the per-pair arrays (40 bytes a pair) stay on the device for the whole
+ *        call: where they do not fit the memory budget (ROH rule 8) the call returns EAGLE_ERR_NOMEM, decided before any kernel runs.
+ *
+ *     The planes are individual-major words, one uint64 per individual per 64 markers, stored word-major so that 64 individuals' words
+ *     of one index are consecutive.  Bits past the last marker and words of padding individuals are zero.  eagle_ibd reads M.ascii as
+ *     eagle_sample_counts reads it (the resident image, else bands of whole lines of the streamed size from the sidecar, the text or a
+ *     VIEW alias's source; a VIEW alias gives the kept individuals): a band writes the words of its own individuals.  eagle_bed_ibd
+ *     reads the .bed rows through the pinned ring in windows of panel markers that end on multiples of 64: a window writes whole words.
+ *     Either way every plane word is written once and the result does not depend on the window size.  k_ibd_walk has one lane per
+ *     pair -- a wave takes one i and 64 consecutive j, or 64 list entries -- and walks the words in order; events are taken by
+ *     find-first-set over the bits of break | cut, the cut plane (a bit where a piece starts) being shared by all pairs.  A count pass, an
+ *     exclusive scan of the per-pair counts on the host, and a fill pass that is skipped when the total exceeds seg_cap; no array of
+ *     pairs x markers exists.
+ *
+ *     Single device: a multi-device context works on its first device.  Argument errors (EAGLE_ERR_ARG: a NULL pointer, dims <= 0,
+ *     and those named below) are decided before the context is used; with ctx == NULL their text is in eagle_open_error().
+ * ------------------------------------------------------------------------------------------- */
+#define EAGLE_IBD_MAX_PAIRS 134217728L
+
+typedef struct eagle_ibd_params { int64_t mode, min_snp, min_len, max_gap, merge_min; } eagle_ibd_params;
+
+/* Rules 1 to 8 on the ingested panel M.ascii (dims = (n, L) of M); pairs (npairs x 2 int32), chrom (L int32) and pos (L int64) may be
+ * NULL.  EAGLE_ERR_ARG: mode not 1 or 2, min_snp < 1, min_len / max_gap / merge_min < 0, L >= 2^31, npairs outside [1, 2^27] (a list) or
+ * n < 2 or n (n - 1) / 2 > 2^27 (all pairs), a pair outside 0 <= i < j < n, seg_cap < 0, seg_out NULL with seg_cap > 0, pos decreasing
+ * inside a block. */
+int eagle_ibd(eagle_ctx* ctx, const char* f_name_ascii_M, const long dims[2], const int32_t* pairs, long npairs, const int32_t* chrom,
+              const int64_t* pos, const eagle_ibd_params* params, double max_memory_in_Gbytes, int64_t* pair_out, int32_t* seg_out, long seg_cap,
+              long* nseg_out);
+
+/* The same by PANEL marker (the Linc markers include selects, L bytes or NULL; chrom and pos by panel marker) from the SNP-major .bed
+ * file bed_path (dims = (n, L) of the file), which still knows its missing calls.
+ * EAGLE_ERR_ARG: those of eagle_ibd with Linc in the place of L, and n > 0x3fffffff, an include that selects no marker. */
+int eagle_bed_ibd(eagle_ctx* ctx, const char* bed_path, const long dims[2], const uint8_t* include, const int32_t* pairs, long npairs,
+                  const int32_t* chrom, const int64_t* pos, const eagle_ibd_params* params, double max_memory_in_Gbytes, int64_t* pair_out,
+                  int32_t* seg_out, long seg_cap, long* nseg_out);
+
+/* ---------------------------------------------------------------------------------------------
  * 1b''''. Genomic relationship matrix (no counterpart that the reference calls: its VanRaden G, E/R/GenomicRel.R, is unused): the one
  *     Gram product the matrices of EIGENSTRAT / PLINK / GCTA and their principal components need, with a weight per marker.  With
  *     g in {-1, 0, +1} = AA, AB, BB as everywhere in this library and integer weights q_m < 2^21,
