@@ -163,7 +163,15 @@ struct PinBuf {
     ~PinBuf() { if (p) (void)hipHostFree(p); }
     hipError_t alloc(size_t bytes) { return hipHostMalloc(&p, bytes ? bytes : 16, hipHostMallocDefault); }
 };
-
+// the two events of a double-buffered pipeline: e[b] is recorded behind the last stream work that touches buffer b
+struct EventPair {
+    hipEvent_t e[2] = {nullptr, nullptr};
+    ~EventPair() { for (int b = 0; b < 2; b++) if (e[b]) (void)hipEventDestroy(e[b]); }
+    hipError_t create() {
+        hipError_t r = hipEventCreateWithFlags(&e[0], hipEventDisableTiming);
+        return r != hipSuccess ? r : hipEventCreateWithFlags(&e[1], hipEventDisableTiming);
+    }
+};
 
 // Registers a device image (rows_pad x ld int8, zero padded) as the resident copy of the text file at `path`
 // (rows lines x cols characters); takes ownership of `dev`.  Stale entries of the same path are dropped.

@@ -244,6 +244,24 @@ static inline BedWindow bed_window(long k, long w, long L, long L_pad) {
     return {c0, std::min(w, L - c0), std::min(w, L_pad - c0)};
 }
 static inline long bed_window_count(long w, long L) { return (L + w - 1) / w; }
+// The staging rule of every eagle_bed_* call (the loaders' rule): the file rows of rb bytes a staging window holds -- 64 MiB of them, or
+// a quarter of max_memory_in_Gbytes when that is less, never fewer than one -- before the caller's own caps.
+static inline long bed_stage_rows(long rb, double mem_gb) {
+    double cap = 67108864.0;
+    if (mem_gb > 0) cap = std::min(cap, mem_gb * 1e9 / 4.0);
+    return std::max(1L, (long)cap / rb);
+}
+// The panel windows of include/eagle_hip.h section 1b'''iv.  fidx: panel marker -> file row, increasing; empty: the identity.  The window
+// that starts at panel marker lo ends at the largest hi <= linc with hi - lo <= wmax whose file rows span at most S rows, but it holds
+// at least `need` markers (what the call needs to advance) or the rest of the panel.
+static inline long bed_panel_file_row(const std::vector<long>& fidx, long p) { return fidx.empty() ? p : fidx[(size_t)p]; }
+static inline long bed_panel_window_end(long lo, long need, long wmax, long S, long linc, const std::vector<long>& fidx) {
+    const long floor_hi = std::min(linc, lo + need);
+    long hi = std::min(linc, lo + wmax);
+    if (fidx.empty()) hi = std::min(hi, lo + S);
+    else hi = (long)(std::upper_bound(fidx.begin() + lo, fidx.begin() + hi, fidx[(size_t)lo] + S - 1) - fidx.begin());
+    return std::max(hi, floor_hi);
+}
 
 // ------------------------------------------------------------------------------------------------
 // Byte arithmetic of the genotype loader (eagle_load.cpp).

@@ -208,6 +208,36 @@ struct SidecarWriter {
     }
 };
 
+// Write-behind of a text file of `stride` bytes per line and its sidecar, from the pinned staging buffers: the lines of chunk k - 1 go to
+// disk under the device work of chunk k.  next(): chunk k, lines [r0, r0 + n), is on its way into pinned buffer b with done.e[b] recorded
+// behind it; chunk k - 1 is written now.
+struct LinesBehind {
+    eagle_ctx* ctx;
+    int fd;
+    const char* path;
+    long stride;
+    SidecarWriter& sc;
+    EventPair& done;
+    int threads;
+    long r0 = -1, n = 0;   // the chunk not yet on disk (r0 < 0: none)
+    int b = 0;
+    int flush() {
+        if (r0 < 0) return EAGLE_OK;
+        hipError_t e = hipEventSynchronize(done.e[b]);
+        if (e != hipSuccess) return eagle_fail_hip(ctx, e, "hipEventSynchronize");
+        if (!pwrite_all(fd, (const char*)ctx->stage_pin[b], (size_t)n * stride, (off_t)r0 * stride, threads))
+            return failf(ctx, EAGLE_ERR_OPEN, "ERROR: could not write %s", path);
+        sc.write(b, r0, n, threads);
+        r0 = -1;
+        return EAGLE_OK;
+    }
+    int next(long r0_, long n_, int b_) {
+        const int rc = flush();
+        r0 = r0_; n = n_; b = b_;
+        return rc;
+    }
+};
+
 }  // namespace
 
 extern "C" int eagle_get_row_column(eagle_ctx* ctx, const char* fname, long dims_out[2]) {
@@ -279,9 +309,8 @@ static int create_M_text(eagle_ctx* ctx, const char* fname, const char* asciifna
         else HIPCHK(ctx, hipMemsetAsync(dev, 0, (size_t)n_pad * ld, ctx->stream));
     }
     struct DevGuard { int8_t*& p; ~DevGuard() { if (p) (void)hipFree(p); } } guard{dev};
-    hipEvent_t done[2] = {nullptr, nullptr};
-    for (int b = 0; b < 2; b++) HIPCHK(ctx, hipEventCreateWithFlags(&done[b], hipEventDisableTiming));
-    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int b = 0; b < 2; b++) if (e[b]) (void)hipEventDestroy(e[b]); } } evg{done};
+    EventPair done;
+    HIPCHK(ctx, done.create());
 
     RowError err;
     long k = 0;
@@ -289,7 +318,7 @@ static int create_M_text(eagle_ctx* ctx, const char* fname, const char* asciifna
         const int b = (int)(k & 1);
         const long nr = std::min(chunk_rows, nlines - r0);
         char* buf = (char*)ctx->stage_pin[b];
-        if (k >= 2) HIPCHK(ctx, hipEventSynchronize(done[b]));
+        if (k >= 2) HIPCHK(ctx, hipEventSynchronize(done.e[b]));
         std::vector<RowError> terr((size_t)threads);
         parallel_for(nr, threads, [&](long a, long e, int t) {
             RowError& my = terr[(size_t)t];
@@ -326,7 +355,7 @@ static int create_M_text(eagle_ctx* ctx, const char* fname, const char* asciifna
             return failf(ctx, EAGLE_ERR_OPEN, "ERROR: could not write %s", asciifname);
         if (dev && err.row < 0) {
             HIPCHK(ctx, hipMemcpyAsync(ctx->stage_raw[b], buf, (size_t)nr * stride, hipMemcpyHostToDevice, ctx->stream));
-            HIPCHK(ctx, hipEventRecord(done[b], ctx->stream));
+            HIPCHK(ctx, hipEventRecord(done.e[b], ctx->stream));
             rc = eagle_dev_decode_ascii(ctx, (const uint8_t*)ctx->stage_raw[b], nr, L, stride, dev + r0 * ld, ld, bad.as<int>(), ctx->stream);
             if (rc) return rc;
         }
@@ -540,25 +569,13 @@ extern "C" int eagle_create_Mt_ascii(eagle_ctx* ctx, const char* f_name, const c
     HIPCHK(ctx, mt.alloc(keep ? (size_t)L_pad * ldn : (size_t)w * ldn));
     if (keep) HIPCHK(ctx, hipMemsetAsync(mt.p, 0, (size_t)L_pad * ldn, ctx->stream));
     if (!src) HIPCHK(ctx, win.alloc((size_t)n_pad * w));
-    hipEvent_t done[2] = {nullptr, nullptr};
-    for (int b = 0; b < 2; b++) HIPCHK(ctx, hipEventCreateWithFlags(&done[b], hipEventDisableTiming));
-    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int b = 0; b < 2; b++) if (e[b]) (void)hipEventDestroy(e[b]); } } evg{done};
+    EventPair done;
+    HIPCHK(ctx, done.create());
 
     SidecarWriter sc;
     (void)sc.open_for(ctx, f_name_ascii, L, n, w);
     // Window k: transpose + encode on the stream, D2H into pinned buffer k&1; the pwrite of window k-1 overlaps it.
-    long pend_c0 = -1, pend_rows = 0;
-    int pend_b = 0;
-    auto flush = [&]() -> int {
-        if (pend_c0 < 0) return EAGLE_OK;
-        hipError_t e = hipEventSynchronize(done[pend_b]);
-        if (e != hipSuccess) return eagle_fail_hip(ctx, e, "hipEventSynchronize");
-        if (!pwrite_all(fdout, (const char*)ctx->stage_pin[pend_b], (size_t)pend_rows * out_stride, (off_t)pend_c0 * out_stride, threads))
-            return failf(ctx, EAGLE_ERR_OPEN, "ERROR: could not write %s", f_name_ascii);
-        sc.write(pend_b, pend_c0, pend_rows, threads);
-        pend_c0 = -1;
-        return EAGLE_OK;
-    };
+    LinesBehind behind{ctx, fdout, f_name_ascii, out_stride, sc, done, threads};
     long k = 0;
     for (long c0 = 0; c0 < L; c0 += w, k++) {
         const int b = (int)(k & 1);
@@ -567,7 +584,7 @@ extern "C" int eagle_create_Mt_ascii(eagle_ctx* ctx, const char* f_name, const c
         long sld;
         if (src) { sp = src->dev + c0; sld = src->ld; }
         else {
-            rc = flush();  // the tile loader below uses the same staging buffers as the pending write
+            rc = behind.flush();  // the tile loader below uses the same staging buffers as the pending write
             if (rc) return rc;
             HIPCHK(ctx, hipMemsetAsync(win.p, 0, (size_t)n_pad * w, ctx->stream));
             rc = eagle_dev_load_ascii(ctx, f_name, 0, n, c0, real, win.as<int8_t>(), w, max_memory_in_Gbytes, threads);
@@ -580,17 +597,15 @@ extern "C" int eagle_create_Mt_ascii(eagle_ctx* ctx, const char* f_name, const c
         if (rc) return rc;
         rc = eagle_dev_encode_ascii(ctx, dst, real, n, ldn, (uint8_t*)ctx->stage_raw[b], ctx->stream);
         if (rc) return rc;
-        if (pend_c0 >= 0 && pend_b == b) { rc = flush(); if (rc) return rc; }
+        if (behind.b == b) { rc = behind.flush(); if (rc) return rc; }
         HIPCHK(ctx, hipMemcpyAsync(ctx->stage_pin[b], ctx->stage_raw[b], (size_t)real * out_stride, hipMemcpyDeviceToHost, ctx->stream));
         rc = sc.pack(b, dst, real, ldn);
         if (rc) return rc;
-        HIPCHK(ctx, hipEventRecord(done[b], ctx->stream));
-        const long this_c0 = c0, this_rows = real;
-        rc = flush();  // window k-1 goes to disk while window k is on the device
+        HIPCHK(ctx, hipEventRecord(done.e[b], ctx->stream));
+        rc = behind.next(c0, real, b);  // window k-1 goes to disk while window k is on the device
         if (rc) return rc;
-        pend_c0 = this_c0; pend_rows = this_rows; pend_b = b;
     }
-    rc = flush();
+    rc = behind.flush();
     if (rc) return rc;
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     say_summary(ctx, type, f_name, n, L, max_memory_in_Gbytes);
@@ -626,20 +641,9 @@ struct TextOut {
 // Lines [r0, r0 + nrows) of a text file of `cols` characters per line from the rows of an int8 image (`img`: the first of them), with their
 // sidecar rows: encode + pack on the stream into staging buffer k & 1, the pwrite of chunk k - 1 under the device work of chunk k.
 int write_lines_from_image(eagle_ctx* ctx, int fd, const char* path, const int8_t* img, long ld, long r0, long nrows, long cols, long chunk_rows,
-                           SidecarWriter& sc, hipEvent_t* done, int threads) {
+                           SidecarWriter& sc, EventPair& done, int threads) {
     const long stride = cols + 1;
-    long pend_r = -1, pend_n = 0;
-    int pend_b = 0;
-    auto flush = [&]() -> int {
-        if (pend_r < 0) return EAGLE_OK;
-        hipError_t e = hipEventSynchronize(done[pend_b]);
-        if (e != hipSuccess) return eagle_fail_hip(ctx, e, "hipEventSynchronize");
-        if (!pwrite_all(fd, (const char*)ctx->stage_pin[pend_b], (size_t)pend_n * stride, (off_t)pend_r * stride, threads))
-            return failf(ctx, EAGLE_ERR_OPEN, "ERROR: could not write %s", path);
-        sc.write(pend_b, pend_r, pend_n, threads);
-        pend_r = -1;
-        return EAGLE_OK;
-    };
+    LinesBehind behind{ctx, fd, path, stride, sc, done, threads};
     long k = 0;
     for (long r = 0; r < nrows; r += chunk_rows, k++) {
         const int b = (int)(k & 1);  // free: chunk k - 2 went to disk while chunk k - 1 was enqueued
@@ -649,39 +653,123 @@ int write_lines_from_image(eagle_ctx* ctx, int fd, const char* path, const int8_
         HIPCHK(ctx, hipMemcpyAsync(ctx->stage_pin[b], ctx->stage_raw[b], (size_t)nr * stride, hipMemcpyDeviceToHost, ctx->stream));
         rc = sc.pack(b, img + r * ld, nr, ld);
         if (rc) return rc;
-        HIPCHK(ctx, hipEventRecord(done[b], ctx->stream));
-        rc = flush();
+        HIPCHK(ctx, hipEventRecord(done.e[b], ctx->stream));
+        rc = behind.next(r0 + r, nr, b);
         if (rc) return rc;
-        pend_r = r0 + r; pend_n = nr; pend_b = b;
     }
-    return flush();
+    return behind.flush();
 }
 
-// A SNP-major .bed file of L markers of n individuals, opened and checked (header, size): *fd_out, or the call's error.
-int open_bed(eagle_ctx* ctx, const char* bed_path, long n, long L, int* fd_out) {
-    const int fdin = open(bed_path, O_RDONLY);
-    if (fdin < 0) return failf(ctx, EAGLE_ERR_OPEN, "ERROR: Could not open  %s", bed_path);
-    struct Closer { int fd; ~Closer() { if (fd >= 0) close(fd); } } closer{fdin};
-    struct stat st;
-    if (fstat(fdin, &st) != 0) return failf(ctx, EAGLE_ERR_OPEN, "ERROR: Could not open  %s", bed_path);
-    unsigned char head[BED_HEADER_BYTES];
-    const ssize_t got = pread(fdin, head, sizeof head, 0);
-    switch (bed_check_header(head, got < 0 ? 0 : (long)got)) {
-        case BED_HEADER_OK: break;
-        case BED_HEADER_INDIVIDUAL_MAJOR:
-            return failf(ctx, EAGLE_ERR_FORMAT, "%s is an individual-major .bed file (third byte 0x00); only SNP-major files are read", bed_path);
-        case BED_HEADER_MODE:
-            return failf(ctx, EAGLE_ERR_FORMAT, "%s: third byte 0x%02x is not a .bed mode (0x01 SNP-major)", bed_path, (unsigned)head[2]);
-        default:
-            return failf(ctx, EAGLE_ERR_FORMAT, "%s is not a PLINK .bed file (it does not start with 0x6c 0x1b)", bed_path);
+// The one staging ring of the .bed entry points: a SNP-major .bed file of L markers of n individuals, opened and checked (header, size),
+// whose rows go to the device in windows the caller chooses (they may overlap, or leave rows out) through the context's two pinned /
+// device staging buffers in turn.  Window k: stage() -- pread into pinned buffer k & 1, upload -- then the caller's kernels on
+// ctx->stream, then release(), which records the buffer's event behind the last operation that reads the staged rows or writes the
+// pinned buffer.  THE buffer-reuse rule lives here and nowhere else: stage() of window k waits for the event of window k - 2, i.e.
+// until window k - 2 has left staging buffer b, so the pread of window k runs under the device work of window k - 1.  A caller that
+// fails inside its window loop drains the stream before it returns: the ring's buffers belong to the context and outlive the call.
+struct BedRing {
+    eagle_ctx* ctx = nullptr;
+    const char* path = nullptr;
+    int fd = -1, threads = 1;
+    long rb = 0;            // bytes of a file row
+    size_t byte_off = 0;    // where the rows lie in a staging buffer (eagle_create_ascii_from_bed keeps a window's text in front of them)
+    long windows = 0;       // windows staged so far
+    EventPair ev;
+    ~BedRing() { if (fd >= 0) close(fd); }
+    int open(eagle_ctx* c, const char* bed_path, long n, long L) {
+        ctx = c; path = bed_path; threads = host_threads(); rb = bed_row_bytes(n);
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        fd = ::open(bed_path, O_RDONLY);
+        struct stat st;
+        if (fd < 0 || fstat(fd, &st) != 0) return failf(ctx, EAGLE_ERR_OPEN, "ERROR: Could not open  %s", bed_path);
+        unsigned char head[BED_HEADER_BYTES];
+        const ssize_t got = pread(fd, head, sizeof head, 0);
+        switch (bed_check_header(head, got < 0 ? 0 : (long)got)) {
+            case BED_HEADER_OK: break;
+            case BED_HEADER_INDIVIDUAL_MAJOR:
+                return failf(ctx, EAGLE_ERR_FORMAT, "%s is an individual-major .bed file (third byte 0x00); only SNP-major files are read", bed_path);
+            case BED_HEADER_MODE:
+                return failf(ctx, EAGLE_ERR_FORMAT, "%s: third byte 0x%02x is not a .bed mode (0x01 SNP-major)", bed_path, (unsigned)head[2]);
+            default:
+                return failf(ctx, EAGLE_ERR_FORMAT, "%s is not a PLINK .bed file (it does not start with 0x6c 0x1b)", bed_path);
+        }
+        if ((long long)st.st_size != bed_expected_size(n, L))
+            return failf(ctx, EAGLE_ERR_FORMAT, "%s holds %lld bytes, but %ld markers of %ld individuals take %lld", bed_path, (long long)st.st_size, L,
+                         n, bed_expected_size(n, L));
+        HIPCHK(ctx, ev.create());
+        return EAGLE_OK;
     }
-    if ((long long)st.st_size != bed_expected_size(n, L))
-        return failf(ctx, EAGLE_ERR_FORMAT, "%s holds %lld bytes, but %ld markers of %ld individuals take %lld", bed_path, (long long)st.st_size, L,
-                     n, bed_expected_size(n, L));
-    *fd_out = fdin;
-    closer.fd = -1;
-    return EAGLE_OK;
-}
+    // staging buffers for windows of up to rows_max rows that start byte_off bytes into a buffer
+    int ensure(long rows_max, size_t off = 0) {
+        byte_off = off;
+        return eagle_stage_ensure(ctx, off + (size_t)rows_max * rb);
+    }
+    int last() const { return (int)((windows - 1) & 1); }   // the buffer staged last
+    char* pinned(int b) const { return (char*)ctx->stage_pin[b]; }
+    uint8_t* device(int b) const { return (uint8_t*)ctx->stage_raw[b]; }
+    // file rows [f0, f0 + rows) on their way to *raw (stream order)
+    int stage(long f0, long rows, const uint8_t** raw) {
+        const int b = (int)(windows & 1);
+        if (windows >= 2) HIPCHK(ctx, hipEventSynchronize(ev.e[b]));  // window k - 2 has left staging buffer b
+        windows++;
+        if (!pread_all(fd, pinned(b) + byte_off, (size_t)rows * rb, (off_t)BED_HEADER_BYTES + (off_t)f0 * rb, threads)) {
+            (void)hipStreamSynchronize(ctx->stream);
+            return failf(ctx, EAGLE_ERR_FORMAT, "%s: could not read markers %ld to %ld", path, f0 + 1, f0 + rows);
+        }
+        HIPCHK(ctx, hipMemcpyAsync(device(b) + byte_off, pinned(b) + byte_off, (size_t)rows * rb, hipMemcpyHostToDevice, ctx->stream));
+        *raw = device(b) + byte_off;
+        return EAGLE_OK;
+    }
+    int release() {
+        HIPCHK(ctx, hipEventRecord(ev.e[last()], ctx->stream));
+        return EAGLE_OK;
+    }
+    // write-behind: until everything enqueued before release() of buffer b's last window is done
+    int wait(int b) {
+        HIPCHK(ctx, hipEventSynchronize(ev.e[b]));
+        return EAGLE_OK;
+    }
+};
+
+// Write-behind of the two imputers' output .bed file, pre-sized with its header and cut back to nothing unless the call gets as far as
+// finish().  push(): window k's patched rows are copied back into the pinned buffer they were read into (stream order: behind its
+// upload), the ring's buffer is released, and the pwrite of window k - 1 runs under the device work of window k.
+struct BedRewrite {
+    TextOut out;
+    eagle_ctx* ctx = nullptr;
+    const char* path = nullptr;
+    long held_r0 = -1, held_n = 0, rb = 0;   // the window not yet on disk (held_r0 < 0: none)
+    int held_b = 0;
+    int open(eagle_ctx* c, const char* out_bed_path, long n, long L) {
+        static const char head[BED_HEADER_BYTES] = {0x6c, 0x1b, 0x01};
+        ctx = c; path = out_bed_path; rb = bed_row_bytes(n);
+        if (!out.open_sized(path, (off_t)bed_expected_size(n, L)) || !pwrite_all(out.fd, head, sizeof head, 0, 1))
+            return failf(ctx, EAGLE_ERR_OPEN, "ERROR: Could not open  %s", path);
+        return EAGLE_OK;
+    }
+    int flush(BedRing& ring) {
+        if (held_r0 < 0) return EAGLE_OK;
+        if (int rc = ring.wait(held_b)) return rc;
+        if (!pwrite_all(out.fd, ring.pinned(held_b), (size_t)held_n * rb, (off_t)BED_HEADER_BYTES + (off_t)held_r0 * rb, ring.threads))
+            return failf(ctx, EAGLE_ERR_OPEN, "ERROR: could not write %s", path);
+        held_r0 = -1;
+        return EAGLE_OK;
+    }
+    // `patched` (device): the rows [r0, r0 + nr) of the output, made from the window staged last
+    int push(BedRing& ring, const void* patched, long r0, long nr) {
+        const int b = ring.last();
+        HIPCHK(ctx, hipMemcpyAsync(ring.pinned(b), patched, (size_t)nr * rb, hipMemcpyDeviceToHost, ctx->stream));
+        int rc = ring.release();
+        if (!rc) rc = flush(ring);
+        held_r0 = r0; held_n = nr; held_b = b;
+        return rc;
+    }
+    int finish(BedRing& ring) {
+        if (int rc = flush(ring)) return rc;
+        out.finish();
+        return EAGLE_OK;
+    }
+};
 
 }  // namespace
 
@@ -695,18 +783,17 @@ extern "C" int eagle_create_ascii_from_bed(eagle_ctx* ctx, const char* bed_path,
     if (!ctx || !bed_path || !f_name_ascii_M || !f_name_ascii_Mt || !dims) return EAGLE_ERR_ARG;
     const long n = dims[0], L = dims[1];
     if (n <= 0 || L <= 0) return eagle_fail(ctx, EAGLE_ERR_ARG, "create_ascii_from_bed: dims must be positive");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    int fdin = -1;
-    if (int orc = open_bed(ctx, bed_path, n, L, &fdin)) return orc;
-    struct Closer { int fd; ~Closer() { if (fd >= 0) close(fd); } } closer{fdin};
+    BedRing ring;
+    if (int orc = ring.open(ctx, bed_path, n, L)) return orc;
 
-    const int threads = host_threads();
-    const long rb = bed_row_bytes(n), n_pad = eagle_pad(n), ldn = n_pad, L_pad = eagle_pad(L);
+    const int threads = ring.threads;
+    const long rb = ring.rb, n_pad = eagle_pad(n), ldn = n_pad, L_pad = eagle_pad(L);
     const size_t budget = eagle_resident_budget();
     const long w = bed_window_markers(n, n_pad, L_pad, (size_t)67108864, budget), nwin = bed_window_count(w, L);
     const long mt_stride = n + 1, bed_off = ((w * mt_stride + 255) / 256) * 256;   // staging buffer: the window's text, then its bed bytes
     const long m_chunk = std::max(1L, std::min(n, (long)(67108864 / (L + 1))));
-    int rc = eagle_stage_ensure(ctx, std::max((size_t)bed_off + (size_t)w * rb, (size_t)m_chunk * (L + 1)));
+    int rc = eagle_stage_ensure(ctx, std::max((size_t)bed_off + (size_t)w * rb, (size_t)m_chunk * (L + 1)));   // one growth for both files' needs
+    if (!rc) rc = ring.ensure(w, (size_t)bed_off);
     if (rc) return rc;
     if (!quiet) { say(ctx, ""); say(ctx, " Reading PLINK binary File  "); say(ctx, ""); say(ctx, " Loading file "); }
 
@@ -716,9 +803,6 @@ extern "C" int eagle_create_ascii_from_bed(eagle_ctx* ctx, const char* bed_path,
     const bool keepM = fits_resident((size_t)n_pad * L_pad);
     const long band = keepM ? n_pad : stream_chunk_rows_core(budget, L_pad, n_pad);   // individuals per pass over the bed file
     HIPCHK(ctx, mimg.alloc((size_t)band * L_pad));
-    hipEvent_t done[2] = {nullptr, nullptr};
-    for (int b = 0; b < 2; b++) HIPCHK(ctx, hipEventCreateWithFlags(&done[b], hipEventDisableTiming));
-    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int b = 0; b < 2; b++) if (e[b]) (void)hipEventDestroy(e[b]); } } evg{done};
     unsigned long long* d_missing = (unsigned long long*)((char*)eagle_ctx_scratch(ctx) + EAGLE_SCR_INGEST);
     HIPCHK(ctx, hipMemsetAsync(d_missing, 0, sizeof(unsigned long long), ctx->stream));
 
@@ -734,60 +818,42 @@ extern "C" int eagle_create_ascii_from_bed(eagle_ctx* ctx, const char* bed_path,
         const bool first = r0 == 0;                       // the pass that writes Mt.ascii
         const bool decode = first || !keepMt;             // later passes find the tiles in Mt's resident image
         const long bcols = std::min(band, n_pad - r0);    // individuals (padded) of this pass's image of M
-        long pend_c0 = -1, pend_rows = 0;
-        int pend_b = 0;
-        auto flush = [&]() -> int {
-            if (pend_c0 < 0) return EAGLE_OK;
-            hipError_t e = hipEventSynchronize(done[pend_b]);
-            if (e != hipSuccess) return eagle_fail_hip(ctx, e, "hipEventSynchronize");
-            if (!pwrite_all(outMt.fd, (const char*)ctx->stage_pin[pend_b], (size_t)pend_rows * mt_stride, (off_t)pend_c0 * mt_stride, threads))
-                return failf(ctx, EAGLE_ERR_OPEN, "ERROR: could not write %s", f_name_ascii_Mt);
-            scMt.write(pend_b, pend_c0, pend_rows, threads);
-            pend_c0 = -1;
-            return EAGLE_OK;
-        };
+        LinesBehind behind{ctx, outMt.fd, f_name_ascii_Mt, mt_stride, scMt, ring.ev, threads};
         for (long k = 0; k < nwin; k++) {
-            const int b = (int)(k & 1);
             const BedWindow bw = bed_window(k, w, L, L_pad);
             int8_t* tile = mt.as<int8_t>() + (keepMt ? bw.c0 * ldn : 0);
+            rc = EAGLE_OK;
             if (decode) {
-                if (k >= 2) HIPCHK(ctx, hipEventSynchronize(done[b]));  // window k - 2 has left staging buffer b
-                char* pin = (char*)ctx->stage_pin[b] + bed_off;
-                uint8_t* raw = (uint8_t*)ctx->stage_raw[b] + bed_off;
-                if (!pread_all(fdin, pin, (size_t)bw.real * rb, (off_t)BED_HEADER_BYTES + (off_t)bw.c0 * rb, threads))
-                    return failf(ctx, EAGLE_ERR_FORMAT, "%s: could not read markers %ld to %ld", bed_path, bw.c0 + 1, bw.c0 + bw.real);
-                HIPCHK(ctx, hipMemcpyAsync(raw, pin, (size_t)bw.real * rb, hipMemcpyHostToDevice, ctx->stream));
-                rc = eagle_dev_bed_decode(ctx, raw, bw.real, bw.padded, n, tile, ldn, first ? scMt.packed(b) : nullptr, scMt.row_bytes,
-                                          first ? d_missing : nullptr, ctx->stream);
-                if (rc) return rc;
+                const uint8_t* raw;
+                rc = ring.stage(bw.c0, bw.real, &raw);
+                if (!rc) rc = eagle_dev_bed_decode(ctx, raw, bw.real, bw.padded, n, tile, ldn, first ? scMt.packed(ring.last()) : nullptr,
+                                                   scMt.row_bytes, first ? d_missing : nullptr, ctx->stream);
             }
-            rc = eagle_dev_transpose_i8(ctx, tile + r0, bw.padded, bcols, ldn, mimg.as<int8_t>() + bw.c0, L_pad, ctx->stream);
-            if (rc) return rc;
-            if (first) {
-                rc = eagle_dev_encode_ascii(ctx, tile, bw.real, n, ldn, (uint8_t*)ctx->stage_raw[b], ctx->stream);
-                if (rc) return rc;
-                HIPCHK(ctx, hipMemcpyAsync(ctx->stage_pin[b], ctx->stage_raw[b], (size_t)bw.real * mt_stride, hipMemcpyDeviceToHost, ctx->stream));
-                rc = scMt.fetch(b, bw.real);
-                if (rc) return rc;
+            if (!rc) rc = eagle_dev_transpose_i8(ctx, tile + r0, bw.padded, bcols, ldn, mimg.as<int8_t>() + bw.c0, L_pad, ctx->stream);
+            if (!rc && first) {   // the window's text: encoded in front of its bed bytes, in the buffer they were staged in
+                const int b = ring.last();
+                rc = eagle_dev_encode_ascii(ctx, tile, bw.real, n, ldn, ring.device(b), ctx->stream);
+                if (!rc) {
+                    const hipError_t e = hipMemcpyAsync(ring.pinned(b), ring.device(b), (size_t)bw.real * mt_stride, hipMemcpyDeviceToHost, ctx->stream);
+                    if (e != hipSuccess) rc = eagle_fail_hip(ctx, e, "hipMemcpyAsync");
+                }
+                if (!rc) rc = scMt.fetch(b, bw.real);
             }
-            HIPCHK(ctx, hipEventRecord(done[b], ctx->stream));
-            if (first) {
-                rc = flush();  // window k - 1 goes to disk while window k is on the device
-                if (rc) return rc;
-                pend_c0 = bw.c0; pend_rows = bw.real; pend_b = b;
-            }
+            if (!rc && decode) rc = ring.release();
+            if (!rc && first) rc = behind.next(bw.c0, bw.real, ring.last());  // window k - 1 goes to disk while window k is on the device
+            if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
         }
         if (first) {
-            rc = flush();
-            if (rc) return rc;
+            rc = behind.flush();
+            if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
             HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
             HIPCHK(ctx, hipMemcpy(&n_missing, d_missing, sizeof n_missing, hipMemcpyDeviceToHost));
             if (n_missing) say_missing_alleles(ctx);
             outMt.finish();  // Mt.ascii is final: its size and mtime key the sidecar and the cache entry
             scMt.finish(f_name_ascii_Mt);
         }
-        rc = write_lines_from_image(ctx, outM.fd, f_name_ascii_M, mimg.as<int8_t>(), L_pad, r0, std::min(band, n - r0), L, m_chunk, scM, done, threads);
-        if (rc) return rc;
+        rc = write_lines_from_image(ctx, outM.fd, f_name_ascii_M, mimg.as<int8_t>(), L_pad, r0, std::min(band, n - r0), L, m_chunk, scM, ring.ev, threads);
+        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
     }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     if (n_missing_out) *n_missing_out = (long)n_missing;
@@ -863,43 +929,27 @@ extern "C" int eagle_marker_counts(eagle_ctx* ctx, const char* f_name_ascii_Mt, 
     return line_counts(ctx, f_name_ascii_Mt, n, L, max_memory_in_Gbytes, counts_out);
 }
 
-// The rows go through the pinned staging ring in windows of up to 64 MiB, as eagle_create_ascii_from_bed reads them: the pread of
-// window k + 1 runs under the copy and the kernel of window k.
+// The rows go through the staging ring (BedRing) in windows of bed_stage_rows: up to 64 MiB.
 extern "C" int eagle_bed_marker_counts(eagle_ctx* ctx, const char* bed_path, const long dims[2], double max_memory_in_Gbytes,
                                        int32_t* counts_out) {
     if (!bed_path || !dims || !counts_out) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_marker_counts: NULL argument");
     const long n = dims[0], L = dims[1];
     if (n <= 0 || L <= 0) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_marker_counts: dims must be positive");
     if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_marker_counts: no context");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    int fdin = -1;
-    if (int orc = open_bed(ctx, bed_path, n, L, &fdin)) return orc;
-    struct Closer { int fd; ~Closer() { if (fd >= 0) close(fd); } } closer{fdin};
-    const int threads = host_threads();
-    const long rb = bed_row_bytes(n);
-    double cap = 67108864.0;
-    if (max_memory_in_Gbytes > 0) cap = std::min(cap, max_memory_in_Gbytes * 1e9 / 4.0);  // the loaders' staging rule
-    const long w = std::max(1L, std::min(L, (long)cap / rb));
-    int rc = eagle_stage_ensure(ctx, (size_t)w * rb);
+    BedRing ring;
+    if (int orc = ring.open(ctx, bed_path, n, L)) return orc;
+    const long w = std::min(L, bed_stage_rows(ring.rb, max_memory_in_Gbytes));
+    int rc = ring.ensure(w);
     if (rc) return rc;
     DevBuf counts;
     HIPCHK(ctx, counts.alloc(sizeof(int32_t) * 4 * (size_t)L));
-    hipEvent_t done[2] = {nullptr, nullptr};
-    for (int b = 0; b < 2; b++) HIPCHK(ctx, hipEventCreateWithFlags(&done[b], hipEventDisableTiming));
-    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int b = 0; b < 2; b++) if (e[b]) (void)hipEventDestroy(e[b]); } } evg{done};
-    long k = 0;
-    for (long r0 = 0; r0 < L; r0 += w, k++) {
-        const int b = (int)(k & 1);
+    for (long r0 = 0; r0 < L; r0 += w) {
         const long nr = std::min(w, L - r0);
-        if (k >= 2) HIPCHK(ctx, hipEventSynchronize(done[b]));  // window k - 2 has left staging buffer b
-        if (!pread_all(fdin, (char*)ctx->stage_pin[b], (size_t)nr * rb, (off_t)BED_HEADER_BYTES + (off_t)r0 * rb, threads)) {
-            (void)hipStreamSynchronize(ctx->stream);
-            return failf(ctx, EAGLE_ERR_FORMAT, "%s: could not read markers %ld to %ld", bed_path, r0 + 1, r0 + nr);
-        }
-        HIPCHK(ctx, hipMemcpyAsync(ctx->stage_raw[b], ctx->stage_pin[b], (size_t)nr * rb, hipMemcpyHostToDevice, ctx->stream));
-        rc = eagle_dev_bed_marker_counts(ctx, (const uint8_t*)ctx->stage_raw[b], nr, n, counts.as<int32_t>() + 4 * r0, ctx->stream);
+        const uint8_t* raw;
+        rc = ring.stage(r0, nr, &raw);
+        if (!rc) rc = eagle_dev_bed_marker_counts(ctx, raw, nr, n, counts.as<int32_t>() + 4 * r0, ctx->stream);
+        if (!rc) rc = ring.release();
         if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-        HIPCHK(ctx, hipEventRecord(done[b], ctx->stream));
     }
     HIPCHK(ctx, hipMemcpyAsync(counts_out, counts.p, sizeof(int32_t) * 4 * (size_t)L, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -930,9 +980,8 @@ extern "C" int eagle_knn_rows(eagle_ctx* ctx, const int32_t* ibs0, const int32_t
     return EAGLE_OK;
 }
 
-// The windows of eagle_bed_marker_counts through the same staging ring.  Window k: pread into pinned buffer k & 1, copy to the device,
-// count (the fallback genotypes), patch into `patched`, copy back into the SAME pinned buffer (stream order: behind its upload); the
-// pwrite of window k - 1 runs under the device work of window k.
+// The windows of eagle_bed_marker_counts through the staging ring, with BedRewrite's write-behind.  Window k: count (the fallback
+// genotypes), patch into `patched`.
 extern "C" int eagle_bed_impute_knn(eagle_ctx* ctx, const char* bed_path, const long dims[2], const int32_t* nbr, int K, int k, int min_votes,
                                     const char* out_bed_path, double max_memory_in_Gbytes, int32_t* counts_out) {
     if (!bed_path || !dims || !nbr || !out_bed_path) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_impute_knn: NULL argument");
@@ -947,16 +996,10 @@ extern "C" int eagle_bed_impute_knn(eagle_ctx* ctx, const char* bed_path, const 
     for (size_t i = 0; i < nn; i++)
         if (nbr[i] < -1 || nbr[i] >= n) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_impute_knn: a neighbour outside [-1, n)");
     if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_impute_knn: no context");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    int fdin = -1;
-    if (int orc = open_bed(ctx, bed_path, n, L, &fdin)) return orc;
-    struct Closer { int fd; ~Closer() { if (fd >= 0) close(fd); } } closer{fdin};
-    const int threads = host_threads();
-    const long rb = bed_row_bytes(n);
-    double cap = 67108864.0;
-    if (max_memory_in_Gbytes > 0) cap = std::min(cap, max_memory_in_Gbytes * 1e9 / 4.0);  // the loaders' staging rule
-    const long w = std::max(1L, std::min(L, (long)cap / rb));
-    int rc = eagle_stage_ensure(ctx, (size_t)w * rb);
+    BedRing ring;
+    if (int orc = ring.open(ctx, bed_path, n, L)) return orc;
+    const long rb = ring.rb, w = std::min(L, bed_stage_rows(rb, max_memory_in_Gbytes));
+    int rc = ring.ensure(w);
     if (rc) return rc;
     DevBuf d_nbr, mcounts, counts, patched;
     HIPCHK(ctx, d_nbr.alloc(sizeof(int32_t) * nn));
@@ -964,50 +1007,21 @@ extern "C" int eagle_bed_impute_knn(eagle_ctx* ctx, const char* bed_path, const 
     HIPCHK(ctx, counts.alloc(sizeof(int32_t) * 2 * (size_t)L));
     HIPCHK(ctx, patched.alloc((size_t)w * rb));
     HIPCHK(ctx, hipMemcpyAsync(d_nbr.p, nbr, sizeof(int32_t) * nn, hipMemcpyHostToDevice, ctx->stream));
-    hipEvent_t done[2] = {nullptr, nullptr};
-    for (int b = 0; b < 2; b++) HIPCHK(ctx, hipEventCreateWithFlags(&done[b], hipEventDisableTiming));
-    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int b = 0; b < 2; b++) if (e[b]) (void)hipEventDestroy(e[b]); } } evg{done};
-    TextOut out;   // cut back to nothing unless the call gets as far as finish()
-    static const char head[BED_HEADER_BYTES] = {0x6c, 0x1b, 0x01};
-    if (!out.open_sized(out_bed_path, (off_t)bed_expected_size(n, L)) || !pwrite_all(out.fd, head, sizeof head, 0, 1))
-        return failf(ctx, EAGLE_ERR_OPEN, "ERROR: Could not open  %s", out_bed_path);
-    long pend_r = -1, pend_n = 0;
-    int pend_b = 0;
-    auto flush = [&]() -> int {
-        if (pend_r < 0) return EAGLE_OK;
-        hipError_t e = hipEventSynchronize(done[pend_b]);
-        if (e != hipSuccess) return eagle_fail_hip(ctx, e, "hipEventSynchronize");
-        if (!pwrite_all(out.fd, (const char*)ctx->stage_pin[pend_b], (size_t)pend_n * rb, (off_t)BED_HEADER_BYTES + (off_t)pend_r * rb, threads))
-            return failf(ctx, EAGLE_ERR_OPEN, "ERROR: could not write %s", out_bed_path);
-        pend_r = -1;
-        return EAGLE_OK;
-    };
-    long wk = 0;
-    for (long r0 = 0; r0 < L; r0 += w, wk++) {
-        const int b = (int)(wk & 1);  // free: window wk - 2 went to disk while window wk - 1 was enqueued
+    BedRewrite out;
+    if (int orc = out.open(ctx, out_bed_path, n, L)) return orc;
+    for (long r0 = 0; r0 < L; r0 += w) {
         const long nr = std::min(w, L - r0);
-        if (!pread_all(fdin, (char*)ctx->stage_pin[b], (size_t)nr * rb, (off_t)BED_HEADER_BYTES + (off_t)r0 * rb, threads)) {
-            (void)hipStreamSynchronize(ctx->stream);
-            return failf(ctx, EAGLE_ERR_FORMAT, "%s: could not read markers %ld to %ld", bed_path, r0 + 1, r0 + nr);
-        }
-        const uint8_t* raw = (const uint8_t*)ctx->stage_raw[b];
-        HIPCHK(ctx, hipMemcpyAsync(ctx->stage_raw[b], ctx->stage_pin[b], (size_t)nr * rb, hipMemcpyHostToDevice, ctx->stream));
-        rc = eagle_dev_bed_marker_counts(ctx, raw, nr, n, mcounts.as<int32_t>(), ctx->stream);
+        const uint8_t* raw;
+        rc = ring.stage(r0, nr, &raw);
+        if (!rc) rc = eagle_dev_bed_marker_counts(ctx, raw, nr, n, mcounts.as<int32_t>(), ctx->stream);
         if (!rc) rc = eagle_dev_bed_impute(ctx, raw, nr, n, d_nbr.as<int32_t>(), K, k, min_votes, mcounts.as<int32_t>(), patched.as<uint8_t>(),
                                            counts.as<int32_t>() + 2 * r0, ctx->stream);
+        if (!rc) rc = out.push(ring, patched.p, r0, nr);
         if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-        HIPCHK(ctx, hipMemcpyAsync(ctx->stage_pin[b], patched.p, (size_t)nr * rb, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipEventRecord(done[b], ctx->stream));
-        rc = flush();
-        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-        pend_r = r0; pend_n = nr; pend_b = b;
     }
-    rc = flush();
-    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
     if (counts_out) HIPCHK(ctx, hipMemcpyAsync(counts_out, counts.p, sizeof(int32_t) * 2 * (size_t)L, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    out.finish();
-    return EAGLE_OK;
+    return out.finish(ring);
 }
 
 // LD-kNNi (kernel in eagle_ldknn.hip).  The ring and the write-behind of eagle_bed_impute_knn; the rows staged for window [r0, r0 + nr) are
@@ -1033,17 +1047,10 @@ extern "C" int eagle_bed_impute_ldknn(eagle_ctx* ctx, const char* bed_path, cons
                 return qc_fail(ctx, EAGLE_ERR_ARG, "bed_impute_ldknn: a partner more than 256 rows from its marker");
         }
     if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_impute_ldknn: no context");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    int fdin = -1;
-    if (int orc = open_bed(ctx, bed_path, n, L, &fdin)) return orc;
-    struct Closer { int fd; ~Closer() { if (fd >= 0) close(fd); } } closer{fdin};
-    const int threads = host_threads();
-    const long rb = bed_row_bytes(n);
-    double cap = 67108864.0;
-    if (max_memory_in_Gbytes > 0) cap = std::min(cap, max_memory_in_Gbytes * 1e9 / 4.0);  // the loaders' staging rule
-    const long w = std::max(1L, std::min(L, (long)cap / rb));
-    const long wmax = std::min(L, w + 2 * LDKNN_HALO);                                     // rows staged for a window, at most
-    int rc = eagle_stage_ensure(ctx, (size_t)wmax * rb);
+    BedRing ring;
+    if (int orc = ring.open(ctx, bed_path, n, L)) return orc;
+    const long rb = ring.rb, w = std::min(L, bed_stage_rows(rb, max_memory_in_Gbytes));
+    int rc = ring.ensure(std::min(L, w + 2 * LDKNN_HALO));   // rows staged for a window, at most
     if (rc) return rc;
     const size_t np = (size_t)L * (size_t)l;
     DevBuf d_part, mcounts, counts, patched;
@@ -1052,51 +1059,22 @@ extern "C" int eagle_bed_impute_ldknn(eagle_ctx* ctx, const char* bed_path, cons
     HIPCHK(ctx, counts.alloc(sizeof(int32_t) * 2 * (size_t)L));
     HIPCHK(ctx, patched.alloc((size_t)w * rb));
     HIPCHK(ctx, hipMemcpyAsync(d_part.p, partners, sizeof(int32_t) * np, hipMemcpyHostToDevice, ctx->stream));
-    hipEvent_t done[2] = {nullptr, nullptr};
-    for (int b = 0; b < 2; b++) HIPCHK(ctx, hipEventCreateWithFlags(&done[b], hipEventDisableTiming));
-    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int b = 0; b < 2; b++) if (e[b]) (void)hipEventDestroy(e[b]); } } evg{done};
-    TextOut out;   // cut back to nothing unless the call gets as far as finish()
-    static const char head[BED_HEADER_BYTES] = {0x6c, 0x1b, 0x01};
-    if (!out.open_sized(out_bed_path, (off_t)bed_expected_size(n, L)) || !pwrite_all(out.fd, head, sizeof head, 0, 1))
-        return failf(ctx, EAGLE_ERR_OPEN, "ERROR: Could not open  %s", out_bed_path);
-    long pend_r = -1, pend_n = 0;
-    int pend_b = 0;
-    auto flush = [&]() -> int {
-        if (pend_r < 0) return EAGLE_OK;
-        hipError_t e = hipEventSynchronize(done[pend_b]);
-        if (e != hipSuccess) return eagle_fail_hip(ctx, e, "hipEventSynchronize");
-        if (!pwrite_all(out.fd, (const char*)ctx->stage_pin[pend_b], (size_t)pend_n * rb, (off_t)BED_HEADER_BYTES + (off_t)pend_r * rb, threads))
-            return failf(ctx, EAGLE_ERR_OPEN, "ERROR: could not write %s", out_bed_path);
-        pend_r = -1;
-        return EAGLE_OK;
-    };
-    long wk = 0;
-    for (long r0 = 0; r0 < L; r0 += w, wk++) {
-        const int b = (int)(wk & 1);  // free: window wk - 2 went to disk while window wk - 1 was enqueued
+    BedRewrite out;
+    if (int orc = out.open(ctx, out_bed_path, n, L)) return orc;
+    for (long r0 = 0; r0 < L; r0 += w) {
         const long nr = std::min(w, L - r0);
         const long h_lo = std::max(0L, r0 - LDKNN_HALO), h_hi = std::min(L, r0 + nr + LDKNN_HALO), staged = h_hi - h_lo;
-        if (!pread_all(fdin, (char*)ctx->stage_pin[b], (size_t)staged * rb, (off_t)BED_HEADER_BYTES + (off_t)h_lo * rb, threads)) {
-            (void)hipStreamSynchronize(ctx->stream);
-            return failf(ctx, EAGLE_ERR_FORMAT, "%s: could not read markers %ld to %ld", bed_path, h_lo + 1, h_hi);
-        }
-        const uint8_t* raw = (const uint8_t*)ctx->stage_raw[b];
-        HIPCHK(ctx, hipMemcpyAsync(ctx->stage_raw[b], ctx->stage_pin[b], (size_t)staged * rb, hipMemcpyHostToDevice, ctx->stream));
-        rc = eagle_dev_bed_marker_counts(ctx, raw + (r0 - h_lo) * rb, nr, n, mcounts.as<int32_t>(), ctx->stream);
+        const uint8_t* raw;
+        rc = ring.stage(h_lo, staged, &raw);
+        if (!rc) rc = eagle_dev_bed_marker_counts(ctx, raw + (r0 - h_lo) * rb, nr, n, mcounts.as<int32_t>(), ctx->stream);
         if (!rc) rc = eagle_dev_bed_impute_ldknn(ctx, raw, staged, r0 - h_lo, nr, r0, h_lo, n, d_part.as<int32_t>(), l, k, min_votes, min_overlap,
                                                  mcounts.as<int32_t>(), patched.as<uint8_t>(), counts.as<int32_t>() + 2 * r0, ctx->stream);
+        if (!rc) rc = out.push(ring, patched.p, r0, nr);
         if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-        HIPCHK(ctx, hipMemcpyAsync(ctx->stage_pin[b], patched.p, (size_t)nr * rb, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipEventRecord(done[b], ctx->stream));
-        rc = flush();
-        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-        pend_r = r0; pend_n = nr; pend_b = b;
     }
-    rc = flush();
-    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
     if (counts_out) HIPCHK(ctx, hipMemcpyAsync(counts_out, counts.p, sizeof(int32_t) * 2 * (size_t)L, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    out.finish();
-    return EAGLE_OK;
+    return out.finish(ring);
 }
 
 namespace {
@@ -1111,9 +1089,8 @@ int filter_write(eagle_ctx* ctx, const char* path, long rows, long cols, long ro
     if (rc) return rc;
     DevBuf img;
     HIPCHK(ctx, img.alloc((size_t)(keep ? rows_pad : band) * ld));
-    hipEvent_t done[2] = {nullptr, nullptr};
-    for (int b = 0; b < 2; b++) HIPCHK(ctx, hipEventCreateWithFlags(&done[b], hipEventDisableTiming));
-    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int b = 0; b < 2; b++) if (e[b]) (void)hipEventDestroy(e[b]); } } evg{done};
+    EventPair done;
+    HIPCHK(ctx, done.create());
     TextOut out;
     if (!out.open_sized(path, (off_t)rows * (cols + 1))) return failf(ctx, EAGLE_ERR_OPEN, "ERROR: Could not open  %s", path);
     SidecarWriter sc;
@@ -1443,67 +1420,60 @@ extern "C" int eagle_ld_stats(eagle_ctx* ctx, const char* f_name_ascii_Mt, const
 // ---------------------------------------------------------------------------------------------------------------
 namespace {
 
-// The panel of a call (the included markers of the file, in file order), the window rule of the header, and the staging of one window:
-// the span of file rows that holds the panel markers [lo, hi) goes through pinned buffer b to the device, and k_bed_ld_pack writes
-// the three operand images of those markers.
-struct BedLdPanel {
-    eagle_ctx* ctx = nullptr;
-    const char* path = nullptr;
-    int fd = -1, threads = 1;
-    long n = 0, L = 0, linc = 0, rb = 0, ld = 0;
+// The panel of a call (the included markers of the file, in file order) on the staging ring: the window rule of the header, and the
+// staging of one window -- the span of file rows that holds the panel markers [lo, hi) goes through the ring to the device, with the
+// offsets of its panel markers' rows when include left rows out.  The caller's kernels read the span, then the caller calls release().
+struct BedPanel {
+    BedRing ring;
+    long n = 0, linc = 0;
     long S = 0;      // file rows the staging budget holds
     long wmax = 0;   // panel markers of a window, at most
     std::vector<long> fidx;   // panel marker -> file row; empty: the identity
     std::vector<long> offs[2];
-    DevBuf d_offs[2], X, C, U;
-    hipEvent_t done[2] = {nullptr, nullptr};
-    long windows = 0;
-    bool pack = true;               // false (eagle_bed_roh): no operand images; the caller works on the staged rows and calls release()
-    const uint8_t* raw = nullptr;   // the rows staged last, and their offsets (null: the identity)
-    const long* raw_off = nullptr;
-    ~BedLdPanel() {
-        for (int b = 0; b < 2; b++) if (done[b]) (void)hipEventDestroy(done[b]);
-        if (fd >= 0) close(fd);
-    }
-    long file_row(long p) const { return fidx.empty() ? p : fidx[(size_t)p]; }
-    // the end of the window that starts at panel marker lo: as many markers as wmax and the staging budget allow, never fewer than
-    // `need` (what the call needs to advance), never beyond the panel
-    long window_end(long lo, long need) const {
-        const long floor_hi = std::min(linc, lo + need);
-        long hi = std::min(linc, lo + wmax);
-        if (fidx.empty()) hi = std::min(hi, lo + S);
-        else hi = (long)(std::upper_bound(fidx.begin() + lo, fidx.begin() + hi, fidx[(size_t)lo] + S - 1) - fidx.begin());
-        return std::max(hi, floor_hi);
-    }
-    int stage(long lo, long hi) {
-        const int b = (int)(windows & 1);
-        if (windows >= 2) HIPCHK(ctx, hipEventSynchronize(done[b]));  // window - 2 has left staging buffer b and its offsets
-        windows++;
-        const long f0 = file_row(lo), span = file_row(hi - 1) - f0 + 1, P = hi - lo;
-        if (!pread_all(fd, (char*)ctx->stage_pin[b], (size_t)span * rb, (off_t)BED_HEADER_BYTES + (off_t)f0 * rb, threads)) {
-            (void)hipStreamSynchronize(ctx->stream);
-            return failf(ctx, EAGLE_ERR_FORMAT, "%s: could not read markers %ld to %ld", path, f0 + 1, f0 + span);
+    DevBuf d_offs[2];
+    long file_row(long p) const { return bed_panel_file_row(fidx, p); }
+    long window_end(long lo, long need) const { return bed_panel_window_end(lo, need, wmax, S, linc, fidx); }
+    // Opens the file and sizes everything a call needs; band_rows_max caps the window further (the partners call's band), 0 = no cap.
+    // need = the markers a window must hold for the call to advance; next_of(hi) = the start of the window after one that ends at hi, or
+    // linc when that was the last one.  The caller walks the same windows again: they are a function of the arguments alone.
+    template <class Next>
+    int open(eagle_ctx* ctx, const char* bed_path, long n_, long L, const uint8_t* include, long linc_, double mem_gb, long band_rows_max, long need,
+             Next next_of) {
+        n = n_; linc = linc_;
+        if (int orc = ring.open(ctx, bed_path, n, L)) return orc;
+        S = bed_stage_rows(ring.rb, mem_gb);
+        wmax = std::max(1024L, (long)(((size_t)1 << 27) / (size_t)ld()));   // one operand image of the LD calls stays under 128 MiB
+        if (band_rows_max > 0) wmax = std::min(wmax, band_rows_max);
+        if (include) {
+            fidx.reserve((size_t)linc);
+            for (long m = 0; m < L; m++) if (include[m]) fidx.push_back(m);
         }
-        HIPCHK(ctx, hipMemcpyAsync(ctx->stage_raw[b], ctx->stage_pin[b], (size_t)span * rb, hipMemcpyHostToDevice, ctx->stream));
-        const long* d_off = nullptr;
-        if (!fidx.empty()) {
-            offs[b].resize((size_t)P);
-            for (long p = 0; p < P; p++) offs[b][(size_t)p] = fidx[(size_t)(lo + p)] - f0;   // in [0, span): fidx increases
-            HIPCHK(ctx, hipMemcpyAsync(d_offs[b].p, offs[b].data(), sizeof(long) * (size_t)P, hipMemcpyHostToDevice, ctx->stream));
-            d_off = d_offs[b].as<long>();
+        long span_max = 1, p_max = 1;
+        for (long lo = 0; lo < linc;) {
+            const long hi = window_end(lo, need);
+            span_max = std::max(span_max, file_row(hi - 1) - file_row(lo) + 1);
+            p_max = std::max(p_max, hi - lo);
+            lo = next_of(hi);
         }
-        raw = (const uint8_t*)ctx->stage_raw[b];
-        raw_off = d_off;
-        if (!pack) return EAGLE_OK;
-        int rc = eagle_dev_bed_ld_pack(ctx, (const uint8_t*)ctx->stage_raw[b], span, d_off, P, n, ld, X.as<int8_t>(), C.as<int8_t>(), U.as<int8_t>(),
-                                       ctx->stream);
-        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-        HIPCHK(ctx, hipEventRecord(done[b], ctx->stream));            // the staging buffer is free once the pack has read it
+        int rc = ring.ensure(span_max);
+        if (rc) return rc;
+        if (include) for (int b = 0; b < 2; b++) HIPCHK(ctx, d_offs[b].alloc(sizeof(long) * (size_t)p_max));
+        wmax = std::min(wmax, p_max);
         return EAGLE_OK;
     }
-    // pack == false: the kernels that read the rows staged last have been launched
-    int release() {
-        HIPCHK(ctx, hipEventRecord(done[(int)((windows - 1) & 1)], ctx->stream));
+    long ld() const { return (n + 15) / 16 * 16; }   // leading dimension of the LD calls' operand images
+    // *raw: the staged span, whose row 0 is the file row of panel marker lo; *d_off: the rows of the markers [lo, hi) in it (null: the identity)
+    int stage(long lo, long hi, const uint8_t** raw, const long** d_off) {
+        const long f0 = file_row(lo), P = hi - lo;
+        if (int rc = ring.stage(f0, file_row(hi - 1) - f0 + 1, raw)) return rc;
+        *d_off = nullptr;
+        if (!fidx.empty()) {
+            const int b = ring.last();   // the offsets of window k - 2 left with its rows
+            offs[b].resize((size_t)P);
+            for (long p = 0; p < P; p++) offs[b][(size_t)p] = fidx[(size_t)(lo + p)] - f0;   // in [0, span): fidx increases
+            HIPCHK(ring.ctx, hipMemcpyAsync(d_offs[b].p, offs[b].data(), sizeof(long) * (size_t)P, hipMemcpyHostToDevice, ring.ctx->stream));
+            *d_off = d_offs[b].as<long>();
+        }
         return EAGLE_OK;
     }
 };
@@ -1516,46 +1486,23 @@ long bedld_count(const uint8_t* include, long L) {
     return c;
 }
 
-// Opens the file and sizes everything a call needs; band_rows_max caps the window further (the partners call's band), 0 = no cap.
-// need = the markers a window must hold for the call to advance; next_of(hi) = the start of the window after one that ends at hi, or
-// linc when that was the last one.  The caller walks the same windows again: they are a function of the arguments alone.
-template <class Next>
-int bedld_open(BedLdPanel& pl, eagle_ctx* ctx, const char* bed_path, long n, long L, const uint8_t* include, long linc, double mem_gb,
-               long band_rows_max, long need, Next next_of) {
-    pl.ctx = ctx; pl.path = bed_path; pl.n = n; pl.L = L; pl.linc = linc;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (int orc = open_bed(ctx, bed_path, n, L, &pl.fd)) return orc;
-    pl.threads = host_threads();
-    pl.rb = bed_row_bytes(n);
-    pl.ld = (n + 15) / 16 * 16;
-    double cap = 67108864.0;
-    if (mem_gb > 0) cap = std::min(cap, mem_gb * 1e9 / 4.0);  // the loaders' staging rule
-    pl.S = std::max(1L, (long)cap / pl.rb);
-    pl.wmax = std::max(1024L, (long)(((size_t)1 << 27) / (size_t)pl.ld));   // one operand image stays under 128 MiB
-    if (band_rows_max > 0) pl.wmax = std::min(pl.wmax, band_rows_max);
-    if (include) {
-        pl.fidx.reserve((size_t)linc);
-        for (long m = 0; m < L; m++) if (include[m]) pl.fidx.push_back(m);
+// The three marker-major operand images of the two LD calls: k_bed_ld_pack writes those of a window's panel markers from the staged
+// span, which is free once the pack has read it.
+struct BedLdOperands {
+    DevBuf X, C, U;
+    int alloc(eagle_ctx* ctx, const BedPanel& pl) {
+        for (DevBuf* d : {&X, &C, &U}) HIPCHK(ctx, d->alloc((size_t)pl.wmax * pl.ld()));
+        return EAGLE_OK;
     }
-    long span_max = 1, p_max = 1;
-    for (long lo = 0; lo < linc;) {
-        const long hi = pl.window_end(lo, need);
-        span_max = std::max(span_max, pl.file_row(hi - 1) - pl.file_row(lo) + 1);
-        p_max = std::max(p_max, hi - lo);
-        lo = next_of(hi);
+    int stage(BedPanel& pl, long lo, long hi) {
+        const uint8_t* raw;
+        const long* d_off;
+        int rc = pl.stage(lo, hi, &raw, &d_off);
+        if (!rc) rc = eagle_dev_bed_ld_pack(pl.ring.ctx, raw, pl.file_row(hi - 1) - pl.file_row(lo) + 1, d_off, hi - lo, pl.n, pl.ld(), X.as<int8_t>(),
+                                            C.as<int8_t>(), U.as<int8_t>(), pl.ring.ctx->stream);
+        return rc ? rc : pl.ring.release();
     }
-    int rc = eagle_stage_ensure(ctx, (size_t)span_max * pl.rb);
-    if (rc) return rc;
-    if (pl.pack) {
-        HIPCHK(ctx, pl.X.alloc((size_t)p_max * pl.ld));
-        HIPCHK(ctx, pl.C.alloc((size_t)p_max * pl.ld));
-        HIPCHK(ctx, pl.U.alloc((size_t)p_max * pl.ld));
-    }
-    if (include) for (int b = 0; b < 2; b++) HIPCHK(ctx, pl.d_offs[b].alloc(sizeof(long) * (size_t)p_max));
-    for (int b = 0; b < 2; b++) HIPCHK(ctx, hipEventCreateWithFlags(&pl.done[b], hipEventDisableTiming));
-    pl.wmax = std::min(pl.wmax, p_max);
-    return EAGLE_OK;
-}
+};
 
 }  // namespace
 
@@ -1574,10 +1521,12 @@ extern "C" int eagle_bed_ld_window(eagle_ctx* ctx, const char* bed_path, const l
     const long linc = bedld_count(include, L);
     if (linc < 1) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_ld_window: include selects no marker");
     if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_ld_window: no context");
-    BedLdPanel pl;
+    BedPanel pl;
+    BedLdOperands op;
     const long need = window + 1;
     auto next_of = [&](long hi) { return hi >= linc ? linc : hi - window; };
-    int rc = bedld_open(pl, ctx, bed_path, n, L, include, linc, max_memory_in_Gbytes, 0, need, next_of);
+    int rc = pl.open(ctx, bed_path, n, L, include, linc, max_memory_in_Gbytes, 0, need, next_of);
+    if (!rc) rc = op.alloc(ctx, pl);
     if (rc) return rc;
     const long wpr = (window + 63) / 64;
     const size_t mask_bytes = sizeof(uint64_t) * (size_t)linc * (size_t)wpr;
@@ -1585,8 +1534,8 @@ extern "C" int eagle_bed_ld_window(eagle_ctx* ctx, const char* bed_path, const l
     HIPCHK(ctx, mask.alloc(mask_bytes));
     for (long lo = 0; lo < linc;) {
         const long hi = pl.window_end(lo, need);
-        rc = pl.stage(lo, hi);
-        if (!rc) rc = eagle_dev_bedld_band(ctx, pl.X.as<int8_t>(), pl.C.as<int8_t>(), pl.U.as<int8_t>(), hi - lo, n, pl.ld, window, r2, min_overlap,
+        rc = op.stage(pl, lo, hi);
+        if (!rc) rc = eagle_dev_bedld_band(ctx, op.X.as<int8_t>(), op.C.as<int8_t>(), op.U.as<int8_t>(), hi - lo, n, pl.ld(), window, r2, min_overlap,
                                            mask.as<uint64_t>() + lo * wpr, wpr, ctx->stream);
         if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
         lo = next_of(hi);
@@ -1608,19 +1557,21 @@ namespace {
 template <class Consume>
 int bedld_panel_cores(eagle_ctx* ctx, const char* bed_path, long n, long L, const uint8_t* include, long linc, long window, int min_overlap,
                       double max_memory_in_Gbytes, Consume consume) {
-    BedLdPanel pl;
+    BedPanel pl;
+    BedLdOperands op;
     const long need = 2 * window + 1;
     auto next_of = [&](long hi) { return hi >= linc ? linc : hi - 2 * window; };              // c1 = hi - window; the next window starts at c1 - window
     const long band_rows = std::max(1024L, (long)(((size_t)256 << 20) / (sizeof(double) * (size_t)window)));   // eagle_ld_partners' cap
-    int rc = bedld_open(pl, ctx, bed_path, n, L, include, linc, max_memory_in_Gbytes, band_rows, need, next_of);
+    int rc = pl.open(ctx, bed_path, n, L, include, linc, max_memory_in_Gbytes, band_rows, need, next_of);
+    if (!rc) rc = op.alloc(ctx, pl);
     if (rc) return rc;
     DevBuf band;
     HIPCHK(ctx, band.alloc(sizeof(double) * (size_t)pl.wmax * (size_t)window));
     for (long lo = 0; lo < linc;) {
         const long hi = pl.window_end(lo, need), nr = hi - lo;
         const long c0 = lo == 0 ? 0 : lo + window, c1 = hi >= linc ? linc : hi - window;
-        rc = pl.stage(lo, hi);
-        if (!rc) rc = eagle_dev_bedld_r2band(ctx, pl.X.as<int8_t>(), pl.C.as<int8_t>(), pl.U.as<int8_t>(), nr, n, pl.ld, window, min_overlap,
+        rc = op.stage(pl, lo, hi);
+        if (!rc) rc = eagle_dev_bedld_r2band(ctx, op.X.as<int8_t>(), op.C.as<int8_t>(), op.U.as<int8_t>(), nr, n, pl.ld(), window, min_overlap,
                                              band.as<double>(), ctx->stream);
         if (!rc) rc = consume(band.as<double>(), nr, c0 - lo, c1 - lo, lo);
         if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
@@ -1836,19 +1787,20 @@ extern "C" int eagle_bed_roh(eagle_ctx* ctx, const char* bed_path, const long di
     if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_roh: no context");
     int rc = roh_begin(ctx, "bed_roh", b, n, linc, pos);
     if (rc) return rc;
-    BedLdPanel pl;
-    pl.pack = false;
+    BedPanel pl;
     const long h = params->w - 1, need = 2 * h + 1;
     auto next_of = [&](long hi) { return hi >= linc ? linc : hi - 2 * h; };
-    rc = bedld_open(pl, ctx, bed_path, n, L, include, linc, max_memory_in_Gbytes, 0, need, next_of);
+    rc = pl.open(ctx, bed_path, n, L, include, linc, max_memory_in_Gbytes, 0, need, next_of);
     if (rc) return rc;
     for (long lo = 0; lo < linc;) {
         const long hi = pl.window_end(lo, need);
         const long c0 = lo == 0 ? 0 : lo + h, c1 = hi >= linc ? linc : hi - h;
-        rc = pl.stage(lo, hi);
-        if (!rc) rc = eagle_dev_roh_flags_bed(ctx, pl.raw, pl.raw_off, n, lo, c0, c1, b.blk.as<int32_t>(), b.nb(), params, b.planes.as<uint64_t>(),
-                                              linc, ctx->stream);
-        if (!rc) rc = pl.release();
+        const uint8_t* raw;
+        const long* d_off;
+        rc = pl.stage(lo, hi, &raw, &d_off);
+        if (!rc) rc = eagle_dev_roh_flags_bed(ctx, raw, d_off, n, lo, c0, c1, b.blk.as<int32_t>(), b.nb(), params, b.planes.as<uint64_t>(), linc,
+                                              ctx->stream);
+        if (!rc) rc = pl.ring.release();
         if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
         lo = next_of(hi);
     }
@@ -2015,17 +1967,18 @@ extern "C" int eagle_bed_ibd(eagle_ctx* ctx, const char* bed_path, const long di
     if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_ibd: no context");
     int rc = ibd_begin(ctx, "bed_ibd", b, n, linc, 3, pairs, npairs, chrom, pos, params);
     if (rc) return rc;
-    BedLdPanel pl;
-    pl.pack = false;
+    BedPanel pl;
     const long need = 64;
     auto next_of = [&](long hi) { return hi >= linc ? linc : hi / 64 * 64; };
-    rc = bedld_open(pl, ctx, bed_path, n, L, include, linc, max_memory_in_Gbytes, 0, need, next_of);
+    rc = pl.open(ctx, bed_path, n, L, include, linc, max_memory_in_Gbytes, 0, need, next_of);
     if (rc) return rc;
     for (long lo = 0; lo < linc;) {
         const long hi = pl.window_end(lo, need), nxt = next_of(hi);
-        rc = pl.stage(lo, hi);
-        if (!rc) rc = eagle_dev_ibd_planes_bed(ctx, pl.raw, pl.raw_off, n, lo, lo / 64, (nxt + 63) / 64, linc, b.planes.as<uint64_t>(), ctx->stream);
-        if (!rc) rc = pl.release();
+        const uint8_t* raw;
+        const long* d_off;
+        rc = pl.stage(lo, hi, &raw, &d_off);
+        if (!rc) rc = eagle_dev_ibd_planes_bed(ctx, raw, d_off, n, lo, lo / 64, (nxt + 63) / 64, linc, b.planes.as<uint64_t>(), ctx->stream);
+        if (!rc) rc = pl.ring.release();
         if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
         lo = nxt;
     }
@@ -2117,36 +2070,21 @@ extern "C" int eagle_bed_sample_counts(eagle_ctx* ctx, const char* bed_path, con
     const long n = dims[0], L = dims[1];
     if (n <= 0 || L <= 0 || L > 0x7fffffffL) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_sample_counts: bad dims");
     if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_sample_counts: no context");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    int fdin = -1;
-    if (int orc = open_bed(ctx, bed_path, n, L, &fdin)) return orc;
-    struct Closer { int fd; ~Closer() { if (fd >= 0) close(fd); } } closer{fdin};
-    const int threads = host_threads();
-    const long rb = bed_row_bytes(n);
-    double cap = 67108864.0;
-    if (max_memory_in_Gbytes > 0) cap = std::min(cap, max_memory_in_Gbytes * 1e9 / 4.0);  // the loaders' staging rule
-    const long w = std::max(1L, std::min(std::min(L, 1L << 25), (long)cap / rb));
-    int rc = eagle_stage_ensure(ctx, (size_t)w * rb);
+    BedRing ring;
+    if (int orc = ring.open(ctx, bed_path, n, L)) return orc;
+    const long w = std::min(std::min(L, 1L << 25), bed_stage_rows(ring.rb, max_memory_in_Gbytes));
+    int rc = ring.ensure(w);
     if (rc) return rc;
     DevBuf counts;
     HIPCHK(ctx, counts.alloc(sizeof(int32_t) * 4 * (size_t)n));
     HIPCHK(ctx, hipMemsetAsync(counts.p, 0, sizeof(int32_t) * 4 * (size_t)n, ctx->stream));
-    hipEvent_t done[2] = {nullptr, nullptr};
-    for (int b = 0; b < 2; b++) HIPCHK(ctx, hipEventCreateWithFlags(&done[b], hipEventDisableTiming));
-    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int b = 0; b < 2; b++) if (e[b]) (void)hipEventDestroy(e[b]); } } evg{done};
-    long k = 0;
-    for (long r0 = 0; r0 < L; r0 += w, k++) {
-        const int b = (int)(k & 1);
+    for (long r0 = 0; r0 < L; r0 += w) {
         const long nr = std::min(w, L - r0);
-        if (k >= 2) HIPCHK(ctx, hipEventSynchronize(done[b]));  // window k - 2 has left staging buffer b
-        if (!pread_all(fdin, (char*)ctx->stage_pin[b], (size_t)nr * rb, (off_t)BED_HEADER_BYTES + (off_t)r0 * rb, threads)) {
-            (void)hipStreamSynchronize(ctx->stream);
-            return failf(ctx, EAGLE_ERR_FORMAT, "%s: could not read markers %ld to %ld", bed_path, r0 + 1, r0 + nr);
-        }
-        HIPCHK(ctx, hipMemcpyAsync(ctx->stage_raw[b], ctx->stage_pin[b], (size_t)nr * rb, hipMemcpyHostToDevice, ctx->stream));
-        rc = eagle_dev_bed_sample_counts(ctx, (const uint8_t*)ctx->stage_raw[b], nr, n, counts.as<int32_t>(), ctx->stream);
+        const uint8_t* raw;
+        rc = ring.stage(r0, nr, &raw);
+        if (!rc) rc = eagle_dev_bed_sample_counts(ctx, raw, nr, n, counts.as<int32_t>(), ctx->stream);
+        if (!rc) rc = ring.release();
         if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-        HIPCHK(ctx, hipEventRecord(done[b], ctx->stream));
     }
     HIPCHK(ctx, hipMemcpyAsync(counts_out, counts.p, sizeof(int32_t) * 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -2176,17 +2114,12 @@ extern "C" int eagle_bed_sample_ibs(eagle_ctx* ctx, const char* bed_path, const 
     if (L >= (1L << 29)) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_sample_ibs: 2^29 markers or more");
     if (min_overlap < 1) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_sample_ibs: min_overlap must be at least 1");
     if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_sample_ibs: no context");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    int fdin = -1;
-    if (int orc = open_bed(ctx, bed_path, n, L, &fdin)) return orc;
-    struct Closer { int fd; ~Closer() { if (fd >= 0) close(fd); } } closer{fdin};
-    const int threads = host_threads();
-    const long rb = bed_row_bytes(n), np = eagle_pad(n);
-    double cap = 67108864.0;
-    if (max_memory_in_Gbytes > 0) cap = std::min(cap, max_memory_in_Gbytes * 1e9 / 4.0);  // the loaders' staging rule
+    BedRing ring;
+    if (int orc = ring.open(ctx, bed_path, n, L)) return orc;
+    const long np = eagle_pad(n);
     const long wplane = std::max(256L, (long)(((size_t)1 << 28) / (size_t)np) / 256 * 256);   // markers of a 128 MiB operand plane
-    const long w = std::max(1L, std::min(std::min(L, wplane), (long)cap / rb));
-    int rc = eagle_stage_ensure(ctx, (size_t)w * rb);
+    const long w = std::min(std::min(L, wplane), bed_stage_rows(ring.rb, max_memory_in_Gbytes));
+    int rc = ring.ensure(w);
     if (rc) return rc;
     const long wp = eagle_pad(w), ld4 = wp / 2;
     const size_t plane = (size_t)np * (size_t)ld4, accn = (size_t)np * np;
@@ -2202,22 +2135,12 @@ extern "C" int eagle_bed_sample_ibs(eagle_ctx* ctx, const char* bed_path, const 
         HIPCHK(ctx, dinc.alloc((size_t)L));
         HIPCHK(ctx, hipMemcpyAsync(dinc.p, include, (size_t)L, hipMemcpyHostToDevice, ctx->stream));
     }
-    hipEvent_t done[2] = {nullptr, nullptr};
-    for (int b = 0; b < 2; b++) HIPCHK(ctx, hipEventCreateWithFlags(&done[b], hipEventDisableTiming));
-    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int b = 0; b < 2; b++) if (e[b]) (void)hipEventDestroy(e[b]); } } evg{done};
-    long k = 0;
-    for (long r0 = 0; r0 < L; r0 += w, k++) {
-        const int b = (int)(k & 1);
+    for (long r0 = 0; r0 < L; r0 += w) {
         const long nr = std::min(w, L - r0), nrp = eagle_pad(nr);
-        if (k >= 2) HIPCHK(ctx, hipEventSynchronize(done[b]));  // window k - 2 has left staging buffer b
-        if (!pread_all(fdin, (char*)ctx->stage_pin[b], (size_t)nr * rb, (off_t)BED_HEADER_BYTES + (off_t)r0 * rb, threads)) {
-            (void)hipStreamSynchronize(ctx->stream);
-            return failf(ctx, EAGLE_ERR_FORMAT, "%s: could not read markers %ld to %ld", bed_path, r0 + 1, r0 + nr);
-        }
-        HIPCHK(ctx, hipMemcpyAsync(ctx->stage_raw[b], ctx->stage_pin[b], (size_t)nr * rb, hipMemcpyHostToDevice, ctx->stream));
-        rc = eagle_dev_bed_pack_fp4(ctx, (const uint8_t*)ctx->stage_raw[b], nr, n, include ? dinc.as<uint8_t>() + r0 : nullptr, np, nrp, m4, ld4,
-                                    (long)plane, ctx->stream);
-        HIPCHK(ctx, hipEventRecord(done[b], ctx->stream));     // the staging buffer is free once the pack has read it
+        const uint8_t* raw;
+        rc = ring.stage(r0, nr, &raw);
+        if (!rc) rc = eagle_dev_bed_pack_fp4(ctx, raw, nr, n, include ? dinc.as<uint8_t>() + r0 : nullptr, np, nrp, m4, ld4, (long)plane, ctx->stream);
+        if (!rc) rc = ring.release();     // the staging buffer is free once the pack has read it
         for (int p = 0; p < 4 && !rc; p++)
             rc = eagle_dev_mmt_accumulate_f4(ctx, m4 + (size_t)p * plane, np, nrp, ld4, acc.as<int32_t>() + (size_t)p * accn, ctx->stream);
         if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }

@@ -139,16 +139,15 @@ static int stream_rows(eagle_ctx* ctx, int fd, off_t off0, long src_stride, cons
     // i.e. wait for the kernels of the previous chunk when the tile is a chunk of a streamed file
     int* const bad = (int*)((char*)ctx->d_scratch + EAGLE_SCR_LOADER_BAD);
     HIPCHK(ctx, hipMemsetAsync(bad, 0, sizeof(int), ctx->stream));
-    hipEvent_t done[2] = {nullptr, nullptr};
-    for (int b = 0; b < 2; b++) HIPCHK(ctx, hipEventCreateWithFlags(&done[b], hipEventDisableTiming));
-    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int b = 0; b < 2; b++) if (e[b]) (void)hipEventDestroy(e[b]); } } evg{done};
+    EventPair done;
+    HIPCHK(ctx, done.create());
     volatile int io_err = 0;
     size_t ri = 0;
     long pos = 0, k = 0;  // next row: runs[ri].src_row + pos
     for (long r = 0; r < nrows; r += chunk_rows, k++) {
         const int b = (int)(k & 1);
         const long nr = std::min(chunk_rows, nrows - r);
-        if (k >= 2) HIPCHK(ctx, hipEventSynchronize(done[b]));  // the copy out of pin[b] two chunks ago has finished
+        if (k >= 2) HIPCHK(ctx, hipEventSynchronize(done.e[b]));  // the copy out of pin[b] two chunks ago has finished
         const double tp = now_s();
         for (long filled = 0; filled < nr && !io_err;) {
             while (runs[ri].count == 0) ri++;
@@ -163,7 +162,7 @@ static int stream_rows(eagle_ctx* ctx, int fd, off_t off0, long src_stride, cons
         ctx->st_file_bytes += nr * nb;
         if (io_err) { (void)hipStreamSynchronize(ctx->stream); return LOAD_SHORT_READ; }
         HIPCHK(ctx, hipMemcpyAsync(ctx->stage_raw[b], ctx->stage_pin[b], (size_t)nr * stride, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipEventRecord(done[b], ctx->stream));
+        HIPCHK(ctx, hipEventRecord(done.e[b], ctx->stream));
         rc = launch((const uint8_t*)ctx->stage_raw[b], r, nr, bad);
         if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
     }

@@ -97,6 +97,27 @@ def test_gpu_bed_ld_stats_missing_codes_and_include(tmp_path, min_overlap):
     check(bed, n, L, codes, include=np.arange(L) % 2 == 0, min_overlap=min_overlap)
 
 
+@pytest.mark.parametrize("every", [1, 3])
+def test_gpu_bed_ld_stats_staging_windows_give_the_same_result(tmp_path, every):
+    """Windows of 100 file rows (a quarter of the budget, the library's arithmetic) against the one window of the default budget."""
+    from eagleeverything_amd import rcpp_api
+    from test_gpu_bed_ld import staging_windows
+    n, L = 129, 700
+    rb = (n + 3) // 4
+    small = 4 * 100 * rb / 1e9
+    Mt8, miss = panel(n, L, seed=44, rate=0.05)
+    bed = write_bed(tmp_path, "st", Mt8, miss)
+    include = None if every == 1 else np.arange(L) % every != 0
+    fidx = None if include is None else np.flatnonzero(include)
+    linc = L if include is None else fidx.size
+    for window in (1, 33):
+        assert len(staging_windows(n, linc, window, small, fidx, partners=True)) >= 3
+        assert len(staging_windows(n, linc, window, 8.0, fidx, partners=True)) == 1
+        for kw in variants(linc, window):
+            one = rcpp_api.bed_ld_stats(bed, (n, L), window, include, 1, **kw)
+            same(rcpp_api.bed_ld_stats(bed, (n, L), window, include, 1, availmemGb=small, **kw), one, (every, window, sorted(kw)))
+
+
 def test_gpu_bed_ld_stats_without_a_missing_code_is_the_panels(tmp_path):
     from eagleeverything_amd import r_api, rcpp_api
     n, L = 257, 300

@@ -170,6 +170,26 @@ def test_gpu_bed_impute_ldknn_windows_give_the_same_bytes(tmp_path):
         assert open(out, "rb").read() == open(outs[0][0], "rb").read() and np.array_equal(counts, outs[0][1])
 
 
+def test_gpu_bed_staging_ring_lives_across_calls_on_one_context(tmp_path):
+    """One context: counts in windows of 100 rows (seven of them), an imputation whose one window needs larger staging buffers, so that
+    the context's ring is grown between the calls, and the counts in windows of 100 rows again."""
+    from eagleeverything_amd import rcpp_api
+    n, L, l = 129, 700, 7
+    rb = (n + 3) // 4
+    small = 4 * 100 * rb / 1e9                                                # the library's arithmetic: a quarter of the budget per window
+    bed, miss = make_bed(tmp_path, n, L, seed=21)
+    part = partner_table(L, l, seed=22)
+    rcpp_api.close_all()                                                      # a context that has staged nothing yet
+    first = rcpp_api.bed_marker_counts(bed, (n, L), max_memory_in_Gbytes=small)
+    counts = rcpp_api.bed_impute_ldknn(bed, (n, L), part, 5, 1, 2, str(tmp_path / "one.bed"))
+    again = rcpp_api.bed_marker_counts(bed, (n, L), max_memory_in_Gbytes=small)
+    assert np.array_equal(first, again) and np.array_equal(first[:, 3], miss.sum(axis=1)) and first[:, 3].sum() > 0
+    rcpp_api.close_all()
+    fresh = rcpp_api.bed_impute_ldknn(bed, (n, L), part, 5, 1, 2, str(tmp_path / "fresh.bed"))
+    assert np.array_equal(counts, fresh) and counts.sum() == miss.sum()
+    assert open(str(tmp_path / "one.bed"), "rb").read() == open(str(tmp_path / "fresh.bed"), "rb").read()
+
+
 def test_gpu_bed_impute_ldknn_refuses_and_leaves_no_file(tmp_path):
     from eagleeverything_amd import rcpp_api
     n, L = 9, 300
