@@ -94,6 +94,13 @@ SIGNATURES = {
                             C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_long, c_lp]),
     "eagle_bed_ibd": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, C.c_void_p, C.POINTER(C.c_int32), C.c_long, C.POINTER(C.c_int32),
                                 C.POINTER(C.c_int64), C.c_void_p, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_long, c_lp]),
+    "eagle_mendel": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, C.POINTER(C.c_int32), C.c_long, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "eagle_bed_mendel": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, C.c_void_p, C.POINTER(C.c_int32), C.c_long, C.c_double, C.POINTER(C.c_int32),
+                                   C.POINTER(C.c_int32)]),
+    "eagle_parentage": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, C.POINTER(C.c_int32), C.c_long, C.POINTER(C.c_int32), C.c_long, C.POINTER(C.c_int32),
+                                  C.c_long, C.c_long, C.c_int, C.c_double, C.POINTER(C.c_int32)]),
+    "eagle_bed_parentage": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, C.c_void_p, C.POINTER(C.c_int32), C.c_long, C.POINTER(C.c_int32), C.c_long,
+                                      C.POINTER(C.c_int32), C.c_long, C.c_long, C.c_int, C.c_double, C.POINTER(C.c_int32)]),
     "eagle_weighted_gram": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, C.POINTER(C.c_uint32), C.c_double, C.POINTER(C.c_int64)]),
     "eagle_sample_scores": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, C.POINTER(C.c_int32), C.c_long, C.c_double, C.POINTER(C.c_int64)]),
     "eagle_marker_scores": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, C.POINTER(C.c_int32), C.c_long, C.c_double, C.POINTER(C.c_int64)]),

@@ -268,6 +268,19 @@ extern "C" int eagle_dev_ibd_planes_bed(eagle_ctx* ctx, const uint8_t* bed, cons
 extern "C" int eagle_dev_ibd_walk(eagle_ctx* ctx, const uint64_t* planes, int nplanes, const uint64_t* cut, long n, long L, const int32_t* pairs,
                                   long P, const int32_t* blk, long nb, const int64_t* pos, const eagle_ibd_params* prm, int fill, int64_t* tot,
                                   const int64_t* offs, int32_t* seg, void* stream);
+// Mendel errors and parentage assignment (eagle_mendel.hip; include/eagle_hip.h section 1b'''viii) on the planes above, device pointers
+// throughout.  trios: T x 3 int32; out: T x 6 int32; marker: L int32 ZEROED by the caller, or null.  The gather writes the sub-planes of an
+// index list (-1: zero words), nplanes x ceil(L / 64) x cnt rounded up to 64 words.  The parentage call works on the offspring [o0, o0 + no)
+// (no <= 65535) of the gathered lists (ns / nd = 0: the sub-planes of the one index -1): part_k / part_n hold 2 no eagle_parentage_parts(ns,
+// nd) entries; best: n_o x 8 int32.
+extern "C" int eagle_dev_mendel_trios(eagle_ctx* ctx, const uint64_t* planes, int nplanes, long n, long L, const int32_t* trios, long T, int32_t* out,
+                                      int32_t* marker, void* stream);
+extern "C" int eagle_dev_plane_gather(eagle_ctx* ctx, const uint64_t* planes, int nplanes, long n, long L, const int32_t* idx, long cnt, uint64_t* dst,
+                                      void* stream);
+extern "C" long eagle_parentage_parts(long ns, long nd);
+extern "C" int eagle_dev_parentage(eagle_ctx* ctx, const uint64_t* O, long n_o, const uint64_t* S, long ns, const uint64_t* D, long nd, int nplanes, long L,
+                                   const int32_t* oidx, const int32_t* sidx, const int32_t* didx, long o0, long no, int min_overlap, int allow_self,
+                                   uint64_t* part_k, int32_t* part_n, int32_t* best, void* stream);
 // Pairwise-complete IBS counts from a .bed file (eagle_bedibs.hip; include/eagle_hip.h section 1b'''ii), device pointers throughout.  The
 // four fp4 operand images (g, u, h, c; plane p at M4 + p * plane_bytes, n_pad rows of ld4 bytes, L_pad markers written) of `rows` raw
 // .bed rows, `include` one byte per row or null; the four n x n int32 results and dist (or null) from the four Gram accumulators

@@ -462,4 +462,73 @@ static inline void ibd_cut_plane(const int32_t* chrom, const int64_t* pos, long 
         if (c) cut[(size_t)(m >> 6)] |= 1ull << (m & 63);
     }
 }
+
+// ------------------------------------------------------------------------------------------------
+// Mendel errors and parentage assignment (include/eagle_hip.h section 1b'''viii): the error word of rule 3 on the bit planes (shared
+// with the kernels of eagle_mendel.hip), the argument rules of eagle_mendel / eagle_parentage, the checks of a trio list and of a
+// candidate list, and the ordinal of a candidate pair.
+// ------------------------------------------------------------------------------------------------
+#define MENDEL_MAX_TRIOS 134217728L   /* 2^27 */
+// The wave-uniform part of rule 3 for one (child, father): hc = the child's hets, E = x | u & Bm | v & Am.
+struct MendelXUV { uint64_t x, u, v; };
+static inline EAGLE_HD MendelXUV mendel_xuv(uint64_t ac, uint64_t bc, uint64_t cc, uint64_t af, uint64_t bf) {
+    const uint64_t hc = cc & ~ac & ~bc;
+    return MendelXUV{(ac & bf) | (bc & af), ac | (hc & bf), bc | (hc & af)};
+}
+// Bit m set where the trio has a Mendel error at marker m of the word.  A and B imply called, so the parents' C planes are not needed.
+static inline EAGLE_HD uint64_t mendel_error_word(uint64_t ac, uint64_t bc, uint64_t cc, uint64_t af, uint64_t bf, uint64_t am, uint64_t bm) {
+    const MendelXUV t = mendel_xuv(ac, bc, cc, af, bf);
+    return t.x | (t.u & bm) | (t.v & am);
+}
+// The bits of word w that are panel markers: all ones but for the last word of a panel whose length is no multiple of 64.
+static inline EAGLE_HD uint64_t mendel_word_mask(long w, long markers) {
+    const long left = markers - 64 * w;
+    return left >= 64 ? ~0ull : (left <= 0 ? 0ull : (1ull << left) - 1ull);
+}
+// What is wrong with a call of eagle_mendel / eagle_bed_mendel over `markers` panel markers, or NULL.
+static inline const char* mendel_arg_error(long markers, long ntrios) {
+    if (markers > 0x7fffffffL) return "2^31 markers or more";
+    if (ntrios < 1 || ntrios > MENDEL_MAX_TRIOS) return "the number of trios must be in [1, 2^27]";
+    return nullptr;
+}
+// The first trio (c, f, m) that is not 0 <= c < n, -1 <= f, m < n, c != f, c != m, f != m unless both are -1; or -1.
+static inline long mendel_trios_check(const int32_t* trios, long ntrios, long n) {
+    for (long k = 0; k < ntrios; k++) {
+        const long c = trios[3 * k], f = trios[3 * k + 1], m = trios[3 * k + 2];
+        if (c < 0 || c >= n || f < -1 || f >= n || m < -1 || m >= n || c == f || c == m || (f == m && f >= 0)) return k;
+    }
+    return -1;
+}
+// What is wrong with a call of eagle_parentage / eagle_bed_parentage, or NULL.  An empty list is one unknown parent.
+static inline const char* parentage_arg_error(long markers, long n_o, long n_s, long n_d, long min_overlap, long allow_self) {
+    if (markers > 0x7fffffffL) return "2^31 markers or more";
+    if (n_o < 1 || n_o > MENDEL_MAX_TRIOS) return "the number of offspring must be in [1, 2^27]";
+    if (n_s < 0 || n_d < 0) return "a candidate list has a negative length";
+    if (n_s == 0 && n_d == 0) return "both candidate lists are empty";
+    if (n_s > 0x7fffffffL || n_d > 0x7fffffffL || (n_s > 0 ? n_s : 1) * (n_d > 0 ? n_d : 1) > 0x7fffffffL)
+        return "sires x dams must be below 2^31";
+    if (min_overlap < 0 || min_overlap > 0x7fffffffL) return "min_overlap must be in [0, 2^31)";
+    if (allow_self != 0 && allow_self != 1) return "allow_self must be 0 or 1";
+    return nullptr;
+}
+// The first entry of a list of individual indices that is outside [0, n) (*dup = false) or repeats an earlier entry (*dup = true); or -1.
+static inline long parentage_list_check(const int32_t* list, long cnt, long n, bool* dup) {
+    *dup = false;
+    if (cnt <= 0) return -1;
+    for (long k = 0; k < cnt; k++)
+        if (list[k] < 0 || list[k] >= n) return k;
+    std::vector<int32_t> s(list, list + cnt);
+    std::sort(s.begin(), s.end());
+    int32_t twice = -1;
+    for (size_t k = 1; k < s.size(); k++)
+        if (s[k] == s[k - 1]) { twice = s[k]; break; }
+    if (twice < 0) return -1;
+    *dup = true;
+    bool seen = false;
+    for (long k = 0; k < cnt; k++)
+        if (list[k] == twice) { if (seen) return k; seen = true; }
+    return -1;
+}
+// The ordinal of the candidate (s_idx-th sire, d_idx-th dam): ties in the error count go to the smaller one.
+static inline EAGLE_HD long parentage_ordinal(long s_idx, long d_idx, long n_d) { return s_idx * (n_d > 0 ? n_d : 1) + d_idx; }
 #endif

@@ -1813,13 +1813,90 @@ extern "C" int eagle_bed_roh(eagle_ctx* ctx, const char* bed_path, const long di
 static_assert(IBD_MAX_PAIRS == EAGLE_IBD_MAX_PAIRS, "eagle_host.h restates the public limit");
 namespace {
 
-// What both entry points hold on the device: the bit planes of the panel, the cut plane, the block table, pos, the pair list and the
-// walk's arrays.
+// The bit planes of a call (eagle_ibd.hip): A and B from the ingested panel, A, B and C from the .bed file, resident for the whole call.
+// build() is the one place that makes them: the budget test of IBD rule 9 over the planes and `extra` further bytes the caller will
+// allocate (named by extra_what in the message) -- EAGLE_ERR_NOMEM before any kernel runs --, the allocation, and the fill: from
+// M.ascii (bed_path null) the resident image in one launch, else bands of whole lines of the streamed size from the sidecar, the text
+// or a VIEW alias's source; from the .bed file the ring's windows of panel markers, each but the last cut back to a multiple of 64
+// markers (it holds at least 64) so that a window writes whole plane words.  Every plane word is written once.
+struct GenoPlanes {
+    DevBuf planes;
+    long n = 0, lp = 0;
+    int nplanes = 2;
+    size_t bytes() const { return sizeof(uint64_t) * (size_t)nplanes * (size_t)((lp + 63) / 64) * (size_t)((n + 63) / 64 * 64); }
+    uint64_t* p() { return planes.as<uint64_t>(); }
+    // path: M.ascii of dims (n, L), or with is_bed the .bed file of dims (n, L) whose panel is the linc markers of include
+    int build(eagle_ctx* ctx, const char* who, bool is_bed, const char* path, long n_, long L, const uint8_t* include, long linc, double mem_gb,
+              size_t extra, const char* extra_what) {
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        n = n_;
+        lp = is_bed ? linc : L;
+        nplanes = is_bed ? 3 : 2;
+        const size_t plane_bytes = bytes();
+        size_t budget = eagle_resident_budget();
+        if (budget == (size_t)-1) {
+            size_t freeb = 0, totalb = 0;
+            HIPCHK(ctx, hipMemGetInfo(&freeb, &totalb));
+            budget = freeb > ((size_t)1 << 30) ? freeb - ((size_t)1 << 30) : 0;
+        }
+        if (plane_bytes > budget || extra > budget - plane_bytes)
+            return failf(ctx, EAGLE_ERR_NOMEM, "%s: the bit planes (%zu bytes) and %s (%zu bytes) do not fit the memory budget", who, plane_bytes,
+                         extra_what, extra);
+        HIPCHK(ctx, planes.alloc(plane_bytes));
+        return is_bed ? fill_bed(ctx, path, L, include, mem_gb) : fill_image(ctx, path, L, mem_gb);
+    }
+
+  private:
+    int fill_image(eagle_ctx* ctx, const char* f_name_ascii_M, long L, double mem_gb) {
+        const int threads = host_threads();
+        const GenoEntry* src = nullptr;
+        int rc = eagle_get_resident(ctx, f_name_ascii_M, n, L, mem_gb, threads, &src);
+        if (rc != EAGLE_OK && rc != EAGLE_STREAM) return rc;
+        if (rc == EAGLE_OK) {
+            rc = eagle_dev_ibd_planes_i8(ctx, src->dev, src->ld, 0, n, n, L, p(), ctx->stream);
+            if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+            return EAGLE_OK;
+        }
+        const long ld = eagle_pad(L), w = std::min(n, stream_chunk_rows_core(eagle_resident_budget(), ld, eagle_pad(n)));
+        DevBuf win;
+        HIPCHK(ctx, win.alloc((size_t)w * ld));
+        for (long r0 = 0; r0 < n; r0 += w) {
+            const long nr = std::min(w, n - r0);
+            HIPCHK(ctx, hipMemsetAsync(win.p, 0, (size_t)w * ld, ctx->stream));
+            rc = eagle_dev_load_ascii(ctx, f_name_ascii_M, r0, nr, 0, L, win.as<int8_t>(), ld, mem_gb, threads);
+            if (!rc) rc = eagle_dev_ibd_planes_i8(ctx, win.as<int8_t>(), ld, r0, nr, n, L, p(), ctx->stream);
+            if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+        }
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // the window leaves with this scope
+        return EAGLE_OK;
+    }
+    int fill_bed(eagle_ctx* ctx, const char* bed_path, long L, const uint8_t* include, double mem_gb) {
+        BedPanel pl;
+        const long linc = lp, need = 64;
+        auto next_of = [&](long hi) { return hi >= linc ? linc : hi / 64 * 64; };
+        int rc = pl.open(ctx, bed_path, n, L, include, linc, mem_gb, 0, need, next_of);
+        if (rc) return rc;
+        for (long lo = 0; lo < linc;) {
+            const long hi = pl.window_end(lo, need), nxt = next_of(hi);
+            const uint8_t* raw;
+            const long* d_off;
+            rc = pl.stage(lo, hi, &raw, &d_off);
+            if (!rc) rc = eagle_dev_ibd_planes_bed(ctx, raw, d_off, n, lo, lo / 64, (nxt + 63) / 64, linc, p(), ctx->stream);
+            if (!rc) rc = pl.ring.release();
+            if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+            lo = nxt;
+        }
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // the ring and the offsets leave with this frame
+        return EAGLE_OK;
+    }
+};
+
+// What both entry points hold on the device beside the planes: the cut plane, the block table, pos, the pair list and the walk's arrays.
 struct IbdBufs {
-    DevBuf planes, cut, blk, pos, pairs, tot, offs, seg;
+    GenoPlanes g;
+    DevBuf cut, blk, pos, pairs, tot, offs, seg;
     std::vector<int32_t> h_blk;
     long lp = 0, n = 0, P = 0;
-    int nplanes = 2;
     long nb() const { return (long)h_blk.size() - 1; }
 };
 
@@ -1849,29 +1926,18 @@ int ibd_check(eagle_ctx* ctx, const char* who, long n, long lp, const int32_t* p
     return EAGLE_OK;
 }
 
-// The planes and the per-pair arrays against the memory budget (rule 9), then the allocations and uploads; no kernel has run when this
-// fails.
-int ibd_begin(eagle_ctx* ctx, const char* who, IbdBufs& b, long n, long lp, int nplanes, const int32_t* pairs, long npairs, const int32_t* chrom,
-              const int64_t* pos, const eagle_ibd_params* prm) {
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+// The bytes of the per-pair arrays of rule 9.
+size_t ibd_pair_bytes(long n, const int32_t* pairs, long npairs) { return (size_t)40 * (size_t)ibd_pair_count(n, pairs != nullptr, npairs); }
+
+// After the planes (GenoPlanes::build, which holds the budget test of rule 9): the allocations and uploads of everything else.
+int ibd_begin(eagle_ctx* ctx, IbdBufs& b, long n, long lp, const int32_t* pairs, long npairs, const int32_t* chrom, const int64_t* pos,
+              const eagle_ibd_params* prm) {
     b.n = n;
     b.lp = lp;
-    b.nplanes = nplanes;
     b.P = ibd_pair_count(n, pairs != nullptr, npairs);
-    const size_t np = (size_t)((n + 63) / 64 * 64), nwords = (size_t)((lp + 63) / 64);
-    const size_t plane_bytes = sizeof(uint64_t) * (size_t)nplanes * nwords * np, pair_bytes = (size_t)40 * (size_t)b.P;
-    size_t budget = eagle_resident_budget();
-    if (budget == (size_t)-1) {
-        size_t freeb = 0, totalb = 0;
-        HIPCHK(ctx, hipMemGetInfo(&freeb, &totalb));
-        budget = freeb > ((size_t)1 << 30) ? freeb - ((size_t)1 << 30) : 0;
-    }
-    if (plane_bytes > budget || pair_bytes > budget - plane_bytes)
-        return failf(ctx, EAGLE_ERR_NOMEM, "%s: the bit planes (%zu bytes) and the per-pair arrays (%zu bytes) do not fit the memory budget", who,
-                     plane_bytes, pair_bytes);
+    const size_t nwords = (size_t)((lp + 63) / 64);
     std::vector<uint64_t> h_cut;
     ibd_cut_plane(chrom, pos, prm->max_gap, lp, h_cut);
-    HIPCHK(ctx, b.planes.alloc(plane_bytes));
     HIPCHK(ctx, b.cut.alloc(sizeof(uint64_t) * nwords));
     HIPCHK(ctx, b.blk.alloc(sizeof(int32_t) * b.h_blk.size()));
     HIPCHK(ctx, b.tot.alloc(sizeof(int64_t) * 4 * (size_t)b.P));
@@ -1894,7 +1960,7 @@ int ibd_begin(eagle_ctx* ctx, const char* who, IbdBufs& b, long n, long lp, int 
 int ibd_end(eagle_ctx* ctx, IbdBufs& b, const eagle_ibd_params* prm, int64_t* pair_out, int32_t* seg_out, long seg_cap, long* nseg_out) {
     const int64_t* d_pos = b.pos.p ? b.pos.as<int64_t>() : nullptr;
     const int32_t* d_pairs = b.pairs.p ? b.pairs.as<int32_t>() : nullptr;
-    int rc = eagle_dev_ibd_walk(ctx, b.planes.as<uint64_t>(), b.nplanes, b.cut.as<uint64_t>(), b.n, b.lp, d_pairs, b.P, b.blk.as<int32_t>(), b.nb(),
+    int rc = eagle_dev_ibd_walk(ctx, b.g.p(), b.g.nplanes, b.cut.as<uint64_t>(), b.n, b.lp, d_pairs, b.P, b.blk.as<int32_t>(), b.nb(),
                                 d_pos, prm, 0, b.tot.as<int64_t>(), nullptr, nullptr, ctx->stream);
     if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
     HIPCHK(ctx, hipMemcpyAsync(pair_out, b.tot.p, sizeof(int64_t) * 4 * (size_t)b.P, hipMemcpyDeviceToHost, ctx->stream));
@@ -1905,7 +1971,7 @@ int ibd_end(eagle_ctx* ctx, IbdBufs& b, const eagle_ibd_params* prm, int64_t* pa
     if (total == 0 || total > seg_cap) return EAGLE_OK;
     HIPCHK(ctx, b.seg.alloc(sizeof(int32_t) * 6 * (size_t)total));
     HIPCHK(ctx, hipMemcpyAsync(b.offs.p, h_offs.data(), sizeof(int64_t) * (size_t)b.P, hipMemcpyHostToDevice, ctx->stream));
-    rc = eagle_dev_ibd_walk(ctx, b.planes.as<uint64_t>(), b.nplanes, b.cut.as<uint64_t>(), b.n, b.lp, d_pairs, b.P, b.blk.as<int32_t>(), b.nb(), d_pos,
+    rc = eagle_dev_ibd_walk(ctx, b.g.p(), b.g.nplanes, b.cut.as<uint64_t>(), b.n, b.lp, d_pairs, b.P, b.blk.as<int32_t>(), b.nb(), d_pos,
                             prm, 1, nullptr, b.offs.as<int64_t>(), b.seg.as<int32_t>(), ctx->stream);
     if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
     HIPCHK(ctx, hipMemcpyAsync(seg_out, b.seg.p, sizeof(int32_t) * 6 * (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
@@ -1915,8 +1981,7 @@ int ibd_end(eagle_ctx* ctx, IbdBufs& b, const eagle_ibd_params* prm, int64_t* pa
 
 }  // namespace
 
-// A line of M.ascii is an individual.  The planes pass over a resident image is one launch; a file that is not resident is read in bands
-// of whole lines of the streamed size, and a band writes the plane words of its own individuals: every word is written once.
+// A line of M.ascii is an individual; the planes are GenoPlanes::build's.
 extern "C" int eagle_ibd(eagle_ctx* ctx, const char* f_name_ascii_M, const long dims[2], const int32_t* pairs, long npairs, const int32_t* chrom,
                          const int64_t* pos, const eagle_ibd_params* params, double max_memory_in_Gbytes, int64_t* pair_out, int32_t* seg_out,
                          long seg_cap, long* nseg_out) {
@@ -1926,33 +1991,14 @@ extern "C" int eagle_ibd(eagle_ctx* ctx, const char* f_name_ascii_M, const long 
     IbdBufs b;
     if (int rc = ibd_check(ctx, "ibd", n, L, pairs, npairs, chrom, pos, params, seg_out, seg_cap, b.h_blk)) return rc;
     if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "ibd: no context");
-    int rc = ibd_begin(ctx, "ibd", b, n, L, 2, pairs, npairs, chrom, pos, params);
+    int rc = b.g.build(ctx, "ibd", false, f_name_ascii_M, n, L, nullptr, L, max_memory_in_Gbytes, ibd_pair_bytes(n, pairs, npairs),
+                       "the per-pair arrays");
+    if (!rc) rc = ibd_begin(ctx, b, n, L, pairs, npairs, chrom, pos, params);
     if (rc) return rc;
-    const int threads = host_threads();
-    const GenoEntry* src = nullptr;
-    rc = eagle_get_resident(ctx, f_name_ascii_M, n, L, max_memory_in_Gbytes, threads, &src);
-    if (rc != EAGLE_OK && rc != EAGLE_STREAM) return rc;
-    if (rc == EAGLE_OK) {
-        rc = eagle_dev_ibd_planes_i8(ctx, src->dev, src->ld, 0, n, n, L, b.planes.as<uint64_t>(), ctx->stream);
-        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-    } else {
-        const long ld = eagle_pad(L), w = std::min(n, stream_chunk_rows_core(eagle_resident_budget(), ld, eagle_pad(n)));
-        DevBuf win;
-        HIPCHK(ctx, win.alloc((size_t)w * ld));
-        for (long r0 = 0; r0 < n; r0 += w) {
-            const long nr = std::min(w, n - r0);
-            HIPCHK(ctx, hipMemsetAsync(win.p, 0, (size_t)w * ld, ctx->stream));
-            rc = eagle_dev_load_ascii(ctx, f_name_ascii_M, r0, nr, 0, L, win.as<int8_t>(), ld, max_memory_in_Gbytes, threads);
-            if (!rc) rc = eagle_dev_ibd_planes_i8(ctx, win.as<int8_t>(), ld, r0, nr, n, L, b.planes.as<uint64_t>(), ctx->stream);
-            if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-        }
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // the window leaves with this scope
-    }
     return ibd_end(ctx, b, params, pair_out, seg_out, seg_cap, nseg_out);
 }
 
-// The .bed rows go through the pinned ring in eagle_bed_roh's windows of panel markers.  A window that is not the last is cut back to a
-// multiple of 64 markers (it holds at least 64), and the next one starts there: a window writes whole plane words.
+// The same from the .bed file (GenoPlanes::build with the ring's windows).
 extern "C" int eagle_bed_ibd(eagle_ctx* ctx, const char* bed_path, const long dims[2], const uint8_t* include, const int32_t* pairs, long npairs,
                              const int32_t* chrom, const int64_t* pos, const eagle_ibd_params* params, double max_memory_in_Gbytes,
                              int64_t* pair_out, int32_t* seg_out, long seg_cap, long* nseg_out) {
@@ -1965,24 +2011,189 @@ extern "C" int eagle_bed_ibd(eagle_ctx* ctx, const char* bed_path, const long di
     IbdBufs b;
     if (int rc = ibd_check(ctx, "bed_ibd", n, linc, pairs, npairs, chrom, pos, params, seg_out, seg_cap, b.h_blk)) return rc;
     if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_ibd: no context");
-    int rc = ibd_begin(ctx, "bed_ibd", b, n, linc, 3, pairs, npairs, chrom, pos, params);
+    int rc = b.g.build(ctx, "bed_ibd", true, bed_path, n, L, include, linc, max_memory_in_Gbytes, ibd_pair_bytes(n, pairs, npairs),
+                       "the per-pair arrays");
+    if (!rc) rc = ibd_begin(ctx, b, n, linc, pairs, npairs, chrom, pos, params);
     if (rc) return rc;
-    BedPanel pl;
-    const long need = 64;
-    auto next_of = [&](long hi) { return hi >= linc ? linc : hi / 64 * 64; };
-    rc = pl.open(ctx, bed_path, n, L, include, linc, max_memory_in_Gbytes, 0, need, next_of);
-    if (rc) return rc;
-    for (long lo = 0; lo < linc;) {
-        const long hi = pl.window_end(lo, need), nxt = next_of(hi);
-        const uint8_t* raw;
-        const long* d_off;
-        rc = pl.stage(lo, hi, &raw, &d_off);
-        if (!rc) rc = eagle_dev_ibd_planes_bed(ctx, raw, d_off, n, lo, lo / 64, (nxt + 63) / 64, linc, b.planes.as<uint64_t>(), ctx->stream);
-        if (!rc) rc = pl.ring.release();
-        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-        lo = nxt;
-    }
     return ibd_end(ctx, b, params, pair_out, seg_out, seg_cap, nseg_out);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Mendel errors and parentage assignment (include/eagle_hip.h section 1b'''viii; kernels in eagle_mendel.hip)
+// ---------------------------------------------------------------------------------------------------------------
+static_assert(MENDEL_MAX_TRIOS == EAGLE_MENDEL_MAX_TRIOS, "eagle_host.h restates the public limit");
+namespace {
+
+// Everything of the trio rule that is decided before the context is used.
+int mendel_check(eagle_ctx* ctx, const char* who, long n, long lp, const int32_t* trios, long ntrios) {
+    char msg[160];
+    if (const char* bad = mendel_arg_error(lp, ntrios)) {
+        snprintf(msg, sizeof msg, "%s: %s", who, bad);
+        return qc_fail(ctx, EAGLE_ERR_ARG, msg);
+    }
+    const long k = mendel_trios_check(trios, ntrios, n);
+    if (k >= 0) {
+        snprintf(msg, sizeof msg, "%s: trio %ld is not (c, f, m) with 0 <= c < n, -1 <= f, m < n, c != f, c != m, f != m", who, k);
+        return qc_fail(ctx, EAGLE_ERR_ARG, msg);
+    }
+    return EAGLE_OK;
+}
+
+// The trio list, the six counts a trio and the marker counts.
+size_t mendel_extra_bytes(long lp, long ntrios, bool marker) { return (size_t)36 * (size_t)ntrios + (marker ? sizeof(int32_t) * (size_t)lp : 0); }
+
+// The trio pass over the planes of g and the download of its tables.
+int mendel_run(eagle_ctx* ctx, GenoPlanes& g, const int32_t* trios, long ntrios, int32_t* trio_out, int32_t* marker_out) {
+    DevBuf d_trios, d_out, d_marker;
+    const size_t T = (size_t)ntrios;
+    HIPCHK(ctx, d_trios.alloc(sizeof(int32_t) * 3 * T));
+    HIPCHK(ctx, d_out.alloc(sizeof(int32_t) * 6 * T));
+    HIPCHK(ctx, hipMemcpyAsync(d_trios.p, trios, sizeof(int32_t) * 3 * T, hipMemcpyHostToDevice, ctx->stream));
+    if (marker_out) {
+        HIPCHK(ctx, d_marker.alloc(sizeof(int32_t) * (size_t)g.lp));
+        HIPCHK(ctx, hipMemsetAsync(d_marker.p, 0, sizeof(int32_t) * (size_t)g.lp, ctx->stream));
+    }
+    int rc = eagle_dev_mendel_trios(ctx, g.p(), g.nplanes, g.n, g.lp, d_trios.as<int32_t>(), ntrios, d_out.as<int32_t>(),
+                                    marker_out ? d_marker.as<int32_t>() : nullptr, ctx->stream);
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    HIPCHK(ctx, hipMemcpyAsync(trio_out, d_out.p, sizeof(int32_t) * 6 * T, hipMemcpyDeviceToHost, ctx->stream));
+    if (marker_out) HIPCHK(ctx, hipMemcpyAsync(marker_out, d_marker.p, sizeof(int32_t) * (size_t)g.lp, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return EAGLE_OK;
+}
+
+// Everything of rules 6 and 7 that is decided before the context is used.
+int parentage_check(eagle_ctx* ctx, const char* who, long n, long lp, const int32_t* offspring, long n_o, const int32_t* sires, long n_s,
+                    const int32_t* dams, long n_d, long min_overlap, long allow_self) {
+    char msg[160];
+    if (const char* bad = parentage_arg_error(lp, n_o, n_s, n_d, min_overlap, allow_self)) {
+        snprintf(msg, sizeof msg, "%s: %s", who, bad);
+        return qc_fail(ctx, EAGLE_ERR_ARG, msg);
+    }
+    if ((n_s > 0 && !sires) || (n_d > 0 && !dams)) {
+        snprintf(msg, sizeof msg, "%s: NULL argument (a candidate list with a positive length)", who);
+        return qc_fail(ctx, EAGLE_ERR_ARG, msg);
+    }
+    const struct { const char* name; const int32_t* list; long cnt; } lists[3] = {{"offspring", offspring, n_o}, {"sires", sires, n_s}, {"dams", dams, n_d}};
+    for (const auto& l : lists) {
+        bool dup = false;
+        const long k = parentage_list_check(l.list, l.cnt, n, &dup);
+        if (k >= 0) {
+            snprintf(msg, sizeof msg, dup ? "%s: %s entry %ld is a duplicate" : "%s: %s entry %ld is outside [0, n)", who, l.name, k);
+            return qc_fail(ctx, EAGLE_ERR_ARG, msg);
+        }
+    }
+    return EAGLE_OK;
+}
+
+long par_pad(long cnt) { return ((cnt > 0 ? cnt : 1) + 63) / 64 * 64; }
+// Offspring of one launch: the partials of a chunk stay under 256 MiB (12 bytes an entry, two entries a part), and gridDim.y under 65536.
+long parentage_chunk(long n_o, long n_s, long n_d) {
+    const long per = 24 * eagle_parentage_parts(n_s, n_d);
+    return std::max(1L, std::min(std::min(n_o, 65535L), ((long)1 << 28) / per));
+}
+// The gathered sub-planes of the three lists, the partials of a chunk, the rows and the lists.
+size_t parentage_extra_bytes(int nplanes, long lp, long n_o, long n_s, long n_d) {
+    const size_t nwords = (size_t)((lp + 63) / 64);
+    return sizeof(uint64_t) * (size_t)nplanes * nwords * (size_t)(par_pad(n_o) + par_pad(n_s) + par_pad(n_d)) +
+           (size_t)24 * (size_t)eagle_parentage_parts(n_s, n_d) * (size_t)parentage_chunk(n_o, n_s, n_d) + (size_t)36 * (size_t)n_o +
+           sizeof(int32_t) * (size_t)(n_s + n_d + 2);
+}
+
+// The gathers of the three lists, the chunks of offspring and the download of the rows.
+int parentage_run(eagle_ctx* ctx, GenoPlanes& g, const int32_t* offspring, long n_o, const int32_t* sires, long n_s, const int32_t* dams, long n_d,
+                  int min_overlap, int allow_self, int32_t* best_out) {
+    const size_t nwords = (size_t)((g.lp + 63) / 64);
+    const int32_t unknown = -1;
+    struct Side { const int32_t* list; long cnt; DevBuf idx, sub; } side[3] = {{offspring, n_o, {}, {}}, {sires, n_s, {}, {}}, {dams, n_d, {}, {}}};
+    for (Side& sd : side) {
+        const long cnt = sd.cnt > 0 ? sd.cnt : 1;            // an empty list: the one index -1
+        HIPCHK(ctx, sd.idx.alloc(sizeof(int32_t) * (size_t)cnt));
+        HIPCHK(ctx, sd.sub.alloc(sizeof(uint64_t) * (size_t)g.nplanes * nwords * (size_t)par_pad(cnt)));
+        HIPCHK(ctx, hipMemcpyAsync(sd.idx.p, sd.cnt > 0 ? sd.list : &unknown, sizeof(int32_t) * (size_t)cnt, hipMemcpyHostToDevice, ctx->stream));
+        int rc = eagle_dev_plane_gather(ctx, g.p(), g.nplanes, g.n, g.lp, sd.idx.as<int32_t>(), cnt, sd.sub.as<uint64_t>(), ctx->stream);
+        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    }
+    const long chunk = parentage_chunk(n_o, n_s, n_d), nparts = eagle_parentage_parts(n_s, n_d);
+    DevBuf part_k, part_n, best;
+    HIPCHK(ctx, part_k.alloc(sizeof(uint64_t) * 2 * (size_t)nparts * (size_t)chunk));
+    HIPCHK(ctx, part_n.alloc(sizeof(int32_t) * 2 * (size_t)nparts * (size_t)chunk));
+    HIPCHK(ctx, best.alloc(sizeof(int32_t) * 8 * (size_t)n_o));
+    for (long o0 = 0; o0 < n_o; o0 += chunk) {               // stream order: a chunk's finish has read the partials before the next one writes them
+        int rc = eagle_dev_parentage(ctx, side[0].sub.as<uint64_t>(), n_o, side[1].sub.as<uint64_t>(), n_s, side[2].sub.as<uint64_t>(), n_d, g.nplanes,
+                                     g.lp, side[0].idx.as<int32_t>(), side[1].idx.as<int32_t>(), side[2].idx.as<int32_t>(), o0, std::min(chunk, n_o - o0),
+                                     min_overlap, allow_self, part_k.as<uint64_t>(), part_n.as<int32_t>(), best.as<int32_t>(), ctx->stream);
+        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    }
+    HIPCHK(ctx, hipMemcpyAsync(best_out, best.p, sizeof(int32_t) * 8 * (size_t)n_o, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // `unknown` and the buffers leave with this frame
+    return EAGLE_OK;
+}
+
+}  // namespace
+
+extern "C" int eagle_mendel(eagle_ctx* ctx, const char* f_name_ascii_M, const long dims[2], const int32_t* trios, long ntrios,
+                            double max_memory_in_Gbytes, int32_t* trio_out, int32_t* marker_out) {
+    if (!f_name_ascii_M || !dims || !trios || !trio_out) return qc_fail(ctx, EAGLE_ERR_ARG, "mendel: NULL argument");
+    const long n = dims[0], L = dims[1];
+    if (n <= 0 || L <= 0) return qc_fail(ctx, EAGLE_ERR_ARG, "mendel: dims must be positive");
+    if (int rc = mendel_check(ctx, "mendel", n, L, trios, ntrios)) return rc;
+    if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "mendel: no context");
+    GenoPlanes g;
+    int rc = g.build(ctx, "mendel", false, f_name_ascii_M, n, L, nullptr, L, max_memory_in_Gbytes, mendel_extra_bytes(L, ntrios, marker_out != nullptr),
+                     "the per-trio and per-marker arrays");
+    if (rc) return rc;
+    return mendel_run(ctx, g, trios, ntrios, trio_out, marker_out);
+}
+
+extern "C" int eagle_bed_mendel(eagle_ctx* ctx, const char* bed_path, const long dims[2], const uint8_t* include, const int32_t* trios, long ntrios,
+                                double max_memory_in_Gbytes, int32_t* trio_out, int32_t* marker_out) {
+    if (!bed_path || !dims || !trios || !trio_out) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_mendel: NULL argument");
+    const long n = dims[0], L = dims[1];
+    if (n <= 0 || L <= 0) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_mendel: dims must be positive");
+    if (n > 0x3fffffffL) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_mendel: 2^30 individuals or more");
+    const long linc = bedld_count(include, L);
+    if (linc < 1) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_mendel: include selects no marker");
+    if (int rc = mendel_check(ctx, "bed_mendel", n, linc, trios, ntrios)) return rc;
+    if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_mendel: no context");
+    GenoPlanes g;
+    int rc = g.build(ctx, "bed_mendel", true, bed_path, n, L, include, linc, max_memory_in_Gbytes,
+                     mendel_extra_bytes(linc, ntrios, marker_out != nullptr), "the per-trio and per-marker arrays");
+    if (rc) return rc;
+    return mendel_run(ctx, g, trios, ntrios, trio_out, marker_out);
+}
+
+extern "C" int eagle_parentage(eagle_ctx* ctx, const char* f_name_ascii_M, const long dims[2], const int32_t* offspring, long n_o, const int32_t* sires,
+                               long n_s, const int32_t* dams, long n_d, long min_overlap, int allow_self, double max_memory_in_Gbytes,
+                               int32_t* best_out) {
+    if (!f_name_ascii_M || !dims || !offspring || !best_out) return qc_fail(ctx, EAGLE_ERR_ARG, "parentage: NULL argument");
+    const long n = dims[0], L = dims[1];
+    if (n <= 0 || L <= 0) return qc_fail(ctx, EAGLE_ERR_ARG, "parentage: dims must be positive");
+    if (int rc = parentage_check(ctx, "parentage", n, L, offspring, n_o, sires, n_s, dams, n_d, min_overlap, allow_self)) return rc;
+    if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "parentage: no context");
+    GenoPlanes g;
+    int rc = g.build(ctx, "parentage", false, f_name_ascii_M, n, L, nullptr, L, max_memory_in_Gbytes, parentage_extra_bytes(2, L, n_o, n_s, n_d),
+                     "the candidates' planes and the partial minima");
+    if (rc) return rc;
+    return parentage_run(ctx, g, offspring, n_o, sires, n_s, dams, n_d, (int)min_overlap, allow_self, best_out);
+}
+
+extern "C" int eagle_bed_parentage(eagle_ctx* ctx, const char* bed_path, const long dims[2], const uint8_t* include, const int32_t* offspring, long n_o,
+                                   const int32_t* sires, long n_s, const int32_t* dams, long n_d, long min_overlap, int allow_self,
+                                   double max_memory_in_Gbytes, int32_t* best_out) {
+    if (!bed_path || !dims || !offspring || !best_out) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_parentage: NULL argument");
+    const long n = dims[0], L = dims[1];
+    if (n <= 0 || L <= 0) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_parentage: dims must be positive");
+    if (n > 0x3fffffffL) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_parentage: 2^30 individuals or more");
+    const long linc = bedld_count(include, L);
+    if (linc < 1) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_parentage: include selects no marker");
+    if (int rc = parentage_check(ctx, "bed_parentage", n, linc, offspring, n_o, sires, n_s, dams, n_d, min_overlap, allow_self)) return rc;
+    if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "bed_parentage: no context");
+    GenoPlanes g;
+    int rc = g.build(ctx, "bed_parentage", true, bed_path, n, L, include, linc, max_memory_in_Gbytes, parentage_extra_bytes(3, linc, n_o, n_s, n_d),
+                     "the candidates' planes and the partial minima");
+    if (rc) return rc;
+    return parentage_run(ctx, g, offspring, n_o, sires, n_s, dams, n_d, (int)min_overlap, allow_self, best_out);
 }
 
 // The loci's rows are gathered into a 64-row image first (k_gather_rows_i8: from the resident image, else from their own lines of

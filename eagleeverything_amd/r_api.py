@@ -1458,6 +1458,220 @@ def ibd_kinship(ibs1, ibs2):
     return (a + b) / 4.0
 
 
+# ---- Mendel errors and parentage assignment (include/eagle_hip.h section 1b'''viii): the restatement in numpy and the interface ----
+def ReadFam(path):
+    """The pedigree of a PLINK .fam file (family, individual, father, mother, sex, phenotype per line) -> {"FID", "IID", "Father",
+    "Mother", "Sex", "Pheno"}: lists of strings, one entry per individual in file order (the order of the .bed file's individuals)."""
+    keys = ("FID", "IID", "Father", "Mother", "Sex", "Pheno")
+    out = {k: [] for k in keys}
+    with open(path) as f:
+        for ln, line in enumerate(f, 1):
+            t = line.split()
+            if not t:
+                continue
+            if len(t) < 6:
+                raise ValueError("%s line %d: a .fam line has 6 fields, found %d" % (path, ln, len(t)))
+            for k, v in zip(keys, t):
+                out[k].append(v)
+    return out
+
+
+def fam_trios(fam):
+    """The trios a .fam file records -> int32 (T, 3) of (child, father, mother) as individual indices in file order.  fam = ReadFam's dict
+    or a path.  A parent is looked up inside the child's family; one named 0 or not in the file becomes -1, and individuals with no known
+    parent are dropped.  ValueError for an individual listed twice, one that is its own parent, or one whose two parents are the same
+    individual."""
+    fam = ReadFam(fam) if isinstance(fam, (str, os.PathLike)) else fam
+    index = {}
+    for i, key in enumerate(zip(fam["FID"], fam["IID"])):
+        if key in index:
+            raise ValueError("fam_trios: individual %s %s is listed twice" % key)
+        index[key] = i
+    rows = []
+    for i, (fid, iid, pa, ma) in enumerate(zip(fam["FID"], fam["IID"], fam["Father"], fam["Mother"])):
+        f = -1 if pa == "0" else index.get((fid, pa), -1)
+        m = -1 if ma == "0" else index.get((fid, ma), -1)
+        if f < 0 and m < 0:
+            continue
+        if f == i or m == i or f == m:
+            raise ValueError("fam_trios: individual %s %s is its own parent or has one individual as both parents" % (fid, iid))
+        rows.append((i, f, m))
+    return np.asarray(rows, dtype=np.int32).reshape(-1, 3)
+
+
+def _mendel_planes(who, g, called):
+    G = np.asarray(g)
+    if G.ndim != 2 or G.shape[0] < 1 or G.shape[1] < 1 or G.min() < -1 or G.max() > 1:
+        raise ValueError("%s: g must be (L, n) with values -1, 0, +1" % who)
+    Cm = np.ones(G.shape, dtype=bool) if called is None else np.asarray(called, dtype=bool)
+    if Cm.shape != G.shape:
+        raise ValueError("%s: called must have the shape of g" % who)
+    return (G == -1) & Cm, (G == 1) & Cm, Cm
+
+
+def mendel_host(g, called, trios):
+    """rcpp_api.mendel / bed_mendel restated in numpy: g = int8 (L, n) with -1 hom A1, 0 het, +1 hom A2, called = bool (L, n) or None
+    (everything called; ibd_genotypes_bed gives both from .bed codes), trios = int (T, 3) -> (trio int32 (T, 6), marker int32 (L)),
+    rules 3 to 5 of include/eagle_hip.h section 1b'''viii by the plane formula on boolean columns.  tests/mendel_truth.py pins it to
+    loops over allele sets."""
+    A, B, Cm = _mendel_planes("mendel_host", g, called)
+    L, n = A.shape
+    tr = rcpp_api.mendel_trios("mendel_host", trios, n)
+    out = np.zeros((tr.shape[0], 6), dtype=np.int32)
+    marker = np.zeros(L, dtype=np.int64)
+    none = np.zeros(L, dtype=bool)
+    for k, (c, f, m) in enumerate(tr.tolist()):
+        Ac, Bc, Cc = A[:, c], B[:, c], Cm[:, c]
+        Af, Bf, Cf = (A[:, f], B[:, f], Cm[:, f]) if f >= 0 else (none, none, none)
+        Am, Bm, Cmo = (A[:, m], B[:, m], Cm[:, m]) if m >= 0 else (none, none, none)
+        Hc = Cc & ~Ac & ~Bc
+        X = (Ac & Bf) | (Bc & Af)
+        E = X | ((Ac | (Hc & Bf)) & Bm) | ((Bc | (Hc & Af)) & Am)
+        out[k] = (np.count_nonzero(Cc & Cf), np.count_nonzero(X), np.count_nonzero(Cc & Cmo), np.count_nonzero((Ac & Bm) | (Bc & Am)),
+                  np.count_nonzero(Cc & Cf & Cmo), np.count_nonzero(E))
+        marker += E
+    return out, marker.astype(np.int32)
+
+
+def parentage_host(g, called, offspring, sires=None, dams=None, min_overlap=1, allow_self=False):
+    """rcpp_api.parentage / bed_parentage restated in numpy -> int32 (n_o, 2, 4): rule 6 of include/eagle_hip.h section 1b'''viii.  With
+    x, u, v of rule 3 for a (child, sire), the errors of the candidate (s, d) are |x| + |u & ~x & B_d| + |v & ~x & A_d| -- the three
+    parts are disjoint -- so all candidates of an offspring are two matrix products of 0 / 1 entries (exact in fp64: every count is
+    below 2^31).  The ranking is a lexicographic sort on (e, ordinal)."""
+    A, B, Cm = _mendel_planes("parentage_host", g, called)
+    L, n = A.shape
+    o, s, d, mo, selfing = rcpp_api.parentage_lists("parentage_host", offspring, sires, dams, n, min_overlap, allow_self)
+    none, ones = np.zeros((L, 1), dtype=bool), np.ones((L, 1), dtype=bool)
+    As, Bs, Cs = (A[:, s], B[:, s], Cm[:, s]) if s.size else (none, none, ones)      # the unknown parent: no genotype; it does not
+    Ad, Bd, Cd = (A[:, d], B[:, d], Cm[:, d]) if d.size else (none, none, ones)      # lower the overlap of the other two
+    si = s.astype(np.int64) if s.size else np.array([-1], dtype=np.int64)
+    di = d.astype(np.int64) if d.size else np.array([-1], dtype=np.int64)
+    Adf, Bdf, Cdf = (x.astype(np.float64) for x in (Ad, Bd, Cd))
+    best = np.full((o.size, 2, 4), -1, dtype=np.int32)
+    for k, c in enumerate(o.tolist()):
+        Ac, Bc, Cc = A[:, c:c + 1], B[:, c:c + 1], Cm[:, c:c + 1]
+        Hc = Cc & ~Ac & ~Bc
+        X = (Ac & Bs) | (Bc & As)
+        U = (Ac | (Hc & Bs)) & ~X
+        V = (Bc | (Hc & As)) & ~X
+        e = X.sum(axis=0)[:, None] + np.rint(U.T.astype(np.float64) @ Bdf + V.T.astype(np.float64) @ Adf).astype(np.int64)
+        ov = np.rint((Cc & Cs).T.astype(np.float64) @ Cdf).astype(np.int64)
+        ok = (si[:, None] != c) & (di[None, :] != c) & (ov >= mo)
+        if not selfing:
+            ok &= (si[:, None] != di[None, :]) | (si[:, None] < 0)
+        flat = np.flatnonzero(ok.ravel())                   # the ordinals of the admissible candidates, increasing
+        order = flat[np.argsort(e.ravel()[flat], kind="stable")][:2]
+        for r, q in enumerate(order.tolist()):
+            best[k, r] = (si[q // di.size], di[q % di.size], e.ravel()[q], ov.ravel()[q])
+    return best
+
+
+def mendel_summary(trios, tab, marker, n):
+    """Mendel's result from the integer outputs: the rates are the only fp64 divisions."""
+    tr = np.asarray(trios, dtype=np.int64).reshape(-1, 3)
+    tab = np.asarray(tab)
+    e = tab[:, 5].astype(np.int64)
+    possible = tab[:, 0].astype(np.int64) + tab[:, 2] - tab[:, 4]      # the child and at least one parent are called
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rate = np.where(possible > 0, e / possible.astype(np.float64), np.nan)
+    as_child, as_parent = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+    np.add.at(as_child, tr[:, 0], e)
+    for col in (1, 2):
+        known = tr[:, col] >= 0
+        np.add.at(as_parent, tr[known, col], e[known])
+    out = {"trios": np.asarray(trios, dtype=np.int32).reshape(-1, 3), "n_cf": tab[:, 0].copy(), "e_cf": tab[:, 1].copy(), "n_cm": tab[:, 2].copy(),
+           "e_cm": tab[:, 3].copy(), "n_trio": tab[:, 4].copy(), "errors": tab[:, 5].copy(), "rate": rate, "errors_as_child": as_child,
+           "errors_as_parent": as_parent, "trio": tab}
+    if marker is not None:
+        out["marker_errors"] = marker
+        out["marker_rate"] = marker / np.float64(tr.shape[0])
+    return out
+
+
+def Mendel(geno, trios=None, fam=None, bed=None, include=None, map=None, availmemGb=8, device=0):
+    """Is the recorded pedigree right?  The Mendel errors of every trio of a pedigreed panel (include/eagle_hip.h section 1b'''viii;
+    rcpp_api.mendel; what PLINK reports as --mendel, agreement with that program is not claimed; every marker is taken as autosomal)
+    -> {"trios": int32 (T, 3) of (child, father, mother), -1 = unknown, "n_cf", "e_cf", "n_cm", "e_cm", "n_trio", "errors": int32 (T)
+    (markers called in child and father, their opposite homozygotes, the same for the mother, markers called in all three, Mendel
+    errors), "rate": fp64 (T) = errors / the markers where the child and at least one parent are called (NaN when there is none),
+    "errors_as_child", "errors_as_parent": int64 (n), the errors of the trios an individual is in, "marker_errors": int32 (L), the
+    trios with an error at each marker, "marker_rate" = marker_errors / T, "trio": the table as returned; with a map also "SNP"}.
+    trios = int (T, 3), or fam = a .fam file (or ReadFam's dict) whose recorded trios are used (fam_trios; default: the .fam of bed).
+    On the ingested (het-filled) panel a missing call is a het, which both hides errors (a het parent passes either allele) and makes
+    them (a het child of two equal homozygotes); bed = the .bed file (or prefix) the panel was ingested from is the route for
+    un-imputed panels: a child that is not called has no error and a parent that is not called can pass either allele
+    (rcpp_api.bed_mendel); include = the panel's markers in the file, default geno's marker_index.  mendel_keep_mask turns
+    marker_errors into a marker filter."""
+    n, L, _, _, src_bed, bdims, inc = _ld_stats_source("Mendel", geno, map, bed, include)
+    if trios is None:
+        if fam is None and src_bed is None:
+            raise ValueError("Mendel: give trios=, fam= or bed=")
+        fam = bed_fileset(src_bed)[2] if fam is None else fam
+        famd = ReadFam(fam) if isinstance(fam, (str, os.PathLike)) else fam
+        if len(famd["IID"]) != n:
+            raise ValueError("Mendel: the .fam names %d individuals, the panel holds %d" % (len(famd["IID"]), n))
+        trios = fam_trios(famd)
+        if trios.shape[0] == 0:
+            raise ValueError("Mendel: the .fam records no parent")
+    tr = rcpp_api.mendel_trios("Mendel", trios, n)
+    if src_bed is None:
+        tab, marker = rcpp_api.mendel(geno["asciifileM"], (n, L), tr, availmemGb, device=device)
+    else:
+        tab, marker = rcpp_api.bed_mendel(src_bed, bdims, tr, inc, availmemGb, device=device)
+    out = mendel_summary(tr, tab, marker, n)
+    if map is not None and "SNP" in map:
+        out["SNP"] = list(map["SNP"])
+    return out
+
+
+def mendel_keep_mask(marker_err, ntrios, max_rate=0.1):
+    """bool (L): the markers whose share of trios with a Mendel error is at most max_rate (PLINK's --me per-marker threshold), from
+    Mendel's marker_errors -- compared as integers: marker_err <= floor(max_rate * ntrios)."""
+    e = np.asarray(marker_err)
+    ntrios = int(ntrios)
+    if ntrios < 1 or not 0.0 <= float(max_rate) <= 1.0:
+        raise ValueError("mendel_keep_mask: ntrios must be at least 1 and max_rate in [0, 1]")
+    if e.size and (e.min() < 0 or e.max() > ntrios):
+        raise ValueError("mendel_keep_mask: a marker with more errors than trios")
+    return e <= int(np.floor(float(max_rate) * ntrios))
+
+
+def parentage_summary(offspring, best, max_rate=0.01):
+    """Parentage's result from the rows of rcpp_api.parentage."""
+    b = np.asarray(best).reshape(-1, 2, 4)
+    has, has2 = b[:, 0, 2] >= 0, b[:, 1, 2] >= 0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rate = np.where(has & (b[:, 0, 3] > 0), b[:, 0, 2] / b[:, 0, 3].astype(np.float64), np.nan)
+    return {"offspring": np.asarray(offspring, dtype=np.int32), "sire": b[:, 0, 0].copy(), "dam": b[:, 0, 1].copy(), "errors": b[:, 0, 2].copy(),
+            "overlap": b[:, 0, 3].copy(), "rate": rate, "runner_sire": b[:, 1, 0].copy(), "runner_dam": b[:, 1, 1].copy(),
+            "runner_errors": b[:, 1, 2].copy(), "gap": np.where(has2, b[:, 1, 2] - b[:, 0, 2], -1).astype(np.int32),
+            "assigned": has & (rate <= float(max_rate)), "best": b}
+
+
+def Parentage(geno, offspring, sires=None, dams=None, bed=None, include=None, min_overlap=1, allow_self=False, max_rate=0.01, availmemGb=8,
+              device=0):
+    """Who are the parents?  For every offspring the pair (sire, dam) of the candidate lists with the fewest Mendel errors, by an
+    exhaustive search on the device (include/eagle_hip.h section 1b'''viii rule 6; rcpp_api.parentage) -> {"offspring", "sire", "dam":
+    int32 individual indices (-1: none, or the unknown parent), "errors", "overlap": int32, "rate": fp64 = errors / overlap,
+    "runner_sire", "runner_dam", "runner_errors": the second-best candidate, "gap": runner_errors - errors (-1 without a runner-up; a
+    small gap is an ambiguous assignment, e.g. full sibs among the candidates), "assigned": bool, rate <= max_rate, "best": the rows as
+    returned}.  offspring, sires, dams = lists of individual indices without duplicates; an individual may be in several lists and is
+    never its own parent.  sires or dams None (or empty) assigns one parent alone.  allow_self admits a candidate that is sire and dam
+    at once (selfing plants).  THE RANK IS BY ERROR COUNT, NOT BY RATE: with bed = the .bed file (or prefix) the overlap of a candidate
+    is the number of markers called in all three, and min_overlap keeps candidates with few called markers from winning by having had
+    few chances to err; on the ingested panel every overlap is L.  Ties go to the candidate earlier in the lists.  The errors of the
+    true parents are the genotyping errors, so max_rate is set from the chip's error rate; every marker is taken as autosomal."""
+    n, L, _, _, src_bed, bdims, inc = _ld_stats_source("Parentage", geno, None, bed, include)
+    lists = rcpp_api.parentage_lists("Parentage", offspring, sires, dams, n, min_overlap, allow_self)
+    if not 0.0 <= float(max_rate) <= 1.0:
+        raise ValueError("Parentage: max_rate must be in [0, 1]")
+    if src_bed is None:
+        best = rcpp_api.parentage(geno["asciifileM"], (n, L), lists[0], lists[1], lists[2], lists[3], bool(lists[4]), availmemGb, device=device)
+    else:
+        best = rcpp_api.bed_parentage(src_bed, bdims, lists[0], lists[1], lists[2], inc, lists[3], bool(lists[4]), availmemGb, device=device)
+    return parentage_summary(lists[0], best, max_rate)
+
+
 # ---- GRM and PCA (include/eagle_hip.h section 1b''''): the exact weighted Gram product on the device, fp64 arithmetic on the host ----
 GRM_QMAX = 2097151    # 2^21 - 1: the largest weight rcpp_api.weighted_gram takes
 

@@ -1141,6 +1141,135 @@ def bed_ibd(bed_path, dims, include=None, pairs=None, chrom=None, pos=None, avai
     return _ibd_call(L.eagle_bed_ibd, device, head, pr, ch, ps, prm, availmemGb, n, cap)
 
 
+# ---- Mendel errors and parentage assignment (include/eagle_hip.h section 1b'''viii): exact integers on the IBD bit planes ----
+MENDEL_MAX_TRIOS = 1 << 27
+
+
+def _whole_int32(who, what, x, ndim):
+    a = np.asarray(x)
+    if a.ndim != ndim:
+        raise ValueError("%s: %s must be a %d-dimensional list of whole numbers" % (who, what, ndim))
+    if a.size == 0:
+        return np.zeros(a.shape, dtype=np.int32)
+    if a.dtype == bool or a.dtype.kind not in "iuf":
+        raise ValueError("%s: %s must be whole numbers" % (who, what))
+    if not np.all(np.isfinite(a)) or not np.array_equal(np.floor(a), a) or a.min() < -(1 << 31) or a.max() >= 1 << 31:
+        raise ValueError("%s: %s must be whole numbers that fit int32" % (who, what))
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def mendel_trios(who, trios, n):
+    """A trio list as contiguous int32 (T, 3) of (child, father, mother); ValueError for a count outside [1, 2^27] or a trio that is not
+    0 <= c < n, -1 <= f, m < n (-1: unknown), c != f, c != m, f != m unless both are -1."""
+    a = np.asarray(trios)
+    if a.ndim != 2 or a.shape[1] != 3 or a.shape[0] < 1 or a.shape[0] > MENDEL_MAX_TRIOS:
+        raise ValueError("%s: the number of trios must be in [1, 2^27] (rows of child, father, mother)" % who)
+    t = _whole_int32(who, "trios", a, 2).astype(np.int64)
+    c, f, m = t[:, 0], t[:, 1], t[:, 2]
+    bad = np.flatnonzero((c < 0) | (c >= n) | (f < -1) | (f >= n) | (m < -1) | (m >= n) | (c == f) | (c == m) | ((f == m) & (f >= 0)))
+    if bad.size:
+        raise ValueError("%s: trio %d is not (c, f, m) with 0 <= c < n, -1 <= f, m < n, c != f, c != m, f != m" % (who, int(bad[0])))
+    return np.ascontiguousarray(t, dtype=np.int32)
+
+
+def parentage_lists(who, offspring, sires, dams, n, min_overlap=1, allow_self=False):
+    """The three index lists of a parentage call as contiguous int32 (None or empty: no list), min_overlap and allow_self as ints;
+    ValueError for an index outside [0, n), a duplicate inside a list, no offspring, both candidate lists empty, sires x dams >= 2^31,
+    a min_overlap outside [0, 2^31) or an allow_self that is not a truth value."""
+    out = []
+    for what, x in (("offspring", offspring), ("sires", sires), ("dams", dams)):
+        a = _whole_int32(who, what, [] if x is None else x, 1)
+        if a.size and (a.min() < 0 or a.max() >= n):
+            raise ValueError("%s: %s entry %d is outside [0, n)" % (who, what, int(np.flatnonzero((a < 0) | (a >= n))[0])))
+        if np.unique(a).size != a.size:
+            raise ValueError("%s: %s holds a duplicate" % (who, what))
+        out.append(a)
+    o, s, d = out
+    if o.size < 1 or o.size > MENDEL_MAX_TRIOS:
+        raise ValueError("%s: the number of offspring must be in [1, 2^27]" % who)
+    if s.size == 0 and d.size == 0:
+        raise ValueError("%s: both candidate lists are empty" % who)
+    if max(s.size, 1) * max(d.size, 1) >= 1 << 31:
+        raise ValueError("%s: sires x dams must be below 2^31" % who)
+    try:
+        mo = int(min_overlap)
+    except (TypeError, ValueError):
+        raise ValueError("%s: min_overlap must be a whole number" % who)
+    if mo != min_overlap or not 0 <= mo < 1 << 31:
+        raise ValueError("%s: min_overlap must be a whole number in [0, 2^31)" % who)
+    if allow_self not in (0, 1, False, True):
+        raise ValueError("%s: allow_self must be 0 or 1" % who)
+    return o, s, d, mo, int(bool(allow_self))
+
+
+def _mendel_call(fn, device, head, tr, nm, mem, markers):
+    out = np.zeros((tr.shape[0], 6), dtype=np.int32)
+    mk = np.zeros(nm, dtype=np.int32) if markers else None
+    _args_first(fn, device, head + (tr.ctypes.data_as(_c_i32p), tr.shape[0], float(mem), out.ctypes.data_as(_c_i32p),
+                                    mk.ctypes.data_as(_c_i32p) if markers else None))
+    return out, mk
+
+
+def mendel(f_name_ascii_M, dims, trios, max_memory_in_Gbytes=8.0, device=0, markers=True):
+    """eagle_mendel -> (trio int32 (T, 6), marker int32 (L) or None): the Mendel errors of include/eagle_hip.h section 1b'''viii on the
+    ingested panel M.ascii (dims = (n, L) of M).  trios: int (T, 3) of (child, father, mother) individual indices, -1 = unknown parent.
+    trio rows = (n_cf, e_cf, n_cm, e_cm, n_trio, e): markers called in child and father, their opposite homozygotes, the same for the
+    mother, markers called in all three, Mendel errors.  marker = the trios of the list with an error at each marker (markers=False:
+    not computed).  ValueError for bad arguments before the library is called.  r_api.mendel_host is the numpy restatement."""
+    L = _lib.load()
+    n, nm = max(int(dims[0]), 0), max(int(dims[1]), 0)
+    tr = mendel_trios("mendel", trios, n)
+    if nm >= 1 << 31:
+        raise ValueError("mendel: 2^31 markers or more")
+    return _mendel_call(L.eagle_mendel, device, (os.fsencode(f_name_ascii_M), _dims(dims)), tr, nm, max_memory_in_Gbytes, markers)
+
+
+def bed_mendel(bed_path, dims, trios, include=None, availmemGb=8.0, device=0, markers=True):
+    """eagle_bed_mendel -> mendel's pair by PANEL marker from a SNP-major PLINK .bed file of dims = (n individuals, L markers), which
+    still knows its missing calls: a child that is not called has no error, a parent that is not called can pass either allele.
+    include as in bed_ld_window."""
+    L = _lib.load()
+    n, nm = max(int(dims[0]), 0), max(int(dims[1]), 0)
+    inc = _bed_ld_include(include, nm, "bed_mendel")
+    linc = nm if inc is None else int(inc.sum())
+    tr = mendel_trios("bed_mendel", trios, n)
+    head = (os.fsencode(bed_path), _dims(dims), inc.ctypes.data_as(C.c_void_p) if inc is not None else None)
+    return _mendel_call(L.eagle_bed_mendel, device, head, tr, linc, availmemGb, markers)
+
+
+def _parentage_call(fn, device, head, lists, mem):
+    o, s, d, mo, selfing = lists
+    best = np.zeros((o.size, 2, 4), dtype=np.int32)
+    _args_first(fn, device, head + (o.ctypes.data_as(_c_i32p), o.size, s.ctypes.data_as(_c_i32p) if s.size else None, s.size,
+                                    d.ctypes.data_as(_c_i32p) if d.size else None, d.size, mo, selfing, float(mem), best.ctypes.data_as(_c_i32p)))
+    return best
+
+
+def parentage(f_name_ascii_M, dims, offspring, sires=None, dams=None, min_overlap=1, allow_self=False, max_memory_in_Gbytes=8.0, device=0):
+    """eagle_parentage -> int32 (n_o, 2, 4): per offspring the best and the runner-up candidate (sire, dam, Mendel errors, overlap) of the
+    exhaustive search over sires x dams (include/eagle_hip.h section 1b'''viii rule 6) on the ingested panel M.ascii (dims = (n, L) of
+    M), as individual indices; -1 rows where there is no such candidate.  An empty (or None) list is one unknown parent.  The rank is
+    by error count, ties to the earlier candidate.  ValueError for bad arguments before the library is called.  r_api.parentage_host is
+    the numpy restatement."""
+    L = _lib.load()
+    n, nm = max(int(dims[0]), 0), max(int(dims[1]), 0)
+    lists = parentage_lists("parentage", offspring, sires, dams, n, min_overlap, allow_self)
+    if nm >= 1 << 31:
+        raise ValueError("parentage: 2^31 markers or more")
+    return _parentage_call(L.eagle_parentage, device, (os.fsencode(f_name_ascii_M), _dims(dims)), lists, max_memory_in_Gbytes)
+
+
+def bed_parentage(bed_path, dims, offspring, sires=None, dams=None, include=None, min_overlap=1, allow_self=False, availmemGb=8.0, device=0):
+    """eagle_bed_parentage -> parentage's rows by PANEL marker from a SNP-major PLINK .bed file, where the overlap of a candidate is the
+    number of markers called in the child and both parents (the known one, in single-parent assignment) and must reach min_overlap."""
+    L = _lib.load()
+    n, nm = max(int(dims[0]), 0), max(int(dims[1]), 0)
+    inc = _bed_ld_include(include, nm, "bed_parentage")
+    lists = parentage_lists("bed_parentage", offspring, sires, dams, n, min_overlap, allow_self)
+    head = (os.fsencode(bed_path), _dims(dims), inc.ctypes.data_as(C.c_void_p) if inc is not None else None)
+    return _parentage_call(L.eagle_bed_parentage, device, head, lists, availmemGb)
+
+
 # ---- GRM (include/eagle_hip.h section 1b''''): the exact weighted Gram product; weights, centring and PCA are r_api's ----
 WGRAM_MAX_WEIGHT = (1 << 21) - 1
 

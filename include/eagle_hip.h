@@ -776,6 +776,78 @@ int eagle_bed_ibd(eagle_ctx* ctx, const char* bed_path, const long dims[2], cons
                   int32_t* seg_out, long seg_cap, long* nseg_out);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1b'''viii. Mendel errors and parentage assignment (no counterpart in the reference): is the recorded pedigree right, and if not, who
+ *     are the parents?  The checks PLINK runs as --mendel / --me and the opposing-homozygote parentage assignment of SNP-chip panels, on
+ *     the bit planes of 1b'''vii.  Agreement with the PLINK program is neither claimed nor tested.  Sex chromosomes are not handled:
+ *     every marker is autosomal.  Setting erroneous genotypes to missing is out of scope.  Everything is integers, so the device and
+ *     numpy (r_api.mendel_host, r_api.parentage_host) agree with ==.
+ *
+ *     1. Genotype and called.  As rule 1 of 1b'''vii: image value -1 / 0 / +1 is hom A1 / het / hom A2, always called (a missing call
+ *        of the original data is a het by now); .bed codes 00 / 10 / 11 are hom A1 / het / hom A2 and code 01 is not called.
+ *     2. Trio.  (c, f, m) = child, father, mother as individual indices.  A parent index -1 is an unknown parent and behaves as an
+ *        individual that is called nowhere; a trio with both parents -1 is legal and has no errors.  0 <= c < n, -1 <= f, m < n,
+ *        c != f, c != m, and f != m unless both are -1 (selfing exists in rule 6 alone); else EAGLE_ERR_ARG.  Trios may repeat, and an
+ *        individual may be a child in one trio and a parent in another.
+ *     3. Mendel error at marker x.  The child is called, and no choice of one allele from each parent gives the child's genotype; a
+ *        not-called or unknown parent can pass either allele.  Of the 64 code triples (hom A1, het, hom A2, not called)^3 exactly 16
+ *        are errors.  On the planes A (hom A1), B (hom A2), C (called), with H_c = C_c & ~A_c & ~B_c:
+ *            X = A_c B_f | B_c A_f      U = A_c | H_c B_f      V = B_c | H_c A_f      E = X | U B_m | V A_m
+ *        which equals the definition on all 64 triples (tests/test_mendel_host.py enumerates them).  A and B imply called, so C is
+ *        needed for H_c and the overlap counts alone.  On the image C is implicit: every bit of a panel marker; the bits of the last
+ *        word past the last marker are masked, so they never become hets.
+ *     4. Per-trio output.  trio_out: ntrios x 6 int32 = (n_cf, e_cf, n_cm, e_cm, n_trio, e).  n_cf = markers where c and f are both
+ *        called, e_cf = opposite homozygotes of c and f; the same for m; n_trio = markers where all three are called; e =
+ *        popcount(E) over the panel.  An unknown parent is called nowhere: on the image n_* = L for known parents and 0 otherwise.
+ *     5. Per-marker output.  marker_out (may be NULL): int32 by panel marker, the number of trios OF THE LIST with an error there
+ *        (PLINK's .lmendel; a trio listed twice counts twice).  Integer sums: any order gives the same result.
+ *     6. Assignment.  offspring (n_o), sires (n_s) and dams (n_d) are lists of individual indices in [0, n); a duplicate inside a list
+ *        is EAGLE_ERR_ARG (an individual may be in several lists).  An empty dam list (n_d = 0, dams may be NULL) means one unknown dam:
+ *        single-parent assignment; likewise an empty sire list; both empty is EAGLE_ERR_ARG.  For the offspring c the admissible
+ *        candidates are the (s, d) with s != c, d != c, overlap >= min_overlap, and s != d unless allow_self.  overlap = n_trio of
+ *        (c, s, d); for single-parent assignment it is n_cf of the child and the one known parent (the unknown parent would make n_trio
+ *        0).  Candidates are ranked by the key (e, ordinal), ordinal = s_idx * max(n_d, 1) + d_idx with s_idx, d_idx the positions in
+ *        the lists; the smaller key wins, so ties in e go to the earlier candidate.  THE RANK IS BY ERROR COUNT, NOT BY ERROR RATE: a
+ *        candidate with few called markers is not penalised beyond min_overlap.  best_out: n_o x 2 x 4 int32, per offspring the best
+ *        and the runner-up as (sire, dam, e, overlap) with sire and dam as individual indices (-1 for the unknown parent); all four
+ *        are -1 where there is no such candidate.
+ *     7. Limits.  ntrios and n_o in [1, EAGLE_MENDEL_MAX_TRIOS = 2^27]; max(n_s, 1) * max(n_d, 1) < 2^31; 0 <= min_overlap < 2^31;
+ *        allow_self 0 or 1; panel markers < 2^31; n <= 0x3fffffff for the .bed file.  The planes (1b'''vii: 2, from the .bed file 3)
+ *        stay on the device for the call, with the per-trio and per-marker arrays or the gathered planes of the three lists and the
+ *        partial minima of a chunk of offspring (under 256 MiB): where they do not fit the memory budget (rule 9 of 1b'''vii) the call
+ *        returns EAGLE_ERR_NOMEM, decided before any kernel runs.
+ *
+ *     The planes are built as for eagle_ibd / eagle_bed_ibd (one helper serves all six entry points): the resident image, a streamed
+ *     panel, a VIEW alias, or the .bed windows that end on multiples of 64.  k_mendel_trios has one lane per trio; the per-marker
+ *     totals of a wave's 64 error words come from one ballot and one popcount per bit and reach the marker array through 32-bit
+ *     integer atomics.  k_plane_gather packs the words of each list word-major; k_parentage gives a wave one offspring, 64
+ *     consecutive dams and four sires a lane, keeps the two smallest keys (e << 32 | ordinal) with their overlaps per lane and
+ *     reduces them over the wave and the workgroup; k_parentage_finish merges the workgroups' partials.  No atomics on that path.
+ *
+ *     Single device: a multi-device context works on its first device.  Argument errors (EAGLE_ERR_ARG: a NULL pointer, dims <= 0,
+ *     and those named above) are decided before the context is used; with ctx == NULL their text is in eagle_open_error().
+ * ------------------------------------------------------------------------------------------- */
+#define EAGLE_MENDEL_MAX_TRIOS 134217728L
+
+/* Rules 1 to 5 on the ingested panel M.ascii (dims = (n, L) of M): trios is ntrios x 3 int32, trio_out ntrios x 6 int32, marker_out L
+ * int32 or NULL. */
+int eagle_mendel(eagle_ctx* ctx, const char* f_name_ascii_M, const long dims[2], const int32_t* trios, long ntrios,
+                 double max_memory_in_Gbytes, int32_t* trio_out, int32_t* marker_out);
+
+/* The same by PANEL marker (the Linc markers include selects, L bytes or NULL) from the SNP-major .bed file bed_path (dims = (n, L) of the
+ * file), which still knows its missing calls.  EAGLE_ERR_ARG also for n > 0x3fffffff and an include that selects no marker. */
+int eagle_bed_mendel(eagle_ctx* ctx, const char* bed_path, const long dims[2], const uint8_t* include, const int32_t* trios, long ntrios,
+                     double max_memory_in_Gbytes, int32_t* trio_out, int32_t* marker_out);
+
+/* Rule 6 on the ingested panel M.ascii: every overlap is L there.  best_out: n_o x 8 int32. */
+int eagle_parentage(eagle_ctx* ctx, const char* f_name_ascii_M, const long dims[2], const int32_t* offspring, long n_o, const int32_t* sires,
+                    long n_s, const int32_t* dams, long n_d, long min_overlap, int allow_self, double max_memory_in_Gbytes, int32_t* best_out);
+
+/* Rule 6 by panel marker from the .bed file, as eagle_bed_mendel reads it. */
+int eagle_bed_parentage(eagle_ctx* ctx, const char* bed_path, const long dims[2], const uint8_t* include, const int32_t* offspring, long n_o,
+                        const int32_t* sires, long n_s, const int32_t* dams, long n_d, long min_overlap, int allow_self,
+                        double max_memory_in_Gbytes, int32_t* best_out);
+
+/* ---------------------------------------------------------------------------------------------
  * 1b''''. Genomic relationship matrix (no counterpart that the reference calls: its VanRaden G, E/R/GenomicRel.R, is unused): the one
  *     Gram product the matrices of EIGENSTRAT / PLINK / GCTA and their principal components need, with a weight per marker.  With
  *     g in {-1, 0, +1} = AA, AB, BB as everywhere in this library and integer weights q_m < 2^21,
