@@ -60,7 +60,7 @@ static void arena_collect(eagle_ctx* ctx) {
         if (pf->bytes > ctx->arena_cap) {
             if (ctx->arena) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(ctx->arena); }
             ctx->arena = pf->p;
-            ctx->arena_S_ptr = nullptr;
+            ctx->arena_gen++;
             ctx->arena_cap = pf->bytes;
         } else (void)hipFree(pf->p);
     } else (void)hipGetLastError();
@@ -100,7 +100,7 @@ static int arena_reserve(eagle_ctx* ctx, size_t total) {
     arena_collect(ctx);
     if (total <= ctx->arena_cap) return EAGLE_OK;
     if (ctx->arena) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(ctx->arena); ctx->arena = nullptr; ctx->arena_cap = 0; }
-    ctx->arena_S_ptr = nullptr;
+    ctx->arena_gen++;
     hipError_t e = hipMalloc(&ctx->arena, total);
     if (e != hipSuccess && eagle_drop_f4_images(ctx) > 0) {   // the fp4 MM^T operand images kept with resident files are not in any budget
         (void)hipGetLastError();
@@ -321,14 +321,14 @@ template <class F> static int run_on_devices(eagle_ctx* ctx, F fn) {
     return EAGLE_OK;
 }
 
-// The resident genotype files AND the grow-only workspaces this context holds between calls (the scan arena -- a background reservation
-// in flight included --, the workspace of the int8 W products): everything a caller can get back without closing the context.
+// The resident genotype files AND what this context holds between calls (the scan arena -- a background reservation in flight included
+// --, the workspace of the int8 W products, the host copy of the cached S): everything a caller can get back without closing the context.
 static void drop_workspaces(eagle_ctx* c) {
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     arena_collect(c);
-    if (c->arena) { (void)hipFree(c->arena); c->arena = nullptr; c->arena_cap = 0; c->arena_off = 0; }
-    c->arena_S_ptr = nullptr;
+    if (c->arena) { (void)hipFree(c->arena); c->arena = nullptr; c->arena_cap = 0; c->arena_off = 0; c->arena_gen++; }
+    c->scache.forget_host();
     if (c->w8_ws) { (void)hipFree(c->w8_ws); c->w8_ws = nullptr; c->w8_ws_cap = 0; }
     if (c->w8_true_ws) { (void)hipFree(c->w8_true_ws); c->w8_true_ws = nullptr; c->w8_true_cap = 0; }
     c->w8_active = false;
@@ -365,8 +365,7 @@ extern "C" void eagle_close(eagle_ctx* ctx) {
     if (ctx->d_bound) (void)hipFree(ctx->d_bound);
     if (ctx->argmax_ws) (void)hipFree(ctx->argmax_ws);
     if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
-    if (ctx->d_Scache) (void)hipFree(ctx->d_Scache);
-    if (ctx->d_Sscr) (void)hipFree(ctx->d_Sscr);
+    ctx->scache.release();
     arena_collect(ctx);
     if (ctx->arena) (void)hipFree(ctx->arena);
     if (ctx->gemv_ws) (void)hipFree(ctx->gemv_ws);
@@ -380,8 +379,6 @@ extern "C" void eagle_close(eagle_ctx* ctx) {
     if (ctx->d_pack) (void)hipFree(ctx->d_pack);
     if (ctx->d_pack2) (void)hipFree(ctx->d_pack2);
     for (int b = 0; b < 2; b++) { if (ctx->stage_pin[b]) (void)hipHostFree(ctx->stage_pin[b]); if (ctx->stage_raw[b]) (void)hipFree(ctx->stage_raw[b]); }
-    if (ctx->h_flag) (void)hipHostFree(ctx->h_flag);
-    free(ctx->h_Scache);
     (void)hipStreamDestroy(ctx->stream);
     if (ctx->load_stream) (void)hipStreamDestroy(ctx->load_stream);
     delete ctx;
@@ -557,25 +554,13 @@ struct PhaseEvents {
     }
 };
 
-// any bit of two device arrays different -> *flag != 0 (the cached S against the caller's)
-__global__ __launch_bounds__(256) void k_bits_differ(const unsigned long long* __restrict__ a, const unsigned long long* __restrict__ b, long count,
-                                                     int* __restrict__ flag) {
-    int d = 0;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < count; i += (long)gridDim.x * 256) d |= a[i] != b[i];
-    if (__any(d) && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
-}
 static int upload_square_on(eagle_ctx* ctx, const double* host, long n, long np, double* dev, hipStream_t st) {
     HIPCHK(ctx, hipMemsetAsync(dev, 0, sizeof(double) * np * np, st));
     HIPCHK(ctx, hipMemcpy2DAsync(dev, sizeof(double) * np, host, sizeof(double) * n, sizeof(double) * n, n, hipMemcpyHostToDevice, st));
     return EAGLE_OK;
 }
 // column-major n x n host matrix -> zero padded np x np device image (row-major image of the transpose)
-static int upload_square(eagle_ctx* ctx, const double* host, long n, long np, double* dev) {
-    HIPCHK(ctx, hipMemsetAsync(dev, 0, sizeof(double) * np * np, ctx->stream));
-    HIPCHK(ctx, hipMemcpy2DAsync(dev, sizeof(double) * np, host, sizeof(double) * n, sizeof(double) * n, n,
-                                 hipMemcpyHostToDevice, ctx->stream));
-    return EAGLE_OK;
-}
+static int upload_square(eagle_ctx* ctx, const double* host, long n, long np, double* dev) { return upload_square_on(ctx, host, n, np, dev, ctx->stream); }
 // The same upload through the context's two pinned staging buffers: host threads copy piece k + 1 of the caller's pageable matrix into
 // one while the DMA of piece k runs out of the other (the runtime's own pageable path stages single-threaded: 25-27 GB/s on the GPU
 // boxes against 50+ this way).  Synchronous for the caller's memory: nothing of `host` is in flight when it returns.
@@ -1060,6 +1045,147 @@ extern "C" int eagle_last_mmt_normalised(eagle_ctx* ctx, double* MMt_norm_out, d
     return download_big(ctx, MMt_norm_out, tmp.p, sizeof(double) * (size_t)n * n);
 }
 
+// ------------------------------------------------------------------------------------------------
+// The cached S (SCache, eagle_ctx.h): every read and write of its state is in this section; the rule it follows is s_plan of eagle_host.h.
+// S = inv_MMt_sqrt is MMt^-1/2, the same matrix in every call of an AM() run, but R builds it anew each time (no pointer identity, and
+// hashing 800 MB costs what copying them costs): the copy of the last call stays on the device, this call computes on it at once, and
+// the caller's matrix is compared with it bit for bit while the card works; a difference starts the work over.
+// ------------------------------------------------------------------------------------------------
+static SPolicy scache_policy() {
+    SPolicy p;
+    p.no_scache = getenv("EAGLE_HIP_NO_SCACHE") != nullptr;
+    if (const char* m = getenv("EAGLE_HIP_SCACHE_MAX_NP")) p.max_np = atol(m);   // (tests force the large-n form at small sizes)
+    p.no_host_verify = getenv("EAGLE_HIP_NO_HOST_SVERIFY") != nullptr;
+    p.trust_s = getenv("EAGLE_HIP_EXPERIMENT_TRUST_S") != nullptr;
+    return p;
+}
+// any bit of two device arrays different -> *flag != 0 (the cached S against the caller's)
+__global__ __launch_bounds__(256) void k_bits_differ(const unsigned long long* __restrict__ a, const unsigned long long* __restrict__ b, long count,
+                                                     int* __restrict__ flag) {
+    int d = 0;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < count; i += (long)gridDim.x * 256) d |= a[i] != b[i];
+    if (__any(d) && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
+}
+// The helper thread's pass over the caller's n x n matrix on the cores that idle while the card works: copied into the host copy (the
+// device copy is, or is about to be, this caller's S), or compared with it (measured against the 800 MB upload + device comparison under
+// the vara kernel: 3.4 ms of the call's 141.5 at the headline size).
+static void scache_host_pass(SCache& c, const double* S_host, long n, bool copy) {
+    c.pending = true;
+    c.host_differs = 0;
+    c.helper = std::thread([&c, S_host, n, copy] {
+        std::atomic<int> differs{0};
+        parallel_for((long)(sizeof(double) * (size_t)n * (size_t)n), std::max(1, std::min(host_threads(), 16)), [&](long a, long b, int) {
+            if (copy) memcpy((char*)c.h_S + a, (const char*)S_host + a, (size_t)(b - a));
+            else if (memcmp((const char*)c.h_S + a, (const char*)S_host + a, (size_t)(b - a)) != 0) differs.store(1);
+        });
+        c.host_differs = differs.load();
+        if (copy) c.h_n = n;
+    });
+}
+// The S this call computes on: *Sa stays slot_S, the call's slot at the head of the arena (taken AFTER arena_reserve: the slot record is
+// judged at the generation the arena has now), or becomes the device copy.
+int SCache::acquire(eagle_ctx* ctx, const SCall& call, const SPolicy& pol, const double* S_host, double* slot_S, double** Sa) {
+    const long n = call.n, np = call.np;
+    const size_t sq = sizeof(double) * (size_t)np * np, hb = sizeof(double) * (size_t)n * (size_t)n;
+    const bool slot_held = s_slot_valid(slot, ctx->arena_gen, (size_t)((char*)slot_S - (char*)ctx->arena), n, np);
+    slot = SSlot();   // (valid again only when this scan has gone through)
+    helper_rc = EAGLE_OK;
+    if (!call.w_direct && np <= pol.max_np && !pol.no_scache && dev_np != np) {
+        if (d_S) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(d_S); d_S = nullptr; }
+        if (d_scr) { (void)hipFree(d_scr); d_scr = nullptr; }
+        dev_n = dev_np = 0;
+        if (hipMalloc((void**)&d_S, sq) == hipSuccess && hipMalloc((void**)&d_scr, sq) == hipSuccess) dev_np = np;
+        else { if (d_S) (void)hipFree(d_S); d_S = nullptr; (void)hipGetLastError(); }
+    }
+    plan = s_plan(call, pol, SHeld{dev_np, dev_n, h_S ? h_n : 0, slot_held});
+    if (plan.source == S_NONE) return EAGLE_OK;
+    const bool cached = plan.source != S_SLOT_VERIFY && plan.source != S_SLOT_UPLOAD;
+    if (plan.source == S_CACHE_UPLOAD || plan.source == S_SLOT_UPLOAD) {
+        int r = upload_square(ctx, S_host, n, np, cached ? d_S : slot_S);
+        if (r) return r;
+        h_n = 0;
+    }
+    if (cached) { dev_n = n; *Sa = d_S; }
+    if (!plan.refresh_host) return EAGLE_OK;
+    // (20 GB at n = 50,000: only when the host has that to spare four times over -- an overcommitted malloc would succeed and the
+    // copy then meet the OOM killer; without a host copy the small sizes verify on the device and the large ones upload S every call)
+    const long pages = sysconf(_SC_AVPHYS_PAGES), psz = sysconf(_SC_PAGESIZE);
+    if (hb > h_cap && pages > 0 && psz > 0 && (double)hb > 0.25 * (double)pages * (double)psz) return EAGLE_OK;
+    if (hb > h_cap) { free(h_S); h_S = (double*)malloc(hb); h_cap = h_S ? hb : 0; }
+    if (h_S) scache_host_pass(*this, S_host, n, true);   // off the critical path, joined before the call returns
+    return EAGLE_OK;
+}
+// Under the scan: the comparison of the caller's S with the copy the products ran on.  The device form sends the caller's S to the scratch
+// copy on the loader stream.  A copy out of PAGEABLE memory blocks the calling thread until the runtime has staged it (14 ms for 800 MB),
+// and since the int8 W ends with a host read of its statistics nothing was queued behind it any more: the card sat idle for those 14 ms
+// (rocprofv3 timeline of the call, tools/upload_probe.py).  The deferred form is therefore issued from the helper thread while the caller
+// goes on queueing the genotype pass and the vara kernel (S's 800 MB at n = 10,000 then hide under the whole scan, not under W alone).
+int SCache::begin_verify(eagle_ctx* ctx, const double* S_host, long n, long np) {
+    if (plan.verify == SV_NONE) return EAGLE_OK;
+    if (plan.verify == SV_HOST) { scache_host_pass(*this, S_host, n, false); return EAGLE_OK; }
+    if (!h_flag) {
+        const hipError_t e = hipHostMalloc((void**)&h_flag, 64, hipHostMallocDefault);
+        if (e != hipSuccess) { plan.verify = SV_NONE; return eagle_fail_hip(ctx, e, "pinned flag"); }
+    }
+    auto compare = [this, ctx, S_host, n, np]() -> int {
+        int* flag = (int*)((char*)ctx->d_scratch + EAGLE_SCR_SCACHE_FLAG);
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        *h_flag = 0;
+        HIPCHK(ctx, hipMemsetAsync(flag, 0, sizeof(int), ctx->load_stream));
+        const int r = upload_square_on(ctx, S_host, n, np, d_scr, ctx->load_stream);
+        if (r) return r;
+        hipLaunchKernelGGL(k_bits_differ, dim3(1024), dim3(256), 0, ctx->load_stream, (const unsigned long long*)d_scr, (const unsigned long long*)d_S,
+                           np * np, flag);
+        HIPCHK(ctx, hipMemcpyAsync(h_flag, flag, sizeof(int), hipMemcpyDeviceToHost, ctx->load_stream));
+        return EAGLE_OK;
+    };
+    pending = true;
+    if (plan.verify == SV_DEVICE_INLINE) return compare();
+    helper = std::thread([this, compare] { helper_rc = compare(); });
+    return EAGLE_OK;
+}
+// Collects what acquire / begin_verify started (nothing of the caller's S may be in flight past here) and applies the outcome to the cache.
+// rc: the caller's state so far; a failure is returned unchanged.
+int SCache::settle(eagle_ctx* ctx, int rc, SOutcome* out) {
+    *out = S_NOTHING;
+    if (!pending) return rc;
+    const SVerify how = plan.verify;
+    leave();
+    if (helper_rc && !rc) rc = helper_rc;
+    hipError_t e = hipStreamSynchronize(ctx->load_stream);
+    if (e != hipSuccess && !rc) rc = eagle_fail_hip(ctx, e, "verification of the cached S");
+    if (rc || how == SV_NONE) return rc;
+    const SOutcome o = s_outcome(how, how == SV_HOST ? host_differs != 0 : *h_flag != 0);
+    if (o == S_SAME) hits++;
+    else {   // the work so far ran on another S than the caller's
+        if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return eagle_fail_hip(ctx, e, "scan on a stale S");
+        if (o == S_OTHER_ON_DEVICE) std::swap(d_S, d_scr);
+        else dev_n = 0;
+        h_n = 0;
+        misses++;
+    }
+    *out = o;
+    return EAGLE_OK;
+}
+// A scan that went through on S in its arena slot, verified or uploaded by this call: the next scan may find it there.
+void SCache::commit(const eagle_ctx* ctx, const double* slot_S, long n, long np) {
+    if (plan.source != S_SLOT_VERIFY && plan.source != S_SLOT_UPLOAD) return;
+    slot.gen = ctx->arena_gen; slot.off = (size_t)((const char*)slot_S - (const char*)ctx->arena); slot.n = n; slot.np = np;
+}
+// Every way out of a scan: the helper thread is joined, nothing stays pending.
+void SCache::leave() {
+    if (helper.joinable()) helper.join();
+    pending = false;
+    plan.verify = SV_NONE;
+}
+void SCache::forget_host() { free(h_S); h_S = nullptr; h_n = 0; h_cap = 0; }   // (eagle_drop_cache: 8 n^2 bytes of host memory)
+void SCache::release() {   // (eagle_close)
+    leave();
+    forget_host();
+    (void)hipFree(d_S); (void)hipFree(d_scr);   // (null: nothing to free)
+    if (h_flag) (void)hipHostFree(h_flag);
+}
+
 // what scan_range's setup reserves for a resident scan of Lr markers on n individuals (the same terms)
 static size_t scan_arena_bytes(eagle_ctx* ctx, long n, long Lr) {
     const long np = eagle_pad(n), Lp = eagle_pad(Lr > 0 ? Lr : 1);
@@ -1102,10 +1228,13 @@ static int ensure_scan_out(eagle_ctx* ctx, long L_pad) {
 // The scan of the markers [m0, m1) of Mt.ascii on ctx's device: a, vara into ctx->d_a / d_vara (and the host ranges
 // a_out[m0..m1), vara_out[m0..m1)).  k of nd devices; rv / rccl: the meeting point and the communicators of a multi-device call
 // (NULL for one device).  Every device passes the same rendezvous in the same order, failed or not.
-static int scan_range(eagle_ctx* ctx, const char* f_name_ascii, long L, long n, long m0, long m1, const std::vector<long>& sel,
-                      const double* inv_MMt_sqrt, const double* dim_reduced_vara, const double* a, double max_memory_in_Gbytes, int quiet,
-                      double* a_out, double* vara_out, int k, int nd, Rendezvous* rv, RcclState* rccl, bool w_direct = false, bool s_trusted = false) {
-    // s_trusted: the device copy of S was uploaded from this very caller matrix a moment ago (the re-run after a deferred
+// This is ONE attempt (scan_range, below, makes at most two).  pol: the switches of the cached S as read for this call; *redo: S_NOTHING,
+// or how the verification settled at the END of the scan found another S than the one it ran on.
+static int scan_once(eagle_ctx* ctx, const char* f_name_ascii, long L, long n, long m0, long m1, const std::vector<long>& sel,
+                     const double* inv_MMt_sqrt, const double* dim_reduced_vara, const double* a, double max_memory_in_Gbytes, int quiet,
+                     double* a_out, double* vara_out, int k, int nd, Rendezvous* rv, RcclState* rccl, bool w_direct, bool s_trusted,
+                     const SPolicy& pol, SOutcome* redo) {
+    // s_trusted: the device copy of S was uploaded from this very caller matrix a moment ago (the second attempt after a deferred
     // verification found another S): no verification this time
     // w_direct (eagle_scan_with_W): inv_MMt_sqrt is not S but W itself, `a` is v = S a_hat; dim_reduced_vara is unused
     const long Lr = m1 - m0;
@@ -1145,9 +1274,6 @@ static int scan_range(eagle_ctx* ctx, const char* f_name_ascii, long L, long n, 
     // certified against ONE lower bound of the maximum over every block of every device, so that the candidates, and with them every
     // returned bit, are those of the one-block scan of the whole file (the per-marker bounds of all blocks stay: 8 bytes per marker).
     const bool bounds_flow = use_i8 && (streamed || rv);
-    // one resident block on one device: the caller's S is compared with a HOST copy of the cached one (memcmp on the cores that idle while
-    // the card works) -- measured: the 800 MB upload + device comparison under the vara kernel cost the call 3.4 ms of 141.5 at the headline size
-    const bool host_verify = !rv && !getenv("EAGLE_HIP_NO_HOST_SVERIFY");   // (a streamed file too: the comparison runs beside the loaders)
     long over_tight_all = 0;   // markers of the whole scan over the tight threshold (CERT_TIGHT_MAX)
     const long Lc = streamed ? stream_chunk_rows(np, Lp) : Lp;  // marker rows per pass
     DevBuf dsel;
@@ -1155,18 +1281,8 @@ static int scan_range(eagle_ctx* ctx, const char* f_name_ascii, long L, long n, 
     const size_t certb = use_i8 ? (size_t)eagle_scan_certify_workspace_bytes(np) : 0;
     const double t0 = now_s();
     double *Sa = nullptr, *Va = nullptr, *tmp = nullptr, *Wu = nullptr, *ah = nullptr, *v = nullptr;
-    bool s_from_cache = false;  // the product runs on the device copy of the last call's S; the caller's S is verified under it
-    bool s_check_pending = false;  // ... and the outcome of that verification has not been collected yet
-    struct Helper {   // the thread that issues a deferred verification (joined on every way out)
-        std::thread t;
-        int rc = EAGLE_OK;
-        void start(const std::function<int()>& f) { t = std::thread([this, f] { rc = f(); }); }
-        int join() { if (t.joinable()) t.join(); return rc; }
-        ~Helper() { if (t.joinable()) t.join(); }
-    } s_verify;
-    int host_flag_store = 0;
-    int* const host_flag = &host_flag_store;   // outcome of a HOST-side verification (1: the caller's S differs from the cached one)
-    int s_check_kind = 0;   // what s_check_pending waits for: 1 = the device comparison, 2 = the host comparison, 3 = only the refresh of the host copy
+    SCache& sc = ctx->scache;   // the S of the last call, kept for this one
+    struct Left { SCache& c; ~Left() { c.leave(); } } left{sc};   // (its helper thread is joined on every way out)
     void *ws = nullptr, *cert = nullptr;
     long* cert_totals = (long*)((char*)ctx->d_scratch + EAGLE_SCR_CERT_TOTALS);  // {re-evaluated, flagged, fell back, over the tight threshold}, summed over marker blocks
     ChunkRing ring;
@@ -1174,39 +1290,12 @@ static int scan_range(eagle_ctx* ctx, const char* f_name_ascii, long L, long n, 
     int8_t* cs[2] = {nullptr, nullptr};
     int32_t* l1s[2] = {nullptr, nullptr};
     PhaseEvents ph;
-    bool s_in_arena = false;   // n_pad > 16,384: the arena slot still holds the last scan's S (see eagle_ctx.h)
-    // the device copy is (about to be) this caller's S: its host copy is made off the critical path, joined before the call returns
-    auto refresh_host_copy = [&]() {
-        const size_t bytes = sizeof(double) * (size_t)n * (size_t)n;
-        // (20 GB at n = 50,000: only when the host has that to spare four times over -- an overcommitted malloc would succeed and the
-        // copy then meet the OOM killer; without a host copy the small sizes verify on the device and the large ones upload S every call)
-        const long pages = sysconf(_SC_AVPHYS_PAGES), psz = sysconf(_SC_PAGESIZE);
-        if (bytes > ctx->h_Scache_cap && pages > 0 && psz > 0 && (double)bytes > 0.25 * (double)pages * (double)psz) return;
-        if (bytes > ctx->h_Scache_cap) {
-            free(ctx->h_Scache);
-            ctx->h_Scache = (double*)malloc(bytes);
-            ctx->h_Scache_cap = ctx->h_Scache ? bytes : 0;
-        }
-        if (!ctx->h_Scache) return;
-        s_check_pending = true;   // (nothing to check: only the join)
-        s_check_kind = 3;
-        s_verify.start([ctx, inv_MMt_sqrt, n, bytes]() -> int {
-            parallel_for((long)bytes, std::max(1, std::min(host_threads(), 16)), [&](long a, long b, int) {
-                memcpy((char*)ctx->h_Scache + a, (const char*)inv_MMt_sqrt + a, (size_t)(b - a));
-            });
-            ctx->h_Scache_n = n;
-            return EAGLE_OK;
-        });
-    };
     auto setup = [&]() -> int {
-        const void* kept = (ctx->arena_S_ptr && ctx->arena_S_base == ctx->arena && ctx->arena_S_n == n && ctx->arena_S_np == np) ? ctx->arena_S_ptr : nullptr;
-        ctx->arena_S_ptr = nullptr;   // (valid again only when this scan has gone through)
         int r = arena_reserve(ctx, 4 * arena_round(sq) + 2 * arena_round(sizeof(double) * np) + arena_round(wsb) + arena_round(certb) +
                                        (streamed ? (use_i8 ? 4 : 2) * arena_round((size_t)Lc * np) + 2 * arena_round((size_t)Lc) +
                                                        2 * arena_round(2 * sizeof(int32_t) * (size_t)Lc) : 0));
         if (r) return r;
         Sa = arena_take<double>(ctx, sq);
-        s_in_arena = kept && kept == (const void*)Sa && ctx->arena_S_base == ctx->arena;
         Va = arena_take<double>(ctx, sq);
         tmp = arena_take<double>(ctx, sq);
         Wu = arena_take<double>(ctx, sq);
@@ -1229,45 +1318,14 @@ static int scan_range(eagle_ctx* ctx, const char* f_name_ascii, long L, long n, 
             if ((r = upload_square(ctx, inv_MMt_sqrt, n, np, Wu))) return r;
             if ((r = upload_vec(ctx, a, n, np, v))) return r;
         } else {
-            // S = inv_MMt_sqrt is MMt^-1/2, the same matrix in every call of an AM() run, but R builds it anew each time (no pointer
-            // identity, and hashing 800 MB costs what copying them costs): the copy of the last call stays on the device, this call
-            // computes on it at once, and the caller's matrix is uploaded on the loader stream and compared bit for bit while the
-            // n^3 products run; a difference starts the products over (below).  V changes with every call; it arrives in row
-            // blocks on the loader stream UNDER the first product, which works on the rows that have landed (below) -- unless the
-            // rows of W are shared between devices (share_w: the row-block product there needs all of V at once).
+            // V changes with every call; it arrives in row blocks on the loader stream UNDER the first product, which works on the rows
+            // that have landed (below) -- unless the rows of W are shared between devices (share_w: the row-block product there needs all
+            // of V at once).
             if (share_w && (r = upload_square_staged(ctx, dim_reduced_vara, n, np, Va, ctx->stream))) return r;
             if ((r = upload_vec(ctx, a, n, np, ah))) return r;
-            // (EAGLE_HIP_SCACHE_MAX_NP: tests force the large-n form -- S kept in its arena slot, host comparison -- at small sizes)
-            const long scache_max_np = getenv("EAGLE_HIP_SCACHE_MAX_NP") ? atol(getenv("EAGLE_HIP_SCACHE_MAX_NP")) : 16384;
-            const bool cacheable = np <= scache_max_np && !getenv("EAGLE_HIP_NO_SCACHE");   // (round 4: also when W's rows are shared)
-            if (cacheable && ctx->scache_np != np) {
-                if (ctx->d_Scache) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(ctx->d_Scache); ctx->d_Scache = nullptr; }
-                if (ctx->d_Sscr) { (void)hipFree(ctx->d_Sscr); ctx->d_Sscr = nullptr; }
-                ctx->scache_n = ctx->scache_np = 0;
-                if (hipMalloc((void**)&ctx->d_Scache, sq) == hipSuccess && hipMalloc((void**)&ctx->d_Sscr, sq) == hipSuccess) ctx->scache_np = np;
-                else { if (ctx->d_Scache) (void)hipFree(ctx->d_Scache); ctx->d_Scache = nullptr; (void)hipGetLastError(); }
-            }
-            if (cacheable && ctx->scache_np == np) {
-                // (EAGLE_HIP_EXPERIMENT_TRUST_S: measurement only -- what the verification traffic costs the kernels it runs under; never set it
-                // for real work: a changed S would go unnoticed)
-                const bool trust = s_trusted || (ctx->scache_n == n && getenv("EAGLE_HIP_EXPERIMENT_TRUST_S"));
-                s_from_cache = ctx->scache_n == n && !trust;
-                if (!s_from_cache && !trust) {
-                    if ((r = upload_square(ctx, inv_MMt_sqrt, n, np, ctx->d_Scache))) return r;
-                    ctx->h_Scache_n = 0;
-                }
-                if (!s_from_cache && host_verify && ctx->h_Scache_n != n) refresh_host_copy();
-                ctx->scache_n = n;
-                Sa = ctx->d_Scache;
-            } else if (!getenv("EAGLE_HIP_NO_SCACHE") && s_in_arena && host_verify && !s_trusted && ctx->h_Scache && ctx->h_Scache_n == n) {
-                // n_pad > 16,384: S is where the last scan left it; the host comparison decides at the end of the call
-                s_from_cache = true;
-            } else {
-                if ((r = upload_square(ctx, inv_MMt_sqrt, n, np, Sa))) return r;
-                ctx->h_Scache_n = 0;
-                if (host_verify && !getenv("EAGLE_HIP_NO_SCACHE")) refresh_host_copy();
-            }
         }
+        // the S to compute on: the cached copy when there is one (the caller's matrix is verified under the products, below), else uploaded
+        if ((r = sc.acquire(ctx, SCall{w_direct, s_trusted, n, np, rv != nullptr, streamed, bounds_flow}, pol, inv_MMt_sqrt, Sa, &Sa))) return r;
         // streamed: every block is worked as a full chunk of Lc rows (one workspace layout for all of them; the rows beyond a short
         // last block are zero and land in the slack behind the shard's results)
         if ((r = ensure_scan_out(ctx, streamed ? (Lr + Lc - 1) / Lc * Lc : Lp))) return r;
@@ -1362,66 +1420,17 @@ static int scan_range(eagle_ctx* ctx, const char* f_name_ascii, long L, long n, 
             }
         }
     }
-    if (!rc && s_from_cache) {
-        // under the scan: the caller's S to the scratch copy (loader stream), compared with the cached one.  One resident block
-        // on one device: nothing below needs the host before the results go back, so the answer is collected only then (S's 800 MB
-        // at n = 10,000 then hide under the whole scan, not under W alone); otherwise (marker blocks, several devices: the host is
-        // in the loop anyway) right here.
-        // Round 4: a copy out of PAGEABLE memory blocks the calling thread until the runtime has staged it (14 ms for 800 MB), and since
-        // the int8 W ends with a host read of its statistics nothing was queued behind it any more: the card sat idle for those 14 ms
-        // (rocprofv3 timeline of the call, tools/upload_probe.py).  The deferred verification is therefore issued from a helper thread
-        // while this one goes on queueing the genotype pass and the vara kernel.
-        int* flag = (int*)((char*)ctx->d_scratch + EAGLE_SCR_SCACHE_FLAG);
-        if (!ctx->h_flag && (e = hipHostMalloc((void**)&ctx->h_flag, 64, hipHostMallocDefault)) != hipSuccess) rc = eagle_fail_hip(ctx, e, "pinned flag");
-        auto verify = [ctx, flag, inv_MMt_sqrt, n, np]() -> int {
-            hipError_t ev = hipSetDevice(ctx->device);
-            if (ev != hipSuccess) return eagle_fail_hip(ctx, ev, "hipSetDevice");
-            *ctx->h_flag = 0;
-            ev = hipMemsetAsync(flag, 0, sizeof(int), ctx->load_stream);
-            if (ev != hipSuccess) return eagle_fail_hip(ctx, ev, "verification of the cached S");
-            int r = upload_square_on(ctx, inv_MMt_sqrt, n, np, ctx->d_Sscr, ctx->load_stream);
-            if (r) return r;
-            hipLaunchKernelGGL(k_bits_differ, dim3(1024), dim3(256), 0, ctx->load_stream, (const unsigned long long*)ctx->d_Sscr,
-                               (const unsigned long long*)ctx->d_Scache, np * np, flag);
-            ev = hipMemcpyAsync(ctx->h_flag, flag, sizeof(int), hipMemcpyDeviceToHost, ctx->load_stream);
-            if (ev != hipSuccess) return eagle_fail_hip(ctx, ev, "verification of the cached S");
-            return EAGLE_OK;
-        };
-        if (!rc) {
-            s_check_pending = true;
-            if (host_verify && ctx->h_Scache && ctx->h_Scache_n == n) {
-                s_check_kind = 2;
-                *host_flag = 0;
-                s_verify.start([ctx, inv_MMt_sqrt, n, host_flag]() -> int {
-                    const size_t bytes = sizeof(double) * (size_t)n * (size_t)n;
-                    std::atomic<int> differs{0};
-                    parallel_for((long)bytes, std::max(1, std::min(host_threads(), 16)), [&](long a, long b, int) {
-                        if (memcmp((const char*)ctx->h_Scache + a, (const char*)inv_MMt_sqrt + a, (size_t)(b - a)) != 0) differs.store(1);
-                    });
-                    *host_flag = differs.load();
-                    return EAGLE_OK;
-                });
-            } else {
-                s_check_kind = 1;
-                if (streamed || bounds_flow || rv) rc = verify();
-                else s_verify.start(verify);
-            }
-        }
+    if (!rc && sc.plan.verify != SV_NONE) {
+        rc = sc.begin_verify(ctx, inv_MMt_sqrt, n, np);
         // (rv: a device of a multi-device call must not defer -- a peer that streams or holds no cached S settles a changed S inline,
-        // and a deferred restart of this one would pass every rendezvous of the call a second time)
-        if (s_check_pending && ((s_check_kind == 1 && (streamed || bounds_flow || rv)) || rc)) {
-            s_check_pending = false;
-            (void)s_verify.join();
-            e = hipStreamSynchronize(ctx->load_stream);
-            if (e != hipSuccess && !rc) rc = eagle_fail_hip(ctx, e, "verification of the cached S");
-            if (!rc && s_check_kind == 1 && *ctx->h_flag) {  // another S: it is already on the device -- start the product over with it
-                if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) rc = eagle_fail_hip(ctx, e, "scan operands");
-                std::swap(ctx->d_Scache, ctx->d_Sscr);
-                Sa = ctx->d_Scache;
-                ctx->h_Scache_n = 0;
-                if (!rc) rc = eagle_dev_scan_operands(ctx, Sa, Va, ah, n, np, v, Wu, tmp, ctx->stream);
-                ctx->scache_misses++;
-            } else if (!rc) ctx->scache_hits++;
+        // and a second attempt of this one would pass every rendezvous of the call a second time)
+        if (sc.plan.verify == SV_DEVICE_INLINE) {
+            SOutcome o;
+            rc = sc.settle(ctx, rc, &o);
+            if (!rc && o == S_OTHER_ON_DEVICE) {   // another S, on the device already: the products start over with it
+                Sa = sc.d_S;
+                rc = eagle_dev_scan_operands(ctx, Sa, Va, ah, n, np, v, Wu, tmp, ctx->stream);
+            }
         }
     }
     if (!rc) ph.mark(ctx->stream, PH_W);
@@ -1569,30 +1578,9 @@ static int scan_range(eagle_ctx* ctx, const char* f_name_ascii, long L, long n, 
     }
 #undef EAGLE_ARRIVE
 #undef EAGLE_ARRIVE2
-    if (s_check_pending) {   // the deferred outcome of the verification of the cached S (nothing of the caller's S may be in flight past here)
-        const int rs = s_verify.join();
-        if (rs && !rc) rc = rs;
-        e = hipStreamSynchronize(ctx->load_stream);
-        if (e != hipSuccess && !rc) rc = eagle_fail_hip(ctx, e, "verification of the cached S");
-        if (!rc && s_check_kind == 1 && *ctx->h_flag) {
-            // another S than the cached one: this scan ran on the wrong operand.  The caller's S is on the device already (the scratch
-            // copy): it becomes the cached one and the scan starts over, once, without another verification.
-            if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return eagle_fail_hip(ctx, e, "scan on a stale S");
-            std::swap(ctx->d_Scache, ctx->d_Sscr);
-            ctx->h_Scache_n = 0;
-            ctx->scache_misses++;
-            return scan_range(ctx, f_name_ascii, L, n, m0, m1, sel, inv_MMt_sqrt, dim_reduced_vara, a, max_memory_in_Gbytes, quiet, a_out, vara_out, k, nd,
-                              rv, rccl, w_direct, true);
-        } else if (!rc && s_check_kind == 2 && *host_flag) {
-            // (host comparison) the caller's S is not on the device: the cache is dropped and the scan starts over with an upload
-            if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return eagle_fail_hip(ctx, e, "scan on a stale S");
-            ctx->scache_n = 0;
-            ctx->h_Scache_n = 0;
-            ctx->scache_misses++;
-            return scan_range(ctx, f_name_ascii, L, n, m0, m1, sel, inv_MMt_sqrt, dim_reduced_vara, a, max_memory_in_Gbytes, quiet, a_out, vara_out, k, nd,
-                              rv, rccl, w_direct, false);
-        } else if (!rc && s_check_kind != 3) ctx->scache_hits++;
-    }
+    SOutcome settled;
+    rc = sc.settle(ctx, rc, &settled);   // the deferred outcome of the verification of the cached S
+    if (!rc && (settled == S_OTHER_ON_DEVICE || settled == S_OTHER_FORGOTTEN)) { *redo = settled; return EAGLE_OK; }   // ran on the wrong operand: once more (scan_range)
     if (timing_on() && !rc) {
         (void)hipStreamSynchronize(ctx->stream);
         fprintf(stderr, "[eaglehip] scan n=%ld markers [%ld, %ld) of %ld on device %d%s: alloc+upload %.1f ms, device compute %.1f ms\n", n, m0, m1, L,
@@ -1615,8 +1603,7 @@ static int scan_range(eagle_ctx* ctx, const char* f_name_ascii, long L, long n, 
         HIPCHK(ctx, hipMemcpyAsync(vara_out + m0, ctx->d_vara, sizeof(double) * (size_t)Lr, hipMemcpyDeviceToHost, ctx->stream));
     }
     HIPCHK(ctx, hipMemcpyAsync(totals, cert_totals, sizeof totals, hipMemcpyDeviceToHost, ctx->stream));
-    struct { double maxabs_off; int S, pad; double bound, sumdiag, R, specH; int S_sliced, pad2; double budget; int e, pad3; unsigned long long lo_sumsq;
-             int maxdiag, hi_overflow, spec_try2, level; double wErr, specH1, budget_loose; } vh = {};   // head of the digit workspace (VaraHdr)
+    VaraHdr vh = {};   // head of the digit workspace
     if (use_i8 && Lr > 0) HIPCHK(ctx, hipMemcpyAsync(&vh, ws, sizeof vh, hipMemcpyDeviceToHost, ctx->stream));
     ph.mark(ctx->stream, PH_D2H);
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -1633,10 +1620,33 @@ static int scan_range(eagle_ctx* ctx, const char* f_name_ascii, long L, long n, 
     ctx->scan_blocks = streamed ? ring.k : 1;
     ctx->scan_host_setup_s = t_setup - t0;
     ctx->scan_range_wall_s = now_s() - t0;
-    if (!w_direct && Lr > 0 && Sa && Sa != ctx->d_Scache) {   // S sits in its arena slot, verified or uploaded by this call: the next scan may find it there
-        ctx->arena_S_ptr = Sa; ctx->arena_S_base = ctx->arena; ctx->arena_S_n = n; ctx->arena_S_np = np;
-    }
+    if (Lr > 0) sc.commit(ctx, Sa, n, np);
     return EAGLE_OK;
+}
+// The scan, and when its deferred verification finds that the cached S it ran on was not the caller's, a second time on the caller's:
+// s_trusted when that S is on the device already (the scratch copy has become the cached one), else with an upload.  The second attempt
+// verifies nothing (s_plan), so there is no third.
+static int scan_range(eagle_ctx* ctx, const char* f_name_ascii, long L, long n, long m0, long m1, const std::vector<long>& sel,
+                      const double* inv_MMt_sqrt, const double* dim_reduced_vara, const double* a, double max_memory_in_Gbytes, int quiet,
+                      double* a_out, double* vara_out, int k, int nd, Rendezvous* rv, RcclState* rccl, bool w_direct = false, bool s_trusted = false) {
+    const SPolicy pol = scache_policy();
+    SOutcome redo = S_NOTHING;
+    auto attempt = [&](bool trusted) {
+        return scan_once(ctx, f_name_ascii, L, n, m0, m1, sel, inv_MMt_sqrt, dim_reduced_vara, a, max_memory_in_Gbytes, quiet, a_out, vara_out, k, nd, rv,
+                         rccl, w_direct, trusted, pol, &redo);
+    };
+    const int rc = attempt(s_trusted);
+    return !rc && redo != S_NOTHING ? attempt(redo == S_OTHER_ON_DEVICE) : rc;
+}
+
+// After a scan on several devices: the lead reports the certificate counters of all of them, and the spectral_off latch of any is everybody's.
+static void merge_peer_scans(eagle_ctx* ctx) {
+    for (eagle_ctx* p : ctx->peers) {
+        ctx->cert_reevaluated += p->cert_reevaluated; ctx->cert_flagged += p->cert_flagged; ctx->cert_fell_back |= p->cert_fell_back;
+        ctx->spectral_off |= p->spectral_off;
+        if (!ctx->scan_digits_cut) { ctx->scan_digits_used = p->scan_digits_used; ctx->scan_digits_cut = p->scan_digits_cut; ctx->scan_specH = p->scan_specH; }
+    }
+    for (eagle_ctx* p : ctx->peers) p->spectral_off = ctx->spectral_off;   // every device of the next scan decides alike
 }
 
 extern "C" int eagle_calculate_a_and_vara(eagle_ctx* ctx, const char* f_name_ascii, const double* selected_loci,
@@ -1684,12 +1694,7 @@ extern "C" int eagle_calculate_a_and_vara(eagle_ctx* ctx, const char* f_name_asc
     });
     ctx->scan_call_wall_s = now_s() - t_call;
     if (rc) return rc;
-    for (eagle_ctx* p : ctx->peers) {
-        ctx->cert_reevaluated += p->cert_reevaluated; ctx->cert_flagged += p->cert_flagged; ctx->cert_fell_back |= p->cert_fell_back;
-        ctx->spectral_off |= p->spectral_off;
-        if (!ctx->scan_digits_cut) { ctx->scan_digits_used = p->scan_digits_used; ctx->scan_digits_cut = p->scan_digits_cut; ctx->scan_specH = p->scan_specH; }
-    }
-    for (eagle_ctx* p : ctx->peers) p->spectral_off = ctx->spectral_off;   // every device of the next scan decides alike
+    merge_peer_scans(ctx);
     return EAGLE_OK;
 }
 
@@ -1717,19 +1722,14 @@ extern "C" int eagle_scan_with_W(eagle_ctx* ctx, const char* f_name_ascii, const
                           nd > 1 ? &rv : nullptr, nullptr, true);
     });
     if (rc) return rc;
-    for (eagle_ctx* p : ctx->peers) {
-        ctx->cert_reevaluated += p->cert_reevaluated; ctx->cert_flagged += p->cert_flagged; ctx->cert_fell_back |= p->cert_fell_back;
-        ctx->spectral_off |= p->spectral_off;
-        if (!ctx->scan_digits_cut) { ctx->scan_digits_used = p->scan_digits_used; ctx->scan_digits_cut = p->scan_digits_cut; ctx->scan_specH = p->scan_specH; }
-    }
-    for (eagle_ctx* p : ctx->peers) p->spectral_off = ctx->spectral_off;   // every device of the next scan decides alike
+    merge_peer_scans(ctx);
     return EAGLE_OK;
 }
 
 extern "C" int eagle_scan_operand_cache_stats(eagle_ctx* ctx, long* hits, long* misses) {
     if (!ctx) return EAGLE_ERR_ARG;
-    long h = ctx->scache_hits, m = ctx->scache_misses;
-    for (eagle_ctx* p : ctx->peers) { h += p->scache_hits; m += p->scache_misses; }
+    long h = ctx->scache.hits, m = ctx->scache.misses;
+    for (eagle_ctx* p : ctx->peers) { h += p->scache.hits; m += p->scache.misses; }
     if (hits) *hits = h;
     if (misses) *misses = m;
     return EAGLE_OK;

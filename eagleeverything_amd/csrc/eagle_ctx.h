@@ -47,6 +47,29 @@ struct ViewAlias {
     mutable int32_t* d_keep = nullptr;   // the keep-map in HBM (axis 1; made on first use)
 };
 
+// The one owner of the cached S (the rule: s_plan in eagle_host.h; the methods: eagle_api.cpp, "The cached S").  A scan calls acquire, then
+// begin_verify behind W, settle where the plan says, commit when it has gone through; leave() on every way out.
+struct SCache {
+    double* d_S = nullptr; double* d_scr = nullptr;   // device copy of the last call's S and the scratch the caller's is compared in (np x np each)
+    long dev_n = 0, dev_np = 0;                       // ... holding an n-individual S (0: none) / allocated for np (0: not)
+    double* h_S = nullptr; long h_n = 0; size_t h_cap = 0;   // host copy (n x n as the caller passed it) for the memcmp; h_n = 0: none
+    SSlot slot;                                       // above max_np: where the last scan left S in the arena
+    int* h_flag = nullptr;                            // 64 pinned bytes: where the device comparison's flag lands
+    long hits = 0, misses = 0;                        // (eagle_scan_operand_cache_stats)
+    // this call
+    SPlan plan;
+    std::thread helper; int helper_rc = 0;            // issues a deferred device comparison, or runs the host comparison / the refresh of the host copy
+    bool pending = false;                             // something was started that settle() has to collect
+    int host_differs = 0;
+    int acquire(eagle_ctx* ctx, const SCall& call, const SPolicy& pol, const double* S_host, double* slot_S, double** Sa);
+    int begin_verify(eagle_ctx* ctx, const double* S_host, long n, long np);
+    int settle(eagle_ctx* ctx, int rc, SOutcome* out);
+    void commit(const eagle_ctx* ctx, const double* slot_S, long n, long np);
+    void leave();
+    void forget_host();
+    void release();
+};
+
 struct eagle_ctx {
     int device = -1;
     // multi-device: the ctx eagle_open_devices returns is the LEAD (first device); it owns one sub-context per further device.
@@ -83,26 +106,18 @@ struct eagle_ctx {
     int scan_digits_used = 0, scan_digits_cut = 0; double scan_specH = 0.0;  // digit slices of the last digit-slice scan (eagle_last_scan_digits)
     double scan_phase_ms[8] = {0}; long scan_blocks = 0;                  // phase clock of the last scan on this device (eagle_last_scan_timing)
     double scan_host_setup_s = 0, scan_range_wall_s = 0, scan_call_wall_s = 0;
-    // S = inv_MMt_sqrt of the last scan, kept on the device: MMt^-1/2 is the same matrix in every find_qtl call of an AM() run
-    // (scan_range: the next call computes on this copy while the caller's matrix is uploaded and compared under the product)
-    double* d_Scache = nullptr; double* d_Sscr = nullptr; long scache_n = 0, scache_np = 0; long scache_hits = 0, scache_misses = 0;
-    // host copy of the cached S (n x n as the caller passed it): one resident block on one device verifies the caller's S against it with the
-    // host's idle cores (memcmp) instead of sending 8 n^2 bytes over PCIe and through HBM under the vara kernel; h_Scache_n = 0: none
-    double* h_Scache = nullptr; long h_Scache_n = 0; size_t h_Scache_cap = 0;
-    // above 16,384 padded individuals no second device copy of S is kept (20 GB at n = 50,000): the last scan's S is still in its ARENA slot
-    // when nothing has re-laid the arena since, and the next scan computes on it if the host comparison agrees (arena_S_ptr: that slot, else null)
-    const void* arena_S_ptr = nullptr; const void* arena_S_base = nullptr; long arena_S_n = 0, arena_S_np = 0;
+    SCache scache;   // S = inv_MMt_sqrt of the last scan, kept for the next one (below)
     // out-of-core bookkeeping of the last streamed call on this device (eagle_last_stream_stats)
     long st_chunks = 0, st_file_bytes = 0;
     double st_pread_s = 0, st_load_wall_s = 0, st_wait_s = 0, st_compute_s = 0, st_total_s = 0, st_starved_s = 0, st_load_first_s = 0;
     void* d_scratch = nullptr;
     void* argmax_ws = nullptr;   // block partials + result of eagle_last_scan_argmax (ctx-owned: no allocation per call)
     void* arena = nullptr; size_t arena_cap = 0, arena_off = 0;  // grow-only device workspace reused across calls
+    unsigned long arena_gen = 1;      // counts every allocation, release or replacement of the arena (what SCache's slot is valid by)
     void* arena_prefetch = nullptr;   // ArenaPrefetch* (eagle_api.cpp): a background hipMalloc of the arena in flight
     void* f4_buf = nullptr; size_t f4_cap = 0;  // fp4 image of the tile eagle_dev_mmt_accumulate is working on
     void* gemm_scratch = nullptr; size_t gemm_scratch_cap = 0;  // split-K partial tiles of the fp64 GEMM's last wave
     void* gemv_ws = nullptr;  // 16 digit-slice rows of the GEMV vectors + their exponents (k_gemv_mfma)
-    int* h_flag = nullptr;   // 64 pinned bytes: where an asynchronous device-to-host copy of a flag lands (the deferred verification of the cached S)
     void* stage_pin[2] = {nullptr, nullptr}; void* stage_raw[2] = {nullptr, nullptr}; size_t stage_cap = 0;  // tile streamer
     // per-device launch state (a process may hold one ctx per GPU): dynamic-LDS attributes set on this device, schedule
     // experiment switch of tools/bench_i8_engine.py (0 = shipped)

@@ -148,6 +148,62 @@ EAGLE_HD static inline int vara_tail_pieces(int tail, int npair) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// The cached S of the scan (SCache, eagle_api.cpp): S = inv_MMt_sqrt is the same matrix in every find_qtl call of an AM() run, so the
+// last call's copy stays on the device -- in a buffer of its own up to max_np padded individuals, else where the scan left it in the
+// arena -- and the next call computes on it while the caller's matrix is compared with it.  s_plan decides from plain values where a
+// call's S comes from, how the caller's matrix is verified and when that is settled; s_outcome what settling means; s_slot_valid
+// whether the arena still holds the slot.  No pointer, no device: tests/host/test_host.cpp enumerates all of it.
+// ------------------------------------------------------------------------------------------------
+struct SPolicy {               // the environment switches, read once per call (tests toggle them between calls of one process)
+    bool no_scache = false;    // EAGLE_HIP_NO_SCACHE: every call uploads S
+    long max_np = 16384;       // EAGLE_HIP_SCACHE_MAX_NP: above it no second device copy (20 GB at n = 50,000): the arena slot
+    bool no_host_verify = false;  // EAGLE_HIP_NO_HOST_SVERIFY: always the device comparison
+    bool trust_s = false;      // EAGLE_HIP_EXPERIMENT_TRUST_S: measurement only -- a changed S would go unnoticed
+};
+struct SCall { bool w_direct, s_trusted; long n, np; bool rv, streamed, bounds_flow; };
+struct SHeld {      // what the cache holds
+    long dev_np;    // the two device buffers are np x np (0: none -- an allocation failure falls through to the arena slot)
+    long dev_n;     // ... and the first holds the S of a call with that many individuals (0: none)
+    long host_n;    // the host copy holds one (0: none)
+    bool slot;      // the arena slot holds this call's (n, np) (s_slot_valid)
+};
+enum SSource { S_NONE, S_CACHE_TRUSTED, S_CACHE_VERIFY, S_CACHE_UPLOAD, S_SLOT_VERIFY, S_SLOT_UPLOAD };
+// host memcmp on the cores that idle while the card works, settled at the end of the call; else the device comparison under the scan,
+// settled right behind W when the host is in the loop anyway (marker blocks, several devices), else at the end from a helper thread
+enum SVerify { SV_NONE, SV_HOST, SV_DEVICE_INLINE, SV_DEVICE_DEFERRED };
+struct SPlan { SSource source = S_NONE; SVerify verify = SV_NONE; bool refresh_host = false; };
+static inline SPlan s_plan(const SCall& c, const SPolicy& p, const SHeld& h) {
+    SPlan r;
+    if (c.w_direct) return r;   // W arrives ready: no S at all
+    const bool host_verify = !c.rv && !p.no_host_verify;
+    const bool buffers = h.dev_np == c.np, on_device = buffers && h.dev_n == c.n, on_host = h.host_n == c.n;
+    const SVerify device = (c.streamed || c.bounds_flow || c.rv) ? SV_DEVICE_INLINE : SV_DEVICE_DEFERRED;   // (a device of a multi-device call never defers)
+    if (c.np <= p.max_np && !p.no_scache && buffers) {
+        if (c.s_trusted || (p.trust_s && on_device)) { r.source = S_CACHE_TRUSTED; r.refresh_host = host_verify && !on_host; }
+        else if (on_device) { r.source = S_CACHE_VERIFY; r.verify = (host_verify && on_host) ? SV_HOST : device; }
+        else { r.source = S_CACHE_UPLOAD; r.refresh_host = host_verify; }   // (the upload has invalidated the host copy)
+    } else if (!p.no_scache && h.slot && host_verify && !c.s_trusted && on_host) {
+        r.source = S_SLOT_VERIFY; r.verify = SV_HOST;
+    } else {
+        r.source = S_SLOT_UPLOAD; r.refresh_host = host_verify && !p.no_scache;
+    }
+    return r;
+}
+// S_SAME: a hit.  S_OTHER_ON_DEVICE: the device comparison has left the caller's S in the scratch buffer -- the two buffers are swapped and
+// the work is redone on it (settled inline: only the operands; at the end: the whole scan a second time, s_trusted).  S_OTHER_FORGOTTEN:
+// the host comparison: the caller's S is not on the device -- the cache forgets what it holds, the scan runs a second time and uploads.
+enum SOutcome { S_NOTHING, S_SAME, S_OTHER_ON_DEVICE, S_OTHER_FORGOTTEN };
+static inline SOutcome s_outcome(SVerify how, bool differs) {
+    return how == SV_NONE ? S_NOTHING : !differs ? S_SAME : how == SV_HOST ? S_OTHER_FORGOTTEN : S_OTHER_ON_DEVICE;
+}
+// The arena slot of S, valid by GENERATION and not by address: eagle_ctx::arena_gen counts every allocation, release or replacement of
+// the arena (a freed block's address may come back), and the record holds only at the generation and offset it was made at.
+struct SSlot { unsigned long gen = 0; size_t off = 0; long n = 0, np = 0; };   // n = 0: none
+static inline bool s_slot_valid(const SSlot& s, unsigned long gen, size_t off, long n, long np) {
+    return s.n > 0 && s.gen == gen && s.off == off && s.n == n && s.np == np;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Text side of the ingestion (eagle_ingest.cpp): line index of a memory-mapped file and the whitespace tokeniser.
 // ------------------------------------------------------------------------------------------------
 static inline void parallel_for(long n, int threads, const std::function<void(long, long, int)>& fn) {

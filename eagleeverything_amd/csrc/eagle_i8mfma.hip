@@ -127,35 +127,7 @@ extern "C" int eagle_dev_mmt_accumulate_i8(eagle_ctx* ctx, const int8_t* M8, lon
 // tiles in lock-step.  This placement is a guess that only affects speed.  The integer partial row-dots of the
 // workers meet in q[s][i] by int64 atomics (one flush per worker).
 // ================================================================================================
-
-struct VaraHdr {        // head of the workspace, written on the device, never read by the host
-    double maxabs_off;  // max |Wu[j][k]|, j != k
-    int S;              // digit slices in use
-    int pad;
-    double bound;       // n_pad^2 * 2^(e+1-8S): absolute error bound of every vara_i
-    double sumdiag;     // sum_k |Wu[k][k]|
-    double R;           // sum_{j<k} Wu[j][k] (the off-diagonal quadratic form of the all-ones vector)
-    double specH;       // > 0: the scan runs on S = S_sliced - 1 digits and |digit error of marker i| <= specH * sum_j m'_ij^2 (k_spectral_decide)
-    int S_sliced;       // digits k_slice_w cut (the scale of the integers Q); S_sliced - S is 0 or 1
-    int pad2;
-    double budget;      // the digit budget of this scan (eagle_set_scan_budget)
-    int e;              // the scale exponent w_scale_exp(maxabs_off): the digits are those of round(Wu * 2^(8 S_sliced - e - 2))
-    int pad3;
-    // second level of the spectral bound (k_gram_hi_i8): sum of squares of the low part of offdiag(Ds Ds), its largest diagonal entry,
-    // whether a high part left int8, whether level 1 declined and level 2 is to run, and the level that took the digit off (0: none)
-    unsigned long long lo_sumsq;
-    int maxdiag, hi_overflow, spec_try2, level;
-    // W itself came from int8 digit slices (eagle_w8.hip): || Wu - truth ||_F <= wErr, i.e. |error of marker i| <= wErr sum_j m'_ij^2 on top
-    // of the digit terms (0: the fp64 products)
-    double wErr;
-    // round 4: the budget is tried TIGHT first (1e-7 unless eagle_set_scan_budget fixed one): `budget` above is the one in force for this
-    // scan -- the tight one if the digits that run certify a marker with q2 = n_pad to it, else the default; specH1 = level 1's bound while
-    // level 2 is being tried
-    double specH1;
-    // the default budget behind a tight one in force (= budget otherwise): what the certificate ENFORCES per marker falls back to it when
-    // more than CERT_TIGHT_MAX markers of the scan miss the tight threshold (see k_cert_select)
-    double budget_loose;
-};
+// (VaraHdr, the head of the workspace: eagle_internal.h -- the host reads it back)
 __global__ __launch_bounds__(256) void k_absmax_offdiag(const double* __restrict__ x, long np, unsigned long long* __restrict__ bits) {
     double m = 0.0;
     const long n = np * np;
@@ -1258,7 +1230,8 @@ __global__ __launch_bounds__(256) void k_vara_i8_finish(const long long* __restr
 // the decision does not depend on how the markers were cut up); more than CERT_TIGHT_MAX of them and the certificate enforces the
 // default budget (1.8 x 5e-7 = 0.9 of the tolerance, round 3's rule), else the tight one.  eagle_cert_info.over_tight reports the count.
 #define CERT_TIGHT_MAX 512
-struct CertHdr { unsigned long long lb_bits; int count; int overflow; int flagged; int tight; };  // = eagle_cert_info of the public header
+struct CertHdr { unsigned long long lb_bits; int count; int overflow; int flagged; int tight; };  // = eagle_cert_info of the public header, which the host reads it as
+static_assert(sizeof(CertHdr) == sizeof(eagle_cert_info) && sizeof(CertHdr) == 24, "CertHdr is the device form of eagle_cert_info");
 
 struct CertCtx { double delta, absR, sumdiag, specH, flag_rel, flag_loose, wErr; int stochastic; };
 __device__ __forceinline__ CertCtx cert_ctx(const VaraHdr* hdr) {

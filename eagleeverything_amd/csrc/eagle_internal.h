@@ -114,6 +114,37 @@ int eagle_dev_line_scores(eagle_ctx* ctx, const int8_t* img, long rows, long col
 #ifdef __cplusplus
 }
 #include "eagle_host.h"
+// Head of the digit workspace of the int8 scan (eagle_i8mfma.hip): written on the device, copied back by scan_range for the figures of
+// eagle_last_scan_digits / _budget / _enforced.
+struct VaraHdr {
+    double maxabs_off;  // max |Wu[j][k]|, j != k
+    int S;              // digit slices in use
+    int pad;
+    double bound;       // n_pad^2 * 2^(e+1-8S): absolute error bound of every vara_i
+    double sumdiag;     // sum_k |Wu[k][k]|
+    double R;           // sum_{j<k} Wu[j][k] (the off-diagonal quadratic form of the all-ones vector)
+    double specH;       // > 0: the scan runs on S = S_sliced - 1 digits and |digit error of marker i| <= specH * sum_j m'_ij^2 (k_spectral_decide)
+    int S_sliced;       // digits k_slice_w cut (the scale of the integers Q); S_sliced - S is 0 or 1
+    int pad2;
+    double budget;      // the digit budget of this scan (eagle_set_scan_budget)
+    int e;              // the scale exponent w_scale_exp(maxabs_off): the digits are those of round(Wu * 2^(8 S_sliced - e - 2))
+    int pad3;
+    // second level of the spectral bound (k_gram_hi_i8): sum of squares of the low part of offdiag(Ds Ds), its largest diagonal entry,
+    // whether a high part left int8, whether level 1 declined and level 2 is to run, and the level that took the digit off (0: none)
+    unsigned long long lo_sumsq;
+    int maxdiag, hi_overflow, spec_try2, level;
+    // W itself came from int8 digit slices (eagle_w8.hip): || Wu - truth ||_F <= wErr, i.e. |error of marker i| <= wErr sum_j m'_ij^2 on top
+    // of the digit terms (0: the fp64 products)
+    double wErr;
+    // round 4: the budget is tried TIGHT first (1e-7 unless eagle_set_scan_budget fixed one): `budget` above is the one in force for this
+    // scan -- the tight one if the digits that run certify a marker with q2 = n_pad to it, else the default; specH1 = level 1's bound while
+    // level 2 is being tried
+    double specH1;
+    // the default budget behind a tight one in force (= budget otherwise): what the certificate ENFORCES per marker falls back to it when
+    // more than CERT_TIGHT_MAX markers of the scan miss the tight threshold (see k_cert_select)
+    double budget_loose;
+};
+static_assert(sizeof(VaraHdr) == 120, "VaraHdr: the device kernels and the host copy agree on this layout");
 struct eagle_ctx;
 bool eagle_w8_wanted(const eagle_ctx* ctx, long n_pad);
 void eagle_w8_release(eagle_ctx* ctx);

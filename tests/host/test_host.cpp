@@ -204,12 +204,97 @@ static void test_loader_windows() {
     }
 }
 
+// ---- the cached S of the scan: s_plan, s_outcome, s_slot_valid ---------------------------------------------------------
+// The expectations are written out row by row from the tables of the rule (first row that applies), not taken from s_plan.
+struct SWant { SSource source; SVerify verify; bool refresh; };
+static SWant s_want(const SCall& c, const SPolicy& p, const SHeld& h) {
+    const bool host_verify = !c.rv && !p.no_host_verify;
+    const bool cacheable = c.np <= p.max_np && !p.no_scache && h.dev_np == c.np;   // (the two device buffers could be allocated)
+    const bool cache_holds_n = h.dev_np == c.np && h.dev_n == c.n, host_holds_n = h.host_n == c.n;
+    // source: no S at all
+    if (c.w_direct) return {S_NONE, SV_NONE, false};
+    // source: device cache, already trusted (the host copy is brought up to date for the calls that follow)
+    if (cacheable && c.s_trusted) return {S_CACHE_TRUSTED, SV_NONE, host_verify && !host_holds_n};
+    if (cacheable && p.trust_s && cache_holds_n) return {S_CACHE_TRUSTED, SV_NONE, host_verify && !host_holds_n};
+    // source: device cache, to be verified -- host memcmp, else the device comparison, inline or deferred
+    if (cacheable && cache_holds_n && host_verify && host_holds_n) return {S_CACHE_VERIFY, SV_HOST, false};
+    if (cacheable && cache_holds_n && (c.streamed || c.bounds_flow || c.rv)) return {S_CACHE_VERIFY, SV_DEVICE_INLINE, false};
+    if (cacheable && cache_holds_n) return {S_CACHE_VERIFY, SV_DEVICE_DEFERRED, false};
+    // source: upload into the device cache (the upload leaves no host copy of n behind: refreshed whenever the host verifies)
+    if (cacheable) return {S_CACHE_UPLOAD, SV_NONE, host_verify};
+    // source: arena slot, to be verified (always by the host)
+    if (!p.no_scache && h.slot && host_verify && !c.s_trusted && host_holds_n) return {S_SLOT_VERIFY, SV_HOST, false};
+    // source: upload into the arena slot
+    return {S_SLOT_UPLOAD, SV_NONE, host_verify && !p.no_scache};
+}
+static void test_scache_rule() {
+    const long n = 900, np = 1024;
+    long cases = 0, seen[6] = {0, 0, 0, 0, 0, 0}, seen_v[4] = {0, 0, 0, 0};
+    for (int bits = 0; bits < 512; bits++)
+        for (long max_np : {0L, 512L, 1024L, 16384L})          // np above, above, AT and below the limit
+            for (long dev_np : {0L, 1024L, 2048L})             // no buffers, buffers of this size, of another
+                for (long dev_n : {0L, 900L, 700L})            // n equal and unequal to what the cache holds
+                    for (long host_n : {0L, 900L, 700L}) {
+                        const SCall c = {(bits & 1) != 0, (bits & 2) != 0, n, np, (bits & 4) != 0, (bits & 8) != 0, (bits & 16) != 0};
+                        SPolicy p;
+                        p.no_scache = (bits & 32) != 0; p.no_host_verify = (bits & 64) != 0; p.trust_s = (bits & 128) != 0; p.max_np = max_np;
+                        const SHeld h = {dev_np, dev_n, host_n, (bits & 256) != 0};
+                        const SPlan got = s_plan(c, p, h);
+                        const SWant want = s_want(c, p, h);
+                        CHECK(got.source == want.source && got.verify == want.verify && got.refresh_host == want.refresh);
+                        cases++; seen[got.source]++; seen_v[got.verify]++;
+                        // the invariants, over the whole enumeration
+                        if (c.rv) CHECK(got.verify != SV_DEVICE_DEFERRED);                         // a device of a multi-device call never defers
+                        if (got.source == S_SLOT_VERIFY) CHECK(host_n == n && got.verify == SV_HOST);  // no arena-slot source without a host copy for n
+                        if (c.w_direct) CHECK(got.source == S_NONE && got.verify == SV_NONE && !got.refresh_host);   // never touches the cache
+                        if (c.s_trusted) CHECK(got.verify == SV_NONE);
+                        if (p.no_scache && !c.w_direct) CHECK(got.source == S_SLOT_UPLOAD && !got.refresh_host);
+                        if (got.refresh_host) CHECK(got.verify == SV_NONE);                         // one helper thread serves both
+                        if (got.verify != SV_NONE) CHECK(got.source == S_CACHE_VERIFY || got.source == S_SLOT_VERIFY);
+                        // a second attempt verifies nothing (no third): trusted, or the cache forgotten (no device copy, no host copy, no slot)
+                        if (dev_n != n && host_n != n) CHECK(got.verify == SV_NONE);
+                        if ((got.source == S_CACHE_TRUSTED || got.source == S_CACHE_VERIFY || got.source == S_CACHE_UPLOAD)) CHECK(np <= max_np && dev_np == np);
+                    }
+    CHECK(cases == 512L * 4 * 27);
+    for (long v : seen) CHECK(v > 0);      // every source and every verification occurs
+    for (long v : seen_v) CHECK(v > 0);
+    // settling
+    CHECK(s_outcome(SV_NONE, false) == S_NOTHING && s_outcome(SV_NONE, true) == S_NOTHING);
+    for (SVerify v : {SV_HOST, SV_DEVICE_INLINE, SV_DEVICE_DEFERRED}) CHECK(s_outcome(v, false) == S_SAME);
+    CHECK(s_outcome(SV_HOST, true) == S_OTHER_FORGOTTEN);            // the caller's S is not on the device
+    CHECK(s_outcome(SV_DEVICE_INLINE, true) == S_OTHER_ON_DEVICE && s_outcome(SV_DEVICE_DEFERRED, true) == S_OTHER_ON_DEVICE);
+}
+// The generation rule.  The model of the arena: a counter bumped by everything that allocates, frees or replaces the block, and an address
+// that MAY come back unchanged (the defect this replaces compared addresses).
+static void test_scache_slot() {
+    struct Arena { unsigned long gen = 1; } ar;
+    const size_t o = 0;
+    SSlot none;
+    CHECK(!s_slot_valid(none, ar.gen, o, 900, 1024));                       // nothing recorded
+    CHECK(!s_slot_valid(none, 0, 0, 0, 0));
+    SSlot s;
+    s.gen = ar.gen; s.off = o; s.n = 900; s.np = 1024;
+    CHECK(s_slot_valid(s, ar.gen, o, 900, 1024));                           // valid at (g, o) ...
+    CHECK(!s_slot_valid(s, ar.gen, o + 256, 900, 1024));                    // ... and only there
+    CHECK(!s_slot_valid(s, ar.gen, o, 901, 1024) && !s_slot_valid(s, ar.gen, o, 900, 1280));
+    for (const char* event : {"grow", "replace by prefetch", "drop"}) {     // each bumps the generation; the block's address is not asked
+        (void)event;
+        const unsigned long before = ar.gen++;
+        CHECK(s_slot_valid(s, before, o, 900, 1024) && !s_slot_valid(s, ar.gen, o, 900, 1024));
+        SSlot again = s;
+        again.gen = ar.gen;                                                  // committed by the scan that went through after the event
+        CHECK(s_slot_valid(again, ar.gen, o, 900, 1024));
+        s = again;
+    }
+}
+
 int main(int argc, char** argv) {
     const std::string what = argc > 1 ? argv[1] : "all";
     if (what == "all" || what == "rendezvous") test_rendezvous();
     if (what == "all" || what == "rules") test_small_rules();
     if (what == "all" || what == "text") test_text();
     if (what == "all" || what == "loader") test_loader_windows();
+    if (what == "all" || what == "scache") { test_scache_rule(); test_scache_slot(); }
     if (g_fail) { fprintf(stderr, "%d check(s) failed\n", g_fail); return 1; }
     printf("host checks passed (%s)\n", what.c_str());
     return 0;

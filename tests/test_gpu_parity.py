@@ -1042,6 +1042,52 @@ def test_S_kept_in_its_arena_slot_above_the_cache_limit(api, tmp_path, monkeypat
         api.drop_cache()
 
 
+def test_S_in_its_arena_slot_is_not_trusted_after_the_arena_grew(api, tmp_path, monkeypatch):
+    """The arena slot of S is valid by the arena's generation, not by its address: the same S on a LARGER file of the same individuals
+    grows the arena (free + allocate, often at the same address), and the scan must upload S again instead of computing on whatever
+    the fresh block holds while the host comparison reports a hit.  Then the slot serves again; and after drop_cache (arena and host
+    copy given back) the same S is an upload once more.  Always the bits of a call with the mechanism switched off."""
+    from eagleeverything_amd import _lib
+    n = 900
+    rng = np.random.default_rng(8)
+    files = {}
+    for L, seed in ((1024, 31), (6000, 47)):                         # two different panels, not one a prefix of the other
+        d = tmp_path / ("L%d" % L)
+        d.mkdir()
+        Mt8 = synth.genotypes_marker_major(n, L, seed=seed)
+        files[L] = (Mt8, synth.write_geno_pair(str(d), Mt8))
+    assert not np.array_equal(files[1024][0], files[6000][0][:1024])
+    lib, pad = _lib.load(), lambda x: (x + 255) // 256 * 256
+    assert lib.eagle_vara_i8_workspace_bytes(pad(n), pad(6000), 0) > lib.eagle_vara_i8_workspace_bytes(pad(n), pad(1024), 0)   # the arena's L-dependent term
+    A = rng.standard_normal((n, 30)) / 6.0
+    S = np.asfortranarray(np.eye(n) + A @ A.T)
+    V = {1: np.asfortranarray(0.6 * np.eye(n) - 0.02 * (A[:, :5] @ A[:, :5].T)), 2: np.asfortranarray(0.9 * np.eye(n) - 0.01 * (A[:, 5:9] @ A[:, 5:9].T))}
+    ahat = rng.standard_normal(n)
+    call = lambda L, v: api.calculate_a_and_vara_rcpp(files[L][1]["asciifileMt"], NA, S, V[v], 8.0, (L, n), ahat)
+    api.drop_cache()
+    monkeypatch.setenv("EAGLE_HIP_NO_SCACHE", "1")
+    ref = {(L, v): call(L, v) for L in (1024, 6000) for v in (1, 2)}
+    monkeypatch.delenv("EAGLE_HIP_NO_SCACHE")
+    monkeypatch.setenv("EAGLE_HIP_SCACHE_MAX_NP", "0")
+    try:
+        api.drop_cache()
+        stats, got = [api.scan_operand_cache_stats()], []
+        for key in ((1024, 1), (1024, 2), (6000, 1), (6000, 2)):
+            got.append((call(*key), key))
+            stats.append(api.scan_operand_cache_stats())
+        api.drop_cache()
+        got.append((call(6000, 2), (6000, 2)))                        # arena and host copy gone: uploaded again
+        stats.append(api.scan_operand_cache_stats())
+        d = [(b[0] - a[0], b[1] - a[1]) for a, b in zip(stats, stats[1:])]
+        print("(hits, misses) per call:", d)
+        assert d == [(0, 0), (1, 0), (0, 0), (1, 0), (0, 0)], d       # filled; hit; arena re-laid: uploaded; hit; dropped: uploaded
+        for r, key in got:
+            np.testing.assert_array_equal(r["a"], ref[key]["a"])
+            np.testing.assert_array_equal(r["vara"], ref[key]["vara"])
+    finally:
+        api.drop_cache()
+
+
 def test_mmt_of_many_individuals_comes_back_through_the_staged_download(api, tmp_path):
     """n = 6,000: the 288 MB result returns through the two pinned staging buffers in 64 MiB pieces (csrc/eagle_api.cpp, download_big),
     a path the smaller shapes above never take; the normalised form too.  Exact against the integer product."""
