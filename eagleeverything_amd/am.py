@@ -780,3 +780,28 @@ def Predict(effects, geno, X=None, availmemGb=8, device=0):
             raise ValueError("Predict: X holds %d columns, the model's design matrix %d" % (X.shape[1], nX))
         out["yhat"] = X @ np.asarray(effects["beta"], dtype=np.float64)[:nX] + out["genetic"]
     return out
+
+
+def EpistasisOfLoci(AMobj, trait, X, geno, availmemGb=8, backend=None, device=0):
+    """Do the loci AM() reported interact with anything in the genome?  r_api.Epistasis(loci = AMobj's loci) on the conditional residual
+    P y of the fitted model -> Epistasis' loci-mode dict, with "loci" 0-based, "selected_loci" as AM() reports them (1-based) and "geno":
+    the panel of the kept individuals the statistics refer to.
+
+    trait, X and geno are what AM() was given (MarkerEffects' rule for NaN records: they leave as a VIEW).  MarkerEffects refits the
+    model with the loci as fixed effects and returns P y; ve P y = y - X beta - ghat is the residual with fixed effects AND the polygenic
+    background taken out, so the interaction test is not confounded by relatedness the way a test on the raw trait is.  The F statistic
+    does not depend on the scale of its trait, so P y is used as it is (r_api.quantise_trait centres and scales it)."""
+    from . import r_api
+    backend = backend or HipBackend(device)
+    y = np.asarray(trait, dtype=np.float64).ravel()
+    X = np.asarray(X, dtype=np.float64).reshape(y.size, -1)
+    indxNA = np.asarray(AMobj.get("indxNA", ()), dtype=np.int64).ravel()
+    (X, y), kept = _drop_na_rows(indxNA, (X, y), geno, backend=backend, device=device)      # once: MarkerEffects gets the kept records
+    eff = MarkerEffects(dict(AMobj, indxNA=()), y, X, kept, availmemGb=availmemGb, backend=backend, device=device)
+    loci0 = [int(j) - 1 for j in eff["loci"]]
+    if not loci0:
+        raise ValueError("EpistasisOfLoci: AM() reported no locus")
+    out = r_api.Epistasis(kept, eff["Py"], loci=loci0, availmemGb=availmemGb, device=device)
+    out["selected_loci"] = list(eff["loci"])
+    out["geno"] = kept
+    return out

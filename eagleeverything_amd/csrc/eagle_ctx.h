@@ -296,6 +296,9 @@ extern "C" long eagle_parentage_parts(long ns, long nd);
 extern "C" int eagle_dev_parentage(eagle_ctx* ctx, const uint64_t* O, long n_o, const uint64_t* S, long ns, const uint64_t* D, long nd, int nplanes, long L,
                                    const int32_t* oidx, const int32_t* sidx, const int32_t* didx, long o0, long no, int min_overlap, int allow_self,
                                    uint64_t* part_k, int32_t* part_n, int32_t* best, void* stream);
+// Epistasis (eagle_epi.hip; include/eagle_hip.h section 1b''''ii): msu[3 r ..] = (sum g, sum g^2, sum y g) of the rows of an int8 Mt tile, y n int32
+// on the device.  The tile kernel is launched by the two entry points in the same file.
+extern "C" int eagle_dev_epi_marker(eagle_ctx* ctx, const int8_t* Mt8, long rows, long n, long ld, const int32_t* y, int64_t* msu, void* stream);
 // Pairwise-complete IBS counts from a .bed file (eagle_bedibs.hip; include/eagle_hip.h section 1b'''ii), device pointers throughout.  The
 // four fp4 operand images (g, u, h, c; plane p at M4 + p * plane_bytes, n_pad rows of ld4 bytes, L_pad markers written) of `rows` raw
 // .bed rows, `include` one byte per row or null; the four n x n int32 results and dist (or null) from the four Gram accumulators

@@ -587,4 +587,105 @@ static inline long parentage_list_check(const int32_t* list, long cnt, long n, b
 }
 // The ordinal of the candidate (s_idx-th sire, d_idx-th dam): ties in the error count go to the smaller one.
 static inline EAGLE_HD long parentage_ordinal(long s_idx, long d_idx, long n_d) { return s_idx * (n_d > 0 ? n_d : 1) + d_idx; }
+
+// ------------------------------------------------------------------------------------------------
+// Epistasis (include/eagle_hip.h section 1b''''ii): the argument rule of eagle_epistasis_loci / eagle_epistasis_pairs, the balanced
+// base-128 digits of the trait, t53 and the 128-bit rule of the statistic.  epi_stat is the ONE statement of the rule in C++: the tile
+// kernel's epilogue (eagle_epi.hip) and the CPU test binary call it as is.
+// ------------------------------------------------------------------------------------------------
+#define EPI_MAX_N 65535L
+#define EPI_YMAX 1000000
+#define EPI_MAX_LOCI 64L
+// What is wrong with the dims and the trait of a call, or NULL.  y may be NULL: not checked.
+static inline const char* epi_arg_error(long n, long L, const int32_t* y) {
+    if (n <= 0 || L <= 0) return "dims must be positive";
+    if (L > 0x7fffffffL) return "2^31 markers or more";
+    if (n > EPI_MAX_N) return "more than EAGLE_EPI_MAX_N = 65535 individuals";
+    if (y)
+        for (long k = 0; k < n; k++)
+            if (y[k] > EPI_YMAX || y[k] < -EPI_YMAX) return "a trait value beyond EAGLE_EPI_YMAX = 1000000 in absolute value";
+    return nullptr;
+}
+static inline const char* epi_loci_arg_error(long L, const long* loci, long nloci) {
+    if (nloci < 1 || nloci > EPI_MAX_LOCI) return "the number of loci must be in [1, 64]";
+    for (long k = 0; k < nloci; k++)
+        if (loci[k] < 0 || loci[k] >= L) return "locus outside [0, L)";
+    return nullptr;
+}
+static inline const char* epi_pairs_arg_error(long gap, double min_stat, long hit_cap, bool has_tables) {
+    if (gap < 0) return "gap must not be negative";
+    if (min_stat != min_stat) return "min_stat is NaN";
+    if (hit_cap < 0) return "hit_cap must not be negative";
+    if (hit_cap > 0 && !has_tables) return "hit_cap > 0 needs hit_ij, hit_stat and hit_mom";
+    return nullptr;
+}
+// y = d0 + 128 d1 + 128^2 d2 with d in [-64, 63]: d_p = ((y_p + 64) & 127) - 64, y_{p+1} = (y_p - d_p) >> 7 (the difference is a multiple
+// of 128, so the shift is exact).  Three digits hold [-64 * 16513, 63 * 16513] = [-1056832, 1040319], which contains every |y| <= 10^6;
+// returns what is left of y behind them (0 there).
+static inline EAGLE_HD int32_t epi_digits(int32_t y, int8_t d[3]) {
+    for (int p = 0; p < 3; p++) {
+        const int32_t dp = ((y + 64) & 127) - 64;
+        d[p] = (int8_t)dp;
+        y = (y - dp) >> 7;
+    }
+    return y;
+}
+typedef __int128 epi_i128;
+// x truncated toward zero to its top 53 bits, as a double: |x| = m 2^sh + (the sh low bits dropped) with m < 2^53; both factors are
+// exact in fp64 and so is their product (|x| < 2^127).
+static inline EAGLE_HD double epi_t53(epi_i128 x) {
+    const bool neg = x < 0;
+    const unsigned __int128 m = neg ? (unsigned __int128)0 - (unsigned __int128)x : (unsigned __int128)x;
+    const uint64_t hi = (uint64_t)(m >> 64), lo = (uint64_t)m;
+    int bits = 0;
+    if (hi) bits = 128 - __builtin_clzll(hi);
+    else if (lo) bits = 64 - __builtin_clzll(lo);
+    const int sh = bits > 53 ? bits - 53 : 0;
+    const uint64_t top = (uint64_t)(m >> sh);
+    const uint64_t pw = (uint64_t)(1023 + sh) << 52;           // 2^sh
+    double p;
+    memcpy(&p, &pw, sizeof p);
+    const double v = (double)top * p;                           // exact
+    return neg ? -v : v;
+}
+#if defined(__HIP_DEVICE_COMPILE__)
+#define EPI_DIV(a, b) __ddiv_rn((a), (b))
+#define EPI_MUL(a, b) __dmul_rn((a), (b))
+#define EPI_SUB(a, b) __dadd_rn((a), -(b))
+#else
+#define EPI_DIV(a, b) ((a) / (b))
+#define EPI_MUL(a, b) ((a) * (b))
+#define EPI_SUB(a, b) ((a) - (b))
+#endif
+struct EpiTrait { long n; int64_t Y, T; };                     // n, sum y, sum y^2
+struct EpiMarker { int64_t s, q, u; };                          // sum g, sum g^2, sum y g
+// The statistic of one pair from its exact sums (rules 1 - 5 of the section): NaN where the pair is undefined.  S (may be NULL): Delta,
+// Sxx, Sxy, Syy as computed, for the tests.  No product feeds a sum in the fp64 part, so nothing can contract into an FMA on the host.
+static inline EAGLE_HD double epi_stat(const EpiTrait& t, const EpiMarker& a, const EpiMarker& b, int64_t d, int64_t e, int64_t f, int64_t h,
+                                       int64_t z, epi_i128* S) {
+    const int64_t n = t.n;
+    const int64_t A00 = a.q * b.q - d * d, A01 = d * b.s - a.s * b.q, A02 = a.s * d - a.q * b.s;
+    const int64_t A11 = n * b.q - b.s * b.s, A12 = a.s * b.s - n * d, A22 = n * a.q - a.s * a.s;
+    const int64_t Delta = n * A00 + a.s * A01 + b.s * A02;
+    const int64_t Ac0 = A00 * d + A01 * e + A02 * f, Ac1 = A01 * d + A11 * e + A12 * f, Ac2 = A02 * d + A12 * e + A22 * f;
+    const epi_i128 cAc = (epi_i128)d * Ac0 + (epi_i128)e * Ac1 + (epi_i128)f * Ac2;
+    const epi_i128 cAu = (epi_i128)t.Y * Ac0 + (epi_i128)a.u * Ac1 + (epi_i128)b.u * Ac2;
+    const epi_i128 Au0 = (epi_i128)A00 * t.Y + (epi_i128)A01 * a.u + (epi_i128)A02 * b.u;
+    const epi_i128 Au1 = (epi_i128)A01 * t.Y + (epi_i128)A11 * a.u + (epi_i128)A12 * b.u;
+    const epi_i128 Au2 = (epi_i128)A02 * t.Y + (epi_i128)A12 * a.u + (epi_i128)A22 * b.u;
+    const epi_i128 uAu = Au0 * t.Y + Au1 * a.u + Au2 * b.u;
+    const epi_i128 Sxx = (epi_i128)Delta * h - cAc, Sxy = (epi_i128)Delta * z - cAu, Syy = (epi_i128)Delta * t.T - uAu;
+    if (S) { S[0] = Delta; S[1] = Sxx; S[2] = Sxy; S[3] = Syy; }
+    const uint64_t nanbits = 0x7ff8000000000000ull, infbits = 0x7ff0000000000000ull;
+    double out;
+    if (!(n > 4 && Delta > 0 && Sxx > 0)) { memcpy(&out, &nanbits, sizeof out); return out; }
+    const double xy = epi_t53(Sxy);
+    const double r2 = EPI_MUL(EPI_DIV(xy, epi_t53(Sxx)), EPI_DIV(xy, epi_t53(Syy)));
+    if (!(r2 < 1.0)) { memcpy(&out, &infbits, sizeof out); return out; }
+    return EPI_DIV(EPI_MUL((double)(n - 4), r2), EPI_SUB(1.0, r2));
+}
+// Whether the pair i < j is tested: not skipped by the gap rule.
+static inline EAGLE_HD bool epi_pair_tested(long i, long j, const int32_t* chrom, long gap) {
+    return !(j - i <= gap && (!chrom || chrom[i] == chrom[j]));
+}
 #endif

@@ -15,6 +15,7 @@
 selected_loci follow R: 1-based, NA = numpy.nan.  The "-1 only if no NA anywhere" rule
 (calculateMMt.R:24, calculate_a_and_vara.R:23) is reproduced literally.
 """
+import math
 import os
 
 import numpy as np
@@ -2236,3 +2237,235 @@ def Predict(effects, geno, X=None, availmemGb=8, device=0):
     """Genetic values of the individuals of any panel with the model's markers from MarkerEffects' result (am.Predict)."""
     from . import am
     return am.Predict(effects, geno, X=X, availmemGb=availmemGb, device=device)
+
+
+# ---- epistasis (include/eagle_hip.h section 1b''''ii): the additive x additive interaction F test between pairs of markers ----
+def quantise_trait(y):
+    """A real trait as integers for the exact epistasis scan -> (yq int32, scale): the trait is centred at its mean, multiplied by
+    scale = the largest power of two that keeps max|y - mean| * scale <= EPI_YMAX = 10^6, and rounded with np.rint.  The F statistic is
+    invariant to a shift and a scale of the trait, so all this costs is the rounding: at most half a unit in 10^6 of the trait's
+    largest deviation from its mean (between 0.5e-6 and 1e-6 of it, as scale is a power of two) per record.  A constant trait gives zeros
+    and scale 1.0; a non-finite record raises ValueError."""
+    ya = np.asarray(y, dtype=np.float64).ravel()
+    if not np.all(np.isfinite(ya)):
+        raise ValueError("quantise_trait: a trait record is not finite (drop NaN records first: am.reshape_geno(view=True))")
+    c = ya - ya.mean() if ya.size else ya
+    mx = float(np.abs(c).max()) if c.size else 0.0
+    if mx == 0.0:
+        return np.zeros(ya.size, dtype=np.int32), 1.0
+    e = int(np.floor(np.log2(rcpp_api.EPI_YMAX / mx)))
+    while np.ldexp(mx, e + 1) <= rcpp_api.EPI_YMAX:
+        e += 1
+    while np.ldexp(mx, e) > rcpp_api.EPI_YMAX:
+        e -= 1
+    scale = float(np.ldexp(1.0, e))
+    return np.rint(c * scale).astype(np.int32), scale
+
+
+def _epi_t53(x):
+    """x (a Python int) truncated toward zero to its top 53 bits, as a float (exact)."""
+    m = -x if x < 0 else x
+    sh = max(0, m.bit_length() - 53)
+    v = float((m >> sh) << sh)
+    return -v if x < 0 else v
+
+
+def _epi_max(a):
+    a = np.asarray(a)
+    if a.dtype == object:
+        return None
+    return int(np.abs(a.astype(np.int64)).max()) if a.size else 0
+
+
+def _epi_mul(a, b):
+    """a * b exactly: in int64 where the operands' magnitudes prove that nothing wraps, else on Python ints (object arrays)."""
+    ma, mb = _epi_max(a), _epi_max(b)
+    if ma is not None and mb is not None and ma * mb < 1 << 62:
+        return np.asarray(a, dtype=np.int64) * np.asarray(b, dtype=np.int64)
+    return np.asarray(a).astype(object) * np.asarray(b).astype(object)
+
+
+def _epi_add(*terms):
+    """The exact sum of the terms, by the same rule."""
+    mx = [_epi_max(t) for t in terms]
+    if all(m is not None for m in mx) and sum(mx) < 1 << 62:
+        out = np.asarray(terms[0], dtype=np.int64)
+        for t in terms[1:]:
+            out = out + np.asarray(t, dtype=np.int64)
+        return out
+    out = np.asarray(terms[0]).astype(object)
+    for t in terms[1:]:
+        out = out + np.asarray(t).astype(object)
+    return out
+
+
+def _epi_sums(n, Y, T, mi, mj, mom):
+    """Delta, Sxx, Sxy, Syy of rule 3, exact: int64 arrays where the magnitudes allow it, else object arrays of Python ints (_epi_mul,
+    _epi_add).  mi, mj: (s, q, u) of the two markers as int64 arrays that broadcast against the leading shape of mom; mom[..., 5]: the
+    five pair sums."""
+    M, A_ = _epi_mul, _epi_add
+    si, qi, ui = (np.asarray(a, dtype=np.int64) for a in mi)
+    sj, qj, uj = (np.asarray(a, dtype=np.int64) for a in mj)
+    d, e, f, h, z = (np.asarray(mom[..., c], dtype=np.int64) for c in range(5))
+    n, Y, T = np.int64(n), np.int64(Y), np.int64(T)
+    neg = lambda a: M(a, np.int64(-1))                                    # noqa: E731
+    A00, A01, A02 = A_(M(qi, qj), neg(M(d, d))), A_(M(d, sj), neg(M(si, qj))), A_(M(si, d), neg(M(qi, sj)))
+    A11, A12, A22 = A_(M(n, qj), neg(M(sj, sj))), A_(M(si, sj), neg(M(n, d))), A_(M(n, qi), neg(M(si, si)))
+    Delta = A_(M(n, A00), M(si, A01), M(sj, A02))
+    Amat = ((A00, A01, A02), (A01, A11, A12), (A02, A12, A22))
+    mv = lambda v: [A_(*[M(Amat[r][c], v[c]) for c in range(3)]) for r in range(3)]      # noqa: E731
+    dot = lambda v, w: A_(*[M(v[r], w[r]) for r in range(3)])                            # noqa: E731
+    c, u = (d, e, f), (Y, ui, uj)
+    Ac, Au = mv(c), mv(u)
+    return (Delta, A_(M(Delta, h), neg(dot(c, Ac))), A_(M(Delta, z), neg(dot(u, Ac))), A_(M(Delta, T), neg(dot(u, Au))))
+
+
+def _epi_t53_array(x):
+    """_epi_t53 of every entry of an int64 or object array -> fp64."""
+    x = np.asarray(x)
+    if x.dtype == object:
+        return np.array([_epi_t53(int(v)) for v in x.ravel()], dtype=np.float64).reshape(x.shape)
+    m = np.abs(x.astype(np.int64)).astype(np.uint64)                      # |x| < 2^62 here (_epi_add's rule)
+    sh = np.zeros(m.shape, dtype=np.uint64)
+    for k in range(53, 64):
+        sh += (m >> np.uint64(k)) != 0
+    v = ((m >> sh) << sh).astype(np.float64)                              # at most 53 significant bits: exact
+    return np.where(x < 0, -v, v)
+
+
+def _epi_stat(n, Delta, Sxx, Sxy, Syy):
+    """Rules 4 and 5 on the arrays of _epi_sums -> fp64 of their shape: every fp64 step one numpy operation, in the header's order."""
+    shape = np.shape(Delta)
+    D, xx, xy, yy = (np.asarray(a).ravel() for a in (Delta, Sxx, Sxy, Syy))
+    ok = (np.asarray(D > 0).astype(bool) & np.asarray(xx > 0).astype(bool)) if n > 4 else np.zeros(D.size, dtype=bool)
+    stat = np.full(D.size, np.nan)
+    idx = np.flatnonzero(ok)
+    if idx.size:
+        fx, fxy, fy = _epi_t53_array(xx[idx]), _epi_t53_array(xy[idx]), _epi_t53_array(yy[idx])
+        with np.errstate(all="ignore"):
+            r2 = (fxy / fx) * (fxy / fy)
+            st = (np.float64(n - 4) * r2) / (np.float64(1.0) - r2)
+        st[~(r2 < 1.0)] = np.inf
+        stat[idx] = st
+    return stat.reshape(shape)
+
+
+def epistasis_host(G, yq, loci=None, chrom=None, gap=0, min_stat=0.0, hit_cap=None):
+    """The numpy restatement of rcpp_api.epistasis_loci (loci given) and rcpp_api.epistasis_pairs (loci None) on the genotypes G, int8 (n,
+    L) in {-1, 0, +1}, and the integer trait yq: integer matrix products for the sums, Python ints for the 128-bit part, numpy fp64 for the
+    six rounded operations.  Returns the same tables: {"stat" (L, k), "mom" (L, k, 5)} or epistasis_pairs' dict (hit_cap None: always with
+    the tables)."""
+    Gi = np.asarray(G, dtype=np.int64)
+    n, L = Gi.shape
+    y = np.asarray(yq, dtype=np.int64).ravel()
+    if y.size != n:
+        raise ValueError("epistasis_host: %d trait records for %d individuals" % (y.size, n))
+    G2 = Gi * Gi
+    Y, T = int(y.sum()), int((y * y).sum())
+    s, q, u = Gi.sum(axis=0), G2.sum(axis=0), y @ Gi
+    cols = np.arange(L) if loci is None else np.atleast_1d(np.asarray(loci, dtype=np.int64)).ravel()
+    Bj, B2 = Gi[:, cols], G2[:, cols]
+    mom = np.stack([Gi.T @ Bj, G2.T @ Bj, Gi.T @ B2, G2.T @ B2, (Gi * y[:, None]).T @ Bj], axis=-1)
+    if loci is not None:
+        S = _epi_sums(n, Y, T, (s[:, None], q[:, None], u[:, None]), (s[cols][None, :], q[cols][None, :], u[cols][None, :]), mom)
+        return {"stat": _epi_stat(n, *S), "mom": mom}
+    ii, jj = np.triu_indices(L, 1)
+    keep = np.ones(ii.size, dtype=bool)
+    if gap > 0:
+        same = np.ones(ii.size, dtype=bool) if chrom is None else np.asarray(chrom).ravel()[ii] == np.asarray(chrom).ravel()[jj]
+        keep = ~((jj - ii <= gap) & same)
+    ii, jj = ii[keep], jj[keep]
+    pm = mom[ii, jj]
+    stat = _epi_stat(n, *_epi_sums(n, Y, T, (s[ii], q[ii], u[ii]), (s[jj], q[jj], u[jj]), pm))
+    defined = ~np.isnan(stat)
+    best = (-1, -1, float("nan"))
+    if defined.any():
+        top = stat[defined].max()
+        k = int(np.flatnonzero(defined & (stat == top))[0])          # triu order is (i, j) order
+        best = (int(ii[k]), int(jj[k]), float(top))
+    hit = np.flatnonzero(defined & (stat >= min_stat))
+    out = {"nhits": int(hit.size), "ntested": int(defined.sum()), "max": best, "hit_ij": None, "hit_stat": None, "hit_mom": None}
+    if hit_cap is None or hit.size <= hit_cap:
+        out.update(hit_ij=np.stack([ii[hit], jj[hit]], axis=1).astype(np.int32), hit_stat=stat[hit], hit_mom=pm[hit])
+    return out
+
+
+def epistasis_effects(n, Y, T, mi, mj, mom, scale=1.0):
+    """b3 and its standard error in the trait's own units from the exact sums -> (b3, se) fp64: b3 = Sxy / Sxx and se^2 = (Sxx Syy -
+    Sxy^2) / ((n - 4) Sxx^2) over `scale` (quantise_trait's), NaN where the pair is undefined."""
+    D, xx, xy, yy = (np.asarray(a, dtype=object) for a in _epi_sums(n, Y, T, mi, mj, mom))
+    shape = D.shape
+    b3, se = np.full(D.size, np.nan), np.full(D.size, np.nan)
+    for k, (dk, a, b, c) in enumerate(zip(D.ravel(), xx.ravel(), xy.ravel(), yy.ravel())):
+        if n > 4 and dk > 0 and a > 0:
+            b3[k] = (b / a) / scale
+            se[k] = math.sqrt(max(a * c - b * b, 0) / (n - 4)) / a / scale      # int / int: true division of Python ints
+    return b3.reshape(shape), se.reshape(shape)
+
+
+def Epistasis(geno, y, loci=None, map=None, gap=0, min_stat=None, p=1e-8, hit_cap=1 << 20, availmemGb=8, device=0):
+    """The additive x additive interaction test y = b0 + b1 g_i + b2 g_j + b3 g_i g_j + e between pairs of markers of a panel (PLINK
+    --epistasis for a quantitative trait; include/eagle_hip.h section 1b''''ii): the F(1, n - 4) of b3 = 0 from exact integer sums on the
+    device.  y: one record per individual; a real trait goes through quantise_trait (which costs at most half a unit in 10^6 of its
+    range), an integer one (|y| <= 10^6) is used as it is.  NaN records raise ValueError: drop them with am.reshape_geno(geno, indxNA,
+    view=True) and pass the kept records.  A constant trait raises ValueError.
+
+    loci (0-based, any number, repeats allowed): every marker against each of them -> {"loci", "stat" fp64 (L, k), NaN = undefined, "p" =
+    scipy.special.fdtrc(1, n - 4, stat), "b3", "se" (trait units), "mom" int64 (L, k, 5), "scale"}.
+    loci None: all pairs i < j, except those at most `gap` markers apart on one chromosome (map: ReadBim's dict, its Chr used; None: one
+    chromosome) -> {"hits": int32 (H, 2), "stat", "p", "b3", "se", "mom" of the hits sorted by (i, j), "nhits", "ntested": the defined
+    pairs, "max": (i, j, stat), "min_stat", "scale"}.  A hit is stat >= min_stat; min_stat None derives it from p: fdtri(1, n - 4, 1 - p).
+    With more than hit_cap hits the tables are None and nhits holds the total.  The panel must fit the device (prune or filter first)."""
+    from scipy import special
+    n, L = int(geno["dim_of_ascii_M"][0]), int(geno["dim_of_ascii_M"][1])
+    ya = np.asarray(y).ravel()
+    if ya.size != n:
+        raise ValueError("Epistasis: %d trait records for %d genotyped individuals" % (ya.size, n))
+    if np.issubdtype(ya.dtype, np.integer):
+        yq, scale = ya.astype(np.int64), 1.0
+        if yq.size and int(np.abs(yq).max()) > rcpp_api.EPI_YMAX:
+            raise ValueError("Epistasis: an integer trait beyond 10^6 in absolute value (pass it as a real trait)")
+    else:
+        if np.any(np.isnan(ya.astype(np.float64))):
+            raise ValueError("Epistasis: the trait holds NaN records; drop them and their genotypes first: am.reshape_geno(geno, indxNA, "
+                             "view=True) gives the panel of the kept individuals")
+        yq, scale = quantise_trait(ya)
+    if yq.size == 0 or int(yq.min()) == int(yq.max()):
+        raise ValueError("Epistasis: the trait is constant")
+    yq = yq.astype(np.int32)
+    Mt, dims = geno["asciifileMt"], (n, L)
+    cnt = rcpp_api.marker_counts(Mt, dims, availmemGb, device=device).astype(np.int64)
+    s, q = cnt[:, 2] - cnt[:, 0], cnt[:, 2] + cnt[:, 0]
+    u = rcpp_api.marker_scores(Mt, dims, yq, availmemGb, device=device)[:, 0]
+    Y, T = int(yq.astype(np.int64).sum()), int((yq.astype(np.int64) ** 2).sum())
+    pval = lambda st: special.fdtrc(1.0, float(n - 4), st) if n > 4 else np.full(np.shape(st), np.nan)      # noqa: E731
+    if loci is not None:
+        lv = np.atleast_1d(np.asarray(loci, dtype=np.int64)).ravel()
+        parts = [rcpp_api.epistasis_loci(Mt, dims, yq, lv[c0:c0 + 64], availmemGb, device=device) for c0 in range(0, max(lv.size, 1), 64)]
+        stat, mom = np.concatenate([a for a, _ in parts], axis=1), np.concatenate([b for _, b in parts], axis=1)
+        b3, se = epistasis_effects(n, Y, T, (s[:, None], q[:, None], u[:, None]), (s[lv][None, :], q[lv][None, :], u[lv][None, :]), mom, scale)
+        return {"loci": lv, "stat": stat, "p": pval(stat), "b3": b3, "se": se, "mom": mom, "scale": scale}
+    chrom = None
+    if map is not None:
+        m = _ld_map("Epistasis", map, geno, L, lambda text: None)
+        if m is False:
+            raise ValueError("Epistasis: the map must hold Chr and Pos entries for the panel's %d markers" % L)
+        chrom = np.unique(np.asarray(m["Chr"]).astype(str), return_inverse=True)[1].astype(np.int32)
+    if min_stat is None:
+        if not 0.0 < float(p) < 1.0 or n <= 4:
+            raise ValueError("Epistasis: p must lie in (0, 1) and n above 4")
+        min_stat = float(special.fdtri(1.0, float(n - 4), 1.0 - float(p)))
+    r = rcpp_api.epistasis_pairs(Mt, dims, yq, chrom, int(gap), float(min_stat), int(hit_cap), availmemGb, device=device)
+    out = {"hits": r["hit_ij"], "stat": r["hit_stat"], "mom": r["hit_mom"], "p": None, "b3": None, "se": None, "nhits": r["nhits"],
+           "ntested": r["ntested"], "max": r["max"], "min_stat": float(min_stat), "scale": scale}
+    if r["hit_ij"] is not None:
+        i, j = r["hit_ij"][:, 0].astype(np.int64), r["hit_ij"][:, 1].astype(np.int64)
+        out["p"] = pval(r["hit_stat"])
+        out["b3"], out["se"] = epistasis_effects(n, Y, T, (s[i], q[i], u[i]), (s[j], q[j], u[j]), r["hit_mom"], scale)
+    return out
+
+
+def EpistasisOfLoci(AMobj, trait, X, geno, availmemGb=8, backend=None, device=0):
+    """Every marker against the loci AM() reported, on the conditional residual of the fitted model (am.EpistasisOfLoci)."""
+    from . import am
+    return am.EpistasisOfLoci(AMobj, trait, X, geno, availmemGb=availmemGb, backend=backend, device=device)

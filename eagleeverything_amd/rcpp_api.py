@@ -1353,6 +1353,75 @@ def marker_scores(f_name_ascii_Mt, dims, v, max_memory_in_Gbytes=8.0, device=0):
                         max_memory_in_Gbytes, device)
 
 
+# ---- epistasis (include/eagle_hip.h section 1b''''ii): exact sums and the F statistic; p-values and effects are r_api's ----
+EPI_MAX_N = 65535
+EPI_YMAX = 1000000
+
+
+class EpiMax(C.Structure):
+    """eagle_epi_max of include/eagle_hip.h section 1b''''ii."""
+    _fields_ = [("i", C.c_int64), ("j", C.c_int64), ("stat", C.c_double)]
+
+
+def _epi_trait(who, y, n):
+    ya = np.asarray(y)
+    if ya.ndim != 1 or ya.size != n or not np.issubdtype(ya.dtype, np.integer):
+        raise ValueError("%s: y must hold one integer per individual (%d); r_api.quantise_trait makes one from a real trait" % (who, n))
+    if ya.size and int(np.abs(ya.astype(np.int64)).max()) > EPI_YMAX:
+        raise ValueError("%s: a trait value beyond EPI_YMAX = %d in absolute value" % (who, EPI_YMAX))
+    return np.ascontiguousarray(ya, dtype=np.int32)
+
+
+def epistasis_loci(f_name_ascii_Mt, dims, y, loci, max_memory_in_Gbytes=8.0, device=0, moments=True):
+    """eagle_epistasis_loci -> (stat fp64 (L, k), mom int64 (L, k, 5) or None): the F(1, n - 4) of the interaction of every marker i with
+    the k <= 64 markers loci (0-based, repeats allowed) for the integer trait y (|y| <= EPI_YMAX; dims = (n, L) of M, n <= EPI_MAX_N), NaN
+    where the pair is undefined, and the five pair sums (d, e, f, h, z).  r_api.epistasis_host is the numpy restatement."""
+    L = _lib.load()
+    n, nm = max(int(dims[0]), 0), max(int(dims[1]), 0)
+    yv = _epi_trait("epistasis_loci", y, n)
+    lv = np.ascontiguousarray(np.atleast_1d(np.asarray(loci, dtype=np.int64)).ravel(), dtype=np.int64)
+    if lv.size and not np.all(np.asarray(loci).ravel() == lv):
+        raise ValueError("epistasis_loci: loci must hold whole numbers")
+    k = max(int(lv.size), 1)
+    stat = np.zeros((nm, k), dtype=np.float64)
+    mom = np.zeros((nm, k, 5), dtype=np.int64) if moments else None
+    _args_first(L.eagle_epistasis_loci, device, (os.fsencode(f_name_ascii_Mt), _dims(dims), yv.ctypes.data_as(_c_i32p), lv.ctypes.data_as(c_lp),
+                                                 lv.size, float(max_memory_in_Gbytes), stat.ctypes.data_as(c_dp),
+                                                 mom.ctypes.data_as(_c_i64p) if moments else None))
+    return stat, mom
+
+
+def epistasis_pairs(f_name_ascii_Mt, dims, y, chrom=None, gap=0, min_stat=0.0, hit_cap=1 << 20, max_memory_in_Gbytes=8.0, device=0):
+    """eagle_epistasis_pairs -> {"nhits", "ntested", "max": (i, j, stat), "hit_ij" int32 (nhits, 2), "hit_stat" fp64 (nhits), "hit_mom"
+    int64 (nhits, 5)}: all pairs i < j of the resident panel except those at most `gap` markers apart on one chromosome (chrom: one whole
+    number per marker, or None = one chromosome), a hit where stat >= min_stat, the tables sorted by (i, j).  With more than hit_cap hits the
+    three tables are None and nhits still holds the total (one call, eagle_roh's capacity rule)."""
+    L = _lib.load()
+    n, nm = max(int(dims[0]), 0), max(int(dims[1]), 0)
+    yv = _epi_trait("epistasis_pairs", y, n)
+    ch = None
+    if chrom is not None:
+        ca = np.asarray(chrom).ravel()
+        if ca.size != nm or not np.all(ca == np.rint(ca.astype(np.float64))):
+            raise ValueError("epistasis_pairs: chrom must hold one whole number per marker")
+        ch = np.ascontiguousarray(ca, dtype=np.int32)
+    cap = int(hit_cap)
+    if cap < 0 or int(gap) != gap or gap < 0 or min_stat != min_stat:
+        raise ValueError("epistasis_pairs: hit_cap and gap must not be negative, min_stat not NaN")
+    ij, st, mom = np.zeros((cap, 2), dtype=np.int32), np.zeros(cap, dtype=np.float64), np.zeros((cap, 5), dtype=np.int64)
+    nh, nt, mx = C.c_long(0), C.c_long(0), EpiMax(-1, -1, float("nan"))
+    _args_first(L.eagle_epistasis_pairs, device, (os.fsencode(f_name_ascii_Mt), _dims(dims), yv.ctypes.data_as(_c_i32p),
+                                                  ch.ctypes.data_as(_c_i32p) if ch is not None else None, int(gap), float(min_stat),
+                                                  float(max_memory_in_Gbytes), ij.ctypes.data_as(_c_i32p) if cap else None,
+                                                  st.ctypes.data_as(c_dp) if cap else None, mom.ctypes.data_as(_c_i64p) if cap else None, cap,
+                                                  C.byref(nh), C.byref(nt), C.addressof(mx)))
+    out = {"nhits": int(nh.value), "ntested": int(nt.value), "max": (int(mx.i), int(mx.j), float(mx.stat)), "hit_ij": None, "hit_stat": None,
+           "hit_mom": None}
+    if out["nhits"] <= cap:
+        out.update(hit_ij=ij[:out["nhits"]].copy(), hit_stat=st[:out["nhits"]].copy(), hit_mom=mom[:out["nhits"]].copy())
+    return out
+
+
 # ---- SURVEY 8 f-4: the dense model algebra on the device, through the C ABI (opt-in; include/eagle_hip.h section 1c) ----
 def _square_any_order(A):
     """(buffer, transposed): a float64 n x n array usable as a column-major matrix without a copy when it is contiguous in

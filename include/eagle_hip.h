@@ -925,6 +925,70 @@ int eagle_marker_scores(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long 
                         int64_t* out);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1b''''ii. Epistasis (no counterpart in the reference, whose model is additive): the exact pairwise marker-interaction scan.  For two
+ *     markers i, j and an integer trait y the model is
+ *         y = b0 + b1 g_i + b2 g_j + b3 g_i g_j + e,
+ *     the additive x additive test of PLINK --epistasis for a quantitative trait (GLIDE and epiGPU ran this regression on GPUs), and the
+ *     statistic is the F(1, n - 4) of b3 = 0.  Every sufficient statistic is an exact integer, so the device (k_epi_tile, eagle_epi.hip)
+ *     and the numpy restatement (r_api.epistasis_host) agree bit for bit.
+ *
+ *     1. Inputs.  Genotypes g in {-1, 0, +1} = AA, AB, BB over the n individuals of Mt.ascii (a VIEW alias of eagle_reshape_m: its kept
+ *        individuals); a missing call of the source is a heterozygote by now, as everywhere on the image.  The trait is int32 with
+ *        |y_k| <= EAGLE_EPI_YMAX = 1000000, and n <= EAGLE_EPI_MAX_N = 65535.  (r_api.quantise_trait maps a real trait onto this grid; F
+ *        does not change under a shift or a scale of y.)
+ *     2. Sums, all exact integers.  Per trait: Y = sum y, T = sum y^2.  Per marker: s = sum g, q = sum g^2, u = sum y g.  Per pair:
+ *        d = sum g_i g_j, e = sum g_i^2 g_j, f = sum g_i g_j^2, h = sum g_i^2 g_j^2, z = sum y g_i g_j.  On the device y = d0 + 128 d1 +
+ *        128^2 d2 with balanced digits in [-64, 63] (d_p = ((y_p + 64) & 127) - 64, y_{p+1} = (y_p - d_p) >> 7), so that digit * g
+ *        stays int8, and z = z0 + 128 z1 + 128^2 z2 in int64.
+ *     3. The rule.  B = [[n, s_i, s_j], [s_i, q_i, d], [s_j, d, q_j]], Delta = det B, A = adj B, c = (d, e, f), u = (Y, u_i, u_j), and
+ *            Sxx = Delta h - c^T A c,   Sxy = Delta z - c^T A u,   Syy = Delta T - u^T A u
+ *        in 128-bit integers (no term exceeds 2^110).  Delta Sxx, Delta Sxy, Delta Syy are Delta^2 times the residual sums of squares and
+ *        products of g_i g_j and y after the regression on (1, g_i, g_j).
+ *     4. The pair is UNDEFINED (stat = NaN) unless n > 4, Delta > 0 and Sxx > 0.  That makes i = j, a monomorphic marker, a duplicate
+ *        marker and a product that lies in the span of its factors undefined, with no special case.
+ *     5. Otherwise, with t53(x) = x truncated toward zero to its top 53 bits, as a double, and every fp64 operation one correctly rounded
+ *        operation in this order (nothing contracts into an FMA),
+ *            r2   = (t53(Sxy) / t53(Sxx)) * (t53(Sxy) / t53(Syy))
+ *            stat = ((double)(n - 4) * r2) / (1.0 - r2),          stat = +inf when !(r2 < 1.0).
+ *        A zero Syy (the trait lies in the span of 1, g_i, g_j: nothing is left to explain) has Sxy = 0 too, so r2 = 0 * (0 / 0) = NaN
+ *        and the pair lands in +inf, not in NaN: it is defined, and it is a hit at every min_stat.  A constant trait does this for every
+ *        defined pair; r_api.Epistasis refuses one.
+ *     6. A hit is stat >= min_stat.  NaN is never a hit; min_stat = -inf makes every defined pair a hit.
+ *
+ *     What is not claimed.  Agreement with the PLINK or GLIDE programs is neither claimed nor tested, because neither is available: the
+ *     tests hold the statistic to exact rational arithmetic instead.  Sex chromosomes, dominance terms and case/control traits are out
+ *     of scope.  No p-value is computed here (r_api.Epistasis adds scipy's fdtrc).
+ *
+ *     eagle_epistasis_loci tests every marker against each of 1 <= nloci <= 64 listed loci (repeats allowed); the output is dense:
+ *     stat_out[i * nloci + k] for marker i and locus loci[k], mom_out (or NULL) the five pair sums (d, e, f, h, z) at
+ *     [(i * nloci + k) * 5 ..], with marker i as g_i and the locus as g_j.  The file is read as eagle_ld_dots reads it: the loci's rows
+ *     are gathered first, then the resident image where it lies, else row windows from the sidecar, the text or a VIEW alias's source;
+ *     both give the same bits.
+ *
+ *     eagle_epistasis_pairs tests all pairs i < j except those with j - i <= gap on the same chromosome (chrom NULL: one chromosome;
+ *     gap = 0 skips nothing).  *ntested_out = the defined pairs among those not skipped; *max_out = the largest defined stat and its
+ *     pair, ties to the smallest (i, j), or (-1, -1, NaN) if none is defined.  *nhits_out is always the total number of hits; the
+ *     tables hit_ij (hit_cap x 2), hit_stat (hit_cap), hit_mom (hit_cap x 5: d, e, f, h, z) are written, sorted by (i, j), iff the total
+ *     is <= hit_cap and untouched otherwise.  The call returns EAGLE_OK either way (eagle_roh's seg_cap semantics).  Two deterministic
+ *     passes without global atomics: per tile pair the counts and the maximum, then the tile pairs that have hits once more into their
+ *     slots.  The image must be resident or fit max_memory_in_Gbytes: otherwise EAGLE_ERR_ARG with a message that says to prune or
+ *     filter first -- a streamed all-pairs pass does not exist.
+ *
+ *     Single device: a multi-device context works on its first device.  Argument errors (EAGLE_ERR_ARG: a NULL pointer, dims <= 0,
+ *     n > EAGLE_EPI_MAX_N, |y| > EAGLE_EPI_YMAX, nloci outside [1, 64], a locus outside [0, L), gap < 0, min_stat NaN, hit_cap < 0, NULL
+ *     tables with hit_cap > 0) are decided before the context is used; with ctx == NULL their text is in eagle_open_error().
+ * ------------------------------------------------------------------------------------------- */
+#define EAGLE_EPI_MAX_N 65535L
+#define EAGLE_EPI_YMAX 1000000
+typedef struct eagle_epi_max { int64_t i, j; double stat; } eagle_epi_max;
+
+int eagle_epistasis_loci(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long dims[2], const int32_t* y, const long* loci, long nloci,
+                         double max_memory_in_Gbytes, double* stat_out, int64_t* mom_out);
+int eagle_epistasis_pairs(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long dims[2], const int32_t* y, const int32_t* chrom, long gap,
+                          double min_stat, double max_memory_in_Gbytes, int32_t* hit_ij, double* hit_stat, int64_t* hit_mom, long hit_cap,
+                          long* nhits_out, long* ntested_out, eagle_epi_max* max_out);
+
+/* ---------------------------------------------------------------------------------------------
  * 1c. Dense n x n model algebra on the device (OPT-IN: north_star keeps calculateH / calculateP / emma.* on
  *     host LAPACK, and nothing above calls these).  Once the scan takes tens of milliseconds the ~10-15 O(n^3) base-R calls
  *     of a find_qtl iteration are the whole run time (the author's note MyPackage/MyREADME:1 names eigen(); his MAGMA
