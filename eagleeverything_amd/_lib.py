@@ -149,6 +149,11 @@ SIGNATURES = {
     "eagle_dev_fold_upper": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p]),
     "eagle_dev_scan_operands": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_long,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "eagle_dev_declare_s": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_long]),
+    "eagle_dev_forget_s": (C.c_int, [C.c_void_p]),
+    "eagle_w8_keep_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "eagle_w8_probe_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]),
     "eagle_dev_gemv_i8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_long, C.c_void_p, C.c_double,
                                     C.c_void_p, C.c_void_p]),
     "eagle_dev_vara_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_long, C.c_void_p, C.c_void_p,

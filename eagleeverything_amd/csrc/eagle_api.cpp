@@ -329,9 +329,34 @@ static void drop_workspaces(eagle_ctx* c) {
     arena_collect(c);
     if (c->arena) { (void)hipFree(c->arena); c->arena = nullptr; c->arena_cap = 0; c->arena_off = 0; c->arena_gen++; }
     c->scache.forget_host();
-    if (c->w8_ws) { (void)hipFree(c->w8_ws); c->w8_ws = nullptr; c->w8_ws_cap = 0; }
+    if (c->w8_ws) { (void)hipFree(c->w8_ws); c->w8_ws = nullptr; c->w8_ws_cap = 0; c->w8_ws_gen++; }
+    w8_keep_forget(c->w8_keep);   // (what was kept with S lay in that workspace)
+    c->w8_maxabs_ready = false;
     if (c->w8_true_ws) { (void)hipFree(c->w8_true_ws); c->w8_true_ws = nullptr; c->w8_true_cap = 0; }
     c->w8_active = false;
+}
+// The device-resident caller's promise about S (include/eagle_hip.h).  Every declaration is a new content number: declaring again after
+// rewriting the image in place is how the caller says "S changed".
+extern "C" int eagle_dev_declare_s(eagle_ctx* ctx, const double* Sa, long n, long n_pad) {
+    if (!ctx) return EAGLE_ERR_ARG;
+    if (!Sa || n <= 0 || n > n_pad) return eagle_fail(ctx, EAGLE_ERR_ARG, "declare_s: bad image or sizes");
+    ctx->w8_declared.Sa = Sa; ctx->w8_declared.n = n; ctx->w8_declared.np = n_pad;
+    ctx->w8_declared.s_gen = ctx->w8_s_gen_next++;
+    return EAGLE_OK;
+}
+extern "C" int eagle_dev_forget_s(eagle_ctx* ctx) {
+    if (!ctx) return EAGLE_ERR_ARG;
+    ctx->w8_declared = W8Declared();
+    w8_keep_forget(ctx->w8_keep);
+    return EAGLE_OK;
+}
+extern "C" int eagle_w8_keep_stats(eagle_ctx* ctx, long* hits, long* misses) {
+    if (!ctx) return EAGLE_ERR_ARG;
+    long h = ctx->w8_keep_hits, m = ctx->w8_keep_misses;
+    for (eagle_ctx* p : ctx->peers) { h += p->w8_keep_hits; m += p->w8_keep_misses; }
+    if (hits) *hits = h;
+    if (misses) *misses = m;
+    return EAGLE_OK;
 }
 extern "C" void eagle_drop_cache(eagle_ctx* ctx) {
     if (!ctx) return;
@@ -1104,6 +1129,7 @@ int SCache::acquire(eagle_ctx* ctx, const SCall& call, const SPolicy& pol, const
         int r = upload_square(ctx, S_host, n, np, cached ? d_S : slot_S);
         if (r) return r;
         h_n = 0;
+        s_gen = ctx->w8_s_gen_next++;   // another content where this call's S lies: what the W engine kept with the last one is void
     }
     if (cached) { dev_n = n; *Sa = d_S; }
     if (!plan.refresh_host) return EAGLE_OK;
@@ -1161,6 +1187,7 @@ int SCache::settle(eagle_ctx* ctx, int rc, SOutcome* out) {
         if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return eagle_fail_hip(ctx, e, "scan on a stale S");
         if (o == S_OTHER_ON_DEVICE) std::swap(d_S, d_scr);
         else dev_n = 0;
+        s_gen = ctx->w8_s_gen_next++;
         h_n = 0;
         misses++;
     }
@@ -1364,7 +1391,9 @@ static int scan_once(eagle_ctx* ctx, const char* f_name_ascii, long L, long n, l
                 // call's): V goes up in blocks of 1,536 rows through the pinned staging buffers (16 host threads), and each block's
                 // statistics, digit slices and columns of the first product run on the compute stream as soon as its rows have landed;
                 // the finish step keeps that product only if the rule, on the statistics of ALL of V, chooses the guessed configuration.
-                int r8 = eagle_w8_begin(ctx, Sa, Va, ah, n, np, v, Wu, tmp, 1, ctx->stream);
+                // (the cache's verdict on S goes with it: the same verified content as the last call's -- no upload, no refresh -- lets the
+                // engine keep what it made from S alone; EAGLE_HIP_NO_SCACHE: nobody vouches for S)
+                int r8 = eagle_w8_begin(ctx, Sa, Va, ah, n, np, v, Wu, tmp, 1, pol.no_scache ? 0 : sc.s_gen, ctx->stream);
                 if (r8 < 0) rc = r8;
                 if (!rc) {
                     const long vb = eagle_w8_vrows_block();

@@ -56,6 +56,7 @@ struct SCache {
     SSlot slot;                                       // above max_np: where the last scan left S in the arena
     int* h_flag = nullptr;                            // 64 pinned bytes: where the device comparison's flag lands
     long hits = 0, misses = 0;                        // (eagle_scan_operand_cache_stats)
+    unsigned long s_gen = 0;                          // the number of the content where a call's S lies (eagle_ctx::w8_s_gen_next; w8_keep_valid)
     // this call
     SPlan plan;
     std::thread helper; int helper_rc = 0;            // issues a deferred device comparison, or runs the host comparison / the refresh of the host copy
@@ -135,6 +136,13 @@ struct eagle_ctx {
     W8Info w8_info;
     void* w8_pipe = nullptr;            // W8Pipe* (eagle_w8.hip): the state between eagle_w8_begin / _vrows / _finish
     int w8_guess_c1 = -1; long w8_guess_np = 0;   // the first product's configuration of the last call: what a pipelined call starts on
+    // what is kept with S between calls (w8_keep_valid, eagle_host.h): the record, the workspace's generation, the caller's declaration
+    // (eagle_dev_declare_s), the counter new S contents take their number from, and how often a call reused / recomputed the S products
+    W8Keep w8_keep; unsigned long w8_ws_gen = 0; W8Declared w8_declared; unsigned long w8_s_gen_next = 1;
+    long w8_keep_hits = 0, w8_keep_misses = 0;
+    size_t attr_w8_rowpass = 0;     // dynamic LDS k_w8_rowpass has been allowed on this device
+    bool w8_maxabs_ready = false;   // the w8 workspace holds max |off-diagonal| of the Wu eagle_w8_finish just made (k_w8_combine2)
+    const unsigned long long* w8_maxabs = nullptr;
     char arch[64] = {0};
     int cu_count = 0;
     int64_t hbm_bytes = 0;

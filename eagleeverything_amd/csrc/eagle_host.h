@@ -203,6 +203,24 @@ static inline bool s_slot_valid(const SSlot& s, unsigned long gen, size_t off, l
     return s.n > 0 && s.gen == gen && s.off == off && s.n == n && s.np == np;
 }
 
+// What the int8 W engine keeps WITH S (eagle_w8.hip): the digit image of S, its row statistics and W8Stats, S 1 and S^T 1 -- everything
+// eagle_w8_begin computes from S alone.  The record says which S they were made from and where they lie; a call may skip the S work only
+// if w8_keep_valid says so.  s_gen names the CONTENT of the image at Sa: the owner of S (the SCache of the reference-shaped call,
+// eagle_dev_declare_s of the device-resident one) gives every new content a new non-zero number, and 0 = "nobody vouches for it":
+// never valid, nothing recorded.  ws_gen counts every allocation or release of the w8 workspace (a freed block's address may come back).
+struct W8Keep { const void* Sa = nullptr; long n = 0, np = 0; const void* ws = nullptr; unsigned long ws_gen = 0, s_gen = 0; const void* stream = nullptr; };
+static inline bool w8_keep_valid(const W8Keep& k, const void* Sa, long n, long np, const void* ws, unsigned long ws_gen, unsigned long s_gen,
+                                 const void* stream) {
+    return s_gen != 0 && k.s_gen == s_gen && k.Sa != nullptr && k.Sa == Sa && k.n == n && k.np == np && k.ws != nullptr && k.ws == ws &&
+           k.ws_gen == ws_gen && k.stream == stream;
+}
+static inline void w8_keep_forget(W8Keep& k) { k = W8Keep(); }   // (workspace gone, S forgotten, the engine declined)
+// eagle_dev_declare_s: the caller's promise that the image at Sa is S and stays as it is.  It vouches for exactly that (pointer, n, n_pad).
+struct W8Declared { const void* Sa = nullptr; long n = 0, np = 0; unsigned long s_gen = 0; };
+static inline unsigned long w8_declared_gen(const W8Declared& d, const void* Sa, long n, long np) {
+    return (d.s_gen != 0 && d.Sa == Sa && d.n == n && d.np == np) ? d.s_gen : 0;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Text side of the ingestion (eagle_ingest.cpp): line index of a memory-mapped file and the whitespace tokeniser.
 // ------------------------------------------------------------------------------------------------

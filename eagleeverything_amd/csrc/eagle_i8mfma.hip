@@ -238,28 +238,8 @@ __global__ __launch_bounds__(256) void k_vara_prep(const double* __restrict__ Wu
 // off (eagle_api.cpp).  Deterministic, a function of W alone: every device and every marker block of a scan decides the same.
 // Not used with a forced digit count, with stochastic rounding, or under tune 29 (A/B switch).
 // ------------------------------------------------------------------------------------------------
-// Ds[i][j] = last digit of Wu[min(i,j)][max(i,j)], 0 on the diagonal: symmetric int8 image, n_pad x n_pad (same llrint as k_slice_w)
-__global__ __launch_bounds__(256) void k_last_digit_sym(const double* __restrict__ Wu, long np, const VaraHdr* __restrict__ hdr, int8_t* __restrict__ Ds,
-                                                        int smax) {
-    __shared__ double tile[32][33];
-    if (hdr->S_sliced >= smax) return;   // every slot of the slice area holds a digit in use: no spare one for this image (S = 7: never taken down)
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    const long bx = blockIdx.x, by = blockIdx.y;
-    const long lo = bx < by ? bx : by, hi = bx < by ? by : bx;
-    for (int r = ty; r < 32; r += 8) tile[r][tx] = Wu[(lo * 32 + r) * np + hi * 32 + tx];  // tile[a][b] = Wu[32 lo + a][32 hi + b]
-    __syncthreads();
-    const int e = hdr->e;
-    const int S = hdr->S_sliced;
-    for (int r = ty; r < 32; r += 8) {
-        double v;   // element (i = 32 by + r, j = 32 bx + tx)
-        if (by < bx) v = tile[r][tx];
-        else if (by > bx) v = tile[tx][r];
-        else v = r < tx ? tile[r][tx] : (r > tx ? tile[tx][r] : 0.0);
-        const long long Q = llrint(ldexp(v, 8 * S - (e + 2)));
-        Ds[(by * 32 + r) * np + bx * 32 + tx] = (int8_t)(((Q + 128) & 255) - 128);
-    }
-}
-
+// Ds[i][j] = last digit of Wu[min(i,j)][max(i,j)], 0 on the diagonal: the symmetric int8 image, n_pad x n_pad, is written by k_slice_w
+// below from the tiles it reads anyway (the same llrint, the same digit).
 // rs[i] += sum_j |(D D^T)_ij| over the upper-triangular 256-tile pairs of the symmetric product (both the row sums of a tile and, off
 // the diagonal, its column sums = the row sums of the mirrored tile).  Whole K per workgroup: |.| does not commute with a K split.
 __global__ __launch_bounds__(512, 2) void k_gram_rowabs_i8(const int8_t* __restrict__ D, long ld, const int* __restrict__ pairs, int npairs,
@@ -456,8 +436,11 @@ __global__ __launch_bounds__(256) void k_spectral_decide(const unsigned long lon
 // tiles hold the W columns in the register dimension: lane half h, column tile n, register x is row n * 32 + 8 (x >> 2) + (x & 3) + 4 h
 // of the wave's 128; storing column c = 64 h + 16 n + x there makes the 64 columns of a lane CONSECUTIVE, and the tile epilogue
 // fetches their genotype bytes with four 16-byte loads from the lane's own marker row.
+// Ds (optional; round to nearest only): the symmetric image of the LAST digit for the spectral bound, Ds[i][j] = last digit of
+// Wu[min(i,j)][max(i,j)], 0 on the diagonal -- written from the upper tiles (bj <= bk), each of which holds both mirrored blocks of it,
+// unless every slot of the slice area holds a digit in use (S = smax: no spare one, the spectral bound is not tried).
 __global__ __launch_bounds__(256) void k_slice_w(const double* __restrict__ Wu, long np, const VaraHdr* __restrict__ hdr,
-                                                 int8_t* __restrict__ Bs, int perm128) {
+                                                 int8_t* __restrict__ Bs, int perm128, int8_t* __restrict__ Ds, int smax) {
     __shared__ double tile[32][33];
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     const long bj = (long)blockIdx.y * 32, bk = (long)blockIdx.x * 32;
@@ -465,6 +448,20 @@ __global__ __launch_bounds__(256) void k_slice_w(const double* __restrict__ Wu, 
     __syncthreads();
     const int e = hdr->e;   // w_scale_exp: mx < 2^e, or mx < 1.96 * 2^e when the mantissa leaves room
     const int nslices = hdr->S;
+    if (Ds && bj <= bk && hdr->S_sliced < smax) {
+        const int Sd = hdr->S_sliced;
+        for (int r = ty; r < 32; r += 8) {
+            // rows bj + r: element (bj + r, bk + tx) itself; rows bk + r (the mirrored block): element (bk + r, bj + tx) = Wu[bj + tx][bk + r]
+            double up = tile[r][tx], lo = tile[tx][r];
+            if (bj == bk) { up = r < tx ? tile[r][tx] : (r > tx ? tile[tx][r] : 0.0); lo = up; }
+            const long long Qu = llrint(ldexp(up, 8 * Sd - (e + 2)));
+            Ds[(bj + r) * np + bk + tx] = (int8_t)(((Qu + 128) & 255) - 128);
+            if (bj != bk) {
+                const long long Ql = llrint(ldexp(lo, 8 * Sd - (e + 2)));
+                Ds[(bk + r) * np + bj + tx] = (int8_t)(((Ql + 128) & 255) - 128);
+            }
+        }
+    }
     for (int r = ty; r < 32; r += 8) {
         // output element (k = bk + r, j = bj + tx):  Q = round(Wu * 2^(8S - e - 2)) is an exact integer below 0.49 * 256^S + 1
         // (llrint of a double of that size is exact); its balanced base-256 digits, least significant first,
@@ -1638,10 +1635,15 @@ extern "C" int eagle_dev_vara_i8_prepare_part(eagle_ctx* ctx, const int8_t* Mt8,
         if (e != hipSuccess) return eagle_fail_hip(ctx, e, "vara_i8 extension memset");
     }
     if (part != 2) {
-        hipLaunchKernelGGL(k_absmax_offdiag, dim3(1024), dim3(256), 0, s, Wu, n_pad, (unsigned long long*)&hdr->maxabs_off);
         // W from the int8 engine (eagle_w8.hip, the image it left is the one being prepared): its error bound rides in the header, and
         // the correction vector of the re-centred markers comes from r = S (V (S 1)) instead of the row sums of this image
         const bool w8 = ctx->w8_active && ctx->w8_Wu == Wu;
+        // ... and the kernel that wrote it took max |off-diagonal| on the way (k_w8_combine2: the same atomic max of the same values)
+        if (w8 && ctx->w8_maxabs_ready) {
+            e = hipMemcpyAsync(&hdr->maxabs_off, ctx->w8_maxabs, sizeof(unsigned long long), hipMemcpyDeviceToDevice, s);
+            if (e != hipSuccess) return eagle_fail_hip(ctx, e, "vara_i8 maxabs copy");
+        } else
+            hipLaunchKernelGGL(k_absmax_offdiag, dim3(1024), dim3(256), 0, s, Wu, n_pad, (unsigned long long*)&hdr->maxabs_off);
         hipLaunchKernelGGL(k_vara_prep, dim3(1), dim3(256), 0, s, Wu, n_pad, nslices, hdr, dW, ctx->scan_budget, w8 ? ctx->w8_eta : 0.0, ctx->scan_budget_tight);
         // correction terms of the re-centred markers: rho and R from Wu, m^T rho from the genotype pass
         double* colpart = (double*)((char*)ws + ws_cp_off(n_pad, L_pad, smax));
@@ -1663,11 +1665,13 @@ extern "C" int eagle_dev_vara_i8_prepare_part(eagle_ctx* ctx, const int8_t* Mt8,
     }
     if (part != 2) {
         dim3 g2((unsigned)(n_pad / 32), (unsigned)(n_pad / 32));
-        hipLaunchKernelGGL(k_slice_w, g2, dim3(256), 0, s, Wu, n_pad, hdr, Bs, vara_piped(ctx, n_pad) ? 1 : 0);
+        const bool spectral = nslices == 0 && !ctx->spectral_off && ctx->tune != 29;
+        hipLaunchKernelGGL(k_slice_w, g2, dim3(256), 0, s, Wu, n_pad, hdr, Bs, vara_piped(ctx, n_pad) ? 1 : 0,
+                           spectral ? Bs + (size_t)(smax - 1) * n_pad * n_pad : (int8_t*)nullptr, smax);
         // one digit fewer if the spectral bound of the last digit allows it (automatic digit count, round to nearest): the last digit's
         // symmetric image goes into the spare slot of the slice area (at most 6 of the 7 are in use), the row sums into the column
         // partials of rho (free again after k_rho_final)
-        if (nslices == 0 && !ctx->spectral_off && ctx->tune != 29) {
+        if (spectral) {
             int8_t* Ds = Bs + (size_t)(smax - 1) * n_pad * n_pad;
             unsigned long long* rsum = (unsigned long long*)((char*)ws + ws_cp_off(n_pad, L_pad, smax));
             const int* pairs = nullptr;
@@ -1675,7 +1679,6 @@ extern "C" int eagle_dev_vara_i8_prepare_part(eagle_ctx* ctx, const int8_t* Mt8,
             rc = syrk_pair_table(ctx, nt, &pairs, s);
             if (rc) return rc;
             const int npairs = nt * (nt + 1) / 2;
-            hipLaunchKernelGGL(k_last_digit_sym, g2, dim3(256), 0, s, Wu, n_pad, hdr, Ds, smax);
             e = hipMemsetAsync(rsum, 0, sizeof(unsigned long long) * (size_t)n_pad, s);
             if (e != hipSuccess) return eagle_fail_hip(ctx, e, "spectral row sums memset");
             hipLaunchKernelGGL(k_gram_rowabs_i8, dim3((unsigned)((npairs + 7) / 8 * 8)), dim3(512), 0, s, Ds, n_pad, pairs, npairs, n_pad / BK8, rsum,

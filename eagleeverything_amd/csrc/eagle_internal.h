@@ -25,7 +25,7 @@ int eagle_dev_scan_operands_w8(eagle_ctx* ctx, const double* Sa, const double* V
 int eagle_dev_colgemv_parts(eagle_ctx* ctx, const double* At, long n, long n_pad, const double* x, double* out, double* part, void* stream);
 // the same in three steps (eagle_w8.hip): V may arrive in row blocks of eagle_w8_vrows_block() rows under the first product
 int eagle_w8_begin(eagle_ctx* ctx, const double* Sa, const double* Va, const double* ahat, long n, long n_pad, double* v_out, double* Wu_out, double* tmp,
-                   int allow_guess, void* stream);
+                   int allow_guess, unsigned long s_gen, void* stream);
 int eagle_w8_vrows(eagle_ctx* ctx, long r0, long r1, void* stream);
 int eagle_w8_finish(eagle_ctx* ctx, void* stream);
 int eagle_w8_vrows_block(void);

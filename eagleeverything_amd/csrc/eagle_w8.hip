@@ -154,6 +154,106 @@ __global__ __launch_bounds__(256) void k_w8_slice(const double* __restrict__ M, 
     if (threadIdx.x == 0) eout[i] = e;
 }
 
+// k_w8_rowstats + k_w8_slice in ONE pass over a row that fits LDS (n_pad * 9 bytes + 6 KiB of reduction scratch <= 160 KiB: n_pad <= 16,384).  k_w8_slice walks 16
+// consecutive doubles per thread -- a wave load touches 64 different 128-byte lines -- and it is the row's second trip from memory; here
+// the row comes in once with coalesced 16-byte loads, the statistics are taken from LDS with k_w8_rowstats's thread-to-element map and
+// reduction tree (ssq is an fp64 sum: its order is part of the result), and the digits and their integer sums follow from LDS, stored as
+// before in 16-byte pieces per plane.  LDS image: 16 doubles, 2 of padding (a thread's 16-byte reads then start 144 bytes apart).
+// Measured (profiles/r18_w_prepare.json): the slicer is bound by the VALU work of the digit peel, not by its loads -- a 256-thread block
+// with the 64-bit peel (one wave per SIMD beside the 92 KB row) ran 973 us against 667 for the two kernels at n_pad = 10,240; 1,024 threads
+// and the peel in 32-bit arithmetic: 571 us.
+#define W8_LIDX(l) ((l) + (((l) >> 4) << 1))
+#define W8_ROWPASS_T 1024
+typedef double w8_f64x2 __attribute__((ext_vector_type(2)));
+__global__ __launch_bounds__(W8_ROWPASS_T) void k_w8_rowpass(const double* __restrict__ M, long np, double* __restrict__ d, double* __restrict__ mx,
+                                                             double* __restrict__ ssq, int* __restrict__ bad, int8_t* __restrict__ D, long sstride,
+                                                             unsigned long long* __restrict__ dssq, int* __restrict__ eout, long row0) {
+    extern __shared__ __attribute__((aligned(16))) double w8_rowl[];   // [np / 16][18]
+    __shared__ double rm[256], rs[256];
+    __shared__ int rb[256];
+    __shared__ unsigned wsq[W8_KMAX][W8_ROWPASS_T / 64];
+    const int t = threadIdx.x;
+    const long i = row0 + blockIdx.x;
+    const double* row = M + i * np;
+    for (long l0 = (long)t * 2; l0 < np; l0 += 2 * W8_ROWPASS_T) *(w8_f64x2*)(w8_rowl + W8_LIDX(l0)) = *(const w8_f64x2*)(row + l0);
+    __syncthreads();
+    // the statistics: the first 256 threads, k_w8_rowstats's map and tree
+    if (t < 256) {
+        double m = 0.0, s = 0.0;
+        int nf = 0;
+        for (long l = t; l < np; l += 256) {
+            const double v = w8_rowl[W8_LIDX(l)];
+            if (!isfinite(v)) nf = 1;
+            if (l != i) {
+                const double a = fabs(v);
+                m = a > m ? a : m;
+                s += v * v;
+            }
+        }
+        rm[t] = m; rs[t] = s; rb[t] = nf;
+    }
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (t < o) {
+            rm[t] = rm[t + o] > rm[t] ? rm[t + o] : rm[t];
+            rs[t] += rs[t + o];
+            rb[t] |= rb[t + o];
+        }
+        __syncthreads();
+    }
+    const double mxi = rm[0];
+    if (t == 0) {
+        d[i] = w8_rowl[W8_LIDX(i)];
+        mx[i] = mxi;
+        ssq[i] = rs[0];
+        if (rb[0]) *bad = 1;
+    }
+    // The digits, 16 consecutive elements per thread.  |Q| < 2^47 (|M| <= mx < 1.96 2^e): the balanced digits of k_w8_slice's 64-bit peel
+    // are those of the low 24 bits, then of the high part plus the carry, in 32-bit arithmetic; their squares summed in 32 bits per
+    // thread and wave (at most 64 x 16 x 2^14 per wave and chunk).
+    const int e = w_scale_exp(mxi);
+    const int sh = 8 * W8_KMAX - e - 2;
+    unsigned sq[W8_KMAX];
+#pragma unroll
+    for (int p = 0; p < W8_KMAX; p++) sq[p] = 0;
+    for (long l0 = (long)t * 16; l0 < np; l0 += (long)W8_ROWPASS_T * 16) {
+        union { i32x4 v; int8_t b[16]; } dg[W8_KMAX];
+        const double* src = w8_rowl + W8_LIDX(l0);
+#pragma unroll
+        for (int u = 0; u < 16; u++) {
+            const long l = l0 + u;
+            long long Q = 0;
+            if (l != i && mxi > 0.0) Q = llrint(ldexp(src[u], sh));
+            int c = (int)((unsigned)Q & 0xffffffu);
+            const int hi = (int)(Q >> 24);
+#pragma unroll
+            for (int p = W8_KMAX - 1; p >= 0; p--) {
+                if (p == W8_KMAX - 4) c += hi;   // (the carry out of the low 24 bits is what is left in c)
+                const int dd = ((c + 128) & 255) - 128;
+                c = (c - dd) >> 8;
+                dg[p].b[u] = (int8_t)dd;
+                sq[p] += (unsigned)(dd * dd);
+            }
+        }
+#pragma unroll
+        for (int p = 0; p < W8_KMAX; p++) *(i32x4*)(D + (long)p * sstride + i * np + l0) = dg[p].v;
+    }
+#pragma unroll
+    for (int p = 0; p < W8_KMAX; p++) {
+        unsigned v = sq[p];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+        if ((t & 63) == 0) wsq[p][t >> 6] = v;
+    }
+    __syncthreads();
+    if (t < W8_KMAX) {
+        unsigned long long tot = 0;
+        for (int w = 0; w < W8_ROWPASS_T / 64; w++) tot += wsq[t][w];
+        dssq[(long)t * np + i] = tot;
+    }
+    if (t == 0) eout[i] = e;
+}
+
 // One block: the numbers the host's configuration choice needs (fixed summation order).  d2: optional second diagonal for the
 // estimate sum_i d2_i^2 |d_i| of sum_k |W_kk|.
 __global__ __launch_bounds__(1024) void k_w8_reduce(long np, const double* __restrict__ d, const double* __restrict__ mx, const double* __restrict__ ssq,
@@ -413,7 +513,7 @@ __global__ __launch_bounds__(256) void k_w8_combine1(const double* __restrict__ 
 __global__ __launch_bounds__(256) void k_w8_combine2(const double* Sa, const double* __restrict__ X, long np, const double* __restrict__ dS,
                                                      const double* __restrict__ dX, const int* __restrict__ eS, const int* __restrict__ eX,
                                                      const int32_t* __restrict__ L, long img_elems, const W8Group* __restrict__ groups, int ngroups,
-                                                     long row0, double* Wu) {
+                                                     long row0, double* Wu, unsigned long long* __restrict__ maxbits) {
     const long bi = (long)blockIdx.y + row0 / 32, bj = blockIdx.x;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     if (bj < bi) {
@@ -423,6 +523,7 @@ __global__ __launch_bounds__(256) void k_w8_combine2(const double* Sa, const dou
     __shared__ double xt[32][33];   // xt[a][b] = X[32 bj + a][32 bi + b]
     for (int r = ty; r < 32; r += 8) xt[r][tx] = X[(bj * 32 + r) * np + bi * 32 + tx];
     __syncthreads();
+    double m = 0.0;   // max |off-diagonal| of this block's part of Wu, as k_absmax_offdiag takes it from the finished image (NaN never wins)
     for (int r = ty; r < 32; r += 8) {
         const long i = bi * 32 + r, j = bj * 32 + tx;
         double v = 0.0;
@@ -432,6 +533,16 @@ __global__ __launch_bounds__(256) void k_w8_combine2(const double* Sa, const dou
             else v = 2.0 * ((dS[i] * xt[tx][r] + Sa[i * np + j] * dX[j]) + g);
         }
         Wu[i * np + j] = v;
+        const double a = i == j ? 0.0 : fabs(v);
+        m = a > m ? a : m;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const double y = __shfl_down(m, o); m = y > m ? y : m; }
+    // (one address for 4 (n_pad / 32)^2 / 2 waves: a wave looks first and only a larger value goes to the atomic -- a stale look costs an
+    // atomic that changes nothing, never the maximum)
+    if ((threadIdx.x & 63) == 0 && m > 0.0) {
+        const unsigned long long mb = (unsigned long long)__double_as_longlong(m);
+        if (mb > __hip_atomic_load(maxbits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(maxbits, mb);
     }
 }
 
@@ -788,6 +899,8 @@ struct W8Ws {
     int8_t *sA, *sB;
     int32_t* levels; size_t level_bytes;
     double *dS, *mxS, *ssqS, *dV, *mxV, *ssqV, *dX, *mxX, *ssqX, *r, *r1, *r2, *sumdiag, *gvpart;
+    double *s1r, *s1c;            // S 1 (row-type product of the image) and S^T 1: kept with S
+    unsigned long long* maxabs;   // bit pattern of max |off-diagonal| of the Wu k_w8_combine2 wrote
     int *eS, *eV, *eX, *bad;
     unsigned long long *dssqS, *dssqV, *dssqX;
     double* asympart;
@@ -806,9 +919,11 @@ static int w8_workspace(eagle_ctx* ctx, long np, W8Ws* w) {
     const size_t level_bytes = full_levels < cap ? full_levels : cap;
     const size_t vec = r256(sizeof(double) * (size_t)np), dss = r256(sizeof(unsigned long long) * W8_KMAX * (size_t)np);
     const size_t asymb = r256(sizeof(double) * (size_t)(np / 32) * (size_t)(np / 32));
-    const size_t need = 2 * r256(W8_KMAX * nn) + r256(level_bytes) + 13 * vec + 8 * vec + 4 * vec + 3 * dss + asymb + 4096;
+    const size_t need = 2 * r256(W8_KMAX * nn) + r256(level_bytes) + 15 * vec + 8 * vec + 4 * vec + 3 * dss + asymb + 4096 + 256;
     if (need > ctx->w8_ws_cap || (getenv("EAGLE_HIP_W8_LEVEL_MB") && need != ctx->w8_ws_cap)) {
         if (ctx->w8_ws) { (void)hipDeviceSynchronize(); (void)hipFree(ctx->w8_ws); ctx->w8_ws = nullptr; ctx->w8_ws_cap = 0; }
+        ctx->w8_ws_gen++;   // what was kept with S lay in the old block (w8_keep_valid)
+        w8_keep_forget(ctx->w8_keep);
         if (hipMalloc(&ctx->w8_ws, need) != hipSuccess) {
             (void)hipGetLastError();
             ctx->w8_ws = nullptr;
@@ -822,7 +937,7 @@ static int w8_workspace(eagle_ctx* ctx, long np, W8Ws* w) {
     w->sB = (int8_t*)take(W8_KMAX * nn);
     w->levels = (int32_t*)take(level_bytes);
     w->level_bytes = level_bytes;
-    double** dv[] = {&w->dS, &w->mxS, &w->ssqS, &w->dV, &w->mxV, &w->ssqV, &w->dX, &w->mxX, &w->ssqX, &w->r, &w->r1, &w->r2, &w->sumdiag};
+    double** dv[] = {&w->dS, &w->mxS, &w->ssqS, &w->dV, &w->mxV, &w->ssqV, &w->dX, &w->mxX, &w->ssqX, &w->r, &w->r1, &w->r2, &w->sumdiag, &w->s1r, &w->s1c};
     for (double** x : dv) *x = (double*)take(vec);
     w->gvpart = (double*)take(8 * vec);
     int** iv[] = {&w->eS, &w->eV, &w->eX, &w->bad};
@@ -831,14 +946,26 @@ static int w8_workspace(eagle_ctx* ctx, long np, W8Ws* w) {
     for (unsigned long long** x : uv) *x = (unsigned long long*)take(dss);
     w->asympart = (double*)take(asymb);
     w->stats = (W8Stats*)take(3 * sizeof(W8Stats));
+    w->maxabs = (unsigned long long*)take(256);
     return 0;
 }
 
 // row statistics + digit slices of the rows [r0, r1) of one operand
 static int w8_rows_of(eagle_ctx* ctx, const double* M, long np, long r0, long r1, double* d, double* mx, double* ssq, int* e, unsigned long long* dssq,
                       int8_t* slices, W8Ws& w, hipStream_t s) {
+    // one pass while a row fits LDS (tune 32: the two-kernel form at any size, for A/B runs and the test that compares the two)
+    const size_t row_lds = (size_t)W8_LIDX(np) * sizeof(double);
+    if (ctx->tune != 32 && row_lds + 6144 <= (size_t)160 * 1024) {
+        if (row_lds > ctx->attr_w8_rowpass) {
+            hipError_t ea = hipFuncSetAttribute((const void*)k_w8_rowpass, hipFuncAttributeMaxDynamicSharedMemorySize, (int)row_lds);
+            if (ea != hipSuccess) return eagle_fail_hip(ctx, ea, "hipFuncSetAttribute(k_w8_rowpass)");
+            ctx->attr_w8_rowpass = row_lds;
+        }
+        hipLaunchKernelGGL(k_w8_rowpass, dim3((unsigned)(r1 - r0)), dim3(W8_ROWPASS_T), row_lds, s, M, np, d, mx, ssq, w.bad, slices, np * np, dssq, e, r0);
+    } else {
     hipLaunchKernelGGL(k_w8_rowstats, dim3((unsigned)(r1 - r0)), dim3(256), 0, s, M, np, d, mx, ssq, w.bad, r0);
     hipLaunchKernelGGL(k_w8_slice, dim3((unsigned)(r1 - r0)), dim3(256), 0, s, M, np, (const double*)mx, slices, np * np, dssq, e, r0);
+    }
     hipError_t er = hipGetLastError();
     if (er != hipSuccess) return eagle_fail_hip(ctx, er, "w8 row statistics");
     return EAGLE_OK;
@@ -948,14 +1075,16 @@ void eagle_w8_release(eagle_ctx* ctx) {
 static int w8_decline(eagle_ctx* ctx, W8Info& info, int why) {
     info.declined = why;
     ctx->w8_info = info;
+    w8_keep_forget(ctx->w8_keep);   // nothing is kept from a call the engine declined (its S may be the reason)
     w8_pipe(ctx)->open = false;
     return 1;
 }
 extern "C" int eagle_w8_vrows_block(void) { return W8_VBLOCK; }
 
 extern "C" int eagle_w8_begin(eagle_ctx* ctx, const double* Sa, const double* Va, const double* ahat, long n, long np, double* v_out, double* Wu_out,
-                              double* tmp, int allow_guess, void* stream) {
+                              double* tmp, int allow_guess, unsigned long s_gen, void* stream) {
     ctx->w8_active = false;
+    ctx->w8_maxabs_ready = false;
     ctx->w8_eta = 0.0;
     ctx->w8_info = W8Info();
     W8Pipe* P = w8_pipe(ctx);
@@ -966,9 +1095,24 @@ extern "C" int eagle_w8_begin(eagle_ctx* ctx, const double* Sa, const double* Va
     W8Ws& w = P->w;
     int rc = eagle_dev_scan_operands_begin(ctx, Sa, ahat, n, np, v_out, tmp, stream);
     if (rc) return rc;
-    // statistics + digit slices of the off-diagonal part F of S (V's follow row block by row block: eagle_w8_vrows)
-    rc = w8_stats_of(ctx, Sa, np, w.dS, w.mxS, w.ssqS, w.eS, w.dssqS, w.sA, nullptr, true, w, w.stats + 0, s);
-    if (rc) return rc;
+    // Everything that depends on S alone -- statistics + digit slices of its off-diagonal part F, S 1 and S^T 1 for the r-vector of
+    // eagle_w8_finish -- is kept with S: a call on the same S (s_gen: its owner's number for this content, 0 = nobody vouches) in the
+    // same workspace finds it all in place.  (V's follow row block by row block: eagle_w8_vrows)
+    if (w8_keep_valid(ctx->w8_keep, Sa, n, np, ctx->w8_ws, ctx->w8_ws_gen, s_gen, stream)) ctx->w8_keep_hits++;
+    else {
+        w8_keep_forget(ctx->w8_keep);
+        ctx->w8_keep_misses++;
+        rc = w8_stats_of(ctx, Sa, np, w.dS, w.mxS, w.ssqS, w.eS, w.dssqS, w.sA, nullptr, true, w, w.stats + 0, s);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_w8_fill_ones, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s, w.r2, n, np);
+        rc = eagle_dev_colgemv_parts(ctx, Sa, n, np, w.r2, w.s1c, w.gvpart, stream);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_w8_rowgemv, dim3((unsigned)(np / 4)), dim3(256), 0, s, Sa, n, np, (const double*)w.r2, w.s1r);
+        if (s_gen) {
+            W8Keep& k = ctx->w8_keep;
+            k.Sa = Sa; k.n = n; k.np = np; k.ws = ctx->w8_ws; k.ws_gen = ctx->w8_ws_gen; k.s_gen = s_gen; k.stream = stream;
+        }
+    }
     hipError_t er = hipMemsetAsync(w.bad, 0, sizeof(int), s);   // (S's flag is in its statistics already; V's rows raise it again)
     if (er != hipSuccess) return eagle_fail_hip(ctx, er, "w8 memset");
     P->open = true;
@@ -1022,13 +1166,11 @@ extern "C" int eagle_w8_finish(eagle_ctx* ctx, void* stream) {
     int rc = w8_reduce_of(ctx, Va, np, w.dV, w.mxV, w.ssqV, w.eV, w.dssqV, w.dS, true, w, w.stats + 1, s);
     if (rc) return rc;
     // r = the row sums of sym(S V S) in fp64: the mean of (Sa Va Sa) 1 (row-type products) and (Sa Va Sa)^T 1 (column-type)
-    hipLaunchKernelGGL(k_w8_fill_ones, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s, w.r2, n, np);
-    rc = eagle_dev_colgemv_parts(ctx, Sa, n, np, w.r2, w.r1, w.gvpart, stream);
-    if (!rc) rc = eagle_dev_colgemv_parts(ctx, Va, n, np, w.r1, w.r, w.gvpart, stream);
+    // (the innermost factors S^T 1 and S 1 came with S: eagle_w8_begin)
+    rc = eagle_dev_colgemv_parts(ctx, Va, n, np, w.s1c, w.r, w.gvpart, stream);
     if (!rc) rc = eagle_dev_colgemv_parts(ctx, Sa, n, np, w.r, w.r1, w.gvpart, stream);     // r1 = (Sa Va Sa)^T 1
     if (rc) return rc;
-    hipLaunchKernelGGL(k_w8_rowgemv, dim3((unsigned)(np / 4)), dim3(256), 0, s, Sa, n, np, (const double*)w.r2, w.r);
-    hipLaunchKernelGGL(k_w8_rowgemv, dim3((unsigned)(np / 4)), dim3(256), 0, s, Va, n, np, (const double*)w.r, w.gvpart);
+    hipLaunchKernelGGL(k_w8_rowgemv, dim3((unsigned)(np / 4)), dim3(256), 0, s, Va, n, np, (const double*)w.s1r, w.gvpart);
     hipLaunchKernelGGL(k_w8_rowgemv, dim3((unsigned)(np / 4)), dim3(256), 0, s, Sa, n, np, (const double*)w.gvpart, w.r);   // r = (Sa Va Sa) 1
     hipLaunchKernelGGL(k_w8_mean2, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s, (const double*)w.r, (const double*)w.r1, np, w.r);
     W8Stats st[3];
@@ -1076,10 +1218,12 @@ extern "C" int eagle_w8_finish(eagle_ctx* ctx, void* stream) {
     double b2 = 0.0;
     const int c2 = w8_choose(st[0], st[2], np, (target - used) / M_SQRT2 * 0.98, &b2);
     if (c2 < 0) return w8_decline(ctx, info, 4);
+    hipError_t em = hipMemsetAsync(w.maxabs, 0, sizeof(unsigned long long), s);   // (every panel's k_w8_combine2 adds its part)
+    if (em != hipSuccess) return eagle_fail_hip(ctx, em, "w8 memset");
     rc = w8_product(ctx, c2, true, np, w.sA, w.sB, w, s, [&](const W8List& l, long img, long row0, long rows) {
         hipLaunchKernelGGL(k_w8_combine2, dim3((unsigned)(np / 32), (unsigned)(rows / 32)), dim3(256), 0, s, Sa, (const double*)tmp, np, (const double*)w.dS,
                            (const double*)w.dX, (const int*)w.eS, (const int*)w.eX, (const int32_t*)w.levels, img, (const W8Group*)l.groups, l.ngroups, row0,
-                           Wu_out);
+                           Wu_out, w.maxabs);
     });
     if (rc) { if (rc == 1) return w8_decline(ctx, info, 5); return rc; }
     const double round2 = ldexp(st[0].maxd * fX + fS * st[2].maxd + fS * fX + st[0].maxd * st[2].maxd * sqrt((double)np), -49);
@@ -1103,13 +1247,35 @@ extern "C" int eagle_w8_finish(eagle_ctx* ctx, void* stream) {
     ctx->w8_Va = Va;
     ctx->w8_n = n;
     ctx->w8_tmp = tmp;
+    ctx->w8_maxabs = w.maxabs;
+    ctx->w8_maxabs_ready = true;
     return EAGLE_OK;
 }
 
 extern "C" int eagle_dev_scan_operands_w8(eagle_ctx* ctx, const double* Sa, const double* Va, const double* ahat, long n, long np, double* v_out,
                                           double* Wu_out, double* tmp, void* stream) {
-    int rc = eagle_w8_begin(ctx, Sa, Va, ahat, n, np, v_out, Wu_out, tmp, 0, stream);
+    // S is kept between calls only on the caller's word (eagle_dev_declare_s): the library cannot see an image rewritten in place
+    int rc = eagle_w8_begin(ctx, Sa, Va, ahat, n, np, v_out, Wu_out, tmp, 0, w8_declared_gen(ctx->w8_declared, Sa, n, np), stream);
     if (!rc) rc = eagle_w8_vrows(ctx, 0, np, stream);
     if (!rc) rc = eagle_w8_finish(ctx, stream);
     return rc;
+}
+
+// Test hook (tests/test_gpu_w8_kept_s.py): the row pass exactly as the pipeline runs it, on the caller's device buffers -- the rows of M in
+// the blocks [cuts[k], cuts[k+1]), then the reduction.  vec3 = d | mx | ssq (n_pad each), slices = 6 planes, dssq = 6 x n_pad.
+extern "C" int eagle_w8_probe_rows(eagle_ctx* ctx, const double* M, long np, const long* cuts, int ncuts, int asym, int8_t* slices, double* vec3, int* e,
+                                   unsigned long long* dssq, W8Stats* stats_dev, void* stream) {
+    if (np % T8 || np <= 0 || ncuts < 2 || cuts[0] != 0 || cuts[ncuts - 1] != np) return eagle_fail(ctx, EAGLE_ERR_ARG, "w8_probe_rows: bad blocks");
+    hipStream_t s = (hipStream_t)stream;
+    W8Ws w;
+    if (w8_workspace(ctx, np, &w)) return eagle_fail(ctx, EAGLE_ERR_HIP, "w8_probe_rows: no workspace");
+    w8_keep_forget(ctx->w8_keep);   // (asympart and the flag are shared with what is kept)
+    hipError_t er = hipMemsetAsync(w.bad, 0, sizeof(int), s);
+    if (er != hipSuccess) return eagle_fail_hip(ctx, er, "w8 memset");
+    for (int k = 0; k + 1 < ncuts; k++) {
+        if (cuts[k + 1] <= cuts[k]) return eagle_fail(ctx, EAGLE_ERR_ARG, "w8_probe_rows: bad blocks");
+        int rc = w8_rows_of(ctx, M, np, cuts[k], cuts[k + 1], vec3, vec3 + np, vec3 + 2 * np, e, dssq, slices, w, s);
+        if (rc) return rc;
+    }
+    return w8_reduce_of(ctx, M, np, vec3, vec3 + np, vec3 + 2 * np, e, dssq, nullptr, asym != 0, w, stats_dev, s);
 }

@@ -456,6 +456,16 @@ def scan_operand_cache_stats(device=0):
     return h.value, m.value
 
 
+def w8_keep_stats(device=0):
+    """(hits, misses): calls of the int8 W engine that found what it keeps with S (digit image, row statistics, S 1) in place / had to
+    compute it, summed over the devices of the context (eagle_w8_keep_stats, include/eagle_hip.h)."""
+    L = _lib.load()
+    ctx = context(device)
+    h, m = C.c_long(), C.c_long()
+    _check(ctx, L.eagle_w8_keep_stats(ctx, C.byref(h), C.byref(m)))
+    return h.value, m.value
+
+
 def last_mmt_normalised(n, device=0):
     """calcMMt.R:13 applied on the device to the last calculateMMt result."""
     L = _lib.load()

@@ -151,6 +151,7 @@ class DeviceShard:
         self.nslices = 0  # 0 = chosen by the library from its error bound
         self.stochastic = False  # digits of W rounded at random (eagle_set_scan_rounding): probabilistic certificate, one digit fewer
         self.extend = True       # eagle_dev_vara_i8_extend after the vara kernel (tests switch it off to see the raw values)
+        self.declare_s = True    # set_operands declares its S image to the context (eagle_dev_declare_s): False = nothing kept between calls
         self.w_mode = 1          # eagle_set_w_mode for the digit-slice scan: 1 = W on the int8 engine from 4,096 padded individuals up, 0 = fp64 GEMM, 2 = int8 always
 
     # ---- plumbing -------------------------------------------------------------------------------
@@ -271,7 +272,13 @@ class DeviceShard:
             out = torch.zeros((np_, np_), dtype=torch.float64, device=self.dev)
             out[:n, :n] = Mx.t()
             return out
+        if self.Sa is not None:   # (the old image is freed below: nothing kept with it may outlive it)
+            self._check(self.L.eagle_dev_forget_s(self.ctx))
         self.Sa, self.Va = pad_t(S), pad_t(V)
+        # this image is S and stays as it is until the next set_operands / release_operands: the int8 W engine keeps what it makes from
+        # S alone (digit image, row statistics, S 1) across the scan_operands() calls in between (include/eagle_hip.h)
+        if self.declare_s:
+            self._check(self.L.eagle_dev_declare_s(self.ctx, self.Sa.data_ptr(), n, np_))
         self.ahat = torch.zeros(np_, dtype=torch.float64, device=self.dev)
         self.ahat[:n] = torch.as_tensor(ahat, dtype=torch.float64, device=self.dev).reshape(-1)
         if self.v is None:
@@ -295,6 +302,7 @@ class DeviceShard:
 
     def release_operands(self):
         """Drop the n x n operand images and the vara workspace (a and vara of the last scan stay)."""
+        self._check(self.L.eagle_dev_forget_s(self.ctx))
         self.Sa = self.Va = self.ahat = self.v = self.Wu = self.tmp = self.W0 = self.v0 = None
         self.ws = None
         self.torch.cuda.empty_cache()

@@ -1141,6 +1141,22 @@ int eagle_dev_mmt_normalise(eagle_ctx* ctx, double* MMt, long n, long ld, const 
  * tmp: n_pad*n_pad doubles of scratch. */
 int eagle_dev_scan_operands(eagle_ctx* ctx, const double* Sa, const double* Va, const double* ahat, long n,
                             long n_pad, double* v_out, double* Wu_out, double* tmp, void* stream);
+/* Lifetime: when the int8 engine formed W (eagle_last_w_info: int8 = 1) the context remembers Sa, Va, Wu_out and tmp -- the scan
+ * that follows re-evaluates single markers from m^T (S (V (S m))) and may redo the products in fp64.  All four must stay allocated and
+ * unchanged until that scan has finished (or the next eagle_dev_scan_operands* call on this context).
+ *
+ * Keeping S between calls.  Everything the int8 engine computes from S alone (its digit image and row statistics, S 1 and S^T 1:
+ * one full pass over S and a half, every call) can stay in the context's workspace.  The library cannot see an image rewritten in
+ * place, so this is opt-in: eagle_dev_declare_s(ctx, Sa, n, n_pad) is the caller's promise that the image at Sa IS S and stays
+ * bit for bit as it is until the next eagle_dev_declare_s or eagle_dev_forget_s on this context.  Calls of eagle_dev_scan_operands
+ * with exactly that (Sa, n, n_pad), on one stream, then compute the S part once; every result is bit for bit what an undeclared call
+ * returns.  A new S in the same buffer: write it, then declare again (every declaration is a new S).  Before freeing the buffer:
+ * eagle_dev_forget_s.  Without a declaration nothing is kept.  eagle_drop_cache, a workspace that had to grow, and a call the engine
+ * declined drop what was kept (the declaration stands: the next call computes it anew).  eagle_dev_scan_operands_rows and the fp64
+ * products take no part in this.  eagle_w8_keep_stats: calls that found / had to compute the S part (summed over the devices). */
+int eagle_dev_declare_s(eagle_ctx* ctx, const double* Sa, long n, long n_pad);
+int eagle_dev_forget_s(eagle_ctx* ctx);
+int eagle_w8_keep_stats(eagle_ctx* ctx, long* hits, long* misses);
 /* Marker-sharded runs share the n^3 part: each rank computes v and the rows [row0, row1) (multiples of 128) of the W^T
  * image (full rows), the row blocks are all-gathered, and eagle_dev_fold_upper folds the complete image in place. */
 int eagle_dev_scan_operands_rows(eagle_ctx* ctx, const double* Sa, const double* Va, const double* ahat, long n, long n_pad,

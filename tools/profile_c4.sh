@@ -8,7 +8,7 @@ OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 CMD="python3 $ROOT/tools/c4_shard.py $N $L 8"
-KF="--kernel-include-regex k_vara_i8|k_w8_gemm|k_gemm_f64|k_syrk_f4|k_gram|k_w8_slice|k_w8_combine"
+KF="--kernel-include-regex k_vara_i8|k_w8_gemm|k_gemm_f64|k_syrk_f4|k_gram|k_w8_slice|k_w8_rowpass|k_w8_combine"
 echo "== stats pass (W on the int8 engine)"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o stats -- $CMD > $OUT/stats.log 2>&1 || { tail -5 $OUT/stats.log; exit 1; }
 echo "== stats pass (W on the fp64 GEMM)"
