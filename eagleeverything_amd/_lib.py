@@ -189,6 +189,10 @@ SIGNATURES = {
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "eagle_dev_vara_i8_mfma": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_long, C.c_int, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    "eagle_dev_pack_2bit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_long, C.c_void_p, C.c_void_p]),
+    "eagle_dev_unpack_2bit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_long, C.c_void_p, C.c_void_p]),
+    "eagle_dev_vara_i8_prepare_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_long, C.c_void_p, C.c_int,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "eagle_dev_spectral_zbuild": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p]),
     "eagle_spectral_zbuild_i8_workspace_bytes": (C.c_int64, [C.c_long, C.c_int]),
     "eagle_dev_spectral_zbuild_i8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
@@ -209,6 +213,11 @@ SIGNATURES = {
                                           C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_int)]),
     "eagle_w8_host_bound": (C.c_double, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_long]),
     "eagle_dev_set_spectral": (None, [C.c_void_p, C.c_int]),
+    "eagle_vara_i8_ws_slot_offset": (C.c_int64, [C.c_long, C.c_long, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "eagle_dev_gemv3_i8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "eagle_dev_gemv3_2bit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "eagle_dev_gemm_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p]),
     "eagle_dev_colgemv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p]),
 }

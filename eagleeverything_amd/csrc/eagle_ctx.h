@@ -122,7 +122,7 @@ struct eagle_ctx {
     void* stage_pin[2] = {nullptr, nullptr}; void* stage_raw[2] = {nullptr, nullptr}; size_t stage_cap = 0;  // tile streamer
     // per-device launch state (a process may hold one ctx per GPU): dynamic-LDS attributes set on this device, schedule
     // experiment switch of tools/bench_i8_engine.py (0 = shipped)
-    bool attr_vara_i8 = false, attr_vara_i8w = false, attr_vara_i8p = false, attr_vara_i8pp = false, attr_vara_i8px = false, attr_syrk_f4w = false, attr_zbuild_i8 = false, attr_vara_f6 = false, attr_gemv = false, attr_w8_gemm = false, attr_knn_rows = false, attr_knn_rows_dist = false, attr_ldknn = false;
+    bool attr_vara_i8 = false, attr_vara_i8w = false, attr_vara_i8p = false, attr_vara_i8pp = false, attr_vara_i8px = false, attr_syrk_f4w = false, attr_zbuild_i8 = false, attr_vara_f6 = false, attr_gemv = false, attr_gemv2 = false, attr_w8_gemm = false, attr_knn_rows = false, attr_knn_rows_dist = false, attr_ldknn = false;
     uint32_t attr_bedld = 0;   // k_bedld_tile<NB, R2>: bit 2 (NB - 2) + R2
     int tune = 0;
     // W = S (V S) on the int8 engine (eagle_w8.hip): workspace, and what the last call left for the scan that follows it

@@ -242,9 +242,20 @@ __global__ __launch_bounds__(256) void k_vara_prep(const double* __restrict__ Wu
 // below from the tiles it reads anyway (the same llrint, the same digit).
 // rs[i] += sum_j |(D D^T)_ij| over the upper-triangular 256-tile pairs of the symmetric product (both the row sums of a tile and, off
 // the diagonal, its column sums = the row sums of the mirrored tile).  Whole K per workgroup: |.| does not commute with a K split.
+// HI (the level-1 call on Ds): the tile epilogue also does the first half of level 2 from the accumulators it holds -- E_hi, lo_sumsq,
+// maxdiag, hi_overflow, see k_gram_hi_i8 below, which forms the same exact product a second time (kept behind tune 33).  G = D D^T is
+// symmetric as an integer matrix, so the upper pair (ti, tj) serves its mirror too: lo^2 of an off-diagonal tile counts twice, and the E_hi
+// tile is stored a second time transposed.  Both stores go through the stage buffers (free after the K loop) as rows of 256 bytes,
+// GRAM_TS apart so that the transposed 4-byte writes of a half-wave spread over the banks.  Only when level 1 CAN hand over to level 2
+// (the conditions under which k_spectral_decide sets spec_try2, all in the header by now): slot smax - 2 holds a live digit otherwise.
+// Level 1 may still take the digit itself: k_gram_hi_settle then puts the three header fields back to zero, as they are without level 2.
+#define GRAM_TS 272
+template <bool HI>
 __global__ __launch_bounds__(512, 2) void k_gram_rowabs_i8(const int8_t* __restrict__ D, long ld, const int* __restrict__ pairs, int npairs,
-                                                           long nstages, unsigned long long* __restrict__ rs, const int* __restrict__ gate) {
+                                                           long nstages, unsigned long long* __restrict__ rs, const int* __restrict__ gate,
+                                                           VaraHdr* __restrict__ hdr, int8_t* __restrict__ Ehi, int shift, int smax) {
     __shared__ __attribute__((aligned(1024))) int8_t lds[2][2][TILE_BYTES];
+    static_assert(T8 * GRAM_TS <= 4 * TILE_BYTES, "the E_hi tile fits the stage buffers");
     if (gate && *gate == 0) return;   // level 2 only when level 1 declined
     const int cpx = (gridDim.x + 7) / 8;
     const int lid = (blockIdx.x & 7) * cpx + (blockIdx.x >> 3);   // an XCD gets a contiguous range of the super-tile ordered list
@@ -298,6 +309,78 @@ __global__ __launch_bounds__(512, 2) void k_gram_rowabs_i8(const int8_t* __restr
             r += __shfl_xor(r, 16);
             if ((lane & 31) == 0) atomicAdd(&rs[(long)ti * T8 + wr * 128 + m * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5)], r);
         }
+    if constexpr (HI) {
+        const int S = hdr->S_sliced;
+        if (!(hdr->maxabs_off > 0.0 && S >= 2 && S < smax - 1 && hdr->S == S && !hdr->pad)) return;   // (uniform over the grid)
+        int8_t* tb = &lds[0][0][0];
+        const int half = 1 << (shift - 1);
+        unsigned long long sq = 0;
+        int dmax = 0, over = 0;
+#pragma unroll
+        for (int m = 0; m < 4; m++)
+#pragma unroll
+            for (int n = 0; n < 2; n++)
+#pragma unroll
+                for (int q = 0; q < 16; q++) {
+                    const int r = wr * 128 + m * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
+                    const int c = wc * 64 + n * 32 + (lane & 31);
+                    const int v = acc[m][n][q];
+                    int hi = 0;
+                    if (ti == tj && r == c) dmax = v > dmax ? v : dmax;
+                    else {
+                        hi = (v + half) >> shift;                 // floor((v + 2^(s-1)) / 2^s): lo in [-2^(s-1), 2^(s-1))
+                        const int lo = v - hi * (1 << shift);     // (|v| + 2^(s-1) < 2^31: no wrap on the way)
+                        sq += (unsigned long long)((long long)lo * lo);
+                        over |= (hi > 127) | (hi < -128);
+                    }
+                    tb[r * GRAM_TS + c] = (int8_t)hi;
+                }
+        __syncthreads();
+#pragma unroll
+        for (int it = 0; it < T8 * 16 / 512; it++) {
+            const int id = it * 512 + t, row = id >> 4, cc = (id & 15) * 16;
+            *(int4*)(Ehi + ((long)ti * T8 + row) * ld + (long)tj * T8 + cc) = *(const int4*)(tb + row * GRAM_TS + cc);
+        }
+        if (ti != tj) {
+            sq *= 2;   // the mirrored tile holds the same entries
+            __syncthreads();
+#pragma unroll
+            for (int m = 0; m < 4; m++)
+#pragma unroll
+                for (int n = 0; n < 2; n++)
+#pragma unroll
+                    for (int g = 0; g < 4; g++) {
+                        const int r = wr * 128 + m * 32 + 8 * g + 4 * (lane >> 5);
+                        const int c = wc * 64 + n * 32 + (lane & 31);
+                        unsigned int pk = 0;
+#pragma unroll
+                        for (int x = 0; x < 4; x++) pk |= (unsigned int)(((acc[m][n][4 * g + x] + half) >> shift) & 255) << (8 * x);
+                        *(unsigned int*)(tb + c * GRAM_TS + r) = pk;
+                    }
+            __syncthreads();
+#pragma unroll
+            for (int it = 0; it < T8 * 16 / 512; it++) {
+                const int id = it * 512 + t, row = id >> 4, cc = (id & 15) * 16;
+                *(int4*)(Ehi + ((long)tj * T8 + row) * ld + (long)ti * T8 + cc) = *(const int4*)(tb + row * GRAM_TS + cc);
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            sq += __shfl_xor(sq, o);
+            const int d2 = __shfl_xor(dmax, o);
+            dmax = d2 > dmax ? d2 : dmax;
+            over |= __shfl_xor(over, o);
+        }
+        if (lane == 0) {
+            if (sq) atomicAdd(&hdr->lo_sumsq, sq);
+            if (dmax) atomicMax(&hdr->maxdiag, dmax);
+            if (over) atomicOr(&hdr->hi_overflow, 1);
+        }
+    }
+}
+// After the level-1 decide of the fused form: level 2 not asked for -> its three fields read as if nobody had computed them.
+__global__ void k_gram_hi_settle(VaraHdr* __restrict__ hdr) {
+    if (!hdr->spec_try2) { hdr->lo_sumsq = 0; hdr->maxdiag = 0; hdr->hi_overflow = 0; }
 }
 
 // Second level (only when the first declined).  ||Ds||_2^2 = lambda_max(G), G = Ds Ds, and Gershgorin's row sums lose a factor ~0.45 n^(1/4)
@@ -1594,6 +1677,12 @@ extern "C" int64_t eagle_vara_i8_workspace_bytes(long n_pad, long L_pad, int nsl
     const int smax = ws_smax(nslices);
     return (int64_t)(ws_xc_off(n_pad, L_pad, smax) + (size_t)ext_cap(L_pad) * (size_t)n_pad);
 }
+// Where slot `slot` (n_pad^2 bytes) of the slice area lies in that workspace, and how many slots it has (tests; not part of the public ABI).
+extern "C" int64_t eagle_vara_i8_ws_slot_offset(long n_pad, long L_pad, int nslices, int slot, int* nslots) {
+    const int smax = ws_smax(nslices);
+    if (nslots) *nslots = smax;
+    return (int64_t)(ws_bs_off(n_pad, L_pad, smax) + (size_t)slot * (size_t)n_pad * (size_t)n_pad);
+}
 
 static int vara_i8_check(eagle_ctx* ctx, long L_pad, long n_pad, long ld, int nslices) {
     if (L_pad % T8 || n_pad % T8 || ld % 128 || n_pad > ld || nslices < 0 || (nslices & ~EAGLE_SLICES_STOCHASTIC) > 8 || (double)ld * T8 >= 2147483648.0)
@@ -1614,8 +1703,9 @@ static bool vara_piped(const eagle_ctx* ctx, long n_pad) { return ctx->tune != 8
 // part 0: everything (one block = the whole scan).  A scan that walks several marker blocks of the SAME L_pad through one workspace
 // (a streamed file) does the W-dependent work once -- part 1: header, digits of W, rho; 4 n_pad^2 S bytes written -- and per block
 // only part 2: q zeroed, ONE pass over the block's genotypes (a = Mt8 v, the diagonal term, m^T rho).
-extern "C" int eagle_dev_vara_i8_prepare_part(eagle_ctx* ctx, const int8_t* Mt8, long L_pad, long n_pad, long ld, const double* Wu,
-                                              int nslices, void* ws, const double* v, double* a_out, void* stream, int part) {
+// Mt2 (may be NULL): the 2-bit image of Mt8 (eagle_dev_pack_2bit, same ld) -- the genotype pass reads it instead, same bits out.
+static int vara_i8_prepare_impl(eagle_ctx* ctx, const int8_t* Mt8, const void* Mt2, long L_pad, long n_pad, long ld, const double* Wu,
+                                int nslices, void* ws, const double* v, double* a_out, void* stream, int part) {
     int rc = vara_i8_check(ctx, L_pad, n_pad, ld, nslices);
     if (rc) return rc;
     if (L_pad == 0) return EAGLE_OK;
@@ -1660,7 +1750,8 @@ extern "C" int eagle_dev_vara_i8_prepare_part(eagle_ctx* ctx, const int8_t* Mt8,
     if (part != 1) {
         // ONE pass over the genotypes: a = Mt8 v (if asked for; a NULL a_out drops it), the diagonal term, and m^T rho
         double* mrho = (double*)((char*)ws + ws_mr_off(n_pad, L_pad, smax));
-        rc = eagle_dev_gemv3_i8(ctx, Mt8, L_pad, n_pad, ld, v ? v : dW, dW, rho, 1.0, v ? a_out : nullptr, vdiag, mrho, stream);
+        rc = Mt2 ? eagle_dev_gemv3_2bit(ctx, Mt2, L_pad, n_pad, ld, v ? v : dW, dW, rho, 1.0, v ? a_out : nullptr, vdiag, mrho, stream)
+                 : eagle_dev_gemv3_i8(ctx, Mt8, L_pad, n_pad, ld, v ? v : dW, dW, rho, 1.0, v ? a_out : nullptr, vdiag, mrho, stream);
         if (rc) return rc;
     }
     if (part != 2) {
@@ -1681,19 +1772,29 @@ extern "C" int eagle_dev_vara_i8_prepare_part(eagle_ctx* ctx, const int8_t* Mt8,
             const int npairs = nt * (nt + 1) / 2;
             e = hipMemsetAsync(rsum, 0, sizeof(unsigned long long) * (size_t)n_pad, s);
             if (e != hipSuccess) return eagle_fail_hip(ctx, e, "spectral row sums memset");
-            hipLaunchKernelGGL(k_gram_rowabs_i8, dim3((unsigned)((npairs + 7) / 8 * 8)), dim3(512), 0, s, Ds, n_pad, pairs, npairs, n_pad / BK8, rsum,
-                               (const int*)nullptr);
-            hipLaunchKernelGGL(k_spectral_decide, dim3(1), dim3(256), 0, s, rsum, n_pad, hdr, ctx->scan_budget, ctx->scan_budget_tight, smax, 1, 0);
             // second level, dropped on the device unless the first declined: E_hi into the next spare slot, then its Gram row sums
             int8_t* Ehi = Bs + (size_t)(smax - 2) * n_pad * n_pad;
             int shift = 8;   // 127 * 2^shift >= 8 standard deviations sqrt(n) 74^2 of a random Gram entry
             while (shift < 23 && 127.0 * (double)(1 << shift) < 8.0 * 5476.0 * sqrt((double)n_pad)) shift++;
-            const int nsc = (nt + 5) / 6;
-            hipLaunchKernelGGL(k_gram_hi_i8, dim3((unsigned)((nsc * nsc * 36 + 7) / 8 * 8)), dim3(512), 0, s, Ds, n_pad, nt, n_pad / BK8, shift, hdr, Ehi);
+            // Ds Ds is formed ONCE: the level-1 product leaves E_hi and the header fields of level 2 on the way (tune 33: the two-kernel
+            // form, the product a second time in k_gram_hi_i8 -- A/B runs and tests/test_gpu_gram_once.py; the same bytes either way)
+            const bool once = ctx->tune != 33;
+            if (once)
+                hipLaunchKernelGGL(k_gram_rowabs_i8<true>, dim3((unsigned)((npairs + 7) / 8 * 8)), dim3(512), 0, s, Ds, n_pad, pairs, npairs, n_pad / BK8,
+                                   rsum, (const int*)nullptr, hdr, Ehi, shift, smax);
+            else
+                hipLaunchKernelGGL(k_gram_rowabs_i8<false>, dim3((unsigned)((npairs + 7) / 8 * 8)), dim3(512), 0, s, Ds, n_pad, pairs, npairs, n_pad / BK8,
+                                   rsum, (const int*)nullptr, (VaraHdr*)nullptr, (int8_t*)nullptr, 0, 0);
+            hipLaunchKernelGGL(k_spectral_decide, dim3(1), dim3(256), 0, s, rsum, n_pad, hdr, ctx->scan_budget, ctx->scan_budget_tight, smax, 1, 0);
+            if (once) hipLaunchKernelGGL(k_gram_hi_settle, dim3(1), dim3(1), 0, s, hdr);
+            else {
+                const int nsc = (nt + 5) / 6;
+                hipLaunchKernelGGL(k_gram_hi_i8, dim3((unsigned)((nsc * nsc * 36 + 7) / 8 * 8)), dim3(512), 0, s, Ds, n_pad, nt, n_pad / BK8, shift, hdr, Ehi);
+            }
             e = hipMemsetAsync(rsum, 0, sizeof(unsigned long long) * (size_t)n_pad, s);
             if (e != hipSuccess) return eagle_fail_hip(ctx, e, "spectral row sums memset");
-            hipLaunchKernelGGL(k_gram_rowabs_i8, dim3((unsigned)((npairs + 7) / 8 * 8)), dim3(512), 0, s, Ehi, n_pad, pairs, npairs, n_pad / BK8, rsum,
-                               (const int*)&hdr->spec_try2);
+            hipLaunchKernelGGL(k_gram_rowabs_i8<false>, dim3((unsigned)((npairs + 7) / 8 * 8)), dim3(512), 0, s, Ehi, n_pad, pairs, npairs, n_pad / BK8, rsum,
+                               (const int*)&hdr->spec_try2, (VaraHdr*)nullptr, (int8_t*)nullptr, 0, 0);
             hipLaunchKernelGGL(k_spectral_decide, dim3(1), dim3(256), 0, s, rsum, n_pad, hdr, ctx->scan_budget, ctx->scan_budget_tight, smax, 2, shift);
         }
     }
@@ -1701,9 +1802,18 @@ extern "C" int eagle_dev_vara_i8_prepare_part(eagle_ctx* ctx, const int8_t* Mt8,
     if (e != hipSuccess) return eagle_fail_hip(ctx, e, "vara_i8_prepare");
     return EAGLE_OK;
 }
+extern "C" int eagle_dev_vara_i8_prepare_part(eagle_ctx* ctx, const int8_t* Mt8, long L_pad, long n_pad, long ld, const double* Wu,
+                                              int nslices, void* ws, const double* v, double* a_out, void* stream, int part) {
+    return vara_i8_prepare_impl(ctx, Mt8, nullptr, L_pad, n_pad, ld, Wu, nslices, ws, v, a_out, stream, part);
+}
 extern "C" int eagle_dev_vara_i8_prepare(eagle_ctx* ctx, const int8_t* Mt8, long L_pad, long n_pad, long ld, const double* Wu,
                                          int nslices, void* ws, const double* v, double* a_out, void* stream) {
-    return eagle_dev_vara_i8_prepare_part(ctx, Mt8, L_pad, n_pad, ld, Wu, nslices, ws, v, a_out, stream, 0);
+    return vara_i8_prepare_impl(ctx, Mt8, nullptr, L_pad, n_pad, ld, Wu, nslices, ws, v, a_out, stream, 0);
+}
+extern "C" int eagle_dev_vara_i8_prepare_packed(eagle_ctx* ctx, const void* Mt2, long L_pad, long n_pad, long ld, const double* Wu,
+                                                int nslices, void* ws, const double* v, double* a_out, void* stream) {
+    if (!Mt2 || ld % 256) return eagle_fail(ctx, EAGLE_ERR_ARG, "vara_i8_prepare_packed: a 2-bit image with ld % 256 == 0");
+    return vara_i8_prepare_impl(ctx, nullptr, Mt2, L_pad, n_pad, ld, Wu, nslices, ws, v, a_out, stream, 0);
 }
 
 // The int8 MFMA kernel over all (marker tile, slice) workers of an image: q[s][i] += ... for the hdr->S slices at Bs (grid sized for smax).

@@ -42,6 +42,8 @@ int eagle_dev_gemv2_i8(eagle_ctx* ctx, const int8_t* Mt8, long L_pad, long n_pad
                        double scale, double* out_a, double* out_d, void* stream);
 int eagle_dev_gemv3_i8(eagle_ctx* ctx, const int8_t* Mt8, long L_pad, long n_pad, long ld, const double* v, const double* w,
                        const double* x, double scale, double* out_a, double* out_d, double* out_x, void* stream);
+int eagle_dev_gemv3_2bit(eagle_ctx* ctx, const void* Mt2, long L_pad, long n_pad, long ld, const double* v, const double* w, const double* x,
+                         double scale, double* out_a, double* out_d, double* out_x, void* stream);
 int eagle_dev_vara_f64_gated(eagle_ctx* ctx, const int8_t* Mt8, long L_pad, long n_pad, long ld, const double* Wu, double* vara_out,
                              const int* run_if, void* stream);
 long eagle_vara_f64_split_partial_doubles(long rows_cap, long n_pad);

@@ -1759,6 +1759,192 @@ extern "C" int eagle_dev_gemv_i8(eagle_ctx* ctx, const int8_t* Mt8, long L_pad, 
     return eagle_dev_gemv2_i8(ctx, Mt8, L_pad, n_pad, ld, v, nullptr, scale, out, nullptr, stream);
 }
 
+// ------------------------------------------------------------------------------------------------
+// The same pass from a 2-BIT image of the genotypes (a quarter of the bytes: the pass above sits on the HBM stream with the matrix
+// pipe a fifth busy).  Genotypes are {-1, 0, +1} and the same bytes in every scan of a run, so the image is made once
+// (eagle_dev_pack_2bit) next to the int8 one: ld / 4 bytes per marker.
+// Layout.  Lane (r, q) of k_gemv_mfma takes, at step st, the 16 bytes k = 64 st + 16 q + j, j < 16, of marker r as four dwords d = j >> 2
+// of four bytes b = j & 3.  Here ONE 16-byte load holds that lane's fragments of the four steps st = 4 T + u of a 256-column
+// super-step T: it lies at byte 64 T + 16 q of the marker's packed row, dword u of it is step 4 T + u, and genotype (d, b) of that step
+// is the 2-bit code m & 3 (0 -> 0, +1 -> 1, -1 -> 3) at bits 8 b + 2 d.  So fragment dword d is one shift, one mask and one byte
+// permute of the packed dword: (p >> 2 d) & 0x03030303 holds the codes of its four bytes, v_perm_b32 looks them up in {0, 1, -1, -1}.
+// The decoded fragment is the int8 image's, byte for byte: the MFMA sums, m^2 = m & 1 and the assembly of a, d, x are those above.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ gv_i32x4 gv2_decode(unsigned int p) {
+    const unsigned int tbl = 0xffff0100u;   // byte c = the genotype of code c
+    gv_i32x4 a;
+#pragma unroll
+    for (int d = 0; d < 4; d++) a[d] = (int)__builtin_amdgcn_perm(tbl, tbl, (p >> (2 * d)) & 0x03030303u);
+    return a;
+}
+// one thread per 16 genotypes (one packed dword): chunk ch = k >> 4 = 16 T + 4 u + q  <->  packed dword 16 T + 4 q + u
+__global__ __launch_bounds__(256) void k_pack_2bit(const int8_t* __restrict__ Mt8, long rows, long ld, unsigned int* __restrict__ P, int unpack,
+                                                   int8_t* __restrict__ out8) {
+    const long nch = ld >> 4;
+    const long total = rows * nch;
+    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        const long row = idx / nch, ch = idx - row * nch;
+        const long T = ch >> 4, u = (ch >> 2) & 3, q = ch & 3;
+        unsigned int* pw = P + row * (ld >> 4) + 16 * T + 4 * q + u;
+        if (unpack) { *(gv_i32x4*)(out8 + row * ld + (ch << 4)) = gv2_decode(*pw); continue; }
+        const gv_i32x4 m = *(const gv_i32x4*)(Mt8 + row * ld + (ch << 4));
+        unsigned int p = 0;
+#pragma unroll
+        for (int d = 0; d < 4; d++) p |= ((unsigned int)m[d] & 0x03030303u) << (2 * d);
+        *pw = p;
+    }
+}
+static int pack_2bit_check(eagle_ctx* ctx, long L_pad, long n_pad, long ld) {
+    if (L_pad % 16 || n_pad % 256 || ld % 256 || n_pad > ld || L_pad < 0 || n_pad < 0)
+        return eagle_fail(ctx, EAGLE_ERR_ARG, "2-bit image: layout contract violated (L_pad % 16, n_pad % 256, ld % 256)");
+    return EAGLE_OK;
+}
+extern "C" int eagle_dev_pack_2bit(eagle_ctx* ctx, const int8_t* Mt8, long L_pad, long n_pad, long ld, void* Mt2, void* stream) {
+    int rc = pack_2bit_check(ctx, L_pad, n_pad, ld);
+    if (rc) return rc;
+    if (L_pad == 0 || ld == 0) return EAGLE_OK;
+    const long total = L_pad * (ld >> 4);
+    hipLaunchKernelGGL(k_pack_2bit, dim3((unsigned)((total + 255) / 256 < 65536 ? (total + 255) / 256 : 65536)), dim3(256), 0, (hipStream_t)stream, Mt8, L_pad, ld,
+                       (unsigned int*)Mt2, 0, (int8_t*)nullptr);
+    LAUNCH_CHECK(ctx);
+    return EAGLE_OK;
+}
+// the int8 image back from the 2-bit one, through the decode of the pass itself (tests)
+extern "C" int eagle_dev_unpack_2bit(eagle_ctx* ctx, const void* Mt2, long L_pad, long n_pad, long ld, int8_t* Mt8, void* stream) {
+    int rc = pack_2bit_check(ctx, L_pad, n_pad, ld);
+    if (rc) return rc;
+    if (L_pad == 0 || ld == 0) return EAGLE_OK;
+    const long total = L_pad * (ld >> 4);
+    hipLaunchKernelGGL(k_pack_2bit, dim3((unsigned)((total + 255) / 256 < 65536 ? (total + 255) / 256 : 65536)), dim3(256), 0, (hipStream_t)stream,
+                       (const int8_t*)nullptr, L_pad, ld, (unsigned int*)Mt2, 1, Mt8);
+    LAUNCH_CHECK(ctx);
+    return EAGLE_OK;
+}
+
+#define GV2_U 4  /* 16-byte packed loads per lane in flight: 16 steps of the int8 pass */
+// k_gemv_mfma with the operand fetch from the 2-bit image Mt2 (row stride ld2 bytes, n_pad % 256 == 0).
+template <bool SQ, bool X3>
+__global__ __launch_bounds__(1024) void k_gemv_mfma_2bit(const uint8_t* __restrict__ Mt2, long L_pad, int n_pad, long ld2,
+                                                         const int8_t* __restrict__ B, const int* __restrict__ exps, double scale,
+                                                         double* __restrict__ out_a, double* __restrict__ out_d, double* __restrict__ out_x,
+                                                         int accumulate) {
+    extern __shared__ __attribute__((aligned(16))) int8_t lB[];  // [16 or 32][n_pad], chunk c of row r stored at chunk c ^ (r & 15)
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int nchunk = n_pad >> 4;
+    for (int idx = t; idx < (X3 ? 32 : 16) * nchunk; idx += 1024) {
+        const int r = idx / nchunk, c = idx - r * nchunk;
+        *(gv_i32x4*)(lB + (long)r * n_pad + ((c ^ (r & 15)) << 4)) = *(const gv_i32x4*)(B + (long)r * n_pad + (c << 4));
+    }
+    __syncthreads();
+    const int r = lane & 15, q = lane >> 4;
+    const int8_t* brow = lB + (long)r * n_pad;
+    const int8_t* brow2 = lB + (long)(16 + r) * n_pad;
+    const double sa = scale * ldexp(1.0, exps[0] - 62), sd = ldexp(1.0, exps[1] - 62), sx = X3 ? ldexp(1.0, exps[2] - 62) : 0.0;
+    const long ngroups = L_pad >> 4;
+    const int nsup = n_pad >> 8;
+    for (long g = (long)blockIdx.x * 16 + wv; g < ngroups; g += (long)gridDim.x * 16) {
+        const uint8_t* pp = Mt2 + (g * 16 + r) * ld2 + (q << 4);
+        gv_i32x4 accA = {0, 0, 0, 0}, accD = {0, 0, 0, 0}, accX = {0, 0, 0, 0};
+        for (int sp = 0; sp < nsup; sp += GV2_U) {
+            gv_i32x4 p[GV2_U];
+#pragma unroll
+            for (int u = 0; u < GV2_U; u++)
+                p[u] = sp + u < nsup ? *(const gv_i32x4*)(pp + ((sp + u) << 6)) : (gv_i32x4){0, 0, 0, 0};
+#pragma unroll
+            for (int u = 0; u < GV2_U; u++) {
+                if (sp + u >= nsup) break;   // (wave-uniform)
+#pragma unroll
+                for (int s4 = 0; s4 < 4; s4++) {
+                    const int st = 4 * (sp + u) + s4;
+                    const gv_i32x4 a = gv2_decode((unsigned int)p[u][s4]);
+                    const gv_i32x4 b = *(const gv_i32x4*)(brow + (((4 * st + q) ^ r) << 4));
+                    accA = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, accA, 0, 0, 0);
+                    if (SQ) {
+                        const gv_i32x4 a2 = a & (gv_i32x4){0x01010101, 0x01010101, 0x01010101, 0x01010101};
+                        accD = __builtin_amdgcn_mfma_i32_16x16x64_i8(a2, b, accD, 0, 0, 0);
+                    }
+                    if (X3) {
+                        const gv_i32x4 b2 = *(const gv_i32x4*)(brow2 + (((4 * st + q) ^ r) << 4));
+                        accX = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b2, accX, 0, 0, 0);
+                    }
+                }
+            }
+        }
+        // lane holds P[row = 4q + e][col = r]: cols 0..7 of accA are the digits of v, cols 8..15 of accD those of w
+        const int s = r & 7;
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            const long long val = (r < 8) ? (long long)accA[e] : (long long)(SQ ? accD[e] : 0);
+            long long hi = s >= 4 ? val << (8 * (s - 4)) : 0, lo = s < 4 ? val << (8 * s) : 0;
+#pragma unroll
+            for (int o = 1; o < 8; o <<= 1) { hi += __shfl_xor(hi, o); lo += __shfl_xor(lo, o); }
+            if (s == 0) {
+                const long row = g * 16 + 4 * q + e;
+                const double x = (double)hi * 4294967296.0 + (double)lo;
+                if (r == 0) { if (out_a) out_a[row] = accumulate ? out_a[row] + sa * x : sa * x; }
+                else if (SQ) out_d[row] = accumulate ? out_d[row] + sd * x : sd * x;
+            }
+            if (X3) {  // cols 0..7 of accX: the digits of the third vector
+                const long long vx = (r < 8) ? (long long)accX[e] : 0;
+                long long hx = s >= 4 ? vx << (8 * (s - 4)) : 0, lx = s < 4 ? vx << (8 * s) : 0;
+#pragma unroll
+                for (int o = 1; o < 8; o <<= 1) { hx += __shfl_xor(hx, o); lx += __shfl_xor(lx, o); }
+                if (r == 0) {
+                    const double xv = sx * ((double)hx * 4294967296.0 + (double)lx);
+                    out_x[g * 16 + 4 * q + e] = accumulate ? out_x[g * 16 + 4 * q + e] + xv : xv;
+                }
+            }
+        }
+    }
+}
+
+// eagle_dev_gemv3_i8 on the 2-bit image of Mt8 (eagle_dev_pack_2bit with the same ld): the same sweeps, the same bits in every output.
+extern "C" int eagle_dev_gemv3_2bit(eagle_ctx* ctx, const void* Mt2v, long L_pad, long n_pad, long ld, const double* v, const double* w,
+                                    const double* x, double scale, double* out_a, double* out_d, double* out_x, void* stream) {
+    int rc = pack_2bit_check(ctx, L_pad, n_pad, ld);
+    if (rc) return rc;
+    if (L_pad == 0 || n_pad == 0) return EAGLE_OK;
+    const uint8_t* Mt2 = (const uint8_t*)Mt2v;
+    const long ld2 = ld >> 2;
+    if (!ctx->gemv_ws) {
+        hipError_t e = hipMalloc(&ctx->gemv_ws, 32 * GV_MAXN + 256);
+        if (e != hipSuccess) return eagle_fail_hip(ctx, e, "gemv workspace");
+    }
+    int8_t* B = (int8_t*)ctx->gemv_ws;
+    int* exps = (int*)(B + 32 * GV_MAXN);
+    if (!ctx->attr_gemv2) {  // per device
+        hipError_t e = hipFuncSetAttribute((const void*)k_gemv_mfma_2bit<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gemv_mfma_2bit<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gemv_mfma_2bit<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) return eagle_fail_hip(ctx, e, "hipFuncSetAttribute");
+        ctx->attr_gemv2 = true;
+    }
+    long blocks = 256;
+    const long groups = L_pad / 16;
+    if (blocks > (groups + 15) / 16) blocks = (groups + 15) / 16;
+    if (x && w) {
+        for (long k0 = 0; k0 < n_pad; k0 += GV_MAXN / 2) {
+            const int nk = (int)(n_pad - k0 < GV_MAXN / 2 ? n_pad - k0 : GV_MAXN / 2);
+            hipLaunchKernelGGL(k_slice_vec, dim3(1), dim3(1024), 0, (hipStream_t)stream, v + k0, w + k0, x + k0, nk, B, exps);
+            hipLaunchKernelGGL((k_gemv_mfma_2bit<true, true>), dim3((unsigned)blocks), dim3(1024), (size_t)32 * nk, (hipStream_t)stream, Mt2 + (k0 >> 2), L_pad,
+                               nk, ld2, B, exps, scale, out_a, out_d, out_x, k0 > 0);
+        }
+        LAUNCH_CHECK(ctx);
+        return EAGLE_OK;
+    }
+    for (long k0 = 0; k0 < n_pad; k0 += GV_MAXN) {
+        const int nk = (int)(n_pad - k0 < GV_MAXN ? n_pad - k0 : GV_MAXN);
+        hipLaunchKernelGGL(k_slice_vec, dim3(1), dim3(1024), 0, (hipStream_t)stream, v + k0, w ? w + k0 : nullptr, (const double*)nullptr, nk, B, exps);
+        if (w) hipLaunchKernelGGL((k_gemv_mfma_2bit<true, false>), dim3((unsigned)blocks), dim3(1024), (size_t)16 * nk, (hipStream_t)stream, Mt2 + (k0 >> 2), L_pad, nk,
+                                  ld2, B, exps, scale, out_a, out_d, (double*)nullptr, k0 > 0);
+        else hipLaunchKernelGGL((k_gemv_mfma_2bit<false, false>), dim3((unsigned)blocks), dim3(1024), (size_t)16 * nk, (hipStream_t)stream, Mt2 + (k0 >> 2), L_pad, nk,
+                                ld2, B, exps, scale, out_a, out_d, (double*)nullptr, k0 > 0);
+    }
+    LAUNCH_CHECK(ctx);
+    if (x) return eagle_dev_gemv3_2bit(ctx, Mt2v, L_pad, n_pad, ld, x, nullptr, nullptr, 1.0, out_x, nullptr, nullptr, stream);
+    return EAGLE_OK;
+}
+
 extern "C" int eagle_dev_vara_f64(eagle_ctx* ctx, const int8_t* Mt8, long L_pad, long n_pad, long ld, const double* Wu,
                                   double* vara_out, void* stream) {
     return eagle_dev_vara_f64_gated(ctx, Mt8, L_pad, n_pad, ld, Wu, vara_out, nullptr, stream);

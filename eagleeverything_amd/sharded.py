@@ -16,6 +16,7 @@ MM^T = sum_s M_s M_s^T (calculateMMt_rcpp.cpp:95).
 `DeviceShard` needs a GPU and calls the device-resident C ABI (section 2 of include/eagle_hip.h).
 """
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -143,6 +144,10 @@ class DeviceShard:
         self.ws = None
         self._ws_mode = None
         self.Mt4 = None
+        self.Mt2 = None
+        # mode 1: the genotype pass of vara_prepare() reads the 2-bit image (packed_image), a quarter of the bytes; EAGLE_HIP_PACKED=0 or
+        # packed = False: the int8 image (A/B runs, as EAGLE_HIP_TUNE for the kernels)
+        self.packed = os.environ.get("EAGLE_HIP_PACKED", "1") != "0"
         self.Mt8s = self.cshift = self.l1 = None
         self.cert_ws = None
         self.certified = True  # digit-slice scans are certified (eagle_dev_scan_certify) before the arg-max
@@ -153,6 +158,17 @@ class DeviceShard:
         self.extend = True       # eagle_dev_vara_i8_extend after the vara kernel (tests switch it off to see the raw values)
         self.declare_s = True    # set_operands declares its S image to the context (eagle_dev_declare_s): False = nothing kept between calls
         self.w_mode = 1          # eagle_set_w_mode for the digit-slice scan: 1 = W on the int8 engine from 4,096 padded individuals up, 0 = fp64 GEMM, 2 = int8 always
+
+    # the images made once from the genotypes go together: whoever drops the re-centred one (new genotypes) drops the 2-bit one with it
+    @property
+    def Mt8s(self):
+        return self._Mt8s
+
+    @Mt8s.setter
+    def Mt8s(self, value):
+        self._Mt8s = value
+        if value is None:
+            self.Mt2 = None
 
     # ---- plumbing -------------------------------------------------------------------------------
     def _stream(self):
@@ -180,6 +196,7 @@ class DeviceShard:
             lo, hi = max(c0, self.first), min(c0 + chunk, self.first + self.Lloc)
             self.Mt8[lo - self.first:hi - self.first, : self.n] = g[lo - c0:hi - c0]
         self.M8 = None
+        self.Mt2 = None
 
     def fill_structured(self, K=2, fst=0.5, seed=5, pmin=0.05, chunk=16384):
         """Synthetic genotypes WITH population structure (Balding-Nichols): K equal sub-populations whose allele frequencies drift from a
@@ -211,6 +228,7 @@ class DeviceShard:
         self._check(self.L.eagle_dev_load_ascii(self.ctx, path.encode(), self.first, self.Lloc, 0, self.n,
                                                 self.Mt8.data_ptr(), self.np_, float(max_mem_gb), int(threads)))
         self.M8 = None
+        self.Mt2 = None
 
     def load_M_ascii(self, path, max_mem_gb=8.0, threads=8):
         """Column window [first, first+Lloc) of every line of M.ascii."""
@@ -373,6 +391,15 @@ class DeviceShard:
                                                       self.Mt8s.data_ptr(), self.cshift.data_ptr(), self.l1.data_ptr(), self._stream()))
         return self.Mt8s, self.cshift
 
+    def packed_image(self):
+        """Mt2: the genotypes at 2 bits (np_ / 4 bytes per marker), made once per shard like shifted_image() for the genotype pass of
+        vara_prepare(); +25 % of the int8 image.  Dropped with Mt8s and wherever the genotypes are refilled."""
+        if self.Mt2 is None:
+            self.Mt2 = self.torch.empty((self.Lp, self.np_ // 4), dtype=self.torch.uint8, device=self.dev)
+            self._check(self.L.eagle_dev_pack_2bit(self.ctx, self.Mt8.data_ptr(), self.Lp, self.np_, self.np_, self.Mt2.data_ptr(),
+                                                   self._stream()))
+        return self.Mt2
+
     def fp4_image(self):
         """Mt4: the genotypes as fp4 (two per byte), made once per shard for the fp4 x fp6 vara kernel (mode 2)."""
         if self.Mt4 is None:
@@ -385,7 +412,10 @@ class DeviceShard:
         """int8 path, phase 1: slice W, and ONE pass over the genotypes for a = Mt v and the diagonal term of vara."""
         ws = self._ws()
         prep = self.L.eagle_dev_vara_f6_prepare if self.mode == 2 else self.L.eagle_dev_vara_i8_prepare
-        self._check(prep(self.ctx, self.Mt8.data_ptr(), self.Lp, self.np_, self.np_,
+        img = self.Mt8
+        if self.mode == 1 and self.packed:
+            prep, img = self.L.eagle_dev_vara_i8_prepare_packed, self.packed_image()
+        self._check(prep(self.ctx, img.data_ptr(), self.Lp, self.np_, self.np_,
                     self.Wu.data_ptr(), self._ns(), ws.data_ptr(), self.v.data_ptr() if with_a else None,
                     self.a.data_ptr() if with_a else None, self._stream()))
 

@@ -1184,6 +1184,17 @@ int eagle_dev_vara_i8_prepare(eagle_ctx* ctx, const int8_t* Mt8, long L_pad, lon
                               int nslices, void* ws, const double* v, double* a_out, void* stream);
 int eagle_dev_vara_i8_mfma(eagle_ctx* ctx, const int8_t* Mt8, long L_pad, long n_pad, long ld, int nslices, void* ws,
                            double* vara_out, double* err_bound_dev, void* stream);
+/* The genotype pass of prepare from a 2-bit image.  Genotypes are {-1, 0, +1} and the same bytes in every scan of a run, and the pass
+ * sits on the HBM stream: eagle_dev_pack_2bit makes, once, the image Mt2 of an int8 image -- ld / 4 bytes per marker, the codes m & 3
+ * laid out so that one 16-byte load is a lane's MFMA fragments of four 64-column steps (csrc/eagle_kernels.hip) -- and
+ * eagle_dev_vara_i8_prepare_packed is eagle_dev_vara_i8_prepare reading it (ld is the int8 image's): the fragments decode to the int8
+ * image's bytes and the integer sums are the same, so a, the diagonal term and m^T rho come out bit for bit.  L_pad % 16 == 0,
+ * n_pad % 256 == 0, ld % 256 == 0.  A value outside {-1, 0, +1} is not representable (its low two bits are kept).
+ * eagle_dev_unpack_2bit: the int8 image back through the decode of the pass. */
+int eagle_dev_pack_2bit(eagle_ctx* ctx, const int8_t* Mt8, long L_pad, long n_pad, long ld, void* Mt2, void* stream);
+int eagle_dev_unpack_2bit(eagle_ctx* ctx, const void* Mt2, long L_pad, long n_pad, long ld, int8_t* Mt8, void* stream);
+int eagle_dev_vara_i8_prepare_packed(eagle_ctx* ctx, const void* Mt2, long L_pad, long n_pad, long ld, const double* Wu,
+                                     int nslices, void* ws, const double* v, double* a_out, void* stream);
 /* Re-centred markers for the digit-slice kernel: Mt8s[i][j] = Mt8[i][j] - c_i for the n real individuals (padding stays
  * zero), c_i in {-1,0,+1} = the majority genotype of marker i, cshift[i] = c_i.  eagle_dev_vara_i8_mfma_shifted runs
  * the MFMA kernel on Mt8s (rare-variant markers become sparse rows, so their truncation error bound

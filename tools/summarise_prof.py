@@ -23,7 +23,12 @@ def find(pattern):
 def short(name):
     for k in OURS:
         if k in name:
-            if "k_gemv_mfma" in name:   # per launch shape: the genotype pass of the digit-slice scan is <true, true> (a, diagonal term, m^T rho)
+            if "k_gemv_mfma_2bit" in name:   # the same pass from the 2-bit image
+                m = re.search(r"k_gemv_mfma_2bit<([^>]*)>", name)
+                return "k_gemv_mfma_2bit<%s>" % (m.group(1).replace(" ", "") if m else "?")
+            if "k_gram_rowabs_i8" in name:   # <true>: level 1 with the E_hi side of level 2 in its epilogue
+                return "k_gram_rowabs_i8<fused>" if ("<true>" in name or "Lb1E" in name) else "k_gram_rowabs_i8"
+            if "k_gemv_mfma" in name:  # per launch shape: the genotype pass of the digit-slice scan is <true, true> (a, diagonal term, m^T rho)
                 m = re.search(r"k_gemv_mfma<([^>]*)>", name)
                 tp = m.group(1).replace(" ", "") if m else ("true,true" if "Lb1ELb1E" in name else ("false,false" if "Lb0ELb0E" in name else ("true,false" if "Lb1ELb0E" in name else "?")))
                 return "k_gemv_mfma<%s>" % tp
