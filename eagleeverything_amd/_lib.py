@@ -214,6 +214,7 @@ SIGNATURES = {
     "eagle_w8_host_bound": (C.c_double, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_long]),
     "eagle_dev_set_spectral": (None, [C.c_void_p, C.c_int]),
     "eagle_vara_i8_ws_slot_offset": (C.c_int64, [C.c_long, C.c_long, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "eagle_vara_i8_ws_rowsum_offset": (C.c_int64, [C.c_long, C.c_long, C.c_int]),
     "eagle_dev_gemv3_i8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "eagle_dev_gemv3_2bit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,

@@ -1683,6 +1683,11 @@ extern "C" int64_t eagle_vara_i8_ws_slot_offset(long n_pad, long L_pad, int nsli
     if (nslots) *nslots = smax;
     return (int64_t)(ws_bs_off(n_pad, L_pad, smax) + (size_t)slot * (size_t)n_pad * (size_t)n_pad);
 }
+// Where the n_pad uint64 row sums of the spectral bound lie after prepare: those of |E_hi E_hi| where level 2 ran, zeros where it was
+// dropped (level 1's are cleared before level 2 runs) -- the column-partial area of rho (tests; not part of the public ABI).
+extern "C" int64_t eagle_vara_i8_ws_rowsum_offset(long n_pad, long L_pad, int nslices) {
+    return (int64_t)ws_cp_off(n_pad, L_pad, ws_smax(nslices));
+}
 
 static int vara_i8_check(eagle_ctx* ctx, long L_pad, long n_pad, long ld, int nslices) {
     if (L_pad % T8 || n_pad % T8 || ld % 128 || n_pad > ld || nslices < 0 || (nslices & ~EAGLE_SLICES_STOCHASTIC) > 8 || (double)ld * T8 >= 2147483648.0)

@@ -17,6 +17,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from exact_lastdigit import decode_header as _hdr   # the head of the digit workspace, decoded in one place
+
 pytestmark = pytest.mark.gpu
 L_MARKERS = 256
 POISON = 0xA5
@@ -31,14 +33,6 @@ def _operands(n, diag):
     v = rng.standard_normal(n)
     Mt8 = rng.integers(-1, 2, size=(L_MARKERS, n)).astype(np.int8)
     return W, v, Mt8
-
-
-def _hdr(raw):
-    h = raw[:120].tobytes()
-    i32 = lambda o: int(np.frombuffer(h[o:o + 4], dtype=np.int32)[0])
-    return {"S": i32(8), "S_sliced": i32(48), "budget": float(np.frombuffer(h[56:64], dtype=np.float64)[0]),
-            "lo_sumsq": int(np.frombuffer(h[72:80], dtype=np.uint64)[0]), "maxdiag": i32(80), "hi_overflow": i32(84), "spec_try2": i32(88),
-            "level": i32(92)}
 
 
 def _run(torch, sh, tune):

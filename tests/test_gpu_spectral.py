@@ -11,6 +11,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from exact_lastdigit import host_decision as _host_decision   # the digit rule restated on the host, stated once
+
 pytestmark = pytest.mark.gpu
 # W_kk of the "quiet" individuals in the constructed panels below: markers that are non-zero only on them have vara = q2 * 0.81 * W_kk.
 QUIET_HOPELESS = 1e-6   # below what ANY digit count of the automatic rule certifies: > 2,048 flagged markers -> fp64 fallback of the block
@@ -96,47 +98,6 @@ def test_one_digit_fewer_under_a_rigorous_spectral_bound():
     u = 2.0 ** (sh.last_e + 2 - 8 * S_wc)
     H_host = 0.5 * u * (np.sqrt(float(g)) + 0.5 * (sh.np_ - 1))
     assert H_host <= sh.last_specH <= H_host * (1 + 1e-12)
-
-
-def _host_decision(Wu, n_pad, budget=5e-7, tight=1e-7, w_err=0.0):
-    """The library's digit rule restated on the host (round 4: the tight budget is tried first, at both levels, then the default):
-    (worst-case digit count, level of the spectral bound that takes one off or 0, H, budget in force)."""
-    off = np.triu(Wu, 1)
-    mx = np.abs(off).max()
-    f, e = np.frexp(mx)
-    e = int(e) - (1 if f <= 0.98 else 0)
-    half_sumdiag = 0.5 * np.abs(np.diag(Wu)).sum()
-    wc = lambda c: float(n_pad) ** 2 * 2.0 ** (e + 1 - 8 * c) + w_err * n_pad
-    S_wc = next((c for c in range(3, 8) if wc(c) <= budget * half_sumdiag), 7)
-    in_force = tight if wc(S_wc) <= tight * half_sumdiag else budget
-    Q = np.rint(np.ldexp(off, 8 * S_wc - (e + 2)))
-    d = (np.mod(Q + 128, 256) - 128).astype(np.int64)
-    Ds = d + d.T
-    G = Ds @ Ds
-    u = 2.0 ** (e + 2 - 8 * S_wc)
-    H1 = 0.5 * u * (np.sqrt(float(np.abs(G).sum(axis=1).max())) + 0.5 * (n_pad - 1))
-    ok = lambda H, b: H > 0.0 and (H + w_err) * n_pad <= b * half_sumdiag
-    if ok(H1, tight):
-        return S_wc, 1, H1, tight
-    # level 2: lambda_max(G) <= max G_jj + 2^s ||E_hi||_2 + ||E_lo||_F
-    shift = 8
-    while shift < 23 and 127.0 * (1 << shift) < 8.0 * 5476.0 * np.sqrt(n_pad):
-        shift += 1
-    E = G - np.diag(np.diag(G))
-    hi = (E + (1 << (shift - 1))) >> shift
-    lo = E - (hi << shift)
-    H2 = 0.0
-    if not (hi.min() < -128 or hi.max() > 127):
-        g2 = np.abs(hi @ hi).sum(axis=1).max()
-        normsq = float(np.diag(G).max()) + 2.0 ** shift * np.sqrt(float(g2)) + np.sqrt(float((lo * lo).sum()))
-        H2 = 0.5 * u * (np.sqrt(normsq) + 0.5 * (n_pad - 1))
-    if ok(H2, tight):
-        return S_wc, 2, H2, tight
-    if ok(H1, budget):
-        return S_wc, 1, H1, budget
-    if ok(H2, budget):
-        return S_wc, 2, H2, budget
-    return S_wc, 0, 0.0, in_force
 
 
 def test_saving_is_not_taken_when_it_does_not_pay_or_is_not_allowed():
