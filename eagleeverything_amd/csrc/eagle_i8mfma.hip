@@ -117,6 +117,9 @@ extern "C" int eagle_dev_mmt_accumulate_i8(eagle_ctx* ctx, const int8_t* M8, lon
 // Slices are stored transposed, Bs[s][k][j] = D_s[j][k] (row = output column k, K = j contiguous), so the scan is the
 // NT product  T_s[i][k] = sum_j Mt8[i][j] * Bs[s][k][j]  with k-tile ct needing only j < (ct+1)*256 (lower
 // triangular image).  The row-dot with m_ik is fused into the tile epilogue.
+// k_vara_i8p reads the same sum over unordered pairs from the other side, q_s[i] = sum_k m_ik sum_{j>k} m_ij D_s[k][j]: its image is
+// Bs[s][k][j] = D_s[k][j] (k_slice_w, `lower`), k-tile ct needs j >= ct*256, and the zero rows of pad256(n) sit at the END of every
+// K loop, where whole stages of them are left out (klive).
 //
 // Work decomposition.  A marker tile (256 markers) is served by S workgroups, one per digit slice ("workers").  Every
 // worker walks the same sequence of column-tile pairs {p, nct-1-p} (each pair costs (nct+1)*2 stages) and the same k
@@ -168,23 +171,34 @@ __global__ __launch_bounds__(256) void k_absmax_offdiag(const double* __restrict
 // bits, for any input); everything downstream -- per-marker flagging, fp64 re-evaluation of the candidates -- is unchanged.
 #define VARA_HOEFFDING_K 8.355  /* sqrt(ln(2 / 1e-30)) */
 // One block: dW[k] = Wu[k][k] (contiguous copy), sumdiag in a fixed order, then the slice count (forced = 1..8: that S).
+// klive (k_slice_w) gets its first value here, from row 0.
 __global__ __launch_bounds__(256) void k_vara_prep(const double* __restrict__ Wu, long n_pad, int forced_arg, VaraHdr* __restrict__ hdr,
-                                                   double* __restrict__ dW, double budget, double wErr, double tight) {
+                                                   double* __restrict__ dW, double budget, double wErr, double tight, int* __restrict__ klive) {
     const int forced = forced_arg & 0xff, stochastic = (forced_arg & EAGLE_SLICES_STOCHASTIC) ? 1 : 0;
     double s = 0.0;
+    int jlast = 0;   // the last non-zero off-diagonal entry of row 0
     for (long k = threadIdx.x; k < n_pad; k += 256) {
         double d = Wu[k * n_pad + k];
         dW[k] = d;
         s += fabs(d);
+        if (k > 0 && Wu[k] != 0.0) jlast = (int)k;
     }
     __shared__ double red[256];
+    __shared__ int jred[256];
     red[threadIdx.x] = s;
+    jred[threadIdx.x] = jlast;
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        if (threadIdx.x < o) {
+            red[threadIdx.x] += red[threadIdx.x + o];
+            jred[threadIdx.x] = max(jred[threadIdx.x], jred[threadIdx.x + o]);
+        }
         __syncthreads();
     }
     if (threadIdx.x == 0) {
+        // k_slice_w's live-stage count starts from what row 0 alone shows (the final value for a dense W): the tiles of the first wave
+        // of workgroups would otherwise all find the zero of the memset and send their atomics to the one address at once
+        if (jred[0] > 0) *klive = jred[0] / BK8 + 1;
         const double mx = hdr->maxabs_off;
         const int e = w_scale_exp(mx);
         const double nn = (double)n_pad * (double)n_pad;
@@ -522,13 +536,41 @@ __global__ __launch_bounds__(256) void k_spectral_decide(const unsigned long lon
 // Ds (optional; round to nearest only): the symmetric image of the LAST digit for the spectral bound, Ds[i][j] = last digit of
 // Wu[min(i,j)][max(i,j)], 0 on the diagonal -- written from the upper tiles (bj <= bk), each of which holds both mirrored blocks of it,
 // unless every slot of the slice area holds a digit in use (S = smax: no spare one, the spectral bound is not tried).
+// lower (with perm128 only): the image k_vara_i8p walks from the diagonal DOWN, Bs[s][crow(k)][j] = digit s of Wu[k][j] for j > k and
+// zero elsewhere -- the untransposed read of the tile; the same entries, the same digits (the rounding key is the entry's position in
+// Wu either way), each unordered pair in the row of its smaller index instead of its larger one.  A tile below the diagonal is zero
+// in that image whatever Wu holds there: it is not read.
+// klive: the live K stages of that walk, raised to (largest j with a non-zero Wu[k][j], k < j) / 128 + 1 from the upper tiles, whichever
+// layout is written -- a function of W alone.  One thread of a block looks first and only a larger value goes to the atomic (as
+// k_w8_combine2; a look per wave instead of per block: +0.08 ms at n_pad = 10,240, profiles/r20_live_k.json).
 __global__ __launch_bounds__(256) void k_slice_w(const double* __restrict__ Wu, long np, const VaraHdr* __restrict__ hdr,
-                                                 int8_t* __restrict__ Bs, int perm128, int8_t* __restrict__ Ds, int smax) {
+                                                 int8_t* __restrict__ Bs, int perm128, int lower, int8_t* __restrict__ Ds, int smax,
+                                                 int* __restrict__ klive) {
     __shared__ double tile[32][33];
+    __shared__ unsigned wcols[4];
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     const long bj = (long)blockIdx.y * 32, bk = (long)blockIdx.x * 32;
-    for (int r = ty; r < 32; r += 8) tile[r][tx] = Wu[(bj + r) * np + bk + tx];  // tile[jj][kk]
+    bool any = false;
+    int seen = 0;   // the look, sent ahead of the tile's loads (a stale one costs an atomic that changes nothing, never the maximum)
+    if (bj <= bk && threadIdx.x == 0) seen = __hip_atomic_load(klive, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (!lower || bj <= bk)
+        for (int r = ty; r < 32; r += 8) {
+            const double w = Wu[(bj + r) * np + bk + tx];
+            tile[r][tx] = w;  // tile[jj][kk]
+            any |= bj + r < bk + tx && w != 0.0;
+        }
+    if (bj <= bk) {
+        const unsigned long long bal = __ballot(any);
+        if ((threadIdx.x & 63) == 0) wcols[threadIdx.x >> 6] = (unsigned)bal | (unsigned)(bal >> 32);
+    }
     __syncthreads();
+    if (bj <= bk && threadIdx.x == 0) {
+        const unsigned cols = wcols[0] | wcols[1] | wcols[2] | wcols[3];   // bit tx: column bk + tx holds a non-zero entry above the diagonal
+        if (cols) {
+            const int kl = (int)((bk + 31 - __builtin_clz(cols)) / BK8) + 1;
+            if (kl > seen) atomicMax(klive, kl);
+        }
+    }
     const int e = hdr->e;   // w_scale_exp: mx < 2^e, or mx < 1.96 * 2^e when the mantissa leaves room
     const int nslices = hdr->S;
     if (Ds && bj <= bk && hdr->S_sliced < smax) {
@@ -546,15 +588,17 @@ __global__ __launch_bounds__(256) void k_slice_w(const double* __restrict__ Wu, 
         }
     }
     for (int r = ty; r < 32; r += 8) {
-        // output element (k = bk + r, j = bj + tx):  Q = round(Wu * 2^(8S - e - 2)) is an exact integer below 0.49 * 256^S + 1
+        // output element (k = bk + r, j = bj + tx) = Wu[j][k]; lower: (k = bj + r, j = bk + tx) = Wu[k][j], the entries above the diagonal
+        // only.  Q = round(Wu * 2^(8S - e - 2)) is an exact integer below 0.49 * 256^S + 1
         // (llrint of a double of that size is exact); its balanced base-256 digits, least significant first,
         // d = ((Q + 128) mod 256) - 128 in [-128,127], Q <- (Q - d)/256; the leading digit ends in [-126,126].
+        const long wrow = lower ? bj + r : bj + tx, wcol = lower ? bk + tx : bk + r;   // the entry of Wu
         long long Q = 0;
-        if (bk + r != bj + tx) {
-            const double yv = ldexp(tile[tx][r], 8 * nslices - (e + 2));
+        if (lower ? wrow < wcol : wrow != wcol) {
+            const double yv = ldexp(lower ? tile[r][tx] : tile[tx][r], 8 * nslices - (e + 2));
             if (hdr->pad) {  // unbiased random rounding, keyed by the entry's position (see VARA_HOEFFDING_K above)
                 const double fl = floor(yv);
-                unsigned long long z = (unsigned long long)((bj + tx) * np + bk + r) + 0x9E3779B97F4A7C15ULL;  // splitmix64
+                unsigned long long z = (unsigned long long)(wrow * np + wcol) + 0x9E3779B97F4A7C15ULL;  // splitmix64
                 z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
                 z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
                 z ^= z >> 31;
@@ -568,13 +612,13 @@ __global__ __launch_bounds__(256) void k_slice_w(const double* __restrict__ Wu, 
                 Q = llrint(yv);
             }
         }
-        const long c = bk + r;
+        const long c = lower ? bj + r : bk + r;
         const long c7 = c & 127, cx = c7 & 15;
         const long crow = perm128 ? (c & ~127L) | (((c7 >> 4) & 3) << 5) | ((cx >> 2) << 3) | (cx & 3) | ((c7 >> 6) << 2) : c;
         for (int s = nslices - 1; s >= 0; s--) {
             long long d = ((Q + 128) & 255) - 128;
             Q = (Q - d) >> 8;
-            Bs[(long)s * np * np + crow * np + bj + tx] = (int8_t)d;
+            Bs[(long)s * np * np + crow * np + (lower ? bk : bj) + tx] = (int8_t)d;
         }
     }
 }
@@ -706,17 +750,23 @@ __global__ __launch_bounds__(1024) void k_rho_final(long np, const double* __res
     if (threadIdx.x == 0) hdr->R = 0.5 * red[0];
 }
 
-struct VaraIt {  // position in a worker's flattened stage sequence: pair p, half (tile p, then tile nct-1-p), stage kt
+struct VaraIt {  // position in a worker's flattened stage sequence: pair p, half (tile p, then tile nct-1-p), stage kt of [.., nk)
     int p, half, ct, kt, nk;
     bool valid;
+    // k_vara_i8p on the lower image of k_slice_w: column tile ct runs the stages [2 ct, max(klive, 2 ct + 2)) -- from its diagonal block
+    // down to the last live stage of W, never fewer than two (the diagonal block itself).  klive <= n_pad / 128 by its rule.  A pair
+    // (p, nct-1-p) costs 2 klive - 2 (nct - 1) stages whatever p, apart from that floor.
+    bool lower = false;
+    int klive = 0;
 };
 __device__ __forceinline__ void vit_set_tile(VaraIt& it, int nct, int npair) {
     while (it.p < npair) {
         int ct = it.half == 0 ? it.p : nct - 1 - it.p;
         if (it.half == 1 && ct == it.p) { it.p++; it.half = 0; continue; }  // middle tile of an odd nct: once only
         it.ct = ct;
-        it.kt = 0;
+        it.kt = it.lower ? (T8 / BK8) * ct : 0;
         it.nk = (T8 / BK8) * (ct + 1);
+        if (it.lower && it.klive > it.nk) it.nk = it.klive;
         it.valid = true;
         return;
     }
@@ -989,7 +1039,7 @@ __global__ __launch_bounds__(512, 2) void k_vara_i8w(const int8_t* __restrict__ 
 template <bool PACE, bool EXT = false>
 __global__ __launch_bounds__(512, 2) void k_vara_i8p(const int8_t* __restrict__ Mt8, long ld, int ntm, const int8_t* __restrict__ Bs,
                                                      long np, const VaraHdr* __restrict__ hdr, long long* __restrict__ q, long Lp, int cut_last_round,
-                                                     int* __restrict__ pace) {
+                                                     int* __restrict__ pace, const int* __restrict__ klive) {
     extern __shared__ __attribute__((aligned(1024))) int8_t ldsv[];  // [2][A 48 KiB | B 32 KiB]
     const int b = blockIdx.x;
     const int xcd = b & 7, slot = b >> 3;
@@ -1016,6 +1066,8 @@ __global__ __launch_bounds__(512, 2) void k_vara_i8p(const int8_t* __restrict__ 
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)(Mt8 + row0 * ld), 0, (int)(rows_here * ld), 0x00020000);
 
     VaraIt cur, nxt;
+    cur.lower = klive != nullptr;   // the lower image and its walk (VaraIt); NULL: the upper one, every tile from stage 0 (tune 34)
+    cur.klive = cur.lower ? min(*klive, (T8 / BK8) * nct) : 0;   // (k_slice_w never counts past n_pad / 128)
     cur.p = pair0; cur.half = 0; vit_set_tile(cur, nct, pair1);
     if (!cur.valid) return;
     nxt = cur;
@@ -1071,7 +1123,7 @@ __global__ __launch_bounds__(512, 2) void k_vara_i8p(const int8_t* __restrict__ 
         tx_klast(c, fa[1], fa[0], fb, offA + buf * STG + ch[0], offB + buf * STG + ch[0], dA);
     };
     while (cur.valid) {
-        const int done_ct = cur.ct, nk = cur.nk;  // nk >= 2
+        const int done_ct = cur.ct, nk = cur.nk - cur.kt;  // nk >= 2
         if (PACE && pace_row && cur.half == 0) {
             if (t == 0) {
                 int* cnt = pace_row + cur.p;
@@ -1087,7 +1139,7 @@ __global__ __launch_bounds__(512, 2) void k_vara_i8p(const int8_t* __restrict__ 
             tx_kstep<false, 1>(c, fa[0], fa[1], fb, offA + buf * STG + ch[1], offB + buf * STG + ch[1], dA, dB);
             stage_rest();
         }
-        cur.kt = nk - 1;
+        cur.kt = cur.nk - 1;
         vit_advance(cur, nct, pair1);
         {
             // the MFMAs above are opaque to the compiler's hazard recogniser: let the last ones retire before the accumulators are
@@ -1704,6 +1756,12 @@ static int vara_i8_check(eagle_ctx* ctx, long L_pad, long n_pad, long ld, int ns
 // below 65,536 padded individuals unless a tune switch asks for one of the others (tools/bench_vara.py: 8 = the 256 x 256 form,
 // 9 = the compiler-scheduled 384 x 256 form).
 static bool vara_piped(const eagle_ctx* ctx, long n_pad) { return ctx->tune != 8 && ctx->tune != 9 && n_pad < 65536; }
+// ... and which way it walks the triangle: from each column tile's diagonal block down to the last live stage of W (the lower image of
+// k_slice_w) unless tune 34 asks for the upper image and every tile from stage 0 -- like the layout, decided at prepare.
+static bool vara_lower(const eagle_ctx* ctx, long n_pad) { return vara_piped(ctx, n_pad) && ctx->tune != 34; }
+// the live-stage count of W, in the spare bytes behind the header: zeroed with it, kept across the marker blocks of a streamed scan
+static int* ws_klive(void* ws) { return (int*)((char*)ws + 128); }
+static_assert(sizeof(VaraHdr) <= 128, "klive sits behind the header");
 
 // part 0: everything (one block = the whole scan).  A scan that walks several marker blocks of the SAME L_pad through one workspace
 // (a streamed file) does the W-dependent work once -- part 1: header, digits of W, rho; 4 n_pad^2 S bytes written -- and per block
@@ -1739,7 +1797,7 @@ static int vara_i8_prepare_impl(eagle_ctx* ctx, const int8_t* Mt8, const void* M
             if (e != hipSuccess) return eagle_fail_hip(ctx, e, "vara_i8 maxabs copy");
         } else
             hipLaunchKernelGGL(k_absmax_offdiag, dim3(1024), dim3(256), 0, s, Wu, n_pad, (unsigned long long*)&hdr->maxabs_off);
-        hipLaunchKernelGGL(k_vara_prep, dim3(1), dim3(256), 0, s, Wu, n_pad, nslices, hdr, dW, ctx->scan_budget, w8 ? ctx->w8_eta : 0.0, ctx->scan_budget_tight);
+        hipLaunchKernelGGL(k_vara_prep, dim3(1), dim3(256), 0, s, Wu, n_pad, nslices, hdr, dW, ctx->scan_budget, w8 ? ctx->w8_eta : 0.0, ctx->scan_budget_tight, ws_klive(ws));
         // correction terms of the re-centred markers: rho and R from Wu, m^T rho from the genotype pass
         double* colpart = (double*)((char*)ws + ws_cp_off(n_pad, L_pad, smax));
         if (w8) {
@@ -1762,8 +1820,8 @@ static int vara_i8_prepare_impl(eagle_ctx* ctx, const int8_t* Mt8, const void* M
     if (part != 2) {
         dim3 g2((unsigned)(n_pad / 32), (unsigned)(n_pad / 32));
         const bool spectral = nslices == 0 && !ctx->spectral_off && ctx->tune != 29;
-        hipLaunchKernelGGL(k_slice_w, g2, dim3(256), 0, s, Wu, n_pad, hdr, Bs, vara_piped(ctx, n_pad) ? 1 : 0,
-                           spectral ? Bs + (size_t)(smax - 1) * n_pad * n_pad : (int8_t*)nullptr, smax);
+        hipLaunchKernelGGL(k_slice_w, g2, dim3(256), 0, s, Wu, n_pad, hdr, Bs, vara_piped(ctx, n_pad) ? 1 : 0, vara_lower(ctx, n_pad) ? 1 : 0,
+                           spectral ? Bs + (size_t)(smax - 1) * n_pad * n_pad : (int8_t*)nullptr, smax, ws_klive(ws));
         // one digit fewer if the spectral bound of the last digit allows it (automatic digit count, round to nearest): the last digit's
         // symmetric image goes into the spare slot of the slice area (at most 6 of the 7 are in use), the row sums into the column
         // partials of rho (free again after k_rho_final)
@@ -1822,8 +1880,9 @@ extern "C" int eagle_dev_vara_i8_prepare_packed(eagle_ctx* ctx, const void* Mt2,
 }
 
 // The int8 MFMA kernel over all (marker tile, slice) workers of an image: q[s][i] += ... for the hdr->S slices at Bs (grid sized for smax).
+// klive: the workspace's live-stage count (ws_klive), for the compact image of the extension too -- its second header holds none.
 static int vara_i8_launch(eagle_ctx* ctx, const int8_t* Mt8s, long L_pad, long n_pad, long ld, int smax, const VaraHdr* hdr, const int8_t* Bs,
-                          long long* q, hipStream_t s, bool ext = false) {
+                          long long* q, const int* klive, hipStream_t s, bool ext = false) {
     const int ntm = (int)(L_pad / T8);
     const int groups = (ntm + 7) / 8;
     if (!ctx->attr_vara_i8) {  // per device: a second ctx on another GPU must set it again
@@ -1840,7 +1899,8 @@ static int vara_i8_launch(eagle_ctx* ctx, const int8_t* Mt8s, long L_pad, long n
         // paced workers (a soft barrier per column-tile pair, round 3's tune 14): 1 % slower at n_pad = 10,240, where the L2 serves 68-72 % of
         // the stage fills anyway, 3.3 % FASTER at n_pad = 50,176, where the unpaced workers drift apart over the 5x longer K loops and the hit
         // rate falls to 53 % (profiles/r04_rocprof_C4, r04_vara_pace_50k.txt): on from 32,768 padded individuals up; same integer sums either way
-        const bool pace = piped && !ext && (ctx->tune == 14 || (ctx->tune == 0 && n_pad >= 32768));
+        const bool pace = piped && !ext && (ctx->tune == 14 || ((ctx->tune == 0 || ctx->tune == 34) && n_pad >= 32768));
+        const int* kl = vara_lower(ctx, n_pad) ? klive : (const int*)nullptr;
         const bool px = piped && ext;
         const void* kfn = !piped ? (const void*)k_vara_i8w
                                  : (pace ? (const void*)k_vara_i8p<true> : (px ? (const void*)k_vara_i8p<false, true> : (const void*)k_vara_i8p<false>));
@@ -1855,8 +1915,8 @@ static int vara_i8_launch(eagle_ctx* ctx, const int8_t* Mt8s, long L_pad, long n
         const dim3 gridw((unsigned)(8 * (gw * smax + 31 * VARA_TAIL_PMAX)));
         const int cut = ctx->tune == 7 ? 0 : 1;
         if (!piped) hipLaunchKernelGGL(k_vara_i8w, gridw, dim3(512), 2 * (TW_ABYTES + TILE_BYTES), s, Mt8s, ld, ntw, Bs, n_pad, hdr, q, L_pad, cut);
-        else if (px) hipLaunchKernelGGL((k_vara_i8p<false, true>), gridw, dim3(512), 2 * (TW_ABYTES + TILE_BYTES), s, Mt8s, ld, ntw, Bs, n_pad, hdr, q, L_pad, cut, (int*)nullptr);
-        else if (!pace) hipLaunchKernelGGL(k_vara_i8p<false>, gridw, dim3(512), 2 * (TW_ABYTES + TILE_BYTES), s, Mt8s, ld, ntw, Bs, n_pad, hdr, q, L_pad, cut, (int*)nullptr);
+        else if (px) hipLaunchKernelGGL((k_vara_i8p<false, true>), gridw, dim3(512), 2 * (TW_ABYTES + TILE_BYTES), s, Mt8s, ld, ntw, Bs, n_pad, hdr, q, L_pad, cut, (int*)nullptr, kl);
+        else if (!pace) hipLaunchKernelGGL(k_vara_i8p<false>, gridw, dim3(512), 2 * (TW_ABYTES + TILE_BYTES), s, Mt8s, ld, ntw, Bs, n_pad, hdr, q, L_pad, cut, (int*)nullptr, kl);
         else {
             // counters [8 XCDs][rounds][pairs], zeroed per launch, in the ctx's GEMM scratch (free during the scan)
             const size_t need = sizeof(int) * 8 * (size_t)((gw * smax + 31) / 32 + 1) * (size_t)((n_pad / T8 + 1) / 2);
@@ -1868,7 +1928,7 @@ static int vara_i8_launch(eagle_ctx* ctx, const int8_t* Mt8s, long L_pad, long n
             }
             hipError_t ea = hipMemsetAsync(ctx->gemm_scratch, 0, need, s);
             if (ea != hipSuccess) return eagle_fail_hip(ctx, ea, "pace counters memset");
-            hipLaunchKernelGGL(k_vara_i8p<true>, gridw, dim3(512), 2 * (TW_ABYTES + TILE_BYTES), s, Mt8s, ld, ntw, Bs, n_pad, hdr, q, L_pad, cut, (int*)ctx->gemm_scratch);
+            hipLaunchKernelGGL(k_vara_i8p<true>, gridw, dim3(512), 2 * (TW_ABYTES + TILE_BYTES), s, Mt8s, ld, ntw, Bs, n_pad, hdr, q, L_pad, cut, (int*)ctx->gemm_scratch, kl);
         }
     } else
     hipLaunchKernelGGL(k_vara_i8, dim3((unsigned)(groups * 8 * smax)), dim3(512), 5 * TILE_BYTES, s, Mt8s, ld, ntm, Bs, n_pad, hdr, q, L_pad);
@@ -1890,7 +1950,7 @@ extern "C" int eagle_dev_vara_i8_mfma_shifted(eagle_ctx* ctx, const int8_t* Mt8s
     double* vdiag = (double*)((char*)ws + ws_vd_off(n_pad, L_pad, smax));
     double* mrho = (double*)((char*)ws + ws_mr_off(n_pad, L_pad, smax));
     int8_t* Bs = (int8_t*)((char*)ws + ws_bs_off(n_pad, L_pad, smax));
-    rc = vara_i8_launch(ctx, Mt8s, L_pad, n_pad, ld, smax, hdr, Bs, q, s);
+    rc = vara_i8_launch(ctx, Mt8s, L_pad, n_pad, ld, smax, hdr, Bs, q, ws_klive(ws), s);
     if (rc) return rc;
     hipLaunchKernelGGL(k_vara_i8_finish, dim3((unsigned)((L_pad + 255) / 256)), dim3(256), 0, s, q, L_pad, hdr, vdiag, cshift, mrho, vara_out);
     if (err_bound_dev) hipLaunchKernelGGL(k_vara_i8_bound, dim3(1), dim3(1), 0, s, hdr, err_bound_dev, (int*)nullptr);
@@ -2008,7 +2068,7 @@ extern "C" int eagle_dev_vara_i8_extend(eagle_ctx* ctx, const int8_t* Mt8s, cons
         hipLaunchKernelGGL(k_ext_head, dim3(1), dim3(64), 0, s, hdr, xh, flag, idx, (int)cap, spare);
         if (pass == 0) hipLaunchKernelGGL(k_ext_copy_slice, dim3(1024), dim3(256), 0, s, xh, hdr, Bs, n_pad * n_pad, spare);
         hipLaunchKernelGGL(k_ext_gather, dim3((unsigned)cap), dim3(256), 0, s, Mt8s, ld, n_pad, xh, idx, Xc, qc);
-        rc = vara_i8_launch(ctx, Xc, cap, n_pad, n_pad, 1, &xh->h2, Bs + (size_t)spare * n_pad * n_pad, qc, s, true);
+        rc = vara_i8_launch(ctx, Xc, cap, n_pad, n_pad, 1, &xh->h2, Bs + (size_t)spare * n_pad * n_pad, qc, ws_klive(ws), s, true);
         if (rc) return rc;
         hipLaunchKernelGGL(k_ext_apply, dim3(64), dim3(256), 0, s, xh, idx, qc, q, L_pad, hdr, vdiag, cshift, mrho, vara);
     }
