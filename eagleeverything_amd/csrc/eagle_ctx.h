@@ -229,6 +229,17 @@ extern "C" int eagle_dev_marker_counts(eagle_ctx* ctx, const int8_t* Mt8, long r
 extern "C" int eagle_dev_bed_marker_counts(eagle_ctx* ctx, const uint8_t* bed, long rows, long n, int32_t* counts, void* stream);
 extern "C" int eagle_dev_gather_rows_i8(eagle_ctx* ctx, const int8_t* src, long ld_src, const int32_t* map, long nrows, long rows_out,
                                         int8_t* out, long ld_out, void* stream);
+// Per-group counts (eagle_groups.hip; include/eagle_hip.h section 1b''''iii), device pointers throughout.  labels[n] in [-1, K) (the CALLER's
+// check), sizes[K] = the individuals per group.  onehot: 64 x ld int8, byte (k, i) = 1 iff labels[i] == k; counts[rows][K][3] = (n0, n1,
+// n2) of an int8 Mt tile per group.  planes: K x ceil(ceil(n/4) / 4) dwords, bit 2q of byte b of plane k set iff individual 4b + q is in
+// group k; counts[rows][K][4] = (hom A1, het, hom A2, missing) of raw .bed rows per group.  p[L] = Fisher's exact test of tables[L][4].
+extern "C" int eagle_dev_group_onehot(eagle_ctx* ctx, const int32_t* labels, long n, int8_t* onehot, long ld, void* stream);
+extern "C" int eagle_dev_group_counts(eagle_ctx* ctx, const int8_t* Mt8, long rows, long n, long ld, const int8_t* onehot, long ld_onehot, int K,
+                                      const int32_t* sizes, int32_t* counts, void* stream);
+extern "C" int eagle_dev_group_bedmask(eagle_ctx* ctx, const int32_t* labels, long n, int K, uint32_t* planes, void* stream);
+extern "C" int eagle_dev_bed_group_counts(eagle_ctx* ctx, const uint8_t* bed, long rows, long n, int K, const uint32_t* planes, const int32_t* sizes,
+                                          int32_t* counts, void* stream);
+extern "C" int eagle_dev_fisher_2x2(eagle_ctx* ctx, const int32_t* tables, long L, double* p, void* stream);
 // Sample QC.  eagle_qc.hip: counts[n][4] (hom A1, het, hom A2, missing per INDIVIDUAL; zeroed by the caller before a file's first
 // window) += the counts over `rows` raw .bed rows; ibs0 / hethet (n x n int32, full and symmetric) from the Gram accumulators D32, Q32
 // (n_pad x n_pad, upper 256-tiles live) and the marker count L; p[L] = the Hardy-Weinberg exact test of counts[L][stride] (stride 3

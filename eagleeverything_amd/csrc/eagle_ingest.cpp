@@ -957,6 +957,143 @@ extern "C" int eagle_bed_marker_counts(eagle_ctx* ctx, const char* bed_path, con
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// Per-group genotype counts and Fisher's exact test (include/eagle_hip.h section 1b''''iii; kernels in eagle_groups.hip)
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+
+// The argument errors the two counting entry points share, decided without a context; sizes[k] = the individuals of group k.
+int group_args(eagle_ctx* ctx, const char* who, const void* path, const long* dims, const int32_t* labels, int K, const void* out,
+               int32_t sizes[EAGLE_GROUPS_MAX]) {
+    char msg[160];
+    auto fail = [&](const char* what) {
+        snprintf(msg, sizeof msg, "%s: %s", who, what);
+        return qc_fail(ctx, EAGLE_ERR_ARG, msg);
+    };
+    if (!path || !dims || !labels || !out) return fail("NULL argument");
+    const long n = dims[0], L = dims[1];
+    if (n <= 0 || L <= 0) return fail("dims must be positive");
+    if (n > 0x3fffffffL) return fail("more than 2^30 - 1 individuals");
+    if (K < 1 || K > EAGLE_GROUPS_MAX) return fail("K outside [1, 64]");
+    for (int k = 0; k < EAGLE_GROUPS_MAX; k++) sizes[k] = 0;
+    for (long i = 0; i < n; i++) {
+        if (labels[i] < -1 || labels[i] >= K) return fail("a label outside [-1, K)");
+        if (labels[i] >= 0) sizes[labels[i]]++;
+    }
+    if (!ctx) return fail("no context");
+    return EAGLE_OK;
+}
+
+// labels (n int32) and sizes (EAGLE_GROUPS_MAX int32 behind them) on the device
+int group_upload(eagle_ctx* ctx, const int32_t* labels, long n, const int32_t* sizes, DevBuf& d_lab) {
+    HIPCHK(ctx, d_lab.alloc(sizeof(int32_t) * ((size_t)n + EAGLE_GROUPS_MAX)));
+    HIPCHK(ctx, hipMemcpyAsync(d_lab.p, labels, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d_lab.as<int32_t>() + n, sizes, sizeof(int32_t) * EAGLE_GROUPS_MAX, hipMemcpyHostToDevice, ctx->stream));
+    return EAGLE_OK;
+}
+
+}  // namespace
+
+// line_counts' routes: the image is counted where it lies when it is (or can be made) resident, else in the row windows of the
+// streamed scans.  The label operand is built once per call; rows are independent, so every route gives the same integers.
+extern "C" int eagle_group_counts(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long dims[2], const int32_t* labels, int K,
+                                  double max_memory_in_Gbytes, int32_t* counts_out) {
+    int32_t sizes[EAGLE_GROUPS_MAX];
+    if (int arc = group_args(ctx, "group_counts", f_name_ascii_Mt, dims, labels, K, counts_out, sizes)) return arc;
+    const long n = dims[0], L = dims[1];
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int threads = host_threads();
+    const long ldh = (n + 15) / 16 * 16;
+    const size_t per_row = sizeof(int32_t) * 3 * (size_t)K;
+    DevBuf d_lab, onehot, counts;
+    HIPCHK(ctx, onehot.alloc((size_t)EAGLE_GROUPS_MAX * ldh));
+    HIPCHK(ctx, counts.alloc(per_row * (size_t)L));
+    int rc = group_upload(ctx, labels, n, sizes, d_lab);
+    if (rc) return rc;
+    const int32_t* d_sizes = d_lab.as<int32_t>() + n;
+    rc = eagle_dev_group_onehot(ctx, d_lab.as<int32_t>(), n, onehot.as<int8_t>(), ldh, ctx->stream);
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    const GenoEntry* src = nullptr;
+    rc = eagle_get_resident(ctx, f_name_ascii_Mt, L, n, max_memory_in_Gbytes, threads, &src);
+    if (rc != EAGLE_OK && rc != EAGLE_STREAM) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    if (rc == EAGLE_OK) {
+        rc = eagle_dev_group_counts(ctx, src->dev, L, n, src->ld, onehot.as<int8_t>(), ldh, K, d_sizes, counts.as<int32_t>(), ctx->stream);
+        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    } else {
+        const long ld = eagle_pad(n), w = stream_chunk_rows_core(eagle_resident_budget(), ld, eagle_pad(L));
+        DevBuf win;
+        HIPCHK(ctx, win.alloc((size_t)w * ld));
+        for (long r0 = 0; r0 < L; r0 += w) {
+            const long nr = std::min(w, L - r0);
+            HIPCHK(ctx, hipMemsetAsync(win.p, 0, (size_t)w * ld, ctx->stream));
+            rc = eagle_dev_load_ascii(ctx, f_name_ascii_Mt, r0, nr, 0, n, win.as<int8_t>(), ld, max_memory_in_Gbytes, threads);
+            if (!rc)
+                rc = eagle_dev_group_counts(ctx, win.as<int8_t>(), nr, n, ld, onehot.as<int8_t>(), ldh, K, d_sizes,
+                                            counts.as<int32_t>() + 3 * (size_t)K * (size_t)r0, ctx->stream);
+            if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+        }
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // `win` is freed on return: its last kernel has finished
+    }
+    HIPCHK(ctx, hipMemcpyAsync(counts_out, counts.p, per_row * (size_t)L, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return EAGLE_OK;
+}
+
+// eagle_bed_marker_counts' windows through the staging ring; the K mask planes are built once per call.
+extern "C" int eagle_bed_group_counts(eagle_ctx* ctx, const char* bed_path, const long dims[2], const int32_t* labels, int K,
+                                      double max_memory_in_Gbytes, int32_t* counts_out) {
+    int32_t sizes[EAGLE_GROUPS_MAX];
+    if (int arc = group_args(ctx, "bed_group_counts", bed_path, dims, labels, K, counts_out, sizes)) return arc;
+    const long n = dims[0], L = dims[1];
+    BedRing ring;
+    if (int orc = ring.open(ctx, bed_path, n, L)) return orc;
+    const long w = std::min(L, bed_stage_rows(ring.rb, max_memory_in_Gbytes)), nd = (ring.rb + 3) / 4;
+    int rc = ring.ensure(w);
+    if (rc) return rc;
+    const size_t per_row = sizeof(int32_t) * 4 * (size_t)K;
+    DevBuf d_lab, planes, counts;
+    HIPCHK(ctx, planes.alloc(sizeof(uint32_t) * (size_t)K * (size_t)nd));
+    HIPCHK(ctx, counts.alloc(per_row * (size_t)L));
+    rc = group_upload(ctx, labels, n, sizes, d_lab);
+    if (!rc) rc = eagle_dev_group_bedmask(ctx, d_lab.as<int32_t>(), n, K, planes.as<uint32_t>(), ctx->stream);
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    for (long r0 = 0; r0 < L; r0 += w) {
+        const long nr = std::min(w, L - r0);
+        const uint8_t* raw;
+        rc = ring.stage(r0, nr, &raw);
+        if (!rc)
+            rc = eagle_dev_bed_group_counts(ctx, raw, nr, n, K, planes.as<uint32_t>(), d_lab.as<int32_t>() + n,
+                                            counts.as<int32_t>() + 4 * (size_t)K * (size_t)r0, ctx->stream);
+        if (!rc) rc = ring.release();
+        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    }
+    HIPCHK(ctx, hipMemcpyAsync(counts_out, counts.p, per_row * (size_t)L, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return EAGLE_OK;
+}
+
+extern "C" int eagle_fisher_2x2(eagle_ctx* ctx, const int32_t* tables, long L, double* p_out) {
+    if (!tables || !p_out) return qc_fail(ctx, EAGLE_ERR_ARG, "fisher_2x2: NULL argument");
+    if (L <= 0) return qc_fail(ctx, EAGLE_ERR_ARG, "fisher_2x2: the number of tables must be positive");
+    for (long i = 0; i < L; i++) {
+        const int32_t* t = tables + 4 * i;
+        if (t[0] < 0 || t[1] < 0 || t[2] < 0 || t[3] < 0 || (long)t[0] + t[1] + t[2] + t[3] > (1L << 30))
+            return qc_fail(ctx, EAGLE_ERR_ARG, "fisher_2x2: an entry is negative or a table sums to more than 2^30");
+    }
+    if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "fisher_2x2: no context");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    DevBuf dt, dp;
+    const size_t tb = sizeof(int32_t) * 4 * (size_t)L;
+    HIPCHK(ctx, dt.alloc(tb));
+    HIPCHK(ctx, dp.alloc(sizeof(double) * (size_t)L));
+    HIPCHK(ctx, hipMemcpyAsync(dt.p, tables, tb, hipMemcpyHostToDevice, ctx->stream));
+    int rc = eagle_dev_fisher_2x2(ctx, dt.as<int32_t>(), L, dp.as<double>(), ctx->stream);
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    HIPCHK(ctx, hipMemcpyAsync(p_out, dp.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return EAGLE_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // kNN imputation of a .bed file (no counterpart in the reference; kernels in eagle_impute.hip)
 // ---------------------------------------------------------------------------------------------------------------
 extern "C" int eagle_knn_rows(eagle_ctx* ctx, const int32_t* ibs0, const int32_t* hethet, long n, int K, int32_t* nbr_out) {

@@ -2469,3 +2469,325 @@ def EpistasisOfLoci(AMobj, trait, X, geno, availmemGb=8, backend=None, device=0)
     """Every marker against the loci AM() reported, on the conditional residual of the fitted model (am.EpistasisOfLoci)."""
     from . import am
     return am.EpistasisOfLoci(AMobj, trait, X, geno, availmemGb=availmemGb, backend=backend, device=device)
+
+
+# ---- per-group genotype counts, Fst and case/control association (include/eagle_hip.h section 1b''''iii) ----
+def group_labels(values):
+    """One value per individual (population names, numbers, ...) -> (labels int32 (n), names): labels[i] = the position of values[i] in
+    names, the sorted distinct values; None and NaN become -1, in no group."""
+    vals = list(np.asarray(values, dtype=object).ravel())
+    gone = [v is None or (isinstance(v, (float, np.floating)) and math.isnan(v)) for v in vals]
+    kept = {v for v, g in zip(vals, gone) if not g}
+    try:
+        names = sorted(kept)
+    except TypeError:
+        names = sorted(kept, key=str)
+    where = {v: k for k, v in enumerate(names)}
+    return np.array([-1 if g else where[v] for v, g in zip(vals, gone)], dtype=np.int32), names
+
+
+def _group_onehot(labels, K):
+    lv = np.asarray(labels, dtype=np.int64).ravel()
+    H = np.zeros((lv.size, int(K)), dtype=np.int64)
+    idx = np.flatnonzero(lv >= 0)
+    H[idx, lv[idx]] = 1
+    return H
+
+
+def group_counts_host(Mt8, labels, K):
+    """rcpp_api.group_counts restated in numpy: Mt8 = int8 (L, n) of -1 / 0 / +1 (marker-major), labels in [-1, K) -> int32 (L, K, 3).
+    The device's rule: s = sum of g and q = sum of g^2 over a group, n2 = (q + s) / 2, n0 = (q - s) / 2, n1 = size - q."""
+    G = np.asarray(Mt8, dtype=np.int64)
+    H = _group_onehot(labels, K)
+    s, q, size = G @ H, (G * G) @ H, H.sum(axis=0)[None, :]
+    return np.stack([(q - s) // 2, size - q, (q + s) // 2], axis=2).astype(np.int32)
+
+
+def bed_group_counts_host(codes, labels, K):
+    """rcpp_api.bed_group_counts restated in numpy: codes = uint8 (L, n) 2-bit codes (read_bed_codes) -> int32 (L, K, 4) = homozygous
+    A1 (code 0), heterozygous (2), homozygous A2 (3), missing (1) per group."""
+    c = np.asarray(codes)
+    H = _group_onehot(labels, K)
+    return np.stack([(c == v).astype(np.int64) @ H for v in (0, 2, 3, 1)], axis=2).astype(np.int32)
+
+
+def fisher_2x2_host(tables):
+    """rcpp_api.fisher_2x2 restated as a scalar fp64 loop in the order of include/eagle_hip.h section 1b''''iii: the same bits."""
+    out = []
+    for a, b, c, d in np.asarray(tables, dtype=np.int64).reshape(-1, 4).tolist():
+        r1, r2, c1 = a + b, c + d, a + c
+        N = r1 + r2
+        if N == 0:
+            out.append(1.0)
+            continue
+        lo, hi = max(0, c1 - r2), min(r1, c1)
+        x0 = min(max((r1 + 1) * (c1 + 1) // (N + 2), lo), hi)
+
+        def walk(cut):
+            tail = cut >= 0.0
+            total = 1.0 if (not tail or 1.0 <= cut) else 0.0
+            pobs = 1.0 if a == x0 else 0.0
+            p = 1.0
+            for x in range(x0, lo, -1):
+                p = (p * float(x * (r2 - c1 + x))) / float((r1 - x + 1) * (c1 - x + 1))
+                if p == 0.0:
+                    break
+                if x - 1 == a:
+                    pobs = p
+                if not tail or p <= cut:
+                    total = total + p
+            p = 1.0
+            for x in range(x0, hi):
+                p = (p * float((r1 - x) * (c1 - x))) / float((x + 1) * (r2 - c1 + x + 1))
+                if p == 0.0:
+                    break
+                if x + 1 == a:
+                    pobs = p
+                if not tail or p <= cut:
+                    total = total + p
+            return total, pobs
+
+        total, pobs = walk(-1.0)
+        tail, _ = walk(pobs * 1.0000001)
+        out.append(min(1.0, tail / total))
+    return np.array(out, dtype=np.float64)
+
+
+def _group_source(who, geno, bed, include):
+    """(n, L, bed file or None, (n, Lbed), include mask or None): the checks LDScore makes of a .bed source."""
+    n, L, _, _, src_bed, bdims, inc = _ld_stats_source(who, geno, None, bed, include if bed is not None else None)
+    return n, L, src_bed, bdims, inc
+
+
+def GroupCounts(geno, groups, bed=None, include=None, availmemGb=8, device=0):
+    """The genotype counts of every marker of a panel within each group of individuals -> {"counts": int32 (L, K, 3) = (n0, n1, n2)
+    per marker and group -- with bed= (L, K, 4) = (hom A1, het, hom A2, missing) --, "names": the K group names, "labels": int32 (n),
+    "sizes": int64 (K), and "freq", "maf", "het", "call_rate": fp64 (L, K), what marker_stats_from_counts makes of each group's counts}.
+    groups: one value per individual (group_labels: None / NaN = in no group).  The counting runs on the device (rcpp_api.group_counts
+    on geno["asciifileMt"], one pass over the int8 image on the matrix cores; include/eagle_hip.h section 1b''''iii), the arithmetic on
+    the host.  Without `bed` a missing call of the source is a heterozygote, as in MarkerStats; bed = the .bed file (or prefix) the panel
+    was ingested from gives the file's own counts (rcpp_api.bed_group_counts), where missing is missing.  include= (a bool mask or marker
+    indices; with bed= of the FILE's markers, default geno's marker_index) subsets the rows on the host.  HWE(out["counts"][:, k])
+    is the Hardy-Weinberg exact test within group k: with k the controls that is the HWE-in-controls filter."""
+    labels, names = group_labels(groups)
+    n, L, src_bed, bdims, inc = _group_source("GroupCounts", geno, bed, include)
+    if labels.size != n:
+        raise ValueError("GroupCounts: %d group entries for %d genotyped individuals" % (labels.size, n))
+    K = max(len(names), 1)
+    if src_bed is not None:
+        c = rcpp_api.bed_group_counts(src_bed, bdims, labels, K, availmemGb, device=device)
+    else:
+        c = rcpp_api.group_counts(geno["asciifileMt"], (n, L), labels, K, availmemGb, device=device)
+        inc = _bed_include_mask(include, L, "GroupCounts")
+    if inc is not None:
+        c = np.ascontiguousarray(c[inc])
+    out = {"counts": c, "names": names, "labels": labels, "sizes": np.bincount(labels[labels >= 0], minlength=K).astype(np.int64)}
+    per = [marker_stats_from_counts(c[:, k, 0], c[:, k, 1], c[:, k, 2], c[:, k, 3] if c.shape[2] == 4 else None) for k in range(K)]
+    for key in ("freq", "maf", "het", "call_rate"):
+        out[key] = np.stack([p[key] for p in per], axis=1)
+    return out
+
+
+def _fst_windows(L, chrom, pos, window, kb):
+    """Window ids per marker (consecutive from 0, cut at chromosome ends) and their table, or (None, None)."""
+    if window is None and kb is None:
+        return None, None
+    ch = np.zeros(L, dtype=np.int64) if chrom is None else np.asarray(chrom, dtype=np.int64).ravel()
+    if kb is not None:
+        if pos is None:
+            raise ValueError("Fst: kb= needs a map with Chr and Pos entries")
+        width = int(round(float(kb) * 1000.0))
+        if width < 1:
+            raise ValueError("Fst: kb must be at least 0.001")
+        cell = np.asarray(pos, dtype=np.int64).ravel() // width
+    else:
+        if int(window) != window or window < 1:
+            raise ValueError("Fst: window must be a whole number of at least 1 marker")
+        first = np.r_[True, ch[1:] != ch[:-1]]                       # position within the chromosome's run of markers
+        start = np.maximum.accumulate(np.where(first, np.arange(L), 0))
+        cell = (np.arange(L) - start) // int(window)
+    new = np.r_[True, (ch[1:] != ch[:-1]) | (cell[1:] != cell[:-1])]
+    wid = np.cumsum(new) - 1
+    first_m = np.flatnonzero(new)
+    last_m = np.r_[first_m[1:], L] - 1
+    return wid, {"chrom": ch[first_m], "first": first_m, "last": last_m}
+
+
+def _ratio_of_sums(num, den, wid):
+    """sum num / sum den over the markers where both are finite; per window when wid is given."""
+    ok = np.isfinite(num) & np.isfinite(den)
+    nu, de = np.where(ok, num, 0.0), np.where(ok, den, 0.0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if wid is None:
+            return np.float64(nu.sum()) / np.float64(de.sum())
+        nw = int(wid[-1]) + 1
+        return np.bincount(wid, weights=nu, minlength=nw) / np.bincount(wid, weights=de, minlength=nw)
+
+
+def fst_from_counts(counts, method="hudson", chrom=None, pos=None, window=None, kb=None):
+    """Fst from per-group genotype counts alone: counts = integer (L, K, 3) or (L, K, 4) (the first three columns are the called
+    genotypes 0 / 1 / 2; p = the frequency of the allele coded 2 among them).  All integer sub-expressions are formed exactly in int64
+    (exact for panels of up to 2^30 individuals, the limit of the C ABI), then as few fp64 operations as the formula needs.
+
+    method="hudson" (Bhatia et al. 2013), per pair of groups with allele counts x_k of a_k = 2 called_k:  num = (p1 - p2)^2 -
+    p1 (1 - p1) / (a1 - 1) - p2 (1 - p2) / (a2 - 1),  den = p1 (1 - p2) + p2 (1 - p1)  ->  {"pairs": (P, 2) group indices, "num", "den",
+    "fst": fp64 (L, P) = num / den, "genome": fp64 (P) = sum num / sum den (the ratio of sums), "matrix": fp64 (K, K) of the latter}.
+    method="wc" (Weir and Cockerham 1984) over all r = K groups, n_i called individuals, h_i the observed heterozygote frequency:
+    the variance components a, b, c  ->  {"a", "b", "c", "theta": a / (a + b + c), "fis": 1 - c / (b + c): fp64 (L), "genome" =
+    sum a / sum (a + b + c), "genome_fis" = 1 - sum c / sum (b + c)}.
+    A marker where a group has fewer than 2 called individuals, or whose denominator is zero, is NaN and is left out of every sum.
+    window= (markers) or kb= (with pos) adds "windows": {"chrom", "first", "last" (marker indices), "fst" / "theta"}: the ratio of sums per
+    window, windows cut at chromosome ends."""
+    c = np.asarray(counts).astype(np.int64)
+    if c.ndim != 3 or c.shape[2] not in (3, 4) or c.shape[1] < 2:
+        raise ValueError("fst_from_counts: counts must be (L, K >= 2, 3 or 4)")
+    L, K = c.shape[0], c.shape[1]
+    called = c[:, :, 0] + c[:, :, 1] + c[:, :, 2]                    # n_k
+    x = 2 * c[:, :, 2] + c[:, :, 1]                                  # copies of the allele coded 2
+    a = 2 * called
+    wid, wtab = _fst_windows(L, chrom, pos, window, kb)
+    f = np.float64
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if method == "hudson":
+            pairs = np.array([(i, j) for i in range(K) for j in range(i + 1, K)], dtype=np.int64)
+            num, den = np.full((L, len(pairs)), np.nan), np.full((L, len(pairs)), np.nan)
+            for t, (i, j) in enumerate(pairs):
+                x1, x2, a1, a2 = x[:, i], x[:, j], a[:, i], a[:, j]
+                ok = (called[:, i] >= 2) & (called[:, j] >= 2)
+                aa = (a1 * a2).astype(f)
+                diff = (x1 * a2 - x2 * a1).astype(f) / aa                                    # p1 - p2
+                w1 = (x1 * (a1 - x1)).astype(f) / ((a1 * a1).astype(f) * (a1 - 1).astype(f))     # p1 (1 - p1) / (a1 - 1)
+                w2 = (x2 * (a2 - x2)).astype(f) / ((a2 * a2).astype(f) * (a2 - 1).astype(f))
+                dint = x1 * (a2 - x2) + x2 * (a1 - x1)
+                ok &= dint != 0
+                num[:, t] = np.where(ok, diff * diff - w1 - w2, np.nan)
+                den[:, t] = np.where(ok, dint.astype(f) / aa, np.nan)
+            out = {"pairs": pairs, "num": num, "den": den, "fst": num / den,
+                   "genome": np.array([_ratio_of_sums(num[:, t], den[:, t], None) for t in range(len(pairs))])}
+            M = np.zeros((K, K))
+            M[pairs[:, 0], pairs[:, 1]] = M[pairs[:, 1], pairs[:, 0]] = out["genome"]
+            out["matrix"] = M
+            if wid is not None:
+                out["windows"] = dict(wtab, fst=np.stack([_ratio_of_sums(num[:, t], den[:, t], wid) for t in range(len(pairs))], axis=1))
+            return out
+        if method != "wc":
+            raise ValueError("fst_from_counts: method must be \"hudson\" or \"wc\"")
+        r = K
+        T, X, H = called.sum(axis=1), x.sum(axis=1), c[:, :, 1].sum(axis=1)
+        ok = np.all(called >= 2, axis=1)
+        Tf = T.astype(f)
+        nbar = Tf / r
+        nc = (Tf - (called * called).sum(axis=1).astype(f) / Tf) / (r - 1)
+        pbar = X.astype(f) / (2 * T).astype(f)
+        hbar = H.astype(f) / Tf
+        dev = (x * T[:, None] - X[:, None] * called).astype(f) / (2 * T).astype(f)[:, None]      # n_i (p_i - pbar)
+        s2 = (dev * dev / called.astype(f)).sum(axis=1) / ((r - 1) * nbar)
+        pq = (X * (2 * T - X)).astype(f) / ((2 * T).astype(f) * (2 * T).astype(f))                # pbar (1 - pbar)
+        rr = (r - 1) / f(r)
+        va = (nbar / nc) * (s2 - (pq - rr * s2 - hbar / 4) / (nbar - 1))
+        vb = (nbar / (nbar - 1)) * (pq - rr * s2 - ((2 * nbar - 1) / (4 * nbar)) * hbar)
+        vc = hbar / 2
+        tot = va + vb + vc
+        ok &= (nc != 0) & (tot != 0)
+        va, vb, vc, tot = (np.where(ok, v, np.nan) for v in (va, vb, vc, tot))
+        bc = vb + vc
+        out = {"a": va, "b": vb, "c": vc, "theta": va / tot, "fis": 1.0 - vc / bc, "genome": _ratio_of_sums(va, tot, None),
+               "genome_fis": 1.0 - _ratio_of_sums(vc, bc, None)}
+        if wid is not None:
+            out["windows"] = dict(wtab, theta=_ratio_of_sums(va, tot, wid), fis=1.0 - _ratio_of_sums(vc, bc, wid))
+        return out
+
+
+def Fst(geno, groups, method="hudson", bed=None, map=None, window=None, kb=None, availmemGb=8, device=0):
+    """Fst between the groups of individuals of a panel, per marker and genome-wide -> fst_from_counts' dict (see there for the two
+    estimators, Hudson per pair of groups and Weir-Cockerham over all of them, and the NaN rule) plus "names", the group names.  It
+    works from GroupCounts' integer counts alone (one pass over the image on the device); bed= counts called genotypes only.
+    map (ReadBim's dict) with window= (markers) or kb= adds per-window ratios of sums, cut at chromosome ends."""
+    chrom = pos = None
+    if map is not None:
+        _, _, chrom, pos, _, _, _ = _ld_stats_source("Fst", geno, map, None, None)
+    elif kb is not None:
+        raise ValueError("Fst: kb= needs a map with Chr and Pos entries")
+    gc = GroupCounts(geno, groups, bed=bed, availmemGb=availmemGb, device=device)
+    if len(gc["names"]) < 2:
+        raise ValueError("Fst: at least two groups are needed")
+    out = fst_from_counts(gc["counts"], method=method, chrom=chrom, pos=pos, window=window, kb=kb)
+    out["names"] = gc["names"]
+    return out
+
+
+def _chi2_2x2(a, b, c, d):
+    """Pearson's chi-square of the 2 x 2 tables (a, b; c, d), int64 arrays: N (ad - bc)^2 / (r1 r2 c1 c2); a zero margin gives NaN."""
+    f = np.float64
+    N, m1, m2 = a + b + c + d, (a + b) * (c + d), (a + c) * (b + d)
+    det = (a * d - b * c).astype(f)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where((m1 != 0) & (m2 != 0), N.astype(f) * (det * det) / (m1.astype(f) * m2.astype(f)), np.nan)
+
+
+def case_control_from_counts(counts, fisher=None):
+    """The case/control association tests of every marker from counts = integer (L, 2, 3 or 4): group 0 the controls, group 1 the cases,
+    columns the called genotypes 0 / 1 / 2 (a fourth column, missing, is not used).  With cases (r0, r1, r2), controls (s0, s1, s2),
+    n_j = r_j + s_j, R = sum r, S = sum s, N = R + S  ->  {"cases", "controls": the two count rows;  "allelic": the 1-df chi-square of the
+    allele table (a, b; c, d) = (2 r2 + r1, 2 r0 + r1; 2 s2 + s1, 2 s0 + s1), "or": a d / (b c);  "trend": Cochran-Armitage with weights
+    0, 1, 2, N (N (r1 + 2 r2) - R (n1 + 2 n2))^2 / (R S (N (n1 + 4 n2) - (n1 + 2 n2)^2));  "genotypic": the 2-df Pearson chi-square of the
+    2 x 3 table;  "dominant" (genotypes 1 and 2 against 0) and "recessive" (2 against 0 and 1): 1-df;  "p_allelic", "p_trend",
+    "p_genotypic", "p_dominant", "p_recessive" by scipy.special.chdtrc;  with fisher= (a function of (L, 4) tables) "p_fisher" of the
+    allele table}.  Integer parts are exact in int64 (up to 2^30 individuals), then as few fp64 operations as the formula needs; a zero
+    margin gives NaN."""
+    from scipy import special
+    c = np.asarray(counts).astype(np.int64)
+    if c.ndim != 3 or c.shape[1] != 2 or c.shape[2] not in (3, 4):
+        raise ValueError("case_control_from_counts: counts must be (L, 2, 3 or 4)")
+    f = np.float64
+    s0, s1, s2 = c[:, 0, 0], c[:, 0, 1], c[:, 0, 2]
+    r0, r1, r2 = c[:, 1, 0], c[:, 1, 1], c[:, 1, 2]
+    n0, n1, n2 = r0 + s0, r1 + s1, r2 + s2
+    R, S = r0 + r1 + r2, s0 + s1 + s2
+    N = R + S
+    a, b, cc, d = 2 * r2 + r1, 2 * r0 + r1, 2 * s2 + s1, 2 * s0 + s1
+    out = {"cases": c[:, 1, :3].copy(), "controls": c[:, 0, :3].copy(), "allelic": _chi2_2x2(a, b, cc, d)}
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out["or"] = (a * d).astype(f) / (b * cc).astype(f)
+        tnum = (N * (r1 + 2 * r2) - R * (n1 + 2 * n2)).astype(f)
+        tvar = N * (n1 + 4 * n2) - (n1 + 2 * n2) * (n1 + 2 * n2)
+        tok = (R != 0) & (S != 0) & (tvar != 0)
+        out["trend"] = np.where(tok, N.astype(f) * (tnum * tnum) / ((R * S).astype(f) * tvar.astype(f)), np.nan)
+        geno = np.zeros(c.shape[0], dtype=f)
+        for row, tot in (((r0, r1, r2), R), ((s0, s1, s2), S)):                  # the six cells in a fixed order
+            for o, col in zip(row, (n0, n1, n2)):
+                dev = (N * o - tot * col).astype(f)                              # N (O - E)
+                geno = geno + dev * dev / (N.astype(f) * (tot * col).astype(f))
+        out["genotypic"] = np.where((R != 0) & (S != 0) & (n0 != 0) & (n1 != 0) & (n2 != 0), geno, np.nan)
+    out["dominant"] = _chi2_2x2(r1 + r2, r0, s1 + s2, s0)
+    out["recessive"] = _chi2_2x2(r2, r0 + r1, s2, s0 + s1)
+    for key, df in (("allelic", 1), ("trend", 1), ("genotypic", 2), ("dominant", 1), ("recessive", 1)):
+        out["p_" + key] = special.chdtrc(float(df), out[key])
+    if fisher is not None:
+        out["p_fisher"] = fisher(np.stack([a, b, cc, d], axis=1))
+    return out
+
+
+def CaseControl(geno, status, bed=None, fisher=False, availmemGb=8, device=0):
+    """Case/control association of every marker of a panel with a binary trait -> case_control_from_counts' dict (the allelic, trend,
+    genotypic, dominant and recessive tests and their p-values; see there).  status: one record per individual, 1 = case, 0 = control,
+    NaN / None = neither.  The counts come from the device in one pass (rcpp_api.group_counts; with bed= from the .bed file, where a
+    missing call is in no cell); fisher=True adds "p_fisher", the exact test of the allele table on the device (rcpp_api.fisher_2x2).
+    HWE(out["controls"]) is the Hardy-Weinberg filter among the controls.  Covariates and stratified tests are out of scope."""
+    st = list(np.asarray(status, dtype=object).ravel())
+    lab = np.full(len(st), -1, dtype=np.int32)
+    for i, v in enumerate(st):
+        if v is None or (isinstance(v, (float, np.floating)) and math.isnan(v)):
+            continue
+        if v != 0 and v != 1:
+            raise ValueError("CaseControl: status must be 1 (case), 0 (control) or NaN / None (neither)")
+        lab[i] = int(v)
+    n, L, src_bed, bdims, inc = _group_source("CaseControl", geno, bed, None)
+    if lab.size != n:
+        raise ValueError("CaseControl: %d status records for %d genotyped individuals" % (lab.size, n))
+    if src_bed is not None:
+        c = rcpp_api.bed_group_counts(src_bed, bdims, lab, 2, availmemGb, device=device)
+        c = c if inc is None else np.ascontiguousarray(c[inc])
+    else:
+        c = rcpp_api.group_counts(geno["asciifileMt"], (n, L), lab, 2, availmemGb, device=device)
+    return case_control_from_counts(c, fisher=(lambda t: rcpp_api.fisher_2x2(t, device=device)) if fisher else None)

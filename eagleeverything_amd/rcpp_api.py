@@ -1432,6 +1432,72 @@ def epistasis_pairs(f_name_ascii_Mt, dims, y, chrom=None, gap=0, min_stat=0.0, h
     return out
 
 
+# ---- per-group genotype counts and Fisher's exact test (include/eagle_hip.h section 1b''''iii); the statistics are r_api's ----
+GROUPS_MAX = 64
+
+
+def _group_labels(who, labels, n, K):
+    """labels as int64 (n) and the number of groups: whole numbers in [-1, K), K = max + 1 (at least 1) when not given."""
+    la = np.asarray(labels)
+    if la.ndim != 1 or la.size != n:
+        raise ValueError("%s: labels must hold one entry per individual (%d)" % (who, n))
+    if la.dtype.kind not in "iuf" or not np.all(np.isfinite(la.astype(np.float64))) or not np.all(la == np.rint(la.astype(np.float64))):
+        raise ValueError("%s: labels must hold whole numbers (-1 = in no group)" % who)
+    lv = la.astype(np.int64)
+    if K is None:
+        K = max(int(lv.max()) + 1, 1) if lv.size else 1
+    if int(K) != K or K < 1:
+        raise ValueError("%s: K must be a whole number of at least 1" % who)
+    if lv.size and (int(lv.min()) < -1 or int(lv.max()) >= K):
+        raise ValueError("%s: a label outside [-1, K = %d)" % (who, K))
+    return lv, int(K)
+
+
+def _group_rounds(fn, who, path, dims, labels, K, width, max_memory_in_Gbytes, device):
+    n, nm = max(int(dims[0]), 0), max(int(dims[1]), 0)
+    lv, K = _group_labels(who, labels, n, K)
+    L = _lib.load()
+    out = np.zeros((nm, K, width), dtype=np.int32)
+    for k0 in range(0, K, GROUPS_MAX):                  # rounds of 64 groups, the others in no group: a partition makes this exact
+        kr = min(GROUPS_MAX, K - k0)
+        lr = np.ascontiguousarray(np.where((lv >= k0) & (lv < k0 + kr), lv - k0, -1), dtype=np.int32)
+        part = out if K <= GROUPS_MAX else np.zeros((nm, kr, width), dtype=np.int32)
+        _args_first(getattr(L, fn), device, (os.fsencode(path), _dims(dims), lr.ctypes.data_as(_c_i32p), kr, float(max_memory_in_Gbytes),
+                                             part.ctypes.data_as(_c_i32p)))
+        if part is not out:
+            out[:, k0:k0 + kr] = part
+    return out
+
+
+def group_counts(f_name_ascii_Mt, dims, labels, K=None, max_memory_in_Gbytes=8.0, device=0):
+    """eagle_group_counts -> int32 (L, K, 3): the numbers of '0', '1', '2' characters of every line of Mt.ascii (dims = (n, L) of M) among
+    the individuals of every group; labels = one whole number in [-1, K) per individual (-1 = in no group; with a view alias one per kept
+    individual), K = max(labels) + 1 when not given.  More than 64 groups run as rounds of 64.  r_api.group_counts_host restates it."""
+    return _group_rounds("eagle_group_counts", "group_counts", f_name_ascii_Mt, dims, labels, K, 3, max_memory_in_Gbytes, device)
+
+
+def bed_group_counts(bed_path, dims, labels, K=None, max_memory_in_Gbytes=8.0, device=0):
+    """eagle_bed_group_counts -> int32 (L, K, 4): homozygous A1, heterozygous, homozygous A2, missing of every marker of a SNP-major PLINK
+    .bed file of dims = (n individuals, L markers) among the individuals of every group (labels and K as in group_counts)."""
+    return _group_rounds("eagle_bed_group_counts", "bed_group_counts", bed_path, dims, labels, K, 4, max_memory_in_Gbytes, device)
+
+
+def fisher_2x2(tables, device=0):
+    """eagle_fisher_2x2 -> fp64 (L): the two-sided Fisher exact test of tables = int (L, 4) rows (a, b, c, d) of the 2 x 2 tables
+    (a, b; c, d), entries >= 0 and sums <= 2^30, in the fixed order of the header (r_api.fisher_2x2_host gives the same bits)."""
+    t = np.asarray(tables)
+    if t.ndim != 2 or t.shape[1] != 4 or t.shape[0] < 1:
+        raise ValueError("fisher_2x2: tables must be (L, 4) with L >= 1")
+    t32 = np.ascontiguousarray(t, dtype=np.int32)
+    if not np.array_equal(t32, t):
+        raise ValueError("fisher_2x2: tables must hold whole numbers that fit int32")
+    if int(t32.min()) < 0 or int(t32.astype(np.int64).sum(axis=1).max()) > 1 << 30:
+        raise ValueError("fisher_2x2: entries must not be negative and a table must not sum to more than 2^30")
+    out = np.zeros(t32.shape[0], dtype=np.float64)
+    _args_first(_lib.load().eagle_fisher_2x2, device, (t32.ctypes.data_as(_c_i32p), t32.shape[0], _dp(out)))
+    return out
+
+
 # ---- SURVEY 8 f-4: the dense model algebra on the device, through the C ABI (opt-in; include/eagle_hip.h section 1c) ----
 def _square_any_order(A):
     """(buffer, transposed): a float64 n x n array usable as a column-major matrix without a copy when it is contiguous in

@@ -989,6 +989,62 @@ int eagle_epistasis_pairs(eagle_ctx* ctx, const char* f_name_ascii_Mt, const lon
                           long* nhits_out, long* ntested_out, eagle_epi_max* max_out);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1b''''iii. Per-group genotype counts and Fisher's exact test (no counterpart in the reference, whose panel is one population with one
+ *     quantitative trait): the genotype counts of every marker WITHIN each group of individuals, the one primitive under per-population
+ *     allele frequencies, Fst, the Hardy-Weinberg test among controls only and the case/control association tests.  The counts are exact
+ *     integers, so the device and a numpy restatement (r_api.group_counts_host, r_api.bed_group_counts_host) agree with ==; every
+ *     statistic is the caller's fp64 arithmetic on them (r_api.GroupCounts, r_api.Fst, r_api.CaseControl).
+ *
+ *     1. Inputs.  labels[i] in {-1, 0, ..., K - 1}, one int32 per individual; -1 = in no group.  1 <= K <= EAGLE_GROUPS_MAX = 64.  With a
+ *        VIEW alias of eagle_reshape_m, labels has dims[0] entries: one per kept individual.  size_k = the number of individuals with
+ *        label k.
+ *     2. Image route (eagle_group_counts).  g in {-1, 0, +1} over the individuals of Mt.ascii; a missing call of the source is a
+ *        heterozygote by now.  s_mk = sum_{i in k} g_im and q_mk = sum_{i in k} g_im^2, then n2 = (q + s) / 2, n0 = (q - s) / 2,
+ *        n1 = size_k - q:  counts_out[(m K + k) 3 + c], c = 0, 1, 2, is int32 of shape L x K x 3, the numbers of '0', '1', '2'
+ *        characters of line m among group k.  On the device s and q are two products of the int8 image with the one-hot label operand on
+ *        v_mfma_i32_32x32x32_i8 (k_group_tile, csrc/eagle_groups.hip); the image is read once.
+ *     3. .bed route (eagle_bed_group_counts).  counts_out[(m K + k) 4 + c] = (homozygous A1, code 00; heterozygous, 10; homozygous A2,
+ *        11; missing, 01) of marker m among group k, int32 of shape L x K x 4, by popcounts of the two bit planes against K bit-mask
+ *        planes (k_bed_group_counts).  The unused bit pairs of a row's last byte are not counted.
+ *     4. Invariants.  Summed over k with every individual labelled, the counts are those of eagle_marker_counts /
+ *        eagle_bed_marker_counts exactly; K = 1 with all labels 0 IS those calls.  A group without an individual has zero counts.
+ *     5. Fisher's exact test of a 2 x 2 table (a, b; c, d), two-sided (eagle_fisher_2x2).  r1 = a + b, r2 = c + d, c1 = a + c,
+ *        N = r1 + r2;  N = 0 gives p = 1.  x runs over lo = max(0, c1 - r2) .. hi = min(r1, c1), the values the first cell can take
+ *        under the margins.  Unnormalised probabilities start from the mode x0 = clamp(floor((r1 + 1) (c1 + 1) / (N + 2)), lo, hi) with
+ *        P(x0) = 1 and follow
+ *            P(x - 1) = P(x) * x (r2 - c1 + x) / ((r1 - x + 1) (c1 - x + 1)),      P(x + 1) = P(x) * (r1 - x) (c1 - x) / ((x + 1) (r2 - c1 + x + 1)).
+ *        Each step is  P' = fl(fl(P * (double)num) / (double)den):  num and den are exact int64 products converted to fp64 once, the
+ *        product and the quotient are rounded separately.  The terms are visited in ONE order: x0, then the lower leg x0 - 1, ..., lo,
+ *        then the upper leg x0 + 1, ..., hi; a leg ends at its first term that is exactly 0.0 (adding zeros changes no bit).  First walk:
+ *        total = 1.0, then total = fl(total + P) for every further term in that order; P(a) is picked up on the way (0.0 if a leg ended
+ *        before it).  cut = fl(P(a) * 1.0000001).  Second walk, the same steps in the same order:  tail = (1.0 <= cut ? 1.0 : 0.0),
+ *        then tail = fl(tail + P) for every term with P <= cut.  p = min(1, fl(tail / total)).  The factor 1.0000001 is the rule of R's
+ *        fisher.test: without it the balanced designs that are the common case (r1 = r2) have mathematically tied terms x and c1 - x
+ *        that the two legs round differently, and the p-value would hang on the last bit.  Nothing is contracted into an FMA and no
+ *        array is kept per table, so a scalar restatement in any IEEE-754 language gives the same bits (r_api.fisher_2x2_host).
+ *
+ *     What is not claimed.  Agreement with the PLINK program is neither claimed nor tested, because it is not available: the tests hold
+ *     the counts to loops over individuals and the statistics to exact rational arithmetic.  Logistic regression with covariates,
+ *     stratified (Cochran-Mantel-Haenszel) tests and sex chromosomes are out of scope.
+ *
+ *     The image route reads the file as eagle_marker_counts reads it: the resident image where it lies (it is never modified), else row
+ *     windows from the sidecar, the text or a VIEW alias's source; rows are independent and the label operand is built once per call, so
+ *     every route gives the same integers.  The .bed route stages the rows as eagle_bed_marker_counts does.  Single device: a
+ *     multi-device context works on its first device.  Argument errors (EAGLE_ERR_ARG: a NULL pointer, dims <= 0, K outside [1, 64],
+ *     a label outside [-1, K), n > 2^30 - 1, a negative table entry, a table sum above 2^30) are decided before the context is used;
+ *     with ctx == NULL their text is in eagle_open_error().
+ * ------------------------------------------------------------------------------------------- */
+#define EAGLE_GROUPS_MAX 64
+
+int eagle_group_counts(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long dims[2], const int32_t* labels, int K,
+                       double max_memory_in_Gbytes, int32_t* counts_out);
+int eagle_bed_group_counts(eagle_ctx* ctx, const char* bed_path, const long dims[2], const int32_t* labels, int K,
+                           double max_memory_in_Gbytes, int32_t* counts_out);
+/* p_out[i] = the test above on tables[4 i .. 4 i + 3] = (a, b, c, d), i < L; one table per device thread (k_fisher_2x2).
+ * EAGLE_ERR_ARG also for L <= 0. */
+int eagle_fisher_2x2(eagle_ctx* ctx, const int32_t* tables, long L, double* p_out);
+
+/* ---------------------------------------------------------------------------------------------
  * 1c. Dense n x n model algebra on the device (OPT-IN: north_star keeps calculateH / calculateP / emma.* on
  *     host LAPACK, and nothing above calls these).  Once the scan takes tens of milliseconds the ~10-15 O(n^3) base-R calls
  *     of a find_qtl iteration are the whole run time (the author's note MyPackage/MyREADME:1 names eigen(); his MAGMA
