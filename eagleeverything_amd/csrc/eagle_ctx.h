@@ -240,6 +240,12 @@ extern "C" int eagle_dev_group_bedmask(eagle_ctx* ctx, const int32_t* labels, lo
 extern "C" int eagle_dev_bed_group_counts(eagle_ctx* ctx, const uint8_t* bed, long rows, long n, int K, const uint32_t* planes, const int32_t* sizes,
                                           int32_t* counts, void* stream);
 extern "C" int eagle_dev_fisher_2x2(eagle_ctx* ctx, const int32_t* tables, long L, double* p, void* stream);
+// Logistic regression per marker (eagle_logit.hip; include/eagle_hip.h section 1b''''iv), device pointers throughout, one row window.
+// X16: n64 x 16 fp64, n64 = n rounded up to 64, row i = the c = p - 1 covariates of individual i then zeros; valid_y: n64 bytes, 0 = not
+// used, 2 = control, 3 = case; both zero from individual n on, and the X16 rows of unused individuals zero.  beta0[c]: the start.
+// stat[rows][4] = (gamma, se, score, loglik), info[rows][2] = (code, evaluations); firth = 0 (ML), 1 (Firth), 2 (fallback).
+extern "C" int eagle_dev_logistic(eagle_ctx* ctx, const int8_t* Mt8, long rows, long n, long ld, const double* X16, const uint8_t* valid_y,
+                                  const double* beta0, int p, int firth, double tol, int max_iter, double* stat, int32_t* info, void* stream);
 // Sample QC.  eagle_qc.hip: counts[n][4] (hom A1, het, hom A2, missing per INDIVIDUAL; zeroed by the caller before a file's first
 // window) += the counts over `rows` raw .bed rows; ibs0 / hethet (n x n int32, full and symmetric) from the Gram accumulators D32, Q32
 // (n_pad x n_pad, upper 256-tiles live) and the marker count L; p[L] = the Hardy-Weinberg exact test of counts[L][stride] (stride 3

@@ -24,6 +24,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <functional>
 
 #include "eagle_ctx.h"
@@ -1089,6 +1090,88 @@ extern "C" int eagle_fisher_2x2(eagle_ctx* ctx, const int32_t* tables, long L, d
     int rc = eagle_dev_fisher_2x2(ctx, dt.as<int32_t>(), L, dp.as<double>(), ctx->stream);
     if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
     HIPCHK(ctx, hipMemcpyAsync(p_out, dp.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return EAGLE_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Logistic regression of a binary trait on covariates and one marker at a time (include/eagle_hip.h section 1b''''iv; the kernel is
+// in eagle_logit.hip).  eagle_group_counts' routes; the covariates are staged once per call as the n64 x 16 padded image the kernel
+// reads (rows of unused individuals zero, so a NaN there is never met) with the status as one byte per individual.
+// ---------------------------------------------------------------------------------------------------------------
+extern "C" int eagle_logistic(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long dims[2], const int32_t* status, const double* X, int c,
+                              const double* beta0, int firth, double tol, int max_iter, double max_memory_in_Gbytes, double* stat_out,
+                              int32_t* info_out) {
+    auto fail = [&](const char* what) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "logistic: %s", what);
+        return qc_fail(ctx, EAGLE_ERR_ARG, msg);
+    };
+    if (!f_name_ascii_Mt || !dims || !status || !X || !beta0 || !stat_out || !info_out) return fail("NULL argument");
+    const long n = dims[0], L = dims[1];
+    if (n <= 0 || L <= 0) return fail("dims must be positive");
+    if (n > 0x3fffffffL) return fail("more than 2^30 - 1 individuals");
+    if (c < 1 || c > 15) return fail("c outside [1, 15]");
+    if (firth < 0 || firth > 2) return fail("firth outside {0, 1, 2}");
+    if (!(tol > 0.0 && tol < 1.0)) return fail("tol not in (0, 1)");
+    if (max_iter < 1 || max_iter > 1000) return fail("max_iter outside [1, 1000]");
+    long ncase = 0, nctrl = 0;
+    for (long i = 0; i < n; i++) {
+        if (status[i] < -1 || status[i] > 1) return fail("a status outside {-1, 0, 1}");
+        if (status[i] < 0) continue;
+        (status[i] ? ncase : nctrl)++;
+        for (int j = 0; j < c; j++)
+            if (!std::isfinite(X[i + (size_t)n * j])) return fail("a non-finite X entry of a used individual");
+    }
+    for (int j = 0; j < c; j++)
+        if (!std::isfinite(beta0[j])) return fail("a non-finite beta0 entry");
+    if (!ncase || !nctrl) return fail("no case or no control among the used individuals");
+    if (!ctx) return fail("no context");
+
+    const long n64 = (n + 63) / 64 * 64;
+    std::vector<double> x16((size_t)n64 * 16, 0.0);
+    std::vector<uint8_t> vy((size_t)n64, 0);
+    for (long i = 0; i < n; i++) {
+        if (status[i] < 0) continue;
+        vy[i] = (uint8_t)(2 | status[i]);
+        for (int j = 0; j < c; j++) x16[(size_t)i * 16 + j] = X[i + (size_t)n * j];
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int threads = host_threads();
+    DevBuf d_x, d_vy, d_b0, stat, info;
+    HIPCHK(ctx, d_x.alloc(sizeof(double) * x16.size()));
+    HIPCHK(ctx, d_vy.alloc(vy.size()));
+    HIPCHK(ctx, d_b0.alloc(sizeof(double) * 16));
+    HIPCHK(ctx, stat.alloc(sizeof(double) * 4 * (size_t)L));
+    HIPCHK(ctx, info.alloc(sizeof(int32_t) * 2 * (size_t)L));
+    HIPCHK(ctx, hipMemcpyAsync(d_x.p, x16.data(), sizeof(double) * x16.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d_vy.p, vy.data(), vy.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d_b0.p, beta0, sizeof(double) * (size_t)c, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));                  // x16 and vy are pageable host vectors
+    const GenoEntry* src = nullptr;
+    int rc = eagle_get_resident(ctx, f_name_ascii_Mt, L, n, max_memory_in_Gbytes, threads, &src);
+    if (rc != EAGLE_OK && rc != EAGLE_STREAM) return rc;
+    if (rc == EAGLE_OK) {
+        rc = eagle_dev_logistic(ctx, src->dev, L, n, src->ld, d_x.as<double>(), d_vy.as<uint8_t>(), d_b0.as<double>(), c + 1, firth, tol, max_iter,
+                                stat.as<double>(), info.as<int32_t>(), ctx->stream);
+        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    } else {
+        const long ld = eagle_pad(n), w = stream_chunk_rows_core(eagle_resident_budget(), ld, eagle_pad(L));
+        DevBuf win;
+        HIPCHK(ctx, win.alloc((size_t)w * ld));
+        for (long r0 = 0; r0 < L; r0 += w) {
+            const long nr = std::min(w, L - r0);
+            HIPCHK(ctx, hipMemsetAsync(win.p, 0, (size_t)w * ld, ctx->stream));
+            rc = eagle_dev_load_ascii(ctx, f_name_ascii_Mt, r0, nr, 0, n, win.as<int8_t>(), ld, max_memory_in_Gbytes, threads);
+            if (!rc)
+                rc = eagle_dev_logistic(ctx, win.as<int8_t>(), nr, n, ld, d_x.as<double>(), d_vy.as<uint8_t>(), d_b0.as<double>(), c + 1, firth, tol,
+                                        max_iter, stat.as<double>() + 4 * (size_t)r0, info.as<int32_t>() + 2 * (size_t)r0, ctx->stream);
+            if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+        }
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // `win` is freed on return: its last kernel has finished
+    }
+    HIPCHK(ctx, hipMemcpyAsync(stat_out, stat.p, sizeof(double) * 4 * (size_t)L, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(info_out, info.p, sizeof(int32_t) * 2 * (size_t)L, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return EAGLE_OK;
 }

@@ -2773,7 +2773,7 @@ def CaseControl(geno, status, bed=None, fisher=False, availmemGb=8, device=0):
     genotypic, dominant and recessive tests and their p-values; see there).  status: one record per individual, 1 = case, 0 = control,
     NaN / None = neither.  The counts come from the device in one pass (rcpp_api.group_counts; with bed= from the .bed file, where a
     missing call is in no cell); fisher=True adds "p_fisher", the exact test of the allele table on the device (rcpp_api.fisher_2x2).
-    HWE(out["controls"]) is the Hardy-Weinberg filter among the controls.  Covariates and stratified tests are out of scope."""
+    HWE(out["controls"]) is the Hardy-Weinberg filter among the controls.  Covariates: Logistic; stratified tests are out of scope."""
     st = list(np.asarray(status, dtype=object).ravel())
     lab = np.full(len(st), -1, dtype=np.int32)
     for i, v in enumerate(st):
@@ -2791,3 +2791,173 @@ def CaseControl(geno, status, bed=None, fisher=False, availmemGb=8, device=0):
     else:
         c = rcpp_api.group_counts(geno["asciifileMt"], (n, L), lab, 2, availmemGb, device=device)
     return case_control_from_counts(c, fisher=(lambda t: rcpp_api.fisher_2x2(t, device=device)) if fisher else None)
+
+
+# ---- logistic regression per marker with covariates, Firth fallback (include/eagle_hip.h section 1b''''iv) ----
+_LOGIT_ETA_MAX, _LOGIT_STEP_MAX, _LOGIT_PIVOT_REL = 40.0, 5.0, 2.0 ** -40
+
+
+def _logit_eval(Xt, y, beta):
+    """One evaluation of section 1b''''iv at beta over the rows of Xt (used individuals only): (mu, y - mu, w, U, I, loglik, max |eta|)."""
+    eta = Xt @ beta
+    e = np.exp(-np.abs(eta))
+    d = 1.0 / (1.0 + e)
+    mu = np.where(eta >= 0.0, d, e * d)
+    w = e * d * d
+    ll = float(np.sum(y * eta - (np.maximum(eta, 0.0) + np.log1p(e))))
+    res = np.where(y > 0.5, np.where(eta >= 0.0, e * d, d), -mu)                    # y - mu without cancellation
+    return mu, res, w, Xt.T @ res, Xt.T @ (w[:, None] * Xt), ll, float(np.max(np.abs(eta)))
+
+
+def _logit_chol(A):
+    """The lower Cholesky factor of A column by column, or None when a pivot is not finite or not above 2^-40 of its diagonal entry."""
+    p = A.shape[0]
+    Lm = np.tril(A).astype(np.float64)
+    d0 = np.diag(A).copy()
+    for j in range(p):
+        d = Lm[j, j]
+        if not (d > d0[j] * _LOGIT_PIVOT_REL) or not (d < np.inf):
+            return None
+        l = math.sqrt(d)
+        Lm[j, j] = l
+        Lm[j + 1:, j] /= l
+        for k in range(j + 1, p):
+            Lm[k:, k] -= Lm[k:, j] * Lm[k, j]
+    return Lm
+
+
+def _logit_solve(Lm, b):
+    from scipy.linalg import solve_triangular
+    return solve_triangular(Lm, solve_triangular(Lm, b, lower=True), lower=True, trans="T")
+
+
+def _logit_fit(Xt, y, start, firth, tol, max_iter, score=None):
+    """One fit of section 1b''''iv from `start` -> (gamma, se, score, loglik, code, evaluations), gamma the LAST parameter."""
+    nan = float("nan")
+    beta = np.array(start, dtype=np.float64)
+    g = beta.size - 1
+    ev = 0
+    with np.errstate(all="ignore"):
+        while ev < max_iter:
+            mu, res, w, U, I, ll, mx = _logit_eval(Xt, y, beta)
+            ev += 1
+            Lm = _logit_chol(I)
+            if Lm is None:
+                return nan, nan, nan if score is None else score, nan, 2, ev
+            if ev == 1 and score is None:
+                score = float(U[g] * U[g] / (Lm[g, g] * Lm[g, g]))
+            if not firth and mx > _LOGIT_ETA_MAX:
+                return nan, nan, score, nan, 3, ev
+            if firth:
+                Inv = _logit_solve(Lm, np.eye(beta.size))
+                h = w * np.einsum("ij,jk,ik->i", Xt, Inv, Xt)
+                U = Xt.T @ (res + h * (0.5 - mu))
+            delta = _logit_solve(Lm, U)
+            md = float(np.max(np.abs(delta))) if np.all(np.isfinite(delta)) else nan
+            if md > _LOGIT_STEP_MAX:
+                delta = delta * (_LOGIT_STEP_MAX / md)
+            beta = beta + delta
+            if md <= tol:
+                return float(beta[g]), 1.0 / float(Lm[g, g]), score, ll, 0, ev
+    return nan, nan, nan if score is None else score, nan, 1, ev
+
+
+def logistic_null_host(X, y, tol=1e-10, max_iter=50):
+    """The covariates-only logistic fit of y (0 / 1) on the columns of X (every row used) -> beta0 fp64 (c): numpy fp64 Newton with the
+    step cap and the stop rule of include/eagle_hip.h section 1b''''iv, from beta = 0.  ValueError when it does not get there."""
+    Xt, yv = np.asarray(X, dtype=np.float64), np.asarray(y, dtype=np.float64).ravel()
+    if Xt.ndim != 2 or Xt.shape[0] != yv.size or Xt.shape[1] < 1:
+        raise ValueError("logistic_null_host: X must be (n, c) with one row per entry of y")
+    beta = np.zeros(Xt.shape[1])
+    for _ in range(int(max_iter)):
+        _, _, _, U, I, _, _ = _logit_eval(Xt, yv, beta)
+        Lm = _logit_chol(I)
+        if Lm is None:
+            raise ValueError("logistic_null_host: the covariates are collinear among the used individuals")
+        delta = _logit_solve(Lm, U)
+        md = float(np.max(np.abs(delta)))
+        if md > _LOGIT_STEP_MAX:
+            delta = delta * (_LOGIT_STEP_MAX / md)
+        beta = beta + delta
+        if md <= tol:
+            return beta
+    raise ValueError("logistic_null_host: the covariates-only fit did not converge (separated by the covariates?)")
+
+
+def logistic_host(Mt8, status, X, firth=2, tol=1e-10, max_iter=50, beta0=None):
+    """rcpp_api.logistic restated in numpy, marker by marker: Mt8 = int8 (L, n) of -1 / 0 / +1 (marker-major), status in {-1, 0, 1}, X
+    (n, c) -> (stat (L, 4), info (L, 2)) by the rule of include/eagle_hip.h section 1b''''iv.  Not bit-equal to the device (exp, log1p
+    and the order of the sums differ); tests/logistic_truth.py holds both to 40-digit roots."""
+    G = np.asarray(Mt8)
+    sv = np.asarray(status).astype(np.int64).ravel()
+    Xa = np.asarray(X, dtype=np.float64)
+    used = sv >= 0
+    Xu, y = Xa[used], sv[used].astype(np.float64)
+    b0 = logistic_null_host(Xu, y, tol, max_iter) if beta0 is None else np.asarray(beta0, dtype=np.float64).ravel()
+    start = np.concatenate([b0, [0.0]])
+    stat, info = np.full((G.shape[0], 4), np.nan), np.zeros((G.shape[0], 2), dtype=np.int32)
+    for m in range(G.shape[0]):
+        Xt = np.column_stack([Xu, G[m, used].astype(np.float64) + 1.0])
+        if firth == 1:
+            r = _logit_fit(Xt, y, start, True, tol, max_iter)
+            r = r[:4] + (r[4] + 256, r[5])
+        else:
+            r = _logit_fit(Xt, y, start, False, tol, max_iter)
+            if firth == 2 and r[4] != 0 and not (r[4] == 2 and r[5] == 1):
+                r = _logit_fit(Xt, y, start, True, tol, max_iter, score=r[2])
+                r = r[:4] + (r[4] + 256, r[5])
+        stat[m], info[m] = r[:4], r[4:]
+    return stat, info
+
+
+_LOGIT_FIRTH = {"ml": 0, "none": 0, False: 0, 0: 0, "firth": 1, True: 1, 1: 1, "fallback": 2, 2: 2}
+
+
+def Logistic(geno, status, X=None, firth="fallback", tol=1e-10, max_iter=50, availmemGb=8, device=0):
+    """Case/control association of every marker of a panel with covariates: the logistic fit  logit P(case) = x' beta + g gamma  per
+    marker on the device (rcpp_api.logistic; include/eagle_hip.h section 1b''''iv) -> {"beta": gamma per allele copy of the '2'
+    character (the allele whose odds ratio CaseControl reports), "se", "or" = exp(beta), "z" = beta / se, "p": two-sided Wald
+    (scipy.special.ndtr), "score": the score test of gamma = 0 and "p_score" (chdtrc, 1 df; with X=None the trend test of CaseControl),
+    "lrt" = 2 (l - l0) and "p_lrt" for maximum-likelihood fits (NaN under Firth), "code", "iterations", "firth": bool per marker,
+    "n_used", "beta0": the covariates-only fit}.  status as in CaseControl: 1 = case, 0 = control, NaN / None = not used.  X: (n, c <=
+    15) covariates WITH the intercept column, e.g. what am.add_pcs(X, pca) returns; None = intercept only; an individual with a NaN
+    covariate is not used.  firth: "fallback" (Firth's penalised fit where ML fails: separation, no convergence), "firth" (every marker)
+    or "ml".  A missing call of the source is a heterozygote on the image, as everywhere else: impute first (ReadMarker(..., impute=k))
+    where that matters; there is no .bed route."""
+    from scipy import special
+    if firth not in _LOGIT_FIRTH:
+        raise ValueError("Logistic: firth must be \"fallback\", \"firth\" or \"ml\"")
+    st = list(np.asarray(status, dtype=object).ravel())
+    sv = np.full(len(st), -1, dtype=np.int32)
+    for i, v in enumerate(st):
+        if v is None or (isinstance(v, (float, np.floating)) and math.isnan(v)):
+            continue
+        if v != 0 and v != 1:
+            raise ValueError("Logistic: status must be 1 (case), 0 (control) or NaN / None (not used)")
+        sv[i] = int(v)
+    n, L = int(geno["dim_of_ascii_M"][0]), int(geno["dim_of_ascii_M"][1])
+    if sv.size != n:
+        raise ValueError("Logistic: %d status records for %d genotyped individuals" % (sv.size, n))
+    Xa = np.ones((n, 1)) if X is None else np.asarray(X, dtype=np.float64)
+    if Xa.ndim == 1:
+        Xa = Xa[:, None]
+    if Xa.ndim != 2 or Xa.shape[0] != n or not 1 <= Xa.shape[1] <= rcpp_api.LOGISTIC_MAX_COVARIATES:
+        raise ValueError("Logistic: X must be (%d, c) with 1 <= c <= %d, the intercept column included" % (n, rcpp_api.LOGISTIC_MAX_COVARIATES))
+    if np.any(np.isinf(Xa)):
+        raise ValueError("Logistic: X holds an infinite entry")
+    sv[np.any(np.isnan(Xa), axis=1)] = -1
+    used = sv >= 0
+    if not (sv == 1).any() or not (sv == 0).any():
+        raise ValueError("Logistic: no case or no control among the used individuals")
+    y = sv[used].astype(np.float64)
+    b0 = logistic_null_host(Xa[used], y, tol, max_iter)
+    ll0 = _logit_eval(Xa[used], y, b0)[5]
+    stat, info = rcpp_api.logistic(geno["asciifileMt"], (n, L), sv, Xa, b0, _LOGIT_FIRTH[firth], tol, max_iter, availmemGb, device=device)
+    beta, se, score, ll = stat[:, 0], stat[:, 1], stat[:, 2], stat[:, 3]
+    is_firth = info[:, 0] >= 256
+    with np.errstate(all="ignore"):
+        z = beta / se
+        lrt = np.where(is_firth, np.nan, 2.0 * (ll - ll0))
+        return {"beta": beta.copy(), "se": se.copy(), "or": np.exp(beta), "z": z, "p": 2.0 * special.ndtr(-np.abs(z)), "score": score.copy(),
+                "p_score": special.chdtrc(1.0, score), "lrt": lrt, "p_lrt": special.chdtrc(1.0, np.maximum(lrt, 0.0)),
+                "code": info[:, 0].copy(), "iterations": info[:, 1].copy(), "firth": is_firth, "n_used": int(used.sum()), "beta0": b0}

@@ -1498,6 +1498,60 @@ def fisher_2x2(tables, device=0):
     return out
 
 
+# ---- logistic regression per marker with covariates (include/eagle_hip.h section 1b''''iv); the p-values are r_api's ----
+LOGISTIC_MAX_COVARIATES = 15
+
+
+def _logistic_inputs(who, n, status, X, beta0, firth, tol, max_iter):
+    """(status int32 (n), X fp64 (n, c) column-major, beta0 fp64 (c) or None) after the checks eagle_logistic makes, as ValueError."""
+    sa = np.asarray(status)
+    if sa.ndim != 1 or sa.size != n:
+        raise ValueError("%s: status must hold one entry per individual (%d)" % (who, n))
+    if sa.dtype.kind not in "iuf" or not np.all(np.isin(sa, (-1, 0, 1))):
+        raise ValueError("%s: status must be 1 (case), 0 (control) or -1 (not used)" % who)
+    sv = np.ascontiguousarray(sa, dtype=np.int32)
+    Xa = np.asarray(X)
+    if Xa.dtype.kind not in "iuf" or Xa.ndim != 2 or Xa.shape[0] != n or not 1 <= Xa.shape[1] <= LOGISTIC_MAX_COVARIATES:
+        raise ValueError("%s: X must be numeric (%d, c) with 1 <= c <= %d, the intercept column included" % (who, n, LOGISTIC_MAX_COVARIATES))
+    Xf = _f64F(Xa)
+    used = sv >= 0
+    if not np.all(np.isfinite(Xf[used])):
+        raise ValueError("%s: X must be finite on the used individuals" % who)
+    if not (sv == 1).any() or not (sv == 0).any():
+        raise ValueError("%s: no case or no control among the used individuals" % who)
+    if firth not in (0, 1, 2) or isinstance(firth, bool):
+        raise ValueError("%s: firth must be 0 (ML), 1 (Firth) or 2 (fallback)" % who)
+    if not 0.0 < float(tol) < 1.0:
+        raise ValueError("%s: tol must lie in (0, 1)" % who)
+    if int(max_iter) != max_iter or not 1 <= max_iter <= 1000:
+        raise ValueError("%s: max_iter must be a whole number in [1, 1000]" % who)
+    b0 = None
+    if beta0 is not None:
+        b0 = np.ascontiguousarray(np.asarray(beta0, dtype=np.float64).ravel())
+        if b0.size != Xf.shape[1] or not np.all(np.isfinite(b0)):
+            raise ValueError("%s: beta0 must hold one finite entry per column of X" % who)
+    return sv, Xf, b0
+
+
+def logistic(f_name_ascii_Mt, dims, status, X, beta0=None, firth=2, tol=1e-10, max_iter=50, availmemGb=8, device=0):
+    """eagle_logistic -> (stat fp64 (L, 4) = (gamma, se, score, log-likelihood), info int32 (L, 2) = (code, evaluations)): the logistic
+    fit of status (1 / 0; -1 = not used) on the columns of X (n, c <= 15; the caller supplies the intercept) and every marker of
+    Mt.ascii in turn (dims = (n, L) of M; g = 0, 1, 2 copies of the '2' character), by the rule of include/eagle_hip.h section
+    1b''''iv: Newton from (beta0, 0), firth = 0 ML / 1 Firth / 2 Firth where ML fails.  beta0 = the covariates-only fit
+    (r_api.logistic_null_host when None).  Codes: 0 converged, 1 max_iter, 2 singular, 3 separation, + 256 the Firth fit.  With a
+    view alias status and X hold one entry per kept individual.  r_api.logistic_host restates it."""
+    n, nm = max(int(dims[0]), 0), max(int(dims[1]), 0)
+    sv, Xf, b0 = _logistic_inputs("logistic", n, status, X, beta0, firth, tol, max_iter)
+    if b0 is None:
+        from . import r_api
+        b0 = np.ascontiguousarray(r_api.logistic_null_host(Xf[sv >= 0], sv[sv >= 0]))
+    L = _lib.load()
+    stat, info = np.zeros((nm, 4), dtype=np.float64), np.zeros((nm, 2), dtype=np.int32)
+    _args_first(L.eagle_logistic, device, (os.fsencode(f_name_ascii_Mt), _dims(dims), sv.ctypes.data_as(_c_i32p), _dp(Xf), Xf.shape[1], _dp(b0),
+                                           int(firth), float(tol), int(max_iter), float(availmemGb), _dp(stat), info.ctypes.data_as(_c_i32p)))
+    return stat, info
+
+
 # ---- SURVEY 8 f-4: the dense model algebra on the device, through the C ABI (opt-in; include/eagle_hip.h section 1c) ----
 def _square_any_order(A):
     """(buffer, transposed): a float64 n x n array usable as a column-major matrix without a copy when it is contiguous in

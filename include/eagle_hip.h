@@ -1024,8 +1024,8 @@ int eagle_epistasis_pairs(eagle_ctx* ctx, const char* f_name_ascii_Mt, const lon
  *        array is kept per table, so a scalar restatement in any IEEE-754 language gives the same bits (r_api.fisher_2x2_host).
  *
  *     What is not claimed.  Agreement with the PLINK program is neither claimed nor tested, because it is not available: the tests hold
- *     the counts to loops over individuals and the statistics to exact rational arithmetic.  Logistic regression with covariates,
- *     stratified (Cochran-Mantel-Haenszel) tests and sex chromosomes are out of scope.
+ *     the counts to loops over individuals and the statistics to exact rational arithmetic.  Logistic regression with covariates is
+ *     section 1b''''iv; stratified (Cochran-Mantel-Haenszel) tests and sex chromosomes are out of scope.
  *
  *     The image route reads the file as eagle_marker_counts reads it: the resident image where it lies (it is never modified), else row
  *     windows from the sidecar, the text or a VIEW alias's source; rows are independent and the label operand is built once per call, so
@@ -1043,6 +1043,69 @@ int eagle_bed_group_counts(eagle_ctx* ctx, const char* bed_path, const long dims
 /* p_out[i] = the test above on tables[4 i .. 4 i + 3] = (a, b, c, d), i < L; one table per device thread (k_fisher_2x2).
  * EAGLE_ERR_ARG also for L <= 0. */
 int eagle_fisher_2x2(eagle_ctx* ctx, const int32_t* tables, long L, double* p_out);
+
+/* ---------------------------------------------------------------------------------------------
+ * 1b''''iv. Logistic regression of a binary trait on covariates and one marker at a time (no counterpart in the reference): what
+ *     eagle_group_counts' case/control tests cannot do, take covariates (the principal components of section 1b'''', sex, age).  For
+ *     marker m over the used individuals i (status[i] in {0, 1}; -1 = not used)
+ *            logit P(y_i = 1) = x_i' beta + g_im gamma,
+ *     X is n x c column-major fp64 as R holds it, and the caller supplies the intercept column;  1 <= c <= 15, so p = c + 1 <= 16
+ *     parameters;  g in {0, 1, 2} counts the '2' character of line m (the image value plus one): the allele whose odds ratio
+ *     CaseControl reports.  x~_i = (x_i, g_im), gamma is the LAST parameter.  A missing call of the source is a heterozygote by now.
+ *     r_api.logistic_host is a scalar restatement of the rule below.
+ *
+ *     1. Start.  Every fit starts at (beta0, 0), beta0 = the covariates-only fit over the used individuals, computed once by the
+ *        caller (r_api.logistic_null_host: fp64 Newton with the stop rule of 4) and passed in.
+ *     2. One evaluation at beta.  eta_i = x~_i' beta, mu_i = 1 / (1 + e^-eta_i), w_i = mu_i (1 - mu_i), U = sum (y_i - mu_i) x~_i,
+ *        I = sum w_i x~_i x~_i', l = sum [y_i eta_i - log(1 + e^eta_i)], all over the used individuals.  With e = exp(-|eta|):
+ *        mu = 1 / (1 + e) for eta >= 0 and e / (1 + e) else, w = e / (1 + e)^2, log(1 + e^eta) = max(eta, 0) + log1p(e), and y - mu is 1 - mu = e / (1 + e) for eta >= 0, 1 / (1 + e) else, or -mu: no overflow
+ *        and no cancellation, so U does not round to zero on a separated marker before code 3 is met.
+ *        The Cholesky factor I = L L' is taken column by column; a pivot must be finite and above 2^-40 of its diagonal entry of I
+ *        (a column that the columns before it explain to the resolution of fp64 is not positive), else code 2.  gamma is last, so
+ *        (I^-1)_gg = 1 / L_gg^2.
+ *     3. Score test.  The first evaluation gives it: score = U_g^2 (I^-1)_gg, the test of gamma = 0 with 1 degree of freedom.  With
+ *        c = 1 (intercept only) this is the Cochran-Armitage trend statistic of case_control_from_counts, N num^2 / (R S tvar).
+ *     4. Maximum likelihood.  Solve I delta = U by the factor; scale delta so that max |delta_j| <= 5; beta <- beta + delta; stop when
+ *        max_j |delta_j| <= tol; at most max_iter evaluations.  Order inside an evaluation: factor (code 2), the score if it is the
+ *        first, max_i |eta_i| > 40 (code 3), the step, the stop.
+ *     5. Firth (Heinze and Schemper 2002).  h_i = w_i x~_i' I^-1 x~_i, U*_j = sum [y_i - mu_i + h_i (1/2 - mu_i)] x~_ij, I delta = U*
+ *        with the same cap and stop as ML and no step halving.  I^-1 is needed before h, so a Firth evaluation takes two passes over
+ *        the individuals.  Inference is Wald from I(beta)^-1 as PLINK 2 does; the penalised likelihood-ratio test is not reported.
+ *        Code 3 is not raised.
+ *     6. Per-marker result.  stat_out[4 m ..] = (gamma, se = sqrt((I^-1)_gg), score, l) and info_out[2 m ..] = (code, evaluations of
+ *        the fit reported).  gamma is beta_g after the last step; se and l are those of the last evaluation, whose point lies within
+ *        that step (at most tol) of it.  Codes: 0 converged; 1 max_iter reached; 2 a Cholesky pivot of I was not positive or not
+ *        finite (a marker that is monomorphic among the used individuals makes gamma's column the intercept's at the first
+ *        evaluation; later on, a separated marker whose weights vanish everywhere but on one genotype does the same); 3 separation (ML
+ *        only): some evaluation had max_i |eta_i| > 40, that individual's weight is below the resolution of fp64; + 256 the value
+ *        reported is the Firth fit.  gamma, se and l are NaN unless the code's low byte is 0; score is NaN only under code 2 at the
+ *        first evaluation.
+ *     7. firth = 0: ML only.  1: Firth for every marker (every code carries + 256).  2 (fallback): ML first; a marker whose ML fit ends
+ *        with code 1, 2 or 3 after the first evaluation (a code 2 AT the first evaluation stays: Firth meets the same matrix) is
+ *        restarted from (beta0, 0) with Firth, in the same kernel and by the same wave; the score stays the first evaluation's.
+ *
+ *     On the device (k_logit_irls<firth>, csrc/eagle_logit.hip) one wave owns one marker; I is the 16 x 16 x n product
+ *     (diag(w) X~)' X~ accumulated on v_mfma_f64_16x16x4_f64 with p padded to 16, four individuals an instruction; eta, mu, w and the
+ *     likelihood term are evaluated once per individual; the factor, the solves and I^-1 are the wave's own fp64 work in LDS.  X~ is
+ *     staged once per call as an n x 16 padded image with the status as one byte per individual; an unused individual contributes
+ *     w = 0 and residual 0 (nothing is gathered), and the genotype column is read from the image row.  No atomics; a marker's result
+ *     depends on its row, X, status and beta0 alone, so it does not depend on how markers fall into row windows or workgroups.
+ *
+ *     What is not claimed.  Agreement with the PLINK or logistf programs is neither claimed nor tested, because neither is available:
+ *     the tests hold the fits to 40-digit roots of the same equations.  Bit equality with the host restatement is not claimed either:
+ *     exp, log1p and the matrix pipe's summation order are not fixed by IEEE 754.  Stratified tests and sex chromosomes stay out of
+ *     scope; so does a .bed route, where a missing call would change the used individuals, and with them the null fit, per marker.
+ *
+ *     The file is read as eagle_group_counts reads it: the resident image where it lies, else row windows from the sidecar, the text
+ *     or a VIEW alias's source; with a VIEW alias status and X have one entry per kept individual.  Single device: a multi-device
+ *     context works on its first device.  Argument errors (EAGLE_ERR_ARG: a NULL pointer, dims <= 0, n > 2^30 - 1, c outside [1, 15],
+ *     a status outside {-1, 0, 1}, a non-finite X entry of a used individual or beta0 entry, firth outside {0, 1, 2}, tol not in
+ *     (0, 1), max_iter outside [1, 1000], no case or no control among the used individuals) are decided before the context is used;
+ *     with ctx == NULL their text is in eagle_open_error().
+ * ------------------------------------------------------------------------------------------- */
+int eagle_logistic(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long dims[2], const int32_t* status, const double* X, int c,
+                   const double* beta0, int firth, double tol, int max_iter, double max_memory_in_Gbytes, double* stat_out,
+                   int32_t* info_out);
 
 /* ---------------------------------------------------------------------------------------------
  * 1c. Dense n x n model algebra on the device (OPT-IN: north_star keeps calculateH / calculateP / emma.* on
