@@ -36,6 +36,7 @@
 #include "../../include/eagle_hip.h"
 #include "eagle_ctx.h"
 #include "eagle_internal.h"
+#include "eagle_lines.h"
 
 static_assert(EPI_MAX_N == EAGLE_EPI_MAX_N && EPI_YMAX == EAGLE_EPI_YMAX, "eagle_host.h and eagle_hip.h state the same limits");
 
@@ -370,69 +371,41 @@ extern "C" int eagle_epistasis_loci(eagle_ctx* ctx, const char* f_name_ascii_Mt,
     if (const char* bad = epi_loci_arg_error(L, loci, nloci)) return epi_fail(ctx, who, bad);
     if (!ctx) return epi_fail(ctx, who, "no context");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const int threads = host_threads();
     const long k = nloci;
-    const GenoEntry* src = nullptr;
-    int rc = eagle_get_resident(ctx, f_name_ascii_Mt, L, n, max_memory_in_Gbytes, threads, &src);
-    if (rc != EAGLE_OK && rc != EAGLE_STREAM) return rc;
-    const long ld = src ? src->ld : eagle_pad(n);
+    ImageLines lines;
+    int rc = lines.open(ctx, f_name_ascii_Mt, L, n, max_memory_in_Gbytes);
+    if (rc) return rc;
+    const long ld = lines.ld();
     EpiTraitDev tr;
     if ((rc = tr.upload(ctx, y, n))) return rc;
-    std::vector<int32_t> map((size_t)k);
-    DevBuf d_map, B8, uniq_img, msuB, stat, mom;
-    HIPCHK(ctx, d_map.alloc(sizeof(int32_t) * 64));
-    HIPCHK(ctx, B8.alloc((size_t)64 * ld));
+    LociRows B;
+    DevBuf msuB, stat, mom;
     HIPCHK(ctx, msuB.alloc(sizeof(int64_t) * 3 * 64));
     HIPCHK(ctx, stat.alloc(sizeof(double) * (size_t)L * (size_t)k));
     if (mom_out) HIPCHK(ctx, mom.alloc(sizeof(int64_t) * 5 * (size_t)L * (size_t)k));
-    const int8_t* from = src ? src->dev : nullptr;
-    if (src) {
-        for (long i = 0; i < k; i++) map[(size_t)i] = (int32_t)loci[i];
-    } else {
-        std::vector<int32_t> u(loci, loci + k);
-        std::sort(u.begin(), u.end());
-        u.erase(std::unique(u.begin(), u.end()), u.end());
-        for (long i = 0; i < k; i++) map[(size_t)i] = (int32_t)(std::lower_bound(u.begin(), u.end(), (int32_t)loci[i]) - u.begin());
-        HIPCHK(ctx, uniq_img.alloc((size_t)64 * ld));
-        HIPCHK(ctx, hipMemsetAsync(uniq_img.p, 0, (size_t)64 * ld, ctx->stream));
-        std::vector<RowRun> runs;
-        append_keep_runs(u.data(), (long)u.size(), runs);
-        rc = eagle_load_rows(ctx, f_name_ascii_Mt, runs, 0, n, uniq_img.as<int8_t>(), ld, max_memory_in_Gbytes, threads);
-        if (rc) return rc;
-        from = uniq_img.as<int8_t>();
-    }
-    HIPCHK(ctx, hipMemcpyAsync(d_map.p, map.data(), sizeof(int32_t) * (size_t)k, hipMemcpyHostToDevice, ctx->stream));
-    rc = eagle_dev_gather_rows_i8(ctx, from, ld, d_map.as<int32_t>(), k, 64, B8.as<int8_t>(), ld, ctx->stream);
-    if (!rc) rc = eagle_dev_epi_marker(ctx, B8.as<int8_t>(), 64, n, ld, tr.y.as<int32_t>(), msuB.as<int64_t>(), ctx->stream);
+    rc = B.gather(lines, loci, k);
+    if (rc) return rc;
+    rc = eagle_dev_epi_marker(ctx, B.rows(), 64, n, ld, tr.y.as<int32_t>(), msuB.as<int64_t>(), ctx->stream);
     if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
 
-    const long w = src ? L : std::min(L, std::max(512L, stream_chunk_rows_core(eagle_resident_budget(), ld, eagle_pad(L))));
-    const long ntmax = (w + EPI_TM - 1) / EPI_TM;
+    const RowWindows ws = lines.disjoint(std::min(L, std::max(512L, lines.stream_rows())));
+    const long ntmax = (ws.cap + EPI_TM - 1) / EPI_TM;
     std::vector<int32_t> tl((size_t)2 * ntmax, 0);
     for (long a = 0; a < ntmax; a++) tl[(size_t)2 * a] = (int32_t)a;
-    DevBuf tiles, msuA, win;
+    DevBuf tiles, msuA;
     HIPCHK(ctx, tiles.alloc(sizeof(int32_t) * tl.size()));
-    HIPCHK(ctx, msuA.alloc(sizeof(int64_t) * 3 * (size_t)w));
+    HIPCHK(ctx, msuA.alloc(sizeof(int64_t) * 3 * (size_t)ws.cap));
     HIPCHK(ctx, hipMemcpyAsync(tiles.p, tl.data(), sizeof(int32_t) * tl.size(), hipMemcpyHostToDevice, ctx->stream));
-    if (!src) HIPCHK(ctx, win.alloc((size_t)w * ld));
-    for (long r0 = 0; r0 < L; r0 += w) {
-        const long nr = std::min(w, L - r0);
-        const int8_t* img = src ? src->dev : win.as<int8_t>();
-        if (!src) {
-            HIPCHK(ctx, hipMemsetAsync(win.p, 0, (size_t)w * ld, ctx->stream));
-            rc = eagle_dev_load_ascii(ctx, f_name_ascii_Mt, r0, nr, 0, n, win.as<int8_t>(), ld, max_memory_in_Gbytes, threads);
-            if (rc) return rc;
-        }
+    rc = lines.each(ws, [&](const int8_t* img, long r0, long nr, long, long) {
         EpiOut o{};
         o.nloci = (int)k;
         o.stat = stat.as<double>() + r0 * k;
         o.mom = mom_out ? mom.as<int64_t>() + 5 * r0 * k : nullptr;
-        rc = eagle_dev_epi_marker(ctx, img, nr, n, ld, tr.y.as<int32_t>(), msuA.as<int64_t>(), ctx->stream);
-        if (!rc)
-            rc = epi_launch<0>(ctx, img, nr, ld, B8.as<int8_t>(), 64, ld, n, tiles.as<int32_t>(), (nr + EPI_TM - 1) / EPI_TM, tr, msuA.as<int64_t>(),
-                               msuB.as<int64_t>(), o);
-        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-    }
+        const int mrc = eagle_dev_epi_marker(ctx, img, nr, n, ld, tr.y.as<int32_t>(), msuA.as<int64_t>(), ctx->stream);
+        return mrc ? mrc : epi_launch<0>(ctx, img, nr, ld, B.rows(), 64, ld, n, tiles.as<int32_t>(), (nr + EPI_TM - 1) / EPI_TM, tr,
+                                         msuA.as<int64_t>(), msuB.as<int64_t>(), o);
+    });
+    if (rc) return rc;
     HIPCHK(ctx, hipMemcpyAsync(stat_out, stat.p, sizeof(double) * (size_t)L * (size_t)k, hipMemcpyDeviceToHost, ctx->stream));
     if (mom_out) HIPCHK(ctx, hipMemcpyAsync(mom_out, mom.p, sizeof(int64_t) * 5 * (size_t)L * (size_t)k, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));       // `map` and `tl` leave with this frame

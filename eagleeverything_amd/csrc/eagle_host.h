@@ -132,6 +132,37 @@ static inline long stream_chunk_rows_core(size_t budget, long row_bytes, long to
     return rows < total_rows_pad ? rows : total_rows_pad;
 }
 
+// The row windows of one pass over the `rows` lines of an image: window k HOLDS the rows [lo, lo + nr), nr <= cap, and OWNS [c0, c1) --
+// the rows whose results are final after its launch.  The owned ranges tile [0, rows) in order; the rows held are the owned ones with
+// `back` rows before and `fwd` rows behind them, clipped to the file.  Three makers, one per pattern of the passes (each site brings
+// its own capacity: the floor and min(rows, .) are the caller's):
+//   row_windows_disjoint(rows, cap)        held = owned, cap rows each;
+//   row_windows_overlapped(rows, w, ov)    windows of w rows that start every w - ov rows and end with the first one that reaches the
+//                                          last row, which owns the rest (a window's last ov rows are written again by the next one);
+//   row_windows_cores(rows, held_max, h)   cores with a halo of h rows on both sides: one window when held_max >= rows, else cores of
+//                                          held_max - 2 h rows (>= 1: held_max > 2 h is the caller's floor).
+struct RowWindow { long lo, nr, c0, c1; };
+struct RowWindows {
+    long rows, cap, core, back, fwd;
+    bool to_end;     // a window that holds the last row owns everything up to it
+    long at = 0;     // c0 of the next window
+    bool next(RowWindow& w) {
+        if (at >= rows) return false;
+        const long c0 = at, lo = std::max(0L, c0 - back);
+        long c1 = std::min(rows, c0 + core);
+        const long hi = std::min(rows, c1 + fwd);
+        if (to_end && hi >= rows) c1 = rows;
+        w = {lo, hi - lo, c0, c1};
+        at = c1;
+        return true;
+    }
+};
+static inline RowWindows row_windows_disjoint(long rows, long cap) { return {rows, cap, cap, 0, 0, false}; }
+static inline RowWindows row_windows_overlapped(long rows, long w, long overlap) { return {rows, w, w - overlap, 0, overlap, true}; }
+static inline RowWindows row_windows_cores(long rows, long held_max, long halo) {
+    return {rows, held_max, held_max >= rows ? rows : held_max - 2 * halo, halo, halo, false};
+}
+
 // Pieces per worker of an XCD's last, partly filled round of `tail` workers on 32 CUs (0 < tail < 32): the workers are cut along
 // their column-tile pairs into p equal pieces, the tail * p pieces run in ceil(tail * p / 32) rounds of 1/p worker-time each; p <=
 // min(npair, VARA_TAIL_PMAX) minimising that cost (p = 1: one whole worker-time for a round that may be 1/32 full; large p: tail/32).

@@ -28,6 +28,7 @@
 #include <functional>
 
 #include "eagle_ctx.h"
+#include "eagle_lines.h"
 
 extern "C" int eagle_dev_encode_ascii(eagle_ctx* ctx, const int8_t* in, long rows, long cols, long ld_in, uint8_t* out, void* stream);
 extern "C" int eagle_dev_plink_code(eagle_ctx* ctx, const uint8_t* chars, long rows, long L, long row0, uint8_t* alleles0,
@@ -725,6 +726,20 @@ struct BedRing {
         HIPCHK(ctx, hipEventRecord(ev.e[last()], ctx->stream));
         return EAGLE_OK;
     }
+    // The plain pass: the file's L rows in disjoint windows of w, each staged and handed to body(r0, nr, raw), which launches on
+    // ctx->stream and calls release() once the staged rows have been read.  A failure drains the stream (the rule of the header comment).
+    template <class Body>
+    int each(long L, long w, Body body) {
+        RowWindows ws = row_windows_disjoint(L, w);
+        RowWindow win;
+        while (ws.next(win)) {
+            const uint8_t* raw;
+            int rc = stage(win.lo, win.nr, &raw);
+            if (!rc) rc = body(win.lo, win.nr, raw);
+            if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+        }
+        return EAGLE_OK;
+    }
     // write-behind: until everything enqueued before release() of buffer b's last window is done
     int wait(int b) {
         HIPCHK(ctx, hipEventSynchronize(ev.e[b]));
@@ -894,28 +909,15 @@ int qc_fail(eagle_ctx* ctx, int code, const char* msg) {
 // scans use, each loaded through eagle_dev_load_ascii (sidecar, text, or a VIEW's source) and counted before the next one is read.
 static int line_counts(eagle_ctx* ctx, const char* f_name_ascii_Mt, long n, long L, double max_memory_in_Gbytes, int32_t* counts_out) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const int threads = host_threads();
     DevBuf counts;
     HIPCHK(ctx, counts.alloc(sizeof(int32_t) * 3 * (size_t)L));
-    const GenoEntry* src = nullptr;
-    int rc = eagle_get_resident(ctx, f_name_ascii_Mt, L, n, max_memory_in_Gbytes, threads, &src);
-    if (rc != EAGLE_OK && rc != EAGLE_STREAM) return rc;
-    if (rc == EAGLE_OK) {
-        rc = eagle_dev_marker_counts(ctx, src->dev, L, n, src->ld, counts.as<int32_t>(), ctx->stream);
-        if (rc) return rc;
-    } else {
-        const long ld = eagle_pad(n), w = stream_chunk_rows_core(eagle_resident_budget(), ld, eagle_pad(L));
-        DevBuf win;
-        HIPCHK(ctx, win.alloc((size_t)w * ld));
-        for (long r0 = 0; r0 < L; r0 += w) {
-            const long nr = std::min(w, L - r0);
-            HIPCHK(ctx, hipMemsetAsync(win.p, 0, (size_t)w * ld, ctx->stream));
-            rc = eagle_dev_load_ascii(ctx, f_name_ascii_Mt, r0, nr, 0, n, win.as<int8_t>(), ld, max_memory_in_Gbytes, threads);
-            if (rc) return rc;
-            rc = eagle_dev_marker_counts(ctx, win.as<int8_t>(), nr, n, ld, counts.as<int32_t>() + 3 * r0, ctx->stream);
-            if (rc) return rc;
-        }
-    }
+    ImageLines lines;
+    int rc = lines.open(ctx, f_name_ascii_Mt, L, n, max_memory_in_Gbytes);
+    if (rc) return rc;
+    rc = lines.each(lines.disjoint(lines.stream_rows()), [&](const int8_t* img, long r0, long nr, long, long) {
+        return eagle_dev_marker_counts(ctx, img, nr, n, lines.ld(), counts.as<int32_t>() + 3 * r0, ctx->stream);
+    });
+    if (rc) return rc;
     HIPCHK(ctx, hipMemcpyAsync(counts_out, counts.p, sizeof(int32_t) * 3 * (size_t)L, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return EAGLE_OK;
@@ -944,14 +946,11 @@ extern "C" int eagle_bed_marker_counts(eagle_ctx* ctx, const char* bed_path, con
     if (rc) return rc;
     DevBuf counts;
     HIPCHK(ctx, counts.alloc(sizeof(int32_t) * 4 * (size_t)L));
-    for (long r0 = 0; r0 < L; r0 += w) {
-        const long nr = std::min(w, L - r0);
-        const uint8_t* raw;
-        rc = ring.stage(r0, nr, &raw);
-        if (!rc) rc = eagle_dev_bed_marker_counts(ctx, raw, nr, n, counts.as<int32_t>() + 4 * r0, ctx->stream);
-        if (!rc) rc = ring.release();
-        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-    }
+    rc = ring.each(L, w, [&](long r0, long nr, const uint8_t* raw) {
+        const int brc = eagle_dev_bed_marker_counts(ctx, raw, nr, n, counts.as<int32_t>() + 4 * r0, ctx->stream);
+        return brc ? brc : ring.release();
+    });
+    if (rc) return rc;
     HIPCHK(ctx, hipMemcpyAsync(counts_out, counts.p, sizeof(int32_t) * 4 * (size_t)L, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return EAGLE_OK;
@@ -1002,7 +1001,6 @@ extern "C" int eagle_group_counts(eagle_ctx* ctx, const char* f_name_ascii_Mt, c
     if (int arc = group_args(ctx, "group_counts", f_name_ascii_Mt, dims, labels, K, counts_out, sizes)) return arc;
     const long n = dims[0], L = dims[1];
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const int threads = host_threads();
     const long ldh = (n + 15) / 16 * 16;
     const size_t per_row = sizeof(int32_t) * 3 * (size_t)K;
     DevBuf d_lab, onehot, counts;
@@ -1013,27 +1011,14 @@ extern "C" int eagle_group_counts(eagle_ctx* ctx, const char* f_name_ascii_Mt, c
     const int32_t* d_sizes = d_lab.as<int32_t>() + n;
     rc = eagle_dev_group_onehot(ctx, d_lab.as<int32_t>(), n, onehot.as<int8_t>(), ldh, ctx->stream);
     if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-    const GenoEntry* src = nullptr;
-    rc = eagle_get_resident(ctx, f_name_ascii_Mt, L, n, max_memory_in_Gbytes, threads, &src);
-    if (rc != EAGLE_OK && rc != EAGLE_STREAM) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-    if (rc == EAGLE_OK) {
-        rc = eagle_dev_group_counts(ctx, src->dev, L, n, src->ld, onehot.as<int8_t>(), ldh, K, d_sizes, counts.as<int32_t>(), ctx->stream);
-        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-    } else {
-        const long ld = eagle_pad(n), w = stream_chunk_rows_core(eagle_resident_budget(), ld, eagle_pad(L));
-        DevBuf win;
-        HIPCHK(ctx, win.alloc((size_t)w * ld));
-        for (long r0 = 0; r0 < L; r0 += w) {
-            const long nr = std::min(w, L - r0);
-            HIPCHK(ctx, hipMemsetAsync(win.p, 0, (size_t)w * ld, ctx->stream));
-            rc = eagle_dev_load_ascii(ctx, f_name_ascii_Mt, r0, nr, 0, n, win.as<int8_t>(), ld, max_memory_in_Gbytes, threads);
-            if (!rc)
-                rc = eagle_dev_group_counts(ctx, win.as<int8_t>(), nr, n, ld, onehot.as<int8_t>(), ldh, K, d_sizes,
-                                            counts.as<int32_t>() + 3 * (size_t)K * (size_t)r0, ctx->stream);
-            if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-        }
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // `win` is freed on return: its last kernel has finished
-    }
+    ImageLines lines;
+    rc = lines.open(ctx, f_name_ascii_Mt, L, n, max_memory_in_Gbytes);
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }   // the one-hot kernel reads this frame's buffers
+    rc = lines.each(lines.disjoint(lines.stream_rows()), [&](const int8_t* img, long r0, long nr, long, long) {
+        return eagle_dev_group_counts(ctx, img, nr, n, lines.ld(), onehot.as<int8_t>(), ldh, K, d_sizes,
+                                      counts.as<int32_t>() + 3 * (size_t)K * (size_t)r0, ctx->stream);
+    });
+    if (rc) return rc;
     HIPCHK(ctx, hipMemcpyAsync(counts_out, counts.p, per_row * (size_t)L, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return EAGLE_OK;
@@ -1057,16 +1042,12 @@ extern "C" int eagle_bed_group_counts(eagle_ctx* ctx, const char* bed_path, cons
     rc = group_upload(ctx, labels, n, sizes, d_lab);
     if (!rc) rc = eagle_dev_group_bedmask(ctx, d_lab.as<int32_t>(), n, K, planes.as<uint32_t>(), ctx->stream);
     if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-    for (long r0 = 0; r0 < L; r0 += w) {
-        const long nr = std::min(w, L - r0);
-        const uint8_t* raw;
-        rc = ring.stage(r0, nr, &raw);
-        if (!rc)
-            rc = eagle_dev_bed_group_counts(ctx, raw, nr, n, K, planes.as<uint32_t>(), d_lab.as<int32_t>() + n,
-                                            counts.as<int32_t>() + 4 * (size_t)K * (size_t)r0, ctx->stream);
-        if (!rc) rc = ring.release();
-        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-    }
+    rc = ring.each(L, w, [&](long r0, long nr, const uint8_t* raw) {
+        const int brc = eagle_dev_bed_group_counts(ctx, raw, nr, n, K, planes.as<uint32_t>(), d_lab.as<int32_t>() + n,
+                                                   counts.as<int32_t>() + 4 * (size_t)K * (size_t)r0, ctx->stream);
+        return brc ? brc : ring.release();
+    });
+    if (rc) return rc;
     HIPCHK(ctx, hipMemcpyAsync(counts_out, counts.p, per_row * (size_t)L, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return EAGLE_OK;
@@ -1137,7 +1118,6 @@ extern "C" int eagle_logistic(eagle_ctx* ctx, const char* f_name_ascii_Mt, const
         for (int j = 0; j < c; j++) x16[(size_t)i * 16 + j] = X[i + (size_t)n * j];
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const int threads = host_threads();
     DevBuf d_x, d_vy, d_b0, stat, info;
     HIPCHK(ctx, d_x.alloc(sizeof(double) * x16.size()));
     HIPCHK(ctx, d_vy.alloc(vy.size()));
@@ -1148,28 +1128,14 @@ extern "C" int eagle_logistic(eagle_ctx* ctx, const char* f_name_ascii_Mt, const
     HIPCHK(ctx, hipMemcpyAsync(d_vy.p, vy.data(), vy.size(), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(d_b0.p, beta0, sizeof(double) * (size_t)c, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));                  // x16 and vy are pageable host vectors
-    const GenoEntry* src = nullptr;
-    int rc = eagle_get_resident(ctx, f_name_ascii_Mt, L, n, max_memory_in_Gbytes, threads, &src);
-    if (rc != EAGLE_OK && rc != EAGLE_STREAM) return rc;
-    if (rc == EAGLE_OK) {
-        rc = eagle_dev_logistic(ctx, src->dev, L, n, src->ld, d_x.as<double>(), d_vy.as<uint8_t>(), d_b0.as<double>(), c + 1, firth, tol, max_iter,
-                                stat.as<double>(), info.as<int32_t>(), ctx->stream);
-        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-    } else {
-        const long ld = eagle_pad(n), w = stream_chunk_rows_core(eagle_resident_budget(), ld, eagle_pad(L));
-        DevBuf win;
-        HIPCHK(ctx, win.alloc((size_t)w * ld));
-        for (long r0 = 0; r0 < L; r0 += w) {
-            const long nr = std::min(w, L - r0);
-            HIPCHK(ctx, hipMemsetAsync(win.p, 0, (size_t)w * ld, ctx->stream));
-            rc = eagle_dev_load_ascii(ctx, f_name_ascii_Mt, r0, nr, 0, n, win.as<int8_t>(), ld, max_memory_in_Gbytes, threads);
-            if (!rc)
-                rc = eagle_dev_logistic(ctx, win.as<int8_t>(), nr, n, ld, d_x.as<double>(), d_vy.as<uint8_t>(), d_b0.as<double>(), c + 1, firth, tol,
-                                        max_iter, stat.as<double>() + 4 * (size_t)r0, info.as<int32_t>() + 2 * (size_t)r0, ctx->stream);
-            if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-        }
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // `win` is freed on return: its last kernel has finished
-    }
+    ImageLines lines;
+    int rc = lines.open(ctx, f_name_ascii_Mt, L, n, max_memory_in_Gbytes);
+    if (rc) return rc;
+    rc = lines.each(lines.disjoint(lines.stream_rows()), [&](const int8_t* img, long r0, long nr, long, long) {
+        return eagle_dev_logistic(ctx, img, nr, n, lines.ld(), d_x.as<double>(), d_vy.as<uint8_t>(), d_b0.as<double>(), c + 1, firth, tol, max_iter,
+                                  stat.as<double>() + 4 * (size_t)r0, info.as<int32_t>() + 2 * (size_t)r0, ctx->stream);
+    });
+    if (rc) return rc;
     HIPCHK(ctx, hipMemcpyAsync(stat_out, stat.p, sizeof(double) * 4 * (size_t)L, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(info_out, info.p, sizeof(int32_t) * 2 * (size_t)L, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -1421,7 +1387,7 @@ int ld_tile_sq(eagle_ctx* ctx, const int8_t* img, long rows, long n, long ld, in
 }
 
 // Rows of a streamed window of Mt: the streamed scans' rule, and at least 512 so that windows overlapping by up to 256 rows advance.
-long ld_stream_rows(long ld, long L) { return std::max(512L, stream_chunk_rows_core(eagle_resident_budget(), ld, eagle_pad(L))); }
+long ld_stream_rows(const ImageLines& lines) { return std::max(512L, lines.stream_rows()); }
 
 }  // namespace
 
@@ -1438,39 +1404,22 @@ extern "C" int eagle_ld_window(eagle_ctx* ctx, const char* f_name_ascii_Mt, cons
     if (!(r2 >= 0.0 && r2 <= 1.0)) return qc_fail(ctx, EAGLE_ERR_ARG, "ld_window: r2 must be in [0, 1]");
     if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "ld_window: no context");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const int threads = host_threads();
     const long wpr = (window + 63) / 64;
     const size_t mask_bytes = sizeof(uint64_t) * (size_t)L * (size_t)wpr;
     DevBuf mask, counts, sq;
     HIPCHK(ctx, mask.alloc(mask_bytes));
-    const GenoEntry* src = nullptr;
-    int rc = eagle_get_resident(ctx, f_name_ascii_Mt, L, n, max_memory_in_Gbytes, threads, &src);
-    if (rc != EAGLE_OK && rc != EAGLE_STREAM) return rc;
-    if (rc == EAGLE_OK) {
-        HIPCHK(ctx, counts.alloc(sizeof(int32_t) * 3 * (size_t)L));
-        HIPCHK(ctx, sq.alloc(sizeof(int32_t) * 2 * (size_t)L));
-        rc = ld_tile_sq(ctx, src->dev, L, n, src->ld, counts.as<int32_t>(), sq.as<int32_t>());
-        if (rc) return rc;
-        rc = eagle_dev_ld_band(ctx, src->dev, L, n, src->ld, sq.as<int32_t>(), window, r2, mask.as<uint64_t>(), wpr, ctx->stream);
-        if (rc) return rc;
-    } else {
-        const long ld = eagle_pad(n), w = ld_stream_rows(ld, L), step = w - window;
-        DevBuf win;
-        HIPCHK(ctx, win.alloc((size_t)w * ld));
-        HIPCHK(ctx, counts.alloc(sizeof(int32_t) * 3 * (size_t)w));
-        HIPCHK(ctx, sq.alloc(sizeof(int32_t) * 2 * (size_t)w));
-        for (long r0 = 0;; r0 += step) {
-            const long nr = std::min(w, L - r0);
-            HIPCHK(ctx, hipMemsetAsync(win.p, 0, (size_t)w * ld, ctx->stream));
-            rc = eagle_dev_load_ascii(ctx, f_name_ascii_Mt, r0, nr, 0, n, win.as<int8_t>(), ld, max_memory_in_Gbytes, threads);
-            if (rc) return rc;
-            rc = ld_tile_sq(ctx, win.as<int8_t>(), nr, n, ld, counts.as<int32_t>(), sq.as<int32_t>());
-            if (rc) return rc;
-            rc = eagle_dev_ld_band(ctx, win.as<int8_t>(), nr, n, ld, sq.as<int32_t>(), window, r2, mask.as<uint64_t>() + r0 * wpr, wpr, ctx->stream);
-            if (rc) return rc;
-            if (r0 + nr >= L) break;
-        }
-    }
+    ImageLines lines;
+    int rc = lines.open(ctx, f_name_ascii_Mt, L, n, max_memory_in_Gbytes);
+    if (rc) return rc;
+    const long ld = lines.ld();
+    const RowWindows ws = lines.resident() ? row_windows_disjoint(L, L) : row_windows_overlapped(L, ld_stream_rows(lines), window);
+    HIPCHK(ctx, counts.alloc(sizeof(int32_t) * 3 * (size_t)ws.cap));
+    HIPCHK(ctx, sq.alloc(sizeof(int32_t) * 2 * (size_t)ws.cap));
+    rc = lines.each(ws, [&](const int8_t* img, long r0, long nr, long, long) {
+        const int trc = ld_tile_sq(ctx, img, nr, n, ld, counts.as<int32_t>(), sq.as<int32_t>());
+        return trc ? trc : eagle_dev_ld_band(ctx, img, nr, n, ld, sq.as<int32_t>(), window, r2, mask.as<uint64_t>() + r0 * wpr, wpr, ctx->stream);
+    });
+    if (rc) return rc;
     HIPCHK(ctx, hipMemcpyAsync(mask_out, mask.p, mask_bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     long pairs = 0;
@@ -1490,37 +1439,23 @@ namespace {
 
 template <class Consume>
 int ld_panel_cores(eagle_ctx* ctx, const char* f_name_ascii_Mt, long n, long L, long window, double max_memory_in_Gbytes, Consume consume) {
-    const int threads = host_threads();
-    DevBuf counts, sq, band, win;
-    const GenoEntry* src = nullptr;
-    int rc = eagle_get_resident(ctx, f_name_ascii_Mt, L, n, max_memory_in_Gbytes, threads, &src);
-    if (rc != EAGLE_OK && rc != EAGLE_STREAM) return rc;
-    const long ld = src ? src->ld : eagle_pad(n);
-    long held_max;   // rows held for a core, at most
-    if (src) held_max = std::max(1024L, (long)(((size_t)256 << 20) / (sizeof(double) * (size_t)window)));
-    else held_max = std::max(1024L, stream_chunk_rows_core(eagle_resident_budget(), ld, eagle_pad(L)));
-    held_max = std::min(held_max, L);
-    const long core = held_max >= L ? L : held_max - 2 * window;
-    if (!src) HIPCHK(ctx, win.alloc((size_t)held_max * ld));
+    DevBuf counts, sq, band;
+    ImageLines lines;
+    int rc = lines.open(ctx, f_name_ascii_Mt, L, n, max_memory_in_Gbytes);
+    if (rc) return rc;
+    const long ld = lines.ld();
+    // rows held for a core, at most
+    const long held_max = std::min(L, std::max(1024L, lines.resident() ? (long)(((size_t)256 << 20) / (sizeof(double) * (size_t)window)) : lines.stream_rows()));
     HIPCHK(ctx, counts.alloc(sizeof(int32_t) * 3 * (size_t)held_max));
     HIPCHK(ctx, sq.alloc(sizeof(int32_t) * 2 * (size_t)held_max));
     HIPCHK(ctx, band.alloc(sizeof(double) * (size_t)held_max * (size_t)window));
-    for (long c0 = 0; c0 < L; c0 += core) {
-        const long c1 = std::min(L, c0 + core), lo = std::max(0L, c0 - window), hi = std::min(L, c1 + window), nr = hi - lo;
-        const int8_t* img;
-        if (src) img = src->dev + lo * ld;
-        else {
-            HIPCHK(ctx, hipMemsetAsync(win.p, 0, (size_t)held_max * ld, ctx->stream));
-            rc = eagle_dev_load_ascii(ctx, f_name_ascii_Mt, lo, nr, 0, n, win.as<int8_t>(), ld, max_memory_in_Gbytes, threads);
-            if (rc) return rc;
-            img = win.as<int8_t>();
-        }
-        rc = ld_tile_sq(ctx, img, nr, n, ld, counts.as<int32_t>(), sq.as<int32_t>());
-        if (!rc) rc = eagle_dev_ld_r2band(ctx, img, nr, n, ld, sq.as<int32_t>(), window, band.as<double>(), ctx->stream);
-        if (!rc) rc = consume(band.as<double>(), nr, c0 - lo, c1 - lo, lo);
-        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-    }
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // the band and the window leave with this frame
+    rc = lines.each(row_windows_cores(L, held_max, window), [&](const int8_t* img, long lo, long nr, long c0, long c1) {
+        int brc = ld_tile_sq(ctx, img, nr, n, ld, counts.as<int32_t>(), sq.as<int32_t>());
+        if (!brc) brc = eagle_dev_ld_r2band(ctx, img, nr, n, ld, sq.as<int32_t>(), window, band.as<double>(), ctx->stream);
+        return brc ? brc : consume(band.as<double>(), nr, c0 - lo, c1 - lo, lo);
+    });
+    if (rc) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // the band leaves with this frame
     return EAGLE_OK;
 }
 
@@ -1642,24 +1577,33 @@ namespace {
 
 // The panel of a call (the included markers of the file, in file order) on the staging ring: the window rule of the header, and the
 // staging of one window -- the span of file rows that holds the panel markers [lo, hi) goes through the ring to the device, with the
-// offsets of its panel markers' rows when include left rows out.  The caller's kernels read the span, then the caller calls release().
+// offsets of its panel markers' rows when include left rows out.  open() walks the windows once to size the buffers and each() walks them
+// again for the call, both through windows(): the two walks are one loop.
 struct BedPanel {
     BedRing ring;
     long n = 0, linc = 0;
     long S = 0;      // file rows the staging budget holds
     long wmax = 0;   // panel markers of a window, at most
+    long need = 0;   // the markers a window must hold for the call to advance
+    std::function<long(long)> next_of;   // the start of the window after one that ends at hi, or linc when that was the last one
     std::vector<long> fidx;   // panel marker -> file row; empty: the identity
     std::vector<long> offs[2];
     DevBuf d_offs[2];
     long file_row(long p) const { return bed_panel_file_row(fidx, p); }
-    long window_end(long lo, long need) const { return bed_panel_window_end(lo, need, wmax, S, linc, fidx); }
+    // f(lo, hi) for every window [lo, hi) of panel markers in turn, until one returns non-zero
+    template <class F>
+    int windows(F f) const {
+        for (long lo = 0; lo < linc;) {
+            const long hi = bed_panel_window_end(lo, need, wmax, S, linc, fidx);
+            if (int rc = f(lo, hi)) return rc;
+            lo = next_of(hi);
+        }
+        return EAGLE_OK;
+    }
     // Opens the file and sizes everything a call needs; band_rows_max caps the window further (the partners call's band), 0 = no cap.
-    // need = the markers a window must hold for the call to advance; next_of(hi) = the start of the window after one that ends at hi, or
-    // linc when that was the last one.  The caller walks the same windows again: they are a function of the arguments alone.
-    template <class Next>
-    int open(eagle_ctx* ctx, const char* bed_path, long n_, long L, const uint8_t* include, long linc_, double mem_gb, long band_rows_max, long need,
-             Next next_of) {
-        n = n_; linc = linc_;
+    int open(eagle_ctx* ctx, const char* bed_path, long n_, long L, const uint8_t* include, long linc_, double mem_gb, long band_rows_max, long need_,
+             std::function<long(long)> next) {
+        n = n_; linc = linc_; need = need_; next_of = std::move(next);
         if (int orc = ring.open(ctx, bed_path, n, L)) return orc;
         S = bed_stage_rows(ring.rb, mem_gb);
         wmax = std::max(1024L, (long)(((size_t)1 << 27) / (size_t)ld()));   // one operand image of the LD calls stays under 128 MiB
@@ -1669,12 +1613,11 @@ struct BedPanel {
             for (long m = 0; m < L; m++) if (include[m]) fidx.push_back(m);
         }
         long span_max = 1, p_max = 1;
-        for (long lo = 0; lo < linc;) {
-            const long hi = window_end(lo, need);
+        (void)windows([&](long lo, long hi) {
             span_max = std::max(span_max, file_row(hi - 1) - file_row(lo) + 1);
             p_max = std::max(p_max, hi - lo);
-            lo = next_of(hi);
-        }
+            return 0;
+        });
         int rc = ring.ensure(span_max);
         if (rc) return rc;
         if (include) for (int b = 0; b < 2; b++) HIPCHK(ctx, d_offs[b].alloc(sizeof(long) * (size_t)p_max));
@@ -1696,6 +1639,19 @@ struct BedPanel {
         }
         return EAGLE_OK;
     }
+    // The call's pass: every window staged and handed to body(lo, hi, raw, d_off), which launches on the ring's stream and calls
+    // ring.release() once the staged span has been read.  A failure drains the stream (BedRing's rule).
+    template <class Body>
+    int each(Body body) {
+        const int rc = windows([&](long lo, long hi) {
+            const uint8_t* raw;
+            const long* d_off;
+            const int src = stage(lo, hi, &raw, &d_off);
+            return src ? src : body(lo, hi, raw, d_off);
+        });
+        if (rc) (void)hipStreamSynchronize(ring.ctx->stream);
+        return rc;
+    }
 };
 
 // Linc of an include mask (L when it is NULL)
@@ -1714,12 +1670,9 @@ struct BedLdOperands {
         for (DevBuf* d : {&X, &C, &U}) HIPCHK(ctx, d->alloc((size_t)pl.wmax * pl.ld()));
         return EAGLE_OK;
     }
-    int stage(BedPanel& pl, long lo, long hi) {
-        const uint8_t* raw;
-        const long* d_off;
-        int rc = pl.stage(lo, hi, &raw, &d_off);
-        if (!rc) rc = eagle_dev_bed_ld_pack(pl.ring.ctx, raw, pl.file_row(hi - 1) - pl.file_row(lo) + 1, d_off, hi - lo, pl.n, pl.ld(), X.as<int8_t>(),
-                                            C.as<int8_t>(), U.as<int8_t>(), pl.ring.ctx->stream);
+    int stage(BedPanel& pl, long lo, long hi, const uint8_t* raw, const long* d_off) {
+        const int rc = eagle_dev_bed_ld_pack(pl.ring.ctx, raw, pl.file_row(hi - 1) - pl.file_row(lo) + 1, d_off, hi - lo, pl.n, pl.ld(), X.as<int8_t>(),
+                                             C.as<int8_t>(), U.as<int8_t>(), pl.ring.ctx->stream);
         return rc ? rc : pl.ring.release();
     }
 };
@@ -1752,14 +1705,12 @@ extern "C" int eagle_bed_ld_window(eagle_ctx* ctx, const char* bed_path, const l
     const size_t mask_bytes = sizeof(uint64_t) * (size_t)linc * (size_t)wpr;
     DevBuf mask;
     HIPCHK(ctx, mask.alloc(mask_bytes));
-    for (long lo = 0; lo < linc;) {
-        const long hi = pl.window_end(lo, need);
-        rc = op.stage(pl, lo, hi);
-        if (!rc) rc = eagle_dev_bedld_band(ctx, op.X.as<int8_t>(), op.C.as<int8_t>(), op.U.as<int8_t>(), hi - lo, n, pl.ld(), window, r2, min_overlap,
-                                           mask.as<uint64_t>() + lo * wpr, wpr, ctx->stream);
-        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-        lo = next_of(hi);
-    }
+    rc = pl.each([&](long lo, long hi, const uint8_t* raw, const long* d_off) {
+        const int src = op.stage(pl, lo, hi, raw, d_off);
+        return src ? src : eagle_dev_bedld_band(ctx, op.X.as<int8_t>(), op.C.as<int8_t>(), op.U.as<int8_t>(), hi - lo, n, pl.ld(), window, r2,
+                                                min_overlap, mask.as<uint64_t>() + lo * wpr, wpr, ctx->stream);
+    });
+    if (rc) return rc;
     HIPCHK(ctx, hipMemcpyAsync(mask_out, mask.p, mask_bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     long pairs = 0;
@@ -1787,16 +1738,14 @@ int bedld_panel_cores(eagle_ctx* ctx, const char* bed_path, long n, long L, cons
     if (rc) return rc;
     DevBuf band;
     HIPCHK(ctx, band.alloc(sizeof(double) * (size_t)pl.wmax * (size_t)window));
-    for (long lo = 0; lo < linc;) {
-        const long hi = pl.window_end(lo, need), nr = hi - lo;
-        const long c0 = lo == 0 ? 0 : lo + window, c1 = hi >= linc ? linc : hi - window;
-        rc = op.stage(pl, lo, hi);
-        if (!rc) rc = eagle_dev_bedld_r2band(ctx, op.X.as<int8_t>(), op.C.as<int8_t>(), op.U.as<int8_t>(), nr, n, pl.ld(), window, min_overlap,
-                                             band.as<double>(), ctx->stream);
-        if (!rc) rc = consume(band.as<double>(), nr, c0 - lo, c1 - lo, lo);
-        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-        lo = next_of(hi);
-    }
+    rc = pl.each([&](long lo, long hi, const uint8_t* raw, const long* d_off) {
+        const long nr = hi - lo, c0 = lo == 0 ? 0 : lo + window, c1 = hi >= linc ? linc : hi - window;
+        int brc = op.stage(pl, lo, hi, raw, d_off);
+        if (!brc) brc = eagle_dev_bedld_r2band(ctx, op.X.as<int8_t>(), op.C.as<int8_t>(), op.U.as<int8_t>(), nr, n, pl.ld(), window, min_overlap,
+                                               band.as<double>(), ctx->stream);
+        return brc ? brc : consume(band.as<double>(), nr, c0 - lo, c1 - lo, lo);
+    });
+    if (rc) return rc;
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // the operand images and the band leave with this frame
     return EAGLE_OK;
 }
@@ -1965,29 +1914,14 @@ extern "C" int eagle_roh(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long
     if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "roh: no context");
     int rc = roh_begin(ctx, "roh", b, n, L, pos);
     if (rc) return rc;
-    const int threads = host_threads();
-    const GenoEntry* src = nullptr;
-    rc = eagle_get_resident(ctx, f_name_ascii_Mt, L, n, max_memory_in_Gbytes, threads, &src);
-    if (rc != EAGLE_OK && rc != EAGLE_STREAM) return rc;
-    if (rc == EAGLE_OK) {
-        rc = eagle_dev_roh_flags_i8(ctx, src->dev, src->ld, n, 0, 0, L, b.blk.as<int32_t>(), b.nb(), params, b.planes.as<uint64_t>(), L, ctx->stream);
-        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-    } else {
-        const long ld = eagle_pad(n), h = params->w - 1;
-        const long held_max = std::min(L, std::max(256L, stream_chunk_rows_core(eagle_resident_budget(), ld, eagle_pad(L))));
-        const long core = held_max >= L ? L : held_max - 2 * h;
-        DevBuf win;
-        HIPCHK(ctx, win.alloc((size_t)held_max * ld));
-        for (long c0 = 0; c0 < L; c0 += core) {
-            const long c1 = std::min(L, c0 + core), lo = std::max(0L, c0 - h), hi = std::min(L, c1 + h), nr = hi - lo;
-            HIPCHK(ctx, hipMemsetAsync(win.p, 0, (size_t)held_max * ld, ctx->stream));
-            rc = eagle_dev_load_ascii(ctx, f_name_ascii_Mt, lo, nr, 0, n, win.as<int8_t>(), ld, max_memory_in_Gbytes, threads);
-            if (!rc) rc = eagle_dev_roh_flags_i8(ctx, win.as<int8_t>(), ld, n, lo, c0, c1, b.blk.as<int32_t>(), b.nb(), params,
-                                                 b.planes.as<uint64_t>(), L, ctx->stream);
-            if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-        }
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // the window leaves with this scope
-    }
+    ImageLines lines;
+    rc = lines.open(ctx, f_name_ascii_Mt, L, n, max_memory_in_Gbytes);
+    if (rc) return rc;
+    const long held_max = lines.resident() ? L : std::min(L, std::max(256L, lines.stream_rows()));
+    rc = lines.each(row_windows_cores(L, held_max, params->w - 1), [&](const int8_t* img, long lo, long, long c0, long c1) {
+        return eagle_dev_roh_flags_i8(ctx, img, lines.ld(), n, lo, c0, c1, b.blk.as<int32_t>(), b.nb(), params, b.planes.as<uint64_t>(), L, ctx->stream);
+    });
+    if (rc) return rc;
     return roh_end(ctx, b, params, ind_out, seg_out, seg_cap, nseg_out);
 }
 
@@ -2012,18 +1946,13 @@ extern "C" int eagle_bed_roh(eagle_ctx* ctx, const char* bed_path, const long di
     auto next_of = [&](long hi) { return hi >= linc ? linc : hi - 2 * h; };
     rc = pl.open(ctx, bed_path, n, L, include, linc, max_memory_in_Gbytes, 0, need, next_of);
     if (rc) return rc;
-    for (long lo = 0; lo < linc;) {
-        const long hi = pl.window_end(lo, need);
+    rc = pl.each([&](long lo, long hi, const uint8_t* raw, const long* d_off) {
         const long c0 = lo == 0 ? 0 : lo + h, c1 = hi >= linc ? linc : hi - h;
-        const uint8_t* raw;
-        const long* d_off;
-        rc = pl.stage(lo, hi, &raw, &d_off);
-        if (!rc) rc = eagle_dev_roh_flags_bed(ctx, raw, d_off, n, lo, c0, c1, b.blk.as<int32_t>(), b.nb(), params, b.planes.as<uint64_t>(), linc,
-                                              ctx->stream);
-        if (!rc) rc = pl.ring.release();
-        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-        lo = next_of(hi);
-    }
+        const int brc = eagle_dev_roh_flags_bed(ctx, raw, d_off, n, lo, c0, c1, b.blk.as<int32_t>(), b.nb(), params, b.planes.as<uint64_t>(), linc,
+                                                ctx->stream);
+        return brc ? brc : pl.ring.release();
+    });
+    if (rc) return rc;
     return roh_end(ctx, b, params, ind_out, seg_out, seg_cap, nseg_out);
 }
 
@@ -2068,27 +1997,11 @@ struct GenoPlanes {
 
   private:
     int fill_image(eagle_ctx* ctx, const char* f_name_ascii_M, long L, double mem_gb) {
-        const int threads = host_threads();
-        const GenoEntry* src = nullptr;
-        int rc = eagle_get_resident(ctx, f_name_ascii_M, n, L, mem_gb, threads, &src);
-        if (rc != EAGLE_OK && rc != EAGLE_STREAM) return rc;
-        if (rc == EAGLE_OK) {
-            rc = eagle_dev_ibd_planes_i8(ctx, src->dev, src->ld, 0, n, n, L, p(), ctx->stream);
-            if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-            return EAGLE_OK;
-        }
-        const long ld = eagle_pad(L), w = std::min(n, stream_chunk_rows_core(eagle_resident_budget(), ld, eagle_pad(n)));
-        DevBuf win;
-        HIPCHK(ctx, win.alloc((size_t)w * ld));
-        for (long r0 = 0; r0 < n; r0 += w) {
-            const long nr = std::min(w, n - r0);
-            HIPCHK(ctx, hipMemsetAsync(win.p, 0, (size_t)w * ld, ctx->stream));
-            rc = eagle_dev_load_ascii(ctx, f_name_ascii_M, r0, nr, 0, L, win.as<int8_t>(), ld, mem_gb, threads);
-            if (!rc) rc = eagle_dev_ibd_planes_i8(ctx, win.as<int8_t>(), ld, r0, nr, n, L, p(), ctx->stream);
-            if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-        }
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // the window leaves with this scope
-        return EAGLE_OK;
+        ImageLines lines;
+        if (int rc = lines.open(ctx, f_name_ascii_M, n, L, mem_gb)) return rc;
+        return lines.each(lines.disjoint(std::min(n, lines.stream_rows())), [&](const int8_t* img, long r0, long nr, long, long) {
+            return eagle_dev_ibd_planes_i8(ctx, img, lines.ld(), r0, nr, n, L, p(), ctx->stream);
+        });
     }
     int fill_bed(eagle_ctx* ctx, const char* bed_path, long L, const uint8_t* include, double mem_gb) {
         BedPanel pl;
@@ -2096,16 +2009,11 @@ struct GenoPlanes {
         auto next_of = [&](long hi) { return hi >= linc ? linc : hi / 64 * 64; };
         int rc = pl.open(ctx, bed_path, n, L, include, linc, mem_gb, 0, need, next_of);
         if (rc) return rc;
-        for (long lo = 0; lo < linc;) {
-            const long hi = pl.window_end(lo, need), nxt = next_of(hi);
-            const uint8_t* raw;
-            const long* d_off;
-            rc = pl.stage(lo, hi, &raw, &d_off);
-            if (!rc) rc = eagle_dev_ibd_planes_bed(ctx, raw, d_off, n, lo, lo / 64, (nxt + 63) / 64, linc, p(), ctx->stream);
-            if (!rc) rc = pl.ring.release();
-            if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-            lo = nxt;
-        }
+        rc = pl.each([&](long lo, long hi, const uint8_t* raw, const long* d_off) {
+            const int brc = eagle_dev_ibd_planes_bed(ctx, raw, d_off, n, lo, lo / 64, (next_of(hi) + 63) / 64, linc, p(), ctx->stream);
+            return brc ? brc : pl.ring.release();
+        });
+        if (rc) return rc;
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // the ring and the offsets leave with this frame
         return EAGLE_OK;
     }
@@ -2428,52 +2336,19 @@ extern "C" int eagle_ld_dots(eagle_ctx* ctx, const char* f_name_ascii_Mt, const 
         if (loci[i] < 0 || loci[i] >= L) return qc_fail(ctx, EAGLE_ERR_ARG, "ld_dots: locus outside [0, L)");
     if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "ld_dots: no context");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const int threads = host_threads();
     const long k = nloci;
-    const GenoEntry* src = nullptr;
-    int rc = eagle_get_resident(ctx, f_name_ascii_Mt, L, n, max_memory_in_Gbytes, threads, &src);
-    if (rc != EAGLE_OK && rc != EAGLE_STREAM) return rc;
-    const long ld = src ? src->ld : eagle_pad(n);
-    std::vector<int32_t> map((size_t)k);
-    DevBuf d_map, B8, dots, uniq_img;
-    HIPCHK(ctx, d_map.alloc(sizeof(int32_t) * 64));
-    HIPCHK(ctx, B8.alloc((size_t)64 * ld));
+    ImageLines lines;
+    int rc = lines.open(ctx, f_name_ascii_Mt, L, n, max_memory_in_Gbytes);
+    if (rc) return rc;
+    LociRows B;
+    DevBuf dots;
     HIPCHK(ctx, dots.alloc(sizeof(int32_t) * (size_t)L * (size_t)k));
-    const int8_t* from = src ? src->dev : nullptr;
-    if (src) {
-        for (long i = 0; i < k; i++) map[(size_t)i] = (int32_t)loci[i];
-    } else {
-        std::vector<int32_t> u(loci, loci + k);
-        std::sort(u.begin(), u.end());
-        u.erase(std::unique(u.begin(), u.end()), u.end());
-        for (long i = 0; i < k; i++) map[(size_t)i] = (int32_t)(std::lower_bound(u.begin(), u.end(), (int32_t)loci[i]) - u.begin());
-        HIPCHK(ctx, uniq_img.alloc((size_t)64 * ld));
-        HIPCHK(ctx, hipMemsetAsync(uniq_img.p, 0, (size_t)64 * ld, ctx->stream));
-        std::vector<RowRun> runs;
-        append_keep_runs(u.data(), (long)u.size(), runs);
-        rc = eagle_load_rows(ctx, f_name_ascii_Mt, runs, 0, n, uniq_img.as<int8_t>(), ld, max_memory_in_Gbytes, threads);
-        if (rc) return rc;
-        from = uniq_img.as<int8_t>();
-    }
-    HIPCHK(ctx, hipMemcpyAsync(d_map.p, map.data(), sizeof(int32_t) * (size_t)k, hipMemcpyHostToDevice, ctx->stream));
-    rc = eagle_dev_gather_rows_i8(ctx, from, ld, d_map.as<int32_t>(), k, 64, B8.as<int8_t>(), ld, ctx->stream);
-    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-    if (src) {
-        rc = eagle_dev_ld_dots(ctx, src->dev, L, n, ld, B8.as<int8_t>(), k, dots.as<int32_t>(), ctx->stream);
-        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-    } else {
-        const long w = ld_stream_rows(ld, L);
-        DevBuf win;
-        HIPCHK(ctx, win.alloc((size_t)w * ld));
-        for (long r0 = 0; r0 < L; r0 += w) {
-            const long nr = std::min(w, L - r0);
-            HIPCHK(ctx, hipMemsetAsync(win.p, 0, (size_t)w * ld, ctx->stream));
-            rc = eagle_dev_load_ascii(ctx, f_name_ascii_Mt, r0, nr, 0, n, win.as<int8_t>(), ld, max_memory_in_Gbytes, threads);
-            if (rc) return rc;
-            rc = eagle_dev_ld_dots(ctx, win.as<int8_t>(), nr, n, ld, B8.as<int8_t>(), k, dots.as<int32_t>() + r0 * k, ctx->stream);
-            if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-        }
-    }
+    rc = B.gather(lines, loci, k);
+    if (rc) return rc;
+    rc = lines.each(lines.disjoint(ld_stream_rows(lines)), [&](const int8_t* img, long r0, long nr, long, long) {
+        return eagle_dev_ld_dots(ctx, img, nr, n, lines.ld(), B.rows(), k, dots.as<int32_t>() + r0 * k, ctx->stream);
+    });
+    if (rc) return rc;
     HIPCHK(ctx, hipMemcpyAsync(dots_out, dots.p, sizeof(int32_t) * (size_t)L * (size_t)k, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return EAGLE_OK;
@@ -2509,14 +2384,11 @@ extern "C" int eagle_bed_sample_counts(eagle_ctx* ctx, const char* bed_path, con
     DevBuf counts;
     HIPCHK(ctx, counts.alloc(sizeof(int32_t) * 4 * (size_t)n));
     HIPCHK(ctx, hipMemsetAsync(counts.p, 0, sizeof(int32_t) * 4 * (size_t)n, ctx->stream));
-    for (long r0 = 0; r0 < L; r0 += w) {
-        const long nr = std::min(w, L - r0);
-        const uint8_t* raw;
-        rc = ring.stage(r0, nr, &raw);
-        if (!rc) rc = eagle_dev_bed_sample_counts(ctx, raw, nr, n, counts.as<int32_t>(), ctx->stream);
-        if (!rc) rc = ring.release();
-        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-    }
+    rc = ring.each(L, w, [&](long, long nr, const uint8_t* raw) {
+        const int brc = eagle_dev_bed_sample_counts(ctx, raw, nr, n, counts.as<int32_t>(), ctx->stream);
+        return brc ? brc : ring.release();
+    });
+    if (rc) return rc;
     HIPCHK(ctx, hipMemcpyAsync(counts_out, counts.p, sizeof(int32_t) * 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return EAGLE_OK;
@@ -2566,16 +2438,15 @@ extern "C" int eagle_bed_sample_ibs(eagle_ctx* ctx, const char* bed_path, const 
         HIPCHK(ctx, dinc.alloc((size_t)L));
         HIPCHK(ctx, hipMemcpyAsync(dinc.p, include, (size_t)L, hipMemcpyHostToDevice, ctx->stream));
     }
-    for (long r0 = 0; r0 < L; r0 += w) {
-        const long nr = std::min(w, L - r0), nrp = eagle_pad(nr);
-        const uint8_t* raw;
-        rc = ring.stage(r0, nr, &raw);
-        if (!rc) rc = eagle_dev_bed_pack_fp4(ctx, raw, nr, n, include ? dinc.as<uint8_t>() + r0 : nullptr, np, nrp, m4, ld4, (long)plane, ctx->stream);
-        if (!rc) rc = ring.release();     // the staging buffer is free once the pack has read it
-        for (int p = 0; p < 4 && !rc; p++)
-            rc = eagle_dev_mmt_accumulate_f4(ctx, m4 + (size_t)p * plane, np, nrp, ld4, acc.as<int32_t>() + (size_t)p * accn, ctx->stream);
-        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-    }
+    rc = ring.each(L, w, [&](long r0, long nr, const uint8_t* raw) {
+        const long nrp = eagle_pad(nr);
+        int brc = eagle_dev_bed_pack_fp4(ctx, raw, nr, n, include ? dinc.as<uint8_t>() + r0 : nullptr, np, nrp, m4, ld4, (long)plane, ctx->stream);
+        if (!brc) brc = ring.release();     // the staging buffer is free once the pack has read it
+        for (int p = 0; p < 4 && !brc; p++)
+            brc = eagle_dev_mmt_accumulate_f4(ctx, m4 + (size_t)p * plane, np, nrp, ld4, acc.as<int32_t>() + (size_t)p * accn, ctx->stream);
+        return brc;
+    });
+    if (rc) return rc;
     rc = eagle_bed_ibs_results(ctx, acc.as<int32_t>(), n, linc, min_overlap, ncalled_out, ibs0_out, hethet_out, hetsum_out, dist_out);
     if (rc) (void)hipStreamSynchronize(ctx->stream);
     return rc;
@@ -2650,7 +2521,6 @@ extern "C" int eagle_weighted_gram(eagle_ctx* ctx, const char* f_name_ascii_M, c
 static int line_scores(eagle_ctx* ctx, const char* path, long rows, long cols, const int32_t* w, long T, int plane_mask,
                        double max_memory_in_Gbytes, int64_t* out) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const int threads = host_threads();
     const size_t outb = sizeof(int64_t) * (size_t)rows * (size_t)T;
     if (!plane_mask) {   // every weight is zero: no product, and the file is not read
         memset(out, 0, outb);
@@ -2658,13 +2528,12 @@ static int line_scores(eagle_ctx* ctx, const char* path, long rows, long cols, c
     }
     // a resident image has 256-padded lines; the longest lines the engine addresses fit it only at the 128-padding of a band
     const bool narrow = (double)eagle_pad(cols) * 256.0 >= 2147483648.0;
-    const GenoEntry* src = nullptr;
-    int rc = narrow ? EAGLE_STREAM : eagle_get_resident(ctx, path, rows, cols, max_memory_in_Gbytes, threads, &src);
-    if (rc != EAGLE_OK && rc != EAGLE_STREAM) return rc;
-    const bool resident = rc == EAGLE_OK;
-    const long ld = resident ? src->ld : (cols + 127) / 128 * 128;
-    const long band = resident ? rows : std::min(rows, stream_chunk_rows_core(eagle_resident_budget(), ld, eagle_pad(rows)));
-    DevBuf dw, dB, c32, dout, win;
+    ImageLines lines;
+    int rc = lines.open(ctx, path, rows, cols, max_memory_in_Gbytes, narrow, (cols + 127) / 128 * 128);
+    if (rc) return rc;
+    const long ld = lines.ld();
+    const long band = lines.resident() ? rows : std::min(rows, lines.stream_rows());
+    DevBuf dw, dB, c32, dout;
     HIPCHK(ctx, dout.alloc(outb));
     HIPCHK(ctx, dw.alloc(sizeof(int32_t) * (size_t)T * (size_t)cols));
     HIPCHK(ctx, dB.alloc((size_t)eagle_score_b_rows(T, plane_mask) * (size_t)ld));
@@ -2672,21 +2541,10 @@ static int line_scores(eagle_ctx* ctx, const char* path, long rows, long cols, c
     HIPCHK(ctx, hipMemcpyAsync(dw.p, w, sizeof(int32_t) * (size_t)T * (size_t)cols, hipMemcpyHostToDevice, ctx->stream));
     rc = eagle_dev_score_digits(ctx, dw.as<int32_t>(), T, cols, ld, plane_mask, dB.as<int8_t>(), ctx->stream);
     if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-    if (resident) {
-        rc = eagle_dev_line_scores(ctx, src->dev, rows, cols, ld, dB.as<int8_t>(), T, plane_mask, c32.as<int32_t>(), dout.as<int64_t>(), ctx->stream);
-        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-    } else {
-        const long wrows = eagle_pad(band);
-        HIPCHK(ctx, win.alloc((size_t)wrows * (size_t)ld));
-        for (long r0 = 0; r0 < rows; r0 += band) {
-            const long nr = std::min(band, rows - r0);
-            HIPCHK(ctx, hipMemsetAsync(win.p, 0, (size_t)wrows * (size_t)ld, ctx->stream));
-            rc = eagle_dev_load_ascii(ctx, path, r0, nr, 0, cols, win.as<int8_t>(), ld, max_memory_in_Gbytes, threads);
-            if (!rc) rc = eagle_dev_line_scores(ctx, win.as<int8_t>(), nr, cols, ld, dB.as<int8_t>(), T, plane_mask, c32.as<int32_t>(),
-                                                dout.as<int64_t>() + r0 * T, ctx->stream);
-            if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-        }
-    }
+    rc = lines.each(row_windows_disjoint(rows, band), [&](const int8_t* img, long r0, long nr, long, long) {
+        return eagle_dev_line_scores(ctx, img, nr, cols, ld, dB.as<int8_t>(), T, plane_mask, c32.as<int32_t>(), dout.as<int64_t>() + r0 * T, ctx->stream);
+    }, eagle_pad(band));   // eagle_dev_line_scores wants the rows up to the next multiple of 256 allocated
+    if (rc) return rc;
     HIPCHK(ctx, hipMemcpyAsync(out, dout.p, outb, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return EAGLE_OK;

@@ -41,9 +41,10 @@ def test_mendel_symbols_declared_exported_and_bound():
     for k in ("k_mendel_trios", "k_plane_gather", "k_parentage", "k_parentage_finish"):
         assert k in kern
     assert "asm" not in re.sub(r"//.*", "", kern)
-    # one helper builds the planes of all six entry points
+    # one helper builds the planes of all six entry points: one launch site per source (the image through the line walker, the .bed ring)
     ing = open(os.path.join(ROOT, "eagleeverything_amd", "csrc", "eagle_ingest.cpp")).read()
-    assert len(re.findall(r"\bg\.build\(ctx, \"", ing)) == 6 and len(re.findall(r"eagle_dev_ibd_planes_(?:i8|bed)\(", ing)) == 3
+    assert len(re.findall(r"\bg\.build\(ctx, \"", ing)) == 6
+    assert len(re.findall(r"eagle_dev_ibd_planes_i8\(", ing)) == 1 and len(re.findall(r"eagle_dev_ibd_planes_bed\(", ing)) == 1
 
 
 def test_header_states_the_rule_and_what_is_not_claimed():
