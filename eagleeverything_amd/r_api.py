@@ -2365,7 +2365,13 @@ def epistasis_host(G, yq, loci=None, chrom=None, gap=0, min_stat=0.0, hit_cap=No
     s, q, u = Gi.sum(axis=0), G2.sum(axis=0), y @ Gi
     cols = np.arange(L) if loci is None else np.atleast_1d(np.asarray(loci, dtype=np.int64)).ravel()
     Bj, B2 = Gi[:, cols], G2[:, cols]
-    mom = np.stack([Gi.T @ Bj, G2.T @ Bj, Gi.T @ B2, G2.T @ B2, (Gi * y[:, None]).T @ Bj], axis=-1)
+    # Every term of the five products is an integer of at most max|y| in absolute value, so every partial sum of the n terms, in any
+    # order, stays below n max|y|: under 2^53 the fp64 product (BLAS) is the exact integer, and numpy's int64 loop is not needed.
+    if n * max(1, int(np.abs(y).max()) if n else 1) < 1 << 53:
+        dot = lambda a, b: np.rint(a.astype(np.float64).T @ b.astype(np.float64)).astype(np.int64)      # noqa: E731
+    else:
+        dot = lambda a, b: a.T @ b                                                                      # noqa: E731
+    mom = np.stack([dot(Gi, Bj), dot(G2, Bj), dot(Gi, B2), dot(G2, B2), dot(Gi * y[:, None], Bj)], axis=-1)
     if loci is not None:
         S = _epi_sums(n, Y, T, (s[:, None], q[:, None], u[:, None]), (s[cols][None, :], q[cols][None, :], u[cols][None, :]), mom)
         return {"stat": _epi_stat(n, *S), "mom": mom}

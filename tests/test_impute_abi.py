@@ -116,3 +116,20 @@ def test_python_wrappers_refuse_before_the_library(tmp_path):
         rcpp_api.knn_rows(np.zeros((3, 3)) + 0.5, np.zeros((3, 3)), 2)
     with pytest.raises(ValueError):
         rcpp_api.bed_impute_knn(str(tmp_path / "a.bed"), (4, 2), np.zeros((3, 2), dtype=np.int32), 1, 1, str(tmp_path / "b.bed"))
+
+
+def test_regime_thresholds_of_the_kernels_are_where_the_gpu_cases_expect_them():
+    """tests/test_gpu_regimes.py runs k_bed_impute on both sides of these thresholds and the two kNN kernels at their LDS maximum; a
+    change here must move its cases (tests/regimes_truth.py restates the arithmetic)."""
+    src = re.sub(r"//.*", "", open(os.path.join(ROOT, "eagleeverything_amd", "csrc", "eagle_impute.hip")).read())
+    flat = " ".join(src.split())
+    assert "#define IMP_STAGE_BYTES (EAGLE_IMPUTE_MAX_N / 4)" in flat and "#define IMP_MAX_ROWS 256" in flat
+    assert "std::max(1L, std::min(std::min((long)IMP_STAGE_BYTES / rb, (long)IMP_MAX_ROWS), std::max(1L, 16384L / rb)))" in flat
+    assert "__shared__ uint8_t stage[IMP_STAGE_BYTES];" in flat and "__shared__ int cnt[IMP_MAX_ROWS][2];" in flat
+    # the two thread layouts: all three uses of the threshold, and the 256 threads they are written for
+    assert flat.count("rb >= 256") == 3 and "const int rpp = rb >= 256 ? 1 : (int)(256 / rb);" in flat
+    assert "const int sub = rb >= 256 ? 0 : (int)(tid / rb);" in flat and "for (long b = rb >= 256 ? tid : tid - sub * rb; b < rb; b += 256)" in flat
+    assert "hipLaunchKernelGGL(k_bed_impute, dim3((unsigned)blocks), dim3(256), 0," in flat
+    # 4 n bytes of dynamic LDS, allowed up to 4 EAGLE_KNN_MAX_N
+    assert flat.count("hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (int)EAGLE_KNN_MAX_N") == 2
+    assert flat.count("dim3((unsigned)n), dim3(256), (size_t)(4 * n)") == 2 and "for (int j = tid; j < n; j += 256)" in flat

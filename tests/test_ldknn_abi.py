@@ -149,3 +149,16 @@ def test_python_wrappers_refuse_before_the_library(tmp_path):
         rcpp_api.bed_impute_ldknn(str(tmp_path / "a.bed"), (4, 2), np.zeros((3, 2), dtype=np.int32), 1, 1, 1, str(tmp_path / "b.bed"))
     with pytest.raises(ValueError):
         rcpp_api.bed_impute_ldknn(str(tmp_path / "a.bed"), (4, 2), np.zeros((2, 2)) + 0.5, 1, 1, 1, str(tmp_path / "b.bed"))
+
+
+def test_regime_thresholds_of_the_kernel_are_where_the_gpu_cases_expect_them():
+    """tests/test_gpu_regimes.py runs k_bed_impute_ldknn past one trip of its 512-thread column loops and at 150 KiB of LDS; a change
+    here must move its cases (tests/regimes_truth.py restates the arithmetic)."""
+    src = re.sub(r"//.*", "", open(os.path.join(ROOT, "eagleeverything_amd", "csrc", "eagle_ldknn.hip")).read())
+    flat = " ".join(src.split())
+    assert "#define LDK_THREADS 512" in flat and "__launch_bounds__(LDK_THREADS)" in flat and "dim3(LDK_THREADS), ldk_lds_bytes(n)" in flat
+    assert "return (size_t)(3 * ((n + 3) / 4 * 4) + 2 * ((bed_row_bytes(n) + 3) / 4)) * 4;" in flat
+    assert "for (int b = tid; b < (int)rb; b += LDK_THREADS)" in flat and flat.count("for (long b = tid; b < rb; b += LDK_THREADS)") == 2
+    assert "for (int b = tid; b < 4 * rbw; b += LDK_THREADS)" in flat
+    assert "hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldk_lds_bytes(EAGLE_LDKNN_MAX_N)" in flat
+    assert re.search(r"#define\s+EAGLE_LDKNN_MAX_N\s+12288L", open(os.path.join(ROOT, "include", "eagle_hip.h")).read())

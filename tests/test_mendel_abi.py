@@ -214,3 +214,16 @@ def test_mendel_host_pieces_under_asan_ubsan(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "mendel host checks passed" in r.stdout
+
+
+def test_the_two_chunk_loops_of_65535_are_where_the_gpu_cases_expect_them():
+    """tests/test_gpu_regimes.py runs the second batch of both loops; a change here must move its cases."""
+    flat = " ".join(re.sub(r"//.*", "", open(os.path.join(ROOT, "eagleeverything_amd", "csrc", "eagle_mendel.hip")).read()).split())
+    assert "for (long w0 = 0; w0 < nwords; w0 += 65535) {" in flat and "const long nw = nwords - w0 < 65535 ? nwords - w0 : 65535;" in flat
+    assert "planes + w0 * np, np, nwords, nplanes, idx, cnt, cp, dst + w0 * cp);" in flat and "dim3((unsigned)(cp / 64), (unsigned)nw)" in flat
+    assert "no > 65535" in flat and "const long oc = o0 + blockIdx.y;" in flat and "best_out + 8 * (o0 + (long)blockIdx.x) + 4 * lane" in flat
+    ingest = " ".join(re.sub(r"//.*", "", open(os.path.join(ROOT, "eagleeverything_amd", "csrc", "eagle_ingest.cpp")).read()).split())
+    assert "std::min(std::min(n_o, 65535L), ((long)1 << 28) / per)" in ingest and "for (long o0 = 0; o0 < n_o; o0 += chunk)" in ingest
+    # the parentage search is the one caller of the gather, over all the panel's words at once; the trio pass never gathers
+    assert ingest.count("eagle_dev_plane_gather(") == 1
+    assert "eagle_dev_plane_gather(ctx, g.p(), g.nplanes, g.n, g.lp, sd.idx.as<int32_t>(), cnt, sd.sub.as<uint64_t>(), ctx->stream)" in ingest
