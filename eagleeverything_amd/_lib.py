@@ -28,6 +28,22 @@ class IbdParams(C.Structure):
     _fields_ = [(f, C.c_int64) for f in ("mode", "min_snp", "min_len", "max_gap", "merge_min")]
 
 
+# The kernel-form switch of eagle_dev_set_tune: enum EagleTune of csrc/eagle_ctx.h without the TUNE_ prefix (what each name selects is
+# written there).  A number that is not listed selects the shipped forms.
+TUNE = {
+    "SHIPPED": 0,
+    "VARA_256": 8,
+    "COMPILER_SCHEDULED": 9,
+    "SYRK_F4P": 10,
+    "SYRK_F4W": 11,
+    "VARA_PACED": 14,
+    "SPECTRAL_OFF": 29,
+    "W8_UNPIPED": 31,
+    "W8_ROWPASS_SPLIT": 32,
+    "GRAM_TWICE": 33,
+    "VARA_UPPER": 34,
+}
+
 # name -> (restype, argtypes); must list every symbol include/eagle_hip.h declares
 SIGNATURES = {
     "eagle_open": (C.c_void_p, [C.c_int]),
@@ -214,6 +230,7 @@ SIGNATURES = {
                                        C.c_void_p]),
     # internal helpers exported for tests / the sharded driver
     "eagle_dev_set_tune": (None, [C.c_void_p, C.c_int]),
+    "eagle_tune_known": (C.c_int, [C.c_int]),
     "eagle_w8_host_work_list": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_long,
                                           C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_int)]),
     "eagle_w8_host_bound": (C.c_double, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_long]),

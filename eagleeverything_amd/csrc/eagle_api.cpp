@@ -157,9 +157,9 @@ extern "C" eagle_ctx* eagle_open(int device) {
         delete ctx;
         return nullptr;
     }
-    // EAGLE_HIP_TUNE=9: the compiler-scheduled forms of the two hand-scheduled kernels (k_vara_i8w, k_syrk_f4) for a whole session:
-    // same results bit for bit, 3-8 % slower; a switch for ruling the inline-asm kernels out when chasing a problem
-    if (const char* tv = getenv("EAGLE_HIP_TUNE")) ctx->tune = atoi(tv);
+    // EAGLE_HIP_TUNE=9 (TUNE_COMPILER_SCHEDULED): the compiler-scheduled forms of the two hand-scheduled kernels (k_vara_i8w, k_syrk_f4) for
+    // a whole session: same results bit for bit, 3-8 % slower; a switch for ruling the inline-asm kernels out when chasing a problem
+    if (const char* tv = getenv("EAGLE_HIP_TUNE")) ctx->tune = tune_known(atoi(tv));
     if (const char* ag = getenv("EAGLE_HIP_ARENA_GB")) {   // reserve the scan arena at open (background thread), e.g. 100 for 50,000 individuals
         const double gb = atof(ag);
         if (gb > 0.0 && gb < 4096.0) arena_prefetch(ctx, (size_t)(gb * 1e9));

@@ -71,6 +71,32 @@ struct SCache {
     void release();
 };
 
+// The kernel-form switch of a context (eagle_ctx::tune; eagle_dev_set_tune, EAGLE_HIP_TUNE): which of several forms of the same
+// computation the launch code picks.  Every form gives the same bits; the values other than the default exist for the tests and tools
+// that compare two forms.  The predicates below the context are the only code that reads the switch.  (_lib.TUNE mirrors the list.)
+enum EagleTune {
+    TUNE_SHIPPED = 0,             // the shipped form of everything
+    TUNE_VARA_256 = 8,            // scan: k_vara_i8 (256 x 256 tile) at any size
+    TUNE_COMPILER_SCHEDULED = 9,  // scan: k_vara_i8w below 32,768 padded individuals (k_vara_i8 from there up); MM^T: k_syrk_f4
+    TUNE_SYRK_F4P = 10,           // MM^T: k_syrk_f4p (256 x 256 tile, pipelined k-step) at any size
+    TUNE_SYRK_F4W = 11,           // MM^T: k_syrk_f4w (384 x 256 tile) below 3,072 padded individuals too
+    TUNE_VARA_PACED = 14,         // scan: the paced k_vara_i8p<true> at any size
+    TUNE_SPECTRAL_OFF = 29,       // scan prepare: no digit saved under the spectral bound
+    TUNE_W8_UNPIPED = 31,         // W engine: the product on the compiler-scheduled 256 x 256 k_w8_gemm
+    TUNE_W8_ROWPASS_SPLIT = 32,   // W engine: row statistics and digit slices as two kernels (k_w8_rowstats, k_w8_slice)
+    TUNE_GRAM_TWICE = 33,         // scan prepare: k_gram_hi_i8 forms the last digit's Gram a second time
+    TUNE_VARA_UPPER = 34,         // scan: the upper image of W's digits, every tile from stage 0
+};
+// v if the enum names it, else the default: a number of a form that has left the library selects the shipped forms
+static inline int tune_known(int v) {
+    switch (v) {
+        case TUNE_VARA_256: case TUNE_COMPILER_SCHEDULED: case TUNE_SYRK_F4P: case TUNE_SYRK_F4W: case TUNE_VARA_PACED: case TUNE_SPECTRAL_OFF:
+        case TUNE_W8_UNPIPED: case TUNE_W8_ROWPASS_SPLIT: case TUNE_GRAM_TWICE: case TUNE_VARA_UPPER:
+            return v;
+        default: return TUNE_SHIPPED;
+    }
+}
+
 struct eagle_ctx {
     int device = -1;
     // multi-device: the ctx eagle_open_devices returns is the LEAD (first device); it owns one sub-context per further device.
@@ -120,11 +146,12 @@ struct eagle_ctx {
     void* gemm_scratch = nullptr; size_t gemm_scratch_cap = 0;  // split-K partial tiles of the fp64 GEMM's last wave
     void* gemv_ws = nullptr;  // 16 digit-slice rows of the GEMV vectors + their exponents (k_gemv_mfma)
     void* stage_pin[2] = {nullptr, nullptr}; void* stage_raw[2] = {nullptr, nullptr}; size_t stage_cap = 0;  // tile streamer
-    // per-device launch state (a process may hold one ctx per GPU): dynamic-LDS attributes set on this device, schedule
-    // experiment switch of tools/bench_i8_engine.py (0 = shipped)
-    bool attr_vara_i8 = false, attr_vara_i8w = false, attr_vara_i8p = false, attr_vara_i8pp = false, attr_vara_i8px = false, attr_syrk_f4w = false, attr_zbuild_i8 = false, attr_vara_f6 = false, attr_gemv = false, attr_gemv2 = false, attr_w8_gemm = false, attr_knn_rows = false, attr_knn_rows_dist = false, attr_ldknn = false;
+    // per-device launch state (a process may hold one ctx per GPU): dynamic-LDS attributes set on this device, the kernel-form
+    // switch (an EagleTune; written through tune_known only)
+    bool attr_vara[5] = {false, false, false, false, false};   // by VaraKernel
+    bool attr_syrk_f4w = false, attr_zbuild_i8 = false, attr_vara_f6 = false, attr_gemv = false, attr_gemv2 = false, attr_w8_gemm = false, attr_knn_rows = false, attr_knn_rows_dist = false, attr_ldknn = false;
     uint32_t attr_bedld = 0;   // k_bedld_tile<NB, R2>: bit 2 (NB - 2) + R2
-    int tune = 0;
+    int tune = TUNE_SHIPPED;
     // W = S (V S) on the int8 engine (eagle_w8.hip): workspace, and what the last call left for the scan that follows it
     int w_mode = 1;            // 0 = always the fp64 GEMM, 1 = int8 digit slices from 4,096 padded individuals up, 2 = int8 at any size (tests)
     void* w8_ws = nullptr; size_t w8_ws_cap = 0; void* w8_host = nullptr;
@@ -147,6 +174,40 @@ struct eagle_ctx {
     int cu_count = 0;
     int64_t hbm_bytes = 0;
 };
+
+// ---- what the switch decides: one predicate per question the launch code asks ----
+// The digit-slice scan (eagle_i8mfma.hip): its kernel, and with it the layout of W's digits, the image orientation and the pacing.
+// Decided by this one function at prepare (layout, orientation) and at launch; `ext`: the compact image of the digit extension.
+//   the pipelined 384 x 256 k_vara_i8p below 65,536 padded individuals (above: the int32 range of its tile row-dots), unless the switch
+//   asks for k_vara_i8 or k_vara_i8w; the lower image (each column tile from its diagonal block down to the last live stage of W,
+//   DESIGN 4.3) unless it asks for the upper one; paced workers from 32,768 padded individuals up -- under TUNE_SHIPPED and
+//   TUNE_VARA_UPPER only: every other value leaves the pacing off at any size (known behaviour of the A/B values)
+enum VaraKernel { VARA_I8 = 0, VARA_I8W, VARA_I8P, VARA_I8P_PACED, VARA_I8P_EXT };   // k_vara_i8, k_vara_i8w, k_vara_i8p<false>, <true>, <false, true>
+struct VaraForm {
+    VaraKernel kernel;
+    bool lower;                                       // the lower image and its walk (k_vara_i8p only)
+    bool piped() const { return kernel >= VARA_I8P; } // k_slice_w lays the digits out for the 384 x 256 pipelined kernel
+};
+static inline VaraForm vara_form(const eagle_ctx* ctx, long n_pad, bool ext) {
+    const int t = ctx->tune;
+    if (t == TUNE_VARA_256 || t == TUNE_COMPILER_SCHEDULED || n_pad >= 65536)
+        return {t == TUNE_COMPILER_SCHEDULED && n_pad < 32768 ? VARA_I8W : VARA_I8, false};
+    const bool paced = !ext && (t == TUNE_VARA_PACED || ((t == TUNE_SHIPPED || t == TUNE_VARA_UPPER) && n_pad >= 32768));
+    return {paced ? VARA_I8P_PACED : (ext ? VARA_I8P_EXT : VARA_I8P), t != TUNE_VARA_UPPER};
+}
+// MM^T on fp4 operands: the 384 x 256 k_syrk_f4w from 3,072 padded individuals up while its row offsets fit (`wide_fits`), below
+// that the 256 x 256 k_syrk_f4p (the wide tiles pad too much there and leave too few workgroups)
+enum MmtKernel { MMT_F4, MMT_F4P, MMT_F4W };
+static inline MmtKernel tune_mmt_kernel(const eagle_ctx* ctx, long n_pad, bool wide_fits) {
+    const int t = ctx->tune;
+    if (t == TUNE_COMPILER_SCHEDULED) return MMT_F4;
+    if (t == TUNE_SYRK_F4P) return MMT_F4P;
+    return (n_pad >= 3072 || t == TUNE_SYRK_F4W) && wide_fits ? MMT_F4W : MMT_F4P;
+}
+static inline bool tune_w8_piped(const eagle_ctx* ctx) { return ctx->tune != TUNE_W8_UNPIPED; }              // k_w8_gemm_p (while it fits)
+static inline bool tune_w8_rowpass_once(const eagle_ctx* ctx) { return ctx->tune != TUNE_W8_ROWPASS_SPLIT; }  // k_w8_rowpass (while a row fits LDS)
+static inline bool tune_spectral_allowed(const eagle_ctx* ctx) { return ctx->tune != TUNE_SPECTRAL_OFF; }
+static inline bool tune_gram_once(const eagle_ctx* ctx) { return ctx->tune != TUNE_GRAM_TWICE; }
 
 extern thread_local char g_open_err[512];
 static inline int host_threads() { unsigned h = std::thread::hardware_concurrency(); return h == 0 ? 1 : (h > 16 ? 16 : (int)h); }

@@ -81,7 +81,7 @@ __global__ __launch_bounds__(512, 2) void k_gram_i8ab(const int8_t* __restrict__
                                                       const int* __restrict__ pairs, int npairs, int nblocks, long nstages,
                                                       long stages_per_split, int32_t* __restrict__ C, long ldc) {
     __shared__ __attribute__((aligned(1024))) int8_t lds[2][2][TILE_BYTES];
-    t8_gram_tiles<0>(lds, A, ldA, B, ldB, pairs, npairs, nblocks, nstages, stages_per_split, C, ldc);
+    t8_gram_tiles(lds, A, ldA, B, ldB, pairs, npairs, nblocks, nstages, stages_per_split, C, ldc);
 }
 
 // The launch rules of eagle_dev_mmt_accumulate_i8 (tile pairs, K splits of at least 16 stages, about 10 waves of 256 workgroups).

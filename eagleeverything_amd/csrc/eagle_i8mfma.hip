@@ -1,7 +1,13 @@
-// eagle_i8mfma.hip -- the int8 MFMA tile engine (v_mfma_i32_32x32x32_i8) and the two kernels built on it.
+// eagle_i8mfma.hip -- the int8 MFMA tile engine (v_mfma_i32_32x32x32_i8) and the kernels built on it.
 //
-//   k_syrk_i8  : MM^T partial sums, C32 += M8 * M8^T                        (E/src/calculateMMt_rcpp.cpp:95)
-//   k_vara_i8  : vara_i = m_i^T W m_i from exact int8 digit slices of W     (E/src/calculate_a_and_vara_rcpp.cpp:97-112)
+//   k_syrk_i8 ............ MM^T partial sums, C32 += M8 * M8^T, int8 operands           (E/src/calculateMMt_rcpp.cpp:95)
+//   k_syrk_f4w / f4p / f4  the same sums from fp4 operands: the shipped 384 x 256 and 256 x 256 forms, the compiler-scheduled one
+//   k_vara_i8p<..> ....... vara_i = m_i^T W m_i from exact int8 digit slices of W        (E/src/calculate_a_and_vara_rcpp.cpp:97-112)
+//   k_vara_i8 / k_vara_i8w the 256 x 256 form of it (n_pad >= 65,536) and the compiler-scheduled 384 x 256 one
+//   k_gram_rowabs_i8<..>, k_gram_hi_i8, k_spectral_decide: the spectral bound of the last digit of W
+//   k_zbuild_i8 .......... Z = Mt8 U from digit slices of U (the eigenbasis scan)
+//   k_vara_f6 ............ the digit-slice scan on the fp4 x fp6 MFMA (opt-in)
+// Which form a context runs: EagleTune and the predicates of eagle_ctx.h.
 //
 // Tile engine.  Workgroup = 512 threads = 8 waves arranged 2 (M) x 4 (N); block tile 256 x 256; wave tile
 // 128 x 64 = 4 x 2 MFMA tiles of 32 x 32 (128 accumulator registers); K step 128 bytes.  Both operands are
@@ -25,12 +31,11 @@
 // ------------------------------------------------------------------------------------------------
 // MM^T: grid.x = upper-triangular 256-tile pairs, grid.y = K splits.  Integer atomics: exact, any order.
 // ------------------------------------------------------------------------------------------------
-template <int TUNE>
 __global__ __launch_bounds__(512, 2) void k_syrk_i8(const int8_t* __restrict__ M8, long ld, const int* __restrict__ pairs,
                                                     int npairs, int nblocks, long nstages, long stages_per_split,
                                                     int32_t* __restrict__ C, long ldc) {
     __shared__ __attribute__((aligned(1024))) int8_t lds[2][2][TILE_BYTES];
-    t8_gram_tiles<TUNE>(lds, M8, ld, M8, ld, pairs, npairs, nblocks, nstages, stages_per_split, C, ldc);
+    t8_gram_tiles(lds, M8, ld, M8, ld, pairs, npairs, nblocks, nstages, stages_per_split, C, ldc);
 }
 
 // Upper-triangular tile pairs (ti<<16 | tj) in super-tile order, cached on the device per tile count.
@@ -62,13 +67,14 @@ int syrk_pair_table(eagle_ctx* ctx, int nt, const int** out, hipStream_t stream)
     return EAGLE_OK;
 }
 
-// Experiment switch for the tile-engine schedule (tools/bench_*.py); 0 is the shipped default.  Per ctx.  Not part of the public
-// ABI.  The switch also decides the layout eagle_dev_vara_i8_prepare gives the digit slices (vara_piped below): set it BEFORE the
-// prepare call of the scan it is meant for.
-extern "C" void eagle_dev_set_tune(eagle_ctx* ctx, int v) { if (ctx) ctx->tune = v; }
+// The kernel-form switch (EagleTune, eagle_ctx.h; tools/bench_*.py and the tests that compare two forms); 0 is the shipped default.  Per
+// ctx.  Not part of the public ABI.  A value that the enum does not name is stored as the default.  The switch also decides the layout
+// eagle_dev_vara_i8_prepare gives the digit slices (vara_form below): set it BEFORE the prepare call of the scan it is meant for.
+extern "C" int eagle_tune_known(int v) { return tune_known(v); }
+extern "C" void eagle_dev_set_tune(eagle_ctx* ctx, int v) { if (ctx) ctx->tune = tune_known(v); }
 
-// The int8 form of the MM^T kernel (the shipped one is k_syrk_f4 below: same engine, fp4 operands, twice the markers per
-// stage).  Kept for the schedule ablations of tools/bench_i8_engine.py; not part of the public ABI.
+// The int8 form of the MM^T kernel (the shipped ones are the k_syrk_f4* below: same engine, fp4 operands, twice the markers per
+// stage).  Kept as the engine's plain form for tools/bench_i8_engine.py; not part of the public ABI.
 extern "C" int eagle_dev_mmt_accumulate_i8(eagle_ctx* ctx, const int8_t* M8, long n_pad, long L_pad, long ld, int32_t* C32,
                                            void* stream) {
     if (n_pad % T8 || L_pad % BK8 || ld % 128 || L_pad > ld || n_pad <= 0 || (double)ld * T8 >= 2147483648.0)
@@ -90,13 +96,7 @@ extern "C" int eagle_dev_mmt_accumulate_i8(eagle_ctx* ctx, const int8_t* M8, lon
     int rc = syrk_pair_table(ctx, nt, &pairs, (hipStream_t)stream);
     if (rc) return rc;
     dim3 grid((unsigned)((nblocks + 7) / 8 * 8));
-#define SYRK_LAUNCH(T) hipLaunchKernelGGL(k_syrk_i8<T>, grid, dim3(512), 0, (hipStream_t)stream, M8, ld, pairs, (int)npairs, (int)nblocks, nstages, per, C32, n_pad)
-    switch (ctx->tune) {
-        case 3: SYRK_LAUNCH(3); break;
-        case 4: SYRK_LAUNCH(4); break;
-        default: SYRK_LAUNCH(0);
-    }
-#undef SYRK_LAUNCH
+    hipLaunchKernelGGL(k_syrk_i8, grid, dim3(512), 0, (hipStream_t)stream, M8, ld, pairs, (int)npairs, (int)nblocks, nstages, per, C32, n_pad);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return eagle_fail_hip(ctx, e, "k_syrk_i8");
     return EAGLE_OK;
@@ -250,14 +250,14 @@ __global__ __launch_bounds__(256) void k_vara_prep(const double* __restrict__ Wu
 // min(specH q2_i, l1_i^2/2 * 128.5 u) per marker.  Markers whose own bound still exceeds the budget are re-evaluated in fp64 like any
 // flagged marker; should more than CERT_CAP of them do (the fp64 fallback of the whole block), the context stops taking the digit
 // off (eagle_api.cpp).  Deterministic, a function of W alone: every device and every marker block of a scan decides the same.
-// Not used with a forced digit count, with stochastic rounding, or under tune 29 (A/B switch).
+// Not used with a forced digit count, with stochastic rounding, or under TUNE_SPECTRAL_OFF (A/B switch).
 // ------------------------------------------------------------------------------------------------
 // Ds[i][j] = last digit of Wu[min(i,j)][max(i,j)], 0 on the diagonal: the symmetric int8 image, n_pad x n_pad, is written by k_slice_w
 // below from the tiles it reads anyway (the same llrint, the same digit).
 // rs[i] += sum_j |(D D^T)_ij| over the upper-triangular 256-tile pairs of the symmetric product (both the row sums of a tile and, off
 // the diagonal, its column sums = the row sums of the mirrored tile).  Whole K per workgroup: |.| does not commute with a K split.
 // HI (the level-1 call on Ds): the tile epilogue also does the first half of level 2 from the accumulators it holds -- E_hi, lo_sumsq,
-// maxdiag, hi_overflow, see k_gram_hi_i8 below, which forms the same exact product a second time (kept behind tune 33).  G = D D^T is
+// maxdiag, hi_overflow, see k_gram_hi_i8 below, which forms the same exact product a second time (kept behind TUNE_GRAM_TWICE).  G = D D^T is
 // symmetric as an integer matrix, so the upper pair (ti, tj) serves its mirror too: lo^2 of an off-diagonal tile counts twice, and the E_hi
 // tile is stored a second time transposed.  Both stores go through the stage buffers (free after the K loop) as rows of 256 bytes,
 // GRAM_TS apart so that the transposed 4-byte writes of a half-wave spread over the banks.  Only when level 1 CAN hand over to level 2
@@ -292,8 +292,8 @@ __global__ __launch_bounds__(512, 2) void k_gram_rowabs_i8(const int8_t* __restr
     const T8Read rd = t8_read_init(wr, wc, lane);
     for (long s = 0; s < nstages; s++) {
         const int kn = (int)((s + 1) * BK8);
-        t8_stage_compute<0>(acc, lds[cur][0], lds[cur][1], rd, s + 1 < nstages, rsA, ln, ldi, kn, lds[cur ^ 1][0], rsB, ln, ldi, kn,
-                            lds[cur ^ 1][1], w);
+        t8_stage_compute(acc, lds[cur][0], lds[cur][1], rd, s + 1 < nstages, rsA, ln, ldi, kn, lds[cur ^ 1][0], rsB, ln, ldi, kn,
+                         lds[cur ^ 1][1], w);
         __syncthreads();
         cur ^= 1;
     }
@@ -433,8 +433,8 @@ __global__ __launch_bounds__(512, 2) void k_gram_hi_i8(const int8_t* __restrict_
     const T8Read rd = t8_read_init(wr, wc, lane);
     for (long s = 0; s < nstages; s++) {
         const int kn = (int)((s + 1) * BK8);
-        t8_stage_compute<0>(acc, lds[cur][0], lds[cur][1], rd, s + 1 < nstages, rsA, ln, ldi, kn, lds[cur ^ 1][0], rsB, ln, ldi, kn,
-                            lds[cur ^ 1][1], w);
+        t8_stage_compute(acc, lds[cur][0], lds[cur][1], rd, s + 1 < nstages, rsA, ln, ldi, kn, lds[cur ^ 1][0], rsB, ln, ldi, kn,
+                         lds[cur ^ 1][1], w);
         __syncthreads();
         cur ^= 1;
     }
@@ -1019,7 +1019,7 @@ __global__ __launch_bounds__(512, 2) void k_vara_i8w(const int8_t* __restrict__ 
 //     sources as it issues and LDS data comes back tens of cycles later, so re-loading a source register right behind the last
 //     MFMA that reads it is safe;
 //   * the next stage's ten LDS-DMA loads per wave go out one at a time behind every second MFMA (3 behind the barrier, 6 in
-//     the next k-step, the last in the one after) instead of as a burst at the top of the stage (the burst alone costs 3-4 %, tune 11-15 experiments);
+//     the next k-step, the last in the one after) instead of as a burst at the top of the stage (the burst alone costs 3-4 %, round-2 experiments);
 //   * the first k-step of a tile uses the inline constant 0 as the C operand: no zeroing pass;
 //   * the stage barrier sits in the middle of the last k-step (after 6 of its 12 MFMAs: all fragment reads of this stage have
 //     returned; the re-loads behind the barrier read the other buffer), so each wave reaches it with matrix work in flight;
@@ -1030,7 +1030,7 @@ __global__ __launch_bounds__(512, 2) void k_vara_i8w(const int8_t* __restrict__ 
 // across asm statements that do not).
 // ------------------------------------------------------------------------------------------------
 // (the tile row-dot of a lane sums 64 products in int32: |sum| <= 32768 K for a K-deep tile, i.e. n_pad < 65536)
-// PACE (experiment of round 3, tools/bench_vara.py tune 14): the 32 workers an XCD runs at a time meet at a soft
+// PACE (experiment of round 3, TUNE_VARA_PACED forces it): the 32 workers an XCD runs at a time meet at a soft
 // barrier before every column-tile pair -- one agent-scope counter per (XCD, round, pair), bounded spin (a worker that is not
 // co-resident with its round only costs the others the spin limit, never a hang) -- so that they stream the shared genotype and
 // W-digit stages in step and the L2 serves them once.  Same integer sums: bit-identical q.
@@ -1066,7 +1066,7 @@ __global__ __launch_bounds__(512, 2) void k_vara_i8p(const int8_t* __restrict__ 
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)(Mt8 + row0 * ld), 0, (int)(rows_here * ld), 0x00020000);
 
     VaraIt cur, nxt;
-    cur.lower = klive != nullptr;   // the lower image and its walk (VaraIt); NULL: the upper one, every tile from stage 0 (tune 34)
+    cur.lower = klive != nullptr;   // the lower image and its walk (VaraIt); NULL: the upper one, every tile from stage 0 (TUNE_VARA_UPPER)
     cur.klive = cur.lower ? min(*klive, (T8 / BK8) * nct) : 0;   // (k_slice_w never counts past n_pad / 128)
     cur.p = pair0; cur.half = 0; vit_set_tile(cur, nct, pair1);
     if (!cur.valid) return;
@@ -1342,7 +1342,7 @@ __global__ __launch_bounds__(256) void k_vara_i8_finish(const long long* __restr
 // l1_i = sum_j |m'_ij| of the re-centred marker (k_marker_shift): the first term is the truncation of W to S digits
 // (|sum_{j<k} m'_j m'_k R_jk| <= 2^(e+1-8S) ((sum|m'_j|)^2 - sum m'_j^2)/2), the others cover the fp64 roundings of the
 // handful of terms the finish kernel adds (each an exactly evaluated integer sum rounded once).
-// Markers are RE-EVALUATED with the fp64 kernel (k_vara_f64<SPLIT>, bitwise the value scan mode 0 gives that marker) when
+// Markers are RE-EVALUATED with the fp64 kernel (k_vara_f64d<SPLIT>, bitwise the value scan mode 0 gives that marker) when
 //   (1) b_i > 1.8 budget |vara_i|                -- the digit result is not certified to 0.9 of the path's 1e-6 tolerance (default budget 5e-7)
 //                                                   (a quadratic form that cancels against its diagonal term, or W with huge
 //                                                   off-diagonal entries), or
@@ -1752,13 +1752,8 @@ static int vara_i8_check(eagle_ctx* ctx, long L_pad, long n_pad, long ld, int ns
 
 // Phase 1: max |off-diagonal|, slice count, diagonal vector, ONE fused pass over the genotypes for
 // vdiag_i = sum_k m_ik^2 W_kk (and a = Mt8 v if v != NULL), digit slices of the off-diagonal part.
-// Which vara kernel a context runs at this size (the prepare step lays the digit slices out for it): the pipelined 384 x 256 kernel
-// below 65,536 padded individuals unless a tune switch asks for one of the others (tools/bench_vara.py: 8 = the 256 x 256 form,
-// 9 = the compiler-scheduled 384 x 256 form).
-static bool vara_piped(const eagle_ctx* ctx, long n_pad) { return ctx->tune != 8 && ctx->tune != 9 && n_pad < 65536; }
-// ... and which way it walks the triangle: from each column tile's diagonal block down to the last live stage of W (the lower image of
-// k_slice_w) unless tune 34 asks for the upper image and every tile from stage 0 -- like the layout, decided at prepare.
-static bool vara_lower(const eagle_ctx* ctx, long n_pad) { return vara_piped(ctx, n_pad) && ctx->tune != 34; }
+// Which vara kernel a context runs at this size, and which way it walks the triangle: vara_form (eagle_ctx.h).  The prepare step lays
+// the digit slices out for that kernel and that walk, so prepare and launch both ask it.
 // the live-stage count of W, in the spare bytes behind the header: zeroed with it, kept across the marker blocks of a streamed scan
 static int* ws_klive(void* ws) { return (int*)((char*)ws + 128); }
 static_assert(sizeof(VaraHdr) <= 128, "klive sits behind the header");
@@ -1819,8 +1814,9 @@ static int vara_i8_prepare_impl(eagle_ctx* ctx, const int8_t* Mt8, const void* M
     }
     if (part != 2) {
         dim3 g2((unsigned)(n_pad / 32), (unsigned)(n_pad / 32));
-        const bool spectral = nslices == 0 && !ctx->spectral_off && ctx->tune != 29;
-        hipLaunchKernelGGL(k_slice_w, g2, dim3(256), 0, s, Wu, n_pad, hdr, Bs, vara_piped(ctx, n_pad) ? 1 : 0, vara_lower(ctx, n_pad) ? 1 : 0,
+        const bool spectral = nslices == 0 && !ctx->spectral_off && tune_spectral_allowed(ctx);
+        const VaraForm form = vara_form(ctx, n_pad, false);
+        hipLaunchKernelGGL(k_slice_w, g2, dim3(256), 0, s, Wu, n_pad, hdr, Bs, form.piped() ? 1 : 0, form.lower ? 1 : 0,
                            spectral ? Bs + (size_t)(smax - 1) * n_pad * n_pad : (int8_t*)nullptr, smax, ws_klive(ws));
         // one digit fewer if the spectral bound of the last digit allows it (automatic digit count, round to nearest): the last digit's
         // symmetric image goes into the spare slot of the slice area (at most 6 of the 7 are in use), the row sums into the column
@@ -1839,9 +1835,9 @@ static int vara_i8_prepare_impl(eagle_ctx* ctx, const int8_t* Mt8, const void* M
             int8_t* Ehi = Bs + (size_t)(smax - 2) * n_pad * n_pad;
             int shift = 8;   // 127 * 2^shift >= 8 standard deviations sqrt(n) 74^2 of a random Gram entry
             while (shift < 23 && 127.0 * (double)(1 << shift) < 8.0 * 5476.0 * sqrt((double)n_pad)) shift++;
-            // Ds Ds is formed ONCE: the level-1 product leaves E_hi and the header fields of level 2 on the way (tune 33: the two-kernel
+            // Ds Ds is formed ONCE: the level-1 product leaves E_hi and the header fields of level 2 on the way (TUNE_GRAM_TWICE: the two-kernel
             // form, the product a second time in k_gram_hi_i8 -- A/B runs and tests/test_gpu_gram_once.py; the same bytes either way)
-            const bool once = ctx->tune != 33;
+            const bool once = tune_gram_once(ctx);
             if (once)
                 hipLaunchKernelGGL(k_gram_rowabs_i8<true>, dim3((unsigned)((npairs + 7) / 8 * 8)), dim3(512), 0, s, Ds, n_pad, pairs, npairs, n_pad / BK8,
                                    rsum, (const int*)nullptr, hdr, Ehi, shift, smax);
@@ -1879,45 +1875,45 @@ extern "C" int eagle_dev_vara_i8_prepare_packed(eagle_ctx* ctx, const void* Mt2,
     return vara_i8_prepare_impl(ctx, nullptr, Mt2, L_pad, n_pad, ld, Wu, nslices, ws, v, a_out, stream, 0);
 }
 
+// One vara kernel on the stream, its dynamic LDS allowed first (per device: a second ctx on another GPU must set it again)
+template <class K, class... Args>
+static int vara_i8_run(eagle_ctx* ctx, VaraKernel which, K kfn, dim3 grid, size_t lds, hipStream_t s, Args... args) {
+    if (!ctx->attr_vara[which]) {
+        hipError_t ea = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (ea != hipSuccess) return eagle_fail_hip(ctx, ea, "hipFuncSetAttribute(k_vara_i8*)");
+        ctx->attr_vara[which] = true;
+    }
+    hipLaunchKernelGGL(kfn, grid, dim3(512), lds, s, args...);
+    return EAGLE_OK;
+}
 // The int8 MFMA kernel over all (marker tile, slice) workers of an image: q[s][i] += ... for the hdr->S slices at Bs (grid sized for smax).
 // klive: the workspace's live-stage count (ws_klive), for the compact image of the extension too -- its second header holds none.
 static int vara_i8_launch(eagle_ctx* ctx, const int8_t* Mt8s, long L_pad, long n_pad, long ld, int smax, const VaraHdr* hdr, const int8_t* Bs,
                           long long* q, const int* klive, hipStream_t s, bool ext = false) {
-    const int ntm = (int)(L_pad / T8);
-    const int groups = (ntm + 7) / 8;
-    if (!ctx->attr_vara_i8) {  // per device: a second ctx on another GPU must set it again
-        hipError_t ea = hipFuncSetAttribute((const void*)k_vara_i8, hipFuncAttributeMaxDynamicSharedMemorySize, 5 * TILE_BYTES);
-        if (ea != hipSuccess) return eagle_fail_hip(ctx, ea, "hipFuncSetAttribute(k_vara_i8)");
-        ctx->attr_vara_i8 = true;
-    }
     // The 384 x 256 tile is the default (C2: 23.05 -> 21.91 ms, C3 shape: 45.2 -> 43.1 ms per 262144 markers; profiles/
     // r02_ab_vara_tile.txt), since round 2 in its asm-pipelined form k_vara_i8p (another -4 to -5 %, profiles/r02_ab_vara_pipe.txt).
-    // All forms give bit-identical q.  The 256 x 256 form serves n_pad >= 65536 (int32 range of the tile row-dots).  A/B switches of tools/bench_vara.py: tune 8 = the 256 x 256 form, 9 = the compiler-scheduled 384 x 256
-    // form (k_vara_i8w), 7 = whole workers in the last round.
-    if (vara_piped(ctx, n_pad) || (ctx->tune == 9 && n_pad < 32768)) {
-        const bool piped = vara_piped(ctx, n_pad);
-        // paced workers (a soft barrier per column-tile pair, round 3's tune 14): 1 % slower at n_pad = 10,240, where the L2 serves 68-72 % of
-        // the stage fills anyway, 3.3 % FASTER at n_pad = 50,176, where the unpaced workers drift apart over the 5x longer K loops and the hit
-        // rate falls to 53 % (profiles/r04_rocprof_C4, r04_vara_pace_50k.txt): on from 32,768 padded individuals up; same integer sums either way
-        const bool pace = piped && !ext && (ctx->tune == 14 || ((ctx->tune == 0 || ctx->tune == 34) && n_pad >= 32768));
-        const int* kl = vara_lower(ctx, n_pad) ? klive : (const int*)nullptr;
-        const bool px = piped && ext;
-        const void* kfn = !piped ? (const void*)k_vara_i8w
-                                 : (pace ? (const void*)k_vara_i8p<true> : (px ? (const void*)k_vara_i8p<false, true> : (const void*)k_vara_i8p<false>));
-        bool& attr = !piped ? ctx->attr_vara_i8w : (pace ? ctx->attr_vara_i8pp : (px ? ctx->attr_vara_i8px : ctx->attr_vara_i8p));
-        if (!attr) {
-            hipError_t ea = hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (TW_ABYTES + TILE_BYTES));
-            if (ea != hipSuccess) return eagle_fail_hip(ctx, ea, "hipFuncSetAttribute(k_vara_i8p/w)");
-            attr = true;
-        }
-        const int ntw = (int)((L_pad + TW_M - 1) / TW_M), gw = (ntw + 7) / 8;
-        // per XCD at most gw * smax workers, plus at most 31 * VARA_TAIL_PMAX more blocks when the last round is cut into pieces
-        const dim3 gridw((unsigned)(8 * (gw * smax + 31 * VARA_TAIL_PMAX)));
-        const int cut = ctx->tune == 7 ? 0 : 1;
-        if (!piped) hipLaunchKernelGGL(k_vara_i8w, gridw, dim3(512), 2 * (TW_ABYTES + TILE_BYTES), s, Mt8s, ld, ntw, Bs, n_pad, hdr, q, L_pad, cut);
-        else if (px) hipLaunchKernelGGL((k_vara_i8p<false, true>), gridw, dim3(512), 2 * (TW_ABYTES + TILE_BYTES), s, Mt8s, ld, ntw, Bs, n_pad, hdr, q, L_pad, cut, (int*)nullptr, kl);
-        else if (!pace) hipLaunchKernelGGL(k_vara_i8p<false>, gridw, dim3(512), 2 * (TW_ABYTES + TILE_BYTES), s, Mt8s, ld, ntw, Bs, n_pad, hdr, q, L_pad, cut, (int*)nullptr, kl);
-        else {
+    // All forms give bit-identical q.  The 256 x 256 form serves n_pad >= 65536 (int32 range of the tile row-dots).
+    // Paced workers (a soft barrier per column-tile pair): 1 % slower at n_pad = 10,240, where the L2 serves 68-72 % of the stage fills
+    // anyway, 3.3 % FASTER at n_pad = 50,176, where the unpaced workers drift apart over the 5x longer K loops and the hit rate falls to
+    // 53 % (profiles/r04_rocprof_C4, r04_vara_pace_50k.txt): on from 32,768 padded individuals up; same integer sums either way
+    const VaraForm form = vara_form(ctx, n_pad, ext);
+    const int ntm = (int)(L_pad / T8), groups = (ntm + 7) / 8;
+    const int ntw = (int)((L_pad + TW_M - 1) / TW_M), gw = (ntw + 7) / 8;
+    // per XCD at most gw * smax workers, plus at most 31 * VARA_TAIL_PMAX more blocks when the last round is cut into pieces
+    const dim3 gridw((unsigned)(8 * (gw * smax + 31 * VARA_TAIL_PMAX)));
+    const size_t ldsw = 2 * (TW_ABYTES + TILE_BYTES);
+    const int cut = 1;   // the last round of workers is cut into pieces
+    const int* kl = form.lower ? klive : (const int*)nullptr;
+    switch (form.kernel) {
+        case VARA_I8:
+            return vara_i8_run(ctx, form.kernel, k_vara_i8, dim3((unsigned)(groups * 8 * smax)), 5 * TILE_BYTES, s, Mt8s, ld, ntm, Bs, n_pad, hdr, q, L_pad);
+        case VARA_I8W:
+            return vara_i8_run(ctx, form.kernel, k_vara_i8w, gridw, ldsw, s, Mt8s, ld, ntw, Bs, n_pad, hdr, q, L_pad, cut);
+        case VARA_I8P:
+            return vara_i8_run(ctx, form.kernel, k_vara_i8p<false>, gridw, ldsw, s, Mt8s, ld, ntw, Bs, n_pad, hdr, q, L_pad, cut, (int*)nullptr, kl);
+        case VARA_I8P_EXT:
+            return vara_i8_run(ctx, form.kernel, k_vara_i8p<false, true>, gridw, ldsw, s, Mt8s, ld, ntw, Bs, n_pad, hdr, q, L_pad, cut, (int*)nullptr, kl);
+        case VARA_I8P_PACED: {
             // counters [8 XCDs][rounds][pairs], zeroed per launch, in the ctx's GEMM scratch (free during the scan)
             const size_t need = sizeof(int) * 8 * (size_t)((gw * smax + 31) / 32 + 1) * (size_t)((n_pad / T8 + 1) / 2);
             if (need > ctx->gemm_scratch_cap) {
@@ -1928,10 +1924,9 @@ static int vara_i8_launch(eagle_ctx* ctx, const int8_t* Mt8s, long L_pad, long n
             }
             hipError_t ea = hipMemsetAsync(ctx->gemm_scratch, 0, need, s);
             if (ea != hipSuccess) return eagle_fail_hip(ctx, ea, "pace counters memset");
-            hipLaunchKernelGGL(k_vara_i8p<true>, gridw, dim3(512), 2 * (TW_ABYTES + TILE_BYTES), s, Mt8s, ld, ntw, Bs, n_pad, hdr, q, L_pad, cut, (int*)ctx->gemm_scratch, kl);
+            return vara_i8_run(ctx, form.kernel, k_vara_i8p<true>, gridw, ldsw, s, Mt8s, ld, ntw, Bs, n_pad, hdr, q, L_pad, cut, (int*)ctx->gemm_scratch, kl);
         }
-    } else
-    hipLaunchKernelGGL(k_vara_i8, dim3((unsigned)(groups * 8 * smax)), dim3(512), 5 * TILE_BYTES, s, Mt8s, ld, ntm, Bs, n_pad, hdr, q, L_pad);
+    }
     return EAGLE_OK;
 }
 
@@ -2922,9 +2917,9 @@ extern "C" int eagle_dev_mmt_accumulate_f4(eagle_ctx* ctx, const void* M4, long 
     if (L_pad == 0) return EAGLE_OK;
     const int nt = (int)(n_pad / T8);
     const long nstages = L_pad / 256;
-    // tune 9: k_syrk_f4 (256 x 256 tiles, compiler-scheduled), 10: k_syrk_f4p (256 x 256, pipelined k-step), else k_syrk_f4w (384 x 256)
-    // (below ~3,000 individuals the 384-row tiles pad too much and leave too few workgroups: the 256 x 256 form is as fast or faster)
-    const bool wide = ctx->tune != 9 && ctx->tune != 10 && (n_pad >= 3072 || ctx->tune == 11) && (double)ld4 * TW_M < 2147483648.0;
+    // k_syrk_f4 (256 x 256 tiles, compiler-scheduled), k_syrk_f4p (256 x 256, pipelined k-step) or k_syrk_f4w (384 x 256)
+    const MmtKernel kernel = tune_mmt_kernel(ctx, n_pad, (double)ld4 * TW_M < 2147483648.0);
+    const bool wide = kernel == MMT_F4W;
     const int* pairs = nullptr;
     long npairs = (long)nt * (nt + 1) / 2;
     int rc;
@@ -2959,7 +2954,7 @@ extern "C" int eagle_dev_mmt_accumulate_f4(eagle_ctx* ctx, const void* M4, long 
             ctx->attr_syrk_f4w = true;
         }
         hipLaunchKernelGGL(k_syrk_f4w, grid, dim3(512), 2 * (TW_ABYTES + TILE_BYTES), (hipStream_t)stream, (const uint8_t*)M4, ld4, pairs, (int)npairs, (int)nblocks, nstages, per, C32, n_pad, n_pad);
-    } else if (ctx->tune == 9) hipLaunchKernelGGL(k_syrk_f4, grid, dim3(512), 0, (hipStream_t)stream, (const uint8_t*)M4, ld4, pairs, (int)npairs, (int)nblocks, nstages, per, C32, n_pad);
+    } else if (kernel == MMT_F4) hipLaunchKernelGGL(k_syrk_f4, grid, dim3(512), 0, (hipStream_t)stream, (const uint8_t*)M4, ld4, pairs, (int)npairs, (int)nblocks, nstages, per, C32, n_pad);
     else hipLaunchKernelGGL(k_syrk_f4p, grid, dim3(512), 0, (hipStream_t)stream, (const uint8_t*)M4, ld4, pairs, (int)npairs, (int)nblocks, nstages, per, C32, n_pad);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return eagle_fail_hip(ctx, e, "k_syrk_f4");

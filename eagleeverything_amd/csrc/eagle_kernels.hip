@@ -3,8 +3,9 @@
 //
 //   k_decode_ascii ........ text tile '0','1','2' -> int8 {-1,0,1}     (E/src/ReadBlock.cpp:52-55)
 //   (k_syrk_i8 / k_vara_i8: the int8 MFMA tile engine lives in eagle_i8mfma.hip)
-//   k_gemm_f64_list ....... fp64 MFMA GEMM (v_mfma_f64_16x16x4_f64): W = S (V S)   (calculate_a_and_vara_rcpp.cpp:97-98)
-//   k_vara_f64<..> ........ same core, A = int8: T = Mt W fused with the row-dot    (calculate_a_and_vara_rcpp.cpp:103-112)
+//   k_gemm_f64_dma ........ fp64 MFMA GEMM (v_mfma_f64_16x16x4_f64): W = S (V S)   (calculate_a_and_vara_rcpp.cpp:97-98)
+//   k_gemm_f64_list8 ...... the same product at sizes that are a multiple of 128 and not of 256
+//   k_vara_f64d<..> ....... A = int8: T = Mt W fused with the row-dot               (calculate_a_and_vara_rcpp.cpp:103-112)
 //   k_gemv_mfma ........... a = Mt v (+ diagonal term of vara)          (calculate_a_and_vara_rcpp.cpp:91,
 //                                                                        calculate_reduced_a_rcpp.cpp:83-84)
 //   k_tsq_* ............... tsq = a^2/vara, first arg-max ignoring NaN  (E/R/find_qtl.R:71-83)
@@ -150,212 +151,17 @@ __global__ __launch_bounds__(256) void k_mmt_normalise(double* __restrict__ A, l
 }
 
 // ------------------------------------------------------------------------------------------------
-// fp64 MFMA GEMM core, C = A * B, v_mfma_f64_16x16x4_f64.
-// Block = 256 threads = 4 waves (2 x 2); block tile 128 x 128; wave tile 64 x 64 = 4 x 4 MFMA tiles;
-// K block 16.  Inside a K block the lane group g = lane>>4 owns k = 4g + s for MFMA step s, so a lane reads
-// 4 consecutive k of its A row at once (the k order of an fp64 sum is a free choice; it is fixed, hence
-// deterministic).
-//   AMODE 0: A is fp64 row-major (k_gemm_f64_list).   AMODE 1: A is int8 row-major (genotypes), converted in registers
-//   (k_vara_f64, which fuses the row-dot out[i] = sum_c C[i][c] * A8[i][c] into the tile epilogue).
-// LDS rows: A f64 [128][16] doubles (+2 pad), A i8 [128][16] bytes, B [16][128] doubles (+4 pad).
+// fp64 MFMA kernels (v_mfma_f64_16x16x4_f64): tile geometry shared by the GEMMs (k_gemm_f64_list8, k_gemm_f64_dma) and the fp64
+// vara kernel (k_vara_f64d).  Output tiles of 128 columns, K block 16.
 // ------------------------------------------------------------------------------------------------
 #define GF_T 128
 #define GF_BK 16
 #define GF_LDB (GF_T + 4)   /* doubles per B row in LDS: 4*stride*8 mod 256 == 128 -> the 4 k-groups hit distinct banks */
 #define GF_LDA (GF_BK + 4)  /* doubles per A row in LDS (pitch 20: 51.2 -> 50.3 ms for W at n = 10,000 against pitch 18; 24 is 10 % slower) */
-
-template <int AMODE>
-struct GfStage {
-    f64x2 b[4];
-    f64x2 a[AMODE == 0 ? 4 : 1];
-    i32x4 a8;
-};
-
-template <int AMODE>
-__device__ __forceinline__ void gf_load(GfStage<AMODE>& s, const void* __restrict__ Ablk, long lda,
-                                        const double* __restrict__ Bblk, long ldb, long k0, int t) {
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        int c = t + 256 * i;           // 1024 chunks of 2 doubles: 16 rows x 64 chunks
-        int kr = c >> 6, cc = c & 63;
-        s.b[i] = *(const f64x2*)(Bblk + (k0 + kr) * ldb + cc * 2);
-    }
-    if (AMODE == 0) {
-        const double* A = (const double*)Ablk;
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            int c = t + 256 * i;       // 1024 chunks: 128 rows x 8 chunks
-            int row = c >> 3, cc = c & 7;
-            s.a[i] = *(const f64x2*)(A + (long)row * lda + k0 + cc * 2);
-        }
-    } else {
-        const int8_t* A = (const int8_t*)Ablk;
-        if (t < 128) s.a8 = *(const i32x4*)(A + (long)t * lda + k0);
-    }
-}
-template <int AMODE, int LDA = GF_LDA>
-__device__ __forceinline__ void gf_store(const GfStage<AMODE>& s, double* ldsA, double* ldsB, int t) {
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        int c = t + 256 * i;
-        int kr = c >> 6, cc = c & 63;
-        *(f64x2*)(ldsB + kr * GF_LDB + cc * 2) = s.b[i];
-    }
-    if (AMODE == 0) {
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            int c = t + 256 * i;
-            int row = c >> 3, cc = c & 7;
-            *(f64x2*)(ldsA + row * LDA + cc * 2) = s.a[i];
-        }
-    } else {
-        if (t < 128) *(i32x4*)((int8_t*)ldsA + t * 16) = s.a8;
-    }
-}
-// mlim: only the first mlim 16-row tiles of the wave's four are computed (the SPLIT vara kernel re-evaluates a handful of
-// rows; the MFMA sequence of a computed element is the same whatever mlim is)
-template <int AMODE, int LDA = GF_LDA>
-__device__ __forceinline__ void gf_compute(f64x4 (&acc)[4][4], const double* ldsA, const double* ldsB, int wr, int wc,
-                                           int lane, int mlim = 4) {
-    const int i16 = lane & 15, g = lane >> 4;
-    int w4[4];  // AMODE 1: the lane's 4 consecutive genotype bytes of each row tile
-    if (AMODE == 1) {
-#pragma unroll
-        for (int m = 0; m < 4; m++) w4[m] = *(const int*)((const int8_t*)ldsA + (wr * 64 + m * 16 + i16) * 16 + 4 * g);
-    }
-#pragma unroll
-    for (int s = 0; s < 4; s++) {
-        double a[4], b[4];
-#pragma unroll
-        for (int m = 0; m < 4; m++) {
-            if (AMODE == 0) a[m] = ldsA[(wr * 64 + m * 16 + i16) * LDA + 4 * g + s];
-            else a[m] = (double)((w4[m] << (24 - 8 * s)) >> 24);  // sign-extended byte s
-        }
-#pragma unroll
-        for (int n = 0; n < 4; n++) b[n] = ldsB[(4 * g + s) * GF_LDB + wc * 64 + n * 16 + i16];
-#pragma unroll
-        for (int m = 0; m < 4; m++)
-            if (m < mlim) {
-#pragma unroll
-                for (int n = 0; n < 4; n++) acc[m][n] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[m], b[n], acc[m][n], 0, 0, 0);
-            }
-    }
-}
-
-// LDS bytes: A: 128*20*8 = 20480 (f64) ; B: 16*132*8 = 16896 ; x2 buffers (two workgroups per CU: 149.5 KiB)
-#define GF_LDSA_DOUBLES (GF_T * GF_LDA)
 #define GF_LDSB_DOUBLES (GF_BK * GF_LDB)
+#define GF_KC 2048  /* K chunk of the canonical summation order (k_vara_f64d) */
 
-// The fp64 vara kernel (calculate_a_and_vara_rcpp.cpp:103-112): vara_i = sum_k m_ik sum_{j<=k} m_ij Wu[j][k] for the 128 markers
-// of a row block, A = int8 genotypes converted in registers, B = Wu (upper triangular fold of W, so column tile ct only
-// needs k < (ct+1)*128).  The summation order is FIXED and is the definition of this library's fp64 result:
-//   s_{ct,c}(i, wc) = the row-dot of column tile ct, restricted to the 64 columns of wave column wc, of the partial product over
-//                     the K chunk c = [2048 c, 2048 (c+1)): the MFMA chain over the chunk, then per lane a 4-term chain over
-//                     the lane's columns, then a butterfly over the 16 lanes of the row;
-//   P_wc(i)         = the s_{ct,c} added one by one, ct ascending, c ascending inside a tile;   vara_i = P_0(i) + P_1(i).
-// SPLIT = false: one workgroup walks every (column tile, chunk) of its row block and keeps P in registers.
-// SPLIT = true : grid.y = column tile, grid.z = chunk; the workgroup writes s_{ct,c} to partial[rb][ct][c][wc][128] and
-//                k_vara_f64_sum forms the same chain -- bitwise the same vara for a row, whichever form computed it and
-//                whatever rows share its block.  That is what lets the digit-slice scan re-evaluate a handful of markers in
-//                fp64 on the whole chip (k_cert_*, eagle_i8mfma.hip: the longest workgroup is one 2048-deep chunk, 0.3 ms,
-//                instead of a 10240-deep tile) and promise the fp64-mode result for them.
-// gate (may be NULL): SPLIT = false -> the launch is dropped unless *gate != 0; SPLIT = true -> row blocks at or beyond
-// *gate rows are dropped.
-#define GF_KC 2048  /* K chunk of the canonical summation order */
-template <bool SPLIT>
-__global__ __launch_bounds__(256, 2) void k_vara_f64(const int8_t* __restrict__ A8, long lda, const double* __restrict__ B, long ldb,
-                                                     double* __restrict__ out, int n_coltiles, long K, const int* __restrict__ gate,
-                                                     double* __restrict__ partial) {
-    __shared__ __attribute__((aligned(16))) double lds[2][GF_LDSA_DOUBLES + GF_LDSB_DOUBLES];
-    if (gate) {
-        if (!SPLIT && *gate == 0) return;
-        if (SPLIT && (long)blockIdx.x * GF_T >= (long)*gate) return;
-    }
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6, wr = w >> 1, wc = w & 1;
-    const int i16 = lane & 15, g = lane >> 4;
-    const long row0 = (long)blockIdx.x * GF_T;
-    const int8_t* Ablk = A8 + row0 * lda;
-    // SPLIT with a row count: 16-row tiles entirely beyond the count are not computed (wave-uniform)
-    int mlim = 4;
-    if (SPLIT && gate) {
-        const long left = (long)*gate - row0 - wr * 64;
-        mlim = left <= 0 ? 0 : (left >= 64 ? 4 : (int)((left + 15) >> 4));
-        mlim = __builtin_amdgcn_readfirstlane(mlim);
-    }
-    const int nchunk_max = (int)((K + GF_KC - 1) / GF_KC);
-    double P[4][4];
-#pragma unroll
-    for (int m = 0; m < 4; m++)
-#pragma unroll
-        for (int q = 0; q < 4; q++) P[m][q] = 0.0;
-    const int ct0 = SPLIT ? (int)blockIdx.y : 0;
-    const int ct1 = SPLIT ? (int)blockIdx.y + 1 : n_coltiles;
-    for (int ct = ct0; ct < ct1; ct++) {
-        const double* Bblk = B + (long)ct * GF_T;
-        const long kend = (long)(ct + 1) * GF_T < K ? (long)(ct + 1) * GF_T : K;
-        const int c0 = SPLIT ? (int)blockIdx.z : 0;
-        const int c1 = SPLIT ? (int)blockIdx.z + 1 : nchunk_max;
-        for (int c = c0; c < c1; c++) {
-            const long kc0 = (long)c * GF_KC;
-            if (kc0 >= kend) break;
-            const long kc1 = kc0 + GF_KC < kend ? kc0 + GF_KC : kend;
-            const long nkb = (kc1 - kc0) / GF_BK;
-            f64x4 acc[4][4];
-#pragma unroll
-            for (int m = 0; m < 4; m++)
-#pragma unroll
-                for (int n = 0; n < 4; n++) acc[m][n] = (f64x4){0.0, 0.0, 0.0, 0.0};
-            GfStage<1> st;
-            gf_load<1>(st, Ablk, lda, Bblk, ldb, kc0, t);
-            __syncthreads();  // the previous chunk's readers are done with buffer 0
-            gf_store<1>(st, lds[0], lds[0] + GF_LDSA_DOUBLES, t);
-            __syncthreads();
-            int cur = 0;
-            for (long kb = 0; kb < nkb; kb++) {
-                const bool more = kb + 1 < nkb;
-                if (more) gf_load<1>(st, Ablk, lda, Bblk, ldb, kc0 + (kb + 1) * GF_BK, t);
-                gf_compute<1>(acc, lds[cur], lds[cur] + GF_LDSA_DOUBLES, wr, wc, lane, mlim);
-                if (more) gf_store<1>(st, lds[cur ^ 1], lds[cur ^ 1] + GF_LDSA_DOUBLES, t);
-                __syncthreads();
-                cur ^= 1;
-            }
-            // C/D map of v_mfma_f64_16x16x4_f64: col = lane&15, row = (lane>>4) + 4*reg
-#pragma unroll
-            for (int m = 0; m < 4; m++)
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const long r = row0 + wr * 64 + m * 16 + g + 4 * q;
-                    const int8_t* mr = A8 + r * lda + (long)ct * GF_T + wc * 64 + i16;
-                    double s = 0.0;
-#pragma unroll
-                    for (int n = 0; n < 4; n++) s += acc[m][n][q] * (double)mr[n * 16];
-                    s += __shfl_xor(s, 1);
-                    s += __shfl_xor(s, 2);
-                    s += __shfl_xor(s, 4);
-                    s += __shfl_xor(s, 8);
-                    if (SPLIT) {
-                        if (i16 == 0)
-                            partial[((((long)blockIdx.x * n_coltiles + ct) * nchunk_max + c) * 2 + wc) * GF_T + wr * 64 + m * 16 + g + 4 * q] = s;
-                    } else {
-                        P[m][q] += s;
-                    }
-                }
-        }
-    }
-    if (!SPLIT) {
-        __syncthreads();
-        double* red = lds[0];  // [2][128]
-        if (i16 == 0) {
-#pragma unroll
-            for (int m = 0; m < 4; m++)
-#pragma unroll
-                for (int q = 0; q < 4; q++) red[wc * 128 + wr * 64 + m * 16 + g + 4 * q] = P[m][q];
-        }
-        __syncthreads();
-        if (t < 128) out[row0 + t] = red[t] + red[128 + t];
-    }
-}
-// vara of the rows of the SPLIT form: out[dst ? dst[r] : r] = P_0 + P_1, P_wc the chain of the partial sums in the order above.
+// vara of the rows of the SPLIT form: out[dst ? dst[r] : r] = P_0 + P_1, P_wc the chain of the partial sums in the order k_vara_f64d defines.
 __global__ __launch_bounds__(128) void k_vara_f64_sum(const double* __restrict__ partial, int n_coltiles, long K, const int* __restrict__ count,
                                                       const long* __restrict__ dst, double* __restrict__ out) {
     const long r = (long)blockIdx.x * GF_T + threadIdx.x;
@@ -686,68 +492,14 @@ extern "C" int eagle_dev_add_i32(eagle_ctx* ctx, int32_t* dst, const int32_t* sr
 // ranges whose partial tiles go to a scratch buffer and are added in a fixed order by k_gemm_f64_tail (deterministic).
 // skip_if / skip_val: the whole launch is dropped on the device when *skip_if == skip_val (the lower-triangle launch of
 // a product the symmetry check found symmetric).
-// ------------------------------------------------------------------------------------------------
-template <int LDA, int XCDMAP>
-__global__ __launch_bounds__(256, 2) void k_gemm_f64_list(const double* __restrict__ A, long lda, const double* __restrict__ B, long ldb,
-                                                          double* __restrict__ C, long ldc, long K, const int* __restrict__ tiles, int n_main,
-                                                          int split, double* __restrict__ scratch, const int* __restrict__ skip_if, int skip_val) {
-    constexpr int LDSA = GF_T * LDA;
-    __shared__ __attribute__((aligned(16))) double lds[2][LDSA + GF_LDSB_DOUBLES];
-    if (skip_if && *skip_if == skip_val) return;
-    int b = blockIdx.x;
-    // XCDMAP: workgroup b runs on XCD b % 8 (observed dealing); give each XCD a contiguous range of the whole tiles of the list
-    if (XCDMAP && b < n_main) b = (b & 7) * (n_main >> 3) + (b >> 3);
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6, wr = w >> 1, wc = w & 1;
-    const int i16 = lane & 15, g = lane >> 4;
-    const long nkb_all = K / GF_BK;
-    int tile;
-    long kb0 = 0, kb1 = nkb_all;
-    double* out;
-    long ldo;
-    if (b < n_main) {
-        tile = tiles[b];
-        out = nullptr; ldo = ldc;
-    } else {
-        const int u = b - n_main, tt = u / split, ks = u - tt * split;
-        tile = tiles[n_main + tt];
-        kb0 = nkb_all * ks / split;
-        kb1 = nkb_all * (ks + 1) / split;
-        out = scratch + (long)u * (GF_T * GF_T);
-        ldo = GF_T;
-    }
-    const long row0 = (long)(tile >> 16) * GF_T, col0 = (long)(tile & 0xffff) * GF_T;
-    const void* Ablk = (const void*)(A + row0 * lda);
-    const double* Bblk = B + col0;
-    f64x4 acc[4][4];
-#pragma unroll
-    for (int m = 0; m < 4; m++)
-#pragma unroll
-        for (int n = 0; n < 4; n++) acc[m][n] = (f64x4){0.0, 0.0, 0.0, 0.0};
-    GfStage<0> st;
-    gf_load<0>(st, Ablk, lda, Bblk, ldb, kb0 * GF_BK, t);
-    gf_store<0, LDA>(st, lds[0], lds[0] + LDSA, t);
-    __syncthreads();
-    int cur = 0;
-    for (long kb = kb0; kb < kb1; kb++) {
-        const bool more = kb + 1 < kb1;
-        if (more) gf_load<0>(st, Ablk, lda, Bblk, ldb, (kb + 1) * GF_BK, t);
-        gf_compute<0, LDA>(acc, lds[cur], lds[cur] + LDSA, wr, wc, lane);
-        if (more) gf_store<0, LDA>(st, lds[cur ^ 1], lds[cur ^ 1] + LDSA, t);
-        __syncthreads();
-        cur ^= 1;
-    }
-    double* dst = out ? out : C + row0 * ldc + col0;
-#pragma unroll
-    for (int m = 0; m < 4; m++)
-#pragma unroll
-        for (int n = 0; n < 4; n++)
-#pragma unroll
-            for (int q = 0; q < 4; q++) dst[(long)(wr * 64 + m * 16 + g + 4 * q) * ldo + wc * 64 + n * 16 + i16] = acc[m][n][q];
-}
-// The same tile with EIGHT waves (4 x 2, wave tile 32 x 64 = 2 x 4 MFMA tiles, 64 accumulator registers): under 128 VGPRs, so two
-// workgroups = 16 waves = 4 per SIMD are resident and the matrix pipe has four waves to choose from around every barrier
-// instead of two (the 4-wave form keeps the fp64 pipe 83 % busy).  Same K order per element: bitwise the same C.
+// Serves the sizes that are a multiple of 128 and not of 256 (k_gemm_f64_dma below has the others).
+// The tile, v_mfma_f64_16x16x4_f64: K block 16; inside a K block the lane group g = lane>>4 owns k = 4g + s for MFMA step s, so a lane
+// reads 4 consecutive k of its A row at once (the k order of an fp64 sum is a free choice; it is fixed, hence deterministic).
+// EIGHT waves (4 x 2, wave tile 32 x 64 = 2 x 4 MFMA tiles, 64 accumulator registers): under 128 VGPRs, so two workgroups = 16 waves
+// = 4 per SIMD are resident and the matrix pipe has four waves to choose from around every barrier instead of two (a four-wave form
+// of the same tile, since removed, kept the fp64 pipe 83 % busy: 50.4 -> 48.4 ms for W at n = 10,000, same bits).
 // Sixteen waves (wave tile 16 x 64, 64 VGPRs with spills) were measured too: 54.8 ms against 48.4 ms at n = 10,000, not kept.
+// ------------------------------------------------------------------------------------------------
 template <int LDA>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_gemm_f64_list8(const double* __restrict__ A, long lda, const double* __restrict__ B, long ldb,
                                                            double* __restrict__ C, long ldc, long K, const int* __restrict__ tiles, int n_main,
@@ -1043,18 +795,29 @@ __global__ __launch_bounds__(256) void k_gemm_f64_dma_tail(const double* __restr
 
 // ------------------------------------------------------------------------------------------------
 // k_vara_f64d (round 3): the fp64 vara kernel -- scan mode 0, the re-evaluation engine of the certification, the overflow fallback --
-// rebuilt on the lessons of k_gemm_f64_dma: every vector instruction between two fp64 MFMAs of a wave costs ~6 of the matrix pipe's
-// cycles (tools/ubench/f64_ceiling.hip), and k_vara_f64 converted its int8 A fragments to doubles inside the K loop (12 VALU per
-// 16 MFMAs, every element converted by both column waves) on top of register-staged B tiles.  Here
+// vara_i = sum_k m_ik sum_{j<=k} m_ij Wu[j][k] (calculate_a_and_vara_rcpp.cpp:103-112) for the 128 markers of a row block, A = int8
+// genotypes, B = Wu (upper triangular fold of W, so column tile ct only needs k < (ct+1)*128).
+// The summation order is FIXED and is the definition of this library's fp64 result:
+//   s_{ct,c}(i, wc) = the row-dot of column tile ct, restricted to the 64 columns of wave column wc, of the partial product over
+//                     the K chunk c = [2048 c, 2048 (c+1)): the MFMA chain over the chunk, then per lane a 4-term chain over
+//                     the lane's columns, then a butterfly over the 16 lanes of the row;
+//   P_wc(i)         = the s_{ct,c} added one by one, ct ascending, c ascending inside a tile;   vara_i = P_0(i) + P_1(i).
+// SPLIT = false: one workgroup walks every (column tile, chunk) of its row block and keeps the running P.
+// SPLIT = true : one workgroup per (column tile, chunk, row block); it writes s_{ct,c} to partial[rb][ct][c][wc][128] and
+//                k_vara_f64_sum forms the same chain -- bitwise the same vara for a row, whichever form computed it and
+//                whatever rows share its block.  That is what lets the digit-slice scan re-evaluate a handful of markers in
+//                fp64 on the whole chip (k_cert_*, eagle_i8mfma.hip: the longest workgroup is one 2048-deep chunk, 0.3 ms,
+//                instead of a 10240-deep tile) and promise the fp64-mode result for them.
+// gate (may be NULL): SPLIT = false -> the launch is dropped unless *gate != 0; SPLIT = true -> row blocks at or beyond
+// *gate rows are dropped, and 16-row tiles entirely beyond the count are not computed.
+// Built on the lessons of k_gemm_f64_dma: every vector instruction between two fp64 MFMAs of a wave costs ~6 of the matrix pipe's
+// cycles (tools/ubench/f64_ceiling.hip), and the round-2 kernel (k_vara_f64, since removed) converted its int8 A fragments to doubles
+// inside the K loop (12 VALU per 16 MFMAs, every element converted by both column waves) on top of register-staged B tiles.  Here
 //   * the genotype bytes of a K block are converted ONCE by the staging threads (8 per thread) and written to LDS as an fp64 tile
 //     [128 rows][128 B] with k_gemm_f64_dma's chunk swizzle; the fragments come back with two ds_read_b128 per 16-row tile;
 //   * Wu's K block arrives by LDS-DMA ([16 k][1 KiB], 128-byte block swizzle), no VGPR staging;
 //   * same lane-group ownership of k as k_gemm_f64_dma ({2g, 2g+1, 8+2g, 9+2g}), same barrier-to-barrier regions;
 //   * 4 waves 2 x 2, wave tile 64 x 64, two workgroups per CU (64 KiB of LDS each): two waves per SIMD.
-// Everything that DEFINES the result is as in k_vara_f64 except the k order inside a K block: per (row, column tile, 2048-deep K
-// chunk, 64-column half) the MFMA chain over the chunk, a 4-term chain + 16-lane butterfly, the partial row-dots added tiles
-// ascending, chunks ascending, the two halves last.  SPLIT = true puts every (tile, chunk) on its own workgroup and k_vara_f64_sum
-// forms the same chain: bitwise the same value for a row whichever form computed it.  (tune 28: the round-2 kernel, for A/B runs.)
 // ------------------------------------------------------------------------------------------------
 #define V2_A_BYTES (GF_T * GF_BK * 8)
 #define V2_B_BYTES (GF_BK * GF_T * 8)
@@ -1259,17 +1022,9 @@ static int gemm_tile_list(eagle_ctx* ctx, int nt, int kind, int rt0, int rt1, co
     auto it = g_gemm_lists.find(key);
     if (it != g_gemm_lists.end()) { *out = it->second.first; *count = it->second.second; return EAGLE_OK; }
     std::vector<int> h;
-    const int base_kind = kind & 15;
-    if (kind & 16) {  // 8 x 8 super-tiles (experiment, tune 23 / 24): 64 consecutive entries share 8 row and 8 column panels
-        for (int si = rt0; si < rt1; si += 8)
-            for (int sj = 0; sj < nt; sj += 8)
-                for (int i = si; i < si + 8 && i < rt1; i++)
-                    for (int j = sj; j < sj + 8 && j < nt; j++)
-                        if (base_kind == 0 || (base_kind == 1 && i <= j) || (base_kind == 2 && i > j)) h.push_back((i << 16) | j);
-    } else
     for (int i = rt0; i < rt1; i++)   // row tile outer: consecutive workgroups share an A row panel (measured 4 % faster than column-major)
         for (int j = 0; j < nt; j++)
-            if (base_kind == 0 || (base_kind == 1 && i <= j) || (base_kind == 2 && i > j)) h.push_back((i << 16) | j);
+            if (kind == 0 || (kind == 1 && i <= j) || (kind == 2 && i > j)) h.push_back((i << 16) | j);
     int* d = nullptr;
     if (!h.empty()) {
         hipError_t e = hipMalloc((void**)&d, h.size() * sizeof(int));
@@ -1360,18 +1115,18 @@ static int gemm_f64_dma_tiles(eagle_ctx* ctx, const double* A, const double* B, 
     return EAGLE_OK;
 }
 
+// sizes k_gemm_f64_dma serves (its 256-row tiles, int32 offsets inside a row panel); the scan operands are pipelined on it at those
+static bool gemm_f64_dma_serves(long np) { return np % 256 == 0 && 256 * np * 8 < 2147483648L; }
 static int gemm_f64_tiles(eagle_ctx* ctx, const double* A, const double* B, double* C, long np, int kind, const int* skip_if, int skip_val,
                           void* stream, int rt0 = 0, int rt1 = -1) {
     if (np % GF_T || np <= 0 || np / GF_T > 65535) return eagle_fail(ctx, EAGLE_ERR_ARG, "gemm_f64: size must be a multiple of 128");
-    // n_pad % 256 == 0 (every size eagle_pad produces): the 256 x 128 LDS-DMA kernel; tune 21..27 keep the 128 x 128 forms for A/B runs
-    if (np % 256 == 0 && 256 * np * 8 < 2147483648L && !(ctx->tune >= 21 && ctx->tune <= 27))
+    // n_pad % 256 == 0 (every size eagle_pad produces): the 256 x 128 LDS-DMA kernel; other multiples of 128: the 128 x 128 tile below
+    if (gemm_f64_dma_serves(np))
         return gemm_f64_dma_tiles(ctx, A, B, C, np, kind, skip_if, skip_val, stream, rt0, rt1 < 0 ? (int)(np / GF_T) : rt1, false);
     const int* tiles = nullptr;
     long count = 0;
     if (rt1 < 0) rt1 = (int)(np / GF_T);
-    const int tune = ctx->tune;
-    const bool super_tiles = tune == 23 || tune == 24;
-    int rc = gemm_tile_list(ctx, (int)(np / GF_T), kind | (super_tiles ? 16 : 0), rt0, rt1, &tiles, &count);
+    int rc = gemm_tile_list(ctx, (int)(np / GF_T), kind, rt0, rt1, &tiles, &count);
     if (rc || count == 0) return rc;
     const long slots = 2L * (ctx->cu_count > 0 ? ctx->cu_count : 256);  // resident workgroups (2 per CU)
     const long n_main = count / slots * slots, tail = count - n_main;
@@ -1397,19 +1152,8 @@ static int gemm_f64_tiles(eagle_ctx* ctx, const double* A, const double* B, doub
         scratch = (double*)ctx->gemm_scratch;
     }
     const long blocks = split > 1 ? n_main + tail * split : count;
-#define GEMM_LAUNCH(LDA_, X_) hipLaunchKernelGGL((k_gemm_f64_list<LDA_, X_>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, A, np, B, np, C, np, np, tiles, \
-                       (int)(split > 1 ? n_main : count), split, scratch, skip_if, skip_val)
-    switch (tune) {  // 21..26: schedule experiments of tools/bench_gemm.py (profiles/r02_gemm_ab.txt); anything else: the shipped form
-        case 21: GEMM_LAUNCH(18, 0); break;      // round 1's A pitch, four waves
-        case 22: GEMM_LAUNCH(24, 0); break;
-        case 23: GEMM_LAUNCH(GF_LDA, 1); break;  // XCD-contiguous 8 x 8 super-tile order: neutral
-        case 24: GEMM_LAUNCH(18, 1); break;
-        case 26: GEMM_LAUNCH(GF_LDA, 0); break;  // four waves per tile, pitch 20 (shipped until the eight-wave form)
-        default:  // (tune 25, and sizes that are not a multiple of 256) eight waves per tile: 50.4 -> 48.4 ms for W at n = 10,000 (66.6 TF incl. v, symmetry check, fold), same bits
-            hipLaunchKernelGGL((k_gemm_f64_list8<GF_LDA>), dim3((unsigned)blocks), dim3(512), 0, (hipStream_t)stream, A, np, B, np, C, np, np, tiles,
-                               (int)(split > 1 ? n_main : count), split, scratch, skip_if, skip_val);
-    }
-#undef GEMM_LAUNCH
+    hipLaunchKernelGGL((k_gemm_f64_list8<GF_LDA>), dim3((unsigned)blocks), dim3(512), 0, (hipStream_t)stream, A, np, B, np, C, np, np, tiles,
+                       (int)(split > 1 ? n_main : count), split, scratch, skip_if, skip_val);
     if (split > 1)
         hipLaunchKernelGGL(k_gemm_f64_tail, dim3((unsigned)(tail * 16)), dim3(256), 0, (hipStream_t)stream, scratch, tiles + n_main, split, C, np, skip_if,
                            skip_val);
@@ -1453,14 +1197,11 @@ extern "C" int eagle_dev_scan_operands_begin(eagle_ctx* ctx, const double* Sa, c
     LAUNCH_CHECK(ctx);
     return EAGLE_OK;
 }
-static bool scan_operands_pipelined(const eagle_ctx* ctx, long n_pad) {
-    return n_pad % 256 == 0 && 256 * n_pad * 8 < 2147483648L && !(ctx->tune >= 21 && ctx->tune <= 27);
-}
 extern "C" int eagle_dev_scan_operands_vrows(eagle_ctx* ctx, const double* Sa, const double* Va, long n_pad, long row0, long row1, double* tmp,
                                              void* stream) {
     if (n_pad % GF_T || row0 % GF_T || row1 % GF_T || row0 < 0 || row1 > n_pad || row0 >= row1)
         return eagle_fail(ctx, EAGLE_ERR_ARG, "scan_operands_vrows: bad padding or row block");
-    if (!scan_operands_pipelined(ctx, n_pad)) return EAGLE_OK;  // (the 128 x 128 kernels of the A/B runs: all of it in _finish)
+    if (!gemm_f64_dma_serves(n_pad)) return EAGLE_OK;  // (the 128 x 128 kernel: all of it in _finish)
     return gemm_f64_dma_tiles(ctx, Va, Sa, tmp, n_pad, 0, nullptr, 0, stream, (int)(row0 / GF_T), (int)(row1 / GF_T), false);
 }
 extern "C" int eagle_dev_scan_operands_finish(eagle_ctx* ctx, const double* Sa, const double* Va, long n_pad, double* Wu_out, double* tmp, void* stream) {
@@ -1473,7 +1214,7 @@ extern "C" int eagle_dev_scan_operands_finish(eagle_ctx* ctx, const double* Sa, 
     LAUNCH_CHECK(ctx);
     int rc;
     const int nt = (int)(n_pad / GF_T);
-    if (scan_operands_pipelined(ctx, n_pad)) {
+    if (gemm_f64_dma_serves(n_pad)) {
         // symmetric: W' = Sa * X on the tiles with column tile <= last row tile ... i.e. NOT strictly above the diagonal, transposed
         // into the upper tiles of Wu (skipped when the check failed)
         rc = gemm_f64_dma_tiles(ctx, Sa, tmp, Wu_out, n_pad, 3, sym, 0, stream, 0, nt, true);
@@ -1956,12 +1697,8 @@ extern "C" int eagle_dev_vara_f64_gated(eagle_ctx* ctx, const int8_t* Mt8, long 
         return eagle_fail(ctx, EAGLE_ERR_ARG, "vara_f64: layout contract violated");
     if (L_pad == 0) return EAGLE_OK;
     dim3 grid((unsigned)(L_pad / GF_T));
-    if (ctx->tune == 28)  // the round-2 kernel (A/B runs)
-        hipLaunchKernelGGL((k_vara_f64<false>), grid, dim3(256), 0, (hipStream_t)stream, Mt8, ld, Wu, n_pad, vara_out, (int)(n_pad / GF_T), n_pad,
-                           run_if, (double*)nullptr);
-    else
-        hipLaunchKernelGGL((k_vara_f64d<false>), grid, dim3(256), 0, (hipStream_t)stream, Mt8, ld, Wu, n_pad, vara_out, (int)(n_pad / GF_T), n_pad,
-                           run_if, (double*)nullptr);
+    hipLaunchKernelGGL((k_vara_f64d<false>), grid, dim3(256), 0, (hipStream_t)stream, Mt8, ld, Wu, n_pad, vara_out, (int)(n_pad / GF_T), n_pad,
+                       run_if, (double*)nullptr);
     LAUNCH_CHECK(ctx);
     return EAGLE_OK;
 }
@@ -1977,13 +1714,9 @@ extern "C" int eagle_dev_vara_f64_split(eagle_ctx* ctx, const int8_t* rows8, lon
         return eagle_fail(ctx, EAGLE_ERR_ARG, "vara_f64_split: layout contract violated");
     if (rows_cap == 0) return EAGLE_OK;
     const int nct = (int)(n_pad / GF_T);
-    dim3 grid((unsigned)(rows_cap / GF_T), (unsigned)nct, (unsigned)((n_pad + GF_KC - 1) / GF_KC));
-    if (ctx->tune == 28)
-        hipLaunchKernelGGL((k_vara_f64<true>), grid, dim3(256), 0, (hipStream_t)stream, rows8, ld, Wu, n_pad, (double*)nullptr, nct, n_pad, count_dev,
-                           partial);
-    else
-        hipLaunchKernelGGL((k_vara_f64d<true>), dim3(grid.y, grid.z, grid.x), dim3(256), 0, (hipStream_t)stream, rows8, ld, Wu, n_pad, (double*)nullptr, nct,
-                           n_pad, count_dev, partial);
+    dim3 grid((unsigned)nct, (unsigned)((n_pad + GF_KC - 1) / GF_KC), (unsigned)(rows_cap / GF_T));   // the row block slowest (k_vara_f64d)
+    hipLaunchKernelGGL((k_vara_f64d<true>), grid, dim3(256), 0, (hipStream_t)stream, rows8, ld, Wu, n_pad, (double*)nullptr, nct, n_pad, count_dev,
+                       partial);
     hipLaunchKernelGGL(k_vara_f64_sum, dim3((unsigned)(rows_cap / GF_T)), dim3(GF_T), 0, (hipStream_t)stream, partial, nct, n_pad, count_dev, dst_dev, out);
     LAUNCH_CHECK(ctx);
     return EAGLE_OK;

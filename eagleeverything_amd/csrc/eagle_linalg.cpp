@@ -6,7 +6,7 @@
 //   eagle_sym_eig ................. eigen(A, symmetric = TRUE)                 rocSOLVER dsyevd
 //   eagle_chol2inv ................ chol2inv(chol(A))                          rocSOLVER dpotrf + dpotri
 //   eagle_inverse ................. solve(A)                                   rocSOLVER dgetrf + dgetri
-//   eagle_matmul .................. A %*% B                                    this library's fp64 MFMA GEMM (k_gemm_f64_list)
+//   eagle_matmul .................. A %*% B                                    this library's fp64 MFMA GEMM (k_gemm_f64_dma)
 //   eagle_mmt_sqrt_and_sqrtinv .... E/R/calculateMMt_sqrt_and_sqrtinv.R:15-47  the four above, data staying in HBM
 //
 // rocSOLVER / rocBLAS are LIBRARY calls (fine for this row: it is not the hot path and has no kernel of this repository to

@@ -106,7 +106,7 @@ __global__ __launch_bounds__(512, 2) void k_line_scores_i8(const int8_t* __restr
         const int kn = (int)((s + 1) * BK8);
         const bool more = s + 1 < s1;
         if (active) {
-            t8_stage_compute<0>(acc, lds[cur][0], lds[cur][1], rd, more, rsA, ln, ld, kn, lds[cur ^ 1][0], rsB, ln, ld, kn, lds[cur ^ 1][1], w);
+            t8_stage_compute(acc, lds[cur][0], lds[cur][1], rd, more, rsA, ln, ld, kn, lds[cur ^ 1][0], rsB, ln, ld, kn, lds[cur ^ 1][1], w);
         } else if (more) {
             t8_stage(rsA, ln, ld, kn, lds[cur ^ 1][0], w);
             t8_stage(rsB, ln, ld, kn, lds[cur ^ 1][1], w);

@@ -11,7 +11,7 @@
 // ~15 ms against ~215 ms for the digit-slice scan of the opaque S, V interface).  The price is the one-time Z = Mt U
 // (2 L n^2 fp64 flop, the cost of one fp64-mode scan) and 8 bytes per genotype of HBM.
 //
-//   k_zbuild ............ Z = Mt8 * U on the fp64 MFMA (int8 A converted in registers; the core of k_vara_f64 with a store epilogue)
+//   k_zbuild ............ Z = Mt8 * U on the fp64 MFMA (int8 A converted in registers; the core of the round-2 fp64 vara kernel with a store epilogue)
 //   k_spectral_scan ..... lin[i][0..p] = z_i^T G (G = [D U^T y | D U^T X]) on v_mfma_f64_16x16x4_f64, quad_i = sum_k z_ik^2 d_k on the VALU,
 //                         one streaming read of Z                                                          (bound: HBM)
 //   k_spectral_finish ... the p x p form per marker, a and vara

@@ -73,8 +73,8 @@ __device__ __forceinline__ void t8_compute(i32x16 (&acc)[4][2], const int8_t* ld
 }
 
 // One pipeline stage: DMA the next stage into (nA, nB) if `more`, then the 4 k-steps of the current stage.
-// TUNE 3 / 4 are ablations for tools/bench_i8_engine.py (3: no DMA, 4: DMA + one k-step); results are wrong there.
-// Measured on the MM^T SYRK (n = 5000, L = 262144, same process, interleaved): full 2.93 ms, no-DMA 2.32 ms, DMA-only
+// Measured on the MM^T SYRK with two ablations that have since left the code (no DMA; DMA + one k-step; wrong results by design)
+// (n = 5000, L = 262144, same process, interleaved): full 2.93 ms, no-DMA 2.32 ms, DMA-only
 // 2.78 ms: the kernel is bound by the L2 -> LDS fill rate (~40 GB/s per CU at a 70-80 % L2 hit rate), not by MFMA issue.
 // Tried and NOT faster (kept out of the code): staggering the DMA issue of waves 4-7 by half a stage (-13 %), spreading
 // the DMA pieces over the k-steps (+-2 %), software-pipelined fragment reads pinned with sched_group_barrier (-3 %),
@@ -95,16 +95,15 @@ __device__ __forceinline__ void t8_compute(i32x16 (&acc)[4][2], const int8_t* ld
 // tools/ubench/fill_rate.hip measures what bounds it: filling 64 KiB of LDS takes 1.15-1.2 us per CU when every line
 // is an L2 hit and 3.1 us when every line comes from HBM, by LDS-DMA and by register staging alike; at the 72-82 %
 // hit rate of these kernels (rocprofv3 TCC_HIT/TCC_REQ) that is 1.5-1.7 us per stage against 0.9-1.1 us of MFMA work.
-template <int TUNE>
 __device__ __forceinline__ void t8_stage_compute(i32x16 (&acc)[4][2], const int8_t* ldsA, const int8_t* ldsB, const T8Read& rd,
                                                  bool more, __amdgpu_buffer_rsrc_t rsA, const T8Lane& lnA, int ldA, int kA,
                                                  int8_t* nA, __amdgpu_buffer_rsrc_t rsB, const T8Lane& lnB, int ldB, int kB,
                                                  int8_t* nB, int w) {
     const int8_t* pa = ldsA + rd.offA;
     const int8_t* pb = ldsB + rd.offB;
-    if (TUNE != 3 && more) { t8_stage(rsA, lnA, ldA, kA, nA, w); t8_stage(rsB, lnB, ldB, kB, nB, w); }
+    if (more) { t8_stage(rsA, lnA, ldA, kA, nA, w); t8_stage(rsB, lnB, ldB, kB, nB, w); }
 #pragma unroll
-    for (int ks = 0; ks < (TUNE == 4 ? 1 : 4); ks++) t8_kstep(acc, pa, pb, rd.ch[ks]);
+    for (int ks = 0; ks < 4; ks++) t8_kstep(acc, pa, pb, rd.ch[ks]);
 }
 
 __device__ __forceinline__ void t8_zero(i32x16 (&acc)[4][2]) {
@@ -118,7 +117,6 @@ __device__ __forceinline__ void t8_zero(i32x16 (&acc)[4][2]) {
 // The body of the Gram kernels on this engine (k_syrk_i8: A = B = M8; k_gram_i8ab of eagle_grm.hip: A = a genotype window, B = the
 // same window with every column scaled):  C[i][j] += sum_k A[i][k] B[j][k]  over the upper-triangular 256-tile pairs of `pairs`
 // (grid.x = pairs x K splits), a tile on the diagonal in full.  Integer atomics: exact, any order.  `lds` is the kernel's 128 KiB.
-template <int TUNE>
 __device__ __forceinline__ void t8_gram_tiles(int8_t (*lds)[2][TILE_BYTES], const int8_t* __restrict__ A, long ldA_, const int8_t* __restrict__ B,
                                               long ldB_, const int* __restrict__ pairs, int npairs, int nblocks, long nstages,
                                               long stages_per_split, int32_t* __restrict__ C, long ldc) {
@@ -151,8 +149,8 @@ __device__ __forceinline__ void t8_gram_tiles(int8_t (*lds)[2][TILE_BYTES], cons
     const T8Read rd = t8_read_init(wr, wc, lane);
     for (long s = s0; s < s1; s++) {
         const int kn = (int)((s + 1) * BK8);
-        t8_stage_compute<TUNE>(acc, lds[cur][0], lds[cur][1], rd, s + 1 < s1, rsA, lnA, ldA, kn, lds[cur ^ 1][0], rsB, lnB, ldB, kn,
-                               lds[cur ^ 1][1], w);
+        t8_stage_compute(acc, lds[cur][0], lds[cur][1], rd, s + 1 < s1, rsA, lnA, ldA, kn, lds[cur ^ 1][0], rsB, lnB, ldB, kn,
+                         lds[cur ^ 1][1], w);
         __syncthreads();
         cur ^= 1;
     }

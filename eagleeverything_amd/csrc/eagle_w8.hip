@@ -353,8 +353,8 @@ __global__ __launch_bounds__(512, 2) void k_w8_gemm(const int8_t* __restrict__ A
             rsA = t8_rsrc(Arow + (long)gp->p[pr1] * sstride, ldi);
             rsB = t8_rsrc(Brow + (long)gp->q[pr1] * sstride, ldi);
         }
-        t8_stage_compute<0>(acc, lds[cur][0], lds[cur][1], rd, more, rsA, ln, ldi, s1 * BK8, lds[cur ^ 1][0], rsB, ln, ldi, s1 * BK8,
-                            lds[cur ^ 1][1], w);
+        t8_stage_compute(acc, lds[cur][0], lds[cur][1], rd, more, rsA, ln, ldi, s1 * BK8, lds[cur ^ 1][0], rsB, ln, ldi, s1 * BK8,
+                         lds[cur ^ 1][1], w);
         __syncthreads();
         cur ^= 1;
         s = s1; pr = pr1;
@@ -953,9 +953,9 @@ static int w8_workspace(eagle_ctx* ctx, long np, W8Ws* w) {
 // row statistics + digit slices of the rows [r0, r1) of one operand
 static int w8_rows_of(eagle_ctx* ctx, const double* M, long np, long r0, long r1, double* d, double* mx, double* ssq, int* e, unsigned long long* dssq,
                       int8_t* slices, W8Ws& w, hipStream_t s) {
-    // one pass while a row fits LDS (tune 32: the two-kernel form at any size, for A/B runs and the test that compares the two)
+    // one pass while a row fits LDS (TUNE_W8_ROWPASS_SPLIT: the two-kernel form at any size, for A/B runs and the test that compares the two)
     const size_t row_lds = (size_t)W8_LIDX(np) * sizeof(double);
-    if (ctx->tune != 32 && row_lds + 6144 <= (size_t)160 * 1024) {
+    if (tune_w8_rowpass_once(ctx) && row_lds + 6144 <= (size_t)160 * 1024) {
         if (row_lds > ctx->attr_w8_rowpass) {
             hipError_t ea = hipFuncSetAttribute((const void*)k_w8_rowpass, hipFuncAttributeMaxDynamicSharedMemorySize, (int)row_lds);
             if (ea != hipSuccess) return eagle_fail_hip(ctx, ea, "hipFuncSetAttribute(k_w8_rowpass)");
@@ -1009,7 +1009,7 @@ static int w8_product(eagle_ctx* ctx, int cfg, bool upper, long np, const int8_t
     for (int rt0 = 0; rt0 < nt; rt0 += (int)rt_per_panel) {
         const int rt1 = (int)std::min<long>(nt, rt0 + rt_per_panel);
         W8List l;
-        const bool piped = ctx->tune != 31 && (double)np * TW_M < 2147483648.0;   // tune 31: the compiler-scheduled 256 x 256 form (A/B runs)
+        const bool piped = tune_w8_piped(ctx) && (double)np * TW_M < 2147483648.0;   // TUNE_W8_UNPIPED: the compiler-scheduled 256 x 256 form (A/B runs)
         int rc = w8_get_list(ctx, nt, rt0, rt1, upper, piped, cfg, maxp, &l, c0, c1);
         if (rc) return rc;
         const long img_elems = (long)(rt1 - rt0) * T8 * ncols;

@@ -2,7 +2,7 @@
 
 Level 1 of the spectral bound needs the row sums of |Ds Ds|, level 2 needs E_hi = round(offdiag(Ds Ds) / 2^s), the sum of squares of what
 the rounding leaves, the largest diagonal entry and an overflow flag: the same exact int32 product.  The level-1 kernel now leaves all of
-it on the way; the two-kernel form (k_gram_hi_i8 forms the product again) stays behind tune 33.  These tests hold the two forms against
+it on the way; the two-kernel form (k_gram_hi_i8 forms the product again) stays behind TUNE["GRAM_TWICE"].  These tests hold the two forms against
 each other, bit for bit, in every state the header can be left in:
   (a)  level 1 takes the digit under eagle_set_scan_budget(5e-7) -- the fused kernel has written the level-2 fields and E_hi by then, and
        the header must read as if nobody had (zeros);
@@ -17,12 +17,14 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from eagleeverything_amd._lib import TUNE
+
 from exact_lastdigit import decode_header as _hdr   # the head of the digit workspace, decoded in one place
 
 pytestmark = pytest.mark.gpu
 L_MARKERS = 256
 POISON = 0xA5
-TWO_KERNELS = 33   # ctx->tune: level 2 forms Ds Ds again
+TWO_KERNELS = TUNE["GRAM_TWICE"]   # level 2 forms Ds Ds again
 
 
 def _operands(n, diag):
@@ -57,7 +59,7 @@ def _run(torch, sh, tune):
         torch.cuda.synchronize()
         return head, slots, sh.vara[:L_MARKERS].cpu().numpy().copy()
     finally:
-        sh.L.eagle_dev_set_tune(sh.ctx, 0)
+        sh.L.eagle_dev_set_tune(sh.ctx, TUNE["SHIPPED"])
 
 
 # diag: the scale of W's diagonal that reaches the case at both sizes (the digit rule restated on the host, as tests/test_gpu_spectral.py
@@ -80,7 +82,7 @@ def test_fused_gram_leaves_what_the_two_kernels_leave(n, case):
     sh._check(sh.L.eagle_set_scan_budget(sh.ctx, budget))
     try:
         head2, slots2, vara2 = _run(torch, sh, TWO_KERNELS)
-        head1, slots1, vara1 = _run(torch, sh, 0)
+        head1, slots1, vara1 = _run(torch, sh, TUNE["SHIPPED"])
     finally:
         sh._check(sh.L.eagle_set_scan_budget(sh.ctx, 0.0))
     h1, h2 = _hdr(head1), _hdr(head2)

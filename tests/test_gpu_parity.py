@@ -10,6 +10,7 @@ import pytest
 
 from conftest import GOLDEN_CASES
 from eagleeverything_amd import synth
+from eagleeverything_amd._lib import TUNE
 
 pytestmark = pytest.mark.gpu
 NA = np.nan
@@ -735,10 +736,10 @@ def test_stochastic_rounding_option(api, oracle):
     Mt_s = sh.Mt8[rows][:, :n].cpu().numpy()
     a_ref, v_ref = oracle.scan_from_i8(Mt_s, S.cpu().numpy(), V.cpu().numpy(), ahat.cpu().numpy())
     sh.mode = 1
-    sh.L.eagle_dev_set_tune(sh.ctx, 29)        # round to nearest WITHOUT the spectral digit saving: the worst-case digit count
+    sh.L.eagle_dev_set_tune(sh.ctx, TUNE["SPECTRAL_OFF"])        # round to nearest WITHOUT the spectral digit saving: the worst-case digit count
     sh.scan()
     torch.cuda.synchronize()
-    sh.L.eagle_dev_set_tune(sh.ctx, 0)
+    sh.L.eagle_dev_set_tune(sh.ctx, TUNE["SHIPPED"])
     S_near, _, maxoff = sh.vara_i8_info()
     best_near = sh.best()[:2]
     sh.stochastic = True

@@ -2,8 +2,8 @@
 klive and lower layout, VaraIt; the walk itself is restated on the host by tests/test_scan_live_k_host.py).
 
 The kernel sums the same integer products in another order and leaves out stages that hold only zeros, so the int64 q block, vara and
-the live-stage count are compared by equality and nothing else: against the same build in the parent's order (tune 34), against the
-compiler-scheduled kernel on the untransposed-row layout (tune 9), under the paced form (tune 14), and against the integer truth of
+the live-stage count are compared by equality and nothing else: against the same build in the parent's order (VARA_UPPER), against the
+compiler-scheduled kernel on the untransposed-row layout (COMPILER_SCHEDULED), under the paced form (VARA_PACED), and against the integer truth of
 tests/exact_scan.py.  W is handed over ready-made (DeviceShard.set_W): the dense W of an exact_scan case; the same with the off-diagonals
 of the last live individuals zeroed (klive below ceil(n / 128)); its diagonal alone (klive = 0: every tile on the two-stage floor); and a
 single off-diagonal entry at (0, n-1).  n -> n_pad: 120 -> 256 (one tile, pad >= 128: the floor binds), 130 -> 256 (pad < 128), 300 -> 512
@@ -19,12 +19,14 @@ import pytest
 
 import exact_lastdigit as xl
 import exact_scan as ex
+from eagleeverything_amd._lib import TUNE
 
 pytestmark = pytest.mark.gpu
 L = 1003
 SHAPES = [120, 130, 300, 600, 700, 1003]
 DESIGNS = ("dense", "tail0", "diag", "corner")
 POISON = 0xA5
+SHIPPED, UPPER, COMPILER, PACED = TUNE["SHIPPED"], TUNE["VARA_UPPER"], TUNE["COMPILER_SCHEDULED"], TUNE["VARA_PACED"]
 
 
 @functools.lru_cache(maxsize=None)
@@ -99,22 +101,22 @@ def test_lower_walk_is_the_upper_walk_and_the_integer_truth(n, S):
             case, a, vara, klive = _designed(n, S, design)
             sh.set_W(np.ldexp(case["X"].astype(np.float64), case["log2u"]), case["ahat"])
             sh.scan_operands()
-            out = {t: _kernel(torch, sh, t, S) for t in (0, 34, 9, 14)}
+            out = {t: _kernel(torch, sh, t, S) for t in (SHIPPED, UPPER, COMPILER, PACED)}
             what = "n=%d S=%d %s" % (n, S, design)
-            q0, v0, a0, kl, S_used, e = out[0]
+            q0, v0, a0, kl, S_used, e = out[SHIPPED]
             print(what, "klive", kl, "of", sh.np_ // 128, "S used", S_used, "e", e)
             assert kl == klive, (what, kl, klive)
             assert S_used == (S if klive else 1)
             assert design == "diag" or int(q0.abs().max()) > 0
-            for t in (34, 9, 14):
-                _assert_same(torch, out[t], out[0], "%s, tune %d against the default" % (what, t))
+            for t in (UPPER, COMPILER, PACED):
+                _assert_same(torch, out[t], out[SHIPPED], "%s, tune %d against the default" % (what, t))
             # the truth applies where the S digits hold W exactly: the unit of the last digit at or below the step 2 u of the folded entries
             assert klive == 0 or 2.0 ** (e + 2 - 8 * S_used) <= 2.0 * 2.0 ** case["log2u"], (what, e, S_used)
             np.testing.assert_array_equal(a0.cpu().numpy(), a, err_msg=what)
             bad = np.flatnonzero(v0.cpu().numpy() != vara)
             assert bad.size == 0, "%s: vara of %d markers, first %d: %r, truth %r" % (what, bad.size, bad[0], float(v0[bad[0]]), vara[bad[0]])
     finally:
-        _tune(sh, 0)
+        _tune(sh, SHIPPED)
 
 
 def test_extension_launch_reads_the_workspace_count():
@@ -139,20 +141,20 @@ def test_extension_launch_reads_the_workspace_count():
         klive = _klive(np.triu(sh.Wu.cpu().numpy(), 1))
         assert klive == 3 and sh.np_ == 512
         sh.extend = False
-        raw = _kernel(torch, sh, 0, xl.SMAX)
+        raw = _kernel(torch, sh, SHIPPED, xl.SMAX)
         assert raw[4] == S_wc - 1 and sh.last_specH > 0.0
         sh.extend = True
-        out = {t: _kernel(torch, sh, t, xl.SMAX) for t in (0, 34, 9)}
-        for t in (34, 9):
-            _assert_same(torch, out[t], out[0], "extension, tune %d against the default" % t)
-        assert out[0][3] == klive
-        v_raw, v_ext = raw[1].cpu().numpy(), out[0][1].cpu().numpy()
+        out = {t: _kernel(torch, sh, t, xl.SMAX) for t in (SHIPPED, UPPER, COMPILER)}
+        for t in (UPPER, COMPILER):
+            _assert_same(torch, out[t], out[SHIPPED], "extension, tune %d against the default" % t)
+        assert out[SHIPPED][3] == klive
+        v_raw, v_ext = raw[1].cpu().numpy(), out[SHIPPED][1].cpu().numpy()
         changed = v_ext != v_raw
         assert 1 <= changed.sum() <= 64
         np.testing.assert_array_equal(v_ext[changed], vara[changed])
     finally:
         os.environ.pop("EAGLE_HIP_EXT_CAP")
-        _tune(sh, 0)
+        _tune(sh, SHIPPED)
         sh.L.eagle_dev_set_spectral(sh.ctx, 1)
         sh.ws = None
 
@@ -169,7 +171,7 @@ def test_second_block_of_a_streamed_scan_keeps_the_count():
     sh.mode, sh.nslices, sh.packed = 1, S, False
     sh.set_W(np.ldexp(case["X"].astype(np.float64), case["log2u"]), case["ahat"])
     sh.scan_operands()
-    q_res, v_res, _, kl_res, _, _ = _kernel(torch, sh, 0, S)
+    q_res, v_res, _, kl_res, _, _ = _kernel(torch, sh, SHIPPED, S)
     assert kl_res == klive == 5 and sh.Lp == 2 * Lb
     Ms, cs = sh.shifted_image()
     part = sh.L.eagle_dev_vara_i8_prepare_part

@@ -11,6 +11,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from eagleeverything_amd._lib import TUNE
+
 from exact_lastdigit import host_decision as _host_decision   # the digit rule restated on the host, stated once
 
 pytestmark = pytest.mark.gpu
@@ -56,10 +58,10 @@ def test_one_digit_fewer_under_a_rigorous_spectral_bound():
     v64 = sh.vara[:L].cpu().numpy().copy()
     best64 = sh.best()[:2]
     sh.mode = 1
-    sh.L.eagle_dev_set_tune(sh.ctx, 29)            # the saving switched off: the worst-case digit count
+    sh.L.eagle_dev_set_tune(sh.ctx, TUNE["SPECTRAL_OFF"])            # the saving switched off: the worst-case digit count
     sh.scan()
     torch.cuda.synchronize()
-    sh.L.eagle_dev_set_tune(sh.ctx, 0)
+    sh.L.eagle_dev_set_tune(sh.ctx, TUNE["SHIPPED"])
     S_wc = sh.vara_i8_info()[0]
     assert sh.last_specH == 0.0 and sh.last_sliced == S_wc
     v_wc = sh.vara[:L].cpu().numpy().copy()
@@ -246,10 +248,10 @@ def test_markers_outside_the_spectral_bound_get_the_dropped_digit_back():
     best64 = sh.best()[:2]
     sh.mode = 1
     sh.certified = False
-    sh.L.eagle_dev_set_tune(sh.ctx, 29)
+    sh.L.eagle_dev_set_tune(sh.ctx, TUNE["SPECTRAL_OFF"])
     sh.scan()
     torch.cuda.synchronize()
-    sh.L.eagle_dev_set_tune(sh.ctx, 0)
+    sh.L.eagle_dev_set_tune(sh.ctx, TUNE["SHIPPED"])
     S_wc = sh.vara_i8_info()[0]
     v_all_digits = sh.vara[:L].cpu().numpy().copy()
     sh.extend = False

@@ -10,6 +10,8 @@ import os
 import numpy as np
 import pytest
 
+from eagleeverything_amd._lib import TUNE
+
 pytestmark = pytest.mark.gpu
 
 
@@ -65,22 +67,22 @@ def test_int8_w_is_within_its_bound_and_does_not_depend_on_engine_or_panels():
         assert abs(info["mean_diag"] - float(torch.diagonal(W64)[:sh.n].abs().mean())) <= 1e-9 * info["mean_diag"]
         assert torch.count_nonzero(torch.tril(W8, -1)) == 0              # folded: nothing below the diagonal
         # the same bits from the compiler-scheduled 256 x 256 engine, and with the products cut into row panels
-        sh.L.eagle_dev_set_tune(sh.ctx, 31)
+        sh.L.eagle_dev_set_tune(sh.ctx, TUNE["W8_UNPIPED"])
         sh.scan_operands()
         torch.cuda.synchronize()
         assert torch.equal(sh.Wu, W8)
-        sh.L.eagle_dev_set_tune(sh.ctx, 0)
+        sh.L.eagle_dev_set_tune(sh.ctx, TUNE["SHIPPED"])
         os.environ["EAGLE_HIP_W8_LEVEL_MB"] = "24"                      # 1536^2 x 4 bytes = 9.4 MB per level image: two row panels and more
         sh.scan_operands()
         torch.cuda.synchronize()
         assert torch.equal(sh.Wu, W8)
-        sh.L.eagle_dev_set_tune(sh.ctx, 31)
+        sh.L.eagle_dev_set_tune(sh.ctx, TUNE["W8_UNPIPED"])
         sh.scan_operands()
         torch.cuda.synchronize()
         assert torch.equal(sh.Wu, W8)
     finally:
         os.environ.pop("EAGLE_HIP_W8_LEVEL_MB", None)
-        sh.L.eagle_dev_set_tune(sh.ctx, 0)
+        sh.L.eagle_dev_set_tune(sh.ctx, TUNE["SHIPPED"])
 
 
 def test_scan_on_the_int8_w_returns_the_fp64_scan():

@@ -20,6 +20,8 @@ import os
 import numpy as np
 import pytest
 
+from eagleeverything_amd._lib import TUNE
+
 import exact_w8 as ex
 
 pytestmark = pytest.mark.gpu
@@ -129,7 +131,7 @@ def test_int8_w_is_the_integer_truth_on_both_engines_and_in_row_panels(n, kind, 
     what = "n=%d %s" % (n, kind)
     try:
         info = _int8_products(torch, sh, both, what + " 384 x 256 engine")
-        sh.L.eagle_dev_set_tune(sh.ctx, 31)
+        sh.L.eagle_dev_set_tune(sh.ctx, TUNE["W8_UNPIPED"])
         _int8_products(torch, sh, both, what + " 256 x 256 engine")
         if n in PANELS:   # room for the level images of two row tiles: at least two row panels in both products, on either engine
             groups = max(_level_groups(info["k1"], info["T1"], sh.np_), _level_groups(info["k2"], info["T2"], sh.np_))
@@ -138,11 +140,11 @@ def test_int8_w_is_the_integer_truth_on_both_engines_and_in_row_panels(n, kind, 
             for k, T in ((info["k1"], info["T1"]), (info["k2"], info["T2"])):
                 assert _row_panels(k, T, sh.np_, mb) >= 2, (k, T, mb)
             _int8_products(torch, sh, both, what + " 256 x 256 engine, row panels")
-            sh.L.eagle_dev_set_tune(sh.ctx, 0)
+            sh.L.eagle_dev_set_tune(sh.ctx, TUNE["SHIPPED"])
             _int8_products(torch, sh, both, what + " 384 x 256 engine, row panels")
     finally:
         os.environ.pop("EAGLE_HIP_W8_LEVEL_MB", None)
-        sh.L.eagle_dev_set_tune(sh.ctx, 0)
+        sh.L.eagle_dev_set_tune(sh.ctx, TUNE["SHIPPED"])
         sh.L.eagle_dev_set_spectral(sh.ctx, 1)
 
 

@@ -11,6 +11,8 @@ import os
 import numpy as np
 import pytest
 
+from eagleeverything_amd._lib import TUNE
+
 pytestmark = pytest.mark.gpu
 
 L_MARKERS = 1024
@@ -172,15 +174,15 @@ def test_one_pass_over_a_row_writes_what_the_two_kernels_write(n, n_pad):
     try:
         for M, asym in ((sh.Sa, 1), (sh.Va, 1), (X, 0)):
             for cuts in blocks:
-                sh.L.eagle_dev_set_tune(sh.ctx, 32)      # the two-kernel form
+                sh.L.eagle_dev_set_tune(sh.ctx, TUNE["W8_ROWPASS_SPLIT"])      # the two-kernel form
                 two = _probe(torch, sh, M, cuts, asym)
-                sh.L.eagle_dev_set_tune(sh.ctx, 0)
+                sh.L.eagle_dev_set_tune(sh.ctx, TUNE["SHIPPED"])
                 one = _probe(torch, sh, M, cuts, asym)
                 for k in two:
                     assert torch.equal(one[k], two[k]), (k, cuts, asym)
                 assert int(two["e"].min()) > -99 and float(two["vec3"][1].max()) > 0.0 and int(two["slices"][0].abs().max()) > 0
     finally:
-        sh.L.eagle_dev_set_tune(sh.ctx, 0)
+        sh.L.eagle_dev_set_tune(sh.ctx, TUNE["SHIPPED"])
 
 
 @pytest.mark.parametrize("devices", [0, (0, 0)])

@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""GPU A/B of k_vara_i8 variants (tune switch) on one resident shard, interleaved rounds in one process."""
+"""GPU A/B of the forms of the digit-slice scan kernel (names of _lib.TUNE in VARIANTS) on one resident shard, interleaved rounds in one
+process.  SHIPPED = the 384 x 256 tile with the asm-pipelined k-step, COMPILER_SCHEDULED = the same tile scheduled by hipcc, VARA_256 = the
+256 x 256 tile, VARA_PACED = the XCD's workers paced by a soft barrier per column-tile pair, VARA_UPPER = the upper image."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -10,7 +12,7 @@ from eagleeverything_amd.sharded import DeviceShard
 
 n, L = int(os.environ.get("N", 5000)), int(os.environ.get("LM", 131072))
 S = int(os.environ.get("SLICES", 5))
-variants = [int(v) for v in os.environ.get("VARIANTS", "0,9,8").split(",")]  # 0 = shipped (384 x 256 tile, asm-pipelined k-step), 9 = the same tile scheduled by hipcc, 8 = the 256 x 256 tile form, 7 = no cut of the last round, 14 = the XCD's workers paced by a soft barrier per column-tile pair (k_vara_i8p<true>, round-3 experiment)
+variants = os.environ.get("VARIANTS", "SHIPPED,COMPILER_SCHEDULED,VARA_256").split(",")
 lib = _lib.load()
 sh = DeviceShard(n, L)
 sh.fill_synthetic()
@@ -25,15 +27,15 @@ ref = None
 res = {v: [] for v in variants}
 for rnd in range(6):
     for v in variants:
-        lib.eagle_dev_set_tune(sh.ctx, v)
+        lib.eagle_dev_set_tune(sh.ctx, _lib.TUNE[v])
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         sh.vara_prepare(with_a=False)  # re-zeroes q
         e0.record(); sh.vara_kernel(); e1.record()
         torch.cuda.synchronize()
         if ref is None: ref = sh.vara.clone()
-        else: assert torch.equal(ref, sh.vara), "variant %d differs" % v
+        else: assert torch.equal(ref, sh.vara), "variant %s differs" % v
         if rnd: res[v].append(e0.elapsed_time(e1))
-lib.eagle_dev_set_tune(sh.ctx, 0)
+lib.eagle_dev_set_tune(sh.ctx, _lib.TUNE["SHIPPED"])
 print("slices used", sh.vara_i8_info())
 for v in variants:
-    ms = np.array(res[v]); print("variant %d: median %.3f ms  min %.3f ms" % (v, np.median(ms), ms.min()))
+    ms = np.array(res[v]); print("variant %s: median %.3f ms  min %.3f ms" % (v, np.median(ms), ms.min()))

@@ -8,6 +8,7 @@ sys.path.insert(0, ROOT)
 import numpy as np
 import torch
 import bench
+from eagleeverything_amd._lib import TUNE
 from eagleeverything_amd.sharded import Collectives
 
 n, L = int(os.environ.get("N", 4096)), int(os.environ.get("LM", 262144))
@@ -24,8 +25,8 @@ ev = torch.linalg.eigvalsh(MMt)
 print("top eigenvalues of MMt/max + 0.95 I:", [round(float(x), 3) for x in ev[-5:]], " median", round(float(ev[n // 2]), 3))
 run.make_operands(MMt)
 sh.mode = 1
-for tune, name in ((29, "worst-case count"), (0, "with the spectral bound")):
-    sh.L.eagle_dev_set_tune(sh.ctx, tune)
+for tune, name in (("SPECTRAL_OFF", "worst-case count"), ("SHIPPED", "with the spectral bound")):
+    sh.L.eagle_dev_set_tune(sh.ctx, TUNE[tune])
     sel, el, parts = run.timed(3, 1)
     torch.cuda.synchronize()
     S_used = sh.vara_i8_info()[0]
@@ -38,7 +39,7 @@ for tune, name in ((29, "worst-case count"), (0, "with the spectral bound")):
     print("    budget in force %.0e level %d;  W engine: int8=%d declined=%d (k,T)=(%d,%d)+(%d,%d) eta/mean|W_kk| %.2e  W %.2f ms"
           % (sh.last_budget, sh.last_level, wi["int8"], wi["declined"], wi["k1"], wi["T1"], wi["k2"], wi["T2"],
              wi["eta"] / wi["mean_diag"] if wi["mean_diag"] else 0.0, parts["w"] * 1e3))
-sh.L.eagle_dev_set_tune(sh.ctx, 0)
+sh.L.eagle_dev_set_tune(sh.ctx, TUNE["SHIPPED"])
 if sh.last_specH > 0:
     q2 = sh.l1[:L, 1].double(); l1 = sh.l1[:L, 0].double()
     v = sh.vara[:L].abs()

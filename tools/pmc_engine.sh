@@ -4,7 +4,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/pmc_engine
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-export VARIANTS=${VARIANTS:-0}
+export VARIANTS=${VARIANTS:-i8}
 rocprofv3 --kernel-include-regex "k_syrk_i8" --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum --output-format csv -d $OUT/tcc -o pmc -- python3 $ROOT/tools/bench_i8_engine.py > $OUT/tcc.log 2>&1 || tail -5 $OUT/tcc.log
 rocprofv3 --kernel-include-regex "k_syrk_i8" --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -o pmc -- python3 $ROOT/tools/bench_i8_engine.py > $OUT/fetch.log 2>&1 || tail -5 $OUT/fetch.log
 cd $ROOT

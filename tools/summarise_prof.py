@@ -38,8 +38,8 @@ def short(name):
                 return "k_gemm_f64_dma_tail"
             if "k_gemm_f64_dma" in name:
                 return "k_gemm_f64_dma"
-            if "k_gemm_f64_list" in name:
-                return "k_gemm_f64_list"
+            if "k_gemm_f64_list8" in name:
+                return "k_gemm_f64_list8"
             if "k_gemm_f64_tail" in name:
                 return "k_gemm_f64_tail"
             if "k_gemm_f64" in name:
@@ -50,10 +50,8 @@ def short(name):
                 return "k_vara_i8p<ext>"   # the launch of eagle_dev_vara_i8_extend (dropped on the device when nobody qualifies)
             if "k_vara_f64_sum" in name:
                 return "k_vara_f64_sum"
-            if "k_vara_f64d" in name:   # round 3's fp64 vara kernel (k_vara_f64 = round 2's, tune 28)
+            if "k_vara_f64d" in name:
                 return "k_vara_f64d<split>" if ("Lb1E" in name or "<true>" in name) else "k_vara_f64d"
-            if "k_vara_f64" in name:
-                return "k_vara_f64<split>" if ("Lb1E" in name or "<true>" in name) else "k_vara_f64"
             return k
     return None
 

@@ -1,5 +1,5 @@
 // What the chip sustains on v_mfma_f64_16x16x4_f64 with nothing else going on: register-resident loops, every SIMD issuing back to
-// back, random operands, ~0.2 s per case -- the ceiling the fp64 kernels of this library (k_gemm_f64_list8, k_vara_f64, k_zbuild)
+// back, random operands, ~0.2 s per case -- the ceiling the fp64 kernels of this library (k_gemm_f64_list8, k_vara_f64d, k_zbuild)
 // are to be measured against (the data sheet says 78.6 TFLOP/s = 128 flop/clk/CU at 2.4 GHz).
 // Cases: waves per SIMD 1 / 2 / 4 (blocks of 256 / 512 threads, 1 or 2 per CU), accumulator tiles per wave 8 (2 x 4) or 16 (4 x 4).
 // Build: hipcc -O3 --offload-arch=gfx950 tools/ubench/f64_ceiling.hip -o tools/ubench/f64_ceiling
