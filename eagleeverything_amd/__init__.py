@@ -6,7 +6,8 @@ mirror of the reference interface used by tests, bench.py and the sharded multi-
   rcpp_api   -- ReadBlock, calculateMMt_rcpp, calculate_a_and_vara_rcpp, calculate_reduced_a_rcpp
   r_api      -- calculateMMt, calcMMt, calculate_a_and_vara, find_qtl (the R wrappers' marshalling rules); the QC chain
                 MarkerStats / FilterMarkers / LDPrune / SampleStats / Relatedness; grm_weights, grm_from_gram, GRM, PCA;
-                Score, ProjectPCA, MarkerEffects, Predict (the fitted model used on any panel with the same markers)
+                Score, ProjectPCA, MarkerEffects, Predict (the fitted model used on any panel with the same markers);
+                GWAS (per-marker mixed-model tests: the P3D score test and the exact test with delta re-estimated), lmm_host
   host_model -- dense n x n model algebra that stays on host LAPACK by design
   sharded    -- marker-sharded multi-GPU scan / MM^T (one process per GPU, torch.distributed over RCCL)
   synth      -- seeded synthetic genotypes of the benchmark shapes

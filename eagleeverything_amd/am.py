@@ -700,6 +700,103 @@ def SummaryAM_traits(results, Y, X, geno, map=None, xnames=None, availmemGb=8, e
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+# GWAS: the single-locus mixed-model scan (no counterpart in the reference, whose AM() reports the loci of ONE multi-locus model): a
+# row per marker for the Manhattan plot and the comparison the Eagle paper draws between AM()'s picks and a single-locus scan.  Two
+# tests of gamma = 0 in y = X beta + m_i gamma + g + e on the Z that SpectralBackend keeps resident: the score test under the null
+# model's variance components (EMMAX / P3D; one eagle_spectral_scan) and the exact test with delta re-estimated per marker (GEMMA /
+# FaST-LMM; eagle_spectral_lmm, include/eagle_hip.h section 1d').
+# ---------------------------------------------------------------------------------------------------------------------------
+_GWAS_EXACT = ("beta", "se", "stat", "p", "delta", "vg", "ve", "ll")
+
+
+def GWAS(trait, X, geno, exact="all", method="reml", p_exact=None, map=None, backend=None, availmemGb=8, device=0, Zmat=None):
+    """Per-marker tests of a quantitative trait under the mixed model; r_api.GWAS forwards here.
+
+    trait (n, NaN = no record), X (n x c, 1 <= c <= 14, the intercept column included), geno: as AM() takes them; rows with NaN in
+    trait or X are dropped as AM() drops them (a VIEW reshape).  backend: an am.SpectralBackend (default: a new one on `device`).  One
+    that already ran on these genotypes -- AM(trait, X, geno, backend=b) -- still holds lam, U and the resident Z: nothing is rebuilt.
+
+    Returns a dict of fp64 (L) columns unless noted:
+      "score" = a^2 / vara, "p_score" = chdtrc(1, score), "beta_p3d" = vg a / vara: the P3D test of every marker under the REML
+        null fit (emma_REMLE_eig on X alone), from one spectral_scan;
+      "beta", "se", "stat", "p", "delta", "vg", "ve", "ll", "code" (int32), "iterations" (int32): the exact test (section 1d' of the
+        header) started at the null fit's ln delta, for every marker (exact="all"), for none (exact="none") or, with p_exact, for
+        the markers with p_score < p_exact only -- the others keep NaN and code -1.  method="reml": stat = (beta / se)^2, p =
+        fdtrc(1, n - c - 1, stat) (Wald); method="ml": stat = 2 (ll - the null ML fit's ll), p = chdtrc(1, stat).  Markers whose code
+        is 2 hold NaN.  This is the optimum reached from the null fit, not emma's search over a grid;
+      "null": {"delta", "vg", "ve", "ll"} of the method's null fit (emma_REMLE_eig / emma_MLE_eig), "null_reml": the same of the REML
+        fit the P3D columns use, "lambda_gc" = median(score) / 0.4549... (the chi^2_1 median), "n_used", "indxNA" and, with map= (L
+        names or a mapping with "SNP"), "names".
+    Zmat (repeated measures) is not supported."""
+    from scipy.special import chdtrc, chdtri, fdtrc
+    from . import r_api, rcpp_api
+    if Zmat is not None:
+        raise NotImplementedError("GWAS: Zmat (repeated measures) is not supported: the exact test has no within-individual terms")
+    if exact not in ("all", "none") or method not in ("reml", "ml"):
+        raise ValueError("GWAS: exact must be \"all\" or \"none\", method \"reml\" or \"ml\"")
+    if p_exact is not None and not 0.0 < float(p_exact) <= 1.0:
+        raise ValueError("GWAS: p_exact must lie in (0, 1]")
+    backend = backend or SpectralBackend(device)
+    if not hasattr(backend, "eig"):
+        raise TypeError("GWAS: the backend must be an am.SpectralBackend (it keeps Z = Mt U resident)")
+    y = np.asarray(trait, dtype=np.float64).ravel().copy()
+    Xa = np.asarray(X, dtype=np.float64).reshape(y.size, -1)
+    c = Xa.shape[1]
+    if not 1 <= c <= rcpp_api.LMM_MAX_COVARIATES:
+        raise ValueError("GWAS: X must hold 1 to %d columns, the intercept included" % rcpp_api.LMM_MAX_COVARIATES)
+    y[np.isnan(Xa).any(axis=1)] = np.nan                                             # AM.R:320-329
+    indxNA = r_api.check_for_NA_in_trait(y)
+    (y, Xa), geno = _drop_na_rows(indxNA, (y, Xa), geno, backend=backend, device=backend.device)
+    n, L = (int(v) for v in geno["dim_of_ascii_M"])
+    if y.size != n:
+        raise ValueError("GWAS: %d trait records for %d genotyped individuals" % (y.size, n))
+    if n <= c + 2:
+        raise ValueError("GWAS: %d individuals for %d columns of X" % (n, c))
+    names = None if map is None else _summary_names(c, None, map, L)[1]
+    if backend.eig is None or backend.lam.size != n or not rcpp_api.spectral_holds(geno["asciifileMt"], backend.U, device=backend.device):
+        backend.calcMMt(geno, availmemGb, 1, np.array([np.nan]), True)                # K, its eigh and Z = Mt U
+    lam, U = backend.eig
+    lam = np.ascontiguousarray(lam, dtype=np.float64)
+    la = host_model.algebra()
+    Ut, ut = la.mm(U.T, Xa), U.T @ y
+    fit = {"reml": emma_REMLE_eig(lam, Ut, ut)}
+    fit["ml"] = emma_MLE_eig(lam, Ut, ut) if method == "ml" else None
+    null = {m: None if r is None else {"delta": r["delta"], "vg": r["vg"], "ve": r["ve"], "ll": r["REML" if m == "reml" else "ML"]}
+            for m, r in fit.items()}
+    if not null["reml"]["vg"] > 0:
+        raise ValueError("GWAS: the null model has no fit (collinear columns of X?)")
+    res = rcpp_api.spectral_scan(lam, Ut, ut, null["reml"]["ve"], null["reml"]["vg"], L, device=backend.device)
+    a, vara = res["a"].ravel(), res["vara"].ravel()
+    with np.errstate(all="ignore"):
+        score = a * a / vara
+        out = {"score": score, "p_score": chdtrc(1.0, score), "beta_p3d": null["reml"]["vg"] * a / vara}
+    for k in _GWAS_EXACT:
+        out[k] = np.full(L, np.nan)
+    out["code"], out["iterations"] = np.full(L, -1, dtype=np.int32), np.zeros(L, dtype=np.int32)
+    idx = None if p_exact is None else np.flatnonzero(out["p_score"] < float(p_exact))
+    if exact == "all" and (idx is None or idx.size):
+        stat, info = rcpp_api.spectral_lmm(lam, Ut, ut, reml=method == "reml", theta0=math.log(null[method]["delta"]), idx=idx,
+                                           n_markers=L, device=backend.device)
+        rows = slice(None) if idx is None else idx
+        for j, k in enumerate(("beta", "se", "delta", "vg", "ll")):
+            out[k][rows] = stat[:, j]
+        out["code"][rows], out["iterations"][rows] = info[:, 0], info[:, 1]
+        out["ve"] = out["delta"] * out["vg"]
+        with np.errstate(all="ignore"):
+            if method == "reml":
+                out["stat"] = (out["beta"] / out["se"]) ** 2
+                out["p"] = fdtrc(1.0, float(n - c - 1), out["stat"])
+            else:
+                out["stat"] = np.where(np.isnan(out["ll"]), np.nan, np.maximum(2.0 * (out["ll"] - null["ml"]["ll"]), 0.0))
+                out["p"] = chdtrc(1.0, out["stat"])
+    out.update({"null": null[method], "null_reml": null["reml"], "lambda_gc": float(np.nanmedian(score) / chdtri(1.0, 0.5)), "n_used": n,
+                "indxNA": indxNA, "method": method})
+    if names is not None:
+        out["names"] = [names(j) for j in range(1, L + 1)]
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
 # Using the fitted model (no counterpart in the reference, which stops at the loci): BLUPs of the marker effects from one exact
 # M^T (P y) on the device (include/eagle_hip.h section 1b''''i) and predictions for any panel with the same markers.
 # ---------------------------------------------------------------------------------------------------------------------------

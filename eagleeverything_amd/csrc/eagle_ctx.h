@@ -307,6 +307,11 @@ extern "C" int eagle_dev_fisher_2x2(eagle_ctx* ctx, const int32_t* tables, long 
 // stat[rows][4] = (gamma, se, score, loglik), info[rows][2] = (code, evaluations); firth = 0 (ML), 1 (Firth), 2 (fallback).
 extern "C" int eagle_dev_logistic(eagle_ctx* ctx, const int8_t* Mt8, long rows, long n, long ld, const double* X16, const uint8_t* valid_y,
                                   const double* beta0, int p, int firth, double tol, int max_iter, double* stat, int32_t* info, void* stream);
+// The exact mixed-model test per marker (include/eagle_hip.h section 1d').  eagle_lmm.hip: rows of Z (ldz fp64 each, ldz >= n64) against the
+// staged image B16 (n64 x 16 fp64: U^T X, a zero column for z, U^T y) and lam64 (n64, +inf from n on), n64 = n rounded up to 64; idx:
+// count device longs or NULL = rows 0 .. count - 1  ->  stat[count][5], info[count][2].
+extern "C" int eagle_dev_lmm(eagle_ctx* ctx, const double* Z, long ldz, const double* B16, const double* lam64, long n, int c, int reml,
+                             double theta0, double tol, int max_iter, const long* idx, long count, double* stat, int32_t* info, void* stream);
 // Sample QC.  eagle_qc.hip: counts[n][4] (hom A1, het, hom A2, missing per INDIVIDUAL; zeroed by the caller before a file's first
 // window) += the counts over `rows` raw .bed rows; ibs0 / hethet (n x n int32, full and symmetric) from the Gram accumulators D32, Q32
 // (n_pad x n_pad, upper 256-tiles live) and the marker count L; p[L] = the Hardy-Weinberg exact test of counts[L][stride] (stride 3

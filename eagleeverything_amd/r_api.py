@@ -2967,3 +2967,131 @@ def Logistic(geno, status, X=None, firth="fallback", tol=1e-10, max_iter=50, ava
         return {"beta": beta.copy(), "se": se.copy(), "or": np.exp(beta), "z": z, "p": 2.0 * special.ndtr(-np.abs(z)), "score": score.copy(),
                 "p_score": special.chdtrc(1.0, score), "lrt": lrt, "p_lrt": special.chdtrc(1.0, np.maximum(lrt, 0.0)),
                 "code": info[:, 0].copy(), "iterations": info[:, 1].copy(), "firth": is_firth, "n_used": int(used.sum()), "beta0": b0}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The exact per-marker mixed-model test (include/eagle_hip.h section 1d'; device: rcpp_api.spectral_lmm, am.GWAS).
+# ---------------------------------------------------------------------------------------------------------------------------
+LMM_THETA_MIN, LMM_THETA_MAX, LMM_STEP_MAX, LMM_PIVOT_REL = -10.0, 10.0, 2.0, 2.0 ** -40
+
+
+def _lmm_eval(lam, B, n, reml, theta):
+    """One evaluation of section 1d' at theta for B = [U^T X | z | U^T y] (n x (p + 1)) -> None (singular) or dict(g, gp, R, gamma,
+    ipp = (A_1^-1)_pp, L = the Cholesky factor of A_1, delta)."""
+    p = B.shape[1] - 1
+    delta = math.exp(theta)
+    w = 1.0 / (lam + delta)
+    w2 = w * w
+    w3 = w2 * w
+    S1, S2, S3 = B.T @ (w[:, None] * B), B.T @ (w2[:, None] * B), B.T @ (w3[:, None] * B)
+    Lm = _logit_chol(S1[:p, :p])                                                      # the pivot rule, LMM_PIVOT_REL = 2^-40
+    if Lm is None:
+        return None
+    b1, b2, b3 = S1[:p, p], S2[:p, p], S3[:p, p]
+    beta = _logit_solve(Lm, b1)
+    R = S1[p, p] - b1 @ beta
+    if not (R > S1[p, p] * LMM_PIVOT_REL) or not (R < np.inf):
+        return None
+    a2, a3 = S2[:p, :p] @ beta, S3[:p, :p] @ beta
+    Q = S2[p, p] + beta @ (a2 - 2.0 * b2)
+    W3 = S3[p, p] + beta @ (a3 - 2.0 * b3)
+    u = b2 - a2
+    C = W3 - u @ _logit_solve(Lm, u)
+    Inv = _logit_solve(Lm, np.eye(p))
+    if reml:
+        M = Inv @ S2[:p, :p]
+        m, T, T2 = n - p, w.sum() - np.sum(Inv * S2[:p, :p]), w2.sum() - 2.0 * np.sum(Inv * S3[:p, :p]) + np.sum(M * M.T)
+    else:
+        m, T, T2 = n, w.sum(), w2.sum()
+    qr = Q / R
+    g = delta * 0.5 * (m * qr - T)
+    gp = g + delta * delta * 0.5 * (m * (qr * qr - 2.0 * C / R) + T2)
+    if not (np.isfinite(g) and np.isfinite(gp)):
+        return None
+    return {"g": float(g), "gp": float(gp), "R": float(R), "gamma": float(beta[p - 1]), "ipp": float(Inv[p - 1, p - 1]), "L": Lm, "delta": delta}
+
+
+def _lmm_fit(lam, B, reml, theta0, tol, max_iter):
+    """The iteration of section 1d' for one marker -> (gamma, se, delta, vg, ll, code, iterations)."""
+    n, p = B.shape[0], B.shape[1] - 1
+    nan = float("nan")
+    theta, lo, hi, have_lo, have_hi, it = float(theta0), LMM_THETA_MIN, LMM_THETA_MAX, False, False, 0
+    with np.errstate(all="ignore"):
+        while True:
+            E = _lmm_eval(lam, B, n, reml, theta)
+            if E is None:
+                return nan, nan, nan, nan, nan, 2, it
+            g, gp = E["g"], E["gp"]
+            if g > 0.0:
+                lo, have_lo = theta, True
+            if g < 0.0:
+                hi, have_hi = theta, True
+            if g > 0.0 and theta >= LMM_THETA_MAX:
+                code = 4
+                break
+            if g < 0.0 and theta <= LMM_THETA_MIN:
+                code = 3
+                break
+            t = theta - g / gp if gp != 0.0 else nan
+            if not (gp < 0.0 and lo < t < hi and abs(t - theta) <= LMM_STEP_MAX):
+                if (g > 0.0 and have_hi) or (g < 0.0 and have_lo):
+                    t = 0.5 * (lo + hi)
+                elif g > 0.0:
+                    t = min(theta + LMM_STEP_MAX, LMM_THETA_MAX)
+                elif g < 0.0:
+                    t = max(theta - LMM_STEP_MAX, LMM_THETA_MIN)
+                else:
+                    t = theta
+            if abs(t - theta) <= tol:
+                code = 0
+                break
+            if it >= max_iter:
+                code = 1
+                break
+            theta = t
+            it += 1
+        m = n - p if reml else n
+        vg = E["R"] / m
+        ll = m * (math.log(m / (2.0 * math.pi)) - 1.0 - math.log(E["R"])) - float(np.sum(np.log(lam + E["delta"])))
+        if reml:
+            ll -= 2.0 * float(np.sum(np.log(np.diag(E["L"]))))
+        return E["gamma"], math.sqrt(vg * E["ipp"]), E["delta"], vg, 0.5 * ll, code, it
+
+
+def lmm_host(lam, UtX, Uty, Zrows, reml=True, theta0=None, tol=1e-10, max_iter=50):
+    """rcpp_api.spectral_lmm restated in numpy, marker by marker, by the rule of include/eagle_hip.h section 1d': lam (n) the
+    eigenvalues of K, UtX = U^T X (n x c, the intercept column included), Uty = U^T y, Zrows (L x n): row i = U^T m_i, what
+    spectral_rows returns transposed -> (stat (L, 5) = gamma, se, delta, vg, ll; info (L, 2) = code, iterations).  theta0: ln delta of
+    the null fit; None: emma_REMLE_eig (reml) / emma_MLE_eig on X alone.  Not bit-equal to the device (exp, log and the order of the
+    sums differ); tests/lmm_truth.py holds both to 40-digit roots."""
+    lam = np.asarray(lam, dtype=np.float64).ravel()
+    n = lam.size
+    Ut = np.asarray(UtX, dtype=np.float64).reshape(n, -1)
+    ut = np.asarray(Uty, dtype=np.float64).ravel()
+    Zr = np.asarray(Zrows, dtype=np.float64).reshape(-1, n)
+    c = Ut.shape[1]
+    if not 1 <= c <= 14 or ut.size != n or n <= c + 2:
+        raise ValueError("lmm_host: UtX must be (n, c) with 1 <= c <= 14 and n > c + 2, Uty of length n")
+    if not (0.0 < tol < 1.0) or not 0 <= int(max_iter) <= 1000:
+        raise ValueError("lmm_host: tol in (0, 1) and max_iter in [0, 1000]")
+    if theta0 is None:
+        from . import am
+        theta0 = math.log((am.emma_REMLE_eig if reml else am.emma_MLE_eig)(lam, Ut, ut)["delta"])
+    theta0 = min(max(float(theta0), LMM_THETA_MIN), LMM_THETA_MAX)
+    stat, info = np.full((Zr.shape[0], 5), np.nan), np.zeros((Zr.shape[0], 2), dtype=np.int32)
+    for i in range(Zr.shape[0]):
+        r = _lmm_fit(lam, np.column_stack([Ut, Zr[i], ut]), bool(reml), theta0, tol, int(max_iter))
+        stat[i], info[i] = r[:5], r[5:]
+    return stat, info
+
+
+def GWAS(trait, X, geno, exact="all", method="reml", p_exact=None, map=None, backend=None, availmemGb=8, device=0, Zmat=None):
+    """The single-locus mixed-model scan of a quantitative trait, y = X beta + m_i gamma + g + e for every marker i (am.GWAS): the P3D /
+    EMMAX score test of every marker from one pass over the resident Z ("score", "p_score", "beta_p3d") and the exact test with delta
+    re-estimated per marker on the device (include/eagle_hip.h section 1d': "beta", "se", "stat", "p", "delta", "vg", "ve", "ll", "code",
+    "iterations") for every marker (exact="all"), none (exact="none") or those with p_score < p_exact.  method="reml": Wald F test;
+    "ml": likelihood-ratio test.  Also "null" (delta, vg, ve, ll), "lambda_gc", "n_used", "indxNA" and with map= "names".  backend: an
+    am.SpectralBackend; one that AM() already ran on these genotypes is reused, nothing is rebuilt."""
+    from . import am
+    return am.GWAS(trait, X, geno, exact=exact, method=method, p_exact=p_exact, map=map, backend=backend, availmemGb=availmemGb,
+                   device=device, Zmat=Zmat)

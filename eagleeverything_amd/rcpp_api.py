@@ -353,6 +353,44 @@ def spectral_rows(idx, device=0):
     return out
 
 
+LMM_MAX_COVARIATES = 14
+
+
+def spectral_lmm(lam, UtX, Uty, reml=True, theta0=0.0, tol=1e-10, max_iter=50, idx=None, n_markers=None, device=0):
+    """eagle_spectral_lmm: the exact mixed-model test of include/eagle_hip.h section 1d' on the resident Z -> (stat (k, 5) = gamma, se,
+    delta, vg, ll; info (k, 2) = code, iterations).  lam (n), UtX (n x c, 1 <= c <= 14, the intercept column included), Uty (n);
+    theta0 = ln delta of the null fit.  idx: 0-based markers, the outputs in list order; None: all n_markers markers of the prepare."""
+    lam = _f64F(np.ravel(lam))
+    n = lam.size
+    UtX = np.asarray(UtX, dtype=np.float64)
+    if UtX.ndim == 1:
+        UtX = UtX[:, None]
+    Uty = _f64F(np.ravel(Uty))
+    if UtX.ndim != 2 or UtX.shape[0] != n or not 1 <= UtX.shape[1] <= LMM_MAX_COVARIATES or Uty.size != n:
+        raise ValueError("spectral_lmm: lam, Uty of length n and UtX (n, c) with 1 <= c <= %d" % LMM_MAX_COVARIATES)
+    if not (np.all(np.isfinite(lam)) and np.all(np.isfinite(UtX)) and np.all(np.isfinite(Uty))):
+        raise ValueError("spectral_lmm: a non-finite operand")
+    if not (0.0 < float(tol) < 1.0) or int(max_iter) != max_iter or not 0 <= int(max_iter) <= 1000 or not np.isfinite(float(theta0)):
+        raise ValueError("spectral_lmm: tol in (0, 1), max_iter an integer in [0, 1000], theta0 finite")
+    if idx is None:
+        if n_markers is None or int(n_markers) < 1:
+            raise ValueError("spectral_lmm: n_markers (the markers of the prepare) is needed without idx")
+        iv, k, ip = None, int(n_markers), None
+    else:
+        iv = np.ascontiguousarray(np.atleast_1d(idx), dtype=np.int64)
+        if iv.ndim != 1 or (iv.size and iv.min() < 0):
+            raise ValueError("spectral_lmm: idx must be a list of 0-based markers")
+        k, ip = iv.size, iv.ctypes.data_as(c_lp)
+    UtX = _f64F(UtX)
+    L = _lib.load()
+    ctx = context(device)
+    stat = np.full((max(k, 1), 5), np.nan)
+    info = np.zeros((max(k, 1), 2), dtype=np.int32)
+    _check(ctx, L.eagle_spectral_lmm(ctx, _dp(lam), _dp(UtX), _dp(Uty), UtX.shape[1], int(bool(reml)), float(theta0), float(tol), int(max_iter),
+                                     ip, k, _dp(stat), info.ctypes.data_as(C.POINTER(C.c_int32))))
+    return stat[:k], info[:k]
+
+
 def calculate_reduced_a_rcpp(f_name_ascii, varG, P, y, max_memory_in_Gbytes, dims, selected_loci, quiet=True,
                              message=None, device=0):
     L = _lib.load()

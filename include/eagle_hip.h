@@ -1183,6 +1183,66 @@ int eagle_spectral_traits_passes(long T, const long* p);
 /* U^T m_j for k markers (0-based idx): the rows of the resident Z, n x k column-major -- the U^T X column a pick adds. */
 int eagle_spectral_rows(eagle_ctx* ctx, const long* idx, long k, double* out);
 
+/* ---------------------------------------------------------------------------------------------
+ * 1d'. The exact per-marker mixed-model test (no counterpart in the reference, which reports the loci its multi-locus model picks):
+ *     for every marker i the fit of  y = X beta + m_i gamma + g + e,  g ~ N(0, sg2 K), e ~ N(0, se2 I),  with delta = se2 / sg2
+ *     RE-ESTIMATED for that marker, as GEMMA and FaST-LMM do -- not the score statistic a^2 / vara of eagle_spectral_scan, which keeps
+ *     the null model's variance components (EMMAX / P3D).  csrc/eagle_lmm.hip, k_lmm_exact; restated in numpy by r_api.lmm_host.
+ *
+ *     Notation.  K = U diag(lambda) U^T is the kinship AM() uses; yt = U^T y, Xt = U^T X, X n x c WITH the intercept column,
+ *     1 <= c <= 14; z = row i of the resident Z (U^T m_i); D = [Xt z], p = c + 1; B = [D yt], c + 2 <= 16 columns;
+ *     w_k(delta) = 1 / (lambda_k + delta);  S_r(delta) = B^T W^r B for r = 1, 2, 3, with blocks A_r (p x p), b_r (p), y_r.
+ *
+ *     One evaluation at theta = ln delta, in this order:
+ *       delta = e^theta; w_k, S_1, S_2, S_3 and s_r = sum_k w_k^r;
+ *       the Cholesky factor of A_1, a pivot tested against LMM_PIVOT_REL times its diagonal entry of A_1;
+ *       beta = A_1^-1 b_1;  R = y_1 - b_1^T beta  (= yt^T P yt), tested against LMM_PIVOT_REL y_1 like a pivot;
+ *       Q = y_2 - 2 beta^T b_2 + beta^T A_2 beta  (= yt^T P^2 yt);
+ *       C = y_3 - 2 beta^T b_3 + beta^T A_3 beta - u^T A_1^-1 u,  u = b_2 - A_2 beta  (= yt^T P^3 yt: with r = yt - D beta,
+ *           r^T W^3 r - (D^T W^2 r)^T A_1^-1 (D^T W^2 r));
+ *       REML:  m = n - p,  T = s_1 - tr(A_1^-1 A_2)  (= tr P),  T2 = s_2 - 2 tr(A_1^-1 A_3) + tr((A_1^-1 A_2)^2)  (= tr P^2);
+ *       ML:    m = n,      T = s_1,                          T2 = s_2;
+ *       l'(delta) = 1/2 [m Q / R - T],   l''(delta) = 1/2 [m (Q^2 / R^2 - 2 C / R) + T2];
+ *       g(theta) = delta l',   g'(theta) = delta l' + delta^2 l''.
+ *     The likelihoods these differentiate:  REML  l = 1/2 [(n - p)(log((n - p) / 2 pi) - 1 - log R) + sum log w - log det A_1],
+ *     ML  l = 1/2 [n (log(n / 2 pi) - 1 - log R) + sum log w].  The log terms enter no g: they are formed once, for the reported l.
+ *
+ *     The iteration seeks the root of g.  theta starts at theta0 = ln delta of the null fit (X alone), clipped to [LMM_THETA_MIN,
+ *     LMM_THETA_MAX] = [-10, 10] (emma.py's llim, ulim); lo = LMM_THETA_MIN and hi = LMM_THETA_MAX, neither evaluated yet.  Then:
+ *       1. evaluate g, g' at theta.  g > 0: lo = theta, an evaluated point; g < 0: hi = theta, an evaluated point;
+ *       2. g > 0 at theta = LMM_THETA_MAX: stop, code 4;  g < 0 at theta = LMM_THETA_MIN: stop, code 3  (a limit at which g still
+ *          points outward is a boundary optimum);
+ *       3. the proposal t: Newton's theta - g / g' when g' < 0, lo < t < hi and |t - theta| <= LMM_STEP_MAX; otherwise (lo + hi) / 2
+ *          when the end on the other side of theta is an evaluated point (one of opposite sign exists); otherwise theta + sign(g)
+ *          LMM_STEP_MAX clipped to the limit (g = 0: t = theta);
+ *       4. |t - theta| <= tol: stop, code 0;  `iterations` = max_iter: stop, code 1;  else theta = t, iterations += 1, back to 1.
+ *     So a call makes iterations + 1 evaluations and max_iter = 0 returns the values at theta0.  Every stop but code 2 reports the
+ *     LAST EVALUATED theta:  gamma = beta_p,  sg2 = R / m,  se2 = delta sg2,  se = sqrt(sg2 (A_1^-1)_pp),  l(theta).
+ *     This is the local optimum reached from the null fit, as GEMMA's Newton stage gives it -- NOT emma.REMLE's search over a grid of
+ *     100 intervals, which compares every local optimum.
+ *
+ *     stat_out[5 o ..] = (gamma, se, delta, sg2 (vg), l), info_out[2 o ..] = (code, iterations) for output position o.  Codes:
+ *     0 converged; 1 max_iter reached; 2 singular: a Cholesky pivot of A_1 was not above LMM_PIVOT_REL of its diagonal entry (a
+ *     monomorphic marker, a marker in the span of X), or R was not above LMM_PIVOT_REL y_1, or g or g' was not finite -- the five
+ *     statistics are NaN; 3 optimum at the lower limit; 4 optimum at the upper limit.
+ *
+ *     eagle_spectral_lmm runs on the Z of the last eagle_spectral_prepare.  lambda: n; UtX: n x c column-major; Uty: n; reml: 1 = REML,
+ *     0 = ML.  idx == NULL: every marker, in order (nidx is not read); else idx holds nidx 0-based markers and the outputs are in list
+ *     order.  A marker's result depends on its row of Z, the operands and theta0 alone: the same bits for all markers, for an index list
+ *     and in any order.  Bit equality with the host restatement is not claimed.  The reduction over the n eigen-directions runs on
+ *     v_mfma_f64_16x16x4_f64 (three instructions per four directions and evaluation), one wave per marker.  Argument errors
+ *     (EAGLE_ERR_ARG with a message; decided before the context is used, with ctx == NULL their text is in eagle_open_error()): a NULL
+ *     pointer, c outside [1, 14], reml outside {0, 1}, theta0 not finite, tol not in (0, 1), max_iter outside [0, 1000], nidx < 0;
+ *     then: no context, a multi-device context (single device only), no eagle_spectral_prepare, n <= c + 2, a marker index out of
+ *     range, lambda_k + e^-10 <= 0 or not finite, a non-finite entry of UtX or Uty.
+ * ------------------------------------------------------------------------------------------- */
+#define LMM_THETA_MIN (-10.0)
+#define LMM_THETA_MAX 10.0
+#define LMM_STEP_MAX 2.0        /* the longest step in theta = ln delta: delta changes by a factor of at most e^2 per evaluation */
+#define LMM_PIVOT_REL 0x1p-40   /* a Cholesky pivot must exceed this fraction of its diagonal entry of A_1 */
+int eagle_spectral_lmm(eagle_ctx* ctx, const double* lambda, const double* UtX, const double* Uty, int c, int reml, double theta0, double tol,
+                       int max_iter, const long* idx, long nidx, double* stat_out, int32_t* info_out);
+
 /* Replaces the R tail of .find_qtl:  tsq <- a^2/vara ; which(tsq == max(tsq, na.rm=TRUE))[1]
  *                                                E/R/find_qtl.R:71-83
  * Evaluated on the device on the a / vara of the LAST eagle_calculate_a_and_vara call of this ctx (still in
