@@ -557,6 +557,32 @@ struct ChunkRing {
     }
 };
 
+// One pass over the Lr markers of a shard that starts at marker m0 of the file: ONE block of the resident image g (ring NULL; Lc is
+// then the shard's padded length), or blocks of Lc markers read back from the file through `ring`, whose two buffers hold Lc rows of
+// np bytes each.  load() yields the block; the caller launches its kernels on ctx->stream -- on as many padded rows as IT works (the
+// scan's main pass: full chunks of Lc; everybody else: eagle_pad(nr)) -- and calls computed(); finish() after the last block of a
+// pass that went through.
+struct MarkerBlock { const int8_t* image; long ld, r0, nr; };
+struct MarkerBlocks {
+    const char* path; long m0, Lr, n, np, Lc; double mem_gb;
+    const GenoEntry* g;
+    ChunkRing* ring;
+    bool full_chunks;     // streamed: a buffer is cleared as a full chunk of Lc rows before its load (else eagle_pad(nr) rows)
+    long r0 = 0;
+    bool more() const { return r0 < Lr; }
+    int slot() const { return ring ? (int)(ring->k & 1) : 0; }   // of the two ring buffers, the one the block loaded last lies in
+    int load(eagle_ctx* ctx, MarkerBlock* b) {
+        const long nr = std::min(Lc, Lr - r0);
+        if (!ring) { *b = {g->dev, g->ld, r0, nr}; return EAGLE_OK; }
+        int8_t* tile = nullptr;
+        const int rc = ring->load(ctx, path, m0 + r0, nr, 0, n, np, (size_t)(full_chunks ? Lc : eagle_pad(nr)) * np, mem_gb, host_threads(), &tile);
+        *b = {tile, np, r0, nr};
+        return rc;
+    }
+    int computed(eagle_ctx* ctx) { r0 += Lc; return ring ? ring->computed(ctx) : EAGLE_OK; }
+    void finish(eagle_ctx* ctx) { if (ring) ring->finish(ctx); }
+};
+
 // Phase clock of one scan call: HIP events on the compute stream, read after the call's final synchronisation
 // (eagle_last_scan_timing).  The interval that ENDS at an event is booked under the event's tag.
 enum { PH_START = 0, PH_UPLOAD, PH_W, PH_LOADWAIT, PH_PREPARE, PH_VARA, PH_CERT, PH_D2H, PH_COUNT };
@@ -1213,11 +1239,11 @@ void SCache::release() {   // (eagle_close)
     if (h_flag) (void)hipHostFree(h_flag);
 }
 
-// what scan_range's setup reserves for a resident scan of Lr markers on n individuals (the same terms)
+// what scan_setup reserves for a resident scan of Lr markers on n individuals (the same terms)
 static size_t scan_arena_bytes(eagle_ctx* ctx, long n, long Lr) {
     const long np = eagle_pad(n), Lp = eagle_pad(Lr > 0 ? Lr : 1);
     const size_t sq = sizeof(double) * (size_t)np * np;
-    const bool use_i8 = ctx->scan_mode == 1 && 64.0 * 512.0 * (double)np < 2147483648.0;
+    const bool use_i8 = scan_use_i8(ctx->scan_mode, np);
     const int nslices = ctx->scan_slices | (ctx->scan_stochastic ? EAGLE_SLICES_STOCHASTIC : 0);
     const size_t wsb = use_i8 ? (size_t)eagle_vara_i8_workspace_bytes(np, Lp, nslices) : 0;
     const size_t certb = use_i8 ? (size_t)eagle_scan_certify_workspace_bytes(np) : 0;
@@ -1252,420 +1278,489 @@ static int ensure_scan_out(eagle_ctx* ctx, long L_pad) {
     return EAGLE_OK;
 }
 
-// The scan of the markers [m0, m1) of Mt.ascii on ctx's device: a, vara into ctx->d_a / d_vara (and the host ranges
-// a_out[m0..m1), vara_out[m0..m1)).  k of nd devices; rv / rccl: the meeting point and the communicators of a multi-device call
-// (NULL for one device).  Every device passes the same rendezvous in the same order, failed or not.
-// This is ONE attempt (scan_range, below, makes at most two).  pol: the switches of the cached S as read for this call; *redo: S_NOTHING,
-// or how the verification settled at the END of the scan found another S than the one it ran on.
-static int scan_once(eagle_ctx* ctx, const char* f_name_ascii, long L, long n, long m0, long m1, const std::vector<long>& sel,
-                     const double* inv_MMt_sqrt, const double* dim_reduced_vara, const double* a, double max_memory_in_Gbytes, int quiet,
-                     double* a_out, double* vara_out, int k, int nd, Rendezvous* rv, RcclState* rccl, bool w_direct, bool s_trusted,
-                     const SPolicy& pol, SOutcome* redo) {
-    // s_trusted: the device copy of S was uploaded from this very caller matrix a moment ago (the second attempt after a deferred
-    // verification found another S): no verification this time
-    // w_direct (eagle_scan_with_W): inv_MMt_sqrt is not S but W itself, `a` is v = S a_hat; dim_reduced_vara is unused
-    const long Lr = m1 - m0;
-    const long np = eagle_pad(n), Lp = eagle_pad(Lr > 0 ? Lr : 1);
-    const size_t sq = sizeof(double) * (size_t)np * np;
-    const bool use_i8 = ctx->scan_mode == 1 && 64.0 * 512.0 * (double)np < 2147483648.0;
-    const int nslices = ctx->scan_slices | (ctx->scan_stochastic ? EAGLE_SLICES_STOCHASTIC : 0);
-    // W's rows shared between devices + ONE all-gather: only for the fp64 products.  The int8 digit-slice products (round 4) cost half
-    // as much, are a deterministic function of S and V -- every device forms the bits a single device forms, no exchange, no all-gather
-    // of 8 n^2 bytes, each device's copy of S stays cached and verified -- and so run replicated on every device.
-    const bool share_w = !w_direct && rccl && (np / 128) % nd == 0 && !(use_i8 && eagle_w8_wanted(ctx, np));  // the same answer on every device
-    int rc = EAGLE_OK;
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e != hipSuccess) rc = eagle_fail_hip(ctx, e, "hipSetDevice");
-#define EAGLE_ARRIVE(v) EAGLE_ARRIVE2(v, 0)
-#define EAGLE_ARRIVE2(v, add)                                                                                      \
-    do {                                                                                                           \
-        if (rv && !rv->arrive(rc == EAGLE_OK, (v), (add))) return rc ? rc : eagle_fail(ctx, EAGLE_ERR_HIP, "another device of the scan failed"); \
-        if (!rv && rc) return rc;                                                                                  \
-    } while (0)
-    GenoEntry* g = nullptr;
-    bool streamed = false;
-    if (!rc && Lr > 0) {
-        // operands, digit + certification workspaces (the arena: what this context already holds of it -- from an earlier call or from
-        // the background reservation -- is not free memory any more and must not be counted against the file a second time), the
-        // re-centred image of the shard
-        arena_collect(ctx);
-        const size_t arena_need = 4 * sq + (use_i8 ? (size_t)eagle_vara_i8_workspace_bytes(np, Lp, nslices) + (size_t)eagle_scan_certify_workspace_bytes(np) : 0);
-        int r = get_resident(ctx, f_name_ascii, m0, Lr, 0, n, max_memory_in_Gbytes, host_threads(), &g,
-                             (arena_need > ctx->arena_cap ? arena_need - ctx->arena_cap : 0) + (use_i8 ? (size_t)Lp * np + 9 * (size_t)Lp : 0) +
-                                 ((size_t)1 << 30));
-        if (r < 0) rc = r;
-        streamed = (r == EAGLE_STREAM);
-    }
-    EAGLE_ARRIVE(streamed ? 1.0 : 0.0);
-    // A scan that does not see all its markers at once -- a file streamed in marker blocks, the shards of several devices -- is
-    // certified against ONE lower bound of the maximum over every block of every device, so that the candidates, and with them every
-    // returned bit, are those of the one-block scan of the whole file (the per-marker bounds of all blocks stay: 8 bytes per marker).
-    const bool bounds_flow = use_i8 && (streamed || rv);
-    long over_tight_all = 0;   // markers of the whole scan over the tight threshold (CERT_TIGHT_MAX)
-    const long Lc = streamed ? stream_chunk_rows(np, Lp) : Lp;  // marker rows per pass
-    DevBuf dsel;
-    const size_t wsb = use_i8 ? (size_t)eagle_vara_i8_workspace_bytes(np, Lc, nslices) : 0;
-    const size_t certb = use_i8 ? (size_t)eagle_scan_certify_workspace_bytes(np) : 0;
-    const double t0 = now_s();
+// ------------------------------------------------------------------------------------------------
+// The scan driver.  scan_range makes at most two attempts; an attempt (scan_once) is the sequence of its stages, which stand below in
+// the order they run.  Three structs: what the caller passed, this device's share of the call, and what the stages hand on.  The
+// modes of an attempt are decided once (scan_plan, eagle_host.h); the stages only read the plan.
+// ------------------------------------------------------------------------------------------------
+struct ScanArgs {   // what the caller passed: built once in each entry point
+    const char* file; long L, n; const std::vector<long>& sel;
+    const double *inv_MMt_sqrt, *dim_reduced_vara, *a;   // w_direct (eagle_scan_with_W): W itself, unused, v = S a_hat
+    double mem_gb; int quiet; double *a_out, *vara_out; bool w_direct;
+};
+// this device's share: the markers [m0, m1), device k of nd; rv / rccl: the meeting point and the communicators of a multi-device call (NULL for one device)
+struct ScanShare { long m0, m1; int k, nd; Rendezvous* rv; RcclState* rccl; };
+struct ScanState {
+    long Lr, np, Lp; size_t sq; int nslices;   // markers of the shard; padded individuals, markers (at least a tile); bytes of an np x np operand
+    ScanPlan plan;
+    GenoEntry* g = nullptr;   // residency: the shard's image (NULL: streamed, or no markers)
+    // setup: the carve-up of the arena
+    long Lc = 0;              // marker rows per pass
     double *Sa = nullptr, *Va = nullptr, *tmp = nullptr, *Wu = nullptr, *ah = nullptr, *v = nullptr;
-    SCache& sc = ctx->scache;   // the S of the last call, kept for this one
-    struct Left { SCache& c; ~Left() { c.leave(); } } left{sc};   // (its helper thread is joined on every way out)
     void *ws = nullptr, *cert = nullptr;
-    long* cert_totals = (long*)((char*)ctx->d_scratch + EAGLE_SCR_CERT_TOTALS);  // {re-evaluated, flagged, fell back, over the tight threshold}, summed over marker blocks
+    long* cert_totals = nullptr;   // {re-evaluated, flagged, fell back, over the tight threshold}, summed over marker blocks
     ChunkRing ring;
-    int8_t* shifted[2] = {nullptr, nullptr};
-    int8_t* cs[2] = {nullptr, nullptr};
-    int32_t* l1s[2] = {nullptr, nullptr};
+    int8_t *shifted[2] = {}, *cs[2] = {}; int32_t* l1s[2] = {};
     PhaseEvents ph;
-    auto setup = [&]() -> int {
-        int r = arena_reserve(ctx, 4 * arena_round(sq) + 2 * arena_round(sizeof(double) * np) + arena_round(wsb) + arena_round(certb) +
-                                       (streamed ? (use_i8 ? 4 : 2) * arena_round((size_t)Lc * np) + 2 * arena_round((size_t)Lc) +
-                                                       2 * arena_round(2 * sizeof(int32_t) * (size_t)Lc) : 0));
-        if (r) return r;
-        Sa = arena_take<double>(ctx, sq);
-        Va = arena_take<double>(ctx, sq);
-        tmp = arena_take<double>(ctx, sq);
-        Wu = arena_take<double>(ctx, sq);
-        ah = arena_take<double>(ctx, sizeof(double) * np);
-        v = arena_take<double>(ctx, sizeof(double) * np);
-        ws = arena_take<char>(ctx, wsb);
-        cert = arena_take<char>(ctx, certb);
-        ph.mark(ctx->stream, PH_START);
-        if (streamed) {
-            if ((r = ring.init(ctx))) return r;
-            ring.buf[0] = arena_take<int8_t>(ctx, (size_t)Lc * np);
-            ring.buf[1] = arena_take<int8_t>(ctx, (size_t)Lc * np);
-            for (int b = 0; b < 2 && use_i8; b++) {
-                shifted[b] = arena_take<int8_t>(ctx, (size_t)Lc * np);
-                cs[b] = arena_take<int8_t>(ctx, (size_t)Lc);
-                l1s[b] = arena_take<int32_t>(ctx, 2 * sizeof(int32_t) * (size_t)Lc);
-            }
-        }
-        if (w_direct) {  // W and v arrive ready: no n^3 work, W goes straight into the buffer the fold works on
-            if ((r = upload_square(ctx, inv_MMt_sqrt, n, np, Wu))) return r;
-            if ((r = upload_vec(ctx, a, n, np, v))) return r;
-        } else {
-            // V changes with every call; it arrives in row blocks on the loader stream UNDER the first product, which works on the rows
-            // that have landed (below) -- unless the rows of W are shared between devices (share_w: the row-block product there needs all
-            // of V at once).
-            if (share_w && (r = upload_square_staged(ctx, dim_reduced_vara, n, np, Va, ctx->stream))) return r;
-            if ((r = upload_vec(ctx, a, n, np, ah))) return r;
-        }
-        // the S to compute on: the cached copy when there is one (the caller's matrix is verified under the products, below), else uploaded
-        if ((r = sc.acquire(ctx, SCall{w_direct, s_trusted, n, np, rv != nullptr, streamed, bounds_flow}, pol, inv_MMt_sqrt, Sa, &Sa))) return r;
-        // streamed: every block is worked as a full chunk of Lc rows (one workspace layout for all of them; the rows beyond a short
-        // last block are zero and land in the slack behind the shard's results)
-        if ((r = ensure_scan_out(ctx, streamed ? (Lr + Lc - 1) / Lc * Lc : Lp))) return r;
-        HIPCHK(ctx, hipMemsetAsync(cert_totals, 0, 4 * sizeof(long), ctx->stream));
-        ph.mark(ctx->stream, PH_UPLOAD);
-        return EAGLE_OK;
-    };
-    if (!rc) rc = setup();
-    const double t_setup = now_s();
-    double t1 = 0;
-    if (timing_on() && !rc) { (void)hipStreamSynchronize(ctx->stream); t1 = now_s(); }
-    // W = S (V S) and v = S a_hat.  Several devices: each computes 1/nd of the rows of W's image and ONE all-gather completes
-    // it everywhere (the n^3 part would otherwise not scale); without device collectives every device computes all of it.
-    if (share_w || w_direct) { ctx->w8_active = false; ctx->w8_info = W8Info(); ctx->w8_info.declined = 7; }
-    if (share_w) {
-        const long rows = np / nd, r0 = k * rows;
-        if (!rc) rc = eagle_dev_scan_operands_rows(ctx, Sa, Va, ah, n, np, r0, r0 + rows, v, Wu, tmp, ctx->stream);
-        if (!rc && (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) rc = eagle_fail_hip(ctx, e, "rows of W");
-        EAGLE_ARRIVE(0.0);
-        const ncclComm_t comm = rccl_comm(rccl, k);
-        ncclResult_t nr = (rccl_fault("allgather", k) || !comm) ? ncclSystemError
-                                                  : rccl->AllGather(Wu + r0 * np, Wu, (size_t)(rows * np), ncclDouble, comm, ctx->stream);
-        if (nr != ncclSuccess) { rc = failf(ctx, EAGLE_ERR_HIP, "ncclAllGather: %s", rccl->GetErrorString(nr)); rccl_abort_all(rccl); }
-        if (!rc) rc = eagle_dev_fold_upper(ctx, Wu, np, ctx->stream);
-    } else if (!rc) {
-        if (w_direct) rc = eagle_dev_fold_upper(ctx, Wu, np, ctx->stream);
-        else {
-            // v = S a_hat at once; then V in blocks of 1024 rows of its image: copy on the loader stream, event, the rows X = V S of
-            // that block on the compute stream.  PCIe (57 GB/s) delivers a block in half the time its product takes, so all of
-            // V's upload but the first block hides under the first n^3 product.
-            if (eagle_w8_wanted(ctx, np)) {
-                // W on the int8 engine (csrc/eagle_w8.hip): its configuration is chosen from statistics of ALL of V, so V is uploaded
-                // whole (loader stream; S's statistics and slices do not wait for it) and the products follow; a call that declines
-                // runs the fp64 products on the resident operands
-                // Since the first version of round 4 the upload is pipelined when this context has a configuration to guess (its last
-                // call's): V goes up in blocks of 1,536 rows through the pinned staging buffers (16 host threads), and each block's
-                // statistics, digit slices and columns of the first product run on the compute stream as soon as its rows have landed;
-                // the finish step keeps that product only if the rule, on the statistics of ALL of V, chooses the guessed configuration.
-                // (the cache's verdict on S goes with it: the same verified content as the last call's -- no upload, no refresh -- lets the
-                // engine keep what it made from S alone; EAGLE_HIP_NO_SCACHE: nobody vouches for S)
-                int r8 = eagle_w8_begin(ctx, Sa, Va, ah, n, np, v, Wu, tmp, 1, pol.no_scache ? 0 : sc.s_gen, ctx->stream);
-                if (r8 < 0) rc = r8;
-                if (!rc) {
-                    const long vb = eagle_w8_vrows_block();
-                    rc = upload_square_staged(ctx, dim_reduced_vara, n, np, Va, ctx->load_stream, vb, [&](long r0, long r1, hipEvent_t landed) -> int {
-                        if (r8) return EAGLE_OK;   // declined at the start (no workspace): only the upload
-                        hipError_t ew = hipStreamWaitEvent(ctx->stream, landed, 0);
-                        if (ew != hipSuccess) return eagle_fail_hip(ctx, ew, "row block event");
-                        const int rv8 = eagle_w8_vrows(ctx, r0, r1, ctx->stream);
-                        if (rv8 < 0) return rv8;
-                        if (rv8) r8 = 1;
-                        return EAGLE_OK;
-                    });
-                }
-                if (!rc && !r8) {
-                    r8 = eagle_w8_finish(ctx, ctx->stream);
-                    if (r8 < 0) rc = r8;
-                }
-                if (!rc && r8 == 1) {   // declined: the fp64 products on the operands that are resident now (v is made already)
-                    hipEvent_t ev = nullptr;
-                    if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) rc = eagle_fail_hip(ctx, e, "hipEventCreate");
-                    if (!rc && ((e = hipEventRecord(ev, ctx->load_stream)) != hipSuccess || (e = hipStreamWaitEvent(ctx->stream, ev, 0)) != hipSuccess))
-                        rc = eagle_fail_hip(ctx, e, "V upload event");
-                    ctx->w8_active = false;
-                    if (!rc) rc = eagle_dev_scan_operands_w_f64(ctx, Sa, Va, np, Wu, tmp, ctx->stream);
-                    if (ev) (void)hipEventDestroy(ev);
-                }
-                if (rc) (void)hipStreamSynchronize(ctx->load_stream);
-            } else {
-            ctx->w8_active = false;
-            ctx->w8_info = W8Info();
-            ctx->w8_info.declined = 7;
-            rc = eagle_dev_scan_operands_begin(ctx, Sa, ah, n, np, v, tmp, ctx->stream);
-            if (!rc && (e = hipMemsetAsync(Va, 0, sq, ctx->load_stream)) != hipSuccess) rc = eagle_fail_hip(ctx, e, "V memset");
-            std::vector<hipEvent_t> landed;
-            for (long b0 = 0; b0 < np && !rc; b0 += EAGLE_VROWS_BLOCK) {
-                const long b1 = std::min(np, b0 + EAGLE_VROWS_BLOCK), hr = std::min(n, b1) - b0;  // rows of the image = columns of the R matrix
-                if (hr > 0) {
-                    e = hipMemcpy2DAsync(Va + b0 * np, sizeof(double) * np, dim_reduced_vara + b0 * n, sizeof(double) * n, sizeof(double) * n, (size_t)hr,
-                                         hipMemcpyHostToDevice, ctx->load_stream);
-                    if (e != hipSuccess) { rc = eagle_fail_hip(ctx, e, "upload of a row block of V"); break; }
-                }
-                hipEvent_t ev = nullptr;
-                if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) { rc = eagle_fail_hip(ctx, e, "hipEventCreate"); break; }
-                landed.push_back(ev);
-                if ((e = hipEventRecord(ev, ctx->load_stream)) != hipSuccess || (e = hipStreamWaitEvent(ctx->stream, ev, 0)) != hipSuccess) {
-                    rc = eagle_fail_hip(ctx, e, "row block event"); break;
-                }
-                rc = eagle_dev_scan_operands_vrows(ctx, Sa, Va, np, b0, b1, tmp, ctx->stream);
-            }
-            if (!rc) rc = eagle_dev_scan_operands_finish(ctx, Sa, Va, np, Wu, tmp, ctx->stream);
-            if (rc) (void)hipStreamSynchronize(ctx->load_stream);  // nothing of the caller's V may still be in flight when we return
-            for (hipEvent_t ev : landed) (void)hipEventDestroy(ev);
-            }
+    double t0 = 0, t_setup = 0;
+    long over_tight_all = 0;  // markers of the whole scan over the tight threshold (CERT_TIGHT_MAX)
+};
+
+// One rendezvous round of a multi-device call (rv; NULL: one device, no round).  true: every device is well so far, the attempt goes
+// on.  false: leave now with *rc -- this device's failure, or the news that another device failed.  A failed device arrives too: the
+// others are waiting for it.
+static bool scan_arrive(eagle_ctx* ctx, Rendezvous* rv, int* rc, double v, long add = 0) {
+    if (!rv) return *rc == EAGLE_OK;
+    if (rv->arrive(*rc == EAGLE_OK, v, add)) return true;
+    if (!*rc) *rc = eagle_fail(ctx, EAGLE_ERR_HIP, "another device of the scan failed");
+    return false;
+}
+
+// Residency: the shard's image in HBM -- there already, or loaded if it fits beside what the scan itself needs -- else *streamed.
+static int scan_residency(eagle_ctx* ctx, const ScanArgs& A, const ScanShare& D, ScanState& st, bool* streamed) {
+    // operands, digit + certification workspaces (the arena: what this context already holds of it -- from an earlier call or from
+    // the background reservation -- is not free memory any more and must not be counted against the file a second time), the
+    // re-centred image of the shard
+    arena_collect(ctx);
+    const bool i8 = scan_use_i8(ctx->scan_mode, st.np);   // (the plan waits for this stage's answer)
+    const size_t arena_need = 4 * st.sq + (i8 ? (size_t)eagle_vara_i8_workspace_bytes(st.np, st.Lp, st.nslices) + (size_t)eagle_scan_certify_workspace_bytes(st.np) : 0);
+    const int r = get_resident(ctx, A.file, D.m0, st.Lr, 0, A.n, A.mem_gb, host_threads(), &st.g,
+                               (arena_need > ctx->arena_cap ? arena_need - ctx->arena_cap : 0) + (i8 ? (size_t)st.Lp * st.np + 9 * (size_t)st.Lp : 0) +
+                                   ((size_t)1 << 30));
+    *streamed = (r == EAGLE_STREAM);
+    return r < 0 ? r : EAGLE_OK;
+}
+
+// Setup: the arena carved up, the operands on their way, the S to compute on, room for the results.
+static int scan_setup(eagle_ctx* ctx, const ScanArgs& A, const ScanShare& D, ScanState& st, bool s_trusted, const SPolicy& pol) {
+    const ScanPlan& P = st.plan;
+    const long n = A.n, np = st.np;
+    const size_t sq = st.sq;
+    const long Lc = st.Lc = P.streamed ? stream_chunk_rows(np, st.Lp) : st.Lp;
+    const size_t wsb = P.use_i8 ? (size_t)eagle_vara_i8_workspace_bytes(np, Lc, st.nslices) : 0;
+    const size_t certb = P.use_i8 ? (size_t)eagle_scan_certify_workspace_bytes(np) : 0;
+    st.cert_totals = (long*)((char*)ctx->d_scratch + EAGLE_SCR_CERT_TOTALS);
+    int r = arena_reserve(ctx, 4 * arena_round(sq) + 2 * arena_round(sizeof(double) * np) + arena_round(wsb) + arena_round(certb) +
+                                   (P.streamed ? (P.use_i8 ? 4 : 2) * arena_round((size_t)Lc * np) + 2 * arena_round((size_t)Lc) +
+                                                     2 * arena_round(2 * sizeof(int32_t) * (size_t)Lc) : 0));
+    if (r) return r;
+    st.Sa = arena_take<double>(ctx, sq);
+    st.Va = arena_take<double>(ctx, sq);
+    st.tmp = arena_take<double>(ctx, sq);
+    st.Wu = arena_take<double>(ctx, sq);
+    st.ah = arena_take<double>(ctx, sizeof(double) * np);
+    st.v = arena_take<double>(ctx, sizeof(double) * np);
+    st.ws = arena_take<char>(ctx, wsb);
+    st.cert = arena_take<char>(ctx, certb);
+    st.ph.mark(ctx->stream, PH_START);
+    if (P.streamed) {
+        if ((r = st.ring.init(ctx))) return r;
+        st.ring.buf[0] = arena_take<int8_t>(ctx, (size_t)Lc * np);
+        st.ring.buf[1] = arena_take<int8_t>(ctx, (size_t)Lc * np);
+        for (int b = 0; b < 2 && P.use_i8; b++) {
+            st.shifted[b] = arena_take<int8_t>(ctx, (size_t)Lc * np);
+            st.cs[b] = arena_take<int8_t>(ctx, (size_t)Lc);
+            st.l1s[b] = arena_take<int32_t>(ctx, 2 * sizeof(int32_t) * (size_t)Lc);
         }
     }
-    if (!rc && sc.plan.verify != SV_NONE) {
-        rc = sc.begin_verify(ctx, inv_MMt_sqrt, n, np);
-        // (rv: a device of a multi-device call must not defer -- a peer that streams or holds no cached S settles a changed S inline,
-        // and a second attempt of this one would pass every rendezvous of the call a second time)
-        if (sc.plan.verify == SV_DEVICE_INLINE) {
-            SOutcome o;
-            rc = sc.settle(ctx, rc, &o);
-            if (!rc && o == S_OTHER_ON_DEVICE) {   // another S, on the device already: the products start over with it
-                Sa = sc.d_S;
-                rc = eagle_dev_scan_operands(ctx, Sa, Va, ah, n, np, v, Wu, tmp, ctx->stream);
-            }
+    if (P.w == W_READY) {  // W and v arrive ready: no n^3 work, W goes straight into the buffer the fold works on
+        if ((r = upload_square(ctx, A.inv_MMt_sqrt, n, np, st.Wu))) return r;
+        if ((r = upload_vec(ctx, A.a, n, np, st.v))) return r;
+    } else {
+        // V changes with every call; it arrives in row blocks on the loader stream UNDER the first product, which works on the rows
+        // that have landed (the W routes) -- unless the rows of W are shared between devices (the row-block product there needs all
+        // of V at once).
+        if (P.w == W_SHARED && (r = upload_square_staged(ctx, A.dim_reduced_vara, n, np, st.Va, ctx->stream))) return r;
+        if ((r = upload_vec(ctx, A.a, n, np, st.ah))) return r;
+    }
+    // the S to compute on: the cached copy when there is one (the caller's matrix is verified under the products: scan_verify_s), else uploaded
+    if ((r = ctx->scache.acquire(ctx, SCall{A.w_direct, s_trusted, n, np, D.rv != nullptr, P.streamed, P.bounds_flow}, pol, A.inv_MMt_sqrt, st.Sa, &st.Sa)))
+        return r;
+    // streamed: every block is worked as a full chunk of Lc rows (one workspace layout for all of them; the rows beyond a short
+    // last block are zero and land in the slack behind the shard's results)
+    if ((r = ensure_scan_out(ctx, P.streamed ? (st.Lr + Lc - 1) / Lc * Lc : st.Lp))) return r;
+    HIPCHK(ctx, hipMemsetAsync(st.cert_totals, 0, 4 * sizeof(long), ctx->stream));
+    st.ph.mark(ctx->stream, PH_UPLOAD);
+    return EAGLE_OK;
+}
+
+// W = S (V S) and v = S a_hat, one function per route of the plan.
+// W_READY: only the fold.
+static int scan_w_ready(eagle_ctx* ctx, ScanState& st) { return eagle_dev_fold_upper(ctx, st.Wu, st.np, ctx->stream); }
+// W_SHARED: each device computes 1/nd of the rows of W's image (the n^3 part would otherwise not scale) ...
+static int scan_w_shared_rows(eagle_ctx* ctx, const ScanArgs& A, const ScanShare& D, ScanState& st) {
+    const long rows = st.np / D.nd, r0 = D.k * rows;
+    int rc = eagle_dev_scan_operands_rows(ctx, st.Sa, st.Va, st.ah, A.n, st.np, r0, r0 + rows, st.v, st.Wu, st.tmp, ctx->stream);
+    hipError_t e;
+    if (!rc && (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) rc = eagle_fail_hip(ctx, e, "rows of W");
+    return rc;
+}
+// ... and, once every device has its rows (scan_once's arrival between the two), ONE all-gather completes it everywhere.
+static int scan_w_shared_gather(eagle_ctx* ctx, const ScanShare& D, ScanState& st) {
+    const long np = st.np, rows = np / D.nd, r0 = D.k * rows;
+    const ncclComm_t comm = rccl_comm(D.rccl, D.k);
+    ncclResult_t nr = (rccl_fault("allgather", D.k) || !comm) ? ncclSystemError
+                                                    : D.rccl->AllGather(st.Wu + r0 * np, st.Wu, (size_t)(rows * np), ncclDouble, comm, ctx->stream);
+    if (nr == ncclSuccess) return eagle_dev_fold_upper(ctx, st.Wu, np, ctx->stream);
+    const int rc = failf(ctx, EAGLE_ERR_HIP, "ncclAllGather: %s", D.rccl->GetErrorString(nr));
+    rccl_abort_all(D.rccl);
+    return rc;
+}
+// W_INT8: W on the int8 engine (csrc/eagle_w8.hip).  Its configuration is chosen from statistics of ALL of V, so V is uploaded whole
+// (loader stream; S's statistics and slices do not wait for it); a call that declines runs the fp64 products on the resident operands.
+// The upload is pipelined when this context has a configuration to guess (its last call's): V goes up in blocks of 1,536 rows through
+// the pinned staging buffers (16 host threads), and each block's statistics, digit slices and columns of the first product run on the
+// compute stream as soon as its rows have landed; the finish step keeps that product only if the rule, on the statistics of ALL of V,
+// chooses the guessed configuration.  (the cache's verdict on S goes with it: the same verified content as the last call's -- no upload,
+// no refresh -- lets the engine keep what it made from S alone; EAGLE_HIP_NO_SCACHE: nobody vouches for S)
+static int scan_w_int8(eagle_ctx* ctx, const ScanArgs& A, ScanState& st, const SPolicy& pol) {
+    const long n = A.n, np = st.np;
+    int rc = EAGLE_OK;
+    hipError_t e;
+    int r8 = eagle_w8_begin(ctx, st.Sa, st.Va, st.ah, n, np, st.v, st.Wu, st.tmp, 1, pol.no_scache ? 0 : ctx->scache.s_gen, ctx->stream);
+    if (r8 < 0) rc = r8;
+    if (!rc) {
+        const long vb = eagle_w8_vrows_block();
+        rc = upload_square_staged(ctx, A.dim_reduced_vara, n, np, st.Va, ctx->load_stream, vb, [&](long r0, long r1, hipEvent_t landed) -> int {
+            if (r8) return EAGLE_OK;   // declined at the start (no workspace): only the upload
+            hipError_t ew = hipStreamWaitEvent(ctx->stream, landed, 0);
+            if (ew != hipSuccess) return eagle_fail_hip(ctx, ew, "row block event");
+            const int rv8 = eagle_w8_vrows(ctx, r0, r1, ctx->stream);
+            if (rv8 < 0) return rv8;
+            if (rv8) r8 = 1;
+            return EAGLE_OK;
+        });
+    }
+    if (!rc && !r8) {
+        r8 = eagle_w8_finish(ctx, ctx->stream);
+        if (r8 < 0) rc = r8;
+    }
+    if (!rc && r8 == 1) {   // declined: the fp64 products on the operands that are resident now (v is made already)
+        hipEvent_t ev = nullptr;
+        if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) rc = eagle_fail_hip(ctx, e, "hipEventCreate");
+        if (!rc && ((e = hipEventRecord(ev, ctx->load_stream)) != hipSuccess || (e = hipStreamWaitEvent(ctx->stream, ev, 0)) != hipSuccess))
+            rc = eagle_fail_hip(ctx, e, "V upload event");
+        ctx->w8_active = false;
+        if (!rc) rc = eagle_dev_scan_operands_w_f64(ctx, st.Sa, st.Va, np, st.Wu, st.tmp, ctx->stream);
+        if (ev) (void)hipEventDestroy(ev);
+    }
+    if (rc) (void)hipStreamSynchronize(ctx->load_stream);
+    return rc;
+}
+// W_FP64: v = S a_hat at once; then V in blocks of 1024 rows of its image: copy on the loader stream, event, the rows X = V S of
+// that block on the compute stream.  PCIe (57 GB/s) delivers a block in half the time its product takes, so all of
+// V's upload but the first block hides under the first n^3 product.
+static int scan_w_fp64(eagle_ctx* ctx, const ScanArgs& A, ScanState& st) {
+    const long n = A.n, np = st.np;
+    hipError_t e;
+    int rc = eagle_dev_scan_operands_begin(ctx, st.Sa, st.ah, n, np, st.v, st.tmp, ctx->stream);
+    if (!rc && (e = hipMemsetAsync(st.Va, 0, st.sq, ctx->load_stream)) != hipSuccess) rc = eagle_fail_hip(ctx, e, "V memset");
+    std::vector<hipEvent_t> landed;
+    for (long b0 = 0; b0 < np && !rc; b0 += EAGLE_VROWS_BLOCK) {
+        const long b1 = std::min(np, b0 + EAGLE_VROWS_BLOCK), hr = std::min(n, b1) - b0;  // rows of the image = columns of the R matrix
+        if (hr > 0) {
+            e = hipMemcpy2DAsync(st.Va + b0 * np, sizeof(double) * np, A.dim_reduced_vara + b0 * n, sizeof(double) * n, sizeof(double) * n, (size_t)hr,
+                                 hipMemcpyHostToDevice, ctx->load_stream);
+            if (e != hipSuccess) { rc = eagle_fail_hip(ctx, e, "upload of a row block of V"); break; }
+        }
+        hipEvent_t ev = nullptr;
+        if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) { rc = eagle_fail_hip(ctx, e, "hipEventCreate"); break; }
+        landed.push_back(ev);
+        if ((e = hipEventRecord(ev, ctx->load_stream)) != hipSuccess || (e = hipStreamWaitEvent(ctx->stream, ev, 0)) != hipSuccess) {
+            rc = eagle_fail_hip(ctx, e, "row block event"); break;
+        }
+        rc = eagle_dev_scan_operands_vrows(ctx, st.Sa, st.Va, np, b0, b1, st.tmp, ctx->stream);
+    }
+    if (!rc) rc = eagle_dev_scan_operands_finish(ctx, st.Sa, st.Va, np, st.Wu, st.tmp, ctx->stream);
+    if (rc) (void)hipStreamSynchronize(ctx->load_stream);  // nothing of the caller's V may still be in flight when we return
+    for (hipEvent_t ev : landed) (void)hipEventDestroy(ev);
+    return rc;
+}
+
+// Verification of S right behind W: the comparison of the caller's matrix with the cached copy the products ran on starts here, and
+// where the plan of the cache says so it is settled here too.
+static int scan_verify_s(eagle_ctx* ctx, const ScanArgs& A, ScanState& st) {
+    SCache& sc = ctx->scache;
+    if (sc.plan.verify == SV_NONE) return EAGLE_OK;
+    int rc = sc.begin_verify(ctx, A.inv_MMt_sqrt, A.n, st.np);
+    // (rv: a device of a multi-device call must not defer -- a peer that streams or holds no cached S settles a changed S inline,
+    // and a second attempt of this one would pass every rendezvous of the call a second time)
+    if (sc.plan.verify == SV_DEVICE_INLINE) {
+        SOutcome o;
+        rc = sc.settle(ctx, rc, &o);
+        if (!rc && o == S_OTHER_ON_DEVICE) {   // another S, on the device already: the products start over with it
+            st.Sa = sc.d_S;
+            rc = eagle_dev_scan_operands(ctx, st.Sa, st.Va, st.ah, A.n, st.np, st.v, st.Wu, st.tmp, ctx->stream);
         }
     }
-    if (!rc) ph.mark(ctx->stream, PH_W);
-    if (!rc && streamed && !quiet) say(ctx, " Mt.ascii streamed through HBM in blocks of %ld markers", Lc);
-    // one pass per marker block: the whole shard when it is resident, else chunks read back from the file
-    for (long r0 = 0; r0 < Lr && !rc; r0 += Lc) {
-        const long nr = std::min(Lc, Lr - r0), nrp = streamed ? Lc : eagle_pad(nr);
-        const int8_t* Mt8 = streamed ? nullptr : g->dev;
-        const long ldm = streamed ? np : g->ld;
-        if (streamed) {
-            int8_t* tile = nullptr;
-            rc = ring.load(ctx, f_name_ascii, m0 + r0, nr, 0, n, np, (size_t)nrp * np, max_memory_in_Gbytes, host_threads(), &tile);
-            if (rc) break;
-            Mt8 = tile;
-            ph.mark(ctx->stream, PH_LOADWAIT);
-        }
-        if (use_i8) {
-            // re-centred image of the markers (kept with a resident file, rebuilt per chunk when streaming)
-            const int8_t* Ms = nullptr;
-            const int8_t* cv = nullptr;
-            const int32_t* l1 = nullptr;
-            if (streamed) {
-                const int b = (int)(ring.k & 1);
-                rc = eagle_dev_marker_shift(ctx, Mt8, nrp, n, np, ldm, shifted[b], cs[b], l1s[b], ctx->stream);
-                if (rc) break;
-                Ms = shifted[b]; cv = cs[b]; l1 = l1s[b];
-            } else {
-                if (!g->dev_s) {
-                    e = hipMalloc((void**)&g->dev_s, (size_t)g->rows_pad * g->ld);
-                    if (e != hipSuccess && eagle_drop_f4_images(ctx) > 0) { (void)hipGetLastError(); e = hipMalloc((void**)&g->dev_s, (size_t)g->rows_pad * g->ld); }
-                    if (e == hipSuccess) e = hipMalloc((void**)&g->cshift, (size_t)g->rows_pad);
-                    if (e == hipSuccess) e = hipMalloc((void**)&g->l1, 2 * sizeof(int32_t) * (size_t)g->rows_pad);
-                    rc = e == hipSuccess ? eagle_dev_marker_shift(ctx, g->dev, g->rows_pad, n, np, g->ld, g->dev_s, g->cshift, g->l1, ctx->stream)
-                                         : eagle_fail_hip(ctx, e, "re-centred image hipMalloc");
-                    if (rc) {  // never leave a half-made image behind: the next call would scan garbage
-                        if (g->dev_s) (void)hipFree(g->dev_s);
-                        if (g->cshift) (void)hipFree(g->cshift);
-                        if (g->l1) (void)hipFree(g->l1);
-                        g->dev_s = nullptr; g->cshift = nullptr; g->l1 = nullptr;
-                        break;
-                    }
-                }
-                Ms = g->dev_s; cv = g->cshift; l1 = g->l1;
-            }
-            // one pass over the genotypes gives a = Mt v and the diagonal term of vara; then the int8 MFMA kernel
-            // (the W-dependent part -- digits of W, rho -- once per scan; per block of a streamed file only the genotype pass)
-            rc = eagle_dev_vara_i8_prepare_part(ctx, Mt8, nrp, np, ldm, Wu, nslices, ws, v, ctx->d_a + r0, ctx->stream, !streamed ? 0 : (r0 == 0 ? 0 : 2));
-            if (rc) break;
-            ph.mark(ctx->stream, PH_PREPARE);
-            rc = eagle_dev_vara_i8_mfma_shifted(ctx, Ms, cv, nrp, np, ldm, nslices, ws, ctx->d_vara + r0, nullptr, ctx->stream);
-            if (rc) break;
-            // markers that fail their budget under the spectral bound get the dropped digit back (a per-marker decision: the same
-            // whatever the blocking; dropped on the device when nobody qualifies)
-            rc = eagle_dev_vara_i8_extend(ctx, Ms, cv, l1, nr, nrp, np, ldm, nslices, ws, ctx->d_vara + r0, ctx->stream);
-            if (rc) break;
-            ph.mark(ctx->stream, PH_VARA);
-            // a-posteriori certificate: markers the digit bounds cannot settle are re-evaluated by the fp64 kernel, so that
-            // which(tsq == max(tsq))[1] on the returned arrays is the marker the fp64 scan selects (find_qtl.R:71-83).  One resident
-            // block on one device: bound, selection and re-evaluation right here.  Marker blocks / device shards: only the
-            // per-marker bounds now; selection against the global lower bound after the last block (below).
-            if (bounds_flow) {
-                rc = eagle_dev_cert_bounds(ctx, nr, nrp, np, cv, l1, nslices, ws, ctx->d_vara + r0, ctx->d_bound + r0, ctx->stream);
-            } else {
-                rc = eagle_dev_scan_certify(ctx, Mt8, nr, nrp, np, ldm, cv, l1, nslices, ws, Wu, ctx->d_a + r0, ctx->d_vara + r0, cert, ctx->stream);
-                if (!rc) rc = eagle_dev_cert_accumulate(ctx, cert, cert_totals, ctx->stream);
-            }
-        } else {
-            rc = eagle_dev_gemv_i8(ctx, Mt8, nrp, np, ldm, v, 1.0, ctx->d_a + r0, ctx->stream);
-            if (rc) break;
-            ph.mark(ctx->stream, PH_PREPARE);
-            rc = eagle_dev_vara_f64(ctx, Mt8, nrp, np, ldm, Wu, ctx->d_vara + r0, ctx->stream);
-            if (!rc) ph.mark(ctx->stream, PH_VARA);
-        }
-        if (rc) break;
-        if (use_i8) ph.mark(ctx->stream, PH_CERT);
-        if (streamed && (rc = ring.computed(ctx))) break;
+    return rc;
+}
+
+// The re-centred image of a resident file for the int8 scan, made by the first such scan of the file and kept with it.
+static int ensure_shifted_image(eagle_ctx* ctx, GenoEntry* g, long n, long np) {
+    if (g->dev_s) return EAGLE_OK;
+    hipError_t e = hipMalloc((void**)&g->dev_s, (size_t)g->rows_pad * g->ld);
+    if (e != hipSuccess && eagle_drop_f4_images(ctx) > 0) { (void)hipGetLastError(); e = hipMalloc((void**)&g->dev_s, (size_t)g->rows_pad * g->ld); }
+    if (e == hipSuccess) e = hipMalloc((void**)&g->cshift, (size_t)g->rows_pad);
+    if (e == hipSuccess) e = hipMalloc((void**)&g->l1, 2 * sizeof(int32_t) * (size_t)g->rows_pad);
+    const int rc = e == hipSuccess ? eagle_dev_marker_shift(ctx, g->dev, g->rows_pad, n, np, g->ld, g->dev_s, g->cshift, g->l1, ctx->stream)
+                                   : eagle_fail_hip(ctx, e, "re-centred image hipMalloc");
+    if (rc) {  // never leave a half-made image behind: the next call would scan garbage
+        if (g->dev_s) (void)hipFree(g->dev_s);
+        if (g->cshift) (void)hipFree(g->cshift);
+        if (g->l1) (void)hipFree(g->l1);
+        g->dev_s = nullptr; g->cshift = nullptr; g->l1 = nullptr;
     }
-    if (streamed && !rc) ring.finish(ctx);
-    if (bounds_flow) {
-        // this shard's lower bound of the maximum tsq (0 for an empty shard) and its markers over the tight threshold: the maximum / the
-        // sum over the devices decide for all of them
-        eagle_cert_info mine = {};
-        if (!rc && Lr > 0) {
-            rc = eagle_dev_cert_lb_b(ctx, Lr, ctx->d_a, ctx->d_vara, ctx->d_bound, cert, ws, ctx->stream);
-            if (!rc) {
-                e = hipMemcpyAsync(&mine, cert, sizeof mine, hipMemcpyDeviceToHost, ctx->stream);
-                if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-                if (e != hipSuccess) rc = eagle_fail_hip(ctx, e, "lower bound of the shard's maximum");
-            }
-        }
-        const double lb = mine.lower_bound;
-        EAGLE_ARRIVE2(lb, (long)mine.over_tight);
-        const double glb = rv ? rv->vmax : lb;
-        over_tight_all = rv ? rv->vsum : (long)mine.over_tight;
-        if (Lr > 0) {
-            eagle_cert_info hd;
-            rc = eagle_dev_cert_select_b(ctx, Lr, ctx->d_a, ctx->d_vara, ctx->d_bound, cert, glb, over_tight_all, ws, ctx->stream);
-            if (!rc) {
-                e = hipMemcpyAsync(&hd, cert, sizeof hd, hipMemcpyDeviceToHost, ctx->stream);
-                if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-                if (e != hipSuccess) rc = eagle_fail_hip(ctx, e, "candidate count");
-            }
-            if (!rc && hd.overflow) {
-                // more candidates than the re-evaluation buffer holds (degenerate operands): all of the shard in fp64
-                // (on the fp64 products, should W have come from the int8 engine)
-                rc = eagle_w8_redo_f64(ctx, np, ctx->stream);
-                if (rc) {
-                } else if (!streamed) {
-                    rc = eagle_dev_vara_f64(ctx, g->dev, Lp, np, g->ld, Wu, ctx->d_vara, ctx->stream);
-                } else {
-                    ChunkRing again;
-                    if (!(rc = again.init(ctx))) {
-                        again.buf[0] = ring.buf[0]; again.buf[1] = ring.buf[1];
-                        for (long r0 = 0; r0 < Lr && !rc; r0 += Lc) {
-                            const long nr = std::min(Lc, Lr - r0), nrp = eagle_pad(nr);
-                            int8_t* tile = nullptr;
-                            rc = again.load(ctx, f_name_ascii, m0 + r0, nr, 0, n, np, (size_t)nrp * np, max_memory_in_Gbytes, host_threads(), &tile);
-                            if (!rc) rc = eagle_dev_vara_f64(ctx, tile, nrp, np, np, Wu, ctx->d_vara + r0, ctx->stream);
-                            if (!rc) rc = again.computed(ctx);
-                        }
-                        if (!rc) again.finish(ctx);
-                    }
-                }
-            } else if (!rc && hd.reevaluated > 0) {
-                if (!streamed) {
-                    rc = eagle_dev_cert_reevaluate(ctx, g->dev, g->ld, np, Wu, ctx->d_vara, cert, ctx->stream);
-                } else {
-                    // only the candidates' rows are read back from the file (its 2-bit sidecar when there is one): typically one or two
-                    const long cnt = hd.reevaluated;
-                    std::vector<long> idx((size_t)cnt);
-                    int8_t* rows = eagle_cert_rows(cert);
-                    e = hipMemcpyAsync(idx.data(), eagle_cert_indices(cert), sizeof(long) * (size_t)cnt, hipMemcpyDeviceToHost, ctx->stream);
-                    if (e == hipSuccess) e = hipMemsetAsync(rows, 0, (size_t)((cnt + 127) / 128 * 128) * (size_t)np, ctx->stream);
-                    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-                    if (e != hipSuccess) rc = eagle_fail_hip(ctx, e, "candidate list");
-                    std::vector<RowRun> runs((size_t)cnt);
-                    for (long c = 0; c < cnt; c++) runs[(size_t)c] = {m0 + idx[(size_t)c], 1};
-                    if (!rc) rc = eagle_load_rows(ctx, f_name_ascii, runs, 0, n, rows, np, max_memory_in_Gbytes, 1);
-                    if (!rc) rc = eagle_dev_cert_reevaluate(ctx, nullptr, np, np, Wu, ctx->d_vara, cert, ctx->stream);
-                }
-            }
-            if (!rc) rc = eagle_dev_cert_accumulate(ctx, cert, cert_totals, ctx->stream);
-            if (!rc) ph.mark(ctx->stream, PH_CERT);
-        }
+    return rc;
+}
+
+// One marker block on the int8 MFMA: b worked as nrp padded rows; slot: which of the two streamed sets of re-centring buffers is free.
+static int scan_block_i8(eagle_ctx* ctx, long n, ScanState& st, const MarkerBlock& b, long nrp, int slot) {
+    const bool streamed = st.plan.streamed;
+    const long np = st.np, r0 = b.r0;
+    // re-centred image of the markers (kept with a resident file, rebuilt per chunk when streaming)
+    const int8_t *Ms, *cv;
+    const int32_t* l1;
+    int rc;
+    if (streamed) {
+        rc = eagle_dev_marker_shift(ctx, b.image, nrp, n, np, b.ld, st.shifted[slot], st.cs[slot], st.l1s[slot], ctx->stream);
+        if (rc) return rc;
+        Ms = st.shifted[slot]; cv = st.cs[slot]; l1 = st.l1s[slot];
+    } else {
+        if ((rc = ensure_shifted_image(ctx, st.g, n, np))) return rc;
+        Ms = st.g->dev_s; cv = st.g->cshift; l1 = st.g->l1;
     }
-#undef EAGLE_ARRIVE
-#undef EAGLE_ARRIVE2
-    SOutcome settled;
-    rc = sc.settle(ctx, rc, &settled);   // the deferred outcome of the verification of the cached S
-    if (!rc && (settled == S_OTHER_ON_DEVICE || settled == S_OTHER_FORGOTTEN)) { *redo = settled; return EAGLE_OK; }   // ran on the wrong operand: once more (scan_range)
-    if (timing_on() && !rc) {
-        (void)hipStreamSynchronize(ctx->stream);
-        fprintf(stderr, "[eaglehip] scan n=%ld markers [%ld, %ld) of %ld on device %d%s: alloc+upload %.1f ms, device compute %.1f ms\n", n, m0, m1, L,
-                ctx->device, streamed ? " (streamed)" : "", (t1 - t0) * 1e3, (now_s() - t1) * 1e3);
-    }
+    // one pass over the genotypes gives a = Mt v and the diagonal term of vara; then the int8 MFMA kernel
+    // (the W-dependent part -- digits of W, rho -- once per scan; per block of a streamed file only the genotype pass)
+    rc = eagle_dev_vara_i8_prepare_part(ctx, b.image, nrp, np, b.ld, st.Wu, st.nslices, st.ws, st.v, ctx->d_a + r0, ctx->stream, !streamed ? 0 : (r0 == 0 ? 0 : 2));
     if (rc) return rc;
+    st.ph.mark(ctx->stream, PH_PREPARE);
+    rc = eagle_dev_vara_i8_mfma_shifted(ctx, Ms, cv, nrp, np, b.ld, st.nslices, st.ws, ctx->d_vara + r0, nullptr, ctx->stream);
+    if (rc) return rc;
+    // markers that fail their budget under the spectral bound get the dropped digit back (a per-marker decision: the same
+    // whatever the blocking; dropped on the device when nobody qualifies)
+    rc = eagle_dev_vara_i8_extend(ctx, Ms, cv, l1, b.nr, nrp, np, b.ld, st.nslices, st.ws, ctx->d_vara + r0, ctx->stream);
+    if (rc) return rc;
+    st.ph.mark(ctx->stream, PH_VARA);
+    // a-posteriori certificate: markers the digit bounds cannot settle are re-evaluated by the fp64 kernel, so that
+    // which(tsq == max(tsq))[1] on the returned arrays is the marker the fp64 scan selects (find_qtl.R:71-83).  One resident
+    // block on one device: bound, selection and re-evaluation right here.  Marker blocks / device shards: only the
+    // per-marker bounds now; selection against the global lower bound after the last block (scan_certify_global).
+    if (st.plan.bounds_flow)
+        return eagle_dev_cert_bounds(ctx, b.nr, nrp, np, cv, l1, st.nslices, st.ws, ctx->d_vara + r0, ctx->d_bound + r0, ctx->stream);
+    rc = eagle_dev_scan_certify(ctx, b.image, b.nr, nrp, np, b.ld, cv, l1, st.nslices, st.ws, st.Wu, ctx->d_a + r0, ctx->d_vara + r0, st.cert, ctx->stream);
+    if (!rc) rc = eagle_dev_cert_accumulate(ctx, st.cert, st.cert_totals, ctx->stream);
+    return rc;
+}
+// ... and in fp64.
+static int scan_block_f64(eagle_ctx* ctx, ScanState& st, const MarkerBlock& b, long nrp) {
+    int rc = eagle_dev_gemv_i8(ctx, b.image, nrp, st.np, b.ld, st.v, 1.0, ctx->d_a + b.r0, ctx->stream);
+    if (rc) return rc;
+    st.ph.mark(ctx->stream, PH_PREPARE);
+    rc = eagle_dev_vara_f64(ctx, b.image, nrp, st.np, b.ld, st.Wu, ctx->d_vara + b.r0, ctx->stream);
+    if (!rc) st.ph.mark(ctx->stream, PH_VARA);
+    return rc;
+}
+static MarkerBlocks scan_marker_blocks(const ScanArgs& A, const ScanShare& D, const ScanState& st, ChunkRing* ring, bool full_chunks) {
+    return MarkerBlocks{A.file, D.m0, st.Lr, A.n, st.np, st.Lc, A.mem_gb, st.g, st.plan.streamed ? ring : nullptr, full_chunks};
+}
+// The block loop: one pass per marker block -- the whole shard when it is resident, else full chunks of Lc rows read back from the file.
+static int scan_blocks(eagle_ctx* ctx, const ScanArgs& A, const ScanShare& D, ScanState& st) {
+    const bool streamed = st.plan.streamed;
+    if (streamed && !A.quiet) say(ctx, " Mt.ascii streamed through HBM in blocks of %ld markers", st.Lc);
+    MarkerBlocks w = scan_marker_blocks(A, D, st, &st.ring, true);
+    while (w.more()) {
+        MarkerBlock b;
+        int rc = w.load(ctx, &b);
+        if (rc) return rc;
+        if (streamed) st.ph.mark(ctx->stream, PH_LOADWAIT);
+        const long nrp = streamed ? st.Lc : eagle_pad(b.nr);
+        rc = st.plan.use_i8 ? scan_block_i8(ctx, A.n, st, b, nrp, w.slot()) : scan_block_f64(ctx, st, b, nrp);
+        if (rc) return rc;
+        if (st.plan.use_i8) st.ph.mark(ctx->stream, PH_CERT);
+        if ((rc = w.computed(ctx))) return rc;
+    }
+    w.finish(ctx);
+    return EAGLE_OK;
+}
+
+// The global certification of a scan whose bounds flow (plan.bounds_flow): such a scan is certified against ONE lower bound of the
+// maximum over every block of every device, so that the candidates, and with them every returned bit, are those of the one-block
+// scan of the whole file (the per-marker bounds of all blocks stay: 8 bytes per marker).
+// First this shard's lower bound of the maximum tsq and its markers over the tight threshold: the maximum / the sum over the devices
+// (scan_once's arrival) decide for all of them.
+static int scan_shard_bound(eagle_ctx* ctx, ScanState& st, eagle_cert_info* mine) {
+    int rc = eagle_dev_cert_lb_b(ctx, st.Lr, ctx->d_a, ctx->d_vara, ctx->d_bound, st.cert, st.ws, ctx->stream);
+    if (rc) return rc;
+    hipError_t e = hipMemcpyAsync(mine, st.cert, sizeof *mine, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    return e != hipSuccess ? eagle_fail_hip(ctx, e, "lower bound of the shard's maximum") : EAGLE_OK;
+}
+// More candidates than the re-evaluation buffer holds (degenerate operands): all of the shard in fp64 (on the fp64 products, should W
+// have come from the int8 engine).  A streamed shard is read once more, through a second ring that borrows the first one's buffers.
+static int scan_redo_f64(eagle_ctx* ctx, const ScanArgs& A, const ScanShare& D, ScanState& st) {
+    int rc = eagle_w8_redo_f64(ctx, st.np, ctx->stream);
+    if (rc) return rc;
+    ChunkRing again;
+    if (st.plan.streamed) {
+        if ((rc = again.init(ctx))) return rc;
+        again.buf[0] = st.ring.buf[0]; again.buf[1] = st.ring.buf[1];
+    }
+    MarkerBlocks w = scan_marker_blocks(A, D, st, &again, false);
+    while (w.more()) {
+        MarkerBlock b;
+        if ((rc = w.load(ctx, &b))) return rc;
+        if ((rc = eagle_dev_vara_f64(ctx, b.image, eagle_pad(b.nr), st.np, b.ld, st.Wu, ctx->d_vara + b.r0, ctx->stream))) return rc;
+        if ((rc = w.computed(ctx))) return rc;
+    }
+    w.finish(ctx);
+    return EAGLE_OK;
+}
+// The fp64 re-evaluation of the cnt candidates.  Streamed: only the candidates' rows are read back from the file (its 2-bit sidecar
+// when there is one): typically one or two.
+static int scan_reevaluate(eagle_ctx* ctx, const ScanArgs& A, const ScanShare& D, ScanState& st, long cnt) {
+    const long np = st.np;
+    if (!st.plan.streamed) return eagle_dev_cert_reevaluate(ctx, st.g->dev, st.g->ld, np, st.Wu, ctx->d_vara, st.cert, ctx->stream);
+    int rc = EAGLE_OK;
+    std::vector<long> idx((size_t)cnt);
+    int8_t* rows = eagle_cert_rows(st.cert);
+    hipError_t e = hipMemcpyAsync(idx.data(), eagle_cert_indices(st.cert), sizeof(long) * (size_t)cnt, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(rows, 0, (size_t)((cnt + 127) / 128 * 128) * (size_t)np, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) rc = eagle_fail_hip(ctx, e, "candidate list");
+    std::vector<RowRun> runs((size_t)cnt);
+    for (long c = 0; c < cnt; c++) runs[(size_t)c] = {D.m0 + idx[(size_t)c], 1};
+    if (!rc) rc = eagle_load_rows(ctx, A.file, runs, 0, A.n, rows, np, A.mem_gb, 1);
+    if (!rc) rc = eagle_dev_cert_reevaluate(ctx, nullptr, np, np, st.Wu, ctx->d_vara, st.cert, ctx->stream);
+    return rc;
+}
+// Then, against the global lower bound glb: selection of this shard's candidates, their re-evaluation (or the redo), the counters.
+static int scan_certify_global(eagle_ctx* ctx, const ScanArgs& A, const ScanShare& D, ScanState& st, double glb) {
+    eagle_cert_info hd;
+    int rc = eagle_dev_cert_select_b(ctx, st.Lr, ctx->d_a, ctx->d_vara, ctx->d_bound, st.cert, glb, st.over_tight_all, st.ws, ctx->stream);
+    if (rc) return rc;
+    hipError_t e = hipMemcpyAsync(&hd, st.cert, sizeof hd, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return eagle_fail_hip(ctx, e, "candidate count");
+    if (hd.overflow) rc = scan_redo_f64(ctx, A, D, st);
+    else if (hd.reevaluated > 0) rc = scan_reevaluate(ctx, A, D, st, hd.reevaluated);
+    if (!rc) rc = eagle_dev_cert_accumulate(ctx, st.cert, st.cert_totals, ctx->stream);
+    if (!rc) st.ph.mark(ctx->stream, PH_CERT);
+    return rc;
+}
+
+// Publish: the selected markers zeroed, the results on the host, the figures of the eagle_last_* getters, the arena slot of S.
+static int scan_publish(eagle_ctx* ctx, const ScanArgs& A, const ScanShare& D, ScanState& st) {
+    const long Lr = st.Lr, m0 = D.m0;
+    DevBuf dsel;
     std::vector<long> in_range;
-    for (long r : sel) if (r >= m0 && r < m1) in_range.push_back(r - m0);
+    for (long r : A.sel) if (r >= m0 && r < D.m1) in_range.push_back(r - m0);
     if (!in_range.empty()) {  // :79-84: a zeroed marker row gives a = 0 and vara = 0 exactly
         HIPCHK(ctx, dsel.alloc(sizeof(long) * in_range.size()));
         HIPCHK(ctx, hipMemcpyAsync(dsel.p, in_range.data(), sizeof(long) * in_range.size(), hipMemcpyHostToDevice, ctx->stream));
-        rc = eagle_dev_zero_rows(ctx, ctx->d_a, ctx->d_vara, Lr, dsel.as<long>(), (long)in_range.size(), 0, ctx->stream);
+        const int rc = eagle_dev_zero_rows(ctx, ctx->d_a, ctx->d_vara, Lr, dsel.as<long>(), (long)in_range.size(), 0, ctx->stream);
         if (rc) return rc;
     }
     ctx->scan_L = Lr;
     ctx->scan_first = m0;
     long totals[4] = {0, 0, 0, 0};
     if (Lr > 0) {
-        HIPCHK(ctx, hipMemcpyAsync(a_out + m0, ctx->d_a, sizeof(double) * (size_t)Lr, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(vara_out + m0, ctx->d_vara, sizeof(double) * (size_t)Lr, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(A.a_out + m0, ctx->d_a, sizeof(double) * (size_t)Lr, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(A.vara_out + m0, ctx->d_vara, sizeof(double) * (size_t)Lr, hipMemcpyDeviceToHost, ctx->stream));
     }
-    HIPCHK(ctx, hipMemcpyAsync(totals, cert_totals, sizeof totals, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(totals, st.cert_totals, sizeof totals, hipMemcpyDeviceToHost, ctx->stream));
     VaraHdr vh = {};   // head of the digit workspace
-    if (use_i8 && Lr > 0) HIPCHK(ctx, hipMemcpyAsync(&vh, ws, sizeof vh, hipMemcpyDeviceToHost, ctx->stream));
-    ph.mark(ctx->stream, PH_D2H);
+    if (st.plan.use_i8 && Lr > 0) HIPCHK(ctx, hipMemcpyAsync(&vh, st.ws, sizeof vh, hipMemcpyDeviceToHost, ctx->stream));
+    st.ph.mark(ctx->stream, PH_D2H);
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     ctx->cert_reevaluated = totals[0]; ctx->cert_flagged = totals[1]; ctx->cert_fell_back = totals[2] != 0;
     ctx->scan_digits_used = vh.S; ctx->scan_digits_cut = vh.S_sliced; ctx->scan_specH = vh.specH;
     ctx->scan_budget_used = vh.budget; ctx->scan_bound_level = vh.level; ctx->scan_w_err = vh.wErr;
     // (one resident block counted on the device; blocks / shards: the sum the devices exchanged)
-    ctx->cert_over_tight = bounds_flow ? over_tight_all : totals[3];
+    ctx->cert_over_tight = st.plan.bounds_flow ? st.over_tight_all : totals[3];
     ctx->scan_budget_enforced = ctx->cert_over_tight > eagle_cert_tight_max() ? vh.budget_loose : vh.budget;
     // a scan that took a digit off under the spectral bound and then had to redo a block in fp64: markers of this data set sit
     // outside what the bound covers -- this context keeps the worst-case digit count from now on (eagle_set_scan_budget re-arms)
     if (ctx->cert_fell_back && vh.specH > 0.0) ctx->spectral_off = true;
-    ph.sum(ctx->scan_phase_ms);
-    ctx->scan_blocks = streamed ? ring.k : 1;
-    ctx->scan_host_setup_s = t_setup - t0;
-    ctx->scan_range_wall_s = now_s() - t0;
-    if (Lr > 0) sc.commit(ctx, Sa, n, np);
+    st.ph.sum(ctx->scan_phase_ms);
+    ctx->scan_blocks = st.plan.streamed ? st.ring.k : 1;
+    ctx->scan_host_setup_s = st.t_setup - st.t0;
+    ctx->scan_range_wall_s = now_s() - st.t0;
+    if (Lr > 0) ctx->scache.commit(ctx, st.Sa, A.n, st.np);
     return EAGLE_OK;
+}
+
+// The scan of the markers [m0, m1) of Mt.ascii on ctx's device: a, vara into ctx->d_a / d_vara (and the host ranges
+// a_out[m0..m1), vara_out[m0..m1)).  Every device passes the same rendezvous in the same order, failed or not: every arrival of the
+// call stands in this function (plan.arrivals of them), and a stage never meets anybody.
+// This is ONE attempt (scan_range, below, makes at most two).  pol: the switches of the cached S as read for this call; *redo: S_NOTHING,
+// or how the verification settled at the END of the scan found another S than the one it ran on.
+// s_trusted: the device copy of S was uploaded from this very caller matrix a moment ago (the second attempt after a deferred
+// verification found another S): no verification this time
+static int scan_once(eagle_ctx* ctx, const ScanArgs& A, const ScanShare& D, bool s_trusted, const SPolicy& pol, SOutcome* redo) {
+    ScanState st;
+    st.Lr = D.m1 - D.m0;
+    st.np = eagle_pad(A.n);
+    st.Lp = eagle_pad(st.Lr > 0 ? st.Lr : 1);
+    st.sq = sizeof(double) * (size_t)st.np * st.np;
+    st.nslices = ctx->scan_slices | (ctx->scan_stochastic ? EAGLE_SLICES_STOCHASTIC : 0);
+    int rc = EAGLE_OK;
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) rc = eagle_fail_hip(ctx, e, "hipSetDevice");
+    bool streamed = false;
+    if (!rc && st.Lr > 0) rc = scan_residency(ctx, A, D, st, &streamed);
+    st.plan = scan_plan(ctx->scan_mode, st.np, D.nd, D.rccl != nullptr, D.rv != nullptr, A.w_direct, eagle_w8_wanted(ctx, st.np), streamed);
+    const ScanPlan& P = st.plan;
+    if (!scan_arrive(ctx, D.rv, &rc, streamed ? 1.0 : 0.0)) return rc;
+
+    SCache& sc = ctx->scache;   // the S of the last call, kept for this one
+    struct Left { SCache& c; ~Left() { c.leave(); } } left{sc};   // (its helper thread is joined on every way out)
+    st.t0 = now_s();
+    rc = scan_setup(ctx, A, D, st, s_trusted, pol);
+    st.t_setup = now_s();
+    double t1 = 0;
+    if (timing_on() && !rc) { (void)hipStreamSynchronize(ctx->stream); t1 = now_s(); }
+
+    if (P.w != W_INT8) { ctx->w8_active = false; ctx->w8_info = W8Info(); ctx->w8_info.declined = 7; }   // (only that route reports on the engine)
+    if (P.w == W_SHARED) {
+        if (!rc) rc = scan_w_shared_rows(ctx, A, D, st);
+        if (!scan_arrive(ctx, D.rv, &rc, 0.0)) return rc;
+        rc = scan_w_shared_gather(ctx, D, st);
+    } else if (!rc) {
+        rc = P.w == W_READY ? scan_w_ready(ctx, st) : P.w == W_INT8 ? scan_w_int8(ctx, A, st, pol) : scan_w_fp64(ctx, A, st);
+    }
+    if (!rc) rc = scan_verify_s(ctx, A, st);
+    if (!rc) st.ph.mark(ctx->stream, PH_W);
+
+    if (!rc) rc = scan_blocks(ctx, A, D, st);
+
+    if (P.bounds_flow) {
+        eagle_cert_info mine = {};   // (an empty shard: lower bound 0, nothing over the tight threshold)
+        if (!rc && st.Lr > 0) rc = scan_shard_bound(ctx, st, &mine);
+        if (!scan_arrive(ctx, D.rv, &rc, mine.lower_bound, (long)mine.over_tight)) return rc;
+        const double glb = D.rv ? D.rv->vmax : mine.lower_bound;
+        st.over_tight_all = D.rv ? D.rv->vsum : (long)mine.over_tight;
+        if (st.Lr > 0) rc = scan_certify_global(ctx, A, D, st, glb);
+    }
+
+    SOutcome settled;
+    rc = sc.settle(ctx, rc, &settled);   // the deferred outcome of the verification of the cached S
+    if (!rc && (settled == S_OTHER_ON_DEVICE || settled == S_OTHER_FORGOTTEN)) { *redo = settled; return EAGLE_OK; }   // ran on the wrong operand: once more (scan_range)
+    if (timing_on() && !rc) {
+        (void)hipStreamSynchronize(ctx->stream);
+        fprintf(stderr, "[eaglehip] scan n=%ld markers [%ld, %ld) of %ld on device %d%s: alloc+upload %.1f ms, device compute %.1f ms\n", A.n, D.m0, D.m1, A.L,
+                ctx->device, streamed ? " (streamed)" : "", (t1 - st.t0) * 1e3, (now_s() - t1) * 1e3);
+    }
+    return rc ? rc : scan_publish(ctx, A, D, st);
 }
 // The scan, and when its deferred verification finds that the cached S it ran on was not the caller's, a second time on the caller's:
 // s_trusted when that S is on the device already (the scratch copy has become the cached one), else with an upload.  The second attempt
 // verifies nothing (s_plan), so there is no third.
-static int scan_range(eagle_ctx* ctx, const char* f_name_ascii, long L, long n, long m0, long m1, const std::vector<long>& sel,
-                      const double* inv_MMt_sqrt, const double* dim_reduced_vara, const double* a, double max_memory_in_Gbytes, int quiet,
-                      double* a_out, double* vara_out, int k, int nd, Rendezvous* rv, RcclState* rccl, bool w_direct = false, bool s_trusted = false) {
+static int scan_range(eagle_ctx* ctx, const ScanArgs& A, const ScanShare& D) {
     const SPolicy pol = scache_policy();
     SOutcome redo = S_NOTHING;
-    auto attempt = [&](bool trusted) {
-        return scan_once(ctx, f_name_ascii, L, n, m0, m1, sel, inv_MMt_sqrt, dim_reduced_vara, a, max_memory_in_Gbytes, quiet, a_out, vara_out, k, nd, rv,
-                         rccl, w_direct, trusted, pol, &redo);
-    };
-    const int rc = attempt(s_trusted);
-    return !rc && redo != S_NOTHING ? attempt(redo == S_OTHER_ON_DEVICE) : rc;
+    const int rc = scan_once(ctx, A, D, false, pol, &redo);
+    return !rc && redo != S_NOTHING ? scan_once(ctx, A, D, redo == S_OTHER_ON_DEVICE, pol, &redo) : rc;
 }
 
 // After a scan on several devices: the lead reports the certificate counters of all of them, and the spectral_off latch of any is everybody's.
@@ -1717,9 +1812,9 @@ extern "C" int eagle_calculate_a_and_vara(eagle_ctx* ctx, const char* f_name_asc
     RcclState* rccl = (RcclState*)ctx->rccl;
     if (rccl && rccl->dead) rccl = nullptr;   // aborted in an earlier call: W on every device, host-staged exchange
     const double t_call = now_s();
+    const ScanArgs args = {f_name_ascii, L, n, sel, inv_MMt_sqrt, dim_reduced_vara, a, max_memory_in_Gbytes, quiet, a_out, vara_out, false};
     rc = run_on_devices(ctx, [&](int k, eagle_ctx* c) -> int {
-        return scan_range(c, f_name_ascii, L, n, edge[k], edge[k + 1], sel, inv_MMt_sqrt, dim_reduced_vara, a, max_memory_in_Gbytes, quiet,
-                          a_out, vara_out, k, nd, nd > 1 || rccl ? &rv : nullptr, rccl);
+        return scan_range(c, args, ScanShare{edge[k], edge[k + 1], k, nd, nd > 1 || rccl ? &rv : nullptr, rccl});
     });
     ctx->scan_call_wall_s = now_s() - t_call;
     if (rc) return rc;
@@ -1746,9 +1841,9 @@ extern "C" int eagle_scan_with_W(eagle_ctx* ctx, const char* f_name_ascii, const
     split_markers(L, nd, edge);
     Rendezvous rv;
     rv.n = nd;
+    const ScanArgs args = {f_name_ascii, L, n, sel, W, nullptr, v, max_memory_in_Gbytes, quiet, a_out, vara_out, true};
     rc = run_on_devices(ctx, [&](int k, eagle_ctx* c) -> int {
-        return scan_range(c, f_name_ascii, L, n, edge[k], edge[k + 1], sel, W, nullptr, v, max_memory_in_Gbytes, quiet, a_out, vara_out, k, nd,
-                          nd > 1 ? &rv : nullptr, nullptr, true);
+        return scan_range(c, args, ScanShare{edge[k], edge[k + 1], k, nd, nd > 1 ? &rv : nullptr, nullptr});
     });
     if (rc) return rc;
     merge_peer_scans(ctx);
@@ -1941,19 +2036,15 @@ static int reduced_a_range(eagle_ctx* ctx, const char* f_name_ascii, long n, lon
     if ((rc = upload_vec(ctx, y, n, np, yv.as<double>()))) return rc;
     rc = eagle_dev_colgemv(ctx, Pa.as<double>(), n, np, yv.as<double>(), py.as<double>(), ctx->stream);  // :82
     if (rc) return rc;
-    for (long r0 = 0; r0 < Lr; r0 += Lc) {  // :83-84, one pass per marker block (the whole shard when resident)
-        const long nr = std::min(Lc, Lr - r0), nrp = eagle_pad(nr);
-        int8_t* tile = nullptr;
-        if (streamed) {
-            rc = ring.load(ctx, f_name_ascii, m0 + r0, nr, 0, n, np, (size_t)nrp * np, max_memory_in_Gbytes, host_threads(), &tile);
-            if (rc) return rc;
-        }
-        rc = eagle_dev_gemv_i8(ctx, streamed ? tile : g->dev, nrp, np, streamed ? np : g->ld, py.as<double>(), varG,
-                               out.as<double>() + r0, ctx->stream);
+    MarkerBlocks w{f_name_ascii, m0, Lr, n, np, Lc, max_memory_in_Gbytes, g, streamed ? &ring : nullptr, false};
+    while (w.more()) {  // :83-84, one pass per marker block (the whole shard when resident)
+        MarkerBlock b;
+        if ((rc = w.load(ctx, &b))) return rc;
+        rc = eagle_dev_gemv_i8(ctx, b.image, eagle_pad(b.nr), np, b.ld, py.as<double>(), varG, out.as<double>() + b.r0, ctx->stream);
         if (rc) return rc;
-        if (streamed && (rc = ring.computed(ctx))) return rc;
+        if ((rc = w.computed(ctx))) return rc;
     }
-    if (streamed) ring.finish(ctx);
+    w.finish(ctx);
     std::vector<long> in_range;
     for (long r : sel) if (r >= m0 && r < m1) in_range.push_back(r - m0);
     if (!in_range.empty()) {  // :74-78

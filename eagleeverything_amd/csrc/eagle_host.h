@@ -27,7 +27,7 @@
 // ------------------------------------------------------------------------------------------------
 enum : size_t {
     EAGLE_SCR_SYM = 0,             // int[2]: k_sym_check's verdict on S and V                      (eagle_kernels.hip)
-    EAGLE_SCR_CERT_TOTALS = 256,   // long[4]: certification counters summed over marker blocks      (eagle_api.cpp scan_range)
+    EAGLE_SCR_CERT_TOTALS = 256,   // long[4]: certification counters summed over marker blocks      (eagle_api.cpp scan_once)
     EAGLE_SCR_INGEST = 512,        // u64[2]: first third-allele / first missing position (ped), missing count (bed); double: trace  (eagle_ingest.cpp, eagle_linalg.cpp)
     EAGLE_SCR_LOADER_BAD = 1024,   // int: invalid characters / codes seen by the tile loaders       (eagle_load.cpp, any stream)
     EAGLE_SCR_SCACHE_FLAG = 2048,  // int: cached S differs from the caller's                        (eagle_api.cpp, load stream)
@@ -232,6 +232,39 @@ static inline SOutcome s_outcome(SVerify how, bool differs) {
 struct SSlot { unsigned long gen = 0; size_t off = 0; long n = 0, np = 0; };   // n = 0: none
 static inline bool s_slot_valid(const SSlot& s, unsigned long gen, size_t off, long n, long np) {
     return s.n > 0 && s.gen == gen && s.off == off && s.n == n && s.np == np;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The modes of one scan attempt on one device (scan_once, eagle_api.cpp), decided here from plain values and only read by the stages.
+// scan_use_i8 is known before the file is looked at (the residency step sizes its arena estimate with it); scan_plan is made once
+// the residency step has said whether the shard is streamed.  No pointer, no device: tests/host/test_host.cpp enumerates all of it.
+//   use_i8       the digit-slice scan on the int8 MFMA: the context's mode, and 64 * 512 * np below 2^31 (the kernel's int32 sums).
+//   w            where W comes from, exactly one route:
+//                  W_READY    eagle_scan_with_W handed W and v over: only the fold;
+//                  W_SHARED   fp64 products, 1/nd of W's rows per device + ONE all-gather -- needs device collectives and np / 128 rows
+//                             blocks that divide by nd, and is never taken where the int8 engine would run: those products cost half
+//                             as much and are a deterministic function of S and V, so every device forms them itself;
+//                  W_INT8     the int8 engine (which may decline at run time and then runs the fp64 products: the route's business);
+//                  W_FP64     the fp64 products, pipelined under V's upload.
+//   bounds_flow  a digit-slice scan that does not see all its markers at once -- marker blocks of a streamed file, shards of several
+//                devices -- keeps per-marker bounds and certifies against ONE lower bound of the maximum after the last block.
+//   arrivals     rendezvous rounds of the call (0 without a rendezvous): one after residency, one before the all-gather, one with the
+//                shard's lower bound.  Devices of one call may differ in `streamed` -- the count must not, and does not: with a
+//                rendezvous bounds_flow is use_i8.
+// ------------------------------------------------------------------------------------------------
+enum WRoute { W_READY, W_SHARED, W_INT8, W_FP64 };
+struct ScanPlan { bool use_i8 = false; WRoute w = W_FP64; bool streamed = false, bounds_flow = false; int arrivals = 0; };
+static inline bool scan_use_i8(int scan_mode, long np) { return scan_mode == 1 && 64.0 * 512.0 * (double)np < 2147483648.0; }
+// rccl: live device collectives; rv: the call has a rendezvous; w8_wanted: eagle_w8_wanted's answer for np
+static inline ScanPlan scan_plan(int scan_mode, long np, int nd, bool rccl, bool rv, bool w_direct, bool w8_wanted, bool streamed) {
+    ScanPlan p;
+    p.use_i8 = scan_use_i8(scan_mode, np);
+    const bool share_w = !w_direct && rccl && (np / 128) % nd == 0 && !(p.use_i8 && w8_wanted);   // the same answer on every device
+    p.w = w_direct ? W_READY : share_w ? W_SHARED : w8_wanted ? W_INT8 : W_FP64;
+    p.streamed = streamed;
+    p.bounds_flow = p.use_i8 && (streamed || rv);
+    p.arrivals = rv ? 1 + (share_w ? 1 : 0) + (p.bounds_flow ? 1 : 0) : 0;
+    return p;
 }
 
 // What the int8 W engine keeps WITH S (eagle_w8.hip): the digit image of S, its row statistics and W8Stats, S 1 and S^T 1 -- everything

@@ -116,7 +116,7 @@ int eagle_dev_line_scores(eagle_ctx* ctx, const int8_t* img, long rows, long col
 #ifdef __cplusplus
 }
 #include "eagle_host.h"
-// Head of the digit workspace of the int8 scan (eagle_i8mfma.hip): written on the device, copied back by scan_range for the figures of
+// Head of the digit workspace of the int8 scan (eagle_i8mfma.hip): written on the device, copied back by scan_publish for the figures of
 // eagle_last_scan_digits / _budget / _enforced.
 struct VaraHdr {
     double maxabs_off;  // max |Wu[j][k]|, j != k

@@ -1172,7 +1172,7 @@ static int gemm_f64_upper(eagle_ctx* ctx, const double* A, const double* B, doub
 }
 
 // W = S (V S) in three steps, so that the caller can overlap the PCIe upload of V with the first product
-// (eagle_api.cpp scan_range: V arrives in row blocks on the loader stream; the device copy of S is already there):
+// (eagle_api.cpp scan_w_fp64: V arrives in row blocks on the loader stream; the device copy of S is already there):
 //   _begin   v = S a_hat (needs Sa, a_hat only).
 //   _vrows   X[r0, r1) = Va[r0, r1) * Sa for one block of rows of Va's image (r0, r1 multiples of 128) into tmp -- needs only
 //            those rows of Va.  For SYMMETRIC operands (every Eagle run: MMt^-1/2 and a variance matrix) X = V S.

@@ -74,18 +74,19 @@ int eagle_device_info(eagle_ctx* ctx, char* arch_out, int arch_len, int* cu_coun
 /* vara kernel: 1 (default) = exact int8 digit slices of W on v_mfma_i32_32x32x32_i8, 0 = fp64 MFMA
  * (v_mfma_f64_16x16x4_f64; also taken automatically when n is too large for the int32 tile sums).
  * eagle_set_scan_slices: S = 1..8 base-256 digits of the off-diagonal part of W, or 0 (default) = chosen per call:
- * the smallest S in 3..7 whose worst-case bound is below the budget (eagle_set_scan_budget, default 5e-7) times 0.5 * sum_k |W_kk| -- half
- * of the 1e-6 relative tolerance of this path, relative to the smallest diagonal term a marker can have (at least half of its genotypes are
+ * the smallest S in 3..7 whose worst-case bound is below the budget (eagle_set_scan_budget; by default 1e-7 first, 5e-7 as the fallback:
+ * eagle_last_scan_budget) times 0.5 * sum_k |W_kk| -- at most half of the 1e-6 relative tolerance of this path, relative to the smallest diagonal term a marker can have (at least half of its genotypes are
  * non-zero in the g-1 coding); measured errors are ~1000x below the bound.  The diagonal term
  * sum_k m_ik^2 W_kk is evaluated in fp64; every vara_i then differs from the exact m_i^T W m_i by at most
  * (sum_j |m_ij|)^2 * 2^(e+1-8S), max_{j!=k} |W_jk + W_kj| < 2^e (or < 1.96 * 2^e: the exponent is lowered by one when the largest
  * entry's mantissa leaves the balanced digits room), plus fp64 rounding of an n-term and an S-term sum. */
 int eagle_set_scan_mode(eagle_ctx* ctx, int mode);
 int eagle_set_scan_slices(eagle_ctx* ctx, int nslices);
-/* Round 3.  The relative digit budget of the int8 scan, 1e-12 .. 5e-7 (default 5e-7 = half of the path's 1e-6 tolerance; rounds 1-2
- * used 1e-7, which this call restores).  It enters twice: the automatic digit count is the smallest S whose bound keeps a typical
- * marker inside the budget, and the certificate sends every marker whose OWN bound exceeds 1.8 x budget (0.9e-6 by default) to the
- * fp64 kernel.  With the automatic count the library also tries ONE DIGIT FEWER than the worst-case bound asks for, under a spectral
+/* Round 3.  The relative digit budget of the int8 scan, 1e-12 .. 5e-7 (5e-7 = half of the path's 1e-6 tolerance).  A context whose
+ * budget was never set tries 1e-7 first and falls back to 5e-7 (eagle_last_scan_budget, below); this call makes its argument the only
+ * budget, 0 restores that default policy.  It enters twice: the automatic digit count is the smallest S whose bound keeps a typical
+ * marker inside the budget, and the certificate sends every marker whose OWN bound exceeds 1.8 x the budget in force (1.8e-7 under the
+ * tight default, 0.9e-6 under the fallback) to the fp64 kernel.  With the automatic count the library also tries ONE DIGIT FEWER than the worst-case bound asks for, under a spectral
  * bound of the truncation error: |error_i| <= (u/2)(||Ds||_2 + (n_pad-1)/2) sum_j m'_ij^2, Ds = the symmetrised last digit of W,
  * ||Ds||_2^2 <= max row sum of |Ds Ds| from an exact int8 MFMA Gram product, or, one level down, max_j (Ds Ds)_jj + ||offdiag(Ds Ds)||_2
  * with the off-diagonal part bounded the same way (csrc/eagle_i8mfma.hip, k_spectral_decide) -- rigorous, deterministic, a function of

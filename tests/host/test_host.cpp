@@ -288,6 +288,57 @@ static void test_scache_slot() {
     }
 }
 
+// ---- the modes of a scan attempt: scan_use_i8, scan_plan ----------------------------------------------------------------
+// The expectations are written out from the rule (for the route: first row that applies), not taken from scan_plan.
+struct ScanWant { bool use_i8; WRoute w; bool bounds_flow; int arrivals; };
+static ScanWant scan_want(int scan_mode, long np, int nd, bool rccl, bool rv, bool w_direct, bool w8_wanted, bool streamed) {
+    // the int8 scan: the context's mode, while 64 * 512 * np stays below 2^31
+    const bool i8 = scan_mode == 1 && np * 32768L < 2147483648L;
+    WRoute w;
+    if (w_direct) w = W_READY;                                                       // W handed over ready
+    else if (rccl && (np / 128) % nd == 0 && !(i8 && w8_wanted)) w = W_SHARED;       // rows shared + all-gather
+    else if (w8_wanted) w = W_INT8;                                                  // the int8 engine
+    else w = W_FP64;                                                                 // fp64, pipelined under V's upload
+    const bool bounds_flow = i8 && (streamed || rv);
+    int arrivals = 0;
+    if (rv) {
+        arrivals = 1;                                // after residency
+        if (w == W_SHARED) arrivals++;               // before the all-gather
+        if (bounds_flow) arrivals++;                 // with the shard's lower bound
+    }
+    return {i8, w, bounds_flow, arrivals};
+}
+static void test_scan_plan() {
+    CHECK(scan_use_i8(1, 65408) && !scan_use_i8(1, 65536) && !scan_use_i8(0, 128));   // the largest padded size that takes the int8 scan, the first that does not
+    long cases = 0, seen[4] = {0, 0, 0, 0};
+    for (int scan_mode : {0, 1})
+        for (long np : {128L, 384L, 65408L, 65536L})
+            for (int nd : {1, 2, 3, 4})
+                for (int bits = 0; bits < 32; bits++) {
+                    const bool rccl = (bits & 1) != 0, rv = (bits & 2) != 0, w_direct = (bits & 4) != 0, w8_wanted = (bits & 8) != 0, streamed = (bits & 16) != 0;
+                    const ScanPlan got = scan_plan(scan_mode, np, nd, rccl, rv, w_direct, w8_wanted, streamed);
+                    const ScanWant want = scan_want(scan_mode, np, nd, rccl, rv, w_direct, w8_wanted, streamed);
+                    CHECK(got.use_i8 == want.use_i8 && got.w == want.w && got.bounds_flow == want.bounds_flow && got.arrivals == want.arrivals);
+                    CHECK(got.streamed == streamed && got.use_i8 == scan_use_i8(scan_mode, np));
+                    cases++;
+                    // the invariants, over the whole enumeration
+                    CHECK(got.w == W_READY || got.w == W_SHARED || got.w == W_INT8 || got.w == W_FP64);   // exactly one route
+                    seen[got.w]++;
+                    CHECK((got.w == W_READY) == w_direct);                          // sharing never comes with a ready W ...
+                    if (got.w == W_SHARED) CHECK(rccl && !(got.use_i8 && w8_wanted) && (np / 128) % nd == 0);   // ... nor where the int8 engine would run
+                    if (got.w == W_INT8) CHECK(w8_wanted && !w_direct);
+                    // devices of one call may differ in `streamed` (and an empty shard never streams): the arrivals must not
+                    const ScanPlan other = scan_plan(scan_mode, np, nd, rccl, rv, w_direct, w8_wanted, !streamed);
+                    CHECK(got.arrivals == other.arrivals && got.w == other.w && got.use_i8 == other.use_i8);
+                    if (rv) CHECK(got.bounds_flow == other.bounds_flow);
+                    if (!rv) CHECK(got.arrivals == 0);
+                    else CHECK(got.arrivals >= 1 && got.arrivals <= 3);
+                    if (!got.use_i8) CHECK(!got.bounds_flow);
+                }
+    CHECK(cases == 2L * 4 * 4 * 32);
+    for (long v : seen) CHECK(v > 0);      // every route occurs
+}
+
 int main(int argc, char** argv) {
     const std::string what = argc > 1 ? argv[1] : "all";
     if (what == "all" || what == "rendezvous") test_rendezvous();
@@ -295,6 +346,7 @@ int main(int argc, char** argv) {
     if (what == "all" || what == "text") test_text();
     if (what == "all" || what == "loader") test_loader_windows();
     if (what == "all" || what == "scache") { test_scache_rule(); test_scache_slot(); }
+    if (what == "all" || what == "plan") test_scan_plan();
     if (g_fail) { fprintf(stderr, "%d check(s) failed\n", g_fail); return 1; }
     printf("host checks passed (%s)\n", what.c_str());
     return 0;

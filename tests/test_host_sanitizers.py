@@ -2,7 +2,7 @@
 not exist on the target pool).
 
   * tests/host/test_host.cpp exercises the HIP-free host pieces of the product (csrc/eagle_host.h: Rendezvous, split_markers,
-    parse_selected_core, stream_chunk_rows_core, vara_tail_pieces, the rule of the scan's cached S, LineIndex + tokeniser) -- the very header libeaglehip.so
+    parse_selected_core, stream_chunk_rows_core, vara_tail_pieces, the rule of the scan's cached S, the plan of a scan's modes, LineIndex + tokeniser) -- the very header libeaglehip.so
     compiles -- under ASan + UBSan, and the Rendezvous cases under TSan.  The failure-injection case is ADVICE r2's deadlock:
     a device that fails right after leaving round k while a slow peer has not yet woken up from round k.
   * the C oracle (test infrastructure) is built with `make -C oracle asan` and run on a golden case in a child process.
