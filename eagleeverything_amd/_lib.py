@@ -128,6 +128,7 @@ SIGNATURES = {
     "eagle_fisher_2x2": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_long, c_dp]),
     "eagle_logistic": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, C.POINTER(C.c_int32), c_dp, C.c_int, c_dp, C.c_int, C.c_double, C.c_int,
                                  C.c_double, c_dp, C.POINTER(C.c_int32)]),
+    "eagle_admixture_em": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, C.c_int, C.c_int, c_dp, c_dp, C.c_double, c_dp]),
     "eagle_read_block": (C.c_int, [C.c_void_p, C.c_char_p, C.c_long, C.c_long, C.c_long, c_dp]),
     "eagle_calculateMMt": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double, C.c_int, c_dp, C.c_long, c_lp, C.c_int, c_dp]),
     "eagle_calculate_a_and_vara": (C.c_int, [C.c_void_p, C.c_char_p, c_dp, C.c_long, c_dp, c_dp, C.c_double, c_lp, c_dp,

@@ -144,6 +144,18 @@ def add_pcs(X, pca, k=None):
     return np.concatenate([X, pcs[:, :k]], axis=1)
 
 
+def add_ancestry(X, adm):
+    """X with the first K - 1 columns of r_api.Admixture()'s "Q" appended: ancestry fractions as fixed effects of AM, GWAS or Logistic,
+    the model-based twin of add_pcs.  The last column is left out: the rows of Q sum to 1, so it is collinear with the intercept.  X
+    and Q must hold the same individuals, in the order of the panel."""
+    X = np.asarray(X, dtype=np.float64)
+    X = X.reshape(-1, 1) if X.ndim == 1 else X
+    Q = np.asarray(adm["Q"], dtype=np.float64)
+    if Q.ndim != 2 or X.shape[0] != Q.shape[0]:
+        raise ValueError("add_ancestry: X holds %d individuals, Q %s" % (X.shape[0], Q.shape[:1]))
+    return np.concatenate([X, Q[:, :Q.shape[1] - 1]], axis=1)
+
+
 def _reshape(geno, indxNA, backend=None, device=0):
     """geno without the individuals indxNA: backend.reshape, reshape_geno writing the files for a backend without one, or for a
     caller that has no backend a view on `device`."""

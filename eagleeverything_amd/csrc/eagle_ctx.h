@@ -307,6 +307,17 @@ extern "C" int eagle_dev_fisher_2x2(eagle_ctx* ctx, const int32_t* tables, long 
 // stat[rows][4] = (gamma, se, score, loglik), info[rows][2] = (code, evaluations); firth = 0 (ML), 1 (Firth), 2 (fallback).
 extern "C" int eagle_dev_logistic(eagle_ctx* ctx, const int8_t* Mt8, long rows, long n, long ld, const double* X16, const uint8_t* valid_y,
                                   const double* beta0, int p, int firth, double tol, int max_iter, double* stat, int32_t* info, void* stream);
+// One EM step of the admixture model (eagle_admix.hip; include/eagle_hip.h section 1b''''v), device pointers throughout.  Q16: n16 x 16
+// and Fin / Fout: L16 x 16 fp64 (n16, L16 = n, L rounded up to 16), columns >= K and the rows beyond n / L zero.  _window: the rows
+// [row0, row0 + rows) of the image, row0 a multiple of 16 and rows one too unless the window ends the panel; llpart[L16 / 16] takes the
+// likelihood of every 16-marker tile, and with update Fout the new frequencies of the window's markers and part[S][n16][16] the Q
+// accumulators of the ranges of admix_range_plan (eagle_host.h).  _finish, once per pass: *ll_out = the sum of llpart, and with update
+// Qout = the new fractions.
+extern "C" int eagle_dev_admix_window(eagle_ctx* ctx, const int8_t* Mt8, long row0, long rows, long n, long L, long ld, int K, int update,
+                                      const double* Q16, const double* Fin, double* Fout, double* llpart, double* part, int S, long range_len,
+                                      void* stream);
+extern "C" int eagle_dev_admix_finish(eagle_ctx* ctx, long n, long L, int K, int update, const double* llpart, double* ll_out, const double* part,
+                                      int S, const double* Qin, double* Qout, void* stream);
 // The exact mixed-model test per marker (include/eagle_hip.h section 1d').  eagle_lmm.hip: rows of Z (ldz fp64 each, ldz >= n64) against the
 // staged image B16 (n64 x 16 fp64: U^T X, a zero column for z, U^T y) and lam64 (n64, +inf from n on), n64 = n rounded up to 64; idx:
 // count device longs or NULL = rows 0 .. count - 1  ->  stat[count][5], info[count][2].

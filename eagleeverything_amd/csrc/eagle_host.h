@@ -163,6 +163,27 @@ static inline RowWindows row_windows_cores(long rows, long held_max, long halo) 
     return {rows, held_max, held_max >= rows ? rows : held_max - 2 * halo, halo, halo, false};
 }
 
+// The marker ranges of the admixture step's Q kernel (include/eagle_hip.h section 1b''''v): ceil(n / 16) tiles of individuals do not
+// fill the card, so [0, L) is cut into S ranges of `len` markers (a multiple of 16; the last one is shorter), range s = [s len,
+// min(L, (s + 1) len)).  A function of (n, L) alone: the sums of a tile depend on it and on nothing else.  S aims at
+// ADMIX_PLAN_WAVES waves and keeps the partials buffer part[S][n16][16] fp64, n16 = n rounded up to 16, within admix_part_cap(n):
+// ADMIX_PART_BYTES, or one range's worth where that alone is more.
+#define ADMIX_PLAN_WAVES 2048L
+#define ADMIX_PART_BYTES (64L << 20)
+struct AdmixPlan { long S, len; };
+static inline long admix_part_cap(long n) {
+    const long one = (n + 15) / 16 * 16 * 16 * 8;
+    return one > ADMIX_PART_BYTES ? one : ADMIX_PART_BYTES;
+}
+static inline AdmixPlan admix_range_plan(long n, long L) {
+    const long tiles = (n + 15) / 16, mt = (L + 15) / 16, one = tiles * 16 * 16 * 8;
+    long want = (ADMIX_PLAN_WAVES + tiles - 1) / tiles;
+    want = std::min(want, std::max(1L, admix_part_cap(n) / one));
+    want = std::max(1L, std::min(want, mt));
+    const long len_t = (mt + want - 1) / want;               // 16-marker tiles per range
+    return {(mt + len_t - 1) / len_t, len_t * 16};
+}
+
 // Pieces per worker of an XCD's last, partly filled round of `tail` workers on 32 CUs (0 < tail < 32): the workers are cut along
 // their column-tile pairs into p equal pieces, the tail * p pieces run in ceil(tail * p / 32) rounds of 1/p worker-time each; p <=
 // min(npair, VARA_TAIL_PMAX) minimising that cost (p = 1: one whole worker-time for a round that may be 1/32 full; large p: tail/32).

@@ -1143,6 +1143,90 @@ extern "C" int eagle_logistic(eagle_ctx* ctx, const char* f_name_ascii_Mt, const
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// Admixture: EM steps of the ancestry model (include/eagle_hip.h section 1b''''v; the kernels are in eagle_admix.hip).
+// eagle_group_counts' routes, one pass over the image per step and one more for the likelihood of the result.  Q and F are staged once
+// per call as 16-column padded images, the steps alternate between two buffers of each, and nothing comes back before the last pass.
+// The streamed windows' cap (lines.stream_rows(): a multiple of 256) is a multiple of 16, which the kernels' tiles and ranges need.
+// ---------------------------------------------------------------------------------------------------------------
+extern "C" int eagle_admixture_em(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long dims[2], int K, int steps, double* Q, double* F,
+                                  double max_memory_in_Gbytes, double* loglik_out) {
+    auto fail = [&](const char* what) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "admixture_em: %s", what);
+        return qc_fail(ctx, EAGLE_ERR_ARG, msg);
+    };
+    if (!f_name_ascii_Mt || !dims || !Q || !F || !loglik_out) return fail("NULL argument");
+    const long n = dims[0], L = dims[1];
+    if (n <= 0 || L <= 0) return fail("dims must be positive");
+    if (n > 0x3fffffffL) return fail("more than 2^30 - 1 individuals");
+    if (K < 1 || K > EAGLE_ADMIX_KMAX) return fail("K outside [1, 16]");
+    if (steps < 0 || steps > 10000) return fail("steps outside [0, 10000]");
+    for (long i = 0; i < n; i++) {
+        double sum = 0.0;
+        for (int k = 0; k < K; k++) {
+            const double q = Q[(size_t)i * K + k];
+            if (!std::isfinite(q)) return fail("a non-finite Q entry");
+            if (q < 0.0) return fail("a negative Q entry");
+            sum += q;
+        }
+        if (!(fabs(sum - 1.0) <= 1e-9)) return fail("a Q row whose sum is off 1 by more than 1e-9");
+    }
+    for (size_t e = 0; e < (size_t)L * K; e++) {
+        if (!std::isfinite(F[e])) return fail("a non-finite F entry");
+        if (F[e] < EAGLE_ADMIX_EPS || F[e] > 1.0 - EAGLE_ADMIX_EPS) return fail("an F entry outside [eps, 1 - eps]");
+    }
+    if (!ctx) return fail("no context");
+
+    const long n16 = (n + 15) / 16 * 16, L16 = (L + 15) / 16 * 16;
+    const AdmixPlan plan = admix_range_plan(n, L);
+    std::vector<double> q16((size_t)n16 * 16, 0.0), f16((size_t)L16 * 16, 0.0);
+    for (long i = 0; i < n; i++)
+        for (int k = 0; k < K; k++) q16[(size_t)i * 16 + k] = Q[(size_t)i * K + k];
+    for (long m = 0; m < L; m++)
+        for (int k = 0; k < K; k++) f16[(size_t)m * 16 + k] = F[(size_t)m * K + k];
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t qb = sizeof(double) * q16.size(), fb = sizeof(double) * f16.size();
+    DevBuf dq[2], df[2], llpart, part, ll;
+    for (int b = 0; b < 2; b++) {
+        HIPCHK(ctx, dq[b].alloc(qb));
+        HIPCHK(ctx, df[b].alloc(fb));
+    }
+    HIPCHK(ctx, llpart.alloc(sizeof(double) * (size_t)(L16 / 16)));
+    HIPCHK(ctx, part.alloc(sizeof(double) * 16 * (size_t)plan.S * (size_t)n16));
+    HIPCHK(ctx, ll.alloc(sizeof(double) * ((size_t)steps + 1)));
+    HIPCHK(ctx, hipMemcpyAsync(dq[0].p, q16.data(), qb, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(df[0].p, f16.data(), fb, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(dq[1].p, 0, qb, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(df[1].p, 0, fb, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));                  // q16 and f16 are pageable host vectors
+    ImageLines lines;
+    int rc = lines.open(ctx, f_name_ascii_Mt, L, n, max_memory_in_Gbytes);
+    if (rc) return rc;
+    int cur = 0;
+    for (int t = 0; t <= steps; t++) {                               // pass t: the likelihood at the parameters entering step t, and the step
+        const int update = t < steps;
+        rc = lines.each(lines.disjoint(lines.stream_rows()), [&](const int8_t* img, long r0, long nr, long, long) {
+            return eagle_dev_admix_window(ctx, img, r0, nr, n, L, lines.ld(), K, update, dq[cur].as<double>(), df[cur].as<double>(),
+                                          df[cur ^ 1].as<double>(), llpart.as<double>(), part.as<double>(), (int)plan.S, plan.len, ctx->stream);
+        });
+        if (rc) return rc;
+        rc = eagle_dev_admix_finish(ctx, n, L, K, update, llpart.as<double>(), ll.as<double>() + t, part.as<double>(), (int)plan.S,
+                                    dq[cur].as<double>(), dq[cur ^ 1].as<double>(), ctx->stream);
+        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+        if (update) cur ^= 1;
+    }
+    HIPCHK(ctx, hipMemcpyAsync(q16.data(), dq[cur].p, qb, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(f16.data(), df[cur].p, fb, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(loglik_out, ll.p, sizeof(double) * ((size_t)steps + 1), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (long i = 0; i < n; i++)
+        for (int k = 0; k < K; k++) Q[(size_t)i * K + k] = q16[(size_t)i * 16 + k];
+    for (long m = 0; m < L; m++)
+        for (int k = 0; k < K; k++) F[(size_t)m * K + k] = f16[(size_t)m * 16 + k];
+    return EAGLE_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // kNN imputation of a .bed file (no counterpart in the reference; kernels in eagle_impute.hip)
 // ---------------------------------------------------------------------------------------------------------------
 extern "C" int eagle_knn_rows(eagle_ctx* ctx, const int32_t* ibs0, const int32_t* hethet, long n, int K, int32_t* nbr_out) {

@@ -2970,6 +2970,136 @@ def Logistic(geno, status, X=None, firth="fallback", tol=1e-10, max_iter=50, ava
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+# Admixture: model-based ancestry proportions (include/eagle_hip.h section 1b''''v; device: rcpp_api.admixture_em).
+# ---------------------------------------------------------------------------------------------------------------------------
+ADMIX_EPS, ADMIX_KMAX = rcpp_api.ADMIX_EPS, rcpp_api.ADMIX_KMAX
+
+
+def _admix_loglik(D, P, Pb):
+    """sum d ln p + (2 - d) ln pbar, a term with a zero factor being 0."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return float(np.sum(np.where(D > 0, D * np.log(P), 0.0) + np.where(D < 2, (2.0 - D) * np.log(Pb), 0.0)))
+
+
+def admixture_host(Mt8, Q, F, steps=1):
+    """rcpp_api.admixture_em restated in numpy: Mt8 = int8 (L, n) of -1 / 0 / +1 (marker-major), Q (n, K), F (L, K) -> (Q, F, loglik
+    (steps + 1)) by the rule of include/eagle_hip.h section 1b''''v.  Not bit-equal to the device (the order of the sums and log
+    differ); tests/admixture_truth.py holds both to 40-digit arithmetic."""
+    D = np.asarray(Mt8).T.astype(np.float64) + 1.0                     # (n, L) dosages
+    Q, F = np.array(Q, dtype=np.float64), np.array(F, dtype=np.float64)
+    twoL = 2.0 * D.shape[1]
+    ll = np.zeros(int(steps) + 1)
+    for t in range(int(steps) + 1):
+        Fb = 1.0 - F
+        P, Pb = Q @ F.T, Q @ Fb.T                                      # p-bar is its own sum
+        ll[t] = _admix_loglik(D, P, Pb)
+        if t == steps:
+            break
+        A, B = D / P, (2.0 - D) / Pb
+        sa, sb = F * (A.T @ Q), Fb * (B.T @ Q)
+        tot = sa + sb
+        with np.errstate(divide="ignore", invalid="ignore"):
+            Fn = np.where(tot > 0.0, sa / tot, F)
+        T = Q * (A @ F + B @ Fb)
+        Qn = np.maximum(T / twoL, ADMIX_EPS)
+        Q, F = Qn / Qn.sum(axis=1, keepdims=True), np.clip(Fn, ADMIX_EPS, 1.0 - ADMIX_EPS)
+    return Q, F, ll
+
+
+def admixture_init(n, L, K, seed, freq=None):
+    """A start for Admixture: Q (n, K) one Dirichlet(1) draw per individual, F (L, K) the marker's frequency (freq, L values; 0.5
+    when None) plus a uniform jitter in [-0.1, 0.1] per population, clipped to [0.05, 0.95].  Both from default_rng(seed)."""
+    rng = np.random.default_rng(seed)
+    Q = rng.dirichlet(np.ones(int(K)), size=int(n))
+    f = np.full(int(L), 0.5) if freq is None else np.asarray(freq, dtype=np.float64).ravel()
+    if f.size != L:
+        raise ValueError("admixture_init: freq must hold one frequency per marker (%d)" % L)
+    F = np.clip(f[:, None] + rng.uniform(-0.1, 0.1, size=(int(L), int(K))), 0.05, 0.95)
+    return Q / Q.sum(axis=1, keepdims=True), F
+
+
+def _admix_project(Q, F):
+    Q = np.maximum(Q, ADMIX_EPS)
+    return Q / Q.sum(axis=1, keepdims=True), np.clip(F, ADMIX_EPS, 1.0 - ADMIX_EPS)
+
+
+def Admixture(geno, K, seed=0, tol=1e-4, max_iter=2000, accel="squarem", init=None, availmemGb=8, device=0, step=None):
+    """Model-based ancestry proportions of a panel for K ancestral populations: EM on the likelihood of FRAPPE / ADMIXTURE / STRUCTURE,
+    every step on the device (rcpp_api.admixture_em; include/eagle_hip.h section 1b''''v) -> {"Q" (n, K): the fractions of every
+    individual, "F" (K, L): the frequency of the '2' character's allele in every population, "loglik": the trace, one entry per EM step
+    evaluated (it never falls), "iterations" = len(loglik) - 1, "converged", "K", "assignment" = argmax_k Q: a groups= argument for
+    Fst and GroupCounts}.  The components are ordered by decreasing mean of Q, so a relabelling of the start does not reach the caller;
+    am.add_ancestry appends Q's columns to a design matrix.
+    accel="squarem" (Varadhan and Roland 2008): a cycle takes two EM steps theta0 -> theta1 -> theta2, r = theta1 - theta0,
+    v = theta2 - theta1 - r, alpha = min(-1, -|r| / |v|), theta' = theta0 - 2 alpha r + alpha^2 v projected (F clipped, Q floored and
+    renormalised), then one stabilising EM step from theta', whose first likelihood is l(theta'); where l(theta') < l(theta2) the cycle
+    falls back to theta2.  accel="none" is plain EM.  Either stops when a cycle (a step) raises the log-likelihood by less than tol,
+    or after max_iter EM steps.  init: (Q, F (L, K)) or None = admixture_init(n, L, K, seed, the markers' frequencies).  step: a
+    callable with rcpp_api.admixture_em's shape to run instead of it (admixture_host on a CPU).  A missing call of the source is a
+    heterozygote on the image: impute first where that matters.  Supervised mode and cross-validation of K are out of scope."""
+    if accel not in ("squarem", "none"):
+        raise ValueError("Admixture: accel must be \"squarem\" or \"none\"")
+    if isinstance(K, bool) or int(K) != K or not 1 <= K <= ADMIX_KMAX:
+        raise ValueError("Admixture: K must be a whole number in [1, %d]" % ADMIX_KMAX)
+    if not tol > 0.0 or isinstance(max_iter, bool) or int(max_iter) != max_iter or max_iter < 1:
+        raise ValueError("Admixture: tol must be positive and max_iter a whole number of at least 1")
+    K, max_iter = int(K), int(max_iter)
+    n, L = int(geno["dim_of_ascii_M"][0]), int(geno["dim_of_ascii_M"][1])
+    fMt, dims = geno["asciifileMt"], (n, L)
+    if init is None:
+        freq = None
+        if step is None:
+            c = rcpp_api.marker_counts(fMt, dims, availmemGb, device=device).astype(np.float64)
+            freq = (c[:, 1] + 2.0 * c[:, 2]) / (2.0 * n)
+        Q, F = admixture_init(n, L, K, seed, freq)
+    else:
+        Q, F = rcpp_api._admixture_inputs("Admixture", n, L, init[0], init[1], 1)
+        if Q.shape[1] != K:
+            raise ValueError("Admixture: init holds %d components, K = %d" % (Q.shape[1], K))
+    if step is None:
+        def step(f, d, Q, F, steps=1):
+            return rcpp_api.admixture_em(f, d, Q, F, steps, availmemGb, device=device)
+    trace, converged = [], False
+    if accel == "none":
+        while len(trace) - 1 < max_iter and not converged:
+            todo = min(8, max_iter - max(len(trace) - 1, 0))
+            Q, F, ll = step(fMt, dims, Q, F, todo)
+            trace.extend(ll if not trace else ll[1:])
+            converged = bool(np.any(np.diff(ll) < tol))
+    else:
+        while not converged:
+            if len(trace) - 1 + 3 > max_iter and trace:
+                break
+            Q1, F1, la = step(fMt, dims, Q, F, 1)
+            Q2, F2, lb = step(fMt, dims, Q1, F1, 1)
+            if not trace:
+                trace.append(float(la[0]))
+            l0 = trace[-1]
+            trace.extend([float(la[1]), float(lb[1])])
+            rq, rf = Q1 - Q, F1 - F
+            vq, vf = Q2 - Q1 - rq, F2 - F1 - rf
+            nr = math.sqrt(float(np.sum(rq * rq) + np.sum(rf * rf)))
+            nv = math.sqrt(float(np.sum(vq * vq) + np.sum(vf * vf)))
+            if nv == 0.0:                                              # the map is linear here: nothing to extrapolate
+                Q, F, converged = Q2, F2, True
+                break
+            alpha = min(-1.0, -nr / nv)
+            Qp, Fp = _admix_project(Q - 2.0 * alpha * rq + alpha * alpha * vq, F - 2.0 * alpha * rf + alpha * alpha * vf)
+            Q3, F3, lc = step(fMt, dims, Qp, Fp, 1)
+            if lc[0] < lb[1] or not np.isfinite(lc[1]):                # the extrapolation lost ground: theta2 stands
+                Q, F = Q2, F2
+                trace.append(float(lb[1]))
+            else:
+                Q, F = Q3, F3
+                trace.append(float(lc[1]))
+            converged = trace[-1] - l0 < tol
+    order = np.argsort(-Q.mean(axis=0), kind="stable")
+    Q, F = np.ascontiguousarray(Q[:, order]), np.ascontiguousarray(F[:, order].T)
+    return {"Q": Q, "F": F, "loglik": np.asarray(trace, dtype=np.float64), "iterations": len(trace) - 1, "converged": bool(converged), "K": K,
+            "assignment": np.argmax(Q, axis=1)}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
 # The exact per-marker mixed-model test (include/eagle_hip.h section 1d'; device: rcpp_api.spectral_lmm, am.GWAS).
 # ---------------------------------------------------------------------------------------------------------------------------
 LMM_THETA_MIN, LMM_THETA_MAX, LMM_STEP_MAX, LMM_PIVOT_REL = -10.0, 10.0, 2.0, 2.0 ** -40

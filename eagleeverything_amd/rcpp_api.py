@@ -1590,6 +1590,50 @@ def logistic(f_name_ascii_Mt, dims, status, X, beta0=None, firth=2, tol=1e-10, m
     return stat, info
 
 
+# ---- admixture: EM steps of the ancestry model (include/eagle_hip.h section 1b''''v); the driver is r_api.Admixture ----
+ADMIX_EPS, ADMIX_KMAX = 1e-6, 16
+
+
+def _admixture_inputs(who, n, nm, Q, F, steps):
+    """(Q fp64 (n, K), F fp64 (L, K), both C-ordered copies) after the checks eagle_admixture_em makes, as ValueError."""
+    Qa, Fa = np.asarray(Q), np.asarray(F)
+    if Qa.dtype.kind not in "iuf" or Qa.ndim != 2 or Qa.shape[0] != n or not 1 <= Qa.shape[1] <= ADMIX_KMAX:
+        raise ValueError("%s: Q must be numeric (%d, K) with 1 <= K <= %d" % (who, n, ADMIX_KMAX))
+    K = Qa.shape[1]
+    if Fa.dtype.kind not in "iuf" or Fa.shape != (nm, K):
+        raise ValueError("%s: F must be numeric (%d, %d): one row per marker, one column per column of Q" % (who, nm, K))
+    if isinstance(steps, bool) or int(steps) != steps or not 0 <= steps <= 10000:
+        raise ValueError("%s: steps must be a whole number in [0, 10000]" % who)
+    Qf, Ff = np.array(Qa, dtype=np.float64, order="C"), np.array(Fa, dtype=np.float64, order="C")
+    if not np.all(np.isfinite(Qf)) or not np.all(np.isfinite(Ff)):
+        raise ValueError("%s: Q and F must be finite" % who)
+    if Ff.size and (Ff.min() < ADMIX_EPS or Ff.max() > 1.0 - ADMIX_EPS):
+        raise ValueError("%s: F must lie in [%g, 1 - %g]" % (who, ADMIX_EPS, ADMIX_EPS))
+    if Qf.size and Qf.min() < 0.0:
+        raise ValueError("%s: Q must not be negative" % who)
+    rows = np.zeros(n)
+    for k in range(K):                                   # the library's order of the sum
+        rows = rows + Qf[:, k]
+    if np.any(np.abs(rows - 1.0) > 1e-9):
+        raise ValueError("%s: every row of Q must sum to 1 within 1e-9" % who)
+    return Qf, Ff
+
+
+def admixture_em(f_name_ascii_Mt, dims, Q, F, steps=1, availmemGb=8, device=0):
+    """eagle_admixture_em -> (Q fp64 (n, K), F fp64 (L, K), loglik fp64 (steps + 1)): `steps` EM steps of the admixture model of
+    include/eagle_hip.h section 1b''''v on Mt.ascii (dims = (n, L) of M), from the fractions Q (rows sum to 1) and the frequencies F
+    (one ROW per marker, within [1e-6, 1 - 1e-6]) of the allele the '2' character stands for.  loglik[t] is the log-likelihood at the
+    parameters entering step t, loglik[-1] that of the result; steps = 0 computes it alone.  The inputs are not modified.  With a view
+    alias Q holds one row per kept individual.  r_api.admixture_host restates it."""
+    n, nm = max(int(dims[0]), 0), max(int(dims[1]), 0)
+    Qf, Ff = _admixture_inputs("admixture_em", n, nm, Q, F, steps)
+    L = _lib.load()
+    ll = np.zeros(int(steps) + 1, dtype=np.float64)
+    _args_first(L.eagle_admixture_em, device, (os.fsencode(f_name_ascii_Mt), _dims(dims), Qf.shape[1], int(steps), _dp(Qf), _dp(Ff),
+                                               float(availmemGb), _dp(ll)))
+    return Qf, Ff, ll
+
+
 # ---- SURVEY 8 f-4: the dense model algebra on the device, through the C ABI (opt-in; include/eagle_hip.h section 1c) ----
 def _square_any_order(A):
     """(buffer, transposed): a float64 n x n array usable as a column-major matrix without a copy when it is contiguous in

@@ -1109,6 +1109,65 @@ int eagle_logistic(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long dims[
                    int32_t* info_out);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1b''''v. Admixture: model-based ancestry proportions (no counterpart in the reference, whose panel is one population): for K
+ *     ancestral populations the fractions Q (n x K, rows sum to 1) of every individual and the allele frequencies F of every
+ *     population, by EM on the likelihood of FRAPPE (Tang et al. 2005), ADMIXTURE (Alexander et al. 2009) and STRUCTURE.  The groups
+ *     that eagle_group_counts, Fst and the case/control tests take from the caller come from here (argmax_k Q), and the columns of Q
+ *     are covariates for the association models as the principal components of section 1b'''' are.
+ *
+ *     1. Model.  g in {-1, 0, +1} over the individuals of line m of Mt.ascii, d = g + 1 copies of the allele that the character '2'
+ *        stands for; a missing call of the source is a heterozygote by now.  For individual i and marker m
+ *            p_im = sum_k q_ik f_km,      pbar_im = sum_k q_ik (1 - f_km):
+ *        p-bar is its own sum, never 1 - p, so every sum of the rule has non-negative terms and is well conditioned in any order.
+ *            l(Q, F) = sum_m sum_i [ d ln p + (2 - d) ln pbar ],   a term with a zero factor (d = 0, or d = 2) being 0.
+ *     2. One EM step (Q, F) -> (Q', F').  With A_im = d_im / p_im and B_im = (2 - d_im) / pbar_im:
+ *            sa_km = f_km sum_i q_ik A_im,      sb_km = (1 - f_km) sum_i q_ik B_im,
+ *            f'_km = clamp(sa / (sa + sb), eps, 1 - eps),   and f'_km = f_km where sa + sb = 0 (no individual has a part in k);
+ *            t_ik = q_ik sum_m (f_km A_im + (1 - f_km) B_im),
+ *            q'_ik = max(t_ik / (2 L), eps), then every row of Q' is divided by its sum.
+ *        eps = EAGLE_ADMIX_EPS = 1e-6 and 1 <= K <= EAGLE_ADMIX_KMAX = 16.  Both halves use the OLD (Q, F).  The likelihood never
+ *        falls under a step, up to the floors.  With K = 1 one step gives f' = clamp(mean(d) / 2).
+ *     3. Storage.  Q is n x K row-major, F is L x K row-major (the frequencies of a window of markers are contiguous), both in and out.
+ *        loglik_out has steps + 1 entries: entry t is l at the parameters entering step t, the last entry is l at the returned
+ *        parameters, from a likelihood-only pass of the same kernel.  steps = 0 computes loglik_out[0] and returns Q and F untouched.
+ *     4. Individuals with index >= n do not exist: the kernels mask them and do not rely on the image's padding (a zero byte would be
+ *        a heterozygote).
+ *
+ *     On the device (csrc/eagle_admix.hip) a step is two tile kernels over the image, both on v_mfma_f64_16x16x4_f64 with K padded to
+ *     16.  k_admix_f: a wave owns 16 markers and walks the individuals 16 at a time; the tile of p and of pbar is ceil(K / 4)
+ *     instructions each, a lane turns its four entries into A and B, and the C/D registers are, as they lie, the B operand of the
+ *     sums over individuals; the lane then writes f'.  The likelihood's terms ride in one register per lane, one partial per 16-marker
+ *     tile, added by k_admix_ll_finish in a fixed order.  k_admix_q is the transposed tile (16 individuals per wave), with the markers
+ *     cut into S ranges whose number and boundaries (multiples of 16) are a function of (n, L) alone (admix_range_plan,
+ *     csrc/eagle_host.h); a range's accumulator lives in the partials buffer part[S][n16][16], and k_admix_q_finish adds the ranges
+ *     in order, applies q / (2 L), the floor and the normalisation.  No atomics.  The whole loop of `steps` stays on the device: Q, F
+ *     and l cross the bus once per call and direction.
+ *
+ *     The same words on every route.  f'_m depends on line m alone; q' depends on the order of the markers and the range plan, never on
+ *     how the lines fall into row windows: a streamed window holds a multiple of 16 lines, and a window that ends inside a range
+ *     leaves the accumulator in the partials buffer in fp64, where the next window takes it up.  So the resident image, the sidecar,
+ *     row windows, the text and a VIEW alias return the same words, and so do steps = 5 and five calls with steps = 1.  Bit equality
+ *     with the host restatement (r_api.admixture_host) is not claimed: the matrix pipe's summation order and log are not fixed by
+ *     IEEE 754; the tests hold both to 40-digit arithmetic within bounds derived from the number of non-negative terms.
+ *
+ *     Out of scope: a .bed route that skips missing calls, supervised mode (known ancestries held fixed), cross-validation of K,
+ *     device-held state between calls, sex chromosomes.  Agreement with the ADMIXTURE or STRUCTURE programs is neither claimed nor
+ *     tested, because neither is available.  The accelerated driver (SQUAREM), the start and the ordering of the components are
+ *     r_api.Admixture's.
+ *
+ *     The file is read as eagle_group_counts reads it; with a VIEW alias Q has one row per kept individual.  Single device: a
+ *     multi-device context works on its first device.  Argument errors (EAGLE_ERR_ARG: a NULL pointer, dims <= 0, n > 2^30 - 1, K
+ *     outside [1, 16], steps outside [0, 10000], a non-finite Q or F entry, an F entry outside [eps, 1 - eps], a negative Q entry, a Q
+ *     row whose sum is off 1 by more than 1e-9) are decided before the context is used; with ctx == NULL their text is in
+ *     eagle_open_error().
+ * ------------------------------------------------------------------------------------------- */
+#define EAGLE_ADMIX_EPS 1e-6
+#define EAGLE_ADMIX_KMAX 16
+
+int eagle_admixture_em(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long dims[2], int K, int steps, double* Q, double* F,
+                       double max_memory_in_Gbytes, double* loglik_out);
+
+/* ---------------------------------------------------------------------------------------------
  * 1c. Dense n x n model algebra on the device (OPT-IN: north_star keeps calculateH / calculateP / emma.* on
  *     host LAPACK, and nothing above calls these).  Once the scan takes tens of milliseconds the ~10-15 O(n^3) base-R calls
  *     of a find_qtl iteration are the whole run time (the author's note MyPackage/MyREADME:1 names eigen(); his MAGMA
