@@ -192,6 +192,17 @@ SIGNATURES = {
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "eagle_dev_scan_certify_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_long, C.c_long, C.c_void_p, C.c_void_p,
                                                C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]),
+    # the certificate of a scan cut into marker blocks / device shards (csrc/eagle_internal.h; tests/test_gpu_certificate.py)
+    "eagle_dev_cert_bounds": (C.c_int, [C.c_void_p, C.c_long, C.c_long, C.c_long, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
+    "eagle_dev_cert_lb_b": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "eagle_dev_cert_select_b": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_long,
+                                          C.c_void_p, C.c_void_p]),
+    "eagle_dev_cert_reevaluate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "eagle_dev_cert_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "eagle_cert_tight_max": (C.c_int, []),
+    "eagle_cert_rows": (C.c_void_p, [C.c_void_p]),
+    "eagle_cert_indices": (C.c_void_p, [C.c_void_p]),
     "eagle_last_scan_certificate": (C.c_int, [C.c_void_p, c_lp, c_lp, C.POINTER(C.c_int)]),
     "eagle_last_stream_stats": (C.c_int, [C.c_void_p, C.c_void_p]),
     "eagle_last_scan_timing": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),

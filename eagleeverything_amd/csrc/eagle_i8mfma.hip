@@ -1349,6 +1349,10 @@ __global__ __launch_bounds__(256) void k_vara_i8_finish(const long long* __restr
 //   (2) a_i^2 / (vara_i - b_i) >= LB (1 - 1e-9),  LB = max_j a_j^2 / (vara_j + b_j)  -- marker i cannot be excluded from being
 //                                                   the arg-max: LB is a lower bound of the true maximum, the left side an upper
 //                                                   bound of marker i's true tsq (vara_i - b_i <= 0: no bound, re-evaluated).
+// A marker whose a_i or vara_i is NaN or Inf is skipped by every kernel below, in LB, in the over_tight count and in the selection (the
+// fp64 kernel gives it the same tsq); a marker with vara_i + b_i <= 0 has no term in LB; a term of LB that is not finite (a_i^2
+// overflows) is dropped after the reduction over its wave of 64 markers, with that wave's other terms: a lower LB, still a lower bound.
+// tests/cert_truth.py restates all of this; tests/test_gpu_certificate.py holds the kernels to it.
 // After that the arg-max over [fp64 values of the candidates, digit values of everybody else] is the arg-max of the fp64
 // scan: every marker that can win carries its fp64 value, every other marker is strictly below the winner in both.
 // At most CERT_CAP markers are re-evaluated per call; if more qualify (degenerate operands) the whole block is redone by the
