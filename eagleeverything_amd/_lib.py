@@ -141,6 +141,8 @@ SIGNATURES = {
     "eagle_spectral_rows": (C.c_int, [C.c_void_p, c_lp, C.c_long, c_dp]),
     "eagle_spectral_lmm": (C.c_int, [C.c_void_p, c_dp, c_dp, c_dp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, c_lp, C.c_long, c_dp,
                                      C.POINTER(C.c_int32)]),
+    "eagle_spectral_settest": (C.c_int, [C.c_void_p, c_dp, c_dp, c_dp, C.c_int, C.c_double, C.c_double, C.c_long, c_lp, c_lp, c_dp, c_dp,
+                                         C.POINTER(C.c_int32), c_dp, c_dp]),
     "eagle_scan_with_W": (C.c_int, [C.c_void_p, C.c_char_p, c_dp, C.c_long, c_dp, c_dp, C.c_double, c_lp, C.c_int, c_dp, c_dp]),
     "eagle_calculate_reduced_a": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double, c_dp, c_dp, C.c_double, c_lp, c_dp,
                                             C.c_long, C.c_int, c_dp]),

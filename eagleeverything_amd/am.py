@@ -721,6 +721,45 @@ def SummaryAM_traits(results, Y, X, geno, map=None, xnames=None, availmemGb=8, e
 _GWAS_EXACT = ("beta", "se", "stat", "p", "delta", "vg", "ve", "ll")
 
 
+def _null_model(who, trait, X, geno, backend, availmemGb, device, map=None, ml=False, min_df=2):
+    """What GWAS and SetTest share: the records without NaN in trait or X (a VIEW reshape, as AM() drops them), the backend's K = U
+    diag(lam) U^T and resident Z = Mt U -- reused when the backend already holds them for these genotypes, built otherwise --, Ut =
+    U^T X, ut = U^T y and the null fit on X alone (emma_REMLE_eig; with ml=True emma_MLE_eig as well) -> dict(backend, geno, y, X, n, L,
+    c, lam, U, Ut, ut, null = {"reml", "ml"}, indxNA, names).  n > c + min_df is required."""
+    from . import r_api, rcpp_api
+    backend = backend or SpectralBackend(device)
+    if not hasattr(backend, "eig"):
+        raise TypeError("%s: the backend must be an am.SpectralBackend (it keeps Z = Mt U resident)" % who)
+    y = np.asarray(trait, dtype=np.float64).ravel().copy()
+    Xa = np.asarray(X, dtype=np.float64).reshape(y.size, -1)
+    c = Xa.shape[1]
+    if not 1 <= c <= rcpp_api.LMM_MAX_COVARIATES:
+        raise ValueError("%s: X must hold 1 to %d columns, the intercept included" % (who, rcpp_api.LMM_MAX_COVARIATES))
+    y[np.isnan(Xa).any(axis=1)] = np.nan                                             # AM.R:320-329
+    indxNA = r_api.check_for_NA_in_trait(y)
+    (y, Xa), geno = _drop_na_rows(indxNA, (y, Xa), geno, backend=backend, device=backend.device)
+    n, L = (int(v) for v in geno["dim_of_ascii_M"])
+    if y.size != n:
+        raise ValueError("%s: %d trait records for %d genotyped individuals" % (who, y.size, n))
+    if n <= c + min_df:
+        raise ValueError("%s: %d individuals for %d columns of X" % (who, n, c))
+    names = None if map is None else _summary_names(c, None, map, L)[1]
+    if backend.eig is None or backend.lam.size != n or not rcpp_api.spectral_holds(geno["asciifileMt"], backend.U, device=backend.device):
+        backend.calcMMt(geno, availmemGb, 1, np.array([np.nan]), True)                # K, its eigh and Z = Mt U
+    lam, U = backend.eig
+    lam = np.ascontiguousarray(lam, dtype=np.float64)
+    la = host_model.algebra()
+    Ut, ut = la.mm(U.T, Xa), U.T @ y
+    fit = {"reml": emma_REMLE_eig(lam, Ut, ut)}
+    fit["ml"] = emma_MLE_eig(lam, Ut, ut) if ml else None
+    null = {m: None if r is None else {"delta": r["delta"], "vg": r["vg"], "ve": r["ve"], "ll": r["REML" if m == "reml" else "ML"]}
+            for m, r in fit.items()}
+    if not null["reml"]["vg"] > 0:
+        raise ValueError("%s: the null model has no fit (collinear columns of X?)" % who)
+    return {"backend": backend, "geno": geno, "y": y, "X": Xa, "n": n, "L": L, "c": c, "lam": lam, "U": U, "Ut": Ut, "ut": ut, "null": null,
+            "indxNA": indxNA, "names": names}
+
+
 def GWAS(trait, X, geno, exact="all", method="reml", p_exact=None, map=None, backend=None, availmemGb=8, device=0, Zmat=None):
     """Per-marker tests of a quantitative trait under the mixed model; r_api.GWAS forwards here.
 
@@ -748,35 +787,8 @@ def GWAS(trait, X, geno, exact="all", method="reml", p_exact=None, map=None, bac
         raise ValueError("GWAS: exact must be \"all\" or \"none\", method \"reml\" or \"ml\"")
     if p_exact is not None and not 0.0 < float(p_exact) <= 1.0:
         raise ValueError("GWAS: p_exact must lie in (0, 1]")
-    backend = backend or SpectralBackend(device)
-    if not hasattr(backend, "eig"):
-        raise TypeError("GWAS: the backend must be an am.SpectralBackend (it keeps Z = Mt U resident)")
-    y = np.asarray(trait, dtype=np.float64).ravel().copy()
-    Xa = np.asarray(X, dtype=np.float64).reshape(y.size, -1)
-    c = Xa.shape[1]
-    if not 1 <= c <= rcpp_api.LMM_MAX_COVARIATES:
-        raise ValueError("GWAS: X must hold 1 to %d columns, the intercept included" % rcpp_api.LMM_MAX_COVARIATES)
-    y[np.isnan(Xa).any(axis=1)] = np.nan                                             # AM.R:320-329
-    indxNA = r_api.check_for_NA_in_trait(y)
-    (y, Xa), geno = _drop_na_rows(indxNA, (y, Xa), geno, backend=backend, device=backend.device)
-    n, L = (int(v) for v in geno["dim_of_ascii_M"])
-    if y.size != n:
-        raise ValueError("GWAS: %d trait records for %d genotyped individuals" % (y.size, n))
-    if n <= c + 2:
-        raise ValueError("GWAS: %d individuals for %d columns of X" % (n, c))
-    names = None if map is None else _summary_names(c, None, map, L)[1]
-    if backend.eig is None or backend.lam.size != n or not rcpp_api.spectral_holds(geno["asciifileMt"], backend.U, device=backend.device):
-        backend.calcMMt(geno, availmemGb, 1, np.array([np.nan]), True)                # K, its eigh and Z = Mt U
-    lam, U = backend.eig
-    lam = np.ascontiguousarray(lam, dtype=np.float64)
-    la = host_model.algebra()
-    Ut, ut = la.mm(U.T, Xa), U.T @ y
-    fit = {"reml": emma_REMLE_eig(lam, Ut, ut)}
-    fit["ml"] = emma_MLE_eig(lam, Ut, ut) if method == "ml" else None
-    null = {m: None if r is None else {"delta": r["delta"], "vg": r["vg"], "ve": r["ve"], "ll": r["REML" if m == "reml" else "ML"]}
-            for m, r in fit.items()}
-    if not null["reml"]["vg"] > 0:
-        raise ValueError("GWAS: the null model has no fit (collinear columns of X?)")
+    nm = _null_model("GWAS", trait, X, geno, backend, availmemGb, device, map=map, ml=method == "ml")
+    backend, n, L, c, lam, Ut, ut, null, indxNA, names = (nm[k] for k in ("backend", "n", "L", "c", "lam", "Ut", "ut", "null", "indxNA", "names"))
     res = rcpp_api.spectral_scan(lam, Ut, ut, null["reml"]["ve"], null["reml"]["vg"], L, device=backend.device)
     a, vara = res["a"].ravel(), res["vara"].ravel()
     with np.errstate(all="ignore"):
@@ -805,6 +817,92 @@ def GWAS(trait, X, geno, exact="all", method="reml", p_exact=None, map=None, bac
                 "indxNA": indxNA, "method": method})
     if names is not None:
         out["names"] = [names(j) for j in range(1, L + 1)]
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# SetTest: is a gene, a window or a candidate region AS A WHOLE associated with the trait?  The burden test and SKAT under the null
+# model GWAS uses (the EMMAX-SKAT / famSKAT tests; no counterpart in the reference): the scores of a set's markers and their
+# covariance varG^2 m_i' P m_j from one eagle_spectral_settest over the resident Z (include/eagle_hip.h section 1d''), the p-values
+# on the host.
+# ---------------------------------------------------------------------------------------------------------------------------
+def _set_weights(weights, L, geno, availmemGb, device):
+    """One weight per marker of the panel: "equal", ("beta", a, b) / "beta" (Beta(MAF; a, b), default (1, 25)) or an array of L."""
+    from . import r_api
+    if isinstance(weights, str) and weights == "equal":
+        return np.ones(L)
+    if (isinstance(weights, str) and weights == "beta") or (isinstance(weights, tuple) and len(weights) in (1, 3) and weights[0] == "beta"):
+        from scipy.stats import beta
+        a, b = (1.0, 25.0) if isinstance(weights, str) or len(weights) == 1 else (float(weights[1]), float(weights[2]))
+        if not (a > 0.0 and b > 0.0):
+            raise ValueError("SetTest: the Beta weights need a, b > 0")
+        maf = np.asarray(r_api.MarkerStats(geno, availmemGb=availmemGb, device=device)["maf"], dtype=np.float64)
+        w = beta.pdf(np.nan_to_num(maf, nan=0.0), a, b)
+        return np.where(np.isfinite(w) & ~np.isnan(maf), w, 0.0)
+    if isinstance(weights, (str, tuple)):
+        raise ValueError("SetTest: weights must be \"equal\", (\"beta\", a, b) or one weight per marker")
+    w = np.asarray(weights, dtype=np.float64).ravel()
+    if w.size != L or not (np.all(np.isfinite(w)) and np.all(w >= 0.0)):
+        raise ValueError("SetTest: %d weights, finite and >= 0, for %d markers" % (w.size, L))
+    return w
+
+
+def SetTest(trait, X, geno, sets, weights="equal", p_refine=1e-3, backend=None, map=None, availmemGb=8, device=0, Zmat=None):
+    """Burden and SKAT tests of marker sets under the mixed model; r_api.SetTest forwards here.
+
+    trait, X, geno, backend: as GWAS takes them (rows with NaN dropped; a SpectralBackend that AM() or GWAS() already ran on these
+    genotypes is reused, nothing is rebuilt).  sets: a list of arrays of 0-based markers, 1 to 64 each, or the dict
+    r_api.sets_from_windows / sets_from_table return (its "names" name the sets); a marker may be in many sets.  weights: "equal",
+    ("beta", a, b) -- Beta(MAF; a, b) of r_api.MarkerStats, "beta" = (1, 25) -- or one weight per marker of the panel.
+
+    Returns a dict, per set (k entries): "n_markers", "n_used" (markers not degenerate: not monomorphic, not in the span of X),
+    "burden" = Ub^2 / Vb, "p_burden" = chdtrc(1, burden), "beta_burden" = vg Ub / Vb (the beta_p3d convention of GWAS), "Q",
+    "p_skat_liu" (modified Liu moment matching on the four traces the device returns), "p_skat" (= p_skat_liu, or for the sets with
+    p_skat_liu < p_refine the saddlepoint p-value from the eigenvalues of W Phi W, a second device call with cov_out for those sets
+    alone), "refined" (bool), "code" (0 ok, 2 nothing left: NaN); and "null" (delta, vg, ve, ll of the REML fit), "names", "n_used_individuals", "indxNA".
+    With map= (L names or a mapping with "SNP") also "markers": the marker names of every set.  Zmat (repeated measures) is not supported."""
+    from scipy.special import chdtrc
+    from . import r_api, rcpp_api
+    if Zmat is not None:
+        raise NotImplementedError("SetTest: Zmat (repeated measures) is not supported: the set statistics have no within-individual terms")
+    if p_refine is not None and not 0.0 <= float(p_refine) <= 1.0:
+        raise ValueError("SetTest: p_refine must lie in [0, 1]")
+    set_names = list(sets["names"]) if hasattr(sets, "keys") else None
+    idx = [np.ascontiguousarray(np.atleast_1d(s), dtype=np.int64) for s in (sets["sets"] if hasattr(sets, "keys") else sets)]
+    k = len(idx)
+    if set_names is None:
+        set_names = ["set%d" % (o + 1) for o in range(k)]
+    if len(set_names) != k:
+        raise ValueError("SetTest: %d names for %d sets" % (len(set_names), k))
+    big = [set_names[o] for o in range(k) if not 1 <= idx[o].size <= rcpp_api.SETTEST_MAX_MARKERS]
+    if big:
+        raise ValueError("SetTest: every set must hold 1 to %d markers: %s" % (rcpp_api.SETTEST_MAX_MARKERS, ", ".join(big)))
+    nm = _null_model("SetTest", trait, X, geno, backend, availmemGb, device, map=map, min_df=1)
+    backend, L, lam, Ut, ut, null = nm["backend"], nm["L"], nm["lam"], nm["Ut"], nm["ut"], nm["null"]["reml"]
+    if any(s.size and (s.min() < 0 or s.max() >= L) for s in idx):
+        raise ValueError("SetTest: the sets hold 0-based markers below %d" % L)
+    w = _set_weights(weights, L, nm["geno"], availmemGb, backend.device)
+    omega = [w[s] for s in idx]
+    res = rcpp_api.spectral_settest(lam, Ut, ut, null["ve"], null["vg"], idx, omega, device=backend.device)
+    stat, info = res["stat"], res["info"]
+    Q, Ub, Vb = stat[:, 0], stat[:, 1], stat[:, 2]
+    with np.errstate(all="ignore"):
+        burden = Ub * Ub / Vb
+        out = {"n_markers": np.array([s.size for s in idx], dtype=np.int64), "n_used": info[:, 1].astype(np.int64), "burden": burden,
+               "p_burden": chdtrc(1.0, burden), "beta_burden": null["vg"] * Ub / Vb, "Q": Q.copy(), "code": info[:, 0].copy()}
+    liu = np.array([r_api.skat_pvalue(Q[o], c=stat[o, 3:7]) if info[o, 0] == 0 else np.nan for o in range(k)])
+    out["p_skat_liu"], out["p_skat"], out["refined"] = liu, liu.copy(), np.zeros(k, dtype=bool)
+    hit = np.flatnonzero(liu < float(p_refine)) if p_refine is not None else np.zeros(0, dtype=np.int64)
+    if hit.size:
+        cov = rcpp_api.spectral_settest(lam, Ut, ut, null["ve"], null["vg"], [idx[o] for o in hit], [omega[o] for o in hit], cov=True,
+                                        device=backend.device)["cov"]
+        for o, Phi in zip(hit, cov):
+            p = r_api.skat_pvalue(Q[o], eig=np.linalg.eigvalsh(Phi * np.outer(omega[o], omega[o])), method="saddle")
+            if p == p:
+                out["p_skat"][o], out["refined"][o] = p, True
+    out.update({"null": null, "names": set_names, "n_used_individuals": nm["n"], "indxNA": nm["indxNA"]})
+    if nm["names"] is not None:
+        out["markers"] = [[nm["names"](int(j) + 1) for j in s] for s in idx]
     return out
 
 

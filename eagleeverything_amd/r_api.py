@@ -3225,3 +3225,265 @@ def GWAS(trait, X, geno, exact="all", method="reml", p_exact=None, map=None, bac
     from . import am
     return am.GWAS(trait, X, geno, exact=exact, method=method, p_exact=p_exact, map=map, backend=backend, availmemGb=availmemGb,
                    device=device, Zmat=Zmat)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Tests of marker sets under the mixed model: burden and SKAT (include/eagle_hip.h section 1d''; device: rcpp_api.spectral_settest,
+# am.SetTest).
+# ---------------------------------------------------------------------------------------------------------------------------
+SETTEST_MAX_MARKERS = 64
+
+
+def settest_host(lam, UtX, Uty, Zrows, varE, varG, sets, omega=None):
+    """rcpp_api.spectral_settest restated in numpy, set by set, by the rule of include/eagle_hip.h section 1d'': lam (n) the
+    eigenvalues of K, UtX = U^T X (n x c, the intercept column included), Uty = U^T y, Zrows (L x n): row j = U^T m_j (what
+    spectral_rows returns, transposed), the null model's varE and varG; sets, omega: as rcpp_api.settest_csr takes them ->
+    {"stat" (k, 7) = Q, Ub, Vb, c_1 .. c_4; "info" (k, 2) = code, markers used; "score": k arrays s; "cov": k arrays Phi}.
+    ValueError when G_xx fails its pivot rule (X^T H^-1 X is not positive definite).  Not bit-equal to the device (the order of the sums
+    differs); tests/settest_truth.py holds both to 40-digit values."""
+    lam = np.asarray(lam, dtype=np.float64).ravel()
+    n = lam.size
+    Ut = np.asarray(UtX, dtype=np.float64).reshape(n, -1)
+    ut = np.asarray(Uty, dtype=np.float64).ravel()
+    Zr = np.asarray(Zrows, dtype=np.float64).reshape(-1, n)
+    c = Ut.shape[1]
+    if not 1 <= c <= 14 or ut.size != n or n <= c + 1:
+        raise ValueError("settest_host: UtX must be (n, c) with 1 <= c <= 14 and n > c + 1, Uty of length n")
+    ptr, idx, w = rcpp_api.settest_csr(sets, omega)
+    m_all = np.diff(ptr)
+    if m_all.size and (m_all.min() < 1 or m_all.max() > SETTEST_MAX_MARKERS):
+        raise ValueError("settest_host: every set must hold 1 to %d markers" % SETTEST_MAX_MARKERS)
+    if idx.size and (idx.min() < 0 or idx.max() >= Zr.shape[0]):
+        raise ValueError("settest_host: marker index out of range")
+    if not (np.all(np.isfinite(w)) and np.all(w >= 0.0)):
+        raise ValueError("settest_host: the weights must be finite and >= 0")
+    h = varE + varG * lam
+    if not np.all((h > 0.0) & np.isfinite(h)):
+        raise ValueError("settest_host: varE + varG * lambda_k must be positive and finite")
+    d = 1.0 / h
+    vg2 = varG * varG
+    k = m_all.size
+    stat, info, score, cov = np.full((k, 7), np.nan), np.zeros((k, 2), dtype=np.int32), [], []
+    for o in range(k):
+        j, om = idx[ptr[o]:ptr[o + 1]], w[ptr[o]:ptr[o + 1]]
+        m = j.size
+        A = np.column_stack([Zr[j].T, Ut, ut])
+        G = A.T @ (d[:, None] * A)
+        G = np.tril(G) + np.tril(G, -1).T
+        Lm = _logit_chol(G[m:m + c, m:m + c])                                         # the pivot rule, LMM_PIVOT_REL = 2^-40
+        if Lm is None:
+            raise ValueError("settest_host: X^T H^-1 X is not positive definite (collinear fixed effects)")
+        B = _logit_solve(Lm, G[m:m + c, np.r_[0:m, m + c]])
+        s = varG * (G[:m, m + c] - G[:m, m:m + c] @ B[:, m])
+        Phi = np.tril(vg2 * (G[:m, :m] - G[:m, m:m + c] @ B[:, :m]))
+        Phi = Phi + np.tril(Phi, -1).T                                                # the mirror is a copy of the lower triangle
+        deg = ~(np.diag(Phi) > LMM_PIVOT_REL * vg2 * np.diag(G)[:m])
+        s[deg] = 0.0
+        Phi[deg, :] = 0.0
+        Phi[:, deg] = 0.0
+        Aw = Phi * np.outer(om, om)
+        Aw2 = Aw @ Aw
+        t = om * s
+        st = (t @ t, t.sum(), Aw.sum(), np.trace(Aw), np.sum(Aw * Aw), np.sum(Aw * Aw2), np.sum(Aw2 * Aw2))
+        none = not (st[2] > 0.0) or not (st[4] > 0.0)
+        if not none:
+            stat[o] = st
+        info[o] = (2 if none else 0, m - int(deg.sum()))
+        score.append(s)
+        cov.append(Phi)
+    return {"stat": stat, "info": info, "score": score, "cov": cov}
+
+
+def _skat_traces(eig):
+    lam = np.asarray(eig, dtype=np.float64).ravel()
+    return tuple(float(np.sum(lam ** r)) for r in (1, 2, 3, 4))
+
+
+def _skat_liu(Q, c):
+    """P(sum_i lambda_i chi^2_1,i > Q) from c_r = sum_i lambda_i^r, r = 1 .. 4, by the moment matching of Liu, Tang & Zhang (2009) in
+    the modified form that matches the kurtosis (SKAT's liu.mod)."""
+    from scipy.special import chdtrc
+    from scipy.stats import ncx2
+    c1, c2, c3, c4 = (float(v) for v in c)
+    if not (c2 > 0.0) or not all(math.isfinite(v) for v in (Q, c1, c2, c3, c4)):
+        return float("nan")
+    s1, s2 = c3 / c2 ** 1.5, c4 / (c2 * c2)
+    # s1^2 >= s2 always (Cauchy-Schwarz), with equality for equal eigenvalues: a difference within 2^-40 s2 is the traces' rounding
+    if s1 * s1 - s2 > LMM_PIVOT_REL * s2:
+        a = 1.0 / (s1 - math.sqrt(s1 * s1 - s2))
+        delta = s1 * a ** 3 - a * a
+        l = a * a - 2.0 * delta
+    else:
+        l = 1.0 / s2
+        a, delta = math.sqrt(l), 0.0
+    q = (Q - c1) / math.sqrt(2.0 * c2) * math.sqrt(2.0) * a + l + delta
+    if q <= 0.0:
+        return 1.0
+    return float(chdtrc(l, q) if delta == 0.0 else ncx2.sf(q, l, delta))
+
+
+def _skat_saddle(Q, eig):
+    """The same tail by Kuonen's (1999) saddlepoint approximation: K(t) = -1/2 sum log(1 - 2 t lambda_i), the root of K'(t) = Q by
+    brentq, then Lugannani & Rice's formula.  NaN where the formula is singular (Q within 1e-6 of the mean in units of the sd)."""
+    from scipy.optimize import brentq
+    from scipy.special import ndtr
+    lam = np.asarray(eig, dtype=np.float64).ravel()
+    lam = lam[lam > 0.0]
+    if lam.size == 0 or not math.isfinite(Q):
+        return float("nan")
+    lmax, mean, sd = float(lam.max()), float(lam.sum()), math.sqrt(2.0 * float(np.sum(lam * lam)))
+    if Q <= 0.0:
+        return 1.0
+    if abs(Q - mean) <= 1e-6 * sd:
+        return float("nan")
+    lam = lam / lmax                                                                  # K' in units of lambda_max
+    q = Q / lmax
+    kp = lambda t: float(np.sum(lam / (1.0 - 2.0 * t * lam))) - q
+    if Q > mean:
+        lo, hi = 0.0, 0.5 * (1.0 - 0.5 / q)                                           # K'(hi) >= 1 / (1 - 2 hi) = 2 q
+    else:
+        lo, hi = -1.0, 0.0
+        while kp(lo) > 0.0:
+            lo *= 2.0
+    t = brentq(kp, lo, hi, xtol=1e-300, rtol=8.9e-16, maxiter=500)
+    K = -0.5 * float(np.sum(np.log1p(-2.0 * t * lam)))
+    K2 = 2.0 * float(np.sum((lam / (1.0 - 2.0 * t * lam)) ** 2))
+    w = math.copysign(math.sqrt(max(2.0 * (t * q - K), 0.0)), t)
+    v = t * math.sqrt(K2)
+    if w == 0.0 or v == 0.0:
+        return float("nan")
+    p = float(ndtr(-w)) + math.exp(-0.5 * w * w) / math.sqrt(2.0 * math.pi) * (1.0 / v - 1.0 / w)
+    return min(max(p, 0.0), 1.0)
+
+
+def skat_pvalue(Q, c=None, eig=None, method="liu"):
+    """P(sum_i lambda_i chi^2_1,i > Q), the null distribution of SKAT's Q with lambda = the eigenvalues of Aw = W Phi W.
+    method="liu": from the traces c = (c_1, c_2, c_3, c_4) = tr(Aw^r) -- what the device returns -- or from eig, by the modified moment
+    matching of Liu et al. (2009): cheap, good to a few per cent down to p ~ 1e-4, drifting below.  method="saddle": from eig by
+    Kuonen's saddlepoint approximation (Lugannani-Rice), whose RELATIVE error stays bounded in the far tail; NaN within 1e-6 standard
+    deviations of the mean, where the formula is singular (use "liu" there)."""
+    if method not in ("liu", "saddle"):
+        raise ValueError("skat_pvalue: method must be \"liu\" or \"saddle\"")
+    if method == "saddle":
+        if eig is None:
+            raise ValueError("skat_pvalue: the saddlepoint approximation needs eig=, the eigenvalues of W Phi W")
+        return _skat_saddle(float(Q), eig)
+    if c is None and eig is None:
+        raise ValueError("skat_pvalue: give c=(c_1, c_2, c_3, c_4) or eig=")
+    if c is None:
+        lam = np.asarray(eig, dtype=np.float64).ravel()
+        c = _skat_traces(lam[lam > 0.0])
+    if len(c) != 4:
+        raise ValueError("skat_pvalue: c holds the four traces c_1 .. c_4")
+    return _skat_liu(float(Q), c)
+
+
+def _set_map(who, map):
+    if not hasattr(map, "keys") or "Chr" not in map or "Pos" not in map:
+        raise ValueError("%s needs a map with Chr and Pos entries (ReadBim's)" % who)
+    chrom, pos = [str(v) for v in map["Chr"]], np.asarray(map["Pos"], dtype=np.int64).ravel()
+    if len(chrom) != pos.size:
+        raise ValueError("%s: the map's Chr and Pos differ in length" % who)
+    return chrom, pos
+
+
+def _chrom_runs(chrom):
+    """[(name, first, end)] of the runs of equal chromosome names, in file order."""
+    runs, first = [], 0
+    for j in range(1, len(chrom) + 1):
+        if j == len(chrom) or chrom[j] != chrom[first]:
+            runs.append((chrom[first], first, j))
+            first = j
+    return runs
+
+
+def sets_from_windows(L_or_map, size=None, step=None, kb=None):
+    """Windows of neighbouring markers as sets -> {"sets": list of int64 arrays of 0-based markers, "names": list of str}.
+    L_or_map: the number of markers (one run) or a map (ReadBim's dict with Chr and Pos): windows are then cut at chromosome ends.
+    size=: windows of `size` <= 64 markers, a new one every `step` markers (default: size, no overlap); the last window of a
+    chromosome may be shorter.  kb= (needs a map with positions ascending inside a chromosome): windows of kb kilobases starting at the
+    chromosome's first marker, a new one every `step` kilobases (default: kb); windows without a marker are left out, a window above
+    64 markers is an error that names it."""
+    if (size is None) == (kb is None):
+        raise ValueError("sets_from_windows: give size= (markers) or kb= (kilobases), not both")
+    if hasattr(L_or_map, "keys"):
+        chrom, pos = _set_map("sets_from_windows", L_or_map)
+        runs = _chrom_runs(chrom)
+    else:
+        if kb is not None:
+            raise ValueError("sets_from_windows: kb= needs a map")
+        runs, pos = [("", 0, int(L_or_map))], None
+    sets, names = [], []
+    if size is not None:
+        size = int(size)
+        step = size if step is None else int(step)
+        if not 1 <= size <= SETTEST_MAX_MARKERS or step < 1:
+            raise ValueError("sets_from_windows: 1 <= size <= %d and step >= 1" % SETTEST_MAX_MARKERS)
+        for name, a, b in runs:
+            for f in range(a, b, step):
+                e = min(f + size, b)
+                sets.append(np.arange(f, e, dtype=np.int64))
+                names.append("%s%d-%d" % (name + ":" if name else "", f, e - 1))
+                if e == b:
+                    break
+        return {"sets": sets, "names": names}
+    width = int(round(float(kb) * 1000.0))
+    stride = width if step is None else int(round(float(step) * 1000.0))
+    if width < 1 or stride < 1:
+        raise ValueError("sets_from_windows: kb and step must be positive")
+    big = []
+    for name, a, b in runs:
+        p = pos[a:b]
+        if np.any(np.diff(p) < 0):
+            raise ValueError("sets_from_windows: positions must ascend inside chromosome %s" % name)
+        start = int(p[0])
+        while start <= int(p[-1]):
+            f, e = a + int(np.searchsorted(p, start, "left")), a + int(np.searchsorted(p, start + width, "left"))
+            if e > f:
+                label = "%s:%d-%d" % (name, start, start + width - 1)
+                if e - f > SETTEST_MAX_MARKERS:
+                    big.append(label)
+                sets.append(np.arange(f, e, dtype=np.int64))
+                names.append(label)
+            start += stride
+    if big:
+        raise ValueError("sets_from_windows: windows above %d markers: %s" % (SETTEST_MAX_MARKERS, ", ".join(big)))
+    return {"sets": sets, "names": names}
+
+
+def sets_from_table(map, regions):
+    """Named regions (genes, candidate intervals) as sets -> {"sets", "names", "empty": names of regions that hold no marker, left
+    out}.  map: ReadBim's dict; regions: rows (name, chr, start, end) or a mapping name -> (chr, start, end), positions in base pairs,
+    both ends included.  Regions above 64 markers raise ValueError with their names."""
+    chrom, pos = _set_map("sets_from_table", map)
+    chrom = np.asarray(chrom)
+    rows = [(k,) + tuple(v) for k, v in regions.items()] if hasattr(regions, "keys") else [tuple(r) for r in regions]
+    sets, names, empty, big = [], [], [], []
+    for r in rows:
+        if len(r) != 4:
+            raise ValueError("sets_from_table: a region is (name, chr, start, end)")
+        name, ch, a, b = str(r[0]), str(r[1]), int(r[2]), int(r[3])
+        j = np.flatnonzero((chrom == ch) & (pos >= a) & (pos <= b)).astype(np.int64)
+        if j.size == 0:
+            empty.append(name)
+            continue
+        if j.size > SETTEST_MAX_MARKERS:
+            big.append("%s (%d)" % (name, j.size))
+        sets.append(j)
+        names.append(name)
+    if big:
+        raise ValueError("sets_from_table: regions above %d markers: %s" % (SETTEST_MAX_MARKERS, ", ".join(big)))
+    return {"sets": sets, "names": names, "empty": empty}
+
+
+def SetTest(trait, X, geno, sets, weights="equal", p_refine=1e-3, backend=None, map=None, availmemGb=8, device=0, Zmat=None):
+    """Burden and SKAT tests of marker sets -- genes, windows, candidate regions -- under y = X beta + g + e with the null REML fit's
+    variance components and the kinship AM() uses (am.SetTest; the EMMAX-SKAT / famSKAT tests): per set "n_markers", "n_used",
+    "burden", "p_burden", "beta_burden", "Q", "p_skat", "p_skat_liu", "refined", "code", plus "null", "names", "n_used_individuals",
+    "indxNA".  sets: a list of arrays of 0-based markers or what sets_from_windows / sets_from_table return; weights: "equal",
+    ("beta", a, b) (Beta(MAF; a, b), default (1, 25)) or one weight per marker.  The sets with a Liu p-value below p_refine get the
+    saddlepoint p-value from the eigenvalues of W Phi W.  backend: an am.SpectralBackend; one that AM() or GWAS() already ran on these
+    genotypes is reused, nothing is rebuilt."""
+    from . import am
+    return am.SetTest(trait, X, geno, sets, weights=weights, p_refine=p_refine, backend=backend, map=map, availmemGb=availmemGb,
+                      device=device, Zmat=Zmat)

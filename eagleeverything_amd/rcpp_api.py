@@ -391,6 +391,77 @@ def spectral_lmm(lam, UtX, Uty, reml=True, theta0=0.0, tol=1e-10, max_iter=50, i
     return stat[:k], info[:k]
 
 
+SETTEST_MAX_MARKERS = 64
+
+
+def settest_csr(sets, omega=None):
+    """(set_ptr (k + 1), set_idx (nnz), omega (nnz)) int64 / int64 / fp64 of `sets`, a list of 1-D arrays of 0-based markers, and
+    `omega`: None (every weight 1), a list of arrays shaped like the sets, or one flat array of nnz weights in CSR order."""
+    idx = [np.ascontiguousarray(np.atleast_1d(s), dtype=np.int64) for s in sets]
+    if any(s.ndim != 1 for s in idx):
+        raise ValueError("settest: every set must be a 1-D list of 0-based markers")
+    ptr = np.zeros(len(idx) + 1, dtype=np.int64)
+    np.cumsum([s.size for s in idx], out=ptr[1:])
+    flat = np.concatenate(idx) if idx else np.zeros(0, dtype=np.int64)
+    if omega is None:
+        w = np.ones(flat.size)
+    elif isinstance(omega, (list, tuple)):
+        if len(omega) != len(idx) or any(np.size(a) != s.size for a, s in zip(omega, idx)):
+            raise ValueError("settest: one weight per marker of every set")
+        w = np.concatenate([np.asarray(a, dtype=np.float64).ravel() for a in omega]) if idx else np.zeros(0)
+    else:
+        w = np.ascontiguousarray(np.ravel(omega), dtype=np.float64)
+        if w.size != flat.size:
+            raise ValueError("settest: one weight per marker of every set")
+    return ptr, np.ascontiguousarray(flat), np.ascontiguousarray(w, dtype=np.float64)
+
+
+def spectral_settest(lam, UtX, Uty, varE, varG, sets, omega=None, scores=False, cov=False, device=0):
+    """eagle_spectral_settest: burden and SKAT statistics of marker sets on the resident Z (include/eagle_hip.h section 1d'') ->
+    {"stat" (k, 7) = Q, Ub, Vb, c_1 .. c_4; "info" (k, 2) = code, markers used} and, with scores=True, "score": a list of k arrays
+    (s_j of every set), with cov=True, "cov": a list of k symmetric (m, m) arrays (Phi).  lam (n), UtX (n x c, 1 <= c <= 14, the
+    intercept column included), Uty (n), the null model's varE and varG; sets, omega: as settest_csr takes them (1 to
+    SETTEST_MAX_MARKERS markers per set, weights finite and >= 0)."""
+    lam = _f64F(np.ravel(lam))
+    n = lam.size
+    UtX = np.asarray(UtX, dtype=np.float64)
+    if UtX.ndim == 1:
+        UtX = UtX[:, None]
+    Uty = _f64F(np.ravel(Uty))
+    if UtX.ndim != 2 or UtX.shape[0] != n or not 1 <= UtX.shape[1] <= LMM_MAX_COVARIATES or Uty.size != n:
+        raise ValueError("spectral_settest: lam, Uty of length n and UtX (n, c) with 1 <= c <= %d" % LMM_MAX_COVARIATES)
+    if not (np.all(np.isfinite(lam)) and np.all(np.isfinite(UtX)) and np.all(np.isfinite(Uty)) and np.isfinite(float(varE))
+            and np.isfinite(float(varG))):
+        raise ValueError("spectral_settest: a non-finite operand")
+    ptr, idx, w = settest_csr(sets, omega)
+    m = np.diff(ptr)
+    if m.size and (m.min() < 1 or m.max() > SETTEST_MAX_MARKERS):
+        raise ValueError("spectral_settest: every set must hold 1 to %d markers" % SETTEST_MAX_MARKERS)
+    if idx.size and idx.min() < 0:
+        raise ValueError("spectral_settest: the sets hold 0-based markers")
+    if not (np.all(np.isfinite(w)) and np.all(w >= 0.0)):
+        raise ValueError("spectral_settest: the weights must be finite and >= 0")
+    UtX = _f64F(UtX)
+    k = m.size
+    L = _lib.load()
+    ctx = context(device)
+    stat = np.full((max(k, 1), 7), np.nan)
+    info = np.zeros((max(k, 1), 2), dtype=np.int32)
+    sc = np.zeros(max(idx.size, 1)) if scores else None
+    cv = np.zeros(max(int(np.sum(m * m)), 1)) if cov else None
+    _check(ctx, L.eagle_spectral_settest(ctx, _dp(lam), _dp(UtX), _dp(Uty), UtX.shape[1], float(varE), float(varG), k, ptr.ctypes.data_as(c_lp),
+                                         idx.ctypes.data_as(c_lp) if idx.size else np.zeros(1, dtype=np.int64).ctypes.data_as(c_lp),
+                                         _dp(w) if w.size else _dp(np.zeros(1)), _dp(stat), info.ctypes.data_as(C.POINTER(C.c_int32)),
+                                         _dp(sc) if scores else None, _dp(cv) if cov else None))
+    out = {"stat": stat[:k], "info": info[:k]}
+    if scores:
+        out["score"] = [sc[ptr[o]:ptr[o + 1]].copy() for o in range(k)]
+    if cov:
+        off = np.concatenate([[0], np.cumsum(m * m)])
+        out["cov"] = [cv[off[o]:off[o + 1]].reshape(m[o], m[o]).copy() for o in range(k)]
+    return out
+
+
 def calculate_reduced_a_rcpp(f_name_ascii, varG, P, y, max_memory_in_Gbytes, dims, selected_loci, quiet=True,
                              message=None, device=0):
     L = _lib.load()

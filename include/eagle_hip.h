@@ -1303,6 +1303,60 @@ int eagle_spectral_rows(eagle_ctx* ctx, const long* idx, long k, double* out);
 int eagle_spectral_lmm(eagle_ctx* ctx, const double* lambda, const double* UtX, const double* Uty, int c, int reml, double theta0, double tol,
                        int max_iter, const long* idx, long nidx, double* stat_out, int32_t* info_out);
 
+/* ---------------------------------------------------------------------------------------------
+ * 1d''. Tests of marker SETS under the mixed model (no counterpart in the reference): is a gene, a window or a candidate region as a
+ *     whole associated with the trait?  The burden test and SKAT (the sequence kernel association test, Wu et al. 2011) under the null
+ *     model's variance components, as EMMAX-SKAT / famSKAT define them.  eagle_spectral_scan gives each marker's score a_i and vara_i =
+ *     varG^2 m_i^T P m_i; a set needs the COVARIANCES varG^2 m_i^T P m_j of its markers, which this call forms from the resident Z.
+ *     csrc/eagle_settest.hip, k_settest_gram; restated in numpy by r_api.settest_host; the p-values are host work (r_api.skat_pvalue).
+ *
+ *     Notation as sections 1d and 1d'.  K = U diag(lambda) U^T;  d_k = 1 / (varE + varG lambda_k);  Xt = U^T X (n x c, 1 <= c <= 14, the
+ *     intercept column included);  yt = U^T y;  z_j = row j of the resident Z.
+ *
+ *     A set S has the markers j_1 .. j_m, 1 <= m <= SETTEST_MAX_MARKERS = 64, and a weight omega_1 .. omega_m per marker, finite and
+ *     >= 0.  The sets arrive in CSR form: set_ptr[nsets + 1], set_idx[] (0-based markers), omega[].  A marker may be in many sets.
+ *
+ *     Per set, in this order:
+ *       1. the augmented weighted Gram G = A^T diag(d) A of A = [z_j1 .. z_jm | Xt | yt] (n x (m + c + 1)), with the blocks G_zz, G_zx,
+ *          G_zy, G_xx, G_xy; the reduction over the n eigen-directions runs on v_mfma_f64_16x16x4_f64;
+ *       2. the Cholesky factor of G_xx, a pivot tested against LMM_PIVOT_REL times its diagonal entry of G_xx: a pivot not above it is
+ *          an argument error of the whole call (X^T H^-1 X is not positive definite, as eagle_spectral_scan_traits reports it; G_xx is
+ *          the same for every set).  Then B = G_xx^-1 [G_xz | G_xy];
+ *       3. the scores s = varG (G_zy - G_zx B_y) and their covariance Phi = varG^2 (G_zz - G_zx B_z): the a, and the matrix whose
+ *          diagonal is the vara, of eagle_spectral_scan for the same operands;
+ *       4. the degenerate-marker rule: a marker with Phi_jj <= LMM_PIVOT_REL varG^2 (G_zz)_jj (a monomorphic marker, a marker in the
+ *          span of X) gets s_j = 0, row and column j of Phi are set to exactly 0, and it is counted in n_degenerate;
+ *       5. with W = diag(omega) and Aw = W Phi W:  Q = sum_j omega_j^2 s_j^2,  Ub = sum_j omega_j s_j,  Vb = omega^T Phi omega,
+ *          c_r = tr(Aw^r) for r = 1 .. 4  (c_2 = |Aw|_F^2, c_3 = tr(Aw Aw^2), c_4 = |Aw^2|_F^2);
+ *       6. Phi is written symmetric bit for bit: the mirror is a copy of the lower triangle.
+ *
+ *     stat_out[7 o ..] = (Q, Ub, Vb, c_1, c_2, c_3, c_4), info_out[2 o ..] = (code, m - n_degenerate) for set o.  Codes: 0 ok; 2 nothing
+ *     left (Vb <= 0 or c_2 <= 0: every marker degenerate or of weight 0) -- the seven statistics are NaN.  score_out (one double per CSR
+ *     entry: s_j) and cov_out (the sets packed one after another, m_s^2 doubles each, row-major: Phi) may each be NULL.
+ *
+ *     From these the host forms (r_api.SetTest):  burden  stat = Ub^2 / Vb ~ chi^2_1, beta = varG Ub / Vb (the beta_p3d convention);
+ *     SKAT  p = P(sum_i lambda_i chi^2_1,i > Q), lambda = eig(Aw), by the modified moment matching of Liu et al. (2009) on c_1 .. c_4
+ *     and, for small p, by a saddlepoint approximation on the eigenvalues of a second call's cov_out.
+ *
+ *     A set's result depends only on its rows of Z, its weights and the staged operands: the same bits for any order of the sets, for a
+ *     set listed twice and for a second call (chunk r of 64 eigen-directions belongs to wave r mod 4, the four partial Grams are added in
+ *     wave order).  Bit equality under a permutation of the markers WITHIN a set is not claimed; bit equality with the host restatement
+ *     is not claimed either.  Not done: sets above 64 markers, SKAT-O's rho grid, re-estimating delta per set, case/control traits, a
+ *     .bed route, more than one device.
+ *
+ *     eagle_spectral_settest runs on the Z of the last eagle_spectral_prepare.  lambda: n; UtX: n x c column-major; Uty: n.  Argument
+ *     errors (EAGLE_ERR_ARG with a message) decided before the context is used -- with ctx == NULL their text is in eagle_open_error():
+ *     a NULL pointer (score_out and cov_out excepted), c outside [1, 14], nsets < 0, varE or varG not finite, set_ptr not non-decreasing
+ *     from 0, an empty set, a set above 64 markers, a negative or non-finite weight, a negative marker index; then: no context, a
+ *     multi-device context (single device only), no eagle_spectral_prepare, n <= c + 1; then what needs the n and L of the resident Z: a
+ *     marker index >= L, varE + varG lambda_k <= 0 or not finite, a non-finite entry of UtX or Uty.  nsets == 0 returns EAGLE_OK.
+ *     (A context whose Z was prepared from a marker range holds the markers [first, first + L): an index outside it is out of range.)
+ * ------------------------------------------------------------------------------------------- */
+#define SETTEST_MAX_MARKERS 64
+int eagle_spectral_settest(eagle_ctx* ctx, const double* lambda, const double* UtX, const double* Uty, int c, double varE, double varG,
+                           long nsets, const long* set_ptr, const long* set_idx, const double* omega, double* stat_out, int32_t* info_out,
+                           double* score_out, double* cov_out);
+
 /* Replaces the R tail of .find_qtl:  tsq <- a^2/vara ; which(tsq == max(tsq, na.rm=TRUE))[1]
  *                                                E/R/find_qtl.R:71-83
  * Evaluated on the device on the a / vara of the LAST eagle_calculate_a_and_vara call of this ctx (still in
