@@ -9,7 +9,9 @@ mirror of the reference interface used by tests, bench.py and the sharded multi-
                 Score, ProjectPCA, MarkerEffects, Predict (the fitted model used on any panel with the same markers);
                 GWAS (per-marker mixed-model tests: the P3D score test and the exact test with delta re-estimated), lmm_host
                 SetTest (burden and SKAT tests of marker sets under the mixed model), settest_host, skat_pvalue,
-                sets_from_windows, sets_from_table
+                sets_from_windows, sets_from_table;
+                MaxT (max(T) permutation p-values of every marker: EMP1 and the family-wise EMP2), maxt_host,
+                maxt_permutations_host, maxt_merge
   host_model -- dense n x n model algebra that stays on host LAPACK by design
   sharded    -- marker-sharded multi-GPU scan / MM^T (one process per GPU, torch.distributed over RCCL)
   synth      -- seeded synthetic genotypes of the benchmark shapes

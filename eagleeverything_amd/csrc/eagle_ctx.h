@@ -301,6 +301,23 @@ extern "C" int eagle_dev_group_bedmask(eagle_ctx* ctx, const int32_t* labels, lo
 extern "C" int eagle_dev_bed_group_counts(eagle_ctx* ctx, const uint8_t* bed, long rows, long n, int K, const uint32_t* planes, const int32_t* sizes,
                                           int32_t* counts, void* stream);
 extern "C" int eagle_dev_fisher_2x2(eagle_ctx* ctx, const int32_t* tables, long L, double* p, void* stream);
+// max(T) permutation testing (eagle_maxt.hip; include/eagle_hip.h section 1b''''vi), device pointers throughout.  keys: nr x NP2 uint64,
+// NP2 = the power of two >= N, sorted per row on return (the low 16 bits of a row = pi).  op: int8 [P][Rtot][ld], rows r0 .. r0 + nr
+// written from the sorted keys, an int32 table perm[nr][N], or the identity (both NULL); rank[n] = position of an individual or -1, tu[N]
+// = the trait of the used individuals.  counts[rows][1][3] of the `used` group -> S, V.  The tile: obs = 1 writes dobs / keyobs from the
+// one-arrangement operand of the trait itself, obs = 0 reads dobs, adds to count1 and writes one (key, marker) partial per tile and
+// permutation at tile_base + tile; S, V, dobs, keyobs, count1 start at the window's first row, row_base = that row's marker index.
+extern "C" int eagle_dev_maxt_permutations(eagle_ctx* ctx, uint64_t seed, long r_first, long nr, long N, long NP2, const uint16_t* strata_u,
+                                           uint64_t* keys, void* stream);
+extern "C" int eagle_dev_maxt_operand(eagle_ctx* ctx, const uint64_t* keys, long NP2, const int32_t* perm, long N, const int32_t* rank,
+                                      const int32_t* tu, long n, long ld, int P, long Rtot, long r0, long nr, int8_t* op, void* stream);
+extern "C" int eagle_dev_maxt_sv(eagle_ctx* ctx, const int32_t* counts, long rows, long N, int32_t* S, int64_t* V, void* stream);
+extern "C" int eagle_dev_maxt_width(int P);
+extern "C" int eagle_dev_maxt_tile(eagle_ctx* ctx, int obs, const int8_t* Mt8, long rows, long n, long ld, const int8_t* op, long ldop, int P, long R,
+                                   long Rstride, long N, long T, const int32_t* S, const int64_t* V, int64_t* dobs, double* keyobs, int32_t* count1,
+                                   double* pkey, int32_t* parg, long tile_base, long row_base, void* stream);
+extern "C" int eagle_dev_maxt_finish(eagle_ctx* ctx, const double* pkey, const int32_t* parg, long ntiles, long R, double* maxkey, int32_t* argmax,
+                                     void* stream);
 // Logistic regression per marker (eagle_logit.hip; include/eagle_hip.h section 1b''''iv), device pointers throughout, one row window.
 // X16: n64 x 16 fp64, n64 = n rounded up to 64, row i = the c = p - 1 covariates of individual i then zeros; valid_y: n64 bytes, 0 = not
 // used, 2 = control, 3 = case; both zero from individual n on, and the X16 rows of unused individuals zero.  beta0[c]: the start.

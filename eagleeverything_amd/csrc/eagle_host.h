@@ -791,4 +791,76 @@ static inline EAGLE_HD double epi_stat(const EpiTrait& t, const EpiMarker& a, co
 static inline EAGLE_HD bool epi_pair_tested(long i, long j, const int32_t* chrom, long gap) {
     return !(j - i <= gap && (!chrom || chrom[i] == chrom[j]));
 }
+
+// ------------------------------------------------------------------------------------------------
+// max(T) permutation testing (include/eagle_hip.h section 1b''''vi): the mixer and the sort key of the seeded permutations, the
+// sign-magnitude base-128 digits of the trait, the check of an explicit permutation row and the argument rule of eagle_maxt.  The
+// kernels of eagle_maxt.hip call the first three as they stand.
+// ------------------------------------------------------------------------------------------------
+#define MAXT_MAX_N 65535L
+#define MAXT_TMAX 1000000
+#define MAXT_RMAX 1024L
+// h(seed, r, j): the top 32 bits of the splitmix64 finaliser of seed + (r 2^16 + j + 1) 0x9E3779B97F4A7C15 (mod 2^64)
+static inline EAGLE_HD uint32_t maxt_mix(uint64_t seed, uint64_t r, uint64_t j) {
+    uint64_t z = seed + ((r << 16) + j + 1) * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return (uint32_t)(z >> 32);
+}
+static inline EAGLE_HD uint64_t maxt_key64(uint64_t seed, uint64_t r, uint64_t j, uint32_t stratum) {
+    return ((uint64_t)stratum << 48) | ((uint64_t)maxt_mix(seed, r, j) << 16) | j;
+}
+// t = sign(t) (m0 + 128 m1 + 16384 m2) with m in [0, 127]: digit p = sign(t) m_p lies in [-127, 127]; |t| <= 2,097,151
+static inline EAGLE_HD void maxt_digits(int32_t t, int8_t d[3]) {
+    const int32_t m = t < 0 ? -t : t, sg = t < 0 ? -1 : 1;
+    d[0] = (int8_t)(sg * (m & 127));
+    d[1] = (int8_t)(sg * ((m >> 7) & 127));
+    d[2] = (int8_t)(sg * ((m >> 14) & 127));
+}
+// the planes a trait of largest magnitude tmax needs: 1 up to 127, 2 up to 16,383, else 3
+static inline int maxt_planes(int64_t tmax) { return tmax <= 127 ? 1 : (tmax <= 16383 ? 2 : 3); }
+// |d| = |N c - S T| <= 2 N^2 tmax: below 2^53 with N <= 65535 and tmax <= 10^6, so d converts to fp64 exactly
+static inline bool maxt_bound_ok(int64_t N, int64_t tmax) { return 2.0 * (double)N * (double)N * (double)tmax < 9007199254740992.0; }
+// whether row[0 .. N) is a permutation of 0 .. N - 1; seen: N bytes of scratch
+static inline bool maxt_is_permutation(const int32_t* row, long N, uint8_t* seen) {
+    memset(seen, 0, (size_t)N);
+    for (long k = 0; k < N; k++) {
+        if (row[k] < 0 || row[k] >= N || seen[row[k]]) return false;
+        seen[row[k]] = 1;
+    }
+    return true;
+}
+// What is wrong with a call of eagle_maxt, or NULL; *N_out = the used individuals, *tmax_out = max |t| among them.
+static inline const char* maxt_arg_error(long n, long L, const int32_t* t, const uint8_t* used, const int32_t* strata, long first, long R,
+                                         const int32_t* perm, long* N_out, int64_t* tmax_out) {
+    if (n <= 0 || L <= 0) return "dims must be positive";
+    if (L > 0x7fffffffL) return "2^31 markers or more";
+    if (n > MAXT_MAX_N) return "more than 65535 individuals";
+    if (first < 1) return "first must be at least 1";
+    if (R < 1 || R > MAXT_RMAX) return "R outside [1, EAGLE_MAXT_RMAX = 1024]";
+    if (first + R > 2147483648L) return "first + R above 2^31";
+    long N = 0, k0 = -1;
+    int64_t tmax = 0;
+    bool constant = true;
+    for (long i = 0; i < n; i++) {
+        if (used && !used[i]) continue;
+        if (t[i] > MAXT_TMAX || t[i] < -MAXT_TMAX) return "a trait value beyond EAGLE_MAXT_TMAX = 1000000 in absolute value";
+        if (!perm && strata && (strata[i] < 0 || strata[i] > 65535)) return "a stratum outside [0, 2^16)";
+        if (k0 < 0) k0 = i;
+        else if (t[i] != t[k0]) constant = false;
+        tmax = std::max<int64_t>(tmax, t[i] < 0 ? -(int64_t)t[i] : t[i]);
+        N++;
+    }
+    if (N < 3) return "fewer than 3 used individuals";
+    if (constant) return "the trait is constant among the used individuals (W = 0)";
+    if (perm) {
+        std::vector<uint8_t> seen((size_t)N);
+        for (long r = 0; r < R; r++)
+            if (!maxt_is_permutation(perm + (size_t)r * (size_t)N, N, seen.data())) return "a row of perm is no permutation of 0 .. N - 1";
+    }
+    *N_out = N;
+    *tmax_out = tmax;
+    return nullptr;
+}
 #endif

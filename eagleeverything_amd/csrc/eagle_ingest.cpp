@@ -1024,6 +1024,152 @@ extern "C" int eagle_group_counts(eagle_ctx* ctx, const char* f_name_ascii_Mt, c
     return EAGLE_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// max(T) permutation testing (include/eagle_hip.h section 1b''''vi; kernels in eagle_maxt.hip).  eagle_group_counts' routes.  The
+// operand of all R arrangements is built once per call (the seeded keys are sorted in blocks of at most MAXT_SORT_BYTES); per window of
+// marker rows: S and V from the `used` group's counts, the observed pass, the permuted pass.  The finish merges the tiles' partials.
+// ---------------------------------------------------------------------------------------------------------------
+static_assert(MAXT_MAX_N == EAGLE_MAXT_MAX_N && MAXT_TMAX == EAGLE_MAXT_TMAX && MAXT_RMAX == EAGLE_MAXT_RMAX, "eagle_host.h and eagle_hip.h disagree");
+#define MAXT_SORT_BYTES (128L << 20)
+extern "C" int eagle_maxt(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long dims[2], const int32_t* t, const uint8_t* used,
+                          const int32_t* strata, uint64_t seed, long first, long R, const int32_t* perm, double max_memory_in_Gbytes,
+                          int64_t* d_obs, int64_t* V, double* key_obs, int32_t* count1, double* maxkey, int32_t* argmax) {
+    auto fail = [&](const char* what) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "maxt: %s", what);
+        return qc_fail(ctx, EAGLE_ERR_ARG, msg);
+    };
+    if (!f_name_ascii_Mt || !dims || !t || !d_obs || !V || !key_obs || !count1 || !maxkey || !argmax) return fail("NULL argument");
+    const long n = dims[0], L = dims[1];
+    long N = 0;
+    int64_t tmax = 0;
+    if (const char* bad = maxt_arg_error(n, L, t, used, strata, first, R, perm, &N, &tmax)) return fail(bad);
+    if (!maxt_bound_ok(N, tmax)) return fail("|d| would reach 2^53");
+    if (!ctx) return fail("no context");
+
+    // u_0 < ... < u_{N-1}; tu[k] = t[u_k]; rank_obs[i] = k of u_k = i; rank_fill[u_sigma[k]] = k (sigma: by stratum, then by position)
+    const int P = maxt_planes(tmax);
+    std::vector<int32_t> tu((size_t)N), rank_obs((size_t)n, -1), rank_fill, labels((size_t)n), u((size_t)N);
+    std::vector<uint16_t> su((size_t)N, 0);
+    int64_t T = 0;
+    for (long i = 0, k = 0; i < n; i++) {
+        const bool in = !used || used[i];
+        labels[(size_t)i] = in ? 0 : -1;
+        if (!in) continue;
+        u[(size_t)k] = (int32_t)i;
+        tu[(size_t)k] = t[i];
+        T += t[i];
+        rank_obs[(size_t)i] = (int32_t)k;
+        if (strata && !perm) su[(size_t)k] = (uint16_t)strata[i];
+        k++;
+    }
+    const bool stratified = strata && !perm;
+    if (stratified) {
+        std::vector<int32_t> sigma((size_t)N);
+        for (long k = 0; k < N; k++) sigma[(size_t)k] = (int32_t)k;
+        std::stable_sort(sigma.begin(), sigma.end(), [&](int32_t a, int32_t b) { return su[(size_t)a] < su[(size_t)b]; });
+        rank_fill.assign((size_t)n, -1);
+        for (long k = 0; k < N; k++) rank_fill[(size_t)u[(size_t)sigma[(size_t)k]]] = (int32_t)k;
+    }
+    int32_t sizes[EAGLE_GROUPS_MAX] = {0};
+    sizes[0] = (int32_t)N;
+    long NP2 = 2;
+    while (NP2 < N) NP2 <<= 1;
+
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const long ldh = (n + 15) / 16 * 16;
+    const long sort_rows = perm ? 0 : std::max(1L, std::min(R, MAXT_SORT_BYTES / (NP2 * 8)));
+    DevBuf d_lab, onehot, counts, d_tu, d_rank_obs, d_rank_fill, d_su, d_perm, keys, op, op_obs, dS, dV, dD, dK, dC, pkey, parg, dmax, darg;
+    HIPCHK(ctx, onehot.alloc((size_t)EAGLE_GROUPS_MAX * ldh));
+    HIPCHK(ctx, counts.alloc(sizeof(int32_t) * 3 * (size_t)L));
+    HIPCHK(ctx, d_tu.alloc(sizeof(int32_t) * (size_t)N));
+    HIPCHK(ctx, d_rank_obs.alloc(sizeof(int32_t) * (size_t)n));
+    HIPCHK(ctx, op.alloc((size_t)P * (size_t)R * ldh));
+    HIPCHK(ctx, op_obs.alloc((size_t)P * ldh));
+    HIPCHK(ctx, dS.alloc(sizeof(int32_t) * (size_t)L));
+    HIPCHK(ctx, dV.alloc(sizeof(int64_t) * (size_t)L));
+    HIPCHK(ctx, dD.alloc(sizeof(int64_t) * (size_t)L));
+    HIPCHK(ctx, dK.alloc(sizeof(double) * (size_t)L));
+    HIPCHK(ctx, dC.alloc(sizeof(int32_t) * (size_t)L));
+    HIPCHK(ctx, dmax.alloc(sizeof(double) * (size_t)R));
+    HIPCHK(ctx, darg.alloc(sizeof(int32_t) * (size_t)R));
+    int rc = group_upload(ctx, labels.data(), n, sizes, d_lab);
+    if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    HIPCHK(ctx, hipMemcpyAsync(d_tu.p, tu.data(), sizeof(int32_t) * (size_t)N, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(d_rank_obs.p, rank_obs.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemsetAsync(dC.p, 0, sizeof(int32_t) * (size_t)L, st));
+    const int32_t* rank_dev = d_rank_obs.as<int32_t>();
+    if (stratified) {
+        HIPCHK(ctx, d_rank_fill.alloc(sizeof(int32_t) * (size_t)n));
+        HIPCHK(ctx, d_su.alloc(sizeof(uint16_t) * (size_t)N));
+        HIPCHK(ctx, hipMemcpyAsync(d_rank_fill.p, rank_fill.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st));
+        HIPCHK(ctx, hipMemcpyAsync(d_su.p, su.data(), sizeof(uint16_t) * (size_t)N, hipMemcpyHostToDevice, st));
+        rank_dev = d_rank_fill.as<int32_t>();
+    }
+    // every later error path drains the stream first: kernels may be queued on this frame's buffers and host vectors
+    auto drain = [&](int code) { (void)hipStreamSynchronize(st); return code; };
+    rc = eagle_dev_group_onehot(ctx, d_lab.as<int32_t>(), n, onehot.as<int8_t>(), ldh, st);
+    if (!rc) rc = eagle_dev_maxt_operand(ctx, nullptr, NP2, nullptr, N, d_rank_obs.as<int32_t>(), d_tu.as<int32_t>(), n, ldh, P, 1, 0, 1, op_obs.as<int8_t>(), st);
+    if (rc) return drain(rc);
+    if (perm) {
+        const size_t pbytes = sizeof(int32_t) * (size_t)R * (size_t)N;
+        hipError_t e = d_perm.alloc(pbytes);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_perm.p, perm, pbytes, hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) return drain(eagle_fail_hip(ctx, e, "maxt: perm upload"));
+        rc = eagle_dev_maxt_operand(ctx, nullptr, NP2, d_perm.as<int32_t>(), N, rank_dev, d_tu.as<int32_t>(), n, ldh, P, R, 0, R, op.as<int8_t>(), st);
+    } else {
+        const hipError_t e = keys.alloc(sizeof(uint64_t) * (size_t)sort_rows * (size_t)NP2);
+        if (e != hipSuccess) return drain(eagle_fail_hip(ctx, e, "maxt: keys"));
+        for (long r0 = 0; r0 < R && !rc; r0 += sort_rows) {
+            const long nr = std::min(sort_rows, R - r0);
+            rc = eagle_dev_maxt_permutations(ctx, seed, first + r0, nr, N, NP2, stratified ? d_su.as<uint16_t>() : nullptr, keys.as<uint64_t>(), st);
+            if (!rc) rc = eagle_dev_maxt_operand(ctx, keys.as<uint64_t>(), NP2, nullptr, N, rank_dev, d_tu.as<int32_t>(), n, ldh, P, R, r0, nr, op.as<int8_t>(), st);
+        }
+    }
+    if (rc) return drain(rc);
+
+    ImageLines lines;
+    rc = lines.open(ctx, f_name_ascii_Mt, L, n, max_memory_in_Gbytes);
+    if (rc) return drain(rc);
+    const RowWindows ws = lines.disjoint(lines.stream_rows());
+    const long wcap = std::min(ws.cap, L), tiles_cap = ((L + wcap - 1) / wcap) * ((wcap + 127) / 128);
+    {
+        hipError_t e = pkey.alloc(sizeof(double) * (size_t)tiles_cap * (size_t)R);
+        if (e == hipSuccess) e = parg.alloc(sizeof(int32_t) * (size_t)tiles_cap * (size_t)R);
+        if (e != hipSuccess) return drain(eagle_fail_hip(ctx, e, "maxt: partials"));
+    }
+    long tile_base = 0;
+    rc = lines.each(ws, [&](const int8_t* img, long r0, long nr, long, long) {
+        if (tile_base + (nr + 127) / 128 > tiles_cap) return eagle_fail(ctx, EAGLE_ERR_ARG, "maxt: more tiles than planned");
+        int32_t* cw = counts.as<int32_t>() + 3 * (size_t)r0;
+        int32_t* Sw = dS.as<int32_t>() + r0;
+        int64_t* Vw = dV.as<int64_t>() + r0;
+        int64_t* Dw = dD.as<int64_t>() + r0;
+        double* Kw = dK.as<double>() + r0;
+        int32_t* Cw = dC.as<int32_t>() + r0;
+        int wrc = eagle_dev_group_counts(ctx, img, nr, n, lines.ld(), onehot.as<int8_t>(), ldh, 1, d_lab.as<int32_t>() + n, cw, st);
+        if (!wrc) wrc = eagle_dev_maxt_sv(ctx, cw, nr, N, Sw, Vw, st);
+        if (!wrc) wrc = eagle_dev_maxt_tile(ctx, 1, img, nr, n, lines.ld(), op_obs.as<int8_t>(), ldh, P, 1, 1, N, T, Sw, Vw, Dw, Kw, Cw, pkey.as<double>(),
+                                            parg.as<int32_t>(), tile_base, r0, st);
+        if (!wrc) wrc = eagle_dev_maxt_tile(ctx, 0, img, nr, n, lines.ld(), op.as<int8_t>(), ldh, P, R, R, N, T, Sw, Vw, Dw, Kw, Cw, pkey.as<double>(),
+                                            parg.as<int32_t>(), tile_base, r0, st);
+        tile_base += (nr + 127) / 128;
+        return wrc;
+    });
+    if (rc) return drain(rc);
+    rc = eagle_dev_maxt_finish(ctx, pkey.as<double>(), parg.as<int32_t>(), tile_base, R, dmax.as<double>(), darg.as<int32_t>(), st);
+    if (rc) return drain(rc);
+    HIPCHK(ctx, hipMemcpyAsync(d_obs, dD.p, sizeof(int64_t) * (size_t)L, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(V, dV.p, sizeof(int64_t) * (size_t)L, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(key_obs, dK.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(count1, dC.p, sizeof(int32_t) * (size_t)L, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(maxkey, dmax.p, sizeof(double) * (size_t)R, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(argmax, darg.p, sizeof(int32_t) * (size_t)R, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return EAGLE_OK;
+}
+
 // eagle_bed_marker_counts' windows through the staging ring; the K mask planes are built once per call.
 extern "C" int eagle_bed_group_counts(eagle_ctx* ctx, const char* bed_path, const long dims[2], const int32_t* labels, int K,
                                       double max_memory_in_Gbytes, int32_t* counts_out) {

@@ -2799,6 +2799,201 @@ def CaseControl(geno, status, bed=None, fisher=False, availmemGb=8, device=0):
     return case_control_from_counts(c, fisher=(lambda t: rcpp_api.fisher_2x2(t, device=device)) if fisher else None)
 
 
+# ---- max(T) permutation p-values (include/eagle_hip.h section 1b''''vi) ----
+def maxt_key64_host(seed, r, N, strata_used=None):
+    """key64(r, j), j < N, of section 1b''''vi -> uint64 (N): (stratum << 48) | (h << 16) | j with h the top 32 bits of the splitmix64
+    finaliser of seed + (r 2^16 + j + 1) 0x9E3779B97F4A7C15; uint64 arithmetic that wraps."""
+    u64 = np.uint64
+    N = int(N)
+    j = np.arange(N, dtype=u64)
+    s = np.zeros(N, dtype=u64) if strata_used is None else np.asarray(strata_used).astype(u64)
+    if s.size != N:
+        raise ValueError("maxt_key64_host: one stratum per used individual")
+    counter = np.full(N, int(r) << 16, dtype=u64) + j + u64(1)
+    z = np.full(N, int(seed) & (2 ** 64 - 1), dtype=u64) + counter * u64(0x9E3779B97F4A7C15)
+    z = (z ^ (z >> u64(30))) * u64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> u64(27))) * u64(0x94D049BB133111EB)
+    z = z ^ (z >> u64(31))
+    return (s << u64(48)) | ((z >> u64(32)) << u64(16)) | j
+
+
+def maxt_permutations_host(N, strata_used, seed, first, R):
+    """The seeded permutations first .. first + R - 1 of section 1b''''vi restated in numpy -> int32 (R, N), in the form the explicit
+    route takes: row q arranges the trait as t'[u_k] = t[u_row[k]].  strata_used: the stratum of every USED individual (None: one
+    stratum).  A stable sort of the 64-bit keys (maxt_key64_host); with sigma the order by (stratum, position) and pi the order of the
+    keys, row[sigma[k]] = pi[k]."""
+    N, R = int(N), int(R)
+    s = np.zeros(N, dtype=np.int64) if strata_used is None else np.asarray(strata_used).astype(np.int64)
+    sigma = np.argsort(s, kind="stable")
+    out = np.empty((R, N), dtype=np.int32)
+    for q in range(R):
+        out[q, sigma] = np.argsort(maxt_key64_host(seed, int(first) + q, N, strata_used), kind="stable")
+    return out
+
+
+def maxt_digit_planes(t):
+    """The int8 planes of the device's operand for integer trait values t (|t| <= 2,097,151) -> (P, planes int8 (P, len(t))): digit p of
+    sign(t) (m0 + 128 m1 + 16384 m2), m in [0, 127]; P = 1 up to max |t| = 127, 2 up to 16,383, else 3."""
+    tv = np.asarray(t, dtype=np.int64)
+    m, sg = np.abs(tv), np.sign(tv)
+    mx = int(m.max()) if m.size else 0
+    P = 1 if mx <= 127 else (2 if mx <= 16383 else 3)
+    return P, np.stack([(sg * ((m >> (7 * p)) & 127)).astype(np.int8) for p in range(P)])
+
+
+def maxt_host(Mt8, t, used, strata, seed, first, R, perm=None):
+    """rcpp_api.maxt restated in numpy: Mt8 = int8 (L, n) of -1 / 0 / +1 (marker-major), t int (n), used a mask or None, strata int (n) or
+    None -> the same dict of d_obs, V, key_obs, count1, maxkey, argmax, word for word.  int64 sums (every product is bounded by 2^53,
+    checked through _epi_mul), key = (d * d) / V as two fp64 operations."""
+    G = np.asarray(Mt8)
+    L, n = G.shape
+    tv = np.asarray(t, dtype=np.int64).ravel()
+    um = np.ones(n, dtype=bool) if used is None else np.asarray(used).astype(bool).ravel()
+    u = np.flatnonzero(um)
+    N, R = int(u.size), int(R)
+    Gu = G[:, u].astype(np.int64)
+    tu = tv[u]
+    S, Q, T = Gu.sum(axis=1), (Gu * Gu).sum(axis=1), int(tu.sum())
+    V = N * Q - S * S
+    if perm is None:
+        perm = maxt_permutations_host(N, None if strata is None else np.asarray(strata).ravel()[u], seed, first, R)
+    perm = np.asarray(perm, dtype=np.int64)
+    ST = np.asarray(_epi_mul(S, np.array([T])), dtype=np.int64)
+
+    def keys(c):
+        d = np.asarray(_epi_mul(np.array([N]), c), dtype=np.int64) - (ST if c.ndim == 1 else ST[:, None])
+        df = d.astype(np.float64)
+        Vf = V.astype(np.float64) if c.ndim == 1 else V.astype(np.float64)[:, None]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return d, np.where(Vf != 0, (df * df) / Vf, 0.0)
+
+    d_obs, key_obs = keys(Gu @ tu)
+    count1 = np.zeros(L, dtype=np.int32)
+    maxkey, argmax = np.zeros(R, dtype=np.float64), np.zeros(R, dtype=np.int32)
+    step = max(1, (1 << 22) // max(L, N))
+    for r0 in range(0, R, step):
+        d, k = keys(Gu @ tu[perm[r0:r0 + step]].T)
+        count1 += (np.abs(d) >= np.abs(d_obs)[:, None]).sum(axis=1).astype(np.int32)
+        maxkey[r0:r0 + step], argmax[r0:r0 + step] = k.max(axis=0), k.argmax(axis=0)
+    return {"d_obs": d_obs, "V": V, "key_obs": key_obs, "count1": count1, "maxkey": maxkey, "argmax": argmax}
+
+
+def maxt_from_raw(raw, t_used, kind, scale=1.0, first=1):
+    """MaxT's result from the raw outputs (rcpp_api.maxt or maxt_host) and the integer trait of the used individuals.  kind "cc": stat =
+    N r^2, the Cochran-Armitage trend chi-square; "qt": stat = (N - 2) r^2 / (1 - r^2), the slope's F(1, N - 2);  r^2 = key / W with W = N
+    sum t^2 - T^2 an exact Python int.  count2[m] = #{r : maxkey_r >= key_obs_m} by a sort of maxkey."""
+    from scipy import special
+    tu = [int(v) for v in np.asarray(t_used).ravel()]
+    N, T = len(tu), sum(tu)
+    W = N * sum(v * v for v in tu) - T * T
+    R = int(raw["maxkey"].size)
+    Wf = float(W)
+
+    def stat_of(key):
+        r2 = np.asarray(key, dtype=np.float64) / Wf
+        if kind == "cc":
+            return r2, float(N) * r2
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return r2, np.where(r2 < 1.0, float(N - 2) * r2 / (1.0 - r2), np.inf)
+
+    ok = raw["V"] != 0
+    r2, stat = stat_of(raw["key_obs"])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        beta = raw["d_obs"].astype(np.float64) / raw["V"].astype(np.float64) / float(scale)
+    p = special.chdtrc(1.0, stat) if kind == "cc" else special.fdtrc(1.0, float(N - 2), stat)
+    count1 = raw["count1"].astype(np.int64)
+    count2 = R - np.searchsorted(np.sort(raw["maxkey"]), raw["key_obs"], side="left").astype(np.int64)
+    nan = lambda a: np.where(ok, a, np.nan)                                                    # noqa: E731
+    return {"stat": nan(stat), "p": nan(p), "beta": nan(beta), "r2": nan(r2), "count1": count1, "count2": count2,
+            "emp1": nan((count1 + 1) / (R + 1.0)), "emp2": nan((count2 + 1) / (R + 1.0)), "max_stat": stat_of(raw["maxkey"])[1],
+            "argmax": raw["argmax"].copy(), "n_used": N, "R": R, "kind": kind, "scale": float(scale), "first": int(first),
+            "key_obs": raw["key_obs"].copy(), "maxkey": raw["maxkey"].copy(), "V": raw["V"].copy()}
+
+
+def maxt_merge(a, b):
+    """Two MaxT results of one panel, trait and seed over disjoint ranges of permutation ordinals (a second call with first=a["first"] +
+    a["R"]) -> the result of the union: count1 add, max_stat / argmax / maxkey concatenate in the order (a, b), count2 and the
+    empirical p-values are counted again."""
+    if a["kind"] != b["kind"] or a["n_used"] != b["n_used"] or not np.array_equal(a["key_obs"], b["key_obs"]):
+        raise ValueError("maxt_merge: the two results are not of one panel and trait")
+    if a["first"] + a["R"] > b["first"] and b["first"] + b["R"] > a["first"]:
+        raise ValueError("maxt_merge: the ranges of permutation ordinals overlap")
+    out = dict(a)
+    R = a["R"] + b["R"]
+    ok = a["V"] != 0
+    out["count1"] = a["count1"] + b["count1"]
+    for k in ("max_stat", "argmax", "maxkey"):
+        out[k] = np.concatenate([a[k], b[k]])
+    out["count2"] = R - np.searchsorted(np.sort(out["maxkey"]), a["key_obs"], side="left").astype(np.int64)
+    out["emp1"] = np.where(ok, (out["count1"] + 1) / (R + 1.0), np.nan)
+    out["emp2"] = np.where(ok, (out["count2"] + 1) / (R + 1.0), np.nan)
+    out["R"], out["first"] = R, min(a["first"], b["first"])
+    return out
+
+
+def maxt_trait(trait, within=None, kind="auto"):
+    """MaxT's preparation -> (t int32 (n), used bool (n), strata int32 (n) or None, kind, scale).  A trait of 1 / 0 / NaN is case/control
+    ("cc": t = the case indicator); any other is quantitative ("qt": t = quantise_trait of the non-NaN records); NaN / None records are not
+    used.  within: any labels (group_labels), the strata of the permutations; a used individual without a label raises ValueError."""
+    vals = list(np.asarray(trait, dtype=object).ravel())
+    ya = np.array([np.nan if v is None else float(v) for v in vals], dtype=np.float64)
+    used = ~np.isnan(ya)
+    if not np.all(np.isfinite(ya[used])):
+        raise ValueError("MaxT: a trait record is infinite")
+    if kind not in ("auto", "cc", "qt"):
+        raise ValueError("MaxT: kind must be 'auto', 'cc' or 'qt'")
+    binary = bool(np.all((ya[used] == 0) | (ya[used] == 1)))
+    if kind == "auto":
+        kind = "cc" if binary else "qt"
+    if kind == "cc" and not binary:
+        raise ValueError("MaxT: a case/control trait must hold 1 (case), 0 (control) or NaN / None (not used)")
+    if int(used.sum()) < 3:
+        raise ValueError("MaxT: fewer than 3 individuals with a trait record")
+    t, scale = np.zeros(ya.size, dtype=np.int32), 1.0
+    if kind == "cc":
+        t[used] = ya[used].astype(np.int32)
+    else:
+        t[used], scale = quantise_trait(ya[used])
+    if int(t[used].min()) == int(t[used].max()):
+        raise ValueError("MaxT: the trait is constant")
+    strata = None
+    if within is not None:
+        lab, names = group_labels(within)
+        if lab.size != ya.size:
+            raise ValueError("MaxT: within must hold one label per individual (%d)" % ya.size)
+        if np.any(lab[used] < 0):
+            raise ValueError("MaxT: an individual with a trait record has no label in within")
+        if len(names) > 65536:
+            raise ValueError("MaxT: more than 65,536 distinct labels in within")
+        strata = np.where(used, lab, 0).astype(np.int32)
+    return t, used, strata, kind, scale
+
+
+def MaxT(geno, trait, R=1000, seed=0, within=None, kind="auto", availmemGb=8, device=0, first=1):
+    """Permutation p-values of every marker of a panel against one trait (PLINK --assoc --mperm / --model trend --mperm; include/eagle_hip.h
+    section 1b''''vi): the R seeded permutations first .. first + R - 1 of the trait among the individuals that have a record, within the
+    groups of within= where given (Admixture(...)["assignment"], family ids), all on the device in exact integers.  trait: one record per
+    individual (maxt_trait: 1 / 0 / NaN is case/control, anything else quantitative; kind= forces either).
+    -> {"stat", "p": the trend chi-square with scipy.special.chdtrc (case/control) or the slope's F(1, N - 2) with fdtrc; "beta" per copy
+    of the allele that '2' stands for, in the trait's units, "r2"; "count1", "count2"; "emp1" = (count1 + 1) / (R + 1), the share of
+    permutations in which the marker's own statistic reaches the observed one, "emp2" = (count2 + 1) / (R + 1), the share whose largest
+    statistic over ALL markers reaches it (family-wise, max(T)); "max_stat" (R) and "argmax" (R): every permutation's largest statistic and
+    the lowest marker that attains it; "n_used", "R", "kind", "scale", "first", and "key_obs", "maxkey", "V" (the raw words maxt_merge
+    needs)}.  Monomorphic markers (V = 0) have NaN in every statistic and p-value.  A second call with first=first + R continues the run;
+    maxt_merge adds two results.  Covariates: pass a residual as the trait."""
+    n, L = int(geno["dim_of_ascii_M"][0]), int(geno["dim_of_ascii_M"][1])
+    t, used, strata, kind, scale = maxt_trait(trait, within, kind)
+    if t.size != n:
+        raise ValueError("MaxT: %d trait records for %d genotyped individuals" % (t.size, n))
+    if n > rcpp_api.MAXT_MAX_N:
+        raise ValueError("MaxT: more than 65,535 individuals")
+    if int(R) < 1 or int(first) < 1:
+        raise ValueError("MaxT: R and first must be at least 1")
+    raw = rcpp_api.maxt(geno["asciifileMt"], (n, L), t, used=None if used.all() else used, strata=strata, seed=seed, first=first, R=R,
+                        availmemGb=availmemGb, device=device)
+    return maxt_from_raw(raw, t[used], kind, scale, first)
+
+
 # ---- logistic regression per marker with covariates, Firth fallback (include/eagle_hip.h section 1b''''iv) ----
 _LOGIT_ETA_MAX, _LOGIT_STEP_MAX, _LOGIT_PIVOT_REL = 40.0, 5.0, 2.0 ** -40
 

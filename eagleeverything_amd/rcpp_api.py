@@ -1607,6 +1607,67 @@ def fisher_2x2(tables, device=0):
     return out
 
 
+# ---- max(T) permutation testing (include/eagle_hip.h section 1b''''vi); the statistics and p-values are r_api's ----
+MAXT_MAX_N = 65535
+MAXT_TMAX = 1000000
+MAXT_RMAX = 1024
+
+
+def maxt(fMt, dims, t, used=None, strata=None, seed=0, first=1, R=1000, perm=None, availmemGb=8, device=0):
+    """eagle_maxt -> {"d_obs" int64 (L), "V" int64 (L), "key_obs" fp64 (L), "count1" int32 (L), "maxkey" fp64 (R), "argmax" int32 (R)}: the
+    raw outputs of section 1b''''vi for the permutations first .. first + R - 1 of an integer trait t (|t| <= 10^6, one entry per
+    individual of Mt.ascii, dims = (n, L) of M).  used: a mask of the individuals that take part (None: all); strata: whole numbers in
+    [0, 2^16) within which the seeded permutations stay; perm: int (R, N) explicit permutations of the used individuals instead of the
+    seeded ones.  More than MAXT_RMAX = 1024 permutations run as several calls of the library, whose count1 add and whose maxkey and
+    argmax concatenate.  r_api.maxt_host restates it: the same words."""
+    n, nm = max(int(dims[0]), 0), max(int(dims[1]), 0)
+    first, R = int(first), int(R)
+
+    def whole(name, a, size, lo, hi):
+        v = np.asarray(a)
+        if v.ndim != 1 or v.size != size:
+            raise ValueError("maxt: %s must hold one entry per individual (%d)" % (name, size))
+        if v.dtype.kind not in "iufb" or not np.all(np.isfinite(v.astype(np.float64))) or not np.all(v == np.rint(v.astype(np.float64))):
+            raise ValueError("maxt: %s must hold whole numbers" % name)
+        return np.ascontiguousarray(np.clip(v.astype(np.int64), lo, hi), dtype=np.int32)
+
+    tv = whole("t", t, n, -MAXT_TMAX - 1, MAXT_TMAX + 1)                  # beyond the limit stays beyond it: the library's error
+    uv = None
+    if used is not None:
+        uv = np.asarray(used)
+        if uv.ndim != 1 or uv.size != n:
+            raise ValueError("maxt: used must hold one entry per individual (%d)" % n)
+        uv = np.ascontiguousarray(uv.astype(bool), dtype=np.uint8)
+    sv = None if strata is None else whole("strata", strata, n, -1, 65536)
+    N = n if uv is None else int(uv.sum())
+    pv = None
+    if perm is not None:
+        pa = np.asarray(perm)
+        if pa.ndim != 2 or pa.shape != (R, N) or pa.dtype.kind not in "iu":
+            raise ValueError("maxt: perm must be whole numbers of shape (R, N) = (%d, %d)" % (R, N))
+        pv = np.ascontiguousarray(np.clip(pa.astype(np.int64), -1, N), dtype=np.int32)
+    L = _lib.load()
+    u8p = C.POINTER(C.c_uint8)
+    out = {"d_obs": np.zeros(nm, dtype=np.int64), "V": np.zeros(nm, dtype=np.int64), "key_obs": np.zeros(nm, dtype=np.float64),
+           "count1": np.zeros(nm, dtype=np.int32), "maxkey": np.zeros(max(R, 0), dtype=np.float64), "argmax": np.zeros(max(R, 0), dtype=np.int32)}
+    r0 = 0
+    while True:
+        nr = R - r0 if R <= 0 else min(MAXT_RMAX, R - r0)                # R <= 0 goes through once: the library's error
+        c1 = np.zeros(nm, dtype=np.int32)
+        mk, am = np.zeros(max(nr, 1), dtype=np.float64), np.zeros(max(nr, 1), dtype=np.int32)
+        pc = None if pv is None else np.ascontiguousarray(pv[r0:r0 + nr])
+        _args_first(L.eagle_maxt, device, (os.fsencode(fMt), _dims(dims), tv.ctypes.data_as(_c_i32p), None if uv is None else uv.ctypes.data_as(u8p),
+                                           None if sv is None else sv.ctypes.data_as(_c_i32p), C.c_uint64(int(seed) & (2 ** 64 - 1)), first + r0, nr,
+                                           None if pc is None else pc.ctypes.data_as(_c_i32p), float(availmemGb),
+                                           out["d_obs"].ctypes.data_as(_c_i64p), out["V"].ctypes.data_as(_c_i64p), _dp(out["key_obs"]),
+                                           c1.ctypes.data_as(_c_i32p), _dp(mk), am.ctypes.data_as(_c_i32p)))
+        out["count1"] += c1
+        out["maxkey"][r0:r0 + nr], out["argmax"][r0:r0 + nr] = mk[:nr], am[:nr]
+        r0 += nr
+        if r0 >= R:
+            return out
+
+
 # ---- logistic regression per marker with covariates (include/eagle_hip.h section 1b''''iv); the p-values are r_api's ----
 LOGISTIC_MAX_COVARIATES = 15
 

@@ -1168,6 +1168,67 @@ int eagle_admixture_em(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long d
                        double max_memory_in_Gbytes, double* loglik_out);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1b''''vi. max(T) permutation p-values of every marker against one trait (no counterpart in the reference; PLINK's --assoc --mperm /
+ *     --model trend --mperm): per marker how often a permuted trait's statistic reaches the observed one (EMP1's count), and per
+ *     permutation the largest statistic over all markers (EMP2's reference distribution, Westfall and Young), which respects the LD
+ *     between the markers.  All sums are integers, so the device and a numpy restatement (r_api.maxt_host) agree with == on every output.
+ *
+ *     1. Inputs.  g in {-1, 0, +1} over the individuals of line m of Mt.ascii, dims = (n, L); a missing call of the source is a
+ *        heterozygote by now.  t[n] int32 with |t_i| <= EAGLE_MAXT_TMAX = 10^6.  used[n] bytes (non-zero = used) or NULL = everybody;
+ *        the used individuals are u_0 < ... < u_{N-1}.  strata[n] int32 in [0, 2^16) or NULL; only the entries of used individuals are
+ *        read.  seed uint64.  first >= 1 and R >= 1: this call makes the permutations with the ordinals first, ..., first + R - 1.
+ *        perm, optional: int32 [R][N], every row a permutation of 0 .. N - 1.  Limits: n <= EAGLE_MAXT_MAX_N = 65,535; 3 <= N;
+ *        R <= EAGLE_MAXT_RMAX = 1024 per call; first + R <= 2^31.  With a VIEW alias t, used and strata have one entry per kept
+ *        individual.
+ *     2. Integers, over the used individuals only.  S_m = sum g, Q_m = sum g^2, V_m = N Q_m - S_m^2;  T = sum t, W = N sum t^2 - T^2;
+ *        W = 0 (a constant trait) is an argument error.  For an arrangement t' of the trait c_m(t') = sum_k g_{u_k, m} t'_{u_k} and
+ *        d_m(t') = N c_m - S_m T.  Bounds: |c| <= N 10^6, so |N c| <= 65535^2 10^6 < 4.3 10^15, |S_m T| <= N . N 10^6 likewise, and
+ *        |d| < 8.6 10^15 < 2^53 = 9.007 10^15;  0 <= V_m <= N^2 < 2^32 (Cauchy-Schwarz below, Q <= N above).  Both convert to fp64
+ *        exactly.
+ *     3. Key.  key_m(t') = fl(fl(d d) / V_m) in fp64: the product and the quotient are rounded separately, nothing is contracted into
+ *        an FMA; key = 0 where V_m = 0 (a monomorphic marker).  r^2 = key / W;  the Cochran-Armitage trend chi-square of a 0/1 trait
+ *        is N r^2 and the F(1, N - 2) of the regression slope is (N - 2) r^2 / (1 - r^2): both increase with key, so the largest key is
+ *        the largest statistic.
+ *     4. Seeded permutation r >= 1.  For j < N, with counter = r 2^16 + j + 1 (all arithmetic mod 2^64):
+ *            z = seed + counter 0x9E3779B97F4A7C15;  z = (z ^ z >> 30) 0xBF58476D1CE4E5B9;  z = (z ^ z >> 27) 0x94D049BB133111EB;
+ *            z ^= z >> 31;  h = z >> 32
+ *        (the splitmix64 finaliser; h has 32 bits).  key64(r, j) = (strata[u_j] << 48) | (h << 16) | j, with stratum 0 when strata is
+ *        NULL: the keys of one r are distinct, and two equal hashes fall back to j -- about N^2 / 2^33 pairs per permutation, half a
+ *        pair at N = 65,535.  pi_r[k] = the j of the k-th smallest key64(r, .);  sigma[k] = the j of the k-th smallest (strata[u_j], j),
+ *        the identity without strata.  t^(r)[u_sigma[k]] = t[u_pi_r[k]].  Trait values never leave their stratum; with every individual
+ *        in its own stratum every permutation is the identity.  With perm given t^(r)[u_k] = t[u_perm[r - first][k]], and seed and strata
+ *        are ignored.  The rule fixes the result, not the sort: the device runs a bitonic network (csrc/eagle_maxt.hip).
+ *     5. Outputs.  d_obs[L] int64 = d_m(t), V[L] int64, key_obs[L] fp64 = key_m(t);  count1[L] int32 = #{r : |d_m(t^(r))| >= |d_obs,m|},
+ *        compared in int64;  maxkey[R] fp64 = max_m key_m(t^(r)) and argmax[R] int32 = the lowest m that attains it.  count1 depends on
+ *        (seed, first, R) alone: calls over [1, a] and [a + 1, R] add up to one call over [1, R], and their maxkey and argmax
+ *        concatenate.  Nothing depends on tiles, windows or the route: integer sums and an fp64 maximum are free of order.
+ *     6. Operand.  The device multiplies the int8 image with an int8 operand [P][R][ld] on v_mfma_i32_32x32x32_i8 (k_maxt_tile): plane p
+ *        of arrangement r holds digit p of t^(r) in sign-magnitude base 128, t = sign(t) (m_0 + 128 m_1 + 16384 m_2), m in [0, 127],
+ *        digit = sign(t) m_p in [-127, 127];  P = 1 for max |t| <= 127 (a 0/1 case indicator), 2 up to 16,383, else 3 (up to
+ *        2,097,151).  c = c_0 + 128 c_1 + 16384 c_2 in int64 in the tile's epilogue, which forms d, the count1 contributions and the
+ *        tile's largest key per permutation; no L x R array is stored.  S and Q come from eagle_group_counts' kernel with `used` as one
+ *        group; the observed pass is the same tile on the trait itself.
+ *
+ *     What is not claimed.  Agreement with the PLINK program is neither claimed nor tested, because it is not available: the tests hold
+ *     the outputs to loops over individuals on exact integers and fractions.  Out of scope: covariates (pass a residual as the trait), a
+ *     .bed route (N would differ per marker), adaptive early stopping (--perm), step-down corrections, permutation of the Logistic and
+ *     GWAS fits, several devices, sex chromosomes.
+ *
+ *     The file is read as eagle_group_counts reads it: the resident image where it lies, else row windows from the sidecar, the text or a
+ *     VIEW alias's source.  Single device: a multi-device context works on its first device.  Argument errors (EAGLE_ERR_ARG: a NULL
+ *     pointer, dims <= 0, n > 65,535, N < 3, |t| > 10^6, W = 0, a stratum outside [0, 2^16), first < 1, R outside [1, 1024],
+ *     first + R > 2^31, a perm row that is no permutation) are decided before the context is used; with ctx == NULL their text is in
+ *     eagle_open_error().
+ * ------------------------------------------------------------------------------------------- */
+#define EAGLE_MAXT_MAX_N 65535L
+#define EAGLE_MAXT_TMAX 1000000
+#define EAGLE_MAXT_RMAX 1024L
+
+int eagle_maxt(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long dims[2], const int32_t* t, const uint8_t* used, const int32_t* strata,
+               uint64_t seed, long first, long R, const int32_t* perm, double max_memory_in_Gbytes, int64_t* d_obs, int64_t* V,
+               double* key_obs, int32_t* count1, double* maxkey, int32_t* argmax);
+
+/* ---------------------------------------------------------------------------------------------
  * 1c. Dense n x n model algebra on the device (OPT-IN: north_star keeps calculateH / calculateP / emma.* on
  *     host LAPACK, and nothing above calls these).  Once the scan takes tens of milliseconds the ~10-15 O(n^3) base-R calls
  *     of a find_qtl iteration are the whole run time (the author's note MyPackage/MyREADME:1 names eigen(); his MAGMA
