@@ -1096,16 +1096,25 @@ __global__ __launch_bounds__(512, 2) void k_vara_i8p(const int8_t* __restrict__ 
     dA.st = 8 * ldi; dA.vE = lnA.voffE; dA.vO = lnA.voffO;
     dB.st = 8 * npi; dB.vE = lnB.voffE; dB.vO = lnB.voffO;
     const i32x4 rsA_raw = x_rsrc(Mt8 + row0 * ld, (unsigned)(rows_here * ld)), rs_none = x_rsrc(Mt8, 0);
+    // dma_arm runs once per stage between two k-steps, where every scalar instruction holds up the next MFMA: the two descriptors of
+    // the stage `nxt` stands on (the empty one past the last stage) are made where `nxt` changes tile, not per stage, and a step inside
+    // a tile is one add and one compare
+    i32x4 rsA_nxt, rsB_nxt;
+    auto nxt_tile = [&] {
+        rsA_nxt = nxt.valid ? rsA_raw : rs_none;
+        rsB_nxt = nxt.valid ? x_rsrc(Bsl + (long)nxt.ct * T8 * np, (unsigned)(T8 * npi)) : rs_none;
+    };
+    nxt_tile();
     auto dma_arm = [&](int into) {  // the sequence of the next stage to fetch, into buffer `into`
-        const bool on = nxt.valid;
         const unsigned base = lds0 + into * STG;
         dA.m0 = base + (w * 6) * 1024 - 1024;
         dB.m0 = base + TW_ABYTES + (w * 4) * 1024 - 1024;
         dA.so = (unsigned)((w * 6) * 8 * ldi + nxt.kt * BK8 - 8 * ldi);
         dB.so = (unsigned)((w * 4) * 8 * npi + nxt.kt * BK8 - 8 * npi);
-        dA.rs = on ? rsA_raw : rs_none;
-        dB.rs = on ? x_rsrc(Bsl + (long)nxt.ct * T8 * np, (unsigned)(T8 * npi)) : rs_none;
-        if (on) vit_advance(nxt, nct, pair1);
+        dA.rs = rsA_nxt;
+        dB.rs = rsB_nxt;
+        if (nxt.kt + 1 < nxt.nk) nxt.kt++;   // (past the last stage too: nothing is fetched there, whatever kt says)
+        else if (nxt.valid) { vit_advance(nxt, nct, pair1); nxt_tile(); }
     };
     dma_arm(1);
     tx_dma3(dA);
