@@ -11,7 +11,8 @@ mirror of the reference interface used by tests, bench.py and the sharded multi-
                 SetTest (burden and SKAT tests of marker sets under the mixed model), settest_host, skat_pvalue,
                 sets_from_windows, sets_from_table;
                 MaxT (max(T) permutation p-values of every marker: EMP1 and the family-wise EMP2), maxt_host,
-                maxt_permutations_host, maxt_merge
+                maxt_permutations_host, maxt_merge;
+                HapLD, HapBlocks (pairwise haplotype EM, D' and haplotype blocks), hap_ld_host, hap_blocks_host, sets_from_blocks
   host_model -- dense n x n model algebra that stays on host LAPACK by design
   sharded    -- marker-sharded multi-GPU scan / MM^T (one process per GPU, torch.distributed over RCCL)
   synth      -- seeded synthetic genotypes of the benchmark shapes

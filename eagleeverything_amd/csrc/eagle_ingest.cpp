@@ -1801,6 +1801,64 @@ extern "C" int eagle_ld_stats(eagle_ctx* ctx, const char* f_name_ascii_Mt, const
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// Pairwise haplotype EM, D' and the verdict masks (include/eagle_hip.h section 1b''''vii; the kernel in eagle_hapld.hip)
+// ---------------------------------------------------------------------------------------------------------------
+// eagle_ld_window's walk: a resident image is one launch; a file that is not resident is read in windows of w rows that start every
+// w - window rows.  Unlike eagle_ld_window a launch writes and counts only the markers its window OWNS -- all but its last `window`
+// markers, which the next window owns, and everything up to the end in the window that holds the last row -- so every output word and
+// every counted pair comes from one launch that held all `window` partners of its marker: the words of the resident pass.
+extern "C" int eagle_hap_ld(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long dims[2], long window, double tol, int max_iter, double fg_cut,
+                            double dprime_cut, double max_memory_in_Gbytes, uint64_t* recomb_mask_out, uint64_t* strong_mask_out,
+                            double* dprime_out, double* r2_out, int64_t* counts_out) {
+    if (!f_name_ascii_Mt || !dims || !counts_out) return qc_fail(ctx, EAGLE_ERR_ARG, "hap_ld: NULL argument");
+    const long n = dims[0], L = dims[1];
+    if (n <= 0 || L <= 0) return qc_fail(ctx, EAGLE_ERR_ARG, "hap_ld: dims must be positive");
+    if (n > 0x3fffffffL) return qc_fail(ctx, EAGLE_ERR_ARG, "hap_ld: 2^30 individuals or more");
+    if (window < 1 || window > 256) return qc_fail(ctx, EAGLE_ERR_ARG, "hap_ld: window must be in [1, 256]");
+    if (!(tol > 0.0 && tol < 1.0)) return qc_fail(ctx, EAGLE_ERR_ARG, "hap_ld: tol must be in (0, 1)");
+    if (max_iter < 1 || max_iter > 100000) return qc_fail(ctx, EAGLE_ERR_ARG, "hap_ld: max_iter must be in [1, 100000]");
+    if (!(fg_cut >= 0.0 && fg_cut <= 1.0)) return qc_fail(ctx, EAGLE_ERR_ARG, "hap_ld: fg_cut must be in [0, 1]");
+    if (!(dprime_cut >= 0.0 && dprime_cut <= 1.0)) return qc_fail(ctx, EAGLE_ERR_ARG, "hap_ld: dprime_cut must be in [0, 1]");
+    if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "hap_ld: no context");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const long wpr = (window + 63) / 64;
+    const size_t mask_bytes = sizeof(uint64_t) * (size_t)L * (size_t)wpr, band_bytes = sizeof(double) * (size_t)L * (size_t)window;
+    DevBuf rec, str, dp, r2, tot, counts, sq;
+    if (recomb_mask_out) HIPCHK(ctx, rec.alloc(mask_bytes));
+    if (strong_mask_out) HIPCHK(ctx, str.alloc(mask_bytes));
+    if (dprime_out) HIPCHK(ctx, dp.alloc(band_bytes));
+    if (r2_out) HIPCHK(ctx, r2.alloc(band_bytes));
+    HIPCHK(ctx, tot.alloc(sizeof(uint64_t) * 4));
+    HIPCHK(ctx, hipMemsetAsync(tot.p, 0, sizeof(uint64_t) * 4, ctx->stream));
+    ImageLines lines;
+    int rc = lines.open(ctx, f_name_ascii_Mt, L, n, max_memory_in_Gbytes);
+    if (rc) return rc;
+    const long ld = lines.ld();
+    const RowWindows ws = lines.resident() ? row_windows_disjoint(L, L) : row_windows_overlapped(L, ld_stream_rows(lines), window);
+    HIPCHK(ctx, counts.alloc(sizeof(int32_t) * 3 * (size_t)ws.cap));
+    HIPCHK(ctx, sq.alloc(sizeof(int32_t) * 2 * (size_t)ws.cap));
+    rc = lines.each(ws, [&](const int8_t* img, long r0, long nr, long c0, long c1) {
+        const int trc = ld_tile_sq(ctx, img, nr, n, ld, counts.as<int32_t>(), sq.as<int32_t>());
+        if (trc) return trc;
+        const long at = c0 - r0;   // the first owned row of the window
+        return eagle_dev_hap_ld(ctx, img + at * ld, nr - at, c1 - c0, n, ld, sq.as<int32_t>() + 2 * at, window, tol, max_iter, fg_cut, dprime_cut,
+                                rec.p ? rec.as<uint64_t>() + c0 * wpr : nullptr, str.p ? str.as<uint64_t>() + c0 * wpr : nullptr, wpr,
+                                dp.p ? dp.as<double>() + c0 * window : nullptr, r2.p ? r2.as<double>() + c0 * window : nullptr,
+                                tot.as<uint64_t>(), ctx->stream);
+    });
+    if (rc) return rc;
+    if (recomb_mask_out) HIPCHK(ctx, hipMemcpyAsync(recomb_mask_out, rec.p, mask_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (strong_mask_out) HIPCHK(ctx, hipMemcpyAsync(strong_mask_out, str.p, mask_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (dprime_out) HIPCHK(ctx, hipMemcpyAsync(dprime_out, dp.p, band_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (r2_out) HIPCHK(ctx, hipMemcpyAsync(r2_out, r2.p, band_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    uint64_t t4[4];
+    HIPCHK(ctx, hipMemcpyAsync(t4, tot.p, sizeof t4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (int c = 0; c < 4; c++) counts_out[c] = (int64_t)t4[c];
+    return EAGLE_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // Pairwise-complete LD from the .bed file (include/eagle_hip.h section 1b'''iv; kernels in eagle_bedld.hip)
 // ---------------------------------------------------------------------------------------------------------------
 namespace {

@@ -103,6 +103,13 @@ int eagle_dev_ld_partners(eagle_ctx* ctx, const double* band, long rows, long wi
 int eagle_dev_ld_reduce(eagle_ctx* ctx, const double* band, long rows, long window, long c_lo, long c_hi, long g0, const int32_t* chrom,
                         const int64_t* pos, long max_dist, const int64_t* edges, int nbins, uint64_t* U, int32_t* cnt, uint64_t* bin_sum,
                         int64_t* bin_pairs, void* stream);
+// Pairwise haplotype EM (eagle_hapld.hip; include/eagle_hip.h section 1b''''vii).  Mt8 / sq: the first of the `crows` markers the launch
+// OWNS, out of `rows` >= crows it holds (the markers behind the owned ones are the partners of the last of them).  recomb / strong (crows x
+// words_per_row uint64) and dprime / r2 (crows x window fp64) start at that marker's row, every word of the owned rows is written, each
+// may be null; counts: four uint64 totals on the device, ADDED to -- zero them before the first launch.
+int eagle_dev_hap_ld(eagle_ctx* ctx, const int8_t* Mt8, long rows, long crows, long n, long ld, const int32_t* sq, long window, double tol,
+                     int max_iter, double fg_cut, double dprime_cut, uint64_t* recomb, uint64_t* strong, long words_per_row, double* dprime,
+                     double* r2, uint64_t* counts, void* stream);
 // The exact line-score pass (eagle_score.hip; include/eagle_hip.h section 1b''''i), device pointers throughout.  B = the int8 digit image of
 // the T x cols int32 weights w: eagle_score_b_rows(T, plane_mask) rows of ld bytes (ld % 128 == 0), row rank(p) T + t = digit plane p of
 // column t for the planes p of plane_mask in increasing order, zero elsewhere.  out[r T + t] = sum_c w[t cols + c] img[r ld + c] for the

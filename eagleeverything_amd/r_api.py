@@ -3682,3 +3682,277 @@ def SetTest(trait, X, geno, sets, weights="equal", p_refine=1e-3, backend=None, 
     from . import am
     return am.SetTest(trait, X, geno, sets, weights=weights, p_refine=p_refine, backend=backend, map=map, availmemGb=availmemGb,
                       device=device, Zmat=Zmat)
+
+
+# ---- pairwise haplotype EM, D' and haplotype blocks (include/eagle_hip.h section 1b''''vii): the restatement in numpy and the interface ----
+def hap_ld_cells(n, si, qi, sj, qj, d, e, f, h):
+    """The nine cells of the 3 x 3 genotype table of a pair of markers from its integer sums (rule 2 of section 1b''''vii) -> dict of
+    int64 arrays "N00" .. "N22" (first digit: the number of B alleles at marker i); N11 is x, the double heterozygotes."""
+    si, qi, sj, qj, d, e, f, h = (np.asarray(a, dtype=np.int64) for a in (si, qi, sj, qj, d, e, f, h))
+    return {"N22": (e + f + h + d) // 4, "N00": (e - f - h + d) // 4, "N20": (e - f + h - d) // 4, "N02": (e + f - h - d) // 4,
+            "N12": (qj + sj - e - f) // 2, "N10": (qj - sj - e + f) // 2, "N21": (qi + si - e - h) // 2, "N01": (qi - si - e + h) // 2,
+            "N11": int(n) - qi - qj + e}
+
+
+def hap_ld_pairs_host(n, si, qi, sj, qj, d, e, f, h, tol=1e-10, max_iter=1000):
+    """Rules 3 to 5 of section 1b''''vii for arrays of pairs of POLYMORPHIC markers, vectorised over the pairs with a per-pair stop
+    mask and the device's order of elementwise fp64 operations -> {"p": fp64 (4, pairs) = pBB, pBA, pAB, pAA, "dprime", "r2", "pmin":
+    fp64, "code": int32 (0 converged, 1 stopped at max_iter), "iterations": int32}."""
+    c = hap_ld_cells(n, si, qi, sj, qj, d, e, f, h)
+    si, sj = np.asarray(si, dtype=np.int64), np.asarray(sj, dtype=np.int64)
+    kBB = (2 * c["N22"] + c["N21"] + c["N12"]).astype(np.float64)
+    kBA = (2 * c["N20"] + c["N21"] + c["N10"]).astype(np.float64)
+    kAB = (2 * c["N02"] + c["N01"] + c["N12"]).astype(np.float64)
+    kAA = (2 * c["N00"] + c["N01"] + c["N10"]).astype(np.float64)
+    x = c["N11"]
+    n = int(n)
+    T = np.float64(2 * n)
+    bi, bj = n + si, n + sj
+    pi, qi_ = bi.astype(np.float64) / T, (2 * n - bi).astype(np.float64) / T
+    pj, qj_ = bj.astype(np.float64) / T, (2 * n - bj).astype(np.float64) / T
+    pipj, piqj, qipj, qiqj = pi * pj, pi * qj_, qi_ * pj, qi_ * qj_
+    zero = x == 0
+    pBB, pBA, pAB, pAA = (np.where(zero, k / T, start) for k, start in ((kBB, pipj), (kBA, piqj), (kAB, qipj), (kAA, qiqj)))
+    code, iters = np.zeros(x.shape, dtype=np.int32), np.zeros(x.shape, dtype=np.int32)
+    live = np.flatnonzero(~zero)
+    xd = x.astype(np.float64)
+    it = 0
+    while live.size:
+        it += 1
+        u, v = pBB[live] * pAA[live], pBA[live] * pAB[live]
+        den = u + v
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t = np.where(den > 0.0, u / den, 0.5)
+        xt = xd[live] * t
+        xo = xd[live] - xt
+        nBB = (kBB[live] + xt) / T
+        delta = np.abs(nBB - pBB[live])
+        pBB[live], pAA[live], pBA[live], pAB[live] = nBB, (kAA[live] + xt) / T, (kBA[live] + xo) / T, (kAB[live] + xo) / T
+        iters[live] = it
+        done = delta <= tol
+        if it == int(max_iter):
+            code[live[~done]] = 1
+            break
+        live = live[~done]
+    D = pBB - pipj
+    dmax = np.where(D >= 0.0, np.minimum(piqj, qipj), np.minimum(pipj, qiqj))
+    dprime = np.clip(D / dmax, -1.0, 1.0)
+    r2 = (D * D) / ((pi * qi_) * (pj * qj_))
+    pmin = np.minimum(np.minimum(pBB, pBA), np.minimum(pAB, pAA))
+    return {"p": np.stack([pBB, pBA, pAB, pAA]), "dprime": dprime, "r2": r2, "pmin": pmin, "code": code, "iterations": iters}
+
+
+def _hap_pack_bits(bits):
+    """bool (L, window) -> uint64 (L, ceil(window / 64)), column o - 1 at bit (o - 1) % 64 of word (o - 1) // 64."""
+    L, window = bits.shape
+    wide = np.zeros((L, (window + 63) // 64 * 64), dtype=np.uint8)
+    wide[:, :window] = bits
+    return np.ascontiguousarray(np.packbits(wide, axis=1, bitorder="little")).view("<u8").astype(np.uint64).reshape(L, -1)
+
+
+def _hap_unpack_bits(mask, window):
+    """uint64 (L, ceil(window / 64)) -> bool (L, window)."""
+    m = np.ascontiguousarray(np.asarray(mask, dtype=np.uint64)).astype("<u8")
+    return np.unpackbits(m.view(np.uint8).reshape(m.shape[0], -1), axis=1, bitorder="little")[:, :int(window)].astype(bool)
+
+
+def hap_ld_host(Mt8, window, tol=1e-10, max_iter=1000, fg_cut=0.01, dprime_cut=0.8):
+    """rcpp_api.hap_ld restated in numpy: Mt8 = int8 (L, n) marker-major genotypes in {-1, 0, +1} (a missing call is a het) -> {"recomb",
+    "strong": uint64 (L, ceil(window / 64)), "dprime", "r2": fp64 (L, window), -2.0 / -1.0 for an undefined pair, "counts": int64 (4),
+    and for the tests "pmin", "pBB": fp64, "iterations", "code": int32 (L, window), 0 where undefined}.  The rule of include/eagle_hip.h
+    section 1b''''vii with the same order of elementwise operations: the same words as the device."""
+    G = np.asarray(Mt8)
+    L, n = G.shape
+    window = int(window)
+    if not 1 <= window <= 256:
+        raise ValueError("hap_ld_host: 1 <= window <= 256")
+    F = G.astype(np.float64)                                   # products and sums of small integers: exact in fp64 below 2^53
+    F2 = F * F
+    Gi = G.astype(np.int64)
+    s, q = Gi.sum(axis=1), (Gi * Gi).sum(axis=1)
+    b = n + s
+    poly = (b > 0) & (b < 2 * n) & (n >= 2)
+    dprime, r2 = np.full((L, window), -2.0), np.full((L, window), -1.0)
+    pmin, pBB = np.zeros((L, window)), np.zeros((L, window))
+    iters, code = np.zeros((L, window), dtype=np.int32), np.zeros((L, window), dtype=np.int32)
+    defined = np.zeros((L, window), dtype=bool)
+    batch, held = [], 0                                        # offsets are run together: the slowest pair of a batch sets its trip count
+
+    def run():
+        i, o = np.concatenate([b[0] for b in batch]), np.concatenate([b[1] for b in batch])
+        sums = [np.concatenate([b[2][k] for b in batch]) for k in range(4)]
+        res = hap_ld_pairs_host(n, s[i], q[i], s[i + o], q[i + o], sums[0], sums[1], sums[2], sums[3], tol, max_iter)
+        defined[i, o - 1] = True
+        dprime[i, o - 1], r2[i, o - 1], pmin[i, o - 1], pBB[i, o - 1] = res["dprime"], res["r2"], res["pmin"], res["p"][0]
+        iters[i, o - 1], code[i, o - 1] = res["iterations"], res["code"]
+
+    for o in range(1, min(window, L - 1) + 1):
+        ok = np.flatnonzero(poly[:-o] & poly[o:])              # markers i with j = i + o, both polymorphic
+        if not ok.size:
+            continue
+        A, B, A2, B2 = F[ok], F[ok + o], F2[ok], F2[ok + o]
+        batch.append((ok, np.full(ok.size, o), [np.rint(np.einsum("ij,ij->i", a, c)).astype(np.int64) for a, c in ((A, B), (A2, B2), (A2, B), (A, B2))]))
+        held += ok.size
+        if held >= 1 << 18:
+            run()
+            batch, held = [], 0
+    if batch:
+        run()
+    rec = defined & (pmin > fg_cut)
+    strong = defined & (np.abs(dprime) >= dprime_cut)
+    counts = np.array([defined.sum(), code.sum(), rec.sum(), strong.sum()], dtype=np.int64)
+    return {"recomb": _hap_pack_bits(rec), "strong": _hap_pack_bits(strong), "dprime": dprime, "r2": r2, "counts": counts, "pmin": pmin,
+            "pBB": pBB, "iterations": iters, "code": code}
+
+
+def _hap_reach(L, chrom, pos, kb):
+    """same(i, j) for i <= j: marker j may share a block that starts at i -- the same chromosome, and within kb of marker i when given."""
+    span = None if kb is None else int(round(float(kb) * 1000.0))
+    if span is not None and (pos is None or span < 1):
+        raise ValueError("hap_blocks_host: kb needs positions and must be at least 0.001")
+
+    def same(i, j):
+        if chrom is not None and chrom[j] != chrom[i]:
+            return False
+        return span is None or abs(int(pos[j]) - int(pos[i])) <= span
+    return same
+
+
+def hap_blocks_host(recomb, strong, window, chrom=None, pos=None, kb=None, method="fourgamete", min_snp=2):
+    """The partition of the map into haplotype blocks from the two verdict masks of hap_ld (uint64 (L, ceil(window / 64))), greedy in
+    map order -> (first int64 (B), last int64 (B), block_of int64 (L), -1 outside any reported block).
+    "fourgamete": the block [i, j] grows to j + 1 while j + 1 - i <= window, marker j + 1 lies on the chromosome of i (chrom: one label
+    per marker) and within kb kilobases of it (pos: base pairs), and no pair (k, j + 1), i <= k <= j, is RECOMBINANT; an undefined pair
+    does not object, so a monomorphic marker joins.  "spine" (Haploview's solid spine of LD): from i the largest j in reach with
+    STRONG(i, k) for every i < k <= j and STRONG(k, j) for every i <= k < j.  Either way the next block starts at j + 1, and blocks below
+    min_snp markers are not reported."""
+    window, min_snp = int(window), int(min_snp)
+    if method not in ("fourgamete", "spine"):
+        raise ValueError("hap_blocks_host: method is 'fourgamete' or 'spine'")
+    if not 1 <= window <= 256 or min_snp < 1:
+        raise ValueError("hap_blocks_host: 1 <= window <= 256 and min_snp >= 1")
+    bits = _hap_unpack_bits(recomb if method == "fourgamete" else strong, window)       # bits[k, j - k - 1]: the pair (k, j)
+    L = bits.shape[0]
+    chrom = None if chrom is None else np.asarray(chrom)
+    pos = None if pos is None else np.asarray(pos, dtype=np.int64)
+    same = _hap_reach(L, chrom, pos, kb)
+    first, last = [], []
+    block_of = np.full(L, -1, dtype=np.int64)
+    i = 0
+    while i < L:
+        j = i
+        if method == "fourgamete":
+            while j + 1 < L and j + 1 - i <= window and same(i, j + 1):
+                k = np.arange(i, j + 1)
+                if bits[k, j - k].any():
+                    break
+                j += 1
+        else:
+            reach = i
+            while reach + 1 < L and reach + 1 - i <= window and same(i, reach + 1) and bits[i, reach - i]:
+                reach += 1
+            for cand in range(reach, i, -1):
+                k = np.arange(i, cand)
+                if bits[k, cand - k - 1].all():
+                    j = cand
+                    break
+        if j - i + 1 >= min_snp:
+            block_of[i:j + 1] = len(first)
+            first.append(i)
+            last.append(j)
+        i = j + 1
+    return np.asarray(first, dtype=np.int64), np.asarray(last, dtype=np.int64), block_of
+
+
+def _hap_source(who, geno, map, kb):
+    """(n, L, map or None, chrom labels or None, pos int64 or None) of a HapLD / HapBlocks call."""
+    n, L = int(geno["dim_of_ascii_M"][0]), int(geno["dim_of_ascii_M"][1])
+    errs = []
+    map = _ld_map(who, map, geno, L, errs.append)
+    if map is False:
+        raise ValueError(who + ":" + errs[0])
+    if map is None:
+        if kb is not None:
+            raise ValueError("%s: kb= needs a map with Chr and Pos entries" % who)
+        return n, L, None, None, None
+    chrom = np.asarray([str(c) for c in map["Chr"]])
+    pos = np.asarray(map["Pos"]).ravel()
+    if not np.array_equal(pos.astype(np.int64), pos):
+        raise ValueError("%s: the map's positions must be whole numbers of base pairs" % who)
+    if kb is not None and int(round(float(kb) * 1000.0)) < 1:
+        raise ValueError("%s: kb must be at least 0.001" % who)
+    return n, L, map, chrom, pos.astype(np.int64)
+
+
+def HapLD(geno, window=50, map=None, kb=None, tol=1e-10, max_iter=1000, availmemGb=8, device=0):
+    """Lewontin's D' and the haplotype r2 of every pair of markers at most `window` <= 256 apart, from haplotype frequencies estimated
+    by EM on the unphased genotypes (include/eagle_hip.h section 1b''''vii; rcpp_api.hap_ld) -> {"dprime": fp64 (L, window), signed,
+    entry (i, o - 1) = the pair (i, i + o), NaN where the pair is not defined, "r2": likewise, "defined": bool (L, window), "counts":
+    int64 (4) of rcpp_api.hap_ld, "mean_abs_dprime": fp64 (window), the mean |D'| of the defined pairs per offset, NaN without one}.  A
+    pair is not defined beyond the panel's end or with a monomorphic member; with a map (ReadBim's dict) also across chromosomes, and
+    with kb= more than kb kilobases apart.  The EM starts at equilibrium (Haploview's); it is not PLINK's cubic solver."""
+    n, L, map, chrom, pos = _hap_source("HapLD", geno, map, kb)
+    window = int(window)
+    raw = rcpp_api.hap_ld(geno["asciifileMt"], (n, L), window, tol, max_iter, bands=True, masks=False, availmemGb=availmemGb, device=device)
+    defined = raw["r2"] >= 0.0
+    if chrom is not None:
+        span = None if kb is None else int(round(float(kb) * 1000.0))
+        for o in range(1, min(window, L - 1) + 1):
+            ok = chrom[:-o] == chrom[o:]
+            if span is not None:
+                ok &= np.abs(pos[o:] - pos[:-o]) <= span
+            defined[:L - o, o - 1] &= ok
+    dprime, r2 = np.where(defined, raw["dprime"], np.nan), np.where(defined, raw["r2"], np.nan)
+    cnt = defined.sum(axis=0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean = np.where(cnt > 0, np.where(defined, np.abs(raw["dprime"]), 0.0).sum(axis=0) / cnt, np.nan)
+    return {"dprime": dprime, "r2": r2, "defined": defined, "counts": raw["counts"], "mean_abs_dprime": mean}
+
+
+def HapBlocks(geno, method="fourgamete", window=50, map=None, kb=None, min_snp=2, fg_cut=0.01, dprime=0.8, tol=1e-10, max_iter=1000,
+              availmemGb=8, device=0):
+    """The haplotype blocks of a panel -> {"blocks": {"first", "last": int64 (B), 0-based markers, both ends included, "n_markers": int64,
+    "chrom": list of str ("" without a map), "start", "end": int64 (the markers' positions; the marker indices without a map),
+    "length": int64 = end - start + 1}, "block_of": int64 (L), the block of every marker, -1 outside any, "share": the share of markers
+    in blocks, "counts": int64 (4) of rcpp_api.hap_ld, "method", "window"}.  The pairwise verdicts come from the device (rcpp_api.hap_ld:
+    RECOMBINANT iff the smallest EM haplotype frequency is above fg_cut, STRONG iff |D'| >= dprime; include/eagle_hip.h section
+    1b''''vii), the partition is hap_blocks_host's: method "fourgamete" (Wang et al. 2002, PLINK's and Haploview's four-gamete rule) or
+    "spine" (Haploview's solid spine of LD), greedy in map order, cut at chromosome ends with a map (ReadBim's dict) and at kb kilobases
+    from the block's first marker with kb=.  Blocks below min_snp markers are not reported.  Gabriel's confidence-interval blocks are
+    out of scope.  sets_from_blocks turns the result into sets for SetTest."""
+    n, L, map, chrom, pos = _hap_source("HapBlocks", geno, map, kb)
+    window = int(window)
+    raw = rcpp_api.hap_ld(geno["asciifileMt"], (n, L), window, tol, max_iter, fg_cut, dprime, availmemGb=availmemGb, device=device)
+    first, last, block_of = hap_blocks_host(raw["recomb"], raw["strong"], window, chrom, pos, kb, method, min_snp)
+    at = np.arange(L, dtype=np.int64) if pos is None else pos
+    start, end = at[first], at[last]
+    blocks = {"first": first, "last": last, "n_markers": last - first + 1, "chrom": ["" if chrom is None else str(chrom[f]) for f in first],
+              "start": start, "end": end, "length": np.abs(end - start) + 1}
+    return {"blocks": blocks, "block_of": block_of, "share": float((block_of >= 0).mean()) if L else 0.0, "counts": raw["counts"],
+            "method": method, "window": window}
+
+
+def sets_from_blocks(blocks, max_markers=64, names=None):
+    """Haplotype blocks as sets -> {"sets": list of int64 arrays of 0-based markers, "names": list of str}, as sets_from_windows
+    returns them.  blocks: what HapBlocks returns, or its "blocks" table.  A block above max_markers <= 64 markers (SetTest's limit) is
+    cut into consecutive pieces of at most max_markers markers, named name/1, name/2, ...  names: one name per block; default
+    "chrom:first-last" ("first-last" without a chromosome)."""
+    tab = blocks["blocks"] if hasattr(blocks, "keys") and "blocks" in blocks else blocks
+    max_markers = int(max_markers)
+    if not 1 <= max_markers <= SETTEST_MAX_MARKERS:
+        raise ValueError("sets_from_blocks: 1 <= max_markers <= %d" % SETTEST_MAX_MARKERS)
+    first, last = np.asarray(tab["first"], dtype=np.int64).ravel(), np.asarray(tab["last"], dtype=np.int64).ravel()
+    chrom = list(tab["chrom"]) if "chrom" in tab else [""] * first.size
+    if first.size != last.size or len(chrom) != first.size or np.any(last < first) or np.any(first < 0):
+        raise ValueError("sets_from_blocks: a block is first <= last, both 0-based markers")
+    if names is not None and len(names) != first.size:
+        raise ValueError("sets_from_blocks: names must hold one name per block (%d)" % first.size)
+    sets, out = [], []
+    for b in range(first.size):
+        f, e = int(first[b]), int(last[b]) + 1
+        name = str(names[b]) if names is not None else "%s%d-%d" % (str(chrom[b]) + ":" if str(chrom[b]) else "", f, e - 1)
+        pieces = range(f, e, max_markers)
+        for k, a in enumerate(pieces):
+            sets.append(np.arange(a, min(a + max_markers, e), dtype=np.int64))
+            out.append(name if len(pieces) == 1 else "%s/%d" % (name, k + 1))
+    return {"sets": sets, "names": out}

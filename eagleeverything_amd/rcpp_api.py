@@ -1668,6 +1668,29 @@ def maxt(fMt, dims, t, used=None, strata=None, seed=0, first=1, R=1000, perm=Non
             return out
 
 
+# ---- pairwise haplotype EM and D' (include/eagle_hip.h section 1b''''vii); the blocks are r_api's ----
+def hap_ld(fMt, dims, window=50, tol=1e-10, max_iter=1000, fg_cut=0.01, dprime_cut=0.8, bands=False, masks=True, availmemGb=8, device=0):
+    """eagle_hap_ld -> {"recomb", "strong": uint64 (L, ceil(window / 64)), bit (o - 1) % 64 of word (o - 1) // 64 of row i = the verdict
+    on the pair of markers (i, i + o), 1 <= o <= window; with bands=True also "dprime" and "r2": fp64 (L, window), entry (i, o - 1), -2.0 /
+    -1.0 for an undefined pair; "counts": int64 (4) = the defined pairs, the pairs whose EM stopped at max_iter, the recombinant bits,
+    the strong bits}: the haplotype frequencies of every pair by EM from the unphased genotypes of Mt.ascii (dims = (n, L) of M), the
+    rule of section 1b''''vii.  masks=False leaves the two masks out.  r_api.hap_ld_host restates it: the same words."""
+    L = _lib.load()
+    nm, w = max(int(dims[1]), 0), int(window)
+    out = {"counts": np.zeros(4, dtype=np.int64)}
+    if masks:
+        out["recomb"] = np.zeros((nm, (w + 63) // 64 if w > 0 else 1), dtype=np.uint64)
+        out["strong"] = np.zeros_like(out["recomb"])
+    if bands:
+        out["dprime"] = np.zeros((nm, max(w, 1)), dtype=np.float64)
+        out["r2"] = np.zeros_like(out["dprime"])
+    _args_first(L.eagle_hap_ld, device, (os.fsencode(fMt), _dims(dims), w, float(tol), int(max_iter), float(fg_cut), float(dprime_cut),
+                                         float(availmemGb), out["recomb"].ctypes.data_as(_c_u64p) if masks else None,
+                                         out["strong"].ctypes.data_as(_c_u64p) if masks else None, _dp(out["dprime"]) if bands else None,
+                                         _dp(out["r2"]) if bands else None, out["counts"].ctypes.data_as(_c_i64p)))
+    return out
+
+
 # ---- logistic regression per marker with covariates (include/eagle_hip.h section 1b''''iv); the p-values are r_api's ----
 LOGISTIC_MAX_COVARIATES = 15
 

@@ -1229,6 +1229,66 @@ int eagle_maxt(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long dims[2], 
                double* key_obs, int32_t* count1, double* maxkey, int32_t* argmax);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1b''''vii. Pairwise haplotype frequencies, Lewontin's D' and the verdicts haplotype blocks are cut from (no counterpart in the
+ *     reference; PLINK's --r2 dprime and --blocks, Haploview): for every pair of markers at most `window` <= 256 apart the four
+ *     haplotype frequencies estimated from the unphased genotypes by EM, D', the haplotype r2, and two bits.  The genotype r2 of
+ *     1b'' cannot give them: the phase of the double heterozygotes is unknown, and D' needs the haplotype frequencies.  Integers until
+ *     a short fp64 epilogue whose order of operations is fixed, so the device and a numpy restatement (r_api.hap_ld_host) agree with ==
+ *     on every output.
+ *
+ *     1. Genotypes and marginals.  g in {-1, 0, +1} over the individuals of line m of Mt.ascii, dims = (n, L); a missing call is a het,
+ *        as everywhere on this route.  Allele B is the allele of '2'.  Per marker s = sum g and q = sum g^2 (k_marker_counts);
+ *        b_i = n + s_i is the number of B alleles out of 2n;  a marker is polymorphic iff 0 < b_i < 2n.
+ *     2. Pair sums and the 3 x 3 table.  For markers i < j four int32 sums over the individuals:  d = sum g_i g_j,  e = sum g_i^2 g_j^2,
+ *        f = sum g_i^2 g_j,  h = sum g_i g_j^2.  The nine cells N_ab (a, b = the number of B alleles at i and at j) are exact integers:
+ *            N22 = (e + f + h + d) / 4    N00 = (e - f - h + d) / 4    N20 = (e - f + h - d) / 4    N02 = (e + f - h - d) / 4
+ *            N12 = (q_j + s_j - e - f) / 2    N10 = (q_j - s_j - e + f) / 2    N21 = (q_i + s_i - e - h) / 2    N01 = (q_i - s_i - e + h) / 2
+ *            N11 = x = n - q_i - q_j + e      (the double heterozygotes, whose phase is unknown)
+ *     3. Known haplotype counts.  k_BB = 2 N22 + N21 + N12,  k_BA = 2 N20 + N21 + N10,  k_AB = 2 N02 + N01 + N12,
+ *        k_AA = 2 N00 + N01 + N10  (first letter: marker i);  k_BB + k_BA + k_AB + k_AA + 2x = 2n.
+ *     4. The EM, in fp64.  Every operation is a single correctly rounded multiplication, addition, subtraction or division
+ *        (the device code is compiled with contraction switched off), so nothing contracts into an FMA.  T = (double)(2n);  p_i = (double)b_i / T,
+ *        q_i = (double)(2n - b_i) / T, formed from the integer and never as 1 - p_i.  Start at equilibrium: pBB = p_i p_j, pBA = p_i q_j,
+ *        pAB = q_i p_j, pAA = q_i q_j.  With x = 0 there is no iteration: every p is k / T.  Otherwise repeat
+ *            u = pBB pAA;  v = pBA pAB;  den = u + v;  t = den > 0 ? u / den : 0.5;  xt = x t;  xo = x - xt;
+ *            the new pBB, pAA, pBA, pAB = (k_BB + xt) / T, (k_AA + xt) / T, (k_BA + xo) / T, (k_AB + xo) / T;
+ *            delta = |pBB_new - pBB|;  iterations += 1;
+ *            stop with code 0 when delta <= tol, else stop with code 1 when iterations = max_iter.
+ *        Defaults tol = 1e-10 and max_iter = 1000.  This is the local optimum reached from the equilibrium start, which is Haploview's
+ *        EM.  It is not PLINK's cubic solver, which compares all roots of the likelihood equation: where the likelihood has two
+ *        maxima the two can differ.
+ *     5. Statistics.  D = pBB - p_i p_j;  Dmax = min(p_i q_j, q_i p_j) when D >= 0, else min(p_i p_j, q_i q_j);  D' = D / Dmax, clamped to
+ *        [-1, 1];  r2_h = (D D) / ((p_i q_i)(p_j q_j));  pmin = the smallest of the four haplotype frequencies.
+ *     6. Verdicts.  RECOMBINANT: all four gametes are seen, iff pmin > fg_cut, strictly (default 0.01, Haploview's four-gamete
+ *        cutoff).  STRONG: iff |D'| >= dprime_cut (default 0.8).
+ *     7. Undefined pairs.  A pair with i + o >= L, or with a monomorphic member, is undefined: neither bit is set, D' is reported as
+ *        -2.0 and r2_h as -1.0.  With n = 1 no pair is defined: one individual says nothing about association.
+ *     8. Outputs.  recomb_mask_out and strong_mask_out have eagle_ld_window's shape, L x ceil(window / 64) uint64: bit o - 1 of row i
+ *        is the pair (i, i + o).  dprime_out and r2_out are L x window fp64, entry (i, o - 1).  Each of the four may be NULL (the two
+ *        bands are held whole on the device while the call runs: 16 L window bytes).  counts_out[4] = the defined pairs, the pairs
+ *        that stopped with code 1, the recombinant bits, the strong bits.  Every output word is written by one workgroup of one
+ *        launch that held all partners of its marker, and the totals are integers: nothing depends on tiles, windows or the route.
+ *
+ *     The kernel (k_hapld_tile, csrc/eagle_hapld.hip) has k_ld_tile's geometry on v_mfma_i32_32x32x32_i8 with four products per block
+ *     pair, g.g, g^2.g^2, g^2.g and g.g^2; only the genotype image is staged, g^2 is made in registers.
+ *
+ *     What is not claimed.  Agreement with the PLINK or Haploview programs is neither claimed nor tested, because neither is
+ *     available: the tests hold the outputs to counting loops, a scalar loop of this rule and the same EM at 40 digits.  Out of
+ *     scope: Gabriel's confidence-interval blocks (their likelihood grid needs log, which IEEE 754 does not fix), a .bed route with
+ *     pairwise-complete tables (nine products), a picks mode against listed loci, multi-marker haplotype frequencies inside a block,
+ *     several devices, sex chromosomes.
+ *
+ *     The file is read as eagle_ld_window reads it: the resident image where it lies, else row windows that overlap by `window` rows
+ *     from the sidecar, the text or a VIEW alias's source.  Single device: a multi-device context works on its first device.
+ *     Argument errors (EAGLE_ERR_ARG: a NULL path, dims or counts_out, dims <= 0, n > 2^30 - 1, window outside [1, 256], tol not in
+ *     (0, 1), max_iter outside [1, 100000], a cut outside [0, 1]) are decided before the context is used; with ctx == NULL their text is
+ *     in eagle_open_error().
+ * ------------------------------------------------------------------------------------------- */
+int eagle_hap_ld(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long dims[2], long window, double tol, int max_iter, double fg_cut,
+                 double dprime_cut, double max_memory_in_Gbytes, uint64_t* recomb_mask_out, uint64_t* strong_mask_out, double* dprime_out,
+                 double* r2_out, int64_t* counts_out);
+
+/* ---------------------------------------------------------------------------------------------
  * 1c. Dense n x n model algebra on the device (OPT-IN: north_star keeps calculateH / calculateP / emma.* on
  *     host LAPACK, and nothing above calls these).  Once the scan takes tens of milliseconds the ~10-15 O(n^3) base-R calls
  *     of a find_qtl iteration are the whole run time (the author's note MyPackage/MyREADME:1 names eigen(); his MAGMA
