@@ -148,7 +148,7 @@ struct eagle_ctx {
     void* stage_pin[2] = {nullptr, nullptr}; void* stage_raw[2] = {nullptr, nullptr}; size_t stage_cap = 0;  // tile streamer
     // per-device launch state (a process may hold one ctx per GPU): dynamic-LDS attributes set on this device, the kernel-form
     // switch (an EagleTune; written through tune_known only)
-    bool attr_vara[5] = {false, false, false, false, false};   // by VaraKernel
+    bool attr_vara[7] = {false, false, false, false, false, false, false};   // by VaraKernel
     bool attr_syrk_f4w = false, attr_zbuild_i8 = false, attr_vara_f6 = false, attr_gemv = false, attr_gemv2 = false, attr_w8_gemm = false, attr_knn_rows = false, attr_knn_rows_dist = false, attr_ldknn = false;
     uint32_t attr_bedld = 0;   // k_bedld_tile<NB, R2>: bit 2 (NB - 2) + R2
     int tune = TUNE_SHIPPED;
@@ -175,6 +175,10 @@ struct eagle_ctx {
     int64_t hbm_bytes = 0;
 };
 
+// Not a value of the switch (its list of names is closed): EAGLE_HIP_STAGE_GLUE=1 in the environment, read at every launch as the other
+// test hooks are, runs k_vara_i8p and k_w8_gemm_p in the form before the engine's stage step (eagle_t8.h) -- the DMA state and the read
+// addresses re-derived in C++ between the k-steps of every stage.  Same bits; A/B runs and tests/test_gpu_stage_step.py.
+static inline bool stage_glue_form() { const char* e = getenv("EAGLE_HIP_STAGE_GLUE"); return e && atoi(e) != 0; }
 // ---- what the switch decides: one predicate per question the launch code asks ----
 // The digit-slice scan (eagle_i8mfma.hip): its kernel, and with it the layout of W's digits, the image orientation and the pacing.
 // Decided by this one function at prepare (layout, orientation) and at launch; `ext`: the compact image of the digit extension.
@@ -182,7 +186,8 @@ struct eagle_ctx {
 //   asks for k_vara_i8 or k_vara_i8w; the lower image (each column tile from its diagonal block down to the last live stage of W,
 //   DESIGN 4.3) unless it asks for the upper one; paced workers from 32,768 padded individuals up -- under TUNE_SHIPPED and
 //   TUNE_VARA_UPPER only: every other value leaves the pacing off at any size (known behaviour of the A/B values)
-enum VaraKernel { VARA_I8 = 0, VARA_I8W, VARA_I8P, VARA_I8P_PACED, VARA_I8P_EXT };   // k_vara_i8, k_vara_i8w, k_vara_i8p<false>, <true>, <false, true>
+enum VaraKernel { VARA_I8 = 0, VARA_I8W, VARA_I8P, VARA_I8P_PACED, VARA_I8P_EXT,   // k_vara_i8, k_vara_i8w, k_vara_i8p<false>, <true>, <false, true>
+                  VARA_I8P_GLUE, VARA_I8P_EXT_GLUE };                                // k_vara_i8p<false, false, true>, <false, true, true> (stage_glue_form)
 struct VaraForm {
     VaraKernel kernel;
     bool lower;                                       // the lower image and its walk (k_vara_i8p only)
@@ -193,6 +198,7 @@ static inline VaraForm vara_form(const eagle_ctx* ctx, long n_pad, bool ext) {
     if (t == TUNE_VARA_256 || t == TUNE_COMPILER_SCHEDULED || n_pad >= 65536)
         return {t == TUNE_COMPILER_SCHEDULED && n_pad < 32768 ? VARA_I8W : VARA_I8, false};
     const bool paced = !ext && (t == TUNE_VARA_PACED || ((t == TUNE_SHIPPED || t == TUNE_VARA_UPPER) && n_pad >= 32768));
+    if (stage_glue_form()) return {ext ? VARA_I8P_EXT_GLUE : VARA_I8P_GLUE, true};   // (unpaced, lower image)
     return {paced ? VARA_I8P_PACED : (ext ? VARA_I8P_EXT : VARA_I8P), t != TUNE_VARA_UPPER};
 }
 // MM^T on fp4 operands: the 384 x 256 k_syrk_f4w from 3,072 padded individuals up while its row offsets fit (`wide_fits`), below

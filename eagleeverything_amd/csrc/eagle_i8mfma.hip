@@ -1036,7 +1036,9 @@ __global__ __launch_bounds__(512, 2) void k_vara_i8w(const int8_t* __restrict__ 
 // W-digit stages in step and the L2 serves them once.  Same integer sums: bit-identical q.
 // EXT: the same kernel under a second name for the run on the compact image of eagle_dev_vara_i8_extend -- a launch that is dropped
 // on the device whenever nobody qualifies, and that a profile should not average into the scan's launches.
-template <bool PACE, bool EXT = false>
+// GLUE: the form before the engine's stage step (eagle_t8.h) -- m0 / so / the read addresses re-derived in C++ between the k-steps of
+// every stage (EAGLE_HIP_STAGE_GLUE, eagle_ctx.h: A/B runs and tests/test_gpu_stage_step.py).  The same loads from the same places in the same order.
+template <bool PACE, bool EXT = false, bool GLUE = false>
 __global__ __launch_bounds__(512, 2) void k_vara_i8p(const int8_t* __restrict__ Mt8, long ld, int ntm, const int8_t* __restrict__ Bs,
                                                      long np, const VaraHdr* __restrict__ hdr, long long* __restrict__ q, long Lp, int cut_last_round,
                                                      int* __restrict__ pace, const int* __restrict__ klive) {
@@ -1096,6 +1098,84 @@ __global__ __launch_bounds__(512, 2) void k_vara_i8p(const int8_t* __restrict__ 
     dA.st = 8 * ldi; dA.vE = lnA.voffE; dA.vO = lnA.voffO;
     dB.st = 8 * npi; dB.vE = lnB.voffE; dB.vO = lnB.voffO;
     const i32x4 rsA_raw = x_rsrc(Mt8 + row0 * ld, (unsigned)(rows_here * ld)), rs_none = x_rsrc(Mt8, 0);
+    if constexpr (!GLUE) {
+        i32x4 fa[2][3], fb[4];
+        TxAcc c;
+        // The engine's stage step (eagle_t8.h).  The fetch runs two stages ahead of the compute: the genotype sequence of the stage
+        // after next starts in a stage's last k-step, the W-digit one in the next stage's first.  A tile has nk >= 2 stages, so only
+        // two sequence starts per tile cross into the next tile: the genotype one in the last k-step of stage nk - 2, the W-digit one
+        // in the first k-step of stage nk - 1.  Those two get the source step and the descriptor of the change (made at the top of the
+        // tile, not between k-steps); every other start steps BK8 along K.  Past the last tile the descriptors are empty.
+        XRead rd;
+        rd.a = offA + ch[0]; rd.b = offB + ch[0];
+        unsigned tog = X_STG;
+        const unsigned dsA = BK8 - 5 * dA.st, dsB = BK8 - 3 * dB.st;
+        dA.rs = rsA_raw;
+        dB.rs = x_rsrc(Bsl + (long)cur.ct * T8 * np, (unsigned)(T8 * npi));
+        tx_seq_init(dA, lds0, w * 6, 6, cur.kt);
+        tx_seq_init(dB, lds0 + TW_ABYTES, w * 4, 4, cur.kt);
+        tx_dma3_s(dA, tog, dsA);
+        tx_prologue(fa[0], fb, rd.a, rd.b);
+        rd.a ^= 32; rd.b ^= 32;   // chunk 1
+        auto stage_rest = [&](unsigned dsa) {
+            tx_kstep2_s(c, fa[1], fa[0], fb, rd, dB);
+            tx_kstep3_s(c, fa[0], fa[1], fb, rd, tog);
+            tx_klast_s(c, fa[1], fa[0], fb, rd, dA, tog, dsa);
+        };
+        while (cur.valid) {
+            const int done_ct = cur.ct, nk = cur.nk - cur.kt;  // nk >= 2
+            nxt = cur;
+            nxt.kt = nxt.nk - 1;
+            vit_advance(nxt, nct, pair1);   // the tile after this one
+            const unsigned dk = (unsigned)(nxt.kt - (cur.nk - 1)) * BK8;
+            const unsigned dsA_chg = dk - 5 * dA.st, dsB_chg = dk - 3 * dB.st;
+            const i32x4 rsA_chg = nxt.valid ? rsA_raw : rs_none;
+            const i32x4 rsB_chg = nxt.valid ? x_rsrc(Bsl + (long)nxt.ct * T8 * np, (unsigned)(T8 * npi)) : rs_none;
+            if (PACE && pace_row && cur.half == 0) {
+                if (t == 0) {
+                    int* cnt = pace_row + cur.p;
+                    (void)__hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    for (int it = 0; it < 2000 && __hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < pace_expected; it++)
+                        __builtin_amdgcn_s_sleep(8);
+                }
+                __syncthreads();
+            }
+            tx_kstep1_s<true>(c, fa[0], fa[1], fb, rd, dA, dB, tog, dsB);
+            for (int kt = 2; kt < nk; kt++) {
+                stage_rest(dsA);
+                tx_kstep1_s<false>(c, fa[0], fa[1], fb, rd, dA, dB, tog, dsB);
+            }
+            tx_kstep2_s(c, fa[1], fa[0], fb, rd, dB);
+            tx_kstep3_s(c, fa[0], fa[1], fb, rd, tog);
+            dA.rs = rsA_chg;
+            tx_klast_s(c, fa[1], fa[0], fb, rd, dA, tog, dsA_chg);
+            dB.rs = rsB_chg;
+            tx_kstep1_s<false>(c, fa[0], fa[1], fb, rd, dA, dB, tog, dsB_chg);
+            stage_rest(dsA);
+            {
+                // the MFMAs above are opaque to the compiler's hazard recogniser: let the last ones retire before the accumulators are
+                // read; and have the re-loads landed, in case the fragments are dead from here (last tile)
+                asm volatile("s_waitcnt lgkmcnt(0)\n\ts_nop 15\n\ts_nop 15" ::: "memory");
+                const int ecol = done_ct * T8;
+#pragma unroll
+                for (int m = 0; m < 3; m++) {
+                    // lane (r, h) holds, for its marker row wr*96 + m*32 + r, the sums over K against the 64 W columns 64 h + 16 n + x of
+                    // the wave's 128 (k_slice_w, perm128): their genotype bytes are 64 consecutive bytes of that row
+                    i32x4 g[4];
+#pragma unroll
+                    for (int n = 0; n < 4; n++) g[n] = __builtin_amdgcn_raw_buffer_load_b128(rsA, evoff + m * 32 * ldi, ecol + n * 16, 0);
+                    int sacc = 0;
+#pragma unroll
+                    for (int n = 0; n < 4; n++)
+#pragma unroll
+                        for (int x = 0; x < 16; x++) sacc += c[m][n][x] * ((g[n][x >> 2] << (24 - 8 * (x & 3))) >> 24);
+                    keep[m] += sacc;
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+            cur = nxt;
+        }
+    } else {
     // dma_arm runs once per stage between two k-steps, where every scalar instruction holds up the next MFMA: the two descriptors of
     // the stage `nxt` stands on (the empty one past the last stage) are made where `nxt` changes tile, not per stage, and a step inside
     // a tile is one add and one compare
@@ -1171,6 +1251,7 @@ __global__ __launch_bounds__(512, 2) void k_vara_i8p(const int8_t* __restrict__ 
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
+    }
     }
     const long qrow = row0 + wr * 96 + r;  // both halves h of a marker's lane pair add their part
     long long* qs = q + (long)sl * Lp + qrow;
@@ -1926,6 +2007,10 @@ static int vara_i8_launch(eagle_ctx* ctx, const int8_t* Mt8s, long L_pad, long n
             return vara_i8_run(ctx, form.kernel, k_vara_i8p<false>, gridw, ldsw, s, Mt8s, ld, ntw, Bs, n_pad, hdr, q, L_pad, cut, (int*)nullptr, kl);
         case VARA_I8P_EXT:
             return vara_i8_run(ctx, form.kernel, k_vara_i8p<false, true>, gridw, ldsw, s, Mt8s, ld, ntw, Bs, n_pad, hdr, q, L_pad, cut, (int*)nullptr, kl);
+        case VARA_I8P_GLUE:
+            return vara_i8_run(ctx, form.kernel, k_vara_i8p<false, false, true>, gridw, ldsw, s, Mt8s, ld, ntw, Bs, n_pad, hdr, q, L_pad, cut, (int*)nullptr, kl);
+        case VARA_I8P_EXT_GLUE:
+            return vara_i8_run(ctx, form.kernel, k_vara_i8p<false, true, true>, gridw, ldsw, s, Mt8s, ld, ntw, Bs, n_pad, hdr, q, L_pad, cut, (int*)nullptr, kl);
         case VARA_I8P_PACED: {
             // counters [8 XCDs][rounds][pairs], zeroed per launch, in the ctx's GEMM scratch (free during the scan)
             const size_t need = sizeof(int) * 8 * (size_t)((gw * smax + 31) / 32 + 1) * (size_t)((n_pad / T8 + 1) / 2);

@@ -288,6 +288,68 @@ __device__ __forceinline__ void tx_kstep(TxAcc& c, i32x4 (&a)[3], i32x4 (&an)[3]
 __device__ __forceinline__ void tx_klast(TxAcc& c, i32x4 (&a)[3], i32x4 (&an)[3], i32x4 (&b)[4], unsigned pa, unsigned pb, XDma& da) {
     asm volatile(X_KLAST : X_ACC_RW(0), X_ACC_RW(1), X_ACC_RW(2), X_FRAGS, X_DMA_OUT(a, da) : [pa] "v"(pa), [pb] "v"(pb), X_DMA_IN(a, da) : "memory", "scc");
 }
+// ---- the stage step: the engine advances both DMA sequences and the fragment-read addresses itself ----
+// A kernel that re-derives m0 / so and the read addresses in C++ between two k-steps of a stage puts that code where both waves of a
+// SIMD wait for it.  Here the state steps inside the asm of the k-steps, between their MFMAs:
+//   * the FIRST load of a sequence (X_DF) moves from the last row group of the previous sequence to the first one of the next:
+//     m0 += tog - (G - 1) KiB (the other LDS buffer, G row groups back), so += ds.  ds = BK8 - (G - 1) st inside a tile or pair; where
+//     the tile or pair changes the caller passes the ds of that one step and the new descriptor.  Same encoded size as X_DM;
+//   * ONE read address per operand (XRead), moved behind the k-step's last read to the chunk the next k-step loads: the swizzled chunk
+//     offsets of a lane are ch[ks] = ch[0] ^ 32 ks and sit in the low 7 bits of the address (row pitch 128 B, buffers 1 KiB aligned), so
+//     the order 1 2 3 0 is ^96, ^32, ^96, ^32 -- and the third k-step adds tog on top, which takes the address to the other
+//     buffer, and then flips tog = +-X_STG.
+// Every (m0, so) a load goes out with and every address a read uses is the one the C++ form computes; tx_seq_init gives the DMA state
+// before the first sequence.  (The additions are 8, 16 or 24 bytes per k-step: the placement of the stream keeps its 8-byte phase.)
+#define X_STG (TW_ABYTES + TILE_BYTES)  /* one LDS stage buffer: operand a, then operand b */
+#define X_DF(vo, s, back) "s_add_u32 %[m0" #s "], %[m0" #s "], %[tog]\n\ts_addk_i32 %[m0" #s "], " #back "\n\ts_mov_b32 m0, %[m0" #s "]\n\t" \
+                          "s_add_u32 %[so" #s "], %[so" #s "], %[ds" #s "]\n\tbuffer_load_dwordx4 %[" #vo #s "], %[rs" #s "], %[so" #s "] offen lds\n\t"
+#define X_VX32 "v_xor_b32 %[pa], 32, %[pa]\n\tv_xor_b32 %[pb], 32, %[pb]\n\t"
+#define X_VX96 "v_xor_b32 %[pa], 0x60, %[pa]\n\tv_xor_b32 %[pb], 0x60, %[pb]\n\t"
+#define X_VXT X_VX96 "v_add_u32 %[pa], %[tog], %[pa]\n\tv_add_u32 %[pb], %[tog], %[pb]\n\ts_xor_b32 %[tog], %[tog], %[flip]\n\t"
+#define X_READ_IO(p) [pa] "+v"(p.a), [pb] "+v"(p.b)
+#define X_KLAST_S X_KLAST_G(X_MF, X_DF(vE, a, -5120), X_DM(vO, a), X_DM(vE, a) X_VX32)
+// (the 384-row operand a: six row groups per wave, 5 KiB back; the 256-row operand b: four, 3 KiB back)
+struct XRead { unsigned a, b; };  // LDS byte addresses of the fragment reads the next k-step issues
+// the state "behind the last load of stage kt into buffer 0" of a wave that issues row groups g0 .. g0 + G - 1 of an operand at LDS
+// address `lds_op`: what the first X_DF (tog = +X_STG) turns into the first load of stage kt + 1 into buffer 1
+__device__ __forceinline__ void tx_seq_init(XDma& d, unsigned lds_op, int g0, int G, int kt) {
+    d.m0 = lds_op + (unsigned)(g0 + G - 1) * 1024u;
+    d.so = (unsigned)(g0 + G - 1) * d.st + (unsigned)kt * BK8;
+}
+__device__ __forceinline__ void tx_dma3_s(XDma& da, unsigned tog, unsigned dsa) {  // three loads on their own (pipeline fill)
+    asm volatile(X_DF(vE, a, -5120) X_DM(vO, a) X_DM(vE, a) : X_DMA_OUT(a, da) : X_DMA_IN(a, da), [tog] "s"(tog), [dsa] "s"(dsa) : "memory", "scc");
+}
+// the stage's first k-step (reads chunk 1): loads 3-5 of the genotype sequence, the first three of the W-digit one
+template <bool FIRST>
+__device__ __forceinline__ void tx_kstep1_s(TxAcc& c, i32x4 (&a)[3], i32x4 (&an)[3], i32x4 (&b)[4], XRead& p, XDma& da, XDma& db, unsigned tog,
+                                            unsigned dsb) {
+    if (FIRST)
+        asm volatile(X_KSTEP(X_MZ, X_DM(vO, a), X_DM(vE, a), X_DM(vO, a), X_DF(vE, b, -3072), X_DM(vO, b), X_DM(vE, b) X_VX96)
+                     : X_ACC_W(0), X_ACC_W(1), X_ACC_W(2), X_FRAGS, X_DMA_OUT(a, da), X_DMA_OUT(b, db), X_READ_IO(p)
+                     : X_DMA_IN(a, da), X_DMA_IN(b, db), [tog] "s"(tog), [dsb] "s"(dsb) : "memory", "scc");
+    else
+        asm volatile(X_KSTEP(X_MF, X_DM(vO, a), X_DM(vE, a), X_DM(vO, a), X_DF(vE, b, -3072), X_DM(vO, b), X_DM(vE, b) X_VX96)
+                     : X_ACC_RW(0), X_ACC_RW(1), X_ACC_RW(2), X_FRAGS, X_DMA_OUT(a, da), X_DMA_OUT(b, db), X_READ_IO(p)
+                     : X_DMA_IN(a, da), X_DMA_IN(b, db), [tog] "s"(tog), [dsb] "s"(dsb) : "memory", "scc");
+}
+// the second (reads chunk 2): the last load of the W-digit sequence
+__device__ __forceinline__ void tx_kstep2_s(TxAcc& c, i32x4 (&a)[3], i32x4 (&an)[3], i32x4 (&b)[4], XRead& p, XDma& db) {
+    asm volatile(X_KSTEP(X_MF, X_DM(vO, b), , , , , X_VX32)
+                 : X_ACC_RW(0), X_ACC_RW(1), X_ACC_RW(2), X_FRAGS, X_DMA_OUT(b, db), X_READ_IO(p) : X_DMA_IN(b, db) : "memory", "scc");
+}
+// the third (reads chunk 3): no DMA; the read addresses and tog move to the other buffer
+__device__ __forceinline__ void tx_kstep3_s(TxAcc& c, i32x4 (&a)[3], i32x4 (&an)[3], i32x4 (&b)[4], XRead& p, unsigned& tog) {
+    asm volatile(X_KSTEP(X_MF, , , , , , X_VXT)
+                 : X_ACC_RW(0), X_ACC_RW(1), X_ACC_RW(2), X_FRAGS, X_READ_IO(p), [tog] "+s"(tog)
+                 : [flip] "i"((int)((unsigned)X_STG ^ (0u - (unsigned)X_STG))) : "memory", "scc");
+}
+// the last, with the barrier (reads chunk 0 of the other buffer): behind it the first three loads of the genotype sequence of the
+// stage after next
+__device__ __forceinline__ void tx_klast_s(TxAcc& c, i32x4 (&a)[3], i32x4 (&an)[3], i32x4 (&b)[4], XRead& p, XDma& da, unsigned tog, unsigned dsa) {
+    asm volatile(X_KLAST_S
+                 : X_ACC_RW(0), X_ACC_RW(1), X_ACC_RW(2), X_FRAGS, X_DMA_OUT(a, da), X_READ_IO(p)
+                 : X_DMA_IN(a, da), [tog] "s"(tog), [dsa] "s"(dsa) : "memory", "scc");
+}
 // hipcc's uniformity analysis calls the scalar outputs of these asm blocks divergent in this kernel (not in k_vara_i8p), puts their
 // loop-carried copies into VGPRs and then cannot feed them to the next block's "s" operands: say it explicitly
 __device__ __forceinline__ void sx_uniform(XDma& d) {

@@ -374,6 +374,11 @@ __global__ __launch_bounds__(512, 2) void k_w8_gemm(const int8_t* __restrict__ A
 // output COLUMNS j (digit slices of V / X), operand "b" (256-row tiles; the registers) = the one whose rows are the output ROWS i
 // (slices of S): a result register is 32 consecutive j of one row i, stored as one 128-byte run.  Work entry: ti = 256-row tile of S,
 // tj = 384-row tile of the column operand (the last one may be short: rows beyond n_pad read as zero and are not stored).
+// The flattened (pair, K stage) sequence runs on the engine's stage step (eagle_t8.h): a digit pair is to it what a column tile is to
+// k_vara_i8p -- nstages >= 2 stages, then one sequence start per operand that goes back to K stage 0 on the next pair's slices.  The
+// pair list of the group is read once into scalar registers; the descriptors of the next pair are made at the top of a pair.
+// GLUE: the form before the step, everything re-derived in C++ between the k-steps (EAGLE_HIP_STAGE_GLUE, eagle_ctx.h; tests/test_gpu_stage_step.py).
+template <bool GLUE>
 __global__ __launch_bounds__(512, 2) void k_w8_gemm_p(const int8_t* __restrict__ Ss, const int8_t* __restrict__ Cs, long sstride, long ld,
                                                       const unsigned* __restrict__ work, int maxlen, const W8Group* __restrict__ groups,
                                                       int32_t* __restrict__ L, long img_elems, long ldc, int row_tile0, int nstages, long np, long col0) {
@@ -409,6 +414,54 @@ __global__ __launch_bounds__(512, 2) void k_w8_gemm_p(const int8_t* __restrict__
     XDma dA, dB;
     dA.st = dB.st = __builtin_amdgcn_readfirstlane(8 * ldi);
     dA.vE = dB.vE = ln.voffE; dA.vO = dB.vO = ln.voffO;
+    i32x4 fa[2][3], fb[4];
+    TxAcc c;
+    if constexpr (!GLUE) {
+        // the group's pair list: p[8] and q[8] as two dwords each (W8Group), pair i in byte i
+        const unsigned* gw = (const unsigned*)gp;
+        const unsigned pw0 = __builtin_amdgcn_readfirstlane(gw[2]), pw1 = __builtin_amdgcn_readfirstlane(gw[3]);
+        const unsigned qw0 = __builtin_amdgcn_readfirstlane(gw[4]), qw1 = __builtin_amdgcn_readfirstlane(gw[5]);
+        auto pair_p = [&](int i) { return (long)(((i < 4 ? pw0 : pw1) >> (8 * (i & 3))) & 0xffu); };
+        auto pair_q = [&](int i) { return (long)(((i < 4 ? qw0 : qw1) >> (8 * (i & 3))) & 0xffu); };
+        XRead rd;
+        rd.a = offA + ch[0]; rd.b = offB + ch[0];
+        unsigned tog = X_STG;
+        const unsigned nrecA = (unsigned)(rows_here * ldi), nrecB = (unsigned)(T8 * ldi);
+        const unsigned dsA = BK8 - 5 * dA.st, dsB = BK8 - 3 * dB.st;
+        const unsigned back = (unsigned)(nstages - 1) * BK8;   // a pair change: from the last K stage to stage 0
+        const unsigned dsA_chg = 0u - back - 5 * dA.st, dsB_chg = 0u - back - 3 * dB.st;
+        const i32x4 rs_none = x_rsrc(Cs, 0);   // nothing left to fetch: the loads write zeros nobody reads
+        dA.rs = x_rsrc(baseA, nrecA);
+        dB.rs = x_rsrc(baseB, nrecB);
+        tx_seq_init(dA, lds0, w * 6, 6, 0);
+        tx_seq_init(dB, lds0 + TW_ABYTES, w * 4, 4, 0);
+        tx_dma3_s(dA, tog, dsA);
+        tx_prologue(fa[0], fb, rd.a, rd.b);
+        rd.a ^= 32; rd.b ^= 32;   // chunk 1
+        auto stage_rest = [&](unsigned dsa) {
+            tx_kstep2_s(c, fa[1], fa[0], fb, rd, dB);
+            tx_kstep3_s(c, fa[0], fa[1], fb, rd, tog);
+            tx_klast_s(c, fa[1], fa[0], fb, rd, dA, tog, dsa);
+        };
+        tx_kstep1_s<true>(c, fa[0], fa[1], fb, rd, dA, dB, tog, dsB);
+        for (int pr = 0; pr < gnp; pr++) {
+            const bool more = pr + 1 < gnp;
+            const i32x4 rsA_chg = more ? x_rsrc(Acol + pair_q(pr + 1) * sstride, nrecA) : rs_none;
+            const i32x4 rsB_chg = more ? x_rsrc(Brow + pair_p(pr + 1) * sstride, nrecB) : rs_none;
+            for (int kt = 2; kt < nstages; kt++) {
+                stage_rest(dsA);
+                tx_kstep1_s<false>(c, fa[0], fa[1], fb, rd, dA, dB, tog, dsB);
+            }
+            tx_kstep2_s(c, fa[1], fa[0], fb, rd, dB);
+            tx_kstep3_s(c, fa[0], fa[1], fb, rd, tog);
+            dA.rs = rsA_chg;
+            tx_klast_s(c, fa[1], fa[0], fb, rd, dA, tog, dsA_chg);
+            dB.rs = rsB_chg;
+            tx_kstep1_s<false>(c, fa[0], fa[1], fb, rd, dA, dB, tog, dsB_chg);
+            stage_rest(dsA);
+            if (more) tx_kstep1_s<false>(c, fa[0], fa[1], fb, rd, dA, dB, tog, dsB);
+        }
+    } else {
     const int total = gnp * nstages;   // the flattened (pair, K stage) sequence of this accumulation group
     int snext = 1, nkt = 1, npr = 0;   // the next stage to fetch: global index, K stage, pair   (nstages >= 2)
     unsigned nrecA = 0, nrecB = 0;
@@ -437,8 +490,6 @@ __global__ __launch_bounds__(512, 2) void k_w8_gemm_p(const int8_t* __restrict__
     tx_dma3(dA);
     sx_uniform(dA);
     int buf = 0;
-    i32x4 fa[2][3], fb[4];
-    TxAcc c;
     tx_prologue(fa[0], fb, offA + ch[0], offB + ch[0]);
     auto stage_rest = [&] {
         const unsigned sa = offA + buf * STG, sb = offB + buf * STG;
@@ -461,6 +512,7 @@ __global__ __launch_bounds__(512, 2) void k_w8_gemm_p(const int8_t* __restrict__
         tx_kstep<false, 1>(c, fa[0], fa[1], fb, offA + buf * STG + ch[1], offB + buf * STG + ch[1], dA, dB);
         sx_uniform(dA); sx_uniform(dB);
         stage_rest();
+    }
     }
     // the MFMAs are opaque to the compiler's hazard recogniser: let the last ones retire; the stale re-loads have to land too
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_nop 15\n\ts_nop 15" ::: "memory");
@@ -1015,11 +1067,12 @@ static int w8_product(eagle_ctx* ctx, int cfg, bool upper, long np, const int8_t
         const long img_elems = (long)(rt1 - rt0) * T8 * ncols;
         if (piped) {
             if (!ctx->attr_w8_gemm) {
-                hipError_t ea = hipFuncSetAttribute((const void*)k_w8_gemm_p, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (TW_ABYTES + TILE_BYTES));
+                hipError_t ea = hipFuncSetAttribute((const void*)k_w8_gemm_p<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (TW_ABYTES + TILE_BYTES));
+                if (ea == hipSuccess) ea = hipFuncSetAttribute((const void*)k_w8_gemm_p<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (TW_ABYTES + TILE_BYTES));
                 if (ea != hipSuccess) return eagle_fail_hip(ctx, ea, "hipFuncSetAttribute(k_w8_gemm_p)");
                 ctx->attr_w8_gemm = true;
             }
-            hipLaunchKernelGGL(k_w8_gemm_p, dim3((unsigned)(8 * l.maxlen)), dim3(512), 2 * (TW_ABYTES + TILE_BYTES), s, sA, sB, np * np, np, (const unsigned*)l.work,
+            hipLaunchKernelGGL(stage_glue_form() ? k_w8_gemm_p<true> : k_w8_gemm_p<false>, dim3((unsigned)(8 * l.maxlen)), dim3(512), 2 * (TW_ABYTES + TILE_BYTES), s, sA, sB, np * np, np, (const unsigned*)l.work,
                                l.maxlen, (const W8Group*)l.groups, w.levels, img_elems, ncols, rt0, (int)(np / BK8), np, col0);
         } else
         hipLaunchKernelGGL(k_w8_gemm, dim3((unsigned)(8 * l.maxlen)), dim3(512), 0, s, sA, sB, np * np, np, (const unsigned*)l.work, l.maxlen,
