@@ -12,7 +12,9 @@ mirror of the reference interface used by tests, bench.py and the sharded multi-
                 sets_from_windows, sets_from_table;
                 MaxT (max(T) permutation p-values of every marker: EMP1 and the family-wise EMP2), maxt_host,
                 maxt_permutations_host, maxt_merge;
-                HapLD, HapBlocks (pairwise haplotype EM, D' and haplotype blocks), hap_ld_host, hap_blocks_host, sets_from_blocks
+                HapLD, HapBlocks (pairwise haplotype EM, D' and haplotype blocks), hap_ld_host, hap_blocks_host, sets_from_blocks;
+                TDT (the transmission disequilibrium test of parent-offspring trios with max(T) flips within families), tdt_host,
+                tdt_families, tdt_summary, tdt_merge
   host_model -- dense n x n model algebra that stays on host LAPACK by design
   sharded    -- marker-sharded multi-GPU scan / MM^T (one process per GPU, torch.distributed over RCCL)
   synth      -- seeded synthetic genotypes of the benchmark shapes

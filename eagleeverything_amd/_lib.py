@@ -129,6 +129,11 @@ SIGNATURES = {
     "eagle_maxt": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.c_uint64, C.c_long,
                              C.c_long, C.POINTER(C.c_int32), C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64), c_dp, C.POINTER(C.c_int32), c_dp,
                              C.POINTER(C.c_int32)]),
+    "eagle_tdt": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, C.POINTER(C.c_int32), C.c_long, C.POINTER(C.c_int32), C.c_uint64, C.c_long, C.c_long,
+                            C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32), c_dp, C.POINTER(C.c_int32), c_dp, C.POINTER(C.c_int32)]),
+    "eagle_bed_tdt": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, C.c_void_p, C.POINTER(C.c_int32), C.c_long, C.POINTER(C.c_int32), C.c_uint64, C.c_long,
+                                C.c_long, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32), c_dp, C.POINTER(C.c_int32), c_dp,
+                                C.POINTER(C.c_int32)]),
     "eagle_hap_ld": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, C.c_long, C.c_double, C.c_int, C.c_double, C.c_double, C.c_double,
                                C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), c_dp, c_dp, C.POINTER(C.c_int64)]),
     "eagle_logistic": (C.c_int,[C.c_void_p, C.c_char_p, c_lp, C.POINTER(C.c_int32), c_dp, C.c_int, c_dp, C.c_int, C.c_double, C.c_int,

@@ -418,6 +418,18 @@ extern "C" int eagle_dev_mendel_trios(eagle_ctx* ctx, const uint64_t* planes, in
 extern "C" int eagle_dev_plane_gather(eagle_ctx* ctx, const uint64_t* planes, int nplanes, long n, long L, const int32_t* idx, long cnt, uint64_t* dst,
                                       void* stream);
 extern "C" long eagle_parentage_parts(long ns, long nd);
+// Transmission disequilibrium test (eagle_tdt.hip; include/eagle_hip.h section 1b''''viii) on the same planes, device pointers throughout.
+// trios: T x 3 int32; out: T x 6 int32; marker: L x 5 int32 ZEROED by the caller.  The finish turns marker into dobs / V / keyobs (L each).
+// The image: rows [m0, m0 + rows) of D[m][t] = d of rule 2, int8 with leading dimension ld = a multiple of 16 >= T, m0 a multiple of 64,
+// every byte of the rows written.  The signs: op [R][ldop] of +-1 for the flips first .. first + R - 1 of the families fam[T], zeros
+// from T on.
+extern "C" int eagle_dev_tdt_trios(eagle_ctx* ctx, const uint64_t* planes, int nplanes, long n, long L, const int32_t* trios, long T, int32_t* out,
+                                   int32_t* marker, void* stream);
+extern "C" int eagle_dev_tdt_finish(eagle_ctx* ctx, const int32_t* marker, long L, int64_t* dobs, int64_t* V, double* keyobs, void* stream);
+extern "C" int eagle_dev_tdt_image(eagle_ctx* ctx, const uint64_t* planes, int nplanes, long n, long L, const int32_t* trios, long T, long m0,
+                                   long rows, int8_t* img, long ld, void* stream);
+extern "C" int eagle_dev_tdt_signs(eagle_ctx* ctx, const int32_t* fam, long T, uint64_t seed, long first, long R, int8_t* op, long ldop,
+                                   void* stream);
 extern "C" int eagle_dev_parentage(eagle_ctx* ctx, const uint64_t* O, long n_o, const uint64_t* S, long ns, const uint64_t* D, long nd, int nplanes, long L,
                                    const int32_t* oidx, const int32_t* sidx, const int32_t* didx, long o0, long no, int min_overlap, int allow_self,
                                    uint64_t* part_k, int32_t* part_n, int32_t* best, void* stream);

@@ -863,4 +863,60 @@ static inline const char* maxt_arg_error(long n, long L, const int32_t* t, const
     *tmax_out = tmax;
     return nullptr;
 }
+
+// ------------------------------------------------------------------------------------------------
+// Transmission disequilibrium test of trios (include/eagle_hip.h section 1b''''viii): the transmission words of rule 2 on the bit planes
+// (shared with the kernels of eagle_tdt.hip), the family rule and the sign rule of the flips (rule 5) and the argument rule of
+// eagle_tdt / eagle_bed_tdt.
+// ------------------------------------------------------------------------------------------------
+#define TDT_MAX_FLIP_TRIOS 65535L
+// k: complete and free of a Mendel error; hf / hm: the informative het parents; pt / pu, mt / mu: the father / the mother passed A2 / A1;
+// w: het x het -> het.  The arguments are the A, B and C words of the child, the father and the mother (an unknown parent: all zero).
+struct TdtWords { uint64_t k, hf, hm, pt, pu, mt, mu, w; };
+static inline EAGLE_HD TdtWords tdt_words(uint64_t ac, uint64_t bc, uint64_t cc, uint64_t af, uint64_t bf, uint64_t cf, uint64_t am, uint64_t bm,
+                                          uint64_t cm) {
+    TdtWords t;
+    t.k = cc & cf & cm & ~mendel_error_word(ac, bc, cc, af, bf, am, bm);
+    const uint64_t hc = cc & ~ac & ~bc;
+    t.hf = cf & ~af & ~bf & t.k;
+    t.hm = cm & ~am & ~bm & t.k;
+    t.pt = t.hf & (bc | (hc & am));
+    t.pu = t.hf & (ac | (hc & bm));
+    t.mt = t.hm & (bc | (hc & af));
+    t.mu = t.hm & (ac | (hc & bf));
+    t.w = t.hf & t.hm & hc;
+    return t;
+}
+// d of rule 2 at bit b of the four transmission words: PT + MT - PU - MU in [-2, 2]
+static inline EAGLE_HD int tdt_d_bit(const TdtWords& t, int b) {
+    return (int)((t.pt >> b) & 1ull) + (int)((t.mt >> b) & 1ull) - (int)((t.pu >> b) & 1ull) - (int)((t.mu >> b) & 1ull);
+}
+// The sign of family phi in flip r >= 1: -1 when bit 31 of h(seed, r, phi) is set (maxt_mix: counter = r 2^16 + phi + 1), else +1.
+static inline EAGLE_HD int tdt_sign(uint64_t seed, uint64_t r, uint32_t phi) { return (maxt_mix(seed, r, phi) >> 31) ? -1 : 1; }
+// The families of a trio list without family ids: the smallest list position with the same (father, mother), so full sibs flip together.
+static inline void tdt_families(const int32_t* trios, long ntrios, int32_t* fam_out) {
+    std::vector<std::pair<uint64_t, int32_t>> key((size_t)ntrios);
+    for (long k = 0; k < ntrios; k++)
+        key[(size_t)k] = {((uint64_t)(uint32_t)trios[3 * k + 1] << 32) | (uint32_t)trios[3 * k + 2], (int32_t)k};
+    std::sort(key.begin(), key.end());                    // by couple, then by position: the first of a run is the smallest position
+    for (size_t i = 0, first = 0; i < key.size(); i++) {
+        if (key[i].first != key[first].first) first = i;
+        fam_out[key[i].second] = key[first].second;
+    }
+}
+// What is wrong with a call of eagle_tdt / eagle_bed_tdt over `markers` panel markers, or NULL.  family may be NULL.
+static inline const char* tdt_arg_error(long markers, long ntrios, const int32_t* family, long first, long R) {
+    if (markers > 0x7fffffffL) return "2^31 markers or more";
+    if (R < 0) return "R must not be negative";
+    if (ntrios < 1 || ntrios > MENDEL_MAX_TRIOS) return "the number of trios must be in [1, 2^27]";
+    if (R == 0) return nullptr;
+    if (ntrios > TDT_MAX_FLIP_TRIOS) return "more than 65535 trios with flips (R >= 1)";
+    if (R > MAXT_RMAX) return "R outside [0, EAGLE_MAXT_RMAX = 1024]";
+    if (first < 1) return "first must be at least 1";
+    if (first + R > 2147483648L) return "first + R above 2^31";
+    if (family)
+        for (long k = 0; k < ntrios; k++)
+            if (family[k] < 0 || family[k] > 65535) return "a family outside [0, 65535]";
+    return nullptr;
+}
 #endif

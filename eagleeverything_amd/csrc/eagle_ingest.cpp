@@ -2262,20 +2262,27 @@ struct GenoPlanes {
     int nplanes = 2;
     size_t bytes() const { return sizeof(uint64_t) * (size_t)nplanes * (size_t)((lp + 63) / 64) * (size_t)((n + 63) / 64 * 64); }
     uint64_t* p() { return planes.as<uint64_t>(); }
-    // path: M.ascii of dims (n, L), or with is_bed the .bed file of dims (n, L) whose panel is the linc markers of include
-    int build(eagle_ctx* ctx, const char* who, bool is_bed, const char* path, long n_, long L, const uint8_t* include, long linc, double mem_gb,
-              size_t extra, const char* extra_what) {
+    // The memory budget of rule 9: the resident budget where one is set, else the device's free memory less 1 GiB.
+    static int budget_bytes(eagle_ctx* ctx, size_t* out) {
         HIPCHK(ctx, hipSetDevice(ctx->device));
-        n = n_;
-        lp = is_bed ? linc : L;
-        nplanes = is_bed ? 3 : 2;
-        const size_t plane_bytes = bytes();
         size_t budget = eagle_resident_budget();
         if (budget == (size_t)-1) {
             size_t freeb = 0, totalb = 0;
             HIPCHK(ctx, hipMemGetInfo(&freeb, &totalb));
             budget = freeb > ((size_t)1 << 30) ? freeb - ((size_t)1 << 30) : 0;
         }
+        *out = budget;
+        return EAGLE_OK;
+    }
+    // path: M.ascii of dims (n, L), or with is_bed the .bed file of dims (n, L) whose panel is the linc markers of include
+    int build(eagle_ctx* ctx, const char* who, bool is_bed, const char* path, long n_, long L, const uint8_t* include, long linc, double mem_gb,
+              size_t extra, const char* extra_what) {
+        n = n_;
+        lp = is_bed ? linc : L;
+        nplanes = is_bed ? 3 : 2;
+        const size_t plane_bytes = bytes();
+        size_t budget = 0;
+        if (int rc = budget_bytes(ctx, &budget)) return rc;
         if (plane_bytes > budget || extra > budget - plane_bytes)
             return failf(ctx, EAGLE_ERR_NOMEM, "%s: the bit planes (%zu bytes) and %s (%zu bytes) do not fit the memory budget", who, plane_bytes,
                          extra_what, extra);
@@ -2610,6 +2617,142 @@ extern "C" int eagle_bed_parentage(eagle_ctx* ctx, const char* bed_path, const l
                      "the candidates' planes and the partial minima");
     if (rc) return rc;
     return parentage_run(ctx, g, offspring, n_o, sires, n_s, dams, n_d, (int)min_overlap, allow_self, best_out);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Transmission disequilibrium test of trios (include/eagle_hip.h section 1b''''viii; kernels in eagle_tdt.hip, the flips' product in
+// eagle_maxt.hip).  The planes are GenoPlanes::build's; the trio pass and its finish give the counts and the observed key; with R >= 1 the
+// int8 image of d is built in bands of whole 128-marker tiles and each band goes through k_maxt_tile against the sign operand.
+// ---------------------------------------------------------------------------------------------------------------
+static_assert(TDT_MAX_FLIP_TRIOS == EAGLE_MAXT_MAX_N, "a flip's trios are the tile's K dimension");
+namespace {
+
+// What a call holds beside the planes, and the rows of an image band.  `fixed`: the trio list, the per-trio and per-marker arrays and,
+// with flips, the families, S, count1, the sign operand, the tile partials and the per-flip maxima; the band takes what is left of the
+// budget, whole 128-marker tiles, at least one, at most 2 GiB.
+struct TdtPlan { long ld = 0, band = 0, tiles = 0; size_t extra = 0; };
+TdtPlan tdt_plan(size_t budget, size_t plane_bytes, long lp, long ntrios, long R) {
+    TdtPlan p;
+    const size_t T = (size_t)ntrios, Lp = (size_t)lp;
+    size_t fixed = (size_t)36 * T + (size_t)44 * Lp;      // trios, trio_out; marker_out (5 int32), d_obs, V, key_obs
+    if (R < 1) { p.extra = fixed; return p; }
+    p.ld = (ntrios + 15) / 16 * 16;
+    p.tiles = (lp + 127) / 128;
+    fixed += (size_t)4 * T + (size_t)8 * Lp + (size_t)R * (size_t)p.ld + (size_t)12 * (size_t)R * (size_t)p.tiles + (size_t)12 * (size_t)R;
+    const size_t used = plane_bytes + fixed, left = budget > used ? budget - used : 0;
+    const long fit = (long)std::min<size_t>(left, (size_t)1 << 31) / p.ld / 128 * 128;
+    p.band = std::min(p.tiles * 128, std::max(128L, fit));
+    p.extra = fixed + (size_t)p.band * (size_t)p.ld;
+    return p;
+}
+
+// Both entry points: the route's name, the checks that need no context, the planes, the kernels, the downloads.
+int tdt_call(eagle_ctx* ctx, const char* who, bool is_bed, const char* path, const long dims[2], const uint8_t* include, const int32_t* trios,
+             long ntrios, const int32_t* family, uint64_t seed, long first, long R, double mem_gb, int32_t* trio_out, int32_t* marker_out,
+             double* key_obs, int32_t* count1, double* maxkey, int32_t* argmax) {
+    char msg[200];
+    auto fail = [&](const char* what) {
+        snprintf(msg, sizeof msg, "%s: %s", who, what);
+        return qc_fail(ctx, EAGLE_ERR_ARG, msg);
+    };
+    if (!path || !dims || !trios || !trio_out || !marker_out || !key_obs) return fail("NULL argument");
+    const long n = dims[0], L = dims[1];
+    if (n <= 0 || L <= 0) return fail("dims must be positive");
+    if (is_bed && n > 0x3fffffffL) return fail("2^30 individuals or more");
+    const long lp = is_bed ? bedld_count(include, L) : L;
+    if (lp < 1) return fail("include selects no marker");
+    if (const char* bad = tdt_arg_error(lp, ntrios, family, first, R)) return fail(bad);
+    if (R >= 1 && (!count1 || !maxkey || !argmax)) return fail("NULL argument (count1, maxkey and argmax are needed with R >= 1)");
+    const long k = mendel_trios_check(trios, ntrios, n);
+    if (k >= 0) {
+        snprintf(msg, sizeof msg, "%s: trio %ld is not (c, f, m) with 0 <= c < n, -1 <= f, m < n, c != f, c != m, f != m", who, k);
+        return qc_fail(ctx, EAGLE_ERR_ARG, msg);
+    }
+    if (!ctx) return fail("no context");
+
+    GenoPlanes g;
+    g.n = n;
+    g.lp = lp;
+    g.nplanes = is_bed ? 3 : 2;
+    size_t budget = 0;
+    if (int rc = GenoPlanes::budget_bytes(ctx, &budget)) return rc;
+    const TdtPlan plan = tdt_plan(budget, g.bytes(), lp, ntrios, R);
+    int rc = g.build(ctx, who, is_bed, path, n, L, include, lp, mem_gb, plan.extra,
+                     "the per-trio and per-marker arrays, the image band, the sign operand and the tile partials");
+    if (rc) return rc;
+
+    hipStream_t st = ctx->stream;
+    const size_t T = (size_t)ntrios, Lp = (size_t)lp;
+    std::vector<int32_t> fam;
+    DevBuf d_trios, d_out, d_marker, dD, dV, dK, d_fam, op, dS, dC, pkey, parg, dmax, darg, img;
+    HIPCHK(ctx, d_trios.alloc(sizeof(int32_t) * 3 * T));
+    HIPCHK(ctx, d_out.alloc(sizeof(int32_t) * 6 * T));
+    HIPCHK(ctx, d_marker.alloc(sizeof(int32_t) * 5 * Lp));
+    HIPCHK(ctx, dD.alloc(sizeof(int64_t) * Lp));
+    HIPCHK(ctx, dV.alloc(sizeof(int64_t) * Lp));
+    HIPCHK(ctx, dK.alloc(sizeof(double) * Lp));
+    if (R >= 1) {
+        HIPCHK(ctx, d_fam.alloc(sizeof(int32_t) * T));
+        HIPCHK(ctx, op.alloc((size_t)R * (size_t)plan.ld));
+        HIPCHK(ctx, dS.alloc(sizeof(int32_t) * Lp));
+        HIPCHK(ctx, dC.alloc(sizeof(int32_t) * Lp));
+        HIPCHK(ctx, pkey.alloc(sizeof(double) * (size_t)plan.tiles * (size_t)R));
+        HIPCHK(ctx, parg.alloc(sizeof(int32_t) * (size_t)plan.tiles * (size_t)R));
+        HIPCHK(ctx, dmax.alloc(sizeof(double) * (size_t)R));
+        HIPCHK(ctx, darg.alloc(sizeof(int32_t) * (size_t)R));
+        HIPCHK(ctx, img.alloc((size_t)plan.band * (size_t)plan.ld));
+    }
+    // every later error path drains the stream first: kernels and copies may be queued on this frame's buffers and on fam
+    auto drain = [&](int code) { (void)hipStreamSynchronize(st); return code; };
+    auto hip = [&](hipError_t e, const char* what) { return e == hipSuccess ? EAGLE_OK : drain(eagle_fail_hip(ctx, e, what)); };
+    if ((rc = hip(hipMemcpyAsync(d_trios.p, trios, sizeof(int32_t) * 3 * T, hipMemcpyHostToDevice, st), "tdt: trio upload"))) return rc;
+    if ((rc = hip(hipMemsetAsync(d_marker.p, 0, sizeof(int32_t) * 5 * Lp, st), "tdt: marker counts"))) return rc;
+    rc = eagle_dev_tdt_trios(ctx, g.p(), g.nplanes, n, lp, d_trios.as<int32_t>(), ntrios, d_out.as<int32_t>(), d_marker.as<int32_t>(), st);
+    if (!rc) rc = eagle_dev_tdt_finish(ctx, d_marker.as<int32_t>(), lp, dD.as<int64_t>(), dV.as<int64_t>(), dK.as<double>(), st);
+    if (rc) return drain(rc);
+    if (R >= 1) {
+        fam.resize(T);
+        if (family) std::copy(family, family + ntrios, fam.begin());
+        else tdt_families(trios, ntrios, fam.data());
+        if ((rc = hip(hipMemcpyAsync(d_fam.p, fam.data(), sizeof(int32_t) * T, hipMemcpyHostToDevice, st), "tdt: family upload"))) return rc;
+        if ((rc = hip(hipMemsetAsync(dS.p, 0, sizeof(int32_t) * Lp, st), "tdt: S"))) return rc;
+        if ((rc = hip(hipMemsetAsync(dC.p, 0, sizeof(int32_t) * Lp, st), "tdt: count1"))) return rc;
+        rc = eagle_dev_tdt_signs(ctx, d_fam.as<int32_t>(), ntrios, seed, first, R, op.as<int8_t>(), plan.ld, st);
+        long tile_base = 0;
+        for (long m0 = 0; m0 < lp && !rc; m0 += plan.band) {   // stream order: a band's tile has read the image before the next band writes it
+            const long rows = std::min(plan.band, lp - m0);
+            rc = eagle_dev_tdt_image(ctx, g.p(), g.nplanes, n, lp, d_trios.as<int32_t>(), ntrios, m0, rows, img.as<int8_t>(), plan.ld, st);
+            if (!rc) rc = eagle_dev_maxt_tile(ctx, 0, img.as<int8_t>(), rows, ntrios, plan.ld, op.as<int8_t>(), plan.ld, 1, R, R, 1, 0,
+                                              dS.as<int32_t>() + m0, dV.as<int64_t>() + m0, dD.as<int64_t>() + m0, dK.as<double>() + m0,
+                                              dC.as<int32_t>() + m0, pkey.as<double>(), parg.as<int32_t>(), tile_base, m0, st);
+            tile_base += (rows + 127) / 128;
+        }
+        if (!rc) rc = eagle_dev_maxt_finish(ctx, pkey.as<double>(), parg.as<int32_t>(), tile_base, R, dmax.as<double>(), darg.as<int32_t>(), st);
+        if (rc) return drain(rc);
+        if ((rc = hip(hipMemcpyAsync(count1, dC.p, sizeof(int32_t) * Lp, hipMemcpyDeviceToHost, st), "tdt: download"))) return rc;
+        if ((rc = hip(hipMemcpyAsync(maxkey, dmax.p, sizeof(double) * (size_t)R, hipMemcpyDeviceToHost, st), "tdt: download"))) return rc;
+        if ((rc = hip(hipMemcpyAsync(argmax, darg.p, sizeof(int32_t) * (size_t)R, hipMemcpyDeviceToHost, st), "tdt: download"))) return rc;
+    }
+    if ((rc = hip(hipMemcpyAsync(trio_out, d_out.p, sizeof(int32_t) * 6 * T, hipMemcpyDeviceToHost, st), "tdt: download"))) return rc;
+    if ((rc = hip(hipMemcpyAsync(marker_out, d_marker.p, sizeof(int32_t) * 5 * Lp, hipMemcpyDeviceToHost, st), "tdt: download"))) return rc;
+    if ((rc = hip(hipMemcpyAsync(key_obs, dK.p, sizeof(double) * Lp, hipMemcpyDeviceToHost, st), "tdt: download"))) return rc;
+    return hip(hipStreamSynchronize(st), "tdt: synchronize");
+}
+
+}  // namespace
+
+extern "C" int eagle_tdt(eagle_ctx* ctx, const char* f_name_ascii_M, const long dims[2], const int32_t* trios, long ntrios, const int32_t* family,
+                         uint64_t seed, long first, long R, double max_memory_in_Gbytes, int32_t* trio_out, int32_t* marker_out, double* key_obs,
+                         int32_t* count1, double* maxkey, int32_t* argmax) {
+    return tdt_call(ctx, "tdt", false, f_name_ascii_M, dims, nullptr, trios, ntrios, family, seed, first, R, max_memory_in_Gbytes, trio_out, marker_out,
+                    key_obs, count1, maxkey, argmax);
+}
+
+extern "C" int eagle_bed_tdt(eagle_ctx* ctx, const char* bed_path, const long dims[2], const uint8_t* include, const int32_t* trios, long ntrios,
+                             const int32_t* family, uint64_t seed, long first, long R, double max_memory_in_Gbytes, int32_t* trio_out,
+                             int32_t* marker_out, double* key_obs, int32_t* count1, double* maxkey, int32_t* argmax) {
+    return tdt_call(ctx, "bed_tdt", true, bed_path, dims, include, trios, ntrios, family, seed, first, R, max_memory_in_Gbytes, trio_out, marker_out,
+                    key_obs, count1, maxkey, argmax);
 }
 
 // The loci's rows are gathered into a 64-row image first (k_gather_rows_i8: from the resident image, else from their own lines of

@@ -2994,6 +2994,201 @@ def MaxT(geno, trait, R=1000, seed=0, within=None, kind="auto", availmemGb=8, de
     return maxt_from_raw(raw, t[used], kind, scale, first)
 
 
+# ---- transmission disequilibrium test of trios with max(T) flips (include/eagle_hip.h section 1b''''viii) ----
+def tdt_families(trios):
+    """The families of a trio list that gives no family ids (rule 5 of section 1b''''viii) -> int32 (T): the smallest list position with
+    the same (father, mother), so full sibs flip together."""
+    tr = np.asarray(trios, dtype=np.int64).reshape(-1, 3)
+    first = {}
+    return np.asarray([first.setdefault((int(f), int(m)), k) for k, (_, f, m) in enumerate(tr.tolist())], dtype=np.int32)
+
+
+def tdt_signs_host(family, seed, first, R):
+    """The signs of rule 5 -> int64 (R, T): flip first + q gives the trios of family phi the sign -1 when bit 31 of the 32-bit splitmix64
+    value at counter = r 2^16 + phi + 1 is set (maxt_key64_host's hash), else +1; uint64 arithmetic that wraps."""
+    u64 = np.uint64
+    fam = np.asarray(family, dtype=np.int64).ravel().astype(u64)
+    r = (np.arange(int(R), dtype=np.int64) + int(first)).astype(u64)
+    counter = (r[:, None] << u64(16)) + fam[None, :] + u64(1)
+    z = u64(int(seed) & (2 ** 64 - 1)) + counter * u64(0x9E3779B97F4A7C15)
+    z = (z ^ (z >> u64(30))) * u64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> u64(27))) * u64(0x94D049BB133111EB)
+    z = z ^ (z >> u64(31))
+    return np.where((z >> u64(63)) != 0, -1, 1).astype(np.int64)
+
+
+def tdt_host(g, called, trios, family=None, seed=0, first=1, R=0):
+    """rcpp_api.tdt / bed_tdt restated in numpy: g = int8 (L, n) with -1 hom A1, 0 het, +1 hom A2, called = bool (L, n) or None (everything
+    called; ibd_genotypes_bed gives both from .bed codes), trios = int (T, 3) -> the same dict of trio, marker, key_obs, count1, maxkey,
+    argmax, word for word: rules 1 to 5 of include/eagle_hip.h section 1b''''viii by the plane formulas on boolean columns, the flips as
+    int64 sums, key = (d * d) / V as two fp64 operations.  tests/tdt_truth.py pins it to loops over allele choices."""
+    A, B, Cm = _mendel_planes("tdt_host", g, called)
+    L, n = A.shape
+    tr, fam, seed, first, R = rcpp_api.tdt_args("tdt_host", trios, n, L, family, seed, first, R)
+    T = tr.shape[0]
+    tab = np.zeros((T, 6), dtype=np.int32)
+    marker = np.zeros((L, 5), dtype=np.int64)
+    D = np.zeros((L, T), dtype=np.int64)
+    none = np.zeros(L, dtype=bool)
+    for k, (c, f, m) in enumerate(tr.tolist()):
+        Ac, Bc, Cc = A[:, c], B[:, c], Cm[:, c]
+        Af, Bf, Cf = (A[:, f], B[:, f], Cm[:, f]) if f >= 0 else (none, none, none)
+        Am, Bm, Cmo = (A[:, m], B[:, m], Cm[:, m]) if m >= 0 else (none, none, none)
+        Hc = Cc & ~Ac & ~Bc
+        E = (Ac & Bf) | (Bc & Af) | ((Ac | (Hc & Bf)) & Bm) | ((Bc | (Hc & Af)) & Am)
+        K = Cc & Cf & Cmo & ~E
+        Hf, Hm = Cf & ~Af & ~Bf & K, Cmo & ~Am & ~Bm & K
+        PT, PU = Hf & (Bc | (Hc & Am)), Hf & (Ac | (Hc & Bm))
+        MT, MU = Hm & (Bc | (Hc & Af)), Hm & (Ac | (Hc & Bf))
+        W = Hf & Hm & Hc
+        kinds = np.stack([PT, PU, MT, MU, W], axis=1).astype(np.int64)
+        cnt = kinds.sum(axis=0)
+        tab[k] = (np.count_nonzero(K), np.count_nonzero(Hf), np.count_nonzero(Hm), cnt[0] + cnt[2] + cnt[4], cnt[1] + cnt[3] + cnt[4], cnt[4])
+        marker += kinds
+        D[:, k] = kinds[:, 0] + kinds[:, 2] - kinds[:, 1] - kinds[:, 3]
+    Tm, Um = marker[:, 0] + marker[:, 2] + marker[:, 4], marker[:, 1] + marker[:, 3] + marker[:, 4]
+    d_obs, V = Tm - Um, Tm + Um
+    Vf = V.astype(np.float64)
+
+    def keys(d):
+        df = d.astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where((Vf if d.ndim == 1 else Vf[:, None]) != 0, (df * df) / (Vf if d.ndim == 1 else Vf[:, None]), 0.0)
+
+    out = {"trio": tab, "marker": marker.astype(np.int32), "key_obs": keys(d_obs), "count1": np.zeros(L, dtype=np.int32),
+           "maxkey": np.zeros(R, dtype=np.float64), "argmax": np.zeros(R, dtype=np.int32)}
+    if R >= 1:
+        fam = tdt_families(tr) if fam is None else fam
+        step = max(1, (1 << 22) // max(L, T))
+        for r0 in range(0, R, step):
+            d = D @ tdt_signs_host(fam, seed, first + r0, min(step, R - r0)).T
+            k = keys(d)
+            out["count1"] += (np.abs(d) >= np.abs(d_obs)[:, None]).sum(axis=1).astype(np.int32)
+            out["maxkey"][r0:r0 + step], out["argmax"][r0:r0 + step] = k.max(axis=0), k.argmax(axis=0)
+    return out
+
+
+def _tdt_chisq(a, b):
+    """(a - b)^2 / (a + b) in fp64 on exact integers, NaN where a + b = 0, and its one-degree-of-freedom p."""
+    from scipy import special
+    a, b = np.asarray(a, dtype=np.int64), np.asarray(b, dtype=np.int64)
+    d, v = (a - b).astype(np.float64), (a + b).astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        x = np.where(v != 0, (d * d) / v, np.nan)
+    return x, special.chdtrc(1.0, x)
+
+
+def tdt_summary(raw, first=1):
+    """TDT's result from the raw outputs (rcpp_api.tdt, bed_tdt or tdt_host): host fp64 on exact integers.  Per marker: "T" = PT + MT + W
+    and "U" = PU + MU + W, the transmissions and non-transmissions of the allele that '2' stands for from het parents; "chisq" = key_obs =
+    (T - U)^2 / (T + U) with "p" = scipy.special.chdtrc(1, chisq); "or" = T / U; "p_exact" = min(1, 2 bdtr(min(T, U), T + U, 0.5)), the
+    two-sided exact binomial test; "chisq_pat", "p_pat" of (PT, PU) and "chisq_mat", "p_mat" of (MT, MU), where the het x het -> het
+    trios (W) cannot take part; "z_poo" = (p1 - p2) / sqrt(p (1 - p) (1 / n1 + 1 / n2)) with p1 = PT / n1, n1 = PT + PU, p2 = MT / n2, n2
+    = MT + MU and p = (PT + MT) / (n1 + n2), the pooled two-proportion z of paternal against maternal transmission, and "p_poo" =
+    2 ndtr(-|z_poo|) (this formula and no other program's).  With flips: "count1", "count2", "emp1" = (count1 + 1) / (R + 1) and "emp2"
+    = (count2 + 1) / (R + 1) as MaxT defines them, "max_stat" = maxkey and "argmax".  Markers without an informative transmission
+    (T + U = 0) have NaN in every statistic and p-value.  "R", "first", and "marker", "key_obs", "maxkey", "trio" (the raw words
+    tdt_merge needs)."""
+    from scipy import special
+    mk = np.asarray(raw["marker"]).astype(np.int64)
+    PT, PU, MT, MU, W = (mk[:, j] for j in range(5))
+    T, U = PT + MT + W, PU + MU + W
+    V = T + U
+    ok = V != 0
+    nan = lambda a: np.where(ok, a, np.nan)                                                    # noqa: E731
+    chisq = np.asarray(raw["key_obs"], dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        odds = np.where(U != 0, T / U.astype(np.float64), np.where(T != 0, np.inf, np.nan))
+        n1, n2 = (PT + PU).astype(np.float64), (MT + MU).astype(np.float64)
+        p1, p2, pp = PT / n1, MT / n2, (PT + MT) / (n1 + n2)
+        z = (p1 - p2) / np.sqrt(pp * (1.0 - pp) * (1.0 / n1 + 1.0 / n2))
+    z = np.where(np.isfinite(z), z, np.nan)
+    cp, pp_ = _tdt_chisq(PT, PU)
+    cm, pm = _tdt_chisq(MT, MU)
+    R = int(np.asarray(raw["maxkey"]).size)
+    out = {"T": T, "U": U, "chisq": nan(chisq), "p": nan(special.chdtrc(1.0, chisq)), "or": odds,
+           "p_exact": nan(np.minimum(1.0, 2.0 * special.bdtr(np.minimum(T, U).astype(np.float64), V, 0.5))),
+           "chisq_pat": cp, "p_pat": pp_, "chisq_mat": cm, "p_mat": pm, "z_poo": z, "p_poo": 2.0 * special.ndtr(-np.abs(z)),
+           "R": R, "first": int(first), "marker": np.asarray(raw["marker"]).copy(), "key_obs": chisq.copy(),
+           "maxkey": np.asarray(raw["maxkey"]).copy(), "trio": np.asarray(raw["trio"]).copy()}
+    if R >= 1:
+        count1 = np.asarray(raw["count1"]).astype(np.int64)
+        count2 = R - np.searchsorted(np.sort(raw["maxkey"]), chisq, side="left").astype(np.int64)
+        out.update({"count1": count1, "count2": count2, "emp1": nan((count1 + 1) / (R + 1.0)), "emp2": nan((count2 + 1) / (R + 1.0)),
+                    "max_stat": np.asarray(raw["maxkey"]).copy(), "argmax": np.asarray(raw["argmax"]).copy()})
+    return out
+
+
+def tdt_merge(a, b):
+    """Two TDT results of one panel, trio list and seed over disjoint ranges of flip ordinals (a second call with first=a["first"] +
+    a["R"]) -> the result of the union: count1 add, max_stat / argmax / maxkey concatenate in the order (a, b), count2 and the empirical
+    p-values are counted again."""
+    if not np.array_equal(a["marker"], b["marker"]) or not np.array_equal(a["trio"], b["trio"]):
+        raise ValueError("tdt_merge: the two results are not of one panel and trio list")
+    if a["R"] < 1 or b["R"] < 1:
+        raise ValueError("tdt_merge: a result without flips")
+    if a["first"] + a["R"] > b["first"] and b["first"] + b["R"] > a["first"]:
+        raise ValueError("tdt_merge: the ranges of flip ordinals overlap")
+    raw = {"marker": a["marker"], "trio": a["trio"], "key_obs": a["key_obs"], "count1": a["count1"] + b["count1"],
+           "maxkey": np.concatenate([a["maxkey"], b["maxkey"]]), "argmax": np.concatenate([a["argmax"], b["argmax"]])}
+    return tdt_summary(raw, min(a["first"], b["first"]))
+
+
+def TDT(geno, trios=None, fam=None, affected=None, bed=None, include=None, map=None, R=0, seed=0, family=None, first=1, availmemGb=8, device=0):
+    """The transmission disequilibrium test of the parent-offspring trios of a pedigreed panel (Spielman 1993; include/eagle_hip.h section
+    1b''''viii; rcpp_api.tdt; what PLINK reports as --tdt, --tdt poo and --tdt mperm, agreement with that program is not claimed; every
+    marker is taken as autosomal): do het parents pass the allele that '2' stands for to their affected children more often than not?
+    Unlike CaseControl on the children it is immune to population stratification.  -> tdt_summary's dict, plus "trios": the int32 (T, 3)
+    trios that were used and, with a map, "SNP".
+    trios = int (T, 3) of (child, father, mother), or fam = a .fam file (or ReadFam's dict) whose recorded trios are used (fam_trios;
+    default: the .fam of bed), as Mendel finds them.  affected: a bool per individual; default the .fam phenotype '2' when a .fam is
+    read, and everybody when trios= is given.  Only trios with an affected child are used; ValueError if none is left.  A trio with an
+    unknown parent, a missing call or a Mendel error at a marker contributes nothing there.
+    R >= 1: R seeded flips of transmitted and untransmitted alleles within families (family: one whole number in [0, 65535] per trio of
+    the list, before the affected children are selected; default: trios with the same parents), giving emp1 and the family-wise emp2 as MaxT does; first=first + R continues a run and
+    tdt_merge adds two results.  At most 65,535 trios with flips.
+    On the ingested (het-filled) panel a missing call is a het, which invents informative parents; bed = the .bed file (or prefix) the
+    panel was ingested from is the route for un-imputed panels (rcpp_api.bed_tdt); include = the panel's markers in the file, default
+    geno's marker_index."""
+    n, L, _, _, src_bed, bdims, inc = _ld_stats_source("TDT", geno, map, bed, include)
+    aff = None
+    if trios is None:
+        if fam is None and src_bed is None:
+            raise ValueError("TDT: give trios=, fam= or bed=")
+        fam = bed_fileset(src_bed)[2] if fam is None else fam
+        famd = ReadFam(fam) if isinstance(fam, (str, os.PathLike)) else fam
+        if len(famd["IID"]) != n:
+            raise ValueError("TDT: the .fam names %d individuals, the panel holds %d" % (len(famd["IID"]), n))
+        trios = fam_trios(famd)
+        if trios.shape[0] == 0:
+            raise ValueError("TDT: the .fam records no parent")
+        aff = np.asarray([p == "2" for p in famd["Pheno"]], dtype=bool)
+    tr = rcpp_api.mendel_trios("TDT", trios, n)
+    if affected is not None:
+        aff = np.asarray(affected)
+        if aff.dtype != bool or aff.shape != (n,):
+            raise ValueError("TDT: affected must be one bool per individual (%d)" % n)
+    if family is not None:
+        family = np.asarray(family)
+        if family.shape != (tr.shape[0],):
+            raise ValueError("TDT: family must hold one entry per trio of the list (%d)" % tr.shape[0])
+    if aff is not None:
+        use = aff[tr[:, 0]]
+        family = None if family is None else family[use]
+        tr = np.ascontiguousarray(tr[use])
+    if tr.shape[0] == 0:
+        raise ValueError("TDT: no trio with an affected child is left")
+    if src_bed is None:
+        raw = rcpp_api.tdt(geno["asciifileM"], (n, L), tr, family, seed, first, R, availmemGb, device=device)
+    else:
+        raw = rcpp_api.bed_tdt(src_bed, bdims, tr, inc, family, seed, first, R, availmemGb, device=device)
+    out = tdt_summary(raw, first)
+    out["trios"] = tr
+    if map is not None and "SNP" in map:
+        out["SNP"] = list(map["SNP"])
+    return out
+
+
 # ---- logistic regression per marker with covariates, Firth fallback (include/eagle_hip.h section 1b''''iv) ----
 _LOGIT_ETA_MAX, _LOGIT_STEP_MAX, _LOGIT_PIVOT_REL = 40.0, 5.0, 2.0 ** -40
 

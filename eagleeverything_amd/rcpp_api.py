@@ -1668,6 +1668,82 @@ def maxt(fMt, dims, t, used=None, strata=None, seed=0, first=1, R=1000, perm=Non
             return out
 
 
+# ---- transmission disequilibrium test of trios (include/eagle_hip.h section 1b''''viii); the statistics and p-values are r_api's ----
+TDT_MAX_FLIP_TRIOS = 65535
+
+
+def tdt_args(who, trios, n, nm, family, seed, first, R):
+    """The arguments of a TDT call checked without the library -> (trios int32 (T, 3), family int32 (T) or None, seed, first, R) as the
+    library takes them; ValueError for what section 1b''''viii calls an argument error: mendel_trios' rule, 2^31 markers or more, a
+    negative R, first < 1, first + R > 2^31, more than 65,535 trios with R >= 1, a family list that is not one whole number in
+    [0, 65535] per trio."""
+    tr = mendel_trios(who, trios, n)
+    if nm >= 1 << 31:
+        raise ValueError("%s: 2^31 markers or more" % who)
+    try:
+        Ri, fi, sd = int(R), int(first), int(seed)
+    except (TypeError, ValueError):
+        raise ValueError("%s: R, first and seed must be whole numbers" % who)
+    if Ri != R or fi != first or sd != seed or Ri < 0:
+        raise ValueError("%s: R, first and seed must be whole numbers, R not negative" % who)
+    fam = None
+    if Ri >= 1:
+        if fi < 1 or fi + Ri > 1 << 31:
+            raise ValueError("%s: first must be at least 1 and first + R at most 2^31" % who)
+        if tr.shape[0] > TDT_MAX_FLIP_TRIOS:
+            raise ValueError("%s: more than 65535 trios with flips (R >= 1)" % who)
+        if family is not None:
+            fam = _whole_int32(who, "family", family, 1)
+            if fam.size != tr.shape[0] or (fam.size and (fam.min() < 0 or fam.max() > 65535)):
+                raise ValueError("%s: family must hold one whole number in [0, 65535] per trio" % who)
+    return tr, fam, sd & (2 ** 64 - 1), fi, Ri
+
+
+def _tdt_call(fn, device, head, tr, fam, seed, first, R, nm, mem):
+    T = tr.shape[0]
+    out = {"trio": np.zeros((T, 6), dtype=np.int32), "marker": np.zeros((nm, 5), dtype=np.int32), "key_obs": np.zeros(nm, dtype=np.float64),
+           "count1": np.zeros(nm, dtype=np.int32), "maxkey": np.zeros(R, dtype=np.float64), "argmax": np.zeros(R, dtype=np.int32)}
+    r0 = 0
+    while True:
+        nr = min(MAXT_RMAX, R - r0)
+        c1 = np.zeros(nm, dtype=np.int32)
+        mk, am = np.zeros(max(nr, 1), dtype=np.float64), np.zeros(max(nr, 1), dtype=np.int32)
+        _args_first(fn, device, head + (tr.ctypes.data_as(_c_i32p), T, None if fam is None else fam.ctypes.data_as(_c_i32p), C.c_uint64(seed),
+                                        first + r0, nr, float(mem), out["trio"].ctypes.data_as(_c_i32p), out["marker"].ctypes.data_as(_c_i32p),
+                                        _dp(out["key_obs"]), c1.ctypes.data_as(_c_i32p), _dp(mk), am.ctypes.data_as(_c_i32p)))
+        out["count1"] += c1
+        out["maxkey"][r0:r0 + nr], out["argmax"][r0:r0 + nr] = mk[:nr], am[:nr]
+        r0 += nr
+        if r0 >= R:
+            return out
+
+
+def tdt(f_name_ascii_M, dims, trios, family=None, seed=0, first=1, R=0, max_memory_in_Gbytes=8.0, device=0):
+    """eagle_tdt -> {"trio" int32 (T, 6), "marker" int32 (L, 5), "key_obs" fp64 (L), "count1" int32 (L), "maxkey" fp64 (R), "argmax" int32
+    (R)}: the raw outputs of include/eagle_hip.h section 1b''''viii on the ingested panel M.ascii (dims = (n, L) of M).  trios: int (T, 3)
+    of (child, father, mother), -1 = unknown parent.  trio rows = (complete markers, informative het fathers, informative het mothers,
+    T_t, U_t, W_t); marker rows = (PT, PU, MT, MU, W) summed over the list; key_obs = the TDT chi-square (T - U)^2 / (T + U).  R = 0:
+    counts only.  R >= 1: the flips first .. first + R - 1 of the families (family: one whole number in [0, 65535] per trio; None: trios
+    with the same parents are one family); more than MAXT_RMAX = 1024 flips run as several calls of the library, whose count1 add and
+    whose maxkey and argmax concatenate.  ValueError for bad arguments before the library is loaded.  r_api.tdt_host restates it."""
+    n, nm = max(int(dims[0]), 0), max(int(dims[1]), 0)
+    tr, fam, sd, fi, Ri = tdt_args("tdt", trios, n, nm, family, seed, first, R)
+    L = _lib.load()
+    return _tdt_call(L.eagle_tdt, device, (os.fsencode(f_name_ascii_M), _dims(dims)), tr, fam, sd, fi, Ri, nm, max_memory_in_Gbytes)
+
+
+def bed_tdt(bed_path, dims, trios, include=None, family=None, seed=0, first=1, R=0, availmemGb=8.0, device=0):
+    """eagle_bed_tdt -> tdt's dict by PANEL marker from a SNP-major PLINK .bed file of dims = (n individuals, L markers), which still knows
+    its missing calls: a trio with a missing call at a marker is not complete there.  include as in bed_ld_window."""
+    n, nm = max(int(dims[0]), 0), max(int(dims[1]), 0)
+    inc = _bed_ld_include(include, nm, "bed_tdt")
+    linc = nm if inc is None else int(inc.sum())
+    tr, fam, sd, fi, Ri = tdt_args("bed_tdt", trios, n, linc, family, seed, first, R)
+    L = _lib.load()
+    head = (os.fsencode(bed_path), _dims(dims), inc.ctypes.data_as(C.c_void_p) if inc is not None else None)
+    return _tdt_call(L.eagle_bed_tdt, device, head, tr, fam, sd, fi, Ri, linc, availmemGb)
+
+
 # ---- pairwise haplotype EM and D' (include/eagle_hip.h section 1b''''vii); the blocks are r_api's ----
 def hap_ld(fMt, dims, window=50, tol=1e-10, max_iter=1000, fg_cut=0.01, dprime_cut=0.8, bands=False, masks=True, availmemGb=8, device=0):
     """eagle_hap_ld -> {"recomb", "strong": uint64 (L, ceil(window / 64)), bit (o - 1) % 64 of word (o - 1) // 64 of row i = the verdict

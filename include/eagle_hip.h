@@ -1289,6 +1289,68 @@ int eagle_hap_ld(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long dims[2]
                  double* r2_out, int64_t* counts_out);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1b''''viii. Transmission disequilibrium test of parent-offspring trios (no counterpart in the reference; Spielman 1993; PLINK's
+ *     --tdt, --tdt poo and --tdt mperm): among heterozygous parents of affected children, is the '2' allele passed on more often than
+ *     not?  The test is immune to population stratification, which the case/control tests of 1b''''iii are not.  On the bit planes of
+ *     1b'''vii with the trios of 1b'''viii.  All outputs are integers or two correctly rounded fp64 operations on exact operands, so
+ *     the device and a numpy restatement (r_api.tdt_host) agree with == on every output.
+ *
+ *     Genotypes, called, trios and their argument errors are rules 1 and 2 of 1b'''viii (Mendel).  H = C & ~A & ~B is the het plane.  A trio
+ *     with an unknown parent is legal and contributes nothing.
+ *
+ *     1. Complete.  K = C_c & C_f & C_m & ~E, with E the Mendel error word of rule 3 of 1b'''viii: all three are called and the trio
+ *        has no Mendel error there.  Hf = H_f & K and Hm = H_m & K are the informative het parents.
+ *     2. Transmissions of the '2' allele.  A2 is the allele of genotype +1, the one CaseControl and Logistic report.
+ *            PT = Hf & (B_c | H_c & A_m)     PU = Hf & (A_c | H_c & B_m)
+ *            MT = Hm & (B_c | H_c & A_f)     MU = Hm & (A_c | H_c & B_f)
+ *            W  = Hf & Hm & H_c
+ *        PT / PU: the father passed A2 / A1; MT / MU: the same for the mother.  W: het x het -> het, one A2 and one A1 were passed
+ *        and the origin is unknown.  Of the 27 called code triples 11 are informative, and popcount(Hf) + popcount(Hm) = PT + PU + MT
+ *        + MU + 2 W on every triple (tests/tdt_truth.py enumerates the allele choices of all 64).  Per trio and marker
+ *        d = PT + MT - PU - MU lies in [-2, 2].
+ *     3. Per-marker output.  marker_out: L x 5 int32 = (PT, PU, MT, MU, W), summed over the trios of the list; a trio listed twice
+ *        counts twice.  T = PT + MT + W, U = PU + MU + W, d_obs = T - U, V = T + U.  key_obs = fl(fl(d d) / V) in fp64, two separately
+ *        rounded operations, 0 where V = 0: the TDT chi-square (T - U)^2 / (T + U) as it is reported.
+ *     4. Per-trio output.  trio_out: ntrios x 6 int32 = (popcount K, popcount Hf, popcount Hm, T_t, U_t, W_t) over the panel, with
+ *        T_t = PT + MT + W and U_t = PU + MU + W of the trio.
+ *     5. Flips.  For R >= 1 only.  The family of trio t is family[t] if given, int32 in [0, 65535]; otherwise the smallest list
+ *        position k with (f_k, m_k) = (f_t, m_t), so full sibs flip together.  Flip r >= 1 gives family phi the sign -1 when bit 31
+ *        of h is set, else +1, with h the 32-bit splitmix64 value of rule 4 of 1b''''vi at counter = r 2^16 + phi + 1: transmitted and
+ *        untransmitted alleles change places in the whole family.  d_m^(r) = sum_t s_r(phi_t) d_{t,m}; V does not change under a flip;
+ *        key^(r) is as in rule 3.  count1[m] = #{r : |d_m^(r)| >= |d_obs,m|}, compared as integers.  maxkey[R] is the largest key of
+ *        flip r and argmax[R] the lowest marker that attains it.  Calls over [first, first + R) add and concatenate exactly as
+ *        eagle_maxt's do.
+ *     6. Limits.  ntrios in [1, 2^27] when R = 0; ntrios <= 65,535, R <= 1024 per call and first + R <= 2^31 when R >= 1; panel markers
+ *        < 2^31; n <= 0x3fffffff for the .bed file.  The planes stay on the device for the call with the per-trio and per-marker
+ *        arrays and, for R >= 1, the int8 image of d (marker-major, leading dimension ceil16(ntrios)), the sign operand and the
+ *        tiles' partial maxima; where the image does not fit the memory budget (rule 9 of 1b'''vii) beside the planes it is built
+ *        and multiplied in bands of whole 128-marker tiles; where even one band does not fit the call returns EAGLE_ERR_NOMEM,
+ *        decided before any kernel runs.  Argument errors are decided before the context is used; with ctx == NULL their text is in
+ *        eagle_open_error().
+ *     7. Not claimed and out of scope.  Agreement with the PLINK program is neither claimed nor tested.  Every marker is autosomal.
+ *        On the ingested image a missing call is a het, which invents informative parents: the .bed route is the one for un-imputed
+ *        panels.  Sib-TDT / DFAM, parental discordance tests, adaptive permutation, covariates and several devices are out of scope.
+ *
+ *     k_tdt_trios (csrc/eagle_tdt.hip) has one lane per trio as k_mendel_trios has, and turns the wave's 64 words of each of the five
+ *     kinds into per-bit totals by ballot and popcount, added to marker_out with 32-bit integer atomics; k_tdt_finish forms d_obs, V
+ *     and key_obs; k_tdt_image transposes 64 markers x 64 trios of d through LDS into the int8 image; k_tdt_signs writes the +-1
+ *     operand; the product, count1 and the per-flip maxima are k_maxt_tile and k_maxt_finish of 1b''''vi as they stand (N = 1, T = 0,
+ *     S = 0).  Single device: a multi-device context works on its first device.
+ * ------------------------------------------------------------------------------------------- */
+/* Rules 1 to 5 on the ingested panel M.ascii (dims = (n, L) of M).  trios: ntrios x 3 int32; family: ntrios int32 or NULL; trio_out:
+ * ntrios x 6 int32; marker_out: L x 5 int32; key_obs: L fp64; R = 0 means counts only: count1 (L int32), maxkey (R fp64) and argmax (R
+ * int32) may then be NULL and seed, first and family are not read. */
+int eagle_tdt(eagle_ctx* ctx, const char* f_name_ascii_M, const long dims[2], const int32_t* trios, long ntrios, const int32_t* family,
+              uint64_t seed, long first, long R, double max_memory_in_Gbytes, int32_t* trio_out, int32_t* marker_out, double* key_obs,
+              int32_t* count1, double* maxkey, int32_t* argmax);
+
+/* The same by PANEL marker (the Linc markers include selects, L bytes or NULL) from the SNP-major .bed file bed_path (dims = (n, L) of the
+ * file), which still knows its missing calls: a trio with a missing call at a marker is not complete there. */
+int eagle_bed_tdt(eagle_ctx* ctx, const char* bed_path, const long dims[2], const uint8_t* include, const int32_t* trios, long ntrios,
+                  const int32_t* family, uint64_t seed, long first, long R, double max_memory_in_Gbytes, int32_t* trio_out,
+                  int32_t* marker_out, double* key_obs, int32_t* count1, double* maxkey, int32_t* argmax);
+
+/* ---------------------------------------------------------------------------------------------
  * 1c. Dense n x n model algebra on the device (OPT-IN: north_star keeps calculateH / calculateP / emma.* on
  *     host LAPACK, and nothing above calls these).  Once the scan takes tens of milliseconds the ~10-15 O(n^3) base-R calls
  *     of a find_qtl iteration are the whole run time (the author's note MyPackage/MyREADME:1 names eigen(); his MAGMA
