@@ -14,7 +14,9 @@ mirror of the reference interface used by tests, bench.py and the sharded multi-
                 maxt_permutations_host, maxt_merge;
                 HapLD, HapBlocks (pairwise haplotype EM, D' and haplotype blocks), hap_ld_host, hap_blocks_host, sets_from_blocks;
                 TDT (the transmission disequilibrium test of parent-offspring trios with max(T) flips within families), tdt_host,
-                tdt_families, tdt_summary, tdt_merge
+                tdt_families, tdt_summary, tdt_merge;
+                ReadMarker(type="VCF"), VcfToBed (a VCF file's GT fields decoded on the device into a PLINK binary fileset, missing
+                calls kept missing for every bed= route), vcf_to_bed_host
   host_model -- dense n x n model algebra that stays on host LAPACK by design
   sharded    -- marker-sharded multi-GPU scan / MM^T (one process per GPU, torch.distributed over RCCL)
   synth      -- seeded synthetic genotypes of the benchmark shapes

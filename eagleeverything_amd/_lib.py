@@ -23,6 +23,12 @@ class RohParams(C.Structure):
     _fields_ = [(f, C.c_int64) for f in ("w", "win_het", "win_miss", "thr16", "min_snp", "min_len", "max_gap", "max_density", "max_het")]
 
 
+class VcfCounts(C.Structure):
+    """eagle_vcf_counts of include/eagle_hip.h section 1b-vcf."""
+    _fields_ = [(f, C.c_long) for f in ("lines", "kept", "multiallelic", "no_alt", "no_gt", "not_snp", "filtered", "missing", "haploid",
+                                        "malformed")]
+
+
 class IbdParams(C.Structure):
     """eagle_ibd_params of include/eagle_hip.h section 1b'''vii."""
     _fields_ = [(f, C.c_int64) for f in ("mode", "min_snp", "min_len", "max_gap", "merge_min")]
@@ -75,6 +81,7 @@ SIGNATURES = {
                                        C.c_double, c_lp, C.c_int, C.c_char_p]),
     "eagle_create_Mt_ascii": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_double, c_lp, C.c_int]),
     "eagle_create_ascii_from_bed": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_double, c_lp, C.c_int, c_lp]),
+    "eagle_vcf_to_bed": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int, C.c_double, C.c_long, c_lp, C.POINTER(VcfCounts)]),
     "eagle_marker_counts": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, C.c_double, C.POINTER(C.c_int32)]),
     "eagle_bed_marker_counts": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, C.c_double, C.POINTER(C.c_int32)]),
     "eagle_filter_markers": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, c_lp, c_lp, C.c_long, C.c_char_p, C.c_char_p, C.c_double, c_lp]),

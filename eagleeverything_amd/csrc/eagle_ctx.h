@@ -294,6 +294,12 @@ extern "C" int eagle_dev_bed_decode(eagle_ctx* ctx, const uint8_t* bed, long rea
 // (zero rows up to rows_out).
 extern "C" int eagle_dev_marker_counts(eagle_ctx* ctx, const int8_t* Mt8, long rows, long n, long ld, int32_t* counts, void* stream);
 extern "C" int eagle_dev_bed_marker_counts(eagle_ctx* ctx, const uint8_t* bed, long rows, long n, int32_t* counts, void* stream);
+// VCF sample fields (eagle_vcf.hip; include/eagle_hip.h section 1b-vcf), device pointers throughout.  text: a staged window, readable up to the
+// next multiple of 16 behind the largest table entry; table[lines][2] = [beg, end) of every kept line from its first sample field;
+// codes[lines][n]: one .bed code per byte; cnt[lines][4] = (fields found, missing, haploid, malformed); bed[lines][ceil(n/4)].
+extern "C" int eagle_dev_vcf_fields(eagle_ctx* ctx, const uint8_t* text, const int64_t* table, long lines, long n, int a2_alt, uint8_t* codes,
+                                    int32_t* cnt, void* stream);
+extern "C" int eagle_dev_vcf_pack(eagle_ctx* ctx, const uint8_t* codes, long lines, long n, uint8_t* bed, void* stream);
 extern "C" int eagle_dev_gather_rows_i8(eagle_ctx* ctx, const int8_t* src, long ld_src, const int32_t* map, long nrows, long rows_out,
                                         int8_t* out, long ld_out, void* stream);
 // Per-group counts (eagle_groups.hip; include/eagle_hip.h section 1b''''iii), device pointers throughout.  labels[n] in [-1, K) (the CALLER's

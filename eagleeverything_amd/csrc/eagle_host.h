@@ -919,4 +919,101 @@ static inline const char* tdt_arg_error(long markers, long ntrios, const int32_t
             if (family[k] < 0 || family[k] > 65535) return "a family outside [0, 65535]";
     return nullptr;
 }
+
+// ------------------------------------------------------------------------------------------------
+// VCF text in front of eagle_vcf_to_bed (include/eagle_hip.h section 1b-vcf): the line splitter of a staged window, the header line,
+// the nine fixed fields of a data line and the verdict on them.  The sample fields are the device's (eagle_vcf.hip).
+// ------------------------------------------------------------------------------------------------
+#define VCF_A2_ALT 1
+#define VCF_SNPS_ONLY 2
+#define VCF_PASS_ONLY 4
+#define VCF_FLAGS_ALL 7
+// The line of buf[0, size) that starts at pos: [*b, *e) without its '\n' and without a '\r' in front of it; *next = where the following
+// line starts.  A tail without '\n' is a line only when `last` (the buffer ends the file); else false: the line is not whole.
+static inline bool vcf_next_line(const char* buf, size_t size, size_t pos, bool last, size_t* b, size_t* e, size_t* next) {
+    if (pos >= size) return false;
+    const char* q = (const char*)memchr(buf + pos, '\n', size - pos);
+    if (!q && !last) return false;
+    size_t end = q ? (size_t)(q - buf) : size;
+    *next = q ? end + 1 : size;
+    if (end > pos && buf[end - 1] == '\r') end--;
+    *b = pos;
+    *e = end;
+    return true;
+}
+// Where the last whole line of buf[0, size) ends (the offset behind its '\n'), 0 when the buffer holds no '\n'.
+static inline size_t vcf_whole_lines(const char* buf, size_t size) {
+    for (size_t i = size; i > 0; i--)
+        if (buf[i - 1] == '\n') return i;
+    return 0;
+}
+struct VcfSpan { const char* p; long len; };
+static inline bool vcf_span_is(const VcfSpan& s, const char* lit) { const size_t n = strlen(lit); return (size_t)s.len == n && memcmp(s.p, lit, n) == 0; }
+// The first `want` tab-separated fields of [p, e) -> f[0 .. want); returns how many there are (at most `want`), and in *rest the byte
+// behind the tab that ends field `want` - 1, or nullptr when the line ends with that field (or before it).
+static inline int vcf_split_tabs(const char* p, const char* e, VcfSpan* f, int want, const char** rest) {
+    int k = 0;
+    *rest = nullptr;
+    while (k < want) {
+        const char* t = (const char*)memchr(p, '\t', (size_t)(e - p));
+        f[k].p = p;
+        f[k].len = (t ? t : e) - p;
+        k++;
+        if (!t) return k;
+        p = t + 1;
+    }
+    *rest = p;
+    return k;
+}
+// The #CHROM line [p, e) -> the sample names; nullptr, or what is wrong with it.
+static inline const char* vcf_header_error(const char* p, const char* e, std::vector<VcfSpan>& names) {
+    names.clear();
+    VcfSpan f[9];
+    const char* rest;
+    if (e - p < 6 || memcmp(p, "#CHROM", 6) != 0) return "no #CHROM line in front of the data";
+    if (vcf_split_tabs(p, e, f, 9, &rest) < 9 || !rest) return "the #CHROM line has fewer than 10 columns";
+    while (rest) {
+        VcfSpan s;
+        const char* r2;
+        vcf_split_tabs(rest, e, &s, 1, &r2);
+        if (s.len == 0) return "an empty sample name";
+        if (memchr(s.p, ' ', (size_t)s.len)) return "a sample name that contains a blank";
+        names.push_back(s);
+        rest = r2;
+    }
+    return nullptr;
+}
+enum VcfVerdict { VCF_KEEP = 0, VCF_MULTIALLELIC, VCF_NO_ALT, VCF_NO_GT, VCF_NOT_SNP, VCF_FILTERED };
+static inline bool vcf_is_base(const VcfSpan& s) {
+    if (s.len != 1) return false;
+    const char c = (char)(s.p[0] & ~0x20);
+    return c == 'A' || c == 'C' || c == 'G' || c == 'T';
+}
+// The verdict on a data line from its nine fixed fields (CHROM POS ID REF ALT QUAL FILTER INFO FORMAT), the first reason that holds.
+static inline VcfVerdict vcf_verdict(const VcfSpan f[9], int flags) {
+    const VcfSpan &ref = f[3], &alt = f[4], &filter = f[6], &format = f[8];
+    if (memchr(alt.p, ',', (size_t)alt.len)) return VCF_MULTIALLELIC;
+    if (vcf_span_is(alt, ".")) return VCF_NO_ALT;
+    if (!(vcf_span_is(format, "GT") || (format.len >= 3 && memcmp(format.p, "GT:", 3) == 0))) return VCF_NO_GT;
+    if ((flags & VCF_SNPS_ONLY) && !(vcf_is_base(ref) && vcf_is_base(alt))) return VCF_NOT_SNP;
+    if ((flags & VCF_PASS_ONLY) && !(vcf_span_is(filter, "PASS") || vcf_span_is(filter, "."))) return VCF_FILTERED;
+    return VCF_KEEP;
+}
+// Tab-separated fields of [p, e): the tabs + 1 (an empty range is one empty field).
+static inline long vcf_count_fields(const char* p, const char* e) {
+    long k = 1;
+    while (p < e && (p = (const char*)memchr(p, '\t', (size_t)(e - p))) != nullptr) { k++; p++; }
+    return k;
+}
+// Bytes a staging window of eagle_vcf_to_bed holds: chunk_bytes, or when that is 0 the staging rule of the eagle_bed_* calls (64 MiB, a
+// quarter of max_memory_in_Gbytes if less); never below 4096.  vcf_line_fits: a window grows to a line only inside that quarter.
+static inline long vcf_window_bytes(long chunk_bytes, double mem_gb) {
+    if (chunk_bytes > 0) return chunk_bytes;
+    double cap = 67108864.0;
+    if (mem_gb > 0) cap = std::min(cap, mem_gb * 1e9 / 4.0);
+    return std::max(4096L, (long)cap);
+}
+static inline bool vcf_line_fits(long line_bytes, double mem_gb) { return mem_gb <= 0 || (double)line_bytes <= mem_gb * 1e9 / 4.0; }
+// Kept lines a window of `cap` text bytes can hold when every kept line carries n sample fields: a field and its separator are two bytes.
+static inline long vcf_window_lines(long cap, long n) { return cap / (2 * n) + 1; }
 #endif

@@ -666,7 +666,7 @@ int write_lines_from_image(eagle_ctx* ctx, int fd, const char* path, const int8_
 // whose rows go to the device in windows the caller chooses (they may overlap, or leave rows out) through the context's two pinned /
 // device staging buffers in turn.  Window k: stage() -- pread into pinned buffer k & 1, upload -- then the caller's kernels on
 // ctx->stream, then release(), which records the buffer's event behind the last operation that reads the staged rows or writes the
-// pinned buffer.  THE buffer-reuse rule lives here and nowhere else: stage() of window k waits for the event of window k - 2, i.e.
+// pinned buffer.  THE buffer-reuse rule lives here and nowhere else: stage() of window k (its first step, acquire()) waits for the event of window k - 2, i.e.
 // until window k - 2 has left staging buffer b, so the pread of window k runs under the device work of window k - 1.  A caller that
 // fails inside its window loop drains the stream before it returns: the ring's buffers belong to the context and outlive the call.
 struct BedRing {
@@ -709,18 +709,42 @@ struct BedRing {
     int last() const { return (int)((windows - 1) & 1); }   // the buffer staged last
     char* pinned(int b) const { return (char*)ctx->stage_pin[b]; }
     uint8_t* device(int b) const { return (uint8_t*)ctx->stage_raw[b]; }
+    // The same ring over a file that is no .bed file (eagle_vcf_to_bed's text): no header check, no rows; the caller stages byte spans
+    // with acquire() / fill() / upload() and keeps the rule by calling release() once per window.  *size_out = the file's bytes.
+    int open_bytes(eagle_ctx* c, const char* file_path, long long* size_out) {
+        ctx = c; path = file_path; threads = host_threads(); rb = 1;
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        fd = ::open(file_path, O_RDONLY);
+        struct stat st;
+        if (fd < 0 || fstat(fd, &st) != 0) return failf(ctx, EAGLE_ERR_OPEN, "ERROR: Could not open  %s", file_path);
+        *size_out = (long long)st.st_size;
+        HIPCHK(ctx, ev.create());
+        return EAGLE_OK;
+    }
+    // the next window's buffer, free: window k - 2 has left it
+    int acquire() {
+        const int b = (int)(windows & 1);
+        if (windows >= 2) HIPCHK(ctx, hipEventSynchronize(ev.e[b]));
+        windows++;
+        return EAGLE_OK;
+    }
+    // `bytes` of the file from `off` into the acquired buffer's pinned half, `at` bytes in
+    bool fill(off_t off, size_t bytes, size_t at) { return pread_all(fd, pinned(last()) + at, bytes, off, threads); }
+    // that span on its way to the device half (stream order)
+    int upload(size_t at, size_t bytes, const uint8_t** raw) {
+        const int b = last();
+        HIPCHK(ctx, hipMemcpyAsync(device(b) + at, pinned(b) + at, bytes, hipMemcpyHostToDevice, ctx->stream));
+        *raw = device(b) + at;
+        return EAGLE_OK;
+    }
     // file rows [f0, f0 + rows) on their way to *raw (stream order)
     int stage(long f0, long rows, const uint8_t** raw) {
-        const int b = (int)(windows & 1);
-        if (windows >= 2) HIPCHK(ctx, hipEventSynchronize(ev.e[b]));  // window k - 2 has left staging buffer b
-        windows++;
-        if (!pread_all(fd, pinned(b) + byte_off, (size_t)rows * rb, (off_t)BED_HEADER_BYTES + (off_t)f0 * rb, threads)) {
+        if (int rc = acquire()) return rc;
+        if (!fill((off_t)BED_HEADER_BYTES + (off_t)f0 * rb, (size_t)rows * rb, byte_off)) {
             (void)hipStreamSynchronize(ctx->stream);
             return failf(ctx, EAGLE_ERR_FORMAT, "%s: could not read markers %ld to %ld", path, f0 + 1, f0 + rows);
         }
-        HIPCHK(ctx, hipMemcpyAsync(device(b) + byte_off, pinned(b) + byte_off, (size_t)rows * rb, hipMemcpyHostToDevice, ctx->stream));
-        *raw = device(b) + byte_off;
-        return EAGLE_OK;
+        return upload(byte_off, (size_t)rows * rb, raw);
     }
     int release() {
         HIPCHK(ctx, hipEventRecord(ev.e[last()], ctx->stream));
@@ -953,6 +977,306 @@ extern "C" int eagle_bed_marker_counts(eagle_ctx* ctx, const char* bed_path, con
     if (rc) return rc;
     HIPCHK(ctx, hipMemcpyAsync(counts_out, counts.p, sizeof(int32_t) * 4 * (size_t)L, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return EAGLE_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// VCF -> PLINK binary fileset (include/eagle_hip.h section 1b-vcf; kernels in eagle_vcf.hip)
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+
+static_assert(VCF_A2_ALT == EAGLE_VCF_A2_ALT && VCF_SNPS_ONLY == EAGLE_VCF_SNPS_ONLY && VCF_PASS_ONLY == EAGLE_VCF_PASS_ONLY, "flag values");
+#define VCF_MAX_WINDOW 1073741824L   /* 2^30: the longest line, and the largest window */
+
+// the output fileset: what this call created is removed again unless the call gets as far as keep()
+struct VcfFileset {
+    std::string bed, bim, fam;
+    FILE* fbim = nullptr;
+    bool made_bed = false, made_fam = false, kept = false;
+    ~VcfFileset() {
+        if (fbim) fclose(fbim);
+        if (kept) return;
+        if (made_bed) unlink(bed.c_str());
+        if (fbim) unlink(bim.c_str());
+        if (made_fam) unlink(fam.c_str());
+    }
+    bool keep() {
+        const bool ok = fbim && fclose(fbim) == 0;
+        fbim = nullptr;
+        if (!ok) unlink(bim.c_str());
+        kept = ok;
+        return ok;
+    }
+};
+
+// the kept lines of one window, until their counters are back: file line numbers, and which staging buffer's pinned table holds them
+struct VcfPending {
+    bool live = false;
+    long window = 0;
+    std::vector<long> line_no;
+};
+
+// Where the line that starts at `from` ends: the offset behind its '\n', or the file size.  -1: a read failed.
+long long vcf_line_end(int fd, long long from, long long fsize) {
+    char buf[65536];
+    for (long long at = from; at < fsize;) {
+        const ssize_t got = pread(fd, buf, (size_t)std::min<long long>((long long)sizeof buf, fsize - at), (off_t)at);
+        if (got <= 0) return -1;
+        const char* q = (const char*)memchr(buf, '\n', (size_t)got);
+        if (q) return at + (q - buf) + 1;
+        at += got;
+    }
+    return fsize;
+}
+
+}  // namespace
+
+// Window k: acquire a staging buffer (the ring's rule), pread whole lines into its pinned half and send them up; the host then splits
+// the lines, parses the fixed fields, appends the .bim lines and fills the kept lines' table while the device still works on window
+// k - 1; table up, k_vcf_fields, k_vcf_pack, counters and rows back into pinned memory, and BedRewrite writes window k - 1's rows.
+// The counters of a window are checked when its buffer comes round again (or at the end): a kept line whose field count is not n fails
+// the call.  Errors are reported in file order: before a host-side error is returned, the lines in front of it are checked.
+extern "C" int eagle_vcf_to_bed(eagle_ctx* ctx, const char* vcf_path, const char* out_prefix, int flags, double max_memory_in_Gbytes,
+                                long chunk_bytes, long dims_out[2], eagle_vcf_counts* counts_out) {
+    if (!vcf_path || !out_prefix || !dims_out || !counts_out) return qc_fail(ctx, EAGLE_ERR_ARG, "vcf_to_bed: NULL argument");
+    if (flags & ~VCF_FLAGS_ALL) return qc_fail(ctx, EAGLE_ERR_ARG, "vcf_to_bed: unknown flag bits (section 1b-vcf: A2_ALT 1, SNPS_ONLY 2, PASS_ONLY 4)");
+    if (chunk_bytes < 0) return qc_fail(ctx, EAGLE_ERR_ARG, "vcf_to_bed: chunk_bytes must not be negative");
+    if (chunk_bytes > VCF_MAX_WINDOW) return qc_fail(ctx, EAGLE_ERR_ARG, "vcf_to_bed: chunk_bytes above 2^30");
+    if (!out_prefix[0]) return qc_fail(ctx, EAGLE_ERR_ARG, "vcf_to_bed: empty output prefix");
+    if (!ctx) return qc_fail(ctx, EAGLE_ERR_ARG, "vcf_to_bed: no context");
+
+    BedRing ring;
+    long long fsize = 0;
+    if (int orc = ring.open_bytes(ctx, vcf_path, &fsize)) return orc;
+    const double mem = max_memory_in_Gbytes;
+    long cap = std::min(vcf_window_bytes(chunk_bytes, mem), VCF_MAX_WINDOW);
+    if (chunk_bytes == 0) cap = std::min<long long>(cap, std::max<long long>(4096, fsize));   // a small file needs no 64 MiB
+    auto text_room = [](long bytes) { return (size_t)((bytes + 16 + 255) / 256 * 256); };     // the rounded-up last 16-byte load stays inside
+    int rc = eagle_stage_ensure(ctx, text_room(cap));
+    if (rc) return rc;
+
+    VcfFileset files;
+    files.bed = std::string(out_prefix) + ".bed";
+    files.bim = std::string(out_prefix) + ".bim";
+    files.fam = std::string(out_prefix) + ".fam";
+    BedRewrite out;
+    eagle_vcf_counts cn;
+    memset(&cn, 0, sizeof cn);
+    bool have_header = false;
+    long n = 0, rb = 0, line_no = 0, window = 0, lines_cap = 0;
+    const int a2_alt = (flags & VCF_A2_ALT) ? 1 : 0;
+    PinBuf pin_tab[2];                      // per staging buffer: the table (16 bytes a line), then the counters (16 bytes a line)
+    DevBuf d_tab, d_codes, d_cnt, d_bed;    // one of each: window k follows window k - 1 in stream order
+    VcfPending pend[2];
+    std::string bimbuf;
+    char msg[400];
+
+    // (re)size what depends on the kept lines a window can hold; the stream is idle and nothing is pending when this is called
+    auto size_lines = [&](long text_bytes) -> int {
+        const long want = vcf_window_lines(text_bytes, n);
+        if (want <= lines_cap) return EAGLE_OK;
+        for (int b = 0; b < 2; b++) {
+            if (pin_tab[b].p) { (void)hipHostFree(pin_tab[b].p); pin_tab[b].p = nullptr; }
+            HIPCHK(ctx, pin_tab[b].alloc(32 * (size_t)want));
+        }
+        for (DevBuf* d : {&d_tab, &d_codes, &d_cnt, &d_bed})
+            if (d->p) { (void)hipFree(d->p); d->p = nullptr; }
+        HIPCHK(ctx, d_tab.alloc(16 * (size_t)want));
+        HIPCHK(ctx, d_cnt.alloc(16 * (size_t)want));
+        HIPCHK(ctx, d_codes.alloc((size_t)want * (size_t)n));
+        HIPCHK(ctx, d_bed.alloc((size_t)want * (size_t)rb));
+        lines_cap = want;
+        return EAGLE_OK;
+    };
+    // the counters of the window that used buffer b: every kept line has n fields, or the call fails with the first that has not
+    auto check = [&](int b) -> int {
+        VcfPending& p = pend[b];
+        if (!p.live) return EAGLE_OK;
+        p.live = false;
+        const int32_t* c = (const int32_t*)((const char*)pin_tab[b].p + 16 * (size_t)lines_cap);
+        for (size_t i = 0; i < p.line_no.size(); i++, c += 4) {
+            if (c[0] != n)
+                return failf(ctx, EAGLE_ERR_FORMAT, "%s line %ld: %d sample fields, the header names %ld (section 1b-vcf)", vcf_path, p.line_no[i],
+                             (int)c[0], n);
+            cn.missing += c[1];
+            cn.haploid += c[2];
+            cn.malformed += c[3];
+        }
+        return EAGLE_OK;
+    };
+    // everything enqueued is done, both windows' counters are checked (the older first) and the rows held back are on disk
+    auto settle = [&]() -> int {
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        const int first = (pend[0].live && pend[1].live && pend[1].window < pend[0].window) ? 1 : 0;
+        int src = check(first);
+        if (!src) src = check(1 - first);
+        if (!src && have_header) src = out.flush(ring);
+        return src;
+    };
+    // a host-side error: what lies in front of it in the file is judged first
+    auto fail_at = [&](int code, const char* text, const std::vector<long>& here_no, const int64_t* here_tab, const char* txt) -> int {
+        int src = settle();
+        if (src) { (void)hipStreamSynchronize(ctx->stream); return src; }
+        for (size_t i = 0; i < here_no.size(); i++) {
+            const long found = vcf_count_fields(txt + here_tab[2 * i], txt + here_tab[2 * i + 1]);
+            if (found != n)
+                return failf(ctx, EAGLE_ERR_FORMAT, "%s line %ld: %ld sample fields, the header names %ld (section 1b-vcf)", vcf_path, here_no[i],
+                             found, n);
+        }
+        return failf(ctx, code, "%s", text);
+    };
+
+    std::vector<long> here_no;
+    std::vector<std::string> names;
+    for (long long pos = 0; pos < fsize;) {
+        long want = (long)std::min<long long>(cap, fsize - pos);
+        rc = ring.acquire();
+        if (!rc) rc = check((int)ring.last());   // the window that used this buffer is through
+        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+        const int b = ring.last();
+        here_no.clear();
+        bool ok = ring.fill((off_t)pos, (size_t)want, 0);
+        size_t wbytes = 0;
+        if (ok) wbytes = pos + want == fsize ? (size_t)want : vcf_whole_lines(ring.pinned(b), (size_t)want);
+        if (ok && wbytes == 0) {   // the line is longer than the window: the window grows to it
+            const long long le = vcf_line_end(ring.fd, pos + want, fsize);
+            ok = le >= 0;
+            if (ok && (le - pos > VCF_MAX_WINDOW || !vcf_line_fits((long)(le - pos), mem))) {
+                snprintf(msg, sizeof msg, "vcf_to_bed: line %ld of %s holds %lld bytes and does not fit max_memory_in_Gbytes (section 1b-vcf, rule 6)",
+                         line_no + 1, vcf_path, le - pos);
+                return fail_at(EAGLE_ERR_ARG, msg, here_no, nullptr, nullptr);
+            }
+            if (ok) {
+                want = (long)(le - pos);
+                rc = settle();
+                if (!rc) rc = eagle_stage_ensure(ctx, text_room(want));
+                if (!rc && have_header) rc = size_lines(want);
+                if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+                ok = ring.fill((off_t)pos, (size_t)want, 0);
+                wbytes = (size_t)want;
+            }
+        }
+        if (!ok) {
+            snprintf(msg, sizeof msg, "%s: could not read the bytes from %lld", vcf_path, pos);
+            return fail_at(EAGLE_ERR_FORMAT, msg, here_no, nullptr, nullptr);
+        }
+        const char* txt = ring.pinned(b);
+        const uint8_t* d_text;
+        rc = ring.upload(0, wbytes, &d_text);   // on its way while the host reads the same bytes
+        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+
+        int64_t* tab = (int64_t*)pin_tab[b].p;   // NULL until the header is read: no line is kept before
+        bimbuf.clear();
+        size_t p = 0, lb, le, next;
+        for (; vcf_next_line(txt, wbytes, p, true, &lb, &le, &next); p = next) {
+            line_no++;
+            if (le == lb) continue;
+            if (le - lb >= 2 && txt[lb] == '#' && txt[lb + 1] == '#') continue;
+            if (!have_header) {
+                std::vector<VcfSpan> spans;
+                if (const char* what = vcf_header_error(txt + lb, txt + le, spans)) {
+                    snprintf(msg, sizeof msg, "%s line %ld: %s (section 1b-vcf)", vcf_path, line_no, what);
+                    return fail_at(EAGLE_ERR_FORMAT, msg, here_no, tab, txt);
+                }
+                n = (long)spans.size();
+                rb = bed_row_bytes(n);
+                for (const VcfSpan& s : spans) names.emplace_back(s.p, (size_t)s.len);
+                FILE* ffam = fopen(files.fam.c_str(), "w");
+                if (ffam) files.made_fam = true;
+                bool wrote = ffam != nullptr;
+                for (size_t i = 0; wrote && i < names.size(); i++) wrote = fprintf(ffam, "%s %s 0 0 0 -9\n", names[i].c_str(), names[i].c_str()) > 0;
+                if (ffam && fclose(ffam) != 0) wrote = false;
+                if (!wrote) { (void)hipStreamSynchronize(ctx->stream); return failf(ctx, EAGLE_ERR_OPEN, "ERROR: Could not open  %s", files.fam.c_str()); }
+                files.fbim = fopen(files.bim.c_str(), "w");
+                if (!files.fbim) { (void)hipStreamSynchronize(ctx->stream); return failf(ctx, EAGLE_ERR_OPEN, "ERROR: Could not open  %s", files.bim.c_str()); }
+                rc = out.open(ctx, files.bed.c_str(), n, 0);
+                files.made_bed = out.out.fd >= 0;
+                if (!rc) {   // nothing but this window's upload is in flight, and it does not touch what size_lines makes
+                    rc = size_lines((long)std::max<size_t>(wbytes, (size_t)cap));
+                    tab = (int64_t*)pin_tab[b].p;
+                }
+                if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+                have_header = true;
+                continue;
+            }
+            cn.lines++;
+            VcfSpan f[9];
+            const char* rest;
+            if (vcf_split_tabs(txt + lb, txt + le, f, 9, &rest) < 9) {
+                snprintf(msg, sizeof msg, "%s line %ld: a data line with fewer than nine fixed fields (section 1b-vcf)", vcf_path, line_no);
+                return fail_at(EAGLE_ERR_FORMAT, msg, here_no, tab, txt);
+            }
+            switch (vcf_verdict(f, flags)) {
+                case VCF_MULTIALLELIC: cn.multiallelic++; continue;
+                case VCF_NO_ALT: cn.no_alt++; continue;
+                case VCF_NO_GT: cn.no_gt++; continue;
+                case VCF_NOT_SNP: cn.not_snp++; continue;
+                case VCF_FILTERED: cn.filtered++; continue;
+                default: break;
+            }
+            // a line too short for n fields is judged here, so that the kept lines of a window always fit lines_cap
+            const long found = !rest ? 0 : ((txt + le) - rest < 2 * n - 1 ? vcf_count_fields(rest, txt + le) : n);
+            if (found != n || (long)here_no.size() >= lines_cap) {
+                snprintf(msg, sizeof msg, "%s line %ld: %ld sample fields, the header names %ld (section 1b-vcf)", vcf_path, line_no, found, n);
+                return fail_at(EAGLE_ERR_FORMAT, msg, here_no, tab, txt);
+            }
+            tab[2 * here_no.size()] = (int64_t)(rest - txt);
+            tab[2 * here_no.size() + 1] = (int64_t)le;
+            here_no.push_back(line_no);
+            const VcfSpan &a1 = a2_alt ? f[3] : f[4], &a2 = a2_alt ? f[4] : f[3];
+            bimbuf.append(f[0].p, (size_t)f[0].len).push_back('\t');
+            if (vcf_span_is(f[2], ".")) {
+                bimbuf.append(f[0].p, (size_t)f[0].len).push_back(':');
+                bimbuf.append(f[1].p, (size_t)f[1].len);
+            } else {
+                bimbuf.append(f[2].p, (size_t)f[2].len);
+            }
+            bimbuf.append("\t0\t").append(f[1].p, (size_t)f[1].len).push_back('\t');
+            bimbuf.append(a1.p, (size_t)a1.len).push_back('\t');
+            bimbuf.append(a2.p, (size_t)a2.len).push_back('\n');
+        }
+        pos += (long long)wbytes;
+        const long kept_here = (long)here_no.size();
+        if (!bimbuf.empty() && fwrite(bimbuf.data(), 1, bimbuf.size(), files.fbim) != bimbuf.size()) {
+            (void)hipStreamSynchronize(ctx->stream);
+            return failf(ctx, EAGLE_ERR_OPEN, "ERROR: could not write %s", files.bim.c_str());
+        }
+        if (kept_here > 0) {
+            int32_t* h_cnt = (int32_t*)((char*)pin_tab[b].p + 16 * (size_t)lines_cap);
+            const hipError_t e1 = hipMemcpyAsync(d_tab.p, tab, 16 * (size_t)kept_here, hipMemcpyHostToDevice, ctx->stream);
+            if (e1 != hipSuccess) rc = eagle_fail_hip(ctx, e1, "hipMemcpyAsync");
+            if (!rc) rc = eagle_dev_vcf_fields(ctx, d_text, d_tab.as<int64_t>(), kept_here, n, a2_alt, d_codes.as<uint8_t>(), d_cnt.as<int32_t>(), ctx->stream);
+            if (!rc) rc = eagle_dev_vcf_pack(ctx, d_codes.as<uint8_t>(), kept_here, n, d_bed.as<uint8_t>(), ctx->stream);
+            if (!rc) {
+                const hipError_t e2 = hipMemcpyAsync(h_cnt, d_cnt.p, 16 * (size_t)kept_here, hipMemcpyDeviceToHost, ctx->stream);
+                if (e2 != hipSuccess) rc = eagle_fail_hip(ctx, e2, "hipMemcpyAsync");
+            }
+            if (!rc) rc = out.push(ring, d_bed.p, cn.kept, kept_here);   // releases the buffer; window k - 1's rows go to disk meanwhile
+            pend[b].live = true;
+            pend[b].window = window;
+            pend[b].line_no = here_no;
+            cn.kept += kept_here;
+        } else {   // nothing for the device: the buffer is released behind its upload, and rows held in the other one go to disk
+            rc = ring.release();
+            if (!rc && have_header) rc = out.flush(ring);
+        }
+        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+        window++;
+    }
+    here_no.clear();
+    if (!have_header) {
+        snprintf(msg, sizeof msg, "%s line %ld: no #CHROM line (section 1b-vcf)", vcf_path, line_no + 1);
+        return fail_at(EAGLE_ERR_FORMAT, msg, here_no, nullptr, nullptr);
+    }
+    rc = settle();
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    if (cn.kept == 0) return failf(ctx, EAGLE_ERR_FORMAT, "%s: no data line is kept, so there is no fileset to write (section 1b-vcf)", vcf_path);
+    rc = out.finish(ring);
+    if (rc) return rc;
+    if (!files.keep()) return failf(ctx, EAGLE_ERR_OPEN, "ERROR: could not write %s", files.bim.c_str());
+    dims_out[0] = n;
+    dims_out[1] = cn.kept;
+    *counts_out = cn;
     return EAGLE_OK;
 }
 

@@ -241,9 +241,123 @@ def _read_marker_bed(filename, availmemGb, quiet, outdir, message, device):
     return {"asciifileM": asciiM, "asciifileMt": asciiMt, "dim_of_ascii_M": dims}
 
 
+# ---- VCF ingestion (include/eagle_hip.h section 1b-vcf): the restatement in plain Python and numpy, and the interface ----
+_VCF_COUNT_FIELDS = ("lines", "kept", "multiallelic", "no_alt", "no_gt", "not_snp", "filtered", "missing", "haploid", "malformed")
+
+
+def _vcf_gt(field):
+    """One sample field -> (class, haploid, malformed): class 0 homozygous REF, 1 het, 2 homozygous ALT, -1 missing (rule 4)."""
+    tokens = field.split(b":", 1)[0].replace(b"|", b"/").split(b"/")
+    if all(t in (b"0", b"1") for t in tokens):
+        if len(tokens) == 1:
+            return (2 if tokens[0] == b"1" else 0), 1, 0
+        if len(tokens) == 2:
+            return (tokens[0] == b"1") + (tokens[1] == b"1"), 0, 0
+    return -1, 0, int(any(t != b"." for t in tokens))
+
+
+def vcf_to_bed_host(vcf_bytes, a2="ref", snps_only=False, pass_only=False):
+    """eagle_vcf_to_bed restated in plain Python and numpy from the rule of include/eagle_hip.h section 1b-vcf: the bytes of a plain-text
+    VCF file -> (bed_bytes, bim_text, fam_text, dims, counts), what the call leaves in <prefix>.bed / .bim / .fam, dims = [n, kept
+    markers] and the counts as a dict.  ValueError, with the 1-based line number where the rule gives one, where the call fails.  Host
+    only, one Python step per sample field: for tests and small files."""
+    if a2 not in ("ref", "alt"):
+        raise ValueError('vcf_to_bed_host: a2 must be "ref" or "alt"')
+    lines = bytes(vcf_bytes).split(b"\n")
+    if lines[-1] == b"":
+        lines.pop()                                            # the bytes behind the last '\n' are a line only when there are some
+    names, rows, bim = None, [], []
+    counts = dict.fromkeys(_VCF_COUNT_FIELDS, 0)
+    # the .bed code of a class: by default A1 = ALT, so homozygous REF is hom A2 = 3; a2="alt" turns the two homozygotes round
+    code_of = {0: 0 if a2 == "alt" else 3, 1: 2, 2: 3 if a2 == "alt" else 0, -1: 1}
+    seen = {}
+    for ln, line in enumerate(lines, 1):
+        if line.endswith(b"\r"):
+            line = line[:-1]
+        if not line or line.startswith(b"##"):
+            continue
+        col = line.split(b"\t")
+        if names is None:
+            if not line.startswith(b"#CHROM"):
+                raise ValueError("line %d: no #CHROM line in front of the data" % ln)
+            if len(col) < 10:
+                raise ValueError("line %d: the #CHROM line has fewer than 10 columns" % ln)
+            names = col[9:]
+            if any(s == b"" or b" " in s for s in names):
+                raise ValueError("line %d: a sample name that is empty or contains a blank" % ln)
+            continue
+        counts["lines"] += 1
+        if len(col) < 9:
+            raise ValueError("line %d: a data line with fewer than nine fixed fields" % ln)
+        chrom, pos, vid, ref, alt, _, flt, _, fmt = col[:9]
+        if b"," in alt:
+            counts["multiallelic"] += 1
+        elif alt == b".":
+            counts["no_alt"] += 1
+        elif not (fmt == b"GT" or fmt.startswith(b"GT:")):
+            counts["no_gt"] += 1
+        elif snps_only and not (ref.upper() in (b"A", b"C", b"G", b"T") and alt.upper() in (b"A", b"C", b"G", b"T")):
+            counts["not_snp"] += 1
+        elif pass_only and flt not in (b"PASS", b"."):
+            counts["filtered"] += 1
+        else:
+            fields = col[9:]
+            if len(fields) != len(names):
+                raise ValueError("line %d: %d sample fields, the header names %d" % (ln, len(fields), len(names)))
+            row = np.empty(len(names), dtype=np.uint8)
+            for i, f in enumerate(fields):
+                g = seen.get(f)
+                if g is None:
+                    g = seen[f] = _vcf_gt(f)
+                row[i] = code_of[g[0]]
+                counts["missing"] += g[0] < 0
+                counts["haploid"] += g[1]
+                counts["malformed"] += g[2]
+            rows.append(row)
+            a1, a2_allele = (ref, alt) if a2 == "alt" else (alt, ref)
+            bim.append(b"\t".join((chrom, chrom + b":" + pos if vid == b"." else vid, b"0", pos, a1, a2_allele)))
+            counts["kept"] += 1
+    if names is None:
+        raise ValueError("line %d: no #CHROM line" % (len(lines) + 1))
+    if not rows:
+        raise ValueError("no data line is kept, so there is no fileset to write")
+    bed = b"\x6c\x1b\x01" + pack_bed_codes(np.stack(rows)).tobytes()
+    bim_text = b"".join(b + b"\n" for b in bim).decode("latin-1")
+    fam_text = b"".join(s + b" " + s + b" 0 0 0 -9\n" for s in names).decode("latin-1")
+    return bed, bim_text, fam_text, [len(names), len(rows)], {k: int(v) for k, v in counts.items()}
+
+
+def VcfToBed(vcf, out_prefix, a2="ref", snps_only=False, pass_only=False, availmemGb=8, chunk_bytes=0, device=0):
+    """A VCF 4.x file as the PLINK binary fileset out_prefix + ".bed" / ".bim" / ".fam" (rcpp_api.vcf_to_bed: the GT fields are decoded
+    on the device, a missing call stays missing) -> {"bed", "bim", "fam", "dims", "counts", "samples"}.  A path that ends in .gz or
+    .bgz is first inflated with the standard library's gzip (a bgzip file is a multi-member gzip file) into a scratch file beside the
+    output, removed afterwards.  a2="ref" (default): A1 = ALT, A2 = REF, the PLINK program's import convention as documented;
+    a2="alt": the library's '2' allele counts ALT copies.  Agreement with PLINK or bcftools is neither claimed nor tested."""
+    import gzip
+    import shutil
+    vcf, prefix = os.fspath(vcf), os.fspath(out_prefix)
+    if not os.path.exists(vcf):
+        raise ValueError("VcfToBed: the file %s could not be found" % vcf)
+    os.makedirs(os.path.dirname(os.path.abspath(prefix)), exist_ok=True)
+    scratch = None
+    try:
+        if vcf.lower().endswith((".gz", ".bgz")):
+            scratch = prefix + ".inflated.vcf"
+            with gzip.open(vcf, "rb") as src, open(scratch, "wb") as dst:
+                shutil.copyfileobj(src, dst, 1 << 24)
+        res = rcpp_api.vcf_to_bed(scratch or vcf, prefix, a2=a2, snps_only=snps_only, pass_only=pass_only, availmemGb=availmemGb,
+                                  chunk_bytes=chunk_bytes, device=device)
+    finally:
+        if scratch is not None and os.path.exists(scratch):
+            os.remove(scratch)
+    with open(res["fam"]) as f:
+        res["samples"] = [ln.split()[0] for ln in f if ln.strip()]
+    return res
+
+
 def ReadMarker(filename=None, type="text", missing=None, AA=None, AB=None, BB=None, availmemGb=16, quiet=True, outdir=None,
                message=None, device=0, maf=None, max_missing=None, drop_monomorphic=False, impute=None, impute_local=None,
-               impute_ld_from="panel"):
+               impute_ld_from="panel", vcf_a2="ref", vcf_snps_only=False, vcf_pass_only=False):
     """E/R/ReadMarker.R:194-318 -> geno dict {asciifileM, asciifileMt, dim_of_ascii_M} or None (the R list / NULL).
     type="PLINKbed" (not in the reference): `filename` is the .bed file of a PLINK binary fileset or its prefix; n and L are the
     line counts of the .fam and .bim beside it, the genotypes go through rcpp_api.create_ascii_from_bed.
@@ -257,8 +371,31 @@ def ReadMarker(filename=None, type="text", missing=None, AA=None, AB=None, BB=No
     filtered, on the statistics of the original file's called genotypes.
     impute_local=l (with impute=k; default None, and then nothing here differs from the lines above): ImputeBed(k=k, local=l), LD-kNNi
     with the chromosomes of the fileset's .bim file.  impute_ld_from="bed" (default "panel": nothing differs) passes ld_from="bed": the
-    partners in local LD come from the .bed file's own pairwise-complete r2."""
+    partners in local LD come from the .bed file's own pairwise-complete r2.
+    type="VCF" (not in the reference): `filename` is a VCF 4.x file, plain or .gz / .bgz.  VcfToBed converts it into
+    <outdir>/vcf/panel.bed / .bim / .fam (vcf_a2, vcf_snps_only, vcf_pass_only are its a2, snps_only, pass_only), and that prefix goes
+    through the type="PLINKbed" route above with the caller's maf, max_missing, drop_monomorphic, impute, impute_local and
+    impute_ld_from: everything downstream is the .bed route's own code.  The dict returned gains "bed" (the prefix to pass as bed= to
+    MarkerStats, Relatedness, LDPrune, ...: the missing calls of the VCF are still missing there), "samples" and "vcf_counts"."""
     say = message or (lambda s: None)
+    if type == "VCF":
+        if filename is None or not os.path.exists(filename):
+            say(" The VCF file %s could not be found. " % filename)
+            say(" ReadMarker has terminated with errors ")
+            return None
+        outdir = outdir or os.path.dirname(os.path.abspath(filename))
+        say(" Converting the VCF file into a PLINK binary fileset ... ")
+        res = VcfToBed(filename, os.path.join(outdir, "vcf", "panel"), a2=vcf_a2, snps_only=vcf_snps_only, pass_only=vcf_pass_only,
+                       availmemGb=availmemGb, device=device)
+        prefix = res["bed"][:-4]
+        geno = ReadMarker(prefix, type="PLINKbed", availmemGb=availmemGb, quiet=quiet, outdir=outdir, message=message, device=device, maf=maf,
+                          max_missing=max_missing, drop_monomorphic=drop_monomorphic, impute=impute, impute_local=impute_local,
+                          impute_ld_from=impute_ld_from)
+        if geno is None:
+            return None
+        geno = dict(geno)
+        geno.update(bed=prefix, samples=res["samples"], vcf_counts=res["counts"])
+        return geno
     if impute is not None and type != "PLINKbed":
         say(' impute needs type = "PLINKbed": only a .bed file still knows which genotypes are missing. \n')
         say(" ReadMarker has terminated with errors")

@@ -690,6 +690,32 @@ def bed_marker_counts(bed_path, dims, max_memory_in_Gbytes=8.0, device=0):
     return out
 
 
+VCF_A2_ALT, VCF_SNPS_ONLY, VCF_PASS_ONLY = 1, 2, 4      # the flags of include/eagle_hip.h section 1b-vcf
+VCF_COUNT_FIELDS = tuple(f for f, _ in _lib.VcfCounts._fields_)
+
+
+def vcf_flags(a2="ref", snps_only=False, pass_only=False):
+    """The flag word of eagle_vcf_to_bed: a2 = "ref" (A1 = ALT, A2 = REF, the default) or "alt" (A2 = ALT)."""
+    if a2 not in ("ref", "alt"):
+        raise ValueError('vcf_to_bed: a2 must be "ref" or "alt"')
+    return (VCF_A2_ALT if a2 == "alt" else 0) | (VCF_SNPS_ONLY if snps_only else 0) | (VCF_PASS_ONLY if pass_only else 0)
+
+
+def vcf_to_bed(vcf, out_prefix, a2="ref", snps_only=False, pass_only=False, availmemGb=8, chunk_bytes=0, device=0):
+    """eagle_vcf_to_bed -> {"bed", "bim", "fam", "dims", "counts"}: the plain-text VCF file `vcf` as the PLINK binary fileset
+    out_prefix + ".bed" / ".bim" / ".fam", its GT fields decoded on the device.  dims = [n samples, kept markers]; counts = the
+    eagle_vcf_counts of the call as a dict.  chunk_bytes caps the text staged per window (0: from availmemGb); the files do not depend
+    on it.  The arguments are checked by the library before it needs a device: EagleError(-3, ...) then, without opening one."""
+    L = _lib.load()
+    flags = vcf_flags(a2, snps_only, pass_only)
+    dims, counts = (C.c_long * 2)(), _lib.VcfCounts()
+    prefix = os.fspath(out_prefix)
+    _args_first(L.eagle_vcf_to_bed, device, (os.fsencode(vcf), os.fsencode(prefix), flags, float(availmemGb), int(chunk_bytes), dims,
+                                             C.byref(counts)))
+    return {"bed": prefix + ".bed", "bim": prefix + ".bim", "fam": prefix + ".fam", "dims": [int(dims[0]), int(dims[1])],
+            "counts": {f: int(getattr(counts, f)) for f in VCF_COUNT_FIELDS}}
+
+
 def filter_markers(fnameM, fnameMt, dims, keep, outM, outMt, max_memory_in_Gbytes=8.0, device=0):
     """eagle_filter_markers -> newdims [n, nkeep]: outM / outMt, their sidecars and resident images for the markers `keep` (0-based,
     strictly increasing) of the panel (fnameM, fnameMt; dims = (n, L) of M).  The keep-list and the paths are checked by the library

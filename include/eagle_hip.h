@@ -259,6 +259,58 @@ int eagle_create_ascii_from_bed(eagle_ctx* ctx, const char* bed_path, const char
                                 double max_memory_in_Gbytes, const long dims[2], int quiet, long* n_missing_out);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1b-vcf. VCF ingestion (no counterpart in the reference): the GT fields of a VCF 4.x file decoded on the device into a PLINK binary
+ *     fileset <prefix>.bed / .bim / .fam, which eagle_create_ascii_from_bed and every eagle_bed_* entry point then read -- with the
+ *     missing calls of the VCF still missing (code 01), which the text and .ped routes cannot keep.  Agreement with the PLINK program or
+ *     with bcftools is neither claimed nor tested: neither is available where this library is built.  Sex chromosomes, dosages (DS / GP),
+ *     phase and the splitting of multi-allelic records are out of scope.  Single device: a multi-device context works on its first device.
+ *
+ *     1. Input.  Plain text (compressed files are the caller's to inflate; r_api.VcfToBed does it).  Lines end at '\n'; a '\r' before
+ *        the '\n' is dropped; an unterminated last line is a line; empty lines are skipped anywhere.  Line numbers are 1-based and count
+ *        every line of the file, skipped ones included.
+ *     2. Header.  Lines that start with "##" are skipped.  The first other line must start with "#CHROM"; its tab-separated columns
+ *        from the 10th on are the n sample names.  EAGLE_ERR_FORMAT with the line number: no #CHROM line (a data line before the
+ *        header, or a file that ends without one), fewer than 10 columns, a sample name that is empty or contains a blank.
+ *     3. Which data lines are kept: decided on the host from the nine fixed fields alone (CHROM POS ID REF ALT QUAL FILTER INFO
+ *        FORMAT; a data line with fewer than nine is EAGLE_ERR_FORMAT).  A line is dropped and counted under the FIRST reason that holds:
+ *        ALT contains a ',' (multiallelic); ALT is "." (no_alt); FORMAT is not "GT" and does not begin with "GT:" (no_gt); with
+ *        EAGLE_VCF_SNPS_ONLY, REF or ALT is not one of A C G T, case-insensitive (not_snp); with EAGLE_VCF_PASS_ONLY, FILTER is
+ *        neither "PASS" nor "." (filtered).  lines = the data lines seen = kept + the five drop counts.
+ *        A kept line must have exactly n sample fields; otherwise EAGLE_ERR_FORMAT, naming the line and the count found.  The sample
+ *        fields of a dropped line are never looked at.
+ *     4. One sample field: the bytes up to the next tab or the line end.  GT is the field up to its first ':'; bytes after the first
+ *        ':' are never looked at.  GT is cut at every '/' or '|' into k tokens (an empty GT is one empty token):
+ *          k = 1, token "0" -> homozygous REF, counted haploid;   k = 1, token "1" -> homozygous ALT, counted haploid;
+ *          k = 2, both tokens in {"0", "1"}: equal -> homozygous REF or homozygous ALT, different -> het;
+ *          anything else -> missing; a missing GT whose tokens are not all "." is also counted malformed ("2/1", "10/1", "0/1/1",
+ *          an empty field, an empty token).
+ *     5. Output.  <prefix>.bed is SNP-major with the codes of 1b: 00 hom A1, 10 het, 01 missing, 11 hom A2, individual 4b+q at bits 2q
+ *        of byte b, the unused bit pairs of a row's last byte zero.  By default A1 = ALT and A2 = REF (the PLINK program's import
+ *        convention AS DOCUMENTED); EAGLE_VCF_A2_ALT makes A2 = ALT, so that the '2' allele of this library counts ALT copies.
+ *        <prefix>.bim: one line per kept marker, CHROM \t ID \t 0 \t POS \t A1 \t A2, ID = CHROM:POS where the file has ".".
+ *        <prefix>.fam: one line per sample, "name name 0 0 0 -9".  A failed call leaves none of the three files.
+ *     6. Windows.  chunk_bytes caps the text staged per window (0: the staging rule of the eagle_bed_* calls, 64 MiB or a quarter of
+ *        max_memory_in_Gbytes if less).  A window holds whole lines only and grows to the longest line when a line is longer than
+ *        chunk_bytes; a line longer than a quarter of max_memory_in_Gbytes (or than 2^30 bytes) is EAGLE_ERR_ARG.  The host finds the
+ *        newlines of a staged window, parses the fixed fields and sends the kept lines' table (first sample field, line end); the
+ *        device finds the tabs, gives every field its ordinal, decodes GT, packs four codes a byte and counts per line (k_vcf_fields,
+ *        k_vcf_pack).  The pread of window k runs under the device work of window k - 1 (the staging ring of the eagle_bed_* calls) and
+ *        the .bed rows go out write-behind.  The files do not depend on chunk_bytes: the same file gives the same bytes at every value.
+ *     7. Argument errors are decided before the context is used (ctx == NULL: the text is in eagle_open_error()): a NULL pointer,
+ *        unknown flag bits, chunk_bytes < 0, an empty prefix.  dims_out = (n, kept markers); a file whose lines are all dropped is
+ *        EAGLE_ERR_FORMAT (a fileset of no marker is none).
+ * ------------------------------------------------------------------------------------------- */
+#define EAGLE_VCF_A2_ALT 1
+#define EAGLE_VCF_SNPS_ONLY 2
+#define EAGLE_VCF_PASS_ONLY 4
+typedef struct eagle_vcf_counts {
+    long lines, kept, multiallelic, no_alt, no_gt, not_snp, filtered, missing, haploid, malformed;
+} eagle_vcf_counts;
+
+int eagle_vcf_to_bed(eagle_ctx* ctx, const char* vcf_path, const char* out_prefix, int flags, double max_memory_in_Gbytes, long chunk_bytes,
+                     long dims_out[2], eagle_vcf_counts* counts_out);
+
+/* ---------------------------------------------------------------------------------------------
  * 1b'. Marker QC (no counterpart in the reference, which leaves filtering to other tools): per-marker genotype counts from the
  *     genotypes this library already holds, and panels restricted to a list of markers.  Integer results only; allele
  *     frequencies, call rates and the filter rules are the caller's arithmetic on the counts (r_api.MarkerStats / FilterMarkers).
