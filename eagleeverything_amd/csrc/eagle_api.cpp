@@ -77,7 +77,7 @@ static void arena_prefetch(eagle_ctx* ctx, size_t total, bool only_if_roomy = fa
     const int device = ctx->device;
     pf->th = std::thread([pf, device] {
         pf->e = hipSetDevice(device);
-        if (pf->e == hipSuccess) pf->e = hipMalloc(&pf->p, pf->bytes);
+        if (pf->e == hipSuccess) pf->e = dev_alloc(&pf->p, pf->bytes);
     });
     ctx->arena_prefetch = pf;
 }
@@ -101,19 +101,21 @@ static int arena_reserve(eagle_ctx* ctx, size_t total) {
     if (total <= ctx->arena_cap) return EAGLE_OK;
     if (ctx->arena) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(ctx->arena); ctx->arena = nullptr; ctx->arena_cap = 0; }
     ctx->arena_gen++;
-    hipError_t e = hipMalloc(&ctx->arena, total);
+    hipError_t e = dev_alloc(&ctx->arena, total);
     if (e != hipSuccess && eagle_drop_f4_images(ctx) > 0) {   // the fp4 MM^T operand images kept with resident files are not in any budget
         (void)hipGetLastError();
-        e = hipMalloc(&ctx->arena, total);
+        e = dev_alloc(&ctx->arena, total);
     }
     if (e != hipSuccess) return eagle_fail_hip(ctx, e, "arena hipMalloc");
     ctx->arena_cap = total;
     return EAGLE_OK;
 }
 static size_t arena_round(size_t b) { return (b + 255) / 256 * 256; }
-template <class T> static T* arena_take(eagle_ctx* ctx, size_t bytes) {
+// (`kept`: the block holds what an earlier call left for this one -- the cached S in its slot -- and is not scratch: DESIGN 3a)
+template <class T> static T* arena_take(eagle_ctx* ctx, size_t bytes, bool kept = false) {
     T* p = (T*)((char*)ctx->arena + ctx->arena_off);
     ctx->arena_off += arena_round(bytes);
+    if (!kept) (void)dev_scratch_handout(p, bytes);
     return p;
 }
 static bool timing_on() { static int v = -1; if (v < 0) v = getenv("EAGLE_HIP_TIMING") ? 1 : 0; return v == 1; }
@@ -152,7 +154,7 @@ extern "C" eagle_ctx* eagle_open(int device) {
     snprintf(ctx->arch, sizeof ctx->arch, "%s", prop.gcnArchName);
     ctx->cu_count = prop.multiProcessorCount;
     ctx->hbm_bytes = (int64_t)prop.totalGlobalMem;
-    if ((e = hipMalloc(&ctx->d_scratch, EAGLE_SCR_BYTES)) != hipSuccess) {
+    if ((e = dev_alloc(&ctx->d_scratch, EAGLE_SCR_BYTES)) != hipSuccess) {
         snprintf(g_open_err, sizeof g_open_err, "hipMalloc: %s", hipGetErrorString(e));
         delete ctx;
         return nullptr;
@@ -411,9 +413,13 @@ extern "C" void eagle_close(eagle_ctx* ctx) {
 
 extern "C" void* eagle_ctx_scratch(eagle_ctx* ctx) { return ctx->d_scratch; }
 extern "C" void* eagle_ctx_f4_buffer(eagle_ctx* ctx, size_t bytes) {
-    if (bytes <= ctx->f4_cap) return ctx->f4_buf;
+    if (bytes <= ctx->f4_cap) {
+        const hipError_t eh = dev_scratch_handout(ctx->f4_buf, bytes);
+        if (eh != hipSuccess) { (void)eagle_fail_hip(ctx, eh, "fp4 image hand-out"); return nullptr; }
+        return ctx->f4_buf;
+    }
     if (ctx->f4_buf) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(ctx->f4_buf); ctx->f4_buf = nullptr; ctx->f4_cap = 0; }
-    hipError_t e = hipMalloc(&ctx->f4_buf, bytes);
+    hipError_t e = dev_alloc(&ctx->f4_buf, bytes);
     if (e != hipSuccess) { (void)eagle_fail_hip(ctx, e, "fp4 image hipMalloc"); ctx->f4_buf = nullptr; return nullptr; }
     ctx->f4_cap = bytes;
     return ctx->f4_buf;
@@ -705,9 +711,9 @@ extern "C" int eagle_read_block(eagle_ctx* ctx, const char* asciifname, long sta
 
 // grow-only ctx-owned device buffer
 template <class T> static int ensure_buf(eagle_ctx* ctx, T** buf, size_t* cap, size_t bytes, const char* what) {
-    if (bytes <= *cap) return EAGLE_OK;
+    if (bytes <= *cap) { HIPCHK(ctx, dev_scratch_handout(*buf, bytes)); return EAGLE_OK; }
     if (*buf) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(*buf); *buf = nullptr; *cap = 0; }
-    hipError_t e = hipMalloc((void**)buf, bytes);
+    hipError_t e = dev_alloc(buf, bytes);
     if (e != hipSuccess) return eagle_fail_hip(ctx, e, what);
     *cap = bytes;
     return EAGLE_OK;
@@ -735,7 +741,7 @@ static int mmt_range(eagle_ctx* ctx, const char* path, long n, long L, long c0, 
         // E/R/summary_am.R:140) is the SYRK + finish only
         const long Lwp = eagle_pad(Lw_all);
         if (!g->dev_f4) {
-            hipError_t e = hipMalloc(&g->dev_f4, (size_t)np * (size_t)(Lwp / 2));
+            hipError_t e = dev_alloc(&g->dev_f4, (size_t)np * (size_t)(Lwp / 2));
             if (e != hipSuccess) { g->dev_f4 = nullptr; (void)hipGetLastError(); }
             else if ((rc = eagle_dev_pack_fp4(ctx, g->dev, np, Lwp, g->ld, g->dev_f4, ctx->stream))) { (void)hipFree(g->dev_f4); g->dev_f4 = nullptr; return rc; }
         }
@@ -806,7 +812,7 @@ int eagle_ibs_counts(eagle_ctx* ctx, const char* path, long n, long L, double me
     if (rc < 0) return rc;
     if (rc == EAGLE_OK) {
         if (!g->dev_f4) {   // as mmt_range makes it: a later calculateMMt on the file finds the image it would have made itself
-            hipError_t e = hipMalloc(&g->dev_f4, (size_t)np * (size_t)(Lp / 2));
+            hipError_t e = dev_alloc(&g->dev_f4, (size_t)np * (size_t)(Lp / 2));
             if (e != hipSuccess) { g->dev_f4 = nullptr; (void)hipGetLastError(); }
             else if ((rc = eagle_dev_pack_fp4(ctx, g->dev, np, Lp, g->ld, g->dev_f4, ctx->stream))) { (void)hipFree(g->dev_f4); g->dev_f4 = nullptr; return rc; }
         }
@@ -1033,10 +1039,10 @@ extern "C" int eagle_calculateMMt(eagle_ctx* ctx, const char* f_name_ascii, doub
     if (ctx->mmt_n != n) {
         if (ctx->d_mmt) { (void)hipFree(ctx->d_mmt); ctx->d_mmt = nullptr; }
         ctx->mmt_n = 0;
-        HIPCHK(ctx, hipMalloc((void**)&ctx->d_mmt, sizeof(double) * (size_t)n * n));
+        HIPCHK(ctx, dev_alloc(&ctx->d_mmt, sizeof(double) * (size_t)n * n));
         ctx->mmt_n = n;
     }
-    if (!ctx->d_mmt_max) HIPCHK(ctx, hipMalloc((void**)&ctx->d_mmt_max, sizeof(double)));
+    if (!ctx->d_mmt_max) HIPCHK(ctx, dev_alloc(&ctx->d_mmt_max, sizeof(double)));
     rc = eagle_dev_mmt_finish(ctx, ctx->d_c32, n, np, ctx->d_mmt, n, ctx->d_mmt_max, ctx->stream);
     if (rc) return rc;
     // AM() calls this once, then works on the host for seconds (eigen, REML) before its first find_qtl: the arena of that scan is
@@ -1145,7 +1151,7 @@ int SCache::acquire(eagle_ctx* ctx, const SCall& call, const SPolicy& pol, const
         if (d_S) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(d_S); d_S = nullptr; }
         if (d_scr) { (void)hipFree(d_scr); d_scr = nullptr; }
         dev_n = dev_np = 0;
-        if (hipMalloc((void**)&d_S, sq) == hipSuccess && hipMalloc((void**)&d_scr, sq) == hipSuccess) dev_np = np;
+        if (dev_alloc(&d_S, sq) == hipSuccess && dev_alloc(&d_scr, sq) == hipSuccess) dev_np = np;
         else { if (d_S) (void)hipFree(d_S); d_S = nullptr; (void)hipGetLastError(); }
     }
     plan = s_plan(call, pol, SHeld{dev_np, dev_n, h_S ? h_n : 0, slot_held});
@@ -1176,12 +1182,14 @@ int SCache::begin_verify(eagle_ctx* ctx, const double* S_host, long n, long np) 
     if (plan.verify == SV_NONE) return EAGLE_OK;
     if (plan.verify == SV_HOST) { scache_host_pass(*this, S_host, n, false); return EAGLE_OK; }
     if (!h_flag) {
-        const hipError_t e = hipHostMalloc((void**)&h_flag, 64, hipHostMallocDefault);
+        const hipError_t e = pin_alloc(&h_flag, 64);
         if (e != hipSuccess) { plan.verify = SV_NONE; return eagle_fail_hip(ctx, e, "pinned flag"); }
     }
     auto compare = [this, ctx, S_host, n, np]() -> int {
-        int* flag = (int*)((char*)ctx->d_scratch + EAGLE_SCR_SCACHE_FLAG);
         HIPCHK(ctx, hipSetDevice(ctx->device));
+        int* flag = (int*)scr_take(ctx, EAGLE_SCR_SCACHE_FLAG);
+        HIPCHK(ctx, dev_scratch_handout(d_scr, sizeof(double) * (size_t)np * np));   // (the scratch copy the caller's S is compared in)
+        pin_scratch_handout(h_flag, 64);
         *h_flag = 0;
         HIPCHK(ctx, hipMemsetAsync(flag, 0, sizeof(int), ctx->load_stream));
         const int r = upload_square_on(ctx, S_host, n, np, d_scr, ctx->load_stream);
@@ -1271,9 +1279,9 @@ static int ensure_scan_out(eagle_ctx* ctx, long L_pad) {
     if (ctx->d_vara) { (void)hipFree(ctx->d_vara); ctx->d_vara = nullptr; }
     if (ctx->d_bound) { (void)hipFree(ctx->d_bound); ctx->d_bound = nullptr; }
     ctx->scan_cap = 0;
-    HIPCHK(ctx, hipMalloc((void**)&ctx->d_a, sizeof(double) * (size_t)L_pad));
-    HIPCHK(ctx, hipMalloc((void**)&ctx->d_vara, sizeof(double) * (size_t)L_pad));
-    HIPCHK(ctx, hipMalloc((void**)&ctx->d_bound, sizeof(double) * (size_t)L_pad));
+    HIPCHK(ctx, dev_alloc(&ctx->d_a, sizeof(double) * (size_t)L_pad));
+    HIPCHK(ctx, dev_alloc(&ctx->d_vara, sizeof(double) * (size_t)L_pad));
+    HIPCHK(ctx, dev_alloc(&ctx->d_bound, sizeof(double) * (size_t)L_pad));
     ctx->scan_cap = L_pad;
     return EAGLE_OK;
 }
@@ -1339,12 +1347,12 @@ static int scan_setup(eagle_ctx* ctx, const ScanArgs& A, const ScanShare& D, Sca
     const long Lc = st.Lc = P.streamed ? stream_chunk_rows(np, st.Lp) : st.Lp;
     const size_t wsb = P.use_i8 ? (size_t)eagle_vara_i8_workspace_bytes(np, Lc, st.nslices) : 0;
     const size_t certb = P.use_i8 ? (size_t)eagle_scan_certify_workspace_bytes(np) : 0;
-    st.cert_totals = (long*)((char*)ctx->d_scratch + EAGLE_SCR_CERT_TOTALS);
+    st.cert_totals = (long*)scr_take(ctx, EAGLE_SCR_CERT_TOTALS);
     int r = arena_reserve(ctx, 4 * arena_round(sq) + 2 * arena_round(sizeof(double) * np) + arena_round(wsb) + arena_round(certb) +
                                    (P.streamed ? (P.use_i8 ? 4 : 2) * arena_round((size_t)Lc * np) + 2 * arena_round((size_t)Lc) +
                                                      2 * arena_round(2 * sizeof(int32_t) * (size_t)Lc) : 0));
     if (r) return r;
-    st.Sa = arena_take<double>(ctx, sq);
+    st.Sa = arena_take<double>(ctx, sq, s_slot_valid(ctx->scache.slot, ctx->arena_gen, ctx->arena_off, n, np));
     st.Va = arena_take<double>(ctx, sq);
     st.tmp = arena_take<double>(ctx, sq);
     st.Wu = arena_take<double>(ctx, sq);
@@ -1499,10 +1507,10 @@ static int scan_verify_s(eagle_ctx* ctx, const ScanArgs& A, ScanState& st) {
 // The re-centred image of a resident file for the int8 scan, made by the first such scan of the file and kept with it.
 static int ensure_shifted_image(eagle_ctx* ctx, GenoEntry* g, long n, long np) {
     if (g->dev_s) return EAGLE_OK;
-    hipError_t e = hipMalloc((void**)&g->dev_s, (size_t)g->rows_pad * g->ld);
-    if (e != hipSuccess && eagle_drop_f4_images(ctx) > 0) { (void)hipGetLastError(); e = hipMalloc((void**)&g->dev_s, (size_t)g->rows_pad * g->ld); }
-    if (e == hipSuccess) e = hipMalloc((void**)&g->cshift, (size_t)g->rows_pad);
-    if (e == hipSuccess) e = hipMalloc((void**)&g->l1, 2 * sizeof(int32_t) * (size_t)g->rows_pad);
+    hipError_t e = dev_alloc(&g->dev_s, (size_t)g->rows_pad * g->ld);
+    if (e != hipSuccess && eagle_drop_f4_images(ctx) > 0) { (void)hipGetLastError(); e = dev_alloc(&g->dev_s, (size_t)g->rows_pad * g->ld); }
+    if (e == hipSuccess) e = dev_alloc(&g->cshift, (size_t)g->rows_pad);
+    if (e == hipSuccess) e = dev_alloc(&g->l1, 2 * sizeof(int32_t) * (size_t)g->rows_pad);
     const int rc = e == hipSuccess ? eagle_dev_marker_shift(ctx, g->dev, g->rows_pad, n, np, g->ld, g->dev_s, g->cshift, g->l1, ctx->stream)
                                    : eagle_fail_hip(ctx, e, "re-centred image hipMalloc");
     if (rc) {  // never leave a half-made image behind: the next call would scan garbage
@@ -1974,7 +1982,8 @@ static int local_scan_argmax(eagle_ctx* ctx, eagle_best* h) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
     // ctx-owned workspace: a hipMalloc / hipFree pair per call costs milliseconds in a process that has 100+ GB mapped (measured:
     // 13 ms per find_qtl-shaped call inside bench.py), and hipFree synchronises the device
-    if (!ctx->argmax_ws) HIPCHK(ctx, hipMalloc(&ctx->argmax_ws, sizeof(double) * 3 * 1024 + 256));
+    if (!ctx->argmax_ws) HIPCHK(ctx, dev_alloc(&ctx->argmax_ws, sizeof(double) * 3 * 1024 + 256));
+    else HIPCHK(ctx, dev_scratch_handout(ctx->argmax_ws, sizeof(double) * 3 * 1024 + 256));
     double* scratch = (double*)ctx->argmax_ws;
     eagle_best* best = (eagle_best*)((char*)ctx->argmax_ws + sizeof(double) * 3 * 1024);
     int rc = eagle_dev_tsq_argmax(ctx, ctx->d_a, ctx->d_vara, ctx->scan_L, nullptr, best, scratch, ctx->stream);

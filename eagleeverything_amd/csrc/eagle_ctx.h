@@ -241,17 +241,64 @@ static inline void say(eagle_ctx* ctx, const char* fmt, ...) {
         if (e__ != hipSuccess) return eagle_fail_hip(ctx, e__, #call); \
     } while (0)
 
+// ---- The allocation path ----
+// Every device and pinned allocation of the library is made by the two functions below, and nowhere else (tests/test_poison_host.py
+// holds the sources to that).  EAGLE_HIP_POISON=<0..255> in the environment, read at every allocation as the other test hooks are,
+// fills what they return with that byte; dev_scratch_handout / pin_scratch_handout do the same where a buffer the context keeps is handed
+// out again as scratch without a new allocation (which buffers are scratch, which are state and never filled).  The fill
+// waits for the device before and behind it -- the buffer may still be read by work in flight on either stream, and is written next on
+// any of them.  Unset: one getenv per allocation and nothing else.
+static inline int poison_byte() { return poison_parse(getenv("EAGLE_HIP_POISON")); }
+static inline hipError_t dev_poison(void* p, size_t bytes, int byte) {
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemset(p, byte, bytes);
+    return e == hipSuccess ? hipDeviceSynchronize() : e;
+}
+static inline hipError_t dev_alloc(void** p, size_t bytes) {
+    const hipError_t e = hipMalloc(p, bytes);
+    const int byte = poison_byte();
+    if (e != hipSuccess || byte < 0 || !bytes) return e;
+    const hipError_t ef = dev_poison(*p, bytes, byte);
+    if (ef != hipSuccess) { (void)hipFree(*p); *p = nullptr; }   // a block that could not be filled is no allocation: the callers treat it as failed
+    return ef;
+}
+template <class T> static inline hipError_t dev_alloc(T** p, size_t bytes) { return dev_alloc((void**)p, bytes); }
+static inline hipError_t pin_alloc(void** p, size_t bytes) {
+    const hipError_t e = hipHostMalloc(p, bytes, hipHostMallocDefault);
+    const int byte = poison_byte();
+    if (e == hipSuccess && byte >= 0) memset(*p, byte, bytes);
+    return e;
+}
+template <class T> static inline hipError_t pin_alloc(T** p, size_t bytes) { return pin_alloc((void**)p, bytes); }
+// `bytes` of a kept buffer about to be used as scratch again (no-ops with the hook unset, or p null)
+static inline hipError_t dev_scratch_handout(void* p, size_t bytes) {
+    const int byte = poison_byte();
+    return byte >= 0 && p && bytes ? dev_poison(p, bytes, byte) : hipSuccess;
+}
+// A sub-region of the context's scratch page as its user takes it (EAGLE_SCR_*, eagle_host.h: every region runs to the next one)
+static inline void* scr_take(eagle_ctx* ctx, size_t off) {
+    static const size_t at[] = {EAGLE_SCR_SYM, EAGLE_SCR_CERT_TOTALS, EAGLE_SCR_INGEST, EAGLE_SCR_LOADER_BAD, EAGLE_SCR_SCACHE_FLAG,
+                                EAGLE_SCR_DOT_PARTIALS, EAGLE_SCR_BYTES};
+    void* p = (char*)ctx->d_scratch + off;
+    for (int k = 0; k < 6; k++) if (at[k] == off) (void)dev_scratch_handout(p, at[k + 1] - off);
+    return p;
+}
+static inline void pin_scratch_handout(void* p, size_t bytes) {
+    const int byte = poison_byte();
+    if (byte >= 0 && p && bytes && hipDeviceSynchronize() == hipSuccess) memset(p, byte, bytes);
+}
+
 // RAII device / pinned buffers so every error path frees what it took
 struct DevBuf {
     void* p = nullptr;
     ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
+    hipError_t alloc(size_t bytes) { return dev_alloc(&p, bytes ? bytes : 16); }
     template <class T> T* as() { return (T*)p; }
 };
 struct PinBuf {
     void* p = nullptr;
     ~PinBuf() { if (p) (void)hipHostFree(p); }
-    hipError_t alloc(size_t bytes) { return hipHostMalloc(&p, bytes ? bytes : 16, hipHostMallocDefault); }
+    hipError_t alloc(size_t bytes) { return pin_alloc(&p, bytes ? bytes : 16); }
 };
 // the two events of a double-buffered pipeline: e[b] is recorded behind the last stream work that touches buffer b
 struct EventPair {

@@ -1016,4 +1016,17 @@ static inline long vcf_window_bytes(long chunk_bytes, double mem_gb) {
 static inline bool vcf_line_fits(long line_bytes, double mem_gb) { return mem_gb <= 0 || (double)line_bytes <= mem_gb * 1e9 / 4.0; }
 // Kept lines a window of `cap` text bytes can hold when every kept line carries n sample fields: a field and its separator are two bytes.
 static inline long vcf_window_lines(long cap, long n) { return cap / (2 * n) + 1; }
+
+// EAGLE_HIP_POISON (eagle_ctx.h, "The allocation path"): the fill byte its value names, or -1 = no fill.  A value is one to three
+// decimal digits that make a number in 0 .. 255 and nothing else; unset, empty, out of range or anything with another character in it
+// leaves the hook off (a test hook that half understands its value would fill with a byte nobody asked for).
+static inline int poison_parse(const char* e) {
+    if (!e || !e[0]) return -1;
+    int v = 0, k = 0;
+    for (; e[k]; k++) {
+        if (e[k] < '0' || e[k] > '9' || k >= 3) return -1;
+        v = 10 * v + (e[k] - '0');
+    }
+    return v <= 255 ? v : -1;
+}
 #endif

@@ -58,7 +58,7 @@ int syrk_pair_table(eagle_ctx* ctx, int nt, const int** out, hipStream_t stream)
             for (int i = si; i < si + G && i < nt; i++)
                 for (int j = (sj > i ? sj : i); j < sj + G && j < nt; j++) h.push_back((i << 16) | j);
     int* d = nullptr;
-    hipError_t e = hipMalloc((void**)&d, h.size() * sizeof(int));
+    hipError_t e = dev_alloc(&d, h.size() * sizeof(int));
     if (e != hipSuccess) return eagle_fail_hip(ctx, e, "pair table alloc");
     e = hipMemcpy(d, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice);
     if (e != hipSuccess) { (void)hipFree(d); return eagle_fail_hip(ctx, e, "pair table copy"); }
@@ -2016,10 +2016,10 @@ static int vara_i8_launch(eagle_ctx* ctx, const int8_t* Mt8s, long L_pad, long n
             const size_t need = sizeof(int) * 8 * (size_t)((gw * smax + 31) / 32 + 1) * (size_t)((n_pad / T8 + 1) / 2);
             if (need > ctx->gemm_scratch_cap) {
                 if (ctx->gemm_scratch) { (void)hipStreamSynchronize(s); (void)hipFree(ctx->gemm_scratch); ctx->gemm_scratch = nullptr; ctx->gemm_scratch_cap = 0; }
-                hipError_t ea = hipMalloc(&ctx->gemm_scratch, need);
+                hipError_t ea = dev_alloc(&ctx->gemm_scratch, need);
                 if (ea != hipSuccess) return eagle_fail_hip(ctx, ea, "pace counters");
                 ctx->gemm_scratch_cap = need;
-            }
+            } else if (hipError_t eh = dev_scratch_handout(ctx->gemm_scratch, need)) return eagle_fail_hip(ctx, eh, "pace counters");
             hipError_t ea = hipMemsetAsync(ctx->gemm_scratch, 0, need, s);
             if (ea != hipSuccess) return eagle_fail_hip(ctx, ea, "pace counters memset");
             return vara_i8_run(ctx, form.kernel, k_vara_i8p<true>, gridw, ldsw, s, Mt8s, ld, ntw, Bs, n_pad, hdr, q, L_pad, cut, (int*)ctx->gemm_scratch, kl);
@@ -2993,7 +2993,7 @@ static int syrk_pair_table_w(eagle_ctx* ctx, int nti, int ntj, const int** out, 
                 for (int j = sj; j < sj + 8 && j < ntj; j++)
                     if (3 * i / 2 <= j) h.push_back((i << 16) | j);
     int* d = nullptr;
-    hipError_t e = hipMalloc((void**)&d, h.size() * sizeof(int));
+    hipError_t e = dev_alloc(&d, h.size() * sizeof(int));
     if (e != hipSuccess) return eagle_fail_hip(ctx, e, "pair table alloc");
     e = hipMemcpy(d, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice);
     if (e != hipSuccess) { (void)hipFree(d); return eagle_fail_hip(ctx, e, "pair table copy"); }

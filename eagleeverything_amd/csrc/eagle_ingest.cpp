@@ -307,7 +307,7 @@ static int create_M_text(eagle_ctx* ctx, const char* fname, const char* asciifna
     HIPCHK(ctx, bad.alloc(sizeof(int)));
     HIPCHK(ctx, hipMemsetAsync(bad.p, 0, sizeof(int), ctx->stream));
     if (nlines == dims[0] && nlines > 0 && L > 0 && fits_resident((size_t)n_pad * ld)) {
-        if (hipMalloc((void**)&dev, (size_t)n_pad * ld) != hipSuccess) dev = nullptr;
+        if (dev_alloc(&dev, (size_t)n_pad * ld) != hipSuccess) dev = nullptr;
         else HIPCHK(ctx, hipMemsetAsync(dev, 0, (size_t)n_pad * ld, ctx->stream));
     }
     struct DevGuard { int8_t*& p; ~DevGuard() { if (p) (void)hipFree(p); } } guard{dev};
@@ -434,7 +434,7 @@ static int create_M_plink(eagle_ctx* ctx, const char* fname, const char* asciifn
     HIPCHK(ctx, hipMemsetAsync(image.p, 0, (size_t)img_rows * ld, ctx->stream));
     HIPCHK(ctx, alleles.alloc((size_t)2 * L));
     HIPCHK(ctx, hipMemsetAsync(alleles.p, 0, (size_t)2 * L, ctx->stream));
-    unsigned long long* flags = (unsigned long long*)((char*)eagle_ctx_scratch(ctx) + EAGLE_SCR_INGEST);   // [0] first third-allele, [1] first missing
+    unsigned long long* flags = (unsigned long long*)scr_take(ctx, EAGLE_SCR_INGEST);   // [0] first third-allele, [1] first missing
     HIPCHK(ctx, hipMemsetAsync(flags, 0xff, 2 * sizeof(unsigned long long), ctx->stream));
 
     SidecarWriter sc;
@@ -843,7 +843,7 @@ extern "C" int eagle_create_ascii_from_bed(eagle_ctx* ctx, const char* bed_path,
     const bool keepM = fits_resident((size_t)n_pad * L_pad);
     const long band = keepM ? n_pad : stream_chunk_rows_core(budget, L_pad, n_pad);   // individuals per pass over the bed file
     HIPCHK(ctx, mimg.alloc((size_t)band * L_pad));
-    unsigned long long* d_missing = (unsigned long long*)((char*)eagle_ctx_scratch(ctx) + EAGLE_SCR_INGEST);
+    unsigned long long* d_missing = (unsigned long long*)scr_take(ctx, EAGLE_SCR_INGEST);
     HIPCHK(ctx, hipMemsetAsync(d_missing, 0, sizeof(unsigned long long), ctx->stream));
 
     TextOut outM, outMt;

@@ -1027,7 +1027,7 @@ static int gemm_tile_list(eagle_ctx* ctx, int nt, int kind, int rt0, int rt1, co
             if (kind == 0 || (kind == 1 && i <= j) || (kind == 2 && i > j)) h.push_back((i << 16) | j);
     int* d = nullptr;
     if (!h.empty()) {
-        hipError_t e = hipMalloc((void**)&d, h.size() * sizeof(int));
+        hipError_t e = dev_alloc(&d, h.size() * sizeof(int));
         if (e != hipSuccess) return eagle_fail_hip(ctx, e, "gemm tile list alloc");
         e = hipMemcpy(d, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice);
         if (e != hipSuccess) { (void)hipFree(d); return eagle_fail_hip(ctx, e, "gemm tile list copy"); }
@@ -1055,7 +1055,7 @@ static int gemm_dma_tile_list(eagle_ctx* ctx, int nt, int kind, int rt0, int rt1
             if (kind == 0 || (kind == 1 && j >= i) || (kind == 2 && j < i) || (kind == 3 && j <= i + 1)) h.push_back((i << 16) | j);
     int* d = nullptr;
     if (!h.empty()) {
-        hipError_t e = hipMalloc((void**)&d, h.size() * sizeof(int));
+        hipError_t e = dev_alloc(&d, h.size() * sizeof(int));
         if (e != hipSuccess) return eagle_fail_hip(ctx, e, "gemm tile list alloc");
         e = hipMemcpy(d, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice);
         if (e != hipSuccess) { (void)hipFree(d); return eagle_fail_hip(ctx, e, "gemm tile list copy"); }
@@ -1089,10 +1089,10 @@ static int gemm_f64_dma_tiles(eagle_ctx* ctx, const double* A, const double* B, 
         const size_t need = (size_t)tail * split * G2_TM * G2_TN * sizeof(double);
         if (need > ctx->gemm_scratch_cap) {
             if (ctx->gemm_scratch) { (void)hipStreamSynchronize((hipStream_t)stream); (void)hipFree(ctx->gemm_scratch); ctx->gemm_scratch = nullptr; ctx->gemm_scratch_cap = 0; }
-            hipError_t e = hipMalloc(&ctx->gemm_scratch, need);
+            hipError_t e = dev_alloc(&ctx->gemm_scratch, need);
             if (e != hipSuccess) return eagle_fail_hip(ctx, e, "gemm scratch");
             ctx->gemm_scratch_cap = need;
-        }
+        } else if (hipError_t e = dev_scratch_handout(ctx->gemm_scratch, need)) return eagle_fail_hip(ctx, e, "gemm scratch");
         scratch = (double*)ctx->gemm_scratch;
     }
     const long blocks = split > 1 ? n_main + tail * split : count;
@@ -1145,10 +1145,10 @@ static int gemm_f64_tiles(eagle_ctx* ctx, const double* A, const double* B, doub
         const size_t need = (size_t)tail * split * GF_T * GF_T * sizeof(double);
         if (need > ctx->gemm_scratch_cap) {
             if (ctx->gemm_scratch) { (void)hipStreamSynchronize((hipStream_t)stream); (void)hipFree(ctx->gemm_scratch); ctx->gemm_scratch = nullptr; ctx->gemm_scratch_cap = 0; }
-            hipError_t e = hipMalloc(&ctx->gemm_scratch, need);
+            hipError_t e = dev_alloc(&ctx->gemm_scratch, need);
             if (e != hipSuccess) return eagle_fail_hip(ctx, e, "gemm scratch");
             ctx->gemm_scratch_cap = need;
-        }
+        } else if (hipError_t e = dev_scratch_handout(ctx->gemm_scratch, need)) return eagle_fail_hip(ctx, e, "gemm scratch");
         scratch = (double*)ctx->gemm_scratch;
     }
     const long blocks = split > 1 ? n_main + tail * split : count;
@@ -1207,7 +1207,7 @@ extern "C" int eagle_dev_scan_operands_vrows(eagle_ctx* ctx, const double* Sa, c
 extern "C" int eagle_dev_scan_operands_finish(eagle_ctx* ctx, const double* Sa, const double* Va, long n_pad, double* Wu_out, double* tmp, void* stream) {
     if (n_pad % GF_T) return eagle_fail(ctx, EAGLE_ERR_ARG, "scan_operands: bad padding");
     hipStream_t s = (hipStream_t)stream;
-    int* sym = (int*)((char*)eagle_ctx_scratch(ctx) + EAGLE_SCR_SYM);
+    int* sym = (int*)scr_take(ctx, EAGLE_SCR_SYM);
     hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, s, sym, 1);
     dim3 g32((unsigned)(n_pad / 32), (unsigned)(n_pad / 32));
     hipLaunchKernelGGL(k_sym_check, g32, dim3(256), 0, s, Sa, Va, n_pad, sym);
@@ -1288,7 +1288,7 @@ extern "C" int eagle_dev_scan_operands_rows(eagle_ctx* ctx, const double* Sa, co
 extern "C" int eagle_dev_fold_upper(eagle_ctx* ctx, double* W, long n_pad, void* stream) {
     if (ctx->w8_Wu == W) ctx->w8_active = false;
     if (n_pad % 32) return eagle_fail(ctx, EAGLE_ERR_ARG, "fold_upper: bad padding");
-    int* sym = (int*)((char*)eagle_ctx_scratch(ctx) + EAGLE_SCR_SYM);
+    int* sym = (int*)scr_take(ctx, EAGLE_SCR_SYM);
     hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, (hipStream_t)stream, sym, 0);
     dim3 g32((unsigned)(n_pad / 32), (unsigned)(n_pad / 32));
     hipLaunchKernelGGL(k_fold_upper, g32, dim3(256), 0, (hipStream_t)stream, W, n_pad, sym);
@@ -1453,9 +1453,9 @@ extern "C" int eagle_dev_gemv3_i8(eagle_ctx* ctx, const int8_t* Mt8, long L_pad,
     if (L_pad % 16 || n_pad % 256 || ld % 16 || n_pad > ld) return eagle_fail(ctx, EAGLE_ERR_ARG, "gemv_i8: layout contract violated (L_pad % 16, n_pad % 256, ld % 16)");
     if (L_pad == 0 || n_pad == 0) return EAGLE_OK;
     if (!ctx->gemv_ws) {
-        hipError_t e = hipMalloc(&ctx->gemv_ws, 32 * GV_MAXN + 256);
+        hipError_t e = dev_alloc(&ctx->gemv_ws, 32 * GV_MAXN + 256);
         if (e != hipSuccess) return eagle_fail_hip(ctx, e, "gemv workspace");
-    }
+    } else if (hipError_t e = dev_scratch_handout(ctx->gemv_ws, 32 * GV_MAXN + 256)) return eagle_fail_hip(ctx, e, "gemv workspace");
     int8_t* B = (int8_t*)ctx->gemv_ws;
     int* exps = (int*)(B + 32 * GV_MAXN);
     if (!ctx->attr_gemv) {  // per device
@@ -1648,9 +1648,9 @@ extern "C" int eagle_dev_gemv3_2bit(eagle_ctx* ctx, const void* Mt2v, long L_pad
     const uint8_t* Mt2 = (const uint8_t*)Mt2v;
     const long ld2 = ld >> 2;
     if (!ctx->gemv_ws) {
-        hipError_t e = hipMalloc(&ctx->gemv_ws, 32 * GV_MAXN + 256);
+        hipError_t e = dev_alloc(&ctx->gemv_ws, 32 * GV_MAXN + 256);
         if (e != hipSuccess) return eagle_fail_hip(ctx, e, "gemv workspace");
-    }
+    } else if (hipError_t e = dev_scratch_handout(ctx->gemv_ws, 32 * GV_MAXN + 256)) return eagle_fail_hip(ctx, e, "gemv workspace");
     int8_t* B = (int8_t*)ctx->gemv_ws;
     int* exps = (int*)(B + 32 * GV_MAXN);
     if (!ctx->attr_gemv2) {  // per device
@@ -2189,7 +2189,7 @@ extern "C" int eagle_dev_transpose_f64(eagle_ctx* ctx, const double* in, double*
     return EAGLE_OK;
 }
 extern "C" int eagle_dev_dot_matrices(eagle_ctx* ctx, const double* A, long lda, const double* B, long ldb, long n, double* out, void* stream) {
-    double* part = (double*)((char*)eagle_ctx_scratch(ctx) + EAGLE_SCR_DOT_PARTIALS);  // 256 partial sums, their own region of the ctx scratch
+    double* part = (double*)scr_take(ctx, EAGLE_SCR_DOT_PARTIALS);  // 256 partial sums, their own region of the ctx scratch
     hipLaunchKernelGGL(k_dot_rows, dim3(256), dim3(256), 0, (hipStream_t)stream, A, lda, B, ldb, n, part);
     hipLaunchKernelGGL(k_dot_final, dim3(1), dim3(1), 0, (hipStream_t)stream, part, 256, out);
     LAUNCH_CHECK(ctx);

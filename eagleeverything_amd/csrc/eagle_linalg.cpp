@@ -252,7 +252,7 @@ extern "C" int eagle_mmt_sqrt_and_sqrtinv(eagle_ctx* ctx, const double* MMt, lon
     if ((rc = dev_chol2inv(ctx, dU.as<double>(), n))) return rc;
     HIPCHK(ctx, hipMemcpyAsync(invsqrt_out, dU.p, sizeof(double) * (size_t)n * n, hipMemcpyDeviceToHost, ctx->stream));
     if (trace_out) {  // tr(sqrt invsqrt) = sum_ij sqrt_ij invsqrt_ij (both symmetric), fixed-order reduction
-        double* d_tr = (double*)((char*)ctx->d_scratch + EAGLE_SCR_INGEST);
+        double* d_tr = (double*)scr_take(ctx, EAGLE_SCR_INGEST);
         if ((rc = eagle_dev_dot_matrices(ctx, dS.as<double>(), N, dU.as<double>(), n, n, d_tr, ctx->stream))) return rc;
         HIPCHK(ctx, hipMemcpyAsync(trace_out, d_tr, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     }

@@ -105,7 +105,10 @@ static void parallel_pread(int fd, uint8_t* dst, long dst_stride, long nrows, lo
 
 // Two pinned host buffers + two device buffers of at least `need` bytes each, owned by the ctx (grow-only).
 int eagle_stage_ensure(eagle_ctx* ctx, size_t need) {
-    if (need <= ctx->stage_cap) return EAGLE_OK;
+    if (need <= ctx->stage_cap) {   // handed out again: every caller asks before it stages the first byte of its pass
+        for (int b = 0; b < 2; b++) { HIPCHK(ctx, dev_scratch_handout(ctx->stage_raw[b], need)); pin_scratch_handout(ctx->stage_pin[b], need); }
+        return EAGLE_OK;
+    }
     (void)hipStreamSynchronize(ctx->stream);
     for (int b = 0; b < 2; b++) {
         if (ctx->stage_pin[b]) { (void)hipHostFree(ctx->stage_pin[b]); ctx->stage_pin[b] = nullptr; }
@@ -113,8 +116,8 @@ int eagle_stage_ensure(eagle_ctx* ctx, size_t need) {
     }
     ctx->stage_cap = 0;
     for (int b = 0; b < 2; b++) {
-        HIPCHK(ctx, hipHostMalloc(&ctx->stage_pin[b], need, hipHostMallocDefault));
-        HIPCHK(ctx, hipMalloc(&ctx->stage_raw[b], need));
+        HIPCHK(ctx, pin_alloc(&ctx->stage_pin[b], need));
+        HIPCHK(ctx, dev_alloc(&ctx->stage_raw[b], need));
     }
     ctx->stage_cap = need;
     return EAGLE_OK;
@@ -137,7 +140,7 @@ static int stream_rows(eagle_ctx* ctx, int fd, off_t off0, long src_stride, cons
     if (rc) return rc;
     // the bad-byte counter lives in the ctx scratch page: a hipMalloc / hipFree per tile would synchronise the device,
     // i.e. wait for the kernels of the previous chunk when the tile is a chunk of a streamed file
-    int* const bad = (int*)((char*)ctx->d_scratch + EAGLE_SCR_LOADER_BAD);
+    int* const bad = (int*)scr_take(ctx, EAGLE_SCR_LOADER_BAD);
     HIPCHK(ctx, hipMemsetAsync(bad, 0, sizeof(int), ctx->stream));
     EventPair done;
     HIPCHK(ctx, done.create());
@@ -218,7 +221,7 @@ static int scan_lines(eagle_ctx* ctx, int fd, const LoadPlan& p, int8_t* dst, lo
     if (rc) return rc;
     char* const pin = (char*)ctx->stage_pin[0];
     uint8_t* const raw = (uint8_t*)ctx->stage_raw[0];
-    int* const bad = (int*)((char*)ctx->d_scratch + EAGLE_SCR_LOADER_BAD);
+    int* const bad = (int*)scr_take(ctx, EAGLE_SCR_LOADER_BAD);
     HIPCHK(ctx, hipMemsetAsync(bad, 0, sizeof(int), ctx->stream));
     long filled = 0, out_row = 0;  // staged rows, destination of the first
     auto flush = [&]() -> int {
@@ -365,7 +368,7 @@ int get_resident(eagle_ctx* ctx, const char* path, long row0, long rows, long co
         HIPCHK(ctx, hipMemGetInfo(&freeb, &totalb));
         if (bytes + reserve_bytes > freeb) return EAGLE_STREAM;  // does not fit beside the operands: stream it
     }
-    HIPCHK(ctx, hipMalloc((void**)&g.dev, bytes));
+    HIPCHK(ctx, dev_alloc(&g.dev, bytes));
     hipError_t e = hipMemsetAsync(g.dev, 0, bytes, ctx->stream);
     if (e != hipSuccess) { (void)hipFree(g.dev); return eagle_fail_hip(ctx, e, "memset"); }
     int rc = eagle_dev_load_ascii(ctx, path, row0, rows, col0, cols, g.dev, g.ld, max_mem_gb, threads);
@@ -507,7 +510,7 @@ int eagle_load_rows(eagle_ctx* ctx, const char* path, const std::vector<RowRun>&
         if (lines > v->lines) return eagle_fail(ctx, EAGLE_ERR_FORMAT, "file has fewer lines than requested");
         if (col0 + ncols > (long)v->keep.size()) return eagle_fail(ctx, EAGLE_ERR_FORMAT, "line shorter than the requested columns");
         if (!v->d_keep) {   // made on first use
-            HIPCHK(ctx, hipMalloc((void**)&v->d_keep, sizeof(int32_t) * std::max((size_t)1, v->keep.size())));
+            HIPCHK(ctx, dev_alloc(&v->d_keep, sizeof(int32_t) * std::max((size_t)1, v->keep.size())));
             HIPCHK(ctx, hipMemcpy(v->d_keep, v->keep.data(), sizeof(int32_t) * v->keep.size(), hipMemcpyHostToDevice));
         }
         p.runs = runs;

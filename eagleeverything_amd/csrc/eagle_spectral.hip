@@ -352,7 +352,7 @@ extern "C" int eagle_spectral_prepare_range(eagle_ctx* ctx, const char* f_name_a
     HIPCHK(ctx, hipMemGetInfo(&freeb, &totalb));
     const size_t zbytes = sizeof(double) * (size_t)Lp * np, ubytes = sizeof(double) * (size_t)np * np;
     if (zbytes + 2 * ubytes + ((size_t)1 << 30) > freeb) return eagle_fail(ctx, EAGLE_ERR_NOMEM, "spectral_prepare: not enough HBM for Z = Mt U (8 bytes per genotype)");
-    HIPCHK(ctx, hipMalloc((void**)&ctx->d_Z, zbytes));
+    HIPCHK(ctx, dev_alloc(&ctx->d_Z, zbytes));
     DevBuf Ut, Ur;
     HIPCHK(ctx, Ut.alloc(ubytes));
     HIPCHK(ctx, Ur.alloc(ubytes));

@@ -755,10 +755,10 @@ extern "C" int eagle_w8_true_vara(eagle_ctx* ctx, const int8_t* rows8, long coun
     const size_t need = (size_t)(3 + W8_JS) * W8_TRUE_CHUNK * n_pad * sizeof(double);
     if (need > ctx->w8_true_cap) {
         if (ctx->w8_true_ws) { (void)hipStreamSynchronize(s); (void)hipFree(ctx->w8_true_ws); ctx->w8_true_ws = nullptr; ctx->w8_true_cap = 0; }
-        hipError_t e = hipMalloc(&ctx->w8_true_ws, need);
+        hipError_t e = dev_alloc(&ctx->w8_true_ws, need);
         if (e != hipSuccess) return eagle_fail_hip(ctx, e, "w8 re-evaluation buffer");
         ctx->w8_true_cap = need;
-    }
+    } else if (hipError_t e = dev_scratch_handout(ctx->w8_true_ws, need)) return eagle_fail_hip(ctx, e, "w8 re-evaluation buffer");
     double* X = (double*)ctx->w8_true_ws;
     double* T = X + (size_t)W8_TRUE_CHUNK * n_pad;
     double* U = T + (size_t)W8_TRUE_CHUNK * n_pad;
@@ -932,8 +932,8 @@ static int w8_get_list(eagle_ctx* ctx, int nt, int rt0, int rt1, bool upper, boo
     if (piped) w8_work_list(rt0, rt1, tj1, T8, TW_M, 8, 4, upper, gs, wl, &l.maxlen, tj0);
     else w8_work_list(rt0, rt1, tj1, T8, T8, 4, 8, upper, gs, wl, &l.maxlen, tj0);
     l.ngroups = (int)gs.size();
-    hipError_t e = hipMalloc((void**)&l.work, wl.size() * sizeof(unsigned) + 16);
-    if (e == hipSuccess) e = hipMalloc((void**)&l.groups, gs.size() * sizeof(W8Group));
+    hipError_t e = dev_alloc(&l.work, wl.size() * sizeof(unsigned) + 16);
+    if (e == hipSuccess) e = dev_alloc(&l.groups, gs.size() * sizeof(W8Group));
     if (e == hipSuccess) e = hipMemcpy(l.work, wl.data(), wl.size() * sizeof(unsigned), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(l.groups, gs.data(), gs.size() * sizeof(W8Group), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
@@ -976,10 +976,10 @@ static int w8_workspace(eagle_ctx* ctx, long np, W8Ws* w) {
         if (ctx->w8_ws) { (void)hipDeviceSynchronize(); (void)hipFree(ctx->w8_ws); ctx->w8_ws = nullptr; ctx->w8_ws_cap = 0; }
         ctx->w8_ws_gen++;   // what was kept with S lay in the old block (w8_keep_valid)
         w8_keep_forget(ctx->w8_keep);
-        if (hipMalloc(&ctx->w8_ws, need) != hipSuccess) {
+        if (dev_alloc(&ctx->w8_ws, need) != hipSuccess) {
             (void)hipGetLastError();
             ctx->w8_ws = nullptr;
-            if (!(eagle_drop_f4_images(ctx) > 0 && hipMalloc(&ctx->w8_ws, need) == hipSuccess)) { (void)hipGetLastError(); ctx->w8_ws = nullptr; return 1; }   // no room: decline
+            if (!(eagle_drop_f4_images(ctx) > 0 && dev_alloc(&ctx->w8_ws, need) == hipSuccess)) { (void)hipGetLastError(); ctx->w8_ws = nullptr; return 1; }   // no room: decline
         }
         ctx->w8_ws_cap = need;
     }
@@ -1000,6 +1000,23 @@ static int w8_workspace(eagle_ctx* ctx, long np, W8Ws* w) {
     w->stats = (W8Stats*)take(3 * sizeof(W8Stats));
     w->maxabs = (unsigned long long*)take(256);
     return 0;
+}
+
+// The workspace handed out to a call (EAGLE_HIP_POISON, eagle_ctx.h): all of it is scratch, except -- `kept`, the call found S's
+// record valid -- what eagle_w8_begin keeps with S: its digit slices sA, dS / mxS / ssqS / eS / dssqS, s1r, s1c and stats[0].
+static hipError_t w8_handout(eagle_ctx* ctx, const W8Ws& w, long np, bool kept) {
+    if (poison_byte() < 0) return hipSuccess;
+    char* const end = (char*)w.maxabs + 256;
+    if (!kept) return dev_scratch_handout(ctx->w8_ws, (size_t)(end - (char*)ctx->w8_ws));
+    const size_t vec = r256(sizeof(double) * (size_t)np), dss = r256(sizeof(unsigned long long) * W8_KMAX * (size_t)np);
+    hipError_t e = dev_scratch_handout(w.sB, (size_t)((char*)w.dS - (char*)w.sB));   // sB and the level images
+    void* const vecs[] = {w.dV, w.mxV, w.ssqV, w.dX, w.mxX, w.ssqX, w.r, w.r1, w.r2, w.sumdiag, w.eV, w.eX, w.bad};
+    for (void* v : vecs) if (e == hipSuccess) e = dev_scratch_handout(v, vec);
+    if (e == hipSuccess) e = dev_scratch_handout(w.gvpart, 8 * vec);
+    if (e == hipSuccess) e = dev_scratch_handout(w.dssqV, 2 * dss);                        // dssqV, dssqX
+    if (e == hipSuccess) e = dev_scratch_handout(w.asympart, (size_t)((char*)w.stats - (char*)w.asympart));
+    if (e == hipSuccess) e = dev_scratch_handout(w.stats + 1, (size_t)(end - (char*)(w.stats + 1)));   // V's and X's statistics, maxabs
+    return e;
 }
 
 // row statistics + digit slices of the rows [r0, r1) of one operand
@@ -1086,9 +1103,10 @@ static int w8_product(eagle_ctx* ctx, int cfg, bool upper, long np, const int8_t
 
 static int w8_fetch(eagle_ctx* ctx, void* dst, const void* src, size_t bytes, hipStream_t s) {
     if (!ctx->w8_host) {
-        hipError_t e = hipHostMalloc((void**)&ctx->w8_host, 4096, hipHostMallocDefault);
+        hipError_t e = pin_alloc(&ctx->w8_host, 4096);
         if (e != hipSuccess) return eagle_fail_hip(ctx, e, "w8 pinned block");
     }
+    pin_scratch_handout(ctx->w8_host, 4096);
     hipError_t e = hipMemcpyAsync(ctx->w8_host, src, bytes, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return eagle_fail_hip(ctx, e, "w8 statistics to the host");
@@ -1151,7 +1169,9 @@ extern "C" int eagle_w8_begin(eagle_ctx* ctx, const double* Sa, const double* Va
     // Everything that depends on S alone -- statistics + digit slices of its off-diagonal part F, S 1 and S^T 1 for the r-vector of
     // eagle_w8_finish -- is kept with S: a call on the same S (s_gen: its owner's number for this content, 0 = nobody vouches) in the
     // same workspace finds it all in place.  (V's follow row block by row block: eagle_w8_vrows)
-    if (w8_keep_valid(ctx->w8_keep, Sa, n, np, ctx->w8_ws, ctx->w8_ws_gen, s_gen, stream)) ctx->w8_keep_hits++;
+    const bool kept = w8_keep_valid(ctx->w8_keep, Sa, n, np, ctx->w8_ws, ctx->w8_ws_gen, s_gen, stream);
+    if (hipError_t eh = w8_handout(ctx, w, np, kept)) return eagle_fail_hip(ctx, eh, "w8 workspace");
+    if (kept) ctx->w8_keep_hits++;
     else {
         w8_keep_forget(ctx->w8_keep);
         ctx->w8_keep_misses++;
@@ -1323,6 +1343,7 @@ extern "C" int eagle_w8_probe_rows(eagle_ctx* ctx, const double* M, long np, con
     W8Ws w;
     if (w8_workspace(ctx, np, &w)) return eagle_fail(ctx, EAGLE_ERR_HIP, "w8_probe_rows: no workspace");
     w8_keep_forget(ctx->w8_keep);   // (asympart and the flag are shared with what is kept)
+    if (hipError_t eh = w8_handout(ctx, w, np, false)) return eagle_fail_hip(ctx, eh, "w8 workspace");
     hipError_t er = hipMemsetAsync(w.bad, 0, sizeof(int), s);
     if (er != hipSuccess) return eagle_fail_hip(ctx, er, "w8 memset");
     for (int k = 0; k + 1 < ncuts; k++) {
