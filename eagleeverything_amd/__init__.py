@@ -17,6 +17,8 @@ mirror of the reference interface used by tests, bench.py and the sharded multi-
                 tdt_families, tdt_summary, tdt_merge;
                 ReadMarker(type="VCF"), VcfToBed (a VCF file's GT fields decoded on the device into a PLINK binary fileset, missing
                 calls kept missing for every bed= route), vcf_to_bed_host
+  glmm       -- GLMM (case/control association under the logistic mixed model: GMMAT's score test with saddlepoint p-values),
+                null_fit, spa, spa_host, spa_pvalues; r_api.GLMM forwards to it
   host_model -- dense n x n model algebra that stays on host LAPACK by design
   sharded    -- marker-sharded multi-GPU scan / MM^T (one process per GPU, torch.distributed over RCCL)
   synth      -- seeded synthetic genotypes of the benchmark shapes

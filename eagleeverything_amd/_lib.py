@@ -145,6 +145,8 @@ SIGNATURES = {
                                C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), c_dp, c_dp, C.POINTER(C.c_int64)]),
     "eagle_logistic": (C.c_int,[C.c_void_p, C.c_char_p, c_lp, C.POINTER(C.c_int32), c_dp, C.c_int, c_dp, C.c_int, C.c_double, C.c_int,
                                  C.c_double, c_dp, C.POINTER(C.c_int32)]),
+    "eagle_glmm_spa": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, c_dp, c_dp, c_dp, C.c_int, c_dp, c_dp, C.c_double, C.c_double, C.c_int,
+                                 C.c_double, c_dp, C.POINTER(C.c_int32)]),
     "eagle_admixture_em": (C.c_int, [C.c_void_p, C.c_char_p, c_lp, C.c_int, C.c_int, c_dp, c_dp, C.c_double, c_dp]),
     "eagle_read_block": (C.c_int, [C.c_void_p, C.c_char_p, C.c_long, C.c_long, C.c_long, c_dp]),
     "eagle_calculateMMt": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double, C.c_int, c_dp, C.c_long, c_lp, C.c_int, c_dp]),

@@ -383,6 +383,13 @@ extern "C" int eagle_dev_maxt_finish(eagle_ctx* ctx, const double* pkey, const i
 // stat[rows][4] = (gamma, se, score, loglik), info[rows][2] = (code, evaluations); firth = 0 (ML), 1 (Firth), 2 (fallback).
 extern "C" int eagle_dev_logistic(eagle_ctx* ctx, const int8_t* Mt8, long rows, long n, long ld, const double* X16, const uint8_t* valid_y,
                                   const double* beta0, int p, int firth, double tol, int max_iter, double* stat, int32_t* info, void* stream);
+// Saddlepoint deviates of the score test under the logistic mixed model (eagle_glmm.hip; include/eagle_hip.h section 1d'''), device
+// pointers throughout, one row window.  X16: n64 x 16 fp64 as eagle_dev_logistic takes it; P4: n64 x 4 fp64 = (mu, 1 - mu, mu (1 - mu),
+// y - mu) per individual and (1/2, 1/2, 0, 0) from individual n on; A16: 16 x 16 fp64 = (X'DX)^-1, zero outside c x c; vara: rows fp64
+// or NULL.  stat[rows][7] = (T, V*, z, zeta_up, r*_up, zeta_lo, r*_lo), info[rows][2] = (code, evaluations).
+extern "C" int eagle_dev_glmm_spa(eagle_ctx* ctx, const int8_t* Mt8, long rows, long n, long ld, const double* X16, const double* P4,
+                                  const double* A16, int c, const double* vara, double cutoff, double tol, int max_iter, double* stat, int32_t* info,
+                                  void* stream);
 // One EM step of the admixture model (eagle_admix.hip; include/eagle_hip.h section 1b''''v), device pointers throughout.  Q16: n16 x 16
 // and Fin / Fout: L16 x 16 fp64 (n16, L16 = n, L rounded up to 16), columns >= K and the rows beyond n / L zero.  _window: the rows
 // [row0, row0 + rows) of the image, row0 a multiple of 16 and rows one too unless the window ends the panel; llpart[L16 / 16] takes the

@@ -1613,6 +1613,79 @@ extern "C" int eagle_logistic(eagle_ctx* ctx, const char* f_name_ascii_Mt, const
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// Saddlepoint p-values of the score test under the logistic mixed model (include/eagle_hip.h section 1d'''; the kernel is in
+// eagle_glmm.hip).  eagle_logistic's routes; the covariates are staged once per call as eagle_logistic stages them, mu, 1 - mu,
+// D = mu (1 - mu) and the residual as a second padded image of four columns, (X'DX)^-1 as a 16 x 16 one.
+// ---------------------------------------------------------------------------------------------------------------
+extern "C" int eagle_glmm_spa(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long dims[2], const double* mu, const double* resid,
+                              const double* X, int c, const double* A, const double* vara_or_NULL, double cutoff, double tol, int max_iter,
+                              double max_memory_in_Gbytes, double* stat_out, int32_t* info_out) {
+    auto fail = [&](const char* what) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "glmm_spa: %s", what);
+        return qc_fail(ctx, EAGLE_ERR_ARG, msg);
+    };
+    if (!f_name_ascii_Mt || !dims || !mu || !resid || !X || !A || !stat_out || !info_out) return fail("NULL argument");
+    const long n = dims[0], L = dims[1];
+    if (n <= 0 || L <= 0) return fail("dims must be positive");
+    if (n > 0x3fffffffL) return fail("more than 2^30 - 1 individuals");
+    if (c < 1 || c > 15) return fail("c outside [1, 15]");
+    for (long i = 0; i < n; i++)
+        if (!(mu[i] > 0.0 && mu[i] < 1.0)) return fail("a mu outside (0, 1)");
+    for (long i = 0; i < n; i++) {
+        if (!std::isfinite(resid[i])) return fail("a non-finite resid entry");
+        for (int j = 0; j < c; j++)
+            if (!std::isfinite(X[i + (size_t)n * j])) return fail("a non-finite X entry");
+    }
+    for (int j = 0; j < c * c; j++)
+        if (!std::isfinite(A[j])) return fail("a non-finite A entry");
+    if (!(cutoff >= 0.0)) return fail("cutoff negative or NaN");
+    if (!(tol > 0.0 && tol < 1.0)) return fail("tol not in (0, 1)");
+    if (max_iter < 1 || max_iter > 1000) return fail("max_iter outside [1, 1000]");
+    if (!ctx) return fail("no context");
+
+    const long n64 = (n + 63) / 64 * 64;
+    std::vector<double> x16((size_t)n64 * 16, 0.0), p4((size_t)n64 * 4, 0.0), a16(256, 0.0);
+    for (long i = 0; i < n64; i++) {
+        double* p = &p4[(size_t)i * 4];
+        if (i >= n) { p[0] = p[1] = 0.5; continue; }
+        p[0] = mu[i];
+        p[1] = 1.0 - mu[i];
+        p[2] = mu[i] * (1.0 - mu[i]);
+        p[3] = resid[i];
+        for (int j = 0; j < c; j++) x16[(size_t)i * 16 + j] = X[i + (size_t)n * j];
+    }
+    for (int i = 0; i < c; i++)
+        for (int j = 0; j < c; j++) a16[i * 16 + j] = A[i + (size_t)c * j];
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    DevBuf d_x, d_p4, d_a16, d_vara, stat, info;
+    HIPCHK(ctx, d_x.alloc(sizeof(double) * x16.size()));
+    HIPCHK(ctx, d_p4.alloc(sizeof(double) * p4.size()));
+    HIPCHK(ctx, d_a16.alloc(sizeof(double) * a16.size()));
+    if (vara_or_NULL) HIPCHK(ctx, d_vara.alloc(sizeof(double) * (size_t)L));
+    HIPCHK(ctx, stat.alloc(sizeof(double) * 7 * (size_t)L));
+    HIPCHK(ctx, info.alloc(sizeof(int32_t) * 2 * (size_t)L));
+    HIPCHK(ctx, hipMemcpyAsync(d_x.p, x16.data(), sizeof(double) * x16.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d_p4.p, p4.data(), sizeof(double) * p4.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d_a16.p, a16.data(), sizeof(double) * a16.size(), hipMemcpyHostToDevice, ctx->stream));
+    if (vara_or_NULL) HIPCHK(ctx, hipMemcpyAsync(d_vara.p, vara_or_NULL, sizeof(double) * (size_t)L, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));                  // the staged images are pageable host vectors
+    ImageLines lines;
+    int rc = lines.open(ctx, f_name_ascii_Mt, L, n, max_memory_in_Gbytes);
+    if (rc) return rc;
+    rc = lines.each(lines.disjoint(lines.stream_rows()), [&](const int8_t* img, long r0, long nr, long, long) {
+        return eagle_dev_glmm_spa(ctx, img, nr, n, lines.ld(), d_x.as<double>(), d_p4.as<double>(), d_a16.as<double>(), c,
+                                  vara_or_NULL ? d_vara.as<double>() + (size_t)r0 : nullptr, cutoff, tol, max_iter,
+                                  stat.as<double>() + 7 * (size_t)r0, info.as<int32_t>() + 2 * (size_t)r0, ctx->stream);
+    });
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(stat_out, stat.p, sizeof(double) * 7 * (size_t)L, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(info_out, info.p, sizeof(int32_t) * 2 * (size_t)L, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return EAGLE_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // Admixture: EM steps of the ancestry model (include/eagle_hip.h section 1b''''v; the kernels are in eagle_admix.hip).
 // eagle_group_counts' routes, one pass over the image per step and one more for the likelihood of the result.  Q and F are staged once
 // per call as 16-column padded images, the steps alternate between two buffers of each, and nothing comes back before the last pass.

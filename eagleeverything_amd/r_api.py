@@ -3754,6 +3754,18 @@ def GWAS(trait, X, geno, exact="all", method="reml", p_exact=None, map=None, bac
                    device=device, Zmat=Zmat)
 
 
+def GLMM(geno, status, X=None, tau=None, spa_cutoff=2.0, tol=1e-10, max_iter=50, map=None, backend=None, availmemGb=8, device=0):
+    """Case/control association of every marker under the logistic mixed model, logit P(case) = x' alpha + b, b ~ N(0, tau K), with
+    saddlepoint p-values (glmm.GLMM: GMMAT's score test and SAIGE's SPA; include/eagle_hip.h section 1d'''): what Logistic cannot do,
+    take a kinship term, and what GWAS on a 0 / 1 trait does not do, respect the trait's distribution.  status as Logistic takes it
+    (1 / 0 / NaN); X: (n, c <= 15) covariates WITH the intercept column, None = intercept only; tau= fixes the variance component
+    (0.0: no kinship term).  Returns "score", "p_norm", "p_spa", "p", "spa_used", "beta", "se", "code", "evaluations" per marker, "null"
+    (tau, alpha, converged, iterations), "lambda_gc", "n_used", "indxNA" and with map= "names"."""
+    from . import glmm
+    return glmm.GLMM(geno, status, X=X, tau=tau, spa_cutoff=spa_cutoff, tol=tol, max_iter=max_iter, map=map, backend=backend,
+                     availmemGb=availmemGb, device=device)
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # Tests of marker sets under the mixed model: burden and SKAT (include/eagle_hip.h section 1d''; device: rcpp_api.spectral_settest,
 # am.SetTest).

@@ -1592,6 +1592,72 @@ int eagle_spectral_settest(eagle_ctx* ctx, const double* lambda, const double* U
                            long nsets, const long* set_ptr, const long* set_idx, const double* omega, double* stat_out, int32_t* info_out,
                            double* score_out, double* cov_out);
 
+/* ---------------------------------------------------------------------------------------------
+ * 1d'''. Saddlepoint p-values of the score test under the logistic mixed model (no counterpart in the reference, whose trait is
+ *     quantitative): case/control association with a kinship term.  The model is GMMAT's (Chen et al. 2016),
+ *            logit mu_i = x_i' alpha + b_i,   b ~ N(0, tau K),
+ *     fitted once per trait on the host by penalised quasi-likelihood (eagleeverything_amd/glmm.py, null_fit), and the p-value of a
+ *     marker's score is SAIGE's saddlepoint approximation (SPA; Dey et al. 2017, Zhou et al. 2018), which repairs the normal
+ *     approximation where it fails: unbalanced case/control ratios and rare alleles.  This call is the per-marker part.
+ *     glmm.spa_host is a numpy restatement of the rule below.
+ *
+ *     Operands, all of the null fit: mu (n, each in (0, 1)); resid = y - mu (n); X (n x c column-major fp64 as R holds it, the caller
+ *     supplies the intercept column, 1 <= c <= 15); A = (X'DX)^-1 (c x c), D = diag(mu_i (1 - mu_i)), made once by the caller; vara
+ *     (one V_m = m' P m per marker, what eagle_scan_with_W returns for W = P) or NULL for V = V*.  g_i in {0, 1, 2} is the image value
+ *     plus one of line m of Mt.ascii; a missing call of the source is a heterozygote by now.  At the fixed point of the null fit
+ *     y - mu = P Y and X'(y - mu) = 0, so the score does not depend on whether m is the image value or the allele count.
+ *
+ *     1. First pass.  s = X'D g, beta = A s, G~_i = g_i - x_i' beta;  T = sum g_i resid_i;  V* = sum D_i G~_i^2;  m = sum G~_i mu_i.
+ *     2. Degenerate marker: V* <= 2^-40 sum D_i g_i^2, or a V that is not finite and positive (a monomorphic marker, a marker in the
+ *        span of X): code 2, z and the four values of 6 are NaN, no evaluation.
+ *     3. Scaling and screen.  z = T / sqrt(V), q = z sqrt(V*) = T sqrt(V* / V).  If |z| <= cutoff the marker ends here with code 4 and
+ *        0 evaluations; SAIGE's cutoff is 2.
+ *     4. The cumulant generating function of sum G~_i (y_i - mu_i), y_i independent Bernoulli(mu_i):
+ *            K(t) = sum log(1 - mu_i + mu_i e^(t G~_i)) - t m,
+ *            K'(t) = sum mu_i G~_i / ((1 - mu_i) e^(-t G~_i) + mu_i) - m,
+ *            K''(t) = sum (1 - mu_i) mu_i G~_i^2 e^(-t G~_i) / ((1 - mu_i) e^(-t G~_i) + mu_i)^2.
+ *        One evaluation is one pass over the individuals.  The centring by m is taken inside the sum, individual by individual, so
+ *        nothing of first order cancels between two sums and nothing overflows: with a = t G~_i, nu = 1 - mu_i for a >= 0 and mu_i
+ *        else, e = exp(-|a|), u = 1 - e, den = 1 - nu u the three terms of individual i are
+ *            nu |a| + log1p(-nu u),     sign(a) D_i G~_i u / den,     D_i G~_i^2 e / den^2,
+ *        one exp and one log1p, as section 1b''''iv evaluates its likelihood.  K'(0) = 0 and K''(0) = V* need no evaluation.
+ *     5. Tails.  There are two, with targets +|q| (zeta_up) and -|q| (zeta_lo); the one on the side of T, the observed side, is
+ *        taken first.  zeta_max = 500 / max_i |G~_i|.  A target is reachable when K'(+-zeta_max) passes it by more than 2^-40 |target| (a statistic AT the edge
+ *        of its support is not reachable, whatever the last bit of the sums), which is the tail's first evaluation.  An unreachable observed-side target is code 3: all carriers are cases, the statistic sits at the edge of its
+ *        support.  An unreachable opposite tail contributes no probability and sets + 256 (zeta = -+zeta_max, r* = -+infinity): the
+ *        usual case for a rare allele.  For a reachable target solve K'(zeta) = target by Newton from zeta = 0 inside the bracket
+ *        [0, +-zeta_max]: zeta <- zeta - (K' - target) / K''; bisect when the step leaves the bracket (or is not a number); evaluate
+ *        there; the bracket is updated by the sign of K' - target; stop when |delta zeta| sqrt(V*) <= tol; at most max_iter evaluations
+ *        per tail, the reachability one included, code 1 otherwise.  The first code that is not 0 ends the marker.
+ *     6. Per-tail deviate at the root: w = sign(zeta) sqrt(2 (zeta target - K(zeta))), v = zeta sqrt(K''(zeta)), r* = w + ln(v / w) / w;
+ *        where |zeta| sqrt(V*) < 10^-4, r* = target / sqrt(V*).
+ *     7. Per-marker result.  stat_out[7 m ..] = (T, V*, z, zeta_up, r*_up, zeta_lo, r*_lo) and info_out[2 m ..] = (code, evaluations
+ *        of both tails).  Codes: 0 both tails solved; 1 max_iter reached; 2 degenerate; 3 observed-side target unreachable; 4 below the
+ *        cutoff; + 256 the opposite tail was unreachable.  The four values of 6 are NaN unless the code's low byte is 0.  The host makes
+ *        p_spa = Phi(-r*_up) + Phi(r*_lo) (scipy.special.ndtr): only this way do far tails keep their precision.
+ *
+ *     On the device (k_glmm_spa, csrc/eagle_glmm.hip) one wave owns one marker, four to a workgroup, no barrier between waves and no
+ *     atomics; X'D g is accumulated on v_mfma_f64_16x16x4_f64 with c padded to 16; a lane owns one individual per chunk of 64 and
+ *     recomputes G~_i at every evaluation (c FMAs) rather than holding it; wave reductions finish an evaluation.  X, mu, D and resid
+ *     are staged once per call as padded images and the genotype is read from the int8 row.  A marker's result depends on its row
+ *     and the per-call operands alone, so it does not depend on how markers fall into row windows or workgroups.
+ *
+ *     What is not claimed.  Agreement with the GMMAT, SAIGE or SPAtest programs is neither claimed nor tested, because none is
+ *     available: the tests hold the roots and deviates to 40-digit solutions of the same equations and the rule itself to full
+ *     enumeration of the 2^n outcomes at n = 18.  Bit equality with the numpy restatement is not claimed either: exp, log1p and the
+ *     order of the sums are not fixed by IEEE 754.  Not done: a .bed route, repeated measures, several devices, SAIGE's variance-ratio
+ *     shortcut (V here is exact), the fast SPA partial-normal split for non-carriers, sex chromosomes.
+ *
+ *     The file is read as eagle_logistic reads it: the resident image where it lies, else row windows from the sidecar, the text or a
+ *     VIEW alias's source; with a VIEW alias the operands have one entry per kept individual.  Single device: a multi-device context
+ *     works on its first device.  Argument errors (EAGLE_ERR_ARG: a NULL pointer (vara excepted), dims <= 0, n > 2^30 - 1, c outside
+ *     [1, 15], a mu outside (0, 1) or not finite, a non-finite X, resid or A entry, cutoff < 0 or NaN, tol not in (0, 1), max_iter
+ *     outside [1, 1000]) are decided before the context is used; with ctx == NULL their text is in eagle_open_error().
+ * ------------------------------------------------------------------------------------------- */
+int eagle_glmm_spa(eagle_ctx* ctx, const char* f_name_ascii_Mt, const long dims[2], const double* mu, const double* resid, const double* X,
+                   int c, const double* A, const double* vara_or_NULL, double cutoff, double tol, int max_iter, double max_memory_in_Gbytes,
+                   double* stat_out, int32_t* info_out);
+
 /* Replaces the R tail of .find_qtl:  tsq <- a^2/vara ; which(tsq == max(tsq, na.rm=TRUE))[1]
  *                                                E/R/find_qtl.R:71-83
  * Evaluated on the device on the a / vara of the LAST eagle_calculate_a_and_vara call of this ctx (still in
